@@ -10,13 +10,18 @@ With N > 1 ranks every rank decodes its own shard (weak scaling, no data-path co
 (BASELINE.json north_star); `decode_only_mpixel_per_s` / `gather_ms` split the two; `per_rank_consumers` is the same job consumed where it was decoded.
 --scaling strong --total-frames T fixes the job instead (BASELINE config 3: 1024 frames over the node).
 
-Besides the headline the N = 1 line reports what callers of the drop-in API see — api_concurrent: the reference crate's call sequence against the libjxl C ABI
+A plain run measures the headline alone: it synthesises the frames, sets the pipeline up, warms up, times the K steps and prints the line.
+--dump-outputs DIR also writes what the last timed step decoded (a seeded sample of its pixels and every row's sums, see dump_outputs).
+Everything else moves behind --full: the comparison of decoded frames with the CPU oracle, the CPU baseline, the realistic-bit-rate and
+cjxl-shaped workloads, the per-rank-consumer leg, the measured copy rate, and the extras below.
+
+With --full the N = 1 line also reports what callers of the drop-in API see — api_concurrent: the reference crate's call sequence against the libjxl C ABI
 from 1 / 8 / 64 host threads (tools/api_concurrent.cc, host bytes in, host pixels out; the shared per-device scheduler coalesces the callers); single_frame_ms:
 one 4K frame through decode_with (gradient LF tree, cjxl-shaped tree) and the reference's own criterion input bench.jxl; streaming_host_out: the pipeline with
 pinned host destinations beside the measured PCIe ceiling; one_pass_128 / pcie_inclusive: a cold batch of 128 frames; the 8K workloads of BASELINE configs 4 and 5
 (f32 HDR EPF 3; lossless Modular Squeeze u16) with the rooflines of their own kernels; step_end_ms / steady_state_ms_per_step; verified_vs_oracle.
 
-Contract: python bench.py --gpus N --steps K --warmup W  → rank 0 prints ONE JSON line.
+Contract: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]  → rank 0 prints ONE JSON line.
 """
 import argparse
 import json
@@ -350,6 +355,12 @@ class Run:
                     checked.append(f"rank{r}:{k}:{fi}")
         return ok, checked
 
+    def last_step_output(self, njobs):
+        """the pixels the caller holds after the last of njobs jobs, frames x H x W x channels: rank 0's gathered step at N > 1, else the last job's output buffer"""
+        if self.gathered is not None:
+            return self.gathered.flatten(0, 1)
+        return self.outs[(njobs - 1) % self.nout]
+
     def close(self):
         if self.ccomm:
             self.torch.cuda.synchronize()
@@ -358,6 +369,22 @@ class Run:
         self.p.close()
         self.outs = None; self.pinned = None; self.gathered = None
         self.torch.cuda.empty_cache()
+
+
+def dump_outputs(out, d, torch, np, samples=1 << 22, row_sum_bytes=32 << 20):
+    """Writes what the last timed step decoded (out: frames x H x W x channels on the device) to d, for an output-by-output comparison of two builds on
+    the same arguments (the inputs are seeded); about 30 MB at the default job:
+      pixels_sample.npy  float32 (n,)                 the samples at a fixed seeded set of n <= `samples` sorted positions of out, flattened
+      frame_sums.npy     float64 (frames, channels)    the exact sum of every channel of every frame
+      row_sums.npy       float64 (frames', H, channels) the exact sum of every row of every channel, for the first frames' frames that fit `row_sum_bytes`"""
+    os.makedirs(d, exist_ok=True)
+    f, h, _, c = out.shape
+    flat = out.reshape(-1)
+    idx = np.unique(np.random.default_rng(1000).integers(0, flat.numel(), size=min(samples, flat.numel())))
+    np.save(os.path.join(d, "pixels_sample.npy"), flat[torch.from_numpy(idx).to(out.device)].to(torch.float32).cpu().numpy())
+    rows = torch.stack([out[i].sum(dim=1, dtype=torch.float64) for i in range(f)])       # (frame by frame: no cast copy of the whole job)
+    np.save(os.path.join(d, "frame_sums.npy"), rows.sum(dim=1).cpu().numpy())
+    np.save(os.path.join(d, "row_sums.npy"), rows[:max(1, row_sum_bytes // (h * c * 8))].cpu().numpy())
 
 
 def _steady(e):
@@ -488,13 +515,16 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=int(os.environ.get("JXL_BENCH_BATCH", "256")), help="frames per GPU per step")
-    ap.add_argument("--distinct", type=int, default=int(os.environ.get("JXL_BENCH_DISTINCT", "0")), help="distinct synthetic frames per GPU (cycled to fill the jobs); default 256, 64 per GPU when N > 1 "
-                    "(the ranks of a node share its host cores for the synthesis: 4.6 s per frame)")
+    ap.add_argument("--distinct", type=int, default=int(os.environ.get("JXL_BENCH_DISTINCT", "0")), help="distinct synthetic frames per GPU (cycled to fill the jobs); default 32, 64 per GPU when N > 1 "
+                    "(synthesis takes 4.6 s of one host core per frame, inside the run's set-up; every frame of a job is parsed, uploaded and decoded on its own whether or not it repeats)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak", help="weak: --batch frames per GPU per step; strong: --total-frames per step over all GPUs")
     ap.add_argument("--total-frames", type=int, default=1024, help="frames per step of the whole job with --scaling strong (BASELINE config 3)")
-    ap.add_argument("--no-extras", action="store_true", help="skip api_concurrent / single_frame_ms / one_pass / streaming_host_out / the 8K workloads (N = 1 only anyway)")
-    ap.add_argument("--no-8k", action="store_true", help="skip the 8K workloads (BASELINE configs 4 and 5)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the comparison of decoded frames with the CPU oracle after the run")
+    ap.add_argument("--full", action="store_true", help="besides the headline: oracle comparison, CPU baseline, the realistic / cjxl-shaped workloads, per-rank consumers (N > 1), "
+                    "the measured copy rate and the extras (N = 1); the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step decoded to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip api_concurrent / single_frame_ms / one_pass / streaming_host_out / the 8K workloads (N = 1 only anyway)")
+    ap.add_argument("--no-8k", action="store_true", help="--full: skip the 8K workloads (BASELINE configs 4 and 5)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the comparison of decoded frames with the CPU oracle after the run")
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--epf", type=int, default=1)
@@ -515,34 +545,45 @@ def main():
     ap.add_argument("--parse-threads", type=int, default=int(os.environ.get("JXL_BENCH_PARSE_THREADS", "8")), help="host threads one job's frames are parsed on")
     ap.add_argument("--texture", type=float, default=5.0, help="strength (sRGB levels) of the texture of the realistic-bit-rate workload (0: skip it)")
     ap.add_argument("--realistic-distinct", type=int, default=64, help="distinct frames of the realistic-bit-rate workload")
-    ap.add_argument("--no-realistic", action="store_true", help="skip the second and third workload (textured frames, ~2 bpp; cjxl-shaped LF trees)")
+    ap.add_argument("--no-realistic", action="store_true", help="--full: skip the second and third workload (textured frames, ~2 bpp; cjxl-shaped LF trees)")
     ap.add_argument("--cjxl-distinct", type=int, default=32, help="distinct frames of the cjxl-shaped workload (textured frames whose LF-group streams use the MA-tree shape of a default-effort "
                     "cjxl encode: weighted predictor); 0: skip it")
     ap.add_argument("--main-tree-shape", type=int, default=0, help="experiments: LF tree shape of the headline workload's frames (1: the cjxl default-effort shape)")
     ap.add_argument("--main-texture", type=float, default=0.0, help="experiments: texture strength of the headline workload's frames")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     W, H = args.width, args.height
+    # the other workloads of --full take at most as many distinct frames as an explicit --distinct
+    other_distinct = args.distinct if args.distinct > 0 else 1 << 30
     if args.distinct <= 0:
-        args.distinct = 256 if world == 1 else 64
+        args.distinct = 32 if world == 1 else 64
     if world > 1:
         args.realistic_distinct = min(args.realistic_distinct, 16)
         os.environ.setdefault("JXL_BENCH_SYNTH_WORKERS", str(max(1, (os.cpu_count() or 1) // int(os.environ.get("LOCAL_WORLD_SIZE", str(world))))))
-    do_extras = world == 1 and not args.no_extras
+    do_extras = args.full and world == 1 and not args.no_extras
+    do_realistic = args.full and not args.no_realistic
+    B = args.batch
+    inner = 1                       # jobs per step
+    if args.scaling == "strong":
+        per_rank = max(1, args.total_frames // world)
+        B = min(args.batch, per_rank)
+        inner = max(1, per_rank // B)
+    if args.dump_outputs and inner > 1 and (world == 1 or args.no_gather):
+        raise SystemExit("--dump-outputs: this step is several jobs per GPU and nothing gathers them; the output ring keeps the last two jobs only")
 
     streams = make_streams(args.distinct, W, H, args.epf, seed0=1000 + 1000 * rank, texture=args.main_texture, tree_shape=args.main_tree_shape)
     # the same frames with photograph-like texture: ~2 bpp at distance 1 instead of 0.8 (second workload of the line, fewer distinct frames)
-    realistic_streams = make_streams(min(args.distinct, args.realistic_distinct), W, H, args.epf, seed0=1000 + 1000 * rank, texture=args.texture) if args.texture > 0 and not args.no_realistic else None
-    cjxl_streams = make_streams(min(args.distinct, args.cjxl_distinct), W, H, args.epf, seed0=1000 + 1000 * rank, texture=args.texture, tree_shape=1) if args.cjxl_distinct > 0 and not args.no_realistic else None
+    realistic_streams = make_streams(min(other_distinct, args.realistic_distinct), W, H, args.epf, seed0=1000 + 1000 * rank, texture=args.texture) if args.texture > 0 and do_realistic else None
+    cjxl_streams = make_streams(min(other_distinct, args.cjxl_distinct), W, H, args.epf, seed0=1000 + 1000 * rank, texture=args.texture, tree_shape=1) if args.cjxl_distinct > 0 and do_realistic else None
     hdr_streams = _pool_map(_make_8k_hdr, [6 + i for i in range(8)]) if do_extras and not args.no_8k else None
     mod_streams = _pool_map(_make_8k_modular, [5 + i for i in range(4)]) if do_extras and not args.no_8k else None
     ycbcr_streams = _pool_map(_make_ycbcr420, [700 + i for i in range(16)]) if do_extras and not args.no_8k else None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(streams, W, H)   # before any GPU runtime is initialised in this process (fork safety)
 
     # the pipeline keeps ~12 HIP streams busy at once (main, HF, LF side streams, copies); the runtime maps streams onto 4 hardware queues by default and kernels of
@@ -568,16 +609,9 @@ def main():
         else:
             dist.init_process_group(backend=backend)
 
-    B = args.batch
-    inner = 1                       # jobs per step
-    if args.scaling == "strong":
-        per_rank = max(1, args.total_frames // world)
-        B = min(args.batch, per_rank)
-        inner = max(1, per_rank // B)
-
-    def measure(streams=streams, texture=args.main_texture, tree_shape=args.main_tree_shape, consumer="gather", **kw):
+    def measure(streams=streams, texture=args.main_texture, tree_shape=args.main_tree_shape, consumer="gather", dump_dir=None, **kw):
         """one workload: the pipeline's batch objects are filled once (what constructing it costs: device arenas, pinned staging), W untimed warm-up steps, then exactly K timed
-        steps from an idle pipeline, bracketed by barrier + synchronize"""
+        steps from an idle pipeline, bracketed by barrier + synchronize; dump_dir: write what the last timed step decoded there"""
         steps, warmup = kw.pop("steps", args.steps), args.warmup
         r = Run(args, jx, torch, dist, streams, dev, local_rank, rank, world, kw.pop("B", B), inner, kw.pop("W", W), kw.pop("H", H), consumer=consumer, **kw)
         try:
@@ -602,7 +636,9 @@ def main():
                    "prepare_ms_per_job": p.info("prepare_us_total") / 1e3 / max(1, p.info("prepared_jobs")), "gather": r.consumer == "gather", "cpu_s": cpu_s, "checksum": int(r.checksum.item()),
                    "nonzeros": p.info("hf_nonzeros") // max(1, p.info("frames")), "lf_simt": [p.info(k) for k in ("lf_simt_frames", "lf_legacy_frames", "lf_simt_wp")],
                    "private_plane_jobs": p.info("private_plane_jobs"), "B": r.B, "steps": steps}
-            if not args.no_verify and rank == 0:
+            if dump_dir and rank == 0:
+                dump_outputs(r.last_step_output(steps * inner), dump_dir, torch, np)
+            if args.full and not args.no_verify and rank == 0:
                 res["verified"], res["verified_frames"] = r.verify(steps * inner, O, np, {"uint8": "u8", "uint16": "u16", "float32": "f32"}[np.dtype(r.dtype).name])
         finally:
             r.close()
@@ -610,11 +646,11 @@ def main():
         torch.cuda.empty_cache()
         return res
 
-    head = measure()
-    realistic = measure(realistic_streams, args.texture, 0) if args.texture > 0 and not args.no_realistic and realistic_streams else None
+    head = measure(dump_dir=args.dump_outputs)
+    realistic = measure(realistic_streams, args.texture, 0) if realistic_streams else None
     cjxl = measure(cjxl_streams, args.texture, 1) if cjxl_streams else None
     # N > 1: the same job with per-rank consumers beside the gather to rank 0 (7 peers x ~80 GB/s of pixels into one GPU's xGMI links bound the gather)
-    local_leg = measure(consumer="per_rank") if (world > 1 or args.per_rank_consumers) and not args.no_gather else None
+    local_leg = measure(consumer="per_rank") if ((world > 1 and args.full) or args.per_rank_consumers) and not args.no_gather else None
     if rank == 0:
         total_px = world * B * inner * W * H * args.steps
         rate = lambda r: total_px / r["elapsed"] / 1e6
@@ -698,7 +734,7 @@ def main():
         if world > 1:
             result["decode_only_mpixel_per_s"] = round(total_px / head["t_decode"] / 1e6, 2)     # until every rank's own decode work was done
             result["gather_ms"] = round((head["elapsed"] - head["t_decode"]) * 1e3, 2)             # what the pixel gather added after that
-        if world == 1:
+        if world == 1 and args.full:
             # practical HBM ceiling next to the spec peak: a device-to-device copy of 4 GiB, read + write counted
             a = torch.empty(1 << 30, dtype=torch.int32, device=dev); bcopy = torch.empty_like(a)
             bcopy.copy_(a); torch.cuda.synchronize()

@@ -1,6 +1,6 @@
 """GPU tests (-m gpu) of bench.py's own control flow: the N > 1 path (frame sharding, per-rank pipelines, chunked gather to rank 0,
 max-over-ranks timing) exercised with two ranks on ONE GPU over gloo — RCCL refuses two ranks per device, so this is a functional check, not
-a measurement — and the per-GPU share of BASELINE config 3 (1024 frames over 8 GPUs = 128 4K frames in one pass)."""
+a measurement —, a plain one-GPU run with --dump-outputs, and the per-GPU share of BASELINE config 3 (1024 frames over 8 GPUs = 128 4K frames in one pass)."""
 import json
 import os
 import subprocess
@@ -29,7 +29,7 @@ def test_two_ranks_share_one_gpu_and_gather(jx):
     port = 29600 + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--width", "512", "--height", "384", "--batch", "16", "--distinct", "6",
-           "--no-extras", "--no-cpu-baseline", "--no-realistic", "--in-flight", "4", "--lf-streams", "3", "--prepare-threads", "2", "--parse-threads", "2"]
+           "--full", "--no-extras", "--no-cpu-baseline", "--no-realistic", "--in-flight", "4", "--lf-streams", "3", "--prepare-threads", "2", "--parse-threads", "2"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -45,6 +45,30 @@ def test_two_ranks_share_one_gpu_and_gather(jx):
     pr = d["per_rank_consumers"]
     assert pr["value"] > 0 and pr["verified_vs_oracle"] is True and pr["checksum_of_checksums"] != 0
     assert d["host_cpu"]["cpu_s_per_frame"] > 0 and d["host_cpu"]["cores_busy"] > 0
+
+
+def test_plain_run_dumps_the_same_outputs_twice(jx, tmp_path):
+    """A plain one-GPU run is the headline alone; --dump-outputs writes the last step's pixels (seeded sample, exact row and frame sums) in float32 /
+    float64, and two runs with the same arguments write the same arrays."""
+    lines = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--width", "512", "--height", "384", "--batch", "16",
+               "--distinct", "6", "--in-flight", "4", "--lf-streams", "3", "--prepare-threads", "2", "--parse-threads", "2", "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append([json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")])
+    for ls in lines:
+        assert len(ls) == 1
+        d = ls[0]
+        assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "Mpixel/s"
+        assert "verified_vs_oracle" not in d and "cpu_baseline" not in d and "workload_realistic" not in d["config"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["frame_sums.npy", "pixels_sample.npy", "row_sums.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "frame_sums.npy").shape == (16, 3) and np.load(tmp_path / "a" / "row_sums.npy").shape == (16, 384, 3)
+    assert np.load(tmp_path / "a" / "frame_sums.npy").sum() == np.load(tmp_path / "a" / "row_sums.npy").sum() > 0
 
 
 def test_config3_per_gpu_share(jx):

@@ -881,6 +881,24 @@ int64_t Batch::Info(const std::string& name) const {
   if (name == "mod_group_lds_bytes") return prepared_ ? (int64_t)ModularGroupLdsBytes(cfg) : -1;
   if (name == "lf_simt_lanes") return lf_simt_.num_lanes;
   if (name == "lf_simt_wp") return lf_simt_.num_lanes ? lf_simt_.any_wp : 0;     // the SIMT launch is the weighted-predictor instantiation
+  // the kernels the last decode's LF / HF stage launched (kernels.h kHfVar* / kLfVar* bits) and the LDS sizes that chose them (bytes, after Prepare)
+  if (name == "hf_variant") return trace_.hf_variant;
+  if (name == "lf_variant") return trace_.lf_variant;
+  if (name == "lf_wide_bytes") return trace_.lf_wide_bytes;
+  if (name == "lf_wide_only") return trace_.lf_wide_only;
+  if (name == "ac_code_bytes") return prepared_ ? cfg.ac_code_bytes : -1;
+  if (name == "ac_code_bytes_compact") return prepared_ ? cfg.ac_code_bytes_compact : -1;
+  if (name == "mod_code_bytes") return prepared_ ? cfg.mod_code_bytes : -1;
+  if (name == "ac_cfg_uniform" || name == "mod_cfg_uniform") {   // every cluster of every AC / global-tree Modular code of the batch shares one hybrid-uint configuration
+    const bool ac = name == "ac_cfg_uniform";
+    auto uniform = [](const HostCode& c) { for (uint32_t v : c.cfg) if (v != c.cfg[0]) return false; return true; };
+    for (size_t i = 0; i < images_.size(); i++) {
+      const FramePlan& p = images_[i]->plan;
+      if (ac) { if (!p.modular) for (auto& code : p.ac_code) if (!uniform(code)) return 0; }
+      else if (p.has_global_tree && !uniform(p.tree_code)) return 0;
+    }
+    return 1;
+  }
   if (!images_.empty() && !images_[0]->plan.modular) {   // geometry / quantiser of the first frame (tests that restate a stage from its defining formula)
     const FramePlan& p = images_[0]->plan;
     if (name == "frame0_bw") return p.bw;
@@ -2236,7 +2254,7 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
     if (any_modchan_) LaunchModularGlobal(dframes_, n, cfg, stream_v);   // Modular frames; extra channels of VarDCT frames
     DebugSync("modular global", stream_v);
     cfg.lf_head_start = part == 1 || part == 5;   // front enqueued on its own: a pipelined caller, the HF stage of another batch is about to start
-    if (any_vardct_) LaunchLfDecode(dframes_, n, max_lf_groups_, cfg, stream_v, &lf_simt_);
+    if (any_vardct_) LaunchLfDecode(dframes_, n, max_lf_groups_, cfg, stream_v, &lf_simt_, &trace_);
     cfg.lf_wide_once = 0;
     DebugSync("LF decode", stream_v);
     CheckLaunches("LF stage");
@@ -2285,7 +2303,7 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
     ClearCoefficientsBeforeHf(stream_v);
     rec(split ? 7 : 2);
     // (progressive flush at the kDC step: no AC group is decoded — the planes stay zero, the IDCT sees the LF part only)
-    if (!cfg.skip_hf) LaunchHfDecode(dframes_, n, max_groups_, cfg, stream_v);
+    if (!cfg.skip_hf) LaunchHfDecode(dframes_, n, max_groups_, cfg, stream_v, &trace_);
     DebugSync("HF decode", stream_v);
     if (any_modchan_) EnqueueModularTail(stream_v);   // (the PassGroup Modular parts start where the HF streams ended)
     LaunchZeroFailedCoefficients(dframes_, n, stream_v);   // (frames that failed up to here are skipped by the IDCT kernels: their planes are zeroed now)

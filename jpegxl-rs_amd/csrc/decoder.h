@@ -244,6 +244,7 @@ class Batch {
   int max_lf_groups_ = 0, max_groups_ = 0, max_w_ = 0, max_h_ = 0, max_bw_ = 0, max_bh_ = 0, max_epf_ = 0;
   bool any_gab_ = false, any_vardct_ = false, any_modular_ = false;
   FilterPlan fplan_;
+  LaunchTrace trace_;             // the entropy-decode kernels the last LF / HF launch took (Info: hf_variant, lf_variant, lf_wide_bytes, lf_wide_only)
   LfSimtPlan lf_simt_;            // SIMT LF decode: device descriptors of the eligible frames' LF-group streams (cfg.lane_stride_lf < 64)
   struct ModFinish { int frame; vec<int> planes; };  // host-side channel lists for modular frames
   vec<vec<size_t>> mod_plane_offsets_;

@@ -954,7 +954,8 @@ void JxlHipBatchSetOption(JxlHipBatch* h, const char* name, int value) {
   else if (n == "debug_stop_after" && value >= 0 && value <= 5) h->b->cfg.debug_stop_after = value;
   else if (n == "keep_orientation") h->keep_orientation = value != 0;   // applies to outputs set afterwards
   else if (n == "hf_block_threads" && value >= 64 && value <= 1024 && value % 64 == 0) h->b->cfg.hf_block_threads = value;
-  else if (n == "lds_code_budget" && value >= 0 && value <= 128 * 1024) h->b->cfg.lds_code_budget = value;
+  // (rounded down to 16 bytes: the kernels put regions of their own behind the staged tables — HfDecodeSimtKernel its lane slots — that must stay aligned)
+  else if (n == "lds_code_budget" && value >= 0 && value <= 128 * 1024) h->b->cfg.lds_code_budget = value & ~15;
   else if (n == "lf_force_big" && value >= -1 && value <= 2) h->b->cfg.lf_force_big = value;
   else if (n == "hf_lanes_per_wave" && value >= 0 && value <= 64) h->b->cfg.hf_lanes_per_wave = value;   // SIMT HF stage: group streams per wavefront (1: the wave-wide kernel where it applies); 0: the throughput packing
 }
@@ -1135,10 +1136,14 @@ int JxlHipDebugDescribe(const uint8_t* data, size_t size, char* out, size_t cap)
                  (unsigned long long)p.flags);
         s += line;
         for (int k = 0; k < 17; k++) if (p.qspec[k].mode != 0) { snprintf(line, sizeof line, "  qtable kind=%d mode=%u raw_den=%g\n", k, p.qspec[k].mode, p.qspec[k].raw_den); s += line; }
-        snprintf(line, sizeof line, "  lf_code contexts=%u clusters=%u log_alpha=%u alias_bytes=%zu\n", p.tree_code.num_ctx, p.tree_code.num_clusters, p.tree_code.log_alpha, p.tree_code.alias.size() * 8);
+        // uniform_cfg: every cluster shares one hybrid-uint configuration (the kernels' FastCode::cfg_uniform)
+        auto uniform = [](const HostCode& c) { for (uint32_t v : c.cfg) if (v != c.cfg[0]) return 0; return 1; };
+        snprintf(line, sizeof line, "  lf_code contexts=%u clusters=%u log_alpha=%u alias_bytes=%zu uniform_cfg=%d\n", p.tree_code.num_ctx, p.tree_code.num_clusters, p.tree_code.log_alpha,
+                 p.tree_code.alias.size() * 8, uniform(p.tree_code));
         s += line;
         for (size_t ps = 0; ps < p.ac_code.size(); ps++) {
-          snprintf(line, sizeof line, "  ac_code pass=%zu contexts=%u clusters=%u log_alpha=%u alias_bytes=%zu\n", ps, p.ac_code[ps].num_ctx, p.ac_code[ps].num_clusters, p.ac_code[ps].log_alpha, p.ac_code[ps].alias.size() * 8);
+          snprintf(line, sizeof line, "  ac_code pass=%zu contexts=%u clusters=%u log_alpha=%u alias_bytes=%zu uniform_cfg=%d\n", ps, p.ac_code[ps].num_ctx, p.ac_code[ps].num_clusters,
+                   p.ac_code[ps].log_alpha, p.ac_code[ps].alias.size() * 8, uniform(p.ac_code[ps]));
           s += line;
         }
       }

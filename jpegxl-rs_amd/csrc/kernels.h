@@ -190,10 +190,24 @@ struct LfSimtPlan {
   int any_wp = 0;              // some SIMT stream keeps weighted-predictor state (the kernel's WP instantiation; LfDecodeKernel follows for the streams it hands back)
 };
 
-// VarDCT stages.  max_* are maxima over the batch (grid sizing); nframes = frames in batch.
-void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, const LaunchCfg& cfg, void* stream, const LfSimtPlan* simt = nullptr);
+// Which entropy-decode kernels the last LF / HF launch took (Batch::Info hf_variant, lf_variant, lf_wide_bytes, lf_wide_only): bit masks, one bit per kernel
+// instantiation — tests assert the path they meant to reach was the one that ran.
+enum : int {
+  kHfVarWave = 1, kHfVarSimtPlain = 2, kHfVarSimtAllLds = 4, kHfVarSimtGlobal = 8, kHfVarLaneStride = 16, kHfVarPrefix = 32,   // HfDecodeWaveKernel, HfDecodeSimtKernel
+  // <true,false,false> / <true,true,true> / <false,true,true>, HfDecodeKernel (lane-stride batches), HfDecodeKernel beside the SIMT kernel (prefix-coded / LZ77 AC codes)
+  kLfVarSimtLean = 1, kLfVarSimtGen = 2, kLfVarSimtWp = 4, kLfVarSimtWpQuad = 8, kLfVarBig = 16, kLfVarSmall = 32,   // LfDecodeSimtKernel<false,false> / <false,true> /
+  // <true,true> / <true,true,true>, LfDecodeKernel<true> (four groups per workgroup, register-capped) / <false> (one group per wavefront, or four uncapped)
+};
+struct LaunchTrace {
+  int hf_variant = 0, lf_variant = 0;
+  uint32_t lf_wide_bytes = 0;   // LDS bytes of the wave-wide decoder's copy of the Modular code's alias tables (0: the lane-0 serial path without it)
+  int lf_wide_only = 0;         // the plain layout was left out (LdAliasAt puts entries together from the wide one)
+};
+
+// VarDCT stages.  max_* are maxima over the batch (grid sizing); nframes = frames in batch.  trace: filled with the kernels launched (nullptr: not recorded).
+void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, const LaunchCfg& cfg, void* stream, const LfSimtPlan* simt = nullptr, LaunchTrace* trace = nullptr);
 void LaunchLfPost(const FrameDev* frames, int nframes, int max_bw, int max_bh, int max_groups, void* stream);
-void LaunchHfDecode(const FrameDev* frames, int nframes, int max_groups, const LaunchCfg& cfg, void* stream);
+void LaunchHfDecode(const FrameDev* frames, int nframes, int max_groups, const LaunchCfg& cfg, void* stream, LaunchTrace* trace = nullptr);
 void LaunchZeroFailedCoefficients(const FrameDev* frames, int nframes, void* stream);   // behind the HF stage: a failed frame's coefficient planes go back to zero
 void LaunchIdct(const FrameDev* frames, int nframes, int max_groups, int max_bw, int max_bh, const LaunchCfg& cfg, void* stream);
 struct FilterPlan {

@@ -6059,7 +6059,10 @@ static const uint32_t* WpDivTable() {
   }
   return table[dev];
 }
-void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, const LaunchCfg& cfg, void* stream, const LfSimtPlan* simt) {
+void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, const LaunchCfg& cfg, void* stream, const LfSimtPlan* simt, LaunchTrace* trace) {
+  LaunchTrace tr;
+  if (!trace) trace = &tr;
+  trace->lf_variant = 0; trace->lf_wide_bytes = 0; trace->lf_wide_only = 0;
   static const bool time_it = getenv("JXL_HIP_TIME_LF") != nullptr;     // experiments: blocking per-kernel times on stderr
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   if (time_it) { for (auto& e : ev) (void)hipEventCreate(&e); (void)hipEventRecord(ev[0], (hipStream_t)stream); }
@@ -6103,9 +6106,10 @@ void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, cons
       const uint32_t lpq = std::min(16u, lpw);
       const int nwq = DivUp((int)simt->num_lanes, (int)lpq);
       hipLaunchKernelGGL((LfDecodeSimtKernel<true, true, true>), dim3(DivUp(nwq, wpb)), block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpq, lf_flags, wp_div);
-    } else if (simt->any_wp) hipLaunchKernelGGL((LfDecodeSimtKernel<true, true>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div);
-    else if (simt->any_general) hipLaunchKernelGGL((LfDecodeSimtKernel<false, true>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div);
-    else hipLaunchKernelGGL((LfDecodeSimtKernel<false, false>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div);
+      trace->lf_variant |= kLfVarSimtWpQuad;
+    } else if (simt->any_wp) { hipLaunchKernelGGL((LfDecodeSimtKernel<true, true>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div); trace->lf_variant |= kLfVarSimtWp; }
+    else if (simt->any_general) { hipLaunchKernelGGL((LfDecodeSimtKernel<false, true>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div); trace->lf_variant |= kLfVarSimtGen; }
+    else { hipLaunchKernelGGL((LfDecodeSimtKernel<false, false>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div); trace->lf_variant |= kLfVarSimtLean; }
     if (!simt->any_legacy && !simt->any_wp) { place(); return; }
     simt_mode = simt->any_wp ? 2 : 0;         // the weighted-predictor lanes may hand streams back: LfDecodeKernel follows for those (and for the legacy frames)
   }
@@ -6123,6 +6127,7 @@ void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, cons
   // difference between one and three IDCT / filter workgroups next to them.  JXL_HIP_LF_WIDE_BOTH: both layouts, as the launches that also serve SIMT hand-backs keep)
   static const bool wide_both = getenv("JXL_HIP_LF_WIDE_BOTH") != nullptr;
   const bool wide_only = wide && wide_bytes && !wide_both;
+  trace->lf_wide_bytes = wide_bytes; trace->lf_wide_only = wide_only ? 1 : 0;
   const uint32_t lds_tables = kLfDecWaves * kWaveLds + tree_cap * 16 + (redo_only_launch || wide_only ? 0u : (uint32_t)std::min(cfg.lds_code_budget, cfg.mod_code_bytes)) + wide_bytes;
   // trees with the weighted predictor: its state rows (channels up to 256 wide — all but the block-info rows) in LDS, one slot per wavefront
   const uint32_t wp_base = cfg.any_wp ? (lds_tables + 15) & ~15u : 0u;
@@ -6147,8 +6152,10 @@ void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, cons
   }
   if (big) {      // (the register cap — 170 VGPRs, with spills — leaves room for the wavefronts of other stages; for the first launches of a cold pipeline the uncapped instantiation measured the same: profiles/r05_notes.md)
     hipLaunchKernelGGL(LfDecodeKernel<true>, dim3(DivUp(max_lf_groups, (int)gpb), nframes), dim3(64 * kLfDecWaves), lds_bytes, (hipStream_t)stream, frames, gpb, tree_cap, lds_tables, simt_mode, wp_base);
+    trace->lf_variant |= kLfVarBig;
   } else {
     hipLaunchKernelGGL(LfDecodeKernel<false>, dim3(DivUp(max_lf_groups, (int)gpb), nframes), dim3(64 * kLfDecWaves), lds_bytes, (hipStream_t)stream, frames, gpb, tree_cap, lds_tables, simt_mode, wp_base);
+    trace->lf_variant |= kLfVarSmall;
   }
   place();
 }
@@ -6174,7 +6181,10 @@ __global__ __launch_bounds__(256) void ZeroFailedCoefKernel(const FrameDev* __re
 void LaunchZeroFailedCoefficients(const FrameDev* frames, int nframes, void* stream) {
   if (nframes > 0) hipLaunchKernelGGL(ZeroFailedCoefKernel, dim3(32, nframes), dim3(256), 0, (hipStream_t)stream, frames);
 }
-void LaunchHfDecode(const FrameDev* frames, int nframes, int max_groups, const LaunchCfg& cfg, void* stream) {
+void LaunchHfDecode(const FrameDev* frames, int nframes, int max_groups, const LaunchCfg& cfg, void* stream, LaunchTrace* trace) {
+  LaunchTrace tr;
+  if (!trace) trace = &tr;
+  trace->hf_variant = 0;
   // latency mode (one stream per wavefront asked for) with plain frames whose AC code fits the LDS in the wide layout: the wave-wide kernel
   static const bool no_wave_hf = getenv("JXL_HIP_NO_WAVE_HF") != nullptr;
   if (!no_wave_hf && cfg.lane_stride_hf == 1 && cfg.hf_lanes_per_wave == 1 && !cfg.any_subsampled && !cfg.any_multipass && !cfg.any_prefix_ac && !cfg.skip_hf && cfg.max_passes == 0) {
@@ -6184,6 +6194,7 @@ void LaunchHfDecode(const FrameDev* frames, int nframes, int max_groups, const L
       static bool attr = false;
       if (!attr) { SetMaxDynamicLds((const void*)HfDecodeWaveKernel, 160 * 1024 - 2048, "HfDecodeWaveKernel"); attr = true; }
       hipLaunchKernelGGL(HfDecodeWaveKernel, dim3(DivUp(max_groups, (int)kHwWaves), nframes), dim3(64 * kHwWaves), lds, (hipStream_t)stream, frames, lds);
+      trace->hf_variant = kHfVarWave;
       return;
     }
   }
@@ -6235,10 +6246,12 @@ void LaunchHfDecode(const FrameDev* frames, int nframes, int max_groups, const L
     if (plain) hipLaunchKernelGGL((HfDecodeSimtKernel<true, false, false>), grid, dim3(threads), lds, (hipStream_t)stream, frames, lds, lanes, lpw, sync, epoch, hf_prio);
     else if (all_lds) hipLaunchKernelGGL((HfDecodeSimtKernel<true, true, true>), grid, dim3(threads), lds, (hipStream_t)stream, frames, lds, lanes, lpw, sync, epoch, hf_prio);
     else hipLaunchKernelGGL((HfDecodeSimtKernel<false, true, true>), grid, dim3(threads), lds, (hipStream_t)stream, frames, lds, lanes, lpw, sync, epoch, hf_prio);
+    trace->hf_variant = plain ? kHfVarSimtPlain : all_lds ? kHfVarSimtAllLds : kHfVarSimtGlobal;
     if (cfg.any_prefix_ac) {   // frames with a prefix-coded AC stream: one group stream per wavefront lane 0, tables in global memory
       static bool attr2 = false;
       if (!attr2) { SetMaxDynamicLds((const void*)HfDecodeKernel, 160 * 1024 - 2048, "HfDecodeKernel"); attr2 = true; }
       hipLaunchKernelGGL(HfDecodeKernel, dim3(DivUp(max_groups, 512 / 64), nframes), dim3(512), 128, (hipStream_t)stream, frames, 64, 128u, 1);
+      trace->hf_variant |= kHfVarPrefix;
     }
     return;
   }
@@ -6249,6 +6262,7 @@ void LaunchHfDecode(const FrameDev* frames, int nframes, int max_groups, const L
   if (!attr_set) { SetMaxDynamicLds((const void*)HfDecodeKernel, 160 * 1024 - 2048, "HfDecodeKernel"); attr_set = true; }
   dim3 grid(DivUp(max_groups, per_block), nframes);
   hipLaunchKernelGGL(HfDecodeKernel, grid, dim3(threads), lds_bytes, (hipStream_t)stream, frames, cfg.lane_stride_hf, lds_bytes, 0);
+  trace->hf_variant = kHfVarLaneStride;
 }
 // JXL_HIP_DEBUG_SYNC: names the launch that the runtime rejected (a rejected launch leaves an error code behind that the next runtime call of the process would report)
 static void DebugLaunch(const char* what) {

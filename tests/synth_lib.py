@@ -325,6 +325,28 @@ def set_lf_tree_shape(shape=0):
     lib().jxlsynth_set_lf_tree_shape(int(shape))
 
 
+# hybrid-uint configurations (split_exponent, msb_in_token, lsb_in_token) a real encoder may give its clusters: split 0, split = log_alpha (-1: msb and lsb
+# are not written), lsb_in_token >= 1, msb_in_token = 0, and the synthesiser's own {4, 2, 0}
+MIXED_UINT_CONFIGS = ((0, 0, 0), (-1, 0, 0), (4, 1, 1), (3, 0, 0), (5, 2, 1), (4, 2, 0), (2, 1, 1), (1, 0, 1), (4, 0, 2))
+
+
+def set_code_shape(min_clusters=0, min_log_alpha=0, uint_configs=None, which="both", max_clusters=0, seed=0):
+    """Shape of the entropy codes written from now on (in this thread): which = "ac" (AC coefficient codes of VarDCT frames), "lf" (the global-tree Modular
+    codes: LF coefficients / HF metadata of VarDCT frames, Modular frames, encode_modular_free) or "both".
+    min_clusters: split until that many clusters (at most one per non-empty context, 256); max_clusters > 0: at most that many;
+    min_log_alpha: log_alpha = max(computed, this), at most 8;
+    uint_configs: None = the synthesiser's one configuration, "mixed" = MIXED_UINT_CONFIGS, or a list of (split, msb, lsb) — every cluster takes one, picked
+    from `seed` (a one-element list: a uniform code under that configuration).  Called without arguments: the synthesiser's own shape again."""
+    cfgs = list(MIXED_UINT_CONFIGS if uint_configs == "mixed" else (uint_configs or ()))
+    flat = [int(v) for c in cfgs for v in c]
+    for split, msb, lsb in cfgs:
+        assert split == -1 or (0 <= split <= 8 and msb >= 0 and lsb >= 0 and msb + lsb <= split), (split, msb, lsb)
+    L = lib()
+    L.jxlsynth_set_code_shape.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_uint32]
+    arr = (C.c_int32 * max(1, len(flat)))(*flat)
+    L.jxlsynth_set_code_shape({"ac": 1, "lf": 2, "both": 3}[which], int(min_clusters), int(max_clusters), int(min_log_alpha), arr, len(cfgs), int(seed))
+
+
 def set_prev_channel_props(on=False):
     """VarDCT frames written from now on (this thread): the MA tree of their LF-group streams also splits on previous-channel properties."""
     lib().jxlsynth_set_prev_channel_props(1 if on else 0)

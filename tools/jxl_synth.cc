@@ -1252,7 +1252,7 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
   }
   { std::vector<const std::vector<Token>*> s; for (auto& d : lgd) { s.push_back(&d.lf_tok); s.push_back(&d.meta_tok); }
     s.push_back(&alpha_global_tok); for (auto& t : alpha_tok) s.push_back(&t); for (auto& t : alpha_lf_tok) s.push_back(&t);
-    BuildEntropyCoder(s, gt.num_leaves + (lz77_lf ? 1 : 0), UintConfig{4, 2, 0}, 32, mod_code);
+    BuildEntropyCoder(s, gt.num_leaves + (lz77_lf ? 1 : 0), UintConfig{4, 2, 0}, 32, mod_code, &LfCodeShape());
     if (lz77_lf) { mod_code.lz77 = true; mod_code.lz_min_symbol = 224; mod_code.lz_min_length = 3; mod_code.lz_len_cfg = UintConfig{3, 0, 0}; } }
   const bool lz77_ac = UseLz77Ac();
   const int npresets = std::max(1, std::min(HfPresets(), ngroups));
@@ -1265,7 +1265,7 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
       for (int g = 0; g < ngroups; g++) ApplyLz77(ac_tok_all[(size_t)ps * ngroups + g], (uint32_t)(495 * nctx * npresets), proto, 0, /*special=*/false);
     }
     std::vector<const std::vector<Token>*> s; for (int g = 0; g < ngroups; g++) s.push_back(&ac_tok_all[(size_t)ps * ngroups + g]);
-    BuildEntropyCoder(s, 495 * nctx * npresets + (lz77_ac ? 1 : 0), UintConfig{4, 2, 0}, 96, ac_codes[ps]);
+    BuildEntropyCoder(s, 495 * nctx * npresets + (lz77_ac ? 1 : 0), UintConfig{4, 2, 0}, 96, ac_codes[ps], &AcCodeShape());
     if (lz77_ac) { ac_codes[ps].lz77 = true; ac_codes[ps].lz_min_symbol = 224; ac_codes[ps].lz_min_length = 3; ac_codes[ps].lz_len_cfg = UintConfig{3, 0, 0}; }
   }
   // --- sections
@@ -1544,7 +1544,7 @@ static std::vector<uint8_t> EncodeModular(const int32_t* const* planes, int ncha
   }
   EntropyCoder tree_code, code;
   { std::vector<const std::vector<Token>*> s{&tree_tokens}; BuildEntropyCoder(s, 6, UintConfig{4, 2, 0}, 6, tree_code); }
-  { std::vector<const std::vector<Token>*> s{&global_tok}; for (auto& g : lftok) s.push_back(&g); for (auto& g : gtok) s.push_back(&g); BuildEntropyCoder(s, t.num_leaves, UintConfig{4, 2, 0}, 64, code); }
+  { std::vector<const std::vector<Token>*> s{&global_tok}; for (auto& g : lftok) s.push_back(&g); for (auto& g : gtok) s.push_back(&g); BuildEntropyCoder(s, t.num_leaves, UintConfig{4, 2, 0}, 64, code, &LfCodeShape()); }
   std::vector<BitWriter> sections;
   {
     BitWriter s;
@@ -1633,6 +1633,15 @@ void jxlsynth_set_custom_filters(int on) { synth::CustomFilters() = on != 0; }
 void jxlsynth_set_modular_group_shift(int shift) { synth::ModularGroupShift() = shift < 0 || shift > 3 ? 1 : shift; }
 void jxlsynth_set_prev_channel_props(int on) { synth::UsePrevChannelProps() = on != 0; }
 void jxlsynth_set_lf_tree_shape(int shape) { synth::LfTreeShape() = shape; }
+// entropy-code shape of the codes written from now on in this thread (synth::CodeShape): which bit 0 = the AC codes, bit 1 = the global-tree Modular codes;
+// cfgs: ncfg triples {split_exponent (-1: = log_alpha), msb_in_token, lsb_in_token}.  Zeros / ncfg 0: the synthesiser's own shape again
+void jxlsynth_set_code_shape(int which, int min_clusters, int max_clusters, int min_log_alpha, const int32_t* cfgs, int ncfg, uint32_t seed) {
+  synth::CodeShape cs;
+  cs.min_clusters = min_clusters; cs.max_clusters = max_clusters; cs.min_log_alpha = std::min(8, min_log_alpha); cs.seed = seed;
+  for (int i = 0; i < ncfg; i++) cs.cfgs.push_back(synth::UintConfig{cfgs[3 * i], cfgs[3 * i + 1], cfgs[3 * i + 2]});
+  if (which & 1) synth::AcCodeShape() = cs;
+  if (which & 2) synth::LfCodeShape() = cs;
+}
 // rgba == NULL: the extra channel is alpha again
 void jxlsynth_set_spot(const float* rgba) { synth::g_spot_set = rgba != nullptr; if (rgba) for (int i = 0; i < 4; i++) synth::g_spot[i] = rgba[i]; }
 // white_point < 0 clears the override

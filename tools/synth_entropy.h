@@ -287,6 +287,19 @@ struct EntropyCoder {
   UintConfig lz_len_cfg{4, 0, 0};
 };
 
+// Shape overrides of the entropy codes written from now on in this thread (tests: codes shaped like a real encoder's — more clusters, larger alias
+// tables, a hybrid-uint configuration per cluster — instead of this synthesiser's one narrow shape).  The defaults change nothing.
+struct CodeShape {
+  int min_clusters = 0;            // keep splitting until this many clusters (at most one per non-empty context, 256), whatever the cost gain
+  int max_clusters = 0;            // > 0: at most this many clusters instead of the caller's limit
+  int min_log_alpha = 0;           // log_alpha = max(computed, this), at most 8
+  std::vector<UintConfig> cfgs;    // non-empty: every cluster takes one of these (split_exponent -1: = log_alpha), picked from `seed`, and its histogram is
+                                   // counted again under it; a cluster whose tokens do not fit one takes the caller's configuration
+  uint32_t seed = 0;
+};
+inline CodeShape& AcCodeShape() { static thread_local CodeShape v; return v; }   // AC coefficient codes of VarDCT frames
+inline CodeShape& LfCodeShape() { static thread_local CodeShape v; return v; }   // global-tree Modular codes: LF / HF metadata of VarDCT frames, Modular frames
+
 inline void MakePrefixCodes(EntropyCoder& ec);
 inline double HistoCost(const std::vector<uint32_t>& h, uint64_t total) {
   if (total == 0) return 0;
@@ -296,9 +309,14 @@ inline double HistoCost(const std::vector<uint32_t>& h, uint64_t total) {
 }
 
 // Builds an entropy code from per-context token statistics: clusters contexts greedily (<= max_clusters) and
-// normalises histograms.  tokens: all tokens that will be coded with this code.
+// normalises histograms.  tokens: all tokens that will be coded with this code.  shape: overrides (CodeShape), nullptr = none.
 inline void BuildEntropyCoder(const std::vector<const std::vector<Token>*>& streams, int num_ctx, const UintConfig& uc,
-                              int max_clusters, EntropyCoder& ec) {
+                              int max_clusters, EntropyCoder& ec, const CodeShape* shape = nullptr) {
+  const CodeShape no_shape;
+  const CodeShape& sh = shape ? *shape : no_shape;
+  const int want_clusters = std::min(256, sh.min_clusters);
+  if (sh.max_clusters > 0) max_clusters = std::min(256, sh.max_clusters);
+  max_clusters = std::max(max_clusters, want_clusters);
   ec.num_ctx = num_ctx;
   ec.log_alpha = 8;
   std::vector<std::vector<uint32_t>> h(num_ctx);
@@ -337,9 +355,10 @@ inline void BuildEntropyCoder(const std::vector<const std::vector<Token>*>& stre
     std::vector<double> best(num_ctx, 0);
     for (int i : nonempty) best[i] = i == seed ? 0 : dist_to(i, 0);
     while ((int)ch.size() < max_clusters) {
-      int far = -1; double fd = 0;
+      const bool forced = (int)ch.size() < want_clusters;     // (CodeShape::min_clusters: the farthest context even when it gains nothing)
+      int far = -1; double fd = forced ? -1e300 : 0;
       for (int i : nonempty) if (assign[i] < 0 && best[i] > fd) { fd = best[i]; far = i; }
-      if (far < 0 || fd < 16.0) break;
+      if (far < 0 || (!forced && fd < 16.0)) break;
       ch.push_back(h[far]); ctot.push_back(tot[far]); assign[far] = (int)ch.size() - 1; best[far] = 0;
       int cl = (int)ch.size() - 1;
       for (int i : nonempty) if (assign[i] < 0) best[i] = std::min(best[i], dist_to(i, cl));
@@ -373,7 +392,53 @@ inline void BuildEntropyCoder(const std::vector<const std::vector<Token>*>& stre
   {  // alias-table size like an encoder would pick it: smallest power of two holding the largest alphabet (>= 32)
     size_t max_alpha = 1;
     for (auto& hh : ch) { size_t n = hh.size(); while (n > 0 && hh[n - 1] == 0) n--; max_alpha = std::max(max_alpha, n); }
-    ec.log_alpha = std::min(8, std::max(5, CeilLog2((uint32_t)max_alpha)));
+    ec.log_alpha = std::min(8, std::max(std::max(5, sh.min_log_alpha), CeilLog2((uint32_t)max_alpha)));
+  }
+  if (!sh.cfgs.empty()) {
+    // a hybrid-uint configuration per cluster: the smallest log_alpha (>= the one asked for) at which every cluster finds one — the first of the list, from a
+    // seeded start, whose re-counted alphabet fits 2^log_alpha and whose literal tokens stay below 224 (where LZ77 length symbols start) — then its histogram
+    const size_t ncl = ch.size();
+    std::vector<std::vector<const Token*>> per(ncl);
+    for (auto* ts : streams) for (const Token& t : *ts) per[ec.ctx_map[t.ctx]].push_back(&t);
+    auto recount = [&](const UintConfig& c, size_t cl, std::vector<uint32_t>& out) {
+      out.clear();
+      for (const Token* t : per[cl]) {
+        uint32_t tok, nb, bits;
+        TokenSymbol(c, *t, &tok, &nb, &bits);
+        if (!t->raw && tok >= 224) return false;
+        if (out.size() <= tok) out.resize(tok + 1, 0);
+        out[tok]++;
+      }
+      return true;
+    };
+    std::vector<UintConfig> pick(ncl);
+    std::vector<std::vector<uint32_t>> hist(ncl);
+    int L = std::min(8, std::max(5, sh.min_log_alpha));
+    for (;; L++) {
+      bool all = true;
+      for (size_t cl = 0; cl < ncl && all; cl++) {
+        uint32_t x = (sh.seed + 1) * 0x9E3779B1u ^ (uint32_t)(cl + 1) * 0x85EBCA77u;
+        x ^= x >> 15; x *= 0x2C1B3C6Du; x ^= x >> 12;
+        const size_t start = x % sh.cfgs.size();
+        bool found = false;
+        for (size_t k = 0; k <= sh.cfgs.size() && !found; k++) {
+          UintConfig c = k < sh.cfgs.size() ? sh.cfgs[(start + k) % sh.cfgs.size()] : uc;
+          if (c.split_exponent < 0) c = UintConfig{L, 0, 0};
+          if (c.split_exponent > L || c.msb < 0 || c.lsb < 0 || c.msb + c.lsb > c.split_exponent) continue;
+          if (!recount(c, cl, hist[cl])) continue;
+          size_t n = hist[cl].size();
+          while (n > 0 && hist[cl][n - 1] == 0) n--;
+          if (n > (1u << L)) continue;
+          pick[cl] = c; found = true;
+        }
+        all = found;
+      }
+      if (all) break;
+      if (L == 8) throw std::runtime_error("code shape: no hybrid-uint configuration fits a cluster");
+    }
+    ec.log_alpha = L;
+    ec.cfg = pick;
+    ch = hist;
   }
   for (size_t c = 0; c < ch.size(); c++) {
     if (ch[c].size() > 256) throw std::runtime_error("ANS alphabet > 256");

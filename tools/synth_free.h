@@ -242,9 +242,9 @@ static std::vector<uint8_t> EncodeModularFree(const FreeParams& fp) {
     }, s.tok);
     s.present = true;
   }
-  // entropy codes: one cluster each; the global code covers every stream that uses the global tree
+  // entropy codes: one cluster each (unless LfCodeShape asks for more); the global code covers every stream that uses the global tree
   auto make_code = [&](const std::vector<const std::vector<Token>*>& ss, int leaves, EntropyCoder& ec) {
-    BuildEntropyCoder(ss, leaves + (fp.lz77 ? 1 : 0), UintConfig{4, 1, 0}, 1, ec);
+    BuildEntropyCoder(ss, leaves + (fp.lz77 ? 1 : 0), UintConfig{4, 1, 0}, 1, ec, &LfCodeShape());
     ec.lz77 = proto.lz77; ec.lz_min_symbol = proto.lz_min_symbol; ec.lz_min_length = proto.lz_min_length; ec.lz_len_cfg = proto.lz_len_cfg;
   };
   auto write_tree_and_code = [&](BitWriter& s, const GTree& t, const std::vector<int>& bfs, const EntropyCoder& code) {

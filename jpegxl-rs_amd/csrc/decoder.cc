@@ -596,11 +596,9 @@ int Batch::Append(ParsedImage&& im) {
 // what the device path cannot take of a frame that parsed (thrown as "unsupported: ...")
 static void CheckFrameSupported(const FramePlan& p, const ImageHeader& ih) {
   if (!p.modular) {
-    // squeezed extra channels (what cjxl does to a progressive or lossy alpha of an RGBA picture): the sub-channels squeezed by >= 3 ride in the LfGroup sections — the LF
-    // kernel decodes them between the LF coefficients and the HF metadata —, the others in the PassGroup sections of ONE pass (ModularGroupFastKernel reads them behind that
-    // pass's coefficients); downsampling entries that spread them over several passes of a VarDCT frame are not handled
-    for (auto& t : p.gtransforms) if (t.id == 2 && p.num_passes > 1 && !(p.pass_min_shift[p.mod_pass] <= 0 && p.pass_max_shift[p.mod_pass] >= 2))
-      throw ParseError("unsupported: squeezed extra channels of a VarDCT frame spread over several passes", true);
+    // (squeezed extra channels, what cjxl does to a progressive or lossy alpha of an RGBA picture, are taken: the sub-channels squeezed by >= 3 ride in the LfGroup
+    // sections — the LF kernel decodes them between the LF coefficients and the HF metadata —, the others in the PassGroup sections of the passes whose brackets hold
+    // them — ModularGroupFastKernel reads them behind that pass's coefficients, FramePlan::mod_pass / mod_passes)
     if (!p.has_global_tree) throw ParseError("unsupported: VarDCT frame without a global MA tree (its LF streams would need local trees)", true);
     if (p.subsampled && (p.base_x != 0.f || p.base_b != 0.f)) throw ParseError("unsupported: chroma from luma in a chroma-subsampled frame", true);
     if (!p.local_streams.empty()) throw ParseError("unsupported: local MA tree in the global Modular stream of a VarDCT frame", true);
@@ -1122,7 +1120,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
         const size_t gd = p.group_dim;
         o.mod_scratch_stride = (8 + 4) * gd * gd + 4 * 65536;
         o.mod_scratch = take(o.mod_scratch_stride * 4 * p.NumModUnits());
-        o.hf_end = take((size_t)p.num_groups * 8);
+        o.hf_end = take((size_t)p.num_groups * p.ModUnitPasses() * 8);   // (pass - mod_pass, g)
         // the Modular streams keep their WP state apart from the LF streams'
         o.mod_wp_stride = p.tree.uses_wp ? 10 * (65536 + 2) : 16;
         o.mod_wp = take(o.mod_wp_stride * 4 * (1 + p.NumModUnits()));

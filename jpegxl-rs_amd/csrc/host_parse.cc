@@ -995,6 +995,14 @@ void ParseFrameStart(const Codestream& cs, const ImageHeader& ih, uint64_t frame
   rg.limit_bits = (p->sections[0].offset + p->sections[0].size) * 8;
   ParseLfGlobal(rg, ih, p);
   p->end_bitpos = rg.pos();
+  if (!p->modular && p->num_passes > 1 && !(p->pass_min_shift[p->mod_pass] <= 0 && p->pass_max_shift[p->mod_pass] >= 2))
+    for (auto& t : p->gtransforms) if (t.id == 2) {
+      // squeezed extra channels whose sub-channels of shift 0..2 lie in the brackets of several passes: Modular units (pass, g) from the first pass with a bracket
+      uint32_t first = 0;
+      while (first < p->mod_pass && p->pass_min_shift[first] > p->pass_max_shift[first]) first++;
+      p->mod_passes = p->num_passes - first; p->mod_pass = first;
+      break;
+    }
   ParseLocalModularStreams(cs, p);
   if (p->max_prop >= 16 + 4 * kMaxModRefs) Unsupported("MA tree property beyond the supported previous-channel references");
   if (!p->single_section && !p->modular) ParseHfGlobal(cs, ih, p->sections[1 + p->num_lf_groups].offset * 8, p);

@@ -122,8 +122,10 @@ struct FramePlan {
   // passes.h GetDownsamplingBracket: the Modular channels PassGroup (pass, g) carries are those with pass_min_shift <= min(hshift, vshift) <= pass_max_shift
   uint32_t num_ds = 0, downsample[4] = {0}, ds_last_pass[4] = {0};
   int32_t pass_min_shift[11] = {0}, pass_max_shift[11] = {2};
-  uint32_t mod_pass = 0;                   // VarDCT frames: the pass whose sections carry the (unsqueezed) extra channels
-  uint32_t ModUnitPasses() const { return modular ? num_passes : 1; }      // Modular sub-streams per group the device decodes
+  // VarDCT frames: the first pass whose sections carry extra channels (shift 0..2), and how many passes from it on do — one (the pass whose bracket
+  // holds shift 0), unless squeezed extra channels are spread over several passes by the downsampling entries: then every pass from the first with a bracket on
+  uint32_t mod_pass = 0, mod_passes = 1;
+  uint32_t ModUnitPasses() const { return modular ? num_passes : mod_passes; }      // Modular sub-streams per group the device decodes
   uint32_t NumModUnits() const { return num_lf_groups + num_groups * ModUnitPasses(); }
   bool is_last = true;
   // LF frames (frame_header.cc kDCFrame / kUseDcFrame): a frame of type 1 is the LF image — one sample per 8x8 block — of the frames one level below it

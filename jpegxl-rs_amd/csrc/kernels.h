@@ -95,7 +95,7 @@ struct FrameDev {
   uint32_t mod_bits;
   int32_t* mod_wp_scratch;        // weighted-predictor state of the Modular sub-streams: global, then one per LfGroup / PassGroup unit
   uint64_t mod_wp_stride;
-  uint64_t* hf_end_bitpos;        // VarDCT frames with extra channels: where each group's HF coefficient stream ended (its Modular part starts there)
+  uint64_t* hf_end_bitpos;        // VarDCT frames with extra channels: where the HF coefficient stream of PassGroup (mod_pass + k, g) ended, at [k * num_groups + g] (its Modular part starts there)
   const int32_t* alpha_plane;     // VarDCT frames: decoded alpha extra channel (image-sized), or null
   float alpha_factor;             // 1 / (2^bits - 1)
   // output
@@ -112,8 +112,8 @@ struct FrameDev {
   uint4* place_rec;               // varblock placement records (one per varblock, grouped per band: BandRecordBase), bw x bh entries
   uint32_t* place_cnt;            // [LF group * 8 + band] records of the band
   uint32_t* band_start;           // [LF group * 8 + band] index of the band's first entry in the LF group's strategy list (0xFFFFFFFF: damaged)
-  uint32_t mod_unit_passes;       // Modular sub-streams per group: the frame's passes (Modular frames), 1 (VarDCT frames: the extra channels' pass only, mod_pass)
-  uint32_t mod_pass;
+  uint32_t mod_unit_passes;       // Modular sub-streams per group: the frame's passes (Modular frames); VarDCT frames: the passes mod_pass, mod_pass + 1, ... that carry extra
+  uint32_t mod_pass;              // channels — one, unless squeezed extra channels are spread over several passes (FramePlan::mod_passes)
   int32_t pass_min_shift[11], pass_max_shift[11];   // passes.h GetDownsamplingBracket per pass: the channels (by min(hshift, vshift)) a PassGroup of that pass carries
   uint32_t lz_lf_base;            // LZ77-coded LF-group streams of a VarDCT frame: index of LF group 0's window in lz_window (the Modular units' windows come first)
   uint32_t use_lf_frame;          // frame_header.cc kUseDcFrame: no LF coefficients in the LfGroups, the LF image is an LF frame's samples (no dequantisation, no smoothing, LF context 0)

@@ -3620,7 +3620,8 @@ template <bool ALL_LDS, bool SUB, bool MULTI> __global__ __launch_bounds__(1024)
     }
   }
   if (err) { SetError(f, err); dead = true; }
-  else if (!dead && f.hf_end_bitpos && pass == f.mod_pass) f.hf_end_bitpos[g] = end_bitpos;   // the Modular part of the extra channels' pass follows its coefficients
+  else if (!dead && f.hf_end_bitpos && pass >= f.mod_pass && pass - f.mod_pass < f.mod_unit_passes)   // the Modular part of a pass that carries extra channels
+    f.hf_end_bitpos[(pass - f.mod_pass) * f.num_groups + g] = end_bitpos;                                 // follows its coefficients
   if (!dead && nz_total) { atomicAdd(f.hf_written, nz_total); nz_total = 0; }
   }  // passes
 }
@@ -5617,8 +5618,8 @@ template <bool BIGTREE> __global__ __launch_bounds__(256, BIGTREE ? 1 : JXL_MODG
   if (!local_pass && f.mod_local && f.mod_local[1 + unit].tree) return;   // decoded by the local pass
   const bool is_lf = unit < f.num_lf_groups;
   if (!f.is_modular && is_lf) return;            // VarDCT: extra channels are never squeezed here, so ModularLfGroup is empty
-  // units after the LF groups: PassGroup (pass, g), pass-major — Modular frames: every pass; VarDCT frames: the pass that carries the extra channels
-  const uint32_t last_pass = is_lf ? 0 : f.is_modular ? (unit - f.num_lf_groups) / f.num_groups : f.mod_pass;
+  // units after the LF groups: PassGroup (pass, g), pass-major — Modular frames: every pass; VarDCT frames: the passes from mod_pass on that carry the extra channels
+  const uint32_t last_pass = is_lf ? 0 : (f.is_modular ? 0 : f.mod_pass) + (unit - f.num_lf_groups) / f.num_groups;
   const uint32_t g = is_lf ? unit : (unit - f.num_lf_groups) % f.num_groups;
   const uint32_t dim = is_lf ? f.group_dim * 8 : f.group_dim;
   const uint32_t cols = is_lf ? f.xlfgroups : f.xgroups;
@@ -5639,7 +5640,7 @@ template <bool BIGTREE> __global__ __launch_bounds__(256, BIGTREE ? 1 : JXL_MODG
     U.go = 0; U.nch = 0; U.direct = 1; U.used = 0;
     if (nch > 0) {
       BitReader tmp;
-      tmp.Init(f.cs, f.is_modular ? f.sec_off[si] * 8 : f.hf_end_bitpos[g], f.cs_size);
+      tmp.Init(f.cs, f.is_modular ? f.sec_off[si] * 8 : f.hf_end_bitpos[unit - f.num_lf_groups], f.cs_size);   // (VarDCT: the end of PassGroup (last_pass, g)'s coefficients)
       bool ok = ReadGroupHeader(tmp, U.gh) && (U.gh.use_global_tree ? local == nullptr : local != nullptr);   // (a local tree the host has not parsed: VarDCT frames)
       if (ok && U.gh.ntransforms != 0) {
         // local transforms: channels are decoded into the unit's scratch (at most kMaxXformChan of them)

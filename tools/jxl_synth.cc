@@ -706,6 +706,20 @@ static void WriteImageHeader(BitWriter& w, int xs, int ys, const Params& p, bool
 
 // bit-plane split of the passes: 2 passes -> shifts {2, 0}; 3 passes -> {3, 1, 0}
 static int PassShift(int num_passes, int pass) { return pass + 1 == num_passes ? 0 : (num_passes == 2 ? 2 : (pass == 0 ? 3 : 1)); }
+// passes.h GetDownsamplingBracket for the frame header WriteFrameHeader writes (VarDCT): PassGroup `pass` carries the Modular channels with
+// min_shift <= min(hshift, vshift) <= max_shift.  pass_ds: entry i is downsample 2^(nds - i) with last pass i -> {[1, 2], [0, 0]} (2 passes),
+// {[2, 2], [1, 1], [0, 0]} (3 passes); without it every channel of shift 0..2 rides in the last pass
+static void PassBracket(const Params& p, int pass, int* min_shift, int* max_shift) {
+  const int np = p.num_passes, nds = p.pass_ds && np > 1 ? np - 1 : 0;
+  int mins = 3, maxs = 2;
+  for (int i = 0;; i++) {
+    if (i < nds) mins = nds - i;
+    if (i + 1 == np) mins = 0;
+    if (i == pass) break;
+    maxs = mins - 1;
+  }
+  *min_shift = mins; *max_shift = maxs;
+}
 
 // VarDCT frames written from now on (this thread) carry a RestorationFilter bundle with every custom field set: gaborish weights, EPF sharpness LUT, channel scales,
 // sigma parameters (loop_filter.cc) — the encoder side does not look at them
@@ -1182,10 +1196,13 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
   }  // passes
   // --- optional alpha: one 8-bit extra channel coded losslessly by the frame's Modular sub-streams (GlobalModular when
   // the image fits one group, else the modular part of every PassGroup), under the same global tree
-  std::vector<Token> alpha_global_tok;
-  std::vector<std::vector<Token>> alpha_tok(ngroups), alpha_lf_tok;
-  std::vector<char> alpha_lf_has, alpha_has;          // squeezed alpha: which LfGroup / PassGroup sections carry a Modular sub-stream
+  // squeezed alpha of a frame with downsampling entries: the sub-channels of shift 0..2 are spread over the PassGroups of every pass (by its bracket);
+  // otherwise they all ride in the last pass.  alpha_tok / alpha_has: (pass, group) of the last sq_passes passes, pass-major
   const bool alpha_sq = alpha && AlphaSqueeze();
+  const int sq_passes = alpha_sq && np > 1 && p.pass_ds ? np : 1;
+  std::vector<Token> alpha_global_tok;
+  std::vector<std::vector<Token>> alpha_tok((size_t)ngroups * sq_passes), alpha_lf_tok;
+  std::vector<char> alpha_lf_has, alpha_has;          // squeezed alpha: which LfGroup / PassGroup sections carry a Modular sub-stream
   const bool alpha_global = alpha && w <= 256 && h <= 256;
   if (alpha) {
     std::vector<int32_t> a32((size_t)w * h);
@@ -1223,9 +1240,15 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
         ModularTokens(gt, root, cr, stream_id, out);
         return true;
       };
-      alpha_lf_tok.resize(nlf); alpha_lf_has.assign(nlf, 0); alpha_has.assign(ngroups, 0);
+      alpha_lf_tok.resize(nlf); alpha_lf_has.assign(nlf, 0); alpha_has.assign((size_t)ngroups * sq_passes, 0);
       for (int g = 0; g < nlf; g++) alpha_lf_has[g] = group_stream((g % xlg) * 2048, (g / xlg) * 2048, 2048, 3, 1000, 1 + nlf + g, alpha_lf_tok[g]);
-      for (int g = 0; g < ngroups; g++) alpha_has[g] = group_stream((g % xg) * 256, (g / xg) * 256, 256, 0, 2, 1 + 3 * nlf + 17 + ngroups * (p.num_passes - 1) + g, alpha_tok[g]);
+      for (int k = 0; k < sq_passes; k++) {
+        const int ps = np - sq_passes + k;
+        int min_shift = 0, max_shift = 2;
+        if (sq_passes > 1) PassBracket(p, ps, &min_shift, &max_shift);
+        for (int g = 0; g < ngroups; g++)
+          alpha_has[(size_t)k * ngroups + g] = group_stream((g % xg) * 256, (g / xg) * 256, 256, min_shift, max_shift, 1 + 3 * nlf + 17 + ngroups * ps + g, alpha_tok[(size_t)k * ngroups + g]);
+      }
     } else if (alpha_global) {
       std::vector<ChanRef> cr{{a32.data(), w, h}};
       ModularTokens(gt, root, cr, 0, alpha_global_tok);
@@ -1354,8 +1377,12 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
     BitWriter s;
     s.put((uint32_t)(g % npresets), CeilLog2((uint32_t)npresets));   // which histogram set (0 bits when there is one)
     EncodeTokens(s, ac_codes[ps], ac_tok_all[(size_t)ps * ngroups + g]);
-    // extra channels (shift 0..2) ride in the last pass (Passes::GetDownsamplingBracket without downsampling entries)
-    if (alpha && (alpha_sq || !alpha_global) && ps == np - 1 && alpha_has[g]) { s.put(1, 1); s.put(1, 1); s.put(0, 2); EncodeTokens(s, mod_code, alpha_tok[g]); }
+    // extra channels (shift 0..2) ride in the last pass (Passes::GetDownsamplingBracket without downsampling entries), squeezed ones of a frame with
+    // downsampling entries in the pass whose bracket holds their shift — behind that pass's coefficients
+    const int k = ps - (np - sq_passes);
+    if (alpha && (alpha_sq || !alpha_global) && k >= 0 && alpha_has[(size_t)k * ngroups + g]) {
+      s.put(1, 1); s.put(1, 1); s.put(0, 2); EncodeTokens(s, mod_code, alpha_tok[(size_t)k * ngroups + g]);
+    }
     sections.push_back(s);
   }
   BitWriter out;

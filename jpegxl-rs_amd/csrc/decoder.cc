@@ -105,6 +105,7 @@ struct ConstOffsets {
   vec<Pass> pass;
   struct Local { uint32_t unit = 0; size_t tree = 0, ctx = 0, cfg = 0, alias = 0, pc = 0, po = 0, ps = 0; };   // sub-streams with their own tree / code
   vec<Local> local;
+  vec<Local> lf_local;   // LfGroup sub-streams with their own tree / code (FramePlan::lf_local; unit = 3 g + k)
   size_t qtable[17 * 3] = {0};
   bool has_qtable[17] = {false};
 };
@@ -599,9 +600,15 @@ static void CheckFrameSupported(const FramePlan& p, const ImageHeader& ih) {
     // (squeezed extra channels, what cjxl does to a progressive or lossy alpha of an RGBA picture, are taken: the sub-channels squeezed by >= 3 ride in the LfGroup
     // sections — the LF kernel decodes them between the LF coefficients and the HF metadata —, the others in the PassGroup sections of the passes whose brackets hold
     // them — ModularGroupFastKernel reads them behind that pass's coefficients, FramePlan::mod_pass / mod_passes)
-    if (!p.has_global_tree) throw ParseError("unsupported: VarDCT frame without a global MA tree (its LF streams would need local trees)", true);
+    // (Modular sub-streams with MA trees and codes of their own are taken in the global stream and the LfGroup sections — FramePlan::lf_local, LfDecodeLocalKernel.
+    // The extra-channel streams behind the AC coefficients of the PassGroup sections are not: their start is known only once the HF stage has run.  A frame with a
+    // global tree whose PassGroup streams do not use it fails in ModularGroupFastKernel with kErrUnsupported; without a global tree it is refused here.)
+    if (!p.has_global_tree) {
+      bool tails = false;
+      for (size_t c = p.global_decodable; c < p.gchannels.size(); c++) tails |= p.gchannels[c].w && p.gchannels[c].h && std::min(p.gchannels[c].hshift, p.gchannels[c].vshift) <= 2;
+      if (tails) throw ParseError("unsupported: VarDCT frame without a global MA tree whose PassGroup sections carry extra channels (local trees behind the AC coefficients)", true);
+    }
     if (p.subsampled && (p.base_x != 0.f || p.base_b != 0.f)) throw ParseError("unsupported: chroma from luma in a chroma-subsampled frame", true);
-    if (!p.local_streams.empty()) throw ParseError("unsupported: local MA tree in the global Modular stream of a VarDCT frame", true);
   }
   for (auto& x : ih.extra) {
     if (x.dim_shift != 0) throw ParseError("unsupported: subsampled extra channel", true);
@@ -1021,6 +1028,15 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       PutCode(arena, ls.code, &l.ctx, &l.cfg, &l.alias, &l.pc, &l.po, &l.ps);
       c.local.push_back(l);
     }
+    for (size_t k = 0; k < p.lf_local.size(); k++) {
+      const FramePlan::LfLocal& ll = p.lf_local[k];
+      if (!ll.present) continue;
+      ConstOffsets::Local l;
+      l.unit = (uint32_t)k;
+      l.tree = arena.Put(ll.tree.nodes.data(), ll.tree.nodes.size() * sizeof(TreeNode));
+      PutCode(arena, ll.code, &l.ctx, &l.cfg, &l.alias, &l.pc, &l.po, &l.ps);
+      c.lf_local.push_back(l);
+    }
     c.bcm = arena.Put(&p.bcm, sizeof(p.bcm));
     if (!p.modular) {
       any_vardct_ = true;
@@ -1106,6 +1122,10 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       bool wide_wp = false;
       if (p.tree.uses_wp && p.has_global_tree)
         for (uint32_t g = 0; g < p.num_lf_groups && !wide_wp; g++) wide_wp = LfChannelUsesWp(p.tree, 2, 1 + 2 * p.num_lf_groups + g);
+      for (uint32_t g = 0; g < p.num_lf_groups && !p.lf_local.empty() && !wide_wp; g++) {   // (local trees: the HF-metadata stream's own, or the global one it uses)
+        const FramePlan::LfLocal& l = p.lf_local[3 * (size_t)g + 2];
+        wide_wp = l.present ? LfChannelUsesWp(l.tree, 2, 1 + 2 * p.num_lf_groups + g) : (p.tree.uses_wp && LfChannelUsesWp(p.tree, 2, 1 + 2 * p.num_lf_groups + g));
+      }
       o.wp_scratch_stride = wide_wp ? 10 * (65536 + 2) : kLfSimtWpInts;
       o.wp_scratch = take(o.wp_scratch_stride * 4 * p.num_lf_groups);
       if (!p.gchannels.empty()) {
@@ -1122,7 +1142,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
         o.mod_scratch = take(o.mod_scratch_stride * 4 * p.NumModUnits());
         o.hf_end = take((size_t)p.num_groups * p.ModUnitPasses() * 8);   // (pass - mod_pass, g)
         // the Modular streams keep their WP state apart from the LF streams'
-        o.mod_wp_stride = p.tree.uses_wp ? 10 * (65536 + 2) : 16;
+        o.mod_wp_stride = (p.tree.uses_wp || (!p.local_streams.empty() && p.local_streams[0].tree.uses_wp)) ? 10 * (65536 + 2) : 16;
         o.mod_wp = take(o.mod_wp_stride * 4 * (1 + p.NumModUnits()));
       }
     } else {
@@ -1146,7 +1166,12 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       o.wp_scratch = take(o.wp_scratch_stride * 4 * (1 + p.NumModUnits()));
       if (e.complex) for (int c = 0; c < 3; c++) { o.plane_a[c] = take_big((size_t)p.bw * 8 * p.bh * 8 * 4); o.plane_b[c] = (size_t)-1; }
     }
-    if (p.has_global_tree && p.tree_code.lz77 && (!p.gchannels.empty() || !p.modular))   // LZ77 windows of the Modular streams (4 MiB each); VarDCT: + one per LF group
+    bool lz_local = false;     // (Modular sub-streams with codes of their own)
+    if (!p.modular) {
+      for (auto& ls : p.local_streams) lz_local |= ls.code.lz77;
+      for (auto& l : p.lf_local) lz_local |= l.present && l.code.lz77;
+    }
+    if (((p.has_global_tree && p.tree_code.lz77) || lz_local) && (!p.gchannels.empty() || !p.modular))   // LZ77 windows of the Modular streams (4 MiB each); VarDCT: + one per LF group
       o.lz_window = take((size_t)(1 + p.NumModUnits() + (p.modular ? 0 : p.num_lf_groups)) * (4u << 20));
     if (!p.modular) {   // LZ77-coded AC streams: a window per group stream (1 MiB each, only for the frames that use them)
       bool lz_ac = p.single_section;    // (a one-section frame's AC code is only parsed once its LF streams have been decoded: always reserved, 1 MiB)
@@ -1269,6 +1294,22 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
         d.code = ViewCode(ls.code, cbase, l.ctx, l.cfg, l.alias, l.pc, l.po, l.ps);
       }
     }
+    if (!p.lf_local.empty()) {
+      // LfGroup sub-streams: [3 g + k] behind the unit table, zero = "uses the frame's tree"; the frame takes LfDecodeLocalKernel
+      const size_t first = local_first_[i] + (p.local_streams.empty() ? 0 : 1 + (size_t)p.NumModUnits());
+      ModLocalDev* table = &local_host_[first];
+      f.lf_local = dlocal_ + first;
+      for (const ConstOffsets::Local& l : c.lf_local) {
+        const FramePlan::LfLocal& ll = p.lf_local[l.unit];
+        ModLocalDev& d = table[l.unit];
+        d.tree = (const TreeNode*)(cbase + l.tree); d.tree_nodes = (uint32_t)ll.tree.nodes.size(); d.uses_wp = ll.tree.uses_wp; d.max_prop = (uint32_t)ll.tree.max_prop;
+        d.data_bitpos = ll.data_bitpos;
+        d.code = ViewCode(ll.code, cbase, l.ctx, l.cfg, l.alias, l.pc, l.po, l.ps);
+        f.lf_lz77 |= ll.code.lz77 ? 1u : 0u;
+      }
+      if (p.has_global_tree && p.tree_code.lz77) f.lf_lz77 = 1;
+      f.tree_max_prop = (uint32_t)p.max_prop;      // (every tree the LF streams may use: whether they keep previous-channel references)
+    }
     f.bcm = (const BlockCtxDev*)(cbase + c.bcm);
     f.status = (uint32_t*)(dwork_ + status_off_) + i;
     f.frame_flags = (uint32_t*)(dwork_ + flags_off) + i;
@@ -1357,6 +1398,19 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     }
   };
 
+  {  // (before the one-section pre-run, whose LF decode reads them) descriptors of the sub-streams with their own tree / code: one table per frame that has any
+    local_first_.assign(n, 0);
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+      const FramePlan& p = images_[i]->plan;
+      local_first_[i] = total;
+      if (!p.local_streams.empty()) total += 1 + (size_t)p.NumModUnits();
+      total += p.lf_local.size();
+    }
+    local_host_.assign(std::max<size_t>(total, 1), ModLocalDev());
+    for (auto& d : local_host_) memset(&d, 0, sizeof(d));
+    DevReserve((void**)&dlocal_, &local_cap_, sizeof(ModLocalDev) * local_host_.size());
+  }
   vec<int> single;
   for (int i = 0; i < n; i++) if (images_[i]->plan.single_section && !images_[i]->plan.modular) {
     single.push_back(i);
@@ -1368,10 +1422,13 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     HIP_CHECK(hipMalloc((void**)&tmpc, Align(hconst_.size())));
     HIP_CHECK(hipMemcpyAsync(tmpc, hconst_.data(), hconst_.size(), hipMemcpyHostToDevice, stream));
     vec<FrameDev> tmpf;
-    for (int i : single) { fill_frame(i, tmpc); tmpf.push_back(frames_host_[i]); }
+    LaunchCfg pcfg = cfg;
+    pcfg.any_local_lf = 0;
+    for (int i : single) { fill_frame(i, tmpc); tmpf.push_back(frames_host_[i]); if (!images_[i]->plan.lf_local.empty()) pcfg.any_local_lf = 1; }
     HIP_CHECK(hipMemcpyAsync(dframes_, tmpf.data(), sizeof(FrameDev) * tmpf.size(), hipMemcpyHostToDevice, stream));
-    if (any_modchan_) LaunchModularGlobal(dframes_, (int)tmpf.size(), cfg, stream_v);   // extra channels of a one-group frame precede the LfGroup
-    LaunchLfDecode(dframes_, (int)tmpf.size(), 1, cfg, stream_v);
+    HIP_CHECK(hipMemcpyAsync(dlocal_, local_host_.data(), sizeof(ModLocalDev) * local_host_.size(), hipMemcpyHostToDevice, stream));   // (streams with their own trees)
+    if (any_modchan_) LaunchModularGlobal(dframes_, (int)tmpf.size(), pcfg, stream_v);   // extra channels of a one-group frame precede the LfGroup
+    LaunchLfDecode(dframes_, (int)tmpf.size(), 1, pcfg, stream_v);
     HIP_CHECK(hipStreamSynchronize(stream));
     for (size_t k = 0; k < single.size(); k++) {
       const int i = single[k];
@@ -1441,13 +1498,17 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     auto code_bytes_compact = [](const HostCode& c) { if (c.use_prefix || c.lz77) return 16;
       return (int)(((c.num_clusters * 4 + 15) & ~15u) + ((c.num_ctx + 15) & ~15u) + (((((size_t)c.num_clusters << c.log_alpha) * 6) + 15) & ~(size_t)15)); };
     cfg.ac_code_bytes_compact = 16;
-    cfg.max_tree_nodes = 1; cfg.mod_code_bytes = 16; cfg.ac_code_bytes = 16; cfg.any_wp = 0; cfg.any_local_trees = 0; cfg.any_subsampled = 0; cfg.any_prefix_ac = 0;
+    cfg.max_tree_nodes = 1; cfg.mod_code_bytes = 16; cfg.ac_code_bytes = 16; cfg.any_wp = 0; cfg.any_local_trees = 0; cfg.any_local_lf = 0; cfg.any_subsampled = 0; cfg.any_prefix_ac = 0;
     for (int i = 0; i < n; i++) {
       const FramePlan& p = images_[i]->plan;
       if (p.has_global_tree) { cfg.max_tree_nodes = std::max<int>(cfg.max_tree_nodes, (int)p.tree.nodes.size()); cfg.mod_code_bytes = std::max(cfg.mod_code_bytes, code_bytes(p.tree_code, false)); cfg.any_wp |= p.tree.uses_wp ? 1 : 0; }
       for (auto& ls : p.local_streams) {
         cfg.max_tree_nodes = std::max<int>(cfg.max_tree_nodes, (int)ls.tree.nodes.size()); cfg.mod_code_bytes = std::max(cfg.mod_code_bytes, code_bytes(ls.code, false)); cfg.any_wp |= ls.tree.uses_wp ? 1 : 0;
         if (ls.unit != 0) cfg.any_local_trees = 1;
+      }
+      if (!p.lf_local.empty()) cfg.any_local_lf = 1;
+      for (auto& l : p.lf_local) if (l.present) {
+        cfg.max_tree_nodes = std::max<int>(cfg.max_tree_nodes, (int)l.tree.nodes.size()); cfg.mod_code_bytes = std::max(cfg.mod_code_bytes, code_bytes(l.code, false)); cfg.any_wp |= l.tree.uses_wp ? 1 : 0;
       }
       if (!p.modular) for (auto& code : p.ac_code) { cfg.ac_code_bytes = std::max(cfg.ac_code_bytes, code_bytes(code, true)); cfg.ac_code_bytes_compact = std::max(cfg.ac_code_bytes_compact, code_bytes_compact(code)); }
       if (p.subsampled) cfg.any_subsampled = 1;
@@ -1461,18 +1522,6 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     for (int i = 0; i < n; i++) { pass_first_[i] = total; total += images_[i]->plan.modular ? 0 : images_[i]->plan.num_passes; }
     passes_host_.assign(std::max<size_t>(total, 1), PassDev());
     DevReserve((void**)&dpasses_, &passes_cap_, sizeof(PassDev) * passes_host_.size());
-  }
-  {  // descriptors of the sub-streams with their own tree / code: one table per frame that has any
-    local_first_.assign(n, 0);
-    size_t total = 0;
-    for (int i = 0; i < n; i++) {
-      const FramePlan& p = images_[i]->plan;
-      local_first_[i] = total;
-      if (!p.local_streams.empty()) total += 1 + (size_t)p.NumModUnits();
-    }
-    local_host_.assign(std::max<size_t>(total, 1), ModLocalDev());
-    for (auto& d : local_host_) memset(&d, 0, sizeof(d));
-    DevReserve((void**)&dlocal_, &local_cap_, sizeof(ModLocalDev) * local_host_.size());
   }
   if (any_complex_) {
     vec<size_t> upw(n, 0);
@@ -1516,7 +1565,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     bool wp_streams = false;                      // some eligible stream keeps weighted-predictor state: the batch takes that instantiation of the kernel
     for (int i = 0; i < n; i++) {
       const FramePlan& p = images_[i]->plan;
-      if (p.modular || !p.has_global_tree || p.tree_code.use_prefix || p.tree_code.lz77 || p.tree_code.log_alpha > 8 || p.tree_code.num_clusters > 256 || p.use_lf_frame) continue;
+      if (p.modular || !p.has_global_tree || !p.lf_local.empty() || p.tree_code.use_prefix || p.tree_code.lz77 || p.tree_code.log_alpha > 8 || p.tree_code.num_clusters > 256 || p.use_lf_frame) continue;
       {   // extra-channel sub-channels squeezed by >= 3 sit in the middle of the LfGroup sections: only the one-wavefront-per-stream kernel decodes those
         bool lf_modular = false;
         for (size_t c = p.global_decodable; c < p.gchannels.size(); c++) lf_modular |= p.gchannels[c].w && p.gchannels[c].h && std::min(p.gchannels[c].hshift, p.gchannels[c].vshift) >= 3;

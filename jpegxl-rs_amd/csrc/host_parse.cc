@@ -811,6 +811,7 @@ void ParseImageHeader(const Codestream& cs, ImageHeader* ih, uint64_t* frame_bit
 
 static void ParseLfGlobal(Reader& r, const ImageHeader& ih, FramePlan* p);
 static void ParseLocalModularStreams(const Codestream& cs, FramePlan* p);
+static void ParseLfLocalStreams(const Codestream& cs, FramePlan* p);
 
 void ParseFrameStart(const Codestream& cs, const ImageHeader& ih, uint64_t frame_bitpos, FramePlan* p, bool header_and_toc_only, bool allow_partial) {
   const bool skip = header_and_toc_only;
@@ -1004,6 +1005,7 @@ void ParseFrameStart(const Codestream& cs, const ImageHeader& ih, uint64_t frame
       break;
     }
   ParseLocalModularStreams(cs, p);
+  ParseLfLocalStreams(cs, p);
   if (p->max_prop >= 16 + 4 * kMaxModRefs) Unsupported("MA tree property beyond the supported previous-channel references");
   if (!p->single_section && !p->modular) ParseHfGlobal(cs, ih, p->sections[1 + p->num_lf_groups].offset * 8, p);
 }
@@ -1258,6 +1260,121 @@ static void ParseLocalModularStreams(const Codestream& cs, FramePlan* p) {
     if (ls.tree.uses_wp) p->mod_local_wp = true;
     p->max_prop = std::max(p->max_prop, ls.tree.max_prop);
     p->local_streams.push_back(std::move(ls));
+  }
+}
+
+// GroupHeader of an LfGroup sub-stream (or of the global stream): use_global_tree, predictor parameters; transforms are not taken there
+static bool ReadSubStreamHeader(Reader& r, WPHeader* wp) {
+  const bool global = r.b();
+  *wp = WPHeader{16, 10, {7, 7, 7, 0, 0}, {13, 12, 12, 12}};
+  if (!r.b()) { wp->p1 = r.u(5); wp->p2 = r.u(5); for (int i = 0; i < 5; i++) wp->p3[i] = r.u(5); for (int i = 0; i < 4; i++) wp->w[i] = r.u(4); }
+  if (r.U32({0, 0}, {0, 1}, {4, 2}, {8, 18}) != 0) Unsupported("transforms in an LF group stream of a VarDCT frame with local MA trees");
+  return global;
+}
+
+// Entropy-decodes a Modular sub-stream on the host (the per-thread decoder of jxl_dev.h, as for RAW quant tables) for one thing only: where it
+// ends, which is where the LfGroup sub-stream behind it starts.  dims: its channels in stream order.
+static uint64_t SkipModularStream(const Codestream& cs, uint64_t bitpos, uint64_t limit_bits, const HostTree& tree, const HostCode& code, const WPHeader& wp,
+                                  uint32_t stream_id, const vec<std::pair<uint32_t, uint32_t>>& dims) {
+  if (code.lz77) Unsupported("LZ77-coded stream in front of an LF group stream with a local MA tree");
+  if (tree.max_prop >= 16) Unsupported("previous-channel properties in a stream in front of an LF group stream with a local MA tree");
+  const DevCode view = code.View();
+  Reader r(cs, bitpos);
+  r.limit_bits = limit_bits;
+  ModularCtx mc;
+  mc.tree = tree.nodes.data(); mc.code = &view; mc.wp = wp; mc.uses_wp = tree.uses_wp; mc.stream_id = stream_id;
+  uint32_t widest = 1;
+  for (auto& d : dims) widest = std::max(widest, d.first);
+  vec<int32_t> wps(tree.uses_wp ? 10 * ((size_t)widest + 2) : 16, 0), buf;
+  mc.wp_scratch = wps.data();
+  AnsReader ans;
+  ans.Init(r.br, view);
+  for (size_t c = 0; c < dims.size(); c++) {
+    if (dims[c].first == 0 || dims[c].second == 0) continue;
+    buf.assign((size_t)dims[c].first * dims[c].second, 0);
+    ChannelDesc ch; ch.data = buf.data(); ch.w = (int)dims[c].first; ch.h = (int)dims[c].second; ch.stride = ch.w;
+    DecodeModularChannel(r.br, ans, mc, ch, (int)c);
+    if (r.pos() > r.limit_bits) throw ParseError("truncated", false);
+  }
+  if (!ans.FinalOk(view)) Fail("LF group stream ANS final state");
+  return r.pos();
+}
+
+// VarDCT frames whose LfGroup sub-streams may bring MA trees / entropy codes of their own (FramePlan::lf_local): every frame without a global tree,
+// and frames whose global stream or whose LF coefficient streams carry trees of their own.  Only the first sub-stream of an LfGroup section starts
+// where the TOC says; the ModularLfGroup and HF-metadata streams start where the data before them ends.  The host finds those positions here,
+// decoding the streams in front of them once (SkipModularStream), so that the device decodes the frame in its normal launches.
+static void ParseLfLocalStreams(const Codestream& cs, FramePlan* p) {
+  p->lf_local.clear();
+  if (p->modular) return;
+  bool local = !p->has_global_tree || !p->local_streams.empty();
+  // (one section with a global Modular image in front of the LfGroup: not looked at — a local LF tree there fails the LF stage with kErrUnsupported)
+  if (!local && !p->use_lf_frame && (!p->single_section || p->gchannels.empty()))
+    for (uint32_t g = 0; g < p->num_lf_groups && !local; g++) {
+      Reader r(cs, p->single_section ? p->global_data_bitpos : p->sections[1 + g].offset * 8);
+      if (!p->single_section) r.limit_bits = (p->sections[1 + g].offset + p->sections[1 + g].size) * 8;
+      r.u(2);                                  // extra_precision
+      local = !r.b();                          // use_global_tree
+    }
+  if (!local) return;
+  p->lf_local.assign(3 * (size_t)p->num_lf_groups, FramePlan::LfLocal());
+  uint64_t pos = p->global_data_bitpos;
+  if (p->single_section && !p->gchannels.empty()) {
+    // one section: the LfGroup follows the global Modular stream
+    const bool own = !p->local_streams.empty() && p->local_streams[0].unit == 0;
+    vec<std::pair<uint32_t, uint32_t>> dims;
+    for (uint32_t c = 0; c < p->global_decodable; c++) dims.push_back({p->gchannels[c].w, p->gchannels[c].h});
+    pos = SkipModularStream(cs, pos, cs.size * 8, own ? p->local_streams[0].tree : p->tree, own ? p->local_streams[0].code : p->tree_code, p->gwp, 0, dims);
+  }
+  for (uint32_t g = 0; g < p->num_lf_groups; g++) {
+    const uint64_t start = p->single_section ? pos : p->sections[1 + g].offset * 8;
+    const uint64_t limit = p->single_section ? cs.size * 8 : (p->sections[1 + g].offset + p->sections[1 + g].size) * 8;
+    const uint32_t gx = g % p->xlfgroups, gy = g / p->xlfgroups;
+    const uint32_t gbw = std::min<uint32_t>(256, p->bw - gx * 256), gbh = std::min<uint32_t>(256, p->bh - gy * 256);
+    const size_t tree_limit = std::min<size_t>(1u << 20, 1024 + 4 * (size_t)gbw * gbh);
+    Reader r(cs, start);
+    r.limit_bits = limit;
+    // one sub-stream: its GroupHeader, its own tree and code if it has them; returns the tree / code it is coded with
+    auto header = [&](int k, WPHeader* wp) -> std::pair<const HostTree*, const HostCode*> {
+      if (ReadSubStreamHeader(r, wp)) {
+        if (!p->has_global_tree) Fail("global tree missing");
+        return {&p->tree, &p->tree_code};
+      }
+      FramePlan::LfLocal& l = p->lf_local[3 * (size_t)g + k];
+      ReadTree(r, &l.tree, tree_limit);
+      ReadEntropyCode(r, l.tree.num_leaves, &l.code);
+      l.data_bitpos = r.pos();
+      l.present = true;
+      p->max_prop = std::max(p->max_prop, l.tree.max_prop);
+      return {&l.tree, &l.code};
+    };
+    WPHeader wp;
+    if (!p->use_lf_frame) {
+      r.u(2);                                                            // extra_precision
+      auto tc = header(0, &wp);
+      vec<std::pair<uint32_t, uint32_t>> dims;
+      const int chan_to_plane[3] = {1, 0, 2};
+      for (int c = 0; c < 3; c++) dims.push_back({gbw >> p->hs[chan_to_plane[c]], gbh >> p->vs[chan_to_plane[c]]});
+      r = Reader(cs, SkipModularStream(cs, r.pos(), limit, *tc.first, *tc.second, wp, 1 + g, dims));
+      r.limit_bits = limit;
+    }
+    // ModularLfGroup: the extra channels' sub-channels squeezed by >= 3 (dec_modular.cc DecodeGroup with the LF group's rectangle)
+    vec<std::pair<uint32_t, uint32_t>> lf_dims;
+    for (size_t c = p->global_decodable; c < p->gchannels.size(); c++) {
+      const auto& m = p->gchannels[c];
+      if (m.w == 0 || m.h == 0 || std::min(m.hshift, m.vshift) < 3) continue;
+      const uint32_t x0 = gx * 2048, y0 = gy * 2048, rx = x0 >> m.hshift, ry = y0 >> m.vshift;
+      if (rx >= m.w || ry >= m.h) continue;
+      const uint32_t rw = std::min<uint32_t>(2048 >> m.hshift, m.w - rx), rh = std::min<uint32_t>(2048 >> m.vshift, m.h - ry);
+      if (rw && rh) lf_dims.push_back({rw, rh});
+    }
+    if (!lf_dims.empty()) {
+      auto tc = header(1, &wp);
+      r = Reader(cs, SkipModularStream(cs, r.pos(), limit, *tc.first, *tc.second, wp, 1 + p->num_lf_groups + g, lf_dims));
+      r.limit_bits = limit;
+    }
+    r.u(CeilLog2(gbw * gbh));                                            // nb_blocks - 1
+    header(2, &wp);                                                      // HF metadata: nothing behind it in the section
   }
 }
 

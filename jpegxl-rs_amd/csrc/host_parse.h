@@ -177,6 +177,12 @@ struct FramePlan {
   // with their stream; data_bitpos = absolute bit position of the stream's ANS state.
   struct LocalStream { uint32_t unit = 0; HostTree tree; HostCode code; uint64_t data_bitpos = 0; };
   vec<LocalStream> local_streams;
+  // VarDCT frames whose LfGroup sub-streams may bring trees / codes of their own: [3 g + k], k = 0 LF coefficients, 1 ModularLfGroup, 2 HF metadata
+  // (present = false: the global tree), parsed with the frame (host_parse.cc ParseLfLocalStreams).  Empty: the frame has a global tree and its global
+  // stream and LF coefficient streams use it — the global-tree LF kernels.
+  struct LfLocal { bool present = false; HostTree tree; HostCode code; uint64_t data_bitpos = 0; };
+  vec<LfLocal> lf_local;
+  size_t NumLfLocal() const { size_t n = 0; for (auto& l : lf_local) n += l.present ? 1 : 0; return n; }
   int max_prop = 0;                  // largest property index any MA tree of the frame tests
   uint64_t global_data_bitpos = 0;   // absolute bit position (codestream) where the global stream's ANS state starts
   uint32_t global_decodable = 0;     // number of leading channels decoded in the global section

@@ -1128,7 +1128,7 @@ int JxlHipDebugDescribe(const uint8_t* data, size_t size, char* out, size_t cap)
       snprintf(line, sizeof line, "frame %d %s type=%u %ux%u at (%d,%d) groups=%u lf_groups=%u passes=%u upsampling=%u patches=%zu splines=%zu noise=%d blend=%u last=%d "
                "tree_nodes=%zu max_prop=%d wp=%d prefix=%d lz77=%d local_streams=%zu transforms=%zu sections=%zu\n", i, p.modular ? "modular" : "vardct", p.frame_type, p.width, p.height,
                p.x0, p.y0, p.num_groups, p.num_lf_groups, p.num_passes, p.upsampling, p.feat.patches.size(), p.feat.splines.size(), (int)p.feat.has_noise, p.blend.mode, (int)p.is_last,
-               p.tree.nodes.size(), p.max_prop, (int)p.tree.uses_wp, (int)p.tree_code.use_prefix, (int)p.tree_code.lz77, p.local_streams.size(), p.gtransforms.size(), p.sections.size());
+               p.tree.nodes.size(), p.max_prop, (int)p.tree.uses_wp, (int)p.tree_code.use_prefix, (int)p.tree_code.lz77, p.local_streams.size() + p.NumLfLocal(), p.gtransforms.size(), p.sections.size());
       s += line;
       if (!p.modular) {
         snprintf(line, sizeof line, "  quantizer global_scale=%u quant_lf=%u m_lf=%g,%g,%g x_qm=%u b_qm=%u cfl_base=%g,%g colour_factor=%u ycbcr=%d sampling=%u,%u,%u flags=%llu\n", p.global_scale, p.quant_lf,

@@ -46,6 +46,9 @@ struct FrameDev {
   uint32_t tree_max_prop;         // largest property index in any MA tree of the frame (>= 16: previous-channel properties)
   const ModLocalDev* mod_local;   // Modular sub-streams with a tree and code of their own, indexed 0 = global stream, 1 + unit = LfGroup /
                                   // PassGroup unit (entries with tree == nullptr use the frame's tree); nullptr: none in this frame
+  const ModLocalDev* lf_local;    // VarDCT frames whose LfGroup sub-streams bring trees / codes of their own (LfDecodeLocalKernel): [3 g + k], k = 0 LF coefficients,
+                                  // 1 ModularLfGroup, 2 HF metadata (tree == nullptr: the global tree); nullptr: the frame takes the global-tree LF kernels
+  uint32_t lf_lz77;               // some LfGroup sub-stream of the frame is LZ77-coded (lz_window holds a window per LF group from lz_lf_base on)
   DevCode ac_code;
   const uint16_t* orders[39];
   const BlockCtxDev* bcm;
@@ -138,6 +141,7 @@ struct LaunchCfg {
   int any_multipass = 0;     // some frame has progressive passes (the general instantiation of the SIMT HF kernel)
   int any_prefix_ac = 0;     // some VarDCT frame's AC code is a prefix code or LZ77-coded (HfDecodeKernel beside the SIMT kernel)
   int any_local_trees = 0;   // some Modular sub-stream carries its own MA tree / code (second launch of the group kernel)
+  int any_local_lf = 0;      // some VarDCT frame's LfGroup sub-streams carry their own trees / codes (LfDecodeLocalKernel)
   // filled by Batch::Prepare: LDS needs of the batch (bytes of cfg + ctx map + alias tables, MA-tree nodes)
   int max_tree_nodes = 1024, mod_code_bytes = 1 << 20, ac_code_bytes = 1 << 20, ac_code_bytes_compact = 1 << 20;   // (compact: 6 bytes per alias slot, StageCodeCompact)
   int force_generic_idct = 0;
@@ -195,8 +199,9 @@ struct LfSimtPlan {
 enum : int {
   kHfVarWave = 1, kHfVarSimtPlain = 2, kHfVarSimtAllLds = 4, kHfVarSimtGlobal = 8, kHfVarLaneStride = 16, kHfVarPrefix = 32,   // HfDecodeWaveKernel, HfDecodeSimtKernel
   // <true,false,false> / <true,true,true> / <false,true,true>, HfDecodeKernel (lane-stride batches), HfDecodeKernel beside the SIMT kernel (prefix-coded / LZ77 AC codes)
-  kLfVarSimtLean = 1, kLfVarSimtGen = 2, kLfVarSimtWp = 4, kLfVarSimtWpQuad = 8, kLfVarBig = 16, kLfVarSmall = 32,   // LfDecodeSimtKernel<false,false> / <false,true> /
-  // <true,true> / <true,true,true>, LfDecodeKernel<true> (four groups per workgroup, register-capped) / <false> (one group per wavefront, or four uncapped)
+  kLfVarSimtLean = 1, kLfVarSimtGen = 2, kLfVarSimtWp = 4, kLfVarSimtWpQuad = 8, kLfVarBig = 16, kLfVarSmall = 32, kLfVarLocal = 64,   // LfDecodeSimtKernel<false,false> / <false,true> /
+  // <true,true> / <true,true,true>, LfDecodeKernel<true> (four groups per workgroup, register-capped) / <false> (one group per wavefront, or four uncapped),
+  // LfDecodeLocalKernel (LF groups with trees / codes of their own)
 };
 struct LaunchTrace {
   int hf_variant = 0, lf_variant = 0;

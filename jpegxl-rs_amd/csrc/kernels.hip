@@ -2165,7 +2165,12 @@ __device__ __forceinline__ bool ModUnitRect(const FrameDev& f, uint32_t c, uint3
 // Entropy decode of one LF group by one wavefront (DecodeChannelCoop): three LF coefficient channels into the quantised LF planes, four
 // HF-metadata channels and the block count (scratch[1]) into the group's scratch.  What follows — chroma-from-luma maps, varblock
 // placement, block-info words — is LfPlaceKernel's, for this kernel's frames and the SIMT kernel's alike.
-__device__ __forceinline__ void LfDecodeGroup(const FrameDev& f, const uint32_t g, ModTables& T, int& s_fail, GroupHeaderD& s_gh, uint32_t* s_u) {
+// LOCAL (LfDecodeLocalKernel, one wavefront per workgroup): any of the three sub-streams may bring an MA tree and an entropy code of its own —
+// FrameDev::lf_local[3 g + k], k = 0 LF coefficients, 1 ModularLfGroup, 2 HF metadata, parsed on the host with the frame (host_parse.cc
+// ParseLfLocalStreams); T is staged afresh for every sub-stream.
+template <bool LOCAL = false>
+__device__ __forceinline__ void LfDecodeGroup(const FrameDev& f, const uint32_t g, ModTables& T, int& s_fail, GroupHeaderD& s_gh, uint32_t* s_u,
+                                              uint32_t tree_cap = 0, uint32_t lds_bytes = 0, uint32_t wp_base = 0) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t gx = g % f.xlfgroups, gy = g / f.xlfgroups;
   const uint32_t bx0 = gx * 256, by0 = gy * 256;
@@ -2186,7 +2191,33 @@ __device__ __forceinline__ void LfDecodeGroup(const FrameDev& f, const uint32_t 
   // HF metadata — use it one after the other
   __shared__ Lz77State s_lz[kLfDecWaves];
   Lz77State& lz = s_lz[(threadIdx.x >> 6) % kLfDecWaves];
-  if (f.mod_code.lz77) {
+  const ModLocalDev* const lf_loc = LOCAL ? f.lf_local + 3 * (size_t)g : nullptr;
+  // LOCAL: lane 0 after reading sub-stream k's GroupHeader — where its data starts (past its own tree and code) and its code
+  auto local_header = [&](int k, BitReader& tmp) -> const DevCode* {
+    if (!s_gh.use_global_tree) {
+      if (!lf_loc[k].tree) { SetError(f, kErrUnsupported); s_fail = 1; return nullptr; }   // (a tree the host has not parsed)
+      br.Init(f.cs, lf_loc[k].data_bitpos, f.single_section ? f.cs_size : f.sec_off[1 + g] + f.sec_size[1 + g]);
+      return &lf_loc[k].code;
+    }
+    if (!f.tree) { SetError(f, kErrUnsupported); s_fail = 1; return nullptr; }
+    br.Init(f.cs, tmp.BitPos(), f.single_section ? f.cs_size : f.sec_off[1 + g] + f.sec_size[1 + g]);
+    return &f.mod_code;
+  };
+  // LOCAL: every lane, once the GroupHeader is in s_gh — the sub-stream's tree and code into the LDS and into mc
+  auto local_stage = [&](int k) {
+    const ModLocalDev* L = s_gh.use_global_tree ? nullptr : &lf_loc[k];
+    const DevCode& cd = L ? L->code : f.mod_code;
+    __syncthreads();                           // (one wavefront per workgroup: the previous sub-stream is done with the LDS)
+    StageModular(L ? L->tree : f.tree, L ? L->tree_nodes : f.tree_nodes, cd, T, tree_cap, lds_bytes);
+    if (wp_base) T.wp_off = wp_base;
+    mc.tree = L ? L->tree : f.tree; mc.code = &cd; mc.uses_wp = L ? L->uses_wp : f.uses_wp;
+    mc.slow = cd.use_prefix || cd.lz77;
+    mc.lz = cd.lz77 ? &lz : nullptr;
+  };
+  if (LOCAL) {
+    if (!f.lz_window && f.lf_lz77) { if (lane == 0) SetError(f, kErrUnsupported); return; }
+    if (lane == 0 && f.lf_lz77) lz.window = f.lz_window + (uint64_t)(f.lz_lf_base + g) * Lz77State::kWindow;
+  } else if (f.mod_code.lz77) {
     if (!f.lz_window) { if (lane == 0) SetError(f, kErrUnsupported); return; }
     if (lane == 0) lz.Init(f.lz_window + (uint64_t)(f.lz_lf_base + g) * Lz77State::kWindow, gbw);   // dist_multiplier: the widest channel of the stream (modular/encoding/encoding.cc)
     mc.lz = &lz;
@@ -2222,9 +2253,16 @@ __device__ __forceinline__ void LfDecodeGroup(const FrameDev& f, const uint32_t 
     s_u[0] = br.Read(2);  // extra_precision
     BitReader tmp;        // GroupHeader parsing reuses the generic reader type: re-sync positions around it
     tmp.Init(f.cs, br.BitPos(), f.cs_size);
+    if (LOCAL) {
+      const DevCode* cd = nullptr;
+      if (!ReadGroupHeader(tmp, s_gh) || s_gh.ntransforms != 0) { SetError(f, kErrUnsupported); s_fail = 1; }
+      else cd = local_header(0, tmp);
+      if (cd) state = cd->use_prefix ? 0x130000u : br.Read(32);
+    } else {
     if (!ReadGroupHeader(tmp, s_gh) || !s_gh.use_global_tree || s_gh.ntransforms != 0) { SetError(f, kErrUnsupported); s_fail = 1; }
     br.Init(f.cs, tmp.BitPos(), sec_end);
     state = f.mod_code.use_prefix ? 0x130000u : br.Read(32);     // (prefix codes carry no ANS state)
+    }
     scratch[0] = (int32_t)s_u[0];
     scratch[1] = 0;
   }
@@ -2232,6 +2270,11 @@ __device__ __forceinline__ void LfDecodeGroup(const FrameDev& f, const uint32_t 
   WaveSync();
   if (s_fail) return;
   mc.wp = s_gh.wp; mc.stream_id = 1 + g;
+  if (LOCAL && has_lf) {
+    local_stage(0);
+    if (mc.lz && lane == 0) lz.Init(lz.window, gbw);
+    WaveSync();
+  }
   if (has_lf) {
     const int chan_to_plane[3] = {1, 0, 2};  // stream channel order is Y, X, B
     for (int c = 0; c < 3; c++) {
@@ -2255,14 +2298,22 @@ __device__ __forceinline__ void LfDecodeGroup(const FrameDev& f, const uint32_t 
         if (has_lf && state != 0x130000u) { SetError(f, kErrAnsFinalState); s_fail = 1; }
         BitReader tmp;
         tmp.Init(f.cs, br.BitPos(), f.cs_size);
+        if (LOCAL) {
+          const DevCode* cd = nullptr;
+          if (!s_fail && (!ReadGroupHeader(tmp, s_gh) || s_gh.ntransforms != 0 || (with_refs && nch_lf > 4))) { SetError(f, kErrUnsupported); s_fail = 1; }
+          else if (!s_fail) cd = local_header(1, tmp);
+          if (cd) state = cd->use_prefix ? 0x130000u : br.Read(32);
+        } else {
         if (!ReadGroupHeader(tmp, s_gh) || !s_gh.use_global_tree || s_gh.ntransforms != 0 || (with_refs && nch_lf > 4)) { SetError(f, kErrUnsupported); s_fail = 1; }
         br.Init(f.cs, tmp.BitPos(), sec_end);
         state = f.mod_code.use_prefix ? 0x130000u : br.Read(32);
+        }
       }
       WaveSync();
       if (s_fail) return;
       mc.wp = s_gh.wp; mc.stream_id = 1 + f.num_lf_groups + g;
-      if (f.mod_code.lz77 && lane == 0) lz.Init(lz.window, widest);
+      if (LOCAL) local_stage(1);
+      if ((LOCAL ? mc.lz != nullptr : f.mod_code.lz77) && lane == 0) lz.Init(lz.window, widest);
       WaveSync();
       int k = 0;
       for (uint32_t c = first_c; c < f.mod_nchan; c++) if (ModUnitRect(f, c, px0, py0, 2048, 3, 1000, &d)) {
@@ -2278,15 +2329,23 @@ __device__ __forceinline__ void LfDecodeGroup(const FrameDev& f, const uint32_t 
     s_u[1] = 1 + br.Read(CeilLog2D(gbw * gbh));
     BitReader tmp;
     tmp.Init(f.cs, br.BitPos(), f.cs_size);
+    if (LOCAL) {
+      const DevCode* cd = nullptr;
+      if (!s_fail && (!ReadGroupHeader(tmp, s_gh) || s_gh.ntransforms != 0)) { SetError(f, kErrUnsupported); s_fail = 1; }
+      else if (!s_fail) cd = local_header(2, tmp);
+      if (cd) state = cd->use_prefix ? 0x130000u : br.Read(32);
+    } else {
     if (!ReadGroupHeader(tmp, s_gh) || !s_gh.use_global_tree || s_gh.ntransforms != 0) { SetError(f, kErrUnsupported); s_fail = 1; }
     br.Init(f.cs, tmp.BitPos(), sec_end);
     state = f.mod_code.use_prefix ? 0x130000u : br.Read(32);
+    }
   }
   WaveSync();
   if (s_fail) return;
   const uint32_t nb_blocks = s_u[1];
   const uint32_t mcw = (gbw + 7) / 8, mch = (gbh + 7) / 8;
-  if (f.mod_code.lz77 && lane == 0) lz.Init(lz.window, max(max(nb_blocks, gbw), mcw));
+  if (LOCAL) local_stage(2);
+  if ((LOCAL ? mc.lz != nullptr : f.mod_code.lz77) && lane == 0) lz.Init(lz.window, max(max(nb_blocks, gbw), mcw));
   WaveSync();
   int32_t* m_ytox = scratch + 16;
   int32_t* m_ytob = m_ytox + mcw * mch;
@@ -2570,7 +2629,7 @@ __global__ __launch_bounds__(256) void LfPlaceExpandKernel(const FrameDev* __res
 // variant for large pipelined batches; single images take the uncapped one (267 VGPRs, LF stage 20 % shorter).
 template <bool CAPPED> __global__ __launch_bounds__(64 * kLfDecWaves, CAPPED ? JXL_LF_MINW : 1) void LfDecodeKernel(const FrameDev* __restrict__ frames, uint32_t groups_per_block, uint32_t tree_cap, uint32_t lds_bytes, int take_simt_frames, uint32_t wp_base) {
   const FrameDev& f = frames[blockIdx.y];
-  if (f.is_modular || (f.lf_simt && !take_simt_frames)) return;
+  if (f.is_modular || (f.lf_simt && !take_simt_frames) || f.lf_local) return;   // (lf_local: LfDecodeLocalKernel's)
   const uint32_t first = blockIdx.x * groups_per_block;
   if (first >= f.num_lf_groups) return;
   // take_simt_frames 2: of the SIMT kernel's frames only the streams it handed back (lf_scratch[2] == kLfRedoMark: values outside the range of its
@@ -2594,6 +2653,19 @@ template <bool CAPPED> __global__ __launch_bounds__(64 * kLfDecWaves, CAPPED ? J
     if (redo_only && LdG(f.lf_scratch + (uint64_t)(first + local) * f.lf_scratch_stride + 2) != kLfRedoMark) continue;
     LfDecodeGroup(f, first + local, T, s_fail_w[wave], s_gh_w[wave], s_u_w[wave]);
   }
+}
+
+// LfGroup sub-streams with MA trees / entropy codes of their own (FrameDev::lf_local): one LF group per workgroup of one wavefront, which stages
+// the tables of each sub-stream as it reaches it (dynamic LDS planned as for ModularGroupFastKernel's local pass; a code over the budget is read
+// through the L2).  Writes what LfDecodeKernel writes; placement follows in the same kernels.
+__global__ __launch_bounds__(64) void LfDecodeLocalKernel(const FrameDev* __restrict__ frames, uint32_t tree_cap, uint32_t lds_bytes, uint32_t wp_base) {
+  const FrameDev& f = frames[blockIdx.y];
+  if (f.is_modular || !f.lf_local || blockIdx.x >= f.num_lf_groups) return;
+  ModTables T;
+  __shared__ int s_fail;
+  __shared__ GroupHeaderD s_gh;
+  __shared__ uint32_t s_u[4];
+  LfDecodeGroup<true>(f, blockIdx.x, T, s_fail, s_gh, s_u, tree_cap, lds_bytes, wp_base);
 }
 
 // =====================================================================================================================
@@ -6060,10 +6132,19 @@ static const uint32_t* WpDivTable() {
   }
   return table[dev];
 }
+static void PlanModularLds(const LaunchCfg& cfg, uint32_t* nwaves_io, uint32_t* tree_cap, uint32_t* lds_tables, uint32_t* wp_base, uint32_t* lds_total);
 void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, const LaunchCfg& cfg, void* stream, const LfSimtPlan* simt, LaunchTrace* trace) {
   LaunchTrace tr;
   if (!trace) trace = &tr;
   trace->lf_variant = 0; trace->lf_wide_bytes = 0; trace->lf_wide_only = 0;
+  if (cfg.any_local_lf) {   // frames whose LfGroup sub-streams bring their own trees / codes: one wavefront per LF group, each staging its tables
+    uint32_t nwaves = 1, tree_cap, lds_tables, wp_base, lds_bytes;
+    PlanModularLds(cfg, &nwaves, &tree_cap, &lds_tables, &wp_base, &lds_bytes);
+    static bool attr_set = false;
+    if (!attr_set) { SetMaxDynamicLds((const void*)LfDecodeLocalKernel, 160 * 1024 - 8192, "LfDecodeLocalKernel"); attr_set = true; }
+    hipLaunchKernelGGL(LfDecodeLocalKernel, dim3(max_lf_groups, nframes), dim3(64), lds_bytes, (hipStream_t)stream, frames, tree_cap, lds_tables, wp_base);
+    trace->lf_variant |= kLfVarLocal;
+  }
   static const bool time_it = getenv("JXL_HIP_TIME_LF") != nullptr;     // experiments: blocking per-kernel times on stderr
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   if (time_it) { for (auto& e : ev) (void)hipEventCreate(&e); (void)hipEventRecord(ev[0], (hipStream_t)stream); }

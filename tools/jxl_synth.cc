@@ -210,8 +210,14 @@ static WpParams LfWpParams() {
   if (LfTreeShape() == 2) { q.p1 = 20; q.p2 = 8; const int p3[5] = {5, 9, 6, 3, 2}; const uint32_t wm[4] = {10, 14, 9, 13}; for (int i = 0; i < 5; i++) q.p3[i] = p3[i]; for (int i = 0; i < 4; i++) q.wmax[i] = wm[i]; }
   return q;
 }
-static void WriteGroupHeaderLf(BitWriter& s) {     // GroupHeader of an LfGroup sub-stream: global tree, predictor parameters, no transforms
-  s.put(1, 1);
+// VardctLocalTrees() (jxlsynth_set_vardct_local_trees): which Modular sub-streams of a VarDCT frame bring an MA tree and an entropy code of their own
+// (GroupHeader.use_global_tree = 0).  0: none; 1: the LF coefficient and HF metadata streams of every LF group, the global tree for the rest;
+// 2: no global tree at all, every sub-stream carries its own; 3: a global tree is written, but every sub-stream (GlobalModular, LF coefficients,
+// ModularLfGroup, HF metadata, PassGroup extra-channel tails) carries its own.  The local tree is the global one written again, so the tokens —
+// and the quantised data — are those of mode 0; only the entropy coding of each stream changes.
+inline int& VardctLocalTrees() { static thread_local int v = 0; return v; }
+static void WriteGroupHeaderLf(BitWriter& s, bool global_tree = true) {     // GroupHeader of an LfGroup sub-stream: global tree (or not), predictor parameters, no transforms
+  s.put(global_tree ? 1 : 0, 1);
   if (LfTreeShape() == 2) {
     const WpParams q = LfWpParams();
     s.put(0, 1); s.put(q.p1, 5); s.put(q.p2, 5);
@@ -1277,6 +1283,33 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
     s.push_back(&alpha_global_tok); for (auto& t : alpha_tok) s.push_back(&t); for (auto& t : alpha_lf_tok) s.push_back(&t);
     BuildEntropyCoder(s, gt.num_leaves + (lz77_lf ? 1 : 0), UintConfig{4, 2, 0}, 32, mod_code, &LfCodeShape());
     if (lz77_lf) { mod_code.lz77 = true; mod_code.lz_min_symbol = 224; mod_code.lz_min_length = 3; mod_code.lz_len_cfg = UintConfig{3, 0, 0}; } }
+  // streams with a tree and code of their own (VardctLocalTrees): the global tree written again, then a code over the stream's tokens alone; the
+  // code's shape rotates over the streams written — ANS, a prefix code, ANS with LZ77 where `lz_ok` (the HF metadata streams, which end their LfGroup
+  // section; dist: LZ77 distance multiplier, as the global code uses it)
+  const int local_mode = VardctLocalTrees();
+  const bool local_lf = local_mode >= 1, local_rest = local_mode >= 2, global_tree = local_mode != 2;
+  int local_count = 0;
+  auto write_local = [&](BitWriter& s, const std::vector<Token>& tok, size_t dist, bool lz_ok) {
+    WriteEntropyCode(s, tree_code);
+    EncodeTokens(s, tree_code, tree_tokens);
+    const int variant = local_count++ % 3;
+    const bool lz = lz77_lf || (variant == 2 && lz_ok);
+    std::vector<Token> t = tok;
+    EntropyCoder ec;
+    if (lz && !lz77_lf) {
+      EntropyCoder proto;
+      proto.lz_min_symbol = 224; proto.lz_min_length = 3; proto.lz_len_cfg = UintConfig{3, 0, 0};
+      ApplyLz77(t, (uint32_t)gt.num_leaves, proto, dist);
+    }
+    const bool outer_prefix = UsePrefixCodes();
+    if (variant == 1 && !lz) UsePrefixCodes() = true;
+    std::vector<const std::vector<Token>*> st{&t};
+    BuildEntropyCoder(st, gt.num_leaves + (lz ? 1 : 0), UintConfig{4, 2, 0}, 32, ec);
+    UsePrefixCodes() = outer_prefix;
+    if (lz) { ec.lz77 = true; ec.lz_min_symbol = 224; ec.lz_min_length = 3; ec.lz_len_cfg = UintConfig{3, 0, 0}; }
+    WriteEntropyCode(s, ec);
+    EncodeTokens(s, ec, t);
+  };
   const bool lz77_ac = UseLz77Ac();
   const int npresets = std::max(1, std::min(HfPresets(), ngroups));
   for (int ps = 0; ps < np; ps++) {
@@ -1319,15 +1352,18 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
       WriteF16(s, cfl_base_x); WriteF16(s, cfl_base_b);
       s.put((uint32_t)(cfl_x_lf + 128), 8); s.put((uint32_t)(cfl_b_lf + 128), 8);
     }
-    s.put(1, 1);  // GlobalModular: has_tree
-    WriteEntropyCode(s, tree_code);
-    EncodeTokens(s, tree_code, tree_tokens);
-    WriteEntropyCode(s, mod_code);
+    s.put(global_tree ? 1 : 0, 1);  // GlobalModular: has_tree
+    if (global_tree) {
+      WriteEntropyCode(s, tree_code);
+      EncodeTokens(s, tree_code, tree_tokens);
+      WriteEntropyCode(s, mod_code);
+    }
     if (alpha) {  // the global Modular image has a channel: GroupHeader + whatever is decodable globally
-      s.put(1, 1); s.put(1, 1);
+      s.put(local_rest ? 0 : 1, 1); s.put(1, 1);
       if (alpha_sq) { s.put(1, 2); s.put(2, 2); WriteU32(s, 0, {0, 0}, {4, 1}, {6, 9}, {8, 41}); }    // one transform: Squeeze with the default chain (zero explicit steps)
       else s.put(0, 2);
-      EncodeTokens(s, mod_code, alpha_global_tok);
+      if (local_rest) write_local(s, alpha_global_tok, 0, false);
+      else EncodeTokens(s, mod_code, alpha_global_tok);
     }
     sections.push_back(s);
   }
@@ -1336,14 +1372,20 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
     LfGroupData& d = lgd[g];
     if (!p.use_lf_frame) {
       s.put((uint32_t)LfExtraPrecision(), 2);  // extra_precision
-      WriteGroupHeaderLf(s);
-      EncodeTokens(s, mod_code, d.lf_tok);
+      WriteGroupHeaderLf(s, !local_lf);
+      if (local_lf) write_local(s, d.lf_tok, (size_t)d.gbw, false);
+      else EncodeTokens(s, mod_code, d.lf_tok);
     }
     // ModularLfGroup: the extra channel's sub-channels squeezed by >= 3 in both directions (none without Squeeze: nothing is written then)
-    if (alpha_sq && alpha_lf_has[g]) { s.put(1, 1); s.put(1, 1); s.put(0, 2); EncodeTokens(s, mod_code, alpha_lf_tok[g]); }
+    if (alpha_sq && alpha_lf_has[g]) {
+      s.put(local_rest ? 0 : 1, 1); s.put(1, 1); s.put(0, 2);
+      if (local_rest) write_local(s, alpha_lf_tok[g], 0, false);
+      else EncodeTokens(s, mod_code, alpha_lf_tok[g]);
+    }
     s.put(d.nb - 1, CeilLog2((uint32_t)(d.gbw * d.gbh)));
-    WriteGroupHeaderLf(s);
-    EncodeTokens(s, mod_code, d.meta_tok);
+    WriteGroupHeaderLf(s, !local_lf);
+    if (local_lf) write_local(s, d.meta_tok, 0, true);
+    else EncodeTokens(s, mod_code, d.meta_tok);
     sections.push_back(s);
   }
   {  // HfGlobal
@@ -1381,7 +1423,9 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
     // downsampling entries in the pass whose bracket holds their shift — behind that pass's coefficients
     const int k = ps - (np - sq_passes);
     if (alpha && (alpha_sq || !alpha_global) && k >= 0 && alpha_has[(size_t)k * ngroups + g]) {
-      s.put(1, 1); s.put(1, 1); s.put(0, 2); EncodeTokens(s, mod_code, alpha_tok[(size_t)k * ngroups + g]);
+      s.put(local_rest ? 0 : 1, 1); s.put(1, 1); s.put(0, 2);
+      if (local_rest) write_local(s, alpha_tok[(size_t)k * ngroups + g], 0, false);
+      else EncodeTokens(s, mod_code, alpha_tok[(size_t)k * ngroups + g]);
     }
     sections.push_back(s);
   }
@@ -1660,6 +1704,7 @@ void jxlsynth_set_custom_filters(int on) { synth::CustomFilters() = on != 0; }
 void jxlsynth_set_modular_group_shift(int shift) { synth::ModularGroupShift() = shift < 0 || shift > 3 ? 1 : shift; }
 void jxlsynth_set_prev_channel_props(int on) { synth::UsePrevChannelProps() = on != 0; }
 void jxlsynth_set_lf_tree_shape(int shape) { synth::LfTreeShape() = shape; }
+void jxlsynth_set_vardct_local_trees(int mode) { synth::VardctLocalTrees() = mode < 0 || mode > 3 ? 0 : mode; }
 // entropy-code shape of the codes written from now on in this thread (synth::CodeShape): which bit 0 = the AC codes, bit 1 = the global-tree Modular codes;
 // cfgs: ncfg triples {split_exponent (-1: = log_alpha), msb_in_token, lsb_in_token}.  Zeros / ncfg 0: the synthesiser's own shape again
 void jxlsynth_set_code_shape(int which, int min_clusters, int max_clusters, int min_log_alpha, const int32_t* cfgs, int ncfg, uint32_t seed) {

@@ -941,6 +941,7 @@ __device__ __forceinline__ void WaveSegment(WaveBits& bits, uint32_t& state, int
   const uint32_t sh = 12 - la;
   int32_t cur = curv;
   int32_t val_prev = 0; int xl_prev = -1;
+  const int32_t nwvec = (int32_t)((uint32_t)prevv - (uint32_t)dvec);      // NW of the segment's samples
   for (int xl = 0; xl < n; xl++) {
     // [A] alias reads
     const uint32_t slot = (state & 0xFFF) >> sh;
@@ -965,11 +966,12 @@ __device__ __forceinline__ void WaveSegment(WaveBits& bits, uint32_t& state, int
       k = __builtin_ctzll(__ballot((d & wc.lmask) == wc.lwant) | (1ull << 63));
     }
     int32_t grad = W;
-    if (NEEDN && (UPRED == 5 || UPRED == -2)) {      // clamped gradient = median(N, W, W + N - NW)
+    if (NEEDN && (UPRED == 5 || UPRED == -2)) {      // clamped gradient
       const int32_t N = __builtin_amdgcn_readlane(prevv, xl);
       const int32_t g0 = V0GRAD ? v0 : (int32_t)((uint32_t)W + (uint32_t)__builtin_amdgcn_readlane(dvec, xl));
+      const int32_t NW = __builtin_amdgcn_readlane(nwvec, xl);
       const int32_t m = min(N, W), M = max(N, W);
-      grad = max(m, min(M, g0));
+      grad = NW < m ? M : (NW > M ? m : g0);      // (not median(N, W, g0): g0 wraps around for samples near 2^31 — float bit patterns — and the sum only counts when NW lies between N and W)
     }
     int32_t guess;
     if (UPRED == 0) guess = 0;
@@ -1316,7 +1318,7 @@ __device__ __forceinline__ void WaveGenSample(WaveBits& bits, uint32_t& state, W
     while ((int32_t)Uniform(nd.x) >= 0) { at = LdS<uint32_t>(at); nd = LdS<uint4>(BG.node_base + (at - BG.next_off) * 4); }      // (paths longer than 12)
     const uint32_t leaf = Uniform(nd.z), pk = leaf & 0xFF, cl = leaf >> 8;
     const int32_t m = min(N, W), M = max(N, W);
-    const int32_t grad = max(m, min(M, pv[0]));
+    const int32_t grad = NW < m ? M : (NW > M ? m : pv[0]);      // (pv[0] wraps around for samples near 2^31: compare NW, as ClampedGradient does)
     guess = pk == 6 ? wpguess : (pk == 5 ? grad : (pk == 1 ? W : 0));
     const uint32_t cfg = wc.cfg_uniform != 0xFFFFFFFFu ? wc.cfg_uniform : Uniform(LdS<uint32_t>(wc.cfg_off + 4 * cl));
     v = WaveTokenAt(bits, state, BG.wide_off + ((cl << la) << 3), BG.cut_off + ((cl << la) << 1), cfg, la).v;
@@ -1333,7 +1335,7 @@ __device__ __forceinline__ void WaveGenSample(WaveBits& bits, uint32_t& state, W
     const uint32_t dlo = (uint32_t)d, dhi = (uint32_t)(d >> 32);
     k = __builtin_ctzll(__ballot((dlo & G.mlo) == G.wlo && (dhi & G.mhi) == G.whi) | (1ull << 63));
     const int32_t m = min(N, W), M = max(N, W);
-    const int32_t grad = max(m, min(M, (int32_t)((uint32_t)W + (uint32_t)N - (uint32_t)NW)));
+    const int32_t grad = NW < m ? M : (NW > M ? m : (int32_t)((uint32_t)W + (uint32_t)N - (uint32_t)NW));
     guess = __builtin_amdgcn_readlane(G.is6 ? wpguess : (G.is5 ? grad : (G.is1 ? W : 0)), k);
   }
   // --- ANS symbol

@@ -367,6 +367,12 @@ def set_float(exp_bits=0):
     L.jxlsynth_set_float(int(exp_bits))
 
 
+def set_orientation(o=1):
+    """EXIF-style orientation (1..8) of the image headers written from now on by every encoder (encode_modular, encode_modular_frame,
+    encode_vardct_frame, encode_ycbcr; encode_vardct's own argument wins when it is not 1); call without arguments to go back to 1."""
+    lib().jxlsynth_set_orientation(int(o))
+
+
 def set_spot(rgba=None):
     """The extra channel of the images written from now on is a spot colour (r, g, b, solidity — half-float precision) instead of alpha;
     call without arguments to go back to alpha."""

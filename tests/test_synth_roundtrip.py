@@ -104,6 +104,26 @@ def test_alpha_passes_permuted_toc_and_orientation_streams():
     assert d.info.orientation == 6 and (d.info.xsize, d.info.ysize) == (600, 400)    # the oracle reports the stored raster
 
 
+def test_set_orientation_reaches_streams_without_an_argument_of_their_own():
+    """S.set_orientation: the image header of a Modular stream (plain and frame-controlled) carries the orientation; the samples are the stored raster, untouched"""
+    rng = np.random.default_rng(7)
+    img = rng.integers(0, 256, (37, 53, 4)).astype(np.int32)
+    plain = S.encode_modular(img, 8, False, 0)
+    for o in (1, 5, 8):
+        S.set_orientation(o)
+        try:
+            streams = [S.encode_modular(img, 8, False, 0), S.encode_modular_frame(img, S.frame(), bits=8)]
+            vardct = S.encode_vardct(S.synthetic_image(3, 64, 40), seed=3, orientation=3)
+        finally:
+            S.set_orientation()
+        for data in streams:
+            d = O.decode(data)
+            assert d.info.orientation == o and (d.info.xsize, d.info.ysize) == (53, 37)
+            assert np.array_equal(d.image("u8", 4), img)
+        assert O.decode(vardct).info.orientation == 3                                # encode_vardct's own argument wins
+    assert S.encode_modular(img, 8, False, 0) == plain and O.decode(plain).info.orientation == 1      # and the setting is gone afterwards
+
+
 @pytest.mark.parametrize("up,custom,floor", [(2, 0, 33.0), (2, 1, 33.0), (4, 1, 28.0), (8, 1, 23.0)])
 def test_upsampled_streams_roundtrip(up, custom, floor):
     img = S.synthetic_image(62, 333, 201)

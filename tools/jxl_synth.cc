@@ -477,6 +477,7 @@ static thread_local ColorOverride g_color;
 static thread_local bool g_spot_set = false;          // the image's extra channel is a spot colour (jxlsynth_set_spot) instead of alpha
 static thread_local float g_spot[4] = {0, 0, 0, 0};   // its colour and solidity
 static thread_local int g_float_exp_bits = 0;     // != 0: the image's samples are floats with this many exponent bits (jxlsynth_set_float)
+static thread_local int g_orientation = 1;        // orientation of the image headers whose Params leave it at 1 (jxlsynth_set_orientation)
 static void IccVarint(std::vector<uint8_t>& v, uint64_t x) { while (x > 127) { v.push_back((uint8_t)(x | 128)); x >>= 7; } v.push_back((uint8_t)x); }
 static std::vector<uint8_t> IccShuffleFwd(const std::vector<uint8_t>& in, size_t width) {   // decoder: out[i] = in[j], j walking columns
   const size_t n = in.size(), rows = (n + width - 1) / width;
@@ -610,7 +611,9 @@ static void WritePreviewSize(BitWriter& w, int xs, int ys) {
 // XYB images written from now on (this thread) carry their own OpsinInverseMatrix bundle: the library's matrix, opsin biases and quantisation biases as binary16 values
 // (so a decoder that reads them computes with slightly different numbers than one that falls back to its defaults)
 static bool& CustomOpsin() { static thread_local bool v = false; return v; }
-static void WriteImageHeader(BitWriter& w, int xs, int ys, const Params& p, bool xyb, int bits, bool has_alpha, bool gray) {
+static void WriteImageHeader(BitWriter& w, int xs, int ys, const Params& pin, bool xyb, int bits, bool has_alpha, bool gray) {
+  Params p = pin;
+  if (p.orientation == 1) p.orientation = g_orientation;     // (every encoder entry point: Modular, frame-controlled and YCbCr streams have no argument of their own)
   w.put(0xFF, 8); w.put(0x0A, 8);
   WriteSize(w, xs, ys);
   const bool custom_opsin = xyb && CustomOpsin();
@@ -1686,6 +1689,8 @@ void jxlsynth_image(uint32_t seed, int w, int h, uint8_t* rgb) { synth::Syntheti
 // ICC profile embedded by the image headers written from now on in this thread (size 0: none, enumerated colour encoding)
 void jxlsynth_set_icc(const uint8_t* icc, size_t size) { synth::g_icc.assign(icc, icc + size); }
 void jxlsynth_set_float(int exp_bits) { synth::g_float_exp_bits = exp_bits; }
+// EXIF-style orientation (1..8) of the image headers written from now on in this thread, whichever encoder writes them
+void jxlsynth_set_orientation(int o) { synth::g_orientation = o >= 1 && o <= 8 ? o : 1; }
 // entropy-coded streams written from now on in this thread use prefix (Huffman) codes instead of ANS — what cjxl's fast efforts emit
 void jxlsynth_set_animation(int tps_num, int tps_den, int loops) { synth::g_anim_num = tps_num; synth::g_anim_den = tps_den > 0 ? tps_den : 1; synth::g_anim_loops = loops; }
 void jxlsynth_set_preview(int w, int h) { synth::g_preview_w = w; synth::g_preview_h = h; }

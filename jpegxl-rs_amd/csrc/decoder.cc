@@ -2,6 +2,7 @@
 #include "decoder.h"
 #include <atomic>
 #include <exception>
+#include <deque>
 #include <mutex>
 #include <thread>
 #include <chrono>
@@ -646,7 +647,6 @@ void Batch::DecodePreview(int i, const OutputSpec& o, void* dst, size_t cap, voi
   if (u->plan.frame_type != 0 || u->plan.use_lf_frame) throw ParseError("the preview must be a regular frame", false);
   u->plan.is_last = true;                              // (whatever the frame says: nothing of the image follows it as far as the preview goes)
   CheckFrameSupported(u->plan, sh->ih);
-  if (sh->ih.extra.size() > 4) throw ParseError("unsupported: more than 4 extra channels in a preview", true);
   Batch tmp(device_);
   ParsedImage pi; pi.complex = true; pi.units.push_back(std::move(u));
   tmp.Append(std::move(pi));
@@ -711,7 +711,6 @@ void Batch::ParseImage(const uint8_t* data, size_t size, ParsedImage* out, bool 
     bitpos = p.frame_end_bitpos;
     if (p.frame_type == 1) {              // an LF frame: kept aside for the frames that refer to it (decoded by Batch::lf_batch_), never displayed
       // (every frame carries the image's extra channels, an LF frame too — libjxl's encoder fills them with zeros there; they are decoded with the frame and not looked at)
-      if (ih.extra.size() > 4) throw ParseError("unsupported: LF frame of an image with more than 4 extra channels", true);
       lf_frames[p.lf_level] = std::shared_ptr<ImageEntry>(e.release());
       continue;
     }
@@ -729,7 +728,6 @@ void Batch::ParseImage(const uint8_t* data, size_t size, ParsedImage* out, bool 
     // (chroma-subsampled frames without anything else: OutputKernel upsamples the chroma planes as it reads them; in the frame tail of complex images ChromaUpsampleKernel does)
   }
   for (auto& x : ih.extra) if (x.depth.is_float) complex = true;   // float extra channels are converted in the frame tail (IntToFloatSample)
-  if (complex && ih.extra.size() > 4) throw ParseError("unsupported: more than 4 extra channels in a multi-frame / feature image", true);
   for (auto& u : units) { u->complex = complex; u->preview_bitpos = preview_bitpos; }
   out->units = std::move(units);
   out->complex = complex;
@@ -959,16 +957,13 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     if (spot && first.out.render_spotcolors) {
       // stage_spot.cc runs in the frame tail; grey images keep one colour plane there (not handled)
       if (first.ih.color_space == 1) throw ParseError("unsupported: spot colours on a grey image", true);
-      if (first.ih.extra.size() > 4) throw ParseError("unsupported: more than 4 extra channels with spot colours", true);
       if (!pi.complex) { pi.complex = true; for (int u = pi.first_unit; u < pi.first_unit + pi.num_units; u++) images_[u]->complex = true; }
     }
     if (first.out.only_frame >= 0 && !pi.complex) {     // a single frame as coded: written by the frame tail (its own size, no blending)
-      if (first.ih.extra.size() > 4) throw ParseError("unsupported: more than 4 extra channels with non-coalesced output", true);
       pi.complex = true;
       for (int u = pi.first_unit; u < pi.first_unit + pi.num_units; u++) images_[u]->complex = true;
     }
     if (first.out.unpremul_alpha && premul && !pi.complex) {
-      if (first.ih.extra.size() > 4) throw ParseError("unsupported: more than 4 extra channels with un-premultiplied output", true);
       pi.complex = true;
       for (int u = pi.first_unit; u < pi.first_unit + pi.num_units; u++) images_[u]->complex = true;
     }
@@ -1071,7 +1066,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
   mod_plane_offsets_.assign(n, {});
   mod_ops_.assign(n, {});
   cbufs_.assign(n, ComplexBufs());
-  for (auto& cb : cbufs_) for (size_t* a : {cb.ecf, cb.up_ec, cb.canvas_ec}) for (int k = 0; k < 4; k++) a[k] = (size_t)-1;
+  for (int i = 0; i < n; i++) for (vec<size_t>* a : {&cbufs_[i].ecf, &cbufs_[i].up_ec, &cbufs_[i].canvas_ec}) a->assign(images_[i]->ih.extra.size(), (size_t)-1);
   for (auto& cb : cbufs_) for (size_t* a : {cb.up, cb.noise, cb.rgb, cb.canvas, cb.pa, cb.pb, cb.color_int}) for (int k = 0; k < 3; k++) a[k] = (size_t)-1;
   post_ops_.clear(); any_complex_ = false;
   vardct_alpha_.assign(n, VarDctAlpha());
@@ -1188,6 +1183,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       for (size_t k = 0; k < ne; k++) cb.ecf[k] = take_big(coded);
       if (p.upsampling > 1) { for (int c = 0; c < 3; c++) cb.up[c] = take_big(full); for (size_t k = 0; k < ne; k++) cb.up_ec[k] = take_big(full); }
       if (p.feat.has_noise) for (int c = 0; c < 3; c++) cb.noise[c] = take_big(full);
+      if (ne > 4 && (p.flags & 2)) for (size_t k = 0; k < ne; k++) cb.ec_tmp.push_back(take_big(coded));
       const bool can_ref = !p.is_last && p.frame_type != 1 && (p.duration == 0 || p.save_as_reference != 0);
       bool replace_all = p.blend.mode == 0;
       for (auto& b : p.ec_blend) if (b.mode != 0) replace_all = false;
@@ -1902,8 +1898,12 @@ void Batch::PlanModularUndo(int i, const std::function<size_t(size_t)>& take) {
 // save as reference | write).  Reference slots are tracked here (frame_header.cc save_as_reference / CanBeReferenced).
 void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
   Arena arena(hconst);
-  struct Slot { bool valid = false, before_ct = false; size_t p[3] = {0, 0, 0}; uint32_t stride = 0; size_t ec[4] = {0, 0, 0, 0}; uint32_t ec_stride = 0; uint32_t w = 0, h = 0; };
+  struct Slot { bool valid = false, before_ct = false; size_t p[3] = {0, 0, 0}; uint32_t stride = 0; vec<size_t> ec; uint32_t ec_stride = 0; uint32_t w = 0, h = 0; };
   auto B = [this](size_t off) { return (float*)(dbig_ + off); };
+  // channel tables of the frames with more than four extra channels (kernels.h EcChanDev): a frame's table takes its place in the constant arena when the frame's
+  // plan starts and is filled step by step; the finished tables are copied into the arena once every frame is planned (the end of this function)
+  struct PendingTable { size_t off; vec<EcChanDev> entries; };
+  std::deque<PendingTable> tables;
   for (const PubImage& pi : pub_) {
     if (!pi.complex) continue;
     Slot slots[4];
@@ -1911,7 +1911,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
     const ImageHeader& ih = first.ih;
     const uint32_t ne = (uint32_t)ih.extra.size();
     uint32_t premul_mask = 0;
-    for (uint32_t k = 0; k < ne; k++) if (ih.extra[k].alpha_associated) premul_mask |= 1u << k;
+    for (uint32_t k = 0; k < ne && ne <= 4; k++) if (ih.extra[k].alpha_associated) premul_mask |= 1u << k;   // (the inlined kernels' mask; the channel table carries the flag per entry)
     for (int u = pi.first_unit; u < pi.first_unit + pi.num_units; u++) {
       const ImageEntry& e = *images_[u];
       const FramePlan& p = e.plan;
@@ -1921,7 +1921,20 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
       const uint32_t nstages = p.modular ? 0 : (p.lf.gab ? 1 : 0) + (p.lf.epf_iters >= 3 ? 3 : p.lf.epf_iters);
       size_t cur[3]; uint32_t cur_stride = p.bw * 8;
       for (int c = 0; c < 3; c++) cur[c] = (nstages & 1) ? cb.pb[c] : cb.pa[c];
-      size_t cur_ec[4] = {0, 0, 0, 0}; uint32_t cur_ec_stride = cw;
+      vec<size_t> cur_ec(ne, 0); uint32_t cur_ec_stride = cw;
+      // more than four extra channels: the extra-channel steps below read a channel table in device memory (kernels.h EcChanDev) instead of pointers inlined
+      // into their argument blocks (`tables` above).
+      const bool tab = ne > 4;
+      vec<EcChanDev> no_table;
+      if (tab) {
+        tables.emplace_back();
+        tables.back().entries.resize(ne);
+        memset(tables.back().entries.data(), 0, ne * sizeof(EcChanDev));
+        tables.back().off = arena.Put(tables.back().entries.data(), ne * sizeof(EcChanDev));
+      }
+      vec<EcChanDev>& tbl = tab ? tables.back().entries : no_table;
+      const size_t o_tab = tab ? tables.back().off : 0;
+      auto DT = [this, o_tab]() { return (const EcChanDev*)(dconst_ + o_tab); };
       if (p.subsampled) {
         // the subsampled channels sit in the top-left corner of their planes: bring them to full resolution (plane b)
         for (int c = 0; c < 3; c++) {
@@ -1959,12 +1972,23 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         const bool efl = ih.extra[k].depth.is_float;
         const float factor = efl ? 1.0f : 1.0f / (float)((1u << ih.extra[k].depth.bits) - 1);
         const uint32_t ebits = efl ? ih.extra[k].depth.bits : 0, eexp = ih.extra[k].depth.exp_bits;
-        post_ops_.push_back([=](void* st) { LaunchIntToFloat((const int32_t*)(dwork_ + src), cw, B(dst), cw, cw, ch, factor, st, ebits, eexp); });
+        if (tab) {
+          EcChanDev& t = tbl[k];
+          t.src_int = (const int32_t*)(dwork_ + src); t.plane = B(dst); t.factor = factor; t.float_bits = ebits; t.float_exp_bits = eexp;
+          t.premul = ih.extra[k].alpha_associated ? 1 : 0; t.type = ih.extra[k].type;
+          for (int c = 0; c < 4; c++) t.spot[c] = ih.extra[k].spot[c];
+          t.fg = t.plane; t.fg_stride = cw;
+        } else post_ops_.push_back([=](void* st) { LaunchIntToFloat((const int32_t*)(dwork_ + src), cw, B(dst), cw, cw, ch, factor, st, ebits, eexp); });
         cur_ec[k] = dst;
       }
+      EcFrameArgs efa;
+      memset(&efa, 0, sizeof(efa));
+      efa.num_extra = ne; efa.w = cw; efa.h = ch; efa.ow = fw; efa.oh = fh; efa.up = p.upsampling;
+      if (tab) post_ops_.push_back([=](void* st) { EcFrameArgs a = efa; a.table = DT(); LaunchEcIntToFloat(a, st); });
       // ---- patches
       if (p.flags & 2) {
         vec<PatchEntryDev> entries;
+        vec<PatchEcDev> pec;        // channel-table form: [placement * ne + channel]
         for (const PatchRefH& pr : p.feat.patches) {
           const Slot& sl = slots[pr.ref];
           if (!sl.valid) throw ParseError("patch refers to an empty reference slot", false);
@@ -1976,10 +2000,18 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
             PatchEntryDev en;
             memset(&en, 0, sizeof(en));
             for (int c = 0; c < 3; c++) en.src[c] = B(sl.p[c]) + (size_t)pr.y0 * sl.stride + pr.x0;
-            for (uint32_t k = 0; k < ne; k++) en.esrc[k] = B(sl.ec[k]) + (size_t)pr.y0 * sl.ec_stride + pr.x0;
+            if (sl.ec.size() < ne) throw ParseError("patch source without the extra channels", false);
+            if (pp.blend.size() < 1 + ne) throw ParseError("patch blending list", false);
+            for (uint32_t k = 0; k < ne; k++) {
+              const float* esrc = B(sl.ec[k]) + (size_t)pr.y0 * sl.ec_stride + pr.x0;
+              const uint32_t mode = pp.blend[1 + k].mode | (pp.blend[1 + k].alpha_channel << 8) | (pp.blend[1 + k].clamp << 16);
+              if (pp.blend[1 + k].alpha_channel >= ne) throw ParseError("patch alpha channel", false);
+              if (tab) pec.push_back(PatchEcDev{esrc, mode, 0}); else { en.esrc[k] = esrc; en.mode[1 + k] = mode; }
+            }
+            if (ne && pp.blend[0].alpha_channel >= ne) throw ParseError("patch alpha channel", false);
             en.src_stride = sl.stride; en.esrc_stride = sl.ec_stride;
             en.x = (int32_t)pp.x; en.y = (int32_t)pp.y; en.xs = pr.xsize; en.ys = pr.ysize;
-            for (uint32_t k = 0; k < 1 + ne; k++) en.mode[k] = pp.blend[k].mode | (pp.blend[k].alpha_channel << 8) | (pp.blend[k].clamp << 16);
+            en.mode[0] = pp.blend[0].mode | (pp.blend[0].alpha_channel << 8) | (pp.blend[0].clamp << 16);
             entries.push_back(en);
           }
         }
@@ -2001,9 +2033,16 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
           PatchFrameArgs pa;
           memset(&pa, 0, sizeof(pa));
           for (int c = 0; c < 3; c++) pa.p[c] = B(cur[c]);
-          for (uint32_t k = 0; k < ne; k++) pa.ec[k] = B(cur_ec[k]);
+          for (uint32_t k = 0; k < ne && !tab; k++) pa.ec[k] = B(cur_ec[k]);
           pa.stride = cur_stride; pa.ec_stride = cur_ec_stride; pa.w = cw; pa.h = ch; pa.num_extra = ne; pa.premul_mask = premul_mask;
-          post_ops_.push_back([=](void* st) { LaunchPatches(pa, (const PatchEntryDev*)(dconst_ + o_e), (const uint32_t*)(dconst_ + o_s), (const uint32_t*)(dconst_ + o_l), st); });
+          if (tab) {
+            if (cb.ec_tmp.size() < ne) throw ParseError("patch planes of the extra channels", false);
+            for (uint32_t k = 0; k < ne; k++) tbl[k].tmp = B(cb.ec_tmp[k]);
+            const size_t o_p = arena.Put(pec.data(), pec.size() * sizeof(PatchEcDev));
+            post_ops_.push_back([=](void* st) {
+              LaunchPatchesTable(pa, DT(), (const PatchEntryDev*)(dconst_ + o_e), (const PatchEcDev*)(dconst_ + o_p), (const uint32_t*)(dconst_ + o_s), (const uint32_t*)(dconst_ + o_l), st);
+            });
+          } else post_ops_.push_back([=](void* st) { LaunchPatches(pa, (const PatchEntryDev*)(dconst_ + o_e), (const uint32_t*)(dconst_ + o_s), (const uint32_t*)(dconst_ + o_l), st); });
         }
       }
       // ---- splines (segments from the host, host_features.cc)
@@ -2030,9 +2069,11 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         }
         for (uint32_t k = 0; k < ne; k++) {
           const size_t src = cur_ec[k], dst = cb.up_ec[k];
-          post_ops_.push_back([=](void* st) { LaunchUpsamplePlane(B(src), cw, cw, ch, B(dst), fw, fw, fh, up, (const float*)(dconst_ + o_w), st); });
+          if (tab) { tbl[k].up = B(dst); tbl[k].fg = tbl[k].up; tbl[k].fg_stride = fw; }
+          else post_ops_.push_back([=](void* st) { LaunchUpsamplePlane(B(src), cw, cw, ch, B(dst), fw, fw, fh, up, (const float*)(dconst_ + o_w), st); });
           cur_ec[k] = dst;
         }
+        if (tab) post_ops_.push_back([=](void* st) { EcFrameArgs a = efa; a.table = DT(); a.up_weights = (const float*)(dconst_ + o_w); LaunchEcUpsample(a, st); });
         cur_stride = fw; cur_ec_stride = fw;
       }
       // ---- noise
@@ -2064,7 +2105,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         Slot& sl = slots[p.save_as_reference];
         sl.valid = true; sl.before_ct = true; sl.stride = cur_stride; sl.ec_stride = cur_ec_stride; sl.w = fw; sl.h = fh;
         for (int c = 0; c < 3; c++) sl.p[c] = cur[c];
-        for (uint32_t k = 0; k < ne; k++) sl.ec[k] = cur_ec[k];
+        sl.ec = cur_ec;
       }
       if (p.frame_type == 2) continue;    // reference-only frames are not displayed
       // ---- colour transform into the output space
@@ -2128,7 +2169,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
       bool replace_all = p.blend.mode == 0;
       for (auto& b : p.ec_blend) if (b.mode != 0) replace_all = false;
       const bool needs_blending = p.have_crop || !replace_all;
-      size_t canvas[3], canvas_ec[4] = {0, 0, 0, 0}; uint32_t canvas_stride, canvas_ec_stride;
+      size_t canvas[3]; vec<size_t> canvas_ec(ne, 0); uint32_t canvas_stride, canvas_ec_stride;
       if (!needs_blending) {
         if (fw != ih.xsize || fh != ih.ysize) throw ParseError("frame size differs from the image size without a crop", false);
         for (int c = 0; c < 3; c++) canvas[c] = cur[c];
@@ -2145,7 +2186,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         BlendArgs ba;
         memset(&ba, 0, sizeof(ba));
         for (int c = 0; c < 3; c++) { ba.fg[c] = B(cur[c]); ba.canvas[c] = B(cb.canvas[c]); }
-        for (uint32_t k = 0; k < ne; k++) { ba.fg_ec[k] = B(cur_ec[k]); ba.canvas_ec[k] = B(cb.canvas_ec[k]); }
+        for (uint32_t k = 0; k < ne && !tab; k++) { ba.fg_ec[k] = B(cur_ec[k]); ba.canvas_ec[k] = B(cb.canvas_ec[k]); }
         ba.fg_stride = cur_stride; ba.fg_ec_stride = cur_ec_stride; ba.fw = fw; ba.fh = fh; ba.x0 = p.x0; ba.y0 = p.y0;
         ba.canvas_stride = ih.xsize; ba.canvas_ec_stride = ih.xsize; ba.img_w = ih.xsize; ba.img_h = ih.ysize; ba.num_extra = ne; ba.premul_mask = premul_mask;
         const Slot* bg = source(p.blend.source);
@@ -2153,15 +2194,26 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         ba.mode[0] = p.blend.mode | (p.blend.alpha_channel << 8) | ((uint32_t)p.blend.clamp << 16);
         if (p.blend.mode == 2 || p.blend.mode == 3) {
           if (ne == 0) throw ParseError("alpha blending without extra channels", false);
-          if (bg) { ba.bg_alpha = B(bg->ec[p.blend.alpha_channel]); ba.bg_alpha_stride = bg->ec_stride; }
+          if (p.blend.alpha_channel >= ne) throw ParseError("blend alpha channel", false);
+          if (bg) { ba.bg_alpha = B(bg->ec.at(p.blend.alpha_channel)); ba.bg_alpha_stride = bg->ec_stride; }
         }
         for (uint32_t k = 0; k < ne; k++) {
           const BlendInfoH& bi = p.ec_blend[k];
-          ba.mode[1 + k] = bi.mode | (bi.alpha_channel << 8) | ((uint32_t)bi.clamp << 16);
+          const uint32_t mode = bi.mode | (bi.alpha_channel << 8) | ((uint32_t)bi.clamp << 16);
+          if (bi.alpha_channel >= ne) throw ParseError("blend alpha channel", false);
           const Slot* eb = source(bi.source);
+          if (eb && eb->ec.size() < ne) throw ParseError("blending source without the extra channels", false);
+          if (tab) {
+            EcChanDev& t = tbl[k];
+            t.mode = mode; t.canvas = B(cb.canvas_ec[k]); t.canvas_stride = ih.xsize;
+            if (eb) { t.bg = B(eb->ec[k]); t.bg_alpha = B(eb->ec[bi.alpha_channel]); t.bg_stride = eb->ec_stride; }
+            continue;
+          }
+          ba.mode[1 + k] = mode;
           if (eb) { ba.bg_ec[k] = B(eb->ec[k]); ba.bg_ec_alpha[k] = B(eb->ec[bi.alpha_channel]); ba.bg_ec_stride[k] = eb->ec_stride; }
         }
-        post_ops_.push_back([=](void* st) { LaunchBlend(ba, st); });
+        if (tab) post_ops_.push_back([=](void* st) { LaunchBlendTable(ba, DT(), st); });
+        else post_ops_.push_back([=](void* st) { LaunchBlend(ba, st); });
         for (int c = 0; c < 3; c++) canvas[c] = cb.canvas[c];
         for (uint32_t k = 0; k < ne; k++) canvas_ec[k] = cb.canvas_ec[k];
         canvas_stride = ih.xsize; canvas_ec_stride = ih.xsize;
@@ -2170,7 +2222,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         Slot& sl = slots[p.save_as_reference];
         sl.valid = true; sl.before_ct = false; sl.stride = canvas_stride; sl.ec_stride = canvas_ec_stride; sl.w = ih.xsize; sl.h = ih.ysize;
         for (int c = 0; c < 3; c++) sl.p[c] = canvas[c];
-        for (uint32_t k = 0; k < ne; k++) sl.ec[k] = canvas_ec[k];
+        sl.ec = canvas_ec;
       }
       // coalescing: the composite of the last frame is what the caller receives — or, for a frame of an animation, the canvas after that frame
       // ... or, decoded once for all of them (SetOutputAllFrames), after every frame of the list, each canvas to its own slot of the output area
@@ -2185,7 +2237,13 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         if (spot || have_deferred_tf) throw ParseError("unsupported: all frames of an animation in one decode with spot colours to render", true);
       }
       // ---- spot colours (stage_spot.cc): colour = mix * spot + (1 - mix) * colour with mix = solidity * channel, channel by channel
-      if (first.out.render_spotcolors) {
+      if (first.out.render_spotcolors && tab) {
+        bool any_spot = false;
+        for (uint32_t k = 0; k < ne; k++) any_spot |= ih.extra[k].type == 2;
+        const size_t c0 = canvas[0], c1 = canvas[1], c2 = canvas[2];
+        const uint32_t use_canvas = needs_blending ? 1 : 0, iw = ih.xsize, ihh = ih.ysize;
+        if (any_spot) post_ops_.push_back([=](void* st) { float* pl[3] = {B(c0), B(c1), B(c2)}; LaunchSpotTable(pl, canvas_stride, DT(), ne, use_canvas, iw, ihh, st); });
+      } else if (first.out.render_spotcolors) {
         for (uint32_t k = 0; k < ne; k++) {
           if (ih.extra[k].type != 2) continue;
           SpotArgs sa;
@@ -2219,6 +2277,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
       break;                      // (frames behind the delivered one: nothing of theirs is needed)
     }
   }
+  for (const PendingTable& t : tables) memcpy(hconst.data() + t.off, t.entries.data(), t.entries.size() * sizeof(EcChanDev));
 }
 
 void Batch::EnqueuePostOps(void* stream) { for (auto& op : post_ops_) op(stream); }

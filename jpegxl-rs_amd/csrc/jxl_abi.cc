@@ -1123,6 +1123,14 @@ int JxlHipDebugDescribe(const uint8_t* data, size_t size, char* out, size_t cap)
     snprintf(line, sizeof line, "image %ux%u bits=%u extra=%zu xyb=%d gray=%d icc=%zu frames=%d\n", ih.xsize, ih.ysize, ih.depth.bits, ih.extra.size(), (int)ih.xyb_encoded,
              (int)(ih.color_space == 1), ih.icc.size(), b.num_units());
     s += line;
+    // the extra channels one by one, for images with more than four of them (the descriptions of all other images stay as they were): what the frame tail's channel table is built from
+    for (size_t k = 0; k < ih.extra.size() && ih.extra.size() > 4; k++) {
+      const ExtraChannel& x = ih.extra[k];
+      const std::string xname(x.name.begin(), x.name.end());
+      snprintf(line, sizeof line, "extra %zu type=%u bits=%u exp_bits=%u premultiplied=%d spot=%g,%g,%g,%g name=%s\n", k, x.type, x.depth.bits, x.depth.is_float ? x.depth.exp_bits : 0,
+               (int)x.alpha_associated, x.spot[0], x.spot[1], x.spot[2], x.spot[3], xname.c_str());
+      s += line;
+    }
     for (int i = 0; i < b.num_units(); i++) {
       const FramePlan& p = b.unit(i).plan;
       snprintf(line, sizeof line, "frame %d %s type=%u %ux%u at (%d,%d) groups=%u lf_groups=%u passes=%u upsampling=%u patches=%zu splines=%zu noise=%d blend=%u last=%d "

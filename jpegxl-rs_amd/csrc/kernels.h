@@ -255,6 +255,39 @@ struct BlendArgs {
   float* canvas[3]; float* canvas_ec[4]; uint32_t canvas_stride, canvas_ec_stride, img_w, img_h, num_extra, premul_mask; uint32_t mode[5];
 };
 struct WriteArgs { const float* p[3]; const float* alpha; uint32_t stride, alpha_stride, img_w, img_h; uint8_t* out; uint64_t out_stride; uint32_t out_channels, out_type, out_big_endian, out_orient, is_gray, unpremul; float out_int_mul; };
+// ---- images with more than four extra channels: the extra-channel half of the frame tail reads a per-frame channel table in device memory
+// (built by Batch::PlanPostOps) instead of pointers inlined into the argument blocks above; the kernels run over (channel, y, x) with the
+// channel on blockIdx.z.  Per-sample arithmetic is that of the inlined forms (shared device functions).
+struct EcChanDev {
+  const int32_t* src_int;            // decoded samples (coded size, row stride = coded width)
+  float* plane;                      // float samples, coded size
+  float* up;                         // upsampled to the frame size (null: the frame is not upsampled)
+  float* tmp;                        // patch blending: the channel's value after a patch, until every channel of the pixel has read the values before it
+  const float* fg;                   // what blending reads: `up` or `plane`
+  const float* bg;                   // the blending source's plane of this channel (null: an empty reference slot, zeros)
+  const float* bg_alpha;             // the same source's plane of channel blend_alpha (modes blend / alpha-weighted add)
+  float* canvas;                     // where the blended channel goes (image size)
+  uint32_t fg_stride, bg_stride, canvas_stride;
+  uint32_t mode;                     // BlendMode | alpha channel << 8 | clamp << 16
+  uint32_t premul;                   // alpha_associated (channels of type alpha)
+  uint32_t float_bits, float_exp_bits;   // float samples: IntToFloatSample instead of the factor
+  float factor;                      // 1 / (2^bits - 1)
+  uint32_t type;                     // ExtraChannelType (2 = spot colour)
+  float spot[4];                     // spot colour and solidity
+};
+// per placement of a patch and extra channel: source plane (at the patch's top-left sample) and PatchBlendMode | alpha channel << 8 | clamp << 16
+struct PatchEcDev { const float* src; uint32_t mode, pad; };
+struct EcFrameArgs { const EcChanDev* table; uint32_t num_extra, w, h, ow, oh, up; const float* up_weights; };
+void LaunchEcIntToFloat(const EcFrameArgs& a, void* stream);      // table[c].src_int -> table[c].plane, w x h
+void LaunchEcUpsample(const EcFrameArgs& a, void* stream);        // table[c].plane (w x h) -> table[c].up (ow x oh)
+// patches of a frame with a channel table: PatchEntryDev::esrc / mode[1..] are not read, `pec` holds [placement * num_extra + channel]
+void LaunchPatchesTable(const PatchFrameArgs& a, const EcChanDev* table, const PatchEntryDev* entries, const PatchEcDev* pec, const uint32_t* tile_start,
+                        const uint32_t* tile_list, void* stream);
+// blending with a channel table: the colour kernel takes fg / bg / canvas / mode[0] of `a` and its alpha through the table (bg_alpha of `a`: the colour
+// source's alpha plane); the extra-channel kernel reads foreground planes and the sources' planes only, never a canvas plane
+void LaunchBlendTable(const BlendArgs& a, const EcChanDev* table, void* stream);
+// spot colours in header order, channel after channel per pixel (the mix is order-dependent)
+void LaunchSpotTable(float* const p[3], uint32_t stride, const EcChanDev* table, uint32_t num_extra, uint32_t use_canvas, uint32_t w, uint32_t h, void* stream);   // use_canvas: the blended planes (else fg)
 void LaunchIntToFloat(const int32_t* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t w, uint32_t h, float factor, void* stream, uint32_t float_bits = 0,
                       uint32_t float_exp_bits = 0);   // float_bits != 0: the integers are float bit patterns (IntToFloatSample)
 void LaunchXybModToFloat(const int32_t* cy, const int32_t* cx, const int32_t* cb, uint32_t src_stride, float* const dst[3], uint32_t dst_stride, uint32_t w, uint32_t h, const float fac[3], void* stream);

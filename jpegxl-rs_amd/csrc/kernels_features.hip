@@ -157,6 +157,46 @@ __global__ __launch_bounds__(256) void PatchKernel(PatchFrameArgs a, const Patch
   }
 }
 
+// The same for a frame with a channel table (more than four extra channels).  A channel's new value goes to its `tmp` plane first and comes
+// back once every channel and the colour of the pixel have read the values from before the patch: the alpha a blending refers to may be any
+// channel, also one that the same patch changes.
+__global__ __launch_bounds__(256) void PatchTableKernel(PatchFrameArgs a, const EcChanDev* __restrict__ table, const PatchEntryDev* __restrict__ entries,
+                                                        const PatchEcDev* __restrict__ pec, const uint32_t* __restrict__ tile_start,
+                                                        const uint32_t* __restrict__ tile_list, uint32_t tiles_x) {
+  const uint32_t tile = blockIdx.x;
+  const uint32_t begin = tile_start[tile], end = tile_start[tile + 1];
+  if (begin == end) return;
+  const uint32_t tx = tile % tiles_x, ty = tile / tiles_x;
+  for (uint32_t t = threadIdx.x; t < 1024; t += blockDim.x) {
+    const int x = (int)(tx * 32 + (t & 31)), y = (int)(ty * 32 + (t >> 5));
+    if (x >= (int)a.w || y >= (int)a.h) continue;
+    const size_t fo = (size_t)y * a.stride + x, eo = (size_t)y * a.ec_stride + x;
+    for (uint32_t k = begin; k < end; k++) {
+      const uint32_t ei = tile_list[k];
+      const PatchEntryDev& e = entries[ei];
+      const PatchEcDev* __restrict__ pe = pec + (size_t)ei * a.num_extra;
+      const int ix = x - e.x, iy = y - e.y;
+      if (ix < 0 || iy < 0 || ix >= (int)e.xs || iy >= (int)e.ys) continue;
+      const size_t so = (size_t)iy * e.src_stride + ix, seo = (size_t)iy * e.esrc_stride + ix;
+      const uint32_t m0 = e.mode[0] & 0xFF, a0 = (e.mode[0] >> 8) & 0xFF; const bool c0 = (e.mode[0] >> 16) & 1;
+      float fa = 1.0f, pa = 1.0f; bool premul = false;
+      if (m0 >= 4) { fa = table[a0].plane[eo]; pa = pe[a0].src[seo]; premul = table[a0].premul != 0; }
+      for (uint32_t c = 0; c < a.num_extra; c++) {
+        const uint32_t m = pe[c].mode & 0xFF, ac = (pe[c].mode >> 8) & 0xFF; const bool cl = (pe[c].mode >> 16) & 1;
+        const float fv = table[c].plane[eo], pv = pe[c].src[seo];
+        float efa = 1.0f, epa = 1.0f;
+        if (m >= 4) { efa = table[ac].plane[eo]; epa = pe[ac].src[seo]; }
+        float o;
+        if (m >= 4 && ac == c) o = PatchBlendAlpha(m, cl, efa, epa);
+        else o = PatchBlendSample(m, cl, m >= 4 ? table[ac].premul != 0 : false, fv, pv, efa, epa);
+        table[c].tmp[eo] = o;
+      }
+      for (int c = 0; c < 3; c++) a.p[c][fo] = PatchBlendSample(m0, c0, premul, a.p[c][fo], e.src[c][so], fa, pa);
+      for (uint32_t c = 0; c < a.num_extra; c++) table[c].plane[eo] = table[c].tmp[eo];
+    }
+  }
+}
+
 // ---- splines (stage_splines.cc; splines.cc DrawSegment) --------------------------------------------------------------------
 // One thread per pixel; the row's segment list is walked in order (ascending segment index, as Splines::Apply does), the
 // contributions are added one by one — same order of float additions per pixel as the scalar reference.
@@ -188,10 +228,7 @@ __global__ __launch_bounds__(256) void SplineKernel(float* p0, float* p1, float*
 }
 
 // ---- upsampling of one plane (stage_upsampling.cc; same definition as kernels.hip UpsampleKernel) ---------------------------
-__global__ void UpsamplePlaneKernel(const float* __restrict__ src, uint32_t src_stride, int w, int h, float* __restrict__ dst, uint32_t dst_stride, int ow, int oh,
-                                    int up, const float* __restrict__ weights) {
-  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y * blockDim.y + threadIdx.y;
-  if (ox >= ow || oy >= oh) return;
+__device__ __forceinline__ float UpsampleSample(const float* __restrict__ src, uint32_t src_stride, int w, int h, int ox, int oy, int up, const float* __restrict__ weights) {
   const int N = up / 2;
   const int x = ox / up, sx = ox % up, y = oy / up, sy = oy % up;
   const int ky = sy < N ? sy : up - 1 - sy, kx = sx < N ? sx : up - 1 - sx;
@@ -210,7 +247,28 @@ __global__ void UpsamplePlaneKernel(const float* __restrict__ src, uint32_t src_
       if (iy == 0 && ix == 0) { mn = v; mx = v; } else { mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
     }
   }
-  dst[(size_t)oy * dst_stride + ox] = sum < mn ? mn : (sum > mx ? mx : sum);
+  return sum < mn ? mn : (sum > mx ? mx : sum);
+}
+__global__ void UpsamplePlaneKernel(const float* __restrict__ src, uint32_t src_stride, int w, int h, float* __restrict__ dst, uint32_t dst_stride, int ow, int oh,
+                                    int up, const float* __restrict__ weights) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y * blockDim.y + threadIdx.y;
+  if (ox >= ow || oy >= oh) return;
+  dst[(size_t)oy * dst_stride + ox] = UpsampleSample(src, src_stride, w, h, ox, oy, up, weights);
+}
+// ---- the same two steps for every extra channel of a frame with a channel table: channel on blockIdx.z (the table entry is wave-uniform)
+__global__ void EcIntToFloatKernel(EcFrameArgs a) {
+  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+  if (x >= a.w || y >= a.h) return;
+  const EcChanDev& c = a.table[blockIdx.z];
+  const size_t o = (size_t)y * a.w + x;
+  const int32_t v = c.src_int[o];
+  c.plane[o] = c.float_bits ? IntToFloatSample(v, c.float_bits, c.float_exp_bits) : (float)v * c.factor;
+}
+__global__ void EcUpsampleKernel(EcFrameArgs a) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y * blockDim.y + threadIdx.y;
+  if (ox >= (int)a.ow || oy >= (int)a.oh) return;
+  const EcChanDev& c = a.table[blockIdx.z];
+  c.up[(size_t)oy * a.ow + ox] = UpsampleSample(c.plane, a.w, (int)a.w, (int)a.h, ox, oy, (int)a.up, a.up_weights);
 }
 
 // ---- noise (dec_noise.cc Random3Planes, stage_noise.cc) --------------------------------------------------------------------
@@ -385,6 +443,11 @@ __device__ __forceinline__ float FrameBlendSampleD(uint32_t mode, bool clamp, bo
     default: return bg * (clamp ? Clamp01(fg) : fg);
   }
 }
+// the alpha channel's own update under modes 2 (blend) / 3 (alpha-weighted add: the background's alpha stays)
+__device__ __forceinline__ float FrameBlendAlphaD(uint32_t mode, bool clamp, float bga, float fga) {
+  const float fa = clamp ? Clamp01(fga) : fga;
+  return mode == 2 ? 1.0f - (1.0f - fa) * (1.0f - bga) : bga;
+}
 __global__ void BlendKernel(BlendArgs a) {
   const int X = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y * blockDim.y + threadIdx.y;
   if (X >= (int)a.img_w || Y >= (int)a.img_h) return;
@@ -413,7 +476,7 @@ __global__ void BlendKernel(BlendArgs a) {
     if (m == 2 || m == 3) {
       const float efga = a.fg_ec[ac][feo];
       const float ebga = a.bg_ec_alpha[e] ? a.bg_ec_alpha[e][(size_t)Y * a.bg_ec_stride[e] + X] : 0.0f;
-      if (ac == e) { const float fa = cl ? Clamp01(efga) : efga; ec_out[e] = m == 2 ? 1.0f - (1.0f - fa) * (1.0f - ebga) : ebga; }
+      if (ac == e) ec_out[e] = FrameBlendAlphaD(m, cl, ebga, efga);
       else ec_out[e] = FrameBlendSampleD(m, cl, (a.premul_mask >> ac) & 1, b, fv, ebga, efga);
     } else ec_out[e] = FrameBlendSampleD(m, cl, false, b, fv, 1.0f, 1.0f);
   }
@@ -422,6 +485,73 @@ __global__ void BlendKernel(BlendArgs a) {
     a.canvas[c][co] = FrameBlendSampleD(mode, clamp, premul, b, a.fg[c][fo], bga, fga);
   }
   for (uint32_t e = 0; e < a.num_extra; e++) a.canvas_ec[e][ceo] = ec_out[e];
+}
+
+// Channel-table forms (more than four extra channels).  Colour: BlendKernel's colour half, the foreground alpha read through the table.
+__global__ void BlendColorTableKernel(BlendArgs a, const EcChanDev* __restrict__ table) {
+  const int X = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y * blockDim.y + threadIdx.y;
+  if (X >= (int)a.img_w || Y >= (int)a.img_h) return;
+  const size_t co = (size_t)Y * a.canvas_stride + X, bo = (size_t)Y * a.bg_stride + X;
+  const int fx = X - a.x0, fy = Y - a.y0;
+  const bool inside = fx >= 0 && fy >= 0 && fx < (int)a.fw && fy < (int)a.fh;
+  if (!inside) {
+    for (int c = 0; c < 3; c++) a.canvas[c][co] = a.bg[0] ? a.bg[c][bo] : 0.0f;
+    return;
+  }
+  const size_t fo = (size_t)fy * a.fg_stride + fx;
+  const uint32_t mode = a.mode[0] & 0xFF, ach = (a.mode[0] >> 8) & 0xFF; const bool clamp = (a.mode[0] >> 16) & 1;
+  float fga = 1.0f, bga = 1.0f; bool premul = false;
+  if (mode == 2 || mode == 3) {
+    const EcChanDev& al = table[ach];
+    fga = al.fg[(size_t)fy * al.fg_stride + fx];
+    bga = a.bg_alpha ? a.bg_alpha[(size_t)Y * a.bg_alpha_stride + X] : 0.0f;
+    premul = al.premul != 0;
+  }
+  for (int c = 0; c < 3; c++) {
+    const float b = a.bg[0] ? a.bg[c][bo] : 0.0f;
+    a.canvas[c][co] = FrameBlendSampleD(mode, clamp, premul, b, a.fg[c][fo], bga, fga);
+  }
+}
+// Extra channels: channel on blockIdx.z.  Every read is of a foreground plane or of a plane of the source (the canvas as an earlier frame left it),
+// every write goes to this frame's own canvas plane of the channel: no slice reads what another one writes.
+__global__ void BlendEcTableKernel(BlendArgs a, const EcChanDev* __restrict__ table) {
+  const int X = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y * blockDim.y + threadIdx.y;
+  if (X >= (int)a.img_w || Y >= (int)a.img_h) return;
+  const uint32_t e = blockIdx.z;
+  const EcChanDev& c = table[e];
+  const size_t bo = (size_t)Y * c.bg_stride + X;
+  const float b = c.bg ? c.bg[bo] : 0.0f;
+  float* out = c.canvas + (size_t)Y * c.canvas_stride + X;
+  const int fx = X - a.x0, fy = Y - a.y0;
+  if (!(fx >= 0 && fy >= 0 && fx < (int)a.fw && fy < (int)a.fh)) { *out = b; return; }
+  const uint32_t m = c.mode & 0xFF, ac = (c.mode >> 8) & 0xFF; const bool cl = (c.mode >> 16) & 1;
+  const float fv = c.fg[(size_t)fy * c.fg_stride + fx];
+  float o;
+  if (m == 2 || m == 3) {
+    const EcChanDev& al = table[ac];
+    const float efga = al.fg[(size_t)fy * al.fg_stride + fx];
+    const float ebga = c.bg_alpha ? c.bg_alpha[bo] : 0.0f;
+    if (ac == e) o = FrameBlendAlphaD(m, cl, ebga, efga);
+    else o = FrameBlendSampleD(m, cl, al.premul != 0, b, fv, ebga, efga);
+  } else o = FrameBlendSampleD(m, cl, false, b, fv, 1.0f, 1.0f);
+  *out = o;
+}
+// Spot colours through the table: one thread per pixel walks the channels in header order (each mix reads what the one before it wrote)
+__global__ void SpotTableKernel(float* p0, float* p1, float* p2, uint32_t stride, const EcChanDev* __restrict__ table, uint32_t num_extra, uint32_t use_canvas,
+                                uint32_t w, uint32_t h) {
+  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+  if (x >= w || y >= h) return;
+  const size_t o = (size_t)y * stride + x;
+  float v[3] = {p0[o], p1[o], p2[o]};
+  for (uint32_t e = 0; e < num_extra; e++) {
+    const EcChanDev& c = table[e];
+    if (c.type != 2) continue;
+    const float s = use_canvas ? c.canvas[(size_t)y * c.canvas_stride + x] : c.fg[(size_t)y * c.fg_stride + x];
+    const float mix = c.spot[3] * s;
+#pragma unroll
+    for (int k = 0; k < 3; k++) v[k] = mix * c.spot[k] + (1.0f - mix) * v[k];
+  }
+  p0[o] = v[0]; p1[o] = v[1]; p2[o] = v[2];
 }
 
 // ---- write stage (stage_write.cc): float planes in the output colour space -> caller layout --------------------------------
@@ -574,6 +704,30 @@ void LaunchSpot(const SpotArgs& a, void* stream) { hipLaunchKernelGGL(SpotKernel
 void LaunchColor(const ColorArgs& a, void* stream) { hipLaunchKernelGGL(ColorKernel, Grid2(a.w, a.h), kBlock2, 0, (hipStream_t)stream, a); }
 void LaunchBlend(const BlendArgs& a, void* stream) { hipLaunchKernelGGL(BlendKernel, Grid2(a.img_w, a.img_h), kBlock2, 0, (hipStream_t)stream, a); }
 void LaunchWrite(const WriteArgs& a, void* stream) { hipLaunchKernelGGL(WriteKernel, Grid2(a.img_w, a.img_h), kBlock2, 0, (hipStream_t)stream, a); }
+void LaunchEcIntToFloat(const EcFrameArgs& a, void* stream) {
+  if (!a.num_extra) return;
+  dim3 g = Grid2(a.w, a.h); g.z = a.num_extra;
+  hipLaunchKernelGGL(EcIntToFloatKernel, g, kBlock2, 0, (hipStream_t)stream, a);
+}
+void LaunchEcUpsample(const EcFrameArgs& a, void* stream) {
+  if (!a.num_extra) return;
+  dim3 g = Grid2(a.ow, a.oh); g.z = a.num_extra;
+  hipLaunchKernelGGL(EcUpsampleKernel, g, kBlock2, 0, (hipStream_t)stream, a);
+}
+void LaunchPatchesTable(const PatchFrameArgs& a, const EcChanDev* table, const PatchEntryDev* entries, const PatchEcDev* pec, const uint32_t* tile_start,
+                        const uint32_t* tile_list, void* stream) {
+  const uint32_t tiles_x = (a.w + 31) / 32, tiles_y = (a.h + 31) / 32;
+  hipLaunchKernelGGL(PatchTableKernel, dim3(tiles_x * tiles_y), dim3(256), 0, (hipStream_t)stream, a, table, entries, pec, tile_start, tile_list, tiles_x);
+}
+void LaunchBlendTable(const BlendArgs& a, const EcChanDev* table, void* stream) {
+  hipLaunchKernelGGL(BlendColorTableKernel, Grid2(a.img_w, a.img_h), kBlock2, 0, (hipStream_t)stream, a, table);
+  if (!a.num_extra) return;
+  dim3 g = Grid2(a.img_w, a.img_h); g.z = a.num_extra;
+  hipLaunchKernelGGL(BlendEcTableKernel, g, kBlock2, 0, (hipStream_t)stream, a, table);
+}
+void LaunchSpotTable(float* const p[3], uint32_t stride, const EcChanDev* table, uint32_t num_extra, uint32_t use_canvas, uint32_t w, uint32_t h, void* stream) {
+  hipLaunchKernelGGL(SpotTableKernel, Grid2(w, h), kBlock2, 0, (hipStream_t)stream, p[0], p[1], p[2], stride, table, num_extra, use_canvas, w, h);
+}
 void LaunchJpegCoefficients(const FrameDev* frames, int fidx, const JpegCoefArgs& a, uint32_t bw, uint32_t bh, void* stream) {
   const uint32_t n = bw * bh * 64;
   hipLaunchKernelGGL(JpegCoefKernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, frames, fidx, a);

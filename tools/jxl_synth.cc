@@ -103,6 +103,7 @@ struct Params {
                                                   // 0: no entries — everything rides in the last pass, the others are empty
   int num_extra_hdr = -1;                         // extra channels announced by the image header (-1: as the frame has)
   int alpha_premultiplied = 0;                    // image header: alpha_associated
+  int upsampling_modular = 0;                     // Modular frames (jxlsynth_modular_ec): > 1 = the frame is coded at 1 / this of the image size
   int xyb_image = 0;                              // Modular frames: the image is XYB encoded (samples are Y, X, B - Y scaled by the LF factors)
   int do_ycbcr = 0; int jpeg_upsampling[3] = {0, 0, 0};   // non-XYB VarDCT frames: YCbCr with per-channel sampling-factor modes (tools/synth_ycbcr.h)
 };
@@ -470,6 +471,13 @@ static void WriteFeatures(BitWriter& s) {
 // header, one command per tag (known names, implicit offsets / sizes, TRC and XYZ triples where they apply), tag data as a mix
 // of insert / shuffle / predict commands chosen to exercise the decoder rather than to compress.
 static thread_local std::vector<uint8_t> g_icc;
+// The extra channels of the image being written, while one of the *_ec entry points runs (jxlsynth_modular_ec / jxlsynth_vardct_ec): the image header announces them
+// one by one (type, bit depth or float layout, name, premultiplied alpha, spot colour) and the frame header carries blending info per channel.  Empty otherwise:
+// the writers below then produce what they always did (at most one extra channel, one blending info for all).
+struct ExtraSpec { int type = 0, bits = 8, exp_bits = 0, premultiplied = 0, blend_mode = 0, blend_alpha = 0, blend_clamp = 0, blend_source = 0; float spot[4] = {0, 0, 0, 0}; std::string name; };
+static thread_local std::vector<ExtraSpec> g_extras;
+static thread_local const int32_t* const* g_extra_planes = nullptr;   // VarDCT: their samples (int32 planes of the frame's coded size)
+static thread_local int g_color_blend_alpha = 0;                      // alpha channel of the colour channels' blending info
 // enumerated colour encoding of the image headers written from now on (jxlsynth_set_color): white point / primaries / transfer function
 // enums of color_encoding_internal.h, gamma in 1e-7 units (0 = use tf), intensity target in nits
 struct ColorOverride { bool set = false; int white_point = 1, primaries = 1, tf = 13; uint32_t gamma = 0; float intensity_target = 255.0f; };
@@ -613,6 +621,7 @@ static void WritePreviewSize(BitWriter& w, int xs, int ys) {
 static bool& CustomOpsin() { static thread_local bool v = false; return v; }
 static void WriteImageHeader(BitWriter& w, int xs, int ys, const Params& pin, bool xyb, int bits, bool has_alpha, bool gray) {
   Params p = pin;
+  if (!g_extras.empty()) has_alpha = true;
   if (p.orientation == 1) p.orientation = g_orientation;     // (every encoder entry point: Modular, frame-controlled and YCbCr streams have no argument of their own)
   w.put(0xFF, 8); w.put(0x0A, 8);
   WriteSize(w, xs, ys);
@@ -643,8 +652,22 @@ static void WriteImageHeader(BitWriter& w, int xs, int ys, const Params& pin, bo
     else if (g_float_exp_bits) { w.put(1, 1); WriteU32(w, bits, {0, 32}, {0, 16}, {0, 24}, {6, 1}); w.put((uint32_t)g_float_exp_bits - 1, 4); }
     else { w.put(0, 1); WriteU32(w, bits, {0, 8}, {0, 10}, {0, 12}, {6, 1}); }
     w.put(1, 1);  // modular_16bit_buffers
-    WriteU32(w, has_alpha ? 1 : 0, {0, 0}, {0, 1}, {4, 2}, {12, 1});
-    if (has_alpha && g_spot_set) {
+    WriteU32(w, !g_extras.empty() ? (uint32_t)g_extras.size() : has_alpha ? 1 : 0, {0, 0}, {0, 1}, {4, 2}, {12, 1});
+    if (!g_extras.empty()) {
+      for (const ExtraSpec& e : g_extras) {                  // headers.cc ExtraChannelInfo
+        if (e.type == 0 && e.bits == 8 && !e.exp_bits && !e.premultiplied && e.name.empty()) { w.put(1, 1); continue; }   // d_alpha
+        w.put(0, 1);
+        WriteU32(w, (uint32_t)e.type, {0, 0}, {0, 1}, {4, 2}, {6, 18});
+        if (e.exp_bits) { w.put(1, 1); WriteU32(w, (uint32_t)e.bits, {0, 32}, {0, 16}, {0, 24}, {6, 1}); w.put((uint32_t)e.exp_bits - 1, 4); }
+        else { w.put(0, 1); WriteU32(w, (uint32_t)e.bits, {0, 8}, {0, 10}, {0, 12}, {6, 1}); }
+        WriteU32(w, 0, {0, 0}, {0, 3}, {0, 4}, {3, 1});      // dim_shift
+        WriteU32(w, (uint32_t)e.name.size(), {0, 0}, {4, 0}, {5, 16}, {10, 48});
+        for (char c : e.name) w.put((uint8_t)c, 8);
+        if (e.type == 0) w.put(e.premultiplied ? 1 : 0, 1);
+        if (e.type == 2) for (int i = 0; i < 4; i++) WriteF16(w, e.spot[i]);
+        if (e.type == 5) WriteU32(w, 1, {0, 1}, {2, 0}, {4, 3}, {8, 19});
+      }
+    } else if (has_alpha && g_spot_set) {
       w.put(0, 1);                                         // not the default 8-bit alpha
       WriteU32(w, 2, {0, 0}, {0, 1}, {4, 2}, {6, 18});     // type kSpotColor
       w.put(0, 1); WriteU32(w, bits, {0, 8}, {0, 10}, {0, 12}, {6, 1});
@@ -784,10 +807,14 @@ static void WriteFrameHeader(BitWriter& w, const Params& p, bool modular, bool x
   if (p.frame_type == 0 || p.frame_type == 3) {
     // blending info (+ one per extra channel)
     for (int i = 0; i < 1 + num_extra; i++) {
-      if (p.blend_mode < 3) w.put((uint32_t)p.blend_mode, 2); else { w.put(3, 2); w.put((uint32_t)p.blend_mode - 3, 2); }
-      if (num_extra > 0 && (p.blend_mode == 2 || p.blend_mode == 3)) w.put(0, 2);   // alpha channel 0
-      if (num_extra > 0 && (p.blend_mode == 2 || p.blend_mode == 3 || p.blend_mode == 4)) w.put(p.blend_clamp ? 1 : 0, 1);
-      if (p.blend_mode != 0 || partial) w.put((uint32_t)p.blend_source, 2);
+      // (one blending info for the colour channels and every extra channel; the *_ec entry points: one of its own per extra channel, the colour's with its alpha channel)
+      const bool own = i > 0 && (size_t)num_extra == g_extras.size();
+      const int mode = own ? g_extras[i - 1].blend_mode : p.blend_mode, clamp = own ? g_extras[i - 1].blend_clamp : p.blend_clamp;
+      const int source = own ? g_extras[i - 1].blend_source : p.blend_source, alpha = own ? g_extras[i - 1].blend_alpha : g_extras.empty() ? 0 : g_color_blend_alpha;
+      if (mode < 3) w.put((uint32_t)mode, 2); else { w.put(3, 2); w.put((uint32_t)mode - 3, 2); }
+      if (num_extra > 0 && (mode == 2 || mode == 3)) WriteU32(w, (uint32_t)alpha, {0, 0}, {0, 1}, {0, 2}, {3, 3});   // alpha channel
+      if (num_extra > 0 && (mode == 2 || mode == 3 || mode == 4)) w.put(clamp ? 1 : 0, 1);
+      if (mode != 0 || partial) w.put((uint32_t)source, 2);
     }
     if (g_anim_num > 0) WriteU32(w, (uint32_t)p.duration, {0, 0}, {0, 1}, {8, 0}, {32, 0});   // duration in ticks (no timecodes)
     w.put(p.is_last ? 1 : 0, 1);  // is_last
@@ -1207,12 +1234,34 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
   // the image fits one group, else the modular part of every PassGroup), under the same global tree
   // squeezed alpha of a frame with downsampling entries: the sub-channels of shift 0..2 are spread over the PassGroups of every pass (by its bracket);
   // otherwise they all ride in the last pass.  alpha_tok / alpha_has: (pass, group) of the last sq_passes passes, pass-major
+  const int nec = (int)g_extras.size();          // (*_ec entry points: that many lossless extra channels instead of the one alpha plane)
+  if (nec && (alpha || AlphaSqueeze() || !g_extra_planes)) throw std::runtime_error("extra-channel list: planes as int32, no alpha plane, no squeeze");
   const bool alpha_sq = alpha && AlphaSqueeze();
   const int sq_passes = alpha_sq && np > 1 && p.pass_ds ? np : 1;
   std::vector<Token> alpha_global_tok;
   std::vector<std::vector<Token>> alpha_tok((size_t)ngroups * sq_passes), alpha_lf_tok;
   std::vector<char> alpha_lf_has, alpha_has;          // squeezed alpha: which LfGroup / PassGroup sections carry a Modular sub-stream
-  const bool alpha_global = alpha && w <= 256 && h <= 256;
+  const bool alpha_global = (alpha || nec) && w <= 256 && h <= 256;
+  if (nec) {
+    // every channel whole in GlobalModular (frames of one group), or a rectangle of every channel in each PassGroup of the last pass
+    if (alpha_global) {
+      std::vector<ChanRef> cr;
+      for (int e = 0; e < nec; e++) cr.push_back({g_extra_planes[e], w, h});
+      ModularTokens(gt, root, cr, 0, alpha_global_tok);
+    } else {
+      for (int g = 0; g < ngroups; g++) {
+        const int x0 = (g % xg) * 256, y0 = (g / xg) * 256, gw = std::min(256, w - x0), gh = std::min(256, h - y0);
+        std::vector<std::vector<int32_t>> rect(nec, std::vector<int32_t>((size_t)gw * gh));
+        std::vector<ChanRef> cr;
+        for (int e = 0; e < nec; e++) {
+          for (int y = 0; y < gh; y++) memcpy(&rect[e][(size_t)y * gw], &g_extra_planes[e][(size_t)(y0 + y) * w + x0], sizeof(int32_t) * gw);
+          cr.push_back({rect[e].data(), gw, gh});
+        }
+        ModularTokens(gt, root, cr, 1 + 3 * nlf + 17 + ngroups * (p.num_passes - 1) + g, alpha_tok[g]);
+      }
+      alpha_has.assign(ngroups, 1);
+    }
+  }
   if (alpha) {
     std::vector<int32_t> a32((size_t)w * h);
     for (size_t i = 0; i < a32.size(); i++) a32[i] = alpha[i];
@@ -1361,7 +1410,7 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
       EncodeTokens(s, tree_code, tree_tokens);
       WriteEntropyCode(s, mod_code);
     }
-    if (alpha) {  // the global Modular image has a channel: GroupHeader + whatever is decodable globally
+    if (alpha || nec) {  // the global Modular image has a channel: GroupHeader + whatever is decodable globally
       s.put(local_rest ? 0 : 1, 1); s.put(1, 1);
       if (alpha_sq) { s.put(1, 2); s.put(2, 2); WriteU32(s, 0, {0, 0}, {4, 1}, {6, 9}, {8, 41}); }    // one transform: Squeeze with the default chain (zero explicit steps)
       else s.put(0, 2);
@@ -1425,7 +1474,7 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
     // extra channels (shift 0..2) ride in the last pass (Passes::GetDownsamplingBracket without downsampling entries), squeezed ones of a frame with
     // downsampling entries in the pass whose bracket holds their shift — behind that pass's coefficients
     const int k = ps - (np - sq_passes);
-    if (alpha && (alpha_sq || !alpha_global) && k >= 0 && alpha_has[(size_t)k * ngroups + g]) {
+    if ((alpha || nec) && (alpha_sq || !alpha_global) && k >= 0 && alpha_has[(size_t)k * ngroups + g]) {
       s.put(local_rest ? 0 : 1, 1); s.put(1, 1); s.put(0, 2);
       if (local_rest) write_local(s, alpha_tok[(size_t)k * ngroups + g], 0, false);
       else EncodeTokens(s, mod_code, alpha_tok[(size_t)k * ngroups + g]);
@@ -1433,11 +1482,11 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
     sections.push_back(s);
   }
   BitWriter out;
-  const bool hdr_alpha = p.num_extra_hdr >= 0 ? p.num_extra_hdr > 0 : alpha != nullptr;
+  const bool hdr_alpha = p.num_extra_hdr >= 0 ? p.num_extra_hdr > 0 : (alpha != nullptr || nec > 0);
   if (p.emit != 1) WriteImageHeader(out, p.canvas_w ? p.canvas_w : img_w, p.canvas_h ? p.canvas_h : img_h, p, true, p.out_bits == 16 ? 16 : 8, hdr_alpha, false);
   if (p.emit == 2) return out.bytes;
   bool lf_default = p.gab == 1 && p.epf_iters == 2;
-  WriteFrameHeader(out, p, false, true, alpha ? 1 : 0, 1, lf_default, img_w, img_h);
+  WriteFrameHeader(out, p, false, true, nec ? nec : alpha ? 1 : 0, 1, lf_default, img_w, img_h);
   WriteTOCAndSections(out, sections, ngroups == 1 && np == 1, (uint32_t)p.permute_toc);
   out.align();
   return out.bytes;
@@ -1523,7 +1572,7 @@ static std::vector<uint8_t> EncodeModular(const int32_t* const* planes, int ncha
   const int group_shift = ModularGroupShift(), gd = 128 << group_shift, lfd = gd * 8;
   const int xg = (w + gd - 1) / gd, yg = (h + gd - 1) / gd, ngroups = xg * yg;
   const int xlg = (w + lfd - 1) / lfd, ylg = (h + lfd - 1) / lfd, nlf = xlg * ylg;
-  const int ntot = nchan + (has_alpha ? 1 : 0);
+  const int ntot = nchan + (!g_extras.empty() ? (int)g_extras.size() : has_alpha ? 1 : 0);
   std::vector<SChan> ch(ntot);
   for (int c = 0; c < ntot; c++) { ch[c].d.assign(planes[c], planes[c] + (size_t)w * h); ch[c].w = w; ch[c].h = h; ch[c].hs = ch[c].vs = 0; }
   if (rct && nchan == 3) {
@@ -1664,9 +1713,11 @@ static std::vector<uint8_t> EncodeModular(const int32_t* const* planes, int ncha
   if (fx) p = *fx;
   p.mod_passes = np;
   p.out_bits = bits; p.gab = 0; p.epf_iters = 0; p.noise = 0; p.upsampling = 1; p.num_passes = 1; p.skip_lf_smoothing = 0;  // lossless: no restoration filters
-  if (p.emit != 1) WriteImageHeader(out, p.canvas_w ? p.canvas_w : w, p.canvas_h ? p.canvas_h : h, p, p.xyb_image != 0, bits, has_alpha, nchan == 1);
+  const int mup = p.upsampling_modular > 1 ? p.upsampling_modular : 1;
+  p.upsampling = mup;
+  if (p.emit != 1) WriteImageHeader(out, p.canvas_w ? p.canvas_w : w * mup, p.canvas_h ? p.canvas_h : h * mup, p, p.xyb_image != 0, bits, has_alpha, nchan == 1);
   if (p.emit == 2) return out.bytes;
-  WriteFrameHeader(out, p, true, p.xyb_image != 0, has_alpha ? 1 : 0, group_shift, false, w, h);
+  WriteFrameHeader(out, p, true, p.xyb_image != 0, ntot - nchan, group_shift, false, w, h);
   WriteTOCAndSections(out, sections, single);
   out.align();
   return out.bytes;
@@ -1822,6 +1873,49 @@ int jxlsynth_modular3(const int32_t* const* planes, int nchan, int has_alpha, in
     return finish(synth::EncodeModular(planes, nchan, w, h, bits, has_alpha != 0, rct != 0, squeeze, &p), out, n);
   } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
+// ---- images with a list of extra channels (any number; the entry points above write at most one) -------------------------------------
+// One entry per extra channel: type (ExtraChannelType: 0 alpha, 1 depth, 2 spot colour, 3 selection mask, 16 optional), bits (8 / 16; the float16 channel: 16 with
+// exp_bits 5, samples are the bit patterns), premultiplied (alpha channels), the channel's own blending info, spot colour + solidity, name.
+struct jxlsynth_extra { int32_t type, bits, exp_bits, premultiplied, blend_mode, blend_alpha, blend_clamp, blend_source; float spot[4]; char name[16]; };
+static void SetExtras(const jxlsynth_extra* ec, int nec, int color_blend_alpha) {
+  synth::g_extras.clear();
+  for (int i = 0; i < nec; i++) {
+    synth::ExtraSpec e;
+    e.type = ec[i].type; e.bits = ec[i].bits; e.exp_bits = ec[i].exp_bits; e.premultiplied = ec[i].premultiplied;
+    e.blend_mode = ec[i].blend_mode; e.blend_alpha = ec[i].blend_alpha; e.blend_clamp = ec[i].blend_clamp; e.blend_source = ec[i].blend_source;
+    for (int k = 0; k < 4; k++) e.spot[k] = ec[i].spot[k];
+    e.name.assign(ec[i].name, strnlen(ec[i].name, sizeof(ec[i].name)));
+    if (e.bits < 1 || e.bits > 31 || e.blend_mode < 0 || e.blend_mode > 4 || e.blend_alpha < 0 || e.blend_alpha >= nec) throw std::runtime_error("extra-channel entry");
+    synth::g_extras.push_back(e);
+  }
+  if (nec < 1 || color_blend_alpha < 0 || color_blend_alpha >= nec) throw std::runtime_error("extra-channel list");
+  synth::g_color_blend_alpha = color_blend_alpha;
+}
+struct ExtrasScope { ~ExtrasScope() { synth::g_extras.clear(); synth::g_extra_planes = nullptr; synth::g_color_blend_alpha = 0; } };
+// Lossless Modular frame: planes = nchan colour planes followed by nec extra planes (w*h int32 each); frame control as jxlsynth_modular3 (fx may be NULL); upsampling 1, 2, 4, 8: the
+// planes are the coded frame (w x h), the image is upsampling times as large; the colour channels blend by fx's info with alpha channel color_blend_alpha
+int jxlsynth_modular_ec(const int32_t* const* planes, int nchan, const jxlsynth_extra* ec, int nec, int color_blend_alpha, int w, int h, int bits, int upsampling,
+                        const jxlsynth_frame* fx, uint8_t** out, size_t* n) {
+  try {
+    ExtrasScope scope;
+    SetExtras(ec, nec, color_blend_alpha);
+    synth::Params p;
+    if (fx) ApplyFrame(p, fx);
+    p.upsampling_modular = upsampling;
+    return finish(synth::EncodeModular(planes, nchan, w, h, bits, false, false, 0, &p), out, n);
+  } catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
+// VarDCT frame as jxlsynth_vardct3 (rgb8 sRGB) with nec lossless extra channels (ec_planes: w*h int32 each)
+int jxlsynth_vardct_ec(const uint8_t* rgb8, const int32_t* const* ec_planes, const jxlsynth_extra* ec, int nec, int color_blend_alpha, int w, int h, const jxlsynth_params* pp,
+                       const jxlsynth_frame* fx, uint8_t** out, size_t* n) {
+  try {
+    ExtrasScope scope;
+    SetExtras(ec, nec, color_blend_alpha);
+    synth::g_extra_planes = ec_planes;
+    return jxlsynth_vardct3(rgb8, nullptr, w, h, pp, fx, out, n);
+  } catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
+
 // planes: nchan (+alpha) pointers to w*h int32 samples
 int jxlsynth_modular2(const int32_t* const* planes, int nchan, int has_alpha, int w, int h, int bits, int rct, int squeeze, uint8_t** out, size_t* n) {
   try { return finish(synth::EncodeModular(planes, nchan, w, h, bits, has_alpha != 0, rct != 0, squeeze), out, n); }

@@ -244,11 +244,27 @@ JxlDecoderStatus JxlHipBatchGetBasicInfo(const JxlHipBatch* batch, int index, Jx
 JxlDecoderStatus JxlHipBatchOutBufferSize(const JxlHipBatch* batch, int index, const JxlPixelFormat* format, size_t* size);
 /* Output format (and optional caller-owned *device* destination; NULL = batch-owned) of image `index`. */
 JxlDecoderStatus JxlHipBatchSetOutput(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer);
+/* ---- the 1:8 decode (thumbnails) --------------------------------------------------------------------------------------------------
+ * downscale = 8: the image comes out at ceil(xsize / 8) x ceil(ysize / 8) pixels, one per 8x8 block — the frame's LF image, which the format stores in front of
+ * the AC groups.  Output pixel (bx, by) is LF sample (bx, by) of each channel after LF dequantisation and (unless the frame header skips it) adaptive LF smoothing —
+ * exactly what the IDCT stage reads as its lowest-frequency input — through the per-pixel tail of the full decode: inverse opsin / YCbCr -> RGB / identity, transfer
+ * function, grey handling, then the write stage with every output type, byte order, row alignment and bit depth.  Gaborish, EPF and noise are defined on
+ * full-resolution pixels and are not applied.  Chroma-subsampled YCbCr frames (JPEG transcodes): a channel with shift (hs, vs) is sampled on the LF grid with the
+ * (1/4, 3/4) taps of the full decode's chroma upsampling, horizontal then vertical, clamped at the channel's own edges.  The alpha slot of 2- / 4-channel output is
+ * 1.0.  The orientation is applied to the small picture as the full decode applies it to the large one (unless kept).  No AC coefficient is decoded, no IDCT and no
+ * filter runs, and a batch of such images only allocates neither coefficient nor pixel planes; the stream may end anywhere behind its LF part (LfGlobal, the LfGroups
+ * and HfGlobal: JxlHipBatchSetOption("allow_partial", 1) before adding such a prefix to a batch; pipeline jobs take them as they are) and decodes to the same bytes as
+ * the whole file.  Taken: single-frame VarDCT images with their own LF coefficients, without extra channels, patches, splines, noise or upsampling; anything else
+ * fails with "unsupported: downscaled decode of ...".  downscale = 1 is the call without the suffix; any other value returns JXL_DEC_ERROR (-1 from Submit) with a
+ * message in JxlHipLastError().  A batch may mix scaled and unscaled images. */
+JxlDecoderStatus JxlHipBatchOutBufferSizeScaled(const JxlHipBatch* batch, int index, const JxlPixelFormat* format, int downscale, size_t* size);
+JxlDecoderStatus JxlHipBatchSetOutputScaled(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int downscale);
 /* Decode-thread packing: lanes between active entropy-decode threads (64 = one stream per wavefront, 1 = 64 per wavefront). */
 void JxlHipBatchSetLaneStride(JxlHipBatch* batch, int lf, int hf);
 /* Tuning / testing knobs: "force_generic_idct", "hf_block_threads", "lds_code_budget", "debug_stop_after", "lf_wide_once" (the next LF stage of the batch takes the
  * one-wavefront-per-stream kernel whatever the lane stride: shorter latency on an idle GPU), "lf_wp_narrow_test" (testing: the SIMT LF kernel's
- * weighted-predictor lanes hand a stream back to the one-wavefront-per-stream kernel at |sample| > 16 instead of 2^20). Unknown names are ignored. */
+ * weighted-predictor lanes hand a stream back to the one-wavefront-per-stream kernel at |sample| > 16 instead of 2^20), "allow_partial" (images added afterwards may
+ * end behind their LF part: they decode at 1:8 only, JxlHipBatchSetOutputScaled; otherwise JxlHipBatchPrepare fails with "truncated"). Unknown names are ignored. */
 void JxlHipBatchSetOption(JxlHipBatch* batch, const char* name, int value);
 /* Uploads streams and tables (inputs become HBM-resident) and allocates work buffers.  hip_stream: hipStream_t or NULL. */
 JxlDecoderStatus JxlHipBatchPrepare(JxlHipBatch* batch, void* hip_stream);
@@ -315,6 +331,10 @@ void JxlHipPipelineDestroy(JxlHipPipeline* pipeline);
  * An image that does not parse or decode fails alone.  Returns the job's ticket (>= 0) or -1 (JxlHipLastError). */
 int64_t JxlHipPipelineSubmit(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
                              void* const* host_out, const size_t* out_capacity);
+/* The same job decoded at 1:8 (downscale = 8, see JxlHipBatchSetOutputScaled; destinations of JxlHipImageOutSizeScaled bytes): streams may end behind their LF part;
+ * an image the 1:8 decode does not take fails alone. */
+int64_t JxlHipPipelineSubmitScaled(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
+                                   void* const* host_out, const size_t* out_capacity, int downscale);
 /* Waits until the job has left the GPU (pixels written, host copies done).  image_status[i] (n entries, optional): 0 decoded, 1 failed; *end_ms (optional): when the
  * job's last byte was written, ms after JxlHipPipelineResetClock.  JXL_DEC_SUCCESS if every image decoded, else JXL_DEC_ERROR (JxlHipLastError names the first).
  * A ticket can be waited for once; jobs complete in submission order. */
@@ -332,6 +352,9 @@ void* JxlHipHostAlloc(size_t bytes);
 void JxlHipHostFree(void* p);
 /* Host-only (needs no GPU): basic info and output size of an image for `format` from its headers — what a caller of JxlHipPipelineSubmit sizes its buffers with. */
 JxlDecoderStatus JxlHipImageOutSize(const uint8_t* data, size_t size, const JxlPixelFormat* format, JxlBasicInfo* info, size_t* out_size);
+/* The same for the 1:8 decode: `info` stays the full-size JxlBasicInfo, *out_size is that of the ceil(xsize / 8) x ceil(ysize / 8) picture; a prefix of the file that holds
+ * the headers is enough. */
+JxlDecoderStatus JxlHipImageOutSizeScaled(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, JxlBasicInfo* info, size_t* out_size);
 /* Device arenas that batches and pipelines let go of are pooled per process (hipMalloc / hipFree of tens of GB cost seconds): JXL_HIP_ARENA_POOL_MB bounds the pool
  * (default 60 % of the device's memory, 0 = off); Trim hands every pooled block back to the runtime — for processes that share the GPU with another allocator —
  * and returns the bytes released; Held = bytes pooled right now. */

@@ -153,6 +153,10 @@ def libjxl():
             "JxlHipBatchAddImage": (C.c_int, [vp, vp, sz]), "JxlHipBatchGetBasicInfo": (C.c_int, [vp, C.c_int, C.POINTER(JxlBasicInfo)]),
             "JxlHipBatchOutBufferSize": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(sz)]),
             "JxlHipBatchSetOutput": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), vp]),
+            "JxlHipBatchOutBufferSizeScaled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(sz)]),
+            "JxlHipBatchSetOutputScaled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), vp, C.c_int]),
+            "JxlHipPipelineSubmitScaled": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.c_int]),
+            "JxlHipImageOutSizeScaled": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlBasicInfo), C.POINTER(sz)]),
             "JxlHipBatchSetLaneStride": (None, [vp, C.c_int, C.c_int]), "JxlHipBatchSetOption": (None, [vp, C.c_char_p, C.c_int]),
             "JxlHipBatchPrepare": (C.c_int, [vp, vp]), "JxlHipBatchDecode": (C.c_int, [vp, vp]),
             "JxlHipBatchDecodeTimed": (C.c_int, [vp, vp]), "JxlHipBatchFinish": (C.c_int, [vp, vp]),
@@ -593,6 +597,7 @@ class BatchDecoder:
             raise CannotCreateDecoder(last_error())
         self._n = 0
         self._fmt = []
+        self._scale = []
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -603,32 +608,53 @@ class BatchDecoder:
         if status != JXL_DEC_SUCCESS:
             raise GenericError(last_error())
 
-    def add(self, data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, device_ptr=None) -> int:
+    def _set_output(self, i, fmt, device_ptr, downscale):
+        L = libjxl()
+        if downscale == 1:
+            self._chk(L.JxlHipBatchSetOutput(self._h, i, C.byref(fmt), device_ptr))
+        else:
+            self._chk(L.JxlHipBatchSetOutputScaled(self._h, i, C.byref(fmt), device_ptr, int(downscale)))
+        self._fmt.append(fmt)
+        self._scale.append(int(downscale))
+
+    def add(self, data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, device_ptr=None, downscale=1) -> int:
+        """downscale=8: the 1:8 decode (include/jxl_hip.h JxlHipBatchSetOutputScaled) — output(i) is the ceil(w / 8) x ceil(h / 8) picture; `data` may end behind
+        the LF part of its frame."""
         L = libjxl()
         buf = np.frombuffer(data, dtype=np.uint8)
-        i = L.JxlHipBatchAddImage(self._h, buf.ctypes.data, len(data))
+        if downscale != 1:
+            L.JxlHipBatchSetOption(self._h, b"allow_partial", 1)
+        try:
+            i = L.JxlHipBatchAddImage(self._h, buf.ctypes.data, len(data))
+        finally:
+            if downscale != 1:
+                L.JxlHipBatchSetOption(self._h, b"allow_partial", 0)
         if i < 0:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
-        self._chk(L.JxlHipBatchSetOutput(self._h, i, C.byref(fmt), device_ptr))
-        self._fmt.append(fmt)
+        self._set_output(i, fmt, device_ptr, downscale)
         self._n += 1
         return i
 
-    def add_many(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, threads=4, endianness=Endianness.Native, align=0) -> int:
+    def add_many(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, threads=4, endianness=Endianness.Native, align=0, downscale=1) -> int:
         """Parses the images of `datas` (bytes objects) on `threads` host threads and appends them in order (JxlHipBatchAddImages);
-        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one."""
+        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale: as for add()."""
         L = libjxl()
         n = len(datas)
         ptrs = (C.c_char_p * n)(*datas)
         sizes = (C.c_size_t * n)(*[len(d) for d in datas])
-        first = L.JxlHipBatchAddImages(self._h, ptrs, sizes, n, int(threads))
+        if downscale != 1:
+            L.JxlHipBatchSetOption(self._h, b"allow_partial", 1)
+        try:
+            first = L.JxlHipBatchAddImages(self._h, ptrs, sizes, n, int(threads))
+        finally:
+            if downscale != 1:
+                L.JxlHipBatchSetOption(self._h, b"allow_partial", 0)
         if first < 0:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
         for k in range(n):
-            self._chk(L.JxlHipBatchSetOutput(self._h, first + k, C.byref(fmt), device_ptrs[k] if device_ptrs is not None else None))
-            self._fmt.append(fmt)
+            self._set_output(first + k, fmt, device_ptrs[k] if device_ptrs is not None else None, downscale)
         self._n += n
         return first
 
@@ -637,6 +663,7 @@ class BatchDecoder:
         libjxl().JxlHipBatchReset(self._h)
         self._n = 0
         self._fmt = []
+        self._scale = []
 
     def info(self, i) -> JxlBasicInfo:
         info = JxlBasicInfo()
@@ -645,7 +672,10 @@ class BatchDecoder:
 
     def out_size(self, i) -> int:
         s = C.c_size_t()
-        self._chk(libjxl().JxlHipBatchOutBufferSize(self._h, i, C.byref(self._fmt[i]), C.byref(s)))
+        if self._scale[i] == 1:
+            self._chk(libjxl().JxlHipBatchOutBufferSize(self._h, i, C.byref(self._fmt[i]), C.byref(s)))
+        else:
+            self._chk(libjxl().JxlHipBatchOutBufferSizeScaled(self._h, i, C.byref(self._fmt[i]), self._scale[i], C.byref(s)))
         return s.value
 
     def set_lane_stride(self, lf=64, hf=64):
@@ -734,12 +764,16 @@ def arena_pool_trim() -> int:
     return int(libjxl().JxlHipArenaPoolTrim())
 
 
-def image_out_size(data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0):
-    """(JxlBasicInfo, bytes of the decoded image in that format) from the headers alone — host-only (JxlHipImageOutSize)."""
+def image_out_size(data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, downscale=1):
+    """(JxlBasicInfo, bytes of the decoded image in that format) from the headers alone — host-only (JxlHipImageOutSize).
+    downscale=8: the size of the 1:8 decode (JxlHipImageOutSizeScaled); the info stays that of the full-size image."""
     fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
     info, size = JxlBasicInfo(), C.c_size_t()
     buf = np.frombuffer(data, dtype=np.uint8)
-    check_dec_status(libjxl().JxlHipImageOutSize(buf.ctypes.data, len(data), C.byref(fmt), C.byref(info), C.byref(size)))
+    if downscale == 1:
+        check_dec_status(libjxl().JxlHipImageOutSize(buf.ctypes.data, len(data), C.byref(fmt), C.byref(info), C.byref(size)))
+    elif libjxl().JxlHipImageOutSizeScaled(buf.ctypes.data, len(data), C.byref(fmt), int(downscale), C.byref(info), C.byref(size)) != JXL_DEC_SUCCESS:
+        raise GenericError(last_error())
     return info, size.value
 
 
@@ -789,9 +823,9 @@ class Pipeline:
 
     __del__ = close
 
-    def submit(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, host_ptrs=None, capacities=None, endianness=Endianness.Native, align=0) -> int:
+    def submit(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, host_ptrs=None, capacities=None, endianness=Endianness.Native, align=0, downscale=1) -> int:
         """Job of len(datas) images (bytes objects).  device_ptrs / host_ptrs: one destination address per image (exactly one of the two lists); the bytes objects and
-        the destinations are kept referenced until wait()."""
+        the destinations are kept referenced until wait().  downscale=8: the job is decoded at 1:8 (JxlHipPipelineSubmitScaled)."""
         n = len(datas)
         ptrs = (C.c_char_p * n)(*datas)
         sizes = (C.c_size_t * n)(*[len(d) for d in datas])
@@ -799,7 +833,10 @@ class Pipeline:
         dev = (C.c_void_p * n)(*device_ptrs) if device_ptrs is not None else None
         host = (C.c_void_p * n)(*host_ptrs) if host_ptrs is not None else None
         caps = (C.c_size_t * n)(*capacities) if capacities is not None else None
-        t = libjxl().JxlHipPipelineSubmit(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps)
+        if downscale == 1:
+            t = libjxl().JxlHipPipelineSubmit(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps)
+        else:
+            t = libjxl().JxlHipPipelineSubmitScaled(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale))
         if t < 0:
             raise GenericError(last_error())
         self._keep[t] = (datas, ptrs, sizes, dev, host, caps, n)

@@ -531,20 +531,21 @@ void Batch::Reset() {
 // Parses `n` images on `threads` host threads (the per-image work of AddImage — container, image and frame headers, TOC, the global
 // sections' tables — is independent) and appends them in order.  Returns the index of the first one; throws what the first failing
 // image threw.
-int Batch::AddImages(const uint8_t* const* datas, const size_t* sizes, int n, int threads) {
+int Batch::AddImages(const uint8_t* const* datas, const size_t* sizes, int n, int threads, bool allow_partial) {
   if (n <= 0) return (int)pub_.size();
   vec<int> index;
   std::vector<std::string> errors;
-  return AddImagesImpl(datas, sizes, n, threads, /*tolerant=*/false, &index, &errors);
+  return AddImagesImpl(datas, sizes, n, threads, /*tolerant=*/false, &index, &errors, allow_partial);
 }
 
 // The pipelined form: an image that does not parse (truncated, damaged headers, a feature the device path does not take) is left out instead of failing the call —
 // (*index)[i] = its index in the batch or -1, (*errors)[i] = what it threw ("" if it parsed).
-void Batch::AddImagesTolerant(const uint8_t* const* datas, const size_t* sizes, int n, int threads, vec<int>* index, std::vector<std::string>* errors) {
-  AddImagesImpl(datas, sizes, n, threads, /*tolerant=*/true, index, errors);
+void Batch::AddImagesTolerant(const uint8_t* const* datas, const size_t* sizes, int n, int threads, vec<int>* index, std::vector<std::string>* errors, bool for_downscale) {
+  AddImagesImpl(datas, sizes, n, threads, /*tolerant=*/true, index, errors, /*allow_partial=*/for_downscale, /*only_downscalable=*/for_downscale);
 }
 
-int Batch::AddImagesImpl(const uint8_t* const* datas, const size_t* sizes, int n, int threads, bool tolerant, vec<int>* index, std::vector<std::string>* errs) {
+static std::string DownscaleRefusalOf(int num_units, const ImageEntry& e);   // (below, with SetOutput)
+int Batch::AddImagesImpl(const uint8_t* const* datas, const size_t* sizes, int n, int threads, bool tolerant, vec<int>* index, std::vector<std::string>* errs, bool allow_partial, bool only_downscalable) {
   index->assign((size_t)std::max(n, 0), -1);
   errs->assign((size_t)std::max(n, 0), std::string());
   if (n <= 0) return (int)pub_.size();
@@ -558,7 +559,7 @@ int Batch::AddImagesImpl(const uint8_t* const* datas, const size_t* sizes, int n
     for (;;) {
       const int i = next.fetch_add(1);
       if (i >= n) break;
-      try { ParseImage(datas[i], sizes[i], &parsed[i], false); } catch (...) { errors[i] = std::current_exception(); }
+      try { ParseImage(datas[i], sizes[i], &parsed[i], allow_partial); } catch (...) { errors[i] = std::current_exception(); }
     }
   };
   if (nt == 1) work();
@@ -574,6 +575,11 @@ int Batch::AddImagesImpl(const uint8_t* const* datas, const size_t* sizes, int n
       try { std::rethrow_exception(errors[i]); } catch (const std::exception& e) { (*errs)[i] = e.what(); } catch (...) { (*errs)[i] = "unknown error"; }
       if ((*errs)[i].empty()) (*errs)[i] = "parse error";
       continue;
+    }
+    if (tolerant && only_downscalable && !parsed[i].units.empty()) {
+      // a job decoded at 1:8: what that decode does not take is left out like an image that does not parse (nothing of it is uploaded or decoded)
+      (*errs)[i] = DownscaleRefusalOf((int)parsed[i].units.size(), *parsed[i].units[0]);
+      if (!(*errs)[i].empty()) continue;
     }
     (*index)[i] = Append(std::move(parsed[i]));
   }
@@ -746,8 +752,10 @@ size_t Batch::OutputStride(const ImageHeader& ih, const OutputSpec& o, uint32_t*
   return stride;
 }
 // Orientations 5..8 transpose the image (codestream_header.rs JxlOrientation); applied unless the caller keeps it.
-uint32_t Batch::OrientedWidth(const ImageHeader& ih, const OutputSpec& o) { return (!o.keep_orientation && ih.orientation > 4) ? ih.ysize : ih.xsize; }
-uint32_t Batch::OrientedHeight(const ImageHeader& ih, const OutputSpec& o) { return (!o.keep_orientation && ih.orientation > 4) ? ih.xsize : ih.ysize; }
+// (1:8 decode, OutputSpec::downscale == 8: one pixel per 8x8 block of the stored picture, the orientation applied to that picture)
+static uint32_t Scaled(uint32_t v, const OutputSpec& o) { return o.downscale == 8 ? (v + 7) / 8 : v; }
+uint32_t Batch::OrientedWidth(const ImageHeader& ih, const OutputSpec& o) { return Scaled((!o.keep_orientation && ih.orientation > 4) ? ih.ysize : ih.xsize, o); }
+uint32_t Batch::OrientedHeight(const ImageHeader& ih, const OutputSpec& o) { return Scaled((!o.keep_orientation && ih.orientation > 4) ? ih.xsize : ih.ysize, o); }
 size_t Batch::OutputSize(const ImageHeader& ih, const OutputSpec& o) {
   // jpegxl-sys decode.rs:1100 JxlDecoderImageOutBufferSize: stride * (h - 1) + w * C * bytes
   uint32_t nc;
@@ -766,8 +774,27 @@ size_t Batch::OutputSizeOf(int i, const OutputSpec& o) const {
   return OutputSize(dims, o);
 }
 static float IntMul(const OutputSpec& o) { const uint32_t full = o.type == 0 ? 8 : 16; const uint32_t b = o.int_bits && o.int_bits < full ? o.int_bits : full; return (float)((1u << b) - 1); }
+// What the 1:8 decode takes: single-frame VarDCT images that carry their own LF coefficients and end in their own pixels (no frame tail).
+static std::string DownscaleRefusalOf(int num_units, const ImageEntry& e) {
+  const FramePlan& p = e.plan;
+  const char* what = nullptr;
+  if (num_units != 1) what = "an image with several frames";
+  else if (p.modular) what = "a Modular frame";
+  else if (p.use_lf_frame || e.lf_source) what = "a frame that takes its LF image from an LF frame";
+  else if (!e.ih.extra.empty()) what = "an image with extra channels";
+  else if (p.upsampling != 1) what = "an upsampled frame";
+  else if (e.complex) what = "a frame with patches, splines, noise, a crop or blending";
+  return what ? std::string("unsupported: downscaled decode of ") + what : std::string();
+}
+std::string Batch::DownscaleRefusal(int i) const { return DownscaleRefusalOf(pub_[i].num_units, *images_[pub_[i].first_unit]); }
 void Batch::SetOutput(int i, const OutputSpec& o) {
   ImageEntry& e = *images_[pub_[i].first_unit];
+  if (o.downscale != 1) {
+    if (o.downscale != 8) throw ParseError("downscale must be 1 or 8", false);
+    const std::string why = DownscaleRefusal(i);
+    if (!why.empty()) throw ParseError(why, true);
+    if (o.only_frame >= 0 || o.upto_frame >= 0) throw ParseError("unsupported: downscaled decode of a single frame of an animation", true);
+  }
   e.out = o;
   if (o.only_frame >= pub_[i].num_units) throw ParseError("non-coalesced output: no such frame", false);
   // (a lone frame that fills the image is the same either way: the plain path keeps it)
@@ -822,6 +849,10 @@ void Batch::StageBytes(uint64_t out[6]) const {
     const uint64_t out_px = (uint64_t)first.out.num_channels * bps;
     out[0] += lf_sec + nblk * (3 * 4 + 4 + 4);
     out[1] += nblk * (12 + 12 + 12 + 12 + 12 + 16);
+    if (first.out.downscale == 8) {      // 1:8 decode: no HF stage, no IDCT, no filters; LfOutputKernel reads three LF samples and writes one pixel per block
+      out[5] += (uint64_t)((p.width + 7) / 8) * ((p.height + 7) / 8) * (12 + out_px);
+      continue;
+    }
     out[2] += hf_sec + (u < hf_written_.size() ? (uint64_t)hf_written_[u] * 4 : 0);
     out[3] += npx * (12 + 12);
     const bool fused = p.lf.gab && p.lf.epf_iters == 1 && e.ih.xyb_encoded && SimpleTransfer(e.ih) && p.upsampling == 1 && !e.complex && !cfg.force_unfused_filters;
@@ -1000,14 +1031,24 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     return true;
   };
   max_lf_groups_ = max_groups_ = max_w_ = max_h_ = max_bw_ = max_bh_ = max_epf_ = 0;
-  any_gab_ = any_vardct_ = any_modular_ = any_modchan_ = any_multipass_ = false;
+  any_gab_ = any_vardct_ = any_modular_ = any_modchan_ = any_multipass_ = any_scaled_ = any_full_vardct_ = false;
   fplan_ = FilterPlan();
+  // frames decoded at 1:8 (OutputSpec::downscale == 8; SetOutput only lets single-frame VarDCT images through): their decode ends behind the LF post-processing
+  auto scaled = [&](int i) { return images_[i]->frame_index == 0 && images_[i]->out.downscale == 8; };
+  vec<size_t> cs_bytes(n, 0);    // codestream bytes the frame's kernels may look at (FrameDev::cs_size)
   for (int i = 0; i < n; i++) {
     ImageEntry& e = *images_[i];
     FramePlan& p = e.plan;
     ConstOffsets& c = co[i];
     if (e.frame_index == 0 && e.out_size == 0) SetOutput(e.pub_index, e.out);
-    if (e.frame_index == 0) c.cs = arena.Put(e.cs.data(), e.cs.padded_size()); else c.cs = co[i - e.frame_index].cs;   // frames share the codestream
+    cs_bytes[i] = e.cs.size;
+    if (scaled(i) && !p.single_section) {
+      // the 1:8 decode reads LfGlobal, the LfGroups and (on the host) HfGlobal: what lies behind the last of them — the AC groups, most of the file — stays on the host
+      size_t end = 0;
+      for (size_t k = 0; k < 2 + (size_t)p.num_lf_groups && k < p.sections.size(); k++) end = std::max<size_t>(end, p.sections[k].offset + p.sections[k].size);
+      cs_bytes[i] = std::min(e.cs.size, end);
+    }
+    if (e.frame_index == 0) c.cs = arena.Put(e.cs.data(), e.cs.padded_size() - (e.cs.size - cs_bytes[i])); else c.cs = co[i - e.frame_index].cs;   // frames share the codestream
     vec<uint64_t> so, ss;
     for (auto& s : p.sections) { so.push_back(s.offset); ss.push_back(s.size); }
     c.sec_off = arena.Put(so.data(), so.size() * 8);
@@ -1041,7 +1082,8 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     max_groups_ = std::max<int>(max_groups_, p.num_groups);
     max_w_ = std::max<int>(max_w_, p.width); max_h_ = std::max<int>(max_h_, p.height);
     max_bw_ = std::max<int>(max_bw_, p.bw); max_bh_ = std::max<int>(max_bh_, p.bh);
-    if (!p.modular) {
+    if (!p.modular) (scaled(i) ? any_scaled_ : any_full_vardct_) = true;
+    if (!p.modular && !scaled(i)) {
       max_epf_ = std::max<int>(max_epf_, p.lf.epf_iters); any_gab_ |= p.lf.gab != 0;
       const bool fusable = p.lf.gab && p.lf.epf_iters == 1 && e.ih.xyb_encoded && SimpleTransfer(e.ih) && p.upsampling == 1 && !e.complex;
       if (p.upsampling > 1 && !e.complex) { fplan_.any_upsampled = true; fplan_.max_out_w = std::max<int>(fplan_.max_out_w, e.ih.xsize); fplan_.max_out_h = std::max<int>(fplan_.max_out_h, e.ih.ysize); }
@@ -1082,7 +1124,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
   size_t wcoef = 0;
   for (int i = 0; i < n; i++) {
     const FramePlan& p = images_[i]->plan;
-    if (p.modular) continue;
+    if (p.modular || scaled(i)) continue;
     for (int c = 0; c < 3; c++) { wo[i].coeff[c] = Align(wcoef); wcoef = wo[i].coeff[c] + (size_t)p.num_groups * 65536 * 4; }
   }
   coeff_bytes_ = Align(wcoef);
@@ -1108,7 +1150,10 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       const size_t ntile = (size_t)((p.bw + 7) / 8) * ((p.bh + 7) / 8);
       o.ytox = take(ntile); o.ytob = take(ntile);
       const size_t plane = (size_t)p.bw * 8 * p.bh * 8 * 4;
-      for (int c = 0; c < 3; c++) { o.plane_a[c] = take_big(plane); o.plane_b[c] = (need_plane_b || e.complex) ? take_big(plane) : (size_t)-1; }
+      for (int c = 0; c < 3; c++) {
+        if (scaled(i)) { o.plane_a[c] = o.plane_b[c] = (size_t)-1; continue; }      // (no full-resolution planes)
+        o.plane_a[c] = take_big(plane); o.plane_b[c] = (need_plane_b || e.complex) ? take_big(plane) : (size_t)-1;
+      }
       if (p.upsampling > 1 && !e.complex) for (int c = 0; c < 4; c++) o.up_plane[c] = take_big((size_t)e.ih.xsize * e.ih.ysize * 4);
       o.lf_scratch_stride = 16 + 2 * 1024 + 3 * 65536;
       o.lf_scratch = take(o.lf_scratch_stride * 4 * p.num_lf_groups);
@@ -1168,7 +1213,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     }
     if (((p.has_global_tree && p.tree_code.lz77) || lz_local) && (!p.gchannels.empty() || !p.modular))   // LZ77 windows of the Modular streams (4 MiB each); VarDCT: + one per LF group
       o.lz_window = take((size_t)(1 + p.NumModUnits() + (p.modular ? 0 : p.num_lf_groups)) * (4u << 20));
-    if (!p.modular) {   // LZ77-coded AC streams: a window per group stream (1 MiB each, only for the frames that use them)
+    if (!p.modular && !scaled(i)) {   // LZ77-coded AC streams: a window per group stream (1 MiB each, only for the frames that use them)
       bool lz_ac = p.single_section;    // (a one-section frame's AC code is only parsed once its LF streams have been decoded: always reserved, 1 MiB)
       for (auto& code : p.ac_code) lz_ac |= code.lz77;
       if (lz_ac) o.lz_ac_window = take((size_t)p.num_groups * kAcLzWindow * 4);
@@ -1259,7 +1304,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     f.width = p.width; f.height = p.height; f.bw = p.bw; f.bh = p.bh; f.xgroups = p.xgroups; f.ygroups = p.ygroups; f.num_groups = p.num_groups;
     f.xlfgroups = p.xlfgroups; f.num_lf_groups = p.num_lf_groups; f.cw = (p.bw + 7) / 8; f.ch = (p.bh + 7) / 8;
     f.group_dim = p.group_dim; f.is_modular = p.modular; f.plane_stride = p.bw * 8; f.plane_rows = p.bh * 8;
-    f.cs = cbase + c.cs; f.cs_size = e.cs.size;
+    f.cs = cbase + c.cs; f.cs_size = cs_bytes[i];
     f.sec_off = (const uint64_t*)(cbase + c.sec_off); f.sec_size = (const uint64_t*)(cbase + c.sec_size);
     f.single_section = p.single_section;
     f.lf_start_bitpos = p.global_data_bitpos;  // VarDCT without extra channels: LfGroup follows LfGlobal directly
@@ -1314,6 +1359,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     f.out_stride = e.out_stride; f.out_channels = e.out.num_channels; f.out_type = e.out.type; f.out_big_endian = e.out.big_endian; f.out_int_mul = IntMul(e.out);
     f.out_orient = e.out.keep_orientation ? 1 : e.ih.orientation;
     f.upsampling = p.upsampling; f.img_w = e.ih.xsize; f.img_h = e.ih.ysize;
+    if (scaled(i)) { f.lf_only = 1; f.img_w = (p.width + 7) / 8; f.img_h = (p.height + 7) / 8; }     // (the picture LfOutputKernel writes; out_stride is SetOutput's, of the same picture)
     if (p.upsampling > 1) { f.up_weights = (const float*)(cbase + c.up_weights); for (int k = 0; k < 4; k++) f.up_plane[k] = (float*)(dbig_ + o.up_plane[k]); }
     f.is_gray = e.ih.color_space == 1;
     f.post_mode = e.complex ? 1 : 0;
@@ -1347,8 +1393,8 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       FillColor(e.ih, p.do_ycbcr, f);
       for (int k = 0; k < 3; k++) {
         f.lfq[k] = (int32_t*)(dwork_ + o.lfq[k]); f.lf[k] = (float*)(dwork_ + o.lf[k]); f.lf_tmp[k] = (float*)(dwork_ + o.lf_tmp[k]);
-        f.llf[k] = (float*)(dwork_ + o.llf[k]); f.coeff[k] = (int32_t*)(dcoef_ + o.coeff[k]);
-        f.plane_a[k] = (float*)(dbig_ + o.plane_a[k]); f.plane_b[k] = o.plane_b[k] == (size_t)-1 ? nullptr : (float*)(dbig_ + o.plane_b[k]);
+        f.llf[k] = (float*)(dwork_ + o.llf[k]); f.coeff[k] = scaled(i) ? nullptr : (int32_t*)(dcoef_ + o.coeff[k]);
+        f.plane_a[k] = o.plane_a[k] == (size_t)-1 ? nullptr : (float*)(dbig_ + o.plane_a[k]); f.plane_b[k] = o.plane_b[k] == (size_t)-1 ? nullptr : (float*)(dbig_ + o.plane_b[k]);
       }
       f.blk_info = (uint32_t*)(dwork_ + o.blk_info); f.coef_off = (uint32_t*)(dwork_ + o.coef_off);
       f.vb_list = (uint2*)(dwork_ + o.vb_list); f.vb_count = (uint32_t*)(dwork_ + o.vb_count);
@@ -1454,7 +1500,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
         cp.orders[b * 3 + ch] = cu.empty() ? natural_off[b] : arena.Put(cu.data(), cu.size() * 2);
       }
     }
-    if (p.num_passes > 1) any_multipass_ = true;
+    if (p.num_passes > 1 && !scaled(i)) any_multipass_ = true;     // (what the HF stage must handle: frames decoded at 1:8 never reach it)
     for (int k = 0; k < 17; k++) {
       int hit = -1;
       for (size_t q = 0; q < qcache.size(); q++) if (qcache[q].kind == k && spec_equal(*qcache[q].spec, p.qspec[k])) { hit = (int)q; break; }
@@ -1506,6 +1552,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       for (auto& l : p.lf_local) if (l.present) {
         cfg.max_tree_nodes = std::max<int>(cfg.max_tree_nodes, (int)l.tree.nodes.size()); cfg.mod_code_bytes = std::max(cfg.mod_code_bytes, code_bytes(l.code, false)); cfg.any_wp |= l.tree.uses_wp ? 1 : 0;
       }
+      if (!p.modular && scaled(i)) continue;     // (the rest sizes and picks the HF / IDCT kernels)
       if (!p.modular) for (auto& code : p.ac_code) { cfg.ac_code_bytes = std::max(cfg.ac_code_bytes, code_bytes(code, true)); cfg.ac_code_bytes_compact = std::max(cfg.ac_code_bytes_compact, code_bytes_compact(code)); }
       if (p.subsampled) cfg.any_subsampled = 1;
       if (!p.modular) for (auto& code : p.ac_code) if (code.use_prefix || code.lz77) cfg.any_prefix_ac = 1;
@@ -1699,7 +1746,9 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     }
   }
   // (a frame cut off inside its AC groups, FramePlan::partial: the HF kernels leave out the group streams that are not completely there; nothing to do when none is)
-  for (int i = 0; i < n; i++) if (images_[i]->plan.partial && images_[i]->plan.partial_ac_sections == 0) cfg.skip_hf = 1;
+  for (int i = 0; i < n; i++) if (images_[i]->plan.partial && images_[i]->plan.partial_ac_sections == 0 && !scaled(i)) cfg.skip_hf = 1;
+  if (refuse_partial_unscaled)
+    for (int i = 0; i < n; i++) if (images_[i]->plan.partial && !scaled(i)) throw ParseError("truncated", false);
   cfg.any_multipass = any_multipass_ ? 1 : 0;
   if (any_multipass_) cfg.lane_stride_hf = 1;   // progressive frames: only the SIMT HF kernel walks the passes
   if (cfg.any_subsampled) cfg.lane_stride_hf = 1;   // so do chroma-subsampled frames (per-channel block grids)
@@ -2406,35 +2455,37 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
   if (do_hf) {
     // the HF decoder only writes non-zero coefficients into cleared planes (outside the per-stage brackets when the
     // halves are timed separately)
-    ClearCoefficientsBeforeHf(stream_v);
+    // (a batch of 1:8 frames only, any_full_vardct_ == false: no coefficient plane exists, nothing of this stage, of the IDCT or of the filters is launched)
+    if (any_full_vardct_) ClearCoefficientsBeforeHf(stream_v);
     rec(split ? 7 : 2);
     // (progressive flush at the kDC step: no AC group is decoded — the planes stay zero, the IDCT sees the LF part only)
-    if (!cfg.skip_hf) LaunchHfDecode(dframes_, n, max_groups_, cfg, stream_v, &trace_);
+    if (!cfg.skip_hf && any_full_vardct_) LaunchHfDecode(dframes_, n, max_groups_, cfg, stream_v, &trace_);
     DebugSync("HF decode", stream_v);
     if (any_modchan_) EnqueueModularTail(stream_v);   // (the PassGroup Modular parts start where the HF streams ended)
-    LaunchZeroFailedCoefficients(dframes_, n, stream_v);   // (frames that failed up to here are skipped by the IDCT kernels: their planes are zeroed now)
+    if (any_full_vardct_) LaunchZeroFailedCoefficients(dframes_, n, stream_v);   // (frames that failed up to here are skipped by the IDCT kernels: their planes are zeroed now)
     CheckLaunches("HF stage / Modular sub-streams");
     rec(3);
   }
   if (do_tail) {
-    if (!cfg.idct_flags_known && flags_pending_ && part != 0) {
+    if (!cfg.idct_flags_known && flags_pending_ && part != 0 && any_full_vardct_) {
       HIP_CHECK(hipEventSynchronize((hipEvent_t)flags_event_));
       ApplyIdctFlags(flags_pinned_);
       flags_pending_ = false;
     }
     if (do_idct) {
       if (split) rec(8);                        // the tail may sit on another stream than the HF stage: its own start mark
-      LaunchIdct(dframes_, n, max_groups_, max_bw_, max_bh_, cfg, stream_v);
+      if (any_full_vardct_) LaunchIdct(dframes_, n, max_groups_, max_bw_, max_bh_, cfg, stream_v);
       DebugSync("IDCT", stream_v);
       CheckLaunches("IDCT stage");
       rec(4);
-      ClearCoefficientsAfterDecode(stream_v);   // (the IDCT kernels zeroed what they read)
+      if (any_full_vardct_) ClearCoefficientsAfterDecode(stream_v);   // (the IDCT kernels zeroed what they read)
     }
     if (do_post) {
-      if (cfg.debug_stop_after != 1) LaunchFilters(dframes_, n, max_w_, max_h_, fplan_, cfg, stream_v);
+      if (cfg.debug_stop_after != 1 && any_full_vardct_) LaunchFilters(dframes_, n, max_w_, max_h_, fplan_, cfg, stream_v);
       DebugSync("filters", stream_v);
       rec(5);
-      if (!cfg.debug_stop_after) LaunchOutput(dframes_, n, max_w_, max_h_, fplan_, cfg, stream_v);
+      if (!cfg.debug_stop_after && any_full_vardct_) LaunchOutput(dframes_, n, max_w_, max_h_, fplan_, cfg, stream_v);
+      if (!cfg.debug_stop_after && any_scaled_) LaunchLfOutput(dframes_, n, max_bw_, max_bh_, stream_v);   // 1:8 frames: the LF image through the colour transform and the write stage
       if (any_complex_ && !cfg.debug_stop_after) EnqueuePostOps(stream_v);   // frame tail of multi-frame / feature images
       DebugSync("output / frame tail", stream_v);
       CheckLaunches("filters / output / frame tail");

@@ -27,6 +27,9 @@ struct OutputSpec {
                                   // (JxlDecoderSetExtraChannelBuffer hands out any extra channel through this slot)
   uint32_t int_bits = 0;          // integer output: 0 = the full range of the sample type, else samples in [0, 2^int_bits - 1] (JxlDecoderSetImageOutBitDepth)
   bool render_spotcolors = true;  // JxlDecoderSetRenderSpotcolors: spot-colour extra channels are mixed into the colour channels (stage_spot.cc)
+  uint32_t downscale = 1;         // 1, or 8: the 1:8 decode — the output is the frame's LF image, ceil(w / 8) x ceil(h / 8) pixels, one per 8x8 block, through the colour transform and the
+                                  // write stage (LfOutputKernel); no AC coefficient is decoded, no IDCT, no restoration filter runs.  Single-frame VarDCT images without extra
+                                  // channels, patches, splines, noise or upsampling (Batch::DownscaleRefusal)
 };
 
 // What the frames of one image share: the codestream and the image header.
@@ -92,9 +95,13 @@ class Batch {
   int AddImage(const uint8_t* data, size_t size, bool allow_partial = false);
   bool is_partial(int i) const;
   // The same for n images, parsed on `threads` host threads and appended in order; returns the index of the first.
-  int AddImages(const uint8_t* const* datas, const size_t* sizes, int n, int threads);
+  int AddImages(const uint8_t* const* datas, const size_t* sizes, int n, int threads, bool allow_partial = false);
+  // "" when image i can be decoded at 1:8 (OutputSpec::downscale == 8), else the reason, "unsupported: downscaled decode of ..."; SetOutput throws it
+  std::string DownscaleRefusal(int i) const;
   // Same, but an image that does not parse is left out instead of failing the call: (*index)[i] = its index in the batch or -1, (*errors)[i] = what it threw.
-  void AddImagesTolerant(const uint8_t* const* datas, const size_t* sizes, int n, int threads, vec<int>* index, std::vector<std::string>* errors);
+  // for_downscale: the images are going to be decoded at 1:8 — a stream may end behind its LF part (allow_partial as for AddImage), and an image that decode does not take is
+  // left out with DownscaleRefusal's message
+  void AddImagesTolerant(const uint8_t* const* datas, const size_t* sizes, int n, int threads, vec<int>* index, std::vector<std::string>* errors, bool for_downscale = false);
   // Forgets the images, keeps device arenas / staging buffer / buffer sharing: the object can be filled and prepared again.
   void Reset();
   size_t size() const { return pub_.size(); }
@@ -144,6 +151,8 @@ class Batch {
   // ALGORITHMIC bytes per stage for one Run of the batch: 0 lf, 1 lfpost, 2 hf, 3 idct, 4 filters, 5 out
   void StageBytes(uint64_t out[6]) const;
   LaunchCfg cfg;
+  bool refuse_partial_unscaled = false;   // Prepare throws "truncated" for an image cut off behind its LF part (AddImage allow_partial) that is not decoded at 1:8 — callers that let
+                                          // such streams in for the sake of 1:8 decodes only (JxlHipBatch*)
   size_t const_bytes() const { return const_size_; }
   size_t work_bytes() const { return work_size_ + (coef_owner_ || coef_is_ext_ ? 0 : coeff_bytes_) + (big_owner_ || big_is_ext_ ? 0 : big_size_); }
   void ShareBigArena(Batch* owner);
@@ -201,7 +210,7 @@ class Batch {
   HostStage hconst_;
   struct ParsedImage { vec<std::unique_ptr<ImageEntry>> units; bool complex = false; };
   static void ParseImage(const uint8_t* data, size_t size, ParsedImage* out, bool allow_partial = false);
-  int AddImagesImpl(const uint8_t* const* datas, const size_t* sizes, int n, int threads, bool tolerant, vec<int>* index, std::vector<std::string>* errors);
+  int AddImagesImpl(const uint8_t* const* datas, const size_t* sizes, int n, int threads, bool tolerant, vec<int>* index, std::vector<std::string>* errors, bool allow_partial = false, bool only_downscalable = false);
   int Append(ParsedImage&& im);
   bool DevReserve(void** ptr, size_t* cap, size_t bytes);
   size_t const_cap_ = 0, work_cap_ = 0, big_cap_ = 0, coef_cap_ = 0, coef_laid_out_ = 0, frames_cap_ = 0, passes_cap_ = 0, local_cap_ = 0;
@@ -245,6 +254,7 @@ class Batch {
   bool prepared_ = false;
   int max_lf_groups_ = 0, max_groups_ = 0, max_w_ = 0, max_h_ = 0, max_bw_ = 0, max_bh_ = 0, max_epf_ = 0;
   bool any_gab_ = false, any_vardct_ = false, any_modular_ = false;
+  bool any_scaled_ = false, any_full_vardct_ = false;   // some VarDCT frame is decoded at 1:8 / at full size (a batch of 1:8 frames only skips the HF stage, the IDCT and the filters)
   FilterPlan fplan_;
   LaunchTrace trace_;             // the entropy-decode kernels the last LF / HF launch took (Info: hf_variant, lf_variant, lf_wide_bytes, lf_wide_only)
   LfSimtPlan lf_simt_;            // SIMT LF decode: device descriptors of the eligible frames' LF-group streams (cfg.lane_stride_lf < 64)

@@ -887,7 +887,7 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
 }
 
 // ---- batch extension ---------------------------------------------------------------------------------------------------
-struct JxlHipBatchStruct { Batch* b; bool keep_orientation = false; };
+struct JxlHipBatchStruct { Batch* b; bool keep_orientation = false; bool allow_partial = false; };
 
 JxlHipBatch* JxlHipBatchCreate(int device) {
   try {
@@ -895,15 +895,16 @@ JxlHipBatch* JxlHipBatchCreate(int device) {
     if (hipGetDeviceCount(&count) != hipSuccess || device >= count) { SetLastError("no usable HIP device (no CPU fallback exists)"); return nullptr; }
     JxlHipBatch* h = new JxlHipBatchStruct();
     h->b = new Batch(device);
+    h->b->refuse_partial_unscaled = true;     // ("allow_partial" lets streams in that end behind their LF part: good for 1:8 decodes only)
     return h;
   } catch (const std::exception& e) { SetLastError(e.what()); return nullptr; }
 }
 void JxlHipBatchDestroy(JxlHipBatch* h) { if (h) { delete h->b; delete h; } }
 int JxlHipBatchAddImage(JxlHipBatch* h, const uint8_t* data, size_t size) {
-  try { return h->b->AddImage(data, size); } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
+  try { return h->b->AddImage(data, size, h->allow_partial); } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
 }
 int JxlHipBatchAddImages(JxlHipBatch* h, const uint8_t* const* datas, const size_t* sizes, int n, int num_threads) {
-  try { return h->b->AddImages(datas, sizes, n, num_threads); } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
+  try { return h->b->AddImages(datas, sizes, n, num_threads, h->allow_partial); } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
 }
 void JxlHipBatchReset(JxlHipBatch* h) { h->b->Reset(); }
 JxlDecoderStatus JxlHipBatchGetBasicInfo(const JxlHipBatch* h, int i, JxlBasicInfo* info) {
@@ -925,6 +926,31 @@ JxlDecoderStatus JxlHipBatchSetOutput(JxlHipBatch* h, int i, const JxlPixelForma
   o.keep_orientation = h->keep_orientation;
   h->b->SetOutput(i, o);
   return JXL_DEC_SUCCESS;
+}
+static bool DownscaleOk(int downscale, const char* who) {
+  if (downscale == 1 || downscale == 8) return true;
+  SetLastError(std::string(who) + ": downscale must be 1 or 8");
+  return false;
+}
+JxlDecoderStatus JxlHipBatchOutBufferSizeScaled(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, size_t* size) {
+  if (!DownscaleOk(downscale, "JxlHipBatchOutBufferSizeScaled")) return JXL_DEC_ERROR;
+  if (downscale == 1) return JxlHipBatchOutBufferSize(h, i, format, size);
+  OutputSpec o;
+  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o)) return JXL_DEC_ERROR;
+  o.keep_orientation = h->keep_orientation;
+  o.downscale = 8;
+  *size = Batch::OutputSize(h->b->image(i).ih, o);
+  return JXL_DEC_SUCCESS;
+}
+JxlDecoderStatus JxlHipBatchSetOutputScaled(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale) {
+  if (!DownscaleOk(downscale, "JxlHipBatchSetOutputScaled")) return JXL_DEC_ERROR;
+  if (downscale == 1) return JxlHipBatchSetOutput(h, i, format, device_buffer);
+  OutputSpec o;
+  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o)) return JXL_DEC_ERROR;
+  o.device_ptr = device_buffer;
+  o.keep_orientation = h->keep_orientation;
+  o.downscale = 8;
+  try { h->b->SetOutput(i, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }   // ("unsupported: downscaled decode of ...")
 }
 void JxlHipBatchSetLaneStride(JxlHipBatch* h, int lf, int hf) {
   auto ok = [](int v) { return v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64; };
@@ -953,6 +979,7 @@ void JxlHipBatchSetOption(JxlHipBatch* h, const char* name, int value) {
   else if (n == "lf_wp_narrow_test") h->b->cfg.lf_wp_narrow_test = value != 0;
   else if (n == "debug_stop_after" && value >= 0 && value <= 5) h->b->cfg.debug_stop_after = value;
   else if (n == "keep_orientation") h->keep_orientation = value != 0;   // applies to outputs set afterwards
+  else if (n == "allow_partial") h->allow_partial = value != 0;         // applies to images added afterwards
   else if (n == "hf_block_threads" && value >= 64 && value <= 1024 && value % 64 == 0) h->b->cfg.hf_block_threads = value;
   // (rounded down to 16 bytes: the kernels put regions of their own behind the staged tables — HfDecodeSimtKernel its lane slots — that must stay aligned)
   else if (n == "lds_code_budget" && value >= 0 && value <= 128 * 1024) h->b->cfg.lds_code_budget = value & ~15;
@@ -1009,6 +1036,17 @@ int64_t JxlHipPipelineSubmit(JxlHipPipeline* h, const uint8_t* const* datas, con
     return h->p->Submit(datas, sizes, n, o, device_out, host_out, out_capacity);
   } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
 }
+int64_t JxlHipPipelineSubmitScaled(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                                   const size_t* out_capacity, int downscale) {
+  if (!DownscaleOk(downscale, "JxlHipPipelineSubmitScaled")) return -1;
+  if (downscale == 1) return JxlHipPipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity);
+  try {
+    OutputSpec o;
+    if (!h || !FormatToSpec(format, &o)) { SetLastError("JxlHipPipelineSubmitScaled: bad pixel format"); return -1; }
+    o.downscale = 8;
+    return h->p->Submit(datas, sizes, n, o, device_out, host_out, out_capacity);
+  } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
+}
 JxlDecoderStatus JxlHipPipelineWait(JxlHipPipeline* h, int64_t ticket, int* image_status, int n, float* end_ms) {
   try {
     PipelineJobResult r;
@@ -1055,6 +1093,25 @@ JxlDecoderStatus JxlHipImageOutSize(const uint8_t* data, size_t size, const JxlP
     std::shared_ptr<ImageShared> sh(new ImageShared());
     bool have_container = false, has_jbrd = false;
     if (!ExtractCodestream(data, size, &sh->cs, &have_container, &has_jbrd, nullptr)) return JXL_DEC_NEED_MORE_INPUT;
+    uint64_t bitpos = 0;
+    ParseImageHeader(sh->cs, &sh->ih, &bitpos);
+    sh->ih.have_container = have_container;
+    if (info) FillBasicInfo(sh->ih, info, false);
+    if (out_size) *out_size = Batch::OutputSize(sh->ih, o);
+    return JXL_DEC_SUCCESS;
+  } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
+}
+
+JxlDecoderStatus JxlHipImageOutSizeScaled(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, JxlBasicInfo* info, size_t* out_size) {
+  if (!DownscaleOk(downscale, "JxlHipImageOutSizeScaled")) return JXL_DEC_ERROR;
+  if (downscale == 1) return JxlHipImageOutSize(data, size, format, info, out_size);
+  try {
+    OutputSpec o;
+    if (!FormatToSpec(format, &o)) { SetLastError("bad pixel format"); return JXL_DEC_ERROR; }
+    o.downscale = 8;
+    std::shared_ptr<ImageShared> sh(new ImageShared());
+    bool have_container = false, has_jbrd = false;
+    (void)ExtractCodestream(data, size, &sh->cs, &have_container, &has_jbrd, nullptr);     // (a prefix of the file will do: the headers say the size)
     uint64_t bitpos = 0;
     ParseImageHeader(sh->cs, &sh->ih, &bitpos);
     sh->ih.have_container = have_container;
@@ -1139,9 +1196,12 @@ int JxlHipDebugDescribe(const uint8_t* data, size_t size, char* out, size_t cap)
                p.tree.nodes.size(), p.max_prop, (int)p.tree.uses_wp, (int)p.tree_code.use_prefix, (int)p.tree_code.lz77, p.local_streams.size() + p.NumLfLocal(), p.gtransforms.size(), p.sections.size());
       s += line;
       if (!p.modular) {
-        snprintf(line, sizeof line, "  quantizer global_scale=%u quant_lf=%u m_lf=%g,%g,%g x_qm=%u b_qm=%u cfl_base=%g,%g colour_factor=%u ycbcr=%d sampling=%u,%u,%u flags=%llu\n", p.global_scale, p.quant_lf,
+        // lf_part_end: where the LF part (LfGlobal, the LfGroups, HfGlobal) ends in the codestream — a prefix that long decodes at 1:8 (JxlHipBatchSetOutputScaled); 0: a one-section frame
+        uint64_t lf_part_end = 0;
+        for (size_t k = 0; !p.single_section && k < 2 + (size_t)p.num_lf_groups && k < p.sections.size(); k++) lf_part_end = std::max<uint64_t>(lf_part_end, p.sections[k].offset + p.sections[k].size);
+        snprintf(line, sizeof line, "  quantizer global_scale=%u quant_lf=%u m_lf=%g,%g,%g x_qm=%u b_qm=%u cfl_base=%g,%g colour_factor=%u ycbcr=%d sampling=%u,%u,%u flags=%llu lf_part_end=%llu\n", p.global_scale, p.quant_lf,
                  p.m_lf[0], p.m_lf[1], p.m_lf[2], p.x_qm_scale, p.b_qm_scale, p.base_x, p.base_b, p.color_factor, (int)p.do_ycbcr, p.jpeg_upsampling[0], p.jpeg_upsampling[1], p.jpeg_upsampling[2],
-                 (unsigned long long)p.flags);
+                 (unsigned long long)p.flags, (unsigned long long)lf_part_end);
         s += line;
         for (int k = 0; k < 17; k++) if (p.qspec[k].mode != 0) { snprintf(line, sizeof line, "  qtable kind=%d mode=%u raw_den=%g\n", k, p.qspec[k].mode, p.qspec[k].raw_den); s += line; }
         // uniform_cfg: every cluster shares one hybrid-uint configuration (the kernels' FastCode::cfg_uniform)

@@ -130,6 +130,8 @@ struct FrameDev {
                                   // write stage are done by the host-planned frame tail (kernels_features.hip) — multi-frame images, image features
   float inverse_gamma;            // colour modes 4 / 5 (XYB -> gamma / Rec.709 transfer)
   float hdr_par[5];               // colour mode 6 (PQ): [0] intensity_target / 10000; 7 (HLG): [0] OOTF exponent, [1] apply it, [2..4] luminances
+  uint32_t lf_only;               // 1:8 decode (OutputSpec::downscale == 8): the output is the LF image, one pixel per 8x8 block, written by LfOutputKernel — img_w / img_h / out_stride
+                                  // describe that bw x bh picture; the HF stage, the IDCT, the filters and OutputKernel leave the frame alone, it has no coefficient or pixel planes
 };
 
 struct LaunchCfg {
@@ -220,6 +222,8 @@ struct FilterPlan {
   int max_out_w = 0, max_out_h = 0; bool any_fused = false, any_unfused = false, any_gab = false; int max_epf = 0; };   // over the VarDCT frames of a batch
 void LaunchFilters(const FrameDev* frames, int nframes, int max_w, int max_h, const FilterPlan& fp, const LaunchCfg& cfg, void* stream);
 void LaunchOutput(const FrameDev* frames, int nframes, int max_w, int max_h, const FilterPlan& fp, const LaunchCfg& cfg, void* stream);
+// 1:8 decode: the LF image of every frame with lf_only set -> colour transform -> the caller's layout (LfOutputKernel); needs the LF post-processing only
+void LaunchLfOutput(const FrameDev* frames, int nframes, int max_bw, int max_bh, void* stream);
 // Modular stages
 struct ModOutputArgs { const int32_t* color[3]; const int32_t* alpha; uint32_t ncolor; float color_factor, alpha_factor; uint32_t float_bits, float_exp_bits; };   // float_bits != 0: colour samples are float bit patterns
 void LaunchModularGlobal(const FrameDev* frames, int nframes, const LaunchCfg& cfg, void* stream);

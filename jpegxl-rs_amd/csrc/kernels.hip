@@ -3260,7 +3260,7 @@ __device__ static const uint8_t kNzCtx[64] = {0,   0,   31,  62,  62,  93,  93, 
 // write; symbols are then read bit by bit through the canonical-code tables in global memory (jxl_dev.h ReadSymbol)
 __global__ __launch_bounds__(512) void HfDecodeKernel(const FrameDev* __restrict__ frames, int lane_stride, uint32_t lds_bytes, int only_prefix) {
   const FrameDev& f = frames[blockIdx.y];
-  if (f.is_modular || FrameFailed(f)) return;
+  if (f.is_modular || f.lf_only || FrameFailed(f)) return;
   const bool pfx = f.ac_code.use_prefix != 0, lz77 = f.ac_code.lz77 != 0;
   const bool slow = pfx || lz77;                                       // symbols through the general reader (tables in global memory)
   if (only_prefix && !slow) return;
@@ -3474,7 +3474,7 @@ template <bool ALL_LDS, bool SUB, bool MULTI> __global__ __launch_bounds__(1024)
   // would part ways in front of the barriers below; the 8 spare bytes behind the 39 order pointers carry it)
   if (threadIdx.x == 0) StS<uint32_t>(kSimtOrdOff + 312, __hip_atomic_load(f.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   __syncthreads();
-  if (f.is_modular || LdS<uint32_t>(kSimtOrdOff + 312) != 0) return;
+  if (f.is_modular || f.lf_only || LdS<uint32_t>(kSimtOrdOff + 312) != 0) return;
   // prefix-coded frames: HfDecodeKernel, launched beside this one — unless they are progressive or chroma-subsampled: those are walked here (the
   // general instantiation), their symbols read bit by bit through the canonical-code tables in global memory (jxl_dev.h ReadSymbol)
   bool any_pfx = f.ac_code.use_prefix != 0 || f.ac_code.lz77 != 0;     // (prefix codes or LZ77: the general symbol reader)
@@ -3714,7 +3714,7 @@ constexpr uint32_t kHwCodeOff = kHwOrdOff + 39 * 128;
 constexpr uint32_t kHwWaves = 4;
 __global__ __launch_bounds__(64 * kHwWaves) void HfDecodeWaveKernel(const FrameDev* __restrict__ frames, uint32_t lds_bytes) {
   const FrameDev& f = frames[blockIdx.y];
-  if (f.is_modular || FrameFailed(f)) return;
+  if (f.is_modular || f.lf_only || FrameFailed(f)) return;
   if (blockIdx.x * kHwWaves >= f.num_groups) return;
   const PassDev& pd = f.passes[0];
   FastCode code;
@@ -4233,6 +4233,7 @@ __device__ __forceinline__ uint32_t Log2Cov8(uint32_t n) { return n == 1 ? 0u : 
 __global__ __launch_bounds__(256) void IdctKernel(const FrameDev* __restrict__ frames, int force_generic) {
   const FrameDev& f = frames[blockIdx.y];
   if (f.is_modular || f.subsampled || ((*f.frame_flags & 1) == 0 && !force_generic) || FrameFailed(f)) return;   // regular frames take IdctTileKernel
+  if (f.lf_only) return;                                                                                                         // (1:8 decode: no coefficients, no planes)
   const uint32_t g = blockIdx.x;
   if (g >= f.num_groups) return;
   const uint32_t gx = g % f.xgroups, gy = g / f.xgroups;
@@ -4372,7 +4373,7 @@ __device__ __forceinline__ int Log2Cov(int n) { return n == 1 ? 0 : n == 2 ? 1 :
 
 __global__ __launch_bounds__(256) void BigIdctKernel(const FrameDev* __restrict__ frames) {
   const FrameDev& f = frames[blockIdx.y];
-  if (f.is_modular || f.subsampled || (*f.frame_flags & 2) == 0 || FrameFailed(f)) return;
+  if (f.is_modular || f.lf_only || f.subsampled || (*f.frame_flags & 2) == 0 || FrameFailed(f)) return;
   const uint32_t g = blockIdx.x;
   if (g >= f.num_groups) return;
   extern __shared__ __align__(16) float s_big[];
@@ -4458,7 +4459,7 @@ __global__ __launch_bounds__(256) void BigIdctKernel(const FrameDev* __restrict_
 // brought to full resolution afterwards (ChromaUpsampleKernel).  Same arithmetic as the 8x8 path of IdctKernel (rows, then columns).
 __global__ __launch_bounds__(256) void IdctSubsampledKernel(const FrameDev* __restrict__ frames) {
   const FrameDev& f = frames[blockIdx.y];
-  if (f.is_modular || !f.subsampled || FrameFailed(f)) return;
+  if (f.is_modular || f.lf_only || !f.subsampled || FrameFailed(f)) return;
   const uint32_t g = blockIdx.x;
   if (g >= f.num_groups) return;
   const uint32_t gx = g % f.xgroups, gy = g / f.xgroups;
@@ -4498,7 +4499,7 @@ __global__ __launch_bounds__(256) void IdctSubsampledKernel(const FrameDev* __re
 constexpr int kSubTileBx = 8, kSubTileBy = 4, kSubCell = 73;            // (cells of 8 rows x 9 floats + 1: rows and columns of neighbouring blocks fall on different banks)
 __global__ __launch_bounds__(256) void IdctSubsampledTileKernel(const FrameDev* __restrict__ frames) {
   const FrameDev& f = frames[blockIdx.z];
-  if (f.is_modular || !f.subsampled || FrameFailed(f)) return;
+  if (f.is_modular || f.lf_only || !f.subsampled || FrameFailed(f)) return;
   const uint32_t c = blockIdx.y, hs = f.hs[c], vs = f.vs[c];
   const uint32_t cbw = f.bw >> hs, cbh = f.bh >> vs;                     // the channel's own block grid (bw, bh are multiples of the largest cell)
   const uint32_t tiles_x = (cbw + kSubTileBx - 1) / kSubTileBx, tiles_y = (cbh + kSubTileBy - 1) / kSubTileBy;
@@ -4614,7 +4615,7 @@ template <int R, int PITCH> __device__ __forceinline__ void TileColPass(float* c
 template <int TB, bool SPECIAL> __global__ __launch_bounds__(TB == 8 ? 256 : JXL_IDCT_T4, TB == 8 ? 2 : JXL_IDCT_MINW) JXL_IDCT_VGPR_ATTR void IdctTileKernel(const FrameDev* __restrict__ frames, int tiles_x, int force_generic) {
   constexpr int kTilePitch = TileGeom<TB>::kPitch, kTilePlane = TileGeom<TB>::kPlane, kNB = TB * TB;
   const FrameDev& f = frames[blockIdx.y];
-  if (f.is_modular || f.subsampled || (*f.frame_flags & 1) != 0 || (force_generic & 3)) return;
+  if (f.is_modular || f.lf_only || f.subsampled || (*f.frame_flags & 1) != 0 || (force_generic & 3)) return;
   if (((*f.frame_flags & 4) != 0) != (TB == 8)) return;     // frames with a varblock that no 32x32 tile contains take the 64x64 tiles
   if (((*f.frame_flags & 8) != 0) != SPECIAL) return;
   const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
@@ -4903,7 +4904,7 @@ __device__ __forceinline__ bool GabFolded(const FrameDev& f, int unfused, int fu
 
 __global__ void GaborishKernel(const FrameDev* __restrict__ frames, int unfused, int fuse_out) {
   const FrameDev& f = frames[blockIdx.z];
-  if (f.is_modular || !f.gab || FusedEligible(f, unfused) || GabFolded(f, unfused, fuse_out)) return;
+  if (f.is_modular || f.lf_only || !f.gab || FusedEligible(f, unfused) || GabFolded(f, unfused, fuse_out)) return;
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
   const int w = (int)f.width, h = (int)f.height;
   if (x >= w || y >= h) return;
@@ -5043,7 +5044,7 @@ __device__ __forceinline__ void StorePixel(const FrameDev& f, int x, int y, floa
 // Channel 3 = the alpha extra channel (int samples scaled to float first).
 __global__ void UpsampleKernel(const FrameDev* __restrict__ frames) {
   const FrameDev& f = frames[blockIdx.z];
-  if (f.is_modular || f.upsampling == 1 || f.post_mode) return;
+  if (f.is_modular || f.lf_only || f.upsampling == 1 || f.post_mode) return;
   const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y * blockDim.y + threadIdx.y;
   if (ox >= (int)f.img_w || oy >= (int)f.img_h) return;
   const int up = (int)f.upsampling, N = up / 2;
@@ -5109,13 +5110,14 @@ __device__ __forceinline__ void ColorAndStore(const FrameDev& f, int x, int y, f
 // Sample (x, y) of channel c of a chroma-subsampled frame at full resolution (stage_chroma_upsampling.cc: horizontal, then vertical, each with the (1/4, 3/4) kernel — out[2x] = 0.25 in[x-1]
 // + 0.75 in[x], out[2x+1] = 0.25 in[x+1] + 0.75 in[x] —, neighbours clamped at the channel's own edges; the channel sits packed in the top-left corner of its plane).  The arithmetic and
 // its order are ChromaUpsampleKernel's (kernels_features.hip: the frame tail of images with features): the vertical step works on horizontally upsampled rows, exactly as two stages would.
-__device__ __forceinline__ float SubsampledAt(const FrameDev& f, const float* __restrict__ plane, int c, uint32_t x, uint32_t y) {
-  const uint32_t hs = f.hs[c], vs = f.vs[c];
-  if (!(hs | vs)) return plane[(size_t)y * f.plane_stride + x];
-  const uint32_t cw = (f.width + (1u << hs) - 1) >> hs, ch = (f.height + (1u << vs) - 1) >> vs;
+// (the rule itself, on any grid: `plane` holds the channel packed top-left with row pitch `stride`; width x height is the size of the FULL grid that (x, y) addresses —
+// pixels for SubsampledAt, LF samples for LfOutputKernel)
+__device__ __forceinline__ float SubsampledSample(const float* __restrict__ plane, uint32_t stride, uint32_t hs, uint32_t vs, uint32_t width, uint32_t height, uint32_t x, uint32_t y) {
+  if (!(hs | vs)) return plane[(size_t)y * stride + x];
+  const uint32_t cw = (width + (1u << hs) - 1) >> hs, ch = (height + (1u << vs) - 1) >> vs;
   const uint32_t sx = x >> hs, sy = y >> vs;
   auto hval = [&](uint32_t row) -> float {
-    const float* in = plane + (size_t)row * f.plane_stride;
+    const float* in = plane + (size_t)row * stride;
     if (!hs) return in[x];
     const float mid = in[sx] * 0.75f;
     const uint32_t nb = (x & 1) ? min(sx + 1, cw - 1) : (sx ? sx - 1 : 0);
@@ -5126,9 +5128,12 @@ __device__ __forceinline__ float SubsampledAt(const FrameDev& f, const float* __
   const uint32_t nb = (y & 1) ? min(sy + 1, ch - 1) : (sy ? sy - 1 : 0);
   return fmaf(0.25f, hval(nb), mid);
 }
+__device__ __forceinline__ float SubsampledAt(const FrameDev& f, const float* __restrict__ plane, int c, uint32_t x, uint32_t y) {
+  return SubsampledSample(plane, f.plane_stride, f.hs[c], f.vs[c], f.width, f.height, x, y);
+}
 __global__ void OutputKernel(const FrameDev* __restrict__ frames, int unfused, int fuse_out) {
   const FrameDev& f = frames[blockIdx.z];
-  if (f.is_modular || f.post_mode || FusedEligible(f, unfused) || EpfWritesOutput(f, unfused, fuse_out)) return;
+  if (f.is_modular || f.post_mode || f.lf_only || FusedEligible(f, unfused) || EpfWritesOutput(f, unfused, fuse_out)) return;
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
   if (x >= (int)f.img_w || y >= (int)f.img_h) return;
   float X, Y, B, A = 1.0f;
@@ -5151,6 +5156,27 @@ __global__ void OutputKernel(const FrameDev* __restrict__ frames, int unfused, i
     if (f.alpha_plane) A = (float)f.alpha_plane[(size_t)y * f.width + x] * f.alpha_factor;
   }
   ColorAndStore(f, x, y, X, Y, B, A);
+}
+
+// 1:8 decode (FrameDev::lf_only): output pixel (bx, by) is the frame's LF sample (bx, by) — after the adaptive smoothing, i.e. what the IDCT stage reads as its LLF
+// input (lf_tmp: LfSmoothKernel copies where it does not smooth) — through the per-pixel tail of the full decode.  Gaborish, EPF and noise are defined on full-resolution
+// pixels and are not applied.  Chroma-subsampled frames: the (1/4, 3/4) rule of SubsampledAt on the LF grid.  One thread per LF sample, the frame on blockIdx.z; the host
+// set img_w x img_h / out_stride to the ceil(width / 8) x ceil(height / 8) picture, so OutPixelPtr applies the orientation to it as it does to the full one.
+__global__ void LfOutputKernel(const FrameDev* __restrict__ frames) {
+  const FrameDev& f = frames[blockIdx.z];
+  if (f.is_modular || !f.lf_only || FrameFailed(f)) return;
+  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+  if (x >= f.img_w || y >= f.img_h || x >= f.bw || y >= f.bh) return;
+  float X, Y, B;
+  if (f.subsampled) {
+    X = SubsampledSample(f.lf_tmp[0], f.bw, f.hs[0], f.vs[0], f.img_w, f.img_h, x, y);
+    Y = SubsampledSample(f.lf_tmp[1], f.bw, f.hs[1], f.vs[1], f.img_w, f.img_h, x, y);
+    B = SubsampledSample(f.lf_tmp[2], f.bw, f.hs[2], f.vs[2], f.img_w, f.img_h, x, y);
+  } else {
+    const size_t o = (size_t)y * f.bw + x;
+    X = f.lf_tmp[0][o]; Y = f.lf_tmp[1][o]; B = f.lf_tmp[2][o];
+  }
+  ColorAndStore(f, (int)x, (int)y, X, Y, B, 1.0f);
 }
 
 // =====================================================================================================================
@@ -5209,7 +5235,7 @@ __device__ __forceinline__ bool EpfPasses12Fused(const FrameDev& f, int unfused,
 template <int PASS> __global__ __launch_bounds__(256) void EpfTileKernel(const FrameDev* __restrict__ frames, int unfused, int tiles_x, int fuse_out) {
   const FrameDev& f = frames[blockIdx.z];
   constexpr int stage = PASS + 1;
-  if (f.is_modular || !FilterStageActive(f, stage) || FusedEligible(f, unfused)) return;
+  if (f.is_modular || f.lf_only || !FilterStageActive(f, stage) || FusedEligible(f, unfused)) return;
   if (PASS >= 1 && EpfPasses12Fused(f, unfused, fuse_out)) return;          // EpfTile12Kernel
   const int w = (int)f.width, h = (int)f.height;
   const uint32_t tile = XcdContiguous(blockIdx.x, gridDim.x);
@@ -5295,7 +5321,7 @@ template <int PASS> __global__ __launch_bounds__(256) void EpfTileKernel(const F
 // into a second LDS tile, and pass 2 runs out of that.  One pass over the planes less; per pixel the arithmetic of the two separate passes (EpfPixel).
 __global__ __launch_bounds__(256) void EpfTile12Kernel(const FrameDev* __restrict__ frames, int unfused, int tiles_x, int fuse_out) {
   const FrameDev& f = frames[blockIdx.z];
-  if (f.is_modular || FusedEligible(f, unfused) || !EpfPasses12Fused(f, unfused, fuse_out)) return;
+  if (f.is_modular || f.lf_only || FusedEligible(f, unfused) || !EpfPasses12Fused(f, unfused, fuse_out)) return;
   const int w = (int)f.width, h = (int)f.height;
   const uint32_t tile = XcdContiguous(blockIdx.x, gridDim.x);
   const int x0 = (int)(tile % (uint32_t)tiles_x) * kEtT, y0 = (int)(tile / (uint32_t)tiles_x) * kEtT;
@@ -5375,7 +5401,7 @@ __device__ __forceinline__ uint32_t XcdContiguous(uint32_t bid, uint32_t nwg) {
 
 __global__ __launch_bounds__(256) void FusedGabEpf1OutKernel(const FrameDev* __restrict__ frames, int unfused, int tiles_x, int swizzle) {
   const FrameDev& f = frames[blockIdx.z];
-  if (f.is_modular || !FusedEligible(f, unfused)) return;
+  if (f.is_modular || f.lf_only || !FusedEligible(f, unfused)) return;
   const int w = (int)f.width, h = (int)f.height;
   const uint32_t tile = swizzle ? XcdContiguous(blockIdx.x, gridDim.x) : blockIdx.x;
   const int x0 = (int)(tile % (uint32_t)tiles_x) * kFtW, y0 = (int)(tile / (uint32_t)tiles_x) * kFtH;
@@ -6254,7 +6280,7 @@ void LaunchLfPost(const FrameDev* frames, int nframes, int max_bw, int max_bh, i
 // behind the HF stage — the coefficient planes are clean again for whichever decode uses them next (pipelines rotate a few sets between many batches).
 __global__ __launch_bounds__(256) void ZeroFailedCoefKernel(const FrameDev* __restrict__ frames) {
   const FrameDev& f = frames[blockIdx.y];
-  if (f.is_modular || !FrameFailed(f)) return;
+  if (f.is_modular || f.lf_only || !FrameFailed(f)) return;
   const size_t n16 = (size_t)f.num_groups * 65536 / 4;
   for (int c = 0; c < 3; c++) {
     int4* p = reinterpret_cast<int4*>(f.coeff[c]);
@@ -6424,6 +6450,10 @@ void LaunchOutput(const FrameDev* frames, int nframes, int max_w, int max_h, con
   dim3 block(64, 4), grid(DivUp(ow, 64), DivUp(oh, 4), nframes);
   if (fp.any_upsampled) hipLaunchKernelGGL(UpsampleKernel, grid, block, 0, (hipStream_t)stream, frames);
   hipLaunchKernelGGL(OutputKernel, grid, block, 0, (hipStream_t)stream, frames, cfg.force_unfused_filters, cfg.debug_stop_after ? 0 : 1);
+}
+void LaunchLfOutput(const FrameDev* frames, int nframes, int max_bw, int max_bh, void* stream) {
+  if (nframes <= 0 || max_bw <= 0 || max_bh <= 0) return;
+  hipLaunchKernelGGL(LfOutputKernel, dim3(DivUp(max_bw, 64), DivUp(max_bh, 4), nframes), dim3(64, 4), 0, (hipStream_t)stream, frames);
 }
 void LaunchModularGlobal(const FrameDev* frames, int nframes, const LaunchCfg& cfg, void* stream);
 // LDS plan of the Modular kernels: per-wavefront regions, tree region (whole tree or pruned per-wavefront slices), the

@@ -242,7 +242,7 @@ void Pipeline::PrepareJob(Job* j, int worker) {
     bt.Reset();
     vec<int> index;
     std::vector<std::string> errors;
-    bt.AddImagesTolerant(j->datas.data(), j->sizes.data(), n, opt_.parse_threads, &index, &errors);
+    bt.AddImagesTolerant(j->datas.data(), j->sizes.data(), n, opt_.parse_threads, &index, &errors, /*for_downscale=*/j->spec.downscale == 8);   // (a 1:8 job needs the LF part of a stream only; what that decode does not take fails alone, here)
     t_parse = std::chrono::steady_clock::now();
     j->batch_index.assign(index.begin(), index.end());
     bool any = false;

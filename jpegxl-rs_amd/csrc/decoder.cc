@@ -774,6 +774,14 @@ size_t Batch::OutputSizeOf(int i, const OutputSpec& o) const {
   return OutputSize(dims, o);
 }
 static float IntMul(const OutputSpec& o) { const uint32_t full = o.type == 0 ? 8 : 16; const uint32_t b = o.int_bits && o.int_bits < full ? o.int_bits : full; return (float)((1u << b) - 1); }
+// Where the write stage puts the image's pixels (work: the arena that holds the output unless the caller named a device buffer)
+static OutputDesc FillOutput(const ImageEntry& e, uint8_t* work) {
+  OutputDesc d;
+  d.out = (uint8_t*)(e.out.device_ptr ? e.out.device_ptr : work + e.off_out);
+  d.out_stride = e.out_stride; d.out_channels = e.out.num_channels; d.out_type = e.out.type; d.out_big_endian = e.out.big_endian; d.out_int_mul = IntMul(e.out);
+  d.out_orient = e.out.keep_orientation ? 1 : e.ih.orientation; d.is_gray = e.ih.color_space == 1;
+  return d;
+}
 // What the 1:8 decode takes: single-frame VarDCT images that carry their own LF coefficients and end in their own pixels (no frame tail).
 static std::string DownscaleRefusalOf(int num_units, const ImageEntry& e) {
   const FramePlan& p = e.plan;
@@ -1355,13 +1363,10 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     f.status = (uint32_t*)(dwork_ + status_off_) + i;
     f.frame_flags = (uint32_t*)(dwork_ + flags_off) + i;
     f.hf_written = (uint32_t*)(dwork_ + hfw_off_) + i;
-    f.out = (uint8_t*)(e.out.device_ptr ? e.out.device_ptr : dwork_ + e.off_out);
-    f.out_stride = e.out_stride; f.out_channels = e.out.num_channels; f.out_type = e.out.type; f.out_big_endian = e.out.big_endian; f.out_int_mul = IntMul(e.out);
-    f.out_orient = e.out.keep_orientation ? 1 : e.ih.orientation;
+    f.od = FillOutput(e, dwork_);
     f.upsampling = p.upsampling; f.img_w = e.ih.xsize; f.img_h = e.ih.ysize;
     if (scaled(i)) { f.lf_only = 1; f.img_w = (p.width + 7) / 8; f.img_h = (p.height + 7) / 8; }     // (the picture LfOutputKernel writes; out_stride is SetOutput's, of the same picture)
     if (p.upsampling > 1) { f.up_weights = (const float*)(cbase + c.up_weights); for (int k = 0; k < 4; k++) f.up_plane[k] = (float*)(dbig_ + o.up_plane[k]); }
-    f.is_gray = e.ih.color_space == 1;
     f.post_mode = e.complex ? 1 : 0;
     f.lz_window = o.lz_window == (size_t)-1 ? nullptr : (uint32_t*)(dwork_ + o.lz_window);
     f.lz_ac_window = o.lz_ac_window == (size_t)-1 ? nullptr : (uint32_t*)(dwork_ + o.lz_ac_window);
@@ -1990,8 +1995,8 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
           if (!p.hs[c] && !p.vs[c]) continue;
           if (cb.pb[c] == (size_t)-1) throw ParseError("chroma upsampling needs the second plane set", false);
           const size_t src = cur[c], dst = cb.pb[c];
-          const uint32_t ccw = (cw + (1u << p.hs[c]) - 1) >> p.hs[c], cch = (ch + (1u << p.vs[c]) - 1) >> p.vs[c], chs = p.hs[c], cvs = p.vs[c];
-          post_ops_.push_back([=](void* st) { LaunchChromaUpsample(B(src), cur_stride, B(dst), cur_stride, ccw, cch, chs, cvs, cw, ch, st); });
+          const uint32_t chs = p.hs[c], cvs = p.vs[c];
+          post_ops_.push_back([=](void* st) { LaunchChromaUpsample(B(src), cur_stride, B(dst), cur_stride, chs, cvs, cw, ch, st); });
           cur[c] = dst;
         }
       }
@@ -2179,7 +2184,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
           FillColor(ih, p.do_ycbcr, fd);
           for (int k = 0; k < 9; k++) ca.opsin_inv[k] = fd.opsin_inv[k];
           for (int k = 0; k < 3; k++) { ca.neg_bias[k] = fd.neg_bias[k]; ca.neg_bias_cbrt[k] = fd.neg_bias_cbrt[k]; }
-          ca.tf_kind = fd.color_mode == 0 ? 0 : fd.color_mode == 1 ? 1 : fd.color_mode == 4 ? 2 : fd.color_mode == 5 ? 3 : fd.color_mode == 6 ? 4 : 5;
+          ca.tf_kind = fd.color_mode;
           for (int k = 0; k < 5; k++) ca.hdr_par[k] = fd.hdr_par[k];
           ca.inverse_gamma = fd.inverse_gamma;
           // spot colours are mixed in linear light when the frame goes straight to the output (dec_cache.cc PreparePipeline: XYB stage,
@@ -2202,9 +2207,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
           break;
         }
         wa.img_w = fw; wa.img_h = fh;
-        wa.out = (uint8_t*)(first.out.device_ptr ? first.out.device_ptr : dwork_ + first.off_out);
-        wa.out_stride = first.out_stride; wa.out_channels = first.out.num_channels; wa.out_type = first.out.type; wa.out_big_endian = first.out.big_endian; wa.out_int_mul = IntMul(first.out);
-        wa.out_orient = first.out.keep_orientation ? 1 : ih.orientation; wa.is_gray = ih.color_space == 1;
+        wa.od = FillOutput(first, dwork_);
         if (have_deferred_tf) {          // (the transfer function had been put off for a spot-colour stage this output does not run)
           ColorArgs ta = deferred_tf;
           for (int c = 0; c < 3; c++) { ta.src[c] = B(cur[c]); ta.dst[c] = B(cur[c]); }
@@ -2318,9 +2321,8 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         break;
       }
       wa.img_w = ih.xsize; wa.img_h = ih.ysize;
-      wa.out = (uint8_t*)(first.out.device_ptr ? first.out.device_ptr : dwork_ + first.off_out) + (all_frames ? (size_t)slot * (first.out_size + 64) : 0);
-      wa.out_stride = first.out_stride; wa.out_channels = first.out.num_channels; wa.out_type = first.out.type; wa.out_big_endian = first.out.big_endian; wa.out_int_mul = IntMul(first.out);
-      wa.out_orient = first.out.keep_orientation ? 1 : ih.orientation; wa.is_gray = ih.color_space == 1;
+      wa.od = FillOutput(first, dwork_);
+      if (all_frames) wa.od.out += (size_t)slot * (first.out_size + 64);
       post_ops_.push_back([=](void* st) { LaunchWrite(wa, st); });
       if (all_frames && slot + 1 < (int)first.deliver_frames.size()) continue;
       break;                      // (frames behind the delivered one: nothing of theirs is needed)

@@ -21,6 +21,16 @@ struct PassDev { DevCode code; const uint16_t* orders[39]; uint32_t shift; uint3
 // Modular frames, where every section starts with its stream).
 struct ModLocalDev { const TreeNode* tree; uint32_t tree_nodes, uses_wp, max_prop, pad; uint64_t data_bitpos; DevCode code; };
 
+// Where and how the write stage puts an image's pixels (pixel_ops.h StorePixel), filled by decoder.cc FillOutput; the image size travels beside it.
+struct OutputDesc {
+  uint8_t* out;
+  uint64_t out_stride;            // bytes per row
+  uint32_t out_channels, out_type /*0 u8 1 u16 2 f32 3 f16*/, out_big_endian;
+  float out_int_mul;              // integer output: sample = round(clamp(v, 0, 1) x this) — 255 / 65535, or 2^bits - 1 (JxlDecoderSetImageOutBitDepth)
+  uint32_t out_orient;            // 1..8: orientation applied while writing (1 = none)
+  uint32_t is_gray;               // grey image: one- and two-channel output takes R (= G = B), of a colour image G
+};
+
 struct FrameDev {
   // geometry
   uint32_t width, height, bw, bh, xgroups, ygroups, num_groups, xlfgroups, num_lf_groups, cw, ch;
@@ -67,7 +77,6 @@ struct FrameDev {
   float epf_sm[3], epf_bsm[3];    // per pass sad multipliers (normal, border)
   float opsin_inv[9], neg_bias[3], neg_bias_cbrt[3];
   uint32_t color_mode;            // 0: XYB->sRGB, 1: XYB->linear, 2: YCbCr->RGB, 3: none (RGB as is), 4: XYB->gamma (FastPowf), 5: XYB->Rec.709, 6: XYB->PQ, 7: XYB->HLG
-  uint32_t is_gray;
   // VarDCT buffers
   int32_t* lfq[3];
   float* lf[3];
@@ -101,12 +110,7 @@ struct FrameDev {
   uint64_t* hf_end_bitpos;        // VarDCT frames with extra channels: where the HF coefficient stream of PassGroup (mod_pass + k, g) ended, at [k * num_groups + g] (its Modular part starts there)
   const int32_t* alpha_plane;     // VarDCT frames: decoded alpha extra channel (image-sized), or null
   float alpha_factor;             // 1 / (2^bits - 1)
-  // output
-  uint8_t* out;
-  uint64_t out_stride;            // bytes per row
-  uint32_t out_channels, out_type /*0 u8 1 u16 2 f32 3 f16*/, out_big_endian;
-  float out_int_mul;              // integer output: sample = round(clamp(v, 0, 1) x this) — 255 / 65535, or 2^bits - 1 (JxlDecoderSetImageOutBitDepth)
-  uint32_t out_orient;            // 1..8: orientation applied while writing (1 = none)
+  OutputDesc od;                  // output
   // upsampling (frame coded at 1/upsampling of the image size): width/height above are the CODED size
   uint32_t upsampling, img_w, img_h;   // img_*: image size the write stage covers (= width/height when upsampling == 1)
   const float* up_weights;        // 15 / 55 / 210 coefficients of the symmetric (5N x 5N) kernel matrix, N = upsampling / 2
@@ -128,7 +132,7 @@ struct FrameDev {
   uint32_t* lz_window;            // LZ77-coded Modular streams: 2^20-entry windows, one per stream (global, then LfGroup / PassGroup units)
   uint32_t post_mode;             // 1: the frame ends in its float planes (after the restoration filters); upsampling, colour transform and the
                                   // write stage are done by the host-planned frame tail (kernels_features.hip) — multi-frame images, image features
-  float inverse_gamma;            // colour modes 4 / 5 (XYB -> gamma / Rec.709 transfer)
+  float inverse_gamma;            // colour mode 4 (XYB -> gamma transfer)
   float hdr_par[5];               // colour mode 6 (PQ): [0] intensity_target / 10000; 7 (HLG): [0] OOTF exponent, [1] apply it, [2..4] luminances
   uint32_t lf_only;               // 1:8 decode (OutputSpec::downscale == 8): the output is the LF image, one pixel per 8x8 block, written by LfOutputKernel — img_w / img_h / out_stride
                                   // describe that bw x bh picture; the HF stage, the IDCT, the filters and OutputKernel leave the frame alone, it has no coefficient or pixel planes
@@ -237,7 +241,8 @@ struct SqueezeBatch { const int32_t* avg[kSqueezeBatch]; const int32_t* res[kSqu
 void LaunchModInvSqueezeBatch(const SqueezeBatch& b, int n, int horizontal, uint32_t aw, uint32_t ah, uint32_t rw, uint32_t rh, void* stream);
 void LaunchModRct(int32_t* a, int32_t* b, int32_t* c, size_t n, uint32_t rct_type, void* stream);
 void LaunchModPalette(const int32_t* pal, int32_t* const* out, uint32_t nb_colors, uint32_t num_c, uint32_t bit_depth, size_t n, void* stream);
-void LaunchChromaUpsample(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t cw, uint32_t ch, uint32_t hs, uint32_t vs, uint32_t out_w, uint32_t out_h, void* stream);
+// a channel subsampled by (hs, vs), packed top-left in src -> out_w x out_h samples in dst (pixel_ops.h SubsampledSample)
+void LaunchChromaUpsample(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t hs, uint32_t vs, uint32_t out_w, uint32_t out_h, void* stream);
 void LaunchModPaletteDelta(const int32_t* pal, int32_t* const* out, uint32_t nb_colors, uint32_t num_c, uint32_t bit_depth, uint32_t nb_deltas, uint32_t predictor,
                            uint32_t w, uint32_t h, const WPHeader& wp, int32_t* wp_scratch, uint32_t wp_stride, void* stream);
 void LaunchModOutput(const FrameDev* frames, int fidx, const ModOutputArgs& a, int w, int h, void* stream);
@@ -249,7 +254,7 @@ struct SplineSegmentDev;   // host_parse.h
 struct PatchEntryDev { const float* src[3]; const float* esrc[4]; uint32_t src_stride, esrc_stride; int32_t x, y; uint32_t xs, ys; uint32_t mode[5]; uint32_t pad; };
 struct PatchFrameArgs { float* p[3]; float* ec[4]; uint32_t stride, ec_stride, w, h, num_extra, premul_mask; };
 struct NoiseArgs { float* p[3]; uint32_t stride, w, h; float* noise[3]; uint32_t noise_stride, group_dim, visible_frame_index, nonvisible_frame_index; float lut[8]; float ytox, ytob; };
-// mode: 3 = transfer function only (after a spot-colour stage in linear light); 0 XYB -> linear -> transfer function (tf_kind 0 sRGB, 1 linear, 2 gamma, 3 Rec.709, 4 PQ, 5 HLG), 1 YCbCr -> RGB, 2 copy
+// mode: 3 = transfer function only (after a spot-colour stage in linear light); 0 XYB -> linear -> transfer function (tf_kind: FrameDev::color_mode's values 0, 1, 4..7), 1 YCbCr -> RGB, 2 copy
 struct ColorArgs { const float* src[3]; float* dst[3]; uint32_t src_stride, dst_stride, w, h, mode, tf_kind; float inverse_gamma, opsin_inv[9], neg_bias[3], neg_bias_cbrt[3], hdr_par[5]; };
 // mode[k] = BlendMode | alpha channel << 8 | clamp << 16; bg pointers are null when the source slot is empty (treated as zeros)
 struct BlendArgs {
@@ -258,7 +263,7 @@ struct BlendArgs {
   const float* bg_ec[4]; const float* bg_ec_alpha[4]; uint32_t bg_ec_stride[4];
   float* canvas[3]; float* canvas_ec[4]; uint32_t canvas_stride, canvas_ec_stride, img_w, img_h, num_extra, premul_mask; uint32_t mode[5];
 };
-struct WriteArgs { const float* p[3]; const float* alpha; uint32_t stride, alpha_stride, img_w, img_h; uint8_t* out; uint64_t out_stride; uint32_t out_channels, out_type, out_big_endian, out_orient, is_gray, unpremul; float out_int_mul; };
+struct WriteArgs { const float* p[3]; const float* alpha; uint32_t stride, alpha_stride, img_w, img_h, unpremul; OutputDesc od; };
 // ---- images with more than four extra channels: the extra-channel half of the frame tail reads a per-frame channel table in device memory
 // (built by Batch::PlanPostOps) instead of pointers inlined into the argument blocks above; the kernels run over (channel, y, x) with the
 // channel on blockIdx.z.  Per-sample arithmetic is that of the inlined forms (shared device functions).

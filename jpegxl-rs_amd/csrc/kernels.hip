@@ -5,6 +5,7 @@
 // Compiled with -ffp-contract=off: every fused multiply-add is an explicit fmaf so results are bit-identical to the
 // CPU oracle's (and to what libjxl's MulAdd does on FMA hardware).
 #include "kernels.h"
+#include "pixel_ops.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <algorithm>
@@ -4874,10 +4875,6 @@ template <int TB, bool SPECIAL> __global__ __launch_bounds__(TB == 8 ? 256 : JXL
 // =====================================================================================================================
 // K_gab / K_epf: loop restoration filters on the (w x h) image with mirrored borders
 // =====================================================================================================================
-__device__ __forceinline__ int MirrorD(int x, int size) {
-  while (x < 0 || x >= size) x = x < 0 ? -x - 1 : 2 * size - 1 - x;
-  return x;
-}
 __device__ __forceinline__ int FilterStagesBefore(const FrameDev& f, int stage, bool gab_folded = false) {  // stage: 0 gab, 1 epf0, 2 epf1, 3 epf2; gab_folded: gaborish runs inside the first EPF pass (no plane of its own)
   int n = 0;
   if (stage > 0 && f.gab && !gab_folded) n++;
@@ -4922,101 +4919,8 @@ __global__ void GaborishKernel(const FrameDev* __restrict__ frames, int unfused,
 
 
 // =====================================================================================================================
-// K_out: XYB -> linear -> sRGB -> clamp/scale/round -> interleaved caller layout (stage_xyb/from_linear/write)
+// K_out: XYB -> linear -> sRGB -> clamp/scale/round -> interleaved caller layout (stage_xyb/from_linear/write); the per-sample arithmetic is pixel_ops.h's
 // =====================================================================================================================
-__device__ __forceinline__ float LinearToSrgb(float v) {
-  const float x = fabsf(v);
-  const float lin = x * 12.92f;
-  const float s = sqrtf(x);
-  float yp = 7.352629620e-1f, yq = 2.424867759e-2f;
-  yp = fmaf(yp, s, 1.474205315f); yq = fmaf(yq, s, 9.258482155e-1f);
-  yp = fmaf(yp, s, 3.903842876e-1f); yq = fmaf(yq, s, 1.340816930f);
-  yp = fmaf(yp, s, 5.287254571e-3f); yq = fmaf(yq, s, 3.036675394e-1f);
-  yp = fmaf(yp, s, -5.135152395e-4f); yq = fmaf(yq, s, 1.004519624e-2f);
-  const float poly = yp / yq;
-  return copysignf(x > 0.0031308f ? poly : lin, v);
-}
-
-// base/fast_math-inl.h FastLog2f / FastPow2f / FastPowf and the transfer functions built on them (stage_from_linear.cc OpGamma, TF_709)
-__device__ __forceinline__ float FastPowfDev(float base, float exponent) {
-  const int32_t x_bits = __float_as_int(base);
-  const int32_t exp_shifted = (x_bits - 0x3f2aaaab) >> 23;
-  const float t = __int_as_float(x_bits - (int32_t)((uint32_t)exp_shifted << 23)) - 1.0f;
-  float yp = fmaf(7.4245873327820566E-01f, t, 1.4287160470083755E+00f); yp = fmaf(yp, t, -1.8503833400518310E-06f);
-  float yq = fmaf(1.7409343003366853E-01f, t, 1.0096718572241148E+00f); yq = fmaf(yq, t, 9.9032814277590719E-01f);
-  const float x = (yp / yq + (float)exp_shifted) * exponent;
-  const float floorx = floorf(x);
-  const float exp = __int_as_float((int32_t)((uint32_t)((int32_t)floorx + 127) << 23));
-  const float frac = x - floorx;
-  float num = frac + 1.01749063e+01f;
-  num = fmaf(num, frac, 4.88687798e+01f);
-  num = fmaf(num, frac, 9.85506591e+01f);
-  num = num * exp;
-  float den = fmaf(frac, 2.10242958e-01f, -2.22328856e-02f);
-  den = fmaf(den, frac, -1.94414990e+01f);
-  den = fmaf(den, frac, 9.85506633e+01f);
-  return num / den;
-}
-__device__ __forceinline__ float GammaFromLinear(float v, float inverse_gamma) { return v <= 1e-5f ? 0.0f : FastPowfDev(v, inverse_gamma); }
-__device__ __forceinline__ float Rec709FromLinear(float v) { return v <= 0.018f ? 4.5f * v : fmaf(1.099f, FastPowfDev(v, 0.45f), -0.099f); }
-
-__device__ __forceinline__ uint16_t FloatToHalfBits(float fv) {
-  const uint32_t x = __float_as_uint(fv);
-  const uint32_t sign = (x >> 16) & 0x8000;
-  const int32_t exp = (int32_t)((x >> 23) & 0xFF) - 127 + 15;
-  uint32_t mant = x & 0x7FFFFF;
-  if (((x >> 23) & 0xFF) == 0xFF) return (uint16_t)(sign | 0x7C00 | (mant ? 0x200 : 0));
-  if (exp >= 31) return (uint16_t)(sign | 0x7C00);
-  if (exp <= 0) {
-    if (exp < -10) return (uint16_t)sign;
-    mant |= 0x800000;
-    const int shift = 14 - exp;
-    uint32_t m = mant >> shift;
-    const uint32_t rem = mant & ((1u << shift) - 1), half = 1u << (shift - 1);
-    if (rem > half || (rem == half && (m & 1))) m++;
-    return (uint16_t)(sign | m);
-  }
-  const uint32_t m = mant >> 13, rem = mant & 0x1FFF;
-  uint32_t r = (uint32_t)(exp << 10) | m;
-  if (rem > 0x1000 || (rem == 0x1000 && (m & 1))) r++;
-  return (uint16_t)(sign | r);
-}
-
-__device__ __forceinline__ void StoreSample(const FrameDev& f, uint8_t* p, float v) {
-  if (f.out_type == 0) {
-    p[0] = (uint8_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, v)) * f.out_int_mul);
-  } else if (f.out_type == 1) {
-    const uint32_t u = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, v)) * f.out_int_mul);
-    if (f.out_big_endian) { p[0] = (uint8_t)(u >> 8); p[1] = (uint8_t)u; } else { p[0] = (uint8_t)u; p[1] = (uint8_t)(u >> 8); }
-  } else if (f.out_type == 2) {
-    const uint32_t u = __float_as_uint(v);
-    if (f.out_big_endian) { p[0] = (uint8_t)(u >> 24); p[1] = (uint8_t)(u >> 16); p[2] = (uint8_t)(u >> 8); p[3] = (uint8_t)u; }
-    else { p[0] = (uint8_t)u; p[1] = (uint8_t)(u >> 8); p[2] = (uint8_t)(u >> 16); p[3] = (uint8_t)(u >> 24); }
-  } else {
-    const uint32_t u = FloatToHalfBits(v);
-    if (f.out_big_endian) { p[0] = (uint8_t)(u >> 8); p[1] = (uint8_t)u; } else { p[0] = (uint8_t)u; p[1] = (uint8_t)(u >> 8); }
-  }
-}
-
-// Position of image sample (x, y) in the output buffer: the header's orientation (1..8, EXIF numbering as in
-// codestream_header.rs JxlOrientation) is applied by the write stage — 2 flip-h, 3 rotate 180, 4 flip-v, 5 transpose,
-// 6 rotate 90 cw, 7 anti-transpose, 8 rotate 90 ccw; out_stride already refers to the oriented width.
-__device__ __forceinline__ uint8_t* OutPixelPtr(const FrameDev& f, int x, int y, uint32_t bps) {
-  const int w = (int)f.img_w, h = (int)f.img_h;
-  int ox = x, oy = y;
-  switch (f.out_orient) {
-    case 2: ox = w - 1 - x; break;
-    case 3: ox = w - 1 - x; oy = h - 1 - y; break;
-    case 4: oy = h - 1 - y; break;
-    case 5: ox = y; oy = x; break;
-    case 6: ox = h - 1 - y; oy = x; break;
-    case 7: ox = h - 1 - y; oy = w - 1 - x; break;
-    case 8: ox = y; oy = w - 1 - x; break;
-    default: break;
-  }
-  return f.out + (size_t)oy * f.out_stride + (size_t)ox * f.out_channels * bps;
-}
-
 // a whole dword of output samples (JXL_PACKED_STORE_NT: with the non-temporal hint — nothing on the device reads decoded pixels again)
 __device__ __forceinline__ void StoreOut32(uint32_t* p, uint32_t v) {
 #ifdef JXL_PACKED_STORE_NT
@@ -5026,51 +4930,21 @@ __device__ __forceinline__ void StoreOut32(uint32_t* p, uint32_t v) {
 #endif
 }
 
-__device__ __forceinline__ void StorePixel(const FrameDev& f, int x, int y, float r, float g, float b, float a) {
-  const uint32_t bps = f.out_type == 0 ? 1 : f.out_type == 2 ? 4 : 2;
-  uint8_t* p = OutPixelPtr(f, x, y, bps);
-  const uint32_t nc = f.out_channels;
-  if (nc <= 2) {
-    StoreSample(f, p, f.is_gray ? r : g);  // gray images carry the same value in all channels; otherwise take G
-    if (nc == 2) StoreSample(f, p + bps, a);
-  } else {
-    StoreSample(f, p, r); StoreSample(f, p + bps, g); StoreSample(f, p + 2 * bps, b);
-    if (nc == 4) StoreSample(f, p + 3 * bps, a);
-  }
-}
 
-// Non-separable 2x / 4x / 8x upsampling of the restored planes (stage_upsampling.cc; same definition and accumulation order
-// as oracle/render.h UpsamplePlane): one thread per output sample and channel, 25 taps, result clamped to the window's range.
+// Non-separable 2x / 4x / 8x upsampling of the restored planes (UpsampleSample): one thread per output sample and channel.
 // Channel 3 = the alpha extra channel (int samples scaled to float first).
 __global__ void UpsampleKernel(const FrameDev* __restrict__ frames) {
   const FrameDev& f = frames[blockIdx.z];
   if (f.is_modular || f.lf_only || f.upsampling == 1 || f.post_mode) return;
   const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y * blockDim.y + threadIdx.y;
   if (ox >= (int)f.img_w || oy >= (int)f.img_h) return;
-  const int up = (int)f.upsampling, N = up / 2;
   const int w = (int)f.width, h = (int)f.height;
-  const int x = ox / up, sx = ox % up, y = oy / up, sy = oy % up;
-  const int ky = sy < N ? sy : up - 1 - sy, kx = sx < N ? sx : up - 1 - sx;
-  const bool fy = sy >= N, fx = sx >= N;
   const bool src_is_a = (FilterStagesBefore(f, 4) & 1) == 0;
   const int nch = f.alpha_plane ? 4 : 3;
   for (int c = 0; c < nch; c++) {
     const float* src = c == 3 ? nullptr : (src_is_a ? f.plane_a[c] : f.plane_b[c]);
-    float sum = 0.0f, mn = 0.0f, mx = 0.0f;
-    for (int iy = 0; iy < 5; iy++) {
-      const int yy = MirrorD(y + iy - 2, h);
-      const int mi = 5 * ky + (fy ? 4 - iy : iy);
-      for (int ix = 0; ix < 5; ix++) {
-        const int xx = MirrorD(x + ix - 2, w);
-        const float v = c == 3 ? (float)f.alpha_plane[(size_t)yy * w + xx] * f.alpha_factor : src[(size_t)yy * f.plane_stride + xx];
-        const int mj = 5 * kx + (fx ? 4 - ix : ix);
-        const int lo = mi < mj ? mi : mj, hi = mi < mj ? mj : mi;
-        const float k = f.up_weights[5 * N * lo - lo * (lo - 1) / 2 + hi - lo];
-        sum = fmaf(k, v, sum);
-        if (iy == 0 && ix == 0) { mn = v; mx = v; } else { mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
-      }
-    }
-    f.up_plane[c][(size_t)oy * f.img_w + ox] = sum < mn ? mn : (sum > mx ? mx : sum);
+    auto fetch = [&](int xx, int yy) { return c == 3 ? (float)f.alpha_plane[(size_t)yy * w + xx] * f.alpha_factor : src[(size_t)yy * f.plane_stride + xx]; };
+    f.up_plane[c][(size_t)oy * f.img_w + ox] = UpsampleSample(fetch, w, h, ox, oy, (int)f.upsampling, f.up_weights);
   }
 }
 
@@ -5080,54 +4954,14 @@ __device__ __forceinline__ uint32_t XcdContiguous(uint32_t bid, uint32_t nwg);
 __device__ __forceinline__ void ColorAndStore(const FrameDev& f, int x, int y, float X, float Y, float B, float A) {
   float r, g, b;
   if (f.color_mode <= 1 || f.color_mode >= 4) {
-    const float gr = (Y + X) - f.neg_bias_cbrt[0];
-    const float gg = (Y - X) - f.neg_bias_cbrt[1];
-    const float gb = B - f.neg_bias_cbrt[2];
-    const float mr = fmaf(gr * gr, gr, f.neg_bias[0]);
-    const float mg = fmaf(gg * gg, gg, f.neg_bias[1]);
-    const float mb = fmaf(gb * gb, gb, f.neg_bias[2]);
-    r = fmaf(f.opsin_inv[2], mb, fmaf(f.opsin_inv[1], mg, f.opsin_inv[0] * mr));
-    g = fmaf(f.opsin_inv[5], mb, fmaf(f.opsin_inv[4], mg, f.opsin_inv[3] * mr));
-    b = fmaf(f.opsin_inv[8], mb, fmaf(f.opsin_inv[7], mg, f.opsin_inv[6] * mr));
-    if (f.color_mode == 0) { r = LinearToSrgb(r); g = LinearToSrgb(g); b = LinearToSrgb(b); }
-    else if (f.color_mode == 4) { r = GammaFromLinear(r, f.inverse_gamma); g = GammaFromLinear(g, f.inverse_gamma); b = GammaFromLinear(b, f.inverse_gamma); }
-    else if (f.color_mode == 5) { r = Rec709FromLinear(r); g = Rec709FromLinear(g); b = Rec709FromLinear(b); }
-    else if (f.color_mode == 6) { r = PqFromLinear(r, f.hdr_par[0]); g = PqFromLinear(g, f.hdr_par[0]); b = PqFromLinear(b, f.hdr_par[0]); }
-    else if (f.color_mode == 7) {
-      HlgInverseOotf(f.hdr_par, r, g, b, [](float x, float e) { return FastPowfDev(x, e); });
-      r = HlgFromLinear(r); g = HlgFromLinear(g); b = HlgFromLinear(b);
-    }
-  } else if (f.color_mode == 2) {
-    const float c128 = 128.0f / 255, crcr = 1.402f, cgcb = -0.114f * 1.772f / 0.587f, cgcr = -0.299f * 1.402f / 0.587f, cbcb = 1.772f;
-    const float yb = Y + c128;
-    r = fmaf(crcr, B, yb);
-    g = fmaf(cgcr, B, fmaf(cgcb, X, yb));
-    b = fmaf(cbcb, X, yb);
-  } else { r = X; g = Y; b = B; }
-  if (f.is_gray) r = g;
-  StorePixel(f, x, y, r, g, b, A);
+    XybToLinear(f, X, Y, B, r, g, b);
+    const float3 t = TransferFromLinear(f, f.color_mode, r, g, b); r = t.x; g = t.y; b = t.z;
+  } else if (f.color_mode == 2) YcbcrToRgb(X, Y, B, r, g, b);
+  else { r = X; g = Y; b = B; }
+  if (f.od.is_gray) r = g;
+  StorePixel(f.od, (int)f.img_w, (int)f.img_h, x, y, r, g, b, A);
 }
-// Sample (x, y) of channel c of a chroma-subsampled frame at full resolution (stage_chroma_upsampling.cc: horizontal, then vertical, each with the (1/4, 3/4) kernel — out[2x] = 0.25 in[x-1]
-// + 0.75 in[x], out[2x+1] = 0.25 in[x+1] + 0.75 in[x] —, neighbours clamped at the channel's own edges; the channel sits packed in the top-left corner of its plane).  The arithmetic and
-// its order are ChromaUpsampleKernel's (kernels_features.hip: the frame tail of images with features): the vertical step works on horizontally upsampled rows, exactly as two stages would.
-// (the rule itself, on any grid: `plane` holds the channel packed top-left with row pitch `stride`; width x height is the size of the FULL grid that (x, y) addresses —
-// pixels for SubsampledAt, LF samples for LfOutputKernel)
-__device__ __forceinline__ float SubsampledSample(const float* __restrict__ plane, uint32_t stride, uint32_t hs, uint32_t vs, uint32_t width, uint32_t height, uint32_t x, uint32_t y) {
-  if (!(hs | vs)) return plane[(size_t)y * stride + x];
-  const uint32_t cw = (width + (1u << hs) - 1) >> hs, ch = (height + (1u << vs) - 1) >> vs;
-  const uint32_t sx = x >> hs, sy = y >> vs;
-  auto hval = [&](uint32_t row) -> float {
-    const float* in = plane + (size_t)row * stride;
-    if (!hs) return in[x];
-    const float mid = in[sx] * 0.75f;
-    const uint32_t nb = (x & 1) ? min(sx + 1, cw - 1) : (sx ? sx - 1 : 0);
-    return fmaf(0.25f, in[nb], mid);
-  };
-  if (!vs) return hval(sy);
-  const float mid = hval(sy) * 0.75f;
-  const uint32_t nb = (y & 1) ? min(sy + 1, ch - 1) : (sy ? sy - 1 : 0);
-  return fmaf(0.25f, hval(nb), mid);
-}
+// Sample (x, y) of channel c of a chroma-subsampled frame at full resolution (the channel sits packed in the top-left corner of its plane)
 __device__ __forceinline__ float SubsampledAt(const FrameDev& f, const float* __restrict__ plane, int c, uint32_t x, uint32_t y) {
   return SubsampledSample(plane, f.plane_stride, f.hs[c], f.vs[c], f.width, f.height, x, y);
 }
@@ -5161,7 +4995,7 @@ __global__ void OutputKernel(const FrameDev* __restrict__ frames, int unfused, i
 // 1:8 decode (FrameDev::lf_only): output pixel (bx, by) is the frame's LF sample (bx, by) — after the adaptive smoothing, i.e. what the IDCT stage reads as its LLF
 // input (lf_tmp: LfSmoothKernel copies where it does not smooth) — through the per-pixel tail of the full decode.  Gaborish, EPF and noise are defined on full-resolution
 // pixels and are not applied.  Chroma-subsampled frames: the (1/4, 3/4) rule of SubsampledAt on the LF grid.  One thread per LF sample, the frame on blockIdx.z; the host
-// set img_w x img_h / out_stride to the ceil(width / 8) x ceil(height / 8) picture, so OutPixelPtr applies the orientation to it as it does to the full one.
+// set img_w x img_h / out_stride to the ceil(width / 8) x ceil(height / 8) picture, so StorePixel applies the orientation to it as it does to the full one.
 __global__ void LfOutputKernel(const FrameDev* __restrict__ frames) {
   const FrameDev& f = frames[blockIdx.z];
   if (f.is_modular || !f.lf_only || FrameFailed(f)) return;
@@ -5465,8 +5299,8 @@ __global__ __launch_bounds__(256) void FusedGabEpf1OutKernel(const FrameDev* __r
   // ---- EPF pass 1 + colour + store
 #ifndef JXL_NO_PACKED_STORE
   // 1: u8 RGB, 2: u8 RGBA written as dwords (rows and buffer 4-byte aligned, width a multiple of 4 so that a quad of lanes is inside the image or outside it)
-  const int packed = (f.out_type == 0 && f.out_orient <= 1 && (w & 3) == 0 && ((uintptr_t)f.out & 3) == 0 && (f.out_stride & 3) == 0 && f.img_w == f.width && f.img_h == f.height)
-                         ? (f.out_channels == 3 ? 1 : f.out_channels == 4 ? 2 : 0) : 0;
+  const int packed = (f.od.out_type == 0 && f.od.out_orient <= 1 && (w & 3) == 0 && ((uintptr_t)f.od.out & 3) == 0 && (f.od.out_stride & 3) == 0 && f.img_w == f.width && f.img_h == f.height)
+                         ? (f.od.out_channels == 3 ? 1 : f.od.out_channels == 4 ? 2 : 0) : 0;
 #endif
   const float sm = f.epf_sm[1], bsm = f.epf_bsm[1];
   const float cs0 = f.epf_channel_scale[0], cs1 = f.epf_channel_scale[1], cs2 = f.epf_channel_scale[2];
@@ -5518,31 +5352,24 @@ __global__ __launch_bounds__(256) void FusedGabEpf1OutKernel(const FrameDev* __r
       const float inv = 1.0f / wsum;
       X = a0 * inv; Y = a1 * inv; B = a2 * inv;
     }
-    // XYB -> linear -> sRGB (OutputKernel)
-    const float gr = (Y + X) - f.neg_bias_cbrt[0];
-    const float gg = (Y - X) - f.neg_bias_cbrt[1];
-    const float gb = B - f.neg_bias_cbrt[2];
-    const float mr = fmaf(gr * gr, gr, f.neg_bias[0]);
-    const float mg = fmaf(gg * gg, gg, f.neg_bias[1]);
-    const float mb = fmaf(gb * gb, gb, f.neg_bias[2]);
-    float r = fmaf(f.opsin_inv[2], mb, fmaf(f.opsin_inv[1], mg, f.opsin_inv[0] * mr));
-    float g = fmaf(f.opsin_inv[5], mb, fmaf(f.opsin_inv[4], mg, f.opsin_inv[3] * mr));
-    float b = fmaf(f.opsin_inv[8], mb, fmaf(f.opsin_inv[7], mg, f.opsin_inv[6] * mr));
+    // XYB -> linear -> sRGB (FusedEligible: colour modes 0 and 1 only)
+    float r, g, b;
+    XybToLinear(f, X, Y, B, r, g, b);
     if (f.color_mode == 0) { r = LinearToSrgb(r); g = LinearToSrgb(g); b = LinearToSrgb(b); }
-    if (f.is_gray) r = g;
+    if (f.od.is_gray) r = g;
 #ifndef JXL_NO_PACKED_STORE
     if (packed) {
       // u8 RGB / RGBA in image orientation: whole dwords instead of three or four byte stores per pixel.  RGB: the four lanes of a quad hold 12 bytes = three
       // dwords; lane j takes the rest of its own pixel and the head of its right neighbour's (DPP quad_perm [1, 2, 3, 3]) and lanes 0..2 store.  Same rounding
       // as StoreSample.
-      const uint32_t pr = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, r)) * f.out_int_mul) & 0xFFu;
-      const uint32_t pg = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, g)) * f.out_int_mul) & 0xFFu;
-      const uint32_t pb = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, b)) * f.out_int_mul) & 0xFFu;
+      const uint32_t pr = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, r)) * f.od.out_int_mul) & 0xFFu;
+      const uint32_t pg = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, g)) * f.od.out_int_mul) & 0xFFu;
+      const uint32_t pb = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, b)) * f.od.out_int_mul) & 0xFFu;
       const uint32_t p = pr | (pg << 8) | (pb << 16);
-      uint8_t* const row = f.out + (size_t)y * f.out_stride;
+      uint8_t* const row = f.od.out + (size_t)y * f.od.out_stride;
       if (packed == 2) {
         const float a = f.alpha_plane ? (float)f.alpha_plane[(size_t)y * f.width + x] * f.alpha_factor : 1.0f;
-        const uint32_t pa = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, a)) * f.out_int_mul) & 0xFFu;
+        const uint32_t pa = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, a)) * f.od.out_int_mul) & 0xFFu;
         StoreOut32(reinterpret_cast<uint32_t*>(row + 4 * (size_t)x), p | (pa << 24));
       } else {
         const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)p, 0xF9, 0xF, 0xF, false);
@@ -5553,7 +5380,7 @@ __global__ __launch_bounds__(256) void FusedGabEpf1OutKernel(const FrameDev* __r
       continue;
     }
 #endif
-    StorePixel(f, x, y, r, g, b, f.alpha_plane ? (float)f.alpha_plane[(size_t)y * f.width + x] * f.alpha_factor : 1.0f);
+    StorePixel(f.od, (int)f.img_w, (int)f.img_h, x, y, r, g, b, f.alpha_plane ? (float)f.alpha_plane[(size_t)y * f.width + x] * f.alpha_factor : 1.0f);
   }
 }
 
@@ -6083,12 +5910,7 @@ __global__ void ModularOutputKernel(const FrameDev* __restrict__ frames, int fid
   if (a.ncolor == 1) { r = g = b = sample(0); }
   else { r = sample(0); g = sample(1); b = sample(2); }
   const float al = a.alpha ? (float)a.alpha[o] * a.alpha_factor : 1.0f;
-  // StorePixel picks r for gray output of gray images and g otherwise
-  const uint32_t bps = f.out_type == 0 ? 1 : f.out_type == 2 ? 4 : 2;
-  uint8_t* p = OutPixelPtr(f, x, y, bps);
-  const uint32_t nc = f.out_channels;
-  if (nc <= 2) { StoreSample(f, p, a.ncolor == 1 ? r : g); if (nc == 2) StoreSample(f, p + bps, al); }
-  else { StoreSample(f, p, r); StoreSample(f, p + bps, g); StoreSample(f, p + 2 * bps, b); if (nc == 4) StoreSample(f, p + 3 * bps, al); }
+  StorePixel(f.od, (int)f.img_w, (int)f.img_h, x, y, r, g, b, al);
 }
 
 // =====================================================================================================================

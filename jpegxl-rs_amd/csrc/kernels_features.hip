@@ -4,8 +4,10 @@
 // reached by the reference through JxlDecoderProcessInput (jpegxl-rs/src/decode.rs:238).  Explicit arguments, one launch per
 // stage and frame, planned by the host (decoder.cc PlanPostOps): these stages are plain streaming passes over the planes
 // (HBM-bound, 8..24 B/px each), only frames that need them pay for them — single-frame images without features keep the
-// fused tile kernels of kernels.hip.  Arithmetic and operation order are those of oracle/image_features.h.
+// fused tile kernels of kernels.hip.  Arithmetic and operation order are those of oracle/image_features.h; upsampling, colour
+// transform, transfer function and the write are pixel_ops.h's, shared with those kernels.
 #include "kernels.h"
+#include "pixel_ops.h"
 #include "host_parse.h"
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -14,37 +16,9 @@ namespace jxlhip {
 
 namespace {
 
-__device__ __forceinline__ int MirrorF(int x, int size) {
-  while (x < 0 || x >= size) x = x < 0 ? -x - 1 : 2 * size - 1 - x;
-  return x;
-}
 __device__ __forceinline__ float Clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
 
 // base/fast_math-inl.h
-__device__ __forceinline__ float FastLog2fD(float x) {
-  const int32_t x_bits = __float_as_int(x);
-  const int32_t exp_bits = x_bits - 0x3f2aaaab;
-  const int32_t exp_shifted = exp_bits >> 23;
-  const float mantissa = __int_as_float(x_bits - (int32_t)((uint32_t)exp_shifted << 23));
-  const float t = mantissa - 1.0f;
-  float yp = fmaf(7.4245873327820566E-01f, t, 1.4287160470083755E+00f); yp = fmaf(yp, t, -1.8503833400518310E-06f);
-  float yq = fmaf(1.7409343003366853E-01f, t, 1.0096718572241148E+00f); yq = fmaf(yq, t, 9.9032814277590719E-01f);
-  return yp / yq + (float)exp_shifted;
-}
-__device__ __forceinline__ float FastPow2fD(float x) {
-  const float floorx = floorf(x);
-  const float exp = __int_as_float((int32_t)((uint32_t)((int32_t)floorx + 127) << 23));
-  const float frac = x - floorx;
-  float num = frac + 1.01749063e+01f;
-  num = fmaf(num, frac, 4.88687798e+01f);
-  num = fmaf(num, frac, 9.85506591e+01f);
-  num = num * exp;
-  float den = fmaf(frac, 2.10242958e-01f, -2.22328856e-02f);
-  den = fmaf(den, frac, -1.94414990e+01f);
-  den = fmaf(den, frac, 9.85506633e+01f);
-  return num / den;
-}
-__device__ __forceinline__ float FastPowfD(float b, float e) { return FastPow2fD(FastLog2fD(b) * e); }
 __device__ __forceinline__ float FastErffD(float x) {
   const float absx = fabsf(x);
   float d = fmaf(absx, 7.77394369e-02f, 2.05260015e-04f);
@@ -55,18 +29,6 @@ __device__ __forceinline__ float FastErffD(float x) {
   const float inv = 1.0f / d2;
   const float r = fmaf(-inv, inv, 1.0f);
   return x <= 0.0f ? -r : r;
-}
-__device__ __forceinline__ float LinearToSrgbF(float v) {   // cms/transfer_functions-inl.h TF_SRGB (same as kernels.hip LinearToSrgb)
-  const float x = fabsf(v);
-  const float lin = x * 12.92f;
-  const float s = sqrtf(x);
-  float yp = 7.352629620e-1f, yq = 2.424867759e-2f;
-  yp = fmaf(yp, s, 1.474205315f); yq = fmaf(yq, s, 9.258482155e-1f);
-  yp = fmaf(yp, s, 3.903842876e-1f); yq = fmaf(yq, s, 1.340816930f);
-  yp = fmaf(yp, s, 5.287254571e-3f); yq = fmaf(yq, s, 3.036675394e-1f);
-  yp = fmaf(yp, s, -5.135152395e-4f); yq = fmaf(yq, s, 1.004519624e-2f);
-  const float poly = yp / yq;
-  return copysignf(x > 0.0031308f ? poly : lin, v);
 }
 
 // ---- integer Modular planes -> float planes (dec_modular.cc ModularImageToDecodedRect) ---------------------------------
@@ -227,33 +189,12 @@ __global__ __launch_bounds__(256) void SplineKernel(float* p0, float* p1, float*
   if (touched) { p0[o] = v0; p1[o] = v1; p2[o] = v2; }
 }
 
-// ---- upsampling of one plane (stage_upsampling.cc; same definition as kernels.hip UpsampleKernel) ---------------------------
-__device__ __forceinline__ float UpsampleSample(const float* __restrict__ src, uint32_t src_stride, int w, int h, int ox, int oy, int up, const float* __restrict__ weights) {
-  const int N = up / 2;
-  const int x = ox / up, sx = ox % up, y = oy / up, sy = oy % up;
-  const int ky = sy < N ? sy : up - 1 - sy, kx = sx < N ? sx : up - 1 - sx;
-  const bool fy = sy >= N, fx = sx >= N;
-  float sum = 0.0f, mn = 0.0f, mx = 0.0f;
-  for (int iy = 0; iy < 5; iy++) {
-    const int yy = MirrorF(y + iy - 2, h);
-    const int mi = 5 * ky + (fy ? 4 - iy : iy);
-    for (int ix = 0; ix < 5; ix++) {
-      const int xx = MirrorF(x + ix - 2, w);
-      const float v = src[(size_t)yy * src_stride + xx];
-      const int mj = 5 * kx + (fx ? 4 - ix : ix);
-      const int lo = mi < mj ? mi : mj, hi = mi < mj ? mj : mi;
-      const float k = weights[5 * N * lo - lo * (lo - 1) / 2 + hi - lo];
-      sum = fmaf(k, v, sum);
-      if (iy == 0 && ix == 0) { mn = v; mx = v; } else { mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
-    }
-  }
-  return sum < mn ? mn : (sum > mx ? mx : sum);
-}
+// ---- upsampling of one plane (stage_upsampling.cc: UpsampleSample) -------------------------------------------------------------
 __global__ void UpsamplePlaneKernel(const float* __restrict__ src, uint32_t src_stride, int w, int h, float* __restrict__ dst, uint32_t dst_stride, int ow, int oh,
                                     int up, const float* __restrict__ weights) {
   const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y * blockDim.y + threadIdx.y;
   if (ox >= ow || oy >= oh) return;
-  dst[(size_t)oy * dst_stride + ox] = UpsampleSample(src, src_stride, w, h, ox, oy, up, weights);
+  dst[(size_t)oy * dst_stride + ox] = UpsampleSample([&](int x, int y) { return src[(size_t)y * src_stride + x]; }, w, h, ox, oy, up, weights);
 }
 // ---- the same two steps for every extra channel of a frame with a channel table: channel on blockIdx.z (the table entry is wave-uniform)
 __global__ void EcIntToFloatKernel(EcFrameArgs a) {
@@ -268,7 +209,7 @@ __global__ void EcUpsampleKernel(EcFrameArgs a) {
   const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y * blockDim.y + threadIdx.y;
   if (ox >= (int)a.ow || oy >= (int)a.oh) return;
   const EcChanDev& c = a.table[blockIdx.z];
-  c.up[(size_t)oy * a.ow + ox] = UpsampleSample(c.plane, a.w, (int)a.w, (int)a.h, ox, oy, (int)a.up, a.up_weights);
+  c.up[(size_t)oy * a.ow + ox] = UpsampleSample([&](int x, int y) { return c.plane[(size_t)y * a.w + x]; }, (int)a.w, (int)a.h, ox, oy, (int)a.up, a.up_weights);
 }
 
 // ---- noise (dec_noise.cc Random3Planes, stage_noise.cc) --------------------------------------------------------------------
@@ -323,7 +264,7 @@ __global__ void NoiseAddKernel(NoiseArgs a) {
   if (x >= w || y >= h) return;
   float conv[3];
   int xs[5], ys[5];
-  for (int i = 0; i < 5; i++) { xs[i] = MirrorF(x + i - 2, w); ys[i] = MirrorF(y + i - 2, h); }
+  for (int i = 0; i < 5; i++) { xs[i] = MirrorD(x + i - 2, w); ys[i] = MirrorD(y + i - 2, h); }
   for (int c = 0; c < 3; c++) {
     const float* n = a.noise[c];
     auto px = [&](int r, int dx) { return n[(size_t)ys[r] * a.noise_stride + xs[dx + 2]]; };
@@ -347,17 +288,7 @@ __global__ void NoiseAddKernel(NoiseArgs a) {
   a.p[2][o] = fmaf(a.ytob, rg, a.p[2][o]);
 }
 
-// ---- colour transform to the output space (stage_xyb.cc, stage_from_linear.cc, stage_ycbcr.cc) -------------------------------
-__device__ __forceinline__ float TransferD(uint32_t kind, float inverse_gamma, float v) {
-  switch (kind) {
-    case 0: return LinearToSrgbF(v);
-    case 1: return v;
-    case 2: return v <= 1e-5f ? 0.0f : FastPowfD(v, inverse_gamma);
-    case 4: return PqFromLinear(v, inverse_gamma);          // (inverse_gamma carries intensity_target / 10000 here)
-    case 5: return HlgFromLinear(v);
-    default: return v <= 0.018f ? 4.5f * v : fmaf(1.099f, FastPowfD(v, 0.45f), -0.099f);
-  }
-}
+// ---- colour transform to the output space (stage_xyb.cc, stage_from_linear.cc, stage_ycbcr.cc: XybToLinear, TransferFromLinear, YcbcrToRgb)
 __global__ void ColorKernel(ColorArgs a) {
   const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
   if (x >= a.w || y >= a.h) return;
@@ -365,29 +296,12 @@ __global__ void ColorKernel(ColorArgs a) {
   const float X = a.src[0][si], Y = a.src[1][si], B = a.src[2][si];
   float r, g, b;
   if (a.mode == 0) {          // XYB -> linear -> transfer function
-    const float gr = (Y + X) - a.neg_bias_cbrt[0];
-    const float gg = (Y - X) - a.neg_bias_cbrt[1];
-    const float gb = B - a.neg_bias_cbrt[2];
-    const float mr = fmaf(gr * gr, gr, a.neg_bias[0]);
-    const float mg = fmaf(gg * gg, gg, a.neg_bias[1]);
-    const float mb = fmaf(gb * gb, gb, a.neg_bias[2]);
-    r = fmaf(a.opsin_inv[2], mb, fmaf(a.opsin_inv[1], mg, a.opsin_inv[0] * mr));
-    g = fmaf(a.opsin_inv[5], mb, fmaf(a.opsin_inv[4], mg, a.opsin_inv[3] * mr));
-    b = fmaf(a.opsin_inv[8], mb, fmaf(a.opsin_inv[7], mg, a.opsin_inv[6] * mr));
-    if (a.tf_kind == 5) HlgInverseOotf(a.hdr_par, r, g, b, [](float x, float e) { return FastPowfD(x, e); });
-    const float tf_par = a.tf_kind == 4 ? a.hdr_par[0] : a.inverse_gamma;
-    r = TransferD(a.tf_kind, tf_par, r); g = TransferD(a.tf_kind, tf_par, g); b = TransferD(a.tf_kind, tf_par, b);
-  } else if (a.mode == 1) {   // YCbCr (planes Cb, Y, Cr) -> RGB
-    const float c128 = 128.0f / 255, crcr = 1.402f, cgcb = -0.114f * 1.772f / 0.587f, cgcr = -0.299f * 1.402f / 0.587f, cbcb = 1.772f;
-    const float yb = Y + c128;
-    r = fmaf(crcr, B, yb);
-    g = fmaf(cgcr, B, fmaf(cgcb, X, yb));
-    b = fmaf(cbcb, X, yb);
-  } else if (a.mode == 3) {   // transfer function only: the planes hold linear light (a spot-colour stage came in between)
+    XybToLinear(a, X, Y, B, r, g, b);
+    const float3 t = TransferFromLinear(a, a.tf_kind, r, g, b); r = t.x; g = t.y; b = t.z;
+  } else if (a.mode == 1) YcbcrToRgb(X, Y, B, r, g, b);   // (planes Cb, Y, Cr)
+  else if (a.mode == 3) {     // transfer function only: the planes hold linear light (a spot-colour stage came in between)
     r = X; g = Y; b = B;
-    if (a.tf_kind == 5) HlgInverseOotf(a.hdr_par, r, g, b, [](float x, float e) { return FastPowfD(x, e); });
-    const float tf_par = a.tf_kind == 4 ? a.hdr_par[0] : a.inverse_gamma;
-    r = TransferD(a.tf_kind, tf_par, r); g = TransferD(a.tf_kind, tf_par, g); b = TransferD(a.tf_kind, tf_par, b);
+    const float3 t = TransferFromLinear(a, a.tf_kind, r, g, b); r = t.x; g = t.y; b = t.z;
   } else { r = X; g = Y; b = B; }
   a.dst[0][di] = r; a.dst[1][di] = g; a.dst[2][di] = b;
 }
@@ -401,30 +315,12 @@ __global__ void SpotKernel(SpotArgs a) {
   for (int c = 0; c < 3; c++) a.p[c][o] = mix * a.color[c] + (1.0f - mix) * a.p[c][o];
 }
 
-// ---- chroma upsampling of subsampled YCbCr frames (stage_chroma_upsampling.cc): horizontal, then vertical, each with the (1/4, 3/4)
-// kernel — out[2x] = 0.25 in[x-1] + 0.75 in[x], out[2x+1] = 0.25 in[x+1] + 0.75 in[x] — neighbours clamped at the channel's own edges.
-// One thread per output sample; the vertical step works on horizontally upsampled rows, exactly as two stages would.
-struct ChromaUpArgs { const float* src; float* dst; uint32_t src_stride, dst_stride, cw, ch, hs, vs, out_w, out_h; };
+// ---- chroma upsampling of subsampled YCbCr frames (stage_chroma_upsampling.cc: SubsampledSample), one thread per output sample
+struct ChromaUpArgs { const float* src; float* dst; uint32_t src_stride, dst_stride, hs, vs, out_w, out_h; };
 __global__ void ChromaUpsampleKernel(ChromaUpArgs a) {
   const uint32_t X = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y * blockDim.y + threadIdx.y;
   if (X >= a.out_w || Y >= a.out_h) return;
-  const uint32_t sx = X >> a.hs, sy = Y >> a.vs;
-  if (sx >= a.cw || sy >= a.ch) return;
-  auto hval = [&](uint32_t row) -> float {
-    const float* in = a.src + (size_t)row * a.src_stride;
-    if (!a.hs) return in[X];
-    const float mid = in[sx] * 0.75f;
-    const uint32_t nb = (X & 1) ? min(sx + 1, a.cw - 1) : (sx ? sx - 1 : 0);
-    return fmaf(0.25f, in[nb], mid);
-  };
-  float v;
-  if (!a.vs) v = hval(sy);
-  else {
-    const float mid = hval(sy) * 0.75f;
-    const uint32_t nb = (Y & 1) ? min(sy + 1, a.ch - 1) : (sy ? sy - 1 : 0);
-    v = fmaf(0.25f, hval(nb), mid);
-  }
-  a.dst[(size_t)Y * a.dst_stride + X] = v;
+  a.dst[(size_t)Y * a.dst_stride + X] = SubsampledSample(a.src, a.src_stride, a.hs, a.vs, a.out_w, a.out_h, X, Y);
 }
 
 // ---- blending of a frame onto the image canvas (stage_blending.cc; blending.cc) ----------------------------------------------
@@ -554,42 +450,7 @@ __global__ void SpotTableKernel(float* p0, float* p1, float* p2, uint32_t stride
   p0[o] = v[0]; p1[o] = v[1]; p2[o] = v[2];
 }
 
-// ---- write stage (stage_write.cc): float planes in the output colour space -> caller layout --------------------------------
-__device__ __forceinline__ uint16_t HalfBits(float fv) {
-  const uint32_t x = __float_as_uint(fv);
-  const uint32_t sign = (x >> 16) & 0x8000;
-  const int32_t exp = (int32_t)((x >> 23) & 0xFF) - 127 + 15;
-  uint32_t mant = x & 0x7FFFFF;
-  if (((x >> 23) & 0xFF) == 0xFF) return (uint16_t)(sign | 0x7C00 | (mant ? 0x200 : 0));
-  if (exp >= 31) return (uint16_t)(sign | 0x7C00);
-  if (exp <= 0) {
-    if (exp < -10) return (uint16_t)sign;
-    mant |= 0x800000;
-    const int shift = 14 - exp;
-    uint32_t m = mant >> shift;
-    const uint32_t rem = mant & ((1u << shift) - 1), half = 1u << (shift - 1);
-    if (rem > half || (rem == half && (m & 1))) m++;
-    return (uint16_t)(sign | m);
-  }
-  const uint32_t m = mant >> 13, rem = mant & 0x1FFF;
-  uint32_t r = (uint32_t)(exp << 10) | m;
-  if (rem > 0x1000 || (rem == 0x1000 && (m & 1))) r++;
-  return (uint16_t)(sign | r);
-}
-__device__ __forceinline__ void StoreSampleW(const WriteArgs& a, uint8_t* p, float v) {
-  if (a.out_type == 0) p[0] = (uint8_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, v)) * a.out_int_mul);
-  else if (a.out_type == 1) {
-    const uint32_t u = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, v)) * a.out_int_mul);
-    if (a.out_big_endian) { p[0] = (uint8_t)(u >> 8); p[1] = (uint8_t)u; } else { p[0] = (uint8_t)u; p[1] = (uint8_t)(u >> 8); }
-  } else if (a.out_type == 2) {
-    const uint32_t u = __float_as_uint(v);
-    if (a.out_big_endian) { p[0] = (uint8_t)(u >> 24); p[1] = (uint8_t)(u >> 16); p[2] = (uint8_t)(u >> 8); p[3] = (uint8_t)u; }
-    else { p[0] = (uint8_t)u; p[1] = (uint8_t)(u >> 8); p[2] = (uint8_t)(u >> 16); p[3] = (uint8_t)(u >> 24); }
-  } else {
-    const uint32_t u = HalfBits(v);
-    if (a.out_big_endian) { p[0] = (uint8_t)(u >> 8); p[1] = (uint8_t)u; } else { p[0] = (uint8_t)u; p[1] = (uint8_t)(u >> 8); }
-  }
-}
+// ---- write stage (stage_write.cc): float planes in the output colour space -> caller layout (StorePixel) ---------------------
 __global__ void WriteKernel(WriteArgs a) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
   const int w = (int)a.img_w, h = (int)a.img_h;
@@ -604,22 +465,7 @@ __global__ void WriteKernel(WriteArgs a) {
       r *= m; g *= m; b *= m;
     }
   }
-  int ox = x, oy = y;
-  switch (a.out_orient) {
-    case 2: ox = w - 1 - x; break;
-    case 3: ox = w - 1 - x; oy = h - 1 - y; break;
-    case 4: oy = h - 1 - y; break;
-    case 5: ox = y; oy = x; break;
-    case 6: ox = h - 1 - y; oy = x; break;
-    case 7: ox = h - 1 - y; oy = w - 1 - x; break;
-    case 8: ox = y; oy = w - 1 - x; break;
-    default: break;
-  }
-  const uint32_t bps = a.out_type == 0 ? 1 : a.out_type == 2 ? 4 : 2;
-  uint8_t* p = a.out + (size_t)oy * a.out_stride + (size_t)ox * a.out_channels * bps;
-  const uint32_t nc = a.out_channels;
-  if (nc <= 2) { StoreSampleW(a, p, a.is_gray ? r : g); if (nc == 2) StoreSampleW(a, p + bps, al); }
-  else { StoreSampleW(a, p, r); StoreSampleW(a, p + bps, g); StoreSampleW(a, p + 2 * bps, b); if (nc == 4) StoreSampleW(a, p + 3 * bps, al); }
+  StorePixel(a.od, w, h, x, y, r, g, b, al);
 }
 
 __global__ void CopyPlaneKernel(const float* __restrict__ src, uint32_t src_stride, float* __restrict__ dst, uint32_t dst_stride, uint32_t w, uint32_t h) {
@@ -736,8 +582,8 @@ void LaunchCopyPlane(const float* src, uint32_t src_stride, float* dst, uint32_t
   hipLaunchKernelGGL(CopyPlaneKernel, Grid2(w, h), kBlock2, 0, (hipStream_t)stream, src, src_stride, dst, dst_stride, w, h);
 }
 
-void LaunchChromaUpsample(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t cw, uint32_t ch, uint32_t hs, uint32_t vs, uint32_t out_w, uint32_t out_h, void* stream) {
-  ChromaUpArgs a{src, dst, src_stride, dst_stride, cw, ch, hs, vs, out_w, out_h};
+void LaunchChromaUpsample(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t hs, uint32_t vs, uint32_t out_w, uint32_t out_h, void* stream) {
+  ChromaUpArgs a{src, dst, src_stride, dst_stride, hs, vs, out_w, out_h};
   hipLaunchKernelGGL(ChromaUpsampleKernel, Grid2(out_w, out_h), kBlock2, 0, (hipStream_t)stream, a);
 }
 

@@ -4,7 +4,7 @@ Given the float the pipeline produced, the u8 / u16 / f16 value, byte order, cha
 format follow from IEEE 754 and the API's documentation, so the reference here is numpy (expected_output below), shares no code with oracle/ and
 needs no tolerance.  The input of the comparison is the product's stored-orientation, 4-channel, little-endian f32 decode of the same stream.
 The comparison rests on one property of the code (kernels.hip / kernels_features.hip): for a given stream and decoder configuration the float
-that reaches StoreSample / StoreSampleW / the packed stores is computed before, and independently of, the output format — the format only
+that reaches StoreSample (pixel_ops.h, the one sample conversion of every kernel below) / the packed stores is computed before, and independently of, the output format — the format only
 selects a branch of the store.  One kernel serves every format of a stream, so no comparison here mixes two kernels; that the fused and the
 stage-by-stage VarDCT kernels agree bit for bit is asserted on its own (test_fused_and_unfused_kernels_write_the_same_floats).
 
@@ -37,6 +37,7 @@ import pytest
 
 from conftest import fixture_bytes
 import synth_lib as S
+from test_gpu_parity import COLOUR_ENCODINGS
 
 pytestmark = pytest.mark.gpu
 
@@ -527,7 +528,7 @@ def float_plane(patterns, w, h, seed):
 
 def float_streams(ints, bits, exp_bits):
     """the plane as a plain image (-> ModularOutputKernel / StoreSample) and as two frames, the second a crop of the same samples blended with mode replace
-    (-> WriteKernel / StoreSampleW; the composite is the plane again)"""
+    (-> WriteKernel; the composite is the plane again)"""
     h, w = ints.shape[:2]
     y0, x0, ch, cw = 5, 7, h // 2, w // 2
     S.set_float(exp_bits)
@@ -595,7 +596,7 @@ def check_all_formats_of_plane(jx, data, base, what, depths=()):
 
 @pytest.mark.parametrize("path", ["plain", "layered"])
 def test_half_converter_on_every_class_of_input(jx, path):
-    """A 24-bit float plane (1 + 7 + 16 bits) through StoreSample (plain) and StoreSampleW (layered): f16 output equals astype(float16) bit for bit for normal halves
+    """A 24-bit float plane (1 + 7 + 16 bits) through ModularOutputKernel (plain) and WriteKernel (layered): f16 output equals astype(float16) bit for bit for normal halves
     rounding down, up and on a tie (kept / bumped), mantissa carry into the exponent and into infinity, [65504, 65520) staying finite, the subnormal range with ties,
     2^-25 exactly -> 0, just above -> 2^-24, below -> 0, zero — each with both signs —; u8 / u16 of negative, above-one and -0 samples clamp."""
     ints = float24_plane()
@@ -612,7 +613,7 @@ def test_half_converter_on_every_class_of_input(jx, path):
 
 @pytest.mark.parametrize("path", ["plain", "layered"])
 def test_integer_rounding_ties_and_non_finite_samples(jx, path):
-    """A binary32 plane through both copies of the conversion: exact ties v x 255 / 65535 / 1023 == k + 0.5 (even and odd k) round to even in u8 / u16 / 10-bit output,
+    """A binary32 plane through both write kernels: exact ties v x 255 / 65535 / 1023 == k + 0.5 (even and odd k) round to even in u8 / u16 / 10-bit output,
     values above 1 clamp; half ties, half subnormals and the underflow edge once more from binary32 input."""
     ints = float32_plane()
     data = float_streams(ints, 32, 8)[path]
@@ -638,8 +639,8 @@ def test_infinity_and_nan_samples(jx, path):
 
 @pytest.mark.parametrize("path", ["plain", "layered", "float_alpha"])
 def test_half_to_float_to_half_is_the_identity(jx, path):
-    """A binary16 plane with every pattern whose exponent field is below 31: f16 output is the file's halves, bit for bit (subnormals, -0), through StoreSample,
-    StoreSampleW and — as an RGBA image whose alpha is a half too — the float-alpha route into WriteKernel."""
+    """A binary16 plane with every pattern whose exponent field is below 31: f16 output is the file's halves, bit for bit (subnormals, -0), through ModularOutputKernel,
+    WriteKernel and — as an RGBA image whose alpha is a half too — the float-alpha route into WriteKernel."""
     ints = float16_plane()
     if path == "float_alpha":
         ints = np.dstack([ints, np.roll(ints[..., 0], 17, axis=1)])
@@ -680,3 +681,42 @@ def test_full_range_ramps(jx):
     for big in (False, True):
         _, _, buf = raw_decode(jx, data, "uint16", 3, big)
         assert np.array_equal(buf.view(">u2" if big else "<u2").reshape(64, 64, 3), img8 * 257)
+
+
+# ---- 5. the fast path and the frame tail are the same function of the same samples ------------------------------------------------------------------
+PATH_ENCODINGS = dict(COLOUR_ENCODINGS, default_srgb={}, linear=dict(white_point=1, primaries=1, tf=8))
+
+
+@pytest.mark.parametrize("name", sorted(PATH_ENCODINGS))
+def test_fast_path_and_frame_tail_write_the_same_samples(jx, name):
+    """One 200 x 136 XYB frame as a single-frame image (the fast path: the last filter kernel or OutputKernel hands it to ColorAndStore -> StorePixel; the default
+    sRGB frame with gaborish and one EPF pass takes FusedGabEpf1OutKernel) and as the first of two frames, the second a 64 x 48 crop that replaces its rectangle
+    (the frame tail: ColorKernel, BlendKernel, WriteKernel).  Colour transform, transfer function and sample conversion of the two paths are one definition
+    (pixel_ops.h), so outside the crop the f32 output is equal bit for bit, and so are u8 and u16 — for every transfer function, with and without the filters."""
+    img = S.synthetic_image(31, 200, 136)
+    x0, y0, cw, ch = 40, 30, 64, 48
+    S.set_color(**PATH_ENCODINGS[name])
+    try:
+        pairs = []
+        for filt in (dict(gab=1, epf_iters=1), dict(gab=0, epf_iters=0)):
+            single = S.encode_vardct(img, seed=5, strategy_mix=2, **filt)
+            layered = S.encode_vardct_frame(img, S.frame(is_last=0, save_as_reference=1), seed=5, strategy_mix=2, **filt) + \
+                S.encode_vardct_frame(S.synthetic_image(9, cw, ch), S.frame(emit=1, have_crop=1, crop_x0=x0, crop_y0=y0, canvas_w=200, canvas_h=136, blend_mode=0, blend_source=1), seed=4)
+            pairs.append((filt, single, layered))
+    finally:
+        S.set_color()
+    compared = np.ones((136, 200), bool)
+    compared[y0:y0 + ch, x0:x0 + cw] = False
+    assert int(compared.sum()) == 200 * 136 - cw * ch                             # the whole image but the crop: nothing else is masked
+    for filt, single, layered in pairs:
+        for dtype, view in (("float32", "<u4"), ("uint8", "u1"), ("uint16", "<u2")):
+            outs = []
+            for data in (single, layered):
+                w, h, buf = raw_decode(jx, data, dtype, 3)
+                assert (w, h) == (200, 136)
+                outs.append(buf.view(view).reshape(136, 200, 3))
+            fast, tail = outs
+            differing = int((fast[compared] != tail[compared]).sum())
+            print(name, filt, dtype, "differing samples outside the crop:", differing)
+            assert differing == 0, (name, filt, dtype, differing)
+            assert not np.array_equal(fast[~compared], tail[~compared])             # (the second frame did land in its rectangle)

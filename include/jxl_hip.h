@@ -259,6 +259,20 @@ JxlDecoderStatus JxlHipBatchSetOutput(JxlHipBatch* batch, int index, const JxlPi
  * message in JxlHipLastError().  A batch may mix scaled and unscaled images. */
 JxlDecoderStatus JxlHipBatchOutBufferSizeScaled(const JxlHipBatch* batch, int index, const JxlPixelFormat* format, int downscale, size_t* size);
 JxlDecoderStatus JxlHipBatchSetOutputScaled(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int downscale);
+/* JPEG bit-stream reconstruction of a whole batch (jpegxl-rs decode.rs:493 `reconstruct`, for many files at once).  JxlHipBatchCanReconstructJpeg: 1 if image
+ * `index` is a lossless JPEG transcode with usable reconstruction data (a `jbrd` box whose markers find their ICC / Exif / XMP payloads, a Huffman-coded source),
+ * else 0 with the reason in JxlHipLastError().  JxlHipBatchReconstructJpegs runs the LF and HF entropy stages once for all images of the batch (it prepares the batch
+ * if need be; no image needs an output set) and writes the files: sequential Huffman scans are entropy-coded on the GPU and only their bytes cross to the host,
+ * which serialises the markers around them; progressive scans and scans with extra zero runs are Huffman-coded on the host from that image's coefficients.
+ * An image that cannot be reconstructed or whose stream is damaged fails alone — the call still returns JXL_DEC_SUCCESS; JxlHipBatchJpegStatus(index) is
+ * JXL_DEC_SUCCESS or JXL_DEC_ERROR with that image's reason in JxlHipLastError().  JxlHipBatchJpegSize / JxlHipBatchCopyJpeg hand out the bytes (size 0: no file),
+ * valid until the next JxlHipBatchReconstructJpegs or JxlHipBatchReset.  JxlHipBatchSetOption("jpeg_host_writer", 1): every image through the host writer.
+ * JxlHipBatchGetInfo "jpeg_device_images" / "jpeg_host_images": files of the last call written by the device / by the host writer. */
+int JxlHipBatchCanReconstructJpeg(JxlHipBatch* batch, int index);
+JxlDecoderStatus JxlHipBatchReconstructJpegs(JxlHipBatch* batch, void* hip_stream);
+JxlDecoderStatus JxlHipBatchJpegStatus(const JxlHipBatch* batch, int index);
+size_t JxlHipBatchJpegSize(const JxlHipBatch* batch, int index);
+JxlDecoderStatus JxlHipBatchCopyJpeg(JxlHipBatch* batch, int index, uint8_t* dst, size_t cap);
 /* Decode-thread packing: lanes between active entropy-decode threads (64 = one stream per wavefront, 1 = 64 per wavefront). */
 void JxlHipBatchSetLaneStride(JxlHipBatch* batch, int lf, int hf);
 /* Tuning / testing knobs: "force_generic_idct", "hf_block_threads", "lds_code_budget", "debug_stop_after", "lf_wide_once" (the next LF stage of the batch takes the

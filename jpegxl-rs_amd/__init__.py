@@ -157,6 +157,8 @@ def libjxl():
             "JxlHipBatchSetOutputScaled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), vp, C.c_int]),
             "JxlHipPipelineSubmitScaled": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.c_int]),
             "JxlHipImageOutSizeScaled": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlBasicInfo), C.POINTER(sz)]),
+            "JxlHipBatchCanReconstructJpeg": (C.c_int, [vp, C.c_int]), "JxlHipBatchReconstructJpegs": (C.c_int, [vp, vp]),
+            "JxlHipBatchJpegStatus": (C.c_int, [vp, C.c_int]), "JxlHipBatchJpegSize": (sz, [vp, C.c_int]), "JxlHipBatchCopyJpeg": (C.c_int, [vp, C.c_int, vp, sz]),
             "JxlHipBatchSetLaneStride": (None, [vp, C.c_int, C.c_int]), "JxlHipBatchSetOption": (None, [vp, C.c_char_p, C.c_int]),
             "JxlHipBatchPrepare": (C.c_int, [vp, vp]), "JxlHipBatchDecode": (C.c_int, [vp, vp]),
             "JxlHipBatchDecodeTimed": (C.c_int, [vp, vp]), "JxlHipBatchFinish": (C.c_int, [vp, vp]),
@@ -715,6 +717,26 @@ class BatchDecoder:
 
     def finish(self, stream=None):
         self._chk(libjxl().JxlHipBatchFinish(self._h, stream))
+
+    # ---- JPEG reconstruction of the batch (include/jxl_hip.h JxlHipBatchReconstructJpegs; decode.rs:493 `reconstruct` for many files at once)
+    def can_reconstruct_jpeg(self, i) -> bool:
+        """True if image i is a lossless JPEG transcode whose file can be given back; otherwise last_error() says why not."""
+        return bool(libjxl().JxlHipBatchCanReconstructJpeg(self._h, i))
+
+    def reconstruct_jpegs(self, stream=None):
+        """One run of the entropy stages for the whole batch, then the JPEG files (sequential scans are entropy-coded on the GPU).  An image that fails
+        does so alone: jpeg(i) raises for it."""
+        self._chk(libjxl().JxlHipBatchReconstructJpegs(self._h, stream))
+
+    def jpeg(self, i) -> bytes:
+        """The reconstructed file of image i; DecodeError with the image's reason if it has none."""
+        L = libjxl()
+        if L.JxlHipBatchJpegStatus(self._h, i) != JXL_DEC_SUCCESS:
+            raise GenericError(last_error())
+        n = L.JxlHipBatchJpegSize(self._h, i)
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        self._chk(L.JxlHipBatchCopyJpeg(self._h, i, out.ctypes.data, n))
+        return out[:n].tobytes()
 
     def device_output(self, i) -> int:
         return libjxl().JxlHipBatchDeviceOutput(self._h, i)

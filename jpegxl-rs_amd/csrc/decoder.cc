@@ -419,6 +419,8 @@ Batch::~Batch() {
   if (status_pinned_) (void)hipHostFree(status_pinned_);
   Pool().Give(dconst_, const_cap_, device_);
   Pool().Give(dwork_, work_cap_, device_);
+  if (djpeg_) Pool().Give(djpeg_, jpeg_cap_, device_);
+  if (djpeg_out_) Pool().Give(djpeg_out_, jpeg_out_cap_, device_);
   if (dcoef_ && !coef_owner_ && !coef_is_ext_) Pool().Give(dcoef_, coef_cap_, device_);
   if (dbig_ && !big_owner_ && !big_is_ext_) Pool().Give(dbig_, big_cap_, device_);
   if (big_owner_) big_owner_->big_sharers_--;
@@ -921,6 +923,8 @@ int64_t Batch::Info(const std::string& name) const {
   }
   if (name == "hf_nonzeros") { int64_t t = 0; for (uint32_t v : hf_written_) t += v; return t; }   // non-zero AC coefficients per decode of the batch (known after a Finish)
   if (name == "mod_group_lds_bytes") return prepared_ ? (int64_t)ModularGroupLdsBytes(cfg) : -1;
+  if (name == "jpeg_device_images") return jpeg_device_images_;     // images of the last ReconstructJpegs whose scans the device wrote / that went through the host writer
+  if (name == "jpeg_host_images") return jpeg_host_images_;
   if (name == "lf_simt_lanes") return lf_simt_.num_lanes;
   if (name == "lf_simt_wp") return lf_simt_.num_lanes ? lf_simt_.any_wp : 0;     // the SIMT launch is the weighted-predictor instantiation
   // the kernels the last decode's LF / HF stage launched (kernels.h kHfVar* / kLfVar* bits) and the LDS sizes that chose them (bytes, after Prepare)
@@ -2529,19 +2533,38 @@ StageTimes Batch::CollectTimes(int* runs) {
   return t;
 }
 
+static std::string DeviceStatusMessage(uint32_t status, int frame, bool* unsupported) {
+  *unsupported = (status & kErrUnsupported) != 0;
+  if (*unsupported) return "unsupported: stream feature on the device path (frame " + std::to_string(frame) + ")";
+  return "corrupt stream (device status " + std::to_string(status) + ", frame " + std::to_string(frame) + ")";
+}
+
 void Batch::Finish(void* stream_v) {
+  vec<uint32_t> status;
+  FinishStatus(stream_v, &status);
+  for (size_t i = 0; i < status.size(); i++) {
+    if (!status[i]) continue;
+    bool unsupported = false;
+    const std::string msg = DeviceStatusMessage(status[i], (int)i, &unsupported);
+    throw ParseError(msg, unsupported);
+  }
+}
+
+// Finish without the throw: waits, hands out the per-unit status words (0 = decoded) and clears the ones that are set, so that a caller can let a damaged
+// frame fail alone (ReconstructJpegs)
+void Batch::FinishStatus(void* stream_v, vec<uint32_t>* status_out) {
   hipStream_t stream = (hipStream_t)stream_v;
   if (lf_batch_) lf_batch_->Finish(stream_v);            // (a damaged LF frame fails the decode like a damaged frame)
   HIP_CHECK(hipStreamSynchronize(stream));
   const int n = (int)images_.size();
-  vec<uint32_t> status(n, 0);
+  vec<uint32_t>& status = *status_out;
+  status.assign(n, 0);
   HIP_CHECK(hipMemcpy(status.data(), dwork_ + status_off_, (size_t)n * 4, hipMemcpyDeviceToHost));
   for (int i = 0; i < n; i++) {
     if (!status[i]) continue;
     HIP_CHECK(hipMemset(dwork_ + status_off_, 0, (size_t)n * 4));
     CoefDirty() = true;                                  // (a failed stream may have written where no IDCT looked)
-    if (status[i] & kErrUnsupported) throw ParseError("unsupported: stream feature on the device path (frame " + std::to_string(i) + ")", true);
-    throw ParseError("corrupt stream (device status " + std::to_string(status[i]) + ", frame " + std::to_string(i) + ")", false);
+    return;                                              // (as when Finish throws: the counters below wait for a decode that succeeds)
   }
   if (any_vardct_ && decodes_since_finish_ > 0) {
     // non-zero coefficients per decode of every frame (deterministic per stream): the HF stage's written bytes for StageBytes
@@ -2663,6 +2686,215 @@ vec<uint8_t> Batch::ReconstructJpeg(int i, void* stream_v) {
   vec<uint8_t> out;
   if (!WriteJpeg(jd, e.ih.xsize, e.ih.ysize, planes, &out, &why)) throw ParseError(why, true);
   return out;
+}
+
+// ---- batch JPEG reconstruction: one entropy run for all images, sequential scans written by the device (jpeg_write.hip) ---------------------
+namespace {
+// quantisation tables and sampling factors of the JPEG from the frame (as ReconstructJpeg documents them); component planes packed one after another
+bool FillJpegFromFrame(const FramePlan& p, JpegData* jd, size_t comp_first[3], size_t* nblk, std::string* why) {
+  const QuantTableSpec& q = p.qspec[0];
+  if (q.mode != 7) { *why = "JPEG reconstruction: quantisation table is not a RAW (JPEG) table"; return false; }
+  const size_t ncomp = jd->components.size();
+  int max_hs = 0, max_vs = 0;
+  for (int c = 0; c < 3; c++) { max_hs = std::max(max_hs, (int)p.hs[c]); max_vs = std::max(max_vs, (int)p.vs[c]); }
+  *nblk = 0;
+  for (size_t c = 0; c < ncomp; c++) {
+    const int ch = ncomp == 1 ? 1 : (c == 0 ? 1 : c == 1 ? 0 : 2);
+    if (q.raw[ch].size() != 64) { *why = "JPEG reconstruction: RAW table size"; return false; }
+    JpegQuantTable& t = jd->quant[jd->components[c].quant_idx];
+    for (int v = 0; v < 8; v++) for (int u = 0; u < 8; u++) t.values[v * 8 + u] = q.raw[ch][u * 8 + v];
+    jd->components[c].h_samp = 1u << (max_hs - p.hs[ch]);
+    jd->components[c].v_samp = 1u << (max_vs - p.vs[ch]);
+    comp_first[c] = *nblk;
+    *nblk += (size_t)(p.bw >> p.hs[ch]) * (p.bh >> p.vs[ch]);
+  }
+  return true;
+}
+struct ScanPlan { JpegHuffTable dc[4], ac[4]; uint32_t restart = 0; bool progressive = false; };
+}  // namespace
+
+void Batch::ReconstructJpegs(void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  const int n = (int)pub_.size();
+  jpeg_results_.clear(); jpeg_results_.resize((size_t)n);
+  jpeg_device_images_ = jpeg_host_images_ = 0;
+  struct Img { bool ok = false, device = false; size_t first_blk = 0, nblk = 0, comp_first[3] = {0, 0, 0}; size_t first_scan = 0, num_scans = 0; std::vector<ScanPlan> plans; };
+  std::vector<Img> im((size_t)n);
+  bool any = false;
+  for (int i = 0; i < n; i++) {
+    std::string why;
+    if (CanReconstructJpeg(i, &why)) { im[i].ok = true; any = true; } else jpeg_results_[i].error = "JPEG reconstruction: " + why;
+  }
+  if (!any) return;
+  if (!prepared_) Prepare(stream_v);
+  HIP_CHECK(hipSetDevice(device_));
+  // ---- host plan: coefficient planes of every image in one arena; scan table and table snapshots of the images the device writes
+  size_t total_blk = 0;
+  vec<JpegScanDev> scans;
+  vec<JpegHuffDev> tables;
+  uint64_t num_blocks = 0, num_segs = 0;
+  for (int i = 0; i < n; i++) {
+    Img& m = im[i];
+    if (!m.ok) continue;
+    const ImageEntry& e = *images_[pub_[i].first_unit];
+    JpegData& jd = *jpeg_data_[i];
+    std::string why;
+    if (!FillJpegFromFrame(e.plan, &jd, m.comp_first, &m.nblk, &why)) { m.ok = false; jpeg_results_[i].error = why; continue; }
+    m.first_blk = total_blk; total_blk += m.nblk;
+    if (jpeg_host_writer) continue;
+    // the marker walk with an emitter that writes nothing: the scans, the tables in force at each
+    vec<uint8_t> scratch;
+    bool eligible = true;
+    vec<JpegScanDev> mine;
+    uint64_t blocks = num_blocks, segs = num_segs;
+    const size_t table0 = tables.size();
+    const bool walked = WriteJpegMarkers(jd, e.ih.xsize, e.ih.ysize, [&](const JpegScanContext& cx, vec<uint8_t>*, std::string*) {
+      const JpegScanInfo& s = *cx.scan;
+      ScanPlan sp; sp.restart = cx.restart_interval; sp.progressive = cx.is_progressive;
+      memcpy(sp.dc, cx.dc_tab, sizeof(sp.dc)); memcpy(sp.ac, cx.ac_tab, sizeof(sp.ac));
+      m.plans.push_back(sp);
+      // sequential scans only: progressive scans, extra zero runs and whatever the tables below cannot express go to the host writer
+      if (cx.is_progressive || s.Ss != 0 || s.Se != 63 || s.Ah != 0 || s.Al != 0 || !s.extra_zero_runs.empty() || s.num_components < 1 || s.num_components > 3) { eligible = false; return true; }
+      JpegScanDev d;
+      memset(&d, 0, sizeof(d));
+      uint32_t cols, rows;
+      JpegScanGrid(cx, &cols, &rows);
+      d.ncomp = s.num_components; d.scan_cols = cols; d.restart = cx.restart_interval;
+      d.frame = (uint32_t)pub_[i].first_unit; d.image = (uint32_t)i;
+      for (uint32_t k = 0; k < s.num_components; k++) {
+        const JpegScanComponent& sc = s.components[k];
+        for (uint32_t k2 = 0; k2 < k; k2++) if (s.components[k2].comp_idx == sc.comp_idx) eligible = false;     // (the DC predictor is kept per component)
+        const JpegComponentInfo& comp = jd.components[sc.comp_idx];
+        if (!cx.dc_tab[sc.dc_tbl_idx & 3].init || !cx.ac_tab[sc.ac_tbl_idx & 3].init) eligible = false;   // (the host writer names the error)
+        d.h[k] = (uint8_t)(s.num_components > 1 ? comp.h_samp : 1); d.v[k] = (uint8_t)(s.num_components > 1 ? comp.v_samp : 1);
+        d.plane[k] = (uint32_t)(m.first_blk + m.comp_first[sc.comp_idx]); d.pitch[k] = cx.mcu_cols * comp.h_samp;
+        d.dc[k] = (uint16_t)(sc.dc_tbl_idx & 3); d.ac[k] = (uint16_t)(4 + (sc.ac_tbl_idx & 3));       // (slots of this scan's snapshot: rebased below)
+        d.blocks_per_mcu += (uint32_t)d.h[k] * d.v[k];
+      }
+      const uint64_t nb = (uint64_t)cols * rows * d.blocks_per_mcu, per_seg = d.restart ? (uint64_t)d.restart * d.blocks_per_mcu : nb;
+      // a block is at most 27 + 63 x 31 + 3 x 16 + 16 bits: segments whose worst case leaves 32 bits stay on the host
+      if (nb == 0 || per_seg * 2044 >= ((uint64_t)1 << 32)) eligible = false;
+      d.first_block = (uint32_t)blocks; d.num_blocks = (uint32_t)nb;
+      d.first_seg = (uint32_t)segs; d.num_segs = (uint32_t)(d.restart ? ((uint64_t)cols * rows + d.restart - 1) / d.restart : 1);
+      blocks += nb; segs += d.num_segs;
+      if (blocks >= ((uint64_t)1 << 31) || segs >= ((uint64_t)1 << 31) || table0 + 8 * (mine.size() + 1) > 65000) { eligible = false; return true; }
+      // table snapshots: eight slots per scan (tables are few hundred bytes; DHT markers between scans redefine slots)
+      const uint32_t base = (uint32_t)(table0 + 8 * mine.size());
+      for (uint32_t k = 0; k < s.num_components; k++) { d.dc[k] = (uint16_t)(base + d.dc[k]); d.ac[k] = (uint16_t)(base + d.ac[k]); }
+      mine.push_back(d);
+      return true;
+    }, &scratch, &why);
+    if (!walked || !eligible || mine.empty() || total_blk * 64 >= ((uint64_t)1 << 37)) continue;        // host writer (it reports what the walk ran into)
+    for (size_t k = 0; k < mine.size(); k++) {
+      for (int t = 0; t < 8; t++) {
+        const JpegHuffTable& src = t < 4 ? m.plans[k].dc[t] : m.plans[k].ac[t - 4];
+        JpegHuffDev hd; memcpy(hd.depth, src.depth, 256); memcpy(hd.code, src.code, 512);
+        tables.push_back(hd);
+      }
+    }
+    m.device = true; m.first_scan = scans.size(); m.num_scans = mine.size();
+    scans.insert(scans.end(), mine.begin(), mine.end());
+    num_blocks = blocks; num_segs = segs;
+  }
+  // ---- arena: coefficients, tables, per-block and per-segment arrays (one allocation per batch object, kept like the other arenas)
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  const size_t o_coef = take(total_blk * 128), o_scans = take(scans.size() * sizeof(JpegScanDev)), o_tables = take(tables.size() * sizeof(JpegHuffDev));
+  const size_t o_bits = take(num_blocks * 4), o_bitpos = take((num_blocks + 1) * 8), o_segbits = take(num_segs * 4), o_segbytes = take(num_segs * 4);
+  const size_t o_segoff = take((num_segs + 1) * 8), o_tile = take((std::max(num_blocks, num_segs) / 1024 + 1) * 8), o_flags = take((size_t)n * 4);
+  DevReserve((void**)&djpeg_, &jpeg_cap_, std::max<size_t>(off, 256));
+  if (!scans.empty()) {
+    HIP_CHECK(hipMemcpyAsync(djpeg_ + o_scans, scans.data(), scans.size() * sizeof(JpegScanDev), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(djpeg_ + o_tables, tables.data(), tables.size() * sizeof(JpegHuffDev), hipMemcpyHostToDevice, stream));
+  }
+  HIP_CHECK(hipMemsetAsync(djpeg_ + o_flags, 0, (size_t)n * 4, stream));
+  // ---- one entropy decode of the batch (LF stage: JPEG DC, block metadata; HF stage: AC), coefficients into JPEG layout
+  RunPart(stream_v, 1, false);
+  RunPart(stream_v, 3, false);
+  for (int i = 0; i < n; i++) {
+    if (!im[i].ok) continue;
+    const int u = pub_[i].first_unit;
+    const FramePlan& p = images_[u]->plan;
+    const JpegData& jd = *jpeg_data_[i];
+    JpegCoefArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ncomp = (uint32_t)jd.components.size();
+    for (size_t c = 0; c < jd.components.size(); c++) a.comp_off[c] = (uint32_t)im[i].comp_first[c];
+    for (size_t c = 0; c < jd.components.size(); c++) for (int k = 0; k < 64; k++) a.qt[c][k] = jd.quant[jd.components[c].quant_idx].values[k];
+    a.out = (int16_t*)(djpeg_ + o_coef) + im[i].first_blk * 64;
+    LaunchJpegCoefficients(dframes_, u, a, p.bw, p.bh, stream_v);
+  }
+  DebugSync("JPEG coefficients", stream_v);
+  JpegWritePlan wp;
+  memset(&wp, 0, sizeof(wp));
+  wp.frames = dframes_; wp.scans = (const JpegScanDev*)(djpeg_ + o_scans); wp.tables = (const JpegHuffDev*)(djpeg_ + o_tables); wp.coef = (const int16_t*)(djpeg_ + o_coef);
+  wp.num_scans = (uint32_t)scans.size(); wp.num_blocks = (uint32_t)num_blocks; wp.num_segs = (uint32_t)num_segs;
+  wp.bits = (uint32_t*)(djpeg_ + o_bits); wp.bitpos = (uint64_t*)(djpeg_ + o_bitpos); wp.seg_bits = (uint32_t*)(djpeg_ + o_segbits); wp.seg_bytes = (uint32_t*)(djpeg_ + o_segbytes);
+  wp.seg_off = (uint64_t*)(djpeg_ + o_segoff); wp.tile_tmp = (uint64_t*)(djpeg_ + o_tile); wp.flags = (uint32_t*)(djpeg_ + o_flags);
+  LaunchJpegSizes(wp, stream_v);
+  CheckLaunches("JPEG writer, sizes");
+  vec<uint32_t> status;
+  FinishStatus(stream_v, &status);         // (waits; the kernels above and below skip frames whose status word is set — it is cleared only on the host's copy)
+  vec<uint32_t> flags((size_t)n, 0);
+  uint64_t raw_bytes = 0;
+  vec<JpegSegDev> recs;
+  vec<uint8_t> stuffed;
+  if (num_segs) {
+    // the one size the device decides: bytes of all segments before stuffing.  Everything pass 2 writes is sized from it here, before the launch.
+    HIP_CHECK(hipMemcpy(&raw_bytes, wp.seg_off + num_segs, 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(flags.data(), wp.flags, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (raw_bytes > num_blocks * 256) throw ParseError("JPEG writer: segment sizes beyond the per-block bound", false);
+    const uint64_t chunks = (raw_bytes + JpegStuffChunkBytes() - 1) / JpegStuffChunkBytes();
+    size_t off2 = 0;
+    auto take2 = [&](size_t bytes) { const size_t o = off2; off2 += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_raw = take2(raw_bytes + 8), o_ffc = take2(chunks * 4), o_ffb = take2((chunks + 1) * 8), o_tile2 = take2((chunks / 1024 + 1) * 8);
+    const size_t o_stuffed = take2(raw_bytes * 2 + 8), o_recs = take2(num_segs * sizeof(JpegSegDev));
+    DevReserve((void**)&djpeg_out_, &jpeg_out_cap_, std::max<size_t>(off2, 256));
+    JpegPackBuffers pb;
+    pb.raw = djpeg_out_ + o_raw; pb.raw_bytes = raw_bytes; pb.ff_count = (uint32_t*)(djpeg_out_ + o_ffc); pb.ff_before = (uint64_t*)(djpeg_out_ + o_ffb);
+    pb.tile_tmp = (uint64_t*)(djpeg_out_ + o_tile2); pb.stuffed = djpeg_out_ + o_stuffed; pb.stuffed_cap = raw_bytes * 2; pb.recs = (JpegSegDev*)(djpeg_out_ + o_recs);
+    // (FinishStatus cleared the status words of frames that failed: pass 1 gave their blocks zero bits, which keeps pass 2 off them)
+    LaunchJpegPack(wp, pb, stream_v);
+    CheckLaunches("JPEG writer, pack");
+    uint64_t num_ff = 0;
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipMemcpy(&num_ff, pb.ff_before + chunks, 8, hipMemcpyDeviceToHost));
+    if (num_ff > raw_bytes) throw ParseError("JPEG writer: stuffing count beyond the buffer", false);
+    recs.resize(num_segs); stuffed.resize(raw_bytes + num_ff);
+    HIP_CHECK(hipMemcpy(recs.data(), pb.recs, num_segs * sizeof(JpegSegDev), hipMemcpyDeviceToHost));
+    if (!stuffed.empty()) HIP_CHECK(hipMemcpy(stuffed.data(), pb.stuffed, stuffed.size(), hipMemcpyDeviceToHost));
+  }
+  // ---- per image: splice (device path) or Huffman-encode on the host from its coefficients
+  for (int i = 0; i < n; i++) {
+    Img& m = im[i];
+    if (!m.ok) continue;
+    JpegResult& r = jpeg_results_[i];
+    const ImageEntry& e = *images_[pub_[i].first_unit];
+    const JpegData& jd = *jpeg_data_[i];
+    if (const uint32_t st = status[pub_[i].first_unit]) { bool unsupported; r.error = DeviceStatusMessage(st, pub_[i].first_unit, &unsupported); continue; }
+    std::string why;
+    if (m.device && flags[i] == 0) {
+      size_t scan_k = 0;
+      const bool ok = WriteJpegMarkers(jd, e.ih.xsize, e.ih.ysize, [&](const JpegScanContext& cx, vec<uint8_t>* out, std::string* err) {
+        if (scan_k >= m.num_scans) { if (err) *err = "JPEG writer: scan count"; return false; }
+        const JpegScanDev& d = scans[m.first_scan + scan_k++];
+        vec<JpegSegmentRecord> segs(d.num_segs);
+        for (uint32_t g = 0; g < d.num_segs; g++) {
+          const JpegSegDev& rec = recs[d.first_seg + g];
+          if (rec.offset + rec.size > stuffed.size()) { if (err) *err = "JPEG writer: segment record outside the buffer"; return false; }
+          segs[g].bytes = stuffed.data() + rec.offset; segs[g].size = rec.size; segs[g].trail_bits = (uint8_t)(rec.trail >> 8); segs[g].trail_count = (uint8_t)(rec.trail & 0xFF);
+        }
+        return SpliceJpegScan(cx, segs.data(), segs.size(), out, err);
+      }, &r.bytes, &why);
+      if (ok) { r.ok = true; jpeg_device_images_++; } else { r.bytes.clear(); r.error = why; }
+      continue;
+    }
+    // host writer: progressive scans, extra zero runs, "jpeg_host_writer" — and images the device flagged, whose error the host writer names
+    vec<int16_t> host(m.nblk * 64);
+    HIP_CHECK(hipMemcpy(host.data(), (const int16_t*)(djpeg_ + o_coef) + m.first_blk * 64, host.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
+    const int16_t* planes[3] = {host.data(), host.data() + m.comp_first[1] * 64, host.data() + m.comp_first[2] * 64};
+    if (WriteJpeg(jd, e.ih.xsize, e.ih.ysize, planes, &r.bytes, &why)) { r.ok = true; jpeg_host_images_++; } else { r.bytes.clear(); r.error = why; }
+  }
 }
 
 void Batch::CopyOutputSlotToHost(int i, int slot, void* dst, size_t size, void* stream_v) {

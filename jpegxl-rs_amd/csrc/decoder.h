@@ -135,6 +135,15 @@ class Batch {
   // the quantised coefficients in JPEG layout and serialises the file on the host; throws ParseError if something does not fit.
   bool CanReconstructJpeg(int i, std::string* why = nullptr);
   vec<uint8_t> ReconstructJpeg(int i, void* stream);
+  // The same for every image of the batch from one run of the entropy stages.  Images whose scans are all sequential Huffman scans get their entropy-coded
+  // segments written on the device (jpeg_write.hip) and spliced between the markers on the host; progressive scans, scans with extra zero runs and
+  // cfg.jpeg_host_writer go through WriteJpeg, from coefficients copied to the host for those images only.  An image that cannot be reconstructed, or whose
+  // stream is damaged, fails alone: jpeg_result(i).  Throws only for what concerns the whole batch (HIP errors, Prepare).
+  struct JpegResult { bool ok = false; std::string error; vec<uint8_t> bytes; };
+  void ReconstructJpegs(void* stream);
+  bool jpeg_host_writer = false;          // every image through the host writer (tests, measurements)
+  const JpegResult* jpeg_result(int i) const { return i >= 0 && (size_t)i < jpeg_results_.size() ? &jpeg_results_[(size_t)i] : nullptr; }
+  void FinishStatus(void* stream, vec<uint32_t>* per_unit);
   // Copies frame i's pixels to host memory (after Finish).
   void CopyOutputToHost(int i, void* dst, size_t size, void* stream);
   // the preview of image i (JXL_DEC_PREVIEW_IMAGE): its header (the image header with the preview's size), the size of its output, the decode into host memory
@@ -203,6 +212,10 @@ class Batch {
   std::unique_ptr<Batch> lf_batch_;
   vec<LfTarget> lf_targets_;                   // (of the batch that decodes LF frames: per image, where its planes go)
   vec<std::unique_ptr<JpegData>> jpeg_data_;   // per image, parsed lazily by CanReconstructJpeg
+  std::vector<JpegResult> jpeg_results_;       // per image, of the last ReconstructJpegs
+  int jpeg_device_images_ = 0, jpeg_host_images_ = 0;
+  uint8_t* djpeg_ = nullptr; size_t jpeg_cap_ = 0;           // ReconstructJpegs: coefficient planes in JPEG layout, scan table, per-block / per-segment arrays
+  uint8_t* djpeg_out_ = nullptr; size_t jpeg_out_cap_ = 0;   // ... raw and stuffed segment bytes, segment records
   bool any_complex_ = false;
   void PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off);
   void EnqueuePostOps(void* stream);

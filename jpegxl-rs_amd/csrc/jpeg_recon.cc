@@ -256,7 +256,7 @@ bool FillJpegMetadata(JpegData* jd, const JpegMetadataSources& src, std::string*
 
 namespace {
 
-struct HuffTable { uint8_t depth[256]; uint16_t code[256]; bool init = false; };
+typedef JpegHuffTable HuffTable;
 
 // dec_jpeg_data_writer.cc BuildHuffmanCodeTable: canonical JPEG code from counts / values (the 256 sentinel keeps the all-ones code free)
 bool BuildHuffTable(const JpegHuffmanCode& h, HuffTable* t) {
@@ -412,7 +412,132 @@ bool EncodeBlockRefinement(const int16_t* c, const HuffTable& act, int Ss, int S
 
 }  // namespace
 
+void JpegScanGrid(const JpegScanContext& cx, uint32_t* scan_cols, uint32_t* scan_rows) {
+  *scan_cols = cx.mcu_cols; *scan_rows = cx.mcu_rows;
+  if (cx.scan->num_components > 1) return;
+  const JpegComponentInfo& c0 = cx.jd->components[cx.scan->components[0].comp_idx];
+  *scan_cols = (cx.width * c0.h_samp + 8 * cx.max_h - 1) / (8 * cx.max_h);
+  *scan_rows = (cx.height * c0.v_samp + 8 * cx.max_v - 1) / (8 * cx.max_v);
+}
+
+bool SpliceJpegScan(const JpegScanContext& cx, const JpegSegmentRecord* segs, size_t num_segs, vec<uint8_t>* out, std::string* err) {
+  auto fail = [&](const char* m) { if (err) *err = std::string("JPEG writer: ") + m; return false; };
+  const JpegData& jd = *cx.jd;
+  for (size_t k = 0; k < num_segs; k++) {
+    const JpegSegmentRecord& g = segs[k];
+    if (k > 0) { out->push_back(0xFF); out->push_back((uint8_t)(0xD0 + ((k - 1) & 7))); }
+    if (g.size) out->insert(out->end(), g.bytes, g.bytes + g.size);
+    if (g.trail_count == 0) continue;
+    if (g.trail_count > 7) return fail("bad segment record");
+    // JumpToByteBoundary (BitWriter::Pad): ones, or the recorded padding bits
+    const int n = 8 - g.trail_count;
+    uint32_t pattern = (1u << n) - 1;
+    if (jd.has_zero_padding_bit) {
+      pattern = 0;
+      for (int i = 0; i < n; i++) { if (*cx.pad_pos >= jd.padding_bits.size()) return fail("padding bits exhausted"); pattern = (pattern << 1) | (jd.padding_bits[(*cx.pad_pos)++] ? 1u : 0u); }
+    }
+    const uint8_t b = (uint8_t)((g.trail_bits & (0xFFu << n)) | pattern);
+    out->push_back(b);
+    if (b == 0xFF) out->push_back(0);
+  }
+  return true;
+}
+
+namespace {
+
+// EncodeScan on the host: the scan's entropy-coded data from the coefficient planes (sequential, progressive first pass, refinement)
+bool EncodeScanHost(const JpegScanContext& cx, const int16_t* const* coeffs, vec<uint8_t>* out, std::string* err) {
+  auto fail = [&](const char* m) { if (err) *err = std::string("JPEG writer: ") + m; return false; };
+  const JpegData& jd = *cx.jd;
+  const JpegScanInfo& s = *cx.scan;
+  const uint32_t width = cx.width, height = cx.height, mcu_cols = cx.mcu_cols, restart_interval = cx.restart_interval;
+  (void)width; (void)height;
+  const HuffTable* dc_tab = cx.dc_tab; const HuffTable* ac_tab = cx.ac_tab;
+  const int mode = s.Ah != 0 ? 2 : cx.is_progressive ? 1 : 0;    // EncodeScan<kMode>: sequential, progressive first pass, refinement
+  EobState eob_state;
+  // ---- entropy-coded segment (EncodeScan, sequential mode).  Interleaved scans: an MCU holds v_samp x h_samp blocks of every scan
+  // component and the MCU grid covers the padded image; a single-component scan walks that component's own blocks, one per MCU,
+  // over ceil(size * samp / (8 * max_samp)) of them (the blocks that hold image data).
+  BitWriter w; w.out = out;
+  int last_dc[4] = {0, 0, 0, 0};
+  uint32_t restarts_to_go = restart_interval, next_restart = 0, block_scan_index = 0;
+  size_t ezr_pos = 0, reset_pos = 0;
+  const bool interleaved = s.num_components > 1;
+  uint32_t scan_cols, scan_rows;
+  JpegScanGrid(cx, &scan_cols, &scan_rows);
+  for (uint32_t my = 0; my < scan_rows; my++) for (uint32_t mx = 0; mx < scan_cols; mx++) {
+    if (restart_interval > 0 && restarts_to_go == 0) {
+      eob_state.Flush(w);
+      if (!w.Pad(jd, cx.pad_pos)) return fail("padding bits exhausted");
+      out->push_back(0xFF); out->push_back((uint8_t)(0xD0 + next_restart));
+      next_restart = (next_restart + 1) & 7;
+      restarts_to_go = restart_interval;
+      memset(last_dc, 0, sizeof(last_dc));
+    }
+    for (uint32_t i = 0; i < s.num_components; i++) {
+      const JpegScanComponent& sc = s.components[i];
+      const JpegComponentInfo& comp = jd.components[sc.comp_idx];
+      const uint32_t nby = interleaved ? comp.v_samp : 1, nbx = interleaved ? comp.h_samp : 1, comp_bw = mcu_cols * comp.h_samp;
+      for (uint32_t iy = 0; iy < nby; iy++) for (uint32_t ix = 0; ix < nbx; ix++) {
+      const HuffTable& dct = dc_tab[sc.dc_tbl_idx & 3];
+      const HuffTable& act = ac_tab[sc.ac_tbl_idx & 3];
+      if ((s.Ss == 0 && s.Ah == 0 && !dct.init) || (s.Se > 0 && !act.init)) return fail("scan uses an undefined Huffman table");
+      if (reset_pos < s.reset_points.size() && s.reset_points[reset_pos] == block_scan_index) { eob_state.Flush(w); reset_pos++; }   // the original file ended its EOB run here
+      int num_zero_runs = 0;
+      if (ezr_pos < s.extra_zero_runs.size() && s.extra_zero_runs[ezr_pos].first == block_scan_index) num_zero_runs = (int)s.extra_zero_runs[ezr_pos++].second;
+      const int16_t* c = coeffs[sc.comp_idx] + ((size_t)(my * nby + iy) * comp_bw + (mx * nbx + ix)) * 64;
+      if (mode != 0) {
+        const bool ok = mode == 1 ? EncodeBlockProgressive(c, dct, act, (int)s.Ss, (int)s.Se, (int)s.Al, num_zero_runs, eob_state, &last_dc[sc.comp_idx], w)
+                                  : EncodeBlockRefinement(c, act, (int)s.Ss, (int)s.Se, (int)s.Al, eob_state, w);
+        if (!ok) return fail("coefficient out of range");
+        if (!w.ok) return fail("symbol without a Huffman code");
+        block_scan_index++;
+        continue;
+      }
+      // EncodeDCTBlockSequential
+      int temp2 = c[0], temp = temp2 - last_dc[sc.comp_idx];
+      last_dc[sc.comp_idx] = temp2;
+      temp2 = temp;
+      if (temp < 0) { temp = -temp; temp2--; }
+      int dc_nbits = 0;
+      while ((temp >> dc_nbits) != 0) dc_nbits++;
+      if (dc_nbits >= 12) return fail("DC difference out of range");
+      w.Symbol(dc_nbits, dct);
+      if (dc_nbits > 0) w.Put((uint32_t)temp2 & ((1u << dc_nbits) - 1), dc_nbits);
+      int r = 0;
+      for (int k = 1; k < 64; k++) {
+        temp = c[kNaturalOrder[k]];
+        if (temp == 0) { r++; continue; }
+        if (temp < 0) { temp = -temp; temp2 = ~temp; } else temp2 = temp;
+        while (r > 15) { w.Symbol(0xF0, act); r -= 16; }
+        int ac_nbits = 0;
+        while ((temp >> ac_nbits) != 0) ac_nbits++;
+        if (ac_nbits >= 16) return fail("AC coefficient out of range");
+        w.Symbol((r << 4) + ac_nbits, act);
+        w.Put((uint32_t)temp2 & ((1u << ac_nbits) - 1), ac_nbits);
+        r = 0;
+      }
+      for (int k = 0; k < num_zero_runs; k++) { w.Symbol(0xF0, act); r -= 16; }
+      if (r > 0) w.Symbol(0, act);
+      if (!w.ok) return fail("symbol without a Huffman code");
+      block_scan_index++;
+      }
+    }
+    if (restart_interval > 0) restarts_to_go--;
+  }
+  eob_state.Flush(w);
+  if (!w.ok) return fail("symbol without a Huffman code");
+  if (!w.Pad(jd, cx.pad_pos)) return fail("padding bits exhausted");
+  return true;
+}
+
+}  // namespace
+
 bool WriteJpeg(const JpegData& jd, uint32_t width, uint32_t height, const int16_t* const* coeffs, vec<uint8_t>* out, std::string* err) {
+  return WriteJpegMarkers(jd, width, height, [&](const JpegScanContext& cx, vec<uint8_t>* o, std::string* e) { return EncodeScanHost(cx, coeffs, o, e); }, out, err);
+}
+
+bool WriteJpegMarkers(const JpegData& jd, uint32_t width, uint32_t height, const JpegScanEmitter& emit, vec<uint8_t>* out, std::string* err) {
   auto fail = [&](const char* m) { if (err) *err = std::string("JPEG writer: ") + m; return false; };
   out->clear();
   out->push_back(0xFF); out->push_back(0xD8);
@@ -481,8 +606,6 @@ bool WriteJpeg(const JpegData& jd, uint32_t width, uint32_t height, const int16_
       const JpegScanInfo& s = jd.scan_info[scan_i++];
       if (s.Ss > s.Se || s.Se > 63 || s.Al > 13 || s.Ah > 13) return fail("bad scan parameters");
       if (!is_progressive && !(s.Ss == 0 && s.Se == 63 && s.Al == 0 && s.Ah == 0)) return fail("spectral selection in a sequential JPEG");
-      const int mode = s.Ah != 0 ? 2 : is_progressive ? 1 : 0;    // EncodeScan<kMode>: sequential, progressive first pass, refinement
-      EobState eob_state;
       const size_t len = 6 + 2 * s.num_components;
       out->push_back(0xFF); out->push_back(0xDA); out->push_back((uint8_t)(len >> 8)); out->push_back((uint8_t)len); out->push_back((uint8_t)s.num_components);
       for (uint32_t i = 0; i < s.num_components; i++) {
@@ -490,84 +613,10 @@ bool WriteJpeg(const JpegData& jd, uint32_t width, uint32_t height, const int16_
         out->push_back((uint8_t)((s.components[i].dc_tbl_idx << 4) | s.components[i].ac_tbl_idx));
       }
       out->push_back((uint8_t)s.Ss); out->push_back((uint8_t)s.Se); out->push_back((uint8_t)((s.Ah << 4) | s.Al));
-      // ---- entropy-coded segment (EncodeScan, sequential mode).  Interleaved scans: an MCU holds v_samp x h_samp blocks of every scan
-      // component and the MCU grid covers the padded image; a single-component scan walks that component's own blocks, one per MCU,
-      // over ceil(size * samp / (8 * max_samp)) of them (the blocks that hold image data).
-      BitWriter w; w.out = out;
-      int last_dc[4] = {0, 0, 0, 0};
-      const uint32_t restart_interval = seen_dri ? jd.restart_interval : 0;
-      uint32_t restarts_to_go = restart_interval, next_restart = 0, block_scan_index = 0;
-      size_t ezr_pos = 0, reset_pos = 0;
-      const bool interleaved = s.num_components > 1;
-      uint32_t scan_cols = mcu_cols, scan_rows = mcu_rows;
-      if (!interleaved) {
-        const JpegComponentInfo& c0 = jd.components[s.components[0].comp_idx];
-        scan_cols = (width * c0.h_samp + 8 * max_h - 1) / (8 * max_h);
-        scan_rows = (height * c0.v_samp + 8 * max_v - 1) / (8 * max_v);
-      }
-      for (uint32_t my = 0; my < scan_rows; my++) for (uint32_t mx = 0; mx < scan_cols; mx++) {
-        if (restart_interval > 0 && restarts_to_go == 0) {
-          eob_state.Flush(w);
-          if (!w.Pad(jd, &pad_pos)) return fail("padding bits exhausted");
-          out->push_back(0xFF); out->push_back((uint8_t)(0xD0 + next_restart));
-          next_restart = (next_restart + 1) & 7;
-          restarts_to_go = restart_interval;
-          memset(last_dc, 0, sizeof(last_dc));
-        }
-        for (uint32_t i = 0; i < s.num_components; i++) {
-          const JpegScanComponent& sc = s.components[i];
-          const JpegComponentInfo& comp = jd.components[sc.comp_idx];
-          const uint32_t nby = interleaved ? comp.v_samp : 1, nbx = interleaved ? comp.h_samp : 1, comp_bw = mcu_cols * comp.h_samp;
-          for (uint32_t iy = 0; iy < nby; iy++) for (uint32_t ix = 0; ix < nbx; ix++) {
-          const HuffTable& dct = dc_tab[sc.dc_tbl_idx & 3];
-          const HuffTable& act = ac_tab[sc.ac_tbl_idx & 3];
-          if ((s.Ss == 0 && s.Ah == 0 && !dct.init) || (s.Se > 0 && !act.init)) return fail("scan uses an undefined Huffman table");
-          if (reset_pos < s.reset_points.size() && s.reset_points[reset_pos] == block_scan_index) { eob_state.Flush(w); reset_pos++; }   // the original file ended its EOB run here
-          int num_zero_runs = 0;
-          if (ezr_pos < s.extra_zero_runs.size() && s.extra_zero_runs[ezr_pos].first == block_scan_index) num_zero_runs = (int)s.extra_zero_runs[ezr_pos++].second;
-          const int16_t* c = coeffs[sc.comp_idx] + ((size_t)(my * nby + iy) * comp_bw + (mx * nbx + ix)) * 64;
-          if (mode != 0) {
-            const bool ok = mode == 1 ? EncodeBlockProgressive(c, dct, act, (int)s.Ss, (int)s.Se, (int)s.Al, num_zero_runs, eob_state, &last_dc[sc.comp_idx], w)
-                                      : EncodeBlockRefinement(c, act, (int)s.Ss, (int)s.Se, (int)s.Al, eob_state, w);
-            if (!ok) return fail("coefficient out of range");
-            if (!w.ok) return fail("symbol without a Huffman code");
-            block_scan_index++;
-            continue;
-          }
-          // EncodeDCTBlockSequential
-          int temp2 = c[0], temp = temp2 - last_dc[sc.comp_idx];
-          last_dc[sc.comp_idx] = temp2;
-          temp2 = temp;
-          if (temp < 0) { temp = -temp; temp2--; }
-          int dc_nbits = 0;
-          while ((temp >> dc_nbits) != 0) dc_nbits++;
-          if (dc_nbits >= 12) return fail("DC difference out of range");
-          w.Symbol(dc_nbits, dct);
-          if (dc_nbits > 0) w.Put((uint32_t)temp2 & ((1u << dc_nbits) - 1), dc_nbits);
-          int r = 0;
-          for (int k = 1; k < 64; k++) {
-            temp = c[kNaturalOrder[k]];
-            if (temp == 0) { r++; continue; }
-            if (temp < 0) { temp = -temp; temp2 = ~temp; } else temp2 = temp;
-            while (r > 15) { w.Symbol(0xF0, act); r -= 16; }
-            int ac_nbits = 0;
-            while ((temp >> ac_nbits) != 0) ac_nbits++;
-            if (ac_nbits >= 16) return fail("AC coefficient out of range");
-            w.Symbol((r << 4) + ac_nbits, act);
-            w.Put((uint32_t)temp2 & ((1u << ac_nbits) - 1), ac_nbits);
-            r = 0;
-          }
-          for (int k = 0; k < num_zero_runs; k++) { w.Symbol(0xF0, act); r -= 16; }
-          if (r > 0) w.Symbol(0, act);
-          if (!w.ok) return fail("symbol without a Huffman code");
-          block_scan_index++;
-          }
-        }
-        if (restart_interval > 0) restarts_to_go--;
-      }
-      eob_state.Flush(w);
-      if (!w.ok) return fail("symbol without a Huffman code");
-      if (!w.Pad(jd, &pad_pos)) return fail("padding bits exhausted");
+      JpegScanContext cx;
+      cx.jd = &jd; cx.scan = &s; cx.scan_index = scan_i - 1; cx.width = width; cx.height = height; cx.mcu_cols = mcu_cols; cx.mcu_rows = mcu_rows; cx.max_h = max_h; cx.max_v = max_v;
+      cx.restart_interval = seen_dri ? jd.restart_interval : 0; cx.is_progressive = is_progressive; cx.dc_tab = dc_tab; cx.ac_tab = ac_tab; cx.pad_pos = &pad_pos;
+      if (!emit(cx, out, err)) return false;
     } else if (m == 0xD9) {
       out->push_back(0xFF); out->push_back(0xD9);
       out->insert(out->end(), jd.tail_data.begin(), jd.tail_data.end());

@@ -5,6 +5,7 @@
 // marker serialisation below run on the host.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -57,6 +58,35 @@ bool FillJpegMetadata(JpegData* jd, const JpegMetadataSources& src, std::string*
 // c, the MCU grid being ceil(size / (8 * max sampling factor)); sampling factors from jd.components (set by the caller from the frame header).
 // Sequential (baseline / extended) and progressive (spectral selection, successive approximation, EOB runs) Huffman scans.
 bool WriteJpeg(const JpegData& jd, uint32_t width, uint32_t height, const int16_t* const* coeffs, vec<uint8_t>* out, std::string* err);
+
+// The two halves of WriteJpeg.  WriteJpegMarkers serialises every marker in jbrd order and hands each scan, behind its SOS header, to
+// `emit`, which appends the scan's entropy-coded data (restart markers and padding included).  WriteJpeg's emitter Huffman-encodes the
+// coefficients on the host; the batch path's emitter splices segments that the device wrote (SpliceJpegScan); an emitter that appends
+// nothing turns the walk into a plan of the file's scans (the Huffman tables in force at each of them, the restart interval).
+struct JpegHuffTable { uint8_t depth[256]; uint16_t code[256]; bool init = false; };   // depth 127: the table has no code for the symbol
+struct JpegScanContext {
+  const JpegData* jd = nullptr;
+  const JpegScanInfo* scan = nullptr;
+  size_t scan_index = 0;
+  uint32_t width = 0, height = 0, mcu_cols = 0, mcu_rows = 0, max_h = 1, max_v = 1;
+  uint32_t restart_interval = 0;            // MCUs per restart segment at this scan (0: no DRI marker so far)
+  bool is_progressive = false;
+  const JpegHuffTable* dc_tab = nullptr;    // [4] slots as defined by the DHT markers in front of this scan
+  const JpegHuffTable* ac_tab = nullptr;
+  size_t* pad_pos = nullptr;                // cursor into jd->padding_bits: runs on across restart segments and scans
+};
+using JpegScanEmitter = std::function<bool(const JpegScanContext&, vec<uint8_t>* out, std::string* err)>;
+bool WriteJpegMarkers(const JpegData& jd, uint32_t width, uint32_t height, const JpegScanEmitter& emit, vec<uint8_t>* out, std::string* err);
+
+// Block grid a scan walks (EncodeScan): the MCU grid for interleaved scans, the component's own blocks that hold image data otherwise.
+void JpegScanGrid(const JpegScanContext& cx, uint32_t* scan_cols, uint32_t* scan_rows);
+
+// One restart segment as the device writer leaves it: the byte-stuffed bytes of the segment's complete bytes, and the bits of its last,
+// incomplete byte (trail_count of them, 0..7, in the top bits of trail_bits).
+struct JpegSegmentRecord { const uint8_t* bytes = nullptr; size_t size = 0; uint8_t trail_bits = 0, trail_count = 0; };
+// Appends a scan from its segments: RSTn markers between them (D0..D7, wrapping), every segment's last byte padded with ones or with the
+// recorded padding bits (a padded byte that comes out as 0xFF is stuffed).
+bool SpliceJpegScan(const JpegScanContext& cx, const JpegSegmentRecord* segs, size_t num_segs, vec<uint8_t>* out, std::string* err);
 
 // One-shot Brotli decompression of a stream whose plain size is not announced (container `brob` boxes): the output buffer grows until the
 // stream fits or `limit` bytes are exceeded.  False when the system has no libbrotlidec or the stream is damaged.

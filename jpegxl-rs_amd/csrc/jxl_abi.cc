@@ -984,6 +984,7 @@ void JxlHipBatchSetOption(JxlHipBatch* h, const char* name, int value) {
   // (rounded down to 16 bytes: the kernels put regions of their own behind the staged tables — HfDecodeSimtKernel its lane slots — that must stay aligned)
   else if (n == "lds_code_budget" && value >= 0 && value <= 128 * 1024) h->b->cfg.lds_code_budget = value & ~15;
   else if (n == "lf_force_big" && value >= -1 && value <= 2) h->b->cfg.lf_force_big = value;
+  else if (n == "jpeg_host_writer") h->b->jpeg_host_writer = value != 0;   // JxlHipBatchReconstructJpegs: every image through the host's Huffman writer
   else if (n == "hf_lanes_per_wave" && value >= 0 && value <= 64) h->b->cfg.hf_lanes_per_wave = value;   // SIMT HF stage: group streams per wavefront (1: the wave-wide kernel where it applies); 0: the throughput packing
 }
 size_t JxlHipBatchDebugRead(JxlHipBatch* h, int index, const char* name, int channel, void* dst, size_t cap, void* s) {
@@ -991,6 +992,35 @@ size_t JxlHipBatchDebugRead(JxlHipBatch* h, int index, const char* name, int cha
 }
 int64_t JxlHipBatchGetInfo(const JxlHipBatch* h, const char* name) {
   try { return h->b->Info(name ? name : ""); } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
+}
+// ---- JPEG reconstruction of a whole batch (decoder.cc Batch::ReconstructJpegs)
+int JxlHipBatchCanReconstructJpeg(JxlHipBatch* h, int i) {
+  try {
+    if (i < 0 || (size_t)i >= h->b->size()) { SetLastError("JxlHipBatchCanReconstructJpeg: no such image"); return 0; }
+    std::string why;
+    if (h->b->CanReconstructJpeg(i, &why)) return 1;
+    SetLastError("JPEG reconstruction: " + why);
+    return 0;
+  } catch (const std::exception& e) { SetLastError(e.what()); return 0; }
+}
+JxlDecoderStatus JxlHipBatchReconstructJpegs(JxlHipBatch* h, void* s) { BATCH_TRY(h->b->ReconstructJpegs(s)) }
+JxlDecoderStatus JxlHipBatchJpegStatus(const JxlHipBatch* h, int i) {
+  const Batch::JpegResult* r = h->b->jpeg_result(i);
+  if (!r) { SetLastError("JxlHipBatchJpegStatus: no such image, or JxlHipBatchReconstructJpegs has not run"); return JXL_DEC_ERROR; }
+  if (r->ok) return JXL_DEC_SUCCESS;
+  SetLastError(r->error);
+  return JXL_DEC_ERROR;
+}
+size_t JxlHipBatchJpegSize(const JxlHipBatch* h, int i) {
+  const Batch::JpegResult* r = h->b->jpeg_result(i);
+  return r && r->ok ? r->bytes.size() : 0;
+}
+JxlDecoderStatus JxlHipBatchCopyJpeg(JxlHipBatch* h, int i, uint8_t* dst, size_t cap) {
+  if (JxlHipBatchJpegStatus(h, i) != JXL_DEC_SUCCESS) return JXL_DEC_ERROR;
+  const Batch::JpegResult* r = h->b->jpeg_result(i);
+  if (!dst || cap < r->bytes.size()) { SetLastError("JxlHipBatchCopyJpeg: the buffer is smaller than JxlHipBatchJpegSize"); return JXL_DEC_ERROR; }
+  if (!r->bytes.empty()) memcpy(dst, r->bytes.data(), r->bytes.size());
+  return JXL_DEC_SUCCESS;
 }
 uint64_t JxlHipBatchTotalPixels(const JxlHipBatch* h) { return h->b->total_pixels(); }
 uint64_t JxlHipBatchCompressedBytes(const JxlHipBatch* h) { return h->b->compressed_bytes(); }

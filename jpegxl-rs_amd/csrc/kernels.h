@@ -315,6 +315,38 @@ void LaunchWrite(const WriteArgs& a, void* stream);
 // chroma-from-luma of the transcoder undone (dec_group.cc, jpeg branch).  qt: the JPEG quantisation tables, natural order.
 struct JpegCoefArgs { int16_t* out; uint32_t ncomp; int32_t qt[3][64]; uint32_t comp_off[3]; };   // comp_off: first block of a component's plane (subsampled frames)
 void LaunchJpegCoefficients(const FrameDev* frames, int fidx, const JpegCoefArgs& a, uint32_t bw, uint32_t bh, void* stream);
+// ---- device-side writer of sequential Huffman JPEG scans (jpeg_write.hip).  One JpegScanDev per (image, scan) of the batch that takes the device path: the blocks
+// of all scans, and their restart segments, are numbered through in table order (first_block / first_seg).
+struct JpegScanDev {
+  uint32_t first_block, num_blocks, first_seg, num_segs;
+  uint32_t frame, image;                 // FrameDev whose status word says whether the coefficients exist; slot of the per-image error flags
+  uint32_t ncomp, blocks_per_mcu, scan_cols, restart;   // restart: MCUs per restart segment, 0 = the scan is one segment
+  uint32_t plane[4], pitch[4];           // per scan component: first block of its coefficient plane in the batch's arena, blocks per plane row
+  uint8_t h[4], v[4]; uint16_t dc[4], ac[4];      // blocks per MCU across / down (1 x 1 in a single-component scan); Huffman tables, as indices into JpegWritePlan::tables
+};
+struct JpegHuffDev { uint8_t depth[256]; uint16_t code[256]; };      // one table slot as defined at one scan (depth 127: no code)
+struct JpegSegDev { uint64_t offset; uint32_t size, trail; };        // a restart segment in the stuffed buffer; trail: (last incomplete byte << 8) | its bit count
+struct JpegWritePlan {
+  const FrameDev* frames; const JpegScanDev* scans; const JpegHuffDev* tables; const int16_t* coef;
+  uint32_t num_scans, num_blocks, num_segs, pad;
+  uint32_t* bits;          // [num_blocks] pass 1
+  uint64_t* bitpos;        // [num_blocks + 1] exclusive scan of bits
+  uint32_t* seg_bits;      // [num_segs]
+  uint32_t* seg_bytes;     // [num_segs] = ceil(seg_bits / 8): every segment starts on a byte
+  uint64_t* seg_off;       // [num_segs + 1] exclusive scan of seg_bytes; the last entry is the size of the raw (unstuffed) buffer
+  uint64_t* tile_tmp;      // [ceil(max(num_blocks, num_segs) / 1024)] scratch of the scans
+  uint32_t* flags;         // per image: 1 DC category >= 12, 2 AC category >= 16, 4 symbol without a code (zeroed by the caller)
+};
+struct JpegPackBuffers {
+  uint8_t* raw; uint64_t raw_bytes;        // = seg_off[num_segs], read back by the host; allocated up to the next multiple of 4
+  uint32_t* ff_count; uint64_t* ff_before; // [chunks], [chunks + 1]: 0xFF bytes per JpegStuffChunkBytes() of raw, and their exclusive scan
+  uint64_t* tile_tmp;                      // [ceil(chunks / 1024)]
+  uint8_t* stuffed; uint64_t stuffed_cap;  // raw with 00 behind every FF: at most 2 x raw_bytes
+  JpegSegDev* recs;                        // [num_segs]
+};
+void LaunchJpegSizes(const JpegWritePlan& p, void* stream);
+void LaunchJpegPack(const JpegWritePlan& p, const JpegPackBuffers& o, void* stream);
+uint32_t JpegStuffChunkBytes();
 void LaunchCopyPlane(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t w, uint32_t h, void* stream);
 
 // names of the kernels (for profiling summaries)

@@ -259,6 +259,20 @@ JxlDecoderStatus JxlHipBatchSetOutput(JxlHipBatch* batch, int index, const JxlPi
  * message in JxlHipLastError().  A batch may mix scaled and unscaled images. */
 JxlDecoderStatus JxlHipBatchOutBufferSizeScaled(const JxlHipBatch* batch, int index, const JxlPixelFormat* format, int downscale, size_t* size);
 JxlDecoderStatus JxlHipBatchSetOutputScaled(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int downscale);
+/* ---- output layout: planar (CHW) planes and a per-channel scale and bias ---------------------------------------------------------
+ * A JxlPixelFormat describes interleaved samples.  JxlHipOutputLayout beside it puts every channel slot into a plane of its own and / or stores float samples as
+ * v x scale + bias, so that a consumer of [N, C, H, W] tensors, normalised per channel, needs no second pass over the decoded pixels.
+ *   planar        the sample of slot c at oriented position (ox, oy) goes to out + c * plane_stride + oy * row_stride + ox * bytes_per_sample.  Slots in the order of the
+ *                 interleaved samples: grey (or G) then alpha for 1 / 2 channels, R G B then alpha for 3 / 4.  row_stride = oriented width x sample size rounded up to
+ *                 format->align; the output is num_channels x plane_stride bytes.
+ *   plane_stride  0 = tight (oriented height x row_stride); else at least that and a multiple of the sample size, or the call fails with a message.
+ *   affine        float16 / float32 output only (an integer type fails: "affine output needs a float sample type"): slot c is stored as fmaf(v, scale[c], bias[c]) in
+ *                 float32, v being the sample a call without it stores; applies to interleaved and planar output alike.  affine = 0: scale / bias are not read.
+ * A NULL layout is the call without the suffix.  Orientation, keep_orientation, byte order, bit depth and downscale (1 or 8) keep their meaning.  Taken by batches and
+ * pipelines, device and pinned-host destinations, every image kind those decode.  The libjxl API above (JxlDecoder*), previews and animation canvases stay interleaved. */
+typedef struct { JXL_BOOL planar; size_t plane_stride; JXL_BOOL affine; float scale[4]; float bias[4]; } JxlHipOutputLayout;
+JxlDecoderStatus JxlHipBatchOutBufferSizeLayout(const JxlHipBatch* batch, int index, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, size_t* size);
+JxlDecoderStatus JxlHipBatchSetOutputLayout(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout);
 /* JPEG bit-stream reconstruction of a whole batch (jpegxl-rs decode.rs:493 `reconstruct`, for many files at once).  JxlHipBatchCanReconstructJpeg: 1 if image
  * `index` is a lossless JPEG transcode with usable reconstruction data (a `jbrd` box whose markers find their ICC / Exif / XMP payloads, a Huffman-coded source),
  * else 0 with the reason in JxlHipLastError().  JxlHipBatchReconstructJpegs runs the LF and HF entropy stages once for all images of the batch (it prepares the batch
@@ -349,6 +363,10 @@ int64_t JxlHipPipelineSubmit(JxlHipPipeline* pipeline, const uint8_t* const* dat
  * an image the 1:8 decode does not take fails alone. */
 int64_t JxlHipPipelineSubmitScaled(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
                                    void* const* host_out, const size_t* out_capacity, int downscale);
+/* The same with an output layout (JxlHipOutputLayout above; NULL = interleaved) and downscale 1 or 8: destinations of JxlHipImageOutSizeLayout bytes.  An image whose size
+ * does not fit layout->plane_stride fails alone. */
+int64_t JxlHipPipelineSubmitLayout(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
+                                   void* const* host_out, const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout);
 /* Waits until the job has left the GPU (pixels written, host copies done).  image_status[i] (n entries, optional): 0 decoded, 1 failed; *end_ms (optional): when the
  * job's last byte was written, ms after JxlHipPipelineResetClock.  JXL_DEC_SUCCESS if every image decoded, else JXL_DEC_ERROR (JxlHipLastError names the first).
  * A ticket can be waited for once; jobs complete in submission order. */
@@ -369,6 +387,9 @@ JxlDecoderStatus JxlHipImageOutSize(const uint8_t* data, size_t size, const JxlP
 /* The same for the 1:8 decode: `info` stays the full-size JxlBasicInfo, *out_size is that of the ceil(xsize / 8) x ceil(ysize / 8) picture; a prefix of the file that holds
  * the headers is enough. */
 JxlDecoderStatus JxlHipImageOutSizeScaled(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, JxlBasicInfo* info, size_t* out_size);
+/* The same for an output layout (JxlHipOutputLayout; NULL = interleaved) at downscale 1 or 8. */
+JxlDecoderStatus JxlHipImageOutSizeLayout(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, JxlBasicInfo* info,
+                                          size_t* out_size);
 /* Device arenas that batches and pipelines let go of are pooled per process (hipMalloc / hipFree of tens of GB cost seconds): JXL_HIP_ARENA_POOL_MB bounds the pool
  * (default 60 % of the device's memory, 0 = off); Trim hands every pooled block back to the runtime — for processes that share the GPU with another allocator —
  * and returns the bytes released; Held = bytes pooled right now. */

@@ -94,6 +94,11 @@ class JxlHipPipelineOptions(C.Structure):
                                          "small_job_frames", "timed", "reserve_frames", "reserve_width", "reserve_height", "reserve_plane_sets")]
 
 
+class JxlHipOutputLayout(C.Structure):
+    """include/jxl_hip.h JxlHipOutputLayout: planar (CHW) planes and / or a per-slot scale and bias for float output"""
+    _fields_ = [("planar", C.c_int), ("plane_stride", C.c_size_t), ("affine", C.c_int), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
 assert C.sizeof(JxlBasicInfo) == 204 and C.sizeof(JxlPixelFormat) == 24 and C.sizeof(JxlMemoryManager) == 24
 
 _lib = None
@@ -157,6 +162,11 @@ def libjxl():
             "JxlHipBatchSetOutputScaled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), vp, C.c_int]),
             "JxlHipPipelineSubmitScaled": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.c_int]),
             "JxlHipImageOutSizeScaled": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlBasicInfo), C.POINTER(sz)]),
+            "JxlHipBatchOutBufferSizeLayout": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(sz)]),
+            "JxlHipBatchSetOutputLayout": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), vp, C.c_int, C.POINTER(JxlHipOutputLayout)]),
+            "JxlHipPipelineSubmitLayout": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.c_int,
+                                                       C.POINTER(JxlHipOutputLayout)]),
+            "JxlHipImageOutSizeLayout": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlBasicInfo), C.POINTER(sz)]),
             "JxlHipBatchCanReconstructJpeg": (C.c_int, [vp, C.c_int]), "JxlHipBatchReconstructJpegs": (C.c_int, [vp, vp]),
             "JxlHipBatchJpegStatus": (C.c_int, [vp, C.c_int]), "JxlHipBatchJpegSize": (sz, [vp, C.c_int]), "JxlHipBatchCopyJpeg": (C.c_int, [vp, C.c_int, vp, sz]),
             "JxlHipBatchSetLaneStride": (None, [vp, C.c_int, C.c_int]), "JxlHipBatchSetOption": (None, [vp, C.c_char_p, C.c_int]),
@@ -588,6 +598,23 @@ def decoder_builder(**options) -> JxlDecoder:
     return JxlDecoder(**options)
 
 
+def _layout(planar, plane_stride, scale, bias):
+    """-> JxlHipOutputLayout, or None for interleaved samples without scale / bias (the calls without a layout).  scale / bias: up to four values, one per channel
+    slot (missing ones 1 / 0); giving either asks for affine output."""
+    if not planar and scale is None and bias is None:
+        if plane_stride:
+            raise ValueError("plane_stride needs planar=True")
+        return None
+    lay = JxlHipOutputLayout(1 if planar else 0, int(plane_stride), 0 if scale is None and bias is None else 1)
+    for dst, src, default in ((lay.scale, scale, 1.0), (lay.bias, bias, 0.0)):
+        vals = [] if src is None else [float(v) for v in np.atleast_1d(src)]
+        if len(vals) > 4:
+            raise ValueError("scale / bias take at most four values, one per channel slot")
+        for c in range(4):
+            dst[c] = vals[c] if c < len(vals) else default
+    return lay
+
+
 # ---- batch extension (include/jxl_hip.h, JxlHipBatch*) -------------------------------------------------------------------
 class BatchDecoder:
     """Device-resident decode of a batch of independent images: inputs and outputs stay in HBM."""
@@ -600,6 +627,7 @@ class BatchDecoder:
         self._n = 0
         self._fmt = []
         self._scale = []
+        self._layouts = []
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -610,18 +638,25 @@ class BatchDecoder:
         if status != JXL_DEC_SUCCESS:
             raise GenericError(last_error())
 
-    def _set_output(self, i, fmt, device_ptr, downscale):
+    def _set_output(self, i, fmt, device_ptr, downscale, layout=None):
         L = libjxl()
-        if downscale == 1:
+        if layout is not None:
+            self._chk(L.JxlHipBatchSetOutputLayout(self._h, i, C.byref(fmt), device_ptr, int(downscale), C.byref(layout)))
+        elif downscale == 1:
             self._chk(L.JxlHipBatchSetOutput(self._h, i, C.byref(fmt), device_ptr))
         else:
             self._chk(L.JxlHipBatchSetOutputScaled(self._h, i, C.byref(fmt), device_ptr, int(downscale)))
         self._fmt.append(fmt)
         self._scale.append(int(downscale))
+        self._layouts.append(layout)
 
-    def add(self, data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, device_ptr=None, downscale=1) -> int:
+    def add(self, data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, device_ptr=None, downscale=1,
+            planar=False, plane_stride=0, scale=None, bias=None) -> int:
         """downscale=8: the 1:8 decode (include/jxl_hip.h JxlHipBatchSetOutputScaled) — output(i) is the ceil(w / 8) x ceil(h / 8) picture; `data` may end behind
-        the LF part of its frame."""
+        the LF part of its frame.
+        planar=True: one plane per channel, [C, H, W] with rows `align`ed and planes plane_stride bytes apart (0 = tight); scale / bias (up to four values, one per
+        channel slot, float16 / float32 output): samples are stored as v * scale[c] + bias[c] (include/jxl_hip.h JxlHipOutputLayout)."""
+        layout = _layout(planar, plane_stride, scale, bias)
         L = libjxl()
         buf = np.frombuffer(data, dtype=np.uint8)
         if downscale != 1:
@@ -634,14 +669,16 @@ class BatchDecoder:
         if i < 0:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
-        self._set_output(i, fmt, device_ptr, downscale)
+        self._set_output(i, fmt, device_ptr, downscale, layout)
         self._n += 1
         return i
 
-    def add_many(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, threads=4, endianness=Endianness.Native, align=0, downscale=1) -> int:
+    def add_many(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, threads=4, endianness=Endianness.Native, align=0, downscale=1,
+                 planar=False, plane_stride=0, scale=None, bias=None) -> int:
         """Parses the images of `datas` (bytes objects) on `threads` host threads and appends them in order (JxlHipBatchAddImages);
-        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale: as for add()."""
+        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale, planar, plane_stride, scale, bias: as for add()."""
         L = libjxl()
+        layout = _layout(planar, plane_stride, scale, bias)
         n = len(datas)
         ptrs = (C.c_char_p * n)(*datas)
         sizes = (C.c_size_t * n)(*[len(d) for d in datas])
@@ -656,7 +693,7 @@ class BatchDecoder:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
         for k in range(n):
-            self._set_output(first + k, fmt, device_ptrs[k] if device_ptrs is not None else None, downscale)
+            self._set_output(first + k, fmt, device_ptrs[k] if device_ptrs is not None else None, downscale, layout)
         self._n += n
         return first
 
@@ -666,6 +703,7 @@ class BatchDecoder:
         self._n = 0
         self._fmt = []
         self._scale = []
+        self._layouts = []
 
     def info(self, i) -> JxlBasicInfo:
         info = JxlBasicInfo()
@@ -674,7 +712,9 @@ class BatchDecoder:
 
     def out_size(self, i) -> int:
         s = C.c_size_t()
-        if self._scale[i] == 1:
+        if self._layouts[i] is not None:
+            self._chk(libjxl().JxlHipBatchOutBufferSizeLayout(self._h, i, C.byref(self._fmt[i]), self._scale[i], C.byref(self._layouts[i]), C.byref(s)))
+        elif self._scale[i] == 1:
             self._chk(libjxl().JxlHipBatchOutBufferSize(self._h, i, C.byref(self._fmt[i]), C.byref(s)))
         else:
             self._chk(libjxl().JxlHipBatchOutBufferSizeScaled(self._h, i, C.byref(self._fmt[i]), self._scale[i], C.byref(s)))
@@ -786,13 +826,18 @@ def arena_pool_trim() -> int:
     return int(libjxl().JxlHipArenaPoolTrim())
 
 
-def image_out_size(data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, downscale=1):
+def image_out_size(data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, downscale=1, planar=False, plane_stride=0, scale=None, bias=None):
     """(JxlBasicInfo, bytes of the decoded image in that format) from the headers alone — host-only (JxlHipImageOutSize).
-    downscale=8: the size of the 1:8 decode (JxlHipImageOutSizeScaled); the info stays that of the full-size image."""
+    downscale=8: the size of the 1:8 decode (JxlHipImageOutSizeScaled); the info stays that of the full-size image.
+    planar, plane_stride, scale, bias: the layout as for BatchDecoder.add (JxlHipImageOutSizeLayout); a layout the image or the sample type does not take raises."""
     fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
     info, size = JxlBasicInfo(), C.c_size_t()
     buf = np.frombuffer(data, dtype=np.uint8)
-    if downscale == 1:
+    layout = _layout(planar, plane_stride, scale, bias)
+    if layout is not None:
+        if libjxl().JxlHipImageOutSizeLayout(buf.ctypes.data, len(data), C.byref(fmt), int(downscale), C.byref(layout), C.byref(info), C.byref(size)) != JXL_DEC_SUCCESS:
+            raise GenericError(last_error())
+    elif downscale == 1:
         check_dec_status(libjxl().JxlHipImageOutSize(buf.ctypes.data, len(data), C.byref(fmt), C.byref(info), C.byref(size)))
     elif libjxl().JxlHipImageOutSizeScaled(buf.ctypes.data, len(data), C.byref(fmt), int(downscale), C.byref(info), C.byref(size)) != JXL_DEC_SUCCESS:
         raise GenericError(last_error())
@@ -845,9 +890,12 @@ class Pipeline:
 
     __del__ = close
 
-    def submit(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, host_ptrs=None, capacities=None, endianness=Endianness.Native, align=0, downscale=1) -> int:
+    def submit(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, host_ptrs=None, capacities=None, endianness=Endianness.Native, align=0, downscale=1,
+               planar=False, plane_stride=0, scale=None, bias=None) -> int:
         """Job of len(datas) images (bytes objects).  device_ptrs / host_ptrs: one destination address per image (exactly one of the two lists); the bytes objects and
-        the destinations are kept referenced until wait().  downscale=8: the job is decoded at 1:8 (JxlHipPipelineSubmitScaled)."""
+        the destinations are kept referenced until wait().  downscale=8: the job is decoded at 1:8 (JxlHipPipelineSubmitScaled).  planar, plane_stride, scale, bias:
+        the layout of every image of the job, as for BatchDecoder.add (JxlHipPipelineSubmitLayout)."""
+        layout = _layout(planar, plane_stride, scale, bias)
         n = len(datas)
         ptrs = (C.c_char_p * n)(*datas)
         sizes = (C.c_size_t * n)(*[len(d) for d in datas])
@@ -855,7 +903,9 @@ class Pipeline:
         dev = (C.c_void_p * n)(*device_ptrs) if device_ptrs is not None else None
         host = (C.c_void_p * n)(*host_ptrs) if host_ptrs is not None else None
         caps = (C.c_size_t * n)(*capacities) if capacities is not None else None
-        if downscale == 1:
+        if layout is not None:
+            t = libjxl().JxlHipPipelineSubmitLayout(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), C.byref(layout))
+        elif downscale == 1:
             t = libjxl().JxlHipPipelineSubmit(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps)
         else:
             t = libjxl().JxlHipPipelineSubmitScaled(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale))

@@ -749,7 +749,7 @@ size_t Batch::OutputStride(const ImageHeader& ih, const OutputSpec& o, uint32_t*
   if (nc == 0) nc = (ih.color_space == 1 ? 1 : 3) + (alpha ? 1 : 0);
   if (channels) *channels = nc;
   const size_t bps = o.type == 0 ? 1 : o.type == 2 ? 4 : 2;
-  size_t stride = (size_t)OrientedWidth(ih, o) * nc * bps;
+  size_t stride = (size_t)OrientedWidth(ih, o) * (o.planar ? 1 : nc) * bps;      // (planar: the row of one plane)
   if (o.align > 1) stride = (stride + o.align - 1) / o.align * o.align;
   return stride;
 }
@@ -763,7 +763,20 @@ size_t Batch::OutputSize(const ImageHeader& ih, const OutputSpec& o) {
   uint32_t nc;
   const size_t stride = OutputStride(ih, o, &nc);
   const size_t bps = o.type == 0 ? 1 : o.type == 2 ? 4 : 2;
+  const std::string why = LayoutRefusal(ih, o);
+  if (!why.empty()) throw ParseError(why, false);
+  if (o.planar) return (size_t)nc * (o.plane_stride ? o.plane_stride : stride * OrientedHeight(ih, o));
   return stride * (OrientedHeight(ih, o) - 1) + (size_t)OrientedWidth(ih, o) * nc * bps;
+}
+std::string Batch::LayoutRefusal(const ImageHeader& ih, const OutputSpec& o) {
+  if (o.affine && o.type != 2 && o.type != 3) return "affine output needs a float sample type";
+  if (o.planar && o.plane_stride) {
+    const size_t bps = o.type == 0 ? 1 : o.type == 2 ? 4 : 2;
+    const size_t tight = OutputStride(ih, o, nullptr) * OrientedHeight(ih, o);
+    if (o.plane_stride < tight) return "planar output: plane_stride " + std::to_string(o.plane_stride) + " is below the " + std::to_string(tight) + " bytes one plane of this image takes";
+    if (o.plane_stride % bps) return "planar output: plane_stride must be a multiple of the sample size";
+  }
+  return std::string();
 }
 void Batch::OutputDims(int i, const OutputSpec& o, uint32_t* w, uint32_t* h) const {
   const ImageEntry& first = *images_[pub_[i].first_unit];
@@ -778,8 +791,11 @@ size_t Batch::OutputSizeOf(int i, const OutputSpec& o) const {
 static float IntMul(const OutputSpec& o) { const uint32_t full = o.type == 0 ? 8 : 16; const uint32_t b = o.int_bits && o.int_bits < full ? o.int_bits : full; return (float)((1u << b) - 1); }
 // Where the write stage puts the image's pixels (work: the arena that holds the output unless the caller named a device buffer)
 static OutputDesc FillOutput(const ImageEntry& e, uint8_t* work) {
-  OutputDesc d;
+  OutputDesc d{};
   d.out = (uint8_t*)(e.out.device_ptr ? e.out.device_ptr : work + e.off_out);
+  d.planar = e.out.planar; d.plane_stride = !e.out.planar ? 0 : e.out.plane_stride ? e.out.plane_stride : e.out_size / std::max(1u, e.out.num_channels);
+  d.affine = e.out.affine;
+  for (int c = 0; c < 4; c++) { d.scale[c] = e.out.scale[c]; d.bias[c] = e.out.bias[c]; }
   d.out_stride = e.out_stride; d.out_channels = e.out.num_channels; d.out_type = e.out.type; d.out_big_endian = e.out.big_endian; d.out_int_mul = IntMul(e.out);
   d.out_orient = e.out.keep_orientation ? 1 : e.ih.orientation; d.is_gray = e.ih.color_space == 1;
   return d;
@@ -821,6 +837,7 @@ void Batch::SetOutput(int i, const OutputSpec& o) {
 }
 void Batch::SetOutputAllFrames(int i, const OutputSpec& o, const vec<int>& frames) {
   if (o.device_ptr || o.only_frame >= 0 || frames.empty()) throw ParseError("SetOutputAllFrames: internal output buffers, coalesced frames only", false);
+  if (o.planar || o.affine) throw ParseError("SetOutputAllFrames: interleaved output without scale / bias only", false);
   for (size_t k = 0; k < frames.size(); k++)
     if (frames[k] < 0 || frames[k] >= pub_[i].num_units || (k && frames[k] <= frames[k - 1])) throw ParseError("SetOutputAllFrames: frame list must be ascending positions among the image's frames", false);
   OutputSpec oo = o;

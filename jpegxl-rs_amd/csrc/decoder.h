@@ -30,6 +30,12 @@ struct OutputSpec {
   uint32_t downscale = 1;         // 1, or 8: the 1:8 decode — the output is the frame's LF image, ceil(w / 8) x ceil(h / 8) pixels, one per 8x8 block, through the colour transform and the
                                   // write stage (LfOutputKernel); no AC coefficient is decoded, no IDCT, no restoration filter runs.  Single-frame VarDCT images without extra
                                   // channels, patches, splines, noise or upsampling (Batch::DownscaleRefusal)
+  // ---- layout (Batch and Pipeline outputs; the libjxl look-alike API, previews and kept animation canvases are interleaved)
+  bool planar = false;            // channel slot c (grey or G, alpha / R, G, B, alpha) is a plane of its own at c x plane_stride: rows of one sample per pixel, oriented width x sample size
+                                  // rounded up to `align` apart; the output is num_channels x plane_stride bytes
+  size_t plane_stride = 0;        // 0 = tight (oriented height x row stride), else at least that and a multiple of the sample size
+  bool affine = false;            // float16 / float32 output: slot c is stored as fmaf(v, scale[c], bias[c])
+  float scale[4] = {1.0f, 1.0f, 1.0f, 1.0f}, bias[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 };
 
 // What the frames of one image share: the codestream and the image header.
@@ -112,6 +118,8 @@ class Batch {
   static uint32_t OrientedWidth(const ImageHeader& ih, const OutputSpec& o);
   static uint32_t OrientedHeight(const ImageHeader& ih, const OutputSpec& o);
   static size_t OutputSize(const ImageHeader& ih, const OutputSpec& o);
+  // "" when the layout of `o` (planar, plane_stride, affine) can be written for an image of ih's size, else the reason; OutputSize and SetOutput throw it
+  static std::string LayoutRefusal(const ImageHeader& ih, const OutputSpec& o);
   // size of the rectangle output `o` of image i covers: the image, or — non-coalesced output — frame o.only_frame as coded (before orientation)
   void OutputDims(int i, const OutputSpec& o, uint32_t* w, uint32_t* h) const;
   size_t OutputSizeOf(int i, const OutputSpec& o) const;

@@ -912,45 +912,52 @@ JxlDecoderStatus JxlHipBatchGetBasicInfo(const JxlHipBatch* h, int i, JxlBasicIn
   FillBasicInfo(h->b->image(i).ih, info, h->keep_orientation);
   return JXL_DEC_SUCCESS;
 }
-JxlDecoderStatus JxlHipBatchOutBufferSize(const JxlHipBatch* h, int i, const JxlPixelFormat* format, size_t* size) {
-  OutputSpec o;
-  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o)) return JXL_DEC_ERROR;
-  o.keep_orientation = h->keep_orientation;
-  *size = Batch::OutputSize(h->b->image(i).ih, o);
-  return JXL_DEC_SUCCESS;
-}
-JxlDecoderStatus JxlHipBatchSetOutput(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer) {
-  OutputSpec o;
-  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o)) return JXL_DEC_ERROR;
-  o.device_ptr = device_buffer;
-  o.keep_orientation = h->keep_orientation;
-  h->b->SetOutput(i, o);
-  return JXL_DEC_SUCCESS;
-}
 static bool DownscaleOk(int downscale, const char* who) {
   if (downscale == 1 || downscale == 8) return true;
   SetLastError(std::string(who) + ": downscale must be 1 or 8");
   return false;
 }
-JxlDecoderStatus JxlHipBatchOutBufferSizeScaled(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, size_t* size) {
-  if (!DownscaleOk(downscale, "JxlHipBatchOutBufferSizeScaled")) return JXL_DEC_ERROR;
-  if (downscale == 1) return JxlHipBatchOutBufferSize(h, i, format, size);
-  OutputSpec o;
-  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o)) return JXL_DEC_ERROR;
-  o.keep_orientation = h->keep_orientation;
-  o.downscale = 8;
-  *size = Batch::OutputSize(h->b->image(i).ih, o);
-  return JXL_DEC_SUCCESS;
+// JxlHipOutputLayout -> OutputSpec (NULL: interleaved samples as they are); what depends on the image's size is checked where the size is known (Batch::LayoutRefusal)
+static bool ApplyLayout(const JxlHipOutputLayout* l, OutputSpec* o, const char* who) {
+  if (!l) return true;
+  o->planar = l->planar != 0; o->plane_stride = o->planar ? l->plane_stride : 0;
+  o->affine = l->affine != 0;
+  if (o->affine) {
+    if (o->type != 2 && o->type != 3) { SetLastError(std::string(who) + ": affine output needs a float sample type"); return false; }
+    for (int c = 0; c < 4; c++) { o->scale[c] = l->scale[c]; o->bias[c] = l->bias[c]; }
+  }
+  return true;
 }
-JxlDecoderStatus JxlHipBatchSetOutputScaled(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale) {
-  if (!DownscaleOk(downscale, "JxlHipBatchSetOutputScaled")) return JXL_DEC_ERROR;
-  if (downscale == 1) return JxlHipBatchSetOutput(h, i, format, device_buffer);
+static JxlDecoderStatus BatchOutBufferSize(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, size_t* size, const char* who) {
+  if (!DownscaleOk(downscale, who)) return JXL_DEC_ERROR;
   OutputSpec o;
-  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o)) return JXL_DEC_ERROR;
+  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o) || !ApplyLayout(layout, &o, who)) return JXL_DEC_ERROR;
+  o.keep_orientation = h->keep_orientation;
+  o.downscale = (uint32_t)downscale;
+  try { *size = Batch::OutputSize(h->b->image(i).ih, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
+}
+static JxlDecoderStatus BatchSetOutput(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout, const char* who) {
+  if (!DownscaleOk(downscale, who)) return JXL_DEC_ERROR;
+  OutputSpec o;
+  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o) || !ApplyLayout(layout, &o, who)) return JXL_DEC_ERROR;
   o.device_ptr = device_buffer;
   o.keep_orientation = h->keep_orientation;
-  o.downscale = 8;
-  try { h->b->SetOutput(i, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }   // ("unsupported: downscaled decode of ...")
+  o.downscale = (uint32_t)downscale;
+  try { h->b->SetOutput(i, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }   // ("unsupported: downscaled decode of ...", a plane_stride that does not fit)
+}
+JxlDecoderStatus JxlHipBatchOutBufferSize(const JxlHipBatch* h, int i, const JxlPixelFormat* format, size_t* size) { return BatchOutBufferSize(h, i, format, 1, nullptr, size, "JxlHipBatchOutBufferSize"); }
+JxlDecoderStatus JxlHipBatchSetOutput(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer) { return BatchSetOutput(h, i, format, device_buffer, 1, nullptr, "JxlHipBatchSetOutput"); }
+JxlDecoderStatus JxlHipBatchOutBufferSizeScaled(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, size_t* size) {
+  return BatchOutBufferSize(h, i, format, downscale, nullptr, size, "JxlHipBatchOutBufferSizeScaled");
+}
+JxlDecoderStatus JxlHipBatchSetOutputScaled(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale) {
+  return BatchSetOutput(h, i, format, device_buffer, downscale, nullptr, "JxlHipBatchSetOutputScaled");
+}
+JxlDecoderStatus JxlHipBatchOutBufferSizeLayout(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, size_t* size) {
+  return BatchOutBufferSize(h, i, format, downscale, layout, size, "JxlHipBatchOutBufferSizeLayout");
+}
+JxlDecoderStatus JxlHipBatchSetOutputLayout(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout) {
+  return BatchSetOutput(h, i, format, device_buffer, downscale, layout, "JxlHipBatchSetOutputLayout");
 }
 void JxlHipBatchSetLaneStride(JxlHipBatch* h, int lf, int hf) {
   auto ok = [](int v) { return v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64; };
@@ -1058,24 +1065,28 @@ JxlHipPipeline* JxlHipPipelineCreate(int device, const JxlHipPipelineOptions* o)
   } catch (const std::exception& e) { SetLastError(e.what()); return nullptr; }
 }
 void JxlHipPipelineDestroy(JxlHipPipeline* h) { if (h) { delete h->p; delete h; } }
-int64_t JxlHipPipelineSubmit(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
-                             const size_t* out_capacity) {
+static int64_t PipelineSubmit(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                              const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const char* who) {
+  if (!DownscaleOk(downscale, who)) return -1;
   try {
     OutputSpec o;
-    if (!h || !FormatToSpec(format, &o)) { SetLastError("JxlHipPipelineSubmit: bad pixel format"); return -1; }
+    if (!h || !FormatToSpec(format, &o)) { SetLastError(std::string(who) + ": bad pixel format"); return -1; }
+    if (!ApplyLayout(layout, &o, who)) return -1;
+    o.downscale = (uint32_t)downscale;
     return h->p->Submit(datas, sizes, n, o, device_out, host_out, out_capacity);
   } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
 }
+int64_t JxlHipPipelineSubmit(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                             const size_t* out_capacity) {
+  return PipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity, 1, nullptr, "JxlHipPipelineSubmit");
+}
 int64_t JxlHipPipelineSubmitScaled(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
                                    const size_t* out_capacity, int downscale) {
-  if (!DownscaleOk(downscale, "JxlHipPipelineSubmitScaled")) return -1;
-  if (downscale == 1) return JxlHipPipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity);
-  try {
-    OutputSpec o;
-    if (!h || !FormatToSpec(format, &o)) { SetLastError("JxlHipPipelineSubmitScaled: bad pixel format"); return -1; }
-    o.downscale = 8;
-    return h->p->Submit(datas, sizes, n, o, device_out, host_out, out_capacity);
-  } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
+  return PipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity, downscale, nullptr, "JxlHipPipelineSubmitScaled");
+}
+int64_t JxlHipPipelineSubmitLayout(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                                   const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout) {
+  return PipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity, downscale, layout, "JxlHipPipelineSubmitLayout");
 }
 JxlDecoderStatus JxlHipPipelineWait(JxlHipPipeline* h, int64_t ticket, int* image_status, int n, float* end_ms) {
   try {
@@ -1116,13 +1127,17 @@ size_t JxlHipArenaPoolTrim(void) { return DeviceArenaPoolTrim(); }
 size_t JxlHipArenaPoolHeld(void) { return DeviceArenaPoolHeld(); }
 void JxlHipSchedulerStats(int device, int64_t* jobs, int64_t* images) { SchedulerStats(device, jobs, images); }
 void JxlHipSchedulerShutdown(void) { SchedulerShutdown(); }
-JxlDecoderStatus JxlHipImageOutSize(const uint8_t* data, size_t size, const JxlPixelFormat* format, JxlBasicInfo* info, size_t* out_size) {
+static JxlDecoderStatus ImageOutSize(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, JxlBasicInfo* info, size_t* out_size, const char* who) {
+  if (!DownscaleOk(downscale, who)) return JXL_DEC_ERROR;
   try {
     OutputSpec o;
     if (!FormatToSpec(format, &o)) { SetLastError("bad pixel format"); return JXL_DEC_ERROR; }
+    if (!ApplyLayout(layout, &o, who)) return JXL_DEC_ERROR;
+    o.downscale = (uint32_t)downscale;
     std::shared_ptr<ImageShared> sh(new ImageShared());
     bool have_container = false, has_jbrd = false;
-    if (!ExtractCodestream(data, size, &sh->cs, &have_container, &has_jbrd, nullptr)) return JXL_DEC_NEED_MORE_INPUT;
+    // (1:8: a prefix of the file will do — the headers say the size)
+    if (!ExtractCodestream(data, size, &sh->cs, &have_container, &has_jbrd, nullptr) && downscale == 1) return JXL_DEC_NEED_MORE_INPUT;
     uint64_t bitpos = 0;
     ParseImageHeader(sh->cs, &sh->ih, &bitpos);
     sh->ih.have_container = have_container;
@@ -1131,24 +1146,14 @@ JxlDecoderStatus JxlHipImageOutSize(const uint8_t* data, size_t size, const JxlP
     return JXL_DEC_SUCCESS;
   } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
 }
-
+JxlDecoderStatus JxlHipImageOutSize(const uint8_t* data, size_t size, const JxlPixelFormat* format, JxlBasicInfo* info, size_t* out_size) {
+  return ImageOutSize(data, size, format, 1, nullptr, info, out_size, "JxlHipImageOutSize");
+}
 JxlDecoderStatus JxlHipImageOutSizeScaled(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, JxlBasicInfo* info, size_t* out_size) {
-  if (!DownscaleOk(downscale, "JxlHipImageOutSizeScaled")) return JXL_DEC_ERROR;
-  if (downscale == 1) return JxlHipImageOutSize(data, size, format, info, out_size);
-  try {
-    OutputSpec o;
-    if (!FormatToSpec(format, &o)) { SetLastError("bad pixel format"); return JXL_DEC_ERROR; }
-    o.downscale = 8;
-    std::shared_ptr<ImageShared> sh(new ImageShared());
-    bool have_container = false, has_jbrd = false;
-    (void)ExtractCodestream(data, size, &sh->cs, &have_container, &has_jbrd, nullptr);     // (a prefix of the file will do: the headers say the size)
-    uint64_t bitpos = 0;
-    ParseImageHeader(sh->cs, &sh->ih, &bitpos);
-    sh->ih.have_container = have_container;
-    if (info) FillBasicInfo(sh->ih, info, false);
-    if (out_size) *out_size = Batch::OutputSize(sh->ih, o);
-    return JXL_DEC_SUCCESS;
-  } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
+  return ImageOutSize(data, size, format, downscale, nullptr, info, out_size, "JxlHipImageOutSizeScaled");
+}
+JxlDecoderStatus JxlHipImageOutSizeLayout(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, JxlBasicInfo* info, size_t* out_size) {
+  return ImageOutSize(data, size, format, downscale, layout, info, out_size, "JxlHipImageOutSizeLayout");
 }
 
 // the pipelines keep ~15 HIP streams busy at once; the runtime maps streams onto 4 hardware queues by default and kernels of streams that share a queue serialise.

@@ -29,6 +29,11 @@ struct OutputDesc {
   float out_int_mul;              // integer output: sample = round(clamp(v, 0, 1) x this) — 255 / 65535, or 2^bits - 1 (JxlDecoderSetImageOutBitDepth)
   uint32_t out_orient;            // 1..8: orientation applied while writing (1 = none)
   uint32_t is_gray;               // grey image: one- and two-channel output takes R (= G = B), of a colour image G
+  // OutputSpec's layout: planar = channel slot c (grey or G, alpha / R, G, B, alpha) is a plane of its own at out + c x plane_stride, out_stride the row pitch of one plane;
+  // affine = float samples are stored as fmaf(v, scale[c], bias[c]).  Both 0: interleaved samples as they are, no multiply anywhere.
+  uint32_t planar, affine;
+  uint64_t plane_stride;          // bytes from one plane to the next (planar)
+  float scale[4], bias[4];        // per slot (affine)
 };
 
 struct FrameDev {

@@ -5298,8 +5298,10 @@ __global__ __launch_bounds__(256) void FusedGabEpf1OutKernel(const FrameDev* __r
   __syncthreads();
   // ---- EPF pass 1 + colour + store
 #ifndef JXL_NO_PACKED_STORE
-  // 1: u8 RGB, 2: u8 RGBA written as dwords (rows and buffer 4-byte aligned, width a multiple of 4 so that a quad of lanes is inside the image or outside it)
-  const int packed = (f.od.out_type == 0 && f.od.out_orient <= 1 && (w & 3) == 0 && ((uintptr_t)f.od.out & 3) == 0 && (f.od.out_stride & 3) == 0 && f.img_w == f.width && f.img_h == f.height)
+  // 1: u8 RGB, 2: u8 RGBA written as dwords (rows and buffer 4-byte aligned, width a multiple of 4 so that a quad of lanes is inside the image or outside it; planar output:
+  // the planes 4-byte aligned as well).  Affine output is float output and goes through StorePixel.
+  const int packed = (f.od.out_type == 0 && !f.od.affine && f.od.out_orient <= 1 && (w & 3) == 0 && ((uintptr_t)f.od.out & 3) == 0 && (f.od.out_stride & 3) == 0 && f.img_w == f.width && f.img_h == f.height &&
+                      (!f.od.planar || (f.od.plane_stride & 3) == 0))
                          ? (f.od.out_channels == 3 ? 1 : f.od.out_channels == 4 ? 2 : 0) : 0;
 #endif
   const float sm = f.epf_sm[1], bsm = f.epf_bsm[1];
@@ -5367,7 +5369,22 @@ __global__ __launch_bounds__(256) void FusedGabEpf1OutKernel(const FrameDev* __r
       const uint32_t pb = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, b)) * f.od.out_int_mul) & 0xFFu;
       const uint32_t p = pr | (pg << 8) | (pb << 16);
       uint8_t* const row = f.od.out + (size_t)y * f.od.out_stride;
-      if (packed == 2) {
+      if (f.od.planar) {
+        // one dword per plane and quad: the quad's four pixels r | g << 8 | b << 16 | a << 24 are a 4 x 4 byte matrix, lane j gathers column j — byte j of every pixel
+        // (DPP quad_perm broadcasts of lanes 0..3) — and stores it to plane j at the quad's first x.  Lane 3 has the alpha plane, or nothing to store.
+        uint32_t q = p;
+        if (packed == 2) {
+          const float a = f.alpha_plane ? (float)f.alpha_plane[(size_t)y * f.width + x] * f.alpha_factor : 1.0f;
+          q |= ((uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, a)) * f.od.out_int_mul) & 0xFFu) << 24;
+        }
+        const uint32_t q0 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q, 0x00, 0xF, 0xF, false);
+        const uint32_t q1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q, 0x55, 0xF, 0xF, false);
+        const uint32_t q2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q, 0xAA, 0xF, 0xF, false);
+        const uint32_t q3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q, 0xFF, 0xF, 0xF, false);
+        const uint32_t j = (uint32_t)lx & 3u, sh = 8u * j;
+        const uint32_t d = ((q0 >> sh) & 0xFFu) | (((q1 >> sh) & 0xFFu) << 8) | (((q2 >> sh) & 0xFFu) << 16) | (((q3 >> sh) & 0xFFu) << 24);
+        if (j < f.od.out_channels) StoreOut32(reinterpret_cast<uint32_t*>(row + (size_t)j * f.od.plane_stride + (size_t)(x - (int)j)), d);
+      } else if (packed == 2) {
         const float a = f.alpha_plane ? (float)f.alpha_plane[(size_t)y * f.width + x] * f.alpha_factor : 1.0f;
         const uint32_t pa = (uint32_t)__float2int_rn(fminf(1.0f, fmaxf(0.0f, a)) * f.od.out_int_mul) & 0xFFu;
         StoreOut32(reinterpret_cast<uint32_t*>(row + 4 * (size_t)x), p | (pa << 24));

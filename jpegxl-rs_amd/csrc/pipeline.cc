@@ -250,8 +250,15 @@ void Pipeline::PrepareJob(Job* j, int worker) {
       if (index[(size_t)i] < 0) { j->result.error[(size_t)i] = errors[(size_t)i]; continue; }
       OutputSpec o = j->spec;
       o.device_ptr = j->device_out.empty() ? nullptr : j->device_out[(size_t)i];
-      const size_t need = bt.OutputSizeOf(index[(size_t)i], o);
-      if (!j->capacity.empty() && j->capacity[(size_t)i] < need) {
+      size_t need = 0;
+      std::string refusal;
+      try { need = bt.OutputSizeOf(index[(size_t)i], o); } catch (const ParseError& e) { refusal = e.what(); }     // (a plane_stride this image does not fit: Batch::LayoutRefusal)
+      if (!refusal.empty()) {
+        // (stays in the batch like an image whose buffer is too small, with a tight plane of its own)
+        j->result.error[(size_t)i] = refusal;
+        o.device_ptr = nullptr; o.plane_stride = 0;
+        j->batch_index[(size_t)i] = -2 - index[(size_t)i];
+      } else if (!j->capacity.empty() && j->capacity[(size_t)i] < need) {
         // (the image stays in the batch — taking it out would renumber the others — and decodes into a buffer of the batch's own; it is reported as failed)
         j->result.error[(size_t)i] = "output buffer too small for this image";
         o.device_ptr = nullptr;

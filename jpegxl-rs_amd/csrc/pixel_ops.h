@@ -132,7 +132,8 @@ __device__ __forceinline__ void StoreSample(const OutputDesc& o, uint8_t* p, flo
 
 // Position of sample (x, y) of the w x h image in the output buffer: the header's orientation (1..8, EXIF numbering as in
 // codestream_header.rs JxlOrientation) is applied by the write stage — 2 flip-h, 3 rotate 180, 4 flip-v, 5 transpose,
-// 6 rotate 90 cw, 7 anti-transpose, 8 rotate 90 ccw; out_stride already refers to the oriented width.
+// 6 rotate 90 cw, 7 anti-transpose, 8 rotate 90 ccw; out_stride already refers to the oriented width.  Interleaved: the pixel's first sample;
+// planar: its sample in plane 0, a row holding one sample per pixel.
 __device__ __forceinline__ uint8_t* OutPixelPtr(const OutputDesc& o, int w, int h, int x, int y, uint32_t bps) {
   int ox = x, oy = y;
   switch (o.out_orient) {
@@ -145,20 +146,24 @@ __device__ __forceinline__ uint8_t* OutPixelPtr(const OutputDesc& o, int w, int 
     case 8: ox = y; oy = w - 1 - x; break;
     default: break;
   }
-  return o.out + (size_t)oy * o.out_stride + (size_t)ox * o.out_channels * bps;
+  return o.out + (size_t)oy * o.out_stride + (size_t)ox * (o.planar ? bps : o.out_channels * bps);
 }
 
-// pixel (x, y) of the w x h image -> 1, 2, 3 or 4 interleaved samples
+// the sample of channel slot c as it is stored: untouched, or (float output, OutputSpec::affine) v x scale[c] + bias[c] in one rounding
+__device__ __forceinline__ float SlotValue(const OutputDesc& o, int c, float v) { return o.affine ? fmaf(v, o.scale[c], o.bias[c]) : v; }
+
+// pixel (x, y) of the w x h image -> 1, 2, 3 or 4 samples, interleaved or one per plane (o.planar and o.affine are the same for the whole launch's image: uniform branches)
 __device__ __forceinline__ void StorePixel(const OutputDesc& o, int w, int h, int x, int y, float r, float g, float b, float a) {
   const uint32_t bps = o.out_type == 0 ? 1 : o.out_type == 2 ? 4 : 2;
   uint8_t* p = OutPixelPtr(o, w, h, x, y, bps);
   const uint32_t nc = o.out_channels;
+  const size_t step = o.planar ? (size_t)o.plane_stride : (size_t)bps;   // from one slot's sample to the next one's
   if (nc <= 2) {
-    StoreSample(o, p, o.is_gray ? r : g);  // gray images carry the same value in all channels; otherwise take G
-    if (nc == 2) StoreSample(o, p + bps, a);
+    StoreSample(o, p, SlotValue(o, 0, o.is_gray ? r : g));  // gray images carry the same value in all channels; otherwise take G
+    if (nc == 2) StoreSample(o, p + step, SlotValue(o, 1, a));
   } else {
-    StoreSample(o, p, r); StoreSample(o, p + bps, g); StoreSample(o, p + 2 * bps, b);
-    if (nc == 4) StoreSample(o, p + 3 * bps, a);
+    StoreSample(o, p, SlotValue(o, 0, r)); StoreSample(o, p + step, SlotValue(o, 1, g)); StoreSample(o, p + 2 * step, SlotValue(o, 2, b));
+    if (nc == 4) StoreSample(o, p + 3 * step, SlotValue(o, 3, a));
   }
 }
 

@@ -273,6 +273,24 @@ JxlDecoderStatus JxlHipBatchSetOutputScaled(JxlHipBatch* batch, int index, const
 typedef struct { JXL_BOOL planar; size_t plane_stride; JXL_BOOL affine; float scale[4]; float bias[4]; } JxlHipOutputLayout;
 JxlDecoderStatus JxlHipBatchOutBufferSizeLayout(const JxlHipBatch* batch, int index, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, size_t* size);
 JxlDecoderStatus JxlHipBatchSetOutputLayout(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout);
+/* ---- output of a requested size: antialiased resize, and crop, at the write stage -------------------------------------------------------------
+ * JxlHipOutputResize makes the output xsize x ysize pixels whatever the image's size, so that a job of differently sized images lands in one [N, C, H, W] tensor.
+ * The source of the resize is the picture the call without it would have written: after the orientation (or as stored, keep_orientation), at downscale 1 or 8; the
+ * crop rectangle is in that picture's coordinates (crop_xsize = crop_ysize = 0 and a zero origin: all of it) and the result is exactly that of cropping first.  Every
+ * channel slot is resampled separately, horizontally then vertically in float32, with the triangle filter with half-pixel centres, widened by the ratio where it shrinks:
+ * per axis with n_in source and n_out target samples, scale = n_in / n_out, support = max(scale, 1), target sample i is centred at c = scale x (i + 0.5) and is the
+ * weighted mean of the source samples j in [max(0, int(c - support + 0.5)), min(n_in, int(c + support + 0.5))) with weights max(0, 1 - |(j - c + 0.5) / support|) —
+ * the filter of Pillow's BILINEAR resize and of torch.nn.functional.interpolate(mode="bilinear", antialias=True, align_corners=False).  At the edges the range is cut
+ * and the weights are renormalised.  The filtered float32 sample is then stored like any other: sample type, byte order, bit depth, align, planar / plane_stride and
+ * scale / bias of `format` and `layout` keep their meaning, and the sizes the calls report are those of an xsize x ysize picture.
+ * Refused with a message in JxlHipLastError(): a target side of 0 or above 65535, an empty crop, a crop that leaves the picture (known per image: such an image of a pipeline
+ * job fails alone).  A NULL resize is the ...Layout call.  The resize does not choose `downscale`: ask for 8 together with a small target for the cost of a thumbnail.
+ * The picture is decoded whole, into a float32 intermediate of the batch's own (counted by JxlHipBatchDeviceBytes), whatever the crop. */
+typedef struct { uint32_t xsize, ysize; uint32_t crop_x0, crop_y0, crop_xsize, crop_ysize; } JxlHipOutputResize;
+JxlDecoderStatus JxlHipBatchOutBufferSizeResized(const JxlHipBatch* batch, int index, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout,
+                                                 const JxlHipOutputResize* resize, size_t* size);
+JxlDecoderStatus JxlHipBatchSetOutputResized(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout,
+                                             const JxlHipOutputResize* resize);
 /* JPEG bit-stream reconstruction of a whole batch (jpegxl-rs decode.rs:493 `reconstruct`, for many files at once).  JxlHipBatchCanReconstructJpeg: 1 if image
  * `index` is a lossless JPEG transcode with usable reconstruction data (a `jbrd` box whose markers find their ICC / Exif / XMP payloads, a Huffman-coded source),
  * else 0 with the reason in JxlHipLastError().  JxlHipBatchReconstructJpegs runs the LF and HF entropy stages once for all images of the batch (it prepares the batch
@@ -367,6 +385,10 @@ int64_t JxlHipPipelineSubmitScaled(JxlHipPipeline* pipeline, const uint8_t* cons
  * does not fit layout->plane_stride fails alone. */
 int64_t JxlHipPipelineSubmitLayout(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
                                    void* const* host_out, const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout);
+/* The same with every image resized (JxlHipOutputResize above; NULL = JxlHipPipelineSubmitLayout): destinations of JxlHipImageOutSizeResized bytes, the same for every
+ * image of the job.  An image the crop leaves fails alone. */
+int64_t JxlHipPipelineSubmitResized(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
+                                    void* const* host_out, const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResize* resize);
 /* Waits until the job has left the GPU (pixels written, host copies done).  image_status[i] (n entries, optional): 0 decoded, 1 failed; *end_ms (optional): when the
  * job's last byte was written, ms after JxlHipPipelineResetClock.  JXL_DEC_SUCCESS if every image decoded, else JXL_DEC_ERROR (JxlHipLastError names the first).
  * A ticket can be waited for once; jobs complete in submission order. */
@@ -390,6 +412,9 @@ JxlDecoderStatus JxlHipImageOutSizeScaled(const uint8_t* data, size_t size, cons
 /* The same for an output layout (JxlHipOutputLayout; NULL = interleaved) at downscale 1 or 8. */
 JxlDecoderStatus JxlHipImageOutSizeLayout(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, JxlBasicInfo* info,
                                           size_t* out_size);
+/* The same for a resized output (JxlHipOutputResize; NULL = JxlHipImageOutSizeLayout): the size of the xsize x ysize picture. */
+JxlDecoderStatus JxlHipImageOutSizeResized(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout,
+                                           const JxlHipOutputResize* resize, JxlBasicInfo* info, size_t* out_size);
 /* Device arenas that batches and pipelines let go of are pooled per process (hipMalloc / hipFree of tens of GB cost seconds): JXL_HIP_ARENA_POOL_MB bounds the pool
  * (default 60 % of the device's memory, 0 = off); Trim hands every pooled block back to the runtime — for processes that share the GPU with another allocator —
  * and returns the bytes released; Held = bytes pooled right now. */

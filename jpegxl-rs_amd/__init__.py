@@ -99,6 +99,11 @@ class JxlHipOutputLayout(C.Structure):
     _fields_ = [("planar", C.c_int), ("plane_stride", C.c_size_t), ("affine", C.c_int), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
 
 
+class JxlHipOutputResize(C.Structure):
+    """include/jxl_hip.h JxlHipOutputResize: the output's size, and the rectangle of the decoded picture that is resampled into it (all zero: the whole picture)"""
+    _fields_ = [(n, C.c_uint32) for n in ("xsize", "ysize", "crop_x0", "crop_y0", "crop_xsize", "crop_ysize")]
+
+
 assert C.sizeof(JxlBasicInfo) == 204 and C.sizeof(JxlPixelFormat) == 24 and C.sizeof(JxlMemoryManager) == 24
 
 _lib = None
@@ -167,6 +172,12 @@ def libjxl():
             "JxlHipPipelineSubmitLayout": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.c_int,
                                                        C.POINTER(JxlHipOutputLayout)]),
             "JxlHipImageOutSizeLayout": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlBasicInfo), C.POINTER(sz)]),
+            "JxlHipBatchOutBufferSizeResized": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResize), C.POINTER(sz)]),
+            "JxlHipBatchSetOutputResized": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), vp, C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResize)]),
+            "JxlHipPipelineSubmitResized": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.c_int,
+                                                        C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResize)]),
+            "JxlHipImageOutSizeResized": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResize), C.POINTER(JxlBasicInfo),
+                                                    C.POINTER(sz)]),
             "JxlHipBatchCanReconstructJpeg": (C.c_int, [vp, C.c_int]), "JxlHipBatchReconstructJpegs": (C.c_int, [vp, vp]),
             "JxlHipBatchJpegStatus": (C.c_int, [vp, C.c_int]), "JxlHipBatchJpegSize": (sz, [vp, C.c_int]), "JxlHipBatchCopyJpeg": (C.c_int, [vp, C.c_int, vp, sz]),
             "JxlHipBatchSetLaneStride": (None, [vp, C.c_int, C.c_int]), "JxlHipBatchSetOption": (None, [vp, C.c_char_p, C.c_int]),
@@ -615,6 +626,24 @@ def _layout(planar, plane_stride, scale, bias):
     return lay
 
 
+def _resize(resize, crop):
+    """-> JxlHipOutputResize, or None for an output of the image's own size.  resize: (width, height) of the output; crop: (x0, y0, width, height) of the decoded picture
+    that is resampled into it (needs resize)."""
+    if resize is None:
+        if crop is not None:
+            raise ValueError("crop needs resize=(width, height)")
+        return None
+    w, h = (int(v) for v in resize)
+    x0, y0, cw, ch = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
+    if min(w, h, x0, y0, cw, ch) < 0 or max(w, h, x0, y0, cw, ch) >= 1 << 32:
+        raise ValueError("resize / crop values must fit 32 unsigned bits")
+    return JxlHipOutputResize(w, h, x0, y0, cw, ch)
+
+
+def _byref(s):
+    return None if s is None else C.byref(s)
+
+
 # ---- batch extension (include/jxl_hip.h, JxlHipBatch*) -------------------------------------------------------------------
 class BatchDecoder:
     """Device-resident decode of a batch of independent images: inputs and outputs stay in HBM."""
@@ -628,6 +657,7 @@ class BatchDecoder:
         self._fmt = []
         self._scale = []
         self._layouts = []
+        self._resizes = []
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -638,9 +668,11 @@ class BatchDecoder:
         if status != JXL_DEC_SUCCESS:
             raise GenericError(last_error())
 
-    def _set_output(self, i, fmt, device_ptr, downscale, layout=None):
+    def _set_output(self, i, fmt, device_ptr, downscale, layout=None, resize=None):
         L = libjxl()
-        if layout is not None:
+        if resize is not None:
+            self._chk(L.JxlHipBatchSetOutputResized(self._h, i, C.byref(fmt), device_ptr, int(downscale), _byref(layout), C.byref(resize)))
+        elif layout is not None:
             self._chk(L.JxlHipBatchSetOutputLayout(self._h, i, C.byref(fmt), device_ptr, int(downscale), C.byref(layout)))
         elif downscale == 1:
             self._chk(L.JxlHipBatchSetOutput(self._h, i, C.byref(fmt), device_ptr))
@@ -649,14 +681,18 @@ class BatchDecoder:
         self._fmt.append(fmt)
         self._scale.append(int(downscale))
         self._layouts.append(layout)
+        self._resizes.append(resize)
 
     def add(self, data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, device_ptr=None, downscale=1,
-            planar=False, plane_stride=0, scale=None, bias=None) -> int:
+            planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None) -> int:
         """downscale=8: the 1:8 decode (include/jxl_hip.h JxlHipBatchSetOutputScaled) — output(i) is the ceil(w / 8) x ceil(h / 8) picture; `data` may end behind
         the LF part of its frame.
         planar=True: one plane per channel, [C, H, W] with rows `align`ed and planes plane_stride bytes apart (0 = tight); scale / bias (up to four values, one per
-        channel slot, float16 / float32 output): samples are stored as v * scale[c] + bias[c] (include/jxl_hip.h JxlHipOutputLayout)."""
+        channel slot, float16 / float32 output): samples are stored as v * scale[c] + bias[c] (include/jxl_hip.h JxlHipOutputLayout).
+        resize=(w, h): the output is w x h pixels, the decoded picture — oriented, at `downscale` — resampled with the antialiased triangle filter (torch's
+        interpolate(mode="bilinear", antialias=True)); crop=(x0, y0, w, h): only that rectangle of the picture, as if cropped first (include/jxl_hip.h JxlHipOutputResize)."""
         layout = _layout(planar, plane_stride, scale, bias)
+        rs = _resize(resize, crop)
         L = libjxl()
         buf = np.frombuffer(data, dtype=np.uint8)
         if downscale != 1:
@@ -669,16 +705,17 @@ class BatchDecoder:
         if i < 0:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
-        self._set_output(i, fmt, device_ptr, downscale, layout)
+        self._set_output(i, fmt, device_ptr, downscale, layout, rs)
         self._n += 1
         return i
 
     def add_many(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, threads=4, endianness=Endianness.Native, align=0, downscale=1,
-                 planar=False, plane_stride=0, scale=None, bias=None) -> int:
+                 planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None) -> int:
         """Parses the images of `datas` (bytes objects) on `threads` host threads and appends them in order (JxlHipBatchAddImages);
-        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale, planar, plane_stride, scale, bias: as for add()."""
+        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale, planar, plane_stride, scale, bias, resize, crop: as for add()."""
         L = libjxl()
         layout = _layout(planar, plane_stride, scale, bias)
+        rs = _resize(resize, crop)
         n = len(datas)
         ptrs = (C.c_char_p * n)(*datas)
         sizes = (C.c_size_t * n)(*[len(d) for d in datas])
@@ -693,7 +730,7 @@ class BatchDecoder:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
         for k in range(n):
-            self._set_output(first + k, fmt, device_ptrs[k] if device_ptrs is not None else None, downscale, layout)
+            self._set_output(first + k, fmt, device_ptrs[k] if device_ptrs is not None else None, downscale, layout, rs)
         self._n += n
         return first
 
@@ -704,6 +741,7 @@ class BatchDecoder:
         self._fmt = []
         self._scale = []
         self._layouts = []
+        self._resizes = []
 
     def info(self, i) -> JxlBasicInfo:
         info = JxlBasicInfo()
@@ -712,7 +750,9 @@ class BatchDecoder:
 
     def out_size(self, i) -> int:
         s = C.c_size_t()
-        if self._layouts[i] is not None:
+        if self._resizes[i] is not None:
+            self._chk(libjxl().JxlHipBatchOutBufferSizeResized(self._h, i, C.byref(self._fmt[i]), self._scale[i], _byref(self._layouts[i]), C.byref(self._resizes[i]), C.byref(s)))
+        elif self._layouts[i] is not None:
             self._chk(libjxl().JxlHipBatchOutBufferSizeLayout(self._h, i, C.byref(self._fmt[i]), self._scale[i], C.byref(self._layouts[i]), C.byref(s)))
         elif self._scale[i] == 1:
             self._chk(libjxl().JxlHipBatchOutBufferSize(self._h, i, C.byref(self._fmt[i]), C.byref(s)))
@@ -826,15 +866,21 @@ def arena_pool_trim() -> int:
     return int(libjxl().JxlHipArenaPoolTrim())
 
 
-def image_out_size(data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, downscale=1, planar=False, plane_stride=0, scale=None, bias=None):
+def image_out_size(data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, downscale=1, planar=False, plane_stride=0, scale=None, bias=None,
+                   resize=None, crop=None):
     """(JxlBasicInfo, bytes of the decoded image in that format) from the headers alone — host-only (JxlHipImageOutSize).
     downscale=8: the size of the 1:8 decode (JxlHipImageOutSizeScaled); the info stays that of the full-size image.
-    planar, plane_stride, scale, bias: the layout as for BatchDecoder.add (JxlHipImageOutSizeLayout); a layout the image or the sample type does not take raises."""
+    planar, plane_stride, scale, bias: the layout as for BatchDecoder.add (JxlHipImageOutSizeLayout); a layout the image or the sample type does not take raises.
+    resize, crop: the size of the resized output, as for BatchDecoder.add (JxlHipImageOutSizeResized); a crop that leaves the image raises."""
     fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
     info, size = JxlBasicInfo(), C.c_size_t()
     buf = np.frombuffer(data, dtype=np.uint8)
     layout = _layout(planar, plane_stride, scale, bias)
-    if layout is not None:
+    rs = _resize(resize, crop)
+    if rs is not None:
+        if libjxl().JxlHipImageOutSizeResized(buf.ctypes.data, len(data), C.byref(fmt), int(downscale), _byref(layout), C.byref(rs), C.byref(info), C.byref(size)) != JXL_DEC_SUCCESS:
+            raise GenericError(last_error())
+    elif layout is not None:
         if libjxl().JxlHipImageOutSizeLayout(buf.ctypes.data, len(data), C.byref(fmt), int(downscale), C.byref(layout), C.byref(info), C.byref(size)) != JXL_DEC_SUCCESS:
             raise GenericError(last_error())
     elif downscale == 1:
@@ -891,11 +937,13 @@ class Pipeline:
     __del__ = close
 
     def submit(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, host_ptrs=None, capacities=None, endianness=Endianness.Native, align=0, downscale=1,
-               planar=False, plane_stride=0, scale=None, bias=None) -> int:
+               planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None) -> int:
         """Job of len(datas) images (bytes objects).  device_ptrs / host_ptrs: one destination address per image (exactly one of the two lists); the bytes objects and
         the destinations are kept referenced until wait().  downscale=8: the job is decoded at 1:8 (JxlHipPipelineSubmitScaled).  planar, plane_stride, scale, bias:
-        the layout of every image of the job, as for BatchDecoder.add (JxlHipPipelineSubmitLayout)."""
+        the layout of every image of the job, as for BatchDecoder.add (JxlHipPipelineSubmitLayout).  resize, crop: every image of the job comes out resize[0] x resize[1]
+        pixels (JxlHipPipelineSubmitResized) — destinations of one size, e.g. consecutive slices of one [N, C, H, W] tensor; an image the crop leaves fails alone."""
         layout = _layout(planar, plane_stride, scale, bias)
+        rs = _resize(resize, crop)
         n = len(datas)
         ptrs = (C.c_char_p * n)(*datas)
         sizes = (C.c_size_t * n)(*[len(d) for d in datas])
@@ -903,7 +951,9 @@ class Pipeline:
         dev = (C.c_void_p * n)(*device_ptrs) if device_ptrs is not None else None
         host = (C.c_void_p * n)(*host_ptrs) if host_ptrs is not None else None
         caps = (C.c_size_t * n)(*capacities) if capacities is not None else None
-        if layout is not None:
+        if rs is not None:
+            t = libjxl().JxlHipPipelineSubmitResized(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), _byref(layout), C.byref(rs))
+        elif layout is not None:
             t = libjxl().JxlHipPipelineSubmitLayout(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), C.byref(layout))
         elif downscale == 1:
             t = libjxl().JxlHipPipelineSubmit(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps)

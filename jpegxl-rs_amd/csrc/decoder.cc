@@ -519,7 +519,7 @@ bool Batch::DevReserve(void** ptr, size_t* cap, size_t bytes) {
 // Forgets the images (and everything derived from them) but keeps the device arenas, the pinned staging buffer and the sharing set up with
 // ShareBigArena / ShareCoefArena: the batch object can be filled again.  The caller makes sure no decode of the old content is in flight.
 void Batch::Reset() {
-  images_.clear(); pub_.clear(); cbufs_.clear(); post_ops_.clear(); jpeg_data_.clear();
+  images_.clear(); pub_.clear(); cbufs_.clear(); post_ops_.clear(); jpeg_data_.clear(); resize_plans_.clear(); resize_ops_.clear();
   frames_host_.clear(); passes_host_.clear(); pass_first_.clear(); local_host_.clear(); local_first_.clear();
   mod_plane_offsets_.clear(); mod_ops_.clear(); vardct_alpha_.clear(); hf_written_.clear();
   // (stage timings recorded so far stay: CollectTimes sums over the object's life)
@@ -643,8 +643,12 @@ ImageHeader Batch::PreviewHeaderOf(int i) const {
   ph.xsize = e.ih.preview_x; ph.ysize = e.ih.preview_y; ph.have_preview = false; ph.intrinsic_x = ph.intrinsic_y = 0;
   return ph;
 }
-size_t Batch::PreviewOutputSize(int i, const OutputSpec& o) const { return OutputSize(PreviewHeaderOf(i), o); }
+size_t Batch::PreviewOutputSize(int i, const OutputSpec& o) const {
+  if (o.resized() || o.cropped()) throw ParseError("preview: no resized output", false);
+  return OutputSize(PreviewHeaderOf(i), o);
+}
 void Batch::DecodePreview(int i, const OutputSpec& o, void* dst, size_t cap, void* stream_v) {
+  if (o.resized() || o.cropped()) throw ParseError("preview: no resized output", false);
   const ImageEntry& e = *images_[pub_[i].first_unit];
   std::shared_ptr<ImageShared> sh(new ImageShared());
   sh->cs = e.cs; sh->ih = PreviewHeaderOf(i);
@@ -756,13 +760,18 @@ size_t Batch::OutputStride(const ImageHeader& ih, const OutputSpec& o, uint32_t*
 // Orientations 5..8 transpose the image (codestream_header.rs JxlOrientation); applied unless the caller keeps it.
 // (1:8 decode, OutputSpec::downscale == 8: one pixel per 8x8 block of the stored picture, the orientation applied to that picture)
 static uint32_t Scaled(uint32_t v, const OutputSpec& o) { return o.downscale == 8 ? (v + 7) / 8 : v; }
-uint32_t Batch::OrientedWidth(const ImageHeader& ih, const OutputSpec& o) { return Scaled((!o.keep_orientation && ih.orientation > 4) ? ih.ysize : ih.xsize, o); }
-uint32_t Batch::OrientedHeight(const ImageHeader& ih, const OutputSpec& o) { return Scaled((!o.keep_orientation && ih.orientation > 4) ? ih.xsize : ih.ysize, o); }
+// (resized output, OutputSpec::resize_w / resize_h: that picture is the source of the resize, the output has the target size)
+uint32_t Batch::SourceWidth(const ImageHeader& ih, const OutputSpec& o) { return Scaled((!o.keep_orientation && ih.orientation > 4) ? ih.ysize : ih.xsize, o); }
+uint32_t Batch::SourceHeight(const ImageHeader& ih, const OutputSpec& o) { return Scaled((!o.keep_orientation && ih.orientation > 4) ? ih.xsize : ih.ysize, o); }
+uint32_t Batch::OrientedWidth(const ImageHeader& ih, const OutputSpec& o) { return o.resized() ? o.resize_w : SourceWidth(ih, o); }
+uint32_t Batch::OrientedHeight(const ImageHeader& ih, const OutputSpec& o) { return o.resized() ? o.resize_h : SourceHeight(ih, o); }
 size_t Batch::OutputSize(const ImageHeader& ih, const OutputSpec& o) {
   // jpegxl-sys decode.rs:1100 JxlDecoderImageOutBufferSize: stride * (h - 1) + w * C * bytes
   uint32_t nc;
   const size_t stride = OutputStride(ih, o, &nc);
   const size_t bps = o.type == 0 ? 1 : o.type == 2 ? 4 : 2;
+  const std::string no_resize = ResizeRefusal(ih, o);
+  if (!no_resize.empty()) throw ParseError(no_resize, false);
   const std::string why = LayoutRefusal(ih, o);
   if (!why.empty()) throw ParseError(why, false);
   if (o.planar) return (size_t)nc * (o.plane_stride ? o.plane_stride : stride * OrientedHeight(ih, o));
@@ -778,6 +787,42 @@ std::string Batch::LayoutRefusal(const ImageHeader& ih, const OutputSpec& o) {
   }
   return std::string();
 }
+std::string Batch::ResizeRefusal(const ImageHeader& ih, const OutputSpec& o) {
+  if (!o.resized()) return o.cropped() ? "resized output: a crop needs a target size" : std::string();
+  if (o.resize_w == 0 || o.resize_h == 0) return "resized output: a target side of 0";
+  if (o.resize_w > 65535 || o.resize_h > 65535) return "resized output: a target side above 65535";
+  if (!o.cropped()) return std::string();
+  const uint32_t w = SourceWidth(ih, o), h = SourceHeight(ih, o);
+  if (o.crop_w == 0 || o.crop_h == 0) return "resized output: the crop is empty";
+  if (o.crop_x0 >= w || o.crop_w > w - o.crop_x0 || o.crop_y0 >= h || o.crop_h > h - o.crop_y0)
+    return "resized output: the crop " + std::to_string(o.crop_w) + " x " + std::to_string(o.crop_h) + " at (" + std::to_string(o.crop_x0) + ", " + std::to_string(o.crop_y0) +
+           ") leaves the " + std::to_string(w) + " x " + std::to_string(h) + " picture";
+  return std::string();
+}
+// One axis of the resize (OutputSpec::resize_w / resize_h): the triangle filter with half-pixel centres, widened by the ratio when it shrinks (the filter of Pillow's BILINEAR
+// reduce and of torch's interpolate(mode="bilinear", antialias=True)).  n_in samples -> n_out; scale = n_in / n_out, support = max(scale, 1), output i has its centre at
+// c = scale x (i + 0.5) and takes the samples j of [max(0, int(c - support + 0.5)), min(n_in, int(c + support + 0.5))) with weight max(0, 1 - |(j - c + 0.5) / support|)
+// over the sum of these: the range is cut at the edges and the weights renormalised, nothing is mirrored or clamped.  Everything in double; a normalised weight is rounded
+// to f32 once.  Samples of weight 0 at either end of a range are left out (they change no sum; at n_in == n_out one tap of weight 1 is left: a copy).
+// lo[i]: first sample of output i; its weights are weight[first[i]] .. weight[first[i + 1] - 1].
+static void ResizeAxis(uint32_t n_in, uint32_t n_out, vec<uint32_t>* lo, vec<uint32_t>* first, vec<float>* weight) {
+  const double scale = (double)n_in / (double)n_out, support = std::max(scale, 1.0);
+  lo->assign(n_out, 0); first->assign((size_t)n_out + 1, 0); weight->clear();
+  vec<double> w;
+  for (uint32_t i = 0; i < n_out; i++) {
+    const double c = scale * ((double)i + 0.5);
+    int64_t a = std::max<int64_t>(0, (int64_t)(c - support + 0.5)), b = std::min<int64_t>((int64_t)n_in, (int64_t)(c + support + 0.5));
+    w.assign((size_t)(b - a), 0.0);
+    double sum = 0.0;
+    for (int64_t j = a; j < b; j++) { w[(size_t)(j - a)] = std::max(0.0, 1.0 - std::fabs(((double)j - c + 0.5) / support)); sum += w[(size_t)(j - a)]; }
+    const int64_t a0 = a;
+    while (b - a > 1 && w[(size_t)(b - 1 - a0)] == 0.0) b--;
+    while (b - a > 1 && w[(size_t)(a - a0)] == 0.0) a++;
+    (*lo)[i] = (uint32_t)a; (*first)[i] = (uint32_t)weight->size();
+    for (int64_t j = a; j < b; j++) weight->push_back((float)(w[(size_t)(j - a0)] / sum));
+  }
+  (*first)[n_out] = (uint32_t)weight->size();
+}
 void Batch::OutputDims(int i, const OutputSpec& o, uint32_t* w, uint32_t* h) const {
   const ImageEntry& first = *images_[pub_[i].first_unit];
   *w = first.ih.xsize; *h = first.ih.ysize;
@@ -790,14 +835,24 @@ size_t Batch::OutputSizeOf(int i, const OutputSpec& o) const {
 }
 static float IntMul(const OutputSpec& o) { const uint32_t full = o.type == 0 ? 8 : 16; const uint32_t b = o.int_bits && o.int_bits < full ? o.int_bits : full; return (float)((1u << b) - 1); }
 // Where the write stage puts the image's pixels (work: the arena that holds the output unless the caller named a device buffer)
-static OutputDesc FillOutput(const ImageEntry& e, uint8_t* work) {
+// A resized output (OutputSpec::resize_w / resize_h): the write stage leaves the picture — oriented, every slot of the output — as plain interleaved f32 among the pixel planes
+// (big: it lives from the write stage to the resize behind it, like the planes the write stage reads), and ResizeKernel writes the caller's destination from it
+// (EnqueueResizes, resize_target = true: the destination as it is described otherwise, the orientation applied already)
+static OutputDesc FillOutput(const ImageEntry& e, uint8_t* work, uint8_t* big, bool resize_target = false) {
   OutputDesc d{};
+  if (e.out.resized() && !resize_target) {
+    d.out = big + e.off_resize_src;
+    d.out_stride = (size_t)e.src_w * e.out.num_channels * 4; d.out_channels = e.out.num_channels; d.out_type = 2; d.out_int_mul = 1.0f;
+    d.out_orient = e.out.keep_orientation ? 1 : e.ih.orientation; d.is_gray = e.ih.color_space == 1;
+    return d;
+  }
   d.out = (uint8_t*)(e.out.device_ptr ? e.out.device_ptr : work + e.off_out);
   d.planar = e.out.planar; d.plane_stride = !e.out.planar ? 0 : e.out.plane_stride ? e.out.plane_stride : e.out_size / std::max(1u, e.out.num_channels);
   d.affine = e.out.affine;
   for (int c = 0; c < 4; c++) { d.scale[c] = e.out.scale[c]; d.bias[c] = e.out.bias[c]; }
   d.out_stride = e.out_stride; d.out_channels = e.out.num_channels; d.out_type = e.out.type; d.out_big_endian = e.out.big_endian; d.out_int_mul = IntMul(e.out);
   d.out_orient = e.out.keep_orientation ? 1 : e.ih.orientation; d.is_gray = e.ih.color_space == 1;
+  if (resize_target) d.out_orient = 1;
   return d;
 }
 // What the 1:8 decode takes: single-frame VarDCT images that carry their own LF coefficients and end in their own pixels (no frame tail).
@@ -832,12 +887,14 @@ void Batch::SetOutput(int i, const OutputSpec& o) {
   e.out_stride = OutputStride(dims, o, &nc);
   e.out.num_channels = nc;
   e.out_size = OutputSize(dims, o);
+  e.src_w = SourceWidth(dims, o); e.src_h = SourceHeight(dims, o);
   e.deliver_frames.clear();
   prepared_ = false;
 }
 void Batch::SetOutputAllFrames(int i, const OutputSpec& o, const vec<int>& frames) {
   if (o.device_ptr || o.only_frame >= 0 || frames.empty()) throw ParseError("SetOutputAllFrames: internal output buffers, coalesced frames only", false);
   if (o.planar || o.affine) throw ParseError("SetOutputAllFrames: interleaved output without scale / bias only", false);
+  if (o.resized() || o.cropped()) throw ParseError("SetOutputAllFrames: no resized output", false);
   for (size_t k = 0; k < frames.size(); k++)
     if (frames[k] < 0 || frames[k] >= pub_[i].num_units || (k && frames[k] <= frames[k - 1])) throw ParseError("SetOutputAllFrames: frame list must be ascending positions among the image's frames", false);
   OutputSpec oo = o;
@@ -873,7 +930,16 @@ void Batch::StageBytes(uint64_t out[6]) const {
       for (size_t s = 2 + p.num_lf_groups; s < p.sections.size(); s++) hf_sec += p.sections[s].size;
     }
     const uint64_t bps = first.out.type == 0 ? 1 : first.out.type == 2 ? 4 : 2;
-    const uint64_t out_px = (uint64_t)first.out.num_channels * bps;
+    uint64_t out_px = (uint64_t)first.out.num_channels * bps;
+    if (first.out.resized()) {
+      // resized output: the write stage's pixels are the f32 intermediate; ResizeKernel reads the resampled rectangle of it and writes the target in the caller's format (once per
+      // image; the horizontally filtered rows between its two passes are traffic, not algorithmic bytes)
+      out_px = (uint64_t)first.out.num_channels * 4;
+      if (&e == &first) {
+        const uint64_t rect = first.out.cropped() ? (uint64_t)first.out.crop_w * first.out.crop_h : (uint64_t)first.src_w * first.src_h;
+        out[5] += rect * out_px + (uint64_t)first.out.resize_w * first.out.resize_h * first.out.num_channels * bps;
+      }
+    }
     out[0] += lf_sec + nblk * (3 * 4 + 4 + 4);
     out[1] += nblk * (12 + 12 + 12 + 12 + 12 + 16);
     if (first.out.downscale == 8) {      // 1:8 decode: no HF stage, no IDCT, no filters; LfOutputKernel reads three LF samples and writes one pixel per block
@@ -1062,6 +1128,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
   max_lf_groups_ = max_groups_ = max_w_ = max_h_ = max_bw_ = max_bh_ = max_epf_ = 0;
   any_gab_ = any_vardct_ = any_modular_ = any_modchan_ = any_multipass_ = any_scaled_ = any_full_vardct_ = false;
   fplan_ = FilterPlan();
+  resize_plans_.clear(); resize_ops_.clear();
   // frames decoded at 1:8 (OutputSpec::downscale == 8; SetOutput only lets single-frame VarDCT images through): their decode ends behind the LF post-processing
   auto scaled = [&](int i) { return images_[i]->frame_index == 0 && images_[i]->out.downscale == 8; };
   vec<size_t> cs_bytes(n, 0);    // codestream bytes the frame's kernels may look at (FrameDev::cs_size)
@@ -1070,6 +1137,17 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     FramePlan& p = e.plan;
     ConstOffsets& c = co[i];
     if (e.frame_index == 0 && e.out_size == 0) SetOutput(e.pub_index, e.out);
+    if (e.frame_index == 0 && e.out.resized()) {     // the two axes' filters of a resized output (ResizeAxis)
+      ResizePlan rp;
+      rp.unit = i;
+      vec<uint32_t> lo, first; vec<float> weight;
+      for (int ax = 0; ax < 2; ax++) {
+        const uint32_t n_in = e.out.cropped() ? (ax ? e.out.crop_h : e.out.crop_w) : (ax ? e.src_h : e.src_w);
+        ResizeAxis(n_in, ax ? e.out.resize_h : e.out.resize_w, &lo, &first, &weight);
+        rp.tab[3 * ax] = arena.Put(lo.data(), lo.size() * 4); rp.tab[3 * ax + 1] = arena.Put(first.data(), first.size() * 4); rp.tab[3 * ax + 2] = arena.Put(weight.data(), weight.size() * 4);
+      }
+      resize_plans_.push_back(rp);
+    }
     cs_bytes[i] = e.cs.size;
     if (scaled(i) && !p.single_section) {
       // the 1:8 decode reads LfGlobal, the LfGroups and (on the host) HfGlobal: what lies behind the last of them — the AC groups, most of the file — stays on the host
@@ -1163,6 +1241,12 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     WorkOffsets& o = wo[i];
     o.end_bitpos = take(16);
     if (e.frame_index == 0 && !e.out.device_ptr) e.off_out = take((e.out_size + 64) * std::max<size_t>(1, e.deliver_frames.size()));
+    if (e.frame_index == 0 && e.out.resized()) {
+      // resized output: the f32 picture the write stage leaves (every slot of the output, interleaved), and the rows of the resampled rectangle after the horizontal pass —
+      // among the pixel planes: written and read between the write stage and the end of the decode, so the jobs of a pipeline share one set (UseSharedPlanes)
+      e.off_resize_src = take_big((size_t)e.src_w * e.src_h * e.out.num_channels * 4);
+      e.off_resize_tmp = take_big((size_t)(e.out.cropped() ? e.out.crop_h : e.src_h) * e.out.resize_w * e.out.num_channels * 4);
+    }
   if (p.upsampling > 1) {   // kernel weights: custom (image header) or library default
       const int upk = p.upsampling == 2 ? 0 : p.upsampling == 4 ? 1 : 2;
       const float* const kDefault[3] = {kUp2, kUp4, kUp8};
@@ -1384,7 +1468,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     f.status = (uint32_t*)(dwork_ + status_off_) + i;
     f.frame_flags = (uint32_t*)(dwork_ + flags_off) + i;
     f.hf_written = (uint32_t*)(dwork_ + hfw_off_) + i;
-    f.od = FillOutput(e, dwork_);
+    f.od = FillOutput(e, dwork_, dbig_);
     f.upsampling = p.upsampling; f.img_w = e.ih.xsize; f.img_h = e.ih.ysize;
     if (scaled(i)) { f.lf_only = 1; f.img_w = (p.width + 7) / 8; f.img_h = (p.height + 7) / 8; }     // (the picture LfOutputKernel writes; out_stride is SetOutput's, of the same picture)
     if (p.upsampling > 1) { f.up_weights = (const float*)(cbase + c.up_weights); for (int k = 0; k < 4; k++) f.up_plane[k] = (float*)(dbig_ + o.up_plane[k]); }
@@ -1722,6 +1806,18 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
   DevReserve((void**)&dconst_, &const_cap_, const_size_);
   HIP_CHECK(hipMemcpyAsync(dconst_, hconst_.data(), hconst_.size(), hipMemcpyHostToDevice, stream));
   for (int i = 0; i < n; i++) { fill_frame(i, dconst_); frames_host_[i].lf_simt = lf_simt_.num_lanes ? simt_frame[i] : 0; }
+  for (const ResizePlan& rp : resize_plans_) {
+    const ImageEntry& e = *images_[rp.unit];
+    const OutputSpec& o = e.out;
+    ResizeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = (const float*)(dbig_ + e.off_resize_src); a.tmp = (float*)(dbig_ + e.off_resize_tmp); a.src_stride = (uint64_t)e.src_w * o.num_channels;
+    a.x0 = o.crop_x0; a.y0 = o.crop_y0; a.in_w = o.cropped() ? o.crop_w : e.src_w; a.in_h = o.cropped() ? o.crop_h : e.src_h; a.out_w = o.resize_w; a.out_h = o.resize_h;
+    a.ax = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[0]), (const uint32_t*)(dconst_ + rp.tab[1]), (const float*)(dconst_ + rp.tab[2])};
+    a.ay = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[3]), (const uint32_t*)(dconst_ + rp.tab[4]), (const float*)(dconst_ + rp.tab[5])};
+    a.od = FillOutput(e, dwork_, dbig_, /*resize_target=*/true);
+    resize_ops_.push_back(a);
+  }
   lf_simt_.units = (const uint2*)(dconst_ + place_units_off);
   if (lf_simt_.num_lanes) {
     lf_simt_.streams = (const LfSimtStream*)(dconst_ + simt_streams_off); lf_simt_.lanes = (const LfSimtLane*)(dconst_ + simt_lanes_off); lf_simt_.luts = dconst_ + simt_luts_off;
@@ -2228,7 +2324,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
           break;
         }
         wa.img_w = fw; wa.img_h = fh;
-        wa.od = FillOutput(first, dwork_);
+        wa.od = FillOutput(first, dwork_, dbig_);
         if (have_deferred_tf) {          // (the transfer function had been put off for a spot-colour stage this output does not run)
           ColorArgs ta = deferred_tf;
           for (int c = 0; c < 3; c++) { ta.src[c] = B(cur[c]); ta.dst[c] = B(cur[c]); }
@@ -2342,7 +2438,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         break;
       }
       wa.img_w = ih.xsize; wa.img_h = ih.ysize;
-      wa.od = FillOutput(first, dwork_);
+      wa.od = FillOutput(first, dwork_, dbig_);
       if (all_frames) wa.od.out += (size_t)slot * (first.out_size + 64);
       post_ops_.push_back([=](void* st) { LaunchWrite(wa, st); });
       if (all_frames && slot + 1 < (int)first.deliver_frames.size()) continue;
@@ -2353,6 +2449,8 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
 }
 
 void Batch::EnqueuePostOps(void* stream) { for (auto& op : post_ops_) op(stream); }
+// Resized outputs: behind everything that writes pixels (the write kernels of plain frames, the Modular tail, the frame tail), on the same stream
+void Batch::EnqueueResizes(void* stream) { for (const ResizeArgs& a : resize_ops_) LaunchResize(a, stream); }
 
 // The HF stage only writes non-zero coefficients into zeroed planes.  The IDCT kernels zero what they consumed (kernels.hip,
 // IdctTileKernel pass 0), so a batch that is decoded again and again never clears its planes as a whole; only a decode whose
@@ -2468,6 +2566,7 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
         rec(5);
         if (any_modchan_) EnqueueModularTail(stream_v);
         if (any_complex_) EnqueuePostOps(stream_v);
+        EnqueueResizes(stream_v);
         CheckLaunches("Modular sub-streams / frame tail");
         rec(6);
         if (timed && split) timed_rest_cursor_++;
@@ -2510,6 +2609,7 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
       if (!cfg.debug_stop_after && any_full_vardct_) LaunchOutput(dframes_, n, max_w_, max_h_, fplan_, cfg, stream_v);
       if (!cfg.debug_stop_after && any_scaled_) LaunchLfOutput(dframes_, n, max_bw_, max_bh_, stream_v);   // 1:8 frames: the LF image through the colour transform and the write stage
       if (any_complex_ && !cfg.debug_stop_after) EnqueuePostOps(stream_v);   // frame tail of multi-frame / feature images
+      if (!cfg.debug_stop_after) EnqueueResizes(stream_v);
       DebugSync("output / frame tail", stream_v);
       CheckLaunches("filters / output / frame tail");
       rec(6);

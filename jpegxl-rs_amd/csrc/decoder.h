@@ -36,6 +36,12 @@ struct OutputSpec {
   size_t plane_stride = 0;        // 0 = tight (oriented height x row stride), else at least that and a multiple of the sample size
   bool affine = false;            // float16 / float32 output: slot c is stored as fmaf(v, scale[c], bias[c])
   float scale[4] = {1.0f, 1.0f, 1.0f, 1.0f}, bias[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  // ---- resize (Batch and Pipeline outputs): the picture the output would have held without it — oriented, at downscale 1 or 8, the "source" — is resampled to
+  // resize_w x resize_h with the antialiased triangle filter (ResizeAxis, decoder.cc); the output's size, strides and layout go by the target size
+  uint32_t resize_w = 0, resize_h = 0;     // 0 x 0 = off, else 1 .. 65535 each
+  uint32_t crop_x0 = 0, crop_y0 = 0, crop_w = 0, crop_h = 0;   // rectangle of the source that is resampled (all 0 = the whole picture): exactly crop first, then resize
+  bool resized() const { return resize_w || resize_h; }
+  bool cropped() const { return crop_x0 || crop_y0 || crop_w || crop_h; }
 };
 
 // What the frames of one image share: the codestream and the image header.
@@ -62,6 +68,8 @@ struct ImageEntry {
   // arena offsets
   size_t off_cs = 0, off_sec = 0, off_tree = 0, off_bcm = 0;
   size_t off_out = 0;
+  size_t off_resize_src = 0, off_resize_tmp = 0;   // (first unit, resized output; pixel-plane arena) the f32 picture the write stage leaves for ResizeKernel, the horizontally filtered rows
+  uint32_t src_w = 0, src_h = 0;                   // (first unit) size of that picture: SetOutput
   explicit ImageEntry(std::shared_ptr<ImageShared> s) : shared(std::move(s)), cs(shared->cs), ih(shared->ih) {}
 };
 
@@ -117,9 +125,15 @@ class Batch {
   static size_t OutputStride(const ImageHeader& ih, const OutputSpec& o, uint32_t* channels);
   static uint32_t OrientedWidth(const ImageHeader& ih, const OutputSpec& o);
   static uint32_t OrientedHeight(const ImageHeader& ih, const OutputSpec& o);
+  // size of the picture a resize reads (OrientedWidth / OrientedHeight of the same output without its resize)
+  static uint32_t SourceWidth(const ImageHeader& ih, const OutputSpec& o);
+  static uint32_t SourceHeight(const ImageHeader& ih, const OutputSpec& o);
   static size_t OutputSize(const ImageHeader& ih, const OutputSpec& o);
   // "" when the layout of `o` (planar, plane_stride, affine) can be written for an image of ih's size, else the reason; OutputSize and SetOutput throw it
   static std::string LayoutRefusal(const ImageHeader& ih, const OutputSpec& o);
+  // "" when the resize of `o` can be done for an image of ih's size (a target side of 0 or above 65535, a crop that is empty or leaves the picture), else the reason;
+  // OutputSize and SetOutput throw it
+  static std::string ResizeRefusal(const ImageHeader& ih, const OutputSpec& o);
   // size of the rectangle output `o` of image i covers: the image, or — non-coalesced output — frame o.only_frame as coded (before orientation)
   void OutputDims(int i, const OutputSpec& o, uint32_t* w, uint32_t* h) const;
   size_t OutputSizeOf(int i, const OutputSpec& o) const;
@@ -227,6 +241,11 @@ class Batch {
   bool any_complex_ = false;
   void PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off);
   void EnqueuePostOps(void* stream);
+  // resized outputs: per image one ResizeArgs (kernels.h), built by Prepare, launched behind everything that writes pixels
+  struct ResizePlan { int unit; size_t tab[6]; };    // constant-arena offsets of the two axes' tables: lo, first, weights of x, then of y
+  vec<ResizePlan> resize_plans_;
+  vec<ResizeArgs> resize_ops_;
+  void EnqueueResizes(void* stream);
   vec<FrameDev> frames_host_;
   HostStage hconst_;
   struct ParsedImage { vec<std::unique_ptr<ImageEntry>> units; bool complex = false; };

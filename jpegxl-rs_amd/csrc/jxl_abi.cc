@@ -928,36 +928,56 @@ static bool ApplyLayout(const JxlHipOutputLayout* l, OutputSpec* o, const char* 
   }
   return true;
 }
-static JxlDecoderStatus BatchOutBufferSize(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, size_t* size, const char* who) {
+// JxlHipOutputResize -> OutputSpec (NULL: the image's own size); a crop is checked where the image's size is known (Batch::ResizeRefusal)
+static bool ApplyResize(const JxlHipOutputResize* r, OutputSpec* o, const char* who) {
+  if (!r) return true;
+  if (r->xsize == 0 || r->ysize == 0) { SetLastError(std::string(who) + ": resized output: a target side of 0"); return false; }
+  if (r->xsize > 65535 || r->ysize > 65535) { SetLastError(std::string(who) + ": resized output: a target side above 65535"); return false; }
+  o->resize_w = r->xsize; o->resize_h = r->ysize;
+  o->crop_x0 = r->crop_x0; o->crop_y0 = r->crop_y0; o->crop_w = r->crop_xsize; o->crop_h = r->crop_ysize;
+  if (o->cropped() && (o->crop_w == 0 || o->crop_h == 0)) { SetLastError(std::string(who) + ": resized output: the crop is empty"); return false; }
+  return true;
+}
+static JxlDecoderStatus BatchOutBufferSize(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResize* resize,
+                                           size_t* size, const char* who) {
   if (!DownscaleOk(downscale, who)) return JXL_DEC_ERROR;
   OutputSpec o;
-  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o) || !ApplyLayout(layout, &o, who)) return JXL_DEC_ERROR;
+  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o) || !ApplyLayout(layout, &o, who) || !ApplyResize(resize, &o, who)) return JXL_DEC_ERROR;
   o.keep_orientation = h->keep_orientation;
   o.downscale = (uint32_t)downscale;
   try { *size = Batch::OutputSize(h->b->image(i).ih, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
 }
-static JxlDecoderStatus BatchSetOutput(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout, const char* who) {
+static JxlDecoderStatus BatchSetOutput(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout,
+                                       const JxlHipOutputResize* resize, const char* who) {
   if (!DownscaleOk(downscale, who)) return JXL_DEC_ERROR;
   OutputSpec o;
-  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o) || !ApplyLayout(layout, &o, who)) return JXL_DEC_ERROR;
+  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o) || !ApplyLayout(layout, &o, who) || !ApplyResize(resize, &o, who)) return JXL_DEC_ERROR;
   o.device_ptr = device_buffer;
   o.keep_orientation = h->keep_orientation;
   o.downscale = (uint32_t)downscale;
-  try { h->b->SetOutput(i, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }   // ("unsupported: downscaled decode of ...", a plane_stride that does not fit)
+  try { h->b->SetOutput(i, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }   // ("unsupported: downscaled decode of ...", a plane_stride that does not fit, a crop that leaves the picture)
 }
-JxlDecoderStatus JxlHipBatchOutBufferSize(const JxlHipBatch* h, int i, const JxlPixelFormat* format, size_t* size) { return BatchOutBufferSize(h, i, format, 1, nullptr, size, "JxlHipBatchOutBufferSize"); }
-JxlDecoderStatus JxlHipBatchSetOutput(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer) { return BatchSetOutput(h, i, format, device_buffer, 1, nullptr, "JxlHipBatchSetOutput"); }
+JxlDecoderStatus JxlHipBatchOutBufferSize(const JxlHipBatch* h, int i, const JxlPixelFormat* format, size_t* size) { return BatchOutBufferSize(h, i, format, 1, nullptr, nullptr, size, "JxlHipBatchOutBufferSize"); }
+JxlDecoderStatus JxlHipBatchSetOutput(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer) { return BatchSetOutput(h, i, format, device_buffer, 1, nullptr, nullptr, "JxlHipBatchSetOutput"); }
 JxlDecoderStatus JxlHipBatchOutBufferSizeScaled(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, size_t* size) {
-  return BatchOutBufferSize(h, i, format, downscale, nullptr, size, "JxlHipBatchOutBufferSizeScaled");
+  return BatchOutBufferSize(h, i, format, downscale, nullptr, nullptr, size, "JxlHipBatchOutBufferSizeScaled");
 }
 JxlDecoderStatus JxlHipBatchSetOutputScaled(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale) {
-  return BatchSetOutput(h, i, format, device_buffer, downscale, nullptr, "JxlHipBatchSetOutputScaled");
+  return BatchSetOutput(h, i, format, device_buffer, downscale, nullptr, nullptr, "JxlHipBatchSetOutputScaled");
 }
 JxlDecoderStatus JxlHipBatchOutBufferSizeLayout(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, size_t* size) {
-  return BatchOutBufferSize(h, i, format, downscale, layout, size, "JxlHipBatchOutBufferSizeLayout");
+  return BatchOutBufferSize(h, i, format, downscale, layout, nullptr, size, "JxlHipBatchOutBufferSizeLayout");
 }
 JxlDecoderStatus JxlHipBatchSetOutputLayout(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout) {
-  return BatchSetOutput(h, i, format, device_buffer, downscale, layout, "JxlHipBatchSetOutputLayout");
+  return BatchSetOutput(h, i, format, device_buffer, downscale, layout, nullptr, "JxlHipBatchSetOutputLayout");
+}
+JxlDecoderStatus JxlHipBatchOutBufferSizeResized(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResize* resize,
+                                                 size_t* size) {
+  return BatchOutBufferSize(h, i, format, downscale, layout, resize, size, "JxlHipBatchOutBufferSizeResized");
+}
+JxlDecoderStatus JxlHipBatchSetOutputResized(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout,
+                                             const JxlHipOutputResize* resize) {
+  return BatchSetOutput(h, i, format, device_buffer, downscale, layout, resize, "JxlHipBatchSetOutputResized");
 }
 void JxlHipBatchSetLaneStride(JxlHipBatch* h, int lf, int hf) {
   auto ok = [](int v) { return v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64; };
@@ -1066,27 +1086,31 @@ JxlHipPipeline* JxlHipPipelineCreate(int device, const JxlHipPipelineOptions* o)
 }
 void JxlHipPipelineDestroy(JxlHipPipeline* h) { if (h) { delete h->p; delete h; } }
 static int64_t PipelineSubmit(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
-                              const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const char* who) {
+                              const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResize* resize, const char* who) {
   if (!DownscaleOk(downscale, who)) return -1;
   try {
     OutputSpec o;
     if (!h || !FormatToSpec(format, &o)) { SetLastError(std::string(who) + ": bad pixel format"); return -1; }
-    if (!ApplyLayout(layout, &o, who)) return -1;
+    if (!ApplyLayout(layout, &o, who) || !ApplyResize(resize, &o, who)) return -1;
     o.downscale = (uint32_t)downscale;
     return h->p->Submit(datas, sizes, n, o, device_out, host_out, out_capacity);
   } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
 }
 int64_t JxlHipPipelineSubmit(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
                              const size_t* out_capacity) {
-  return PipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity, 1, nullptr, "JxlHipPipelineSubmit");
+  return PipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity, 1, nullptr, nullptr, "JxlHipPipelineSubmit");
 }
 int64_t JxlHipPipelineSubmitScaled(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
                                    const size_t* out_capacity, int downscale) {
-  return PipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity, downscale, nullptr, "JxlHipPipelineSubmitScaled");
+  return PipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity, downscale, nullptr, nullptr, "JxlHipPipelineSubmitScaled");
 }
 int64_t JxlHipPipelineSubmitLayout(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
                                    const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout) {
-  return PipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity, downscale, layout, "JxlHipPipelineSubmitLayout");
+  return PipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity, downscale, layout, nullptr, "JxlHipPipelineSubmitLayout");
+}
+int64_t JxlHipPipelineSubmitResized(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                                    const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResize* resize) {
+  return PipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity, downscale, layout, resize, "JxlHipPipelineSubmitResized");
 }
 JxlDecoderStatus JxlHipPipelineWait(JxlHipPipeline* h, int64_t ticket, int* image_status, int n, float* end_ms) {
   try {
@@ -1127,12 +1151,13 @@ size_t JxlHipArenaPoolTrim(void) { return DeviceArenaPoolTrim(); }
 size_t JxlHipArenaPoolHeld(void) { return DeviceArenaPoolHeld(); }
 void JxlHipSchedulerStats(int device, int64_t* jobs, int64_t* images) { SchedulerStats(device, jobs, images); }
 void JxlHipSchedulerShutdown(void) { SchedulerShutdown(); }
-static JxlDecoderStatus ImageOutSize(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, JxlBasicInfo* info, size_t* out_size, const char* who) {
+static JxlDecoderStatus ImageOutSize(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResize* resize,
+                                     JxlBasicInfo* info, size_t* out_size, const char* who) {
   if (!DownscaleOk(downscale, who)) return JXL_DEC_ERROR;
   try {
     OutputSpec o;
     if (!FormatToSpec(format, &o)) { SetLastError("bad pixel format"); return JXL_DEC_ERROR; }
-    if (!ApplyLayout(layout, &o, who)) return JXL_DEC_ERROR;
+    if (!ApplyLayout(layout, &o, who) || !ApplyResize(resize, &o, who)) return JXL_DEC_ERROR;
     o.downscale = (uint32_t)downscale;
     std::shared_ptr<ImageShared> sh(new ImageShared());
     bool have_container = false, has_jbrd = false;
@@ -1147,13 +1172,17 @@ static JxlDecoderStatus ImageOutSize(const uint8_t* data, size_t size, const Jxl
   } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
 }
 JxlDecoderStatus JxlHipImageOutSize(const uint8_t* data, size_t size, const JxlPixelFormat* format, JxlBasicInfo* info, size_t* out_size) {
-  return ImageOutSize(data, size, format, 1, nullptr, info, out_size, "JxlHipImageOutSize");
+  return ImageOutSize(data, size, format, 1, nullptr, nullptr, info, out_size, "JxlHipImageOutSize");
 }
 JxlDecoderStatus JxlHipImageOutSizeScaled(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, JxlBasicInfo* info, size_t* out_size) {
-  return ImageOutSize(data, size, format, downscale, nullptr, info, out_size, "JxlHipImageOutSizeScaled");
+  return ImageOutSize(data, size, format, downscale, nullptr, nullptr, info, out_size, "JxlHipImageOutSizeScaled");
 }
 JxlDecoderStatus JxlHipImageOutSizeLayout(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, JxlBasicInfo* info, size_t* out_size) {
-  return ImageOutSize(data, size, format, downscale, layout, info, out_size, "JxlHipImageOutSizeLayout");
+  return ImageOutSize(data, size, format, downscale, layout, nullptr, info, out_size, "JxlHipImageOutSizeLayout");
+}
+JxlDecoderStatus JxlHipImageOutSizeResized(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResize* resize,
+                                           JxlBasicInfo* info, size_t* out_size) {
+  return ImageOutSize(data, size, format, downscale, layout, resize, info, out_size, "JxlHipImageOutSizeResized");
 }
 
 // the pipelines keep ~15 HIP streams busy at once; the runtime maps streams onto 4 hardware queues by default and kernels of streams that share a queue serialise.

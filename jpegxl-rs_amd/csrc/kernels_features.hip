@@ -474,6 +474,58 @@ __global__ void CopyPlaneKernel(const float* __restrict__ src, uint32_t src_stri
   dst[(size_t)y * dst_stride + x] = src[(size_t)y * src_stride + x];
 }
 
+// ---- resized output (OutputSpec::resize_w / resize_h) --------------------------------------------------------------------------------------
+// Separable antialiased triangle filter over the f32 picture the write stage left (decoder.cc FillOutput): the horizontal pass (kVertical = false) turns the rows of the
+// resampled rectangle into rows of out_w pixels in `tmp`, the vertical pass turns those into the out_w x out_h target and stores it through SlotValue / StoreSample /
+// OutPixelPtr — type, byte order, bit depth, row alignment, planes and scale / bias as for every other output.  The host built each axis' taps (ResizeAxis: first sample,
+// normalised f32 weights); a thread owns one pixel, all NC slots, and walks its taps — as many as the ratio asks for — with one fmaf per tap, the first tap a plain product
+// (a copy at ratio 1 stays bit-exact).  A wavefront is 64 neighbouring pixels of one row: horizontally their tap windows adjoin or overlap, so the wave reads one
+// contiguous stretch of the row and every later tap finds its line in the vector L1; vertically the lanes read 64 neighbouring pixels of the same row of `tmp` per tap and
+// lo / first / weight are wave-uniform.  No LDS, nothing that grows with the ratio but the trip count.
+template <int NC, bool kVertical> __global__ __launch_bounds__(256) void ResizeKernel(ResizeArgs a) {
+  const uint32_t ox = blockIdx.x * 64 + threadIdx.x;
+  if (ox >= a.out_w) return;
+  float acc[NC];
+  if (!kVertical) {
+    const uint32_t lo = a.ax.lo[ox], t0 = a.ax.first[ox], nt = a.ax.first[ox + 1] - t0;
+    const float* __restrict__ wt = a.ax.weight + t0;
+    for (uint32_t y = blockIdx.y * 4 + threadIdx.y; y < a.in_h; y += gridDim.y * 4) {
+      const float* __restrict__ in = a.src + (size_t)(a.y0 + y) * a.src_stride + (size_t)(a.x0 + lo) * NC;
+      const float w0 = wt[0];
+#pragma unroll
+      for (int c = 0; c < NC; c++) acc[c] = w0 * in[c];
+      for (uint32_t j = 1; j < nt; j++) {
+        const float w = wt[j];
+#pragma unroll
+        for (int c = 0; c < NC; c++) acc[c] = fmaf(w, in[(size_t)j * NC + c], acc[c]);
+      }
+      float* __restrict__ out = a.tmp + ((size_t)y * a.out_w + ox) * NC;
+#pragma unroll
+      for (int c = 0; c < NC; c++) out[c] = acc[c];
+    }
+  } else {
+    const uint32_t oy = blockIdx.y * 4 + threadIdx.y;
+    if (oy >= a.out_h) return;
+    const uint32_t lo = a.ay.lo[oy], t0 = a.ay.first[oy], nt = a.ay.first[oy + 1] - t0;
+    const float* __restrict__ wt = a.ay.weight + t0;
+    const size_t pitch = (size_t)a.out_w * NC;
+    const float* __restrict__ in = a.tmp + (size_t)lo * pitch + (size_t)ox * NC;
+    const float w0 = wt[0];
+#pragma unroll
+    for (int c = 0; c < NC; c++) acc[c] = w0 * in[c];
+    for (uint32_t j = 1; j < nt; j++) {
+      const float w = wt[j];
+#pragma unroll
+      for (int c = 0; c < NC; c++) acc[c] = fmaf(w, in[(size_t)j * pitch + c], acc[c]);
+    }
+    const uint32_t bps = a.od.out_type == 0 ? 1 : a.od.out_type == 2 ? 4 : 2;
+    uint8_t* const p = OutPixelPtr(a.od, (int)a.out_w, (int)a.out_h, (int)ox, (int)oy, bps);
+    const size_t step = a.od.planar ? (size_t)a.od.plane_stride : (size_t)bps;
+#pragma unroll
+    for (int c = 0; c < NC; c++) StoreSample(a.od, p + c * step, SlotValue(a.od, c, acc[c]));
+  }
+}
+
 // ---- JPEG reconstruction: coefficients back into JPEG layout --------------------------------------------------------------------------
 __global__ void JpegCoefKernel(const FrameDev* __restrict__ frames, int fidx, JpegCoefArgs a) {
   const FrameDev& f = frames[fidx];
@@ -582,6 +634,21 @@ void LaunchCopyPlane(const float* src, uint32_t src_stride, float* dst, uint32_t
   hipLaunchKernelGGL(CopyPlaneKernel, Grid2(w, h), kBlock2, 0, (hipStream_t)stream, src, src_stride, dst, dst_stride, w, h);
 }
 
+template <int NC> static void LaunchResizeNc(const ResizeArgs& a, hipStream_t st) {
+  const dim3 block(64, 4);
+  const uint32_t gx = (a.out_w + 63) / 64;
+  hipLaunchKernelGGL((ResizeKernel<NC, false>), dim3(gx, std::min<uint32_t>((a.in_h + 3) / 4, 65535u)), block, 0, st, a);
+  hipLaunchKernelGGL((ResizeKernel<NC, true>), dim3(gx, (a.out_h + 3) / 4), block, 0, st, a);
+}
+void LaunchResize(const ResizeArgs& a, void* stream) {
+  if (!a.in_w || !a.in_h || !a.out_w || !a.out_h) return;
+  switch (a.od.out_channels) {
+    case 1: LaunchResizeNc<1>(a, (hipStream_t)stream); break;
+    case 2: LaunchResizeNc<2>(a, (hipStream_t)stream); break;
+    case 3: LaunchResizeNc<3>(a, (hipStream_t)stream); break;
+    default: LaunchResizeNc<4>(a, (hipStream_t)stream); break;
+  }
+}
 void LaunchChromaUpsample(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t hs, uint32_t vs, uint32_t out_w, uint32_t out_h, void* stream) {
   ChromaUpArgs a{src, dst, src_stride, dst_stride, hs, vs, out_w, out_h};
   hipLaunchKernelGGL(ChromaUpsampleKernel, Grid2(out_w, out_h), kBlock2, 0, (hipStream_t)stream, a);

@@ -252,11 +252,11 @@ void Pipeline::PrepareJob(Job* j, int worker) {
       o.device_ptr = j->device_out.empty() ? nullptr : j->device_out[(size_t)i];
       size_t need = 0;
       std::string refusal;
-      try { need = bt.OutputSizeOf(index[(size_t)i], o); } catch (const ParseError& e) { refusal = e.what(); }     // (a plane_stride this image does not fit: Batch::LayoutRefusal)
+      try { need = bt.OutputSizeOf(index[(size_t)i], o); } catch (const ParseError& e) { refusal = e.what(); }     // (a plane_stride this image does not fit, a crop that leaves it: Batch::LayoutRefusal / ResizeRefusal)
       if (!refusal.empty()) {
-        // (stays in the batch like an image whose buffer is too small, with a tight plane of its own)
+        // (stays in the batch like an image whose buffer is too small, with a tight plane of its own and no crop)
         j->result.error[(size_t)i] = refusal;
-        o.device_ptr = nullptr; o.plane_stride = 0;
+        o.device_ptr = nullptr; o.plane_stride = 0; o.crop_x0 = o.crop_y0 = o.crop_w = o.crop_h = 0;
         j->batch_index[(size_t)i] = -2 - index[(size_t)i];
       } else if (!j->capacity.empty() && j->capacity[(size_t)i] < need) {
         // (the image stays in the batch — taking it out would renumber the others — and decodes into a buffer of the batch's own; it is reported as failed)

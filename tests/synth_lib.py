@@ -161,6 +161,61 @@ def encode_modular_free(seed=1, w=64, h=64, nchan=3, has_alpha=False, bits=8, tr
     return _take(out, n)
 
 
+def rct(begin_c, rct_type):
+    """Transform entry of encode_modular_scripted: reversible colour transform of type 0..41 over channels begin_c .. begin_c + 2"""
+    return (0, int(begin_c), int(rct_type), 0, 0, 0)
+
+
+def palette(begin_c, num_c, nb_colors, nb_deltas=0, predictor=0):
+    """Transform entry of encode_modular_scripted: palette over channels begin_c .. begin_c + num_c - 1"""
+    return (1, int(begin_c), int(num_c), int(nb_colors), int(nb_deltas), int(predictor))
+
+
+def split(prop, value, left, right):
+    """Tree node of encode_modular_scripted: property > value ? node `left` : node `right`"""
+    return (int(prop), int(value), int(left), int(right), 0)
+
+
+def leaf(predictor=0, offset=0, mul_log=0, mul_bits=0):
+    """Tree node of encode_modular_scripted: value = token * ((mul_bits + 1) << mul_log) + offset + prediction"""
+    return (-1, int(predictor), int(offset), int(mul_log), int(mul_bits))
+
+
+def encode_modular_scripted(w, h, planes, bits=8, nchan=3, has_alpha=False, group_shift=1, global_transforms=(), local_transforms=(), tree=(leaf(),),
+                            local_tree=False):
+    """Scripted Modular stream (tools/synth_script.h): nothing is random and nothing is simulated — the caller decides everything.
+    bits: 2, 8, 12 or 16; nchan: 1 or 3; group_shift 0..3 (groups of 128 << shift samples a side).
+    global_transforms: up to 4 of rct() / palette(), in stream order (= the order an encoder applies them; a decoder undoes them last to first); begin_c
+      counts meta channels, as the format does.
+    local_transforms: up to 4, written into EVERY section stream.  RCT and plain palettes only: the GPU decoder's section parser takes no Squeeze, no palette
+      with nb_deltas > 0 or a predictor, no palette over (local) meta channels, at most 8 channels before and 12 after the transforms; the writer refuses the
+      same.  They need an image of more than one group.
+    tree: nodes of split() / leaf(), node 0 the root — the global tree, or with local_tree=True a tree of its own in every stream (and no global one).
+    planes: one int array per channel of the CODED channel list, holding the value each token carries (what the decoder multiplies, offsets and adds to its
+      prediction).  The list: the channels after the global transforms, meta channels (palettes: nb_colors wide, num_c high) first; those the GlobalModular
+      section carries come first (every meta channel, then every channel that fits a group); for the others, what the local transforms make of them — local
+      meta channels (one plane, the same in every section), then planes of the image's size.  Planes that do not match the derived list are refused with a message."""
+    L = lib()
+    L.jxlsynth_modular_scripted.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                            C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+
+    def flat(rows, n):
+        v = [int(x) for r in rows for x in r]
+        assert len(v) == n * len(rows)
+        return (C.c_int32 * max(1, len(v)))(*v)
+    keep = [np.ascontiguousarray(np.asarray(p), dtype=np.int32) for p in planes]
+    for p, q in zip(planes, keep):
+        assert np.asarray(p).ndim == 2 and np.array_equal(np.asarray(p), q), "planes are 2-D arrays of int32 values"
+    hdr = (C.c_int32 * 7)(w, h, bits, nchan, 1 if has_alpha else 0, group_shift, 1 if local_tree else 0)
+    ptrs = (C.c_void_p * max(1, len(keep)))(*[p.ctypes.data for p in keep])
+    dims = flat([(p.shape[1], p.shape[0]) for p in keep], 2)
+    out = C.c_void_p(); n = C.c_size_t()
+    if L.jxlsynth_modular_scripted(hdr, flat(global_transforms, 6), len(global_transforms), flat(local_transforms, 6), len(local_transforms), flat(tree, 5), len(tree),
+                                   ptrs, dims, len(keep), C.byref(out), C.byref(n)):
+        raise RuntimeError(L.jxlsynth_last_error().decode())
+    return _take(out, n)
+
+
 def set_icc(icc: bytes = b""):
     """Embed `icc` (an ICC profile) in the image headers written from now on (b"" = back to enumerated colour encodings)."""
     L = lib()

@@ -1726,6 +1726,7 @@ static std::vector<uint8_t> EncodeModular(const int32_t* const* planes, int ncha
 }  // namespace synth
 
 #include "synth_free.h"
+#include "synth_script.h"
 #include "synth_ycbcr.h"
 
 // ---- C API ---------------------------------------------------------------------------------------------------------
@@ -1955,6 +1956,26 @@ int jxlsynth_modular_free(const jxlsynth_free_params* pp, uint8_t** out, size_t*
     p.tree_flags = pp->tree_flags; p.tree_depth = pp->tree_depth; p.local_trees = pp->local_trees; p.lz77 = pp->lz77;
     p.palette = pp->palette; p.nb_colors = pp->nb_colors; p.nb_deltas = pp->nb_deltas; p.pal_pred = pp->pal_pred;
     return finish(synth::EncodeModularFree(p), out, n);
+  } catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
+// Scripted Modular stream (tools/synth_script.h): the caller decides the transforms, the MA tree and the value of every token.
+// hdr: {w, h, bits, nchan, has_alpha, group_shift, local_tree};  gt / lt: 6 ints per transform {id, begin_c, a, b, c, d} (id 0 RCT: a = rct_type; id 1 palette:
+// a = num_c, b = nb_colors, c = nb_deltas, d = predictor);  nodes: 5 ints per node, node 0 the root — inner {property, split, left (property > split), right, 0},
+// leaf {-1, predictor, offset, mul_log, mul_bits};  planes / dims: the coded channel list and the (w, h) the caller gives each plane.
+int jxlsynth_modular_scripted(const int32_t* hdr, const int32_t* gt, int n_gt, const int32_t* lt, int n_lt, const int32_t* nodes, int n_nodes,
+                              const int32_t* const* planes, const int32_t* dims, int n_planes, uint8_t** out, size_t* n) {
+  try {
+    synth::ScriptParams p;
+    p.w = hdr[0]; p.h = hdr[1]; p.bits = hdr[2]; p.nchan = hdr[3]; p.has_alpha = hdr[4]; p.group_shift = hdr[5]; p.local_tree = hdr[6];
+    for (int i = 0; i < n_gt; i++) p.global_t.push_back({gt[6 * i], gt[6 * i + 1], gt[6 * i + 2], gt[6 * i + 3], gt[6 * i + 4], gt[6 * i + 5]});
+    for (int i = 0; i < n_lt; i++) p.local_t.push_back({lt[6 * i], lt[6 * i + 1], lt[6 * i + 2], lt[6 * i + 3], lt[6 * i + 4], lt[6 * i + 5]});
+    for (int i = 0; i < n_nodes; i++) {
+      const int32_t* q = nodes + 5 * i;
+      if (q[0] >= 0) p.tree.add_inner(q[0], q[1], q[2], q[3]);
+      else { const int id = p.tree.add_leaf(q[1]); p.tree.nodes[id].off = q[2]; p.tree.nodes[id].mul_log = q[3]; p.tree.nodes[id].mul_bits = q[4]; }
+    }
+    for (int i = 0; i < n_planes; i++) { p.planes.push_back(planes[i]); p.dims.push_back({dims[2 * i], dims[2 * i + 1]}); }
+    return finish(synth::EncodeModularScripted(p), out, n);
   } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
 }

@@ -1341,7 +1341,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       for (size_t k = 0; k < ne; k++) cb.ecf[k] = take_big(coded);
       if (p.upsampling > 1) { for (int c = 0; c < 3; c++) cb.up[c] = take_big(full); for (size_t k = 0; k < ne; k++) cb.up_ec[k] = take_big(full); }
       if (p.feat.has_noise) for (int c = 0; c < 3; c++) cb.noise[c] = take_big(full);
-      if (ne > 4 && (p.flags & 2)) for (size_t k = 0; k < ne; k++) cb.ec_tmp.push_back(take_big(coded));
+      if (p.flags & 2) for (size_t k = 0; k < ne; k++) cb.ec_tmp.push_back(take_big(coded));
       const bool can_ref = !p.is_last && p.frame_type != 1 && (p.duration == 0 || p.save_as_reference != 0);
       bool replace_all = p.blend.mode == 0;
       for (auto& b : p.ec_blend) if (b.mode != 0) replace_all = false;
@@ -2071,7 +2071,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
   Arena arena(hconst);
   struct Slot { bool valid = false, before_ct = false; size_t p[3] = {0, 0, 0}; uint32_t stride = 0; vec<size_t> ec; uint32_t ec_stride = 0; uint32_t w = 0, h = 0; };
   auto B = [this](size_t off) { return (float*)(dbig_ + off); };
-  // channel tables of the frames with more than four extra channels (kernels.h EcChanDev): a frame's table takes its place in the constant arena when the frame's
+  // channel tables of the frames with extra channels (kernels.h EcChanDev): a frame's table takes its place in the constant arena when the frame's
   // plan starts and is filled step by step; the finished tables are copied into the arena once every frame is planned (the end of this function)
   struct PendingTable { size_t off; vec<EcChanDev> entries; };
   std::deque<PendingTable> tables;
@@ -2081,8 +2081,24 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
     const ImageEntry& first = *images_[pi.first_unit];
     const ImageHeader& ih = first.ih;
     const uint32_t ne = (uint32_t)ih.extra.size();
-    uint32_t premul_mask = 0;
-    for (uint32_t k = 0; k < ne && ne <= 4; k++) if (ih.extra[k].alpha_associated) premul_mask |= 1u << k;   // (the inlined kernels' mask; the channel table carries the flag per entry)
+    bool has_spot = false;
+    for (uint32_t k = 0; k < ne; k++) has_spot |= ih.extra[k].type == 2;
+    const bool render_spots = has_spot && first.out.render_spotcolors;
+    // the write stage's arguments: colour planes, the alpha the caller's layout takes (the picked extra channel, else the first of type alpha), w x h samples
+    auto write_args = [&](const size_t p[3], uint32_t stride, const vec<size_t>& ec, uint32_t ec_stride, uint32_t w, uint32_t h) {
+      WriteArgs wa;
+      memset(&wa, 0, sizeof(wa));
+      for (int c = 0; c < 3; c++) wa.p[c] = B(p[c]);
+      wa.stride = stride;
+      for (uint32_t k = 0; k < ne; k++) if (first.out.alpha_from_extra >= 0 ? (int)k == first.out.alpha_from_extra : ih.extra[k].type == 0) {
+        wa.alpha = B(ec[k]); wa.alpha_stride = ec_stride;
+        wa.unpremul = first.out.unpremul_alpha && ih.extra[k].alpha_associated && (first.out.num_channels == 2 || first.out.num_channels == 4);
+        break;
+      }
+      wa.img_w = w; wa.img_h = h;
+      wa.od = FillOutput(first, dwork_, dbig_);
+      return wa;
+    };
     for (int u = pi.first_unit; u < pi.first_unit + pi.num_units; u++) {
       const ImageEntry& e = *images_[u];
       const FramePlan& p = e.plan;
@@ -2093,18 +2109,11 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
       size_t cur[3]; uint32_t cur_stride = p.bw * 8;
       for (int c = 0; c < 3; c++) cur[c] = (nstages & 1) ? cb.pb[c] : cb.pa[c];
       vec<size_t> cur_ec(ne, 0); uint32_t cur_ec_stride = cw;
-      // more than four extra channels: the extra-channel steps below read a channel table in device memory (kernels.h EcChanDev) instead of pointers inlined
-      // into their argument blocks (`tables` above).
-      const bool tab = ne > 4;
-      vec<EcChanDev> no_table;
-      if (tab) {
-        tables.emplace_back();
-        tables.back().entries.resize(ne);
-        memset(tables.back().entries.data(), 0, ne * sizeof(EcChanDev));
-        tables.back().off = arena.Put(tables.back().entries.data(), ne * sizeof(EcChanDev));
-      }
-      vec<EcChanDev>& tbl = tab ? tables.back().entries : no_table;
-      const size_t o_tab = tab ? tables.back().off : 0;
+      // the extra-channel steps below read the frame's channel table in device memory (`tables` above); without extra channels it is empty and they are skipped
+      tables.emplace_back();
+      vec<EcChanDev>& tbl = tables.back().entries;
+      tbl.assign(ne, EcChanDev{});
+      const size_t o_tab = tables.back().off = arena.Put(tbl.data(), ne * sizeof(EcChanDev));
       auto DT = [this, o_tab]() { return (const EcChanDev*)(dconst_ + o_tab); };
       if (p.subsampled) {
         // the subsampled channels sit in the top-left corner of their planes: bring them to full resolution (plane b)
@@ -2143,23 +2152,21 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         const bool efl = ih.extra[k].depth.is_float;
         const float factor = efl ? 1.0f : 1.0f / (float)((1u << ih.extra[k].depth.bits) - 1);
         const uint32_t ebits = efl ? ih.extra[k].depth.bits : 0, eexp = ih.extra[k].depth.exp_bits;
-        if (tab) {
-          EcChanDev& t = tbl[k];
-          t.src_int = (const int32_t*)(dwork_ + src); t.plane = B(dst); t.factor = factor; t.float_bits = ebits; t.float_exp_bits = eexp;
-          t.premul = ih.extra[k].alpha_associated ? 1 : 0; t.type = ih.extra[k].type;
-          for (int c = 0; c < 4; c++) t.spot[c] = ih.extra[k].spot[c];
-          t.fg = t.plane; t.fg_stride = cw;
-        } else post_ops_.push_back([=](void* st) { LaunchIntToFloat((const int32_t*)(dwork_ + src), cw, B(dst), cw, cw, ch, factor, st, ebits, eexp); });
+        EcChanDev& t = tbl[k];
+        t.src_int = (const int32_t*)(dwork_ + src); t.plane = B(dst); t.factor = factor; t.float_bits = ebits; t.float_exp_bits = eexp;
+        t.premul = ih.extra[k].alpha_associated ? 1 : 0; t.type = ih.extra[k].type;
+        for (int c = 0; c < 4; c++) t.spot[c] = ih.extra[k].spot[c];
+        t.fg = t.plane; t.fg_stride = cw;
         cur_ec[k] = dst;
       }
       EcFrameArgs efa;
       memset(&efa, 0, sizeof(efa));
       efa.num_extra = ne; efa.w = cw; efa.h = ch; efa.ow = fw; efa.oh = fh; efa.up = p.upsampling;
-      if (tab) post_ops_.push_back([=](void* st) { EcFrameArgs a = efa; a.table = DT(); LaunchEcIntToFloat(a, st); });
+      post_ops_.push_back([=](void* st) { EcFrameArgs a = efa; a.table = DT(); LaunchEcIntToFloat(a, st); });
       // ---- patches
       if (p.flags & 2) {
         vec<PatchEntryDev> entries;
-        vec<PatchEcDev> pec;        // channel-table form: [placement * ne + channel]
+        vec<PatchEcDev> pec;        // [placement * ne + channel]
         for (const PatchRefH& pr : p.feat.patches) {
           const Slot& sl = slots[pr.ref];
           if (!sl.valid) throw ParseError("patch refers to an empty reference slot", false);
@@ -2177,12 +2184,12 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
               const float* esrc = B(sl.ec[k]) + (size_t)pr.y0 * sl.ec_stride + pr.x0;
               const uint32_t mode = pp.blend[1 + k].mode | (pp.blend[1 + k].alpha_channel << 8) | (pp.blend[1 + k].clamp << 16);
               if (pp.blend[1 + k].alpha_channel >= ne) throw ParseError("patch alpha channel", false);
-              if (tab) pec.push_back(PatchEcDev{esrc, mode, 0}); else { en.esrc[k] = esrc; en.mode[1 + k] = mode; }
+              pec.push_back(PatchEcDev{esrc, mode, 0});
             }
             if (ne && pp.blend[0].alpha_channel >= ne) throw ParseError("patch alpha channel", false);
             en.src_stride = sl.stride; en.esrc_stride = sl.ec_stride;
             en.x = (int32_t)pp.x; en.y = (int32_t)pp.y; en.xs = pr.xsize; en.ys = pr.ysize;
-            en.mode[0] = pp.blend[0].mode | (pp.blend[0].alpha_channel << 8) | (pp.blend[0].clamp << 16);
+            en.mode = pp.blend[0].mode | (pp.blend[0].alpha_channel << 8) | (pp.blend[0].clamp << 16);
             entries.push_back(en);
           }
         }
@@ -2204,16 +2211,13 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
           PatchFrameArgs pa;
           memset(&pa, 0, sizeof(pa));
           for (int c = 0; c < 3; c++) pa.p[c] = B(cur[c]);
-          for (uint32_t k = 0; k < ne && !tab; k++) pa.ec[k] = B(cur_ec[k]);
-          pa.stride = cur_stride; pa.ec_stride = cur_ec_stride; pa.w = cw; pa.h = ch; pa.num_extra = ne; pa.premul_mask = premul_mask;
-          if (tab) {
-            if (cb.ec_tmp.size() < ne) throw ParseError("patch planes of the extra channels", false);
-            for (uint32_t k = 0; k < ne; k++) tbl[k].tmp = B(cb.ec_tmp[k]);
-            const size_t o_p = arena.Put(pec.data(), pec.size() * sizeof(PatchEcDev));
-            post_ops_.push_back([=](void* st) {
-              LaunchPatchesTable(pa, DT(), (const PatchEntryDev*)(dconst_ + o_e), (const PatchEcDev*)(dconst_ + o_p), (const uint32_t*)(dconst_ + o_s), (const uint32_t*)(dconst_ + o_l), st);
-            });
-          } else post_ops_.push_back([=](void* st) { LaunchPatches(pa, (const PatchEntryDev*)(dconst_ + o_e), (const uint32_t*)(dconst_ + o_s), (const uint32_t*)(dconst_ + o_l), st); });
+          pa.stride = cur_stride; pa.ec_stride = cur_ec_stride; pa.w = cw; pa.h = ch; pa.num_extra = ne;
+          if (cb.ec_tmp.size() < ne) throw ParseError("patch planes of the extra channels", false);
+          for (uint32_t k = 0; k < ne; k++) tbl[k].tmp = B(cb.ec_tmp[k]);
+          const size_t o_p = arena.Put(pec.data(), pec.size() * sizeof(PatchEcDev));
+          post_ops_.push_back([=](void* st) {
+            LaunchPatches(pa, DT(), (const PatchEntryDev*)(dconst_ + o_e), (const PatchEcDev*)(dconst_ + o_p), (const uint32_t*)(dconst_ + o_s), (const uint32_t*)(dconst_ + o_l), st);
+          });
         }
       }
       // ---- splines (segments from the host, host_features.cc)
@@ -2239,12 +2243,10 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
           cur[c] = dst;
         }
         for (uint32_t k = 0; k < ne; k++) {
-          const size_t src = cur_ec[k], dst = cb.up_ec[k];
-          if (tab) { tbl[k].up = B(dst); tbl[k].fg = tbl[k].up; tbl[k].fg_stride = fw; }
-          else post_ops_.push_back([=](void* st) { LaunchUpsamplePlane(B(src), cw, cw, ch, B(dst), fw, fw, fh, up, (const float*)(dconst_ + o_w), st); });
-          cur_ec[k] = dst;
+          tbl[k].up = B(cb.up_ec[k]); tbl[k].fg = tbl[k].up; tbl[k].fg_stride = fw;
+          cur_ec[k] = cb.up_ec[k];
         }
-        if (tab) post_ops_.push_back([=](void* st) { EcFrameArgs a = efa; a.table = DT(); a.up_weights = (const float*)(dconst_ + o_w); LaunchEcUpsample(a, st); });
+        post_ops_.push_back([=](void* st) { EcFrameArgs a = efa; a.table = DT(); a.up_weights = (const float*)(dconst_ + o_w); LaunchEcUpsample(a, st); });
         cur_stride = fw; cur_ec_stride = fw;
       }
       // ---- noise
@@ -2280,11 +2282,9 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
       }
       if (p.frame_type == 2) continue;    // reference-only frames are not displayed
       // ---- colour transform into the output space
-      bool has_spot = false;
-      for (uint32_t k = 0; k < ne; k++) if (ih.extra[k].type == 2) has_spot = true;
       bool blends = p.have_crop || p.blend.mode != 0;
       for (auto& b : p.ec_blend) if (b.mode != 0) blends = true;
-      const bool spot_after_linear = has_spot && first.out.render_spotcolors && p.is_last && !blends;
+      const bool spot_after_linear = render_spots && p.is_last && !blends;
       ColorArgs deferred_tf;
       memset(&deferred_tf, 0, sizeof(deferred_tf));
       bool have_deferred_tf = false;
@@ -2314,17 +2314,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
       if (first.out.only_frame >= 0 && u == pi.first_unit + first.out.only_frame) {
         // ---- non-coalesced output (JxlDecoderSetCoalescing(false)): this frame's own pixels after the colour transform, frame-sized, not
         // blended; the frames before it have been composed as usual (it may draw patches from them), the ones after it are not needed
-        WriteArgs wa;
-        memset(&wa, 0, sizeof(wa));
-        for (int c = 0; c < 3; c++) wa.p[c] = B(cur[c]);
-        wa.stride = cur_stride;
-        for (uint32_t k = 0; k < ne; k++) if (first.out.alpha_from_extra >= 0 ? (int)k == first.out.alpha_from_extra : ih.extra[k].type == 0) {
-          wa.alpha = B(cur_ec[k]); wa.alpha_stride = cur_ec_stride;
-          wa.unpremul = first.out.unpremul_alpha && ih.extra[k].alpha_associated && (first.out.num_channels == 2 || first.out.num_channels == 4);
-          break;
-        }
-        wa.img_w = fw; wa.img_h = fh;
-        wa.od = FillOutput(first, dwork_, dbig_);
+        const WriteArgs wa = write_args(cur, cur_stride, cur_ec, cur_ec_stride, fw, fh);
         if (have_deferred_tf) {          // (the transfer function had been put off for a spot-colour stage this output does not run)
           ColorArgs ta = deferred_tf;
           for (int c = 0; c < 3; c++) { ta.src[c] = B(cur[c]); ta.dst[c] = B(cur[c]); }
@@ -2355,12 +2345,11 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         BlendArgs ba;
         memset(&ba, 0, sizeof(ba));
         for (int c = 0; c < 3; c++) { ba.fg[c] = B(cur[c]); ba.canvas[c] = B(cb.canvas[c]); }
-        for (uint32_t k = 0; k < ne && !tab; k++) { ba.fg_ec[k] = B(cur_ec[k]); ba.canvas_ec[k] = B(cb.canvas_ec[k]); }
-        ba.fg_stride = cur_stride; ba.fg_ec_stride = cur_ec_stride; ba.fw = fw; ba.fh = fh; ba.x0 = p.x0; ba.y0 = p.y0;
-        ba.canvas_stride = ih.xsize; ba.canvas_ec_stride = ih.xsize; ba.img_w = ih.xsize; ba.img_h = ih.ysize; ba.num_extra = ne; ba.premul_mask = premul_mask;
+        ba.fg_stride = cur_stride; ba.fw = fw; ba.fh = fh; ba.x0 = p.x0; ba.y0 = p.y0;
+        ba.canvas_stride = ih.xsize; ba.img_w = ih.xsize; ba.img_h = ih.ysize; ba.num_extra = ne;
         const Slot* bg = source(p.blend.source);
         if (bg) { for (int c = 0; c < 3; c++) ba.bg[c] = B(bg->p[c]); ba.bg_stride = bg->stride; }
-        ba.mode[0] = p.blend.mode | (p.blend.alpha_channel << 8) | ((uint32_t)p.blend.clamp << 16);
+        ba.mode = p.blend.mode | (p.blend.alpha_channel << 8) | ((uint32_t)p.blend.clamp << 16);
         if (p.blend.mode == 2 || p.blend.mode == 3) {
           if (ne == 0) throw ParseError("alpha blending without extra channels", false);
           if (p.blend.alpha_channel >= ne) throw ParseError("blend alpha channel", false);
@@ -2372,17 +2361,11 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
           if (bi.alpha_channel >= ne) throw ParseError("blend alpha channel", false);
           const Slot* eb = source(bi.source);
           if (eb && eb->ec.size() < ne) throw ParseError("blending source without the extra channels", false);
-          if (tab) {
-            EcChanDev& t = tbl[k];
-            t.mode = mode; t.canvas = B(cb.canvas_ec[k]); t.canvas_stride = ih.xsize;
-            if (eb) { t.bg = B(eb->ec[k]); t.bg_alpha = B(eb->ec[bi.alpha_channel]); t.bg_stride = eb->ec_stride; }
-            continue;
-          }
-          ba.mode[1 + k] = mode;
-          if (eb) { ba.bg_ec[k] = B(eb->ec[k]); ba.bg_ec_alpha[k] = B(eb->ec[bi.alpha_channel]); ba.bg_ec_stride[k] = eb->ec_stride; }
+          EcChanDev& t = tbl[k];
+          t.mode = mode; t.canvas = B(cb.canvas_ec[k]); t.canvas_stride = ih.xsize;
+          if (eb) { t.bg = B(eb->ec[k]); t.bg_alpha = B(eb->ec[bi.alpha_channel]); t.bg_stride = eb->ec_stride; }
         }
-        if (tab) post_ops_.push_back([=](void* st) { LaunchBlendTable(ba, DT(), st); });
-        else post_ops_.push_back([=](void* st) { LaunchBlend(ba, st); });
+        post_ops_.push_back([=](void* st) { LaunchBlend(ba, DT(), st); });
         for (int c = 0; c < 3; c++) canvas[c] = cb.canvas[c];
         for (uint32_t k = 0; k < ne; k++) canvas_ec[k] = cb.canvas_ec[k];
         canvas_stride = ih.xsize; canvas_ec_stride = ih.xsize;
@@ -2401,25 +2384,13 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
       const bool deliver = all_frames ? slot >= 0 : (first.out.upto_frame >= 0 ? u == pi.first_unit + first.out.upto_frame : p.is_last);
       if (!deliver) continue;
       if (all_frames) {   // (delivery must leave the canvas as it is: the frames behind blend onto it)
-        bool spot = false;
-        for (uint32_t k = 0; k < ne; k++) spot |= ih.extra[k].type == 2 && first.out.render_spotcolors;
-        if (spot || have_deferred_tf) throw ParseError("unsupported: all frames of an animation in one decode with spot colours to render", true);
+        if (render_spots || have_deferred_tf) throw ParseError("unsupported: all frames of an animation in one decode with spot colours to render", true);
       }
       // ---- spot colours (stage_spot.cc): colour = mix * spot + (1 - mix) * colour with mix = solidity * channel, channel by channel
-      if (first.out.render_spotcolors && tab) {
-        bool any_spot = false;
-        for (uint32_t k = 0; k < ne; k++) any_spot |= ih.extra[k].type == 2;
+      if (render_spots) {
         const size_t c0 = canvas[0], c1 = canvas[1], c2 = canvas[2];
         const uint32_t use_canvas = needs_blending ? 1 : 0, iw = ih.xsize, ihh = ih.ysize;
-        if (any_spot) post_ops_.push_back([=](void* st) { float* pl[3] = {B(c0), B(c1), B(c2)}; LaunchSpotTable(pl, canvas_stride, DT(), ne, use_canvas, iw, ihh, st); });
-      } else if (first.out.render_spotcolors) {
-        for (uint32_t k = 0; k < ne; k++) {
-          if (ih.extra[k].type != 2) continue;
-          SpotArgs sa;
-          for (int c = 0; c < 3; c++) { sa.p[c] = B(canvas[c]); sa.color[c] = ih.extra[k].spot[c]; }
-          sa.stride = canvas_stride; sa.spot = B(canvas_ec[k]); sa.spot_stride = canvas_ec_stride; sa.scale = ih.extra[k].spot[3]; sa.w = ih.xsize; sa.h = ih.ysize;
-          post_ops_.push_back([=](void* st) { LaunchSpot(sa, st); });
-        }
+        post_ops_.push_back([=](void* st) { float* pl[3] = {B(c0), B(c1), B(c2)}; LaunchSpot(pl, canvas_stride, DT(), ne, use_canvas, iw, ihh, st); });
       }
       if (have_deferred_tf) {
         ColorArgs ta = deferred_tf;
@@ -2428,24 +2399,14 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
         post_ops_.push_back([=](void* st) { LaunchColor(ta, st); });
       }
       // ---- write stage
-      WriteArgs wa;
-      memset(&wa, 0, sizeof(wa));
-      for (int c = 0; c < 3; c++) wa.p[c] = B(canvas[c]);
-      wa.stride = canvas_stride;
-      for (uint32_t k = 0; k < ne; k++) if (first.out.alpha_from_extra >= 0 ? (int)k == first.out.alpha_from_extra : ih.extra[k].type == 0) {
-        wa.alpha = B(canvas_ec[k]); wa.alpha_stride = canvas_ec_stride;
-        wa.unpremul = first.out.unpremul_alpha && ih.extra[k].alpha_associated && (first.out.num_channels == 2 || first.out.num_channels == 4);
-        break;
-      }
-      wa.img_w = ih.xsize; wa.img_h = ih.ysize;
-      wa.od = FillOutput(first, dwork_, dbig_);
+      WriteArgs wa = write_args(canvas, canvas_stride, canvas_ec, canvas_ec_stride, ih.xsize, ih.ysize);
       if (all_frames) wa.od.out += (size_t)slot * (first.out_size + 64);
       post_ops_.push_back([=](void* st) { LaunchWrite(wa, st); });
       if (all_frames && slot + 1 < (int)first.deliver_frames.size()) continue;
       break;                      // (frames behind the delivered one: nothing of theirs is needed)
     }
   }
-  for (const PendingTable& t : tables) memcpy(hconst.data() + t.off, t.entries.data(), t.entries.size() * sizeof(EcChanDev));
+  for (const PendingTable& t : tables) if (!t.entries.empty()) memcpy(hconst.data() + t.off, t.entries.data(), t.entries.size() * sizeof(EcChanDev));
 }
 
 void Batch::EnqueuePostOps(void* stream) { for (auto& op : post_ops_) op(stream); }

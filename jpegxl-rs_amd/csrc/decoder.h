@@ -221,7 +221,7 @@ class Batch {
   struct ComplexBufs {      // big-arena offsets of one complex unit ((size_t)-1: not allocated)
     size_t up[3], noise[3], rgb[3], canvas[3], pa[3], pb[3];
     vec<size_t> ecf, up_ec, canvas_ec;   // per extra channel: float planes (coded size), upsampled, blended onto the canvas
-    vec<size_t> ec_tmp;                  // more than four extra channels + patches: one plane per channel the patch kernel parks new values in
+    vec<size_t> ec_tmp;                  // frames with patches: one plane (coded size) per extra channel, where the patch kernel parks new values
     vec<size_t> ec_int;     // work-arena offsets of the decoded extra channels (int32, coded size)
     size_t color_int[3];            // Modular frames: work-arena offsets of the colour channels after the inverse transforms
     uint32_t nb_color_int = 0;

@@ -253,25 +253,10 @@ void LaunchModPaletteDelta(const int32_t* pal, int32_t* const* out, uint32_t nb_
 void LaunchModOutput(const FrameDev* frames, int fidx, const ModOutputArgs& a, int w, int h, void* stream);
 
 // ---- frame tail of images with several frames or image features (kernels_features.hip); explicit arguments, device pointers ----
+// The three colour planes travel in the argument blocks.  A frame's extra channels — any number of them — are described by a per-frame channel table in device
+// memory (EcChanDev, built by Batch::PlanPostOps in the constant arena); the per-channel kernels run over (channel, y, x) with the channel on blockIdx.z, so a
+// table entry is wave-uniform.  A frame without extra channels has no table and its extra-channel launches are skipped.
 struct SplineSegmentDev;   // host_parse.h
-// One placement of a patch: source rectangle (pointers already at its top-left sample) -> frame position (x, y).
-// mode[k] = PatchBlendMode | alpha channel << 8 | clamp << 16 for k = 0 (colour), 1 + e (extra channel e)
-struct PatchEntryDev { const float* src[3]; const float* esrc[4]; uint32_t src_stride, esrc_stride; int32_t x, y; uint32_t xs, ys; uint32_t mode[5]; uint32_t pad; };
-struct PatchFrameArgs { float* p[3]; float* ec[4]; uint32_t stride, ec_stride, w, h, num_extra, premul_mask; };
-struct NoiseArgs { float* p[3]; uint32_t stride, w, h; float* noise[3]; uint32_t noise_stride, group_dim, visible_frame_index, nonvisible_frame_index; float lut[8]; float ytox, ytob; };
-// mode: 3 = transfer function only (after a spot-colour stage in linear light); 0 XYB -> linear -> transfer function (tf_kind: FrameDev::color_mode's values 0, 1, 4..7), 1 YCbCr -> RGB, 2 copy
-struct ColorArgs { const float* src[3]; float* dst[3]; uint32_t src_stride, dst_stride, w, h, mode, tf_kind; float inverse_gamma, opsin_inv[9], neg_bias[3], neg_bias_cbrt[3], hdr_par[5]; };
-// mode[k] = BlendMode | alpha channel << 8 | clamp << 16; bg pointers are null when the source slot is empty (treated as zeros)
-struct BlendArgs {
-  const float* fg[3]; const float* fg_ec[4]; uint32_t fg_stride, fg_ec_stride, fw, fh; int32_t x0, y0;
-  const float* bg[3]; uint32_t bg_stride; const float* bg_alpha; uint32_t bg_alpha_stride;
-  const float* bg_ec[4]; const float* bg_ec_alpha[4]; uint32_t bg_ec_stride[4];
-  float* canvas[3]; float* canvas_ec[4]; uint32_t canvas_stride, canvas_ec_stride, img_w, img_h, num_extra, premul_mask; uint32_t mode[5];
-};
-struct WriteArgs { const float* p[3]; const float* alpha; uint32_t stride, alpha_stride, img_w, img_h, unpremul; OutputDesc od; };
-// ---- images with more than four extra channels: the extra-channel half of the frame tail reads a per-frame channel table in device memory
-// (built by Batch::PlanPostOps) instead of pointers inlined into the argument blocks above; the kernels run over (channel, y, x) with the
-// channel on blockIdx.z.  Per-sample arithmetic is that of the inlined forms (shared device functions).
 struct EcChanDev {
   const int32_t* src_int;            // decoded samples (coded size, row stride = coded width)
   float* plane;                      // float samples, coded size
@@ -289,31 +274,40 @@ struct EcChanDev {
   uint32_t type;                     // ExtraChannelType (2 = spot colour)
   float spot[4];                     // spot colour and solidity
 };
-// per placement of a patch and extra channel: source plane (at the patch's top-left sample) and PatchBlendMode | alpha channel << 8 | clamp << 16
-struct PatchEcDev { const float* src; uint32_t mode, pad; };
 struct EcFrameArgs { const EcChanDev* table; uint32_t num_extra, w, h, ow, oh, up; const float* up_weights; };
 void LaunchEcIntToFloat(const EcFrameArgs& a, void* stream);      // table[c].src_int -> table[c].plane, w x h
 void LaunchEcUpsample(const EcFrameArgs& a, void* stream);        // table[c].plane (w x h) -> table[c].up (ow x oh)
-// patches of a frame with a channel table: PatchEntryDev::esrc / mode[1..] are not read, `pec` holds [placement * num_extra + channel]
-void LaunchPatchesTable(const PatchFrameArgs& a, const EcChanDev* table, const PatchEntryDev* entries, const PatchEcDev* pec, const uint32_t* tile_start,
-                        const uint32_t* tile_list, void* stream);
-// blending with a channel table: the colour kernel takes fg / bg / canvas / mode[0] of `a` and its alpha through the table (bg_alpha of `a`: the colour
-// source's alpha plane); the extra-channel kernel reads foreground planes and the sources' planes only, never a canvas plane
-void LaunchBlendTable(const BlendArgs& a, const EcChanDev* table, void* stream);
-// spot colours in header order, channel after channel per pixel (the mix is order-dependent)
-void LaunchSpotTable(float* const p[3], uint32_t stride, const EcChanDev* table, uint32_t num_extra, uint32_t use_canvas, uint32_t w, uint32_t h, void* stream);   // use_canvas: the blended planes (else fg)
+// One placement of a patch: source rectangle (pointers already at its top-left sample) -> frame position (x, y); mode = PatchBlendMode | alpha channel << 8 | clamp << 16
+// of the colour.  Per placement and extra channel, PatchEcDev [placement * num_extra + channel]: source plane (at the same sample) and the channel's mode word.
+struct PatchEntryDev { const float* src[3]; uint32_t src_stride, esrc_stride; int32_t x, y; uint32_t xs, ys; uint32_t mode, pad; };
+struct PatchEcDev { const float* src; uint32_t mode, pad; };
+struct PatchFrameArgs { float* p[3]; uint32_t stride, ec_stride, w, h, num_extra; };
+struct NoiseArgs { float* p[3]; uint32_t stride, w, h; float* noise[3]; uint32_t noise_stride, group_dim, visible_frame_index, nonvisible_frame_index; float lut[8]; float ytox, ytob; };
+// mode: 3 = transfer function only (after a spot-colour stage in linear light); 0 XYB -> linear -> transfer function (tf_kind: FrameDev::color_mode's values 0, 1, 4..7), 1 YCbCr -> RGB, 2 copy
+struct ColorArgs { const float* src[3]; float* dst[3]; uint32_t src_stride, dst_stride, w, h, mode, tf_kind; float inverse_gamma, opsin_inv[9], neg_bias[3], neg_bias_cbrt[3], hdr_par[5]; };
+// Blending of the colour: mode = BlendMode | alpha channel << 8 | clamp << 16; bg pointers are null when the source slot is empty (treated as zeros); bg_alpha: the colour
+// source's plane of the alpha channel.  The foreground alpha and every extra channel go through the table.
+struct BlendArgs {
+  const float* fg[3]; uint32_t fg_stride, fw, fh; int32_t x0, y0;
+  const float* bg[3]; uint32_t bg_stride; const float* bg_alpha; uint32_t bg_alpha_stride;
+  float* canvas[3]; uint32_t canvas_stride, img_w, img_h, num_extra, mode;
+};
+struct WriteArgs { const float* p[3]; const float* alpha; uint32_t stride, alpha_stride, img_w, img_h, unpremul; OutputDesc od; };
 void LaunchIntToFloat(const int32_t* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t w, uint32_t h, float factor, void* stream, uint32_t float_bits = 0,
                       uint32_t float_exp_bits = 0);   // float_bits != 0: the integers are float bit patterns (IntToFloatSample)
 void LaunchXybModToFloat(const int32_t* cy, const int32_t* cx, const int32_t* cb, uint32_t src_stride, float* const dst[3], uint32_t dst_stride, uint32_t w, uint32_t h, const float fac[3], void* stream);
-void LaunchPatches(const PatchFrameArgs& a, const PatchEntryDev* entries, const uint32_t* tile_start, const uint32_t* tile_list, void* stream);
+// table / pec: null for a frame without extra channels
+void LaunchPatches(const PatchFrameArgs& a, const EcChanDev* table, const PatchEntryDev* entries, const PatchEcDev* pec, const uint32_t* tile_start, const uint32_t* tile_list,
+                   void* stream);
 void LaunchSplines(float* const p[3], uint32_t stride, uint32_t w, uint32_t h, const SplineSegmentDev* segs, const uint32_t* row_start, const uint32_t* indices, void* stream);
 void LaunchUpsamplePlane(const float* src, uint32_t src_stride, uint32_t w, uint32_t h, float* dst, uint32_t dst_stride, uint32_t ow, uint32_t oh, uint32_t up, const float* weights, void* stream);
 void LaunchNoise(const NoiseArgs& a, void* stream);
 void LaunchColor(const ColorArgs& a, void* stream);
-// stage_spot.cc: p[c] = mix * color[c] + (1 - mix) * p[c], mix = scale * spot
-struct SpotArgs { float* p[3]; const float* spot; uint32_t stride, spot_stride, w, h; float color[3], scale; };
-void LaunchSpot(const SpotArgs& a, void* stream);
-void LaunchBlend(const BlendArgs& a, void* stream);
+// the colour kernel, then the extra channels' (it reads foreground planes and the sources' planes only, never a canvas plane)
+void LaunchBlend(const BlendArgs& a, const EcChanDev* table, void* stream);
+// stage_spot.cc: p[c] = mix * color[c] + (1 - mix) * p[c], mix = solidity * plate, for the spot-colour channels in header order, channel after channel per pixel (the
+// mix is order-dependent); use_canvas: the plates are the blended planes (else fg)
+void LaunchSpot(float* const p[3], uint32_t stride, const EcChanDev* table, uint32_t num_extra, uint32_t use_canvas, uint32_t w, uint32_t h, void* stream);
 void LaunchWrite(const WriteArgs& a, void* stream);
 // JPEG reconstruction: quantised coefficients of a JPEG-transcoded frame in JPEG layout — component c (0 Y, 1 Cb, 2 Cr), block raster
 // order, 64 coefficients in natural (row-major) order: DC from the quantised LF image, AC from the coefficient planes with the integer

@@ -85,46 +85,12 @@ __device__ __forceinline__ float PatchBlendAlpha(uint32_t mode, bool clamp, floa
 }
 
 // One workgroup per 32x32 tile of the frame; the tile's list names, in dictionary order, the patch placements that touch it, so
-// every pixel sees its patches in the order libjxl applies them (float additions do not commute).
-__global__ __launch_bounds__(256) void PatchKernel(PatchFrameArgs a, const PatchEntryDev* __restrict__ entries, const uint32_t* __restrict__ tile_start,
+// every pixel sees its patches in the order libjxl applies them (float additions do not commute).  An extra channel's new value goes
+// to its `tmp` plane first and comes back once every channel and the colour of the pixel have read the values from before the patch:
+// the alpha a blending refers to may be any channel, also one that the same patch changes.
+__global__ __launch_bounds__(256) void PatchKernel(PatchFrameArgs a, const EcChanDev* __restrict__ table, const PatchEntryDev* __restrict__ entries,
+                                                   const PatchEcDev* __restrict__ pec, const uint32_t* __restrict__ tile_start,
                                                    const uint32_t* __restrict__ tile_list, uint32_t tiles_x) {
-  const uint32_t tile = blockIdx.x;
-  const uint32_t begin = tile_start[tile], end = tile_start[tile + 1];
-  if (begin == end) return;
-  const uint32_t tx = tile % tiles_x, ty = tile / tiles_x;
-  for (uint32_t t = threadIdx.x; t < 1024; t += blockDim.x) {
-    const int x = (int)(tx * 32 + (t & 31)), y = (int)(ty * 32 + (t >> 5));
-    if (x >= (int)a.w || y >= (int)a.h) continue;
-    const size_t fo = (size_t)y * a.stride + x, eo = (size_t)y * a.ec_stride + x;
-    for (uint32_t k = begin; k < end; k++) {
-      const PatchEntryDev& e = entries[tile_list[k]];
-      const int ix = x - e.x, iy = y - e.y;
-      if (ix < 0 || iy < 0 || ix >= (int)e.xs || iy >= (int)e.ys) continue;
-      const size_t so = (size_t)iy * e.src_stride + ix, seo = (size_t)iy * e.esrc_stride + ix;
-      const uint32_t m0 = e.mode[0] & 0xFF, a0 = (e.mode[0] >> 8) & 0xFF; const bool c0 = (e.mode[0] >> 16) & 1;
-      float fa = 1.0f, pa = 1.0f; bool premul = false;
-      if (m0 >= 4) { fa = a.ec[a0][eo]; pa = e.esrc[a0][seo]; premul = (a.premul_mask >> a0) & 1; }
-      float ec_out[4];
-      for (uint32_t c = 0; c < a.num_extra; c++) {
-        const uint32_t m = e.mode[1 + c] & 0xFF, ac = (e.mode[1 + c] >> 8) & 0xFF; const bool cl = (e.mode[1 + c] >> 16) & 1;
-        const float fv = a.ec[c][eo], pv = e.esrc[c][seo];
-        float efa = 1.0f, epa = 1.0f;
-        if (m >= 4) { efa = a.ec[ac][eo]; epa = e.esrc[ac][seo]; }
-        if (m >= 4 && ac == c) ec_out[c] = PatchBlendAlpha(m, cl, efa, epa);
-        else ec_out[c] = PatchBlendSample(m, cl, m >= 4 ? ((a.premul_mask >> ac) & 1) != 0 : false, fv, pv, efa, epa);
-      }
-      for (int c = 0; c < 3; c++) a.p[c][fo] = PatchBlendSample(m0, c0, premul, a.p[c][fo], e.src[c][so], fa, pa);
-      for (uint32_t c = 0; c < a.num_extra; c++) a.ec[c][eo] = ec_out[c];
-    }
-  }
-}
-
-// The same for a frame with a channel table (more than four extra channels).  A channel's new value goes to its `tmp` plane first and comes
-// back once every channel and the colour of the pixel have read the values from before the patch: the alpha a blending refers to may be any
-// channel, also one that the same patch changes.
-__global__ __launch_bounds__(256) void PatchTableKernel(PatchFrameArgs a, const EcChanDev* __restrict__ table, const PatchEntryDev* __restrict__ entries,
-                                                        const PatchEcDev* __restrict__ pec, const uint32_t* __restrict__ tile_start,
-                                                        const uint32_t* __restrict__ tile_list, uint32_t tiles_x) {
   const uint32_t tile = blockIdx.x;
   const uint32_t begin = tile_start[tile], end = tile_start[tile + 1];
   if (begin == end) return;
@@ -140,7 +106,7 @@ __global__ __launch_bounds__(256) void PatchTableKernel(PatchFrameArgs a, const 
       const int ix = x - e.x, iy = y - e.y;
       if (ix < 0 || iy < 0 || ix >= (int)e.xs || iy >= (int)e.ys) continue;
       const size_t so = (size_t)iy * e.src_stride + ix, seo = (size_t)iy * e.esrc_stride + ix;
-      const uint32_t m0 = e.mode[0] & 0xFF, a0 = (e.mode[0] >> 8) & 0xFF; const bool c0 = (e.mode[0] >> 16) & 1;
+      const uint32_t m0 = e.mode & 0xFF, a0 = (e.mode >> 8) & 0xFF; const bool c0 = (e.mode >> 16) & 1;
       float fa = 1.0f, pa = 1.0f; bool premul = false;
       if (m0 >= 4) { fa = table[a0].plane[eo]; pa = pe[a0].src[seo]; premul = table[a0].premul != 0; }
       for (uint32_t c = 0; c < a.num_extra; c++) {
@@ -196,7 +162,7 @@ __global__ void UpsamplePlaneKernel(const float* __restrict__ src, uint32_t src_
   if (ox >= ow || oy >= oh) return;
   dst[(size_t)oy * dst_stride + ox] = UpsampleSample([&](int x, int y) { return src[(size_t)y * src_stride + x]; }, w, h, ox, oy, up, weights);
 }
-// ---- the same two steps for every extra channel of a frame with a channel table: channel on blockIdx.z (the table entry is wave-uniform)
+// ---- the same two steps for every extra channel of a frame: channel on blockIdx.z (the table entry is wave-uniform)
 __global__ void EcIntToFloatKernel(EcFrameArgs a) {
   const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
   if (x >= a.w || y >= a.h) return;
@@ -306,15 +272,6 @@ __global__ void ColorKernel(ColorArgs a) {
   a.dst[0][di] = r; a.dst[1][di] = g; a.dst[2][di] = b;
 }
 
-__global__ void SpotKernel(SpotArgs a) {
-  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-  if (x >= a.w || y >= a.h) return;
-  const float mix = a.scale * a.spot[(size_t)y * a.spot_stride + x];
-  const size_t o = (size_t)y * a.stride + x;
-#pragma unroll
-  for (int c = 0; c < 3; c++) a.p[c][o] = mix * a.color[c] + (1.0f - mix) * a.p[c][o];
-}
-
 // ---- chroma upsampling of subsampled YCbCr frames (stage_chroma_upsampling.cc: SubsampledSample), one thread per output sample
 struct ChromaUpArgs { const float* src; float* dst; uint32_t src_stride, dst_stride, hs, vs, out_w, out_h; };
 __global__ void ChromaUpsampleKernel(ChromaUpArgs a) {
@@ -344,47 +301,8 @@ __device__ __forceinline__ float FrameBlendAlphaD(uint32_t mode, bool clamp, flo
   const float fa = clamp ? Clamp01(fga) : fga;
   return mode == 2 ? 1.0f - (1.0f - fa) * (1.0f - bga) : bga;
 }
-__global__ void BlendKernel(BlendArgs a) {
-  const int X = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y * blockDim.y + threadIdx.y;
-  if (X >= (int)a.img_w || Y >= (int)a.img_h) return;
-  const size_t co = (size_t)Y * a.canvas_stride + X, ceo = (size_t)Y * a.canvas_ec_stride + X;
-  const size_t bo = (size_t)Y * a.bg_stride + X;
-  const int fx = X - a.x0, fy = Y - a.y0;
-  const bool inside = fx >= 0 && fy >= 0 && fx < (int)a.fw && fy < (int)a.fh;
-  if (!inside) {
-    for (int c = 0; c < 3; c++) a.canvas[c][co] = a.bg[0] ? a.bg[c][bo] : 0.0f;
-    for (uint32_t e = 0; e < a.num_extra; e++) a.canvas_ec[e][ceo] = a.bg_ec[e] ? a.bg_ec[e][(size_t)Y * a.bg_ec_stride[e] + X] : 0.0f;
-    return;
-  }
-  const size_t fo = (size_t)fy * a.fg_stride + fx, feo = (size_t)fy * a.fg_ec_stride + fx;
-  const uint32_t mode = a.mode[0] & 0xFF, ach = (a.mode[0] >> 8) & 0xFF; const bool clamp = (a.mode[0] >> 16) & 1;
-  float fga = 1.0f, bga = 1.0f; bool premul = false;
-  if (mode == 2 || mode == 3) {
-    fga = a.fg_ec[ach][feo];
-    bga = a.bg_alpha ? a.bg_alpha[(size_t)Y * a.bg_alpha_stride + X] : 0.0f;
-    premul = (a.premul_mask >> ach) & 1;
-  }
-  float ec_out[4];
-  for (uint32_t e = 0; e < a.num_extra; e++) {
-    const uint32_t m = a.mode[1 + e] & 0xFF, ac = (a.mode[1 + e] >> 8) & 0xFF; const bool cl = (a.mode[1 + e] >> 16) & 1;
-    const float b = a.bg_ec[e] ? a.bg_ec[e][(size_t)Y * a.bg_ec_stride[e] + X] : 0.0f;
-    const float fv = a.fg_ec[e][feo];
-    if (m == 2 || m == 3) {
-      const float efga = a.fg_ec[ac][feo];
-      const float ebga = a.bg_ec_alpha[e] ? a.bg_ec_alpha[e][(size_t)Y * a.bg_ec_stride[e] + X] : 0.0f;
-      if (ac == e) ec_out[e] = FrameBlendAlphaD(m, cl, ebga, efga);
-      else ec_out[e] = FrameBlendSampleD(m, cl, (a.premul_mask >> ac) & 1, b, fv, ebga, efga);
-    } else ec_out[e] = FrameBlendSampleD(m, cl, false, b, fv, 1.0f, 1.0f);
-  }
-  for (int c = 0; c < 3; c++) {
-    const float b = a.bg[0] ? a.bg[c][bo] : 0.0f;
-    a.canvas[c][co] = FrameBlendSampleD(mode, clamp, premul, b, a.fg[c][fo], bga, fga);
-  }
-  for (uint32_t e = 0; e < a.num_extra; e++) a.canvas_ec[e][ceo] = ec_out[e];
-}
-
-// Channel-table forms (more than four extra channels).  Colour: BlendKernel's colour half, the foreground alpha read through the table.
-__global__ void BlendColorTableKernel(BlendArgs a, const EcChanDev* __restrict__ table) {
+// Colour: the foreground alpha is read through the channel table (null without extra channels: such a frame has no alpha to blend against).
+__global__ void BlendColorKernel(BlendArgs a, const EcChanDev* __restrict__ table) {
   const int X = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y * blockDim.y + threadIdx.y;
   if (X >= (int)a.img_w || Y >= (int)a.img_h) return;
   const size_t co = (size_t)Y * a.canvas_stride + X, bo = (size_t)Y * a.bg_stride + X;
@@ -395,7 +313,7 @@ __global__ void BlendColorTableKernel(BlendArgs a, const EcChanDev* __restrict__
     return;
   }
   const size_t fo = (size_t)fy * a.fg_stride + fx;
-  const uint32_t mode = a.mode[0] & 0xFF, ach = (a.mode[0] >> 8) & 0xFF; const bool clamp = (a.mode[0] >> 16) & 1;
+  const uint32_t mode = a.mode & 0xFF, ach = (a.mode >> 8) & 0xFF; const bool clamp = (a.mode >> 16) & 1;
   float fga = 1.0f, bga = 1.0f; bool premul = false;
   if (mode == 2 || mode == 3) {
     const EcChanDev& al = table[ach];
@@ -410,7 +328,7 @@ __global__ void BlendColorTableKernel(BlendArgs a, const EcChanDev* __restrict__
 }
 // Extra channels: channel on blockIdx.z.  Every read is of a foreground plane or of a plane of the source (the canvas as an earlier frame left it),
 // every write goes to this frame's own canvas plane of the channel: no slice reads what another one writes.
-__global__ void BlendEcTableKernel(BlendArgs a, const EcChanDev* __restrict__ table) {
+__global__ void BlendEcKernel(BlendArgs a, const EcChanDev* __restrict__ table) {
   const int X = blockIdx.x * blockDim.x + threadIdx.x, Y = blockIdx.y * blockDim.y + threadIdx.y;
   if (X >= (int)a.img_w || Y >= (int)a.img_h) return;
   const uint32_t e = blockIdx.z;
@@ -432,9 +350,9 @@ __global__ void BlendEcTableKernel(BlendArgs a, const EcChanDev* __restrict__ ta
   } else o = FrameBlendSampleD(m, cl, false, b, fv, 1.0f, 1.0f);
   *out = o;
 }
-// Spot colours through the table: one thread per pixel walks the channels in header order (each mix reads what the one before it wrote)
-__global__ void SpotTableKernel(float* p0, float* p1, float* p2, uint32_t stride, const EcChanDev* __restrict__ table, uint32_t num_extra, uint32_t use_canvas,
-                                uint32_t w, uint32_t h) {
+// ---- spot colours (stage_spot.cc): one thread per pixel walks the channels in header order (each mix reads what the one before it wrote)
+__global__ void SpotKernel(float* p0, float* p1, float* p2, uint32_t stride, const EcChanDev* __restrict__ table, uint32_t num_extra, uint32_t use_canvas,
+                           uint32_t w, uint32_t h) {
   const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
   if (x >= w || y >= h) return;
   const size_t o = (size_t)y * stride + x;
@@ -581,10 +499,6 @@ void LaunchXybModToFloat(const int32_t* cy, const int32_t* cx, const int32_t* cb
                          const float fac[3], void* stream) {
   hipLaunchKernelGGL(XybModToFloatKernel, Grid2(w, h), kBlock2, 0, (hipStream_t)stream, cy, cx, cb, src_stride, dst[0], dst[1], dst[2], dst_stride, w, h, fac[0], fac[1], fac[2]);
 }
-void LaunchPatches(const PatchFrameArgs& a, const PatchEntryDev* entries, const uint32_t* tile_start, const uint32_t* tile_list, void* stream) {
-  const uint32_t tiles_x = (a.w + 31) / 32, tiles_y = (a.h + 31) / 32;
-  hipLaunchKernelGGL(PatchKernel, dim3(tiles_x * tiles_y), dim3(256), 0, (hipStream_t)stream, a, entries, tile_start, tile_list, tiles_x);
-}
 void LaunchSplines(float* const p[3], uint32_t stride, uint32_t w, uint32_t h, const SplineSegmentDev* segs, const uint32_t* row_start, const uint32_t* indices, void* stream) {
   hipLaunchKernelGGL(SplineKernel, dim3((w + 255) / 256, h), dim3(256), 0, (hipStream_t)stream, p[0], p[1], p[2], stride, w, h, segs, row_start, indices);
 }
@@ -598,9 +512,7 @@ void LaunchNoise(const NoiseArgs& a, void* stream) {
                      a.visible_frame_index, a.nonvisible_frame_index);
   hipLaunchKernelGGL(NoiseAddKernel, Grid2(a.w, a.h), kBlock2, 0, (hipStream_t)stream, a);
 }
-void LaunchSpot(const SpotArgs& a, void* stream) { hipLaunchKernelGGL(SpotKernel, Grid2(a.w, a.h), kBlock2, 0, (hipStream_t)stream, a); }
 void LaunchColor(const ColorArgs& a, void* stream) { hipLaunchKernelGGL(ColorKernel, Grid2(a.w, a.h), kBlock2, 0, (hipStream_t)stream, a); }
-void LaunchBlend(const BlendArgs& a, void* stream) { hipLaunchKernelGGL(BlendKernel, Grid2(a.img_w, a.img_h), kBlock2, 0, (hipStream_t)stream, a); }
 void LaunchWrite(const WriteArgs& a, void* stream) { hipLaunchKernelGGL(WriteKernel, Grid2(a.img_w, a.img_h), kBlock2, 0, (hipStream_t)stream, a); }
 void LaunchEcIntToFloat(const EcFrameArgs& a, void* stream) {
   if (!a.num_extra) return;
@@ -612,19 +524,19 @@ void LaunchEcUpsample(const EcFrameArgs& a, void* stream) {
   dim3 g = Grid2(a.ow, a.oh); g.z = a.num_extra;
   hipLaunchKernelGGL(EcUpsampleKernel, g, kBlock2, 0, (hipStream_t)stream, a);
 }
-void LaunchPatchesTable(const PatchFrameArgs& a, const EcChanDev* table, const PatchEntryDev* entries, const PatchEcDev* pec, const uint32_t* tile_start,
-                        const uint32_t* tile_list, void* stream) {
+void LaunchPatches(const PatchFrameArgs& a, const EcChanDev* table, const PatchEntryDev* entries, const PatchEcDev* pec, const uint32_t* tile_start, const uint32_t* tile_list,
+                   void* stream) {
   const uint32_t tiles_x = (a.w + 31) / 32, tiles_y = (a.h + 31) / 32;
-  hipLaunchKernelGGL(PatchTableKernel, dim3(tiles_x * tiles_y), dim3(256), 0, (hipStream_t)stream, a, table, entries, pec, tile_start, tile_list, tiles_x);
+  hipLaunchKernelGGL(PatchKernel, dim3(tiles_x * tiles_y), dim3(256), 0, (hipStream_t)stream, a, table, entries, pec, tile_start, tile_list, tiles_x);
 }
-void LaunchBlendTable(const BlendArgs& a, const EcChanDev* table, void* stream) {
-  hipLaunchKernelGGL(BlendColorTableKernel, Grid2(a.img_w, a.img_h), kBlock2, 0, (hipStream_t)stream, a, table);
+void LaunchBlend(const BlendArgs& a, const EcChanDev* table, void* stream) {
+  hipLaunchKernelGGL(BlendColorKernel, Grid2(a.img_w, a.img_h), kBlock2, 0, (hipStream_t)stream, a, table);
   if (!a.num_extra) return;
   dim3 g = Grid2(a.img_w, a.img_h); g.z = a.num_extra;
-  hipLaunchKernelGGL(BlendEcTableKernel, g, kBlock2, 0, (hipStream_t)stream, a, table);
+  hipLaunchKernelGGL(BlendEcKernel, g, kBlock2, 0, (hipStream_t)stream, a, table);
 }
-void LaunchSpotTable(float* const p[3], uint32_t stride, const EcChanDev* table, uint32_t num_extra, uint32_t use_canvas, uint32_t w, uint32_t h, void* stream) {
-  hipLaunchKernelGGL(SpotTableKernel, Grid2(w, h), kBlock2, 0, (hipStream_t)stream, p[0], p[1], p[2], stride, table, num_extra, use_canvas, w, h);
+void LaunchSpot(float* const p[3], uint32_t stride, const EcChanDev* table, uint32_t num_extra, uint32_t use_canvas, uint32_t w, uint32_t h, void* stream) {
+  hipLaunchKernelGGL(SpotKernel, Grid2(w, h), kBlock2, 0, (hipStream_t)stream, p[0], p[1], p[2], stride, table, num_extra, use_canvas, w, h);
 }
 void LaunchJpegCoefficients(const FrameDev* frames, int fidx, const JpegCoefArgs& a, uint32_t bw, uint32_t bh, void* stream) {
   const uint32_t n = bw * bh * 64;

@@ -1,5 +1,6 @@
-"""Images with more than four extra channels through the frame tail (blending, patches, per-channel upsampling / float conversion, spot colours,
-un-premultiplied and non-coalesced output, LF frames, previews): the channel-table kernels of kernels_features.hip.
+"""Extra channels through the frame tail (blending, patches, per-channel upsampling / float conversion, spot colours, un-premultiplied and
+non-coalesced output, LF frames, previews), from one channel to nine: the frame tail describes a frame's extra channels by a channel table of any
+length (kernels.h EcChanDev), and the streams here are built for channel counts on both sides of four, where an earlier form of the tail changed its path.
 
 How the planes are pinned.  The oracle hands out the colour channels and the FIRST extra channel of type alpha.  A channel's type plays no part
 in blending (only its index, the alpha-associated flag of alpha channels and, for the colour, the spot plates do), so extra channel e of a
@@ -9,8 +10,7 @@ the synthesiser, which shares nothing with either decoder.
 
 Modes the oracle does not decode (PARITY.md): non-coalesced output and the canvases of an animation's earlier frames are compared with the oracle's decode
 of the frame written as an image of its own / of the stream cut behind that frame, as the tests of those modes with fewer channels do.
-
-On the parent commit the GPU tests 4 - 12 and 14 end in `unsupported: more than 4 extra channels ...`."""
+"""
 import ctypes as C
 import functools
 import numpy as np
@@ -20,12 +20,12 @@ import synth_lib as S
 import synth_extra as X
 
 W, H, FW, FH, X0, Y0 = 300, 200, 150, 90, 211, -37      # canvas; cropped second frame, partly off the canvas to the right and at the top
-OTHER_MODES = [X.REPLACE, X.ADD, X.MULADD, X.MUL, X.BLEND]     # of the channels beside the referred alpha, in turn; that alpha itself blends: all five modes from n = 5 on
+OTHER_MODES = [X.REPLACE, X.ADD, X.MULADD, X.MUL, X.BLEND]     # of the channels beside the referred alpha, in turn; that alpha itself blends: all five modes occur from n = 5 on
 
 
 def _extras(n, relabel=None, alpha_at=5, second_alpha=True, premul_at=None, spots=(), f16_at=None, blend=True, source=1):
     """n channel entries: the alpha that blending refers to at min(alpha_at, n - 1), an unrelated alpha at 0, depth / selection / optional / 16-bit
-    channels in between, every frame-blend mode among them (clamp on for the multiply and one blend channel)."""
+    channels in between, from n = 5 on every frame-blend mode among them (clamp on for the multiply and one blend channel)."""
     a = min(alpha_at, n - 1)
     out, turn = [], 0
     for k in range(n):
@@ -50,7 +50,7 @@ def _extras(n, relabel=None, alpha_at=5, second_alpha=True, premul_at=None, spot
             t, spot = (X.ALPHA if k in (relabel, premul_at) else X.OPTIONAL), (0, 0, 0, 0)
         out.append(X.extra(type=t, bits=bits, exp_bits=exp, premultiplied=premul if t == X.ALPHA else 0, mode=mode, alpha=a, clamp=1 if mode == X.MUL or k == 2 else 0,
                            source=source if blend else 0, spot=spot, name=b"ch%d" % k if k % 2 else b""))
-    if blend:
+    if blend and n >= 5:
         assert {e.blend_mode for e in out} == {0, 1, 2, 3, 4}, "case 4: every frame-blend mode among the extras"
         assert any(e.blend_clamp for e in out if e.blend_mode == X.MUL) and any(e.blend_clamp for e in out if e.blend_mode in (X.BLEND, X.MULADD))
     return out, a
@@ -74,7 +74,7 @@ def _as_float(plane, e):
 
 @functools.lru_cache(maxsize=None)
 def layered(kind, n, relabel=None, frames=2, upto=None, only=None, premul=False):
-    """Two (or three) frames: a full first frame saved as reference 1, then cropped frames blended onto it — colour with mode blend against alpha index 5,
+    """Two (or three) frames: a full first frame saved as reference 1, then cropped frames blended onto it — colour with mode blend against alpha index min(5, n - 1),
     the extras each with a mode of their own.  upto: the stream cut behind frame `upto` (that frame marked last); only: frame `only` as an image of its own.
     Returns (stream, source planes per frame, extras of the blended frames)."""
     pm = min(5, n - 1) if premul else None            # premul: the alpha that blending refers to is premultiplied
@@ -217,7 +217,7 @@ def assert_planes(got, make, n):
 
 
 # ---------------------------------------------------------------------------------------------------------------- CPU
-NS = [5, 6, 9]
+NS = [1, 2, 4, 5, 6, 9]
 
 
 @pytest.mark.parametrize("n", NS)
@@ -234,14 +234,19 @@ def test_oracle_decodes_the_streams_and_lossless_planes_are_the_source(n):
         assert O.decode(full).info.num_extra_channels == n
     if n != 6:
         return
-    # every other stream of the GPU tests below (they use 5 or 6 channels; decoded once, with the n = 6 case), twins included where a twin is what the test reads
-    makes = [lambda: spot_single(None), lambda: spot_single(4), lambda: spot_layered(None), lambda: spot_layered(1), lambda: float_stream(None)[0], lambda: float_stream(2)[0],
-             lambda: upsampled(None)[0], lambda: upsampled(3)[0], lambda: xyb_modular(None), lambda: xyb_modular(4), lambda: patched(None), lambda: patched(5), lambda: patched(None, True),
-             lambda: patched(3, True), lambda: lf_frame_image(None), lambda: lf_frame_image(2), lambda: preview_image(None)[0], lambda: preview_image(None)[1], lambda: preview_image(1)[0],
-             lambda: premultiplied_image()[0], lambda: layered("vardct", 6, premul=True)[0], lambda: layered("vardct", 6, relabel=2, premul=True)[0]]
-    for k, make in enumerate(makes):
+    # every other stream of the GPU tests below (decoded once, with the n = 6 case), twins included where a twin is what the test reads: (channels, stream)
+    makes = [(6, lambda: spot_single(None)), (6, lambda: spot_single(4)), (6, lambda: spot_layered(None)), (6, lambda: spot_layered(1)), (5, lambda: float_stream(None)[0]),
+             (5, lambda: float_stream(2)[0]), (5, lambda: upsampled(None)[0]), (5, lambda: upsampled(3)[0]), (5, lambda: xyb_modular(None)), (5, lambda: xyb_modular(4)),
+             (6, lambda: patched(None)), (6, lambda: patched(5)), (6, lambda: patched(None, True)), (6, lambda: patched(3, True)), (5, lambda: lf_frame_image(None)),
+             (5, lambda: lf_frame_image(2)), (5, lambda: preview_image(None)[0]), (5, lambda: preview_image(None)[1]), (5, lambda: preview_image(1)[0]),
+             (6, lambda: premultiplied_image()[0]), (6, lambda: layered("vardct", 6, premul=True)[0]), (6, lambda: layered("vardct", 6, relabel=2, premul=True)[0]),
+             (4, lambda: spot_single(None, 4)), (4, lambda: spot_single(2, 4)), (4, lambda: spot_layered(None, 4)), (4, lambda: spot_layered(1, 4)), (4, lambda: float_stream(None, 4)[0]),
+             (4, lambda: float_stream(2, 4)[0]), (2, lambda: upsampled(None, 2)[0]), (2, lambda: upsampled(1, 2)[0])]
+    for m in PATCHED_NS[:-1]:
+        makes += [(m, lambda m=m: patched(None, False, m)), (m, lambda m=m: patched(m - 1, False, m)), (m, lambda m=m: patched(None, True, m)), (m, lambda m=m: patched(0, True, m))]
+    for k, (m, make) in enumerate(makes):
         ref = O.decode(make())
-        assert ref.info.num_extra_channels in (5, 6) and ref.info.xsize > 0, k
+        assert ref.info.num_extra_channels == m and ref.info.xsize > 0, k
     S.set_animation(10, 1, 0)
     try:
         layered.cache_clear()
@@ -267,7 +272,7 @@ def test_host_parse_reports_every_extra_channel(jxh, n):
     lines = buf.value.decode().split("\n")
     assert "extra=%d " % n in lines[0]
     rows = [dict(t.split("=", 1) for t in l.split()[2:]) for l in lines if l.startswith("extra ")]
-    assert len(rows) == n
+    assert len(rows) == (n if n > 4 else 0)      # (the description lists the channels one by one from five on; those of images with fewer stay as they always were)
     for k, r in enumerate(rows):
         assert (int(r["type"]), int(r["bits"]), r["name"].encode()) == (ex[k].type, ex[k].bits, ex[k].name), k
         if ex[k].type == X.SPOT:
@@ -344,19 +349,25 @@ def test_layered_image_non_coalesced(jx, kind, n):
             assert np.array_equal(fr["planes"][e].reshape(fr["size"][1], fr["size"][0]), _as_float(src[f][e], ex_f[e])), (f, e)
 
 
+PATCHED_NS = [1, 2, 4, 6]
+PATCH_REF, PATCH_RECT, PATCH_AT = (64, 48), (2, 2, 40, 35), ((5, 5), (259, 10), (120, 160), (130, 165))      # reference frame; the patch in it (x0, y0, xsize, ysize); its placements
+
+
 @functools.lru_cache(maxsize=None)
-def patched(relabel, premul=False):
-    n = 6
-    ex, a = _extras(n, relabel, blend=False, premul_at=5 if premul else None)
-    ref_img, main = S.synthetic_image(41, 64, 48), S.synthetic_image(42, W, H)
+def patched(relabel, premul=False, n=6):
+    ex, a = _extras(n, relabel, blend=False, premul_at=min(5, n - 1) if premul else None)
+    ref_img, main = S.synthetic_image(41, *PATCH_REF), S.synthetic_image(42, W, H)
     hdr = dict(frame_type=2, is_last=0, save_before_ct=1, have_crop=1, canvas_w=W, canvas_h=H, save_as_reference=1)
-    ref = X.encode_vardct_ec(ref_img, _planes(n, 64, 48, 300, ex), ex, S.frame(**hdr), color_alpha=a, seed=3)
-    # per placement: colour + six channels; modes 1 - 7 all occur, alpha-reading modes refer to channel 5 (also from channel 5 itself)
-    pos = [(5, 5, [(4, 5, 0), (1, 0, 0), (2, 0, 0), (3, 0, 1), (4, 5, 0), (5, 5, 1), (4, 5, 0)]),
-           (259, 10, [(5, 5, 1), (6, 5, 0), (7, 5, 1), (0, 0, 0), (1, 0, 0), (2, 0, 0), (5, 5, 0)]),
-           (120, 160, [(6, 5, 0), (3, 0, 0), (4, 5, 1), (6, 5, 1), (7, 5, 0), (1, 0, 0), (6, 5, 0)]),
-           (130, 165, [(7, 5, 1), (2, 0, 0), (5, 5, 0), (4, 5, 0), (3, 0, 1), (7, 5, 0), (7, 5, 1)])]
-    S.set_features(patches=[(1, 2, 2, 40, 35, pos)], num_extra=n)
+    ref = X.encode_vardct_ec(ref_img, _planes(n, *PATCH_REF, 300, ex), ex, S.frame(**hdr), color_alpha=a, seed=3)
+    # per placement: colour + six channels; modes 1 - 7 all occur, alpha-reading modes refer to channel 5 (also from channel 5 itself).  With n < 6 channels: the colour,
+    # the first n - 1 channels and, as channel a = n - 1, the referred alpha's own entry; the alpha-reading modes refer to a.  The last two placements overlap, and in
+    # every placement some channel reads the alpha that the same patch rewrites.
+    blends = [[(4, 5, 0), (1, 0, 0), (2, 0, 0), (3, 0, 1), (4, 5, 0), (5, 5, 1), (4, 5, 0)],
+              [(5, 5, 1), (6, 5, 0), (7, 5, 1), (0, 0, 0), (1, 0, 0), (2, 0, 0), (5, 5, 0)],
+              [(6, 5, 0), (3, 0, 0), (4, 5, 1), (6, 5, 1), (7, 5, 0), (1, 0, 0), (6, 5, 0)],
+              [(7, 5, 1), (2, 0, 0), (5, 5, 0), (4, 5, 0), (3, 0, 1), (7, 5, 0), (7, 5, 1)]]
+    pos = [(x, y, [(m, a if m >= 4 else 0, c) for m, _, c in modes[:n] + modes[6:]]) for (x, y), modes in zip(PATCH_AT, blends)]
+    S.set_features(patches=[(1, *PATCH_RECT, pos)], num_extra=n)
     try:
         return ref + X.encode_vardct_ec(main, _planes(n, W, H, 400, ex), ex, S.frame(emit=1), color_alpha=a, seed=4)
     finally:
@@ -364,13 +375,13 @@ def patched(relabel, premul=False):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("premul", [False, True])
-def test_patches_with_per_channel_modes(jx, premul):
-    """premul: the alpha the patch blendings refer to (channel 5) is premultiplied — the other branch of modes 4 / 5"""
-    stream = patched(None, premul)
-    (fr,) = abi_decode(jx, stream, 6, "u8")
+@pytest.mark.parametrize("premul,n", [pytest.param(pm, n, id=str(pm) + ("" if n == 6 else "-%d" % n)) for n in reversed(PATCHED_NS) for pm in (False, True)])
+def test_patches_with_per_channel_modes(jx, premul, n):
+    """premul: the alpha the patch blendings refer to (channel min(5, n - 1)) is premultiplied — the other branch of modes 4 / 5"""
+    stream = patched(None, premul, n)
+    (fr,) = abi_decode(jx, stream, n, "u8")
     assert_colour(fr["px"], stream, "u8")
-    assert_planes(fr["planes"], lambda e: patched(e, premul), 6)
+    assert_planes(fr["planes"], lambda e: patched(e, premul, n), n)
     (fr,) = abi_decode(jx, stream, 0, "f32")
     assert_colour(fr["px"], stream, "f32")
 
@@ -427,75 +438,78 @@ def test_premultiplied_alpha_unpremultiplied_output(jx):
         assert np.array_equal(fr["planes"][e].reshape(H, W), _as_float(pl[e], ex[e])), e
 
 
-SPOTS = ((1, (1.0, 0.25, 0.0, 0.75)), (4, (0.0, 0.5, 1.0, 0.5)))
+def _spots(n):
+    """two plates: at 1 and 4 among six channels, at 1 and 2 among four (the referred alpha is channel n - 1 of those)"""
+    return ((1, (1.0, 0.25, 0.0, 0.75)), (4 if n == 6 else 2, (0.0, 0.5, 1.0, 0.5)))
 
 
 @functools.lru_cache(maxsize=None)
-def spot_single(relabel):
-    ex, a = _extras(6, relabel, spots=SPOTS, blend=False)
-    return X.encode_vardct_ec(S.synthetic_image(61, W, H), _planes(6, W, H, 600, ex), ex, S.frame(), color_alpha=a, seed=6)
+def spot_single(relabel, n=6):
+    ex, a = _extras(n, relabel, spots=_spots(n), blend=False)
+    return X.encode_vardct_ec(S.synthetic_image(61, W, H), _planes(n, W, H, 600, ex), ex, S.frame(), color_alpha=a, seed=6)
 
 
 @functools.lru_cache(maxsize=None)
-def spot_layered(relabel):
-    ex0, a = _extras(6, relabel, spots=SPOTS, blend=False)
-    ex1, _ = _extras(6, relabel, spots=SPOTS, blend=True)
-    f0 = X.encode_vardct_ec(S.synthetic_image(62, W, H), _planes(6, W, H, 700, ex0), ex0, S.frame(is_last=0, save_as_reference=1), color_alpha=a, seed=7)
-    f1 = X.encode_vardct_ec(S.synthetic_image(63, FW, FH), _planes(6, FW, FH, 800, ex1), ex1,
+def spot_layered(relabel, n=6):
+    ex0, a = _extras(n, relabel, spots=_spots(n), blend=False)
+    ex1, _ = _extras(n, relabel, spots=_spots(n), blend=True)
+    f0 = X.encode_vardct_ec(S.synthetic_image(62, W, H), _planes(n, W, H, 700, ex0), ex0, S.frame(is_last=0, save_as_reference=1), color_alpha=a, seed=7)
+    f1 = X.encode_vardct_ec(S.synthetic_image(63, FW, FH), _planes(n, FW, FH, 800, ex1), ex1,
                             S.frame(emit=1, have_crop=1, crop_x0=X0, crop_y0=Y0, canvas_w=W, canvas_h=H, blend_mode=X.BLEND, blend_source=1), color_alpha=a, seed=8)
     return f0 + f1
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("make", [spot_single, spot_layered])
-@pytest.mark.parametrize("render", [True, False])
-def test_two_spot_plates_in_header_order(jx, make, render):
-    stream = make(None)
+@pytest.mark.parametrize("render,make,n", [pytest.param(r, m, n, id="%s-%s" % (r, m.__name__) + ("" if n == 6 else "-%d" % n))
+                                           for n in (6, 4) for m in (spot_single, spot_layered) for r in (True, False)])
+def test_two_spot_plates_in_header_order(jx, make, render, n):
+    stream = make(None, n)
     O.set_render_spotcolors(render)
     try:
         for ctype in ("u8", "f32"):
-            (fr,) = abi_decode(jx, stream, 6 if ctype == "u8" else 0, ctype, spot=render)
+            (fr,) = abi_decode(jx, stream, n if ctype == "u8" else 0, ctype, spot=render)
             assert_colour(fr["px"], stream, ctype)
             if ctype == "u8":
-                assert_planes(fr["planes"], make, 6)
+                assert_planes(fr["planes"], lambda e: make(e, n), n)
     finally:
         O.set_render_spotcolors(True)
 
 
 @functools.lru_cache(maxsize=None)
-def float_stream(relabel):
-    ex, a = _extras(5, relabel, f16_at=2, blend=False)
-    pl = _planes(5, W, H, 900, ex)
+def float_stream(relabel, n=5):
+    ex, a = _extras(n, relabel, f16_at=2, blend=False)
+    pl = _planes(n, W, H, 900, ex)
     return X.encode_modular_ec(S.synthetic_image(71, W, H).astype(np.int32), pl, ex, S.frame(), color_alpha=a), pl, ex
 
 
 @pytest.mark.gpu
 def test_float16_extra_channel(jx):
-    stream, pl, ex = float_stream(None)
-    (fr,) = abi_decode(jx, stream, 5, "u8")
-    assert_colour(fr["px"], stream, "u8")
-    assert_planes(fr["planes"], lambda e: float_stream(e)[0], 5)
-    for e in range(5):
-        assert np.array_equal(fr["planes"][e].reshape(H, W), _as_float(pl[e], ex[e])), e
+    for n in (5, 4):
+        stream, pl, ex = float_stream(None, n)
+        (fr,) = abi_decode(jx, stream, n, "u8")
+        assert_colour(fr["px"], stream, "u8")
+        assert_planes(fr["planes"], lambda e: float_stream(e, n)[0], n)
+        for e in range(n):
+            assert np.array_equal(fr["planes"][e].reshape(H, W), _as_float(pl[e], ex[e])), (n, e)
 
 
 @functools.lru_cache(maxsize=None)
-def upsampled(relabel):
-    ex, a = _extras(5, relabel, blend=False)
-    pl = _planes(5, W // 2, H // 2, 1000, ex)
+def upsampled(relabel, n=5):
+    ex, a = _extras(n, relabel, blend=False)
+    pl = _planes(n, W // 2, H // 2, 1000, ex)
     pl[1] = np.full_like(pl[1], 77)                  # a flat plane: the one kind of source plane that upsampling hands back unchanged (see the test)
     return X.encode_modular_ec(S.synthetic_image(81, W // 2, H // 2).astype(np.int32), pl, ex, S.frame(), color_alpha=a, upsampling=2), pl, ex
 
 
 @pytest.mark.gpu
 def test_upsampled_modular_frame(jx):
-    stream, pl, ex = upsampled(None)
-    for ctype in ("u8", "f32"):
-        (fr,) = abi_decode(jx, stream, 5 if ctype == "u8" else 0, ctype)
+    for n, ctype in ((5, "u8"), (5, "f32"), (2, "u8"), (2, "f32")):
+        stream, pl, ex = upsampled(None, n)
+        (fr,) = abi_decode(jx, stream, n if ctype == "u8" else 0, ctype)
         assert_colour(fr["px"], stream, ctype)
         if ctype == "u8":
             assert fr["size"] == (W, H)
-            assert_planes(fr["planes"], lambda e: upsampled(e)[0], 5)
+            assert_planes(fr["planes"], lambda e: upsampled(e, n)[0], n)
             # Source planes: an upsampled sample is a weighted sum of 25 coded samples clamped to their range, so it equals no source sample in general and the
             # planes cannot be pinned against the source the way the unscaled lossless cases are.  A flat plane can: the clamp to [min, max] = [v, v] gives v back.
             assert np.array_equal(fr["planes"][1].reshape(H, W), np.full((H, W), _as_float(pl[1], ex[1])[0, 0], np.float32))

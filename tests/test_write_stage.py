@@ -691,7 +691,7 @@ PATH_ENCODINGS = dict(COLOUR_ENCODINGS, default_srgb={}, linear=dict(white_point
 def test_fast_path_and_frame_tail_write_the_same_samples(jx, name):
     """One 200 x 136 XYB frame as a single-frame image (the fast path: the last filter kernel or OutputKernel hands it to ColorAndStore -> StorePixel; the default
     sRGB frame with gaborish and one EPF pass takes FusedGabEpf1OutKernel) and as the first of two frames, the second a 64 x 48 crop that replaces its rectangle
-    (the frame tail: ColorKernel, BlendKernel, WriteKernel).  Colour transform, transfer function and sample conversion of the two paths are one definition
+    (the frame tail: ColorKernel, BlendColorKernel, WriteKernel).  Colour transform, transfer function and sample conversion of the two paths are one definition
     (pixel_ops.h), so outside the crop the f32 output is equal bit for bit, and so are u8 and u16 — for every transfer function, with and without the filters."""
     img = S.synthetic_image(31, 200, 136)
     x0, y0, cw, ch = 40, 30, 64, 48

@@ -1,5 +1,5 @@
 #!/bin/bash
-# VGPRs / spills / scratch / LDS of every kernel in lib/libjxl.so's gfx950 code object (llvm-readelf --notes on the extracted bundle)
+# VGPRs / SGPRs / spills / scratch of every kernel in lib/libjxl.so's gfx950 code object (llvm-readelf --notes on the extracted bundle)
 set -e
 cd "$(dirname "$0")/../.."
 LIB=${1:-jpegxl-rs_amd/lib/libjxl.so}
@@ -27,11 +27,11 @@ while True:
     open(path, "wb").write(data[i:i + size])
     txt = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", path], capture_output=True, text=True).stdout
     for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_count:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", txt, re.S):
-        out.append((m.group(1), int(m.group(4)), int(m.group(5)), int(m.group(2))))
+        out.append((m.group(1), int(m.group(4)), int(m.group(3)), int(m.group(5)), int(m.group(2))))
 flt = subprocess.run(["c++filt"] + [o[0] for o in out], capture_output=True, text=True).stdout.splitlines()
-print(f"{'kernel':90s} {'VGPRs':>6s} {'spilled':>8s} {'scratch B':>10s}")
-for (n, v, sp, sc), d in sorted(zip(out, flt), key=lambda t: t[1]):
-    d = re.sub(r"\(.*", "", d).replace("void jxlhip::", "")
-    print(f"{d[:90]:90s} {v:6d} {sp:8d} {sc:10d}")
+print(f"{'kernel':90s} {'VGPRs':>6s} {'SGPRs':>6s} {'spilled':>8s} {'scratch B':>10s}")
+for (n, v, sg, sp, sc), d in sorted(zip(out, flt), key=lambda t: t[1]):
+    d = re.sub(r"\(.*", "", d.replace("(anonymous namespace)::", "")).replace("void jxlhip::", "")
+    print(f"{d[:90]:90s} {v:6d} {sg:6d} {sp:8d} {sc:10d}")
 PY
 rm -rf $TMP

@@ -295,11 +295,14 @@ JxlDecoderStatus JxlHipBatchSetOutputResized(JxlHipBatch* batch, int index, cons
  * `index` is a lossless JPEG transcode with usable reconstruction data (a `jbrd` box whose markers find their ICC / Exif / XMP payloads, a Huffman-coded source),
  * else 0 with the reason in JxlHipLastError().  JxlHipBatchReconstructJpegs runs the LF and HF entropy stages once for all images of the batch (it prepares the batch
  * if need be; no image needs an output set) and writes the files: sequential Huffman scans are entropy-coded on the GPU and only their bytes cross to the host,
- * which serialises the markers around them; progressive scans and scans with extra zero runs are Huffman-coded on the host from that image's coefficients.
+ * which serialises the markers around them; progressive files (by default) and scans with extra zero runs are Huffman-coded on the host from that image's coefficients.
  * An image that cannot be reconstructed or whose stream is damaged fails alone — the call still returns JXL_DEC_SUCCESS; JxlHipBatchJpegStatus(index) is
  * JXL_DEC_SUCCESS or JXL_DEC_ERROR with that image's reason in JxlHipLastError().  JxlHipBatchJpegSize / JxlHipBatchCopyJpeg hand out the bytes (size 0: no file),
  * valid until the next JxlHipBatchReconstructJpegs or JxlHipBatchReset.  JxlHipBatchSetOption("jpeg_host_writer", 1): every image through the host writer.
- * JxlHipBatchGetInfo "jpeg_device_images" / "jpeg_host_images": files of the last call written by the device / by the host writer. */
+ * JxlHipBatchSetOption("jpeg_device_progressive", 1): progressive files (SOF2) are written by the device too, where every scan is a first DC pass, a DC refinement,
+ * a first AC pass or an AC refinement of one component; the default 0 sends progressive files through the host writer, and "jpeg_host_writer" wins over it.
+ * JxlHipBatchGetInfo "jpeg_device_images" / "jpeg_host_images": files of the last call written by the device / by the host writer;
+ * "jpeg_device_progressive_images": those of the device's files that have at least one progressive scan. */
 int JxlHipBatchCanReconstructJpeg(JxlHipBatch* batch, int index);
 JxlDecoderStatus JxlHipBatchReconstructJpegs(JxlHipBatch* batch, void* hip_stream);
 JxlDecoderStatus JxlHipBatchJpegStatus(const JxlHipBatch* batch, int index);

@@ -803,9 +803,10 @@ class BatchDecoder:
         """True if image i is a lossless JPEG transcode whose file can be given back; otherwise last_error() says why not."""
         return bool(libjxl().JxlHipBatchCanReconstructJpeg(self._h, i))
 
-    def reconstruct_jpegs(self, stream=None):
-        """One run of the entropy stages for the whole batch, then the JPEG files (sequential scans are entropy-coded on the GPU).  An image that fails
-        does so alone: jpeg(i) raises for it."""
+    def reconstruct_jpegs(self, stream=None, progressive_on_device=False):
+        """One run of the entropy stages for the whole batch, then the JPEG files (sequential scans are entropy-coded on the GPU; with progressive_on_device
+        the scans of progressive files as well, otherwise those files are coded on the host).  An image that fails does so alone: jpeg(i) raises for it."""
+        self.set_option("jpeg_device_progressive", 1 if progressive_on_device else 0)
         self._chk(libjxl().JxlHipBatchReconstructJpegs(self._h, stream))
 
     def jpeg(self, i) -> bytes:

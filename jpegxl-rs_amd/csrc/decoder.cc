@@ -1008,6 +1008,7 @@ int64_t Batch::Info(const std::string& name) const {
   if (name == "mod_group_lds_bytes") return prepared_ ? (int64_t)ModularGroupLdsBytes(cfg) : -1;
   if (name == "jpeg_device_images") return jpeg_device_images_;     // images of the last ReconstructJpegs whose scans the device wrote / that went through the host writer
   if (name == "jpeg_host_images") return jpeg_host_images_;
+  if (name == "jpeg_device_progressive_images") return jpeg_device_progressive_images_;    // ... of the device's, those with at least one progressive scan
   if (name == "lf_simt_lanes") return lf_simt_.num_lanes;
   if (name == "lf_simt_wp") return lf_simt_.num_lanes ? lf_simt_.any_wp : 0;     // the SIMT launch is the weighted-predictor instantiation
   // the kernels the last decode's LF / HF stage launched (kernels.h kHfVar* / kLfVar* bits) and the LDS sizes that chose them (bytes, after Prepare)
@@ -2795,8 +2796,8 @@ void Batch::ReconstructJpegs(void* stream_v) {
   hipStream_t stream = (hipStream_t)stream_v;
   const int n = (int)pub_.size();
   jpeg_results_.clear(); jpeg_results_.resize((size_t)n);
-  jpeg_device_images_ = jpeg_host_images_ = 0;
-  struct Img { bool ok = false, device = false; size_t first_blk = 0, nblk = 0, comp_first[3] = {0, 0, 0}; size_t first_scan = 0, num_scans = 0; std::vector<ScanPlan> plans; };
+  jpeg_device_images_ = jpeg_host_images_ = jpeg_device_progressive_images_ = 0;
+  struct Img { bool ok = false, device = false, progressive = false; size_t first_blk = 0, nblk = 0, comp_first[3] = {0, 0, 0}; size_t first_scan = 0, num_scans = 0; std::vector<ScanPlan> plans; };
   std::vector<Img> im((size_t)n);
   bool any = false;
   for (int i = 0; i < n; i++) {
@@ -2810,6 +2811,8 @@ void Batch::ReconstructJpegs(void* stream_v) {
   size_t total_blk = 0;
   vec<JpegScanDev> scans;
   vec<JpegHuffDev> tables;
+  vec<uint32_t> resets;          // reset points of the AC progressive scans, as batch block numbers
+  bool any_progressive = false;
   uint64_t num_blocks = 0, num_segs = 0;
   for (int i = 0; i < n; i++) {
     Img& m = im[i];
@@ -2824,6 +2827,8 @@ void Batch::ReconstructJpegs(void* stream_v) {
     vec<uint8_t> scratch;
     bool eligible = true;
     vec<JpegScanDev> mine;
+    vec<uint32_t> my_resets;
+    bool progressive_scans = false;
     uint64_t blocks = num_blocks, segs = num_segs;
     const size_t table0 = tables.size();
     const bool walked = WriteJpegMarkers(jd, e.ih.xsize, e.ih.ysize, [&](const JpegScanContext& cx, vec<uint8_t>*, std::string*) {
@@ -2831,10 +2836,20 @@ void Batch::ReconstructJpegs(void* stream_v) {
       ScanPlan sp; sp.restart = cx.restart_interval; sp.progressive = cx.is_progressive;
       memcpy(sp.dc, cx.dc_tab, sizeof(sp.dc)); memcpy(sp.ac, cx.ac_tab, sizeof(sp.ac));
       m.plans.push_back(sp);
-      // sequential scans only: progressive scans, extra zero runs and whatever the tables below cannot express go to the host writer
-      if (cx.is_progressive || s.Ss != 0 || s.Se != 63 || s.Ah != 0 || s.Al != 0 || !s.extra_zero_runs.empty() || s.num_components < 1 || s.num_components > 3) { eligible = false; return true; }
+      // sequential scans, and with jpeg_device_progressive the four progressive kinds: extra zero runs, a progressive scan that codes DC and AC
+      // together and whatever the tables below cannot express go to the host writer
+      if ((cx.is_progressive && !jpeg_device_progressive) || !s.extra_zero_runs.empty() || s.num_components < 1 || s.num_components > 3) { eligible = false; return true; }
+      uint32_t kind = kJpegSequential;
+      if (cx.is_progressive) {
+        if (s.Ss == 0 && s.Se != 0) { eligible = false; return true; }
+        if (s.Ss > 0 && s.num_components != 1) { eligible = false; return true; }
+        kind = s.Ss == 0 ? (s.Ah == 0 ? kJpegDcFirst : kJpegDcRefine) : (s.Ah == 0 ? kJpegAcFirst : kJpegAcRefine);
+        progressive_scans = true;
+      } else if (s.Ss != 0 || s.Se != 63 || s.Ah != 0 || s.Al != 0) { eligible = false; return true; }
+      const bool needs_dc = kind == kJpegSequential || kind == kJpegDcFirst, needs_ac = kind == kJpegSequential || kind >= kJpegAcFirst;
       JpegScanDev d;
       memset(&d, 0, sizeof(d));
+      d.kind = kind; d.ss = (uint8_t)s.Ss; d.se = (uint8_t)s.Se; d.ah = (uint8_t)s.Ah; d.al = (uint8_t)s.Al;
       uint32_t cols, rows;
       JpegScanGrid(cx, &cols, &rows);
       d.ncomp = s.num_components; d.scan_cols = cols; d.restart = cx.restart_interval;
@@ -2843,19 +2858,32 @@ void Batch::ReconstructJpegs(void* stream_v) {
         const JpegScanComponent& sc = s.components[k];
         for (uint32_t k2 = 0; k2 < k; k2++) if (s.components[k2].comp_idx == sc.comp_idx) eligible = false;     // (the DC predictor is kept per component)
         const JpegComponentInfo& comp = jd.components[sc.comp_idx];
-        if (!cx.dc_tab[sc.dc_tbl_idx & 3].init || !cx.ac_tab[sc.ac_tbl_idx & 3].init) eligible = false;   // (the host writer names the error)
+        if ((needs_dc && !cx.dc_tab[sc.dc_tbl_idx & 3].init) || (needs_ac && !cx.ac_tab[sc.ac_tbl_idx & 3].init)) eligible = false;   // (the host writer names the error)
         d.h[k] = (uint8_t)(s.num_components > 1 ? comp.h_samp : 1); d.v[k] = (uint8_t)(s.num_components > 1 ? comp.v_samp : 1);
         d.plane[k] = (uint32_t)(m.first_blk + m.comp_first[sc.comp_idx]); d.pitch[k] = cx.mcu_cols * comp.h_samp;
         d.dc[k] = (uint16_t)(sc.dc_tbl_idx & 3); d.ac[k] = (uint16_t)(4 + (sc.ac_tbl_idx & 3));       // (slots of this scan's snapshot: rebased below)
         d.blocks_per_mcu += (uint32_t)d.h[k] * d.v[k];
       }
       const uint64_t nb = (uint64_t)cols * rows * d.blocks_per_mcu, per_seg = d.restart ? (uint64_t)d.restart * d.blocks_per_mcu : nb;
-      // a block is at most 27 + 63 x 31 + 3 x 16 + 16 bits: segments whose worst case leaves 32 bits stay on the host
+      // a block is at most 27 + 63 x 31 + 3 x 16 + 16 bits: segments whose worst case leaves 32 bits stay on the host.  The progressive kinds stay below that: 28 bits
+      // (first DC pass), 63 x 31 + 3 x 16 + 30 for the EOBn symbol (first AC pass), 63 x 17 + 3 x 16 + 30 (AC refinement: a symbol and its sign, or one correction bit)
       if (nb == 0 || per_seg * 2044 >= ((uint64_t)1 << 32)) eligible = false;
       d.first_block = (uint32_t)blocks; d.num_blocks = (uint32_t)nb;
       d.first_seg = (uint32_t)segs; d.num_segs = (uint32_t)(d.restart ? ((uint64_t)cols * rows + d.restart - 1) / d.restart : 1);
       blocks += nb; segs += d.num_segs;
       if (blocks >= ((uint64_t)1 << 31) || segs >= ((uint64_t)1 << 31) || table0 + 8 * (mine.size() + 1) > 65000) { eligible = false; return true; }
+      if (kind >= kJpegAcFirst) {
+        // reset points: blocks in front of which the original file ended its end-of-band run (the host writer walks them with a cursor, so they count only in order)
+        d.reset_first = (uint32_t)(resets.size() + my_resets.size());
+        uint64_t last = 0;
+        for (size_t k = 0; k < s.reset_points.size(); k++) {
+          const uint64_t rp = s.reset_points[k];
+          if (k > 0 && rp <= last) { eligible = false; return true; }
+          last = rp;
+          if (rp < nb) my_resets.push_back((uint32_t)(d.first_block + rp));
+        }
+        d.reset_count = (uint32_t)(resets.size() + my_resets.size()) - d.reset_first;
+      }
       // table snapshots: eight slots per scan (tables are few hundred bytes; DHT markers between scans redefine slots)
       const uint32_t base = (uint32_t)(table0 + 8 * mine.size());
       for (uint32_t k = 0; k < s.num_components; k++) { d.dc[k] = (uint16_t)(base + d.dc[k]); d.ac[k] = (uint16_t)(base + d.ac[k]); }
@@ -2870,8 +2898,10 @@ void Batch::ReconstructJpegs(void* stream_v) {
         tables.push_back(hd);
       }
     }
-    m.device = true; m.first_scan = scans.size(); m.num_scans = mine.size();
+    m.device = true; m.progressive = progressive_scans; m.first_scan = scans.size(); m.num_scans = mine.size();
+    any_progressive = any_progressive || progressive_scans;
     scans.insert(scans.end(), mine.begin(), mine.end());
+    resets.insert(resets.end(), my_resets.begin(), my_resets.end());
     num_blocks = blocks; num_segs = segs;
   }
   // ---- arena: coefficients, tables, per-block and per-segment arrays (one allocation per batch object, kept like the other arenas)
@@ -2880,10 +2910,15 @@ void Batch::ReconstructJpegs(void* stream_v) {
   const size_t o_coef = take(total_blk * 128), o_scans = take(scans.size() * sizeof(JpegScanDev)), o_tables = take(tables.size() * sizeof(JpegHuffDev));
   const size_t o_bits = take(num_blocks * 4), o_bitpos = take((num_blocks + 1) * 8), o_segbits = take(num_segs * 4), o_segbytes = take(num_segs * 4);
   const size_t o_segoff = take((num_segs + 1) * 8), o_tile = take((std::max(num_blocks, num_segs) / 1024 + 1) * 8), o_flags = take((size_t)n * 4);
+  // progressive scans: per-block head / tail, flush flags, span numbers and first blocks, reset points
+  const size_t nprog = any_progressive ? num_blocks : 0;
+  const size_t o_meta = take(nprog * 4), o_flush = take(nprog * 4), o_spanidx = take(any_progressive ? (num_blocks + 1) * 8 : 0), o_spanfirst = take(nprog * 4);
+  const size_t o_resets = take(resets.size() * 4);
   DevReserve((void**)&djpeg_, &jpeg_cap_, std::max<size_t>(off, 256));
   if (!scans.empty()) {
     HIP_CHECK(hipMemcpyAsync(djpeg_ + o_scans, scans.data(), scans.size() * sizeof(JpegScanDev), hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(djpeg_ + o_tables, tables.data(), tables.size() * sizeof(JpegHuffDev), hipMemcpyHostToDevice, stream));
+    if (!resets.empty()) HIP_CHECK(hipMemcpyAsync(djpeg_ + o_resets, resets.data(), resets.size() * 4, hipMemcpyHostToDevice, stream));
   }
   HIP_CHECK(hipMemsetAsync(djpeg_ + o_flags, 0, (size_t)n * 4, stream));
   // ---- one entropy decode of the batch (LF stage: JPEG DC, block metadata; HF stage: AC), coefficients into JPEG layout
@@ -2909,6 +2944,9 @@ void Batch::ReconstructJpegs(void* stream_v) {
   wp.num_scans = (uint32_t)scans.size(); wp.num_blocks = (uint32_t)num_blocks; wp.num_segs = (uint32_t)num_segs;
   wp.bits = (uint32_t*)(djpeg_ + o_bits); wp.bitpos = (uint64_t*)(djpeg_ + o_bitpos); wp.seg_bits = (uint32_t*)(djpeg_ + o_segbits); wp.seg_bytes = (uint32_t*)(djpeg_ + o_segbytes);
   wp.seg_off = (uint64_t*)(djpeg_ + o_segoff); wp.tile_tmp = (uint64_t*)(djpeg_ + o_tile); wp.flags = (uint32_t*)(djpeg_ + o_flags);
+  wp.has_spans = any_progressive ? 1 : 0;
+  wp.meta = (uint32_t*)(djpeg_ + o_meta); wp.flush = (uint32_t*)(djpeg_ + o_flush); wp.span_idx = (uint64_t*)(djpeg_ + o_spanidx); wp.span_first = (uint32_t*)(djpeg_ + o_spanfirst);
+  wp.resets = (const uint32_t*)(djpeg_ + o_resets);
   LaunchJpegSizes(wp, stream_v);
   CheckLaunches("JPEG writer, sizes");
   vec<uint32_t> status;
@@ -2964,10 +3002,11 @@ void Batch::ReconstructJpegs(void* stream_v) {
         }
         return SpliceJpegScan(cx, segs.data(), segs.size(), out, err);
       }, &r.bytes, &why);
-      if (ok) { r.ok = true; jpeg_device_images_++; } else { r.bytes.clear(); r.error = why; }
+      if (ok) { r.ok = true; jpeg_device_images_++; jpeg_device_progressive_images_ += m.progressive ? 1 : 0; } else { r.bytes.clear(); r.error = why; }
       continue;
     }
-    // host writer: progressive scans, extra zero runs, "jpeg_host_writer" — and images the device flagged, whose error the host writer names
+    // host writer: progressive files (without "jpeg_device_progressive"), extra zero runs, "jpeg_host_writer" — and images the device flagged: the host writer
+    // names their error, or writes the span whose correction bits it flushes on its own
     vec<int16_t> host(m.nblk * 64);
     HIP_CHECK(hipMemcpy(host.data(), (const int16_t*)(djpeg_ + o_coef) + m.first_blk * 64, host.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
     const int16_t* planes[3] = {host.data(), host.data() + m.comp_first[1] * 64, host.data() + m.comp_first[2] * 64};

@@ -158,12 +158,15 @@ class Batch {
   bool CanReconstructJpeg(int i, std::string* why = nullptr);
   vec<uint8_t> ReconstructJpeg(int i, void* stream);
   // The same for every image of the batch from one run of the entropy stages.  Images whose scans are all sequential Huffman scans get their entropy-coded
-  // segments written on the device (jpeg_write.hip) and spliced between the markers on the host; progressive scans, scans with extra zero runs and
+  // segments written on the device (jpeg_write.hip) and spliced between the markers on the host; progressive files (unless jpeg_device_progressive), scans with extra zero runs and
   // cfg.jpeg_host_writer go through WriteJpeg, from coefficients copied to the host for those images only.  An image that cannot be reconstructed, or whose
   // stream is damaged, fails alone: jpeg_result(i).  Throws only for what concerns the whole batch (HIP errors, Prepare).
   struct JpegResult { bool ok = false; std::string error; vec<uint8_t> bytes; };
   void ReconstructJpegs(void* stream);
   bool jpeg_host_writer = false;          // every image through the host writer (tests, measurements)
+  // progressive files too get their scans written on the device where every scan is a first DC pass, a DC refinement, a first AC pass or an AC refinement of one
+  // component (DESIGN.md §5 lists what stays with the host writer); off: progressive files go through the host writer
+  bool jpeg_device_progressive = false;
   const JpegResult* jpeg_result(int i) const { return i >= 0 && (size_t)i < jpeg_results_.size() ? &jpeg_results_[(size_t)i] : nullptr; }
   void FinishStatus(void* stream, vec<uint32_t>* per_unit);
   // Copies frame i's pixels to host memory (after Finish).
@@ -235,7 +238,7 @@ class Batch {
   vec<LfTarget> lf_targets_;                   // (of the batch that decodes LF frames: per image, where its planes go)
   vec<std::unique_ptr<JpegData>> jpeg_data_;   // per image, parsed lazily by CanReconstructJpeg
   std::vector<JpegResult> jpeg_results_;       // per image, of the last ReconstructJpegs
-  int jpeg_device_images_ = 0, jpeg_host_images_ = 0;
+  int jpeg_device_images_ = 0, jpeg_host_images_ = 0, jpeg_device_progressive_images_ = 0;
   uint8_t* djpeg_ = nullptr; size_t jpeg_cap_ = 0;           // ReconstructJpegs: coefficient planes in JPEG layout, scan table, per-block / per-segment arrays
   uint8_t* djpeg_out_ = nullptr; size_t jpeg_out_cap_ = 0;   // ... raw and stuffed segment bytes, segment records
   bool any_complex_ = false;

@@ -1,4 +1,4 @@
-// jxl-hip: device-side writer of sequential Huffman JPEG scans (batch JPEG reconstruction, decoder.cc Batch::ReconstructJpegs).
+// jxl-hip: device-side writer of Huffman JPEG scans, sequential and progressive (batch JPEG reconstruction, decoder.cc Batch::ReconstructJpegs).
 // Input: the int16 coefficient planes JpegCoefKernel leaves in device memory (natural order, MCU-padded block grids).  Output: for every
 // restart segment of every eligible scan the byte-stuffed bytes of its complete bytes plus the bits of its last, incomplete byte; the host
 // pads that byte and splices the segments between the markers (jpeg_recon.cc SpliceJpegScan).
@@ -10,6 +10,17 @@
 //            every segment landed
 // Both passes derive a lane's code from JpegLaneCode, so the sizes of pass 1 are exactly what pass 2 writes; pass 2 checks every store
 // against the block's own bit count and the buffer size all the same.
+//
+// Progressive scans (JpegScanDev::kind; jpeg_recon.cc EncodeBlockProgressive / EncodeBlockRefinement / EobState are the reference).  The DC kinds are one piece in
+// lane 0.  In the AC kinds a block's trailing zeros do not end the block but join an end-of-band run that the canonical writer carries from block to block, together
+// with the correction bits of the blocks in the run.  Written per block that is: head (the bits the block emits itself) | EOBn, if the block heads a run | tail (the
+// correction bits it buffers), concatenated in plain block order.  A flush point is a block with a non-empty head, a reset point or the first block of a restart
+// segment; a span runs from one flush point to the next or to the segment's end; its joining blocks are the flush block, if it joins, and every block behind it; the
+// run heads are the joining blocks number 0, 0x7FFF, 2 * 0x7FFF, ... with n = min(0x7FFF, joining blocks left).
+//   pass 1   JpegBlockBitsKernel also leaves head / tail / joins (meta) and the flush flag of every block; ProgLaneCode is the shared definition of the four kinds
+//   spans    ScanU32 over the flush flags numbers the spans, JpegSpanScatterKernel lists their first blocks, JpegRunHeadKernel adds the EOBn symbol to the bits of
+//            every run head (RunHeadCode, shared with pass 2) and flags spans that hold more correction bits than the canonical writer buffers (65473)
+//   pass 2   JpegPackKernel writes head, EOBn and tail of a block at its bit position
 #include "kernels.h"
 #include <hip/hip_runtime.h>
 
@@ -98,13 +109,181 @@ __device__ inline LaneCode BlockLaneCode(const JpegWritePlan& p, const JpegScanD
   return JpegLaneCode(c, lane, ac_mask, pred, p.tables[r.dc], p.tables[r.ac]);
 }
 
+// ---- progressive kinds ------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kMetaHeadMask = 0xFFF, kMetaTailShift = 12, kMetaTailMask = 0xFF, kMetaJoins = 1u << 20;
+constexpr uint32_t kEobRunMax = 0x7FFF, kTailBitsMax = (1u << 16) - 64 + 1;     // EobState::BufferEndOfBand flushes at either
+
+__device__ inline uint32_t WaveExclusiveSum(uint32_t v, uint32_t lane, uint32_t* total) {
+  uint32_t incl = v;
+  for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d, 64); if ((int)lane >= d) incl += o; }
+  *total = __shfl(incl, 63, 64);
+  return incl - v;
+}
+__device__ inline uint64_t BitsBelow(uint32_t k) { return (1ull << k) - 1ull; }               // bits 0 .. k - 1, k <= 63
+__device__ inline uint64_t BitsUpTo(uint32_t k) { return (2ull << k) - 1ull; }                // bits 0 .. k, k <= 63
+
+// What lane `lane` (zigzag position) places in its block of a progressive scan.  In the head: piece A at a_off; rep_n ZRL codes and piece B from b_off on; one
+// correction bit at corr_off of the head or of the tail.  head / tail / joins are the block's (the same in every lane); err as in LaneCode.
+//   first DC pass   A = code of the difference of the shifted DC values (category >= 13 is the error)          DC refinement   A = bit Al of c0
+//   first AC pass   ZRLs and B = symbol + magnitude bits of |c| >> Al, the zero run counted inside the band; no end-of-block symbol
+//   AC refinement   a coefficient that becomes non-zero (|c| >> Al == 1) is a symbol (r << 4) + 1 and its sign, r = z & 15 with z the zeros since the previous such
+//                   coefficient; one that already was non-zero has one correction bit.  At a non-zero position up to the last new coefficient the writer has emitted
+//                   z >> 4 ZRLs since the previous symbol, so the position emits the difference to the non-zero position in front of it.  The correction bits ride
+//                   behind the first code emitted after them; those behind the last new coefficient are the tail.  So an emitting position ("event") writes
+//                   A (its first code) | the correction bits between the previous event and itself | B (further ZRLs, the symbol if a ZRL came first).
+struct ProgLane { uint32_t a_bits, a_len, a_off, rep_n, rep_code, rep_len, b_bits, b_len, b_off, corr_len, corr_bit, corr_off, corr_in_tail, head, tail, joins, err; };
+__device__ inline ProgLane ProgLaneCode(const JpegWritePlan& p, const JpegScanDev& s, const BlockRef& r, uint32_t lane) {
+  ProgLane o;
+  memset(&o, 0, sizeof(o));
+  const int c = p.coef[(size_t)r.blk * 64 + kJpegNatural[lane]];
+  if (s.kind == kJpegDcFirst || s.kind == kJpegDcRefine) {
+    const int pred = r.has_pred ? (int)p.coef[(size_t)r.pred * 64] : 0;
+    if (lane == 0) {
+      if (s.kind == kJpegDcRefine) { o.a_bits = (uint32_t)(c >> s.al) & 1u; o.a_len = 1; }
+      else {
+        int temp = (c >> s.al) - (pred >> s.al), temp2 = temp;
+        if (temp < 0) { temp = -temp; temp2--; }
+        const uint32_t nbits = temp ? 32 - __builtin_clz((uint32_t)temp) : 0;
+        const JpegHuffDev& dct = p.tables[r.dc];
+        if (nbits >= 13) o.err = 1;
+        else if (dct.depth[nbits] > 16) o.err = 4;
+        else {
+          const uint32_t d = dct.depth[nbits];
+          o.a_bits = (((uint32_t)dct.code[nbits] & ((1u << d) - 1u)) << nbits) | ((uint32_t)temp2 & ((1u << nbits) - 1u));
+          o.a_len = d + nbits;
+        }
+      }
+    }
+    o.head = __shfl(o.a_len, 0, 64);
+    return o;
+  }
+  const JpegHuffDev& act = p.tables[r.ac];
+  const bool in_band = lane >= s.ss && lane <= s.se;
+  const uint32_t a = in_band ? (uint32_t)(c < 0 ? -c : c) >> s.al : 0;
+  const uint64_t low = BitsBelow(lane);
+  if (s.kind == kJpegAcFirst) {
+    const uint64_t mask = __ballot(a != 0);
+    if (a) {
+      const uint32_t nbits = 32 - __builtin_clz(a);
+      const uint64_t below = mask & low;
+      const uint32_t prev = below ? 63 - __builtin_clzll(below) : s.ss - 1u, run = lane - prev - 1;
+      const uint32_t sym = ((run & 15) << 4) | (nbits & 15), d = act.depth[sym];
+      o.rep_n = run >> 4;
+      if (o.rep_n) { o.rep_len = act.depth[0xF0]; o.rep_code = act.code[0xF0] & ((1u << (o.rep_len & 31)) - 1u); }
+      if (nbits >= 16) { o.rep_n = o.rep_len = 0; o.err = 2; }
+      else if (d > 16 || o.rep_len > 16) { o.rep_n = o.rep_len = 0; o.err = 4; }
+      else {
+        const uint32_t temp2 = c < 0 ? ~a : a;
+        o.b_bits = (((uint32_t)act.code[sym] & ((1u << d) - 1u)) << nbits) | (temp2 & ((1u << nbits) - 1u));
+        o.b_len = d + nbits;
+      }
+    }
+    o.b_off = WaveExclusiveSum(o.rep_n * o.rep_len + o.b_len, lane, &o.head);
+    o.joins = mask == 0 || 63u - (uint32_t)__builtin_clzll(mask) < s.se;
+    return o;
+  }
+  // AC refinement
+  const bool is_new = a == 1, is_old = a > 1;
+  const uint64_t newm = __ballot(is_new), oldm = __ballot(is_old), nzm = newm | oldm;
+  const uint64_t zerom = BitsUpTo(s.se) & ~BitsBelow(s.ss) & ~nzm;
+  const uint32_t eob = newm ? 63 - __builtin_clzll(newm) : 0;
+  if ((is_new || is_old) && lane <= eob) {
+    const uint64_t lastnew = newm & low;
+    const uint32_t ln = lastnew ? 63 - __builtin_clzll(lastnew) : s.ss - 1u;
+    const uint64_t since = low & ~BitsUpTo(ln);                       // positions behind the previous new coefficient, in front of this one
+    const uint32_t z = __builtin_popcountll(zerom & since);
+    const uint64_t pn = nzm & since;
+    const uint32_t zprev = pn ? __builtin_popcountll(zerom & since & BitsBelow(63 - __builtin_clzll(pn))) : 0;
+    const uint32_t nz = (z >> 4) - (zprev >> 4);
+    const uint32_t zl = act.depth[0xF0], zc = act.code[0xF0] & ((1u << (zl & 31)) - 1u);
+    uint32_t piece = 0, plen = 0;
+    if (is_new) {
+      const uint32_t sym = ((z & 15) << 4) | 1, d = act.depth[sym];
+      if (d > 16) o.err = 4;
+      else { piece = (((uint32_t)act.code[sym] & ((1u << d) - 1u)) << 1) | (c < 0 ? 0u : 1u); plen = d + 1; }
+    }
+    if (nz && zl > 16) o.err = 4;
+    if (!o.err) {
+      if (nz) { o.a_bits = zc; o.a_len = zl; o.rep_n = nz - 1; o.rep_code = zc; o.rep_len = zl; o.b_bits = piece; o.b_len = plen; }
+      else { o.a_bits = piece; o.a_len = plen; }
+    }
+  }
+  uint32_t sum;
+  const uint32_t ex = WaveExclusiveSum(o.a_len + o.rep_n * o.rep_len + o.b_len, lane, &sum);
+  const uint64_t eventm = __ballot(o.a_len != 0), tailm = oldm & ~BitsUpTo(eob);
+  o.head = sum + (newm ? (uint32_t)__builtin_popcountll(oldm & BitsBelow(eob)) : 0);
+  o.tail = __builtin_popcountll(tailm);
+  o.joins = newm == 0 || eob < s.se;
+  const uint64_t pem = eventm & low;
+  const uint32_t olds_below = __builtin_popcountll(oldm & low);
+  o.a_off = ex + (pem ? (uint32_t)__builtin_popcountll(oldm & BitsBelow(63 - __builtin_clzll(pem))) : 0);
+  o.b_off = ex + o.a_len + olds_below;
+  const uint64_t later = eventm & ~BitsUpTo(lane);
+  const uint32_t ne = later ? (uint32_t)__builtin_ctzll(later) : lane;
+  const uint32_t ex_ne = __shfl(ex, ne, 64), a_ne = __shfl(o.a_len, ne, 64);
+  if (is_old) {
+    o.corr_len = 1; o.corr_bit = a & 1;
+    if (newm && lane < eob) o.corr_off = ex_ne + a_ne + olds_below;
+    else { o.corr_in_tail = 1; o.corr_off = __builtin_popcountll(tailm & low); }
+  }
+  return o;
+}
+
+__device__ inline bool IsResetPoint(const JpegWritePlan& p, const JpegScanDev& s, uint32_t b) {
+  uint32_t lo = s.reset_first, hi = s.reset_first + s.reset_count;
+  while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; const uint32_t v = p.resets[mid]; if (v == b) return true; if (v < b) lo = mid + 1; else hi = mid; }
+  return false;
+}
+
+// The EOBn symbol of block `b` of an AC progressive scan, if it heads an end-of-band run (len 0 otherwise).  From the span table: the block's span starts at the
+// last flush point f <= b and ends at the next one or at the end of the restart segment.  with_tails (span pass only, where bitpos still holds the scan of
+// head + tail): the run head of the span's first run also sums the span's correction bits — behind f every block of the span has an empty head — and reports 8
+// when they exceed what the canonical writer buffers before it flushes on its own.
+struct RunHead { uint32_t bits, len, err; };
+__device__ inline RunHead RunHeadCode(const JpegWritePlan& p, const JpegScanDev& s, const BlockRef& r, uint32_t b, bool with_tails) {
+  RunHead o = {0, 0, 0};
+  const uint64_t incl = p.span_idx[b] + p.flush[b], nspans = p.span_idx[p.num_blocks];
+  if (incl == 0 || incl > nspans) return o;
+  const uint32_t f = p.span_first[incl - 1];
+  const uint64_t per = s.restart ? (uint64_t)s.restart * s.blocks_per_mcu : s.num_blocks;
+  const uint64_t scan_end = (uint64_t)s.first_block + s.num_blocks, seg_end = r.seg_first + per < scan_end ? r.seg_first + per : scan_end;
+  uint64_t e = incl < nspans ? p.span_first[incl] : p.num_blocks;
+  if (e > seg_end) e = seg_end;
+  if (f > b || f < r.seg_first || e <= b) return o;        // (cannot happen: a segment's first block is a flush point)
+  const uint32_t mf = p.meta[f];
+  const uint32_t first = (mf & kMetaJoins) ? f : f + 1;
+  if (b < first || (b - first) % kEobRunMax) return o;
+  const uint32_t left = (uint32_t)(e - b), n = left < kEobRunMax ? left : kEobRunMax;
+  const uint32_t nbits = 31 - __builtin_clz(n);
+  const JpegHuffDev& act = p.tables[r.ac];
+  const uint32_t d = act.depth[nbits << 4];
+  if (d > 16) { o.err = 4; return o; }
+  o.bits = (((uint32_t)act.code[nbits << 4] & ((1u << d) - 1u)) << nbits) | (n & ((1u << nbits) - 1u));
+  o.len = d + nbits;
+  if (with_tails && b == first && p.bitpos[e] - p.bitpos[f] - (mf & kMetaHeadMask) > kTailBitsMax) o.err = 8;
+  return o;
+}
+
 // ---- pass 1: bits per block ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void JpegBlockBitsKernel(JpegWritePlan p) {
   const uint32_t b = blockIdx.x * 4 + threadIdx.x / 64, lane = threadIdx.x & 63;
   if (b >= p.num_blocks) return;
   const JpegScanDev& s = FindScan<false>(p.scans, p.num_scans, b);
+  if (p.has_spans && lane == 0) { p.meta[b] = 0; p.flush[b] = 0; }
   if (*p.frames[s.frame].status != 0) { if (lane == 0) p.bits[b] = 0; return; }      // (a frame whose entropy stages failed has no coefficients)
   const BlockRef r = LocateBlock(s, b);
+  if (s.kind != kJpegSequential) {
+    const ProgLane pl = ProgLaneCode(p, s, r, lane);
+    uint32_t err = pl.err;
+    for (int d = 32; d >= 1; d >>= 1) err |= __shfl_xor(err, d, 64);
+    if (lane == 0) {
+      p.bits[b] = pl.head + pl.tail;
+      p.meta[b] = (pl.head & kMetaHeadMask) | ((pl.tail & kMetaTailMask) << kMetaTailShift) | (pl.joins ? kMetaJoins : 0);
+      if (s.kind >= kJpegAcFirst) p.flush[b] = pl.head != 0 || b == r.seg_first || IsResetPoint(p, s, b);
+      if (err) atomicOr(&p.flags[s.image], err);
+    }
+    return;
+  }
   const LaneCode lc = BlockLaneCode(p, s, r, lane);
   uint32_t n = lc.zrl_n * lc.zrl_len + lc.len, err = lc.err;
   for (int d = 32; d >= 1; d >>= 1) { n += __shfl_xor(n, d, 64); err |= __shfl_xor(err, d, 64); }
@@ -112,6 +291,23 @@ __global__ __launch_bounds__(256) void JpegBlockBitsKernel(JpegWritePlan p) {
     p.bits[b] = n;
     if (err) atomicOr(&p.flags[s.image], err);
   }
+}
+
+// ---- spans of the AC progressive kinds: first blocks, then the EOBn symbols of the run heads -------------------------------------------------
+__global__ __launch_bounds__(256) void JpegSpanScatterKernel(JpegWritePlan p) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= p.num_blocks || !p.flush[b]) return;
+  const uint64_t k = p.span_idx[b];
+  if (k < p.num_blocks) p.span_first[k] = b;
+}
+__global__ __launch_bounds__(256) void JpegRunHeadKernel(JpegWritePlan p) {
+  const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= p.num_blocks) return;
+  const JpegScanDev& s = FindScan<false>(p.scans, p.num_scans, b);
+  if (s.kind < kJpegAcFirst || *p.frames[s.frame].status != 0) return;
+  const RunHead h = RunHeadCode(p, s, LocateBlock(s, b), b, true);
+  if (h.len) p.bits[b] += h.len;
+  if (h.err) atomicOr(&p.flags[s.image], h.err);
 }
 
 // ---- exclusive scan of n uint32 values into n + 1 uint64 (out[n] = total): tiles of 1024 ------------------------------------------------
@@ -204,6 +400,30 @@ __global__ __launch_bounds__(256) void JpegPackKernel(JpegWritePlan p, uint32_t*
   const uint32_t block_bits = p.bits[b];
   if (block_bits == 0) return;
   const BlockRef r = LocateBlock(s, b);
+  if (s.kind != kJpegSequential) {
+    const ProgLane pl = ProgLaneCode(p, s, r, lane);
+    const uint32_t meta = p.meta[b], head = meta & kMetaHeadMask, tail = (meta >> kMetaTailShift) & kMetaTailMask;
+    // (cannot happen: both passes count the same code) head | EOBn | tail are the block's own bits, and every store below stays inside its part
+    if (pl.head != head || pl.tail != tail || head + tail > block_bits) return;
+    const uint32_t eob_len = block_bits - head - tail;
+    const uint64_t base = p.seg_off[r.seg] * 8 + (p.bitpos[b] - p.bitpos[r.seg_first]);
+    if (base + block_bits > raw_words * 32) return;
+    if (pl.a_len && pl.a_off + pl.a_len <= head) PutBits(raw, base + pl.a_off, pl.a_bits, pl.a_len, raw_words);
+    if (pl.b_off + pl.rep_n * pl.rep_len + pl.b_len <= head) {
+      uint64_t pos = base + pl.b_off;
+      for (uint32_t k = 0; k < pl.rep_n; k++) { PutBits(raw, pos, pl.rep_code, pl.rep_len, raw_words); pos += pl.rep_len; }
+      if (pl.b_len) PutBits(raw, pos, pl.b_bits, pl.b_len, raw_words);
+    }
+    if (pl.corr_len && pl.corr_bit) {
+      if (!pl.corr_in_tail) { if (pl.corr_off < head) PutBits(raw, base + pl.corr_off, 1, 1, raw_words); }
+      else if (pl.corr_off < tail) PutBits(raw, base + head + eob_len + pl.corr_off, 1, 1, raw_words);
+    }
+    if (lane == 0 && eob_len && s.kind >= kJpegAcFirst) {
+      const RunHead h = RunHeadCode(p, s, r, b, false);
+      if (h.len == eob_len) PutBits(raw, base + head, h.bits, h.len, raw_words);
+    }
+    return;
+  }
   const LaneCode lc = BlockLaneCode(p, s, r, lane);
   const uint32_t n = lc.zrl_n * lc.zrl_len + lc.len;
   uint32_t incl = n;
@@ -271,6 +491,12 @@ void LaunchJpegSizes(const JpegWritePlan& p, void* stream_v) {
   hipStream_t stream = (hipStream_t)stream_v;
   if (!p.num_blocks || !p.num_segs) return;
   hipLaunchKernelGGL(JpegBlockBitsKernel, dim3((p.num_blocks + 3) / 4), dim3(256), 0, stream, p);
+  if (p.has_spans) {
+    ScanU32(p.bits, p.num_blocks, p.bitpos, p.tile_tmp, stream);          // head + tail: the span pass takes a span's correction bits from it
+    ScanU32(p.flush, p.num_blocks, p.span_idx, p.tile_tmp, stream);
+    hipLaunchKernelGGL(JpegSpanScatterKernel, dim3((p.num_blocks + 255) / 256), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(JpegRunHeadKernel, dim3((p.num_blocks + 255) / 256), dim3(256), 0, stream, p);
+  }
   ScanU32(p.bits, p.num_blocks, p.bitpos, p.tile_tmp, stream);
   hipLaunchKernelGGL(JpegSegBytesKernel, dim3((p.num_segs + 255) / 256), dim3(256), 0, stream, p);
   ScanU32(p.seg_bytes, p.num_segs, p.seg_off, p.tile_tmp, stream);

@@ -1012,6 +1012,7 @@ void JxlHipBatchSetOption(JxlHipBatch* h, const char* name, int value) {
   else if (n == "lds_code_budget" && value >= 0 && value <= 128 * 1024) h->b->cfg.lds_code_budget = value & ~15;
   else if (n == "lf_force_big" && value >= -1 && value <= 2) h->b->cfg.lf_force_big = value;
   else if (n == "jpeg_host_writer") h->b->jpeg_host_writer = value != 0;   // JxlHipBatchReconstructJpegs: every image through the host's Huffman writer
+  else if (n == "jpeg_device_progressive") h->b->jpeg_device_progressive = value != 0;   // ... progressive files written by the device as well (jpeg_host_writer wins)
   else if (n == "hf_lanes_per_wave" && value >= 0 && value <= 64) h->b->cfg.hf_lanes_per_wave = value;   // SIMT HF stage: group streams per wavefront (1: the wave-wide kernel where it applies); 0: the throughput packing
 }
 size_t JxlHipBatchDebugRead(JxlHipBatch* h, int index, const char* name, int channel, void* dst, size_t cap, void* s) {

@@ -314,27 +314,42 @@ void LaunchWrite(const WriteArgs& a, void* stream);
 // chroma-from-luma of the transcoder undone (dec_group.cc, jpeg branch).  qt: the JPEG quantisation tables, natural order.
 struct JpegCoefArgs { int16_t* out; uint32_t ncomp; int32_t qt[3][64]; uint32_t comp_off[3]; };   // comp_off: first block of a component's plane (subsampled frames)
 void LaunchJpegCoefficients(const FrameDev* frames, int fidx, const JpegCoefArgs& a, uint32_t bw, uint32_t bh, void* stream);
-// ---- device-side writer of sequential Huffman JPEG scans (jpeg_write.hip).  One JpegScanDev per (image, scan) of the batch that takes the device path: the blocks
+// ---- device-side writer of Huffman JPEG scans (jpeg_write.hip).  One JpegScanDev per (image, scan) of the batch that takes the device path: the blocks
 // of all scans, and their restart segments, are numbered through in table order (first_block / first_seg).
+// kind: what a block of the scan codes.  Sequential: DC difference, AC coefficients, end of block.  The four progressive kinds (spectral band Ss..Se, successive
+// approximation Ah / Al): first DC pass (difference of c0 >> Al), DC refinement (one bit), first AC pass (|c| >> Al of the band; trailing zeros join an end-of-band
+// run), AC refinement (newly non-zero coefficients as symbols, one correction bit for every coefficient that already was non-zero).
+enum JpegScanKind : uint32_t { kJpegSequential = 0, kJpegDcFirst = 1, kJpegDcRefine = 2, kJpegAcFirst = 3, kJpegAcRefine = 4 };
 struct JpegScanDev {
   uint32_t first_block, num_blocks, first_seg, num_segs;
   uint32_t frame, image;                 // FrameDev whose status word says whether the coefficients exist; slot of the per-image error flags
   uint32_t ncomp, blocks_per_mcu, scan_cols, restart;   // restart: MCUs per restart segment, 0 = the scan is one segment
   uint32_t plane[4], pitch[4];           // per scan component: first block of its coefficient plane in the batch's arena, blocks per plane row
   uint8_t h[4], v[4]; uint16_t dc[4], ac[4];      // blocks per MCU across / down (1 x 1 in a single-component scan); Huffman tables, as indices into JpegWritePlan::tables
+  uint32_t kind;                         // JpegScanKind
+  uint8_t ss, se, ah, al;
+  uint32_t reset_first, reset_count;     // AC kinds: the scan's reset points in JpegWritePlan::resets (batch block numbers, ascending)
 };
 struct JpegHuffDev { uint8_t depth[256]; uint16_t code[256]; };      // one table slot as defined at one scan (depth 127: no code)
 struct JpegSegDev { uint64_t offset; uint32_t size, trail; };        // a restart segment in the stuffed buffer; trail: (last incomplete byte << 8) | its bit count
 struct JpegWritePlan {
   const FrameDev* frames; const JpegScanDev* scans; const JpegHuffDev* tables; const int16_t* coef;
-  uint32_t num_scans, num_blocks, num_segs, pad;
-  uint32_t* bits;          // [num_blocks] pass 1
+  uint32_t num_scans, num_blocks, num_segs;
+  uint32_t has_spans;      // some scan is of a progressive kind: the span pass runs and the arrays at the end exist
+  uint32_t* bits;          // [num_blocks] pass 1 (progressive AC kinds: head + tail; the span pass adds the EOBn symbol of a run head)
   uint64_t* bitpos;        // [num_blocks + 1] exclusive scan of bits
   uint32_t* seg_bits;      // [num_segs]
   uint32_t* seg_bytes;     // [num_segs] = ceil(seg_bits / 8): every segment starts on a byte
   uint64_t* seg_off;       // [num_segs + 1] exclusive scan of seg_bytes; the last entry is the size of the raw (unstuffed) buffer
   uint64_t* tile_tmp;      // [ceil(max(num_blocks, num_segs) / 1024)] scratch of the scans
-  uint32_t* flags;         // per image: 1 DC category >= 12, 2 AC category >= 16, 4 symbol without a code (zeroed by the caller)
+  uint32_t* flags;         // per image: 1 DC category out of range, 2 AC category >= 16, 4 symbol without a code, 8 a span's correction bits exceed what the
+                           // canonical writer buffers (zeroed by the caller); any of them sends the image through the host writer
+  // progressive scans (jpeg_write.hip, "spans"): a block's code is head | EOBn if it heads an end-of-band run | tail
+  uint32_t* meta;          // [num_blocks] head bits | tail bits << 12 | joins the end-of-band run << 20
+  uint32_t* flush;         // [num_blocks] 1: a flush point (the block emits bits of its own, is a reset point or starts a restart segment); 0 elsewhere and outside AC kinds
+  uint64_t* span_idx;      // [num_blocks + 1] exclusive scan of flush: spans in front of a block
+  uint32_t* span_first;    // [num_blocks] the flush points in order: first block of every span
+  const uint32_t* resets;  // reset points of all scans
 };
 struct JpegPackBuffers {
   uint8_t* raw; uint64_t raw_bytes;        // = seg_off[num_segs], read back by the host; allocated up to the next multiple of 4

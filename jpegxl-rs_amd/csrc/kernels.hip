@@ -5934,7 +5934,8 @@ __global__ void ModularOutputKernel(const FrameDev* __restrict__ frames, int fid
 // launchers
 // =====================================================================================================================
 const char* const kKernelNames[] = {"LfDecodeKernel", "LfDequantKernel", "LfSmoothKernel", "LlfSigmaKernel", "HfDecodeKernel", "IdctKernel",
-                                    "GaborishKernel", "EpfTileKernel", "OutputKernel", "ModularGlobalFastKernel", "ModularGroupFastKernel", nullptr};
+                                    "GaborishKernel", "EpfTileKernel", "OutputKernel", "ModularGlobalFastKernel", "ModularGroupFastKernel", "JpegSpanScatterKernel",
+                                    "JpegRunHeadKernel", nullptr};
 
 // (per device, once; decoders of several host threads may get here at the same time)
 static std::mutex g_tables_mu;

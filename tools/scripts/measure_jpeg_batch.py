@@ -4,17 +4,23 @@
 Input: --files baseline 4:2:0 JPEGs of --width x --height, written at run time by Pillow from tests/jpeg_cases.photo (--distinct different pictures, cycled) and
 turned into JPEG XL by tests/jpeg_tools.transcode.  Legs (--legs, comma separated):
 
-  device   BatchDecoder.reconstruct_jpegs(): one entropy run, sequential scans entropy-coded on the GPU
+  device   BatchDecoder.reconstruct_jpegs(): one entropy run, sequential scans entropy-coded on the GPU (progressive files: on the host)
+  device_progressive   reconstruct_jpegs(progressive_on_device=True), i.e. JxlHipBatchSetOption("jpeg_device_progressive", 1): progressive scans entropy-coded on the GPU as well
   host     the same call with JxlHipBatchSetOption("jpeg_host_writer", 1): one entropy run, every file Huffman-coded on one host thread
   single   decoder_builder().reconstruct() file by file
 
 Every leg adds the files to its decoder, reconstructs and fetches the bytes, --reps times after --warmup; the median is reported as ms per batch and files/s, and
 the bytes are compared with the source files once.  Prints one JSON line.  --legs single runs nothing of the batch interface: with PYTHONPATH pointing at a build
-of an earlier commit the same script measures that build — the baseline the batch call is judged against."""
+of an earlier commit the same script measures that build — the baseline the batch call is judged against.
+
+--progressive: the input files are progressive (Pillow's default scan script: ten scans, spectral selection and successive approximation).  The baseline of the
+device_progressive leg is the device leg of the parent build (PYTHONPATH, --legs device), whose batch call codes these files on the host.
+--cache DIR keeps the input files and their transcodes (the parser of tests/jpeg_tools.py is plain Python and slow on large files) for the next run."""
 import argparse
 import io
 import json
 import os
+import pickle
 import sys
 import time
 
@@ -38,29 +44,43 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--legs", default="device,host,single")
+    ap.add_argument("--progressive", action="store_true")
+    ap.add_argument("--cache", default=None)
     args = ap.parse_args()
     from PIL import Image
     import jpeg_cases as JC
     import jpeg_tools as J
     import jpegxl_rs_amd as jx
-    jpegs = []
-    for k in range(args.distinct):
-        buf = io.BytesIO()
-        Image.fromarray(JC.photo(args.width, args.height, seed=100 + k)).save(buf, "JPEG", quality=args.quality, subsampling=2)
-        jpegs.append(buf.getvalue())
-    jxls = [J.transcode(d) for d in jpegs]
+    cached = args.cache and os.path.join(args.cache, "jpeg_batch_%dx%d_q%d_n%d%s.pickle" % (args.width, args.height, args.quality, args.distinct, "_progressive" if args.progressive else ""))
+    if cached and os.path.exists(cached):
+        with open(cached, "rb") as f:
+            jpegs, jxls = pickle.load(f)
+    else:
+        jpegs = []
+        for k in range(args.distinct):
+            buf = io.BytesIO()
+            Image.fromarray(JC.photo(args.width, args.height, seed=100 + k)).save(buf, "JPEG", quality=args.quality, subsampling=2, progressive=args.progressive)
+            jpegs.append(buf.getvalue())
+        jxls = [J.transcode(d) for d in jpegs]
+        if cached:
+            os.makedirs(args.cache, exist_ok=True)
+            with open(cached, "wb") as f:
+                pickle.dump((jpegs, jxls), f)
     files = [jpegs[k % args.distinct] for k in range(args.files)]
     inputs = [jxls[k % args.distinct] for k in range(args.files)]
-    out = {"what": "JPEG reconstruction, files per second", "files": args.files, "distinct": args.distinct, "size": [args.width, args.height], "quality": args.quality,
+    out = {"what": "JPEG reconstruction, files per second", "files": args.files, "distinct": args.distinct, "size": [args.width, args.height], "quality": args.quality, "progressive": args.progressive,
            "jpeg_bytes": sum(len(f) for f in files), "package": os.path.dirname(os.path.abspath(jx.__file__))}
 
-    def batch_leg(host_writer):
+    def batch_leg(host_writer, progressive_on_device=False):
         b = jx.BatchDecoder(0)
         if host_writer:
             b.set_option("jpeg_host_writer", 1)
         for d in inputs:
             b.add(d)
-        b.reconstruct_jpegs()
+        if progressive_on_device:
+            b.reconstruct_jpegs(progressive_on_device=True)
+        else:
+            b.reconstruct_jpegs()
         got = [b.jpeg(i) for i in range(len(inputs))]
         counts = (b.info_value("jpeg_device_images"), b.info_value("jpeg_host_images"))
         del b
@@ -71,7 +91,7 @@ def main():
         return [dec.reconstruct(d)[1][1] for d in inputs], None
 
     for leg in args.legs.split(","):
-        run = single_leg if leg == "single" else (lambda h=(leg == "host"): batch_leg(h))
+        run = single_leg if leg == "single" else (lambda h=(leg == "host"), p=(leg == "device_progressive"): batch_leg(h, p))
         times, counts = [], None
         for r in range(args.warmup + args.reps):
             t0 = time.perf_counter()

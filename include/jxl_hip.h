@@ -291,6 +291,28 @@ JxlDecoderStatus JxlHipBatchOutBufferSizeResized(const JxlHipBatch* batch, int i
                                                  const JxlHipOutputResize* resize, size_t* size);
 JxlDecoderStatus JxlHipBatchSetOutputResized(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout,
                                              const JxlHipOutputResize* resize);
+/* ---- resampled output: the resize above with a filter and a mirror of the image's own --------------------------------------------------------------------
+ * JxlHipOutputResample is JxlHipOutputResize — same meaning of xsize, ysize and the crop, same refusals — with two more choices:
+ *   filter   0 = the antialiased triangle filter of JxlHipOutputResize; 1 = antialiased cubic convolution with a = -0.5, the filter of Pillow's BICUBIC resize and of
+ *            torch.nn.functional.interpolate(mode="bicubic", antialias=True, align_corners=False).  Any other value is refused.
+ *            Both are one rule per axis with a kernel k of radius r (triangle: k(x) = max(0, 1 - |x|), r = 1; cubic: k(x) = ((a + 2)|x| - (a + 3))|x|^2 + 1 for |x| < 1,
+ *            a(((|x| - 5)|x| + 8)|x| - 4) for 1 <= |x| < 2, 0 beyond, r = 2): with n_in source and n_out target samples, scale = n_in / n_out, s = max(scale, 1), target
+ *            sample i is centred at c = scale x (i + 0.5) and takes the source samples j of [max(0, int(c - r x s + 0.5)), min(n_in, int(c + r x s + 0.5))) with the weights
+ *            k((j - c + 0.5) / s) over their sum: at the edges the range is cut and the weights renormalised.  Weights are computed and normalised in double and rounded
+ *            to float32 once; the sums are float32, horizontally then vertically.  The cubic's negative lobes let a float result leave the range of its samples; integer
+ *            sample types clamp it.  A target of the source's size is a bit-exact copy with either filter.
+ *   mirror   target column ox of the resampled picture is stored at column xsize - 1 - ox: a horizontal flip of the finished target, after crop, orientation and
+ *            resize — exactly the output without mirror with its columns reversed, in every sample type and layout.
+ * filter = 0, mirror = 0 is the ...Resized call, byte for byte.  A pipeline job takes one JxlHipOutputResample per image (each[i] belongs to image i): crop, filter and
+ * mirror are the image's own; xsize x ysize must be the same in all n entries (the destinations are slices of one tensor, JxlHipImageOutSizeResized bytes each), else the
+ * submission is refused, as it is for a NULL `each`, a filter above 1 and everything JxlHipPipelineSubmitResized refuses.  An image its crop leaves fails alone.
+ * The resizes of one decode are launched together: one launch pair (horizontal, vertical) per group of images with the same number of channel slots.
+ * JxlHipBatchGetInfo(batch, "resize_launches") is the number of resize launches of the last decode. */
+typedef struct { uint32_t xsize, ysize, crop_x0, crop_y0, crop_xsize, crop_ysize; uint32_t filter; JXL_BOOL mirror; } JxlHipOutputResample;
+JxlDecoderStatus JxlHipBatchOutBufferSizeResampled(const JxlHipBatch* batch, int index, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout,
+                                                   const JxlHipOutputResample* resample, size_t* size);
+JxlDecoderStatus JxlHipBatchSetOutputResampled(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout,
+                                               const JxlHipOutputResample* resample);
 /* JPEG bit-stream reconstruction of a whole batch (jpegxl-rs decode.rs:493 `reconstruct`, for many files at once).  JxlHipBatchCanReconstructJpeg: 1 if image
  * `index` is a lossless JPEG transcode with usable reconstruction data (a `jbrd` box whose markers find their ICC / Exif / XMP payloads, a Huffman-coded source),
  * else 0 with the reason in JxlHipLastError().  JxlHipBatchReconstructJpegs runs the LF and HF entropy stages once for all images of the batch (it prepares the batch
@@ -392,6 +414,9 @@ int64_t JxlHipPipelineSubmitLayout(JxlHipPipeline* pipeline, const uint8_t* cons
  * image of the job.  An image the crop leaves fails alone. */
 int64_t JxlHipPipelineSubmitResized(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
                                     void* const* host_out, const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResize* resize);
+/* The same with a resample per image (JxlHipOutputResample above, n entries; every entry the same xsize x ysize). */
+int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
+                                      void* const* host_out, const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each);
 /* Waits until the job has left the GPU (pixels written, host copies done).  image_status[i] (n entries, optional): 0 decoded, 1 failed; *end_ms (optional): when the
  * job's last byte was written, ms after JxlHipPipelineResetClock.  JXL_DEC_SUCCESS if every image decoded, else JXL_DEC_ERROR (JxlHipLastError names the first).
  * A ticket can be waited for once; jobs complete in submission order. */

@@ -104,6 +104,11 @@ class JxlHipOutputResize(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("xsize", "ysize", "crop_x0", "crop_y0", "crop_xsize", "crop_ysize")]
 
 
+class JxlHipOutputResample(C.Structure):
+    """include/jxl_hip.h JxlHipOutputResample: JxlHipOutputResize with a filter (0 triangle, 1 cubic) and a mirror of the image's own"""
+    _fields_ = [(n, C.c_uint32) for n in ("xsize", "ysize", "crop_x0", "crop_y0", "crop_xsize", "crop_ysize", "filter")] + [("mirror", C.c_int)]
+
+
 assert C.sizeof(JxlBasicInfo) == 204 and C.sizeof(JxlPixelFormat) == 24 and C.sizeof(JxlMemoryManager) == 24
 
 _lib = None
@@ -178,6 +183,10 @@ def libjxl():
                                                         C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResize)]),
             "JxlHipImageOutSizeResized": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResize), C.POINTER(JxlBasicInfo),
                                                     C.POINTER(sz)]),
+            "JxlHipBatchOutBufferSizeResampled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(sz)]),
+            "JxlHipBatchSetOutputResampled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), vp, C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample)]),
+            "JxlHipPipelineSubmitResampled": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.c_int,
+                                                          C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample)]),
             "JxlHipBatchCanReconstructJpeg": (C.c_int, [vp, C.c_int]), "JxlHipBatchReconstructJpegs": (C.c_int, [vp, vp]),
             "JxlHipBatchJpegStatus": (C.c_int, [vp, C.c_int]), "JxlHipBatchJpegSize": (sz, [vp, C.c_int]), "JxlHipBatchCopyJpeg": (C.c_int, [vp, C.c_int, vp, sz]),
             "JxlHipBatchSetLaneStride": (None, [vp, C.c_int, C.c_int]), "JxlHipBatchSetOption": (None, [vp, C.c_char_p, C.c_int]),
@@ -640,6 +649,43 @@ def _resize(resize, crop):
     return JxlHipOutputResize(w, h, x0, y0, cw, ch)
 
 
+_FILTERS = {"bilinear": 0, "bicubic": 1}
+
+
+def _filter_id(filter):
+    """"bilinear" (the antialiased triangle filter) / "bicubic" (antialiased cubic convolution, a = -0.5), or the number include/jxl_hip.h gives them"""
+    if filter is None:
+        return 0
+    if isinstance(filter, str):
+        if filter not in _FILTERS:
+            raise ValueError(f"filter must be one of {sorted(_FILTERS)}, not {filter!r}")
+        return _FILTERS[filter]
+    return int(filter)
+
+
+def _resample(resize, crop, filter, mirror):
+    """-> JxlHipOutputResample: _resize() with the filter and the mirror (both need resize)"""
+    if resize is None:
+        raise ValueError("crop, filter and mirror need resize=(width, height)")
+    rs = _resize(resize, crop)
+    f = _filter_id(filter)
+    if not 0 <= f < 1 << 32:
+        raise ValueError("filter must fit 32 unsigned bits")
+    return JxlHipOutputResample(rs.xsize, rs.ysize, rs.crop_x0, rs.crop_y0, rs.crop_xsize, rs.crop_ysize, f, 1 if mirror else 0)
+
+
+def _per_image(value, n, is_one):
+    """one value for the job, or a sequence of n per-image values -> (list of n, whether it was a sequence)"""
+    if value is None or isinstance(value, (str, bytes)) or not hasattr(value, "__iter__"):
+        return [value] * n, False
+    vals = list(value)                      # (any iterable, a generator included)
+    if is_one(vals):
+        return [tuple(vals)] * n, False
+    if len(vals) != n:
+        raise ValueError(f"a per-image sequence needs {n} entries, not {len(vals)}")
+    return vals, True
+
+
 def _byref(s):
     return None if s is None else C.byref(s)
 
@@ -670,7 +716,9 @@ class BatchDecoder:
 
     def _set_output(self, i, fmt, device_ptr, downscale, layout=None, resize=None):
         L = libjxl()
-        if resize is not None:
+        if isinstance(resize, JxlHipOutputResample):
+            self._chk(L.JxlHipBatchSetOutputResampled(self._h, i, C.byref(fmt), device_ptr, int(downscale), _byref(layout), C.byref(resize)))
+        elif resize is not None:
             self._chk(L.JxlHipBatchSetOutputResized(self._h, i, C.byref(fmt), device_ptr, int(downscale), _byref(layout), C.byref(resize)))
         elif layout is not None:
             self._chk(L.JxlHipBatchSetOutputLayout(self._h, i, C.byref(fmt), device_ptr, int(downscale), C.byref(layout)))
@@ -684,15 +732,17 @@ class BatchDecoder:
         self._resizes.append(resize)
 
     def add(self, data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, device_ptr=None, downscale=1,
-            planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None) -> int:
+            planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False) -> int:
         """downscale=8: the 1:8 decode (include/jxl_hip.h JxlHipBatchSetOutputScaled) — output(i) is the ceil(w / 8) x ceil(h / 8) picture; `data` may end behind
         the LF part of its frame.
         planar=True: one plane per channel, [C, H, W] with rows `align`ed and planes plane_stride bytes apart (0 = tight); scale / bias (up to four values, one per
         channel slot, float16 / float32 output): samples are stored as v * scale[c] + bias[c] (include/jxl_hip.h JxlHipOutputLayout).
         resize=(w, h): the output is w x h pixels, the decoded picture — oriented, at `downscale` — resampled with the antialiased triangle filter (torch's
-        interpolate(mode="bilinear", antialias=True)); crop=(x0, y0, w, h): only that rectangle of the picture, as if cropped first (include/jxl_hip.h JxlHipOutputResize)."""
+        interpolate(mode="bilinear", antialias=True)); crop=(x0, y0, w, h): only that rectangle of the picture, as if cropped first (include/jxl_hip.h JxlHipOutputResize).
+        filter="bilinear" (that triangle filter) | "bicubic" (antialiased cubic convolution, a = -0.5: torch's mode="bicubic", antialias=True); mirror=True: the resampled
+        picture is stored with its columns reversed (include/jxl_hip.h JxlHipOutputResample).  Both need resize; a call without them is the ...Resized call as before."""
         layout = _layout(planar, plane_stride, scale, bias)
-        rs = _resize(resize, crop)
+        rs = _resize(resize, crop) if filter is None and not mirror else _resample(resize, crop, filter, mirror)
         L = libjxl()
         buf = np.frombuffer(data, dtype=np.uint8)
         if downscale != 1:
@@ -710,12 +760,12 @@ class BatchDecoder:
         return i
 
     def add_many(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, threads=4, endianness=Endianness.Native, align=0, downscale=1,
-                 planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None) -> int:
+                 planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False) -> int:
         """Parses the images of `datas` (bytes objects) on `threads` host threads and appends them in order (JxlHipBatchAddImages);
-        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale, planar, plane_stride, scale, bias, resize, crop: as for add()."""
+        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale, planar, plane_stride, scale, bias, resize, crop, filter, mirror: as for add()."""
         L = libjxl()
         layout = _layout(planar, plane_stride, scale, bias)
-        rs = _resize(resize, crop)
+        rs = _resize(resize, crop) if filter is None and not mirror else _resample(resize, crop, filter, mirror)
         n = len(datas)
         ptrs = (C.c_char_p * n)(*datas)
         sizes = (C.c_size_t * n)(*[len(d) for d in datas])
@@ -750,7 +800,9 @@ class BatchDecoder:
 
     def out_size(self, i) -> int:
         s = C.c_size_t()
-        if self._resizes[i] is not None:
+        if isinstance(self._resizes[i], JxlHipOutputResample):
+            self._chk(libjxl().JxlHipBatchOutBufferSizeResampled(self._h, i, C.byref(self._fmt[i]), self._scale[i], _byref(self._layouts[i]), C.byref(self._resizes[i]), C.byref(s)))
+        elif self._resizes[i] is not None:
             self._chk(libjxl().JxlHipBatchOutBufferSizeResized(self._h, i, C.byref(self._fmt[i]), self._scale[i], _byref(self._layouts[i]), C.byref(self._resizes[i]), C.byref(s)))
         elif self._layouts[i] is not None:
             self._chk(libjxl().JxlHipBatchOutBufferSizeLayout(self._h, i, C.byref(self._fmt[i]), self._scale[i], C.byref(self._layouts[i]), C.byref(s)))
@@ -938,21 +990,35 @@ class Pipeline:
     __del__ = close
 
     def submit(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, host_ptrs=None, capacities=None, endianness=Endianness.Native, align=0, downscale=1,
-               planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None) -> int:
+               planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False) -> int:
         """Job of len(datas) images (bytes objects).  device_ptrs / host_ptrs: one destination address per image (exactly one of the two lists); the bytes objects and
         the destinations are kept referenced until wait().  downscale=8: the job is decoded at 1:8 (JxlHipPipelineSubmitScaled).  planar, plane_stride, scale, bias:
         the layout of every image of the job, as for BatchDecoder.add (JxlHipPipelineSubmitLayout).  resize, crop: every image of the job comes out resize[0] x resize[1]
-        pixels (JxlHipPipelineSubmitResized) — destinations of one size, e.g. consecutive slices of one [N, C, H, W] tensor; an image the crop leaves fails alone."""
+        pixels (JxlHipPipelineSubmitResized) — destinations of one size, e.g. consecutive slices of one [N, C, H, W] tensor; an image the crop leaves fails alone.
+        crop, filter ("bilinear" | "bicubic") and mirror each take one value for the job or a sequence of len(datas) per-image values (a None in a crop sequence: the
+        whole picture; four plain integers are always ONE crop (x0, y0, w, h) for the whole job, also when the job has four images — per-image crops are a sequence of
+        4-tuples or Nones; a string or a number is one filter / mirror for the job, any other iterable is read as per-image values).  Whenever one of them is a sequence, or filter / mirror is set, the job goes out with one JxlHipOutputResample per image
+        (JxlHipPipelineSubmitResampled): one target size, everything else the image's own."""
         layout = _layout(planar, plane_stride, scale, bias)
-        rs = _resize(resize, crop)
         n = len(datas)
+        crops, seq_c = _per_image(crop, n, lambda v: len(v) == 4 and all(isinstance(x, (int, np.integer)) for x in v))
+        if not seq_c and crop is not None and n:
+            crop = crops[0]                 # (an iterable of four integers has been read: keep the tuple)
+        filters, seq_f = _per_image(filter, n, lambda v: False)
+        mirrors, seq_m = _per_image(mirror, n, lambda v: False)
+        each = None
+        if seq_c or seq_f or seq_m or filter is not None or mirror:
+            each = (JxlHipOutputResample * max(1, n))(*[_resample(resize, crops[k], filters[k], mirrors[k]) for k in range(n)])
+        rs = None if each is not None else _resize(resize, crop)
         ptrs = (C.c_char_p * n)(*datas)
         sizes = (C.c_size_t * n)(*[len(d) for d in datas])
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
         dev = (C.c_void_p * n)(*device_ptrs) if device_ptrs is not None else None
         host = (C.c_void_p * n)(*host_ptrs) if host_ptrs is not None else None
         caps = (C.c_size_t * n)(*capacities) if capacities is not None else None
-        if rs is not None:
+        if each is not None:
+            t = libjxl().JxlHipPipelineSubmitResampled(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), _byref(layout), each)
+        elif rs is not None:
             t = libjxl().JxlHipPipelineSubmitResized(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), _byref(layout), C.byref(rs))
         elif layout is not None:
             t = libjxl().JxlHipPipelineSubmitLayout(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), C.byref(layout))

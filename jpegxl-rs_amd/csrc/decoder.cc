@@ -519,7 +519,7 @@ bool Batch::DevReserve(void** ptr, size_t* cap, size_t bytes) {
 // Forgets the images (and everything derived from them) but keeps the device arenas, the pinned staging buffer and the sharing set up with
 // ShareBigArena / ShareCoefArena: the batch object can be filled again.  The caller makes sure no decode of the old content is in flight.
 void Batch::Reset() {
-  images_.clear(); pub_.clear(); cbufs_.clear(); post_ops_.clear(); jpeg_data_.clear(); resize_plans_.clear(); resize_ops_.clear();
+  images_.clear(); pub_.clear(); cbufs_.clear(); post_ops_.clear(); jpeg_data_.clear(); resize_plans_.clear(); resize_groups_.clear();
   frames_host_.clear(); passes_host_.clear(); pass_first_.clear(); local_host_.clear(); local_first_.clear();
   mod_plane_offsets_.clear(); mod_ops_.clear(); vardct_alpha_.clear(); hf_written_.clear();
   // (stage timings recorded so far stay: CollectTimes sums over the object's life)
@@ -788,7 +788,8 @@ std::string Batch::LayoutRefusal(const ImageHeader& ih, const OutputSpec& o) {
   return std::string();
 }
 std::string Batch::ResizeRefusal(const ImageHeader& ih, const OutputSpec& o) {
-  if (!o.resized()) return o.cropped() ? "resized output: a crop needs a target size" : std::string();
+  if (!o.resized()) return o.cropped() ? "resized output: a crop needs a target size" : o.mirror || o.resize_filter ? "resized output: a filter or a mirror needs a target size" : std::string();
+  if (o.resize_filter > 1) return "resized output: filter " + std::to_string(o.resize_filter) + " is not known (0 = triangle, 1 = cubic)";
   if (o.resize_w == 0 || o.resize_h == 0) return "resized output: a target side of 0";
   if (o.resize_w > 65535 || o.resize_h > 65535) return "resized output: a target side above 65535";
   if (!o.cropped()) return std::string();
@@ -799,22 +800,32 @@ std::string Batch::ResizeRefusal(const ImageHeader& ih, const OutputSpec& o) {
            ") leaves the " + std::to_string(w) + " x " + std::to_string(h) + " picture";
   return std::string();
 }
-// One axis of the resize (OutputSpec::resize_w / resize_h): the triangle filter with half-pixel centres, widened by the ratio when it shrinks (the filter of Pillow's BILINEAR
-// reduce and of torch's interpolate(mode="bilinear", antialias=True)).  n_in samples -> n_out; scale = n_in / n_out, support = max(scale, 1), output i has its centre at
-// c = scale x (i + 0.5) and takes the samples j of [max(0, int(c - support + 0.5)), min(n_in, int(c + support + 0.5))) with weight max(0, 1 - |(j - c + 0.5) / support|)
-// over the sum of these: the range is cut at the edges and the weights renormalised, nothing is mirrored or clamped.  Everything in double; a normalised weight is rounded
-// to f32 once.  Samples of weight 0 at either end of a range are left out (they change no sum; at n_in == n_out one tap of weight 1 is left: a copy).
+// One axis of the resize (OutputSpec::resize_w / resize_h): a filter kernel k of radius r with half-pixel centres, widened by the ratio when it shrinks.  filter 0: the
+// triangle, k(x) = max(0, 1 - |x|), r = 1 (Pillow's BILINEAR reduce, torch's interpolate(mode="bilinear", antialias=True)); filter 1: cubic convolution with a = -0.5,
+// k(x) = ((a + 2)|x| - (a + 3))|x|^2 + 1 below 1, a(((|x| - 5)|x| + 8)|x| - 4) below 2, r = 2 (Pillow's BICUBIC, torch's mode="bicubic", antialias=True).
+// n_in samples -> n_out; scale = n_in / n_out, support = max(scale, 1), output i has its centre at c = scale x (i + 0.5) and takes the samples j of
+// [max(0, int(c - r x support + 0.5)), min(n_in, int(c + r x support + 0.5))) with weight k((j - c + 0.5) / support) over the sum of these: the range is cut at the edges and
+// the weights renormalised, nothing is mirrored or clamped.  Everything in double; a normalised weight is rounded to f32 once.  Samples of weight 0 at either end of a
+// range are left out (they change no sum; at n_in == n_out one tap of weight 1 is left, for either filter: a copy).
 // lo[i]: first sample of output i; its weights are weight[first[i]] .. weight[first[i + 1] - 1].
-static void ResizeAxis(uint32_t n_in, uint32_t n_out, vec<uint32_t>* lo, vec<uint32_t>* first, vec<float>* weight) {
-  const double scale = (double)n_in / (double)n_out, support = std::max(scale, 1.0);
+static double ResizeFilterWeight(uint32_t filter, double x) {
+  x = std::fabs(x);
+  if (filter == 0) return std::max(0.0, 1.0 - x);
+  const double a = -0.5;
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0;
+  if (x < 2.0) return a * (((x - 5.0) * x + 8.0) * x - 4.0);
+  return 0.0;
+}
+static void ResizeAxis(uint32_t filter, uint32_t n_in, uint32_t n_out, vec<uint32_t>* lo, vec<uint32_t>* first, vec<float>* weight) {
+  const double scale = (double)n_in / (double)n_out, support = std::max(scale, 1.0), reach = (filter ? 2.0 : 1.0) * support;
   lo->assign(n_out, 0); first->assign((size_t)n_out + 1, 0); weight->clear();
   vec<double> w;
   for (uint32_t i = 0; i < n_out; i++) {
     const double c = scale * ((double)i + 0.5);
-    int64_t a = std::max<int64_t>(0, (int64_t)(c - support + 0.5)), b = std::min<int64_t>((int64_t)n_in, (int64_t)(c + support + 0.5));
+    int64_t a = std::max<int64_t>(0, (int64_t)(c - reach + 0.5)), b = std::min<int64_t>((int64_t)n_in, (int64_t)(c + reach + 0.5));
     w.assign((size_t)(b - a), 0.0);
     double sum = 0.0;
-    for (int64_t j = a; j < b; j++) { w[(size_t)(j - a)] = std::max(0.0, 1.0 - std::fabs(((double)j - c + 0.5) / support)); sum += w[(size_t)(j - a)]; }
+    for (int64_t j = a; j < b; j++) { w[(size_t)(j - a)] = ResizeFilterWeight(filter, ((double)j - c + 0.5) / support); sum += w[(size_t)(j - a)]; }
     const int64_t a0 = a;
     while (b - a > 1 && w[(size_t)(b - 1 - a0)] == 0.0) b--;
     while (b - a > 1 && w[(size_t)(a - a0)] == 0.0) a++;
@@ -1006,6 +1017,7 @@ int64_t Batch::Info(const std::string& name) const {
   }
   if (name == "hf_nonzeros") { int64_t t = 0; for (uint32_t v : hf_written_) t += v; return t; }   // non-zero AC coefficients per decode of the batch (known after a Finish)
   if (name == "mod_group_lds_bytes") return prepared_ ? (int64_t)ModularGroupLdsBytes(cfg) : -1;
+  if (name == "resize_launches") return resize_launches_;           // kernel launches the last decode's resizes took (two per group of the table: Batch::EnqueueResizes)
   if (name == "jpeg_device_images") return jpeg_device_images_;     // images of the last ReconstructJpegs whose scans the device wrote / that went through the host writer
   if (name == "jpeg_host_images") return jpeg_host_images_;
   if (name == "jpeg_device_progressive_images") return jpeg_device_progressive_images_;    // ... of the device's, those with at least one progressive scan
@@ -1129,7 +1141,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
   max_lf_groups_ = max_groups_ = max_w_ = max_h_ = max_bw_ = max_bh_ = max_epf_ = 0;
   any_gab_ = any_vardct_ = any_modular_ = any_modchan_ = any_multipass_ = any_scaled_ = any_full_vardct_ = false;
   fplan_ = FilterPlan();
-  resize_plans_.clear(); resize_ops_.clear();
+  resize_plans_.clear(); resize_groups_.clear();
   // frames decoded at 1:8 (OutputSpec::downscale == 8; SetOutput only lets single-frame VarDCT images through): their decode ends behind the LF post-processing
   auto scaled = [&](int i) { return images_[i]->frame_index == 0 && images_[i]->out.downscale == 8; };
   vec<size_t> cs_bytes(n, 0);    // codestream bytes the frame's kernels may look at (FrameDev::cs_size)
@@ -1144,7 +1156,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       vec<uint32_t> lo, first; vec<float> weight;
       for (int ax = 0; ax < 2; ax++) {
         const uint32_t n_in = e.out.cropped() ? (ax ? e.out.crop_h : e.out.crop_w) : (ax ? e.src_h : e.src_w);
-        ResizeAxis(n_in, ax ? e.out.resize_h : e.out.resize_w, &lo, &first, &weight);
+        ResizeAxis(e.out.resize_filter, n_in, ax ? e.out.resize_h : e.out.resize_w, &lo, &first, &weight);
         rp.tab[3 * ax] = arena.Put(lo.data(), lo.size() * 4); rp.tab[3 * ax + 1] = arena.Put(first.data(), first.size() * 4); rp.tab[3 * ax + 2] = arena.Put(weight.data(), weight.size() * 4);
       }
       resize_plans_.push_back(rp);
@@ -1803,22 +1815,41 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     }
   }
   mark("simt_plan");
+  // resized outputs: the table of ResizeArgs takes its place in the constant arena here and is filled below, once the arena's device address is known — on every
+  // Prepare, from the arenas as they are now (shared planes may have moved); sorted by slot count, each run of equal slots cut into groups of resize_group_max entries
+  auto resize_slots = [&](const ResizePlan& rp) { return std::min(4u, std::max(1u, images_[rp.unit]->out.num_channels)); };   // (which ResizeKernel<NC> the image takes: sort key and group key)
+  std::stable_sort(resize_plans_.begin(), resize_plans_.end(), [&](const ResizePlan& a, const ResizePlan& b) { return resize_slots(a) < resize_slots(b); });
+  resize_table_off_ = 0;
+  if (!resize_plans_.empty()) {
+    resize_table_off_ = arena.Put(nullptr, 0);                                                   // (an aligned place; Put copies from its source, so the table's room is made here)
+    hconst_.Resize(resize_table_off_ + resize_plans_.size() * sizeof(ResizeArgs));                 // (every entry is written below)
+  }
   const_size_ = Align(hconst_.size());
   DevReserve((void**)&dconst_, &const_cap_, const_size_);
+  {
+    const uint32_t group_max = std::max(1u, std::min(resize_group_max, kResizeGroupMax));
+    ResizeArgs* table = (ResizeArgs*)(hconst_.data() + resize_table_off_);
+    for (size_t k = 0; k < resize_plans_.size(); k++) {
+      const ResizePlan& rp = resize_plans_[k];
+      const ImageEntry& e = *images_[rp.unit];
+      const OutputSpec& o = e.out;
+      ResizeArgs a;
+      memset(&a, 0, sizeof(a));
+      a.src = (const float*)(dbig_ + e.off_resize_src); a.tmp = (float*)(dbig_ + e.off_resize_tmp); a.src_stride = (uint64_t)e.src_w * o.num_channels;
+      a.x0 = o.crop_x0; a.y0 = o.crop_y0; a.in_w = o.cropped() ? o.crop_w : e.src_w; a.in_h = o.cropped() ? o.crop_h : e.src_h; a.out_w = o.resize_w; a.out_h = o.resize_h;
+      a.mirror = o.mirror ? 1 : 0;
+      a.ax = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[0]), (const uint32_t*)(dconst_ + rp.tab[1]), (const float*)(dconst_ + rp.tab[2])};
+      a.ay = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[3]), (const uint32_t*)(dconst_ + rp.tab[4]), (const float*)(dconst_ + rp.tab[5])};
+      a.od = FillOutput(e, dwork_, dbig_, /*resize_target=*/true);
+      table[k] = a;
+      const uint32_t slots = resize_slots(rp);
+      if (resize_groups_.empty() || resize_groups_.back().slots != slots || resize_groups_.back().count >= group_max) resize_groups_.push_back(ResizeGroup{(uint32_t)k, 0, slots, 0, 0, 0});
+      ResizeGroup& g = resize_groups_.back();
+      g.count++; g.max_out_w = std::max(g.max_out_w, a.out_w); g.max_in_h = std::max(g.max_in_h, a.in_h); g.max_out_h = std::max(g.max_out_h, a.out_h);
+    }
+  }
   HIP_CHECK(hipMemcpyAsync(dconst_, hconst_.data(), hconst_.size(), hipMemcpyHostToDevice, stream));
   for (int i = 0; i < n; i++) { fill_frame(i, dconst_); frames_host_[i].lf_simt = lf_simt_.num_lanes ? simt_frame[i] : 0; }
-  for (const ResizePlan& rp : resize_plans_) {
-    const ImageEntry& e = *images_[rp.unit];
-    const OutputSpec& o = e.out;
-    ResizeArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = (const float*)(dbig_ + e.off_resize_src); a.tmp = (float*)(dbig_ + e.off_resize_tmp); a.src_stride = (uint64_t)e.src_w * o.num_channels;
-    a.x0 = o.crop_x0; a.y0 = o.crop_y0; a.in_w = o.cropped() ? o.crop_w : e.src_w; a.in_h = o.cropped() ? o.crop_h : e.src_h; a.out_w = o.resize_w; a.out_h = o.resize_h;
-    a.ax = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[0]), (const uint32_t*)(dconst_ + rp.tab[1]), (const float*)(dconst_ + rp.tab[2])};
-    a.ay = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[3]), (const uint32_t*)(dconst_ + rp.tab[4]), (const float*)(dconst_ + rp.tab[5])};
-    a.od = FillOutput(e, dwork_, dbig_, /*resize_target=*/true);
-    resize_ops_.push_back(a);
-  }
   lf_simt_.units = (const uint2*)(dconst_ + place_units_off);
   if (lf_simt_.num_lanes) {
     lf_simt_.streams = (const LfSimtStream*)(dconst_ + simt_streams_off); lf_simt_.lanes = (const LfSimtLane*)(dconst_ + simt_lanes_off); lf_simt_.luts = dconst_ + simt_luts_off;
@@ -2412,7 +2443,11 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
 
 void Batch::EnqueuePostOps(void* stream) { for (auto& op : post_ops_) op(stream); }
 // Resized outputs: behind everything that writes pixels (the write kernels of plain frames, the Modular tail, the frame tail), on the same stream
-void Batch::EnqueueResizes(void* stream) { for (const ResizeArgs& a : resize_ops_) LaunchResize(a, stream); }
+// (one launch pair per group of the table Prepare left in the constant arena: kernels_features.hip ResizeKernel)
+void Batch::EnqueueResizes(void* stream) {
+  resize_launches_ = 0;
+  for (const ResizeGroup& g : resize_groups_) { LaunchResizeGroup((const ResizeArgs*)(dconst_ + resize_table_off_), g, stream); resize_launches_ += 2; }
+}
 
 // The HF stage only writes non-zero coefficients into zeroed planes.  The IDCT kernels zero what they consumed (kernels.hip,
 // IdctTileKernel pass 0), so a batch that is decoded again and again never clears its planes as a whole; only a decode whose

@@ -37,9 +37,11 @@ struct OutputSpec {
   bool affine = false;            // float16 / float32 output: slot c is stored as fmaf(v, scale[c], bias[c])
   float scale[4] = {1.0f, 1.0f, 1.0f, 1.0f}, bias[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   // ---- resize (Batch and Pipeline outputs): the picture the output would have held without it — oriented, at downscale 1 or 8, the "source" — is resampled to
-  // resize_w x resize_h with the antialiased triangle filter (ResizeAxis, decoder.cc); the output's size, strides and layout go by the target size
+  // resize_w x resize_h with the antialiased filter resize_filter (ResizeAxis, decoder.cc); the output's size, strides and layout go by the target size
   uint32_t resize_w = 0, resize_h = 0;     // 0 x 0 = off, else 1 .. 65535 each
   uint32_t crop_x0 = 0, crop_y0 = 0, crop_w = 0, crop_h = 0;   // rectangle of the source that is resampled (all 0 = the whole picture): exactly crop first, then resize
+  uint32_t resize_filter = 0;              // 0 = triangle, 1 = cubic convolution with a = -0.5 (resized outputs only)
+  bool mirror = false;                     // resized outputs only: target column ox is stored at column resize_w - 1 - ox, a flip of the finished target
   bool resized() const { return resize_w || resize_h; }
   bool cropped() const { return crop_x0 || crop_y0 || crop_w || crop_h; }
 };
@@ -167,6 +169,7 @@ class Batch {
   // progressive files too get their scans written on the device where every scan is a first DC pass, a DC refinement, a first AC pass or an AC refinement of one
   // component (DESIGN.md §5 lists what stays with the host writer); off: progressive files go through the host writer
   bool jpeg_device_progressive = false;
+  uint32_t resize_group_max = kResizeGroupMax;   // testing: images per resize launch (1 .. kResizeGroupMax)
   const JpegResult* jpeg_result(int i) const { return i >= 0 && (size_t)i < jpeg_results_.size() ? &jpeg_results_[(size_t)i] : nullptr; }
   void FinishStatus(void* stream, vec<uint32_t>* per_unit);
   // Copies frame i's pixels to host memory (after Finish).
@@ -244,10 +247,13 @@ class Batch {
   bool any_complex_ = false;
   void PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off);
   void EnqueuePostOps(void* stream);
-  // resized outputs: per image one ResizeArgs (kernels.h), built by Prepare, launched behind everything that writes pixels
+  // resized outputs: per image one ResizeArgs (kernels.h), built by Prepare into a table of the constant arena — sorted by slot count, cut into groups of at most
+  // resize_group_max entries — and launched group by group behind everything that writes pixels
   struct ResizePlan { int unit; size_t tab[6]; };    // constant-arena offsets of the two axes' tables: lo, first, weights of x, then of y
   vec<ResizePlan> resize_plans_;
-  vec<ResizeArgs> resize_ops_;
+  vec<ResizeGroup> resize_groups_;
+  size_t resize_table_off_ = 0;
+  int64_t resize_launches_ = 0;                      // kernel launches of the last EnqueueResizes
   void EnqueueResizes(void* stream);
   vec<FrameDev> frames_host_;
   HostStage hconst_;

@@ -938,23 +938,37 @@ static bool ApplyResize(const JxlHipOutputResize* r, OutputSpec* o, const char* 
   if (o->cropped() && (o->crop_w == 0 || o->crop_h == 0)) { SetLastError(std::string(who) + ": resized output: the crop is empty"); return false; }
   return true;
 }
+// JxlHipOutputResample -> OutputSpec: ApplyResize's checks, and the filter
+static bool ApplyResample(const JxlHipOutputResample* r, OutputSpec* o, const char* who) {
+  if (!r) { SetLastError(std::string(who) + ": no JxlHipOutputResample given"); return false; }
+  const JxlHipOutputResize rs{r->xsize, r->ysize, r->crop_x0, r->crop_y0, r->crop_xsize, r->crop_ysize};
+  if (!ApplyResize(&rs, o, who)) return false;
+  if (r->filter > 1) { SetLastError(std::string(who) + ": resized output: filter " + std::to_string(r->filter) + " is not known (0 = triangle, 1 = cubic)"); return false; }
+  o->resize_filter = r->filter; o->mirror = r->mirror != 0;
+  return true;
+}
+// JxlPixelFormat + layout + resize (or resample, for the ...Resampled calls: `resampled` set, NULL refused) -> OutputSpec.  What does not depend on the image is checked
+// first, so a refusal of the arguments is reported whatever the batch holds.
+static bool BatchSpec(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResize* resize,
+                      const JxlHipOutputResample* resample, bool resampled, OutputSpec* o, const char* who) {
+  if (!DownscaleOk(downscale, who)) return false;
+  if (!FormatToSpec(format, o) || !ApplyLayout(layout, o, who) || !(resampled ? ApplyResample(resample, o, who) : ApplyResize(resize, o, who))) return false;
+  if (!h || i < 0 || (size_t)i >= h->b->size()) { SetLastError(std::string(who) + ": no such image"); return false; }
+  o->keep_orientation = h->keep_orientation;
+  o->downscale = (uint32_t)downscale;
+  return true;
+}
 static JxlDecoderStatus BatchOutBufferSize(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResize* resize,
-                                           size_t* size, const char* who) {
-  if (!DownscaleOk(downscale, who)) return JXL_DEC_ERROR;
+                                           size_t* size, const char* who, const JxlHipOutputResample* resample = nullptr, bool resampled = false) {
   OutputSpec o;
-  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o) || !ApplyLayout(layout, &o, who) || !ApplyResize(resize, &o, who)) return JXL_DEC_ERROR;
-  o.keep_orientation = h->keep_orientation;
-  o.downscale = (uint32_t)downscale;
+  if (!BatchSpec(h, i, format, downscale, layout, resize, resample, resampled, &o, who)) return JXL_DEC_ERROR;
   try { *size = Batch::OutputSize(h->b->image(i).ih, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
 }
 static JxlDecoderStatus BatchSetOutput(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout,
-                                       const JxlHipOutputResize* resize, const char* who) {
-  if (!DownscaleOk(downscale, who)) return JXL_DEC_ERROR;
+                                       const JxlHipOutputResize* resize, const char* who, const JxlHipOutputResample* resample = nullptr, bool resampled = false) {
   OutputSpec o;
-  if (i < 0 || (size_t)i >= h->b->size() || !FormatToSpec(format, &o) || !ApplyLayout(layout, &o, who) || !ApplyResize(resize, &o, who)) return JXL_DEC_ERROR;
+  if (!BatchSpec(h, i, format, downscale, layout, resize, resample, resampled, &o, who)) return JXL_DEC_ERROR;
   o.device_ptr = device_buffer;
-  o.keep_orientation = h->keep_orientation;
-  o.downscale = (uint32_t)downscale;
   try { h->b->SetOutput(i, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }   // ("unsupported: downscaled decode of ...", a plane_stride that does not fit, a crop that leaves the picture)
 }
 JxlDecoderStatus JxlHipBatchOutBufferSize(const JxlHipBatch* h, int i, const JxlPixelFormat* format, size_t* size) { return BatchOutBufferSize(h, i, format, 1, nullptr, nullptr, size, "JxlHipBatchOutBufferSize"); }
@@ -978,6 +992,14 @@ JxlDecoderStatus JxlHipBatchOutBufferSizeResized(const JxlHipBatch* h, int i, co
 JxlDecoderStatus JxlHipBatchSetOutputResized(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout,
                                              const JxlHipOutputResize* resize) {
   return BatchSetOutput(h, i, format, device_buffer, downscale, layout, resize, "JxlHipBatchSetOutputResized");
+}
+JxlDecoderStatus JxlHipBatchOutBufferSizeResampled(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout,
+                                                   const JxlHipOutputResample* resample, size_t* size) {
+  return BatchOutBufferSize(h, i, format, downscale, layout, nullptr, size, "JxlHipBatchOutBufferSizeResampled", resample, true);
+}
+JxlDecoderStatus JxlHipBatchSetOutputResampled(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout,
+                                               const JxlHipOutputResample* resample) {
+  return BatchSetOutput(h, i, format, device_buffer, downscale, layout, nullptr, "JxlHipBatchSetOutputResampled", resample, true);
 }
 void JxlHipBatchSetLaneStride(JxlHipBatch* h, int lf, int hf) {
   auto ok = [](int v) { return v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64; };
@@ -1013,6 +1035,7 @@ void JxlHipBatchSetOption(JxlHipBatch* h, const char* name, int value) {
   else if (n == "lf_force_big" && value >= -1 && value <= 2) h->b->cfg.lf_force_big = value;
   else if (n == "jpeg_host_writer") h->b->jpeg_host_writer = value != 0;   // JxlHipBatchReconstructJpegs: every image through the host's Huffman writer
   else if (n == "jpeg_device_progressive") h->b->jpeg_device_progressive = value != 0;   // ... progressive files written by the device as well (jpeg_host_writer wins)
+  else if (n == "resize_group_max" && value >= 1 && (uint32_t)value <= kResizeGroupMax) h->b->resize_group_max = (uint32_t)value;   // testing: images per resize launch (applies to the next Prepare)
   else if (n == "hf_lanes_per_wave" && value >= 0 && value <= 64) h->b->cfg.hf_lanes_per_wave = value;   // SIMT HF stage: group streams per wavefront (1: the wave-wide kernel where it applies); 0: the throughput packing
 }
 size_t JxlHipBatchDebugRead(JxlHipBatch* h, int index, const char* name, int channel, void* dst, size_t cap, void* s) {
@@ -1112,6 +1135,29 @@ int64_t JxlHipPipelineSubmitLayout(JxlHipPipeline* h, const uint8_t* const* data
 int64_t JxlHipPipelineSubmitResized(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
                                     const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResize* resize) {
   return PipelineSubmit(h, datas, sizes, n, format, device_out, host_out, out_capacity, downscale, layout, resize, "JxlHipPipelineSubmitResized");
+}
+int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                                      const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each) {
+  const char* who = "JxlHipPipelineSubmitResampled";
+  if (!DownscaleOk(downscale, who)) return -1;
+  try {
+    OutputSpec base;
+    if (!h || !FormatToSpec(format, &base)) { SetLastError(std::string(who) + ": bad pixel format"); return -1; }
+    if (!ApplyLayout(layout, &base, who)) return -1;
+    base.downscale = (uint32_t)downscale;
+    if (n > 0 && !each) { SetLastError(std::string(who) + ": no JxlHipOutputResample given (one per image)"); return -1; }
+    std::vector<OutputSpec> specs((size_t)std::max(n, 0), base);
+    for (int i = 0; i < n; i++) {
+      if (!ApplyResample(&each[i], &specs[(size_t)i], who)) { SetLastError("image " + std::to_string(i) + ": " + JxlHipLastError()); return -1; }
+      if (each[i].xsize != each[0].xsize || each[i].ysize != each[0].ysize) {
+        SetLastError(std::string(who) + ": image " + std::to_string(i) + " asks for " + std::to_string(each[i].xsize) + " x " + std::to_string(each[i].ysize) + ", image 0 for " +
+                     std::to_string(each[0].xsize) + " x " + std::to_string(each[0].ysize) + ": one target size per job");
+        return -1;
+      }
+    }
+    if (n > 0) { base.resize_w = each[0].xsize; base.resize_h = each[0].ysize; }
+    return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity, specs.empty() ? nullptr : specs.data());
+  } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
 }
 JxlDecoderStatus JxlHipPipelineWait(JxlHipPipeline* h, int64_t ticket, int* image_status, int n, float* end_ms) {
   try {

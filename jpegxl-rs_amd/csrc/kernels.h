@@ -362,14 +362,19 @@ void LaunchJpegSizes(const JpegWritePlan& p, void* stream);
 void LaunchJpegPack(const JpegWritePlan& p, const JpegPackBuffers& o, void* stream);
 uint32_t JpegStuffChunkBytes();
 void LaunchCopyPlane(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t w, uint32_t h, void* stream);
-// ---- resized output (OutputSpec::resize_w / resize_h): separable antialiased triangle filter, horizontal pass then vertical, f32 throughout.
+// ---- resized output (OutputSpec::resize_w / resize_h): separable antialiased filter (triangle or cubic convolution), horizontal pass then vertical, f32 throughout.
 // One axis' filter as the host built it (decoder.cc ResizeAxis): output index i takes the taps first[i] .. first[i + 1] - 1 of `weight` (normalised, double rounded once to f32)
 // from the input samples lo[i], lo[i] + 1, ...; the number of taps is whatever the ratio asks for.
 struct ResizeAxisDev { const uint32_t* lo; const uint32_t* first; const float* weight; };
 // src: interleaved f32 picture of od.out_channels slots, src_stride floats per row, of which the rectangle (x0, y0) in_w x in_h is resampled to out_w x out_h; tmp:
-// in_h x out_w x slots floats (the horizontally filtered rows); od: the caller's destination, out_orient 1 — the source is oriented already
-struct ResizeArgs { const float* src; float* tmp; uint64_t src_stride; uint32_t x0, y0, in_w, in_h, out_w, out_h; ResizeAxisDev ax, ay; OutputDesc od; };
-void LaunchResize(const ResizeArgs& a, void* stream);
+// in_h x out_w x slots floats (the horizontally filtered rows); od: the caller's destination, out_orient 1 — the source is oriented already; mirror: target column ox is
+// stored at out_w - 1 - ox
+struct ResizeArgs { const float* src; float* tmp; uint64_t src_stride; uint32_t x0, y0, in_w, in_h, out_w, out_h, mirror; ResizeAxisDev ax, ay; OutputDesc od; };
+// The resizes of a decode are one device table of ResizeArgs, sorted by slot count; a group is a run of `count` entries from `first` on with the same number of slots,
+// served by one launch per pass (image on blockIdx.z, the grid sized for the group's largest extents).  count <= kResizeGroupMax (gridDim.z is limited to 65535).
+constexpr uint32_t kResizeGroupMax = 32768;
+struct ResizeGroup { uint32_t first, count, slots, max_out_w, max_in_h, max_out_h; };
+void LaunchResizeGroup(const ResizeArgs* table, const ResizeGroup& g, void* stream);
 
 // names of the kernels (for profiling summaries)
 extern const char* const kKernelNames[];

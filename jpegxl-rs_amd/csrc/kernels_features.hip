@@ -393,14 +393,18 @@ __global__ void CopyPlaneKernel(const float* __restrict__ src, uint32_t src_stri
 }
 
 // ---- resized output (OutputSpec::resize_w / resize_h) --------------------------------------------------------------------------------------
-// Separable antialiased triangle filter over the f32 picture the write stage left (decoder.cc FillOutput): the horizontal pass (kVertical = false) turns the rows of the
+// Separable antialiased filter (triangle or cubic: the weights are the host's, ResizeAxis) over the f32 picture the write stage left (decoder.cc FillOutput): the horizontal pass (kVertical = false) turns the rows of the
 // resampled rectangle into rows of out_w pixels in `tmp`, the vertical pass turns those into the out_w x out_h target and stores it through SlotValue / StoreSample /
 // OutPixelPtr — type, byte order, bit depth, row alignment, planes and scale / bias as for every other output.  The host built each axis' taps (ResizeAxis: first sample,
 // normalised f32 weights); a thread owns one pixel, all NC slots, and walks its taps — as many as the ratio asks for — with one fmaf per tap, the first tap a plain product
 // (a copy at ratio 1 stays bit-exact).  A wavefront is 64 neighbouring pixels of one row: horizontally their tap windows adjoin or overlap, so the wave reads one
 // contiguous stretch of the row and every later tap finds its line in the vector L1; vertically the lanes read 64 neighbouring pixels of the same row of `tmp` per tap and
 // lo / first / weight are wave-uniform.  No LDS, nothing that grows with the ratio but the trip count.
-template <int NC, bool kVertical> __global__ __launch_bounds__(256) void ResizeKernel(ResizeArgs a) {
+// One launch serves a group of images of NC slots: blockIdx.z picks the image's entry of the device table (Batch::Prepare wrote it), read once per block into scalar
+// registers — the entry is the same for every lane and nothing is stored before it has been read; the grid spans the group's largest extents and a block outside its own
+// image's returns at once.  mirror: the finished target pixel ox is stored at column out_w - 1 - ox (a flip of the result: sources, taps and sums are untouched).
+template <int NC, bool kVertical> __global__ __launch_bounds__(256) void ResizeKernel(const ResizeArgs* __restrict__ table) {
+  const ResizeArgs a = table[blockIdx.z];
   const uint32_t ox = blockIdx.x * 64 + threadIdx.x;
   if (ox >= a.out_w) return;
   float acc[NC];
@@ -437,7 +441,7 @@ template <int NC, bool kVertical> __global__ __launch_bounds__(256) void ResizeK
       for (int c = 0; c < NC; c++) acc[c] = fmaf(w, in[(size_t)j * pitch + c], acc[c]);
     }
     const uint32_t bps = a.od.out_type == 0 ? 1 : a.od.out_type == 2 ? 4 : 2;
-    uint8_t* const p = OutPixelPtr(a.od, (int)a.out_w, (int)a.out_h, (int)ox, (int)oy, bps);
+    uint8_t* const p = OutPixelPtr(a.od, (int)a.out_w, (int)a.out_h, (int)(a.mirror ? a.out_w - 1 - ox : ox), (int)oy, bps);
     const size_t step = a.od.planar ? (size_t)a.od.plane_stride : (size_t)bps;
 #pragma unroll
     for (int c = 0; c < NC; c++) StoreSample(a.od, p + c * step, SlotValue(a.od, c, acc[c]));
@@ -546,19 +550,19 @@ void LaunchCopyPlane(const float* src, uint32_t src_stride, float* dst, uint32_t
   hipLaunchKernelGGL(CopyPlaneKernel, Grid2(w, h), kBlock2, 0, (hipStream_t)stream, src, src_stride, dst, dst_stride, w, h);
 }
 
-template <int NC> static void LaunchResizeNc(const ResizeArgs& a, hipStream_t st) {
+template <int NC> static void LaunchResizeNc(const ResizeArgs* table, const ResizeGroup& g, hipStream_t st) {
   const dim3 block(64, 4);
-  const uint32_t gx = (a.out_w + 63) / 64;
-  hipLaunchKernelGGL((ResizeKernel<NC, false>), dim3(gx, std::min<uint32_t>((a.in_h + 3) / 4, 65535u)), block, 0, st, a);
-  hipLaunchKernelGGL((ResizeKernel<NC, true>), dim3(gx, (a.out_h + 3) / 4), block, 0, st, a);
+  const uint32_t gx = (g.max_out_w + 63) / 64;
+  hipLaunchKernelGGL((ResizeKernel<NC, false>), dim3(gx, std::min<uint32_t>((g.max_in_h + 3) / 4, 65535u), g.count), block, 0, st, table + g.first);
+  hipLaunchKernelGGL((ResizeKernel<NC, true>), dim3(gx, (g.max_out_h + 3) / 4, g.count), block, 0, st, table + g.first);
 }
-void LaunchResize(const ResizeArgs& a, void* stream) {
-  if (!a.in_w || !a.in_h || !a.out_w || !a.out_h) return;
-  switch (a.od.out_channels) {
-    case 1: LaunchResizeNc<1>(a, (hipStream_t)stream); break;
-    case 2: LaunchResizeNc<2>(a, (hipStream_t)stream); break;
-    case 3: LaunchResizeNc<3>(a, (hipStream_t)stream); break;
-    default: LaunchResizeNc<4>(a, (hipStream_t)stream); break;
+void LaunchResizeGroup(const ResizeArgs* table, const ResizeGroup& g, void* stream) {
+  if (!g.count || g.count > kResizeGroupMax || !g.max_out_w || !g.max_in_h || !g.max_out_h) return;
+  switch (g.slots) {
+    case 1: LaunchResizeNc<1>(table, g, (hipStream_t)stream); break;
+    case 2: LaunchResizeNc<2>(table, g, (hipStream_t)stream); break;
+    case 3: LaunchResizeNc<3>(table, g, (hipStream_t)stream); break;
+    default: LaunchResizeNc<4>(table, g, (hipStream_t)stream); break;
   }
 }
 void LaunchChromaUpsample(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t hs, uint32_t vs, uint32_t out_w, uint32_t out_h, void* stream) {

@@ -152,7 +152,8 @@ Pipeline::Job* Pipeline::FindJob(int64_t ticket) {
   return it == jobs_.end() ? nullptr : it->second.get();
 }
 
-int64_t Pipeline::Submit(const uint8_t* const* datas, const size_t* sizes, int n, const OutputSpec& spec, void* const* device_out, void* const* host_out, const size_t* out_capacity) {
+int64_t Pipeline::Submit(const uint8_t* const* datas, const size_t* sizes, int n, const OutputSpec& spec, void* const* device_out, void* const* host_out, const size_t* out_capacity,
+                         const OutputSpec* each) {
   if (n <= 0 || !datas || !sizes) throw ParseError("JxlHipPipelineSubmit: no images", false);
   if (!device_out == !host_out) throw ParseError("JxlHipPipelineSubmit: exactly one of device_out / host_out must be given", false);
   std::shared_ptr<Job> job(new Job());
@@ -161,6 +162,7 @@ int64_t Pipeline::Submit(const uint8_t* const* datas, const size_t* sizes, int n
   if (host_out) job->host_out.assign(host_out, host_out + n);
   if (out_capacity) job->capacity.assign(out_capacity, out_capacity + n);
   job->spec = spec; job->spec.device_ptr = nullptr;
+  if (each) job->each.assign(each, each + n);
   job->result.status.assign((size_t)n, 1); job->result.error.assign((size_t)n, std::string());
   std::unique_lock<std::mutex> lock(mu_);
   if (shutdown_) throw ParseError("JxlHipPipelineSubmit: the pipeline is shutting down", false);
@@ -248,15 +250,15 @@ void Pipeline::PrepareJob(Job* j, int worker) {
     bool any = false;
     for (int i = 0; i < n; i++) {
       if (index[(size_t)i] < 0) { j->result.error[(size_t)i] = errors[(size_t)i]; continue; }
-      OutputSpec o = j->spec;
+      OutputSpec o = j->each.empty() ? j->spec : j->each[(size_t)i];
       o.device_ptr = j->device_out.empty() ? nullptr : j->device_out[(size_t)i];
       size_t need = 0;
       std::string refusal;
       try { need = bt.OutputSizeOf(index[(size_t)i], o); } catch (const ParseError& e) { refusal = e.what(); }     // (a plane_stride this image does not fit, a crop that leaves it: Batch::LayoutRefusal / ResizeRefusal)
       if (!refusal.empty()) {
-        // (stays in the batch like an image whose buffer is too small, with a tight plane of its own and no crop)
+        // (stays in the batch like an image whose buffer is too small, with a tight plane of its own and no crop, mirror or filter)
         j->result.error[(size_t)i] = refusal;
-        o.device_ptr = nullptr; o.plane_stride = 0; o.crop_x0 = o.crop_y0 = o.crop_w = o.crop_h = 0;
+        o.device_ptr = nullptr; o.plane_stride = 0; o.crop_x0 = o.crop_y0 = o.crop_w = o.crop_h = 0; o.mirror = false; o.resize_filter = 0;
         j->batch_index[(size_t)i] = -2 - index[(size_t)i];
       } else if (!j->capacity.empty() && j->capacity[(size_t)i] < need) {
         // (the image stays in the batch — taking it out would renumber the others — and decodes into a buffer of the batch's own; it is reported as failed)

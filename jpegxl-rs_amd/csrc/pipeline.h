@@ -57,7 +57,9 @@ class Pipeline {
   // as the image's output in that format (out_capacity[i], when given, is checked).  Host destinations should be pinned (hipHostMalloc / JxlHipHostAlloc) — pageable
   // memory works, slower.  The compressed bytes and the destinations must stay valid until Wait(ticket) returns.  Blocks while `in_flight` jobs are on their way.
   // Returns the job's ticket (>= 0).
-  int64_t Submit(const uint8_t* const* datas, const size_t* sizes, int n, const OutputSpec& spec, void* const* device_out, void* const* host_out, const size_t* out_capacity);
+  // each (optional, n entries): image i is decoded to each[i] instead of `spec` — same format, layout, downscale and target size as `spec`; crop, filter and mirror are its own.
+  int64_t Submit(const uint8_t* const* datas, const size_t* sizes, int n, const OutputSpec& spec, void* const* device_out, void* const* host_out, const size_t* out_capacity,
+                 const OutputSpec* each = nullptr);
   // Waits until job `ticket` has left the GPU (outputs written, host copies done) and hands out its per-image results; a ticket can be waited for once.
   void Wait(int64_t ticket, PipelineJobResult* out);
   void WaitAll();                                  // every job submitted so far has left the GPU (results stay collectable)
@@ -76,6 +78,7 @@ class Pipeline {
     std::vector<const uint8_t*> datas; std::vector<size_t> sizes;
     std::vector<void*> device_out, host_out; std::vector<size_t> capacity;
     OutputSpec spec;
+    std::vector<OutputSpec> each;              // per image, when the job was submitted with specs of its own (empty: `spec` for all)
     std::vector<int> batch_index;              // per image: index in the batch, -1 = failed before it got there
     PipelineJobResult result;
     std::string job_error;                     // the whole job failed (Prepare threw)

@@ -6,6 +6,8 @@
 
   interleaved     u8 RGB at full size, [N, H, W, 3] — the decode alone
   resized         float16 planes of --target x --target pixels with a per-channel scale and bias, [N, 3, T, T] = (resize(v) - mean) / std, straight from the decode
+  resampled       the resized leg with what a training input pipeline asks of every image (JxlHipPipelineSubmitResampled): a random-resized-crop rectangle of its own (area
+                  0.08 - 1 of the picture, aspect ratio 3/4 - 4/3, log-uniform; seed 7), the bicubic filter, and a mirror on every second image
   consumer        what a consumer of that tensor does without the resize: the interleaved leg, plus — for every job, on a stream of the consumer's own, as soon as the job has
                   left the pipeline — torch's interpolate(mode="bilinear", antialias=True) of the job's output (permuted to [N, 3, H, W], float16) to the target, then scale and
                   bias.  The step is the distance between the ends of that second pass (torch events), which is when the consumer has its tensor.
@@ -13,7 +15,9 @@
 Prints one JSON line."""
 import argparse
 import json
+import math
 import os
+import random
 import sys
 import time
 
@@ -29,15 +33,27 @@ def percentile(xs, q):
     return xs[min(len(xs) - 1, int(q * len(xs)))]
 
 
+def random_resized_crop(rng, W, H):
+    """torchvision's RandomResizedCrop.get_params: area 0.08 - 1 of the picture, log-uniform aspect ratio 3/4 - 4/3, ten tries, else the whole picture"""
+    for _ in range(10):
+        area = W * H * rng.uniform(0.08, 1.0)
+        ratio = math.exp(rng.uniform(math.log(3 / 4), math.log(4 / 3)))
+        w, h = int(round(math.sqrt(area * ratio))), int(round(math.sqrt(area / ratio)))
+        if 0 < w <= W and 0 < h <= H:
+            return (rng.randint(0, W - w), rng.randint(0, H - h), w, h)
+    return (0, 0, W, H)
+
+
 def leg(jx, torch, streams, name, batch, steps, warmup, in_flight, W, H, T, chunk):
     # (the f32 picture a resized output is filtered from lives among the pixel planes the jobs of a pipeline share: leg `resized` reserves a second set and a margin for the
     # horizontally filtered rows, so that no job falls back to planes of its own)
-    reserve = dict(reserve_frames=batch + (batch + 7) // 8, reserve_plane_sets=2) if name == "resized" else dict(reserve_frames=batch)
+    reserve = dict(reserve_frames=batch + (batch + 7) // 8, reserve_plane_sets=2) if name in ("resized", "resampled") else dict(reserve_frames=batch)
     p = jx.Pipeline(0, jobs_in_flight=in_flight, lf_streams=in_flight, reserve_width=W, reserve_height=H, **reserve)
     lag = max(0, p.info("slots") - 2)
     nbuf = 2                                        # (destinations rotate over two buffers, as in measure_planar_output.py)
     scale_l, bias_l = [1.0 / s for s in STD], [-m / s for m, s in zip(MEAN, STD)]
-    if name == "resized":
+    rng = random.Random(7)
+    if name in ("resized", "resampled"):
         dtype, shape, tdtype = "float16", (batch, 3, T, T), torch.float16
         extra = dict(planar=True, scale=scale_l, bias=bias_l, resize=(T, T))
     else:
@@ -77,7 +93,10 @@ def leg(jx, torch, streams, name, batch, steps, warmup, in_flight, W, H, T, chun
             off = (k * 37) % len(streams)
             frames = [streams[(off + i) % len(streams)] for i in range(batch)]
             base = outs[k % nbuf].data_ptr()
-            tickets.append(p.submit(frames, dtype, 3, device_ptrs=[base + i * frame_bytes for i in range(batch)], **extra))
+            own = {}
+            if name == "resampled":
+                own = dict(crop=[random_resized_crop(rng, W, H) for _ in range(batch)], filter="bicubic", mirror=[i % 2 == 1 for i in range(batch)])
+            tickets.append(p.submit(frames, dtype, 3, device_ptrs=[base + i * frame_bytes for i in range(batch)], **extra, **own))
             if k >= lag:
                 ends.append(p.wait(tickets[k - lag])[1])
                 if consumer:

@@ -523,7 +523,7 @@ void Batch::Reset() {
   frames_host_.clear(); passes_host_.clear(); pass_first_.clear(); local_host_.clear(); local_first_.clear();
   mod_plane_offsets_.clear(); mod_ops_.clear(); vardct_alpha_.clear(); hf_written_.clear();
   // (stage timings recorded so far stay: CollectTimes sums over the object's life)
-  any_complex_ = false; any_gab_ = any_vardct_ = any_modular_ = any_modchan_ = any_multipass_ = false;
+  any_complex_ = false; any_vardct_ = any_modchan_ = any_multipass_ = false;
   prepared_ = false; ran_once_ = false; flags_pending_ = false; decodes_since_finish_ = 0;
   cfg.idct_flags_known = 0; cfg.skip_hf = 0; cfg.max_passes = 0;
   lf_simt_ = LfSimtPlan();
@@ -1061,62 +1061,224 @@ void* Batch::device_output(int i) const {
   return e.out.device_ptr ? e.out.device_ptr : (void*)(dwork_ + e.off_out);
 }
 
-void Batch::Prepare(void* stream_v, bool wait_upload) {
-  hipStream_t stream = (hipStream_t)stream_v;
-  HIP_CHECK(hipSetDevice(device_));
-  InitDeviceTables(stream_v);
-  // Device allocations are kept from one Prepare to the next and only replaced when they are too small (DevReserve): a batch object
-  // that is refilled step after step (JxlHipBatchReset + AddImages + Prepare, the streaming loop of bench.py) allocates once —
-  // hipFree synchronises the device, hipMalloc of gigabytes takes milliseconds.
-  if (clear_stream_) (void)hipStreamSynchronize((hipStream_t)clear_stream_);   // a pending clear of the old coefficient planes
-  clear_pending_ = false;
-  if (coef_owner_) dcoef_ = nullptr;
-  if (big_owner_) dbig_ = nullptr;
-  if (big_is_ext_) { dbig_ = nullptr; big_cap_ = 0; big_is_ext_ = false; }          // (pointers into the pipeline's planes: decided anew below)
-  if (coef_is_ext_) { dcoef_ = nullptr; coef_cap_ = 0; coef_laid_out_ = 0; coef_is_ext_ = false; }
-  const int n = (int)images_.size();
-  // JXL_HIP_TIME_PREPARE=1: host milliseconds of the phases of this function on stderr
+// ---- Batch::Prepare: phases over one PrepareState, in the order Prepare lists them --------------------------------------------------------
+namespace {
+// offsets of one unit's buffers in the work arena (lfq .. end_bitpos, place_*, mod_*, lz_*) and in the coefficient / pixel-plane arenas (coeff, plane_*, up_plane)
+struct WorkOffsets {
+  size_t lfq[3], lf[3], lf_tmp[3], llf[3], blk_info, coef_off, vb_list, vb_count, ytox, ytob, coeff[3], plane_a[3], plane_b[3], inv_sigma, lf_scratch, wp_scratch, end_bitpos,
+      place_rec = 0, place_cnt = 0, band_start = 0,
+      mod_scratch, hf_end = 0, mod_wp = 0, up_plane[4] = {0, 0, 0, 0};
+  size_t lf_scratch_stride, wp_scratch_stride, mod_scratch_stride, mod_wp_stride = 0, lz_window = (size_t)-1, lz_ac_window = (size_t)-1;
+};
+struct QCache { const QuantTableSpec* spec; int kind; size_t off[3]; };     // quant tables are shared between frames with identical specs
+bool SpecEqual(const QuantTableSpec& a, const QuantTableSpec& b) {
+  if (a.mode != b.mode || a.num_bands != b.num_bands || a.num_bands4 != b.num_bands4) return false;
+  if (memcmp(a.bands, b.bands, sizeof(a.bands)) || memcmp(a.idw, b.idw, sizeof(a.idw)) || memcmp(a.dct2w, b.dct2w, sizeof(a.dct2w))) return false;
+  if (memcmp(a.dct4mul, b.dct4mul, sizeof(a.dct4mul)) || memcmp(a.dct4x8mul, b.dct4x8mul, sizeof(a.dct4x8mul))) return false;
+  if (a.mode == 5 && (memcmp(a.afvw, b.afvw, sizeof(a.afvw)) || memcmp(a.bands4, b.bands4, sizeof(a.bands4)))) return false;
+  if (a.mode == 7 && (a.raw_den != b.raw_den || a.raw[0] != b.raw[0] || a.raw[1] != b.raw[1] || a.raw[2] != b.raw[2])) return false;
+  return true;
+}
+ConstOffsets::Local PutLocal(Arena& arena, uint32_t unit, const HostTree& tree, const HostCode& code) {    // a sub-stream's own tree and code
+  ConstOffsets::Local l;
+  l.unit = unit;
+  l.tree = arena.Put(tree.nodes.data(), tree.nodes.size() * sizeof(TreeNode));
+  PutCode(arena, code, &l.ctx, &l.cfg, &l.alias, &l.pc, &l.po, &l.ps);
+  return l;
+}
+// descriptor of a sub-stream with its own tree and code, from where PutLocal put them
+void FillLocalDev(ModLocalDev& d, const HostTree& tree, const HostCode& code, uint64_t data_bitpos, const ConstOffsets::Local& l, const uint8_t* cbase) {
+  d.tree = (const TreeNode*)(cbase + l.tree); d.tree_nodes = (uint32_t)tree.nodes.size(); d.uses_wp = tree.uses_wp; d.max_prop = (uint32_t)tree.max_prop;
+  d.data_bitpos = data_bitpos;
+  d.code = ViewCode(code, cbase, l.ctx, l.cfg, l.alias, l.pc, l.po, l.ps);
+}
+// The quant tables of `spec` for kind k, put into the arena once per Prepare and spec (qcache); the DCT128/256 tables are large (up to 64K weights per channel) and
+// computed once per process and spec.
+const size_t* QuantTableOffsets(Arena& arena, vec<QCache>& qcache, const QuantTableSpec& spec, int k) {
+  for (const QCache& q : qcache) if (q.kind == k && SpecEqual(*q.spec, spec)) return q.off;
+  QCache qc; qc.spec = &spec; qc.kind = k;
+  for (int ch = 0; ch < 3; ch++) {
+    struct Big { QuantTableSpec spec; int kind, ch; std::vector<float> t; };   // process-lifetime cache: plain allocator
+    static std::mutex mu;
+    static std::vector<Big> big;
+    vec<float> local;
+    if (k >= 13) {
+      std::lock_guard<std::mutex> lock(mu);
+      const Big* found = nullptr;
+      for (const Big& b : big) if (b.kind == k && b.ch == ch && SpecEqual(b.spec, spec)) { found = &b; break; }
+      if (!found) {
+        if (big.size() >= 48) big.clear();
+        big.push_back(Big{spec, k, ch, {}});
+        { vec<float> tmp; ComputeQuantTable(spec, k, ch, &tmp); big.back().t.assign(tmp.begin(), tmp.end()); }
+        found = &big.back();
+      }
+      local.assign(found->t.begin(), found->t.end());
+    } else ComputeQuantTable(spec, k, ch, &local);
+    qc.off[ch] = arena.Put(local.data(), local.size() * 4);
+  }
+  qcache.push_back(qc);
+  return qcache.back().off;
+}
+// LDS bytes of a code's tables (prefix codes / LZ77 streams are read through the tables in global memory: nothing to size the LDS for)
+int CodeBytes(const HostCode& c, bool ctx) {
+  if (c.use_prefix || c.lz77) return 16;
+  return (int)(((c.num_clusters * 4 + 15) & ~15u) + (ctx ? ((c.num_ctx + 15) & ~15u) : 0) + ((size_t)c.num_clusters << c.log_alpha) * 8);
+}
+int CodeBytesCompact(const HostCode& c) {
+  if (c.use_prefix || c.lz77) return 16;
+  return (int)(((c.num_clusters * 4 + 15) & ~15u) + ((c.num_ctx + 15) & ~15u) + (((((size_t)c.num_clusters << c.log_alpha) * 6) + 15) & ~(size_t)15));
+}
+void SizeForModularStream(LaunchCfg& cfg, const HostTree& tree, const HostCode& code) {     // the global tree, a local stream, an LF-local stream
+  cfg.max_tree_nodes = std::max<int>(cfg.max_tree_nodes, (int)tree.nodes.size()); cfg.mod_code_bytes = std::max(cfg.mod_code_bytes, CodeBytes(code, false)); cfg.any_wp |= tree.uses_wp ? 1 : 0;
+}
+// indices of `cost`, the dearest first (ties in index order)
+template <class T> vec<uint32_t> OrderByCostDescending(const vec<T>& cost) {
+  vec<uint32_t> order(cost.size());
+  for (size_t k = 0; k < order.size(); k++) order[k] = (uint32_t)k;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
+  return order;
+}
+// What the SIMT LF plan gathers over the frames: the blob of cluster tables and which instantiation of the kernel the eligible streams need
+struct LfSimtTables {
+  vec<uint8_t> luts;
+  std::map<std::string, uint32_t> lut_of;       // table content -> offset in the blob (frames of one encoder share most tables)
+  bool general = false;                         // some eligible stream needs the instantiation with two-property tables / the rarer properties and predictors
+  bool wp = false;                              // some eligible stream keeps weighted-predictor state: the batch takes that instantiation of the kernel
+  uint32_t Intern(const uint8_t* bytes, size_t size) {
+    const std::string key((const char*)bytes, size);
+    auto it = lut_of.find(key);
+    if (it == lut_of.end()) { it = lut_of.emplace(key, (uint32_t)luts.size()).first; luts.insert(luts.end(), bytes, bytes + size); }
+    return it->second;
+  }
+};
+// The LF-group streams of frame `frame` as LfDecodeSimtKernel takes them, in *mine; false: the frame keeps LfDecodeKernel (what its channels interned so far stays in t)
+bool ClassifyLfStreams(const FramePlan& p, uint32_t frame, LfSimtTables& t, vec<LfSimtStream>* mine) {
+  if (p.modular || !p.has_global_tree || !p.lf_local.empty() || p.tree_code.use_prefix || p.tree_code.lz77 || p.tree_code.log_alpha > 8 || p.tree_code.num_clusters > 256 || p.use_lf_frame) return false;
+  // extra-channel sub-channels squeezed by >= 3 sit in the middle of the LfGroup sections: only the one-wavefront-per-stream kernel decodes those
+  for (size_t c = p.global_decodable; c < p.gchannels.size(); c++) if (p.gchannels[c].w && p.gchannels[c].h && std::min(p.gchannels[c].hshift, p.gchannels[c].vshift) >= 3) return false;
+  for (uint32_t g = 0; g < p.num_lf_groups; g++) {
+    LfSimtStream s;
+    memset(&s, 0, sizeof(s));
+    s.frame = frame; s.group = g;
+    for (int c = 0; c < 7; c++) {
+      LfChanClass cl;
+      if (!ClassifyLfChannel(p.tree, p.tree_code, c < 3 ? c : c - 3, c < 3 ? 1 + g : 1 + 2 * p.num_lf_groups + g, &cl)) return false;
+      if (cl.uses_wp && c == 5) return false;      // (the block-info rows are up to 65 536 wide: the per-lane weighted-predictor rows hold 256)
+      auto word = [&](const LfRowClass& rc) { return rc.kind | (rc.pred << 2) | (rc.sel_a << 5) | (rc.sel_b << 7) | (cl.uses_wp ? kLfSimtWpLive : 0u) | (rc.cluster << 16); };
+      if (cl.rows.size() == 1) {
+        s.chan[c].lut_off = cl.rows[0].kind ? t.Intern(cl.rows[0].lut.data(), cl.rows[0].lut.size()) : 0;
+        s.chan[c].info = word(cl.rows[0]);
+      } else {   // the class depends on the row: [512 bytes: row -> class][classes x {table offset, class word}]
+        vec<uint8_t> blob(512 + 8 * cl.rows.size());
+        memcpy(blob.data(), cl.row_to_class, 512);
+        for (size_t k = 0; k < cl.rows.size(); k++) {
+          const uint32_t e[2] = {cl.rows[k].kind ? t.Intern(cl.rows[k].lut.data(), cl.rows[k].lut.size()) : 0u, word(cl.rows[k])};
+          memcpy(blob.data() + 512 + 8 * k, e, 8);
+        }
+        s.chan[c].lut_off = t.Intern(blob.data(), blob.size());
+        s.chan[c].info = kLfSimtRows | (cl.uses_wp ? kLfSimtWpLive : 0u);
+      }
+      if (cl.uses_wp) t.wp = true;
+      for (const LfRowClass& rc : cl.rows)      // beyond what the lean instantiation handles: one cluster per row or a table over W + N - NW; zero / W / clamped gradient
+        if (rc.kind == 2 || (rc.kind == 1 && rc.sel_a != 0) || !(rc.pred == 0 || rc.pred == 1 || rc.pred == 3)) t.general = true;
+    }
+    mine->push_back(s);
+  }
+  return true;
+}
+// Streams of the given costs (not empty) spread over lanes, longest-processing-time-first; the number of lanes grows from the lower bound (total work / longest
+// stream) until no lane carries noticeably more than the longest stream: a lane more costs nothing, a lane with two long streams doubles the stage's latency
+vec<vec<uint32_t>> PackLanes(const vec<uint64_t>& cost) {
+  uint64_t total = 0, longest = 0;
+  for (uint64_t cst : cost) { total += cst; longest = std::max(longest, cst); }
+  const vec<uint32_t> order = OrderByCostDescending(cost);
+  vec<vec<uint32_t>> lane_streams;
+  for (size_t nlanes = std::max<size_t>(1, std::min<size_t>(cost.size(), (size_t)((total + longest - 1) / longest)));; nlanes = std::min(cost.size(), nlanes + std::max<size_t>(1, nlanes / 64))) {
+    lane_streams.assign(nlanes, vec<uint32_t>());
+    std::priority_queue<std::pair<uint64_t, uint32_t>, std::vector<std::pair<uint64_t, uint32_t>>, std::greater<std::pair<uint64_t, uint32_t>>> pq;
+    for (size_t l = 0; l < nlanes; l++) pq.push({0, (uint32_t)l});
+    uint64_t makespan = 0;
+    for (uint32_t k : order) { auto top = pq.top(); pq.pop(); lane_streams[top.second].push_back(k); makespan = std::max(makespan, top.first + cost[k]); pq.push({top.first + cost[k], top.second}); }
+    if (makespan <= longest + longest / 16 || nlanes >= cost.size()) return lane_streams;
+  }
+}
+uint32_t ResizeSlots(const ImageEntry& e) { return std::min(4u, std::max(1u, e.out.num_channels)); }   // (which ResizeKernel<NC> the image takes: sort key and group key)
+}  // namespace
+
+// What the phases of one Prepare share.  Each phase's comment says what it reads from here and what it adds; nothing else passes between them but the Batch's members.
+struct Batch::PrepareState {
+  const int n;                     // units
+  hipStream_t stream;
+  Arena arena;                     // over hconst_: streams and tables, uploaded as the constant arena
+  vec<ConstOffsets> co;            // per unit: where its tables are in the constant arena
+  vec<WorkOffsets> wo;             // per unit: where its buffers are in the work / plane arenas
+  vec<size_t> cs_bytes;            // per unit: codestream bytes the frame's kernels may look at (FrameDev::cs_size)
+  size_t natural_off[13] = {0};    // natural coefficient orders (shared by all frames)
+  vec<QCache> qcache;
+  vec<uint8_t> simt_frame;         // per unit: its LF-group streams are in the SIMT plan
+  size_t place_units_off = 0, simt_streams_off = 0, simt_lanes_off = 0, simt_luts_off = 0;
+  bool need_plane_b = false;
+  // `take` = the per-batch work arena (everything the LF stage writes, scratch, status, outputs); `take_big` = pixel planes, only touched between HF decode and the
+  // write stage (shareable)
+  size_t w = 0, wbig = 0;
+  size_t take(size_t bytes) { const size_t off = Align(w); w = off + bytes; return off; }
+  size_t take_big(size_t bytes) { const size_t off = Align(wbig); wbig = off + bytes; return off; }
+  // JXL_HIP_TIME_PREPARE=1: host milliseconds of the phases of Prepare on stderr
   const bool time_phases = getenv("JXL_HIP_TIME_PREPARE") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
+  std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
   std::string t_report;
-  auto mark = [&](const char* what) {
+  void mark(const char* what) {
     if (!time_phases) return;
     const auto now = std::chrono::steady_clock::now();
     char buf[64];
     snprintf(buf, sizeof buf, " %s %.2f", what, std::chrono::duration<double, std::milli>(now - t_last).count());
     t_report += buf; t_last = now;
-  };
-  // un-premultiplying alpha (JxlDecoderSetUnpremultiplyAlpha, jpegxl-rs decode.rs:353) happens in the write stage of the frame tail
+  }
+  PrepareState(HostStage& hconst, int units, hipStream_t s) : n(units), stream(s), arena(hconst), co(units), wo(units), cs_bytes(units, 0), simt_frame(units, 0) {}
+};
+
+// frames decoded at 1:8 (OutputSpec::downscale == 8; SetOutput only lets single-frame VarDCT images through): their decode ends behind the LF post-processing
+bool Batch::DecodedAtEighth(int unit) const { return images_[unit]->frame_index == 0 && images_[unit]->out.downscale == 8; }
+
+// Device allocations are kept from one Prepare to the next and only replaced when they are too small (DevReserve): a batch object
+// that is refilled step after step (JxlHipBatchReset + AddImages + Prepare, the streaming loop of bench.py) allocates once —
+// hipFree synchronises the device, hipMalloc of gigabytes takes milliseconds.  Pointers into somebody else's planes are decided anew (ReserveArenas).
+void Batch::ResetForPrepare() {
+  if (clear_stream_) (void)hipStreamSynchronize((hipStream_t)clear_stream_);   // a pending clear of the old coefficient planes
+  clear_pending_ = false;
+  if (coef_owner_) dcoef_ = nullptr;
+  if (big_owner_) dbig_ = nullptr;
+  if (big_is_ext_) { dbig_ = nullptr; big_cap_ = 0; big_is_ext_ = false; }          // (pointers into the pipeline's planes)
+  if (coef_is_ext_) { dcoef_ = nullptr; coef_cap_ = 0; coef_laid_out_ = 0; coef_is_ext_ = false; }
+}
+
+void Batch::MarkComplex(PubImage& pi) {
+  pi.complex = true;
+  for (int u = pi.first_unit; u < pi.first_unit + pi.num_units; u++) images_[u]->complex = true;
+}
+
+// Images whose output only the frame tail can write become complex: rendered spot colours (stage_spot.cc; grey images keep one colour plane there: not handled), a single
+// frame as coded (its own size, no blending), un-premultiplied alpha (JxlDecoderSetUnpremultiplyAlpha, jpegxl-rs decode.rs:353).  Reads and adds nothing of PrepareState.
+void Batch::PromoteToComplex() {
   for (PubImage& pi : pub_) {
     ImageEntry& first = *images_[pi.first_unit];
-    bool premul = false;
+    bool premul = false, spot = false;
     for (auto& x : first.ih.extra) if (x.type == 0) { premul = x.alpha_associated; break; }
-    bool spot = false;
     for (auto& x : first.ih.extra) if (x.type == 2) spot = true;
-    if (spot && first.out.render_spotcolors) {
-      // stage_spot.cc runs in the frame tail; grey images keep one colour plane there (not handled)
-      if (first.ih.color_space == 1) throw ParseError("unsupported: spot colours on a grey image", true);
-      if (!pi.complex) { pi.complex = true; for (int u = pi.first_unit; u < pi.first_unit + pi.num_units; u++) images_[u]->complex = true; }
-    }
-    if (first.out.only_frame >= 0 && !pi.complex) {     // a single frame as coded: written by the frame tail (its own size, no blending)
-      pi.complex = true;
-      for (int u = pi.first_unit; u < pi.first_unit + pi.num_units; u++) images_[u]->complex = true;
-    }
-    if (first.out.unpremul_alpha && premul && !pi.complex) {
-      pi.complex = true;
-      for (int u = pi.first_unit; u < pi.first_unit + pi.num_units; u++) images_[u]->complex = true;
-    }
+    if (spot && first.out.render_spotcolors && first.ih.color_space == 1) throw ParseError("unsupported: spot colours on a grey image", true);
+    if ((spot && first.out.render_spotcolors) || first.out.only_frame >= 0 || (first.out.unpremul_alpha && premul)) MarkComplex(pi);
   }
+}
+
+// "tables1".  Adds natural_off, cs_bytes and, per unit, co's codestream, section tables, trees, codes and bcm; fills resize_plans_ (axis tables), the batch maxima and fplan_.
+void Batch::PutStreamTables(PrepareState& st) {
+  Arena& arena = st.arena;
   hconst_.clear();
   {
     size_t guess = (size_t)1 << 20;      // streams + tables: one allocation instead of a dozen doublings
     for (auto& e : images_) { guess += sizeof(FrameDev) + 4 * sizeof(PassDev) + 1024; if (e->frame_index == 0) guess += e->cs.padded_size() + ((size_t)256 << 10); }
     hconst_.Reserve(guess);
   }
-  Arena arena(hconst_);
-  vec<ConstOffsets> co(n);
-  // natural coefficient orders (shared)
-  size_t natural_off[13];
   {
     // (process-wide: the orders of the DCT128/256 buckets are 16K..64K entries each)
     static std::mutex mu;
@@ -1124,31 +1286,17 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     std::lock_guard<std::mutex> lock(mu);
     for (int b = 0; b < 13; b++) {
       if (natural[b].empty()) { const vec<uint16_t> v = NaturalCoeffOrder(kBucketStrategy[b]); natural[b].assign(v.begin(), v.end()); }
-      natural_off[b] = arena.Put(natural[b].data(), natural[b].size() * 2);
+      st.natural_off[b] = arena.Put(natural[b].data(), natural[b].size() * 2);
     }
   }
-  // quant tables are shared between frames with identical specs
-  struct QCache { const QuantTableSpec* spec; int kind; size_t off[3]; };
-  vec<QCache> qcache;
-  auto spec_equal = [](const QuantTableSpec& a, const QuantTableSpec& b) {
-    if (a.mode != b.mode || a.num_bands != b.num_bands || a.num_bands4 != b.num_bands4) return false;
-    if (memcmp(a.bands, b.bands, sizeof(a.bands)) || memcmp(a.idw, b.idw, sizeof(a.idw)) || memcmp(a.dct2w, b.dct2w, sizeof(a.dct2w))) return false;
-    if (memcmp(a.dct4mul, b.dct4mul, sizeof(a.dct4mul)) || memcmp(a.dct4x8mul, b.dct4x8mul, sizeof(a.dct4x8mul))) return false;
-    if (a.mode == 5 && (memcmp(a.afvw, b.afvw, sizeof(a.afvw)) || memcmp(a.bands4, b.bands4, sizeof(a.bands4)))) return false;
-    if (a.mode == 7 && (a.raw_den != b.raw_den || a.raw[0] != b.raw[0] || a.raw[1] != b.raw[1] || a.raw[2] != b.raw[2])) return false;
-    return true;
-  };
-  max_lf_groups_ = max_groups_ = max_w_ = max_h_ = max_bw_ = max_bh_ = max_epf_ = 0;
-  any_gab_ = any_vardct_ = any_modular_ = any_modchan_ = any_multipass_ = any_scaled_ = any_full_vardct_ = false;
+  max_lf_groups_ = max_groups_ = max_w_ = max_h_ = max_bw_ = max_bh_ = 0;
+  any_vardct_ = any_modchan_ = any_multipass_ = any_scaled_ = any_full_vardct_ = false;
   fplan_ = FilterPlan();
   resize_plans_.clear(); resize_groups_.clear();
-  // frames decoded at 1:8 (OutputSpec::downscale == 8; SetOutput only lets single-frame VarDCT images through): their decode ends behind the LF post-processing
-  auto scaled = [&](int i) { return images_[i]->frame_index == 0 && images_[i]->out.downscale == 8; };
-  vec<size_t> cs_bytes(n, 0);    // codestream bytes the frame's kernels may look at (FrameDev::cs_size)
-  for (int i = 0; i < n; i++) {
+  for (int i = 0; i < st.n; i++) {
     ImageEntry& e = *images_[i];
     FramePlan& p = e.plan;
-    ConstOffsets& c = co[i];
+    ConstOffsets& c = st.co[i];
     if (e.frame_index == 0 && e.out_size == 0) SetOutput(e.pub_index, e.out);
     if (e.frame_index == 0 && e.out.resized()) {     // the two axes' filters of a resized output (ResizeAxis)
       ResizePlan rp;
@@ -1161,14 +1309,14 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       }
       resize_plans_.push_back(rp);
     }
-    cs_bytes[i] = e.cs.size;
-    if (scaled(i) && !p.single_section) {
+    st.cs_bytes[i] = e.cs.size;
+    if (DecodedAtEighth(i) && !p.single_section) {
       // the 1:8 decode reads LfGlobal, the LfGroups and (on the host) HfGlobal: what lies behind the last of them — the AC groups, most of the file — stays on the host
       size_t end = 0;
       for (size_t k = 0; k < 2 + (size_t)p.num_lf_groups && k < p.sections.size(); k++) end = std::max<size_t>(end, p.sections[k].offset + p.sections[k].size);
-      cs_bytes[i] = std::min(e.cs.size, end);
+      st.cs_bytes[i] = std::min(e.cs.size, end);
     }
-    if (e.frame_index == 0) c.cs = arena.Put(e.cs.data(), e.cs.padded_size() - (e.cs.size - cs_bytes[i])); else c.cs = co[i - e.frame_index].cs;   // frames share the codestream
+    if (e.frame_index == 0) c.cs = arena.Put(e.cs.data(), e.cs.padded_size() - (e.cs.size - st.cs_bytes[i])); else c.cs = st.co[i - e.frame_index].cs;   // frames share the codestream
     vec<uint64_t> so, ss;
     for (auto& s : p.sections) { so.push_back(s.offset); ss.push_back(s.size); }
     c.sec_off = arena.Put(so.data(), so.size() * 8);
@@ -1177,54 +1325,28 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       c.tree = arena.Put(p.tree.nodes.data(), p.tree.nodes.size() * sizeof(TreeNode));
       PutCode(arena, p.tree_code, &c.mod_ctx, &c.mod_cfg, &c.mod_alias, &c.mod_pc, &c.mod_po, &c.mod_ps);
     }
-    for (auto& ls : p.local_streams) {
-      ConstOffsets::Local l;
-      l.unit = ls.unit;
-      l.tree = arena.Put(ls.tree.nodes.data(), ls.tree.nodes.size() * sizeof(TreeNode));
-      PutCode(arena, ls.code, &l.ctx, &l.cfg, &l.alias, &l.pc, &l.po, &l.ps);
-      c.local.push_back(l);
-    }
-    for (size_t k = 0; k < p.lf_local.size(); k++) {
-      const FramePlan::LfLocal& ll = p.lf_local[k];
-      if (!ll.present) continue;
-      ConstOffsets::Local l;
-      l.unit = (uint32_t)k;
-      l.tree = arena.Put(ll.tree.nodes.data(), ll.tree.nodes.size() * sizeof(TreeNode));
-      PutCode(arena, ll.code, &l.ctx, &l.cfg, &l.alias, &l.pc, &l.po, &l.ps);
-      c.lf_local.push_back(l);
-    }
+    for (auto& ls : p.local_streams) c.local.push_back(PutLocal(arena, ls.unit, ls.tree, ls.code));
+    for (size_t k = 0; k < p.lf_local.size(); k++) if (p.lf_local[k].present) c.lf_local.push_back(PutLocal(arena, (uint32_t)k, p.lf_local[k].tree, p.lf_local[k].code));
     c.bcm = arena.Put(&p.bcm, sizeof(p.bcm));
-    if (!p.modular) {
-      any_vardct_ = true;
-      // (single-section frames: HfGlobal is parsed in the pre-run below; reserve nothing here)
-    } else any_modular_ = true;
+    if (!p.modular) any_vardct_ = true;      // (single-section frames: HfGlobal is parsed in the pre-run; nothing is reserved for it here)
     max_lf_groups_ = std::max<int>(max_lf_groups_, p.num_lf_groups);
     max_groups_ = std::max<int>(max_groups_, p.num_groups);
     max_w_ = std::max<int>(max_w_, p.width); max_h_ = std::max<int>(max_h_, p.height);
     max_bw_ = std::max<int>(max_bw_, p.bw); max_bh_ = std::max<int>(max_bh_, p.bh);
-    if (!p.modular) (scaled(i) ? any_scaled_ : any_full_vardct_) = true;
-    if (!p.modular && !scaled(i)) {
-      max_epf_ = std::max<int>(max_epf_, p.lf.epf_iters); any_gab_ |= p.lf.gab != 0;
+    if (!p.modular) (DecodedAtEighth(i) ? any_scaled_ : any_full_vardct_) = true;
+    if (!p.modular && !DecodedAtEighth(i)) {
       const bool fusable = p.lf.gab && p.lf.epf_iters == 1 && e.ih.xyb_encoded && SimpleTransfer(e.ih) && p.upsampling == 1 && !e.complex;
       if (p.upsampling > 1 && !e.complex) { fplan_.any_upsampled = true; fplan_.max_out_w = std::max<int>(fplan_.max_out_w, e.ih.xsize); fplan_.max_out_h = std::max<int>(fplan_.max_out_h, e.ih.ysize); }
       fplan_.any_fused |= fusable; fplan_.any_unfused |= !fusable;
       fplan_.any_gab |= p.lf.gab != 0; fplan_.max_epf = std::max<int>(fplan_.max_epf, p.lf.epf_iters);
     }
   }
-  mark("tables1");
-  // ---- work arena layout: `take` = the per-batch arena (everything the LF stage writes, scratch, status, outputs);
-  // `take_big` = coefficient and pixel planes, only touched between HF decode and the write stage (shareable)
-  size_t w = 0, wbig = 0;
-  auto take = [&](size_t bytes) { size_t off = Align(w); w = off + bytes; return off; };
-  auto take_big = [&](size_t bytes) { size_t off = Align(wbig); wbig = off + bytes; return off; };
-  const bool need_plane_b = fplan_.any_unfused || cfg.force_unfused_filters;
-  struct WorkOffsets {
-    size_t lfq[3], lf[3], lf_tmp[3], llf[3], blk_info, coef_off, vb_list, vb_count, ytox, ytob, coeff[3], plane_a[3], plane_b[3], inv_sigma, lf_scratch, wp_scratch, end_bitpos,
-        place_rec = 0, place_cnt = 0, band_start = 0,
-        mod_scratch, hf_end = 0, mod_wp = 0, up_plane[4] = {0, 0, 0, 0};
-    size_t lf_scratch_stride, wp_scratch_stride, mod_scratch_stride, mod_wp_stride = 0, lz_window = (size_t)-1, lz_ac_window = (size_t)-1;
-  };
-  vec<WorkOffsets> wo(n);
+}
+
+// Lays out the work arena, the coefficient planes and the pixel planes.  Reads fplan_ (PutStreamTables); adds wo, the arena cursors, need_plane_b and co's up_weights / mod_chan.
+void Batch::LayOutWork(PrepareState& st) {
+  const int n = st.n;
+  st.need_plane_b = fplan_.any_unfused || cfg.force_unfused_filters;
   mod_plane_offsets_.assign(n, {});
   mod_ops_.assign(n, {});
   cbufs_.assign(n, ComplexBufs());
@@ -1232,10 +1354,9 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
   for (auto& cb : cbufs_) for (size_t* a : {cb.up, cb.noise, cb.rgb, cb.canvas, cb.pa, cb.pb, cb.color_int}) for (int k = 0; k < 3; k++) a[k] = (size_t)-1;
   post_ops_.clear(); any_complex_ = false;
   vardct_alpha_.assign(n, VarDctAlpha());
-  status_off_ = take((size_t)n * 4);
-  const size_t flags_off = take((size_t)n * 4);
-  flags_off_ = flags_off;
-  hfw_off_ = take((size_t)n * 4);
+  status_off_ = st.take((size_t)n * 4);
+  flags_off_ = st.take((size_t)n * 4);
+  hfw_off_ = st.take((size_t)n * 4);
   hf_written_.assign(n, 0); decodes_since_finish_ = 0;
   cfg.idct_flags_known = 0; ran_once_ = false; flags_pending_ = false;
   // coefficient buffers of all frames are contiguous so that one memset clears them
@@ -1244,129 +1365,147 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
   size_t wcoef = 0;
   for (int i = 0; i < n; i++) {
     const FramePlan& p = images_[i]->plan;
-    if (p.modular || scaled(i)) continue;
-    for (int c = 0; c < 3; c++) { wo[i].coeff[c] = Align(wcoef); wcoef = wo[i].coeff[c] + (size_t)p.num_groups * 65536 * 4; }
+    if (p.modular || DecodedAtEighth(i)) continue;
+    for (int c = 0; c < 3; c++) { st.wo[i].coeff[c] = Align(wcoef); wcoef = st.wo[i].coeff[c] + (size_t)p.num_groups * 65536 * 4; }
   }
   coeff_bytes_ = Align(wcoef);
   for (int i = 0; i < n; i++) {
     ImageEntry& e = *images_[i];
     const FramePlan& p = e.plan;
-    WorkOffsets& o = wo[i];
-    o.end_bitpos = take(16);
-    if (e.frame_index == 0 && !e.out.device_ptr) e.off_out = take((e.out_size + 64) * std::max<size_t>(1, e.deliver_frames.size()));
+    WorkOffsets& o = st.wo[i];
+    o.end_bitpos = st.take(16);
+    if (e.frame_index == 0 && !e.out.device_ptr) e.off_out = st.take((e.out_size + 64) * std::max<size_t>(1, e.deliver_frames.size()));
     if (e.frame_index == 0 && e.out.resized()) {
       // resized output: the f32 picture the write stage leaves (every slot of the output, interleaved), and the rows of the resampled rectangle after the horizontal pass —
       // among the pixel planes: written and read between the write stage and the end of the decode, so the jobs of a pipeline share one set (UseSharedPlanes)
-      e.off_resize_src = take_big((size_t)e.src_w * e.src_h * e.out.num_channels * 4);
-      e.off_resize_tmp = take_big((size_t)(e.out.cropped() ? e.out.crop_h : e.src_h) * e.out.resize_w * e.out.num_channels * 4);
+      e.off_resize_src = st.take_big((size_t)e.src_w * e.src_h * e.out.num_channels * 4);
+      e.off_resize_tmp = st.take_big((size_t)(e.out.cropped() ? e.out.crop_h : e.src_h) * e.out.resize_w * e.out.num_channels * 4);
     }
-  if (p.upsampling > 1) {   // kernel weights: custom (image header) or library default
+    if (p.upsampling > 1) {   // kernel weights: custom (image header) or library default
       const int upk = p.upsampling == 2 ? 0 : p.upsampling == 4 ? 1 : 2;
       const float* const kDefault[3] = {kUp2, kUp4, kUp8};
       static const size_t kCount[3] = {15, 55, 210};
       const vec<float>& cw = e.ih.up_weights[upk];
-      co[i].up_weights = cw.empty() ? arena.Put(kDefault[upk], kCount[upk] * 4) : arena.Put(cw.data(), cw.size() * 4);
+      st.co[i].up_weights = cw.empty() ? st.arena.Put(kDefault[upk], kCount[upk] * 4) : st.arena.Put(cw.data(), cw.size() * 4);
     }
-    if (!p.modular) {
-      const size_t nb = (size_t)p.bw * p.bh;
-      for (int c = 0; c < 3; c++) { o.lfq[c] = take(nb * 4); o.lf[c] = take(nb * 4); o.lf_tmp[c] = take(nb * 4); o.llf[c] = take(nb * 4); }
-      o.blk_info = take(nb * 4); o.coef_off = take(nb * 4); o.inv_sigma = take(nb * 4);
-      o.vb_list = take((size_t)p.num_groups * 1024 * 8); o.vb_count = take((size_t)p.num_groups * 4);
-      o.place_rec = take(nb * 16); o.place_cnt = take((size_t)p.num_lf_groups * 8 * 4); o.band_start = take((size_t)p.num_lf_groups * 8 * 4);
-      const size_t ntile = (size_t)((p.bw + 7) / 8) * ((p.bh + 7) / 8);
-      o.ytox = take(ntile); o.ytob = take(ntile);
-      const size_t plane = (size_t)p.bw * 8 * p.bh * 8 * 4;
-      for (int c = 0; c < 3; c++) {
-        if (scaled(i)) { o.plane_a[c] = o.plane_b[c] = (size_t)-1; continue; }      // (no full-resolution planes)
-        o.plane_a[c] = take_big(plane); o.plane_b[c] = (need_plane_b || e.complex) ? take_big(plane) : (size_t)-1;
-      }
-      if (p.upsampling > 1 && !e.complex) for (int c = 0; c < 4; c++) o.up_plane[c] = take_big((size_t)e.ih.xsize * e.ih.ysize * 4);
-      o.lf_scratch_stride = 16 + 2 * 1024 + 3 * 65536;
-      o.lf_scratch = take(o.lf_scratch_stride * 4 * p.num_lf_groups);
-      // weighted-predictor state of an LF-group stream.  LfDecodeSimtKernel: two rows of 258 records of 32 bytes; LfDecodeKernel's global
-      // form (channels wider than its LDS slot — only the block-info rows, up to 65 536 wide, can be): five arrays of 2 x (width + 2) ints
-      bool wide_wp = false;
-      if (p.tree.uses_wp && p.has_global_tree)
-        for (uint32_t g = 0; g < p.num_lf_groups && !wide_wp; g++) wide_wp = LfChannelUsesWp(p.tree, 2, 1 + 2 * p.num_lf_groups + g);
-      for (uint32_t g = 0; g < p.num_lf_groups && !p.lf_local.empty() && !wide_wp; g++) {   // (local trees: the HF-metadata stream's own, or the global one it uses)
-        const FramePlan::LfLocal& l = p.lf_local[3 * (size_t)g + 2];
-        wide_wp = l.present ? LfChannelUsesWp(l.tree, 2, 1 + 2 * p.num_lf_groups + g) : (p.tree.uses_wp && LfChannelUsesWp(p.tree, 2, 1 + 2 * p.num_lf_groups + g));
-      }
-      o.wp_scratch_stride = wide_wp ? 10 * (65536 + 2) : kLfSimtWpInts;
-      o.wp_scratch = take(o.wp_scratch_stride * 4 * p.num_lf_groups);
-      if (!p.gchannels.empty()) {
-        // extra channels (alpha, ...) ride in the frame's Modular sub-streams: planes, channel table, undo plan
-        any_modchan_ = true;
-        vec<size_t>& mp = mod_plane_offsets_[i];
-        for (auto& ch : p.gchannels) mp.push_back(take((size_t)ch.w * ch.h * 4 + 64));
-        PlanModularUndo(i, take);
-        vec<ModChanDev> table;
-        for (size_t k = 0; k < p.gchannels.size(); k++) table.push_back(ModChanDev{mp[k], p.gchannels[k].w, p.gchannels[k].h, p.gchannels[k].hshift, p.gchannels[k].vshift});
-        co[i].mod_chan = arena.Put(table.data(), table.size() * sizeof(ModChanDev));
-        const size_t gd = p.group_dim;
-        o.mod_scratch_stride = (8 + 4) * gd * gd + 4 * 65536;
-        o.mod_scratch = take(o.mod_scratch_stride * 4 * p.NumModUnits());
-        o.hf_end = take((size_t)p.num_groups * p.ModUnitPasses() * 8);   // (pass - mod_pass, g)
-        // the Modular streams keep their WP state apart from the LF streams'
-        o.mod_wp_stride = (p.tree.uses_wp || (!p.local_streams.empty() && p.local_streams[0].tree.uses_wp)) ? 10 * (65536 + 2) : 16;
-        o.mod_wp = take(o.mod_wp_stride * 4 * (1 + p.NumModUnits()));
-      }
-    } else {
-      any_modchan_ = true;
-      // planes for every channel of the global image, then the plan that undoes the global transforms
-      vec<size_t>& mp = mod_plane_offsets_[i];
-      for (auto& ch : p.gchannels) mp.push_back(take((size_t)ch.w * ch.h * 4 + 64));
-      PlanModularUndo(i, take);
-      vec<ModChanDev> table;
-      for (size_t k = 0; k < p.gchannels.size(); k++) table.push_back(ModChanDev{mp[k], p.gchannels[k].w, p.gchannels[k].h, p.gchannels[k].hshift, p.gchannels[k].vshift});
-      co[i].mod_chan = arena.Put(table.data(), table.size() * sizeof(ModChanDev));
-      const size_t gd = p.group_dim;
-      // per-unit scratch: channels of units with transforms of their own are decoded there (worst case 12 planes of a group + palettes: 4 MB per unit, 4.3 GB for the 1040
-      // units of an 8192x8192 frame) — the host has read every unit's header: frames without such units get none; weighted-predictor rows: two rows x five arrays of the widest channel
-      const bool tight = p.mod_units_scanned && !p.mod_local_transforms;
-      o.mod_scratch_stride = tight ? 64 : (8 + 4) * gd * gd + 4 * 65536;
-      o.mod_scratch = take(o.mod_scratch_stride * 4 * p.NumModUnits());
-      size_t widest = gd;
-      for (auto& ch : p.gchannels) widest = std::max<size_t>(widest, ch.w);
-      o.wp_scratch_stride = (p.tree.uses_wp || p.mod_local_wp) ? (tight ? 10 * (widest + 2) : 10 * (65536 + 2)) : 16;
-      o.wp_scratch = take(o.wp_scratch_stride * 4 * (1 + p.NumModUnits()));
-      if (e.complex) for (int c = 0; c < 3; c++) { o.plane_a[c] = take_big((size_t)p.bw * 8 * p.bh * 8 * 4); o.plane_b[c] = (size_t)-1; }
-    }
+    if (!p.modular) LayOutVarDct(i, st); else LayOutModular(i, st);
     bool lz_local = false;     // (Modular sub-streams with codes of their own)
     if (!p.modular) {
       for (auto& ls : p.local_streams) lz_local |= ls.code.lz77;
       for (auto& l : p.lf_local) lz_local |= l.present && l.code.lz77;
     }
     if (((p.has_global_tree && p.tree_code.lz77) || lz_local) && (!p.gchannels.empty() || !p.modular))   // LZ77 windows of the Modular streams (4 MiB each); VarDCT: + one per LF group
-      o.lz_window = take((size_t)(1 + p.NumModUnits() + (p.modular ? 0 : p.num_lf_groups)) * (4u << 20));
-    if (!p.modular && !scaled(i)) {   // LZ77-coded AC streams: a window per group stream (1 MiB each, only for the frames that use them)
+      o.lz_window = st.take((size_t)(1 + p.NumModUnits() + (p.modular ? 0 : p.num_lf_groups)) * (4u << 20));
+    if (!p.modular && !DecodedAtEighth(i)) {   // LZ77-coded AC streams: a window per group stream (1 MiB each, only for the frames that use them)
       bool lz_ac = p.single_section;    // (a one-section frame's AC code is only parsed once its LF streams have been decoded: always reserved, 1 MiB)
       for (auto& code : p.ac_code) lz_ac |= code.lz77;
-      if (lz_ac) o.lz_ac_window = take((size_t)p.num_groups * kAcLzWindow * 4);
+      if (lz_ac) o.lz_ac_window = st.take((size_t)p.num_groups * kAcLzWindow * 4);
     }
-    if (e.complex) {
-      // buffers of the frame tail (PlanPostOps): float extra channels, upsampled planes, noise planes, colour-transformed planes
-      // (only when the untransformed ones must survive as a reference frame), canvas (only when the frame is blended)
-      any_complex_ = true;
-      ComplexBufs& cb = cbufs_[i];
-      const size_t ne = e.ih.extra.size();
-      const size_t coded = (size_t)p.width * p.height * 4, full = (size_t)p.frame_w * p.frame_h * 4, img = (size_t)e.ih.xsize * e.ih.ysize * 4;
-      for (size_t k = 0; k < ne; k++) cb.ecf[k] = take_big(coded);
-      if (p.upsampling > 1) { for (int c = 0; c < 3; c++) cb.up[c] = take_big(full); for (size_t k = 0; k < ne; k++) cb.up_ec[k] = take_big(full); }
-      if (p.feat.has_noise) for (int c = 0; c < 3; c++) cb.noise[c] = take_big(full);
-      if (p.flags & 2) for (size_t k = 0; k < ne; k++) cb.ec_tmp.push_back(take_big(coded));
-      const bool can_ref = !p.is_last && p.frame_type != 1 && (p.duration == 0 || p.save_as_reference != 0);
-      bool replace_all = p.blend.mode == 0;
-      for (auto& b : p.ec_blend) if (b.mode != 0) replace_all = false;
-      const bool needs_blending = p.have_crop || !replace_all;
-      if (p.frame_type != 2) {
-        if (can_ref && p.save_before_ct) for (int c = 0; c < 3; c++) cb.rgb[c] = take_big(full);
-        if (needs_blending) { for (int c = 0; c < 3; c++) cb.canvas[c] = take_big(img); for (size_t k = 0; k < ne; k++) cb.canvas_ec[k] = take_big(img); }
-      }
-      for (int c = 0; c < 3; c++) { cb.pa[c] = o.plane_a[c]; cb.pb[c] = o.plane_b[c]; }
-    }
+    if (e.complex) LayOutComplexBufs(i, st);
   }
-  work_size_ = Align(w);
+  work_size_ = Align(st.w);
+}
+
+// The Modular channels of a frame (every channel of a Modular frame, the extra channels of a VarDCT frame): planes in the work arena, the plan that undoes the global
+// transforms, the channel table.  Adds co[i].mod_chan; fills mod_plane_offsets_[i] and mod_ops_[i].
+void Batch::LayOutModChannels(int i, PrepareState& st) {
+  const FramePlan& p = images_[i]->plan;
+  any_modchan_ = true;
+  vec<size_t>& mp = mod_plane_offsets_[i];
+  for (auto& ch : p.gchannels) mp.push_back(st.take((size_t)ch.w * ch.h * 4 + 64));
+  PlanModularUndo(i, [&st](size_t bytes) { return st.take(bytes); });
+  vec<ModChanDev> table;
+  for (size_t k = 0; k < p.gchannels.size(); k++) table.push_back(ModChanDev{mp[k], p.gchannels[k].w, p.gchannels[k].h, p.gchannels[k].hshift, p.gchannels[k].vshift});
+  st.co[i].mod_chan = st.arena.Put(table.data(), table.size() * sizeof(ModChanDev));
+}
+
+// Buffers of a VarDCT unit: LF-stage outputs and scratch in the work arena, pixel planes; with extra channels, their Modular channels.  Reads need_plane_b; adds wo[i].
+void Batch::LayOutVarDct(int i, PrepareState& st) {
+  const ImageEntry& e = *images_[i]; const FramePlan& p = e.plan;
+  WorkOffsets& o = st.wo[i];
+  const size_t nb = (size_t)p.bw * p.bh;
+  for (int c = 0; c < 3; c++) { o.lfq[c] = st.take(nb * 4); o.lf[c] = st.take(nb * 4); o.lf_tmp[c] = st.take(nb * 4); o.llf[c] = st.take(nb * 4); }
+  o.blk_info = st.take(nb * 4); o.coef_off = st.take(nb * 4); o.inv_sigma = st.take(nb * 4);
+  o.vb_list = st.take((size_t)p.num_groups * 1024 * 8); o.vb_count = st.take((size_t)p.num_groups * 4);
+  o.place_rec = st.take(nb * 16); o.place_cnt = st.take((size_t)p.num_lf_groups * 8 * 4); o.band_start = st.take((size_t)p.num_lf_groups * 8 * 4);
+  const size_t ntile = (size_t)((p.bw + 7) / 8) * ((p.bh + 7) / 8);
+  o.ytox = st.take(ntile); o.ytob = st.take(ntile);
+  const size_t plane = (size_t)p.bw * 8 * p.bh * 8 * 4;
+  for (int c = 0; c < 3; c++) {
+    if (DecodedAtEighth(i)) { o.plane_a[c] = o.plane_b[c] = (size_t)-1; continue; }      // (no full-resolution planes)
+    o.plane_a[c] = st.take_big(plane); o.plane_b[c] = (st.need_plane_b || e.complex) ? st.take_big(plane) : (size_t)-1;
+  }
+  if (p.upsampling > 1 && !e.complex) for (int c = 0; c < 4; c++) o.up_plane[c] = st.take_big((size_t)e.ih.xsize * e.ih.ysize * 4);
+  o.lf_scratch_stride = 16 + 2 * 1024 + 3 * 65536;
+  o.lf_scratch = st.take(o.lf_scratch_stride * 4 * p.num_lf_groups);
+  // weighted-predictor state of an LF-group stream.  LfDecodeSimtKernel: two rows of 258 records of 32 bytes; LfDecodeKernel's global
+  // form (channels wider than its LDS slot — only the block-info rows, up to 65 536 wide, can be): five arrays of 2 x (width + 2) ints
+  bool wide_wp = false;
+  if (p.tree.uses_wp && p.has_global_tree)
+    for (uint32_t g = 0; g < p.num_lf_groups && !wide_wp; g++) wide_wp = LfChannelUsesWp(p.tree, 2, 1 + 2 * p.num_lf_groups + g);
+  for (uint32_t g = 0; g < p.num_lf_groups && !p.lf_local.empty() && !wide_wp; g++) {   // (local trees: the HF-metadata stream's own, or the global one it uses)
+    const FramePlan::LfLocal& l = p.lf_local[3 * (size_t)g + 2];
+    wide_wp = l.present ? LfChannelUsesWp(l.tree, 2, 1 + 2 * p.num_lf_groups + g) : (p.tree.uses_wp && LfChannelUsesWp(p.tree, 2, 1 + 2 * p.num_lf_groups + g));
+  }
+  o.wp_scratch_stride = wide_wp ? 10 * (65536 + 2) : kLfSimtWpInts;
+  o.wp_scratch = st.take(o.wp_scratch_stride * 4 * p.num_lf_groups);
+  if (p.gchannels.empty()) return;
+  LayOutModChannels(i, st);      // extra channels (alpha, ...) ride in the frame's Modular sub-streams
+  const size_t gd = p.group_dim;
+  o.mod_scratch_stride = (8 + 4) * gd * gd + 4 * 65536;
+  o.mod_scratch = st.take(o.mod_scratch_stride * 4 * p.NumModUnits());
+  o.hf_end = st.take((size_t)p.num_groups * p.ModUnitPasses() * 8);   // (pass - mod_pass, g)
+  // the Modular streams keep their WP state apart from the LF streams'
+  o.mod_wp_stride = (p.tree.uses_wp || (!p.local_streams.empty() && p.local_streams[0].tree.uses_wp)) ? 10 * (65536 + 2) : 16;
+  o.mod_wp = st.take(o.mod_wp_stride * 4 * (1 + p.NumModUnits()));
+}
+
+// Buffers of a Modular unit: its channels, per-unit scratch, weighted-predictor rows; float planes when the frame tail composes it.  Adds wo[i].
+void Batch::LayOutModular(int i, PrepareState& st) {
+  const ImageEntry& e = *images_[i]; const FramePlan& p = e.plan;
+  WorkOffsets& o = st.wo[i];
+  LayOutModChannels(i, st);
+  const size_t gd = p.group_dim;
+  // per-unit scratch: channels of units with transforms of their own are decoded there (worst case 12 planes of a group + palettes: 4 MB per unit, 4.3 GB for the 1040
+  // units of an 8192x8192 frame) — the host has read every unit's header: frames without such units get none; weighted-predictor rows: two rows x five arrays of the widest channel
+  const bool tight = p.mod_units_scanned && !p.mod_local_transforms;
+  o.mod_scratch_stride = tight ? 64 : (8 + 4) * gd * gd + 4 * 65536;
+  o.mod_scratch = st.take(o.mod_scratch_stride * 4 * p.NumModUnits());
+  size_t widest = gd;
+  for (auto& ch : p.gchannels) widest = std::max<size_t>(widest, ch.w);
+  o.wp_scratch_stride = (p.tree.uses_wp || p.mod_local_wp) ? (tight ? 10 * (widest + 2) : 10 * (65536 + 2)) : 16;
+  o.wp_scratch = st.take(o.wp_scratch_stride * 4 * (1 + p.NumModUnits()));
+  if (e.complex) for (int c = 0; c < 3; c++) { o.plane_a[c] = st.take_big((size_t)p.bw * 8 * p.bh * 8 * 4); o.plane_b[c] = (size_t)-1; }
+}
+
+// Buffers of the frame tail (PlanPostOps) of a complex unit: float extra channels, upsampled planes, noise planes, colour-transformed planes (only when the
+// untransformed ones must survive as a reference frame), canvas (only when the frame is blended).  Reads wo[i]'s planes; fills cbufs_[i].
+void Batch::LayOutComplexBufs(int i, PrepareState& st) {
+  const ImageEntry& e = *images_[i]; const FramePlan& p = e.plan;
+  any_complex_ = true;
+  ComplexBufs& cb = cbufs_[i];
+  const size_t ne = e.ih.extra.size();
+  const size_t coded = (size_t)p.width * p.height * 4, full = (size_t)p.frame_w * p.frame_h * 4, img = (size_t)e.ih.xsize * e.ih.ysize * 4;
+  for (size_t k = 0; k < ne; k++) cb.ecf[k] = st.take_big(coded);
+  if (p.upsampling > 1) { for (int c = 0; c < 3; c++) cb.up[c] = st.take_big(full); for (size_t k = 0; k < ne; k++) cb.up_ec[k] = st.take_big(full); }
+  if (p.feat.has_noise) for (int c = 0; c < 3; c++) cb.noise[c] = st.take_big(full);
+  if (p.flags & 2) for (size_t k = 0; k < ne; k++) cb.ec_tmp.push_back(st.take_big(coded));
+  const bool can_ref = !p.is_last && p.frame_type != 1 && (p.duration == 0 || p.save_as_reference != 0);
+  bool replace_all = p.blend.mode == 0;
+  for (auto& b : p.ec_blend) if (b.mode != 0) replace_all = false;
+  const bool needs_blending = p.have_crop || !replace_all;
+  if (p.frame_type != 2) {
+    if (can_ref && p.save_before_ct) for (int c = 0; c < 3; c++) cb.rgb[c] = st.take_big(full);
+    if (needs_blending) { for (int c = 0; c < 3; c++) cb.canvas[c] = st.take_big(img); for (size_t k = 0; k < ne; k++) cb.canvas_ec[k] = st.take_big(img); }
+  }
+  for (int c = 0; c < 3; c++) { cb.pa[c] = st.wo[i].plane_a[c]; cb.pb[c] = st.wo[i].plane_b[c]; }
+}
+
+// The work arena with its clear policy, the pixel planes and the coefficient planes (own, an owner's, or the pipeline's shared set), the frame descriptors' device array.
+// Reads the arena cursors and need_plane_b; adds nothing.
+void Batch::ReserveArenas(PrepareState& st) {
+  const int n = st.n;
+  hipStream_t stream = st.stream;
   {
     // The arena is cleared when it is new.  A refilled batch of plain VarDCT frames (the streaming loop: 14 MB of LF-stage outputs per 4K frame, 3.6 GB per
     // batch of 256) only gets its status / flag / counter words zeroed: every kernel of that path writes what it reads later (valid streams) or treats what it
@@ -1387,8 +1526,8 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     } else if (plain && !cautious && !fresh) HIP_CHECK(hipMemsetAsync(dwork_, 0, head, stream));
     else HIP_CHECK(hipMemsetAsync(dwork_, 0, work_size_, stream));
   }
-  big_size_ = Align(wbig);
-  has_plane_b_ = need_plane_b;
+  big_size_ = Align(st.wbig);
+  has_plane_b_ = st.need_plane_b;
   bool plain_planes = n > 0;      // plain VarDCT frames overwrite every sample of the pixel planes they read: they can take planes that hold another decode's leftovers
   for (int i = 0; i < n; i++) { const ImageEntry& e = *images_[i]; if (e.plan.modular || e.complex || e.plan.upsampling > 1) plain_planes = false; }
   if (big_owner_) {
@@ -1414,205 +1553,218 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
     if (fresh || coeff_bytes_ != coef_laid_out_) coef_dirty_ = true;   // new planes, or another layout of them: the first decode clears them in its own stream
   }
   coef_laid_out_ = coeff_bytes_;
-  mark("layout+reserve");
   DevReserve((void**)&dframes_, &frames_cap_, sizeof(FrameDev) * std::max(n, 1));
-
-  // ---- single-section VarDCT frames: HfGlobal starts where the device-decoded LfGroup ends.  Pre-run the LF stage
-  // for those frames now, read the end position back and parse HfGlobal on the host.
   frames_host_.assign(n, FrameDev());
-  auto fill_frame = [&](int i, const uint8_t* cbase) {
-    ImageEntry& e = *images_[i];
-    const FramePlan& p = e.plan;
-    const ConstOffsets& c = co[i];
-    const WorkOffsets& o = wo[i];
-    FrameDev& f = frames_host_[i];
-    memset(&f, 0, sizeof(f));
-    f.width = p.width; f.height = p.height; f.bw = p.bw; f.bh = p.bh; f.xgroups = p.xgroups; f.ygroups = p.ygroups; f.num_groups = p.num_groups;
-    f.xlfgroups = p.xlfgroups; f.num_lf_groups = p.num_lf_groups; f.cw = (p.bw + 7) / 8; f.ch = (p.bh + 7) / 8;
-    f.group_dim = p.group_dim; f.is_modular = p.modular; f.plane_stride = p.bw * 8; f.plane_rows = p.bh * 8;
-    f.cs = cbase + c.cs; f.cs_size = cs_bytes[i];
-    f.sec_off = (const uint64_t*)(cbase + c.sec_off); f.sec_size = (const uint64_t*)(cbase + c.sec_size);
-    f.single_section = p.single_section;
-    f.lf_start_bitpos = p.global_data_bitpos;  // VarDCT without extra channels: LfGroup follows LfGlobal directly
-    f.stream_end_bitpos = (uint64_t*)(dwork_ + o.end_bitpos);
-    if (p.has_global_tree) {
-      f.tree = (const TreeNode*)(cbase + c.tree);
-      f.tree_nodes = (uint32_t)p.tree.nodes.size();
-      f.mod_code = ViewCode(p.tree_code, cbase, c.mod_ctx, c.mod_cfg, c.mod_alias, c.mod_pc, c.mod_po, c.mod_ps);
-      f.mod_cfg_uniform = p.tree_code.cfg.empty() ? 0xFFFFFFFFu : p.tree_code.cfg[0];
-      for (uint32_t v : p.tree_code.cfg) if (v != p.tree_code.cfg[0]) f.mod_cfg_uniform = 0xFFFFFFFFu;
-    }
-    f.uses_wp = p.tree.uses_wp; f.gwp = p.gwp;
-    f.mod_unit_passes = p.ModUnitPasses(); f.mod_pass = p.mod_pass;
-    for (int k = 0; k < 11; k++) { f.pass_min_shift[k] = p.pass_min_shift[k]; f.pass_max_shift[k] = p.pass_max_shift[k]; }
-    f.tree_max_prop = (uint32_t)p.tree.max_prop;
-    for (int k = 0; k < 3; k++) { f.hs[k] = p.hs[k]; f.vs[k] = p.vs[k]; }
-    f.subsampled = p.subsampled;
-    if (!c.local.empty()) {
-      // descriptor table of the frame's units (0 = global stream), zero = "uses the frame's tree"
-      ModLocalDev* table = &local_host_[local_first_[i]];
-      f.mod_local = dlocal_ + local_first_[i];
-      for (size_t k = 0; k < c.local.size(); k++) {
-        const ConstOffsets::Local& l = c.local[k];
-        const FramePlan::LocalStream& ls = p.local_streams[k];
-        ModLocalDev& d = table[l.unit];
-        d.tree = (const TreeNode*)(cbase + l.tree); d.tree_nodes = (uint32_t)ls.tree.nodes.size(); d.uses_wp = ls.tree.uses_wp; d.max_prop = (uint32_t)ls.tree.max_prop;
-        d.data_bitpos = ls.data_bitpos;
-        d.code = ViewCode(ls.code, cbase, l.ctx, l.cfg, l.alias, l.pc, l.po, l.ps);
-      }
-    }
-    if (!p.lf_local.empty()) {
-      // LfGroup sub-streams: [3 g + k] behind the unit table, zero = "uses the frame's tree"; the frame takes LfDecodeLocalKernel
-      const size_t first = local_first_[i] + (p.local_streams.empty() ? 0 : 1 + (size_t)p.NumModUnits());
-      ModLocalDev* table = &local_host_[first];
-      f.lf_local = dlocal_ + first;
-      for (const ConstOffsets::Local& l : c.lf_local) {
-        const FramePlan::LfLocal& ll = p.lf_local[l.unit];
-        ModLocalDev& d = table[l.unit];
-        d.tree = (const TreeNode*)(cbase + l.tree); d.tree_nodes = (uint32_t)ll.tree.nodes.size(); d.uses_wp = ll.tree.uses_wp; d.max_prop = (uint32_t)ll.tree.max_prop;
-        d.data_bitpos = ll.data_bitpos;
-        d.code = ViewCode(ll.code, cbase, l.ctx, l.cfg, l.alias, l.pc, l.po, l.ps);
-        f.lf_lz77 |= ll.code.lz77 ? 1u : 0u;
-      }
-      if (p.has_global_tree && p.tree_code.lz77) f.lf_lz77 = 1;
-      f.tree_max_prop = (uint32_t)p.max_prop;      // (every tree the LF streams may use: whether they keep previous-channel references)
-    }
-    f.bcm = (const BlockCtxDev*)(cbase + c.bcm);
-    f.status = (uint32_t*)(dwork_ + status_off_) + i;
-    f.frame_flags = (uint32_t*)(dwork_ + flags_off) + i;
-    f.hf_written = (uint32_t*)(dwork_ + hfw_off_) + i;
-    f.od = FillOutput(e, dwork_, dbig_);
-    f.upsampling = p.upsampling; f.img_w = e.ih.xsize; f.img_h = e.ih.ysize;
-    if (scaled(i)) { f.lf_only = 1; f.img_w = (p.width + 7) / 8; f.img_h = (p.height + 7) / 8; }     // (the picture LfOutputKernel writes; out_stride is SetOutput's, of the same picture)
-    if (p.upsampling > 1) { f.up_weights = (const float*)(cbase + c.up_weights); for (int k = 0; k < 4; k++) f.up_plane[k] = (float*)(dbig_ + o.up_plane[k]); }
-    f.post_mode = e.complex ? 1 : 0;
-    f.lz_window = o.lz_window == (size_t)-1 ? nullptr : (uint32_t*)(dwork_ + o.lz_window);
-    f.lz_ac_window = o.lz_ac_window == (size_t)-1 ? nullptr : (uint32_t*)(dwork_ + o.lz_ac_window);
-    f.lz_lf_base = 1 + p.NumModUnits();
-    f.wp_scratch = (int32_t*)(dwork_ + o.wp_scratch); f.wp_scratch_stride = o.wp_scratch_stride;
-    if (!p.modular) {
-      const float inv_gs = 65536.0f / (float)p.global_scale;
-      const float inv_quant_lf = inv_gs / (float)p.quant_lf;
-      for (int k = 0; k < 3; k++) f.lf_fac[k] = p.m_lf[k] * inv_quant_lf;
-      f.cfl_lf_x = p.base_x + (float)p.ytox_lf * (1.0f / (float)p.color_factor);
-      f.cfl_lf_b = p.base_b + (float)p.ytob_lf * (1.0f / (float)p.color_factor);
-      f.inv_global_scale = inv_gs;
-      f.x_dm = std::pow(0.8f, (float)p.x_qm_scale - 2.0f); f.b_dm = std::pow(0.8f, (float)p.b_qm_scale - 2.0f);
-      for (int k = 0; k < 4; k++) f.quant_bias[k] = e.ih.quant_bias[k];
-      f.color_scale = 1.0f / (float)p.color_factor; f.base_x = p.base_x; f.base_b = p.base_b;
-      f.skip_lf_smoothing = (p.flags & 128) != 0 || p.use_lf_frame;     // (dec_frame.cc FinalizeDC: no adaptive smoothing of an LF frame's samples)
-      f.use_lf_frame = p.use_lf_frame ? 1 : 0;
-      f.gab = p.lf.gab; f.epf_iters = p.lf.epf_iters;
-      for (int k = 0; k < 3; k++) {
-        const float w1 = p.lf.gab_w[2 * k], w2 = p.lf.gab_w[2 * k + 1];
-        const float div = 1.0f + 4.0f * (w1 + w2);
-        f.gab_w[3 * k] = 1.0f / div; f.gab_w[3 * k + 1] = w1 / div; f.gab_w[3 * k + 2] = w2 / div;
-      }
-      for (int k = 0; k < 8; k++) f.epf_sharp_lut[k] = p.lf.sharp_lut[k];
-      for (int k = 0; k < 3; k++) f.epf_channel_scale[k] = p.lf.channel_scale[k];
-      f.epf_quant_mul = p.lf.quant_mul; f.epf_quant_scale = (float)p.global_scale / 65536.0f;
-      const float scales[3] = {p.lf.pass0_sigma_scale, 1.0f, p.lf.pass2_sigma_scale};
-      for (int k = 0; k < 3; k++) { f.epf_sm[k] = scales[k] * 1.65f; f.epf_bsm[k] = f.epf_sm[k] * p.lf.border_sad_mul; }
-      FillColor(e.ih, p.do_ycbcr, f);
-      for (int k = 0; k < 3; k++) {
-        f.lfq[k] = (int32_t*)(dwork_ + o.lfq[k]); f.lf[k] = (float*)(dwork_ + o.lf[k]); f.lf_tmp[k] = (float*)(dwork_ + o.lf_tmp[k]);
-        f.llf[k] = (float*)(dwork_ + o.llf[k]); f.coeff[k] = scaled(i) ? nullptr : (int32_t*)(dcoef_ + o.coeff[k]);
-        f.plane_a[k] = o.plane_a[k] == (size_t)-1 ? nullptr : (float*)(dbig_ + o.plane_a[k]); f.plane_b[k] = o.plane_b[k] == (size_t)-1 ? nullptr : (float*)(dbig_ + o.plane_b[k]);
-      }
-      f.blk_info = (uint32_t*)(dwork_ + o.blk_info); f.coef_off = (uint32_t*)(dwork_ + o.coef_off);
-      f.vb_list = (uint2*)(dwork_ + o.vb_list); f.vb_count = (uint32_t*)(dwork_ + o.vb_count);
-      f.place_rec = (uint4*)(dwork_ + o.place_rec); f.place_cnt = (uint32_t*)(dwork_ + o.place_cnt); f.band_start = (uint32_t*)(dwork_ + o.band_start);
-      f.ytox = (int8_t*)(dwork_ + o.ytox); f.ytob = (int8_t*)(dwork_ + o.ytob);
-      f.inv_sigma = (float*)(dwork_ + o.inv_sigma);
-      f.lf_scratch = (int32_t*)(dwork_ + o.lf_scratch); f.lf_scratch_stride = o.lf_scratch_stride;
-      // HfGlobal-derived fields (present once parsed)
-      if (!p.ac_code.empty()) {
-        f.num_passes = cfg.max_passes > 0 ? std::min<uint32_t>(p.num_passes, (uint32_t)cfg.max_passes) : p.num_passes;     // (a progressive flush shows the first passes only; the later ones' sections stay unread)
-        f.passes = dpasses_ + pass_first_[i];
-        for (uint32_t ps = 0; ps < p.num_passes; ps++) {
-          const ConstOffsets::Pass& cp = c.pass[ps];
-          PassDev& pd = passes_host_[pass_first_[i] + ps];
-          pd.code = ViewCode(p.ac_code[ps], cbase, cp.ac_ctx, cp.ac_cfg, cp.ac_alias, cp.ac_pc, cp.ac_po, cp.ac_ps);
-          for (int k = 0; k < 39; k++) pd.orders[k] = (const uint16_t*)(cbase + cp.orders[k]);
-          pd.shift = ps + 1 < p.num_passes ? p.pass_shift[ps] : 0; pd.pad = 0;
-        }
-        f.ac_code = passes_host_[pass_first_[i]].code;
-        for (int k = 0; k < 39; k++) f.orders[k] = passes_host_[pass_first_[i]].orders[k];
-        for (int k = 0; k < 17 * 3; k++) f.qtable[k] = c.has_qtable[k / 3] ? (const float*)(cbase + c.qtable[k]) : nullptr;
-        f.num_hf_presets = p.num_hf_presets;
-        uint32_t bits = 0; while ((1u << bits) < p.num_hf_presets) bits++;
-        f.preset_bits = bits;
-        f.hf_start_bitpos = p.end_bitpos;
-      }
-    } else {
-      f.hf_start_bitpos = 0;
-      f.mod_wp_scratch = f.wp_scratch; f.mod_wp_stride = f.wp_scratch_stride;
-    }
-    if (!p.gchannels.empty()) {
-      f.mod_nchan = (uint32_t)p.gchannels.size(); f.mod_nb_meta = p.nb_meta_channels;
-      f.mod_chan = (const ModChanDev*)(cbase + c.mod_chan); f.mod_base = dwork_;
-      f.mod_global_decodable = p.global_decodable; f.mod_global_bitpos = p.global_data_bitpos;
-      f.mod_group_scratch = (int32_t*)(dwork_ + o.mod_scratch); f.mod_group_scratch_stride = o.mod_scratch_stride;
-      f.mod_bits = e.ih.depth.bits;
-      if (!p.modular) {
-        f.hf_end_bitpos = (uint64_t*)(dwork_ + o.hf_end);
-        f.mod_wp_scratch = (int32_t*)(dwork_ + o.mod_wp); f.mod_wp_stride = o.mod_wp_stride;
-        f.alpha_plane = vardct_alpha_[i].has ? (const int32_t*)(dwork_ + vardct_alpha_[i].off) : nullptr;
-        f.alpha_factor = vardct_alpha_[i].factor;
-      }
-    }
-  };
+}
 
-  {  // (before the one-section pre-run, whose LF decode reads them) descriptors of the sub-streams with their own tree / code: one table per frame that has any
-    local_first_.assign(n, 0);
-    size_t total = 0;
-    for (int i = 0; i < n; i++) {
-      const FramePlan& p = images_[i]->plan;
-      local_first_[i] = total;
-      if (!p.local_streams.empty()) total += 1 + (size_t)p.NumModUnits();
-      total += p.lf_local.size();
+// frames_host_[i] from what exists at the time of the call, with the constant arena at `cbase` on the device: called for the one-section frames before HfGlobal is
+// parsed (p.ac_code is empty then: no pass tables yet) and for every frame once everything is in the arena.  Reads co[i], wo[i], cs_bytes[i]; adds nothing.
+void Batch::FillFrameDev(int i, const uint8_t* cbase, const PrepareState& st) {
+  const FramePlan& p = images_[i]->plan;
+  FrameDev& f = frames_host_[i];
+  memset(&f, 0, sizeof(f));
+  FillFrameCommon(i, cbase, st);
+  if (!p.modular) FillFrameVarDct(i, cbase, st);
+  else { f.hf_start_bitpos = 0; f.mod_wp_scratch = f.wp_scratch; f.mod_wp_stride = f.wp_scratch_stride; }
+  if (!p.gchannels.empty()) FillFrameModChannels(i, cbase, st);
+}
+
+// geometry, codestream and section tables, the global and local trees and codes, status words, output, LZ77 windows: what every kind of frame has
+void Batch::FillFrameCommon(int i, const uint8_t* cbase, const PrepareState& st) {
+  ImageEntry& e = *images_[i];
+  const FramePlan& p = e.plan;
+  const ConstOffsets& c = st.co[i]; const WorkOffsets& o = st.wo[i];
+  FrameDev& f = frames_host_[i];
+  f.width = p.width; f.height = p.height; f.bw = p.bw; f.bh = p.bh; f.xgroups = p.xgroups; f.ygroups = p.ygroups; f.num_groups = p.num_groups;
+  f.xlfgroups = p.xlfgroups; f.num_lf_groups = p.num_lf_groups; f.cw = (p.bw + 7) / 8; f.ch = (p.bh + 7) / 8;
+  f.group_dim = p.group_dim; f.is_modular = p.modular; f.plane_stride = p.bw * 8; f.plane_rows = p.bh * 8;
+  f.cs = cbase + c.cs; f.cs_size = st.cs_bytes[i];
+  f.sec_off = (const uint64_t*)(cbase + c.sec_off); f.sec_size = (const uint64_t*)(cbase + c.sec_size);
+  f.single_section = p.single_section;
+  f.lf_start_bitpos = p.global_data_bitpos;  // VarDCT without extra channels: LfGroup follows LfGlobal directly
+  f.stream_end_bitpos = (uint64_t*)(dwork_ + o.end_bitpos);
+  if (p.has_global_tree) {
+    f.tree = (const TreeNode*)(cbase + c.tree);
+    f.tree_nodes = (uint32_t)p.tree.nodes.size();
+    f.mod_code = ViewCode(p.tree_code, cbase, c.mod_ctx, c.mod_cfg, c.mod_alias, c.mod_pc, c.mod_po, c.mod_ps);
+    f.mod_cfg_uniform = p.tree_code.cfg.empty() ? 0xFFFFFFFFu : p.tree_code.cfg[0];
+    for (uint32_t v : p.tree_code.cfg) if (v != p.tree_code.cfg[0]) f.mod_cfg_uniform = 0xFFFFFFFFu;
+  }
+  f.uses_wp = p.tree.uses_wp; f.gwp = p.gwp;
+  f.mod_unit_passes = p.ModUnitPasses(); f.mod_pass = p.mod_pass;
+  for (int k = 0; k < 11; k++) { f.pass_min_shift[k] = p.pass_min_shift[k]; f.pass_max_shift[k] = p.pass_max_shift[k]; }
+  f.tree_max_prop = (uint32_t)p.tree.max_prop;
+  for (int k = 0; k < 3; k++) { f.hs[k] = p.hs[k]; f.vs[k] = p.vs[k]; }
+  f.subsampled = p.subsampled;
+  if (!c.local.empty()) {
+    // descriptor table of the frame's units (0 = global stream), zero = "uses the frame's tree"
+    ModLocalDev* table = &local_host_[local_first_[i]];
+    f.mod_local = dlocal_ + local_first_[i];
+    for (size_t k = 0; k < c.local.size(); k++) FillLocalDev(table[c.local[k].unit], p.local_streams[k].tree, p.local_streams[k].code, p.local_streams[k].data_bitpos, c.local[k], cbase);
+  }
+  if (!p.lf_local.empty()) {
+    // LfGroup sub-streams: [3 g + k] behind the unit table, zero = "uses the frame's tree"; the frame takes LfDecodeLocalKernel
+    const size_t first = local_first_[i] + (p.local_streams.empty() ? 0 : 1 + (size_t)p.NumModUnits());
+    ModLocalDev* table = &local_host_[first];
+    f.lf_local = dlocal_ + first;
+    for (const ConstOffsets::Local& l : c.lf_local) {
+      const FramePlan::LfLocal& ll = p.lf_local[l.unit];
+      FillLocalDev(table[l.unit], ll.tree, ll.code, ll.data_bitpos, l, cbase);
+      f.lf_lz77 |= ll.code.lz77 ? 1u : 0u;
     }
-    local_host_.assign(std::max<size_t>(total, 1), ModLocalDev());
-    for (auto& d : local_host_) memset(&d, 0, sizeof(d));
-    DevReserve((void**)&dlocal_, &local_cap_, sizeof(ModLocalDev) * local_host_.size());
+    if (p.has_global_tree && p.tree_code.lz77) f.lf_lz77 = 1;
+    f.tree_max_prop = (uint32_t)p.max_prop;      // (every tree the LF streams may use: whether they keep previous-channel references)
   }
-  vec<int> single;
-  for (int i = 0; i < n; i++) if (images_[i]->plan.single_section && !images_[i]->plan.modular) {
-    single.push_back(i);
-    images_[i]->plan.ac_code.clear();      // (a batch that is prepared again: HfGlobal is parsed afresh below, fill_frame must not look for its tables yet)
+  f.bcm = (const BlockCtxDev*)(cbase + c.bcm);
+  f.status = (uint32_t*)(dwork_ + status_off_) + i;
+  f.frame_flags = (uint32_t*)(dwork_ + flags_off_) + i;
+  f.hf_written = (uint32_t*)(dwork_ + hfw_off_) + i;
+  f.od = FillOutput(e, dwork_, dbig_);
+  f.upsampling = p.upsampling; f.img_w = e.ih.xsize; f.img_h = e.ih.ysize;
+  if (DecodedAtEighth(i)) { f.lf_only = 1; f.img_w = (p.width + 7) / 8; f.img_h = (p.height + 7) / 8; }     // (the picture LfOutputKernel writes; out_stride is SetOutput's, of the same picture)
+  if (p.upsampling > 1) { f.up_weights = (const float*)(cbase + c.up_weights); for (int k = 0; k < 4; k++) f.up_plane[k] = (float*)(dbig_ + o.up_plane[k]); }
+  f.post_mode = e.complex ? 1 : 0;
+  f.lz_window = o.lz_window == (size_t)-1 ? nullptr : (uint32_t*)(dwork_ + o.lz_window);
+  f.lz_ac_window = o.lz_ac_window == (size_t)-1 ? nullptr : (uint32_t*)(dwork_ + o.lz_ac_window);
+  f.lz_lf_base = 1 + p.NumModUnits();
+  f.wp_scratch = (int32_t*)(dwork_ + o.wp_scratch); f.wp_scratch_stride = o.wp_scratch_stride;
+}
+
+// quantiser, colour and filter parameters, LF-stage buffers, planes and, once HfGlobal has been parsed, the per-pass tables and quant tables of a VarDCT frame
+void Batch::FillFrameVarDct(int i, const uint8_t* cbase, const PrepareState& st) {
+  const ImageEntry& e = *images_[i]; const FramePlan& p = e.plan;
+  const ConstOffsets& c = st.co[i]; const WorkOffsets& o = st.wo[i];
+  FrameDev& f = frames_host_[i];
+  const float inv_gs = 65536.0f / (float)p.global_scale;
+  const float inv_quant_lf = inv_gs / (float)p.quant_lf;
+  for (int k = 0; k < 3; k++) f.lf_fac[k] = p.m_lf[k] * inv_quant_lf;
+  f.cfl_lf_x = p.base_x + (float)p.ytox_lf * (1.0f / (float)p.color_factor);
+  f.cfl_lf_b = p.base_b + (float)p.ytob_lf * (1.0f / (float)p.color_factor);
+  f.inv_global_scale = inv_gs;
+  f.x_dm = std::pow(0.8f, (float)p.x_qm_scale - 2.0f); f.b_dm = std::pow(0.8f, (float)p.b_qm_scale - 2.0f);
+  for (int k = 0; k < 4; k++) f.quant_bias[k] = e.ih.quant_bias[k];
+  f.color_scale = 1.0f / (float)p.color_factor; f.base_x = p.base_x; f.base_b = p.base_b;
+  f.skip_lf_smoothing = (p.flags & 128) != 0 || p.use_lf_frame;     // (dec_frame.cc FinalizeDC: no adaptive smoothing of an LF frame's samples)
+  f.use_lf_frame = p.use_lf_frame ? 1 : 0;
+  f.gab = p.lf.gab; f.epf_iters = p.lf.epf_iters;
+  for (int k = 0; k < 3; k++) {
+    const float w1 = p.lf.gab_w[2 * k], w2 = p.lf.gab_w[2 * k + 1];
+    const float div = 1.0f + 4.0f * (w1 + w2);
+    f.gab_w[3 * k] = 1.0f / div; f.gab_w[3 * k + 1] = w1 / div; f.gab_w[3 * k + 2] = w2 / div;
   }
-  if (!single.empty()) {
-    // temporary upload of what exists so far
-    uint8_t* tmpc = nullptr;
-    HIP_CHECK(hipMalloc((void**)&tmpc, Align(hconst_.size())));
-    HIP_CHECK(hipMemcpyAsync(tmpc, hconst_.data(), hconst_.size(), hipMemcpyHostToDevice, stream));
-    vec<FrameDev> tmpf;
-    LaunchCfg pcfg = cfg;
-    pcfg.any_local_lf = 0;
-    for (int i : single) { fill_frame(i, tmpc); tmpf.push_back(frames_host_[i]); if (!images_[i]->plan.lf_local.empty()) pcfg.any_local_lf = 1; }
-    HIP_CHECK(hipMemcpyAsync(dframes_, tmpf.data(), sizeof(FrameDev) * tmpf.size(), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(dlocal_, local_host_.data(), sizeof(ModLocalDev) * local_host_.size(), hipMemcpyHostToDevice, stream));   // (streams with their own trees)
-    if (any_modchan_) LaunchModularGlobal(dframes_, (int)tmpf.size(), pcfg, stream_v);   // extra channels of a one-group frame precede the LfGroup
-    LaunchLfDecode(dframes_, (int)tmpf.size(), 1, pcfg, stream_v);
-    HIP_CHECK(hipStreamSynchronize(stream));
-    for (size_t k = 0; k < single.size(); k++) {
-      const int i = single[k];
-      uint32_t status = 0;
-      uint64_t endpos[2] = {0, 0};
-      HIP_CHECK(hipMemcpy(&status, tmpf[k].status, 4, hipMemcpyDeviceToHost));
-      HIP_CHECK(hipMemcpy(endpos, tmpf[k].stream_end_bitpos, 16, hipMemcpyDeviceToHost));
-      if (status) { (void)hipFree(tmpc); throw ParseError(status & kErrUnsupported ? "unsupported: stream feature (LF stage)" : "corrupt LF group stream", (status & kErrUnsupported) != 0); }
-      ParseHfGlobal(images_[i]->cs, images_[i]->ih, endpos[0], &images_[i]->plan);
+  for (int k = 0; k < 8; k++) f.epf_sharp_lut[k] = p.lf.sharp_lut[k];
+  for (int k = 0; k < 3; k++) f.epf_channel_scale[k] = p.lf.channel_scale[k];
+  f.epf_quant_mul = p.lf.quant_mul; f.epf_quant_scale = (float)p.global_scale / 65536.0f;
+  const float scales[3] = {p.lf.pass0_sigma_scale, 1.0f, p.lf.pass2_sigma_scale};
+  for (int k = 0; k < 3; k++) { f.epf_sm[k] = scales[k] * 1.65f; f.epf_bsm[k] = f.epf_sm[k] * p.lf.border_sad_mul; }
+  FillColor(e.ih, p.do_ycbcr, f);
+  for (int k = 0; k < 3; k++) {
+    f.lfq[k] = (int32_t*)(dwork_ + o.lfq[k]); f.lf[k] = (float*)(dwork_ + o.lf[k]); f.lf_tmp[k] = (float*)(dwork_ + o.lf_tmp[k]);
+    f.llf[k] = (float*)(dwork_ + o.llf[k]); f.coeff[k] = DecodedAtEighth(i) ? nullptr : (int32_t*)(dcoef_ + o.coeff[k]);
+    f.plane_a[k] = o.plane_a[k] == (size_t)-1 ? nullptr : (float*)(dbig_ + o.plane_a[k]); f.plane_b[k] = o.plane_b[k] == (size_t)-1 ? nullptr : (float*)(dbig_ + o.plane_b[k]);
+  }
+  f.blk_info = (uint32_t*)(dwork_ + o.blk_info); f.coef_off = (uint32_t*)(dwork_ + o.coef_off);
+  f.vb_list = (uint2*)(dwork_ + o.vb_list); f.vb_count = (uint32_t*)(dwork_ + o.vb_count);
+  f.place_rec = (uint4*)(dwork_ + o.place_rec); f.place_cnt = (uint32_t*)(dwork_ + o.place_cnt); f.band_start = (uint32_t*)(dwork_ + o.band_start);
+  f.ytox = (int8_t*)(dwork_ + o.ytox); f.ytob = (int8_t*)(dwork_ + o.ytob);
+  f.inv_sigma = (float*)(dwork_ + o.inv_sigma);
+  f.lf_scratch = (int32_t*)(dwork_ + o.lf_scratch); f.lf_scratch_stride = o.lf_scratch_stride;
+  // HfGlobal-derived fields (present once parsed)
+  if (!p.ac_code.empty()) {
+    f.num_passes = cfg.max_passes > 0 ? std::min<uint32_t>(p.num_passes, (uint32_t)cfg.max_passes) : p.num_passes;     // (a progressive flush shows the first passes only; the later ones' sections stay unread)
+    f.passes = dpasses_ + pass_first_[i];
+    for (uint32_t ps = 0; ps < p.num_passes; ps++) {
+      const ConstOffsets::Pass& cp = c.pass[ps];
+      PassDev& pd = passes_host_[pass_first_[i] + ps];
+      pd.code = ViewCode(p.ac_code[ps], cbase, cp.ac_ctx, cp.ac_cfg, cp.ac_alias, cp.ac_pc, cp.ac_po, cp.ac_ps);
+      for (int k = 0; k < 39; k++) pd.orders[k] = (const uint16_t*)(cbase + cp.orders[k]);
+      pd.shift = ps + 1 < p.num_passes ? p.pass_shift[ps] : 0; pd.pad = 0;
     }
-    HIP_CHECK(hipMemsetAsync(dwork_ + status_off_, 0, (size_t)n * 4, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    (void)hipFree(tmpc);
+    f.ac_code = passes_host_[pass_first_[i]].code;
+    for (int k = 0; k < 39; k++) f.orders[k] = passes_host_[pass_first_[i]].orders[k];
+    for (int k = 0; k < 17 * 3; k++) f.qtable[k] = c.has_qtable[k / 3] ? (const float*)(cbase + c.qtable[k]) : nullptr;
+    f.num_hf_presets = p.num_hf_presets;
+    uint32_t bits = 0; while ((1u << bits) < p.num_hf_presets) bits++;
+    f.preset_bits = bits;
+    f.hf_start_bitpos = p.end_bitpos;
   }
-  // ---- HfGlobal tables (now available for every VarDCT frame)
+}
+
+// the Modular channels of a frame (LayOutModChannels): channel table, scratch; VarDCT frames: their own weighted-predictor rows and the alpha plane the write stage reads
+void Batch::FillFrameModChannels(int i, const uint8_t* cbase, const PrepareState& st) {
+  const FramePlan& p = images_[i]->plan;
+  const WorkOffsets& o = st.wo[i];
+  FrameDev& f = frames_host_[i];
+  f.mod_nchan = (uint32_t)p.gchannels.size(); f.mod_nb_meta = p.nb_meta_channels;
+  f.mod_chan = (const ModChanDev*)(cbase + st.co[i].mod_chan); f.mod_base = dwork_;
+  f.mod_global_decodable = p.global_decodable; f.mod_global_bitpos = p.global_data_bitpos;
+  f.mod_group_scratch = (int32_t*)(dwork_ + o.mod_scratch); f.mod_group_scratch_stride = o.mod_scratch_stride;
+  f.mod_bits = images_[i]->ih.depth.bits;
+  if (p.modular) return;
+  f.hf_end_bitpos = (uint64_t*)(dwork_ + o.hf_end);
+  f.mod_wp_scratch = (int32_t*)(dwork_ + o.mod_wp); f.mod_wp_stride = o.mod_wp_stride;
+  f.alpha_plane = vardct_alpha_[i].has ? (const int32_t*)(dwork_ + vardct_alpha_[i].off) : nullptr;
+  f.alpha_factor = vardct_alpha_[i].factor;
+}
+
+// Descriptors of the sub-streams with their own tree / code, one table per frame that has any: sized and reserved before the one-section pre-run, whose LF decode
+// reads them (FillFrameDev fills them).  Reads and adds nothing of PrepareState.
+void Batch::SizeLocalTables() {
+  const int n = (int)images_.size();
+  local_first_.assign(n, 0);
+  size_t total = 0;
   for (int i = 0; i < n; i++) {
-    ImageEntry& e = *images_[i];
-    FramePlan& p = e.plan;
-    ConstOffsets& c = co[i];
+    const FramePlan& p = images_[i]->plan;
+    local_first_[i] = total;
+    if (!p.local_streams.empty()) total += 1 + (size_t)p.NumModUnits();
+    total += p.lf_local.size();
+  }
+  local_host_.assign(std::max<size_t>(total, 1), ModLocalDev());
+  for (auto& d : local_host_) memset(&d, 0, sizeof(d));
+  DevReserve((void**)&dlocal_, &local_cap_, sizeof(ModLocalDev) * local_host_.size());
+}
+
+// Single-section VarDCT frames: HfGlobal starts where the device-decoded LfGroup ends.  The LF stage of those frames runs now, from a temporary upload of what the
+// constant arena holds so far; the end position is read back and HfGlobal parsed on the host.  Reads co, wo, cs_bytes (FillFrameDev); adds the frames' plan.ac_code etc.
+void Batch::PreRunSingleSection(PrepareState& st) {
+  hipStream_t stream = st.stream;
+  vec<int> single;
+  for (int i = 0; i < st.n; i++) if (images_[i]->plan.single_section && !images_[i]->plan.modular) {
+    single.push_back(i);
+    images_[i]->plan.ac_code.clear();      // (a batch that is prepared again: HfGlobal is parsed afresh below, FillFrameVarDct must not look for its tables yet)
+  }
+  if (single.empty()) return;
+  struct DevFree { uint8_t* p = nullptr; ~DevFree() { (void)hipFree(p); } } tmpc;      // freed on every way out
+  HIP_CHECK(hipMalloc((void**)&tmpc.p, Align(hconst_.size())));
+  HIP_CHECK(hipMemcpyAsync(tmpc.p, hconst_.data(), hconst_.size(), hipMemcpyHostToDevice, stream));
+  vec<FrameDev> tmpf;
+  LaunchCfg pcfg = cfg;
+  pcfg.any_local_lf = 0;
+  for (int i : single) { FillFrameDev(i, tmpc.p, st); tmpf.push_back(frames_host_[i]); if (!images_[i]->plan.lf_local.empty()) pcfg.any_local_lf = 1; }
+  HIP_CHECK(hipMemcpyAsync(dframes_, tmpf.data(), sizeof(FrameDev) * tmpf.size(), hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipMemcpyAsync(dlocal_, local_host_.data(), sizeof(ModLocalDev) * local_host_.size(), hipMemcpyHostToDevice, stream));   // (streams with their own trees)
+  if (any_modchan_) LaunchModularGlobal(dframes_, (int)tmpf.size(), pcfg, stream);   // extra channels of a one-group frame precede the LfGroup
+  LaunchLfDecode(dframes_, (int)tmpf.size(), 1, pcfg, stream);
+  HIP_CHECK(hipStreamSynchronize(stream));
+  for (size_t k = 0; k < single.size(); k++) {
+    const int i = single[k];
+    uint32_t status = 0;
+    uint64_t endpos[2] = {0, 0};
+    HIP_CHECK(hipMemcpy(&status, tmpf[k].status, 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(endpos, tmpf[k].stream_end_bitpos, 16, hipMemcpyDeviceToHost));
+    if (status) throw ParseError(status & kErrUnsupported ? "unsupported: stream feature (LF stage)" : "corrupt LF group stream", (status & kErrUnsupported) != 0);
+    ParseHfGlobal(images_[i]->cs, images_[i]->ih, endpos[0], &images_[i]->plan);
+  }
+  HIP_CHECK(hipMemsetAsync(dwork_ + status_off_, 0, (size_t)st.n * 4, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// "hf_tables": HfGlobal's tables, now parsed for every VarDCT frame.  Reads natural_off; adds co's pass tables (AC codes, coefficient orders) and quant tables, qcache.
+void Batch::PutHfTables(PrepareState& st) {
+  Arena& arena = st.arena;
+  for (int i = 0; i < st.n; i++) {
+    FramePlan& p = images_[i]->plan;
+    ConstOffsets& c = st.co[i];
     if (p.modular) continue;
     c.pass.assign(p.num_passes, ConstOffsets::Pass());
     for (uint32_t ps = 0; ps < p.num_passes; ps++) {
@@ -1620,292 +1772,233 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
       PutCode(arena, p.ac_code[ps], &cp.ac_ctx, &cp.ac_cfg, &cp.ac_alias, &cp.ac_pc, &cp.ac_po, &cp.ac_ps);
       for (int b = 0; b < 13; b++) for (int ch = 0; ch < 3; ch++) {
         const auto& cu = p.custom_order[(size_t)ps * 39 + b * 3 + ch];
-        cp.orders[b * 3 + ch] = cu.empty() ? natural_off[b] : arena.Put(cu.data(), cu.size() * 2);
+        cp.orders[b * 3 + ch] = cu.empty() ? st.natural_off[b] : arena.Put(cu.data(), cu.size() * 2);
       }
     }
-    if (p.num_passes > 1 && !scaled(i)) any_multipass_ = true;     // (what the HF stage must handle: frames decoded at 1:8 never reach it)
+    if (p.num_passes > 1 && !DecodedAtEighth(i)) any_multipass_ = true;     // (what the HF stage must handle: frames decoded at 1:8 never reach it)
     for (int k = 0; k < 17; k++) {
-      int hit = -1;
-      for (size_t q = 0; q < qcache.size(); q++) if (qcache[q].kind == k && spec_equal(*qcache[q].spec, p.qspec[k])) { hit = (int)q; break; }
-      if (hit < 0) {
-        QCache qc; qc.spec = &p.qspec[k]; qc.kind = k;
-        for (int ch = 0; ch < 3; ch++) {
-          // the DCT128/256 tables are large (up to 64K weights per channel): computed once per process and spec
-          struct Big { QuantTableSpec spec; int kind, ch; std::vector<float> t; };   // process-lifetime cache: plain allocator
-          static std::mutex mu;
-          static std::vector<Big> big;
-          vec<float> local;
-          const vec<float>* t = &local;
-          if (k >= 13) {
-            std::lock_guard<std::mutex> lock(mu);
-            const Big* found = nullptr;
-            for (const Big& b : big) if (b.kind == k && b.ch == ch && spec_equal(b.spec, p.qspec[k])) { found = &b; break; }
-            if (!found) {
-              if (big.size() >= 48) big.clear();
-              big.push_back(Big{p.qspec[k], k, ch, {}});
-              { vec<float> tmp; ComputeQuantTable(p.qspec[k], k, ch, &tmp); big.back().t.assign(tmp.begin(), tmp.end()); }
-              found = &big.back();
-            }
-            local.assign(found->t.begin(), found->t.end());
-          } else ComputeQuantTable(p.qspec[k], k, ch, &local);
-          qc.off[ch] = arena.Put(t->data(), t->size() * 4);
-        }
-        qcache.push_back(qc); hit = (int)qcache.size() - 1;
-      }
-      for (int ch = 0; ch < 3; ch++) c.qtable[k * 3 + ch] = qcache[hit].off[ch];
+      const size_t* off = QuantTableOffsets(arena, st.qcache, p.qspec[k], k);
+      for (int ch = 0; ch < 3; ch++) c.qtable[k * 3 + ch] = off[ch];
       c.has_qtable[k] = true;
     }
   }
-  mark("hf_tables");
-  {  // LDS right-sizing for the decode kernels
-    auto code_bytes = [](const HostCode& c, bool ctx) { if (c.use_prefix || c.lz77) return 16;   /* prefix codes / LZ77 streams are read through the tables in global memory: nothing to size the LDS for */
-      return (int)(((c.num_clusters * 4 + 15) & ~15u) + (ctx ? ((c.num_ctx + 15) & ~15u) : 0) + ((size_t)c.num_clusters << c.log_alpha) * 8); };
-    auto code_bytes_compact = [](const HostCode& c) { if (c.use_prefix || c.lz77) return 16;
-      return (int)(((c.num_clusters * 4 + 15) & ~15u) + ((c.num_ctx + 15) & ~15u) + (((((size_t)c.num_clusters << c.log_alpha) * 6) + 15) & ~(size_t)15)); };
-    cfg.ac_code_bytes_compact = 16;
-    cfg.max_tree_nodes = 1; cfg.mod_code_bytes = 16; cfg.ac_code_bytes = 16; cfg.any_wp = 0; cfg.any_local_trees = 0; cfg.any_local_lf = 0; cfg.any_subsampled = 0; cfg.any_prefix_ac = 0;
-    for (int i = 0; i < n; i++) {
-      const FramePlan& p = images_[i]->plan;
-      if (p.has_global_tree) { cfg.max_tree_nodes = std::max<int>(cfg.max_tree_nodes, (int)p.tree.nodes.size()); cfg.mod_code_bytes = std::max(cfg.mod_code_bytes, code_bytes(p.tree_code, false)); cfg.any_wp |= p.tree.uses_wp ? 1 : 0; }
-      for (auto& ls : p.local_streams) {
-        cfg.max_tree_nodes = std::max<int>(cfg.max_tree_nodes, (int)ls.tree.nodes.size()); cfg.mod_code_bytes = std::max(cfg.mod_code_bytes, code_bytes(ls.code, false)); cfg.any_wp |= ls.tree.uses_wp ? 1 : 0;
-        if (ls.unit != 0) cfg.any_local_trees = 1;
-      }
-      if (!p.lf_local.empty()) cfg.any_local_lf = 1;
-      for (auto& l : p.lf_local) if (l.present) {
-        cfg.max_tree_nodes = std::max<int>(cfg.max_tree_nodes, (int)l.tree.nodes.size()); cfg.mod_code_bytes = std::max(cfg.mod_code_bytes, code_bytes(l.code, false)); cfg.any_wp |= l.tree.uses_wp ? 1 : 0;
-      }
-      if (!p.modular && scaled(i)) continue;     // (the rest sizes and picks the HF / IDCT kernels)
-      if (!p.modular) for (auto& code : p.ac_code) { cfg.ac_code_bytes = std::max(cfg.ac_code_bytes, code_bytes(code, true)); cfg.ac_code_bytes_compact = std::max(cfg.ac_code_bytes_compact, code_bytes_compact(code)); }
-      if (p.subsampled) cfg.any_subsampled = 1;
-      if (!p.modular) for (auto& code : p.ac_code) if (code.use_prefix || code.lz77) cfg.any_prefix_ac = 1;
-    }
-    if (getenv("JXL_HIP_DEBUG_LDS")) fprintf(stderr, "[jxl-hip] LDS sizing: tree nodes %d, modular code %d B, AC code %d B (compact %d B), BlockCtxDev %zu B\n", cfg.max_tree_nodes, cfg.mod_code_bytes, cfg.ac_code_bytes, cfg.ac_code_bytes_compact, sizeof(BlockCtxDev));
-  }
-  {  // per-pass table descriptors (device array next to the frame descriptors)
-    pass_first_.assign(n, 0);
-    size_t total = 0;
-    for (int i = 0; i < n; i++) { pass_first_[i] = total; total += images_[i]->plan.modular ? 0 : images_[i]->plan.num_passes; }
-    passes_host_.assign(std::max<size_t>(total, 1), PassDev());
-    DevReserve((void**)&dpasses_, &passes_cap_, sizeof(PassDev) * passes_host_.size());
-  }
-  if (any_complex_) {
-    vec<size_t> upw(n, 0);
-    for (int i = 0; i < n; i++) upw[i] = co[i].up_weights;
-    PlanPostOps(hconst_, upw);
-  }
-  mark("misc");
-  lf_simt_ = LfSimtPlan();
-  // ---- varblock placement units: every 32-row band of every LF group of every VarDCT frame, the tallest / widest first (the lanes of a
-  // wavefront then carry bands of similar length)
-  size_t place_units_off = 0;
-  {
-    vec<uint2> units;
-    vec<uint32_t> ucost;
-    for (int i = 0; i < n; i++) {
-      const FramePlan& p = images_[i]->plan;
-      if (p.modular) continue;
-      for (uint32_t g = 0; g < p.num_lf_groups; g++) {
-        const uint32_t gx = g % p.xlfgroups, gy = g / p.xlfgroups;
-        const uint32_t gbw = std::min<uint32_t>(256, p.bw - gx * 256), gbh = std::min<uint32_t>(256, p.bh - gy * 256);
-        for (uint32_t band = 0; band * 32 < gbh; band++) { units.push_back(make_uint2((uint32_t)i, g | (band << 16))); ucost.push_back(std::min<uint32_t>(32, gbh - band * 32) * gbw); }
-      }
-    }
-    vec<uint32_t> order(units.size());
-    for (size_t k = 0; k < order.size(); k++) order[k] = (uint32_t)k;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return ucost[a] > ucost[b]; });
-    vec<uint2> sorted;
-    for (uint32_t k : order) sorted.push_back(units[k]);
-    place_units_off = arena.Put(sorted.data(), sorted.size() * sizeof(uint2));
-    lf_simt_.num_units = (uint32_t)sorted.size();
-  }
-  // ---- SIMT LF decode plan (cfg.lane_stride_lf < 64): streams of eligible frames, spread over lanes of about equal work
-  vec<uint8_t> simt_frame(n, 0);
-  size_t simt_streams_off = 0, simt_lanes_off = 0, simt_luts_off = 0;
-  if (any_vardct_ && cfg.lane_stride_lf < 64) {
-    vec<LfSimtStream> streams;
-    vec<uint64_t> cost;
-    vec<uint8_t> luts;
-    std::map<std::string, uint32_t> lut_of;       // table content -> offset in the blob (frames of one encoder share most tables)
-    bool general_streams = false;                 // some eligible stream needs the instantiation with two-property tables / the rarer properties and predictors
-    bool wp_streams = false;                      // some eligible stream keeps weighted-predictor state: the batch takes that instantiation of the kernel
-    for (int i = 0; i < n; i++) {
-      const FramePlan& p = images_[i]->plan;
-      if (p.modular || !p.has_global_tree || !p.lf_local.empty() || p.tree_code.use_prefix || p.tree_code.lz77 || p.tree_code.log_alpha > 8 || p.tree_code.num_clusters > 256 || p.use_lf_frame) continue;
-      {   // extra-channel sub-channels squeezed by >= 3 sit in the middle of the LfGroup sections: only the one-wavefront-per-stream kernel decodes those
-        bool lf_modular = false;
-        for (size_t c = p.global_decodable; c < p.gchannels.size(); c++) lf_modular |= p.gchannels[c].w && p.gchannels[c].h && std::min(p.gchannels[c].hshift, p.gchannels[c].vshift) >= 3;
-        if (lf_modular) continue;
-      }
-      vec<LfSimtStream> mine;
-      bool ok = true;
-      for (uint32_t g = 0; g < p.num_lf_groups && ok; g++) {
-        LfSimtStream st;
-        memset(&st, 0, sizeof(st));
-        st.frame = (uint32_t)i; st.group = g;
-        for (int c = 0; c < 7 && ok; c++) {
-          LfChanClass cl;
-          ok = ClassifyLfChannel(p.tree, p.tree_code, c < 3 ? c : c - 3, c < 3 ? 1 + g : 1 + 2 * p.num_lf_groups + g, &cl);
-          if (ok && cl.uses_wp && c == 5) ok = false;      // (the block-info rows are up to 65 536 wide: the per-lane weighted-predictor rows hold 256)
-          if (!ok) break;
-          auto intern = [&](const uint8_t* bytes, size_t size) {      // table content -> offset in the blob (frames of one encoder share most tables)
-            const std::string key((const char*)bytes, size);
-            auto it = lut_of.find(key);
-            if (it == lut_of.end()) { it = lut_of.emplace(key, (uint32_t)luts.size()).first; luts.insert(luts.end(), bytes, bytes + size); }
-            return it->second;
-          };
-          auto word = [&](const LfRowClass& rc) { return rc.kind | (rc.pred << 2) | (rc.sel_a << 5) | (rc.sel_b << 7) | (cl.uses_wp ? kLfSimtWpLive : 0u) | (rc.cluster << 16); };
-          if (cl.rows.size() == 1) {
-            st.chan[c].lut_off = cl.rows[0].kind ? intern(cl.rows[0].lut.data(), cl.rows[0].lut.size()) : 0;
-            st.chan[c].info = word(cl.rows[0]);
-          } else {   // the class depends on the row: [512 bytes: row -> class][classes x {table offset, class word}]
-            vec<uint8_t> blob(512 + 8 * cl.rows.size());
-            memcpy(blob.data(), cl.row_to_class, 512);
-            for (size_t k = 0; k < cl.rows.size(); k++) {
-              const uint32_t e[2] = {cl.rows[k].kind ? intern(cl.rows[k].lut.data(), cl.rows[k].lut.size()) : 0u, word(cl.rows[k])};
-              memcpy(blob.data() + 512 + 8 * k, e, 8);
-            }
-            st.chan[c].lut_off = intern(blob.data(), blob.size());
-            st.chan[c].info = kLfSimtRows | (cl.uses_wp ? kLfSimtWpLive : 0u);
-          }
-          if (cl.uses_wp) wp_streams = true;
-          for (const LfRowClass& rc : cl.rows)      // beyond what the lean instantiation handles: one cluster per row or a table over W + N - NW; zero / W / clamped gradient
-            if (rc.kind == 2 || (rc.kind == 1 && rc.sel_a != 0) || !(rc.pred == 0 || rc.pred == 1 || rc.pred == 3)) general_streams = true;
-        }
-        if (ok) mine.push_back(st);
-      }
-      if (!ok) continue;
-      simt_frame[i] = 1;
-      for (auto& st : mine) {
-        const uint32_t gx = st.group % p.xlfgroups, gy = st.group / p.xlfgroups;
-        const uint64_t gbw = std::min<uint32_t>(256, p.bw - gx * 256), gbh = std::min<uint32_t>(256, p.bh - gy * 256);
-        streams.push_back(st); cost.push_back(gbw * gbh * 5 + 2048);
-      }
-    }
-    if (!streams.empty()) {
-      // longest-processing-time-first; the number of lanes grows from the lower bound (total work / longest stream) until no lane carries
-      // noticeably more than the longest stream: a lane more costs nothing, a lane with two long streams doubles the stage's latency
-      uint64_t total = 0, longest = 0;
-      for (uint64_t cst : cost) { total += cst; longest = std::max(longest, cst); }
-      vec<uint32_t> order(streams.size());
-      for (size_t k = 0; k < order.size(); k++) order[k] = (uint32_t)k;
-      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-      vec<vec<uint32_t>> lane_streams;
-      for (size_t nlanes = std::max<size_t>(1, std::min<size_t>(streams.size(), (size_t)((total + longest - 1) / longest)));; nlanes = std::min(streams.size(), nlanes + std::max<size_t>(1, nlanes / 64))) {
-        lane_streams.assign(nlanes, vec<uint32_t>());
-        std::priority_queue<std::pair<uint64_t, uint32_t>, std::vector<std::pair<uint64_t, uint32_t>>, std::greater<std::pair<uint64_t, uint32_t>>> pq;
-        for (size_t l = 0; l < nlanes; l++) pq.push({0, (uint32_t)l});
-        uint64_t makespan = 0;
-        for (uint32_t k : order) { auto top = pq.top(); pq.pop(); lane_streams[top.second].push_back(k); makespan = std::max(makespan, top.first + cost[k]); pq.push({top.first + cost[k], top.second}); }
-        if (makespan <= longest + longest / 16 || nlanes >= streams.size()) break;
-      }
-      // lanes of the same frames next to each other (they read the same tables)
-      std::stable_sort(lane_streams.begin(), lane_streams.end(), [&](const vec<uint32_t>& a, const vec<uint32_t>& b) { return streams[a[0]].frame < streams[b[0]].frame; });
-      vec<LfSimtStream> flat;
-      vec<LfSimtLane> lanes;
-      for (auto& ls : lane_streams) { lanes.push_back(LfSimtLane{(uint32_t)flat.size(), (uint32_t)ls.size()}); for (uint32_t k : ls) flat.push_back(streams[k]); }
-      simt_streams_off = arena.Put(flat.data(), flat.size() * sizeof(LfSimtStream));
-      simt_lanes_off = arena.Put(lanes.data(), lanes.size() * sizeof(LfSimtLane));
-      simt_luts_off = arena.Put(luts.data(), luts.size());
-      lf_simt_.num_lanes = (uint32_t)lanes.size();
-      lf_simt_.lanes_per_wave = (uint32_t)std::max(1, 64 / std::max(1, cfg.lane_stride_lf));
-      lf_simt_.any_legacy = 0; lf_simt_.any_wp = wp_streams ? 1 : 0; lf_simt_.any_general = general_streams || wp_streams ? 1 : 0;
+}
 
-      for (int i = 0; i < n; i++) if (!images_[i]->plan.modular && !simt_frame[i]) lf_simt_.any_legacy = 1;
+// LDS right-sizing for the decode kernels and what else of cfg follows from the parsed frames.  Reads and adds nothing of PrepareState.
+void Batch::SizeLds() {
+  cfg.ac_code_bytes_compact = 16;
+  cfg.max_tree_nodes = 1; cfg.mod_code_bytes = 16; cfg.ac_code_bytes = 16; cfg.any_wp = 0; cfg.any_local_trees = 0; cfg.any_local_lf = 0; cfg.any_subsampled = 0; cfg.any_prefix_ac = 0;
+  for (int i = 0; i < (int)images_.size(); i++) {
+    const FramePlan& p = images_[i]->plan;
+    if (p.has_global_tree) SizeForModularStream(cfg, p.tree, p.tree_code);
+    for (auto& ls : p.local_streams) { SizeForModularStream(cfg, ls.tree, ls.code); if (ls.unit != 0) cfg.any_local_trees = 1; }
+    if (!p.lf_local.empty()) cfg.any_local_lf = 1;
+    for (auto& l : p.lf_local) if (l.present) SizeForModularStream(cfg, l.tree, l.code);
+    if (!p.modular && DecodedAtEighth(i)) continue;     // (the rest sizes and picks the HF / IDCT kernels)
+    if (!p.modular) for (auto& code : p.ac_code) { cfg.ac_code_bytes = std::max(cfg.ac_code_bytes, CodeBytes(code, true)); cfg.ac_code_bytes_compact = std::max(cfg.ac_code_bytes_compact, CodeBytesCompact(code)); }
+    if (p.subsampled) cfg.any_subsampled = 1;
+    if (!p.modular) for (auto& code : p.ac_code) if (code.use_prefix || code.lz77) cfg.any_prefix_ac = 1;
+  }
+  if (getenv("JXL_HIP_DEBUG_LDS")) fprintf(stderr, "[jxl-hip] LDS sizing: tree nodes %d, modular code %d B, AC code %d B (compact %d B), BlockCtxDev %zu B\n", cfg.max_tree_nodes, cfg.mod_code_bytes, cfg.ac_code_bytes, cfg.ac_code_bytes_compact, sizeof(BlockCtxDev));
+}
+
+// per-pass table descriptors (device array next to the frame descriptors; FillFrameVarDct fills them).  Reads and adds nothing of PrepareState.
+void Batch::SizePassTables() {
+  const int n = (int)images_.size();
+  pass_first_.assign(n, 0);
+  size_t total = 0;
+  for (int i = 0; i < n; i++) { pass_first_[i] = total; total += images_[i]->plan.modular ? 0 : images_[i]->plan.num_passes; }
+  passes_host_.assign(std::max<size_t>(total, 1), PassDev());
+  DevReserve((void**)&dpasses_, &passes_cap_, sizeof(PassDev) * passes_host_.size());
+}
+
+// Varblock placement units: every 32-row band of every LF group of every VarDCT frame, the tallest / widest first (the lanes of a wavefront then carry bands of
+// similar length).  Adds place_units_off; starts lf_simt_ anew.
+void Batch::PlanPlacementUnits(PrepareState& st) {
+  lf_simt_ = LfSimtPlan();
+  vec<uint2> units;
+  vec<uint32_t> ucost;
+  for (int i = 0; i < st.n; i++) {
+    const FramePlan& p = images_[i]->plan;
+    if (p.modular) continue;
+    for (uint32_t g = 0; g < p.num_lf_groups; g++) {
+      const uint32_t gx = g % p.xlfgroups, gy = g / p.xlfgroups;
+      const uint32_t gbw = std::min<uint32_t>(256, p.bw - gx * 256), gbh = std::min<uint32_t>(256, p.bh - gy * 256);
+      for (uint32_t band = 0; band * 32 < gbh; band++) { units.push_back(make_uint2((uint32_t)i, g | (band << 16))); ucost.push_back(std::min<uint32_t>(32, gbh - band * 32) * gbw); }
     }
   }
-  mark("simt_plan");
-  // resized outputs: the table of ResizeArgs takes its place in the constant arena here and is filled below, once the arena's device address is known — on every
-  // Prepare, from the arenas as they are now (shared planes may have moved); sorted by slot count, each run of equal slots cut into groups of resize_group_max entries
-  auto resize_slots = [&](const ResizePlan& rp) { return std::min(4u, std::max(1u, images_[rp.unit]->out.num_channels)); };   // (which ResizeKernel<NC> the image takes: sort key and group key)
-  std::stable_sort(resize_plans_.begin(), resize_plans_.end(), [&](const ResizePlan& a, const ResizePlan& b) { return resize_slots(a) < resize_slots(b); });
+  vec<uint2> sorted;
+  for (uint32_t k : OrderByCostDescending(ucost)) sorted.push_back(units[k]);
+  st.place_units_off = st.arena.Put(sorted.data(), sorted.size() * sizeof(uint2));
+  lf_simt_.num_units = (uint32_t)sorted.size();
+}
+
+// SIMT LF decode plan (cfg.lane_stride_lf < 64): the LF-group streams of the eligible frames, spread over lanes of about equal work.  Adds simt_frame and the
+// offsets of the streams, lanes and cluster tables; fills lf_simt_'s counts and flags.
+void Batch::PlanLfSimt(PrepareState& st) {
+  if (!any_vardct_ || cfg.lane_stride_lf >= 64) return;
+  vec<LfSimtStream> streams;
+  vec<uint64_t> cost;
+  LfSimtTables tables;
+  for (int i = 0; i < st.n; i++) {
+    const FramePlan& p = images_[i]->plan;
+    vec<LfSimtStream> mine;
+    if (!ClassifyLfStreams(p, (uint32_t)i, tables, &mine)) continue;
+    st.simt_frame[i] = 1;
+    for (auto& s : mine) {
+      const uint32_t gx = s.group % p.xlfgroups, gy = s.group / p.xlfgroups;
+      const uint64_t gbw = std::min<uint32_t>(256, p.bw - gx * 256), gbh = std::min<uint32_t>(256, p.bh - gy * 256);
+      streams.push_back(s); cost.push_back(gbw * gbh * 5 + 2048);
+    }
+  }
+  if (streams.empty()) return;
+  vec<vec<uint32_t>> lane_streams = PackLanes(cost);
+  // lanes of the same frames next to each other (they read the same tables)
+  std::stable_sort(lane_streams.begin(), lane_streams.end(), [&](const vec<uint32_t>& a, const vec<uint32_t>& b) { return streams[a[0]].frame < streams[b[0]].frame; });
+  vec<LfSimtStream> flat;
+  vec<LfSimtLane> lanes;
+  for (auto& ls : lane_streams) { lanes.push_back(LfSimtLane{(uint32_t)flat.size(), (uint32_t)ls.size()}); for (uint32_t k : ls) flat.push_back(streams[k]); }
+  st.simt_streams_off = st.arena.Put(flat.data(), flat.size() * sizeof(LfSimtStream));
+  st.simt_lanes_off = st.arena.Put(lanes.data(), lanes.size() * sizeof(LfSimtLane));
+  st.simt_luts_off = st.arena.Put(tables.luts.data(), tables.luts.size());
+  lf_simt_.num_lanes = (uint32_t)lanes.size();
+  lf_simt_.lanes_per_wave = (uint32_t)std::max(1, 64 / std::max(1, cfg.lane_stride_lf));
+  lf_simt_.any_legacy = 0; lf_simt_.any_wp = tables.wp ? 1 : 0; lf_simt_.any_general = tables.general || tables.wp ? 1 : 0;
+  for (int i = 0; i < st.n; i++) if (!images_[i]->plan.modular && !st.simt_frame[i]) lf_simt_.any_legacy = 1;
+}
+
+// Resized outputs: the table of ResizeArgs takes its place in the constant arena here (BuildResizeTable fills it once the arena's device address is known);
+// resize_plans_ sorted by slot count.  Adds the table's room to the arena.
+void Batch::PlaceResizeTable(PrepareState& st) {
+  std::stable_sort(resize_plans_.begin(), resize_plans_.end(), [&](const ResizePlan& a, const ResizePlan& b) { return ResizeSlots(*images_[a.unit]) < ResizeSlots(*images_[b.unit]); });
   resize_table_off_ = 0;
-  if (!resize_plans_.empty()) {
-    resize_table_off_ = arena.Put(nullptr, 0);                                                   // (an aligned place; Put copies from its source, so the table's room is made here)
-    hconst_.Resize(resize_table_off_ + resize_plans_.size() * sizeof(ResizeArgs));                 // (every entry is written below)
+  if (resize_plans_.empty()) return;
+  resize_table_off_ = st.arena.Put(nullptr, 0);                                                // (an aligned place; Put copies from its source, so the table's room is made here)
+  hconst_.Resize(resize_table_off_ + resize_plans_.size() * sizeof(ResizeArgs));                 // (BuildResizeTable writes every entry)
+}
+
+// The ResizeArgs of every resized output — on every Prepare, from the arenas as they are now (shared planes may have moved) — and resize_groups_: each run of equal
+// slot counts cut into groups of resize_group_max entries.  Needs dconst_, dwork_ and dbig_; reads nothing of PrepareState.
+void Batch::BuildResizeTable() {
+  const uint32_t group_max = std::max(1u, std::min(resize_group_max, kResizeGroupMax));
+  ResizeArgs* table = (ResizeArgs*)(hconst_.data() + resize_table_off_);
+  for (size_t k = 0; k < resize_plans_.size(); k++) {
+    const ResizePlan& rp = resize_plans_[k];
+    const ImageEntry& e = *images_[rp.unit];
+    const OutputSpec& o = e.out;
+    ResizeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = (const float*)(dbig_ + e.off_resize_src); a.tmp = (float*)(dbig_ + e.off_resize_tmp); a.src_stride = (uint64_t)e.src_w * o.num_channels;
+    a.x0 = o.crop_x0; a.y0 = o.crop_y0; a.in_w = o.cropped() ? o.crop_w : e.src_w; a.in_h = o.cropped() ? o.crop_h : e.src_h; a.out_w = o.resize_w; a.out_h = o.resize_h;
+    a.mirror = o.mirror ? 1 : 0;
+    a.ax = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[0]), (const uint32_t*)(dconst_ + rp.tab[1]), (const float*)(dconst_ + rp.tab[2])};
+    a.ay = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[3]), (const uint32_t*)(dconst_ + rp.tab[4]), (const float*)(dconst_ + rp.tab[5])};
+    a.od = FillOutput(e, dwork_, dbig_, /*resize_target=*/true);
+    table[k] = a;
+    const uint32_t slots = ResizeSlots(e);
+    if (resize_groups_.empty() || resize_groups_.back().slots != slots || resize_groups_.back().count >= group_max) resize_groups_.push_back(ResizeGroup{(uint32_t)k, 0, slots, 0, 0, 0});
+    ResizeGroup& g = resize_groups_.back();
+    g.count++; g.max_out_w = std::max(g.max_out_w, a.out_w); g.max_in_h = std::max(g.max_in_h, a.in_h); g.max_out_h = std::max(g.max_out_h, a.out_h);
   }
-  const_size_ = Align(hconst_.size());
-  DevReserve((void**)&dconst_, &const_cap_, const_size_);
-  {
-    const uint32_t group_max = std::max(1u, std::min(resize_group_max, kResizeGroupMax));
-    ResizeArgs* table = (ResizeArgs*)(hconst_.data() + resize_table_off_);
-    for (size_t k = 0; k < resize_plans_.size(); k++) {
-      const ResizePlan& rp = resize_plans_[k];
-      const ImageEntry& e = *images_[rp.unit];
-      const OutputSpec& o = e.out;
-      ResizeArgs a;
-      memset(&a, 0, sizeof(a));
-      a.src = (const float*)(dbig_ + e.off_resize_src); a.tmp = (float*)(dbig_ + e.off_resize_tmp); a.src_stride = (uint64_t)e.src_w * o.num_channels;
-      a.x0 = o.crop_x0; a.y0 = o.crop_y0; a.in_w = o.cropped() ? o.crop_w : e.src_w; a.in_h = o.cropped() ? o.crop_h : e.src_h; a.out_w = o.resize_w; a.out_h = o.resize_h;
-      a.mirror = o.mirror ? 1 : 0;
-      a.ax = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[0]), (const uint32_t*)(dconst_ + rp.tab[1]), (const float*)(dconst_ + rp.tab[2])};
-      a.ay = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[3]), (const uint32_t*)(dconst_ + rp.tab[4]), (const float*)(dconst_ + rp.tab[5])};
-      a.od = FillOutput(e, dwork_, dbig_, /*resize_target=*/true);
-      table[k] = a;
-      const uint32_t slots = resize_slots(rp);
-      if (resize_groups_.empty() || resize_groups_.back().slots != slots || resize_groups_.back().count >= group_max) resize_groups_.push_back(ResizeGroup{(uint32_t)k, 0, slots, 0, 0, 0});
-      ResizeGroup& g = resize_groups_.back();
-      g.count++; g.max_out_w = std::max(g.max_out_w, a.out_w); g.max_in_h = std::max(g.max_in_h, a.in_h); g.max_out_h = std::max(g.max_out_h, a.out_h);
+}
+
+// Every frame's descriptor with the constant arena at its device address, and lf_simt_'s pointers into it.  Reads co, wo, cs_bytes, simt_frame and the plan offsets.
+void Batch::FillFrames(const PrepareState& st) {
+  for (int i = 0; i < st.n; i++) { FillFrameDev(i, dconst_, st); frames_host_[i].lf_simt = lf_simt_.num_lanes ? st.simt_frame[i] : 0; }
+  lf_simt_.units = (const uint2*)(dconst_ + st.place_units_off);
+  if (!lf_simt_.num_lanes) return;
+  lf_simt_.streams = (const LfSimtStream*)(dconst_ + st.simt_streams_off); lf_simt_.lanes = (const LfSimtLane*)(dconst_ + st.simt_lanes_off); lf_simt_.luts = dconst_ + st.simt_luts_off;
+}
+
+// The descriptor arrays travel through the pinned staging buffer, too (a copy from pageable memory is staged by the runtime and holds the calling thread — and
+// others — up for as long as the device is busy): appended behind the constant arena's content, which has been copied out of it before.  Adds them to the arena.
+void Batch::UploadDescriptors(PrepareState& st) {
+  const size_t o_frames = st.arena.Put(frames_host_.data(), sizeof(FrameDev) * (size_t)st.n);
+  const size_t o_passes = st.arena.Put(passes_host_.data(), sizeof(PassDev) * passes_host_.size());
+  const size_t o_local = st.arena.Put(local_host_.data(), sizeof(ModLocalDev) * local_host_.size());
+  HIP_CHECK(hipMemcpyAsync(dframes_, hconst_.data() + o_frames, sizeof(FrameDev) * (size_t)st.n, hipMemcpyHostToDevice, st.stream));
+  HIP_CHECK(hipMemcpyAsync(dpasses_, hconst_.data() + o_passes, sizeof(PassDev) * passes_host_.size(), hipMemcpyHostToDevice, st.stream));
+  HIP_CHECK(hipMemcpyAsync(dlocal_, hconst_.data() + o_local, sizeof(ModLocalDev) * local_host_.size(), hipMemcpyHostToDevice, st.stream));
+}
+
+// LF frames the units refer to: a batch of their own, every LF frame a one-frame image of its own size that ends in its XYB planes (PlanPostOps).  Reads frames_host_.
+void Batch::PrepareLfFrameBatch(void* stream_v, bool wait_upload) {
+  const int n = (int)images_.size();
+  vec<int> users;
+  for (int i = 0; i < n; i++) if (images_[i]->lf_source) users.push_back(i);
+  if (users.empty()) lf_batch_.reset();
+  else {
+    if (!lf_batch_) lf_batch_.reset(new Batch(device_)); else lf_batch_->Reset();
+    lf_batch_->lf_targets_.assign(users.size(), LfTarget());
+    for (size_t k = 0; k < users.size(); k++) {
+      const ImageEntry& user = *images_[users[k]];
+      const ImageEntry& src = *user.lf_source;
+      std::shared_ptr<ImageShared> sh(new ImageShared());
+      sh->cs = src.cs; sh->ih = src.ih;
+      sh->ih.xsize = src.plan.width; sh->ih.ysize = src.plan.height; sh->ih.orientation = 1; sh->ih.intrinsic_x = sh->ih.intrinsic_y = 0; sh->ih.have_preview = false;
+      std::unique_ptr<ImageEntry> e(new ImageEntry(sh));
+      e->plan = src.plan; e->frame_bitpos = src.frame_bitpos; e->frame_index = 0; e->complex = true;
+      e->visible_frame_index = src.visible_frame_index; e->nonvisible_frame_index = src.nonvisible_frame_index;
+      e->lf_source = src.lf_source;                      // (an LF frame may itself sit on the LF frame of the next level)
+      ParsedImage pi; pi.complex = true; pi.units.push_back(std::move(e));
+      lf_batch_->Append(std::move(pi));
+      LfTarget& t = lf_batch_->lf_targets_[k];
+      for (int c = 0; c < 3; c++) t.dst[c] = frames_host_[users[k]].lf[c];
+      t.pitch = user.plan.bw; t.w = user.plan.bw; t.h = user.plan.bh;
     }
+    lf_batch_->cfg.lane_stride_lf = 64;
+    lf_batch_->Prepare(stream_v, wait_upload);
   }
-  HIP_CHECK(hipMemcpyAsync(dconst_, hconst_.data(), hconst_.size(), hipMemcpyHostToDevice, stream));
-  for (int i = 0; i < n; i++) { fill_frame(i, dconst_); frames_host_[i].lf_simt = lf_simt_.num_lanes ? simt_frame[i] : 0; }
-  lf_simt_.units = (const uint2*)(dconst_ + place_units_off);
-  if (lf_simt_.num_lanes) {
-    lf_simt_.streams = (const LfSimtStream*)(dconst_ + simt_streams_off); lf_simt_.lanes = (const LfSimtLane*)(dconst_ + simt_lanes_off); lf_simt_.luts = dconst_ + simt_luts_off;
-  }
-  mark("fill_frames");
-  {
-    // the descriptor arrays travel through the pinned staging buffer, too (a copy from pageable memory is staged by the runtime and holds the calling thread —
-    // and others — up for as long as the device is busy); appended behind the constant arena's content, which has been copied out of it above
-    const size_t o_frames = arena.Put(frames_host_.data(), sizeof(FrameDev) * (size_t)n);
-    const size_t o_passes = arena.Put(passes_host_.data(), sizeof(PassDev) * passes_host_.size());
-    const size_t o_local = arena.Put(local_host_.data(), sizeof(ModLocalDev) * local_host_.size());
-    HIP_CHECK(hipMemcpyAsync(dframes_, hconst_.data() + o_frames, sizeof(FrameDev) * (size_t)n, hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(dpasses_, hconst_.data() + o_passes, sizeof(PassDev) * passes_host_.size(), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(dlocal_, hconst_.data() + o_local, sizeof(ModLocalDev) * local_host_.size(), hipMemcpyHostToDevice, stream));
-  }
-  mark("h2d_enqueue");
-  // (a pipelined caller enqueues the LF stage on the same stream right behind the upload and never waits for it on the host: the pinned staging buffer is not touched
-  // again before the object's next Prepare, which comes after this decode has left the GPU)
-  if (wait_upload) HIP_CHECK(hipStreamSynchronize(stream));
-  mark("upload_wait");
-  if (time_phases) fprintf(stderr, "[jxl-hip] Prepare of %d frames (%.1f MB of tables and streams, %.1f MB work arena), ms:%s\n", n, hconst_.size() / 1e6, work_size_ / 1e6, t_report.c_str());
-  // ---- LF frames the units refer to: a batch of their own, every LF frame a one-frame image of its own size that ends in its XYB planes (PlanPostOps)
-  {
-    vec<int> users;
-    for (int i = 0; i < n; i++) if (images_[i]->lf_source) users.push_back(i);
-    if (users.empty()) lf_batch_.reset();
-    else {
-      if (!lf_batch_) lf_batch_.reset(new Batch(device_)); else lf_batch_->Reset();
-      lf_batch_->lf_targets_.assign(users.size(), LfTarget());
-      for (size_t k = 0; k < users.size(); k++) {
-        const ImageEntry& user = *images_[users[k]];
-        const ImageEntry& src = *user.lf_source;
-        std::shared_ptr<ImageShared> sh(new ImageShared());
-        sh->cs = src.cs; sh->ih = src.ih;
-        sh->ih.xsize = src.plan.width; sh->ih.ysize = src.plan.height; sh->ih.orientation = 1; sh->ih.intrinsic_x = sh->ih.intrinsic_y = 0; sh->ih.have_preview = false;
-        std::unique_ptr<ImageEntry> e(new ImageEntry(sh));
-        e->plan = src.plan; e->frame_bitpos = src.frame_bitpos; e->frame_index = 0; e->complex = true;
-        e->visible_frame_index = src.visible_frame_index; e->nonvisible_frame_index = src.nonvisible_frame_index;
-        e->lf_source = src.lf_source;                      // (an LF frame may itself sit on the LF frame of the next level)
-        ParsedImage pi; pi.complex = true; pi.units.push_back(std::move(e));
-        lf_batch_->Append(std::move(pi));
-        LfTarget& t = lf_batch_->lf_targets_[k];
-        for (int c = 0; c < 3; c++) t.dst[c] = frames_host_[users[k]].lf[c];
-        t.pitch = user.plan.bw; t.w = user.plan.bw; t.h = user.plan.bh;
-      }
-      lf_batch_->cfg.lane_stride_lf = 64;
-      lf_batch_->Prepare(stream_v, wait_upload);
-    }
-  }
+}
+
+// What of cfg follows from partial, progressive and chroma-subsampled frames.  Reads nothing of PrepareState.
+void Batch::FinishCfg() {
+  const int n = (int)images_.size();
   // (a frame cut off inside its AC groups, FramePlan::partial: the HF kernels leave out the group streams that are not completely there; nothing to do when none is)
-  for (int i = 0; i < n; i++) if (images_[i]->plan.partial && images_[i]->plan.partial_ac_sections == 0 && !scaled(i)) cfg.skip_hf = 1;
+  for (int i = 0; i < n; i++) if (images_[i]->plan.partial && images_[i]->plan.partial_ac_sections == 0 && !DecodedAtEighth(i)) cfg.skip_hf = 1;
   if (refuse_partial_unscaled)
-    for (int i = 0; i < n; i++) if (images_[i]->plan.partial && !scaled(i)) throw ParseError("truncated", false);
+    for (int i = 0; i < n; i++) if (images_[i]->plan.partial && !DecodedAtEighth(i)) throw ParseError("truncated", false);
   cfg.any_multipass = any_multipass_ ? 1 : 0;
   if (any_multipass_) cfg.lane_stride_hf = 1;   // progressive frames: only the SIMT HF kernel walks the passes
   if (cfg.any_subsampled) cfg.lane_stride_hf = 1;   // so do chroma-subsampled frames (per-channel block grids)
+}
+
+void Batch::Prepare(void* stream_v, bool wait_upload) {
+  HIP_CHECK(hipSetDevice(device_));
+  InitDeviceTables(stream_v);
+  ResetForPrepare();
+  PrepareState st(hconst_, (int)images_.size(), (hipStream_t)stream_v);
+  PromoteToComplex();
+  PutStreamTables(st);  st.mark("tables1");
+  LayOutWork(st);
+  ReserveArenas(st);  st.mark("layout+reserve");
+  SizeLocalTables();
+  PreRunSingleSection(st);
+  PutHfTables(st);  st.mark("hf_tables");
+  SizeLds();
+  SizePassTables();
+  if (any_complex_) {
+    vec<size_t> upw;
+    for (const ConstOffsets& c : st.co) upw.push_back(c.up_weights);
+    PlanPostOps(hconst_, upw);
+  }
+  st.mark("misc");
+  PlanPlacementUnits(st);
+  PlanLfSimt(st);  st.mark("simt_plan");
+  PlaceResizeTable(st);
+  const_size_ = Align(hconst_.size());      // the constant arena is complete: reserved and uploaded; what follows points into it at its device address
+  DevReserve((void**)&dconst_, &const_cap_, const_size_);
+  BuildResizeTable();
+  HIP_CHECK(hipMemcpyAsync(dconst_, hconst_.data(), hconst_.size(), hipMemcpyHostToDevice, st.stream));
+  FillFrames(st);  st.mark("fill_frames");
+  UploadDescriptors(st);  st.mark("h2d_enqueue");
+  // (a pipelined caller enqueues the LF stage on the same stream right behind the upload and never waits for it on the host: the pinned staging buffer is not touched
+  // again before the object's next Prepare, which comes after this decode has left the GPU)
+  if (wait_upload) HIP_CHECK(hipStreamSynchronize(st.stream));
+  st.mark("upload_wait");
+  if (st.time_phases) fprintf(stderr, "[jxl-hip] Prepare of %d frames (%.1f MB of tables and streams, %.1f MB work arena), ms:%s\n", st.n, hconst_.size() / 1e6, work_size_ / 1e6, st.t_report.c_str());
+  PrepareLfFrameBatch(stream_v, wait_upload);
+  FinishCfg();
   prepared_ = true;
 }
 
@@ -2013,8 +2106,7 @@ void Batch::EnqueueModularTail(void* stream_v) {
 // Builds the list of kernels that undo the global transforms of Modular image i (transform.cc, reverse order) and feed
 // the write stage, tracking the channel list on the host exactly as MetaApply built it; `take` reserves work-arena bytes.
 void Batch::PlanModularUndo(int i, const std::function<size_t(size_t)>& take) {
-  const ImageEntry& e = *images_[i];
-  const FramePlan& p = e.plan;
+  const ImageEntry& e = *images_[i]; const FramePlan& p = e.plan;
   struct HC { size_t off; uint32_t w, h; };
   vec<HC> list;
   for (size_t k = 0; k < p.gchannels.size(); k++) list.push_back({mod_plane_offsets_[i][k], p.gchannels[k].w, p.gchannels[k].h});

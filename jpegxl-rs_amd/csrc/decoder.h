@@ -216,13 +216,29 @@ class Batch {
   uint64_t compressed_bytes() const;
 
  private:
-  void BuildFrameDev(int i, FrameDev* fd, uint8_t* hconst, size_t* const_off, bool measure_only);
-  void UploadFrames(void* stream);
-  void EnqueueVarDCTFront(void* stream);
   int device_;
   vec<std::unique_ptr<ImageEntry>> images_;   // decode units (frames), in image order
   struct PubImage { int first_unit = 0, num_units = 1; bool complex = false; };
   vec<PubImage> pub_;                          // images as the caller counts them
+  // ---- the phases of Prepare, in the order it calls them (decoder.cc); what they share beyond the members is in PrepareState
+  struct PrepareState;
+  void ResetForPrepare(); void PromoteToComplex(); void MarkComplex(PubImage& pi);
+  void PutStreamTables(PrepareState& st);
+  void LayOutWork(PrepareState& st);      // per unit: LayOutVarDct or LayOutModular (both through LayOutModChannels), LayOutComplexBufs
+  void LayOutVarDct(int i, PrepareState& st); void LayOutModular(int i, PrepareState& st); void LayOutModChannels(int i, PrepareState& st); void LayOutComplexBufs(int i, PrepareState& st);
+  void ReserveArenas(PrepareState& st);
+  void SizeLocalTables(); void PreRunSingleSection(PrepareState& st);
+  void PutHfTables(PrepareState& st);
+  void SizeLds(); void SizePassTables();
+  void PlanPlacementUnits(PrepareState& st); void PlanLfSimt(PrepareState& st);
+  void PlaceResizeTable(PrepareState& st); void BuildResizeTable();
+  void FillFrames(const PrepareState& st);     // per unit FillFrameDev: FillFrameCommon, then FillFrameVarDct, then FillFrameModChannels
+  void FillFrameDev(int i, const uint8_t* cbase, const PrepareState& st); void FillFrameCommon(int i, const uint8_t* cbase, const PrepareState& st);
+  void FillFrameVarDct(int i, const uint8_t* cbase, const PrepareState& st); void FillFrameModChannels(int i, const uint8_t* cbase, const PrepareState& st);
+  void UploadDescriptors(PrepareState& st);
+  void PrepareLfFrameBatch(void* stream, bool wait_upload);
+  void FinishCfg();
+  bool DecodedAtEighth(int unit) const;      // the unit is decoded at 1:8 (OutputSpec::downscale == 8): its decode ends behind the LF post-processing
   // ---- frame tail of complex images
   struct ComplexBufs {      // big-arena offsets of one complex unit ((size_t)-1: not allocated)
     size_t up[3], noise[3], rgb[3], canvas[3], pa[3], pb[3];
@@ -299,16 +315,15 @@ class Batch {
   vec<uint32_t> hf_written_;   // per unit: non-zero AC coefficients per decode (from the device counter, read by Finish)
   uint32_t decodes_since_finish_ = 0;
   bool ran_once_ = false;         // a complete decode (incl. the LF stage) has been enqueued since Prepare
-  size_t coeff_off_ = 0, coeff_bytes_ = 0, status_off_ = 0, modplane_off_ = 0, modplane_bytes_ = 0;
+  size_t coeff_bytes_ = 0, status_off_ = 0;
   bool prepared_ = false;
-  int max_lf_groups_ = 0, max_groups_ = 0, max_w_ = 0, max_h_ = 0, max_bw_ = 0, max_bh_ = 0, max_epf_ = 0;
-  bool any_gab_ = false, any_vardct_ = false, any_modular_ = false;
+  int max_lf_groups_ = 0, max_groups_ = 0, max_w_ = 0, max_h_ = 0, max_bw_ = 0, max_bh_ = 0;
+  bool any_vardct_ = false;
   bool any_scaled_ = false, any_full_vardct_ = false;   // some VarDCT frame is decoded at 1:8 / at full size (a batch of 1:8 frames only skips the HF stage, the IDCT and the filters)
   FilterPlan fplan_;
   LaunchTrace trace_;             // the entropy-decode kernels the last LF / HF launch took (Info: hf_variant, lf_variant, lf_wide_bytes, lf_wide_only)
   LfSimtPlan lf_simt_;            // SIMT LF decode: device descriptors of the eligible frames' LF-group streams (cfg.lane_stride_lf < 64)
-  struct ModFinish { int frame; vec<int> planes; };  // host-side channel lists for modular frames
-  vec<vec<size_t>> mod_plane_offsets_;
+  vec<vec<size_t>> mod_plane_offsets_;   // per frame: work-arena offsets of the planes of its Modular channels
   // one kernel launch of the host-planned tail of a Modular image: inverse global transforms, then the write stage
   struct ModOp {
     enum Kind { kRct, kPalette, kSqueeze, kOutput } kind = kRct;
@@ -327,7 +342,7 @@ class Batch {
   void EnqueueModularTail(void* stream);
   void PlanModularUndo(int i, const std::function<size_t(size_t)>& take);
   vec<vec<void*>> timed_events_;
-  size_t timed_rest_cursor_ = 0;       // per frame: work-arena offsets of planes (incl. spare)
+  size_t timed_rest_cursor_ = 0;       // timed decodes run in parts (RunPart): which entry of timed_events_ the next "rest" part records into; CollectTimes starts it over
 };
 
 // device arena pool (decoder.cc): blocks a batch or a pipeline lets go of are kept for the next one that asks for that much memory on that device

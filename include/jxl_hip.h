@@ -228,7 +228,7 @@ int JxlHipDebugWriteJpegSampled(const uint8_t* jbrd, size_t jbrd_size, uint32_t 
    (NUL-terminated, truncated to cap).  0 = accepted, 1 = rejected (JxlHipLastError()). */
 int JxlHipDebugDescribe(const uint8_t* data, size_t size, char* out, size_t cap);
 /* Creates a batch bound to HIP device `device`. */
-JxlHipBatch* JxlHipBatchCreate(int device);
+JxlHipBatch* JxlHipBatchCreate(int device);   /* device -1: a host-only batch (no GPU needed) — images are parsed, outputs set, the host-only queries answered; it cannot be prepared or decoded */
 void JxlHipBatchDestroy(JxlHipBatch* batch);
 /* Parses one image (headers, TOC, global tables) and appends it; returns its index or -1. */
 int JxlHipBatchAddImage(JxlHipBatch* batch, const uint8_t* data, size_t size);
@@ -330,6 +330,25 @@ JxlDecoderStatus JxlHipBatchReconstructJpegs(JxlHipBatch* batch, void* hip_strea
 JxlDecoderStatus JxlHipBatchJpegStatus(const JxlHipBatch* batch, int index);
 size_t JxlHipBatchJpegSize(const JxlHipBatch* batch, int index);
 JxlDecoderStatus JxlHipBatchCopyJpeg(JxlHipBatch* batch, int index, uint8_t* dst, size_t cap);
+/* The samples libjpeg gives for the original file of a JPEG transcode — a second way from the batch to pixels, beside JxlHipBatchDecode, which keeps giving libjxl's
+ * rendering of the frame.  Integer arithmetic throughout: coefficient x quantiser, libjpeg's jpeg_idct_islow, its "fancy" chroma upsampling (replication for chroma planes
+ * at most two samples wide) and its fixed-point YCbCr -> RGB; integer sample k enters the write stage as (float)k x (1 / 255), so every output format, layout, orientation
+ * and the resized / resampled outputs work as for JxlHipBatchDecode (u8 gives k, u16 gives 257 k).  For files that a JPEG encoder wrote from 8-bit samples the u8 output
+ * equals libjpeg's / libjpeg-turbo's default decode sample for sample.
+ * JxlHipBatchCanDecodeJpegPixels (host only): 1 if image `index` is eligible, else 0 with the reason, "unsupported: libjpeg-exact decode of ...", in JxlHipLastError().
+ * Eligible: one VarDCT frame in YCbCr (or of a grey image), not XYB, no extra channels, upsampling 1, one pass, a RAW quantisation table, no gaborish, no EPF, no patches /
+ * splines / noise / crop; luma at full resolution and both chroma channels at 4:4:4, 4:2:2 or 4:2:0; an output at downscale 1.  No `jbrd` box is needed: a transcode
+ * stored without reconstruction data, or as a bare codestream, qualifies.  (The quantisation table of a one-group frame is only known once the batch is prepared:
+ * JxlHipBatchDecodeJpegPixels looks again and fails that image alone.)
+ * JxlHipBatchDecodeJpegPixels runs the LF and HF entropy stages once for all images (it prepares the batch if need be), then the integer pixel path, and writes to the
+ * destinations set with JxlHipBatchSetOutput / ...Layout / ...Resized / ...Resampled; it waits for the result.  An image that is not eligible or whose stream is damaged
+ * fails alone — the call still returns JXL_DEC_SUCCESS; it fails only for what concerns the whole batch (HIP errors, no images, an image that cannot be prepared).
+ * JxlHipBatchJpegPixelsStatus(index): JXL_DEC_SUCCESS, or JXL_DEC_ERROR with that image's reason in JxlHipLastError().  JxlHipBatchDeviceOutput / JxlHipBatchCopyOutput
+ * hand out the pixels as after a decode.  JxlHipBatchGetInfo "jpeg_pixel_images": images the last call wrote; "jpeg_pixel_launches": launches of its two pixel kernels
+ * (two per 32768 images).  A JxlHipBatchDecode or JxlHipBatchReconstructJpegs of the same batch afterwards gives what it gives on a fresh one. */
+int JxlHipBatchCanDecodeJpegPixels(JxlHipBatch* batch, int index);
+JxlDecoderStatus JxlHipBatchDecodeJpegPixels(JxlHipBatch* batch, void* hip_stream);
+JxlDecoderStatus JxlHipBatchJpegPixelsStatus(const JxlHipBatch* batch, int index);
 /* Decode-thread packing: lanes between active entropy-decode threads (64 = one stream per wavefront, 1 = 64 per wavefront). */
 void JxlHipBatchSetLaneStride(JxlHipBatch* batch, int lf, int hf);
 /* Tuning / testing knobs: "force_generic_idct", "hf_block_threads", "lds_code_budget", "debug_stop_after", "lf_wide_once" (the next LF stage of the batch takes the

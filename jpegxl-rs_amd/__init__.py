@@ -189,6 +189,7 @@ def libjxl():
                                                           C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample)]),
             "JxlHipBatchCanReconstructJpeg": (C.c_int, [vp, C.c_int]), "JxlHipBatchReconstructJpegs": (C.c_int, [vp, vp]),
             "JxlHipBatchJpegStatus": (C.c_int, [vp, C.c_int]), "JxlHipBatchJpegSize": (sz, [vp, C.c_int]), "JxlHipBatchCopyJpeg": (C.c_int, [vp, C.c_int, vp, sz]),
+            "JxlHipBatchCanDecodeJpegPixels": (C.c_int, [vp, C.c_int]), "JxlHipBatchDecodeJpegPixels": (C.c_int, [vp, vp]), "JxlHipBatchJpegPixelsStatus": (C.c_int, [vp, C.c_int]),
             "JxlHipBatchSetLaneStride": (None, [vp, C.c_int, C.c_int]), "JxlHipBatchSetOption": (None, [vp, C.c_char_p, C.c_int]),
             "JxlHipBatchPrepare": (C.c_int, [vp, vp]), "JxlHipBatchDecode": (C.c_int, [vp, vp]),
             "JxlHipBatchDecodeTimed": (C.c_int, [vp, vp]), "JxlHipBatchFinish": (C.c_int, [vp, vp]),
@@ -870,6 +871,18 @@ class BatchDecoder:
         out = np.empty(max(n, 1), dtype=np.uint8)
         self._chk(L.JxlHipBatchCopyJpeg(self._h, i, out.ctypes.data, n))
         return out[:n].tobytes()
+
+    # ---- libjpeg-exact pixels of JPEG transcodes (include/jxl_hip.h JxlHipBatchDecodeJpegPixels)
+    def can_decode_jpeg_pixels(self, i) -> bool:
+        """True if decode_jpeg_pixels() takes image i (host only); otherwise last_error() says why not: "unsupported: libjpeg-exact decode of ..."."""
+        return bool(libjxl().JxlHipBatchCanDecodeJpegPixels(self._h, i))
+
+    def decode_jpeg_pixels(self, stream=None) -> list:
+        """The samples libjpeg gives for the original JPEG file of every transcode of the batch (integer IDCT, libjpeg's chroma upsampling and colour conversion), written
+        like a decode(): output(i) / device_output(i) hand them out.  Returns, per image, None or the reason why that image has no pixels (it fails alone)."""
+        L = libjxl()
+        self._chk(L.JxlHipBatchDecodeJpegPixels(self._h, stream))
+        return [None if L.JxlHipBatchJpegPixelsStatus(self._h, i) == JXL_DEC_SUCCESS else last_error() for i in range(self._n)]
 
     def device_output(self, i) -> int:
         return libjxl().JxlHipBatchDeviceOutput(self._h, i)

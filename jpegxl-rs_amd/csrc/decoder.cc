@@ -519,7 +519,7 @@ bool Batch::DevReserve(void** ptr, size_t* cap, size_t bytes) {
 // Forgets the images (and everything derived from them) but keeps the device arenas, the pinned staging buffer and the sharing set up with
 // ShareBigArena / ShareCoefArena: the batch object can be filled again.  The caller makes sure no decode of the old content is in flight.
 void Batch::Reset() {
-  images_.clear(); pub_.clear(); cbufs_.clear(); post_ops_.clear(); jpeg_data_.clear(); resize_plans_.clear(); resize_groups_.clear();
+  images_.clear(); pub_.clear(); cbufs_.clear(); post_ops_.clear(); jpeg_data_.clear(); jpeg_pixel_results_.clear(); resize_plans_.clear(); resize_groups_.clear();
   frames_host_.clear(); passes_host_.clear(); pass_first_.clear(); local_host_.clear(); local_first_.clear();
   mod_plane_offsets_.clear(); mod_ops_.clear(); vardct_alpha_.clear(); hf_written_.clear();
   // (stage timings recorded so far stay: CollectTimes sums over the object's life)
@@ -1021,6 +1021,8 @@ int64_t Batch::Info(const std::string& name) const {
   if (name == "jpeg_device_images") return jpeg_device_images_;     // images of the last ReconstructJpegs whose scans the device wrote / that went through the host writer
   if (name == "jpeg_host_images") return jpeg_host_images_;
   if (name == "jpeg_device_progressive_images") return jpeg_device_progressive_images_;    // ... of the device's, those with at least one progressive scan
+  if (name == "jpeg_pixel_images") return jpeg_pixel_images_;       // images the last DecodeJpegPixels wrote
+  if (name == "jpeg_pixel_launches") return jpeg_pixel_launches_;   // ... launches of its two pixel kernels (two per group of the image table, however many images a group holds)
   if (name == "lf_simt_lanes") return lf_simt_.num_lanes;
   if (name == "lf_simt_wp") return lf_simt_.num_lanes ? lf_simt_.any_wp : 0;     // the SIMT launch is the weighted-predictor instantiation
   // the kernels the last decode's LF / HF stage launched (kernels.h kHfVar* / kLfVar* bits) and the LDS sizes that chose them (bytes, after Prepare)
@@ -2805,15 +2807,24 @@ void Batch::ApplyIdctFlags(const uint32_t* flags) {
 }
 
 // ---- JPEG reconstruction -----------------------------------------------------------------------------------------------------------------
+// What a lossless JPEG transcode looks like as a frame: one VarDCT frame in YCbCr (or of a grey image), not XYB, without extra channels, upsampling, passes or
+// image features.  (The RAW quantisation table belongs to it too, but a one-group frame's is only known after Prepare: the callers look at it then.)
+bool Batch::IsPlainJpegFrame(int i) const {
+  const PubImage& pi = pub_[i];
+  const ImageEntry& e = *images_[pi.first_unit];
+  const FramePlan& p = e.plan;
+  if (pi.num_units != 1 || (pi.complex && !p.subsampled) || p.modular || e.ih.xyb_encoded || !p.do_ycbcr && e.ih.color_space != 1) return false;
+  if (p.upsampling != 1 || p.num_passes != 1 || !e.ih.extra.empty()) return false;
+  if (p.subsampled && ((p.flags & (1 | 2 | 16)) || p.have_crop || p.frame_type != 0)) return false;
+  return true;
+}
+
 bool Batch::CanReconstructJpeg(int i, std::string* why) {
   auto no = [&](const char* m) { if (why) *why = m; return false; };
   const PubImage& pi = pub_[i];
   const ImageEntry& e = *images_[pi.first_unit];
   if (e.shared->boxes.jbrd.empty()) return no("no jbrd box");
-  const FramePlan& p = e.plan;
-  if (pi.num_units != 1 || (pi.complex && !p.subsampled) || p.modular || e.ih.xyb_encoded || !p.do_ycbcr && e.ih.color_space != 1) return no("not a plain JPEG-transcoded frame");
-  if (p.upsampling != 1 || p.num_passes != 1 || !e.ih.extra.empty()) return no("not a plain JPEG-transcoded frame");
-  if (p.subsampled && ((p.flags & (1 | 2 | 16)) || p.have_crop || p.frame_type != 0)) return no("not a plain JPEG-transcoded frame");
+  if (!IsPlainJpegFrame(i)) return no("not a plain JPEG-transcoded frame");
   if (jpeg_data_.size() < pub_.size()) jpeg_data_.resize(pub_.size());
   if (!jpeg_data_[i]) {
     std::unique_ptr<JpegData> jd(new JpegData());
@@ -2895,36 +2906,67 @@ vec<uint8_t> Batch::ReconstructJpeg(int i, void* stream_v) {
 }
 
 // ---- batch JPEG reconstruction: one entropy run for all images, sequential scans written by the device (jpeg_write.hip) ---------------------
+// What the frame of a JPEG transcode says about the JPEG (as ReconstructJpeg documents it): quantisation tables in JPEG's natural order, sampling factors and, for the
+// coefficient arena, the component planes packed one after another — component c (0 Y, 1 Cb, 2 Cr = channels 1, 0, 2) is a grid of grid_w x grid_h blocks from block
+// comp_first[c] on.  hs / vs: the component's shifts against the frame's block grid.
+struct JpegFrameGrid {
+  uint32_t ncomp = 0;
+  int32_t qt[3][64];
+  uint32_t h_samp[3] = {1, 1, 1}, v_samp[3] = {1, 1, 1}, hs[3] = {0, 0, 0}, vs[3] = {0, 0, 0}, grid_w[3] = {0, 0, 0}, grid_h[3] = {0, 0, 0};
+  size_t comp_first[3] = {0, 0, 0}, nblk = 0;
+};
 namespace {
-// quantisation tables and sampling factors of the JPEG from the frame (as ReconstructJpeg documents them); component planes packed one after another
-bool FillJpegFromFrame(const FramePlan& p, JpegData* jd, size_t comp_first[3], size_t* nblk, std::string* why) {
+// `what`: whose error it is ("JPEG reconstruction")
+bool JpegGridFromFrame(const FramePlan& p, size_t ncomp, const char* what, JpegFrameGrid* g, std::string* why) {
   const QuantTableSpec& q = p.qspec[0];
-  if (q.mode != 7) { *why = "JPEG reconstruction: quantisation table is not a RAW (JPEG) table"; return false; }
-  const size_t ncomp = jd->components.size();
+  if (q.mode != 7) { *why = std::string(what) + ": quantisation table is not a RAW (JPEG) table"; return false; }
   int max_hs = 0, max_vs = 0;
   for (int c = 0; c < 3; c++) { max_hs = std::max(max_hs, (int)p.hs[c]); max_vs = std::max(max_vs, (int)p.vs[c]); }
-  *nblk = 0;
+  g->ncomp = (uint32_t)ncomp; g->nblk = 0;
   for (size_t c = 0; c < ncomp; c++) {
     const int ch = ncomp == 1 ? 1 : (c == 0 ? 1 : c == 1 ? 0 : 2);
-    if (q.raw[ch].size() != 64) { *why = "JPEG reconstruction: RAW table size"; return false; }
+    if (q.raw[ch].size() != 64) { *why = std::string(what) + ": RAW table size"; return false; }
+    for (int v = 0; v < 8; v++) for (int u = 0; u < 8; u++) g->qt[c][v * 8 + u] = q.raw[ch][u * 8 + v];      // (libjxl's coefficient layout is the transpose of JPEG's)
+    g->hs[c] = p.hs[ch]; g->vs[c] = p.vs[ch];
+    g->h_samp[c] = 1u << (max_hs - p.hs[ch]); g->v_samp[c] = 1u << (max_vs - p.vs[ch]);
+    g->grid_w[c] = p.bw >> p.hs[ch]; g->grid_h[c] = p.bh >> p.vs[ch];
+    g->comp_first[c] = g->nblk;
+    g->nblk += (size_t)g->grid_w[c] * g->grid_h[c];
+  }
+  return true;
+}
+// ... into the JPEG's own description (reconstruction: the component count is the jbrd box's)
+bool FillJpegFromFrame(const FramePlan& p, JpegData* jd, JpegFrameGrid* g, std::string* why) {
+  if (!JpegGridFromFrame(p, jd->components.size(), "JPEG reconstruction", g, why)) return false;
+  for (size_t c = 0; c < jd->components.size(); c++) {
     JpegQuantTable& t = jd->quant[jd->components[c].quant_idx];
-    for (int v = 0; v < 8; v++) for (int u = 0; u < 8; u++) t.values[v * 8 + u] = q.raw[ch][u * 8 + v];
-    jd->components[c].h_samp = 1u << (max_hs - p.hs[ch]);
-    jd->components[c].v_samp = 1u << (max_vs - p.vs[ch]);
-    comp_first[c] = *nblk;
-    *nblk += (size_t)(p.bw >> p.hs[ch]) * (p.bh >> p.vs[ch]);
+    for (int k = 0; k < 64; k++) t.values[k] = g->qt[c][k];
+    jd->components[c].h_samp = g->h_samp[c]; jd->components[c].v_samp = g->v_samp[c];
   }
   return true;
 }
 struct ScanPlan { JpegHuffTable dc[4], ac[4]; uint32_t restart = 0; bool progressive = false; };
 }  // namespace
 
+// image i's quantised coefficients into JPEG layout (JpegCoefKernel): component planes one after another from `out` on
+void Batch::EnqueueJpegCoefficients(int i, const JpegFrameGrid& g, int16_t* out, void* stream_v) {
+  const int u = pub_[i].first_unit;
+  const FramePlan& p = images_[u]->plan;
+  JpegCoefArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ncomp = g.ncomp;
+  for (uint32_t c = 0; c < g.ncomp; c++) a.comp_off[c] = (uint32_t)g.comp_first[c];
+  for (uint32_t c = 0; c < g.ncomp; c++) for (int k = 0; k < 64; k++) a.qt[c][k] = g.qt[c][k];
+  a.out = out;
+  LaunchJpegCoefficients(dframes_, u, a, p.bw, p.bh, stream_v);
+}
+
 void Batch::ReconstructJpegs(void* stream_v) {
   hipStream_t stream = (hipStream_t)stream_v;
   const int n = (int)pub_.size();
   jpeg_results_.clear(); jpeg_results_.resize((size_t)n);
   jpeg_device_images_ = jpeg_host_images_ = jpeg_device_progressive_images_ = 0;
-  struct Img { bool ok = false, device = false, progressive = false; size_t first_blk = 0, nblk = 0, comp_first[3] = {0, 0, 0}; size_t first_scan = 0, num_scans = 0; std::vector<ScanPlan> plans; };
+  struct Img { bool ok = false, device = false, progressive = false; size_t first_blk = 0; JpegFrameGrid grid; size_t first_scan = 0, num_scans = 0; std::vector<ScanPlan> plans; };
   std::vector<Img> im((size_t)n);
   bool any = false;
   for (int i = 0; i < n; i++) {
@@ -2947,8 +2989,10 @@ void Batch::ReconstructJpegs(void* stream_v) {
     const ImageEntry& e = *images_[pub_[i].first_unit];
     JpegData& jd = *jpeg_data_[i];
     std::string why;
-    if (!FillJpegFromFrame(e.plan, &jd, m.comp_first, &m.nblk, &why)) { m.ok = false; jpeg_results_[i].error = why; continue; }
-    m.first_blk = total_blk; total_blk += m.nblk;
+    if (!FillJpegFromFrame(e.plan, &jd, &m.grid, &why)) { m.ok = false; jpeg_results_[i].error = why; continue; }
+    // (the tables as the file's components refer to them: components that share a table slot share the table)
+    for (size_t c = 0; c < jd.components.size(); c++) for (int k = 0; k < 64; k++) m.grid.qt[c][k] = jd.quant[jd.components[c].quant_idx].values[k];
+    m.first_blk = total_blk; total_blk += m.grid.nblk;
     if (jpeg_host_writer) continue;
     // the marker walk with an emitter that writes nothing: the scans, the tables in force at each
     vec<uint8_t> scratch;
@@ -2987,7 +3031,7 @@ void Batch::ReconstructJpegs(void* stream_v) {
         const JpegComponentInfo& comp = jd.components[sc.comp_idx];
         if ((needs_dc && !cx.dc_tab[sc.dc_tbl_idx & 3].init) || (needs_ac && !cx.ac_tab[sc.ac_tbl_idx & 3].init)) eligible = false;   // (the host writer names the error)
         d.h[k] = (uint8_t)(s.num_components > 1 ? comp.h_samp : 1); d.v[k] = (uint8_t)(s.num_components > 1 ? comp.v_samp : 1);
-        d.plane[k] = (uint32_t)(m.first_blk + m.comp_first[sc.comp_idx]); d.pitch[k] = cx.mcu_cols * comp.h_samp;
+        d.plane[k] = (uint32_t)(m.first_blk + m.grid.comp_first[sc.comp_idx]); d.pitch[k] = cx.mcu_cols * comp.h_samp;
         d.dc[k] = (uint16_t)(sc.dc_tbl_idx & 3); d.ac[k] = (uint16_t)(4 + (sc.ac_tbl_idx & 3));       // (slots of this scan's snapshot: rebased below)
         d.blocks_per_mcu += (uint32_t)d.h[k] * d.v[k];
       }
@@ -3053,16 +3097,7 @@ void Batch::ReconstructJpegs(void* stream_v) {
   RunPart(stream_v, 3, false);
   for (int i = 0; i < n; i++) {
     if (!im[i].ok) continue;
-    const int u = pub_[i].first_unit;
-    const FramePlan& p = images_[u]->plan;
-    const JpegData& jd = *jpeg_data_[i];
-    JpegCoefArgs a;
-    memset(&a, 0, sizeof(a));
-    a.ncomp = (uint32_t)jd.components.size();
-    for (size_t c = 0; c < jd.components.size(); c++) a.comp_off[c] = (uint32_t)im[i].comp_first[c];
-    for (size_t c = 0; c < jd.components.size(); c++) for (int k = 0; k < 64; k++) a.qt[c][k] = jd.quant[jd.components[c].quant_idx].values[k];
-    a.out = (int16_t*)(djpeg_ + o_coef) + im[i].first_blk * 64;
-    LaunchJpegCoefficients(dframes_, u, a, p.bw, p.bh, stream_v);
+    EnqueueJpegCoefficients(i, im[i].grid, (int16_t*)(djpeg_ + o_coef) + im[i].first_blk * 64, stream_v);
   }
   DebugSync("JPEG coefficients", stream_v);
   JpegWritePlan wp;
@@ -3134,10 +3169,127 @@ void Batch::ReconstructJpegs(void* stream_v) {
     }
     // host writer: progressive files (without "jpeg_device_progressive"), extra zero runs, "jpeg_host_writer" — and images the device flagged: the host writer
     // names their error, or writes the span whose correction bits it flushes on its own
-    vec<int16_t> host(m.nblk * 64);
+    vec<int16_t> host(m.grid.nblk * 64);
     HIP_CHECK(hipMemcpy(host.data(), (const int16_t*)(djpeg_ + o_coef) + m.first_blk * 64, host.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
-    const int16_t* planes[3] = {host.data(), host.data() + m.comp_first[1] * 64, host.data() + m.comp_first[2] * 64};
+    const int16_t* planes[3] = {host.data(), host.data() + m.grid.comp_first[1] * 64, host.data() + m.grid.comp_first[2] * 64};
     if (WriteJpeg(jd, e.ih.xsize, e.ih.ysize, planes, &r.bytes, &why)) { r.ok = true; jpeg_host_images_++; } else { r.bytes.clear(); r.error = why; }
+  }
+}
+
+// ---- libjpeg-exact pixels of JPEG transcodes: the entropy run of ReconstructJpegs, then integer IDCT, libjpeg's chroma upsampling and colour conversion (jpeg_pixels.hip)
+namespace {
+// what of a frame's RAW table and sampling the pixel path takes ("" = all of it); only meaningful once HfGlobal has been parsed
+std::string JpegPixelTableRefusal(const FramePlan& p) {
+  const QuantTableSpec& q = p.qspec[0];
+  if (q.mode != 7 || q.raw[0].size() != 64 || q.raw[1].size() != 64 || q.raw[2].size() != 64) return "a frame without a RAW (JPEG) quantisation table";
+  return std::string();
+}
+}  // namespace
+
+bool Batch::CanDecodeJpegPixels(int i, std::string* why) const {
+  auto no = [&](const std::string& m) { if (why) *why = "unsupported: libjpeg-exact decode of " + m; return false; };
+  const ImageEntry& e = *images_[pub_[i].first_unit];
+  const FramePlan& p = e.plan;
+  if (!IsPlainJpegFrame(i)) return no("an image that is not a plain JPEG-transcoded frame");
+  if (pub_[i].complex || p.have_crop || p.frame_type != 0 || (p.flags & (1 | 2 | 16))) return no("a frame with patches, splines, noise, a crop or blending");
+  if (p.use_lf_frame || e.lf_source) return no("a frame that takes its LF image from an LF frame");
+  if (p.lf.gab || p.lf.epf_iters) return no("a frame with restoration filters");
+  // Y at full resolution, both chroma channels with the same shifts: 4:4:4, 4:2:2, 4:2:0 (4:4:0 and the rest: libjpeg has rules for them that no test here could pin)
+  if (p.hs[1] || p.vs[1] || p.hs[0] != p.hs[2] || p.vs[0] != p.vs[2] || p.hs[0] > 1 || p.vs[0] > 1 || (p.vs[0] && !p.hs[0]))
+    return no("chroma sampling other than 4:4:4, 4:2:2 and 4:2:0");
+  if (e.out.downscale != 1) return no("an output with downscale 8 (libjpeg's scaled IDCTs are other arithmetic)");
+  if (e.ih.xsize > 65535 || e.ih.ysize > 65535) return no("an image larger than a JPEG file can be");
+  if (!(p.single_section && p.ac_code.empty())) {      // (HfGlobal of a one-group frame is parsed by Prepare)
+    const std::string t = JpegPixelTableRefusal(p);
+    if (!t.empty()) return no(t);
+  }
+  return true;
+}
+
+void Batch::DecodeJpegPixels(void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  const int n = (int)pub_.size();
+  jpeg_pixel_results_.clear(); jpeg_pixel_results_.resize((size_t)n);
+  jpeg_pixel_images_ = jpeg_pixel_launches_ = 0;
+  if (!n) throw ParseError("DecodeJpegPixels: the batch holds no image", false);
+  struct Img { bool ok = false; size_t first_blk = 0; JpegFrameGrid grid; };
+  std::vector<Img> im((size_t)n);
+  bool any = false;
+  for (int i = 0; i < n; i++) {
+    std::string why;
+    if (CanDecodeJpegPixels(i, &why)) { im[i].ok = true; any = true; } else jpeg_pixel_results_[i].error = why;
+  }
+  if (!any) return;
+  if (!prepared_) Prepare(stream_v);
+  HIP_CHECK(hipSetDevice(device_));
+  // ---- host plan: the coefficient planes of every image in one arena, laid out as ReconstructJpegs lays them out, and the image table behind them
+  size_t total_blk = 0;
+  vec<JpegPixelImage> table;
+  vec<int> table_image;
+  for (int i = 0; i < n; i++) {
+    Img& m = im[i];
+    if (!m.ok) continue;
+    const int u = pub_[i].first_unit;
+    const ImageEntry& e = *images_[u];
+    const FramePlan& p = e.plan;
+    std::string why = JpegPixelTableRefusal(p);
+    if (!why.empty()) { m.ok = false; jpeg_pixel_results_[i].error = "unsupported: libjpeg-exact decode of " + why; continue; }
+    const uint32_t ncomp = e.ih.color_space == 1 ? 1 : 3;
+    if (!JpegGridFromFrame(p, ncomp, "libjpeg-exact decode", &m.grid, &why)) { m.ok = false; jpeg_pixel_results_[i].error = why; continue; }
+    const JpegFrameGrid& g = m.grid;
+    const FrameDev& f = frames_host_[u];
+    // every address of the two kernels follows from this entry: the component grids must hold the components' real extents, the planes they are written to must exist
+    bool fits = g.nblk < ((size_t)1 << 31) && f.plane_a[0] && f.plane_a[1] && f.plane_a[2] && !f.lf_only;
+    for (uint32_t c = 0; c < ncomp && fits; c++) {
+      const uint32_t cw = (e.ih.xsize + (1u << g.hs[c]) - 1) >> g.hs[c], ch = (e.ih.ysize + (1u << g.vs[c]) - 1) >> g.vs[c];
+      fits = g.grid_w[c] && g.grid_h[c] && (uint64_t)g.grid_w[c] * 8 >= cw && (uint64_t)g.grid_h[c] * 8 >= ch && g.grid_w[c] <= p.bw && g.grid_h[c] <= p.bh;
+    }
+    if (!fits) { m.ok = false; jpeg_pixel_results_[i].error = "unsupported: libjpeg-exact decode of a frame whose block grid does not hold the image"; continue; }
+    m.first_blk = total_blk; total_blk += g.nblk;
+    JpegPixelImage t;
+    memset(&t, 0, sizeof(t));
+    for (uint32_t c = 0; c < ncomp; c++) {
+      t.plane[c] = (uint8_t*)f.plane_a[ncomp == 1 ? 1 : (c == 0 ? 1 : c == 1 ? 0 : 2)];     // (the frame's own pixel planes, which this decode does not use otherwise: bw x bh x 64 floats each)
+      t.comp_first[c] = (uint32_t)g.comp_first[c]; t.grid_w[c] = g.grid_w[c];
+      for (int k = 0; k < 64; k++) t.qt[c][k] = g.qt[c][k];
+    }
+    t.nblk = (uint32_t)g.nblk; t.ncomp = ncomp; t.frame = (uint32_t)u;
+    t.width = e.ih.xsize; t.height = e.ih.ysize; t.hs = ncomp == 3 ? g.hs[1] : 0; t.vs = ncomp == 3 ? g.vs[1] : 0;
+    table.push_back(t); table_image.push_back(i);
+  }
+  if (table.empty()) return;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  const size_t o_coef = take(total_blk * 128), o_table = take(table.size() * sizeof(JpegPixelImage));
+  DevReserve((void**)&djpeg_, &jpeg_cap_, std::max<size_t>(off, 256));
+  for (size_t k = 0; k < table.size(); k++) table[k].coef = (const int16_t*)(djpeg_ + o_coef) + im[table_image[k]].first_blk * 64;
+  HIP_CHECK(hipMemcpyAsync(djpeg_ + o_table, table.data(), table.size() * sizeof(JpegPixelImage), hipMemcpyHostToDevice, stream));
+  // ---- one entropy decode of the batch (LF stage: JPEG DC, block metadata; HF stage: AC), coefficients into JPEG layout
+  RunPart(stream_v, 1, false);
+  RunPart(stream_v, 3, false);
+  for (size_t k = 0; k < table.size(); k++) EnqueueJpegCoefficients(table_image[k], im[table_image[k]].grid, (int16_t*)table[k].coef, stream_v);
+  DebugSync("JPEG coefficients", stream_v);
+  // ---- the pixel half: one launch per kernel and group of the table, then the resizes of resized outputs over the f32 pictures the write stage left
+  const JpegPixelImage* dtable = (const JpegPixelImage*)(djpeg_ + o_table);
+  for (size_t first = 0; first < table.size(); first += kJpegPixelGroupMax) {
+    JpegPixelGroup g{(uint32_t)first, (uint32_t)std::min<size_t>(kJpegPixelGroupMax, table.size() - first), 0, 0, 0};
+    for (uint32_t k = 0; k < g.count; k++) {
+      const JpegPixelImage& t = table[first + k];
+      g.max_nblk = std::max(g.max_nblk, t.nblk); g.max_w = std::max(g.max_w, t.width); g.max_h = std::max(g.max_h, t.height);
+    }
+    LaunchJpegPixelGroup(dframes_, dtable, g, stream_v);
+    jpeg_pixel_launches_ += 2;
+  }
+  EnqueueResizes(stream_v);
+  DebugSync("JPEG pixels", stream_v);
+  CheckLaunches("JPEG pixels");
+  vec<uint32_t> status;
+  FinishStatus(stream_v, &status);
+  for (size_t k = 0; k < table.size(); k++) {
+    const int i = table_image[k];
+    JpegPixelResult& r = jpeg_pixel_results_[i];
+    if (const uint32_t st = status[pub_[i].first_unit]) { bool unsupported; r.error = DeviceStatusMessage(st, pub_[i].first_unit, &unsupported); continue; }
+    r.ok = true; jpeg_pixel_images_++;
   }
 }
 

@@ -99,6 +99,8 @@ class HostStage {
 // `dirty` / `clean_extent` are the coefficient planes' bookkeeping (see Batch::ClearCoefficientsBeforeHf); the owner serialises the decodes that share one set.
 struct SharedPlanes { uint8_t* p = nullptr; size_t cap = 0; bool dirty = true; size_t clean_extent = 0; };
 
+struct JpegFrameGrid;      // quantisation tables, sampling factors and component grids of a JPEG-transcoded frame (decoder.cc)
+
 struct StageTimes { float lf_ms = 0, lfpost_ms = 0, hf_ms = 0, idct_ms = 0, filter_ms = 0, out_ms = 0, total_ms = 0; };
 
 class Batch {
@@ -171,6 +173,16 @@ class Batch {
   bool jpeg_device_progressive = false;
   uint32_t resize_group_max = kResizeGroupMax;   // testing: images per resize launch (1 .. kResizeGroupMax)
   const JpegResult* jpeg_result(int i) const { return i >= 0 && (size_t)i < jpeg_results_.size() ? &jpeg_results_[(size_t)i] : nullptr; }
+  // The samples libjpeg gives for the original file of a JPEG transcode, instead of libjxl's rendering of the frame (Run): integer dequantisation and IDCT, libjpeg's
+  // "fancy" chroma upsampling and fixed-point YCbCr -> RGB (jpeg_pixels.hip), written through the write stage to the outputs set with SetOutput.  Takes the frame
+  // conditions of CanReconstructJpeg without those on the `jbrd` box, 4:4:4 / 4:2:2 / 4:2:0 or grey, at downscale 1; CanDecodeJpegPixels is host-only and says
+  // "unsupported: libjpeg-exact decode of ..." otherwise (the quantisation table of a one-group frame is only known after Prepare: DecodeJpegPixels looks again).
+  // DecodeJpegPixels runs the entropy stages once for the whole batch; an image that is not eligible, or whose stream is damaged, fails alone: jpeg_pixel_result(i).
+  // Throws only for what concerns the whole batch (HIP errors, no prepared images).
+  struct JpegPixelResult { bool ok = false; std::string error; };
+  bool CanDecodeJpegPixels(int i, std::string* why = nullptr) const;
+  void DecodeJpegPixels(void* stream);
+  const JpegPixelResult* jpeg_pixel_result(int i) const { return i >= 0 && (size_t)i < jpeg_pixel_results_.size() ? &jpeg_pixel_results_[(size_t)i] : nullptr; }
   void FinishStatus(void* stream, vec<uint32_t>* per_unit);
   // Copies frame i's pixels to host memory (after Finish).
   void CopyOutputToHost(int i, void* dst, size_t size, void* stream);
@@ -257,6 +269,10 @@ class Batch {
   vec<LfTarget> lf_targets_;                   // (of the batch that decodes LF frames: per image, where its planes go)
   vec<std::unique_ptr<JpegData>> jpeg_data_;   // per image, parsed lazily by CanReconstructJpeg
   std::vector<JpegResult> jpeg_results_;       // per image, of the last ReconstructJpegs
+  std::vector<JpegPixelResult> jpeg_pixel_results_;   // per image, of the last DecodeJpegPixels
+  int64_t jpeg_pixel_images_ = 0, jpeg_pixel_launches_ = 0;   // images the last DecodeJpegPixels wrote; launches of its two pixel kernels (two per group of the image table)
+  bool IsPlainJpegFrame(int i) const;          // the frame conditions CanReconstructJpeg and CanDecodeJpegPixels share
+  void EnqueueJpegCoefficients(int i, const JpegFrameGrid& g, int16_t* out, void* stream);   // JpegCoefKernel: image i's coefficients into JPEG layout at `out`
   int jpeg_device_images_ = 0, jpeg_host_images_ = 0, jpeg_device_progressive_images_ = 0;
   uint8_t* djpeg_ = nullptr; size_t jpeg_cap_ = 0;           // ReconstructJpegs: coefficient planes in JPEG layout, scan table, per-block / per-segment arrays
   uint8_t* djpeg_out_ = nullptr; size_t jpeg_out_cap_ = 0;   // ... raw and stuffed segment bytes, segment records

@@ -892,7 +892,8 @@ struct JxlHipBatchStruct { Batch* b; bool keep_orientation = false; bool allow_p
 JxlHipBatch* JxlHipBatchCreate(int device) {
   try {
     int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device >= count) { SetLastError("no usable HIP device (no CPU fallback exists)"); return nullptr; }
+    // (device -1: a host-only batch — images are parsed, outputs set and the host-only queries answered; it cannot be prepared or decoded)
+    if (device != -1 && (hipGetDeviceCount(&count) != hipSuccess || device >= count)) { SetLastError("no usable HIP device (no CPU fallback exists)"); return nullptr; }
     JxlHipBatch* h = new JxlHipBatchStruct();
     h->b = new Batch(device);
     h->b->refuse_partial_unscaled = true;     // ("allow_partial" lets streams in that end behind their LF part: good for 1:8 decodes only)
@@ -1072,6 +1073,24 @@ JxlDecoderStatus JxlHipBatchCopyJpeg(JxlHipBatch* h, int i, uint8_t* dst, size_t
   if (!dst || cap < r->bytes.size()) { SetLastError("JxlHipBatchCopyJpeg: the buffer is smaller than JxlHipBatchJpegSize"); return JXL_DEC_ERROR; }
   if (!r->bytes.empty()) memcpy(dst, r->bytes.data(), r->bytes.size());
   return JXL_DEC_SUCCESS;
+}
+// ---- libjpeg-exact pixels of the batch's JPEG transcodes (decoder.cc Batch::DecodeJpegPixels)
+int JxlHipBatchCanDecodeJpegPixels(JxlHipBatch* h, int i) {
+  try {
+    if (i < 0 || (size_t)i >= h->b->size()) { SetLastError("JxlHipBatchCanDecodeJpegPixels: no such image"); return 0; }
+    std::string why;
+    if (h->b->CanDecodeJpegPixels(i, &why)) return 1;
+    SetLastError(why);
+    return 0;
+  } catch (const std::exception& e) { SetLastError(e.what()); return 0; }
+}
+JxlDecoderStatus JxlHipBatchDecodeJpegPixels(JxlHipBatch* h, void* s) { BATCH_TRY(h->b->DecodeJpegPixels(s)) }
+JxlDecoderStatus JxlHipBatchJpegPixelsStatus(const JxlHipBatch* h, int i) {
+  const Batch::JpegPixelResult* r = h->b->jpeg_pixel_result(i);
+  if (!r) { SetLastError("JxlHipBatchJpegPixelsStatus: no such image, or JxlHipBatchDecodeJpegPixels has not run"); return JXL_DEC_ERROR; }
+  if (r->ok) return JXL_DEC_SUCCESS;
+  SetLastError(r->error);
+  return JXL_DEC_ERROR;
 }
 uint64_t JxlHipBatchTotalPixels(const JxlHipBatch* h) { return h->b->total_pixels(); }
 uint64_t JxlHipBatchCompressedBytes(const JxlHipBatch* h) { return h->b->compressed_bytes(); }

@@ -361,6 +361,22 @@ struct JpegPackBuffers {
 void LaunchJpegSizes(const JpegWritePlan& p, void* stream);
 void LaunchJpegPack(const JpegWritePlan& p, const JpegPackBuffers& o, void* stream);
 uint32_t JpegStuffChunkBytes();
+// ---- libjpeg-exact pixels of JPEG transcodes (jpeg_pixels.hip; decoder.cc Batch::DecodeJpegPixels).  One JpegPixelImage per image that takes the path, in a device
+// table; both kernels run over a group of the table with the image on blockIdx.z.  coef: the image's quantised coefficients as JpegCoefKernel leaves them (components
+// one after another, block raster order of the padded grid, natural order); qt: the JPEG quantisation tables, natural order.  plane[c]: u8 samples of component c
+// (0 Y, 1 Cb, 2 Cr) after the integer IDCT, grid_w[c] x 8 bytes per row, the whole padded grid.  hs / vs: the chroma components' shifts against luma (0 / 1).
+struct JpegPixelImage {
+  const int16_t* coef;
+  uint8_t* plane[3];
+  uint32_t comp_first[3], grid_w[3];     // first block of component c among the image's blocks; blocks per row of its grid
+  uint32_t nblk, ncomp;
+  uint32_t frame;                        // FrameDev of the image: status word, block info, OutputDesc
+  uint32_t width, height, hs, vs;
+  int32_t qt[3][64];
+};
+constexpr uint32_t kJpegPixelGroupMax = 32768;       // images per launch (gridDim.z is limited to 65535)
+struct JpegPixelGroup { uint32_t first, count, max_nblk, max_w, max_h; };      // a run of the table served by one launch per kernel, the grids sized for its largest image
+void LaunchJpegPixelGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);   // JpegIdctKernel, then JpegColorOutKernel
 void LaunchCopyPlane(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t w, uint32_t h, void* stream);
 // ---- resized output (OutputSpec::resize_w / resize_h): separable antialiased filter (triangle or cubic convolution), horizontal pass then vertical, f32 throughout.
 // One axis' filter as the host built it (decoder.cc ResizeAxis): output index i takes the taps first[i] .. first[i + 1] - 1 of `weight` (normalised, double rounded once to f32)

@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""Milliseconds per batch and Mpixel/s of the three ways from a batch of JPEG transcodes to the pixels of the original JPEG files.
+
+Input: --files baseline 4:2:0 JPEGs of --width x --height, written at run time by Pillow from tests/jpeg_cases.photo (--distinct different pictures, cycled) and
+turned into JPEG XL by tests/jpeg_tools.transcode.  Output of the two device legs: u8 RGB in device memory (one caller-owned buffer per image).  Legs (--legs):
+
+  pixels       BatchDecoder.decode_jpeg_pixels() of a prepared batch: the entropy stages, then the integer pixel path (csrc/jpeg_pixels.hip); the call waits for the result
+  decode       decode() + finish() of the same prepared batch: libjxl's rendering through the float VarDCT pipeline — the pixel path these files had before
+               decode_jpeg_pixels existed.  It runs nothing of the new interface: with PYTHONPATH pointing at a build of an earlier commit the same script measures that build
+  reconstruct  what a user needs without the new call to get libjpeg's samples: reconstruct_jpegs(), the files fetched to the host, Pillow decoding them on --threads
+               host threads (reported whole and in its two parts)
+
+Every leg runs --reps times after --warmup; the median is reported.  The first run of a leg is checked: pixels and reconstruct equal Pillow's decode of the source
+file exactly, decode is reported with its largest difference from it.  Prints one JSON line.
+--cache DIR keeps the input files and their transcodes (the parser of tests/jpeg_tools.py is plain Python and slow on large files) for the next run; --legs "" only fills it."""
+import argparse
+import io
+import json
+import os
+import pickle
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.append(ROOT)                     # (behind PYTHONPATH: another build of the package may be measured with this script)
+sys.path.append(os.path.join(ROOT, "tests"))
+
+
+def median(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=64)
+    ap.add_argument("--distinct", type=int, default=2)
+    ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--quality", type=int, default=90)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--legs", default="pixels,decode,reconstruct")
+    ap.add_argument("--cache", default=None)
+    args = ap.parse_args()
+    import numpy as np
+    from PIL import Image
+    import jpeg_cases as JC
+    import jpeg_tools as J
+    cached = args.cache and os.path.join(args.cache, "jpeg_pixels_%dx%d_q%d_n%d.pickle" % (args.width, args.height, args.quality, args.distinct))
+    if cached and os.path.exists(cached):
+        with open(cached, "rb") as f:
+            jpegs, jxls = pickle.load(f)
+    else:
+        jpegs = []
+        for k in range(args.distinct):
+            buf = io.BytesIO()
+            Image.fromarray(JC.photo(args.width, args.height, seed=100 + k)).save(buf, "JPEG", quality=args.quality, subsampling=2)
+            jpegs.append(buf.getvalue())
+        jxls = [J.transcode(d) for d in jpegs]
+        if cached:
+            os.makedirs(args.cache, exist_ok=True)
+            with open(cached, "wb") as f:
+                pickle.dump((jpegs, jxls), f)
+    legs = [leg for leg in args.legs.split(",") if leg]
+    if not legs:
+        return
+    import torch
+    import jpegxl_rs_amd as jx
+    files = [jpegs[k % args.distinct] for k in range(args.files)]
+    inputs = [jxls[k % args.distinct] for k in range(args.files)]
+    w, h = args.width, args.height
+    mpix = args.files * w * h / 1e6
+    want = [np.asarray(Image.open(io.BytesIO(d))) for d in jpegs]
+    out = {"what": "pixels of JPEG transcodes, u8 RGB", "files": args.files, "distinct": args.distinct, "size": [w, h], "quality": args.quality, "megapixels": round(mpix, 1),
+           "jpeg_bytes": sum(len(f) for f in files), "package": os.path.dirname(os.path.abspath(jx.__file__))}
+
+    def report(times):
+        ms = median(times[args.warmup:])
+        return {"ms_per_batch": round(ms, 2), "mpixel_per_s": round(mpix / ms * 1e3, 1), "ms_min": round(min(times[args.warmup:]), 2)}
+
+    def prepared_batch():
+        b = jx.BatchDecoder(0)
+        bufs = [torch.zeros(w * h * 3, dtype=torch.uint8, device="cuda:0") for _ in inputs]
+        for d, t in zip(inputs, bufs):
+            b.add(d, num_channels=3, device_ptr=t.data_ptr())
+        b.prepare()
+        return b, bufs
+
+    for leg in legs:
+        times = []
+        if leg in ("pixels", "decode"):
+            b, bufs = prepared_batch()
+            if leg == "pixels" and not hasattr(b, "decode_jpeg_pixels"):
+                out[leg] = "this build has no decode_jpeg_pixels"
+                continue
+            for r in range(args.warmup + args.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if leg == "pixels":
+                    errs = b.decode_jpeg_pixels()
+                else:
+                    b.decode(); b.finish()
+                torch.cuda.synchronize()
+                times.append((time.perf_counter() - t0) * 1e3)
+                if r == 0:
+                    got = [bufs[k].cpu().numpy().reshape(h, w, 3) for k in range(args.distinct)]
+                    diff = max(int(np.abs(g.astype(int) - x.astype(int)).max()) for g, x in zip(got, want))
+                    if leg == "pixels":
+                        assert errs == [None] * len(inputs), errs
+                        assert diff == 0, "pixels differ from Pillow's decode of the source files"
+            out[leg] = report(times)
+            out[leg]["max_difference_from_pillow"] = diff
+            if leg == "pixels":
+                out[leg]["pixel_launches"] = b.info_value("jpeg_pixel_launches")
+            del b, bufs
+        elif leg == "reconstruct":
+            parts = []
+            pool = ThreadPoolExecutor(args.threads)
+            for r in range(args.warmup + args.reps):
+                b = jx.BatchDecoder(0)
+                for d in inputs:
+                    b.add(d)
+                t0 = time.perf_counter()
+                b.reconstruct_jpegs()
+                got = [b.jpeg(i) for i in range(len(inputs))]
+                t1 = time.perf_counter()
+                px = list(pool.map(lambda d: np.asarray(Image.open(io.BytesIO(d))), got))
+                t2 = time.perf_counter()
+                times.append((t2 - t0) * 1e3)
+                parts.append(((t1 - t0) * 1e3, (t2 - t1) * 1e3))
+                if r == 0:
+                    assert got == files, "bytes differ from the source files"
+                    assert all(np.array_equal(px[k], want[k]) for k in range(args.distinct))
+                del b
+            pool.shutdown()
+            out[leg] = report(times)
+            out[leg]["reconstruct_ms"] = round(median([p[0] for p in parts[args.warmup:]]), 2)
+            out[leg]["host_decode_ms"] = round(median([p[1] for p in parts[args.warmup:]]), 2)
+            out[leg]["host_threads"] = args.threads
+        else:
+            raise SystemExit("unknown leg " + leg)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -345,7 +345,9 @@ JxlDecoderStatus JxlHipBatchCopyJpeg(JxlHipBatch* batch, int index, uint8_t* dst
  * fails alone — the call still returns JXL_DEC_SUCCESS; it fails only for what concerns the whole batch (HIP errors, no images, an image that cannot be prepared).
  * JxlHipBatchJpegPixelsStatus(index): JXL_DEC_SUCCESS, or JXL_DEC_ERROR with that image's reason in JxlHipLastError().  JxlHipBatchDeviceOutput / JxlHipBatchCopyOutput
  * hand out the pixels as after a decode.  JxlHipBatchGetInfo "jpeg_pixel_images": images the last call wrote; "jpeg_pixel_launches": launches of its two pixel kernels
- * (two per 32768 images).  A JxlHipBatchDecode or JxlHipBatchReconstructJpegs of the same batch afterwards gives what it gives on a fresh one. */
+ * (two per 32768 images).  A JxlHipBatchDecode or JxlHipBatchReconstructJpegs of the same batch afterwards gives what it gives on a fresh one.
+ * The integer IDCT reads the coefficients where the HF stage left them and zeroes what it read, as the float IDCT does: after a call in which every image of the batch
+ * was decoded, the coefficient planes are clean for the next decode.  The same decode as jobs of a pipeline: JxlHipPipelineSubmitJpegPixels below. */
 int JxlHipBatchCanDecodeJpegPixels(JxlHipBatch* batch, int index);
 JxlDecoderStatus JxlHipBatchDecodeJpegPixels(JxlHipBatch* batch, void* hip_stream);
 JxlDecoderStatus JxlHipBatchJpegPixelsStatus(const JxlHipBatch* batch, int index);
@@ -365,7 +367,8 @@ JxlDecoderStatus JxlHipBatchDecodeTimed(JxlHipBatch* batch, void* hip_stream);
 /* Enqueues one part of a decode: 0 = everything, 1 = front (LF decode, LF post-processing), 2 = rest (HF decode, IDCT,
  * filters, output); the rest may also be enqueued in two pieces, 3 = HF decode, 4 = IDCT, filters, output, and so may the front,
  * 5 = LF decode (all the HF decode needs), 6 = LF post-processing (needed by piece 4 only); piece 4 in turn as 7 = IDCT (the last stage
- * that touches the coefficient planes) and 8 = restoration filters, colour, write.  Front and rest may
+ * that touches the coefficient planes) and 8 = restoration filters, colour, write.  (9, 10 and 11 are the pieces of the libjpeg-exact decode that
+ * JxlHipBatchDecodeJpegPixels and the pipeline enqueue in the places of 7, 8 and 6; they need that decode's plan and do nothing without it.)  Front and rest may
  * go to different streams; the caller orders them with events, which lets the latency-bound LF stage of later batches overlap
  * the other stages of the current one (bench.py: three batches in flight, LF stages on two side streams). */
 JxlDecoderStatus JxlHipBatchDecodePart(JxlHipBatch* batch, void* hip_stream, int part, int timed);
@@ -436,6 +439,15 @@ int64_t JxlHipPipelineSubmitResized(JxlHipPipeline* pipeline, const uint8_t* con
 /* The same with a resample per image (JxlHipOutputResample above, n entries; every entry the same xsize x ysize). */
 int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
                                       void* const* host_out, const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each);
+/* A job of libjpeg-exact pixels: every image is decoded to the samples libjpeg gives for the JPEG file it was transcoded from (JxlHipBatchDecodeJpegPixels above, as
+ * stages of the pipeline: the job shares coefficient sets and pixel planes with plain jobs, which may be mixed with it freely).  Eligible is what
+ * JxlHipBatchCanDecodeJpegPixels takes; an image that is not eligible fails alone with that call's reason ("unsupported: libjpeg-exact decode of ..."), and so does an
+ * image whose stream is damaged — a frame with a transform other than DCT8 is named as such.  layout: NULL = interleaved; each: NULL, or n JxlHipOutputResample of one
+ * target size (crop, filter and mirror the image's own), as for JxlHipPipelineSubmitResampled.  There is no downscale: libjpeg's scaled IDCTs are other arithmetic.
+ * Destinations are sized as for JxlHipPipelineSubmitLayout / ...Resampled at downscale 1. */
+int64_t JxlHipPipelineSubmitJpegPixels(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
+                                       void* const* host_out, const size_t* out_capacity, const JxlHipOutputLayout* layout /* NULL = interleaved */,
+                                       const JxlHipOutputResample* each /* NULL, or n entries of one target size */);
 /* Waits until the job has left the GPU (pixels written, host copies done).  image_status[i] (n entries, optional): 0 decoded, 1 failed; *end_ms (optional): when the
  * job's last byte was written, ms after JxlHipPipelineResetClock.  JXL_DEC_SUCCESS if every image decoded, else JXL_DEC_ERROR (JxlHipLastError names the first).
  * A ticket can be waited for once; jobs complete in submission order. */
@@ -446,7 +458,9 @@ JxlDecoderStatus JxlHipPipelineCollectTimes(JxlHipPipeline* pipeline, JxlHipStag
 void JxlHipPipelineStageBytes(JxlHipPipeline* pipeline, uint64_t out[6]);   /* algorithmic bytes per stage of the job prepared last (JxlHipBatchStageBytes) */
 /* "jobs", "slots", "coefficient_sets", "device_bytes", "shared_big_bytes", "shared_coef_bytes", "private_plane_jobs" (jobs that did not fit the shared planes),
  * "prepare_us_total" / "prepared_jobs" (host time of the prepare threads since the last clock reset), and of the job prepared / finished last: "frames",
- * "compressed_bytes", "total_pixels", "hf_nonzeros", "lf_simt_frames", "lf_legacy_frames", "lf_simt_wp".  -1: unknown name. */
+ * "compressed_bytes", "total_pixels", "hf_nonzeros", "lf_simt_frames", "lf_legacy_frames", "lf_simt_wp", "jpeg_pixel_images" (images of a libjpeg-exact job that took
+ * that path; after the job has finished: that were decoded; 0 for a plain job), "jpeg_pixel_launches" (launches of its two pixel kernels: two per 32768 such images).
+ * -1: unknown name. */
 int64_t JxlHipPipelineGetInfo(JxlHipPipeline* pipeline, const char* name);
 /* Pinned host memory for host_out destinations (hipHostMalloc / hipHostFree). */
 void* JxlHipHostAlloc(size_t bytes);

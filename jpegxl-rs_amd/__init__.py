@@ -189,6 +189,8 @@ def libjxl():
                                                           C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample)]),
             "JxlHipBatchCanReconstructJpeg": (C.c_int, [vp, C.c_int]), "JxlHipBatchReconstructJpegs": (C.c_int, [vp, vp]),
             "JxlHipBatchJpegStatus": (C.c_int, [vp, C.c_int]), "JxlHipBatchJpegSize": (sz, [vp, C.c_int]), "JxlHipBatchCopyJpeg": (C.c_int, [vp, C.c_int, vp, sz]),
+            "JxlHipPipelineSubmitJpegPixels": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz),
+                                                           C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample)]),
             "JxlHipBatchCanDecodeJpegPixels": (C.c_int, [vp, C.c_int]), "JxlHipBatchDecodeJpegPixels": (C.c_int, [vp, vp]), "JxlHipBatchJpegPixelsStatus": (C.c_int, [vp, C.c_int]),
             "JxlHipBatchSetLaneStride": (None, [vp, C.c_int, C.c_int]), "JxlHipBatchSetOption": (None, [vp, C.c_char_p, C.c_int]),
             "JxlHipBatchPrepare": (C.c_int, [vp, vp]), "JxlHipBatchDecode": (C.c_int, [vp, vp]),
@@ -1003,7 +1005,7 @@ class Pipeline:
     __del__ = close
 
     def submit(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, host_ptrs=None, capacities=None, endianness=Endianness.Native, align=0, downscale=1,
-               planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False) -> int:
+               planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_pixels=False) -> int:
         """Job of len(datas) images (bytes objects).  device_ptrs / host_ptrs: one destination address per image (exactly one of the two lists); the bytes objects and
         the destinations are kept referenced until wait().  downscale=8: the job is decoded at 1:8 (JxlHipPipelineSubmitScaled).  planar, plane_stride, scale, bias:
         the layout of every image of the job, as for BatchDecoder.add (JxlHipPipelineSubmitLayout).  resize, crop: every image of the job comes out resize[0] x resize[1]
@@ -1011,7 +1013,11 @@ class Pipeline:
         crop, filter ("bilinear" | "bicubic") and mirror each take one value for the job or a sequence of len(datas) per-image values (a None in a crop sequence: the
         whole picture; four plain integers are always ONE crop (x0, y0, w, h) for the whole job, also when the job has four images — per-image crops are a sequence of
         4-tuples or Nones; a string or a number is one filter / mirror for the job, any other iterable is read as per-image values).  Whenever one of them is a sequence, or filter / mirror is set, the job goes out with one JxlHipOutputResample per image
-        (JxlHipPipelineSubmitResampled): one target size, everything else the image's own."""
+        (JxlHipPipelineSubmitResampled): one target size, everything else the image's own.
+        jpeg_pixels: a job of libjpeg-exact pixels (JxlHipPipelineSubmitJpegPixels; BatchDecoder.decode_jpeg_pixels as pipeline stages) with the same keywords; an image
+        that decode does not take fails alone, downscale other than 1 is refused here."""
+        if jpeg_pixels and int(downscale) != 1:
+            raise GenericError("unsupported: libjpeg-exact decode of an output with downscale %d (libjpeg's scaled IDCTs are other arithmetic)" % int(downscale))
         layout = _layout(planar, plane_stride, scale, bias)
         n = len(datas)
         crops, seq_c = _per_image(crop, n, lambda v: len(v) == 4 and all(isinstance(x, (int, np.integer)) for x in v))
@@ -1029,7 +1035,11 @@ class Pipeline:
         dev = (C.c_void_p * n)(*device_ptrs) if device_ptrs is not None else None
         host = (C.c_void_p * n)(*host_ptrs) if host_ptrs is not None else None
         caps = (C.c_size_t * n)(*capacities) if capacities is not None else None
-        if each is not None:
+        if jpeg_pixels:
+            if each is None and resize is not None:
+                each = (JxlHipOutputResample * max(1, n))(*[_resample(resize, crop, None, False) for _ in range(n)])      # (filter 0, no mirror: the ...Resized call, byte for byte)
+            t = libjxl().JxlHipPipelineSubmitJpegPixels(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, _byref(layout), each)
+        elif each is not None:
             t = libjxl().JxlHipPipelineSubmitResampled(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), _byref(layout), each)
         elif rs is not None:
             t = libjxl().JxlHipPipelineSubmitResized(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), _byref(layout), C.byref(rs))

@@ -421,6 +421,7 @@ Batch::~Batch() {
   Pool().Give(dwork_, work_cap_, device_);
   if (djpeg_) Pool().Give(djpeg_, jpeg_cap_, device_);
   if (djpeg_out_) Pool().Give(djpeg_out_, jpeg_out_cap_, device_);
+  if (djpeg_table_) Pool().Give(djpeg_table_, jpeg_table_cap_, device_);
   if (dcoef_ && !coef_owner_ && !coef_is_ext_) Pool().Give(dcoef_, coef_cap_, device_);
   if (dbig_ && !big_owner_ && !big_is_ext_) Pool().Give(dbig_, big_cap_, device_);
   if (big_owner_) big_owner_->big_sharers_--;
@@ -519,7 +520,7 @@ bool Batch::DevReserve(void** ptr, size_t* cap, size_t bytes) {
 // Forgets the images (and everything derived from them) but keeps the device arenas, the pinned staging buffer and the sharing set up with
 // ShareBigArena / ShareCoefArena: the batch object can be filled again.  The caller makes sure no decode of the old content is in flight.
 void Batch::Reset() {
-  images_.clear(); pub_.clear(); cbufs_.clear(); post_ops_.clear(); jpeg_data_.clear(); jpeg_pixel_results_.clear(); resize_plans_.clear(); resize_groups_.clear();
+  images_.clear(); pub_.clear(); cbufs_.clear(); post_ops_.clear(); jpeg_data_.clear(); jpeg_pixel_results_.clear(); jpeg_pixel_table_.clear(); jpeg_pixel_table_image_.clear(); jpeg_pixel_groups_.clear(); resize_plans_.clear(); resize_groups_.clear();
   frames_host_.clear(); passes_host_.clear(); pass_first_.clear(); local_host_.clear(); local_first_.clear();
   mod_plane_offsets_.clear(); mod_ops_.clear(); vardct_alpha_.clear(); hf_written_.clear();
   // (stage timings recorded so far stay: CollectTimes sums over the object's life)
@@ -2596,11 +2597,15 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
   // 6 = LF post-processing (dequantised LF, LLF, EPF sigma: what the IDCT and the filters need) — a pipelined caller lets the HF stage
   // wait for piece 5 only, so that the post-processing kernels, which wait for wavefront slots beside the pixel kernels of the batch
   // before, are off the critical path.
-  const bool do_lf = part == 0 || part == 1 || part == 5, do_lfpost = part == 0 || part == 1 || part == 6, do_front = do_lf || do_lfpost;
+  // 11 = piece 6 without its kernels, for a decode whose tail reads nothing they produce (the libjpeg-exact tail below): only the stage mark is recorded
+  const bool do_lf = part == 0 || part == 1 || part == 5, do_lfpost = part == 0 || part == 1 || part == 6 || part == 11, do_front = do_lf || do_lfpost;
   // ... and so may the tail: 7 = IDCT (the last stage that touches the coefficient planes: a caller that rotates coefficient sets lets the next
   // HF stage of that set start behind it), 8 = restoration filters, colour, write
-  const bool do_hf = part == 0 || part == 2 || part == 3, do_tail = part == 0 || part == 2 || part == 4 || part == 7 || part == 8;
-  const bool do_idct = do_tail && part != 8, do_post = do_tail && part != 7;
+  // The libjpeg-exact tail of JPEG transcodes (PlanJpegPixels / EnqueueJpegPixelTable first) takes the places of 7 and 8: 9 = integer IDCT over the HF planes, which
+  // zeroes what it reads like the float IDCT, 10 = chroma upsampling, colour, write, resizes.
+  const bool jpeg_tail = part == 9 || part == 10;
+  const bool do_hf = part == 0 || part == 2 || part == 3, do_tail = part == 0 || part == 2 || part == 4 || part == 7 || part == 8 || jpeg_tail;
+  const bool do_idct = do_tail && part != 8 && part != 10, do_post = do_tail && part != 7 && part != 9;
   const bool split = part != 0;                       // halves timed separately
   if (do_hf || do_tail) ran_once_ = true;
   if (do_hf) decodes_since_finish_++;
@@ -2643,11 +2648,13 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
     rec(1);
   }
   if (do_lfpost) {
-    if (lf_batch_) lf_batch_->RunPart(stream_v, 0, false);     // LF frames: decoded to the end, their planes copied into the LF planes of the units that refer to them
-    if (any_vardct_) LaunchLfPost(dframes_, n, max_bw_, max_bh_, max_groups_, stream_v);
-    DebugSync("LF post", stream_v);
-    CheckLaunches("LF post-processing");
-    if (part == 1 || part == 6) rec(2);
+    if (part != 11) {
+      if (lf_batch_) lf_batch_->RunPart(stream_v, 0, false);     // LF frames: decoded to the end, their planes copied into the LF planes of the units that refer to them
+      if (any_vardct_) LaunchLfPost(dframes_, n, max_bw_, max_bh_, max_groups_, stream_v);
+      DebugSync("LF post", stream_v);
+      CheckLaunches("LF post-processing");
+    }
+    if (part == 1 || part == 6 || part == 11) rec(2);
   }
   if (!any_vardct_) {
     if (do_hf) { rec(split ? 7 : 2); rec(3); }
@@ -2655,9 +2662,9 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
       if (do_idct) rec(4);
       if (do_post) {
         rec(5);
-        if (any_modchan_) EnqueueModularTail(stream_v);
-        if (any_complex_) EnqueuePostOps(stream_v);
-        EnqueueResizes(stream_v);
+        if (any_modchan_ && !jpeg_tail) EnqueueModularTail(stream_v);      // (no image of such a batch takes the libjpeg-exact tail: nothing is written)
+        if (any_complex_ && !jpeg_tail) EnqueuePostOps(stream_v);
+        if (!jpeg_tail) EnqueueResizes(stream_v);
         CheckLaunches("Modular sub-streams / frame tail");
         rec(6);
         if (timed && split) timed_rest_cursor_++;
@@ -2680,20 +2687,29 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
     rec(3);
   }
   if (do_tail) {
-    if (!cfg.idct_flags_known && flags_pending_ && part != 0 && any_full_vardct_) {
+    if (!cfg.idct_flags_known && flags_pending_ && part != 0 && any_full_vardct_ && !jpeg_tail) {      // (the libjpeg-exact tail has one IDCT kernel: nothing to wait for)
       HIP_CHECK(hipEventSynchronize((hipEvent_t)flags_event_));
       ApplyIdctFlags(flags_pinned_);
       flags_pending_ = false;
     }
     if (do_idct) {
       if (split) rec(8);                        // the tail may sit on another stream than the HF stage: its own start mark
-      if (any_full_vardct_) LaunchIdct(dframes_, n, max_groups_, max_bw_, max_bh_, cfg, stream_v);
+      if (jpeg_tail) EnqueueJpegIdct(stream_v);
+      else if (any_full_vardct_) LaunchIdct(dframes_, n, max_groups_, max_bw_, max_bh_, cfg, stream_v);
       DebugSync("IDCT", stream_v);
       CheckLaunches("IDCT stage");
       rec(4);
       if (any_full_vardct_) ClearCoefficientsAfterDecode(stream_v);   // (the IDCT kernels zeroed what they read)
     }
-    if (do_post) {
+    if (do_post && jpeg_tail) {
+      rec(5);
+      EnqueueJpegColorOut(stream_v);
+      EnqueueResizes(stream_v);
+      DebugSync("JPEG pixels", stream_v);
+      CheckLaunches("JPEG pixels");
+      rec(6);
+      if (timed && split) timed_rest_cursor_++;
+    } else if (do_post) {
       if (cfg.debug_stop_after != 1 && any_full_vardct_) LaunchFilters(dframes_, n, max_w_, max_h_, fplan_, cfg, stream_v);
       DebugSync("filters", stream_v);
       rec(5);
@@ -3206,91 +3222,139 @@ bool Batch::CanDecodeJpegPixels(int i, std::string* why) const {
   return true;
 }
 
-void Batch::DecodeJpegPixels(void* stream_v) {
-  hipStream_t stream = (hipStream_t)stream_v;
+// ---- host plan (after Prepare): which images take the path, their component grids, the image table and the launch groups over it
+size_t Batch::PlanJpegPixels() {
   const int n = (int)pub_.size();
   jpeg_pixel_results_.clear(); jpeg_pixel_results_.resize((size_t)n);
   jpeg_pixel_images_ = jpeg_pixel_launches_ = 0;
-  if (!n) throw ParseError("DecodeJpegPixels: the batch holds no image", false);
-  struct Img { bool ok = false; size_t first_blk = 0; JpegFrameGrid grid; };
-  std::vector<Img> im((size_t)n);
-  bool any = false;
+  jpeg_pixel_table_.clear(); jpeg_pixel_table_image_.clear(); jpeg_pixel_groups_.clear();
+  if (!prepared_) throw ParseError("PlanJpegPixels: the batch is not prepared", false);
+  vec<JpegPixelImage>& table = jpeg_pixel_table_;
   for (int i = 0; i < n; i++) {
     std::string why;
-    if (CanDecodeJpegPixels(i, &why)) { im[i].ok = true; any = true; } else jpeg_pixel_results_[i].error = why;
-  }
-  if (!any) return;
-  if (!prepared_) Prepare(stream_v);
-  HIP_CHECK(hipSetDevice(device_));
-  // ---- host plan: the coefficient planes of every image in one arena, laid out as ReconstructJpegs lays them out, and the image table behind them
-  size_t total_blk = 0;
-  vec<JpegPixelImage> table;
-  vec<int> table_image;
-  for (int i = 0; i < n; i++) {
-    Img& m = im[i];
-    if (!m.ok) continue;
+    if (!CanDecodeJpegPixels(i, &why)) { jpeg_pixel_results_[i].error = why; continue; }
     const int u = pub_[i].first_unit;
     const ImageEntry& e = *images_[u];
     const FramePlan& p = e.plan;
-    std::string why = JpegPixelTableRefusal(p);
-    if (!why.empty()) { m.ok = false; jpeg_pixel_results_[i].error = "unsupported: libjpeg-exact decode of " + why; continue; }
+    why = JpegPixelTableRefusal(p);
+    if (!why.empty()) { jpeg_pixel_results_[i].error = "unsupported: libjpeg-exact decode of " + why; continue; }
     const uint32_t ncomp = e.ih.color_space == 1 ? 1 : 3;
-    if (!JpegGridFromFrame(p, ncomp, "libjpeg-exact decode", &m.grid, &why)) { m.ok = false; jpeg_pixel_results_[i].error = why; continue; }
-    const JpegFrameGrid& g = m.grid;
+    JpegFrameGrid g;
+    if (!JpegGridFromFrame(p, ncomp, "libjpeg-exact decode", &g, &why)) { jpeg_pixel_results_[i].error = why; continue; }
     const FrameDev& f = frames_host_[u];
-    // every address of the two kernels follows from this entry: the component grids must hold the components' real extents, the planes they are written to must exist
-    bool fits = g.nblk < ((size_t)1 << 31) && f.plane_a[0] && f.plane_a[1] && f.plane_a[2] && !f.lf_only;
+    // every address of the two kernels follows from this entry and the frame's own block grid: the component grids must hold the components' real extents and lie inside
+    // the frame's grid, the planes that are read and written must exist
+    bool fits = g.nblk < ((size_t)1 << 31) && f.plane_a[0] && f.plane_a[1] && f.plane_a[2] && !f.lf_only && f.coef_off && f.blk_info && f.status;
     for (uint32_t c = 0; c < ncomp && fits; c++) {
+      const int chn = ncomp == 1 ? 1 : (c == 0 ? 1 : c == 1 ? 0 : 2);
       const uint32_t cw = (e.ih.xsize + (1u << g.hs[c]) - 1) >> g.hs[c], ch = (e.ih.ysize + (1u << g.vs[c]) - 1) >> g.vs[c];
-      fits = g.grid_w[c] && g.grid_h[c] && (uint64_t)g.grid_w[c] * 8 >= cw && (uint64_t)g.grid_h[c] * 8 >= ch && g.grid_w[c] <= p.bw && g.grid_h[c] <= p.bh;
+      fits = g.grid_w[c] && g.grid_h[c] && (uint64_t)g.grid_w[c] * 8 >= cw && (uint64_t)g.grid_h[c] * 8 >= ch && g.grid_w[c] <= p.bw && g.grid_h[c] <= p.bh && f.coeff[chn] && f.lfq[chn];
     }
-    if (!fits) { m.ok = false; jpeg_pixel_results_[i].error = "unsupported: libjpeg-exact decode of a frame whose block grid does not hold the image"; continue; }
-    m.first_blk = total_blk; total_blk += g.nblk;
+    const bool walk = ncomp == 3 && !g.hs[1] && !g.vs[1];      // 4:4:4 colour: chroma from luma, one position per block of the frame
+    if (walk) fits = fits && f.ytox && f.ytob;
+    if (!fits) { jpeg_pixel_results_[i].error = "unsupported: libjpeg-exact decode of a frame whose block grid does not hold the image"; continue; }
     JpegPixelImage t;
     memset(&t, 0, sizeof(t));
     for (uint32_t c = 0; c < ncomp; c++) {
       t.plane[c] = (uint8_t*)f.plane_a[ncomp == 1 ? 1 : (c == 0 ? 1 : c == 1 ? 0 : 2)];     // (the frame's own pixel planes, which this decode does not use otherwise: bw x bh x 64 floats each)
-      t.comp_first[c] = (uint32_t)g.comp_first[c]; t.grid_w[c] = g.grid_w[c];
-      for (int k = 0; k < 64; k++) t.qt[c][k] = g.qt[c][k];
+      t.comp_first[c] = (uint32_t)g.comp_first[c]; t.grid_w[c] = g.grid_w[c]; t.grid_h[c] = g.grid_h[c];
+      for (int v = 0; v < 8; v++) for (int h = 0; h < 8; h++) {
+        const int nat = v * 8 + h, tr = h * 8 + v;           // (the kernel reads the tables beside the coefficients: the planes' transposed layout)
+        t.qt[c][tr] = g.qt[c][nat];
+        if (c && walk) t.cfl_ratio[c - 1][tr] = g.qt[c][nat] > 0 ? (int32_t)((int64_t)2048 * g.qt[0][nat] / g.qt[c][nat]) : 0;
+      }
     }
-    t.nblk = (uint32_t)g.nblk; t.ncomp = ncomp; t.frame = (uint32_t)u;
+    t.npos = walk ? g.grid_w[0] * g.grid_h[0] : (uint32_t)g.nblk; t.ncomp = ncomp; t.frame = (uint32_t)u;
     t.width = e.ih.xsize; t.height = e.ih.ysize; t.hs = ncomp == 3 ? g.hs[1] : 0; t.vs = ncomp == 3 ? g.vs[1] : 0;
-    table.push_back(t); table_image.push_back(i);
+    table.push_back(t); jpeg_pixel_table_image_.push_back(i);
   }
-  if (table.empty()) return;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_coef = take(total_blk * 128), o_table = take(table.size() * sizeof(JpegPixelImage));
-  DevReserve((void**)&djpeg_, &jpeg_cap_, std::max<size_t>(off, 256));
-  for (size_t k = 0; k < table.size(); k++) table[k].coef = (const int16_t*)(djpeg_ + o_coef) + im[table_image[k]].first_blk * 64;
-  HIP_CHECK(hipMemcpyAsync(djpeg_ + o_table, table.data(), table.size() * sizeof(JpegPixelImage), hipMemcpyHostToDevice, stream));
-  // ---- one entropy decode of the batch (LF stage: JPEG DC, block metadata; HF stage: AC), coefficients into JPEG layout
-  RunPart(stream_v, 1, false);
-  RunPart(stream_v, 3, false);
-  for (size_t k = 0; k < table.size(); k++) EnqueueJpegCoefficients(table_image[k], im[table_image[k]].grid, (int16_t*)table[k].coef, stream_v);
-  DebugSync("JPEG coefficients", stream_v);
-  // ---- the pixel half: one launch per kernel and group of the table, then the resizes of resized outputs over the f32 pictures the write stage left
-  const JpegPixelImage* dtable = (const JpegPixelImage*)(djpeg_ + o_table);
   for (size_t first = 0; first < table.size(); first += kJpegPixelGroupMax) {
     JpegPixelGroup g{(uint32_t)first, (uint32_t)std::min<size_t>(kJpegPixelGroupMax, table.size() - first), 0, 0, 0};
     for (uint32_t k = 0; k < g.count; k++) {
       const JpegPixelImage& t = table[first + k];
-      g.max_nblk = std::max(g.max_nblk, t.nblk); g.max_w = std::max(g.max_w, t.width); g.max_h = std::max(g.max_h, t.height);
+      g.max_npos = std::max(g.max_npos, t.npos); g.max_w = std::max(g.max_w, t.width); g.max_h = std::max(g.max_h, t.height);
     }
-    LaunchJpegPixelGroup(dframes_, dtable, g, stream_v);
-    jpeg_pixel_launches_ += 2;
+    jpeg_pixel_groups_.push_back(g);
   }
-  EnqueueResizes(stream_v);
-  DebugSync("JPEG pixels", stream_v);
-  CheckLaunches("JPEG pixels");
-  vec<uint32_t> status;
-  FinishStatus(stream_v, &status);
-  for (size_t k = 0; k < table.size(); k++) {
-    const int i = table_image[k];
+  return table.size();
+}
+
+// The table goes into a buffer of its own (not the constant arena: Prepare's layout does not know about this decode).  The host copy stays in the batch until the
+// next plan, so the copy may still be on its way when this returns.
+void Batch::EnqueueJpegPixelTable(void* stream_v, bool fail_refused) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  HIP_CHECK(hipSetDevice(device_));
+  if (!jpeg_pixel_table_.empty()) {
+    const size_t bytes = jpeg_pixel_table_.size() * sizeof(JpegPixelImage);
+    DevReserve((void**)&djpeg_table_, &jpeg_table_cap_, std::max<size_t>(bytes, 256));
+    HIP_CHECK(hipMemcpyAsync(djpeg_table_, jpeg_pixel_table_.data(), bytes, hipMemcpyHostToDevice, stream));
+  }
+  if (!fail_refused) return;
+  // nobody consumes the coefficients of a frame that is not in the table: with its status word set the entropy stages skip it where they can, and what the HF stage
+  // wrote for it before is zeroed behind that stage (ZeroFailedCoefKernel), like a damaged frame's
+  static const uint32_t kRefused = kErrUnsupported;
+  vec<uint8_t> in_table(images_.size(), 0);
+  for (int i : jpeg_pixel_table_image_) in_table[(size_t)pub_[i].first_unit] = 1;
+  for (size_t u = 0; u < images_.size(); u++)
+    if (!in_table[u]) HIP_CHECK(hipMemcpyAsync(dwork_ + status_off_ + u * 4, &kRefused, 4, hipMemcpyHostToDevice, stream));
+}
+
+void Batch::EnqueueJpegIdct(void* stream_v) {
+  const JpegPixelImage* dtable = (const JpegPixelImage*)djpeg_table_;
+  for (const JpegPixelGroup& g : jpeg_pixel_groups_) { LaunchJpegIdctGroup(dframes_, dtable, g, stream_v); jpeg_pixel_launches_++; }
+  // (a frame the kernel failed — kErrVarblock — has been consumed in part only: its planes are zeroed whole, as behind the HF stage)
+  if (!jpeg_pixel_groups_.empty()) LaunchZeroFailedCoefficients(dframes_, (int)images_.size(), stream_v);
+}
+void Batch::EnqueueJpegColorOut(void* stream_v) {
+  const JpegPixelImage* dtable = (const JpegPixelImage*)djpeg_table_;
+  for (const JpegPixelGroup& g : jpeg_pixel_groups_) { LaunchJpegColorOutGroup(dframes_, dtable, g, stream_v); jpeg_pixel_launches_++; }
+}
+
+// what a status word means for an image of this path: kErrVarblock is set by JpegIdctPlanesKernel itself
+static std::string JpegPixelStatusMessage(uint32_t st, int frame) {
+  if (st & kErrVarblock) return "corrupt stream: a JPEG-transcoded frame with a transform other than DCT8 (device status " + std::to_string(st) + ", frame " + std::to_string(frame) + ")";
+  bool unsupported;
+  return DeviceStatusMessage(st, frame, &unsupported);
+}
+void Batch::HarvestJpegPixels(const vec<uint32_t>& status) {
+  jpeg_pixel_images_ = 0;
+  for (size_t k = 0; k < jpeg_pixel_table_image_.size(); k++) {
+    const int i = jpeg_pixel_table_image_[k];
     JpegPixelResult& r = jpeg_pixel_results_[i];
-    if (const uint32_t st = status[pub_[i].first_unit]) { bool unsupported; r.error = DeviceStatusMessage(st, pub_[i].first_unit, &unsupported); continue; }
+    const int u = pub_[i].first_unit;
+    if (const uint32_t st = (size_t)u < status.size() ? status[(size_t)u] : 1u) { r.error = JpegPixelStatusMessage(st, u); continue; }
     r.ok = true; jpeg_pixel_images_++;
   }
+}
+
+// The batch call: plan, one entropy decode of the batch, the pixel kernels, harvest — with a host wait at the end
+void Batch::DecodeJpegPixels(void* stream_v) {
+  const int n = (int)pub_.size();
+  jpeg_pixel_results_.clear(); jpeg_pixel_results_.resize((size_t)n);
+  jpeg_pixel_images_ = jpeg_pixel_launches_ = 0;
+  jpeg_pixel_table_.clear(); jpeg_pixel_table_image_.clear(); jpeg_pixel_groups_.clear();
+  if (!n) throw ParseError("DecodeJpegPixels: the batch holds no image", false);
+  bool any = false;
+  for (int i = 0; i < n; i++) {
+    std::string why;
+    if (CanDecodeJpegPixels(i, &why)) any = true; else jpeg_pixel_results_[i].error = why;
+  }
+  if (!any) return;
+  if (!prepared_) Prepare(stream_v);
+  HIP_CHECK(hipSetDevice(device_));
+  if (!PlanJpegPixels()) return;
+  EnqueueJpegPixelTable(stream_v, /*fail_refused=*/false);
+  // ---- one entropy decode of the batch (LF stage: JPEG DC, block metadata; HF stage: AC)
+  RunPart(stream_v, 1, false);
+  RunPart(stream_v, 3, false);
+  // ---- the pixel half: one launch per kernel and group of the table, then the resizes of resized outputs over the f32 pictures the write stage left
+  RunPart(stream_v, 9, false);
+  RunPart(stream_v, 10, false);
+  vec<uint32_t> status;
+  FinishStatus(stream_v, &status);          // (a frame that failed leaves the set marked dirty)
+  // frames outside the table went through the HF stage too, and nobody consumed their coefficients
+  if (jpeg_pixel_table_.size() != images_.size()) CoefDirty() = true;
+  HarvestJpegPixels(status);
 }
 
 void Batch::CopyOutputSlotToHost(int i, int slot, void* dst, size_t size, void* stream_v) {

@@ -182,6 +182,16 @@ class Batch {
   struct JpegPixelResult { bool ok = false; std::string error; };
   bool CanDecodeJpegPixels(int i, std::string* why = nullptr) const;
   void DecodeJpegPixels(void* stream);
+  // DecodeJpegPixels in its steps, for callers that order the stages themselves (Pipeline jobs of this kind):
+  //   PlanJpegPixels            host only, after Prepare: eligibility, the component grids, the image table and its launch groups; an image that is refused gets its
+  //                             jpeg_pixel_result now.  Returns the number of images in the table.
+  //   EnqueueJpegPixelTable     uploads the table into a buffer of its own on `stream`; fail_refused: the status words of the frames that are NOT in the table are set
+  //                             (kErrUnsupported), so that the HF stage's ZeroFailedCoefKernel puts zeros back where nobody will consume their coefficients
+  //   RunPart(stream, 9 / 10)   the integer IDCT over the HF planes (the last stage that touches the coefficient set, which is clean behind it); colour, write and resizes
+  //   HarvestJpegPixels         the status words (FinishStatus / HarvestStatus) -> jpeg_pixel_result of the images in the table
+  size_t PlanJpegPixels();
+  void EnqueueJpegPixelTable(void* stream, bool fail_refused);
+  void HarvestJpegPixels(const vec<uint32_t>& per_unit);
   const JpegPixelResult* jpeg_pixel_result(int i) const { return i >= 0 && (size_t)i < jpeg_pixel_results_.size() ? &jpeg_pixel_results_[(size_t)i] : nullptr; }
   void FinishStatus(void* stream, vec<uint32_t>* per_unit);
   // Copies frame i's pixels to host memory (after Finish).
@@ -194,7 +204,7 @@ class Batch {
   // Same as Run but brackets every stage with HIP events recorded on `stream` (no host sync).  CollectTimes() waits for
   // all recorded runs and returns the per-stage sums (ms) and the number of runs; used by bench.py for the roofline.
   void RunTimed(void* stream);
-  void RunPart(void* stream, int part, bool timed);
+  void RunPart(void* stream, int part, bool timed);   // parts: decoder.cc; 9 / 10 / 11 are the libjpeg-exact tail (after PlanJpegPixels) in the places of 7 / 8 / 6
   StageTimes CollectTimes(int* runs);
   void DebugTimeline(void* ref_event, float out[9]);
   // ALGORITHMIC bytes per stage for one Run of the batch: 0 lf, 1 lfpost, 2 hf, 3 idct, 4 filters, 5 out
@@ -271,6 +281,12 @@ class Batch {
   std::vector<JpegResult> jpeg_results_;       // per image, of the last ReconstructJpegs
   std::vector<JpegPixelResult> jpeg_pixel_results_;   // per image, of the last DecodeJpegPixels
   int64_t jpeg_pixel_images_ = 0, jpeg_pixel_launches_ = 0;   // images the last DecodeJpegPixels wrote; launches of its two pixel kernels (two per group of the image table)
+  vec<JpegPixelImage> jpeg_pixel_table_;       // PlanJpegPixels: the image table (host copy; the upload reads it), the image of every entry, the launch groups
+  vec<int> jpeg_pixel_table_image_;
+  std::vector<JpegPixelGroup> jpeg_pixel_groups_;
+  uint8_t* djpeg_table_ = nullptr; size_t jpeg_table_cap_ = 0;   // the table on the device
+  void EnqueueJpegIdct(void* stream);          // JpegIdctPlanesKernel per group, then ZeroFailedCoefKernel for the frames it failed
+  void EnqueueJpegColorOut(void* stream);      // JpegColorOutKernel per group
   bool IsPlainJpegFrame(int i) const;          // the frame conditions CanReconstructJpeg and CanDecodeJpegPixels share
   void EnqueueJpegCoefficients(int i, const JpegFrameGrid& g, int16_t* out, void* stream);   // JpegCoefKernel: image i's coefficients into JPEG layout at `out`
   int jpeg_device_images_ = 0, jpeg_host_images_ = 0, jpeg_device_progressive_images_ = 0;

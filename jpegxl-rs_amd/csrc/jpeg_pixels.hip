@@ -1,7 +1,8 @@
 // jxl-hip: the samples libjpeg gives for the original file of a JPEG transcode (decoder.cc Batch::DecodeJpegPixels) — integer arithmetic throughout, no part of the
-// float VarDCT pipeline.  Input: the int16 coefficient planes JpegCoefKernel leaves in device memory (natural order, MCU-padded block grids) and the JPEG
+// float VarDCT pipeline.  Input: the quantised coefficients where the HF stage left them (FrameDev::coeff, the DC terms in FrameDev::lfq) and the JPEG
 // quantisation tables.  Output: the caller's pixels through the write stage (pixel_ops.h StorePixel).
-//   JpegIdctKernel       dequantisation and libjpeg's jpeg_idct_islow (jidctint.c: CONST_BITS 13, PASS1_BITS 2) -> u8 component planes of the padded grids
+//   JpegIdctPlanesKernel chroma from luma (4:4:4), dequantisation and libjpeg's jpeg_idct_islow (jidctint.c: CONST_BITS 13, PASS1_BITS 2) -> u8 component planes of the
+//                        padded grids; zeroes the coefficients it read
 //   JpegColorOutKernel   "fancy" chroma upsampling (jdsample.c h2v1 / h2v2 triangle filters; plain replication for planes at most two samples wide), fixed-point
 //                        YCbCr -> RGB (jdcolor.c), sample k enters the write stage as (float)k x (1 / 255)
 // Every sum that a damaged stream can drive out of range is formed in uint32_t: it wraps, nothing is undefined; the samples of such a stream mean nothing, but every
@@ -40,46 +41,106 @@ template <int N> __device__ __forceinline__ void JpegIdct1D(const uint32_t i[8],
 
 __device__ __forceinline__ uint32_t ClampU8(int32_t v) { return (uint32_t)min(max(v, 0), 255); }
 
-// A wavefront takes eight blocks, lane = (block j, k).  Pass 1: the lane owns column k of its block; pass 2: row k.
-__global__ __launch_bounds__(256) void JpegIdctKernel(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table) {
+// The integer IDCT straight from the HF stage's coefficient planes (FrameDev::coeff, FrameDev::lfq): what JpegCoefKernel (kernels_features.hip) would have
+// gathered into JPEG layout is read where the HF stage left it, and zeroed, so that the coefficient set is clean for its next user as after IdctTileKernel.
+//   Work: a wavefront takes eight *positions* of the image's list, lane = (position j, k).  A position of a grey or subsampled image is one block of one component
+//   (components one after another, block raster order of their padded grids, as comp_first says); a position of a 4:4:4 colour image is one block position of the
+//   frame, whose lane group walks Y, Cb, Cr in three steps.  Pass 1: the lane owns column k (u = k) of its block; pass 2: row k.
+//   Mapping: block (sx, sy) of component c is frame block (sx << hs, sy << vs); its coefficients are the 64 dwords at g x 65536 + coef_off[o] of channel ch (Y = 1,
+//   Cb in the X slot 0, Cr in the B slot 2), g the 256x256 group of that frame block; libjxl stores the transpose of JPEG's (v, u), so column u = k is the eight
+//   consecutive dwords 8 k .. 8 k + 7: two 16-byte loads per lane, 256 contiguous bytes per block, eight such runs per wavefront.  The DC term is lfq at (sx, sy)
+//   of the padded grid (which is o itself at 4:4:4).  qt and cfl_ratio of the table are kept in the same transposed layout and are read the same way.
+//   Chroma from luma (4:4:4 only): a chroma coefficient is coeff + cfl(y) with JpegCoefKernel's formula; the lane keeps Y's quantised column in registers from
+//   step 0 on, so chroma never reads Y's dwords from memory.
+//   One reader per dword: a (channel, frame block) pair belongs to exactly one (position, step), and of its 64 dwords lane k alone reads — and then zeroes —
+//   8 k .. 8 k + 7; DCT8 blocks of one group have disjoint slots (the placement gives every varblock its own).  So no dword is read by one lane and zeroed by
+//   another: there is no order between wavefronts (or workgroups) to get wrong, in particular none between "chroma reads Y" and "Y is zeroed".  (A damaged
+//   stream with larger varblocks breaks the disjointness; such a frame fails with kErrVarblock, its samples are not delivered and its planes are zeroed whole.)
+//   Addresses: (sx << hs, sy << vs) is checked against the frame's grid, coef_off — written by the placement for every block of a frame that has not failed, as
+//   the float IDCT kernels rely on — is in addition brought to a multiple of 64 at most 65536 - 64, so that whatever a damaged stream left there stays inside
+//   the group's 65536 dwords and 16-byte aligned.
+//   LDS: 72 dwords per block.  Pass 1's column stores are ds_write_b32 (banks (a / 4) % 32, one 32-lane half at a time): the half's lanes (j = 0 .. 3, k) hit
+//   banks (8 j + k + 8 r) % 32, all different.  Pass 2 reads rows with ds_read_b128.
+__global__ __launch_bounds__(256) void JpegIdctPlanesKernel(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table) {
   __shared__ __attribute__((aligned(16))) int32_t ws[kIdctWaves][kIdctBlocksPerWave * kIdctBlockStride];
   const JpegPixelImage& im = table[blockIdx.z];
   const FrameDev& f = frames[im.frame];
-  if (blockIdx.x * (kIdctWaves * kIdctBlocksPerWave) >= im.nblk || *f.status != 0) return;     // (uniform over the workgroup)
+  if (blockIdx.x * (kIdctWaves * kIdctBlocksPerWave) >= im.npos || *f.status != 0) return;     // (uniform over the workgroup; a failed frame's planes are zeroed by ZeroFailedCoefKernel)
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane >> 3, k = lane & 7;
-  const uint32_t blk = (blockIdx.x * kIdctWaves + wave) * kIdctBlocksPerWave + j;
-  const bool live = blk < im.nblk;
-  const uint32_t c = im.ncomp == 3 ? (blk >= im.comp_first[2] ? 2u : blk >= im.comp_first[1] ? 1u : 0u) : 0u;
-  const uint32_t local = blk - im.comp_first[c], gw = im.grid_w[c], bx = local % gw, by = local / gw;
-  int32_t* const w = ws[wave] + j * kIdctBlockStride;
-  if (live) {
-    if (k == 0) {
-      // the entropy stages of a damaged stream may have placed other transforms than DCT8: the frame fails through its status word (its samples are not delivered)
-      const uint32_t sx = c ? bx << im.hs : bx, sy = c ? by << im.vs : by;
-      if (sx < f.bw && sy < f.bh && (f.blk_info[(size_t)sy * f.bw + sx] & 31u) != 0) atomicOr(f.status, (uint32_t)kErrVarblock);
-    }
-    const int16_t* __restrict__ cf = im.coef + (size_t)blk * 64 + k;
-    const int32_t* __restrict__ q = im.qt[c] + k;
-    uint32_t in[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) in[r] = (uint32_t)(int32_t)cf[r * 8] * (uint32_t)q[r * 8];
-    int32_t col[8];
-    JpegIdct1D<11>(in, col);
-#pragma unroll
-    for (int r = 0; r < 8; r++) w[r * 8 + k] = col[r];
+  const uint32_t pos = (blockIdx.x * kIdctWaves + wave) * kIdctBlocksPerWave + j;
+  const bool walk = im.ncomp == 3 && !im.hs;                 // 4:4:4: Y, Cb, Cr of one block position
+  const uint32_t steps = walk ? 3u : 1u;                     // (uniform over the workgroup: the barriers below are reached by all of it)
+  uint32_t c = 0, bx = 0, by = 0;
+  {
+    if (!walk && im.ncomp == 3) c = pos >= im.comp_first[2] ? 2u : pos >= im.comp_first[1] ? 1u : 0u;
+    const uint32_t local = pos - (walk ? 0u : im.comp_first[c]), gw = im.grid_w[c];
+    bx = local % gw; by = local / gw;
   }
-  __syncthreads();
-  if (!live) return;
-  uint32_t in[8];
-  const int4 lo = *(const int4*)(w + k * 8), hi = *(const int4*)(w + k * 8 + 4);
-  in[0] = (uint32_t)lo.x; in[1] = (uint32_t)lo.y; in[2] = (uint32_t)lo.z; in[3] = (uint32_t)lo.w;
-  in[4] = (uint32_t)hi.x; in[5] = (uint32_t)hi.y; in[6] = (uint32_t)hi.z; in[7] = (uint32_t)hi.w;
-  int32_t row[8];
-  JpegIdct1D<18>(in, row);
-  uint2 px;
-  px.x = ClampU8(row[0] + 128) | ClampU8(row[1] + 128) << 8 | ClampU8(row[2] + 128) << 16 | ClampU8(row[3] + 128) << 24;
-  px.y = ClampU8(row[4] + 128) | ClampU8(row[5] + 128) << 8 | ClampU8(row[6] + 128) << 16 | ClampU8(row[7] + 128) << 24;
-  *(uint2*)(im.plane[c] + ((size_t)by * 8 + k) * ((size_t)gw * 8) + (size_t)bx * 8) = px;
+  int32_t* const w = ws[wave] + j * kIdctBlockStride;
+  int32_t ycol[8] = {0, 0, 0, 0, 0, 0, 0, 0};               // Y's quantised column k (4:4:4), for the chroma steps
+  size_t tile = 0;
+  for (uint32_t step = 0; step < steps; step++) {
+    if (walk) c = step;
+    const uint32_t ch = im.ncomp == 1 ? 1u : (c == 0 ? 1u : c == 1 ? 0u : 2u);
+    const uint32_t hs = c ? im.hs : 0u, vs = c ? im.vs : 0u, gw = im.grid_w[c];
+    const uint32_t sx = bx << hs, sy = by << vs;            // the frame block that carries this component block
+    const bool live = pos < im.npos && by < im.grid_h[c] && sx < f.bw && sy < f.bh;
+    if (live) {
+      const size_t o = (size_t)sy * f.bw + sx;
+      // the entropy stages of a damaged stream may have placed other transforms than DCT8: the frame fails through its status word (its samples are not delivered)
+      if (k == 0 && (f.blk_info[o] & 31u) != 0) atomicOr(f.status, (uint32_t)kErrVarblock);
+      const uint32_t g = (sy / 32) * f.xgroups + sx / 32;
+      const uint32_t coff = min(f.coef_off[o] & ~63u, 65536u - 64u);
+      int4* const src = (int4*)(f.coeff[ch] + (size_t)g * 65536 + coff + k * 8);
+      const int4 lo = src[0], hi = src[1];
+      if (lo.x | lo.y | lo.z | lo.w) src[0] = make_int4(0, 0, 0, 0);      // consumed: the planes stay clean for the next decode
+      if (hi.x | hi.y | hi.z | hi.w) src[1] = make_int4(0, 0, 0, 0);
+      int32_t cf[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};   // cf[v]: coefficient (v, u = k)
+      const int4 qlo = *(const int4*)(im.qt[c] + k * 8), qhi = *(const int4*)(im.qt[c] + k * 8 + 4);
+      const int32_t q[8] = {qlo.x, qlo.y, qlo.z, qlo.w, qhi.x, qhi.y, qhi.z, qhi.w};
+      if (walk) {
+        if (c == 0) {
+          tile = (size_t)(sy / 8) * f.cw + sx / 8;
+#pragma unroll
+          for (int r = 0; r < 8; r++) ycol[r] = cf[r];
+        } else {
+          const int32_t fac = c == 1 ? (int32_t)f.ytox[tile] : (int32_t)f.ytob[tile];
+          const int32_t ff = fac * 2048 / 84;                             // (C++ division: truncates toward zero)
+          const int32_t* __restrict__ ratio = im.cfl_ratio[c - 1] + k * 8;   // 2048 qt[0][i] / qt[c][i], the host's division
+          const int4 rlo = *(const int4*)ratio, rhi = *(const int4*)(ratio + 4);
+          const int32_t rt[8] = {rlo.x, rlo.y, rlo.z, rlo.w, rhi.x, rhi.y, rhi.z, rhi.w};
+#pragma unroll
+          for (int r = 0; r < 8; r++) {
+            const int32_t scale = (int32_t)((uint32_t)rt[r] * (uint32_t)ff);
+            const int32_t cfl = (int32_t)((uint32_t)ycol[r] * (uint32_t)((int32_t)((uint32_t)scale + 1024u) >> 11) + 1024u) >> 11;
+            cf[r] = (int32_t)((uint32_t)cf[r] + (uint32_t)cfl);
+          }
+        }
+      }
+      if (k == 0) cf[0] = f.lfq[ch][(size_t)by * f.bw + bx];              // (no chroma from luma on the DC term: the LF stage has its own)
+      uint32_t in[8];
+#pragma unroll
+      for (int r = 0; r < 8; r++) in[r] = (uint32_t)(int32_t)(int16_t)cf[r] * (uint32_t)q[r];     // (int16_t: the width JPEG gives a coefficient, as JpegCoefKernel stores it)
+      int32_t col[8];
+      JpegIdct1D<11>(in, col);
+#pragma unroll
+      for (int r = 0; r < 8; r++) w[r * 8 + k] = col[r];
+    }
+    __syncthreads();
+    if (live) {
+      uint32_t in[8];
+      const int4 lo = *(const int4*)(w + k * 8), hi = *(const int4*)(w + k * 8 + 4);
+      in[0] = (uint32_t)lo.x; in[1] = (uint32_t)lo.y; in[2] = (uint32_t)lo.z; in[3] = (uint32_t)lo.w;
+      in[4] = (uint32_t)hi.x; in[5] = (uint32_t)hi.y; in[6] = (uint32_t)hi.z; in[7] = (uint32_t)hi.w;
+      int32_t row[8];
+      JpegIdct1D<18>(in, row);
+      uint2 px;
+      px.x = ClampU8(row[0] + 128) | ClampU8(row[1] + 128) << 8 | ClampU8(row[2] + 128) << 16 | ClampU8(row[3] + 128) << 24;
+      px.y = ClampU8(row[4] + 128) | ClampU8(row[5] + 128) << 8 | ClampU8(row[6] + 128) << 16 | ClampU8(row[7] + 128) << 24;
+      *(uint2*)(im.plane[c] + ((size_t)by * 8 + k) * ((size_t)gw * 8) + (size_t)bx * 8) = px;
+    }
+    if (step + 1 < steps) __syncthreads();                  // (the next step's pass 1 overwrites the workspace)
+  }
 }
 
 // The two chroma samples of output pixels (2 sx, 2 sx + 1) of row y from plane s (jdsample.c): cw x ch is the component's real extent, the padded part of the grid is
@@ -134,10 +195,13 @@ __global__ __launch_bounds__(256) void JpegColorOutKernel(const FrameDev* __rest
 
 }  // namespace
 
-void LaunchJpegPixelGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream) {
-  if (!g.count || g.count > kJpegPixelGroupMax || !g.max_nblk || !g.max_w || !g.max_h) return;
+void LaunchJpegIdctGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream) {
+  if (!g.count || g.count > kJpegPixelGroupMax || !g.max_npos || !g.max_w || !g.max_h) return;
   const uint32_t per_wg = kIdctWaves * kIdctBlocksPerWave;
-  hipLaunchKernelGGL(JpegIdctKernel, dim3((g.max_nblk + per_wg - 1) / per_wg, 1, g.count), dim3(256), 0, (hipStream_t)stream, frames, table + g.first);
+  hipLaunchKernelGGL(JpegIdctPlanesKernel, dim3((g.max_npos + per_wg - 1) / per_wg, 1, g.count), dim3(256), 0, (hipStream_t)stream, frames, table + g.first);
+}
+void LaunchJpegColorOutGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream) {
+  if (!g.count || g.count > kJpegPixelGroupMax || !g.max_npos || !g.max_w || !g.max_h) return;
   hipLaunchKernelGGL(JpegColorOutKernel, dim3((g.max_w + 63) / 64, (g.max_h + 7) / 8, g.count), dim3(32, 8), 0, (hipStream_t)stream, frames, table + g.first);
 }
 

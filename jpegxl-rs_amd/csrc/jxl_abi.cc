@@ -1178,6 +1178,29 @@ int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* h, const uint8_t* const* d
     return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity, specs.empty() ? nullptr : specs.data());
   } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
 }
+// a libjpeg-exact job (Pipeline::Submit, jpeg_pixels): the layout and the per-image resamples of the calls above, no downscale
+int64_t JxlHipPipelineSubmitJpegPixels(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                                       const size_t* out_capacity, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each) {
+  const char* who = "JxlHipPipelineSubmitJpegPixels";
+  try {
+    OutputSpec base;
+    if (!h || !FormatToSpec(format, &base)) { SetLastError(std::string(who) + ": bad pixel format"); return -1; }
+    if (!ApplyLayout(layout, &base, who)) return -1;
+    base.downscale = 1;
+    if (!each) return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity, nullptr, /*jpeg_pixels=*/true);
+    std::vector<OutputSpec> specs((size_t)std::max(n, 0), base);
+    for (int i = 0; i < n; i++) {
+      if (!ApplyResample(&each[i], &specs[(size_t)i], who)) { SetLastError("image " + std::to_string(i) + ": " + JxlHipLastError()); return -1; }
+      if (each[i].xsize != each[0].xsize || each[i].ysize != each[0].ysize) {
+        SetLastError(std::string(who) + ": image " + std::to_string(i) + " asks for " + std::to_string(each[i].xsize) + " x " + std::to_string(each[i].ysize) + ", image 0 for " +
+                     std::to_string(each[0].xsize) + " x " + std::to_string(each[0].ysize) + ": one target size per job");
+        return -1;
+      }
+    }
+    if (n > 0) { base.resize_w = each[0].xsize; base.resize_h = each[0].ysize; }
+    return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity, specs.empty() ? nullptr : specs.data(), /*jpeg_pixels=*/true);
+  } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
+}
 JxlDecoderStatus JxlHipPipelineWait(JxlHipPipeline* h, int64_t ticket, int* image_status, int n, float* end_ms) {
   try {
     PipelineJobResult r;

@@ -362,21 +362,25 @@ void LaunchJpegSizes(const JpegWritePlan& p, void* stream);
 void LaunchJpegPack(const JpegWritePlan& p, const JpegPackBuffers& o, void* stream);
 uint32_t JpegStuffChunkBytes();
 // ---- libjpeg-exact pixels of JPEG transcodes (jpeg_pixels.hip; decoder.cc Batch::DecodeJpegPixels).  One JpegPixelImage per image that takes the path, in a device
-// table; both kernels run over a group of the table with the image on blockIdx.z.  coef: the image's quantised coefficients as JpegCoefKernel leaves them (components
-// one after another, block raster order of the padded grid, natural order); qt: the JPEG quantisation tables, natural order.  plane[c]: u8 samples of component c
-// (0 Y, 1 Cb, 2 Cr) after the integer IDCT, grid_w[c] x 8 bytes per row, the whole padded grid.  hs / vs: the chroma components' shifts against luma (0 / 1).
-struct JpegPixelImage {
-  const int16_t* coef;
+// table; both kernels run over a group of the table with the image on blockIdx.z.  The coefficients are read from the frame's own planes (FrameDev::coeff / lfq / coef_off),
+// where the HF stage left them.  qt: the JPEG quantisation tables; cfl_ratio[c - 1]: 2048 x qt[0][i] / qt[c][i] (4:4:4 colour: chroma from luma, JpegCoefKernel's formula) —
+// both in the layout of the coefficient planes, the transpose of JPEG's natural order (index u * 8 + v).  plane[c]: u8 samples of component c (0 Y, 1 Cb, 2 Cr) after the
+// integer IDCT, grid_w[c] x 8 bytes per row, the whole padded grid.  hs / vs: the chroma components' shifts against luma (0 / 1) = against the frame's block grid.
+struct alignas(16) JpegPixelImage {
   uint8_t* plane[3];
-  uint32_t comp_first[3], grid_w[3];     // first block of component c among the image's blocks; blocks per row of its grid
-  uint32_t nblk, ncomp;
-  uint32_t frame;                        // FrameDev of the image: status word, block info, OutputDesc
+  uint32_t grid_w[3], grid_h[3];         // the component's padded grid, in blocks
+  uint32_t comp_first[3];                // grey and subsampled images: first position of component c (4:4:4 colour: unused, a position is one block of all three)
+  uint32_t npos;                         // positions JpegIdctPlanesKernel walks: the blocks of all components, or at 4:4:4 colour the blocks of the luma grid
+  uint32_t ncomp;
+  uint32_t frame;                        // FrameDev of the image: status word, block info, coefficient planes, OutputDesc
   uint32_t width, height, hs, vs;
-  int32_t qt[3][64];
+  alignas(16) int32_t qt[3][64];
+  alignas(16) int32_t cfl_ratio[2][64];
 };
 constexpr uint32_t kJpegPixelGroupMax = 32768;       // images per launch (gridDim.z is limited to 65535)
-struct JpegPixelGroup { uint32_t first, count, max_nblk, max_w, max_h; };      // a run of the table served by one launch per kernel, the grids sized for its largest image
-void LaunchJpegPixelGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);   // JpegIdctKernel, then JpegColorOutKernel
+struct JpegPixelGroup { uint32_t first, count, max_npos, max_w, max_h; };      // a run of the table served by one launch per kernel, the grids sized for its largest image
+void LaunchJpegIdctGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);       // JpegIdctPlanesKernel
+void LaunchJpegColorOutGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);   // JpegColorOutKernel, behind it on the same stream
 void LaunchCopyPlane(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t w, uint32_t h, void* stream);
 // ---- resized output (OutputSpec::resize_w / resize_h): separable antialiased filter (triangle or cubic convolution), horizontal pass then vertical, f32 throughout.
 // One axis' filter as the host built it (decoder.cc ResizeAxis): output index i takes the taps first[i] .. first[i + 1] - 1 of `weight` (normalised, double rounded once to f32)

@@ -153,9 +153,14 @@ Pipeline::Job* Pipeline::FindJob(int64_t ticket) {
 }
 
 int64_t Pipeline::Submit(const uint8_t* const* datas, const size_t* sizes, int n, const OutputSpec& spec, void* const* device_out, void* const* host_out, const size_t* out_capacity,
-                         const OutputSpec* each) {
+                         const OutputSpec* each, bool jpeg_pixels) {
   if (n <= 0 || !datas || !sizes) throw ParseError("JxlHipPipelineSubmit: no images", false);
   if (!device_out == !host_out) throw ParseError("JxlHipPipelineSubmit: exactly one of device_out / host_out must be given", false);
+  if (jpeg_pixels) {
+    bool scaled = spec.downscale != 1;
+    for (int i = 0; each && i < n; i++) scaled |= each[i].downscale != 1;
+    if (scaled) throw ParseError("JxlHipPipelineSubmitJpegPixels: unsupported: libjpeg-exact decode of an output with downscale 8 (libjpeg's scaled IDCTs are other arithmetic)", true);
+  }
   std::shared_ptr<Job> job(new Job());
   job->datas.assign(datas, datas + n); job->sizes.assign(sizes, sizes + n);
   if (device_out) job->device_out.assign(device_out, device_out + n);
@@ -163,6 +168,7 @@ int64_t Pipeline::Submit(const uint8_t* const* datas, const size_t* sizes, int n
   if (out_capacity) job->capacity.assign(out_capacity, out_capacity + n);
   job->spec = spec; job->spec.device_ptr = nullptr;
   if (each) job->each.assign(each, each + n);
+  job->jpeg_pixels = jpeg_pixels;
   job->result.status.assign((size_t)n, 1); job->result.error.assign((size_t)n, std::string());
   std::unique_lock<std::mutex> lock(mu_);
   if (shutdown_) throw ParseError("JxlHipPipelineSubmit: the pipeline is shutting down", false);
@@ -255,10 +261,16 @@ void Pipeline::PrepareJob(Job* j, int worker) {
       size_t need = 0;
       std::string refusal;
       try { need = bt.OutputSizeOf(index[(size_t)i], o); } catch (const ParseError& e) { refusal = e.what(); }     // (a plane_stride this image does not fit, a crop that leaves it: Batch::LayoutRefusal / ResizeRefusal)
+      std::string not_eligible;
       if (!refusal.empty()) {
         // (stays in the batch like an image whose buffer is too small, with a tight plane of its own and no crop, mirror or filter)
         j->result.error[(size_t)i] = refusal;
         o.device_ptr = nullptr; o.plane_stride = 0; o.crop_x0 = o.crop_y0 = o.crop_w = o.crop_h = 0; o.mirror = false; o.resize_filter = 0;
+        j->batch_index[(size_t)i] = -2 - index[(size_t)i];
+      } else if (j->jpeg_pixels && !bt.CanDecodeJpegPixels(index[(size_t)i], &not_eligible)) {
+        // (a libjpeg-exact job: what that decode does not take stays in the batch too and fails with the batch call's reason; nothing is written for it)
+        j->result.error[(size_t)i] = not_eligible;
+        o.device_ptr = nullptr;
         j->batch_index[(size_t)i] = -2 - index[(size_t)i];
       } else if (!j->capacity.empty() && j->capacity[(size_t)i] < need) {
         // (the image stays in the batch — taking it out would renumber the others — and decodes into a buffer of the batch's own; it is reported as failed)
@@ -285,9 +297,24 @@ void Pipeline::PrepareJob(Job* j, int worker) {
     // milliseconds behind other streams' entropy kernels)
     void* side = lf_side_[(size_t)(j->ticket % (int64_t)lf_side_.size())];
     bt.Prepare(side, /*wait_upload=*/false);
+    size_t jpeg_table = 0;
+    if (j->jpeg_pixels) {
+      // the host plan of the libjpeg-exact tail; its table travels on the stream of the LF stage.  What Prepare alone could tell (the quantisation table of a
+      // one-group frame, a block grid that does not hold the image) fails its image here.
+      jpeg_table = bt.PlanJpegPixels();
+      for (int i = 0; i < n; i++) {
+        const int bi = index[(size_t)i];
+        if (bi < 0 || j->batch_index[(size_t)i] < 0) continue;
+        const Batch::JpegPixelResult* r = bt.jpeg_pixel_result(bi);
+        if (r && !r->error.empty()) { j->result.error[(size_t)i] = r->error; j->batch_index[(size_t)i] = -2 - bi; }
+      }
+      bt.EnqueueJpegPixelTable(side, /*fail_refused=*/true);
+    }
     t_prep = std::chrono::steady_clock::now();
     {
       std::lock_guard<std::mutex> lock(mu_);
+      last_info_["jpeg_pixel_images"] = (int64_t)jpeg_table;
+      last_info_["jpeg_pixel_launches"] = 2 * (int64_t)((jpeg_table + kJpegPixelGroupMax - 1) / kJpegPixelGroupMax);
       want_big_ = std::max(want_big_, bt.big_bytes_wanted()); want_coef_ = std::max(want_coef_, bt.coef_bytes_wanted());
       if (!bt.uses_shared_big() || !bt.uses_shared_coef()) private_plane_jobs_++;
       bt.StageBytes(last_stage_bytes_);
@@ -314,7 +341,9 @@ void Pipeline::PrepareJob(Job* j, int worker) {
     bt.RunPart(side, 5, opt_.timed != 0);           // LF decode + varblock placement: all the HF stage waits for
     Record(s.lf_done, side);
     if (j->wide_chain) { { std::lock_guard<std::mutex> lock(mu_); wide_enqueued_ = std::max(wide_enqueued_, j->ticket); } cv_.notify_all(); }
-    bt.RunPart(side, 6, opt_.timed != 0);           // LF post-processing: needed by the IDCT only
+    // LF post-processing: needed by the float IDCT and the filters only — the libjpeg-exact tail reads lfq, the coefficient planes, block info and offsets, the
+    // chroma-from-luma maps: nothing LfDequantKernel, LfSmoothKernel, LlfSigmaKernel or LlfKernel write (lf, lf_tmp, llf, inv_sigma)
+    bt.RunPart(side, j->jpeg_pixels ? 11 : 6, opt_.timed != 0);
     Record(s.front_done, side);
   } catch (const std::exception& e) {
     j->job_error = e.what();
@@ -350,9 +379,9 @@ void Pipeline::IssueTail(Job* j) {
     try {
       StreamWait(main_, s.hf_done);
       StreamWait(main_, s.front_done);
-      bt.RunPart(main_, 7, opt_.timed != 0);      // IDCT: the last stage that touches the coefficient set
+      bt.RunPart(main_, j->jpeg_pixels ? 9 : 7, opt_.timed != 0);      // IDCT (float, or the integer one over the HF planes): the last stage that touches the coefficient set, which is clean behind it
       Record(s.idct_done, main_);
-      bt.RunPart(main_, 8, opt_.timed != 0);      // restoration filters, colour, write
+      bt.RunPart(main_, j->jpeg_pixels ? 10 : 8, opt_.timed != 0);     // restoration filters, colour, write (libjpeg-exact jobs: chroma upsampling, colour, write); resizes
       Record(s.rest_done, main_);
       void* d2h = d2h_[0];
       StreamWait(d2h, s.rest_done);
@@ -430,7 +459,7 @@ void Pipeline::Harvest(Job* j) {
   bool readback_ok = false;
   vec<uint32_t> st;
   if (j->job_error.empty()) {
-    try { bt.HarvestStatus(&st); readback_ok = true; } catch (const std::exception& e) { j->job_error = e.what(); }
+    try { bt.HarvestStatus(&st); if (j->jpeg_pixels) bt.HarvestJpegPixels(st); readback_ok = true; } catch (const std::exception& e) { j->job_error = e.what(); }
   }
   if (j->done_event) {
     (void)hipEventSynchronize((hipEvent_t)j->done_event);
@@ -452,7 +481,9 @@ void Pipeline::Harvest(Job* j) {
     for (int u = bt.first_unit_of(bi); u < bt.first_unit_of(bi) + bt.num_units_of(bi); u++) bad |= st[(size_t)u];
     if (bad) {
       j->result.status[i] = 1;
-      j->result.error[i] = (bad & kErrUnsupported) ? "unsupported: stream feature on the device path" : "corrupt stream (device status " + std::to_string(bad) + ")";
+      const Batch::JpegPixelResult* jr = j->jpeg_pixels ? bt.jpeg_pixel_result(bi) : nullptr;
+      if (jr && !jr->error.empty()) j->result.error[i] = jr->error;      // (names what JpegIdctPlanesKernel refused: a transform other than DCT8)
+      else j->result.error[i] = (bad & kErrUnsupported) ? "unsupported: stream feature on the device path" : "corrupt stream (device status " + std::to_string(bad) + ")";
     } else j->result.status[i] = 0;
   }
   static const bool trace = getenv("JXL_HIP_SCHED_TRACE") != nullptr;
@@ -469,6 +500,7 @@ void Pipeline::Harvest(Job* j) {
   {
     std::lock_guard<std::mutex> lock(mu_);
     if (readback_ok) last_info_["hf_nonzeros"] = bt.Info("hf_nonzeros");
+    if (readback_ok) { last_info_["jpeg_pixel_images"] = j->jpeg_pixels ? bt.Info("jpeg_pixel_images") : 0; last_info_["jpeg_pixel_launches"] = j->jpeg_pixels ? bt.Info("jpeg_pixel_launches") : 0; }
     j->state = kHarvested;
   }
   cv_.notify_all();

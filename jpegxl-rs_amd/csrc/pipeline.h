@@ -57,16 +57,18 @@ class Pipeline {
   // as the image's output in that format (out_capacity[i], when given, is checked).  Host destinations should be pinned (hipHostMalloc / JxlHipHostAlloc) — pageable
   // memory works, slower.  The compressed bytes and the destinations must stay valid until Wait(ticket) returns.  Blocks while `in_flight` jobs are on their way.
   // Returns the job's ticket (>= 0).
+  // jpeg_pixels: a libjpeg-exact job (Batch::DecodeJpegPixels as pipeline stages) — every image is decoded to the samples libjpeg gives for the JPEG file it was
+  // transcoded from; an image Batch::CanDecodeJpegPixels refuses fails alone with that reason.  `spec` and `each` mean what they mean otherwise; downscale 8 is refused here.
   // each (optional, n entries): image i is decoded to each[i] instead of `spec` — same format, layout, downscale and target size as `spec`; crop, filter and mirror are its own.
   int64_t Submit(const uint8_t* const* datas, const size_t* sizes, int n, const OutputSpec& spec, void* const* device_out, void* const* host_out, const size_t* out_capacity,
-                 const OutputSpec* each = nullptr);
+                 const OutputSpec* each = nullptr, bool jpeg_pixels = false);
   // Waits until job `ticket` has left the GPU (outputs written, host copies done) and hands out its per-image results; a ticket can be waited for once.
   void Wait(int64_t ticket, PipelineJobResult* out);
   void WaitAll();                                  // every job submitted so far has left the GPU (results stay collectable)
   void ResetClock();                               // end_ms of later jobs counts from here (call on an idle pipeline)
   StageTimes CollectTimes(int* runs);              // per-stage HIP-event sums over all jobs since the last call (options.timed)
   void StageBytes(uint64_t out[6]);                // algorithmic bytes per stage of the job prepared last
-  int64_t Info(const char* name);                  // "device_bytes", "jobs", "shared_big_bytes", "shared_coef_bytes", "private_plane_jobs", batch infos of the last job ("hf_nonzeros", "lf_simt_frames" ...)
+  int64_t Info(const char* name);                  // "device_bytes", "jobs", "shared_big_bytes", "shared_coef_bytes", "private_plane_jobs", "jpeg_pixel_images", "jpeg_pixel_launches" (of the job prepared or finished last), batch infos of the last job ("hf_nonzeros", "lf_simt_frames" ...)
   double prepare_seconds_total() const { return prepare_s_total_; }
   int64_t prepared_jobs() const { return prepared_jobs_; }
   int device() const { return device_; }
@@ -79,6 +81,7 @@ class Pipeline {
     std::vector<void*> device_out, host_out; std::vector<size_t> capacity;
     OutputSpec spec;
     std::vector<OutputSpec> each;              // per image, when the job was submitted with specs of its own (empty: `spec` for all)
+    bool jpeg_pixels = false;                  // a libjpeg-exact job: the tail is the integer IDCT over the HF planes + libjpeg's upsampling and colour conversion
     std::vector<int> batch_index;              // per image: index in the batch, -1 = failed before it got there
     PipelineJobResult result;
     std::string job_error;                     // the whole job failed (Prepare threw)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Milliseconds per batch and Mpixel/s of the three ways from a batch of JPEG transcodes to the pixels of the original JPEG files.
+"""Milliseconds per batch and Mpixel/s of the ways from a batch of JPEG transcodes to the pixels of the original JPEG files.
 
 Input: --files baseline 4:2:0 JPEGs of --width x --height, written at run time by Pillow from tests/jpeg_cases.photo (--distinct different pictures, cycled) and
 turned into JPEG XL by tests/jpeg_tools.transcode.  Output of the two device legs: u8 RGB in device memory (one caller-owned buffer per image).  Legs (--legs):
@@ -9,6 +9,10 @@ turned into JPEG XL by tests/jpeg_tools.transcode.  Output of the two device leg
                decode_jpeg_pixels existed.  It runs nothing of the new interface: with PYTHONPATH pointing at a build of an earlier commit the same script measures that build
   reconstruct  what a user needs without the new call to get libjpeg's samples: reconstruct_jpegs(), the files fetched to the host, Pillow decoding them on --threads
                host threads (reported whole and in its two parts)
+  pipeline     --jobs jobs of the same --files transcodes through Pipeline.submit(jpeg_pixels=True), all submitted before the first wait: the entropy stages of later jobs
+               overlap the integer pixel path of earlier ones.  ms_per_batch is the wall time from the first submit to the last wait over --jobs; "stages_ms_per_job" are
+               the pipeline's own HIP-event brackets (the `timed` option, JxlHipPipelineCollectTimes) per job: the largest of them is the step of the schedule
+  pipeline_float  the same jobs without jpeg_pixels: libjxl's rendering through the float tail — what a loader of these files gets from a Pipeline otherwise
 
 Every leg runs --reps times after --warmup; the median is reported.  The first run of a leg is checked: pixels and reconstruct equal Pillow's decode of the source
 file exactly, decode is reported with its largest difference from it.  Prints one JSON line.
@@ -44,6 +48,7 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--legs", default="pixels,decode,reconstruct")
     ap.add_argument("--cache", default=None)
+    ap.add_argument("--jobs", type=int, default=6, help="pipeline legs: jobs per repetition")
     args = ap.parse_args()
     import numpy as np
     from PIL import Image
@@ -116,6 +121,38 @@ def main():
             if leg == "pixels":
                 out[leg]["pixel_launches"] = b.info_value("jpeg_pixel_launches")
             del b, bufs
+        elif leg in ("pipeline", "pipeline_float"):
+            exact = leg == "pipeline"
+            if exact and "jpeg_pixels" not in jx.Pipeline.submit.__code__.co_varnames:
+                out[leg] = "this build has no Pipeline.submit(jpeg_pixels=True)"
+                continue
+            p = jx.Pipeline(0, timed=1, reserve_frames=args.files, reserve_width=w, reserve_height=h)
+            bufs = [[torch.zeros(w * h * 3, dtype=torch.uint8, device="cuda:0") for _ in inputs] for _ in range(min(args.jobs, 3))]
+            kw = dict(jpeg_pixels=True) if exact else {}
+            stages = None
+            for r in range(args.warmup + args.reps):
+                if r == args.warmup:
+                    p.collect_times()                      # (the brackets of the warm-up jobs are dropped)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                tickets = [p.submit(inputs, "uint8", 3, device_ptrs=[t.data_ptr() for t in bufs[k % len(bufs)]], **kw) for k in range(args.jobs)]
+                for t in tickets:
+                    st, _ = p.wait(t)
+                    assert st == [0] * len(inputs), st
+                torch.cuda.synchronize()
+                times.append((time.perf_counter() - t0) * 1e3 / args.jobs)
+                if r == 0:
+                    got = [bufs[0][k].cpu().numpy().reshape(h, w, 3) for k in range(args.distinct)]
+                    diff = max(int(np.abs(g.astype(int) - x.astype(int)).max()) for g, x in zip(got, want))
+                    assert not exact or diff == 0, "pixels differ from Pillow's decode of the source files"
+            st, runs = p.collect_times()
+            stages = {k: round(v / max(runs, 1), 2) for k, v in st.items()}
+            out[leg] = report(times)
+            out[leg].update(jobs_per_rep=args.jobs, max_difference_from_pillow=diff, stages_ms_per_job=stages, timed_jobs=runs, private_plane_jobs=p.info("private_plane_jobs"))
+            if exact:
+                out[leg]["pixel_launches"] = p.info("jpeg_pixel_launches")
+            p.close()
+            del p, bufs
         elif leg == "reconstruct":
             parts = []
             pool = ThreadPoolExecutor(args.threads)

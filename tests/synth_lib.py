@@ -171,6 +171,21 @@ def palette(begin_c, num_c, nb_colors, nb_deltas=0, predictor=0):
     return (1, int(begin_c), int(num_c), int(nb_colors), int(nb_deltas), int(predictor))
 
 
+def squeeze(steps=None):
+    """Transform entries of encode_modular_scripted (a LIST: add it to the others): one Squeeze transform, either explicit steps
+    (horizontal, in_place, begin_c, num_c) or, with steps=None, the default chain the decoder derives from the channel list"""
+    if steps is None:
+        return [(2, 0, 0, 0, 0, 0)]
+    assert len(steps) >= 1 and all(n >= 1 for _, _, _, n in steps)
+    return [(2, int(b), int(n), int(bool(hz)), int(bool(ip)), 1 if k else 0) for k, (hz, ip, b, n) in enumerate(steps)]
+
+
+def wp_header(p1=16, p2=10, p3=(7, 7, 7, 0, 0), w=(13, 12, 12, 12)):
+    """Weighted-predictor header of encode_modular_scripted (None there: the stream says "all default")"""
+    assert len(p3) == 5 and len(w) == 4
+    return dict(p1=int(p1), p2=int(p2), p3=tuple(int(v) for v in p3), w=tuple(int(v) for v in w))
+
+
 def split(prop, value, left, right):
     """Tree node of encode_modular_scripted: property > value ? node `left` : node `right`"""
     return (int(prop), int(value), int(left), int(right), 0)
@@ -182,11 +197,12 @@ def leaf(predictor=0, offset=0, mul_log=0, mul_bits=0):
 
 
 def encode_modular_scripted(w, h, planes, bits=8, nchan=3, has_alpha=False, group_shift=1, global_transforms=(), local_transforms=(), tree=(leaf(),),
-                            local_tree=False):
+                            local_tree=False, global_wp=None, section_wp=None):
     """Scripted Modular stream (tools/synth_script.h): nothing is random and nothing is simulated — the caller decides everything.
     bits: 2, 8, 12 or 16; nchan: 1 or 3; group_shift 0..3 (groups of 128 << shift samples a side).
-    global_transforms: up to 4 of rct() / palette(), in stream order (= the order an encoder applies them; a decoder undoes them last to first); begin_c
-      counts meta channels, as the format does.
+    global_wp / section_wp: wp_header() of the GlobalModular stream / of every section stream (None: default); the two may differ.
+    global_transforms: rct() / palette() entries and squeeze() lists (Squeeze: images of at most one group only), in stream order (= the order an encoder
+      applies them; a decoder undoes them last to first); begin_c counts meta channels, as the format does.
     local_transforms: up to 4, written into EVERY section stream.  RCT and plain palettes only: the GPU decoder's section parser takes no Squeeze, no palette
       with nb_deltas > 0 or a predictor, no palette over (local) meta channels, at most 8 channels before and 12 after the transforms; the writer refuses the
       same.  They need an image of more than one group.
@@ -196,7 +212,7 @@ def encode_modular_scripted(w, h, planes, bits=8, nchan=3, has_alpha=False, grou
       section carries come first (every meta channel, then every channel that fits a group); for the others, what the local transforms make of them — local
       meta channels (one plane, the same in every section), then planes of the image's size.  Planes that do not match the derived list are refused with a message."""
     L = lib()
-    L.jxlsynth_modular_scripted.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,
+    L.jxlsynth_modular_scripted2.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,
                                             C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
 
     def flat(rows, n):
@@ -206,14 +222,37 @@ def encode_modular_scripted(w, h, planes, bits=8, nchan=3, has_alpha=False, grou
     keep = [np.ascontiguousarray(np.asarray(p), dtype=np.int32) for p in planes]
     for p, q in zip(planes, keep):
         assert np.asarray(p).ndim == 2 and np.array_equal(np.asarray(p), q), "planes are 2-D arrays of int32 values"
+    wps = []
+    for q in (global_wp, section_wp):
+        wps += [0] + [16, 10, 7, 7, 7, 0, 0, 13, 12, 12, 12] if q is None else [1, q["p1"], q["p2"], *q["p3"], *q["w"]]
     hdr = (C.c_int32 * 7)(w, h, bits, nchan, 1 if has_alpha else 0, group_shift, 1 if local_tree else 0)
+    wps = (C.c_int32 * 24)(*wps)
     ptrs = (C.c_void_p * max(1, len(keep)))(*[p.ctypes.data for p in keep])
     dims = flat([(p.shape[1], p.shape[0]) for p in keep], 2)
     out = C.c_void_p(); n = C.c_size_t()
-    if L.jxlsynth_modular_scripted(hdr, flat(global_transforms, 6), len(global_transforms), flat(local_transforms, 6), len(local_transforms), flat(tree, 5), len(tree),
+    if L.jxlsynth_modular_scripted2(hdr, wps, flat(global_transforms, 6), len(global_transforms), flat(local_transforms, 6), len(local_transforms), flat(tree, 5), len(tree),
                                    ptrs, dims, len(keep), C.byref(out), C.byref(n)):
         raise RuntimeError(L.jxlsynth_last_error().decode())
     return _take(out, n)
+
+
+def lf_residuals(planes, shape):
+    """The synthesiser's LF tokeniser (the ModularTokens that frame encoding calls) on three equally sized int32 planes as one stream, under the LF subtree for
+    LF tree shape 1 or 2 with that shape's predictor parameters -> (3, h, w) int64: the signed residual every token carries"""
+    L = lib()
+    L.jxlsynth_lf_residuals.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]
+    keep = [np.ascontiguousarray(np.asarray(p), dtype=np.int32) for p in planes]
+    assert len(keep) == 3 and keep[0].ndim == 2 and all(p.shape == keep[0].shape for p in keep)
+    h, w = keep[0].shape
+    out = np.zeros((3, h, w), np.int32)
+    ptrs = (C.c_void_p * 3)(*[p.ctypes.data for p in keep])
+    set_lf_tree_shape(shape)
+    try:
+        if L.jxlsynth_lf_residuals(ptrs, w, h, out.ctypes.data):
+            raise RuntimeError(L.jxlsynth_last_error().decode())
+    finally:
+        set_lf_tree_shape(0)
+    return out.astype(np.int64)
 
 
 def set_icc(icc: bytes = b""):

@@ -1960,13 +1960,22 @@ int jxlsynth_modular_free(const jxlsynth_free_params* pp, uint8_t** out, size_t*
 }
 // Scripted Modular stream (tools/synth_script.h): the caller decides the transforms, the MA tree and the value of every token.
 // hdr: {w, h, bits, nchan, has_alpha, group_shift, local_tree};  gt / lt: 6 ints per transform {id, begin_c, a, b, c, d} (id 0 RCT: a = rct_type; id 1 palette:
-// a = num_c, b = nb_colors, c = nb_deltas, d = predictor);  nodes: 5 ints per node, node 0 the root — inner {property, split, left (property > split), right, 0},
+// a = num_c, b = nb_colors, c = nb_deltas, d = predictor; id 2: one Squeeze step, see synth_script.h);  nodes: 5 ints per node, node 0 the root — inner {property, split, left (property > split), right, 0},
 // leaf {-1, predictor, offset, mul_log, mul_bits};  planes / dims: the coded channel list and the (w, h) the caller gives each plane.
-int jxlsynth_modular_scripted(const int32_t* hdr, const int32_t* gt, int n_gt, const int32_t* lt, int n_lt, const int32_t* nodes, int n_nodes,
-                              const int32_t* const* planes, const int32_t* dims, int n_planes, uint8_t** out, size_t* n) {
+// jxlsynth_modular_scripted2 adds wp: twice (GlobalModular stream, section streams) {custom, p1, p2, p3[5], w[4]} — the weighted-predictor header, custom = 0 "all default" — 24 ints,
+// or NULL: what jxlsynth_modular_scripted writes (both headers default).
+int jxlsynth_modular_scripted2(const int32_t* hdr, const int32_t* wp, const int32_t* gt, int n_gt, const int32_t* lt, int n_lt, const int32_t* nodes, int n_nodes,
+                               const int32_t* const* planes, const int32_t* dims, int n_planes, uint8_t** out, size_t* n) {
   try {
     synth::ScriptParams p;
     p.w = hdr[0]; p.h = hdr[1]; p.bits = hdr[2]; p.nchan = hdr[3]; p.has_alpha = hdr[4]; p.group_shift = hdr[5]; p.local_tree = hdr[6];
+    for (int k = 0; wp && k < 2; k++) {
+      synth::ScriptWp& q = k ? p.swp : p.gwp;
+      const int32_t* v = wp + 12 * k;
+      q.custom = v[0]; q.p1 = v[1]; q.p2 = v[2];
+      for (int i = 0; i < 5; i++) q.p3[i] = v[3 + i];
+      for (int i = 0; i < 4; i++) q.w[i] = v[8 + i];
+    }
     for (int i = 0; i < n_gt; i++) p.global_t.push_back({gt[6 * i], gt[6 * i + 1], gt[6 * i + 2], gt[6 * i + 3], gt[6 * i + 4], gt[6 * i + 5]});
     for (int i = 0; i < n_lt; i++) p.local_t.push_back({lt[6 * i], lt[6 * i + 1], lt[6 * i + 2], lt[6 * i + 3], lt[6 * i + 4], lt[6 * i + 5]});
     for (int i = 0; i < n_nodes; i++) {
@@ -1976,6 +1985,28 @@ int jxlsynth_modular_scripted(const int32_t* hdr, const int32_t* gt, int n_gt, c
     }
     for (int i = 0; i < n_planes; i++) { p.planes.push_back(planes[i]); p.dims.push_back({dims[2 * i], dims[2 * i + 1]}); }
     return finish(synth::EncodeModularScripted(p), out, n);
+  } catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
+int jxlsynth_modular_scripted(const int32_t* hdr, const int32_t* gt, int n_gt, const int32_t* lt, int n_lt, const int32_t* nodes, int n_nodes,
+                              const int32_t* const* planes, const int32_t* dims, int n_planes, uint8_t** out, size_t* n) {
+  return jxlsynth_modular_scripted2(hdr, nullptr, gt, n_gt, lt, n_lt, nodes, n_nodes, planes, dims, n_planes, out, n);
+}
+// The synthesiser's LF tokeniser on planes of the caller's: three w x h planes as ONE stream (an LF group's coefficient stream, stream id 1) through the
+// ModularTokens that frame encoding calls, under the LF subtree of MakeGlobalTree for the current LfTreeShape() (1 or 2) with LfWpParams().
+// out: 3 * w * h signed residuals (the values the tokens carry), channel after channel.
+int jxlsynth_lf_residuals(const int32_t* const* planes, int w, int h, int32_t* out) {
+  try {
+    if (synth::LfTreeShape() != 1 && synth::LfTreeShape() != 2) throw std::runtime_error("lf_residuals: LF tree shape must be 1 or 2");
+    if (w < 1 || h < 1) throw std::runtime_error("lf_residuals: empty planes");
+    std::vector<int> bfs;
+    const synth::GTree gt = synth::MakeGlobalTree(1, &bfs);
+    std::vector<synth::ChanRef> cr;
+    for (int i = 0; i < 3; i++) cr.push_back({planes[i], w, h});
+    std::vector<synth::Token> tok;
+    synth::ModularTokens(gt, bfs[0], cr, 1, tok, synth::LfWpParams());
+    if (tok.size() != (size_t)3 * w * h) throw std::runtime_error("lf_residuals: token count");
+    for (size_t i = 0; i < tok.size(); i++) { const uint32_t v = tok[i].value; out[i] = (v & 1) ? -(int32_t)(v >> 1) - 1 : (int32_t)(v >> 1); }
+    return 0;
   } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
 }

@@ -324,7 +324,8 @@ JxlDecoderStatus JxlHipBatchSetOutputResampled(JxlHipBatch* batch, int index, co
  * JxlHipBatchSetOption("jpeg_device_progressive", 1): progressive files (SOF2) are written by the device too, where every scan is a first DC pass, a DC refinement,
  * a first AC pass or an AC refinement of one component; the default 0 sends progressive files through the host writer, and "jpeg_host_writer" wins over it.
  * JxlHipBatchGetInfo "jpeg_device_images" / "jpeg_host_images": files of the last call written by the device / by the host writer;
- * "jpeg_device_progressive_images": those of the device's files that have at least one progressive scan. */
+ * "jpeg_device_progressive_images": those of the device's files that have at least one progressive scan; "jpeg_gather_launches": launches of the kernel that
+ * gathers the coefficients of all images into the writer's arena (one per 32768 images).  The same as jobs of a pipeline: JxlHipPipelineSubmitJpegs below. */
 int JxlHipBatchCanReconstructJpeg(JxlHipBatch* batch, int index);
 JxlDecoderStatus JxlHipBatchReconstructJpegs(JxlHipBatch* batch, void* hip_stream);
 JxlDecoderStatus JxlHipBatchJpegStatus(const JxlHipBatch* batch, int index);
@@ -448,6 +449,25 @@ int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* pipeline, const uint8_t* c
 int64_t JxlHipPipelineSubmitJpegPixels(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
                                        void* const* host_out, const size_t* out_capacity, const JxlHipOutputLayout* layout /* NULL = interleaved */,
                                        const JxlHipOutputResample* each /* NULL, or n entries of one target size */);
+/* A reconstruction job: the original JPEG file of every image, byte for byte (JxlHipBatchReconstructJpegs above, as stages of the pipeline: the entropy stages run
+ * ahead on the side streams, one gather launch per job moves the coefficients out of the shared coefficient set — which is clean behind it —, and the pack pass, the
+ * copies and the host splice of a job run in the thread that collects it, beside the entropy stages of the jobs behind it).  Such jobs mix freely with plain, 1:8,
+ * resized and libjpeg-exact jobs.  There is no pixel format and there are no destinations: nobody can size a JPEG file from its transcode, so the files stay with
+ * the pipeline until they are collected.  flags: the two switches of the batch call; unknown bits refuse the submission.  An image the batch call refuses fails alone
+ * with that call's reason ("JPEG reconstruction: no jbrd box", ...), and so does an image whose stream is damaged; what a reconstruction job refuses is exactly what
+ * JxlHipBatchReconstructJpegs refuses.  A job in which no image can be reconstructed fails as a whole (every image carries the reason) without touching the GPU.
+ * JxlHipPipelineWaitJpegs waits like JxlHipPipelineWait and also gives the files' sizes (jpeg_sizes[i], n entries, optional; 0: no file); it keeps the files until
+ * JxlHipPipelineReleaseJpegs(ticket), after which the ticket is unknown.  On a ticket of another kind it is an error of the call, and that ticket stays waitable.
+ * Between the two, JxlHipPipelineJpegStatus(ticket, i) is JXL_DEC_SUCCESS or JXL_DEC_ERROR with that image's reason in JxlHipLastError(), and JxlHipPipelineCopyJpeg
+ * copies image i's file (refused if `capacity` is smaller than the file).  JxlHipPipelineWait on a reconstruction ticket gives the statuses and releases the files.
+ * A finished reconstruction job that nobody waits for, or that is never released, holds its files until the pipeline's bounded history of uncollected jobs drops it. */
+#define JXL_HIP_JPEG_DEVICE_PROGRESSIVE 1u   /* batch option jpeg_device_progressive */
+#define JXL_HIP_JPEG_HOST_WRITER        2u   /* batch option jpeg_host_writer; wins */
+int64_t JxlHipPipelineSubmitJpegs(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, uint32_t flags);
+JxlDecoderStatus JxlHipPipelineWaitJpegs(JxlHipPipeline* pipeline, int64_t ticket, int* image_status, size_t* jpeg_sizes, int n, float* end_ms);
+JxlDecoderStatus JxlHipPipelineJpegStatus(JxlHipPipeline* pipeline, int64_t ticket, int i);
+JxlDecoderStatus JxlHipPipelineCopyJpeg(JxlHipPipeline* pipeline, int64_t ticket, int i, void* dst, size_t capacity);
+void JxlHipPipelineReleaseJpegs(JxlHipPipeline* pipeline, int64_t ticket);
 /* Waits until the job has left the GPU (pixels written, host copies done).  image_status[i] (n entries, optional): 0 decoded, 1 failed; *end_ms (optional): when the
  * job's last byte was written, ms after JxlHipPipelineResetClock.  JXL_DEC_SUCCESS if every image decoded, else JXL_DEC_ERROR (JxlHipLastError names the first).
  * A ticket can be waited for once; jobs complete in submission order. */
@@ -459,8 +479,9 @@ void JxlHipPipelineStageBytes(JxlHipPipeline* pipeline, uint64_t out[6]);   /* a
 /* "jobs", "slots", "coefficient_sets", "device_bytes", "shared_big_bytes", "shared_coef_bytes", "private_plane_jobs" (jobs that did not fit the shared planes),
  * "prepare_us_total" / "prepared_jobs" (host time of the prepare threads since the last clock reset), and of the job prepared / finished last: "frames",
  * "compressed_bytes", "total_pixels", "hf_nonzeros", "lf_simt_frames", "lf_legacy_frames", "lf_simt_wp", "jpeg_pixel_images" (images of a libjpeg-exact job that took
- * that path; after the job has finished: that were decoded; 0 for a plain job), "jpeg_pixel_launches" (launches of its two pixel kernels: two per 32768 such images).
- * -1: unknown name. */
+ * that path; after the job has finished: that were decoded; 0 for a plain job), "jpeg_pixel_launches" (launches of its two pixel kernels: two per 32768 such images);
+ * of the job finished last, 0 unless it was a reconstruction job: "jpeg_device_images", "jpeg_host_images", "jpeg_device_progressive_images" (as JxlHipBatchGetInfo),
+ * "jpeg_gather_launches" (launches of the gather kernel: one per 32768 images).  -1: unknown name. */
 int64_t JxlHipPipelineGetInfo(JxlHipPipeline* pipeline, const char* name);
 /* Pinned host memory for host_out destinations (hipHostMalloc / hipHostFree). */
 void* JxlHipHostAlloc(size_t bytes);

@@ -35,6 +35,7 @@ JXL_NATIVE_ENDIAN, JXL_LITTLE_ENDIAN, JXL_BIG_ENDIAN = 0, 1, 2
  JXL_DEC_JPEG_NEED_MORE_OUTPUT, JXL_DEC_BOX_NEED_MORE_OUTPUT) = 0, 1, 2, 3, 5, 6, 7
 JXL_DEC_BASIC_INFO, JXL_DEC_COLOR_ENCODING, JXL_DEC_PREVIEW_IMAGE, JXL_DEC_FRAME = 0x40, 0x100, 0x200, 0x400
 JXL_DEC_FULL_IMAGE, JXL_DEC_JPEG_RECONSTRUCTION, JXL_DEC_BOX, JXL_DEC_FRAME_PROGRESSION, JXL_DEC_BOX_COMPLETE = 0x1000, 0x2000, 0x4000, 0x8000, 0x10000
+JXL_HIP_JPEG_DEVICE_PROGRESSIVE, JXL_HIP_JPEG_HOST_WRITER = 1, 2      # flags of JxlHipPipelineSubmitJpegs
 
 
 class JxlPixelFormat(C.Structure):
@@ -207,6 +208,10 @@ def libjxl():
             "JxlHipPipelineCreate": (vp, [C.c_int, C.POINTER(JxlHipPipelineOptions)]), "JxlHipPipelineDestroy": (None, [vp]),
             "JxlHipPipelineSubmit": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz)]),
             "JxlHipPipelineWait": (C.c_int, [vp, C.c_int64, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float)]),
+            "JxlHipPipelineSubmitJpegs": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.c_uint32]),
+            "JxlHipPipelineWaitJpegs": (C.c_int, [vp, C.c_int64, C.POINTER(C.c_int), C.POINTER(sz), C.c_int, C.POINTER(C.c_float)]),
+            "JxlHipPipelineJpegStatus": (C.c_int, [vp, C.c_int64, C.c_int]), "JxlHipPipelineCopyJpeg": (C.c_int, [vp, C.c_int64, C.c_int, vp, sz]),
+            "JxlHipPipelineReleaseJpegs": (None, [vp, C.c_int64]),
             "JxlHipPipelineWaitAll": (C.c_int, [vp]), "JxlHipPipelineResetClock": (C.c_int, [vp]),
             "JxlHipPipelineCollectTimes": (C.c_int, [vp, C.POINTER(JxlHipStageTimes), C.POINTER(C.c_int)]),
             "JxlHipPipelineStageBytes": (None, [vp, C.POINTER(C.c_uint64 * 6)]), "JxlHipPipelineGetInfo": (C.c_int64, [vp, C.c_char_p]),
@@ -1064,6 +1069,48 @@ class Pipeline:
         if rc != JXL_DEC_SUCCESS and check:
             raise GenericError(last_error())
         return list(st)[:n], float(end.value)
+
+    # ---- reconstruction jobs (include/jxl_hip.h JxlHipPipelineSubmitJpegs; BatchDecoder.reconstruct_jpegs as pipeline stages)
+    def submit_jpegs(self, datas, progressive_on_device=False, host_writer=False) -> int:
+        """Job of len(datas) JPEG transcodes whose original files are wanted back, byte for byte.  No format and no destinations: the files stay with the pipeline
+        until wait_jpegs(ticket).  progressive_on_device / host_writer: the two switches of BatchDecoder.reconstruct_jpegs (host_writer wins).  An image that
+        cannot be reconstructed fails alone; such jobs mix freely with every other kind of job."""
+        n = len(datas)
+        ptrs = (C.c_char_p * n)(*datas)
+        sizes = (C.c_size_t * n)(*[len(d) for d in datas])
+        flags = (JXL_HIP_JPEG_DEVICE_PROGRESSIVE if progressive_on_device else 0) | (JXL_HIP_JPEG_HOST_WRITER if host_writer else 0)
+        t = libjxl().JxlHipPipelineSubmitJpegs(self._h, ptrs, sizes, n, flags)
+        if t < 0:
+            raise GenericError(last_error())
+        self._keep[t] = (datas, ptrs, sizes, None, None, None, n)
+        return t
+
+    def wait_jpegs(self, ticket: int):
+        """-> (files, errors, end_ms): files[i] is the reconstructed file of image i as bytes, or None; errors[i] is None, or that image's reason.  Releases the ticket."""
+        L = libjxl()
+        n = self._keep[ticket][6] if ticket in self._keep else 0
+        st = (C.c_int * max(1, n))()
+        sizes = (C.c_size_t * max(1, n))()
+        end = C.c_float()
+        rc = L.JxlHipPipelineWaitJpegs(self._h, int(ticket), st, sizes, n, C.byref(end))
+        call_error = last_error() if rc != JXL_DEC_SUCCESS else ""
+        files, errors = [None] * n, [None] * n
+        try:
+            for i in range(n):
+                if st[i] == 0:
+                    out = np.empty(max(int(sizes[i]), 1), dtype=np.uint8)
+                    if L.JxlHipPipelineCopyJpeg(self._h, int(ticket), i, out.ctypes.data, int(sizes[i])) != JXL_DEC_SUCCESS:
+                        raise GenericError(last_error())
+                    files[i] = out[:int(sizes[i])].tobytes()
+                    continue
+                L.JxlHipPipelineJpegStatus(self._h, int(ticket), i)
+                errors[i] = last_error()
+                if "JxlHipPipelineJpegStatus: unknown ticket" in errors[i]:      # (the wait itself failed — a ticket of another kind, an unknown one: nothing was collected)
+                    raise GenericError(call_error or errors[i])
+        finally:
+            L.JxlHipPipelineReleaseJpegs(self._h, int(ticket))
+            self._keep.pop(ticket, None)
+        return files, errors, float(end.value)
 
     def wait_all(self):
         check_dec_status(libjxl().JxlHipPipelineWaitAll(self._h))

@@ -417,6 +417,8 @@ Batch::~Batch() {
   if (flags_pinned_) (void)hipHostFree(flags_pinned_);
   if (status_event_) (void)hipEventDestroy((hipEvent_t)status_event_);
   if (status_pinned_) (void)hipHostFree(status_pinned_);
+  if (jpeg_pinned_) (void)hipHostFree(jpeg_pinned_);
+  for (void* ev : jpeg_copy_event_) if (ev) (void)hipEventDestroy((hipEvent_t)ev);
   Pool().Give(dconst_, const_cap_, device_);
   Pool().Give(dwork_, work_cap_, device_);
   if (djpeg_) Pool().Give(djpeg_, jpeg_cap_, device_);
@@ -520,7 +522,7 @@ bool Batch::DevReserve(void** ptr, size_t* cap, size_t bytes) {
 // Forgets the images (and everything derived from them) but keeps the device arenas, the pinned staging buffer and the sharing set up with
 // ShareBigArena / ShareCoefArena: the batch object can be filled again.  The caller makes sure no decode of the old content is in flight.
 void Batch::Reset() {
-  images_.clear(); pub_.clear(); cbufs_.clear(); post_ops_.clear(); jpeg_data_.clear(); jpeg_pixel_results_.clear(); jpeg_pixel_table_.clear(); jpeg_pixel_table_image_.clear(); jpeg_pixel_groups_.clear(); resize_plans_.clear(); resize_groups_.clear();
+  images_.clear(); pub_.clear(); cbufs_.clear(); post_ops_.clear(); jpeg_data_.clear(); jw_.reset(); jpeg_pixel_results_.clear(); jpeg_pixel_table_.clear(); jpeg_pixel_table_image_.clear(); jpeg_pixel_groups_.clear(); resize_plans_.clear(); resize_groups_.clear();
   frames_host_.clear(); passes_host_.clear(); pass_first_.clear(); local_host_.clear(); local_first_.clear();
   mod_plane_offsets_.clear(); mod_ops_.clear(); vardct_alpha_.clear(); hf_written_.clear();
   // (stage timings recorded so far stay: CollectTimes sums over the object's life)
@@ -1022,6 +1024,7 @@ int64_t Batch::Info(const std::string& name) const {
   if (name == "jpeg_device_images") return jpeg_device_images_;     // images of the last ReconstructJpegs whose scans the device wrote / that went through the host writer
   if (name == "jpeg_host_images") return jpeg_host_images_;
   if (name == "jpeg_device_progressive_images") return jpeg_device_progressive_images_;    // ... of the device's, those with at least one progressive scan
+  if (name == "jpeg_gather_launches") return jpeg_gather_launches_;                        // ... launches of JpegGatherKernel: one per group of the gather table
   if (name == "jpeg_pixel_images") return jpeg_pixel_images_;       // images the last DecodeJpegPixels wrote
   if (name == "jpeg_pixel_launches") return jpeg_pixel_launches_;   // ... launches of its two pixel kernels (two per group of the image table, however many images a group holds)
   if (name == "lf_simt_lanes") return lf_simt_.num_lanes;
@@ -2961,54 +2964,132 @@ bool FillJpegFromFrame(const FramePlan& p, JpegData* jd, JpegFrameGrid* g, std::
   }
   return true;
 }
-struct ScanPlan { JpegHuffTable dc[4], ac[4]; uint32_t restart = 0; bool progressive = false; };
 }  // namespace
 
-// image i's quantised coefficients into JPEG layout (JpegCoefKernel): component planes one after another from `out` on
-void Batch::EnqueueJpegCoefficients(int i, const JpegFrameGrid& g, int16_t* out, void* stream_v) {
-  const int u = pub_[i].first_unit;
-  const FramePlan& p = images_[u]->plan;
-  JpegCoefArgs a;
-  memset(&a, 0, sizeof(a));
-  a.ncomp = g.ncomp;
-  for (uint32_t c = 0; c < g.ncomp; c++) a.comp_off[c] = (uint32_t)g.comp_first[c];
-  for (uint32_t c = 0; c < g.ncomp; c++) for (int k = 0; k < 64; k++) a.qt[c][k] = g.qt[c][k];
-  a.out = out;
-  LaunchJpegCoefficients(dframes_, u, a, p.bw, p.bh, stream_v);
-}
-
-void Batch::ReconstructJpegs(void* stream_v) {
-  hipStream_t stream = (hipStream_t)stream_v;
-  const int n = (int)pub_.size();
-  jpeg_results_.clear(); jpeg_results_.resize((size_t)n);
-  jpeg_device_images_ = jpeg_host_images_ = jpeg_device_progressive_images_ = 0;
+// What the phases of a batch reconstruction share (PlanJpegWrite fills it, the next plan replaces it)
+struct Batch::JpegWriteState {
+  struct ScanPlan { JpegHuffTable dc[4], ac[4]; uint32_t restart = 0; bool progressive = false; };
   struct Img { bool ok = false, device = false, progressive = false; size_t first_blk = 0; JpegFrameGrid grid; size_t first_scan = 0, num_scans = 0; std::vector<ScanPlan> plans; };
-  std::vector<Img> im((size_t)n);
-  bool any = false;
-  for (int i = 0; i < n; i++) {
-    std::string why;
-    if (CanReconstructJpeg(i, &why)) { im[i].ok = true; any = true; } else jpeg_results_[i].error = "JPEG reconstruction: " + why;
-  }
-  if (!any) return;
-  if (!prepared_) Prepare(stream_v);
-  HIP_CHECK(hipSetDevice(device_));
-  // ---- host plan: coefficient planes of every image in one arena; scan table and table snapshots of the images the device writes
-  size_t total_blk = 0;
+  std::vector<Img> im;
   vec<JpegScanDev> scans;
   vec<JpegHuffDev> tables;
   vec<uint32_t> resets;          // reset points of the AC progressive scans, as batch block numbers
-  bool any_progressive = false;
+  bool any_progressive = false, fail_refused = false;
+  bool head_pending = false;     // the raw size and the flag words are on their way to (or in) pinned memory: EnqueueJpegHeadReadback
   uint64_t num_blocks = 0, num_segs = 0;
+  size_t total_blk = 0, images_ok = 0;
+  size_t o_coef = 0, o_scans = 0, o_tables = 0, o_flags = 0, o_resets = 0, o_gather = 0, arena_bytes = 0;
+  size_t o_bits = 0, o_bitpos = 0, o_segbits = 0, o_segbytes = 0, o_segoff = 0, o_tile = 0, o_meta = 0, o_flush = 0, o_spanidx = 0, o_spanfirst = 0;
+  JpegWritePlan wp;              // device pointers: valid from EnqueueJpegPlan on
+  vec<JpegPixelImage> gather;    // the gather table (host copy; the upload reads it), the image of every entry, the launch groups over it
+  vec<int> gather_image;
+  std::vector<JpegPixelGroup> groups;
+};
+
+// Pinned staging of the reconstruction's copies to the host: a head of `head` bytes (the raw size and the per-image flag words: 8 + 4 n) and two chunks of
+// kJpegStageChunk bytes behind it, which CopyJpegToHost fills in turn.  Small and of a fixed size — pinning memory costs about as much per byte as copying it, and a
+// pipeline has a batch object per slot —; it only grows with the number of images (hipHostFree waits for the device).
+static constexpr size_t kJpegStageChunk = (size_t)4 << 20;
+uint8_t* Batch::JpegPinned(size_t head) {
+  const size_t head_cap = (std::max<size_t>(head, 4096) + 4095) & ~(size_t)4095, bytes = head_cap + 2 * kJpegStageChunk;
+  if (jpeg_pinned_ && jpeg_pinned_cap_ >= bytes) return jpeg_pinned_;
+  if (jpeg_pinned_) (void)hipHostFree(jpeg_pinned_);
+  jpeg_pinned_ = nullptr; jpeg_pinned_cap_ = 0;
+  const size_t cap = 2 * head_cap + 2 * kJpegStageChunk;
+  HIP_CHECK(hipHostMalloc((void**)&jpeg_pinned_, cap));
+  jpeg_pinned_cap_ = cap;
+  return jpeg_pinned_;
+}
+// `bytes` from device memory into pageable host memory, on `stream`: hipMemcpyAsync into the two pinned chunks in turn, the host copying chunk k - 1 out while chunk k
+// is on its way; waits for the last one.  (Not hipMemcpy: that goes through the null stream and would stall the streams of a pipeline's other jobs.)
+void Batch::CopyJpegToHost(void* dst_v, const void* src_v, size_t bytes, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  uint8_t* dst = (uint8_t*)dst_v;
+  const uint8_t* src = (const uint8_t*)src_v;
+  if (!jpeg_pinned_ || jpeg_pinned_cap_ < 2 * kJpegStageChunk) throw ParseError("CopyJpegToHost without staging", false);
+  uint8_t* chunk[2] = {jpeg_pinned_ + jpeg_pinned_cap_ - 2 * kJpegStageChunk, jpeg_pinned_ + jpeg_pinned_cap_ - kJpegStageChunk};
+  for (int k = 0; k < 2; k++) if (!jpeg_copy_event_[k]) { hipEvent_t ev; HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); jpeg_copy_event_[k] = ev; }
+  size_t prev_off = 0, prev_len = 0;
+  int k = 0;
+  for (size_t off = 0; off < bytes; off += kJpegStageChunk, k ^= 1) {
+    const size_t len = std::min(kJpegStageChunk, bytes - off);
+    HIP_CHECK(hipMemcpyAsync(chunk[k], src + off, len, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipEventRecord((hipEvent_t)jpeg_copy_event_[k], stream));
+    if (prev_len) { HIP_CHECK(hipEventSynchronize((hipEvent_t)jpeg_copy_event_[k ^ 1])); memcpy(dst + prev_off, chunk[k ^ 1], prev_len); }
+    prev_off = off; prev_len = len;
+  }
+  if (prev_len) { HIP_CHECK(hipEventSynchronize((hipEvent_t)jpeg_copy_event_[k ^ 1])); memcpy(dst + prev_off, chunk[k ^ 1], prev_len); }
+}
+
+// ---- phase 1, host only (after Prepare): which images can be reconstructed, the coefficient planes of all of them in one arena, the gather table over it, and — for the
+// images the device writes — scan table, table snapshots and reset points.  An image that cannot be reconstructed gets its jpeg_result now.  Returns the images left.
+size_t Batch::PlanJpegWrite() {
+  const int n = (int)pub_.size();
+  jpeg_results_.clear(); jpeg_results_.resize((size_t)n);
+  jpeg_device_images_ = jpeg_host_images_ = jpeg_device_progressive_images_ = 0;
+  jpeg_gather_launches_ = 0;
+  jw_ = std::make_shared<JpegWriteState>();
+  JpegWriteState& w = *jw_;
+  typedef JpegWriteState::Img Img;
+  typedef JpegWriteState::ScanPlan ScanPlan;
+  memset(&w.wp, 0, sizeof(w.wp));
+  w.im.resize((size_t)n);
+  std::vector<Img>& im = w.im;
+  for (int i = 0; i < n; i++) {
+    std::string why;
+    if (CanReconstructJpeg(i, &why)) im[i].ok = true; else jpeg_results_[i].error = "JPEG reconstruction: " + why;
+  }
+  if (!prepared_) throw ParseError("PlanJpegWrite: the batch is not prepared", false);
+  // ---- coefficient planes of every image in one arena; scan table and table snapshots of the images the device writes
+  size_t& total_blk = w.total_blk;
+  vec<JpegScanDev>& scans = w.scans;
+  vec<JpegHuffDev>& tables = w.tables;
+  vec<uint32_t>& resets = w.resets;
+  bool& any_progressive = w.any_progressive;
+  uint64_t& num_blocks = w.num_blocks;
+  uint64_t& num_segs = w.num_segs;
   for (int i = 0; i < n; i++) {
     Img& m = im[i];
     if (!m.ok) continue;
-    const ImageEntry& e = *images_[pub_[i].first_unit];
+    const int unit = pub_[i].first_unit;
+    const ImageEntry& e = *images_[unit];
+    const FramePlan& p = e.plan;
     JpegData& jd = *jpeg_data_[i];
     std::string why;
-    if (!FillJpegFromFrame(e.plan, &jd, &m.grid, &why)) { m.ok = false; jpeg_results_[i].error = why; continue; }
+    if (!FillJpegFromFrame(p, &jd, &m.grid, &why)) { m.ok = false; jpeg_results_[i].error = why; continue; }
     // (the tables as the file's components refer to them: components that share a table slot share the table)
     for (size_t c = 0; c < jd.components.size(); c++) for (int k = 0; k < 64; k++) m.grid.qt[c][k] = jd.quant[jd.components[c].quant_idx].values[k];
+    {
+      // the gather's entry.  Every address of the kernel follows from it and the frame's own block grid: the component grids must lie inside the frame's, the planes
+      // that are read must exist
+      const JpegFrameGrid& g = m.grid;
+      const FrameDev& f = frames_host_[unit];
+      const uint32_t ncomp = g.ncomp;
+      bool fits = (total_blk + g.nblk) < ((size_t)1 << 31) && !f.lf_only && f.coef_off && f.blk_info && f.status;
+      bool walk = ncomp == 3;
+      for (uint32_t c = 0; c < ncomp && fits; c++) {
+        const int chn = ncomp == 1 ? 1 : (c == 0 ? 1 : c == 1 ? 0 : 2);
+        fits = g.grid_w[c] && g.grid_h[c] && g.grid_w[c] <= p.bw && g.grid_h[c] <= p.bh && g.hs[c] < 8 && g.vs[c] < 8 && f.coeff[chn] && f.lfq[chn];
+        if (g.hs[c] | g.vs[c]) walk = false;          // 4:4:4 colour: chroma from luma, one position per block of the frame
+      }
+      if (walk) fits = fits && f.ytox && f.ytob;
+      if (!fits) { m.ok = false; jpeg_results_[i].error = "JPEG reconstruction: the frame's block grid does not hold the image"; continue; }
+      JpegPixelImage t;
+      memset(&t, 0, sizeof(t));
+      for (uint32_t c = 0; c < ncomp; c++) {
+        t.comp_first[c] = (uint32_t)g.comp_first[c]; t.grid_w[c] = g.grid_w[c]; t.grid_h[c] = g.grid_h[c]; t.comp_hs[c] = g.hs[c]; t.comp_vs[c] = g.vs[c];
+        for (int v = 0; v < 8; v++) for (int h = 0; h < 8; h++) {
+          const int nat = v * 8 + h, tr = h * 8 + v;           // (the kernel reads the ratios beside the coefficients: the planes' transposed layout)
+          t.qt[c][tr] = g.qt[c][nat];
+          if (c && walk) t.cfl_ratio[c - 1][tr] = g.qt[c][nat] != 0 ? (int32_t)((int64_t)2048 * g.qt[0][nat] / g.qt[c][nat]) : 0;
+        }
+      }
+      t.npos = walk ? g.grid_w[0] * g.grid_h[0] : (uint32_t)g.nblk; t.ncomp = ncomp; t.frame = (uint32_t)unit;
+      t.width = e.ih.xsize; t.height = e.ih.ysize; t.hs = ncomp == 3 ? g.hs[1] : 0; t.vs = ncomp == 3 ? g.vs[1] : 0;
+      w.gather.push_back(t); w.gather_image.push_back(i);
+    }
     m.first_blk = total_blk; total_blk += m.grid.nblk;
+    w.images_ok++;
     if (jpeg_host_writer) continue;
     // the marker walk with an emitter that writes nothing: the scans, the tables in force at each
     vec<uint8_t> scratch;
@@ -3091,53 +3172,125 @@ void Batch::ReconstructJpegs(void* stream_v) {
     resets.insert(resets.end(), my_resets.begin(), my_resets.end());
     num_blocks = blocks; num_segs = segs;
   }
-  // ---- arena: coefficients, tables, per-block and per-segment arrays (one allocation per batch object, kept like the other arenas)
+  // ---- the launch groups of the gather table
+  for (size_t first = 0; first < w.gather.size(); first += kJpegPixelGroupMax) {
+    JpegPixelGroup g{(uint32_t)first, (uint32_t)std::min<size_t>(kJpegPixelGroupMax, w.gather.size() - first), 0, 0, 0};
+    for (uint32_t k = 0; k < g.count; k++) g.max_npos = std::max(g.max_npos, w.gather[first + k].npos);
+    w.groups.push_back(g);
+  }
+  // ---- arena: coefficients, tables, gather table, per-block and per-segment arrays (one allocation per batch object, kept like the other arenas)
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_coef = take(total_blk * 128), o_scans = take(scans.size() * sizeof(JpegScanDev)), o_tables = take(tables.size() * sizeof(JpegHuffDev));
-  const size_t o_bits = take(num_blocks * 4), o_bitpos = take((num_blocks + 1) * 8), o_segbits = take(num_segs * 4), o_segbytes = take(num_segs * 4);
-  const size_t o_segoff = take((num_segs + 1) * 8), o_tile = take((std::max(num_blocks, num_segs) / 1024 + 1) * 8), o_flags = take((size_t)n * 4);
+  w.o_coef = take(total_blk * 128); w.o_scans = take(scans.size() * sizeof(JpegScanDev)); w.o_tables = take(tables.size() * sizeof(JpegHuffDev));
+  w.o_bits = take(num_blocks * 4); w.o_bitpos = take((num_blocks + 1) * 8); w.o_segbits = take(num_segs * 4); w.o_segbytes = take(num_segs * 4);
+  w.o_segoff = take((num_segs + 1) * 8); w.o_tile = take((std::max(num_blocks, num_segs) / 1024 + 1) * 8); w.o_flags = take((size_t)n * 4);
   // progressive scans: per-block head / tail, flush flags, span numbers and first blocks, reset points
   const size_t nprog = any_progressive ? num_blocks : 0;
-  const size_t o_meta = take(nprog * 4), o_flush = take(nprog * 4), o_spanidx = take(any_progressive ? (num_blocks + 1) * 8 : 0), o_spanfirst = take(nprog * 4);
-  const size_t o_resets = take(resets.size() * 4);
-  DevReserve((void**)&djpeg_, &jpeg_cap_, std::max<size_t>(off, 256));
-  if (!scans.empty()) {
-    HIP_CHECK(hipMemcpyAsync(djpeg_ + o_scans, scans.data(), scans.size() * sizeof(JpegScanDev), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(djpeg_ + o_tables, tables.data(), tables.size() * sizeof(JpegHuffDev), hipMemcpyHostToDevice, stream));
-    if (!resets.empty()) HIP_CHECK(hipMemcpyAsync(djpeg_ + o_resets, resets.data(), resets.size() * 4, hipMemcpyHostToDevice, stream));
+  w.o_meta = take(nprog * 4); w.o_flush = take(nprog * 4); w.o_spanidx = take(any_progressive ? (num_blocks + 1) * 8 : 0); w.o_spanfirst = take(nprog * 4);
+  w.o_resets = take(resets.size() * 4);
+  w.o_gather = take(w.gather.size() * sizeof(JpegPixelImage));
+  w.arena_bytes = off;
+  return w.images_ok;
+}
+
+// ---- phase 2: the arena, and into it the scan table, the table snapshots, the reset points and the gather table; the flags are cleared.  The host copies stay in the
+// plan, so the uploads may still be on their way when this returns.  fail_refused: as in EnqueueJpegPixelTable, for frames that are not in the gather table.
+void Batch::EnqueueJpegPlan(void* stream_v, bool fail_refused) {
+  if (!jw_) throw ParseError("EnqueueJpegPlan without PlanJpegWrite", false);
+  JpegWriteState& w = *jw_;
+  hipStream_t stream = (hipStream_t)stream_v;
+  const size_t n = pub_.size();
+  HIP_CHECK(hipSetDevice(device_));
+  DevReserve((void**)&djpeg_, &jpeg_cap_, std::max<size_t>(w.arena_bytes, 256));
+  JpegPinned(8 + 4 * n);
+  w.fail_refused = fail_refused;
+  w.head_pending = false;
+  for (size_t k = 0; k < w.gather.size(); k++) w.gather[k].coef_out = (int16_t*)(djpeg_ + w.o_coef) + w.im[(size_t)w.gather_image[k]].first_blk * 64;
+  if (!w.scans.empty()) {
+    HIP_CHECK(hipMemcpyAsync(djpeg_ + w.o_scans, w.scans.data(), w.scans.size() * sizeof(JpegScanDev), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(djpeg_ + w.o_tables, w.tables.data(), w.tables.size() * sizeof(JpegHuffDev), hipMemcpyHostToDevice, stream));
+    if (!w.resets.empty()) HIP_CHECK(hipMemcpyAsync(djpeg_ + w.o_resets, w.resets.data(), w.resets.size() * 4, hipMemcpyHostToDevice, stream));
   }
-  HIP_CHECK(hipMemsetAsync(djpeg_ + o_flags, 0, (size_t)n * 4, stream));
-  // ---- one entropy decode of the batch (LF stage: JPEG DC, block metadata; HF stage: AC), coefficients into JPEG layout
-  RunPart(stream_v, 1, false);
-  RunPart(stream_v, 3, false);
-  for (int i = 0; i < n; i++) {
-    if (!im[i].ok) continue;
-    EnqueueJpegCoefficients(i, im[i].grid, (int16_t*)(djpeg_ + o_coef) + im[i].first_blk * 64, stream_v);
-  }
-  DebugSync("JPEG coefficients", stream_v);
-  JpegWritePlan wp;
+  if (!w.gather.empty()) HIP_CHECK(hipMemcpyAsync(djpeg_ + w.o_gather, w.gather.data(), w.gather.size() * sizeof(JpegPixelImage), hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipMemsetAsync(djpeg_ + w.o_flags, 0, n * 4, stream));
+  JpegWritePlan& wp = w.wp;
   memset(&wp, 0, sizeof(wp));
-  wp.frames = dframes_; wp.scans = (const JpegScanDev*)(djpeg_ + o_scans); wp.tables = (const JpegHuffDev*)(djpeg_ + o_tables); wp.coef = (const int16_t*)(djpeg_ + o_coef);
-  wp.num_scans = (uint32_t)scans.size(); wp.num_blocks = (uint32_t)num_blocks; wp.num_segs = (uint32_t)num_segs;
-  wp.bits = (uint32_t*)(djpeg_ + o_bits); wp.bitpos = (uint64_t*)(djpeg_ + o_bitpos); wp.seg_bits = (uint32_t*)(djpeg_ + o_segbits); wp.seg_bytes = (uint32_t*)(djpeg_ + o_segbytes);
-  wp.seg_off = (uint64_t*)(djpeg_ + o_segoff); wp.tile_tmp = (uint64_t*)(djpeg_ + o_tile); wp.flags = (uint32_t*)(djpeg_ + o_flags);
-  wp.has_spans = any_progressive ? 1 : 0;
-  wp.meta = (uint32_t*)(djpeg_ + o_meta); wp.flush = (uint32_t*)(djpeg_ + o_flush); wp.span_idx = (uint64_t*)(djpeg_ + o_spanidx); wp.span_first = (uint32_t*)(djpeg_ + o_spanfirst);
-  wp.resets = (const uint32_t*)(djpeg_ + o_resets);
-  LaunchJpegSizes(wp, stream_v);
+  wp.frames = dframes_; wp.scans = (const JpegScanDev*)(djpeg_ + w.o_scans); wp.tables = (const JpegHuffDev*)(djpeg_ + w.o_tables); wp.coef = (const int16_t*)(djpeg_ + w.o_coef);
+  wp.num_scans = (uint32_t)w.scans.size(); wp.num_blocks = (uint32_t)w.num_blocks; wp.num_segs = (uint32_t)w.num_segs;
+  wp.bits = (uint32_t*)(djpeg_ + w.o_bits); wp.bitpos = (uint64_t*)(djpeg_ + w.o_bitpos); wp.seg_bits = (uint32_t*)(djpeg_ + w.o_segbits); wp.seg_bytes = (uint32_t*)(djpeg_ + w.o_segbytes);
+  wp.seg_off = (uint64_t*)(djpeg_ + w.o_segoff); wp.tile_tmp = (uint64_t*)(djpeg_ + w.o_tile); wp.flags = (uint32_t*)(djpeg_ + w.o_flags);
+  wp.has_spans = w.any_progressive ? 1 : 0;
+  wp.meta = (uint32_t*)(djpeg_ + w.o_meta); wp.flush = (uint32_t*)(djpeg_ + w.o_flush); wp.span_idx = (uint64_t*)(djpeg_ + w.o_spanidx); wp.span_first = (uint32_t*)(djpeg_ + w.o_spanfirst);
+  wp.resets = (const uint32_t*)(djpeg_ + w.o_resets);
+  if (!fail_refused) return;
+  // nobody consumes the coefficients of a frame that is not in the gather table: with its status word set the entropy stages skip it where they can, and what the HF
+  // stage wrote for it before is zeroed behind that stage (ZeroFailedCoefKernel), like a damaged frame's
+  static const uint32_t kRefused = kErrUnsupported;
+  vec<uint8_t> in_table(images_.size(), 0);
+  for (int i : w.gather_image) in_table[(size_t)pub_[i].first_unit] = 1;
+  for (size_t u = 0; u < images_.size(); u++)
+    if (!in_table[u]) HIP_CHECK(hipMemcpyAsync(dwork_ + status_off_ + u * 4, &kRefused, 4, hipMemcpyHostToDevice, stream));
+}
+
+// ---- phase 3, behind the HF stage: JpegGatherKernel, one launch per group of the table, then ZeroFailedCoefKernel for the frames it failed (kErrVarblock: consumed in
+// part only).  With fail_refused every frame of the batch is either gathered or zeroed whole: the coefficient set is clean behind this.  Without it the planes stay
+// marked dirty (an image may have been ineligible, a frame may fail).  Then the sizes pass of the writer.  Nothing here waits on the host.
+void Batch::EnqueueJpegGather(void* stream_v) {
+  if (!jw_) throw ParseError("EnqueueJpegGather without PlanJpegWrite", false);
+  JpegWriteState& w = *jw_;
+  const JpegPixelImage* dtable = (const JpegPixelImage*)(djpeg_ + w.o_gather);
+  for (const JpegPixelGroup& g : w.groups) { LaunchJpegGatherGroup(dframes_, dtable, g, stream_v); jpeg_gather_launches_++; }
+  if (!w.groups.empty()) LaunchZeroFailedCoefficients(dframes_, (int)images_.size(), stream_v);
+  DebugSync("JPEG coefficients", stream_v);
+  CheckLaunches("JPEG gather");
+  if (w.fail_refused && any_full_vardct_) ClearCoefficientsAfterDecode(stream_v);
+}
+void Batch::EnqueueJpegSizes(void* stream_v) {
+  if (!jw_) throw ParseError("EnqueueJpegSizes without PlanJpegWrite", false);
+  LaunchJpegSizes(jw_->wp, stream_v);
   CheckLaunches("JPEG writer, sizes");
-  vec<uint32_t> status;
-  FinishStatus(stream_v, &status);         // (waits; the kernels above and below skip frames whose status word is set — it is cleared only on the host's copy)
+}
+// The one size the device decides (bytes of all segments before stuffing) and the per-image flag words, to pinned memory behind the sizes pass — for callers that
+// have a copy stream of their own (the pipeline sends them with the status words); FinishJpegWrite fetches them itself otherwise.
+void Batch::EnqueueJpegHeadReadback(void* stream_v) {
+  if (!jw_) throw ParseError("EnqueueJpegHeadReadback without PlanJpegWrite", false);
+  JpegWriteState& w = *jw_;
+  hipStream_t stream = (hipStream_t)stream_v;
+  const size_t n = pub_.size();
+  uint8_t* pin = JpegPinned(8 + 4 * n);
+  memset(pin, 0, 8 + 4 * n);
+  if (w.num_segs) {
+    HIP_CHECK(hipMemcpyAsync(pin, w.wp.seg_off + w.num_segs, 8, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(pin + 8, w.wp.flags, n * 4, hipMemcpyDeviceToHost, stream));
+  }
+  w.head_pending = true;
+}
+
+// ---- phase 4: with the status words of the entropy run (FinishStatus / HarvestStatus) — the raw size and the flags, the pack and stuffing pass sized from them, the
+// stuffed bytes and segment records back, then per image the splice, or the host writer from that image's coefficients.  Every copy is a hipMemcpyAsync on `stream`
+// into pinned staging, followed by a wait for it (CopyJpegToHost): nothing goes through the null stream, which would stall the streams of a pipeline's other jobs.
+void Batch::FinishJpegWrite(void* stream_v, const vec<uint32_t>& status) {
+  if (!jw_) throw ParseError("FinishJpegWrite without PlanJpegWrite", false);
+  JpegWriteState& w = *jw_;
+  typedef JpegWriteState::Img Img;
+  hipStream_t stream = (hipStream_t)stream_v;
+  const int n = (int)pub_.size();
+  const uint64_t num_blocks = w.num_blocks, num_segs = w.num_segs;
+  const JpegWritePlan& wp = w.wp;
+  HIP_CHECK(hipSetDevice(device_));
   vec<uint32_t> flags((size_t)n, 0);
   uint64_t raw_bytes = 0;
   vec<JpegSegDev> recs;
-  vec<uint8_t> stuffed;
+  vec<uint8_t> stuffed_bytes;
+  const uint8_t* stuffed = nullptr;
+  size_t stuffed_size = 0;
   if (num_segs) {
-    // the one size the device decides: bytes of all segments before stuffing.  Everything pass 2 writes is sized from it here, before the launch.
-    HIP_CHECK(hipMemcpy(&raw_bytes, wp.seg_off + num_segs, 8, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(flags.data(), wp.flags, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (!w.head_pending) { EnqueueJpegHeadReadback(stream_v); HIP_CHECK(hipStreamSynchronize(stream)); }
+    w.head_pending = false;
+    memcpy(&raw_bytes, jpeg_pinned_, 8);
+    memcpy(flags.data(), jpeg_pinned_ + 8, (size_t)n * 4);
     if (raw_bytes > num_blocks * 256) throw ParseError("JPEG writer: segment sizes beyond the per-block bound", false);
+    // Everything pass 2 writes is sized from the raw size here, before the launch.
     const uint64_t chunks = (raw_bytes + JpegStuffChunkBytes() - 1) / JpegStuffChunkBytes();
     size_t off2 = 0;
     auto take2 = [&](size_t bytes) { const size_t o = off2; off2 += (bytes + 255) & ~(size_t)255; return o; };
@@ -3147,49 +3300,89 @@ void Batch::ReconstructJpegs(void* stream_v) {
     JpegPackBuffers pb;
     pb.raw = djpeg_out_ + o_raw; pb.raw_bytes = raw_bytes; pb.ff_count = (uint32_t*)(djpeg_out_ + o_ffc); pb.ff_before = (uint64_t*)(djpeg_out_ + o_ffb);
     pb.tile_tmp = (uint64_t*)(djpeg_out_ + o_tile2); pb.stuffed = djpeg_out_ + o_stuffed; pb.stuffed_cap = raw_bytes * 2; pb.recs = (JpegSegDev*)(djpeg_out_ + o_recs);
-    // (FinishStatus cleared the status words of frames that failed: pass 1 gave their blocks zero bits, which keeps pass 2 off them)
+    // (pass 1 gave the blocks of frames that failed zero bits, which keeps pass 2 off them whether or not their status words are still set)
     LaunchJpegPack(wp, pb, stream_v);
     CheckLaunches("JPEG writer, pack");
+    // the stuffing count first (it sizes the copy of the bytes), then the records and the bytes
     uint64_t num_ff = 0;
-    HIP_CHECK(hipStreamSynchronize(stream));
-    HIP_CHECK(hipMemcpy(&num_ff, pb.ff_before + chunks, 8, hipMemcpyDeviceToHost));
+    CopyJpegToHost(&num_ff, pb.ff_before + chunks, 8, stream_v);
     if (num_ff > raw_bytes) throw ParseError("JPEG writer: stuffing count beyond the buffer", false);
-    recs.resize(num_segs); stuffed.resize(raw_bytes + num_ff);
-    HIP_CHECK(hipMemcpy(recs.data(), pb.recs, num_segs * sizeof(JpegSegDev), hipMemcpyDeviceToHost));
-    if (!stuffed.empty()) HIP_CHECK(hipMemcpy(stuffed.data(), pb.stuffed, stuffed.size(), hipMemcpyDeviceToHost));
+    recs.resize(num_segs);
+    CopyJpegToHost(recs.data(), pb.recs, num_segs * sizeof(JpegSegDev), stream_v);
+    stuffed_size = raw_bytes + num_ff;
+    stuffed_bytes.resize(stuffed_size);
+    CopyJpegToHost(stuffed_bytes.data(), pb.stuffed, stuffed_size, stream_v);
+    stuffed = stuffed_bytes.data();
   }
   // ---- per image: splice (device path) or Huffman-encode on the host from its coefficients
+  vec<int> host_images;
   for (int i = 0; i < n; i++) {
-    Img& m = im[i];
+    Img& m = w.im[i];
     if (!m.ok) continue;
     JpegResult& r = jpeg_results_[i];
     const ImageEntry& e = *images_[pub_[i].first_unit];
     const JpegData& jd = *jpeg_data_[i];
-    if (const uint32_t st = status[pub_[i].first_unit]) { bool unsupported; r.error = DeviceStatusMessage(st, pub_[i].first_unit, &unsupported); continue; }
+    const int unit = pub_[i].first_unit;
+    if (const uint32_t st = (size_t)unit < status.size() ? status[(size_t)unit] : 1u) { bool unsupported; r.error = DeviceStatusMessage(st, unit, &unsupported); continue; }
     std::string why;
     if (m.device && flags[i] == 0) {
       size_t scan_k = 0;
       const bool ok = WriteJpegMarkers(jd, e.ih.xsize, e.ih.ysize, [&](const JpegScanContext& cx, vec<uint8_t>* out, std::string* err) {
         if (scan_k >= m.num_scans) { if (err) *err = "JPEG writer: scan count"; return false; }
-        const JpegScanDev& d = scans[m.first_scan + scan_k++];
+        const JpegScanDev& d = w.scans[m.first_scan + scan_k++];
         vec<JpegSegmentRecord> segs(d.num_segs);
         for (uint32_t g = 0; g < d.num_segs; g++) {
           const JpegSegDev& rec = recs[d.first_seg + g];
-          if (rec.offset + rec.size > stuffed.size()) { if (err) *err = "JPEG writer: segment record outside the buffer"; return false; }
-          segs[g].bytes = stuffed.data() + rec.offset; segs[g].size = rec.size; segs[g].trail_bits = (uint8_t)(rec.trail >> 8); segs[g].trail_count = (uint8_t)(rec.trail & 0xFF);
+          if (rec.offset + rec.size > stuffed_size) { if (err) *err = "JPEG writer: segment record outside the buffer"; return false; }
+          segs[g].bytes = stuffed + rec.offset; segs[g].size = rec.size; segs[g].trail_bits = (uint8_t)(rec.trail >> 8); segs[g].trail_count = (uint8_t)(rec.trail & 0xFF);
         }
         return SpliceJpegScan(cx, segs.data(), segs.size(), out, err);
       }, &r.bytes, &why);
       if (ok) { r.ok = true; jpeg_device_images_++; jpeg_device_progressive_images_ += m.progressive ? 1 : 0; } else { r.bytes.clear(); r.error = why; }
       continue;
     }
-    // host writer: progressive files (without "jpeg_device_progressive"), extra zero runs, "jpeg_host_writer" — and images the device flagged: the host writer
-    // names their error, or writes the span whose correction bits it flushes on its own
+    host_images.push_back(i);
+  }
+  // host writer: progressive files (without "jpeg_device_progressive"), extra zero runs, "jpeg_host_writer" — and images the device flagged: the host writer
+  // names their error, or writes the span whose correction bits it flushes on its own
+  for (int i : host_images) {
+    Img& m = w.im[i];
+    JpegResult& r = jpeg_results_[i];
+    const ImageEntry& e = *images_[pub_[i].first_unit];
+    const JpegData& jd = *jpeg_data_[i];
+    std::string why;
     vec<int16_t> host(m.grid.nblk * 64);
-    HIP_CHECK(hipMemcpy(host.data(), (const int16_t*)(djpeg_ + o_coef) + m.first_blk * 64, host.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
+    CopyJpegToHost(host.data(), (const int16_t*)(djpeg_ + w.o_coef) + m.first_blk * 64, host.size() * sizeof(int16_t), stream_v);
     const int16_t* planes[3] = {host.data(), host.data() + m.grid.comp_first[1] * 64, host.data() + m.grid.comp_first[2] * 64};
     if (WriteJpeg(jd, e.ih.xsize, e.ih.ysize, planes, &r.bytes, &why)) { r.ok = true; jpeg_host_images_++; } else { r.bytes.clear(); r.error = why; }
   }
+}
+
+// The batch call: the four phases in sequence on the caller's stream, around one entropy decode of the batch, with its host waits
+void Batch::ReconstructJpegs(void* stream_v) {
+  const int n = (int)pub_.size();
+  jpeg_results_.clear(); jpeg_results_.resize((size_t)n);
+  jpeg_device_images_ = jpeg_host_images_ = jpeg_device_progressive_images_ = 0;
+  jpeg_gather_launches_ = 0;
+  jw_.reset();
+  bool any = false;
+  for (int i = 0; i < n; i++) {
+    std::string why;
+    if (CanReconstructJpeg(i, &why)) any = true; else jpeg_results_[i].error = "JPEG reconstruction: " + why;
+  }
+  if (!any) return;
+  if (!prepared_) Prepare(stream_v);
+  HIP_CHECK(hipSetDevice(device_));
+  PlanJpegWrite();
+  EnqueueJpegPlan(stream_v, /*fail_refused=*/false);
+  // ---- one entropy decode of the batch (LF stage: JPEG DC, block metadata; HF stage: AC), coefficients into JPEG layout
+  RunPart(stream_v, 1, false);
+  RunPart(stream_v, 3, false);
+  EnqueueJpegGather(stream_v);
+  EnqueueJpegSizes(stream_v);
+  vec<uint32_t> status;
+  FinishStatus(stream_v, &status);         // (waits; the kernels above and below skip frames whose status word is set — it is cleared only on the host's copy)
+  FinishJpegWrite(stream_v, status);
 }
 
 // ---- libjpeg-exact pixels of JPEG transcodes: the entropy run of ReconstructJpegs, then integer IDCT, libjpeg's chroma upsampling and colour conversion (jpeg_pixels.hip)

@@ -172,6 +172,25 @@ class Batch {
   // component (DESIGN.md §5 lists what stays with the host writer); off: progressive files go through the host writer
   bool jpeg_device_progressive = false;
   uint32_t resize_group_max = kResizeGroupMax;   // testing: images per resize launch (1 .. kResizeGroupMax)
+  // ReconstructJpegs in its phases, for callers that order the stages themselves (Pipeline jobs of this kind); ReconstructJpegs is the four in sequence on one stream:
+  //   PlanJpegWrite             host only, after Prepare: CanReconstructJpeg per image, the marker walk (scans, table snapshots, reset points), the arena layout, the gather
+  //                             table, and which images the device writes (jpeg_host_writer, jpeg_device_progressive); an image that cannot be reconstructed
+  //                             gets its jpeg_result now.  Returns the number of images left.
+  //   EnqueueJpegPlan           uploads scan table, tables, resets and gather table on `stream`, clears the flags; fail_refused: the status words of the frames that are
+  //                             NOT in the gather table are set (kErrUnsupported), so that ZeroFailedCoefKernel puts zeros back where nobody will consume coefficients
+  //   EnqueueJpegGather         behind the HF stage (RunPart 3): JpegGatherKernel, one launch per group of at most kJpegPixelGroupMax images — the last stage that touches
+  //                             the coefficient planes; with fail_refused they are clean behind it
+  //   EnqueueJpegSizes          the sizes pass of the device writer.  Neither waits on the host.
+  //   EnqueueJpegHeadReadback   (optional) the raw size and the flag words to pinned memory on a copy stream of the caller's, who waits for it before FinishJpegWrite
+  //   FinishJpegWrite           with the status words (FinishStatus / HarvestStatus): pack and stuffing pass, bytes and records back, splice or host writer per image.
+  //                             Every copy is a hipMemcpyAsync on `stream` into pinned staging followed by a wait for that stream.  Fills jpeg_result(i) and the counters.
+  size_t PlanJpegWrite();
+  void EnqueueJpegPlan(void* stream, bool fail_refused);
+  void EnqueueJpegGather(void* stream);
+  void EnqueueJpegSizes(void* stream);
+  void EnqueueJpegHeadReadback(void* stream);
+  void FinishJpegWrite(void* stream, const vec<uint32_t>& per_unit);
+  JpegResult* mutable_jpeg_result(int i) { return i >= 0 && (size_t)i < jpeg_results_.size() ? &jpeg_results_[(size_t)i] : nullptr; }   // (a pipeline job moves the bytes out)
   const JpegResult* jpeg_result(int i) const { return i >= 0 && (size_t)i < jpeg_results_.size() ? &jpeg_results_[(size_t)i] : nullptr; }
   // The samples libjpeg gives for the original file of a JPEG transcode, instead of libjxl's rendering of the frame (Run): integer dequantisation and IDCT, libjpeg's
   // "fancy" chroma upsampling and fixed-point YCbCr -> RGB (jpeg_pixels.hip), written through the write stage to the outputs set with SetOutput.  Takes the frame
@@ -288,8 +307,14 @@ class Batch {
   void EnqueueJpegIdct(void* stream);          // JpegIdctPlanesKernel per group, then ZeroFailedCoefKernel for the frames it failed
   void EnqueueJpegColorOut(void* stream);      // JpegColorOutKernel per group
   bool IsPlainJpegFrame(int i) const;          // the frame conditions CanReconstructJpeg and CanDecodeJpegPixels share
-  void EnqueueJpegCoefficients(int i, const JpegFrameGrid& g, int16_t* out, void* stream);   // JpegCoefKernel: image i's coefficients into JPEG layout at `out`
+  struct JpegWriteState;                       // what the phases of ReconstructJpegs share (decoder.cc): the plan of the last PlanJpegWrite
+  std::shared_ptr<JpegWriteState> jw_;
+  uint8_t* jpeg_pinned_ = nullptr; size_t jpeg_pinned_cap_ = 0;   // pinned staging of the reconstruction's copies to the host: a head and two chunks
+  void* jpeg_copy_event_[2] = {nullptr, nullptr};
+  uint8_t* JpegPinned(size_t head);
+  void CopyJpegToHost(void* dst, const void* src, size_t bytes, void* stream);
   int jpeg_device_images_ = 0, jpeg_host_images_ = 0, jpeg_device_progressive_images_ = 0;
+  int64_t jpeg_gather_launches_ = 0;           // launches of JpegGatherKernel of the last reconstruction (one per group of the gather table)
   uint8_t* djpeg_ = nullptr; size_t jpeg_cap_ = 0;           // ReconstructJpegs: coefficient planes in JPEG layout, scan table, per-block / per-segment arrays
   uint8_t* djpeg_out_ = nullptr; size_t jpeg_out_cap_ = 0;   // ... raw and stuffed segment bytes, segment records
   bool any_complex_ = false;

@@ -3,6 +3,8 @@
 // quantisation tables.  Output: the caller's pixels through the write stage (pixel_ops.h StorePixel).
 //   JpegIdctPlanesKernel chroma from luma (4:4:4), dequantisation and libjpeg's jpeg_idct_islow (jidctint.c: CONST_BITS 13, PASS1_BITS 2) -> u8 component planes of the
 //                        padded grids; zeroes the coefficients it read
+//   JpegGatherKernel     the same coefficients, read and zeroed the same way, into the int16 arena of the JPEG writer (jpeg_write.hip): batch reconstruction and
+//                        reconstruction jobs of the pipeline, one launch per group of images
 //   JpegColorOutKernel   "fancy" chroma upsampling (jdsample.c h2v1 / h2v2 triangle filters; plain replication for planes at most two samples wide), fixed-point
 //                        YCbCr -> RGB (jdcolor.c), sample k enters the write stage as (float)k x (1 / 255)
 // Every sum that a damaged stream can drive out of range is formed in uint32_t: it wraps, nothing is undefined; the samples of such a stream mean nothing, but every
@@ -105,16 +107,12 @@ __global__ __launch_bounds__(256) void JpegIdctPlanesKernel(const FrameDev* __re
           for (int r = 0; r < 8; r++) ycol[r] = cf[r];
         } else {
           const int32_t fac = c == 1 ? (int32_t)f.ytox[tile] : (int32_t)f.ytob[tile];
-          const int32_t ff = fac * 2048 / 84;                             // (C++ division: truncates toward zero)
+          const int32_t ff = JpegCflFactor(fac);
           const int32_t* __restrict__ ratio = im.cfl_ratio[c - 1] + k * 8;   // 2048 qt[0][i] / qt[c][i], the host's division
           const int4 rlo = *(const int4*)ratio, rhi = *(const int4*)(ratio + 4);
           const int32_t rt[8] = {rlo.x, rlo.y, rlo.z, rlo.w, rhi.x, rhi.y, rhi.z, rhi.w};
 #pragma unroll
-          for (int r = 0; r < 8; r++) {
-            const int32_t scale = (int32_t)((uint32_t)rt[r] * (uint32_t)ff);
-            const int32_t cfl = (int32_t)((uint32_t)ycol[r] * (uint32_t)((int32_t)((uint32_t)scale + 1024u) >> 11) + 1024u) >> 11;
-            cf[r] = (int32_t)((uint32_t)cf[r] + (uint32_t)cfl);
-          }
+          for (int r = 0; r < 8; r++) cf[r] = (int32_t)((uint32_t)cf[r] + (uint32_t)JpegCflTerm(ycol[r], rt[r], ff));
         }
       }
       if (k == 0) cf[0] = f.lfq[ch][(size_t)by * f.bw + bx];              // (no chroma from luma on the DC term: the LF stage has its own)
@@ -140,6 +138,100 @@ __global__ __launch_bounds__(256) void JpegIdctPlanesKernel(const FrameDev* __re
       *(uint2*)(im.plane[c] + ((size_t)by * 8 + k) * ((size_t)gw * 8) + (size_t)bx * 8) = px;
     }
     if (step + 1 < steps) __syncthreads();                  // (the next step's pass 1 overwrites the workspace)
+  }
+}
+
+// The quantised coefficients of a group of images from the HF stage's planes into the int16 arena of the JPEG writer (jpeg_write.hip; decoder.cc Batch::PlanJpegWrite):
+// natural order, component planes back to back from im.coef_out on, grids as the table says.  What JpegCoefKernel (kernels_features.hip) does per image with a thread
+// per coefficient, in one launch per group and with the access pattern of JpegIdctPlanesKernel above — the same positions (eight per wavefront, lane = (position j, k),
+// a 4:4:4 colour position walks Y, Cb, Cr), the same mapping of a component block to its frame block, its group and its 64 dwords, the same two 16-byte loads of column
+// u = k, the same zeroing of what was read, the same DC term from lfq, the same chroma from luma (pixel_ops.h JpegCflTerm) with Y's column kept in registers.  Only the
+// shifts are per component here (comp_hs / comp_vs: reconstruction also takes samplings the pixel path refuses), and chroma from luma applies when all of them are 0.
+//   One reader per dword, as above: a (channel, frame block) pair belongs to exactly one (position, step), and of its 64 dwords lane k alone reads — and then zeroes —
+//   8 k .. 8 k + 7.  So there is no order between wavefronts or workgroups to get wrong; the coefficient set is clean behind the launch, except for frames that
+//   failed (a block that is not DCT8 sets kErrVarblock; a failed frame is skipped from then on): those are zeroed whole by ZeroFailedCoefKernel behind the launch.
+//   Addresses: every one comes from the host's table and the frame's grid; (sx << hs, sy << vs) is checked against the frame's grid, coef_off is brought to a multiple
+//   of 64 at most 65536 - 64.  The stream decides values only.
+//   Transpose: the lane holds column u = k, eight values v = 0 .. 7, the arena wants out[v x 8 + u] as int16_t.  Through LDS, 128 bytes per block and 1 KB per
+//   wavefront, no padding: row v of block j lives in the 16-byte slot 8 j + (v ^ 2 (j & 3)).
+//     Column stores: lanes k and k ^ 1 first exchange half of their values (two __shfl_xor of packed pairs), so that the even lane holds the dwords {u = k, k + 1} of
+//     rows 0, 2, 4, 6 and the odd lane those of rows 1, 3, 5, 7: four ds_write_b32 per lane.  Store i of lane (j, k) goes to row v = 2 i + (k & 1), dword
+//     32 j + 4 (v ^ 2 (j & 3)) + (k >> 1).  Banks of a store are (a / 4) % 32, one 32-lane half (j & 3 = 0 .. 3, k) at a time: v ^ 2 (j & 3) =
+//     2 (i ^ (j & 3)) + (k & 1) takes each of the eight slots once over ((j & 3), (k & 1)), and k >> 1 the four dwords of a slot: 32 lanes, 32 banks.
+//     Row loads: lane (j, k) reads slot 8 j + k with one ds_read_b128 — row v = k ^ 2 (j & 3) of its block.  Banks of that load are (a / 4) % 64, sixteen 16-byte
+//     slots, over the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (and the same + 32): the slots 8 j + k mod 16 of a group are {0-3}, {12-15}, {4-7},
+//     {8-11} resp. {4-7}, {8-11}, {0-3}, {12-15}: all sixteen different.
+//   The lane then stores its row as one 16-byte vector; the eight lanes of a block fill one contiguous, 128-byte aligned run of 128 bytes.
+__global__ __launch_bounds__(256) void JpegGatherKernel(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table) {
+  __shared__ __attribute__((aligned(16))) uint32_t ts[kIdctWaves][kIdctBlocksPerWave * 32];
+  const JpegPixelImage& im = table[blockIdx.z];
+  const FrameDev& f = frames[im.frame];
+  if (blockIdx.x * (kIdctWaves * kIdctBlocksPerWave) >= im.npos || *f.status != 0) return;     // (a failed frame's planes are zeroed by ZeroFailedCoefKernel)
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane >> 3, k = lane & 7;
+  const uint32_t pos = (blockIdx.x * kIdctWaves + wave) * kIdctBlocksPerWave + j;
+  const bool walk = im.ncomp == 3 && !(im.comp_hs[0] | im.comp_vs[0] | im.comp_hs[1] | im.comp_vs[1] | im.comp_hs[2] | im.comp_vs[2]);   // 4:4:4: Y, Cb, Cr of one block position
+  const uint32_t steps = walk ? 3u : 1u;                     // (uniform over the workgroup: the barriers below are reached by all of it)
+  uint32_t c = 0, bx = 0, by = 0;
+  {
+    if (!walk && im.ncomp == 3) c = pos >= im.comp_first[2] ? 2u : pos >= im.comp_first[1] ? 1u : 0u;
+    const uint32_t local = pos - (walk ? 0u : im.comp_first[c]), gw = im.grid_w[c];
+    bx = local % gw; by = local / gw;
+  }
+  uint32_t* const tw = ts[wave] + j * 32;
+  const uint32_t sw = 2 * (j & 3), odd = k & 1;
+  int32_t ycol[8] = {0, 0, 0, 0, 0, 0, 0, 0};               // Y's quantised column k (4:4:4), for the chroma steps
+  size_t tile = 0;
+  for (uint32_t step = 0; step < steps; step++) {
+    if (walk) c = step;
+    const uint32_t ch = im.ncomp == 1 ? 1u : (c == 0 ? 1u : c == 1 ? 0u : 2u);
+    const uint32_t hs = im.comp_hs[c], vs = im.comp_vs[c], gw = im.grid_w[c];
+    const uint32_t sx = bx << hs, sy = by << vs;            // the frame block that carries this component block
+    const bool live = pos < im.npos && by < im.grid_h[c] && sx < f.bw && sy < f.bh;
+    int32_t cf[8] = {0, 0, 0, 0, 0, 0, 0, 0};               // cf[v]: coefficient (v, u = k)
+    if (live) {
+      const size_t o = (size_t)sy * f.bw + sx;
+      if (k == 0 && (f.blk_info[o] & 31u) != 0) atomicOr(f.status, (uint32_t)kErrVarblock);
+      const uint32_t g = (sy / 32) * f.xgroups + sx / 32;
+      const uint32_t coff = min(f.coef_off[o] & ~63u, 65536u - 64u);
+      int4* const src = (int4*)(f.coeff[ch] + (size_t)g * 65536 + coff + k * 8);
+      const int4 lo = src[0], hi = src[1];
+      if (lo.x | lo.y | lo.z | lo.w) src[0] = make_int4(0, 0, 0, 0);      // consumed: the coefficient set stays clean for its next user
+      if (hi.x | hi.y | hi.z | hi.w) src[1] = make_int4(0, 0, 0, 0);
+      cf[0] = lo.x; cf[1] = lo.y; cf[2] = lo.z; cf[3] = lo.w; cf[4] = hi.x; cf[5] = hi.y; cf[6] = hi.z; cf[7] = hi.w;
+      if (walk) {
+        if (c == 0) {
+          tile = (size_t)(sy / 8) * f.cw + sx / 8;
+#pragma unroll
+          for (int r = 0; r < 8; r++) ycol[r] = cf[r];
+        } else {
+          const int32_t ff = JpegCflFactor(c == 1 ? (int32_t)f.ytox[tile] : (int32_t)f.ytob[tile]);
+          const int32_t* __restrict__ ratio = im.cfl_ratio[c - 1] + k * 8;   // 2048 qt[0][i] / qt[c][i], the host's division
+          const int4 rlo = *(const int4*)ratio, rhi = *(const int4*)(ratio + 4);
+          const int32_t rt[8] = {rlo.x, rlo.y, rlo.z, rlo.w, rhi.x, rhi.y, rhi.z, rhi.w};
+#pragma unroll
+          for (int r = 0; r < 8; r++) cf[r] = (int32_t)((uint32_t)cf[r] + (uint32_t)JpegCflTerm(ycol[r], rt[r], ff));
+        }
+      }
+      if (k == 0) cf[0] = f.lfq[ch][(size_t)by * f.bw + bx];              // (no chroma from luma on the DC term: the LF stage has its own)
+    }
+    // (int16_t: the width JPEG gives a coefficient, as JpegCoefKernel stores it.)  The lane sends the rows its partner k ^ 1 stores: the odd lane its even rows.
+    uint32_t p[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) p[r] = (uint32_t)cf[r] & 0xFFFFu;
+    const uint32_t r0 = (uint32_t)__shfl_xor((int)(odd ? p[0] | p[2] << 16 : p[1] | p[3] << 16), 1, 64);
+    const uint32_t r1 = (uint32_t)__shfl_xor((int)(odd ? p[4] | p[6] << 16 : p[5] | p[7] << 16), 1, 64);
+    uint32_t d[4];
+    if (odd) { d[0] = (r0 & 0xFFFFu) | p[1] << 16; d[1] = (r0 >> 16) | p[3] << 16; d[2] = (r1 & 0xFFFFu) | p[5] << 16; d[3] = (r1 >> 16) | p[7] << 16; }
+    else { d[0] = p[0] | r0 << 16; d[1] = p[2] | (r0 >> 16) << 16; d[2] = p[4] | r1 << 16; d[3] = p[6] | (r1 >> 16) << 16; }
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) tw[4 * ((2 * i + odd) ^ sw) + (k >> 1)] = d[i];
+    __syncthreads();
+    if (live) {
+      const uint4 row = *(const uint4*)(tw + 4 * k);
+      const uint32_t v = k ^ sw;
+      *(uint4*)(im.coef_out + ((size_t)im.comp_first[c] + (size_t)by * gw + bx) * 64 + v * 8) = row;
+    }
+    if (step + 1 < steps) __syncthreads();                  // (the next step's column stores overwrite the rows)
   }
 }
 
@@ -199,6 +291,11 @@ void LaunchJpegIdctGroup(const FrameDev* frames, const JpegPixelImage* table, co
   if (!g.count || g.count > kJpegPixelGroupMax || !g.max_npos || !g.max_w || !g.max_h) return;
   const uint32_t per_wg = kIdctWaves * kIdctBlocksPerWave;
   hipLaunchKernelGGL(JpegIdctPlanesKernel, dim3((g.max_npos + per_wg - 1) / per_wg, 1, g.count), dim3(256), 0, (hipStream_t)stream, frames, table + g.first);
+}
+void LaunchJpegGatherGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream) {
+  if (!g.count || g.count > kJpegPixelGroupMax || !g.max_npos) return;
+  const uint32_t per_wg = kIdctWaves * kIdctBlocksPerWave;
+  hipLaunchKernelGGL(JpegGatherKernel, dim3((g.max_npos + per_wg - 1) / per_wg, 1, g.count), dim3(256), 0, (hipStream_t)stream, frames, table + g.first);
 }
 void LaunchJpegColorOutGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream) {
   if (!g.count || g.count > kJpegPixelGroupMax || !g.max_npos || !g.max_w || !g.max_h) return;

@@ -1,5 +1,5 @@
-// jxl-hip: device-side writer of Huffman JPEG scans, sequential and progressive (batch JPEG reconstruction, decoder.cc Batch::ReconstructJpegs).
-// Input: the int16 coefficient planes JpegCoefKernel leaves in device memory (natural order, MCU-padded block grids).  Output: for every
+// jxl-hip: device-side writer of Huffman JPEG scans, sequential and progressive (batch JPEG reconstruction, decoder.cc Batch::ReconstructJpegs and its phases; reconstruction
+// jobs of a pipeline).  Input: the int16 coefficient planes JpegGatherKernel (jpeg_pixels.hip) leaves in device memory (natural order, MCU-padded block grids).  Output: for every
 // restart segment of every eligible scan the byte-stuffed bytes of its complete bytes plus the bits of its last, incomplete byte; the host
 // pads that byte and splices the segments between the markers (jpeg_recon.cc SpliceJpegScan).
 //   pass 1   JpegBlockBitsKernel   one wavefront per 8x8 block, lane k = zigzag coefficient k: bits of the block's Huffman code

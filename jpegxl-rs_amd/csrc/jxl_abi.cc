@@ -1216,6 +1216,44 @@ JxlDecoderStatus JxlHipPipelineWait(JxlHipPipeline* h, int64_t ticket, int* imag
     return all_ok ? JXL_DEC_SUCCESS : JXL_DEC_ERROR;
   } catch (const std::exception& e) { SetLastError(e.what()); if (image_status) for (int i = 0; i < n; i++) image_status[i] = 1; return JXL_DEC_ERROR; }
 }
+// ---- reconstruction jobs (Pipeline::SubmitJpegs: Batch::ReconstructJpegs as pipeline stages)
+int64_t JxlHipPipelineSubmitJpegs(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, uint32_t flags) {
+  try {
+    if (!h) { SetLastError("JxlHipPipelineSubmitJpegs: no pipeline"); return -1; }
+    if (flags & ~(uint32_t)(JXL_HIP_JPEG_DEVICE_PROGRESSIVE | JXL_HIP_JPEG_HOST_WRITER)) { SetLastError("JxlHipPipelineSubmitJpegs: unknown flag bits"); return -1; }
+    return h->p->SubmitJpegs(datas, sizes, n, flags);
+  } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
+}
+JxlDecoderStatus JxlHipPipelineWaitJpegs(JxlHipPipeline* h, int64_t ticket, int* image_status, size_t* jpeg_sizes, int n, float* end_ms) {
+  try {
+    PipelineJobResult r;
+    h->p->WaitJpegs(ticket, &r);
+    bool all_ok = true;
+    std::string first;
+    for (size_t i = 0; i < r.status.size(); i++) {
+      if (image_status && (int)i < n) image_status[i] = r.status[i];
+      if (jpeg_sizes && (int)i < n) jpeg_sizes[i] = i < r.jpeg_sizes.size() ? r.jpeg_sizes[i] : 0;
+      if (r.status[i] != 0) { all_ok = false; if (first.empty()) first = "image " + std::to_string(i) + ": " + r.error[i]; }
+    }
+    if (end_ms) *end_ms = r.end_ms;
+    if (!all_ok) SetLastError(first);
+    return all_ok ? JXL_DEC_SUCCESS : JXL_DEC_ERROR;
+  } catch (const std::exception& e) {
+    SetLastError(e.what());
+    for (int i = 0; i < n; i++) { if (image_status) image_status[i] = 1; if (jpeg_sizes) jpeg_sizes[i] = 0; }
+    return JXL_DEC_ERROR;
+  }
+}
+JxlDecoderStatus JxlHipPipelineJpegStatus(JxlHipPipeline* h, int64_t ticket, int i) {
+  try {
+    std::string why;
+    if (h->p->JpegStatus(ticket, i, &why) == 0) return JXL_DEC_SUCCESS;
+    SetLastError(why);
+    return JXL_DEC_ERROR;
+  } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
+}
+JxlDecoderStatus JxlHipPipelineCopyJpeg(JxlHipPipeline* h, int64_t ticket, int i, void* dst, size_t capacity) { BATCH_TRY(h->p->CopyJpeg(ticket, i, dst, capacity)) }
+void JxlHipPipelineReleaseJpegs(JxlHipPipeline* h, int64_t ticket) { if (h) h->p->ReleaseJpegs(ticket); }
 JxlDecoderStatus JxlHipPipelineWaitAll(JxlHipPipeline* h) { BATCH_TRY(h->p->WaitAll()) }
 JxlDecoderStatus JxlHipPipelineResetClock(JxlHipPipeline* h) { BATCH_TRY(h->p->ResetClock()) }
 JxlDecoderStatus JxlHipPipelineCollectTimes(JxlHipPipeline* h, JxlHipStageTimes* t, int* runs) {

@@ -374,6 +374,10 @@ struct alignas(16) JpegPixelImage {
   uint32_t ncomp;
   uint32_t frame;                        // FrameDev of the image: status word, block info, coefficient planes, OutputDesc
   uint32_t width, height, hs, vs;
+  // JpegGatherKernel (reconstruction: Batch::PlanJpegWrite fills the same entry, without planes): where the image's int16 coefficients go — natural order, component c
+  // from block comp_first[c] on (at 4:4:4 too), 16-byte aligned — and every component's own shifts against the frame's block grid
+  int16_t* coef_out;
+  uint32_t comp_hs[3], comp_vs[3];
   alignas(16) int32_t qt[3][64];
   alignas(16) int32_t cfl_ratio[2][64];
 };
@@ -381,6 +385,7 @@ constexpr uint32_t kJpegPixelGroupMax = 32768;       // images per launch (gridD
 struct JpegPixelGroup { uint32_t first, count, max_npos, max_w, max_h; };      // a run of the table served by one launch per kernel, the grids sized for its largest image
 void LaunchJpegIdctGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);       // JpegIdctPlanesKernel
 void LaunchJpegColorOutGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);   // JpegColorOutKernel, behind it on the same stream
+void LaunchJpegGatherGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);     // JpegGatherKernel (max_w / max_h unused)
 void LaunchCopyPlane(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t w, uint32_t h, void* stream);
 // ---- resized output (OutputSpec::resize_w / resize_h): separable antialiased filter (triangle or cubic convolution), horizontal pass then vertical, f32 throughout.
 // One axis' filter as the host built it (decoder.cc ResizeAxis): output index i takes the taps first[i] .. first[i + 1] - 1 of `weight` (normalised, double rounded once to f32)

@@ -108,6 +108,7 @@ Pipeline::~Pipeline() {
   for (auto& kv : jobs_) if (kv.second->done_event) (void)hipEventDestroy((hipEvent_t)kv.second->done_event);
   jobs_.clear();
   for (auto& s : slots_) {
+    if (s->finish_stream) { (void)hipStreamSynchronize((hipStream_t)s->finish_stream); (void)hipStreamDestroy((hipStream_t)s->finish_stream); }
     s->batch.reset();
     for (void* e : {s->lf_done, s->front_done, s->hf_done, s->idct_done, s->rest_done}) if (e) (void)hipEventDestroy((hipEvent_t)e);
   }
@@ -168,7 +169,22 @@ int64_t Pipeline::Submit(const uint8_t* const* datas, const size_t* sizes, int n
   if (out_capacity) job->capacity.assign(out_capacity, out_capacity + n);
   job->spec = spec; job->spec.device_ptr = nullptr;
   if (each) job->each.assign(each, each + n);
-  job->jpeg_pixels = jpeg_pixels;
+  job->kind = jpeg_pixels ? kJpegPixels : kPlain;
+  return Enqueue(job, n);
+}
+
+int64_t Pipeline::SubmitJpegs(const uint8_t* const* datas, const size_t* sizes, int n, uint32_t flags) {
+  if (n <= 0 || !datas || !sizes) throw ParseError("JxlHipPipelineSubmitJpegs: no images", false);
+  if (flags & ~(kPipelineJpegDeviceProgressive | kPipelineJpegHostWriter)) throw ParseError("JxlHipPipelineSubmitJpegs: unknown flag bits", false);
+  std::shared_ptr<Job> job(new Job());
+  job->datas.assign(datas, datas + n); job->sizes.assign(sizes, sizes + n);
+  job->kind = kJpegFiles; job->jpeg_flags = flags;
+  job->jpeg_files.resize((size_t)n);
+  job->result.jpeg_sizes.assign((size_t)n, 0);
+  return Enqueue(job, n);
+}
+
+int64_t Pipeline::Enqueue(const std::shared_ptr<Job>& job, int n) {
   job->result.status.assign((size_t)n, 1); job->result.error.assign((size_t)n, std::string());
   std::unique_lock<std::mutex> lock(mu_);
   if (shutdown_) throw ParseError("JxlHipPipelineSubmit: the pipeline is shutting down", false);
@@ -254,7 +270,22 @@ void Pipeline::PrepareJob(Job* j, int worker) {
     t_parse = std::chrono::steady_clock::now();
     j->batch_index.assign(index.begin(), index.end());
     bool any = false;
-    for (int i = 0; i < n; i++) {
+    const bool files = j->kind == kJpegFiles;
+    if (files) {
+      // a reconstruction job: no outputs.  What the batch call refuses fails alone here, with that call's text, and stays in the batch (its frame is never consumed:
+      // EnqueueJpegPlan below sets its status word, so that the HF stage puts zeros back behind it); a job without one image to reconstruct never reaches the GPU
+      bt.jpeg_host_writer = (j->jpeg_flags & kPipelineJpegHostWriter) != 0;
+      bt.jpeg_device_progressive = (j->jpeg_flags & kPipelineJpegDeviceProgressive) != 0;
+      for (int i = 0; i < n; i++) {
+        const int bi = index[(size_t)i];
+        if (bi < 0) { j->result.error[(size_t)i] = errors[(size_t)i]; continue; }
+        std::string why;
+        if (bt.CanReconstructJpeg(bi, &why)) any = true;
+        else { j->result.error[(size_t)i] = "JPEG reconstruction: " + why; j->batch_index[(size_t)i] = -2 - bi; }
+      }
+      if (!any) { j->job_error = "JPEG reconstruction: no image of the job can be reconstructed"; return; }
+    }
+    for (int i = 0; i < n && !files; i++) {
       if (index[(size_t)i] < 0) { j->result.error[(size_t)i] = errors[(size_t)i]; continue; }
       OutputSpec o = j->each.empty() ? j->spec : j->each[(size_t)i];
       o.device_ptr = j->device_out.empty() ? nullptr : j->device_out[(size_t)i];
@@ -267,7 +298,7 @@ void Pipeline::PrepareJob(Job* j, int worker) {
         j->result.error[(size_t)i] = refusal;
         o.device_ptr = nullptr; o.plane_stride = 0; o.crop_x0 = o.crop_y0 = o.crop_w = o.crop_h = 0; o.mirror = false; o.resize_filter = 0;
         j->batch_index[(size_t)i] = -2 - index[(size_t)i];
-      } else if (j->jpeg_pixels && !bt.CanDecodeJpegPixels(index[(size_t)i], &not_eligible)) {
+      } else if (j->kind == kJpegPixels && !bt.CanDecodeJpegPixels(index[(size_t)i], &not_eligible)) {
         // (a libjpeg-exact job: what that decode does not take stays in the batch too and fails with the batch call's reason; nothing is written for it)
         j->result.error[(size_t)i] = not_eligible;
         o.device_ptr = nullptr;
@@ -298,7 +329,20 @@ void Pipeline::PrepareJob(Job* j, int worker) {
     void* side = lf_side_[(size_t)(j->ticket % (int64_t)lf_side_.size())];
     bt.Prepare(side, /*wait_upload=*/false);
     size_t jpeg_table = 0;
-    if (j->jpeg_pixels) {
+    if (files) {
+      // the host plan of the reconstruction; scan table, tables, resets and gather table travel on the stream of the LF stage.  What Prepare alone could tell (the
+      // quantisation table of a one-group frame) fails its image here.
+      const size_t left = bt.PlanJpegWrite();
+      for (int i = 0; i < n; i++) {
+        const int bi = index[(size_t)i];
+        if (bi < 0 || j->batch_index[(size_t)i] < 0) continue;
+        const Batch::JpegResult* r = bt.jpeg_result(bi);
+        if (r && !r->error.empty()) { j->result.error[(size_t)i] = r->error; j->batch_index[(size_t)i] = -2 - bi; }
+      }
+      if (!left) throw ParseError("JPEG reconstruction: no image of the job can be reconstructed", true);
+      bt.EnqueueJpegPlan(side, /*fail_refused=*/true);
+    }
+    if (j->kind == kJpegPixels) {
       // the host plan of the libjpeg-exact tail; its table travels on the stream of the LF stage.  What Prepare alone could tell (the quantisation table of a
       // one-group frame, a block grid that does not hold the image) fails its image here.
       jpeg_table = bt.PlanJpegPixels();
@@ -338,12 +382,13 @@ void Pipeline::PrepareJob(Job* j, int worker) {
       lock.unlock();
       if (chained) StreamWait(side, slots_[(size_t)(j->wide_after % nbuf_)]->lf_done);
     }
-    bt.RunPart(side, 5, opt_.timed != 0);           // LF decode + varblock placement: all the HF stage waits for
+    const bool timed = opt_.timed != 0 && !files;   // (a reconstruction job has no pixel stages to bracket: its parts are not timed)
+    bt.RunPart(side, 5, timed);           // LF decode + varblock placement: all the HF stage waits for
     Record(s.lf_done, side);
     if (j->wide_chain) { { std::lock_guard<std::mutex> lock(mu_); wide_enqueued_ = std::max(wide_enqueued_, j->ticket); } cv_.notify_all(); }
-    // LF post-processing: needed by the float IDCT and the filters only — the libjpeg-exact tail reads lfq, the coefficient planes, block info and offsets, the
+    // LF post-processing: needed by the float IDCT and the filters only — the libjpeg-exact tail and the reconstruction's gather read lfq, the coefficient planes, block info and offsets, the
     // chroma-from-luma maps: nothing LfDequantKernel, LfSmoothKernel, LlfSigmaKernel or LlfKernel write (lf, lf_tmp, llf, inv_sigma)
-    bt.RunPart(side, j->jpeg_pixels ? 11 : 6, opt_.timed != 0);
+    bt.RunPart(side, j->kind != kPlain ? 11 : 6, timed);
     Record(s.front_done, side);
   } catch (const std::exception& e) {
     j->job_error = e.what();
@@ -367,7 +412,7 @@ void Pipeline::IssueHf(Job* j) {
     StreamWait(hs, s.lf_done);
     // the coefficient set's previous user has consumed (and zeroed) it: its tail was issued before this call (tails go out in order, HF stages at most hf_streams ahead)
     if (j->ticket >= ncoef_) StreamWait(hs, slots_[(size_t)((j->ticket - ncoef_) % nbuf_)]->idct_done);
-    s.batch->RunPart(hs, 3, opt_.timed != 0);
+    s.batch->RunPart(hs, 3, opt_.timed != 0 && j->kind != kJpegFiles);
     Record(s.hf_done, hs);
   } catch (const std::exception& e) { j->job_error = e.what(); }
 }
@@ -379,12 +424,17 @@ void Pipeline::IssueTail(Job* j) {
     try {
       StreamWait(main_, s.hf_done);
       StreamWait(main_, s.front_done);
-      bt.RunPart(main_, j->jpeg_pixels ? 9 : 7, opt_.timed != 0);      // IDCT (float, or the integer one over the HF planes): the last stage that touches the coefficient set, which is clean behind it
+      // IDCT (float, or the integer one over the HF planes; a reconstruction job: the gather into the JPEG writer's arena): the last stage that touches the coefficient
+      // set, which is clean behind it
+      if (j->kind == kJpegFiles) bt.EnqueueJpegGather(main_); else bt.RunPart(main_, j->kind == kJpegPixels ? 9 : 7, opt_.timed != 0);
       Record(s.idct_done, main_);
-      bt.RunPart(main_, j->jpeg_pixels ? 10 : 8, opt_.timed != 0);     // restoration filters, colour, write (libjpeg-exact jobs: chroma upsampling, colour, write); resizes
+      // restoration filters, colour, write (libjpeg-exact jobs: chroma upsampling, colour, write); resizes.  A reconstruction job: the sizes pass of the writer — its
+      // pack pass, sized on the host from what that pass found, and the splice belong to the harvest
+      if (j->kind == kJpegFiles) bt.EnqueueJpegSizes(main_); else bt.RunPart(main_, j->kind == kJpegPixels ? 10 : 8, opt_.timed != 0);
       Record(s.rest_done, main_);
       void* d2h = d2h_[0];
       StreamWait(d2h, s.rest_done);
+      if (j->kind == kJpegFiles) bt.EnqueueJpegHeadReadback(d2h);      // the raw size and the flag words travel with the status words
       if (!j->host_out.empty()) {
         // equally sized images at equal distances on both sides (a job of same-shaped frames into one host buffer): one pitched copy instead of one per image
         bool pitched = j->host_out.size() >= 2;
@@ -459,13 +509,29 @@ void Pipeline::Harvest(Job* j) {
   bool readback_ok = false;
   vec<uint32_t> st;
   if (j->job_error.empty()) {
-    try { bt.HarvestStatus(&st); if (j->jpeg_pixels) bt.HarvestJpegPixels(st); readback_ok = true; } catch (const std::exception& e) { j->job_error = e.what(); }
+    try { bt.HarvestStatus(&st); if (j->kind == kJpegPixels) bt.HarvestJpegPixels(st); readback_ok = true; } catch (const std::exception& e) { j->job_error = e.what(); }
+  }
+  bool finish_failed = false;
+  double finish_ms = 0;
+  if (j->kind == kJpegFiles && readback_ok) {
+    const auto f0 = std::chrono::steady_clock::now();
+    // pack pass, copies and splice of THIS job, on a stream no other job's stages queue behind, in the thread that collects it (or the prepare thread that takes over
+    // its slot) — while the issuer goes on with the entropy stages of the jobs behind it
+    try {
+      if (!s.finish_stream) s.finish_stream = NewStream(0);
+      bt.FinishJpegWrite(s.finish_stream, st);
+      if (j->done_event) Record(j->done_event, s.finish_stream);        // end_ms: behind the last copy of the finish phase
+      static const char* const kCounts[4] = {"jpeg_device_images", "jpeg_host_images", "jpeg_device_progressive_images", "jpeg_gather_launches"};
+      for (int k = 0; k < 4; k++) j->jpeg_counts[k] = bt.Info(kCounts[k]);
+    } catch (const std::exception& e) { j->job_error = e.what(); finish_failed = true; }
+    finish_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
   }
   if (j->done_event) {
     (void)hipEventSynchronize((hipEvent_t)j->done_event);
     float ms = 0;
     if (hipEventElapsedTime(&ms, (hipEvent_t)clock_event_, (hipEvent_t)j->done_event) == hipSuccess) j->result.end_ms = ms; else (void)hipGetLastError();
   }
+  if (finish_failed && s.finish_stream) (void)hipStreamSynchronize((hipStream_t)s.finish_stream);
   if (!j->job_error.empty() && !readback_ok) {
     // a job that failed half-way: whatever it enqueued must have left the GPU before the slot is reused
     (void)hipStreamSynchronize((hipStream_t)main_);
@@ -477,17 +543,27 @@ void Pipeline::Harvest(Job* j) {
     const int bi = i < j->batch_index.size() ? j->batch_index[i] : -1;
     if (!j->result.error[i].empty()) { j->result.status[i] = 1; continue; }
     if (!j->job_error.empty() || bi < 0) { j->result.status[i] = 1; j->result.error[i] = j->job_error.empty() ? "not decoded" : j->job_error; continue; }
+    if (j->kind == kJpegFiles) {
+      // (a damaged stream: FinishJpegWrite has named the status word, as the batch call does)
+      Batch::JpegResult* r = bt.mutable_jpeg_result(bi);
+      if (r && r->ok) { j->result.status[i] = 0; j->result.jpeg_sizes[i] = r->bytes.size(); j->jpeg_files[i] = std::move(r->bytes); r->bytes.clear(); }
+      else { j->result.status[i] = 1; j->result.error[i] = r && !r->error.empty() ? r->error : "JPEG reconstruction: no file"; }
+      continue;
+    }
     uint32_t bad = 0;
     for (int u = bt.first_unit_of(bi); u < bt.first_unit_of(bi) + bt.num_units_of(bi); u++) bad |= st[(size_t)u];
     if (bad) {
       j->result.status[i] = 1;
-      const Batch::JpegPixelResult* jr = j->jpeg_pixels ? bt.jpeg_pixel_result(bi) : nullptr;
+      const Batch::JpegPixelResult* jr = j->kind == kJpegPixels ? bt.jpeg_pixel_result(bi) : nullptr;
       if (jr && !jr->error.empty()) j->result.error[i] = jr->error;      // (names what JpegIdctPlanesKernel refused: a transform other than DCT8)
       else j->result.error[i] = (bad & kErrUnsupported) ? "unsupported: stream feature on the device path" : "corrupt stream (device status " + std::to_string(bad) + ")";
     } else j->result.status[i] = 0;
   }
   static const bool trace = getenv("JXL_HIP_SCHED_TRACE") != nullptr;
-  if (trace && opt_.timed && readback_ok) {
+  if (trace && readback_ok && j->kind == kJpegFiles)
+    fprintf(stderr, "[pipe %.1f] job %lld (reconstruction, %zu images): status words in hand, then pack pass + copies + splice %.1f ms on the collecting thread; done at %.1f ms\n",
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(), (long long)j->ticket, n, finish_ms, j->result.end_ms);
+  if (trace && opt_.timed && readback_ok && j->kind != kJpegFiles) {
     float tl[9];
     bt.DebugTimeline(clock_event_, tl);
     fprintf(stderr, "[pipe] job %lld timeline (ms): LF %.1f .. %.1f, LF post end %.1f, HF %.1f .. %.1f, IDCT %.1f .. %.1f, filters end %.1f, out end %.1f\n", (long long)j->ticket, tl[0], tl[1], tl[2], tl[7], tl[3],
@@ -500,29 +576,73 @@ void Pipeline::Harvest(Job* j) {
   {
     std::lock_guard<std::mutex> lock(mu_);
     if (readback_ok) last_info_["hf_nonzeros"] = bt.Info("hf_nonzeros");
-    if (readback_ok) { last_info_["jpeg_pixel_images"] = j->jpeg_pixels ? bt.Info("jpeg_pixel_images") : 0; last_info_["jpeg_pixel_launches"] = j->jpeg_pixels ? bt.Info("jpeg_pixel_launches") : 0; }
+    if (readback_ok) { last_info_["jpeg_pixel_images"] = j->kind == kJpegPixels ? bt.Info("jpeg_pixel_images") : 0; last_info_["jpeg_pixel_launches"] = j->kind == kJpegPixels ? bt.Info("jpeg_pixel_launches") : 0; }
+    if (readback_ok) {
+      last_info_["jpeg_device_images"] = j->jpeg_counts[0]; last_info_["jpeg_host_images"] = j->jpeg_counts[1];
+      last_info_["jpeg_device_progressive_images"] = j->jpeg_counts[2]; last_info_["jpeg_gather_launches"] = j->jpeg_counts[3];
+    }
     j->state = kHarvested;
   }
   cv_.notify_all();
 }
 
+std::shared_ptr<Pipeline::Job> Pipeline::WaitIssued(int64_t ticket, const char* who, bool jpegs) {
+  std::unique_lock<std::mutex> lock(mu_);
+  auto it = jobs_.find(ticket);
+  if (it == jobs_.end()) throw ParseError(std::string(who) + ": unknown ticket (never submitted, collected already, or too old)", false);
+  std::shared_ptr<Job> job = it->second;
+  if (jpegs && job->kind != kJpegFiles) throw ParseError(std::string(who) + ": this ticket is not a reconstruction job's (JxlHipPipelineSubmitJpegs)", false);
+  if (job->waited) throw ParseError(std::string(who) + ": this ticket is being waited for already", false);
+  job->waited = true;
+  cv_.wait(lock, [&] { return shutdown_ || job->state >= kTailIssued; });
+  if (job->state < kTailIssued) throw ParseError(std::string(who) + ": the pipeline is shutting down", false);
+  return job;
+}
+
 void Pipeline::Wait(int64_t ticket, PipelineJobResult* out) {
-  std::shared_ptr<Job> job;
-  {
-    std::unique_lock<std::mutex> lock(mu_);
-    auto it = jobs_.find(ticket);
-    if (it == jobs_.end()) throw ParseError("JxlHipPipelineWait: unknown ticket (never submitted, collected already, or too old)", false);
-    job = it->second;
-    if (job->waited) throw ParseError("JxlHipPipelineWait: this ticket is being waited for already", false);
-    job->waited = true;
-    cv_.wait(lock, [&] { return shutdown_ || job->state >= kTailIssued; });
-    if (job->state < kTailIssued) throw ParseError("JxlHipPipelineWait: the pipeline is shutting down", false);
-  }
+  std::shared_ptr<Job> job = WaitIssued(ticket, "JxlHipPipelineWait", false);
   Harvest(job.get());
   if (out) *out = job->result;
   std::lock_guard<std::mutex> lock(mu_);
   if (job->done_event) { (void)hipEventDestroy((hipEvent_t)job->done_event); job->done_event = nullptr; }
-  jobs_.erase(ticket);
+  jobs_.erase(ticket);          // (a reconstruction job: its files go with it)
+}
+
+void Pipeline::WaitJpegs(int64_t ticket, PipelineJobResult* out) {
+  std::shared_ptr<Job> job = WaitIssued(ticket, "JxlHipPipelineWaitJpegs", true);
+  Harvest(job.get());
+  if (out) *out = job->result;
+  std::lock_guard<std::mutex> lock(mu_);
+  if (job->done_event) { (void)hipEventDestroy((hipEvent_t)job->done_event); job->done_event = nullptr; }
+  job->collected = true;        // (stays in jobs_ with its files until ReleaseJpegs)
+}
+
+std::shared_ptr<Pipeline::Job> Pipeline::CollectedJpegs(int64_t ticket, int i, const char* who) {
+  std::lock_guard<std::mutex> lock(mu_);
+  auto it = jobs_.find(ticket);
+  if (it == jobs_.end() || it->second->kind != kJpegFiles || !it->second->collected)
+    throw ParseError(std::string(who) + ": unknown ticket (not a reconstruction job's, not waited for with JxlHipPipelineWaitJpegs, or released already)", false);
+  if (i < 0 || (size_t)i >= it->second->jpeg_files.size()) throw ParseError(std::string(who) + ": no such image", false);
+  return it->second;
+}
+int Pipeline::JpegStatus(int64_t ticket, int i, std::string* error) {
+  std::shared_ptr<Job> job = CollectedJpegs(ticket, i, "JxlHipPipelineJpegStatus");
+  if (job->result.status[(size_t)i] == 0) return 0;
+  if (error) *error = job->result.error[(size_t)i];
+  return 1;
+}
+void Pipeline::CopyJpeg(int64_t ticket, int i, void* dst, size_t capacity) {
+  std::shared_ptr<Job> job = CollectedJpegs(ticket, i, "JxlHipPipelineCopyJpeg");
+  if (job->result.status[(size_t)i] != 0) throw ParseError(job->result.error[(size_t)i], false);
+  const vec<uint8_t>& f = job->jpeg_files[(size_t)i];
+  if (!dst || capacity < f.size()) throw ParseError("JxlHipPipelineCopyJpeg: the buffer is smaller than the file", false);
+  if (!f.empty()) memcpy(dst, f.data(), f.size());
+}
+void Pipeline::ReleaseJpegs(int64_t ticket) {
+  std::lock_guard<std::mutex> lock(mu_);
+  auto it = jobs_.find(ticket);
+  if (it == jobs_.end() || it->second->kind != kJpegFiles || !it->second->collected) return;
+  jobs_.erase(it);
 }
 
 void Pipeline::WaitAll() {

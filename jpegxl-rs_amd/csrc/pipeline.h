@@ -47,7 +47,11 @@ struct PipelineJobResult {
   std::vector<int> status;            // per image: 0 decoded, 1 failed
   std::vector<std::string> error;     // per image: "" or what went wrong
   float end_ms = 0;                   // when the job's last byte had been written / copied, ms after the pipeline's clock was reset
+  std::vector<size_t> jpeg_sizes;     // reconstruction jobs: bytes of image i's file (0: none)
 };
+
+// flags of a reconstruction job (include/jxl_hip.h JXL_HIP_JPEG_*): the two switches of the batch call
+constexpr uint32_t kPipelineJpegDeviceProgressive = 1u, kPipelineJpegHostWriter = 2u;
 
 class Pipeline {
  public:
@@ -62,26 +66,46 @@ class Pipeline {
   // each (optional, n entries): image i is decoded to each[i] instead of `spec` — same format, layout, downscale and target size as `spec`; crop, filter and mirror are its own.
   int64_t Submit(const uint8_t* const* datas, const size_t* sizes, int n, const OutputSpec& spec, void* const* device_out, void* const* host_out, const size_t* out_capacity,
                  const OutputSpec* each = nullptr, bool jpeg_pixels = false);
+  // A reconstruction job (Batch::ReconstructJpegs as pipeline stages): the original JPEG file of every image, byte for byte.  No output spec and no destinations —
+  // nobody can size a JPEG file from its transcode —: the files stay with the pipeline until they are collected.  An image the batch call refuses fails alone with
+  // that call's text ("JPEG reconstruction: no jbrd box", ...); a job in which no image can be reconstructed fails as a whole, without touching the GPU.  flags:
+  // kPipelineJpegDeviceProgressive / kPipelineJpegHostWriter (Batch::jpeg_device_progressive / jpeg_host_writer; the latter wins); unknown bits refuse the submission.
+  // Such jobs mix freely with every other kind over the same coefficient sets and slots.
+  int64_t SubmitJpegs(const uint8_t* const* datas, const size_t* sizes, int n, uint32_t flags);
+  // Waits like Wait, but keeps the files: JpegStatus / CopyJpeg hand them out until ReleaseJpegs(ticket).  A ticket of another kind is refused (and stays waitable).
+  // Wait on a reconstruction ticket gives the statuses and releases the files.  A harvested reconstruction job that nobody waits for holds its files until the
+  // bounded history of uncollected jobs drops it (8 x slots + 64 jobs back), and so does one that was waited for and never released.
+  void WaitJpegs(int64_t ticket, PipelineJobResult* out);
+  int JpegStatus(int64_t ticket, int i, std::string* error);        // 0: image i has a file; 1: *error says why not.  Throws for a ticket that is not held, or no such image
+  void CopyJpeg(int64_t ticket, int i, void* dst, size_t capacity);   // throws if the image has no file or the buffer is smaller than it
+  void ReleaseJpegs(int64_t ticket);                                // forgets the job and its files (unknown tickets are ignored)
   // Waits until job `ticket` has left the GPU (outputs written, host copies done) and hands out its per-image results; a ticket can be waited for once.
   void Wait(int64_t ticket, PipelineJobResult* out);
   void WaitAll();                                  // every job submitted so far has left the GPU (results stay collectable)
   void ResetClock();                               // end_ms of later jobs counts from here (call on an idle pipeline)
   StageTimes CollectTimes(int* runs);              // per-stage HIP-event sums over all jobs since the last call (options.timed)
   void StageBytes(uint64_t out[6]);                // algorithmic bytes per stage of the job prepared last
-  int64_t Info(const char* name);                  // "device_bytes", "jobs", "shared_big_bytes", "shared_coef_bytes", "private_plane_jobs", "jpeg_pixel_images", "jpeg_pixel_launches" (of the job prepared or finished last), batch infos of the last job ("hf_nonzeros", "lf_simt_frames" ...)
+  int64_t Info(const char* name);                  // "device_bytes", "jobs", "shared_big_bytes", "shared_coef_bytes", "private_plane_jobs", "jpeg_pixel_images", "jpeg_pixel_launches" (of the job prepared or finished last), "jpeg_device_images", "jpeg_host_images", "jpeg_device_progressive_images", "jpeg_gather_launches" (of the job finished last; 0 unless it was a reconstruction job), batch infos of the last job ("hf_nonzeros", "lf_simt_frames" ...)
   double prepare_seconds_total() const { return prepare_s_total_; }
   int64_t prepared_jobs() const { return prepared_jobs_; }
   int device() const { return device_; }
 
  private:
   enum State { kQueued = 0, kPreparing, kFrontIssued, kTailIssued, kHarvested };
+  // what a job's tail is: the float IDCT, filters and write; the integer IDCT over the HF planes + libjpeg's upsampling and colour conversion (libjpeg-exact pixels);
+  // the gather into the JPEG writer's arena + its sizes pass, with the pack pass and the splice at harvest (reconstruction)
+  enum Kind { kPlain = 0, kJpegPixels, kJpegFiles };
   struct Job {
     int64_t ticket = 0;
     std::vector<const uint8_t*> datas; std::vector<size_t> sizes;
     std::vector<void*> device_out, host_out; std::vector<size_t> capacity;
     OutputSpec spec;
     std::vector<OutputSpec> each;              // per image, when the job was submitted with specs of its own (empty: `spec` for all)
-    bool jpeg_pixels = false;                  // a libjpeg-exact job: the tail is the integer IDCT over the HF planes + libjpeg's upsampling and colour conversion
+    Kind kind = kPlain;
+    uint32_t jpeg_flags = 0;                   // reconstruction jobs: kPipelineJpeg*
+    std::vector<vec<uint8_t>> jpeg_files;      // reconstruction jobs, from the harvest on: image i's file (empty: none)
+    int64_t jpeg_counts[4] = {0, 0, 0, 0};     // ... device images, host images, device progressive images, gather launches
+    bool collected = false;                    // WaitJpegs has returned: the files can be handed out
     std::vector<int> batch_index;              // per image: index in the batch, -1 = failed before it got there
     PipelineJobResult result;
     std::string job_error;                     // the whole job failed (Prepare threw)
@@ -95,6 +119,7 @@ class Pipeline {
   struct Slot {
     std::unique_ptr<Batch> batch;
     void *lf_done = nullptr, *front_done = nullptr, *hf_done = nullptr, *idct_done = nullptr, *rest_done = nullptr;
+    void* finish_stream = nullptr;             // reconstruction jobs: the stream of FinishJpegWrite at harvest (nothing else queues on it; made when first needed)
     std::mutex mu;                             // harvest of the slot's current job
   };
   void PrepareWorker(int worker);
@@ -104,6 +129,9 @@ class Pipeline {
   void IssueTail(Job* j);
   void Harvest(Job* j);                        // waits for the job's completion on the GPU, fills j->result (once)
   Job* FindJob(int64_t ticket);                // (mu_ held)
+  int64_t Enqueue(const std::shared_ptr<Job>& job, int n);   // back-pressure, ticket, cold-start chain, history bound, prepare queue
+  std::shared_ptr<Job> WaitIssued(int64_t ticket, const char* who, bool jpegs);
+  std::shared_ptr<Job> CollectedJpegs(int64_t ticket, int i, const char* who);
   void GrowSharedWhenIdle();                   // (mu_ held, nothing in flight)
   void ReservePlanes(SharedPlanes* sp, size_t bytes);
 

@@ -214,4 +214,14 @@ __device__ __forceinline__ float SubsampledSample(const float* __restrict__ plan
   return fmaf(0.25f, hval(nb), mid);
 }
 
+// ---- integer chroma from luma of a JPEG transcode (dec_group.cc, jpeg branch; the formula of JpegCoefKernel) -------------------------------------------------
+// What a 4:4:4 chroma coefficient takes from the quantised luma coefficient y at the same place: fac is the tile's ytox / ytob, ratio the host's division
+// 2048 x qt[0][i] / qt[c][i].  JpegCflFactor: fac * 2048 / 84, C++ division (truncates toward zero).  The sums a damaged stream can drive out of range are
+// formed in uint32_t: they wrap, nothing is undefined.  JpegIdctPlanesKernel and JpegGatherKernel both call these: one definition.
+__device__ __forceinline__ int32_t JpegCflFactor(int32_t fac) { return fac * 2048 / 84; }
+__device__ __forceinline__ int32_t JpegCflTerm(int32_t y, int32_t ratio, int32_t ff) {
+  const int32_t scale = (int32_t)((uint32_t)ratio * (uint32_t)ff);
+  return (int32_t)((uint32_t)y * (uint32_t)((int32_t)((uint32_t)scale + 1024u) >> 11) + 1024u) >> 11;
+}
+
 }  // namespace jxlhip

@@ -8,6 +8,9 @@ turned into JPEG XL by tests/jpeg_tools.transcode.  Legs (--legs, comma separate
   device_progressive   reconstruct_jpegs(progressive_on_device=True), i.e. JxlHipBatchSetOption("jpeg_device_progressive", 1): progressive scans entropy-coded on the GPU as well
   host     the same call with JxlHipBatchSetOption("jpeg_host_writer", 1): one entropy run, every file Huffman-coded on one host thread
   single   decoder_builder().reconstruct() file by file
+  pipeline the same files as reconstruction jobs of --job-files (16) through one Pipeline with its default options (Pipeline.submit_jpegs), all submitted, then waited
+           for in order: the pack pass, the copies and the host splice of job k run beside the entropy stages of the jobs behind it.  It is judged against leg `device`
+           of a build of the parent commit (PYTHONPATH, --legs device) on the same machine in the same call.
 
 Every leg adds the files to its decoder, reconstructs and fetches the bytes, --reps times after --warmup; the median is reported as ms per batch and files/s, and
 the bytes are compared with the source files once.  Prints one JSON line.  --legs single runs nothing of the batch interface: with PYTHONPATH pointing at a build
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--legs", default="device,host,single")
     ap.add_argument("--progressive", action="store_true")
     ap.add_argument("--cache", default=None)
+    ap.add_argument("--job-files", type=int, default=16)
     args = ap.parse_args()
     from PIL import Image
     import jpeg_cases as JC
@@ -90,8 +94,22 @@ def main():
         dec = jx.decoder_builder()
         return [dec.reconstruct(d)[1][1] for d in inputs], None
 
+    def pipeline_leg():
+        p = jx.Pipeline(0)
+        try:
+            tickets = [p.submit_jpegs(inputs[k:k + args.job_files], progressive_on_device=args.progressive) for k in range(0, len(inputs), args.job_files)]
+            got, dev, host = [], 0, 0
+            for t in tickets:
+                files, errors, _ = p.wait_jpegs(t)
+                assert errors == [None] * len(files), errors
+                got += files
+                dev += p.info("jpeg_device_images"); host += p.info("jpeg_host_images")
+        finally:
+            p.close()
+        return got, (dev, host)
+
     for leg in args.legs.split(","):
-        run = single_leg if leg == "single" else (lambda h=(leg == "host"), p=(leg == "device_progressive"): batch_leg(h, p))
+        run = single_leg if leg == "single" else pipeline_leg if leg == "pipeline" else (lambda h=(leg == "host"), p=(leg == "device_progressive"): batch_leg(h, p))
         times, counts = [], None
         for r in range(args.warmup + args.reps):
             t0 = time.perf_counter()

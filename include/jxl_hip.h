@@ -352,6 +352,34 @@ JxlDecoderStatus JxlHipBatchCopyJpeg(JxlHipBatch* batch, int index, uint8_t* dst
 int JxlHipBatchCanDecodeJpegPixels(JxlHipBatch* batch, int index);
 JxlDecoderStatus JxlHipBatchDecodeJpegPixels(JxlHipBatch* batch, void* hip_stream);
 JxlDecoderStatus JxlHipBatchJpegPixelsStatus(const JxlHipBatch* batch, int index);
+/* libjpeg's scaled decodes, exact: jpeg_scale = 2, 4, 8 gives the samples libjpeg gives for the original file at scale_num / scale_denom = 1 / jpeg_scale (what
+ * PIL.Image.draft asks for) — the ceil(xsize / s) x ceil(ysize / s) picture, s = jpeg_scale.  It is not the 1:8 decode of `downscale` (libjxl's float rendering of the LF
+ * image); the two cannot be combined.  jpeg_scale = 1 is JxlHipBatchSetOutput... at downscale 1, byte for byte; any other value is refused ("jpeg_scale must be 1, 2, 4
+ * or 8").  layout and resample may be NULL (interleaved samples; the picture's own size).  The scaled picture takes the place of the full-size one as the source of
+ * everything behind it: orientation, sample types, layouts, scale / bias, resize, crop (coordinates in the scaled picture) and mirror.  An output with jpeg_scale != 1 can
+ * only be set for an image JxlHipBatchCanDecodeJpegPixels takes (else JXL_DEC_ERROR with that call's reason) and is written by JxlHipBatchDecodeJpegPixels alone: a
+ * JxlHipBatchDecode writes the other images and JxlHipBatchFinish fails with "unsupported: image i has an output with jpeg_scale ...".
+ * The arithmetic (libjpeg-turbo jdmaster.c, jidctred.c, jdsample.c; CONST_BITS 13, PASS1_BITS 2, DESCALE(x, n) = (x + 2^(n-1)) >> n), with m = 8 / s:
+ *  1. IDCT size per component: n = m; while n < 8 and (hmax m) % (h_c n 2) == 0 and (vmax m) % (v_c n 2) == 0: n = 2 n.  Grey, 4:4:4, every luma and 4:2:2 chroma take
+ *     n = m; 4:2:0 chroma takes n = 2 m and needs no upsampling at all.  A block gives n x n samples; the component's real extent is
+ *     ceil(xsize h_c n / (hmax 8)) x ceil(ysize v_c n / (vmax 8)).
+ *  2. Dequantised input for every n: d[v][u] = coefficient x quantiser, as at full size (chroma from luma at 4:4:4 and the DC term included).
+ *  3. n = 8: jpeg_idct_islow.
+ *  4. n = 4: columns u = 0, 1, 2, 3, 5, 6, 7 (column 4 is never read); with i0 .. i7 the column's rows (i4 unused): t0 = i0 << 14, t2 = 15137 i2 - 6270 i6,
+ *     a0 = -1730 i7 + 11893 i5 - 17799 i3 + 8697 i1, a2 = -4176 i7 - 4926 i5 + 7373 i3 + 20995 i1; out0 = DESCALE(t0 + t2 + a2, 12), out1 = DESCALE(t0 - t2 + a0, 12),
+ *     out2 = DESCALE(t0 - t2 - a0, 12), out3 = DESCALE(t0 + t2 - a2, 12).  Pass 2: the same on the four workspace rows over entries 0, 1, 2, 3, 5, 6, 7, DESCALE(., 19).
+ *  5. n = 2: columns u = 0, 1, 3, 5, 7; t10 = i0 << 15, t0 = -5906 i7 + 6967 i5 - 10426 i3 + 29692 i1, outputs DESCALE(t10 +- t0, 13).  Pass 2: the same on the two rows
+ *     over entries 0, 1, 3, 5, 7, DESCALE(., 20).
+ *  6. n = 1: DESCALE(d[0][0], 3).
+ *  7. + 128, clamped to [0, 255], in all forms.
+ *  8. Upsampling of a component whose extent is half the output's (4:2:2 chroma only): the h2v1 "fancy" rule if m > 1 and its width > 2, else replication (every
+ *     s = 8 case: libjpeg turns fancy upsampling off when the smallest IDCT is 1 x 1).
+ *  9. Colour conversion as at full size.
+ * "jpeg_pixel_launches" counts two launches per group of the image table; images of scale 1 and scaled images form groups of their own (a batch that mixes them: four). */
+JxlDecoderStatus JxlHipBatchOutBufferSizeJpegScaled(const JxlHipBatch* batch, int index, const JxlPixelFormat* format, int jpeg_scale, const JxlHipOutputLayout* layout,
+                                                    const JxlHipOutputResample* resample, size_t* size);
+JxlDecoderStatus JxlHipBatchSetOutputJpegScaled(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int jpeg_scale, const JxlHipOutputLayout* layout,
+                                                const JxlHipOutputResample* resample);
 /* Decode-thread packing: lanes between active entropy-decode threads (64 = one stream per wavefront, 1 = 64 per wavefront). */
 void JxlHipBatchSetLaneStride(JxlHipBatch* batch, int lf, int hf);
 /* Tuning / testing knobs: "force_generic_idct", "hf_block_threads", "lds_code_budget", "debug_stop_after", "lf_wide_once" (the next LF stage of the batch takes the
@@ -444,11 +472,17 @@ int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* pipeline, const uint8_t* c
  * stages of the pipeline: the job shares coefficient sets and pixel planes with plain jobs, which may be mixed with it freely).  Eligible is what
  * JxlHipBatchCanDecodeJpegPixels takes; an image that is not eligible fails alone with that call's reason ("unsupported: libjpeg-exact decode of ..."), and so does an
  * image whose stream is damaged — a frame with a transform other than DCT8 is named as such.  layout: NULL = interleaved; each: NULL, or n JxlHipOutputResample of one
- * target size (crop, filter and mirror the image's own), as for JxlHipPipelineSubmitResampled.  There is no downscale: libjpeg's scaled IDCTs are other arithmetic.
+ * target size (crop, filter and mirror the image's own), as for JxlHipPipelineSubmitResampled.  There is no downscale (the 1:8 LF decode is libjxl's rendering, not libjpeg's
+ * samples); libjpeg's own scaled decodes: JxlHipPipelineSubmitJpegPixelsScaled below.
  * Destinations are sized as for JxlHipPipelineSubmitLayout / ...Resampled at downscale 1. */
 int64_t JxlHipPipelineSubmitJpegPixels(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
                                        void* const* host_out, const size_t* out_capacity, const JxlHipOutputLayout* layout /* NULL = interleaved */,
                                        const JxlHipOutputResample* each /* NULL, or n entries of one target size */);
+/* The same at one of libjpeg's scales (JxlHipBatchSetOutputJpegScaled above: jpeg_scale = 1, 2, 4, 8; a job takes one scale, another value refuses the submission):
+ * destinations are sized with JxlHipImageOutSizeJpegScaled, crops are in the scaled picture.  The other Submit calls have no jpeg_scale: only this decode writes it. */
+int64_t JxlHipPipelineSubmitJpegPixelsScaled(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format,
+                                             void* const* device_out, void* const* host_out, const size_t* out_capacity, const JxlHipOutputLayout* layout /* NULL = interleaved */,
+                                             const JxlHipOutputResample* each /* NULL, or n entries of one target size */, int jpeg_scale);
 /* A reconstruction job: the original JPEG file of every image, byte for byte (JxlHipBatchReconstructJpegs above, as stages of the pipeline: the entropy stages run
  * ahead on the side streams, one gather launch per job moves the coefficients out of the shared coefficient set — which is clean behind it —, and the pack pass, the
  * copies and the host splice of a job run in the thread that collects it, beside the entropy stages of the jobs behind it).  Such jobs mix freely with plain, 1:8,
@@ -497,6 +531,10 @@ JxlDecoderStatus JxlHipImageOutSizeLayout(const uint8_t* data, size_t size, cons
 /* The same for a resized output (JxlHipOutputResize; NULL = JxlHipImageOutSizeLayout): the size of the xsize x ysize picture. */
 JxlDecoderStatus JxlHipImageOutSizeResized(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout,
                                            const JxlHipOutputResize* resize, JxlBasicInfo* info, size_t* out_size);
+/* The same for libjpeg's scaled decode (JxlHipBatchSetOutputJpegScaled: jpeg_scale = 1, 2, 4, 8; layout and resample may be NULL): the size of the
+ * ceil(xsize / jpeg_scale) x ceil(ysize / jpeg_scale) picture, or of the target it is resampled to.  Whether the image is a JPEG transcode is not looked at here. */
+JxlDecoderStatus JxlHipImageOutSizeJpegScaled(const uint8_t* data, size_t size, const JxlPixelFormat* format, int jpeg_scale, const JxlHipOutputLayout* layout,
+                                              const JxlHipOutputResample* resample, JxlBasicInfo* info, size_t* out_size);
 /* Device arenas that batches and pipelines let go of are pooled per process (hipMalloc / hipFree of tens of GB cost seconds): JXL_HIP_ARENA_POOL_MB bounds the pool
  * (default 60 % of the device's memory, 0 = off); Trim hands every pooled block back to the runtime — for processes that share the GPU with another allocator —
  * and returns the bytes released; Held = bytes pooled right now. */

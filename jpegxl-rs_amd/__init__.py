@@ -192,6 +192,12 @@ def libjxl():
             "JxlHipBatchJpegStatus": (C.c_int, [vp, C.c_int]), "JxlHipBatchJpegSize": (sz, [vp, C.c_int]), "JxlHipBatchCopyJpeg": (C.c_int, [vp, C.c_int, vp, sz]),
             "JxlHipPipelineSubmitJpegPixels": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz),
                                                            C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample)]),
+            "JxlHipPipelineSubmitJpegPixelsScaled": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz),
+                                                                 C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.c_int]),
+            "JxlHipBatchOutBufferSizeJpegScaled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(sz)]),
+            "JxlHipBatchSetOutputJpegScaled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), vp, C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample)]),
+            "JxlHipImageOutSizeJpegScaled": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(JxlBasicInfo),
+                                                       C.POINTER(sz)]),
             "JxlHipBatchCanDecodeJpegPixels": (C.c_int, [vp, C.c_int]), "JxlHipBatchDecodeJpegPixels": (C.c_int, [vp, vp]), "JxlHipBatchJpegPixelsStatus": (C.c_int, [vp, C.c_int]),
             "JxlHipBatchSetLaneStride": (None, [vp, C.c_int, C.c_int]), "JxlHipBatchSetOption": (None, [vp, C.c_char_p, C.c_int]),
             "JxlHipBatchPrepare": (C.c_int, [vp, vp]), "JxlHipBatchDecode": (C.c_int, [vp, vp]),
@@ -682,6 +688,16 @@ def _resample(resize, crop, filter, mirror):
     return JxlHipOutputResample(rs.xsize, rs.ysize, rs.crop_x0, rs.crop_y0, rs.crop_xsize, rs.crop_ysize, f, 1 if mirror else 0)
 
 
+def _jpeg_scaled(jpeg_scale, downscale, rs):
+    """libjpeg's scaled decodes (include/jxl_hip.h JxlHipBatchSetOutputJpegScaled): refuses the combination with downscale; the resize of such an output always travels
+    as a JxlHipOutputResample (filter 0, no mirror: the ...Resized call, byte for byte)"""
+    if int(downscale) != 1:
+        raise GenericError("unsupported: jpeg_scale %d together with downscale %d (one of the two scaled decodes)" % (int(jpeg_scale), int(downscale)))
+    if isinstance(rs, JxlHipOutputResize):
+        rs = JxlHipOutputResample(rs.xsize, rs.ysize, rs.crop_x0, rs.crop_y0, rs.crop_xsize, rs.crop_ysize, 0, 0)
+    return rs
+
+
 def _per_image(value, n, is_one):
     """one value for the job, or a sequence of n per-image values -> (list of n, whether it was a sequence)"""
     if value is None or isinstance(value, (str, bytes)) or not hasattr(value, "__iter__"):
@@ -710,6 +726,7 @@ class BatchDecoder:
         self._n = 0
         self._fmt = []
         self._scale = []
+        self._jpeg_scale = []
         self._layouts = []
         self._resizes = []
 
@@ -722,9 +739,12 @@ class BatchDecoder:
         if status != JXL_DEC_SUCCESS:
             raise GenericError(last_error())
 
-    def _set_output(self, i, fmt, device_ptr, downscale, layout=None, resize=None):
+    def _set_output(self, i, fmt, device_ptr, downscale, layout=None, resize=None, jpeg_scale=1):
         L = libjxl()
-        if isinstance(resize, JxlHipOutputResample):
+        if jpeg_scale != 1:
+            resize = _jpeg_scaled(jpeg_scale, downscale, resize)
+            self._chk(L.JxlHipBatchSetOutputJpegScaled(self._h, i, C.byref(fmt), device_ptr, int(jpeg_scale), _byref(layout), _byref(resize)))
+        elif isinstance(resize, JxlHipOutputResample):
             self._chk(L.JxlHipBatchSetOutputResampled(self._h, i, C.byref(fmt), device_ptr, int(downscale), _byref(layout), C.byref(resize)))
         elif resize is not None:
             self._chk(L.JxlHipBatchSetOutputResized(self._h, i, C.byref(fmt), device_ptr, int(downscale), _byref(layout), C.byref(resize)))
@@ -736,11 +756,12 @@ class BatchDecoder:
             self._chk(L.JxlHipBatchSetOutputScaled(self._h, i, C.byref(fmt), device_ptr, int(downscale)))
         self._fmt.append(fmt)
         self._scale.append(int(downscale))
+        self._jpeg_scale.append(int(jpeg_scale))
         self._layouts.append(layout)
         self._resizes.append(resize)
 
     def add(self, data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, device_ptr=None, downscale=1,
-            planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False) -> int:
+            planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_scale=1) -> int:
         """downscale=8: the 1:8 decode (include/jxl_hip.h JxlHipBatchSetOutputScaled) — output(i) is the ceil(w / 8) x ceil(h / 8) picture; `data` may end behind
         the LF part of its frame.
         planar=True: one plane per channel, [C, H, W] with rows `align`ed and planes plane_stride bytes apart (0 = tight); scale / bias (up to four values, one per
@@ -748,7 +769,10 @@ class BatchDecoder:
         resize=(w, h): the output is w x h pixels, the decoded picture — oriented, at `downscale` — resampled with the antialiased triangle filter (torch's
         interpolate(mode="bilinear", antialias=True)); crop=(x0, y0, w, h): only that rectangle of the picture, as if cropped first (include/jxl_hip.h JxlHipOutputResize).
         filter="bilinear" (that triangle filter) | "bicubic" (antialiased cubic convolution, a = -0.5: torch's mode="bicubic", antialias=True); mirror=True: the resampled
-        picture is stored with its columns reversed (include/jxl_hip.h JxlHipOutputResample).  Both need resize; a call without them is the ...Resized call as before."""
+        picture is stored with its columns reversed (include/jxl_hip.h JxlHipOutputResample).  Both need resize; a call without them is the ...Resized call as before.
+        jpeg_scale=2 | 4 | 8: libjpeg's scaled decode of a JPEG transcode (include/jxl_hip.h JxlHipBatchSetOutputJpegScaled) — the ceil(w / s) x ceil(h / s) picture
+        PIL's draft() gives for the original file, sample for sample, as the source of everything above (a crop is in the scaled picture).  Only decode_jpeg_pixels()
+        writes such an output (decode() + finish() fail the image); not together with downscale."""
         layout = _layout(planar, plane_stride, scale, bias)
         rs = _resize(resize, crop) if filter is None and not mirror else _resample(resize, crop, filter, mirror)
         L = libjxl()
@@ -763,14 +787,14 @@ class BatchDecoder:
         if i < 0:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
-        self._set_output(i, fmt, device_ptr, downscale, layout, rs)
+        self._set_output(i, fmt, device_ptr, downscale, layout, rs, jpeg_scale)
         self._n += 1
         return i
 
     def add_many(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, threads=4, endianness=Endianness.Native, align=0, downscale=1,
-                 planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False) -> int:
+                 planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_scale=1) -> int:
         """Parses the images of `datas` (bytes objects) on `threads` host threads and appends them in order (JxlHipBatchAddImages);
-        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale, planar, plane_stride, scale, bias, resize, crop, filter, mirror: as for add()."""
+        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale, planar, plane_stride, scale, bias, resize, crop, filter, mirror, jpeg_scale: as for add()."""
         L = libjxl()
         layout = _layout(planar, plane_stride, scale, bias)
         rs = _resize(resize, crop) if filter is None and not mirror else _resample(resize, crop, filter, mirror)
@@ -788,7 +812,7 @@ class BatchDecoder:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
         for k in range(n):
-            self._set_output(first + k, fmt, device_ptrs[k] if device_ptrs is not None else None, downscale, layout, rs)
+            self._set_output(first + k, fmt, device_ptrs[k] if device_ptrs is not None else None, downscale, layout, rs, jpeg_scale)
         self._n += n
         return first
 
@@ -798,6 +822,7 @@ class BatchDecoder:
         self._n = 0
         self._fmt = []
         self._scale = []
+        self._jpeg_scale = []
         self._layouts = []
         self._resizes = []
 
@@ -808,7 +833,10 @@ class BatchDecoder:
 
     def out_size(self, i) -> int:
         s = C.c_size_t()
-        if isinstance(self._resizes[i], JxlHipOutputResample):
+        if self._jpeg_scale[i] != 1:
+            rs = _jpeg_scaled(self._jpeg_scale[i], self._scale[i], self._resizes[i])
+            self._chk(libjxl().JxlHipBatchOutBufferSizeJpegScaled(self._h, i, C.byref(self._fmt[i]), self._jpeg_scale[i], _byref(self._layouts[i]), _byref(rs), C.byref(s)))
+        elif isinstance(self._resizes[i], JxlHipOutputResample):
             self._chk(libjxl().JxlHipBatchOutBufferSizeResampled(self._h, i, C.byref(self._fmt[i]), self._scale[i], _byref(self._layouts[i]), C.byref(self._resizes[i]), C.byref(s)))
         elif self._resizes[i] is not None:
             self._chk(libjxl().JxlHipBatchOutBufferSizeResized(self._h, i, C.byref(self._fmt[i]), self._scale[i], _byref(self._layouts[i]), C.byref(self._resizes[i]), C.byref(s)))
@@ -940,8 +968,9 @@ def arena_pool_trim() -> int:
 
 
 def image_out_size(data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, downscale=1, planar=False, plane_stride=0, scale=None, bias=None,
-                   resize=None, crop=None):
+                   resize=None, crop=None, jpeg_scale=1):
     """(JxlBasicInfo, bytes of the decoded image in that format) from the headers alone — host-only (JxlHipImageOutSize).
+    jpeg_scale=2 | 4 | 8: the size of libjpeg's scaled decode, as for BatchDecoder.add (JxlHipImageOutSizeJpegScaled); not together with downscale.
     downscale=8: the size of the 1:8 decode (JxlHipImageOutSizeScaled); the info stays that of the full-size image.
     planar, plane_stride, scale, bias: the layout as for BatchDecoder.add (JxlHipImageOutSizeLayout); a layout the image or the sample type does not take raises.
     resize, crop: the size of the resized output, as for BatchDecoder.add (JxlHipImageOutSizeResized); a crop that leaves the image raises."""
@@ -950,7 +979,11 @@ def image_out_size(data: bytes, dtype="uint8", num_channels=0, endianness=Endian
     buf = np.frombuffer(data, dtype=np.uint8)
     layout = _layout(planar, plane_stride, scale, bias)
     rs = _resize(resize, crop)
-    if rs is not None:
+    if jpeg_scale != 1:
+        rs = _jpeg_scaled(jpeg_scale, downscale, rs)
+        if libjxl().JxlHipImageOutSizeJpegScaled(buf.ctypes.data, len(data), C.byref(fmt), int(jpeg_scale), _byref(layout), _byref(rs), C.byref(info), C.byref(size)) != JXL_DEC_SUCCESS:
+            raise GenericError(last_error())
+    elif rs is not None:
         if libjxl().JxlHipImageOutSizeResized(buf.ctypes.data, len(data), C.byref(fmt), int(downscale), _byref(layout), C.byref(rs), C.byref(info), C.byref(size)) != JXL_DEC_SUCCESS:
             raise GenericError(last_error())
     elif layout is not None:
@@ -1010,7 +1043,7 @@ class Pipeline:
     __del__ = close
 
     def submit(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, host_ptrs=None, capacities=None, endianness=Endianness.Native, align=0, downscale=1,
-               planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_pixels=False) -> int:
+               planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_pixels=False, jpeg_scale=1) -> int:
         """Job of len(datas) images (bytes objects).  device_ptrs / host_ptrs: one destination address per image (exactly one of the two lists); the bytes objects and
         the destinations are kept referenced until wait().  downscale=8: the job is decoded at 1:8 (JxlHipPipelineSubmitScaled).  planar, plane_stride, scale, bias:
         the layout of every image of the job, as for BatchDecoder.add (JxlHipPipelineSubmitLayout).  resize, crop: every image of the job comes out resize[0] x resize[1]
@@ -1020,9 +1053,13 @@ class Pipeline:
         4-tuples or Nones; a string or a number is one filter / mirror for the job, any other iterable is read as per-image values).  Whenever one of them is a sequence, or filter / mirror is set, the job goes out with one JxlHipOutputResample per image
         (JxlHipPipelineSubmitResampled): one target size, everything else the image's own.
         jpeg_pixels: a job of libjpeg-exact pixels (JxlHipPipelineSubmitJpegPixels; BatchDecoder.decode_jpeg_pixels as pipeline stages) with the same keywords; an image
-        that decode does not take fails alone, downscale other than 1 is refused here."""
+        that decode does not take fails alone, downscale other than 1 is refused here.
+        jpeg_scale=2 | 4 | 8 (with jpeg_pixels only; one scale per job): libjpeg's scaled decode, as for BatchDecoder.add (JxlHipPipelineSubmitJpegPixelsScaled) —
+        destinations are sized with image_out_size(..., jpeg_scale=), crops are in the scaled picture."""
         if jpeg_pixels and int(downscale) != 1:
             raise GenericError("unsupported: libjpeg-exact decode of an output with downscale %d (libjpeg's scaled IDCTs are other arithmetic)" % int(downscale))
+        if jpeg_scale != 1 and not jpeg_pixels:
+            raise GenericError("unsupported: jpeg_scale %s in a job that is not a libjpeg-exact one (jpeg_pixels=True: only that decode writes libjpeg's scaled picture)" % (jpeg_scale,))
         layout = _layout(planar, plane_stride, scale, bias)
         n = len(datas)
         crops, seq_c = _per_image(crop, n, lambda v: len(v) == 4 and all(isinstance(x, (int, np.integer)) for x in v))
@@ -1043,7 +1080,10 @@ class Pipeline:
         if jpeg_pixels:
             if each is None and resize is not None:
                 each = (JxlHipOutputResample * max(1, n))(*[_resample(resize, crop, None, False) for _ in range(n)])      # (filter 0, no mirror: the ...Resized call, byte for byte)
-            t = libjxl().JxlHipPipelineSubmitJpegPixels(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, _byref(layout), each)
+            if jpeg_scale != 1:
+                t = libjxl().JxlHipPipelineSubmitJpegPixelsScaled(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, _byref(layout), each, int(jpeg_scale))
+            else:
+                t = libjxl().JxlHipPipelineSubmitJpegPixels(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, _byref(layout), each)
         elif each is not None:
             t = libjxl().JxlHipPipelineSubmitResampled(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), _byref(layout), each)
         elif rs is not None:

@@ -762,7 +762,8 @@ size_t Batch::OutputStride(const ImageHeader& ih, const OutputSpec& o, uint32_t*
 }
 // Orientations 5..8 transpose the image (codestream_header.rs JxlOrientation); applied unless the caller keeps it.
 // (1:8 decode, OutputSpec::downscale == 8: one pixel per 8x8 block of the stored picture, the orientation applied to that picture)
-static uint32_t Scaled(uint32_t v, const OutputSpec& o) { return o.downscale == 8 ? (v + 7) / 8 : v; }
+// (libjpeg's scaled decode, OutputSpec::jpeg_scale = 2, 4, 8: ceil(side / jpeg_scale) of the stored picture — jdmaster.c jpeg_calc_output_dimensions —, never both)
+static uint32_t Scaled(uint32_t v, const OutputSpec& o) { return o.downscale == 8 ? (v + 7) / 8 : o.jpeg_scale > 1 ? (v + o.jpeg_scale - 1) / o.jpeg_scale : v; }
 // (resized output, OutputSpec::resize_w / resize_h: that picture is the source of the resize, the output has the target size)
 uint32_t Batch::SourceWidth(const ImageHeader& ih, const OutputSpec& o) { return Scaled((!o.keep_orientation && ih.orientation > 4) ? ih.ysize : ih.xsize, o); }
 uint32_t Batch::SourceHeight(const ImageHeader& ih, const OutputSpec& o) { return Scaled((!o.keep_orientation && ih.orientation > 4) ? ih.xsize : ih.ysize, o); }
@@ -889,6 +890,13 @@ void Batch::SetOutput(int i, const OutputSpec& o) {
     const std::string why = DownscaleRefusal(i);
     if (!why.empty()) throw ParseError(why, true);
     if (o.only_frame >= 0 || o.upto_frame >= 0) throw ParseError("unsupported: downscaled decode of a single frame of an animation", true);
+  }
+  if (o.jpeg_scale != 1) {
+    if (o.jpeg_scale != 2 && o.jpeg_scale != 4 && o.jpeg_scale != 8) throw ParseError("jpeg_scale must be 1, 2, 4 or 8", false);
+    if (o.downscale != 1) throw ParseError("unsupported: jpeg_scale " + std::to_string(o.jpeg_scale) + " together with downscale " + std::to_string(o.downscale) + " (one of the two scaled decodes)", true);
+    // (only the libjpeg-exact decode writes such an output: what it does not take has no scaled picture at all)
+    std::string why;
+    if (!CanDecodeJpegPixelsAs(i, o, &why)) throw ParseError(why, true);
   }
   e.out = o;
   if (o.only_frame >= pub_[i].num_units) throw ParseError("non-coalesced output: no such frame", false);
@@ -1627,6 +1635,9 @@ void Batch::FillFrameCommon(int i, const uint8_t* cbase, const PrepareState& st)
   f.hf_written = (uint32_t*)(dwork_ + hfw_off_) + i;
   f.od = FillOutput(e, dwork_, dbig_);
   f.upsampling = p.upsampling; f.img_w = e.ih.xsize; f.img_h = e.ih.ysize;
+  // (an output with jpeg_scale: DecodeJpegPixels writes it from its own table; the write stage of a Run, which fails such an image, stays inside the scaled picture —
+  // OutputKernel, the only writer of a frame CanDecodeJpegPixelsAs takes, is bounded by img_w x img_h)
+  if (e.frame_index == 0 && e.out.jpeg_scale > 1) { f.img_w = (e.ih.xsize + e.out.jpeg_scale - 1) / e.out.jpeg_scale; f.img_h = (e.ih.ysize + e.out.jpeg_scale - 1) / e.out.jpeg_scale; }
   if (DecodedAtEighth(i)) { f.lf_only = 1; f.img_w = (p.width + 7) / 8; f.img_h = (p.height + 7) / 8; }     // (the picture LfOutputKernel writes; out_stride is SetOutput's, of the same picture)
   if (p.upsampling > 1) { f.up_weights = (const float*)(cbase + c.up_weights); for (int k = 0; k < 4; k++) f.up_plane[k] = (float*)(dbig_ + o.up_plane[k]); }
   f.post_mode = e.complex ? 1 : 0;
@@ -2720,6 +2731,7 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
       if (!cfg.debug_stop_after && any_scaled_) LaunchLfOutput(dframes_, n, max_bw_, max_bh_, stream_v);   // 1:8 frames: the LF image through the colour transform and the write stage
       if (any_complex_ && !cfg.debug_stop_after) EnqueuePostOps(stream_v);   // frame tail of multi-frame / feature images
       if (!cfg.debug_stop_after) EnqueueResizes(stream_v);
+      FailJpegScaledOutputs(stream_v);
       DebugSync("output / frame tail", stream_v);
       CheckLaunches("filters / output / frame tail");
       rec(6);
@@ -2766,13 +2778,25 @@ static std::string DeviceStatusMessage(uint32_t status, int frame, bool* unsuppo
   return "corrupt stream (device status " + std::to_string(status) + ", frame " + std::to_string(frame) + ")";
 }
 
+// An output with OutputSpec::jpeg_scale != 1 is the picture of libjpeg's scaled decode, which the float pipeline has no way to compute: behind a Run the image's
+// status word is set, so that Finish fails it — alone, the others are written — with the reason below.  (Its write stage has stayed inside the scaled picture:
+// FrameDev::img_w / img_h.)
+void Batch::FailJpegScaledOutputs(void* stream_v) {
+  static const uint32_t kRefused = kErrUnsupported;
+  for (size_t u = 0; u < images_.size(); u++)
+    if (images_[u]->frame_index == 0 && images_[u]->out.jpeg_scale != 1) HIP_CHECK(hipMemcpyAsync(dwork_ + status_off_ + u * 4, &kRefused, 4, hipMemcpyHostToDevice, (hipStream_t)stream_v));
+}
+
 void Batch::Finish(void* stream_v) {
   vec<uint32_t> status;
   FinishStatus(stream_v, &status);
   for (size_t i = 0; i < status.size(); i++) {
     if (!status[i]) continue;
     bool unsupported = false;
-    const std::string msg = DeviceStatusMessage(status[i], (int)i, &unsupported);
+    std::string msg = DeviceStatusMessage(status[i], (int)i, &unsupported);
+    if (unsupported && images_[i]->frame_index == 0 && images_[i]->out.jpeg_scale != 1)
+      msg = "unsupported: image " + std::to_string(images_[i]->pub_index) + " has an output with jpeg_scale " + std::to_string(images_[i]->out.jpeg_scale) +
+            ", which only the libjpeg-exact decode writes (DecodeJpegPixels)";
     throw ParseError(msg, unsupported);
   }
 }
@@ -3395,7 +3419,12 @@ std::string JpegPixelTableRefusal(const FramePlan& p) {
 }
 }  // namespace
 
-bool Batch::CanDecodeJpegPixels(int i, std::string* why) const {
+bool Batch::CanDecodeJpegPixels(int i, std::string* why) const { return CanDecodeJpegPixelsAs(i, images_[pub_[i].first_unit]->out, why); }
+// ... with the output given: SetOutput asks before it takes a spec with jpeg_scale.
+// The write stage of a Run relies on this list for such an output (FillFrameCommon sets FrameDev::img_w / img_h to the scaled picture): without gaborish, EPF,
+// upsampling, extra channels and image features a frame reaches the caller's buffer through OutputKernel alone, which is bounded by img_w x img_h.  The fused filter
+// kernels, the EPF kernels that write, the Modular write and the frame tail are bounded by the frame's own size — whoever lets such a frame in here must bound those too.
+bool Batch::CanDecodeJpegPixelsAs(int i, const OutputSpec& out, std::string* why) const {
   auto no = [&](const std::string& m) { if (why) *why = "unsupported: libjpeg-exact decode of " + m; return false; };
   const ImageEntry& e = *images_[pub_[i].first_unit];
   const FramePlan& p = e.plan;
@@ -3406,7 +3435,7 @@ bool Batch::CanDecodeJpegPixels(int i, std::string* why) const {
   // Y at full resolution, both chroma channels with the same shifts: 4:4:4, 4:2:2, 4:2:0 (4:4:0 and the rest: libjpeg has rules for them that no test here could pin)
   if (p.hs[1] || p.vs[1] || p.hs[0] != p.hs[2] || p.vs[0] != p.vs[2] || p.hs[0] > 1 || p.vs[0] > 1 || (p.vs[0] && !p.hs[0]))
     return no("chroma sampling other than 4:4:4, 4:2:2 and 4:2:0");
-  if (e.out.downscale != 1) return no("an output with downscale 8 (libjpeg's scaled IDCTs are other arithmetic)");
+  if (out.downscale != 1) return no("an output with downscale 8 (libjpeg's scaled IDCTs are other arithmetic)");
   if (e.ih.xsize > 65535 || e.ih.ysize > 65535) return no("an image larger than a JPEG file can be");
   if (!(p.single_section && p.ac_code.empty())) {      // (HfGlobal of a one-group frame is parsed by Prepare)
     const std::string t = JpegPixelTableRefusal(p);
@@ -3422,7 +3451,10 @@ size_t Batch::PlanJpegPixels() {
   jpeg_pixel_images_ = jpeg_pixel_launches_ = 0;
   jpeg_pixel_table_.clear(); jpeg_pixel_table_image_.clear(); jpeg_pixel_groups_.clear();
   if (!prepared_) throw ParseError("PlanJpegPixels: the batch is not prepared", false);
+  // entries of scale 1 first, the scaled ones (OutputSpec::jpeg_scale) behind them: the two kinds take different kernels and never share a launch group
   vec<JpegPixelImage>& table = jpeg_pixel_table_;
+  vec<JpegPixelImage> scaled_table;
+  vec<int> scaled_image;
   for (int i = 0; i < n; i++) {
     std::string why;
     if (!CanDecodeJpegPixels(i, &why)) { jpeg_pixel_results_[i].error = why; continue; }
@@ -3459,16 +3491,43 @@ size_t Batch::PlanJpegPixels() {
     }
     t.npos = walk ? g.grid_w[0] * g.grid_h[0] : (uint32_t)g.nblk; t.ncomp = ncomp; t.frame = (uint32_t)u;
     t.width = e.ih.xsize; t.height = e.ih.ysize; t.hs = ncomp == 3 ? g.hs[1] : 0; t.vs = ncomp == 3 ? g.vs[1] : 0;
-    table.push_back(t); jpeg_pixel_table_image_.push_back(i);
-  }
-  for (size_t first = 0; first < table.size(); first += kJpegPixelGroupMax) {
-    JpegPixelGroup g{(uint32_t)first, (uint32_t)std::min<size_t>(kJpegPixelGroupMax, table.size() - first), 0, 0, 0};
-    for (uint32_t k = 0; k < g.count; k++) {
-      const JpegPixelImage& t = table[first + k];
-      g.max_npos = std::max(g.max_npos, t.npos); g.max_w = std::max(g.max_w, t.width); g.max_h = std::max(g.max_h, t.height);
+    t.scale = e.out.jpeg_scale;
+    if (t.scale == 1) { table.push_back(t); jpeg_pixel_table_image_.push_back(i); continue; }
+    // libjpeg's scaled decode (jdmaster.c): the smallest IDCT is m = 8 / scale; a component whose sampling factors are below the largest takes twice that as long as
+    // both of its dimensions still need upsampling by a factor of two — 4:2:0 chroma does, once (n = 2 m: it then has the picture's extent), 4:2:2 chroma does not
+    // (its height has the picture's already).  hmax / h_c = 1 << hs and vmax / v_c = 1 << vs for chroma, 1 for luma.
+    const uint32_t m = 8 / t.scale;
+    t.out_w = (t.width + t.scale - 1) / t.scale; t.out_h = (t.height + t.scale - 1) / t.scale;
+    for (uint32_t c = 0; c < ncomp; c++) {
+      const uint32_t rh = c ? 1u << t.hs : 1u, rv = c ? 1u << t.vs : 1u;      // hmax / h_c, vmax / v_c
+      uint32_t nn = m;
+      while (nn < 8 && (rh * m) % (nn * 2) == 0 && (rv * m) % (nn * 2) == 0) nn *= 2;
+      t.n[c] = nn; t.pitch[c] = g.grid_w[c] * nn;
+      t.ext_w[c] = (uint32_t)(((uint64_t)t.width * nn + (uint64_t)rh * 8 - 1) / ((uint64_t)rh * 8));
+      t.ext_h[c] = (uint32_t)(((uint64_t)t.height * nn + (uint64_t)rv * 8 - 1) / ((uint64_t)rv * 8));
     }
-    jpeg_pixel_groups_.push_back(g);
+    // (the grids hold the full-size extents — `fits` above —, so grid x n holds these; a plane of grid_w x n by grid_h x n bytes lies inside the frame's float plane)
+    t.chroma_up = ncomp == 3 && t.hs && !t.vs ? 1u : 0u;      // 4:2:2: ext_w = ceil(out_w / 2), all of the picture's height
+    t.chroma_fancy = m > 1 ? 1u : 0u;                         // (jdsample.c: no fancy upsampling when the smallest IDCT is 1 x 1)
+    scaled_table.push_back(t); scaled_image.push_back(i);
   }
+  const size_t plain = table.size();
+  table.insert(table.end(), scaled_table.begin(), scaled_table.end());
+  jpeg_pixel_table_image_.insert(jpeg_pixel_table_image_.end(), scaled_image.begin(), scaled_image.end());
+  auto group_runs = [&](size_t from, size_t to, bool scaled) {
+    for (size_t first = from; first < to; first += kJpegPixelGroupMax) {
+      JpegPixelGroup g{(uint32_t)first, (uint32_t)std::min<size_t>(kJpegPixelGroupMax, to - first), 0, 0, 0};
+      g.scaled = scaled ? 1u : 0u;
+      for (uint32_t k = 0; k < g.count; k++) {
+        const JpegPixelImage& t = table[first + k];
+        g.max_npos = std::max(g.max_npos, t.npos);
+        g.max_w = std::max(g.max_w, scaled ? t.out_w : t.width); g.max_h = std::max(g.max_h, scaled ? t.out_h : t.height);
+      }
+      jpeg_pixel_groups_.push_back(g);
+    }
+  };
+  group_runs(0, plain, false);
+  group_runs(plain, table.size(), true);
   return table.size();
 }
 

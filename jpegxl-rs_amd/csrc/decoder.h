@@ -30,13 +30,16 @@ struct OutputSpec {
   uint32_t downscale = 1;         // 1, or 8: the 1:8 decode — the output is the frame's LF image, ceil(w / 8) x ceil(h / 8) pixels, one per 8x8 block, through the colour transform and the
                                   // write stage (LfOutputKernel); no AC coefficient is decoded, no IDCT, no restoration filter runs.  Single-frame VarDCT images without extra
                                   // channels, patches, splines, noise or upsampling (Batch::DownscaleRefusal)
+  uint32_t jpeg_scale = 1;        // 1, 2, 4, 8: libjpeg's scaled decode of a JPEG transcode (scale_num / scale_denom = 1 / jpeg_scale: jdmaster.c, jidctred.c) — the picture is the
+                                  // ceil(w / jpeg_scale) x ceil(h / jpeg_scale) one libjpeg gives for the original file, from reduced IDCTs.  Other than 1: only with downscale 1, only
+                                  // for images Batch::CanDecodeJpegPixels takes (SetOutput), and written by Batch::DecodeJpegPixels alone — Run fails such an image
   // ---- layout (Batch and Pipeline outputs; the libjxl look-alike API, previews and kept animation canvases are interleaved)
   bool planar = false;            // channel slot c (grey or G, alpha / R, G, B, alpha) is a plane of its own at c x plane_stride: rows of one sample per pixel, oriented width x sample size
                                   // rounded up to `align` apart; the output is num_channels x plane_stride bytes
   size_t plane_stride = 0;        // 0 = tight (oriented height x row stride), else at least that and a multiple of the sample size
   bool affine = false;            // float16 / float32 output: slot c is stored as fmaf(v, scale[c], bias[c])
   float scale[4] = {1.0f, 1.0f, 1.0f, 1.0f}, bias[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  // ---- resize (Batch and Pipeline outputs): the picture the output would have held without it — oriented, at downscale 1 or 8, the "source" — is resampled to
+  // ---- resize (Batch and Pipeline outputs): the picture the output would have held without it — oriented, at downscale 1 or 8 or at jpeg_scale, the "source" — is resampled to
   // resize_w x resize_h with the antialiased filter resize_filter (ResizeAxis, decoder.cc); the output's size, strides and layout go by the target size
   uint32_t resize_w = 0, resize_h = 0;     // 0 x 0 = off, else 1 .. 65535 each
   uint32_t crop_x0 = 0, crop_y0 = 0, crop_w = 0, crop_h = 0;   // rectangle of the source that is resampled (all 0 = the whole picture): exactly crop first, then resize
@@ -197,9 +200,11 @@ class Batch {
   // conditions of CanReconstructJpeg without those on the `jbrd` box, 4:4:4 / 4:2:2 / 4:2:0 or grey, at downscale 1; CanDecodeJpegPixels is host-only and says
   // "unsupported: libjpeg-exact decode of ..." otherwise (the quantisation table of a one-group frame is only known after Prepare: DecodeJpegPixels looks again).
   // DecodeJpegPixels runs the entropy stages once for the whole batch; an image that is not eligible, or whose stream is damaged, fails alone: jpeg_pixel_result(i).
-  // Throws only for what concerns the whole batch (HIP errors, no prepared images).
+  // Throws only for what concerns the whole batch (HIP errors, no prepared images).  An output with OutputSpec::jpeg_scale = 2, 4, 8 is libjpeg's scaled decode of the
+  // file (jidctred.c's reduced IDCTs): such images take JpegIdctScaledKernel / JpegColorOutScaledKernel, in launch groups of their own behind those of scale 1.
   struct JpegPixelResult { bool ok = false; std::string error; };
   bool CanDecodeJpegPixels(int i, std::string* why = nullptr) const;
+  bool CanDecodeJpegPixelsAs(int i, const OutputSpec& out, std::string* why) const;      // the same for an output that is not set yet (SetOutput)
   void DecodeJpegPixels(void* stream);
   // DecodeJpegPixels in its steps, for callers that order the stages themselves (Pipeline jobs of this kind):
   //   PlanJpegPixels            host only, after Prepare: eligibility, the component grids, the image table and its launch groups; an image that is refused gets its
@@ -211,6 +216,7 @@ class Batch {
   size_t PlanJpegPixels();
   void EnqueueJpegPixelTable(void* stream, bool fail_refused);
   void HarvestJpegPixels(const vec<uint32_t>& per_unit);
+  size_t jpeg_pixel_group_count() const { return jpeg_pixel_groups_.size(); }      // (after PlanJpegPixels: every group is one launch of each of the two pixel kernels)
   const JpegPixelResult* jpeg_pixel_result(int i) const { return i >= 0 && (size_t)i < jpeg_pixel_results_.size() ? &jpeg_pixel_results_[(size_t)i] : nullptr; }
   void FinishStatus(void* stream, vec<uint32_t>* per_unit);
   // Copies frame i's pixels to host memory (after Finish).
@@ -303,6 +309,7 @@ class Batch {
   vec<JpegPixelImage> jpeg_pixel_table_;       // PlanJpegPixels: the image table (host copy; the upload reads it), the image of every entry, the launch groups
   vec<int> jpeg_pixel_table_image_;
   std::vector<JpegPixelGroup> jpeg_pixel_groups_;
+  void FailJpegScaledOutputs(void* stream);    // Run's tail: the status words of images with OutputSpec::jpeg_scale != 1, which only DecodeJpegPixels writes
   uint8_t* djpeg_table_ = nullptr; size_t jpeg_table_cap_ = 0;   // the table on the device
   void EnqueueJpegIdct(void* stream);          // JpegIdctPlanesKernel per group, then ZeroFailedCoefKernel for the frames it failed
   void EnqueueJpegColorOut(void* stream);      // JpegColorOutKernel per group

@@ -7,6 +7,8 @@
 //                        reconstruction jobs of the pipeline, one launch per group of images
 //   JpegColorOutKernel   "fancy" chroma upsampling (jdsample.c h2v1 / h2v2 triangle filters; plain replication for planes at most two samples wide), fixed-point
 //                        YCbCr -> RGB (jdcolor.c), sample k enters the write stage as (float)k x (1 / 255)
+//   JpegIdctScaledKernel / JpegColorOutScaledKernel   the same two stages for libjpeg's scaled decodes (scale 1/2, 1/4, 1/8: jdmaster.c, jidctred.c): reduced IDCTs
+//                        of 4 x 4, 2 x 2 or 1 x 1 samples per block (8 x 8 for 4:2:0 chroma at 1/2) -> planes of n x n samples per block -> the scaled picture
 // Every sum that a damaged stream can drive out of range is formed in uint32_t: it wraps, nothing is undefined; the samples of such a stream mean nothing, but every
 // address is derived from the host's table alone.
 #include "kernels.h"
@@ -41,6 +43,23 @@ template <int N> __device__ __forceinline__ void JpegIdct1D(const uint32_t i[8],
   out[3] = Descale<N>(t13 + a0); out[4] = Descale<N>(t13 - a0);
 }
 
+// jidctred.c's 1-D transforms of the reduced IDCTs, same constants' scale (CONST_BITS 13).  jpeg_idct_4x4: four results from i0, i2, i6 (even part, one bit more
+// than the 8-point form: i0 << 14) and i1, i3, i5, i7; i4 is not an input.  jpeg_idct_2x2: two results from i0 (<< 15) and i1, i3, i5, i7.
+template <int N> __device__ __forceinline__ void JpegIdct1D4(const uint32_t i[8], int32_t out[4]) {
+  const uint32_t t0 = i[0] << 14;
+  const uint32_t t2 = i[2] * 15137u + i[6] * (uint32_t)-6270;
+  const uint32_t t10 = t0 + t2, t12 = t0 - t2;
+  const uint32_t a0 = i[7] * (uint32_t)-1730 + i[5] * 11893u + i[3] * (uint32_t)-17799 + i[1] * 8697u;
+  const uint32_t a2 = i[7] * (uint32_t)-4176 + i[5] * (uint32_t)-4926 + i[3] * 7373u + i[1] * 20995u;
+  out[0] = Descale<N>(t10 + a2); out[3] = Descale<N>(t10 - a2);
+  out[1] = Descale<N>(t12 + a0); out[2] = Descale<N>(t12 - a0);
+}
+template <int N> __device__ __forceinline__ void JpegIdct1D2(const uint32_t i[8], int32_t out[2]) {
+  const uint32_t t10 = i[0] << 15;
+  const uint32_t t0 = i[7] * (uint32_t)-5906 + i[5] * 6967u + i[3] * (uint32_t)-10426 + i[1] * 29692u;
+  out[0] = Descale<N>(t10 + t0); out[1] = Descale<N>(t10 - t0);
+}
+
 __device__ __forceinline__ uint32_t ClampU8(int32_t v) { return (uint32_t)min(max(v, 0), 255); }
 
 // The integer IDCT straight from the HF stage's coefficient planes (FrameDev::coeff, FrameDev::lfq): what JpegCoefKernel (kernels_features.hip) would have
@@ -63,8 +82,24 @@ __device__ __forceinline__ uint32_t ClampU8(int32_t v) { return (uint32_t)min(ma
 //   the group's 65536 dwords and 16-byte aligned.
 //   LDS: 72 dwords per block.  Pass 1's column stores are ds_write_b32 (banks (a / 4) % 32, one 32-lane half at a time): the half's lanes (j = 0 .. 3, k) hit
 //   banks (8 j + k + 8 r) % 32, all different.  Pass 2 reads rows with ds_read_b128.
-__global__ __launch_bounds__(256) void JpegIdctPlanesKernel(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table) {
-  __shared__ __attribute__((aligned(16))) int32_t ws[kIdctWaves][kIdctBlocksPerWave * kIdctBlockStride];
+// One body for both kernels (JpegIdctBody): kScaled = false is the 8 x 8 form above with n = 8 a constant.  kScaled = true is libjpeg's scaled decode
+// (JpegPixelImage::scale = 2, 4, 8) with the reduced transforms of jidctred.c: positions, lanes, the mapping of a component block to its frame block, its group and its
+// 64 dwords, the two 16-byte loads of column u = k, chroma from luma with Y's column kept in registers, the DC term from lfq, kErrVarblock and the clamped coef_off are
+// shared; what differs is the transform and the store.
+//   Component c takes the n x n transform, n = im.n[c] (8, 4, 2, 1): components of one image differ (4:2:0: luma 8 / scale, chroma twice that), so the blocks of one
+//   wavefront do — n is a per-lane value, the two barriers of a step stay outside every branch on it (steps and `walk` are uniform over the workgroup as above).
+//   Every lane loads and zeroes its 8 dwords whatever n is — the columns and rows the reduced transforms ignore, all of a block's AC terms at n = 1 —: the coefficient
+//   set must be clean for its next user.
+//   Pass 1 (lane = column k): n = 8 all columns; n = 4 all but column 4 (jpeg_idct_4x4 never reads it); n = 2 columns 0, 1, 3, 5, 7; n = 1 lane 0 alone, which hands
+//   the dequantised DC term through.  The lane writes n results, rows r = 0 .. n - 1, to w[8 r + k].  Pass 2 (lanes k < n, row k): eight workspace entries (of which
+//   the transform uses those of the columns above) -> n samples, + 128, clamped, one store of n bytes at row by x n + k, column bx x n of the plane (pitch
+//   grid_w x n, so every store is aligned to its own size).
+//   LDS: 72 dwords per block as in the 8 x 8 form.  Pass 1's stores are ds_write_b32, banks (a / 4) % 32, one 32-lane half at a time: the half's lanes (j = 0 .. 3,
+//   k) hit banks (8 j + k + 8 r) % 32 in store r — the 8 x 8 form's pattern with lanes missing (column 4 at n = 4, the even columns but 0 at n = 2, all but lane 0 at
+//   n = 1) and with only the first n of its eight stores: a subset of a conflict-free pattern.  Pass 2 reads rows with two ds_read_b128 from the lanes k < n, at the
+//   8 x 8 form's addresses 72 j + 8 k: again a subset.  The entries of a row that pass 1 did not write (column 4; the even columns) are read and not used.
+template <bool kScaled> __device__ __forceinline__ void JpegIdctBody(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table,
+                                                                    int32_t (*ws)[kIdctBlocksPerWave * kIdctBlockStride]) {
   const JpegPixelImage& im = table[blockIdx.z];
   const FrameDev& f = frames[im.frame];
   if (blockIdx.x * (kIdctWaves * kIdctBlocksPerWave) >= im.npos || *f.status != 0) return;     // (uniform over the workgroup; a failed frame's planes are zeroed by ZeroFailedCoefKernel)
@@ -84,18 +119,18 @@ __global__ __launch_bounds__(256) void JpegIdctPlanesKernel(const FrameDev* __re
   for (uint32_t step = 0; step < steps; step++) {
     if (walk) c = step;
     const uint32_t ch = im.ncomp == 1 ? 1u : (c == 0 ? 1u : c == 1 ? 0u : 2u);
-    const uint32_t hs = c ? im.hs : 0u, vs = c ? im.vs : 0u, gw = im.grid_w[c];
+    const uint32_t hs = c ? im.hs : 0u, vs = c ? im.vs : 0u;
+    const uint32_t n = kScaled ? im.n[c] : 8u, pitch = kScaled ? im.pitch[c] : im.grid_w[c] * 8u;      // (scale 1: the branches on n below fold away)
     const uint32_t sx = bx << hs, sy = by << vs;            // the frame block that carries this component block
     const bool live = pos < im.npos && by < im.grid_h[c] && sx < f.bw && sy < f.bh;
     if (live) {
       const size_t o = (size_t)sy * f.bw + sx;
-      // the entropy stages of a damaged stream may have placed other transforms than DCT8: the frame fails through its status word (its samples are not delivered)
       if (k == 0 && (f.blk_info[o] & 31u) != 0) atomicOr(f.status, (uint32_t)kErrVarblock);
       const uint32_t g = (sy / 32) * f.xgroups + sx / 32;
       const uint32_t coff = min(f.coef_off[o] & ~63u, 65536u - 64u);
       int4* const src = (int4*)(f.coeff[ch] + (size_t)g * 65536 + coff + k * 8);
       const int4 lo = src[0], hi = src[1];
-      if (lo.x | lo.y | lo.z | lo.w) src[0] = make_int4(0, 0, 0, 0);      // consumed: the planes stay clean for the next decode
+      if (lo.x | lo.y | lo.z | lo.w) src[0] = make_int4(0, 0, 0, 0);      // consumed — also what a reduced transform does not use: the planes stay clean for the next decode
       if (hi.x | hi.y | hi.z | hi.w) src[1] = make_int4(0, 0, 0, 0);
       int32_t cf[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};   // cf[v]: coefficient (v, u = k)
       const int4 qlo = *(const int4*)(im.qt[c] + k * 8), qhi = *(const int4*)(im.qt[c] + k * 8 + 4);
@@ -106,8 +141,7 @@ __global__ __launch_bounds__(256) void JpegIdctPlanesKernel(const FrameDev* __re
 #pragma unroll
           for (int r = 0; r < 8; r++) ycol[r] = cf[r];
         } else {
-          const int32_t fac = c == 1 ? (int32_t)f.ytox[tile] : (int32_t)f.ytob[tile];
-          const int32_t ff = JpegCflFactor(fac);
+          const int32_t ff = JpegCflFactor(c == 1 ? (int32_t)f.ytox[tile] : (int32_t)f.ytob[tile]);
           const int32_t* __restrict__ ratio = im.cfl_ratio[c - 1] + k * 8;   // 2048 qt[0][i] / qt[c][i], the host's division
           const int4 rlo = *(const int4*)ratio, rhi = *(const int4*)(ratio + 4);
           const int32_t rt[8] = {rlo.x, rlo.y, rlo.z, rlo.w, rhi.x, rhi.y, rhi.z, rhi.w};
@@ -119,26 +153,61 @@ __global__ __launch_bounds__(256) void JpegIdctPlanesKernel(const FrameDev* __re
       uint32_t in[8];
 #pragma unroll
       for (int r = 0; r < 8; r++) in[r] = (uint32_t)(int32_t)(int16_t)cf[r] * (uint32_t)q[r];     // (int16_t: the width JPEG gives a coefficient, as JpegCoefKernel stores it)
-      int32_t col[8];
-      JpegIdct1D<11>(in, col);
+      if (n == 8) {
+        int32_t col[8];
+        JpegIdct1D<11>(in, col);
 #pragma unroll
-      for (int r = 0; r < 8; r++) w[r * 8 + k] = col[r];
+        for (int r = 0; r < 8; r++) w[r * 8 + k] = col[r];
+      } else if (n == 4) {
+        if (k != 4) {
+          int32_t col[4];
+          JpegIdct1D4<12>(in, col);
+#pragma unroll
+          for (int r = 0; r < 4; r++) w[r * 8 + k] = col[r];
+        }
+      } else if (n == 2) {
+        if (k == 0 || (k & 1)) {
+          int32_t col[2];
+          JpegIdct1D2<13>(in, col);
+          w[k] = col[0]; w[8 + k] = col[1];
+        }
+      } else if (k == 0) w[0] = (int32_t)in[0];
     }
     __syncthreads();
-    if (live) {
+    if (live && k < n) {
       uint32_t in[8];
       const int4 lo = *(const int4*)(w + k * 8), hi = *(const int4*)(w + k * 8 + 4);
       in[0] = (uint32_t)lo.x; in[1] = (uint32_t)lo.y; in[2] = (uint32_t)lo.z; in[3] = (uint32_t)lo.w;
       in[4] = (uint32_t)hi.x; in[5] = (uint32_t)hi.y; in[6] = (uint32_t)hi.z; in[7] = (uint32_t)hi.w;
-      int32_t row[8];
-      JpegIdct1D<18>(in, row);
-      uint2 px;
-      px.x = ClampU8(row[0] + 128) | ClampU8(row[1] + 128) << 8 | ClampU8(row[2] + 128) << 16 | ClampU8(row[3] + 128) << 24;
-      px.y = ClampU8(row[4] + 128) | ClampU8(row[5] + 128) << 8 | ClampU8(row[6] + 128) << 16 | ClampU8(row[7] + 128) << 24;
-      *(uint2*)(im.plane[c] + ((size_t)by * 8 + k) * ((size_t)gw * 8) + (size_t)bx * 8) = px;
+      uint8_t* const dst = im.plane[c] + ((size_t)by * n + k) * (size_t)pitch + (size_t)bx * n;
+      if (n == 8) {
+        int32_t row[8];
+        JpegIdct1D<18>(in, row);
+        uint2 px;
+        px.x = ClampU8(row[0] + 128) | ClampU8(row[1] + 128) << 8 | ClampU8(row[2] + 128) << 16 | ClampU8(row[3] + 128) << 24;
+        px.y = ClampU8(row[4] + 128) | ClampU8(row[5] + 128) << 8 | ClampU8(row[6] + 128) << 16 | ClampU8(row[7] + 128) << 24;
+        *(uint2*)dst = px;
+      } else if (n == 4) {
+        int32_t row[4];
+        JpegIdct1D4<19>(in, row);
+        *(uint32_t*)dst = ClampU8(row[0] + 128) | ClampU8(row[1] + 128) << 8 | ClampU8(row[2] + 128) << 16 | ClampU8(row[3] + 128) << 24;
+      } else if (n == 2) {
+        int32_t row[2];
+        JpegIdct1D2<20>(in, row);
+        *(uint16_t*)dst = (uint16_t)(ClampU8(row[0] + 128) | ClampU8(row[1] + 128) << 8);
+      } else *dst = (uint8_t)ClampU8(Descale<3>(in[0]) + 128);
     }
     if (step + 1 < steps) __syncthreads();                  // (the next step's pass 1 overwrites the workspace)
   }
+}
+
+__global__ __launch_bounds__(256) void JpegIdctPlanesKernel(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table) {
+  __shared__ __attribute__((aligned(16))) int32_t ws[kIdctWaves][kIdctBlocksPerWave * kIdctBlockStride];
+  JpegIdctBody<false>(frames, table, ws);
+}
+__global__ __launch_bounds__(256) void JpegIdctScaledKernel(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table) {
+  __shared__ __attribute__((aligned(16))) int32_t ws[kIdctWaves][kIdctBlocksPerWave * kIdctBlockStride];
+  JpegIdctBody<true>(frames, table, ws);
 }
 
 // The quantised coefficients of a group of images from the HF stage's planes into the int16 arena of the JPEG writer (jpeg_write.hip; decoder.cc Batch::PlanJpegWrite):
@@ -285,12 +354,49 @@ __global__ __launch_bounds__(256) void JpegColorOutKernel(const FrameDev* __rest
   }
 }
 
+// JpegColorOutKernel for libjpeg's scaled decodes: the picture is im.out_w x im.out_h, component c's plane has im.pitch[c] bytes per row and im.ext_w[c] x im.ext_h[c]
+// real samples.  Luma always has the picture's extent, chroma too at 4:4:4 and at 4:2:0 (whose chroma took the IDCT of twice the size: jdmaster.c) — no upsampling at
+// all; 4:2:2 chroma (im.chroma_up) has half the width: jdsample.c's h2v1 "fancy" rule if the smallest IDCT is larger than 1 x 1 (im.chroma_fancy) and the plane is more
+// than two samples wide, else plain replication.  A thread takes the output pixels (2 t, 2 t + 1) of a row, as above; colour conversion and the write stage are the same.
+__global__ __launch_bounds__(256) void JpegColorOutScaledKernel(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table) {
+  const JpegPixelImage& im = table[blockIdx.z];
+  const FrameDev& f = frames[im.frame];
+  const uint32_t t = blockIdx.x * 32 + threadIdx.x, x0 = t * 2, y = blockIdx.y * 8 + threadIdx.y;
+  if (x0 >= im.out_w || y >= im.out_h || *f.status != 0) return;
+  const uint32_t npix = x0 + 1 < im.out_w ? 2 : 1;
+  const float k255 = 1.0f / 255;
+  const uint8_t* __restrict__ yrow = im.plane[0] + (size_t)y * im.pitch[0];
+  const int32_t lum[2] = {yrow[x0], npix == 2 ? yrow[x0 + 1] : 0};      // (a row of n = 1 samples per block may end at x0)
+  if (im.ncomp == 1) {
+    for (uint32_t i = 0; i < npix; i++) { const float v = (float)lum[i] * k255; StorePixel(f.od, (int)im.out_w, (int)im.out_h, (int)(x0 + i), (int)y, v, v, v, 1.0f); }
+    return;
+  }
+  int32_t cb[2], cr[2];
+  if (!im.chroma_up) {
+    const size_t o = (size_t)y * im.pitch[1] + x0, o1 = o + (npix == 2 ? 1 : 0);
+    cb[0] = im.plane[1][o]; cb[1] = im.plane[1][o1]; cr[0] = im.plane[2][o]; cr[1] = im.plane[2][o1];
+  } else {
+    // (t < ext_w: out_w <= 2 ext_w.  A width of at most 2 makes ChromaPair replicate)
+    const uint32_t cw = im.chroma_fancy ? im.ext_w[1] : 1u;
+    ChromaPair(im.plane[1], im.pitch[1], 0, cw, im.ext_h[1], t, y, cb);
+    ChromaPair(im.plane[2], im.pitch[1], 0, cw, im.ext_h[1], t, y, cr);
+  }
+  for (uint32_t i = 0; i < npix; i++) {
+    const int32_t u = cb[i] - 128, v = cr[i] - 128;
+    const int32_t r = min(max(lum[i] + ((91881 * v + 32768) >> 16), 0), 255);
+    const int32_t g = min(max(lum[i] + ((-22554 * u - 46802 * v + 32768) >> 16), 0), 255);
+    const int32_t b = min(max(lum[i] + ((116130 * u + 32768) >> 16), 0), 255);
+    StorePixel(f.od, (int)im.out_w, (int)im.out_h, (int)(x0 + i), (int)y, (float)r * k255, (float)g * k255, (float)b * k255, 1.0f);
+  }
+}
+
 }  // namespace
 
 void LaunchJpegIdctGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream) {
   if (!g.count || g.count > kJpegPixelGroupMax || !g.max_npos || !g.max_w || !g.max_h) return;
   const uint32_t per_wg = kIdctWaves * kIdctBlocksPerWave;
-  hipLaunchKernelGGL(JpegIdctPlanesKernel, dim3((g.max_npos + per_wg - 1) / per_wg, 1, g.count), dim3(256), 0, (hipStream_t)stream, frames, table + g.first);
+  if (g.scaled) hipLaunchKernelGGL(JpegIdctScaledKernel, dim3((g.max_npos + per_wg - 1) / per_wg, 1, g.count), dim3(256), 0, (hipStream_t)stream, frames, table + g.first);
+  else hipLaunchKernelGGL(JpegIdctPlanesKernel, dim3((g.max_npos + per_wg - 1) / per_wg, 1, g.count), dim3(256), 0, (hipStream_t)stream, frames, table + g.first);
 }
 void LaunchJpegGatherGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream) {
   if (!g.count || g.count > kJpegPixelGroupMax || !g.max_npos) return;
@@ -299,7 +405,8 @@ void LaunchJpegGatherGroup(const FrameDev* frames, const JpegPixelImage* table, 
 }
 void LaunchJpegColorOutGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream) {
   if (!g.count || g.count > kJpegPixelGroupMax || !g.max_npos || !g.max_w || !g.max_h) return;
-  hipLaunchKernelGGL(JpegColorOutKernel, dim3((g.max_w + 63) / 64, (g.max_h + 7) / 8, g.count), dim3(32, 8), 0, (hipStream_t)stream, frames, table + g.first);
+  if (g.scaled) hipLaunchKernelGGL(JpegColorOutScaledKernel, dim3((g.max_w + 63) / 64, (g.max_h + 7) / 8, g.count), dim3(32, 8), 0, (hipStream_t)stream, frames, table + g.first);
+  else hipLaunchKernelGGL(JpegColorOutKernel, dim3((g.max_w + 63) / 64, (g.max_h + 7) / 8, g.count), dim3(32, 8), 0, (hipStream_t)stream, frames, table + g.first);
 }
 
 }  // namespace jxlhip

@@ -1002,6 +1002,29 @@ JxlDecoderStatus JxlHipBatchSetOutputResampled(JxlHipBatch* h, int i, const JxlP
                                                const JxlHipOutputResample* resample) {
   return BatchSetOutput(h, i, format, device_buffer, downscale, layout, nullptr, "JxlHipBatchSetOutputResampled", resample, true);
 }
+// libjpeg's scaled decodes (OutputSpec::jpeg_scale): the ...Resampled calls at downscale 1 with a scale of their own; layout and resample may be NULL
+static bool JpegScaleOk(int jpeg_scale, const char* who) {
+  if (jpeg_scale == 1 || jpeg_scale == 2 || jpeg_scale == 4 || jpeg_scale == 8) return true;
+  SetLastError(std::string(who) + ": jpeg_scale must be 1, 2, 4 or 8");
+  return false;
+}
+JxlDecoderStatus JxlHipBatchOutBufferSizeJpegScaled(const JxlHipBatch* h, int i, const JxlPixelFormat* format, int jpeg_scale, const JxlHipOutputLayout* layout,
+                                                    const JxlHipOutputResample* resample, size_t* size) {
+  const char* who = "JxlHipBatchOutBufferSizeJpegScaled";
+  OutputSpec o;
+  if (!JpegScaleOk(jpeg_scale, who) || !BatchSpec(h, i, format, 1, layout, nullptr, resample, resample != nullptr, &o, who)) return JXL_DEC_ERROR;
+  o.jpeg_scale = (uint32_t)jpeg_scale;
+  try { *size = Batch::OutputSize(h->b->image(i).ih, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
+}
+JxlDecoderStatus JxlHipBatchSetOutputJpegScaled(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int jpeg_scale, const JxlHipOutputLayout* layout,
+                                                const JxlHipOutputResample* resample) {
+  const char* who = "JxlHipBatchSetOutputJpegScaled";
+  OutputSpec o;
+  if (!JpegScaleOk(jpeg_scale, who) || !BatchSpec(h, i, format, 1, layout, nullptr, resample, resample != nullptr, &o, who)) return JXL_DEC_ERROR;
+  o.jpeg_scale = (uint32_t)jpeg_scale;
+  o.device_ptr = device_buffer;
+  try { h->b->SetOutput(i, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }   // (an image the libjpeg-exact decode does not take, a crop that leaves the scaled picture)
+}
 void JxlHipBatchSetLaneStride(JxlHipBatch* h, int lf, int hf) {
   auto ok = [](int v) { return v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64; };
   if (ok(lf)) h->b->cfg.lane_stride_lf = lf;
@@ -1179,14 +1202,14 @@ int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* h, const uint8_t* const* d
   } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
 }
 // a libjpeg-exact job (Pipeline::Submit, jpeg_pixels): the layout and the per-image resamples of the calls above, no downscale
-int64_t JxlHipPipelineSubmitJpegPixels(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
-                                       const size_t* out_capacity, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each) {
-  const char* who = "JxlHipPipelineSubmitJpegPixels";
+static int64_t PipelineSubmitJpegPixels(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                                        const size_t* out_capacity, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, int jpeg_scale, const char* who) {
+  if (!JpegScaleOk(jpeg_scale, who)) return -1;
   try {
     OutputSpec base;
     if (!h || !FormatToSpec(format, &base)) { SetLastError(std::string(who) + ": bad pixel format"); return -1; }
     if (!ApplyLayout(layout, &base, who)) return -1;
-    base.downscale = 1;
+    base.downscale = 1; base.jpeg_scale = (uint32_t)jpeg_scale;
     if (!each) return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity, nullptr, /*jpeg_pixels=*/true);
     std::vector<OutputSpec> specs((size_t)std::max(n, 0), base);
     for (int i = 0; i < n; i++) {
@@ -1200,6 +1223,15 @@ int64_t JxlHipPipelineSubmitJpegPixels(JxlHipPipeline* h, const uint8_t* const* 
     if (n > 0) { base.resize_w = each[0].xsize; base.resize_h = each[0].ysize; }
     return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity, specs.empty() ? nullptr : specs.data(), /*jpeg_pixels=*/true);
   } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
+}
+int64_t JxlHipPipelineSubmitJpegPixels(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                                       const size_t* out_capacity, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each) {
+  return PipelineSubmitJpegPixels(h, datas, sizes, n, format, device_out, host_out, out_capacity, layout, each, 1, "JxlHipPipelineSubmitJpegPixels");
+}
+// the same at one of libjpeg's scales (OutputSpec::jpeg_scale): one scale per job
+int64_t JxlHipPipelineSubmitJpegPixelsScaled(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
+                                             void* const* host_out, const size_t* out_capacity, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, int jpeg_scale) {
+  return PipelineSubmitJpegPixels(h, datas, sizes, n, format, device_out, host_out, out_capacity, layout, each, jpeg_scale, "JxlHipPipelineSubmitJpegPixelsScaled");
 }
 JxlDecoderStatus JxlHipPipelineWait(JxlHipPipeline* h, int64_t ticket, int* image_status, int n, float* end_ms) {
   try {
@@ -1290,6 +1322,26 @@ static JxlDecoderStatus ImageOutSize(const uint8_t* data, size_t size, const Jxl
     bool have_container = false, has_jbrd = false;
     // (1:8: a prefix of the file will do — the headers say the size)
     if (!ExtractCodestream(data, size, &sh->cs, &have_container, &has_jbrd, nullptr) && downscale == 1) return JXL_DEC_NEED_MORE_INPUT;
+    uint64_t bitpos = 0;
+    ParseImageHeader(sh->cs, &sh->ih, &bitpos);
+    sh->ih.have_container = have_container;
+    if (info) FillBasicInfo(sh->ih, info, false);
+    if (out_size) *out_size = Batch::OutputSize(sh->ih, o);
+    return JXL_DEC_SUCCESS;
+  } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
+}
+JxlDecoderStatus JxlHipImageOutSizeJpegScaled(const uint8_t* data, size_t size, const JxlPixelFormat* format, int jpeg_scale, const JxlHipOutputLayout* layout,
+                                              const JxlHipOutputResample* resample, JxlBasicInfo* info, size_t* out_size) {
+  const char* who = "JxlHipImageOutSizeJpegScaled";
+  if (!JpegScaleOk(jpeg_scale, who)) return JXL_DEC_ERROR;
+  try {
+    OutputSpec o;
+    if (!FormatToSpec(format, &o)) { SetLastError("bad pixel format"); return JXL_DEC_ERROR; }
+    if (!ApplyLayout(layout, &o, who) || (resample && !ApplyResample(resample, &o, who))) return JXL_DEC_ERROR;
+    o.jpeg_scale = (uint32_t)jpeg_scale;
+    std::shared_ptr<ImageShared> sh(new ImageShared());
+    bool have_container = false, has_jbrd = false;
+    if (!ExtractCodestream(data, size, &sh->cs, &have_container, &has_jbrd, nullptr)) return JXL_DEC_NEED_MORE_INPUT;
     uint64_t bitpos = 0;
     ParseImageHeader(sh->cs, &sh->ih, &bitpos);
     sh->ih.have_container = have_container;

@@ -374,6 +374,11 @@ struct alignas(16) JpegPixelImage {
   uint32_t ncomp;
   uint32_t frame;                        // FrameDev of the image: status word, block info, coefficient planes, OutputDesc
   uint32_t width, height, hs, vs;
+  // libjpeg's scaled decode (OutputSpec::jpeg_scale = 2, 4, 8; entries of scale 1 leave all of this 0 apart from `scale`): component c takes the n[c] x n[c] IDCT
+  // (jdmaster.c: 8 / scale, twice that for 4:2:0 chroma), its plane has pitch[c] = grid_w[c] x n[c] bytes per row and n[c] rows per block row, of which ext_w[c] x
+  // ext_h[c] are real samples; the picture is out_w x out_h = ceil(width / scale) x ceil(height / scale).  chroma_up: 0 = the chroma planes have the picture's
+  // extent, 1 = half its width (4:2:2): h2v1 upsampling, "fancy" if chroma_fancy (8 / scale > 1) and the plane is more than two samples wide, else replication
+  uint32_t scale, n[3], pitch[3], ext_w[3], ext_h[3], out_w, out_h, chroma_up, chroma_fancy;
   // JpegGatherKernel (reconstruction: Batch::PlanJpegWrite fills the same entry, without planes): where the image's int16 coefficients go — natural order, component c
   // from block comp_first[c] on (at 4:4:4 too), 16-byte aligned — and every component's own shifts against the frame's block grid
   int16_t* coef_out;
@@ -382,9 +387,11 @@ struct alignas(16) JpegPixelImage {
   alignas(16) int32_t cfl_ratio[2][64];
 };
 constexpr uint32_t kJpegPixelGroupMax = 32768;       // images per launch (gridDim.z is limited to 65535)
-struct JpegPixelGroup { uint32_t first, count, max_npos, max_w, max_h; };      // a run of the table served by one launch per kernel, the grids sized for its largest image
-void LaunchJpegIdctGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);       // JpegIdctPlanesKernel
-void LaunchJpegColorOutGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);   // JpegColorOutKernel, behind it on the same stream
+// a run of the table served by one launch per kernel, the grids sized for its largest image (max_w x max_h: of the pictures that are written); scaled: a run of
+// entries with scale 2, 4, 8, which take the two ...Scaled kernels — entries of scale 1 and scaled ones never share a run
+struct JpegPixelGroup { uint32_t first, count, max_npos, max_w, max_h, scaled = 0; };
+void LaunchJpegIdctGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);       // JpegIdctPlanesKernel / JpegIdctScaledKernel
+void LaunchJpegColorOutGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);   // JpegColorOutKernel / JpegColorOutScaledKernel, behind it on the same stream
 void LaunchJpegGatherGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);     // JpegGatherKernel (max_w / max_h unused)
 void LaunchCopyPlane(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t w, uint32_t h, void* stream);
 // ---- resized output (OutputSpec::resize_w / resize_h): separable antialiased filter (triangle or cubic convolution), horizontal pass then vertical, f32 throughout.

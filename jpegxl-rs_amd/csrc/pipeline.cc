@@ -162,6 +162,14 @@ int64_t Pipeline::Submit(const uint8_t* const* datas, const size_t* sizes, int n
     for (int i = 0; each && i < n; i++) scaled |= each[i].downscale != 1;
     if (scaled) throw ParseError("JxlHipPipelineSubmitJpegPixels: unsupported: libjpeg-exact decode of an output with downscale 8 (libjpeg's scaled IDCTs are other arithmetic)", true);
   }
+  {
+    // libjpeg's scaled decodes (OutputSpec::jpeg_scale): one scale per job, and only the libjpeg-exact decode writes such an output
+    const uint32_t js = spec.jpeg_scale;
+    if (js != 1 && js != 2 && js != 4 && js != 8) throw ParseError("JxlHipPipelineSubmit: jpeg_scale must be 1, 2, 4 or 8", false);
+    for (int i = 0; each && i < n; i++)
+      if (each[i].jpeg_scale != js) throw ParseError("JxlHipPipelineSubmit: image " + std::to_string(i) + " asks for jpeg_scale " + std::to_string(each[i].jpeg_scale) + ", the job for " + std::to_string(js) + ": one scale per job", false);
+    if (js != 1 && !jpeg_pixels) throw ParseError("JxlHipPipelineSubmit: unsupported: jpeg_scale " + std::to_string(js) + " in a job that is not a libjpeg-exact one (only that decode writes libjpeg's scaled picture)", true);
+  }
   std::shared_ptr<Job> job(new Job());
   job->datas.assign(datas, datas + n); job->sizes.assign(sizes, sizes + n);
   if (device_out) job->device_out.assign(device_out, device_out + n);
@@ -289,6 +297,8 @@ void Pipeline::PrepareJob(Job* j, int worker) {
       if (index[(size_t)i] < 0) { j->result.error[(size_t)i] = errors[(size_t)i]; continue; }
       OutputSpec o = j->each.empty() ? j->spec : j->each[(size_t)i];
       o.device_ptr = j->device_out.empty() ? nullptr : j->device_out[(size_t)i];
+      // (an image the libjpeg-exact decode does not take has no scaled picture: it stays in the batch at scale 1, unwritten, and fails with that decode's reason below)
+      if (j->kind == kJpegPixels && o.jpeg_scale != 1 && !bt.CanDecodeJpegPixels(index[(size_t)i], nullptr)) o.jpeg_scale = 1;
       size_t need = 0;
       std::string refusal;
       try { need = bt.OutputSizeOf(index[(size_t)i], o); } catch (const ParseError& e) { refusal = e.what(); }     // (a plane_stride this image does not fit, a crop that leaves it: Batch::LayoutRefusal / ResizeRefusal)
@@ -358,7 +368,7 @@ void Pipeline::PrepareJob(Job* j, int worker) {
     {
       std::lock_guard<std::mutex> lock(mu_);
       last_info_["jpeg_pixel_images"] = (int64_t)jpeg_table;
-      last_info_["jpeg_pixel_launches"] = 2 * (int64_t)((jpeg_table + kJpegPixelGroupMax - 1) / kJpegPixelGroupMax);
+      last_info_["jpeg_pixel_launches"] = j->kind == kJpegPixels ? 2 * (int64_t)bt.jpeg_pixel_group_count() : 0;
       want_big_ = std::max(want_big_, bt.big_bytes_wanted()); want_coef_ = std::max(want_coef_, bt.coef_bytes_wanted());
       if (!bt.uses_shared_big() || !bt.uses_shared_coef()) private_plane_jobs_++;
       bt.StageBytes(last_stage_bytes_);

@@ -63,7 +63,8 @@ class Pipeline {
   // Returns the job's ticket (>= 0).
   // jpeg_pixels: a libjpeg-exact job (Batch::DecodeJpegPixels as pipeline stages) — every image is decoded to the samples libjpeg gives for the JPEG file it was
   // transcoded from; an image Batch::CanDecodeJpegPixels refuses fails alone with that reason.  `spec` and `each` mean what they mean otherwise; downscale 8 is refused here.
-  // each (optional, n entries): image i is decoded to each[i] instead of `spec` — same format, layout, downscale and target size as `spec`; crop, filter and mirror are its own.
+  // spec.jpeg_scale (2, 4, 8: libjpeg's scaled decode) is taken by such a job only, one scale per job; any other job with it is refused.
+  // each (optional, n entries): image i is decoded to each[i] instead of `spec` — same format, layout, downscale, jpeg_scale and target size as `spec`; crop, filter and mirror are its own.
   int64_t Submit(const uint8_t* const* datas, const size_t* sizes, int n, const OutputSpec& spec, void* const* device_out, void* const* host_out, const size_t* out_capacity,
                  const OutputSpec* each = nullptr, bool jpeg_pixels = false);
   // A reconstruction job (Batch::ReconstructJpegs as pipeline stages): the original JPEG file of every image, byte for byte.  No output spec and no destinations —

@@ -12,6 +12,9 @@ turned into JPEG XL by tests/jpeg_tools.transcode.  Output of the two device leg
   pipeline     --jobs jobs of the same --files transcodes through Pipeline.submit(jpeg_pixels=True), all submitted before the first wait: the entropy stages of later jobs
                overlap the integer pixel path of earlier ones.  ms_per_batch is the wall time from the first submit to the last wait over --jobs; "stages_ms_per_job" are
                the pipeline's own HIP-event brackets (the `timed` option, JxlHipPipelineCollectTimes) per job: the largest of them is the step of the schedule
+               --resize W,H: every image of the jobs comes out W x H (the triangle filter); --jpeg_scale 2 | 4 | 8: libjpeg's scaled decode (Pipeline.submit(jpeg_scale=)),
+               the source of that resize.  With either, the pixels are not compared with Pillow here (tests/test_jpeg_scaled_pixels.py does); "pixel_half_ms_per_job" is
+               idct_ms + out_ms of the brackets: integer IDCT, colour-out and the resizes
   pipeline_float  the same jobs without jpeg_pixels: libjxl's rendering through the float tail — what a loader of these files gets from a Pipeline otherwise
 
 Every leg runs --reps times after --warmup; the median is reported.  The first run of a leg is checked: pixels and reconstruct equal Pillow's decode of the source
@@ -49,6 +52,8 @@ def main():
     ap.add_argument("--legs", default="pixels,decode,reconstruct")
     ap.add_argument("--cache", default=None)
     ap.add_argument("--jobs", type=int, default=6, help="pipeline legs: jobs per repetition")
+    ap.add_argument("--resize", default=None, help="pipeline legs: W,H of every output")
+    ap.add_argument("--jpeg_scale", type=int, default=1, help="pipeline leg: libjpeg's scaled decode (2, 4, 8)")
     args = ap.parse_args()
     import numpy as np
     from PIL import Image
@@ -127,8 +132,19 @@ def main():
                 out[leg] = "this build has no Pipeline.submit(jpeg_pixels=True)"
                 continue
             p = jx.Pipeline(0, timed=1, reserve_frames=args.files, reserve_width=w, reserve_height=h)
-            bufs = [[torch.zeros(w * h * 3, dtype=torch.uint8, device="cuda:0") for _ in inputs] for _ in range(min(args.jobs, 3))]
+            resize = tuple(int(v) for v in args.resize.split(",")) if args.resize else None
+            scaled = exact and args.jpeg_scale != 1
+            if scaled and "jpeg_scale" not in jx.Pipeline.submit.__code__.co_varnames:
+                out[leg] = "this build has no Pipeline.submit(jpeg_scale=)"
+                p.close()
+                continue
+            ow, oh = resize if resize else (-(-w // args.jpeg_scale), -(-h // args.jpeg_scale)) if scaled else (w, h)
+            bufs = [[torch.zeros(ow * oh * 3, dtype=torch.uint8, device="cuda:0") for _ in inputs] for _ in range(min(args.jobs, 3))]
             kw = dict(jpeg_pixels=True) if exact else {}
+            if resize:
+                kw["resize"] = resize
+            if scaled:
+                kw["jpeg_scale"] = args.jpeg_scale
             stages = None
             for r in range(args.warmup + args.reps):
                 if r == args.warmup:
@@ -141,7 +157,9 @@ def main():
                     assert st == [0] * len(inputs), st
                 torch.cuda.synchronize()
                 times.append((time.perf_counter() - t0) * 1e3 / args.jobs)
-                if r == 0:
+                if r == 0 and (resize or scaled):
+                    diff = None
+                elif r == 0:
                     got = [bufs[0][k].cpu().numpy().reshape(h, w, 3) for k in range(args.distinct)]
                     diff = max(int(np.abs(g.astype(int) - x.astype(int)).max()) for g, x in zip(got, want))
                     assert not exact or diff == 0, "pixels differ from Pillow's decode of the source files"
@@ -149,8 +167,9 @@ def main():
             stages = {k: round(v / max(runs, 1), 2) for k, v in st.items()}
             out[leg] = report(times)
             out[leg].update(jobs_per_rep=args.jobs, max_difference_from_pillow=diff, stages_ms_per_job=stages, timed_jobs=runs, private_plane_jobs=p.info("private_plane_jobs"))
+            out[leg].update(output_size=[ow, oh], device_bytes=p.info("device_bytes"), pixel_half_ms_per_job=round(stages.get("idct_ms", 0) + stages.get("out_ms", 0), 3))
             if exact:
-                out[leg]["pixel_launches"] = p.info("jpeg_pixel_launches")
+                out[leg].update(pixel_launches=p.info("jpeg_pixel_launches"), jpeg_scale=args.jpeg_scale)
             p.close()
             del p, bufs
         elif leg == "reconstruct":

@@ -380,6 +380,33 @@ JxlDecoderStatus JxlHipBatchOutBufferSizeJpegScaled(const JxlHipBatch* batch, in
                                                     const JxlHipOutputResample* resample, size_t* size);
 JxlDecoderStatus JxlHipBatchSetOutputJpegScaled(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int jpeg_scale, const JxlHipOutputLayout* layout,
                                                 const JxlHipOutputResample* resample);
+/* The integer resample of libjpeg-exact outputs: Pillow's 8-bit resize, byte for byte.  JxlHipBatchSetOutputJpegResampled is JxlHipBatchSetOutputJpegScaled with
+ * `flags`; flags = 0 is that call, byte for byte; bit 0, JXL_HIP_RESAMPLE_U8, selects the integer resample; every other bit is refused.  Sizes are those of
+ * JxlHipBatchOutBufferSizeJpegScaled / JxlHipImageOutSizeJpegScaled.  With the flag the u8 output equals
+ * numpy.asarray(PIL.Image.open(file).crop(box).resize((xsize, ysize), BILINEAR | BICUBIC)) (after draft() for jpeg_scale, after the orientation) byte for byte: crop, then
+ * resize — not resize(size, box=box), which reads taps outside the box.
+ * The rule.  The source is the u8 picture the output would have held without a resize: libjpeg's samples after jpeg_scale, after the orientation (or as stored, under
+ * "keep_orientation"), in the output's channel slots (grey replicated, the alpha slot 255), cut to the crop — an axis sees n_in = the crop's side.  Per axis, n_in -> n_out,
+ * with kernel k and radius r of `filter` as given for JxlHipOutputResample above:
+ *   scale = n_in / n_out and s = max(scale, 1), in double; target sample i is centred at c = scale x (i + 0.5) and takes the source samples j of
+ *   [max(0, int(c - r s + 0.5)), min(n_in, int(c + r s + 0.5))); the double weights are w_j = k((j - c + 0.5) / s), each divided by their sum (the weights of
+ *   JxlHipOutputResample before they are rounded to float32);
+ *   the integer weight is kk_j = int(w_j x 2^22 + 0.5) for w_j >= 0 and int(w_j x 2^22 - 0.5) for w_j < 0, int truncating towards zero; the integer weights are not
+ *   renormalised;
+ *   a sample is clamp((2^21 + sum_j p_j x kk_j) >> 22, 0, 255): the sum in int32 (sum |kk| x 255 < 2^31 for both filters), the shift arithmetic.
+ * The horizontal pass runs first, over the rows of the crop, and gives u8; the vertical pass runs over that u8 result.  The clamp between the passes is part of the
+ * definition: cubic overshoot is cut twice.  A target of the crop's own size needs no special case (the single weight is 2^22: a copy).  Taps of kk = 0 at either end of a
+ * range may be left out.  The finished u8 value k is stored as the libjpeg-exact decode stores a sample: u8 k, u16 257 k, float16 / float32 (float)k x (1 / 255), through
+ * scale / bias — every sample type, byte order, 1 - 4 channels, row alignment and planar layout follow from the u8 result; `mirror` is the flip of the finished target.
+ * Such an output's intermediates are u8 (JxlHipBatchDeviceBytes: a quarter of the float32 ones of the other resized outputs).
+ * Refused, each as "unsupported: integer resample ...": the flag without a resample (no target size); the flag for an image JxlHipBatchCanDecodeJpegPixels does not take
+ * (in a pipeline job that image fails alone); together with downscale 8 (the bindings' keyword: these calls have no downscale).  Like an output with jpeg_scale != 1 it is
+ * written by JxlHipBatchDecodeJpegPixels alone: a JxlHipBatchDecode writes the other images and JxlHipBatchFinish fails with "unsupported: integer resample of image i ...".
+ * The launches are those of the other resized outputs (one pair per group of equal slot count; integer and float32 resamples never share a group).
+ * JxlHipBatchGetInfo(batch, "resize_u8_images"): images of the last decode that were resampled this way. */
+#define JXL_HIP_RESAMPLE_U8 1u
+JxlDecoderStatus JxlHipBatchSetOutputJpegResampled(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int jpeg_scale,
+                                                   const JxlHipOutputLayout* layout, const JxlHipOutputResample* resample, uint32_t flags);
 /* Decode-thread packing: lanes between active entropy-decode threads (64 = one stream per wavefront, 1 = 64 per wavefront). */
 void JxlHipBatchSetLaneStride(JxlHipBatch* batch, int lf, int hf);
 /* Tuning / testing knobs: "force_generic_idct", "hf_block_threads", "lds_code_budget", "debug_stop_after", "lf_wide_once" (the next LF stage of the batch takes the
@@ -483,6 +510,12 @@ int64_t JxlHipPipelineSubmitJpegPixels(JxlHipPipeline* pipeline, const uint8_t* 
 int64_t JxlHipPipelineSubmitJpegPixelsScaled(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format,
                                              void* const* device_out, void* const* host_out, const size_t* out_capacity, const JxlHipOutputLayout* layout /* NULL = interleaved */,
                                              const JxlHipOutputResample* each /* NULL, or n entries of one target size */, int jpeg_scale);
+/* The same with flags (JxlHipBatchSetOutputJpegResampled above): JXL_HIP_RESAMPLE_U8 makes the integer resample the property of the job — every image of it is
+ * resampled in Pillow's 8-bit arithmetic; flags = 0 is the call above, byte for byte; other bits, and the flag with a NULL `each`, refuse the submission.  An image the
+ * libjpeg-exact decode does not take fails alone ("unsupported: integer resample of ...").  Such jobs mix with every other kind of job over the same buffer sets. */
+int64_t JxlHipPipelineSubmitJpegPixelsResampled(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format,
+                                                void* const* device_out, void* const* host_out, const size_t* out_capacity, const JxlHipOutputLayout* layout /* NULL = interleaved */,
+                                                const JxlHipOutputResample* each /* n entries of one target size */, int jpeg_scale, uint32_t flags);
 /* A reconstruction job: the original JPEG file of every image, byte for byte (JxlHipBatchReconstructJpegs above, as stages of the pipeline: the entropy stages run
  * ahead on the side streams, one gather launch per job moves the coefficients out of the shared coefficient set — which is clean behind it —, and the pack pass, the
  * copies and the host splice of a job run in the thread that collects it, beside the entropy stages of the jobs behind it).  Such jobs mix freely with plain, 1:8,

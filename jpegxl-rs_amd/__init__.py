@@ -194,6 +194,9 @@ def libjxl():
                                                            C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample)]),
             "JxlHipPipelineSubmitJpegPixelsScaled": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz),
                                                                  C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.c_int]),
+            "JxlHipPipelineSubmitJpegPixelsResampled": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz),
+                                                                    C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.c_int, C.c_uint32]),
+            "JxlHipBatchSetOutputJpegResampled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), vp, C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.c_uint32]),
             "JxlHipBatchOutBufferSizeJpegScaled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(sz)]),
             "JxlHipBatchSetOutputJpegScaled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), vp, C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample)]),
             "JxlHipImageOutSizeJpegScaled": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(JxlBasicInfo),
@@ -698,6 +701,17 @@ def _jpeg_scaled(jpeg_scale, downscale, rs):
     return rs
 
 
+JXL_HIP_RESAMPLE_U8 = 1
+
+
+def _resize_u8(downscale, rs):
+    """the integer resample (include/jxl_hip.h JxlHipBatchSetOutputJpegResampled): refuses what the C calls have no argument for, a downscale and a missing target"""
+    if int(downscale) != 1:
+        raise GenericError("unsupported: integer resample together with downscale %d (the 1:8 decode is not a libjpeg-exact one)" % int(downscale))
+    if rs is None:
+        raise GenericError("unsupported: integer resample without a target size (resize_u8 needs resize=(width, height))")
+
+
 def _per_image(value, n, is_one):
     """one value for the job, or a sequence of n per-image values -> (list of n, whether it was a sequence)"""
     if value is None or isinstance(value, (str, bytes)) or not hasattr(value, "__iter__"):
@@ -739,9 +753,13 @@ class BatchDecoder:
         if status != JXL_DEC_SUCCESS:
             raise GenericError(last_error())
 
-    def _set_output(self, i, fmt, device_ptr, downscale, layout=None, resize=None, jpeg_scale=1):
+    def _set_output(self, i, fmt, device_ptr, downscale, layout=None, resize=None, jpeg_scale=1, resize_u8=False):
         L = libjxl()
-        if jpeg_scale != 1:
+        if resize_u8:
+            _resize_u8(downscale, resize)
+            resize = _jpeg_scaled(jpeg_scale, downscale, resize)
+            self._chk(L.JxlHipBatchSetOutputJpegResampled(self._h, i, C.byref(fmt), device_ptr, int(jpeg_scale), _byref(layout), _byref(resize), JXL_HIP_RESAMPLE_U8))
+        elif jpeg_scale != 1:
             resize = _jpeg_scaled(jpeg_scale, downscale, resize)
             self._chk(L.JxlHipBatchSetOutputJpegScaled(self._h, i, C.byref(fmt), device_ptr, int(jpeg_scale), _byref(layout), _byref(resize)))
         elif isinstance(resize, JxlHipOutputResample):
@@ -761,7 +779,7 @@ class BatchDecoder:
         self._resizes.append(resize)
 
     def add(self, data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, device_ptr=None, downscale=1,
-            planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_scale=1) -> int:
+            planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_scale=1, resize_u8=False) -> int:
         """downscale=8: the 1:8 decode (include/jxl_hip.h JxlHipBatchSetOutputScaled) — output(i) is the ceil(w / 8) x ceil(h / 8) picture; `data` may end behind
         the LF part of its frame.
         planar=True: one plane per channel, [C, H, W] with rows `align`ed and planes plane_stride bytes apart (0 = tight); scale / bias (up to four values, one per
@@ -772,7 +790,10 @@ class BatchDecoder:
         picture is stored with its columns reversed (include/jxl_hip.h JxlHipOutputResample).  Both need resize; a call without them is the ...Resized call as before.
         jpeg_scale=2 | 4 | 8: libjpeg's scaled decode of a JPEG transcode (include/jxl_hip.h JxlHipBatchSetOutputJpegScaled) — the ceil(w / s) x ceil(h / s) picture
         PIL's draft() gives for the original file, sample for sample, as the source of everything above (a crop is in the scaled picture).  Only decode_jpeg_pixels()
-        writes such an output (decode() + finish() fail the image); not together with downscale."""
+        writes such an output (decode() + finish() fail the image); not together with downscale.
+        resize_u8=True (needs resize, and an image decode_jpeg_pixels() takes): the resample runs in Pillow's 8-bit arithmetic over the u8 picture libjpeg gives
+        (include/jxl_hip.h JxlHipBatchSetOutputJpegResampled) — the u8 output is np.asarray(Image.open(file).crop(box).resize(size, BILINEAR | BICUBIC)) byte for
+        byte, every other type and layout follows from it, and the intermediates are u8.  Only decode_jpeg_pixels() writes such an output; not together with downscale."""
         layout = _layout(planar, plane_stride, scale, bias)
         rs = _resize(resize, crop) if filter is None and not mirror else _resample(resize, crop, filter, mirror)
         L = libjxl()
@@ -787,14 +808,14 @@ class BatchDecoder:
         if i < 0:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
-        self._set_output(i, fmt, device_ptr, downscale, layout, rs, jpeg_scale)
+        self._set_output(i, fmt, device_ptr, downscale, layout, rs, jpeg_scale, resize_u8)
         self._n += 1
         return i
 
     def add_many(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, threads=4, endianness=Endianness.Native, align=0, downscale=1,
-                 planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_scale=1) -> int:
+                 planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_scale=1, resize_u8=False) -> int:
         """Parses the images of `datas` (bytes objects) on `threads` host threads and appends them in order (JxlHipBatchAddImages);
-        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale, planar, plane_stride, scale, bias, resize, crop, filter, mirror, jpeg_scale: as for add()."""
+        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale, planar, plane_stride, scale, bias, resize, crop, filter, mirror, jpeg_scale, resize_u8: as for add()."""
         L = libjxl()
         layout = _layout(planar, plane_stride, scale, bias)
         rs = _resize(resize, crop) if filter is None and not mirror else _resample(resize, crop, filter, mirror)
@@ -812,7 +833,7 @@ class BatchDecoder:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
         for k in range(n):
-            self._set_output(first + k, fmt, device_ptrs[k] if device_ptrs is not None else None, downscale, layout, rs, jpeg_scale)
+            self._set_output(first + k, fmt, device_ptrs[k] if device_ptrs is not None else None, downscale, layout, rs, jpeg_scale, resize_u8)
         self._n += n
         return first
 
@@ -1043,7 +1064,7 @@ class Pipeline:
     __del__ = close
 
     def submit(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, host_ptrs=None, capacities=None, endianness=Endianness.Native, align=0, downscale=1,
-               planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_pixels=False, jpeg_scale=1) -> int:
+               planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_pixels=False, jpeg_scale=1, resize_u8=False) -> int:
         """Job of len(datas) images (bytes objects).  device_ptrs / host_ptrs: one destination address per image (exactly one of the two lists); the bytes objects and
         the destinations are kept referenced until wait().  downscale=8: the job is decoded at 1:8 (JxlHipPipelineSubmitScaled).  planar, plane_stride, scale, bias:
         the layout of every image of the job, as for BatchDecoder.add (JxlHipPipelineSubmitLayout).  resize, crop: every image of the job comes out resize[0] x resize[1]
@@ -1055,7 +1076,13 @@ class Pipeline:
         jpeg_pixels: a job of libjpeg-exact pixels (JxlHipPipelineSubmitJpegPixels; BatchDecoder.decode_jpeg_pixels as pipeline stages) with the same keywords; an image
         that decode does not take fails alone, downscale other than 1 is refused here.
         jpeg_scale=2 | 4 | 8 (with jpeg_pixels only; one scale per job): libjpeg's scaled decode, as for BatchDecoder.add (JxlHipPipelineSubmitJpegPixelsScaled) —
-        destinations are sized with image_out_size(..., jpeg_scale=), crops are in the scaled picture."""
+        destinations are sized with image_out_size(..., jpeg_scale=), crops are in the scaled picture.
+        resize_u8=True (with jpeg_pixels and resize only): every image of the job is resampled in Pillow's 8-bit arithmetic, as for BatchDecoder.add
+        (JxlHipPipelineSubmitJpegPixelsResampled); an image the libjpeg-exact decode does not take fails alone."""
+        if resize_u8:
+            _resize_u8(downscale, resize)
+            if not jpeg_pixels:
+                raise GenericError("unsupported: integer resample in a job that is not a libjpeg-exact one (resize_u8 needs jpeg_pixels=True: it resamples the u8 picture libjpeg gives)")
         if jpeg_pixels and int(downscale) != 1:
             raise GenericError("unsupported: libjpeg-exact decode of an output with downscale %d (libjpeg's scaled IDCTs are other arithmetic)" % int(downscale))
         if jpeg_scale != 1 and not jpeg_pixels:
@@ -1080,7 +1107,9 @@ class Pipeline:
         if jpeg_pixels:
             if each is None and resize is not None:
                 each = (JxlHipOutputResample * max(1, n))(*[_resample(resize, crop, None, False) for _ in range(n)])      # (filter 0, no mirror: the ...Resized call, byte for byte)
-            if jpeg_scale != 1:
+            if resize_u8:
+                t = libjxl().JxlHipPipelineSubmitJpegPixelsResampled(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, _byref(layout), each, int(jpeg_scale), JXL_HIP_RESAMPLE_U8)
+            elif jpeg_scale != 1:
                 t = libjxl().JxlHipPipelineSubmitJpegPixelsScaled(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, _byref(layout), each, int(jpeg_scale))
             else:
                 t = libjxl().JxlHipPipelineSubmitJpegPixels(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, _byref(layout), each)

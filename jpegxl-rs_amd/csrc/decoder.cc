@@ -838,6 +838,30 @@ static void ResizeAxis(uint32_t filter, uint32_t n_in, uint32_t n_out, vec<uint3
   }
   (*first)[n_out] = (uint32_t)weight->size();
 }
+// The integer form (OutputSpec::resize_u8; the rule: include/jxl_hip.h): the same ranges and the same normalised double weights — not their f32 roundings —, each as
+// kk = int(w x 2^22 + 0.5) for w >= 0, int(w x 2^22 - 0.5) below, truncating: Pillow's 8-bit coefficients (Resample.c normalize_coeffs_8bpc, PRECISION_BITS = 32 - 8 - 2).
+// They are not renormalised.  Taps of kk == 0 at either end of a range are left out (they change no sum); one tap always stays.
+static void ResizeAxisInt(uint32_t filter, uint32_t n_in, uint32_t n_out, vec<uint32_t>* lo, vec<uint32_t>* first, vec<int32_t>* weight) {
+  const double scale = (double)n_in / (double)n_out, support = std::max(scale, 1.0), reach = (filter ? 2.0 : 1.0) * support;
+  lo->assign(n_out, 0); first->assign((size_t)n_out + 1, 0); weight->clear();
+  vec<double> w;
+  vec<int32_t> kk;
+  for (uint32_t i = 0; i < n_out; i++) {
+    const double c = scale * ((double)i + 0.5);
+    int64_t a = std::max<int64_t>(0, (int64_t)(c - reach + 0.5)), b = std::min<int64_t>((int64_t)n_in, (int64_t)(c + reach + 0.5));
+    if (b <= a) { a = std::min<int64_t>(a, (int64_t)n_in - 1); b = a + 1; }      // (cannot happen for n_in >= 1: the centre's own sample is inside the reach)
+    w.assign((size_t)(b - a), 0.0); kk.assign((size_t)(b - a), 0);
+    double sum = 0.0;
+    for (int64_t j = a; j < b; j++) { w[(size_t)(j - a)] = ResizeFilterWeight(filter, ((double)j - c + 0.5) / support); sum += w[(size_t)(j - a)]; }
+    for (size_t t = 0; t < w.size(); t++) { const double v = w[t] / sum; kk[t] = v < 0.0 ? (int32_t)(v * 4194304.0 - 0.5) : (int32_t)(v * 4194304.0 + 0.5); }
+    const int64_t a0 = a;
+    while (b - a > 1 && kk[(size_t)(b - 1 - a0)] == 0) b--;
+    while (b - a > 1 && kk[(size_t)(a - a0)] == 0) a++;
+    (*lo)[i] = (uint32_t)a; (*first)[i] = (uint32_t)weight->size();
+    for (int64_t j = a; j < b; j++) weight->push_back(kk[(size_t)(j - a0)]);
+  }
+  (*first)[n_out] = (uint32_t)weight->size();
+}
 void Batch::OutputDims(int i, const OutputSpec& o, uint32_t* w, uint32_t* h) const {
   const ImageEntry& first = *images_[pub_[i].first_unit];
   *w = first.ih.xsize; *h = first.ih.ysize;
@@ -858,6 +882,8 @@ static OutputDesc FillOutput(const ImageEntry& e, uint8_t* work, uint8_t* big, b
   if (e.out.resized() && !resize_target) {
     d.out = big + e.off_resize_src;
     d.out_stride = (size_t)e.src_w * e.out.num_channels * 4; d.out_channels = e.out.num_channels; d.out_type = 2; d.out_int_mul = 1.0f;
+    // (OutputSpec::resize_u8: the same picture as interleaved u8 — the libjpeg-exact write stage stores its sample k as k — for ResizeU8Kernel)
+    if (e.out.resize_u8) { d.out_stride = (size_t)e.src_w * e.out.num_channels; d.out_type = 0; d.out_int_mul = 255.0f; }
     d.out_orient = e.out.keep_orientation ? 1 : e.ih.orientation; d.is_gray = e.ih.color_space == 1;
     return d;
   }
@@ -897,6 +923,13 @@ void Batch::SetOutput(int i, const OutputSpec& o) {
     // (only the libjpeg-exact decode writes such an output: what it does not take has no scaled picture at all)
     std::string why;
     if (!CanDecodeJpegPixelsAs(i, o, &why)) throw ParseError(why, true);
+  }
+  if (o.resize_u8) {
+    // the integer resample (OutputSpec::resize_u8) is defined over the u8 picture libjpeg gives: it needs a target, and an image that decode takes
+    if (!o.resized()) throw ParseError("unsupported: integer resample without a target size (resize_u8 needs a resized output)", true);
+    if (o.downscale != 1) throw ParseError("unsupported: integer resample together with downscale " + std::to_string(o.downscale) + " (the 1:8 decode is not a libjpeg-exact one)", true);
+    std::string why;
+    if (!CanDecodeJpegPixelsAs(i, o, &why)) throw ParseError("unsupported: integer resample of an image the libjpeg-exact decode does not take (" + why + ")", true);
   }
   e.out = o;
   if (o.only_frame >= pub_[i].num_units) throw ParseError("non-coalesced output: no such frame", false);
@@ -956,7 +989,7 @@ void Batch::StageBytes(uint64_t out[6]) const {
     if (first.out.resized()) {
       // resized output: the write stage's pixels are the f32 intermediate; ResizeKernel reads the resampled rectangle of it and writes the target in the caller's format (once per
       // image; the horizontally filtered rows between its two passes are traffic, not algorithmic bytes)
-      out_px = (uint64_t)first.out.num_channels * 4;
+      out_px = (uint64_t)first.out.num_channels * (first.out.resize_u8 ? 1 : 4);      // (OutputSpec::resize_u8: a u8 intermediate, ResizeU8Kernel)
       if (&e == &first) {
         const uint64_t rect = first.out.cropped() ? (uint64_t)first.out.crop_w * first.out.crop_h : (uint64_t)first.src_w * first.src_h;
         out[5] += rect * out_px + (uint64_t)first.out.resize_w * first.out.resize_h * first.out.num_channels * bps;
@@ -1028,6 +1061,7 @@ int64_t Batch::Info(const std::string& name) const {
   }
   if (name == "hf_nonzeros") { int64_t t = 0; for (uint32_t v : hf_written_) t += v; return t; }   // non-zero AC coefficients per decode of the batch (known after a Finish)
   if (name == "mod_group_lds_bytes") return prepared_ ? (int64_t)ModularGroupLdsBytes(cfg) : -1;
+  if (name == "resize_u8_images") return resize_u8_images_;         // images of the last decode whose resize ran in Pillow's 8-bit arithmetic (OutputSpec::resize_u8: ResizeU8Kernel)
   if (name == "resize_launches") return resize_launches_;           // kernel launches the last decode's resizes took (two per group of the table: Batch::EnqueueResizes)
   if (name == "jpeg_device_images") return jpeg_device_images_;     // images of the last ReconstructJpegs whose scans the device wrote / that went through the host writer
   if (name == "jpeg_host_images") return jpeg_host_images_;
@@ -1315,11 +1349,13 @@ void Batch::PutStreamTables(PrepareState& st) {
     if (e.frame_index == 0 && e.out.resized()) {     // the two axes' filters of a resized output (ResizeAxis)
       ResizePlan rp;
       rp.unit = i;
-      vec<uint32_t> lo, first; vec<float> weight;
+      vec<uint32_t> lo, first; vec<float> weight; vec<int32_t> kk;
       for (int ax = 0; ax < 2; ax++) {
         const uint32_t n_in = e.out.cropped() ? (ax ? e.out.crop_h : e.out.crop_w) : (ax ? e.src_h : e.src_w);
-        ResizeAxis(e.out.resize_filter, n_in, ax ? e.out.resize_h : e.out.resize_w, &lo, &first, &weight);
-        rp.tab[3 * ax] = arena.Put(lo.data(), lo.size() * 4); rp.tab[3 * ax + 1] = arena.Put(first.data(), first.size() * 4); rp.tab[3 * ax + 2] = arena.Put(weight.data(), weight.size() * 4);
+        if (e.out.resize_u8) ResizeAxisInt(e.out.resize_filter, n_in, ax ? e.out.resize_h : e.out.resize_w, &lo, &first, &kk);
+        else ResizeAxis(e.out.resize_filter, n_in, ax ? e.out.resize_h : e.out.resize_w, &lo, &first, &weight);
+        rp.tab[3 * ax] = arena.Put(lo.data(), lo.size() * 4); rp.tab[3 * ax + 1] = arena.Put(first.data(), first.size() * 4);
+        rp.tab[3 * ax + 2] = e.out.resize_u8 ? arena.Put(kk.data(), kk.size() * 4) : arena.Put(weight.data(), weight.size() * 4);
       }
       resize_plans_.push_back(rp);
     }
@@ -1392,8 +1428,10 @@ void Batch::LayOutWork(PrepareState& st) {
     if (e.frame_index == 0 && e.out.resized()) {
       // resized output: the f32 picture the write stage leaves (every slot of the output, interleaved), and the rows of the resampled rectangle after the horizontal pass —
       // among the pixel planes: written and read between the write stage and the end of the decode, so the jobs of a pipeline share one set (UseSharedPlanes)
-      e.off_resize_src = st.take_big((size_t)e.src_w * e.src_h * e.out.num_channels * 4);
-      e.off_resize_tmp = st.take_big((size_t)(e.out.cropped() ? e.out.crop_h : e.src_h) * e.out.resize_w * e.out.num_channels * 4);
+      // (OutputSpec::resize_u8: both hold u8 samples, a quarter of it)
+      const size_t sample = e.out.resize_u8 ? 1 : 4;
+      e.off_resize_src = st.take_big((size_t)e.src_w * e.src_h * e.out.num_channels * sample);
+      e.off_resize_tmp = st.take_big((size_t)(e.out.cropped() ? e.out.crop_h : e.src_h) * e.out.resize_w * e.out.num_channels * sample);
     }
     if (p.upsampling > 1) {   // kernel weights: custom (image header) or library default
       const int upk = p.upsampling == 2 ? 0 : p.upsampling == 4 ? 1 : 2;
@@ -1887,7 +1925,9 @@ void Batch::PlanLfSimt(PrepareState& st) {
 // Resized outputs: the table of ResizeArgs takes its place in the constant arena here (BuildResizeTable fills it once the arena's device address is known);
 // resize_plans_ sorted by slot count.  Adds the table's room to the arena.
 void Batch::PlaceResizeTable(PrepareState& st) {
-  std::stable_sort(resize_plans_.begin(), resize_plans_.end(), [&](const ResizePlan& a, const ResizePlan& b) { return ResizeSlots(*images_[a.unit]) < ResizeSlots(*images_[b.unit]); });
+  // (the f32 resizes first, the integer ones of OutputSpec::resize_u8 behind them: the two arithmetics take different kernels and never share a launch group)
+  auto key = [&](const ResizePlan& r) { return (images_[r.unit]->out.resize_u8 ? 8u : 0u) + ResizeSlots(*images_[r.unit]); };
+  std::stable_sort(resize_plans_.begin(), resize_plans_.end(), [&](const ResizePlan& a, const ResizePlan& b) { return key(a) < key(b); });
   resize_table_off_ = 0;
   if (resize_plans_.empty()) return;
   resize_table_off_ = st.arena.Put(nullptr, 0);                                                // (an aligned place; Put copies from its source, so the table's room is made here)
@@ -1905,7 +1945,8 @@ void Batch::BuildResizeTable() {
     const OutputSpec& o = e.out;
     ResizeArgs a;
     memset(&a, 0, sizeof(a));
-    a.src = (const float*)(dbig_ + e.off_resize_src); a.tmp = (float*)(dbig_ + e.off_resize_tmp); a.src_stride = (uint64_t)e.src_w * o.num_channels;
+    a.src = (const float*)(dbig_ + e.off_resize_src); a.tmp = (float*)(dbig_ + e.off_resize_tmp); a.src_stride = (uint64_t)e.src_w * o.num_channels;   // (resize_u8: bytes, and so is the stride)
+    a.u8 = o.resize_u8 ? 1 : 0;
     a.x0 = o.crop_x0; a.y0 = o.crop_y0; a.in_w = o.cropped() ? o.crop_w : e.src_w; a.in_h = o.cropped() ? o.crop_h : e.src_h; a.out_w = o.resize_w; a.out_h = o.resize_h;
     a.mirror = o.mirror ? 1 : 0;
     a.ax = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[0]), (const uint32_t*)(dconst_ + rp.tab[1]), (const float*)(dconst_ + rp.tab[2])};
@@ -1913,7 +1954,8 @@ void Batch::BuildResizeTable() {
     a.od = FillOutput(e, dwork_, dbig_, /*resize_target=*/true);
     table[k] = a;
     const uint32_t slots = ResizeSlots(e);
-    if (resize_groups_.empty() || resize_groups_.back().slots != slots || resize_groups_.back().count >= group_max) resize_groups_.push_back(ResizeGroup{(uint32_t)k, 0, slots, 0, 0, 0});
+    if (resize_groups_.empty() || resize_groups_.back().slots != slots || resize_groups_.back().u8 != a.u8 || resize_groups_.back().count >= group_max)
+      resize_groups_.push_back(ResizeGroup{(uint32_t)k, 0, slots, 0, 0, 0, a.u8});
     ResizeGroup& g = resize_groups_.back();
     g.count++; g.max_out_w = std::max(g.max_out_w, a.out_w); g.max_in_h = std::max(g.max_in_h, a.in_h); g.max_out_h = std::max(g.max_out_h, a.out_h);
   }
@@ -2554,8 +2596,8 @@ void Batch::EnqueuePostOps(void* stream) { for (auto& op : post_ops_) op(stream)
 // Resized outputs: behind everything that writes pixels (the write kernels of plain frames, the Modular tail, the frame tail), on the same stream
 // (one launch pair per group of the table Prepare left in the constant arena: kernels_features.hip ResizeKernel)
 void Batch::EnqueueResizes(void* stream) {
-  resize_launches_ = 0;
-  for (const ResizeGroup& g : resize_groups_) { LaunchResizeGroup((const ResizeArgs*)(dconst_ + resize_table_off_), g, stream); resize_launches_ += 2; }
+  resize_launches_ = resize_u8_images_ = 0;
+  for (const ResizeGroup& g : resize_groups_) { LaunchResizeGroup((const ResizeArgs*)(dconst_ + resize_table_off_), g, stream); resize_launches_ += 2; if (g.u8) resize_u8_images_ += g.count; }
 }
 
 // The HF stage only writes non-zero coefficients into zeroed planes.  The IDCT kernels zero what they consumed (kernels.hip,
@@ -2778,13 +2820,14 @@ static std::string DeviceStatusMessage(uint32_t status, int frame, bool* unsuppo
   return "corrupt stream (device status " + std::to_string(status) + ", frame " + std::to_string(frame) + ")";
 }
 
-// An output with OutputSpec::jpeg_scale != 1 is the picture of libjpeg's scaled decode, which the float pipeline has no way to compute: behind a Run the image's
+// An output with OutputSpec::jpeg_scale != 1 is the picture of libjpeg's scaled decode, which the float pipeline has no way to compute — and one with
+// OutputSpec::resize_u8 is resampled from libjpeg's u8 picture, which it has no way to compute either: behind a Run the image's
 // status word is set, so that Finish fails it — alone, the others are written — with the reason below.  (Its write stage has stayed inside the scaled picture:
 // FrameDev::img_w / img_h.)
 void Batch::FailJpegScaledOutputs(void* stream_v) {
   static const uint32_t kRefused = kErrUnsupported;
   for (size_t u = 0; u < images_.size(); u++)
-    if (images_[u]->frame_index == 0 && images_[u]->out.jpeg_scale != 1) HIP_CHECK(hipMemcpyAsync(dwork_ + status_off_ + u * 4, &kRefused, 4, hipMemcpyHostToDevice, (hipStream_t)stream_v));
+    if (images_[u]->frame_index == 0 && (images_[u]->out.jpeg_scale != 1 || images_[u]->out.resize_u8)) HIP_CHECK(hipMemcpyAsync(dwork_ + status_off_ + u * 4, &kRefused, 4, hipMemcpyHostToDevice, (hipStream_t)stream_v));
 }
 
 void Batch::Finish(void* stream_v) {
@@ -2797,6 +2840,8 @@ void Batch::Finish(void* stream_v) {
     if (unsupported && images_[i]->frame_index == 0 && images_[i]->out.jpeg_scale != 1)
       msg = "unsupported: image " + std::to_string(images_[i]->pub_index) + " has an output with jpeg_scale " + std::to_string(images_[i]->out.jpeg_scale) +
             ", which only the libjpeg-exact decode writes (DecodeJpegPixels)";
+    else if (unsupported && images_[i]->frame_index == 0 && images_[i]->out.resize_u8)
+      msg = "unsupported: integer resample of image " + std::to_string(images_[i]->pub_index) + " under a plain decode: only the libjpeg-exact decode writes an output with resize_u8 (DecodeJpegPixels)";
     throw ParseError(msg, unsupported);
   }
 }

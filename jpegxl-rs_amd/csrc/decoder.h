@@ -45,6 +45,9 @@ struct OutputSpec {
   uint32_t crop_x0 = 0, crop_y0 = 0, crop_w = 0, crop_h = 0;   // rectangle of the source that is resampled (all 0 = the whole picture): exactly crop first, then resize
   uint32_t resize_filter = 0;              // 0 = triangle, 1 = cubic convolution with a = -0.5 (resized outputs only)
   bool mirror = false;                     // resized outputs only: target column ox is stored at column resize_w - 1 - ox, a flip of the finished target
+  bool resize_u8 = false;                  // resized outputs of the libjpeg-exact decode only (Batch::CanDecodeJpegPixels, downscale 1): the resample is Pillow's 8-bit one over the
+                                           // u8 picture libjpeg gives (include/jxl_hip.h, JxlHipBatchSetOutputJpegResampled: int32 weights of 22 fraction bits, rounded and clamped
+                                           // to u8 behind each pass), byte for byte im.crop(box).resize(size, filter); the intermediate is u8.  Written by DecodeJpegPixels alone
   bool resized() const { return resize_w || resize_h; }
   bool cropped() const { return crop_x0 || crop_y0 || crop_w || crop_h; }
 };
@@ -74,6 +77,7 @@ struct ImageEntry {
   size_t off_cs = 0, off_sec = 0, off_tree = 0, off_bcm = 0;
   size_t off_out = 0;
   size_t off_resize_src = 0, off_resize_tmp = 0;   // (first unit, resized output; pixel-plane arena) the f32 picture the write stage leaves for ResizeKernel, the horizontally filtered rows
+                                                   // (OutputSpec::resize_u8: both in u8, for ResizeU8Kernel)
   uint32_t src_w = 0, src_h = 0;                   // (first unit) size of that picture: SetOutput
   explicit ImageEntry(std::shared_ptr<ImageShared> s) : shared(std::move(s)), cs(shared->cs), ih(shared->ih) {}
 };
@@ -334,6 +338,7 @@ class Batch {
   vec<ResizeGroup> resize_groups_;
   size_t resize_table_off_ = 0;
   int64_t resize_launches_ = 0;                      // kernel launches of the last EnqueueResizes
+  int64_t resize_u8_images_ = 0;                     // ... images of it that took ResizeU8Kernel (OutputSpec::resize_u8)
   void EnqueueResizes(void* stream);
   vec<FrameDev> frames_host_;
   HostStage hconst_;

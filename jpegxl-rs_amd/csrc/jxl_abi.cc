@@ -1025,6 +1025,23 @@ JxlDecoderStatus JxlHipBatchSetOutputJpegScaled(JxlHipBatch* h, int i, const Jxl
   o.device_ptr = device_buffer;
   try { h->b->SetOutput(i, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }   // (an image the libjpeg-exact decode does not take, a crop that leaves the scaled picture)
 }
+// ... with flags (JXL_HIP_RESAMPLE_U8: the integer resample, OutputSpec::resize_u8); flags = 0 is the call above
+static bool ResampleFlagsOk(uint32_t flags, bool have_resample, const char* who) {
+  if (flags & ~(uint32_t)JXL_HIP_RESAMPLE_U8) { SetLastError(std::string(who) + ": unknown flag bits"); return false; }
+  if ((flags & JXL_HIP_RESAMPLE_U8) && !have_resample) { SetLastError(std::string(who) + ": unsupported: integer resample without a target size (no JxlHipOutputResample given)"); return false; }
+  return true;
+}
+JxlDecoderStatus JxlHipBatchSetOutputJpegResampled(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int jpeg_scale, const JxlHipOutputLayout* layout,
+                                                   const JxlHipOutputResample* resample, uint32_t flags) {
+  const char* who = "JxlHipBatchSetOutputJpegResampled";
+  OutputSpec o;
+  if (!ResampleFlagsOk(flags, resample != nullptr, who)) return JXL_DEC_ERROR;
+  if (!JpegScaleOk(jpeg_scale, who) || !BatchSpec(h, i, format, 1, layout, nullptr, resample, resample != nullptr, &o, who)) return JXL_DEC_ERROR;
+  o.jpeg_scale = (uint32_t)jpeg_scale;
+  o.resize_u8 = (flags & JXL_HIP_RESAMPLE_U8) != 0;
+  o.device_ptr = device_buffer;
+  try { h->b->SetOutput(i, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }   // (as above; "unsupported: integer resample of ..." for an image that decode does not take)
+}
 void JxlHipBatchSetLaneStride(JxlHipBatch* h, int lf, int hf) {
   auto ok = [](int v) { return v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64; };
   if (ok(lf)) h->b->cfg.lane_stride_lf = lf;
@@ -1203,13 +1220,15 @@ int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* h, const uint8_t* const* d
 }
 // a libjpeg-exact job (Pipeline::Submit, jpeg_pixels): the layout and the per-image resamples of the calls above, no downscale
 static int64_t PipelineSubmitJpegPixels(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
-                                        const size_t* out_capacity, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, int jpeg_scale, const char* who) {
+                                        const size_t* out_capacity, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, int jpeg_scale, const char* who, uint32_t flags = 0) {
   if (!JpegScaleOk(jpeg_scale, who)) return -1;
+  if (!ResampleFlagsOk(flags, each != nullptr, who)) return -1;
   try {
     OutputSpec base;
     if (!h || !FormatToSpec(format, &base)) { SetLastError(std::string(who) + ": bad pixel format"); return -1; }
     if (!ApplyLayout(layout, &base, who)) return -1;
     base.downscale = 1; base.jpeg_scale = (uint32_t)jpeg_scale;
+    base.resize_u8 = (flags & JXL_HIP_RESAMPLE_U8) != 0;      // (the job's property: every image of it, OutputSpec::resize_u8)
     if (!each) return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity, nullptr, /*jpeg_pixels=*/true);
     std::vector<OutputSpec> specs((size_t)std::max(n, 0), base);
     for (int i = 0; i < n; i++) {
@@ -1232,6 +1251,12 @@ int64_t JxlHipPipelineSubmitJpegPixels(JxlHipPipeline* h, const uint8_t* const* 
 int64_t JxlHipPipelineSubmitJpegPixelsScaled(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
                                              void* const* host_out, const size_t* out_capacity, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, int jpeg_scale) {
   return PipelineSubmitJpegPixels(h, datas, sizes, n, format, device_out, host_out, out_capacity, layout, each, jpeg_scale, "JxlHipPipelineSubmitJpegPixelsScaled");
+}
+// ... with flags (JXL_HIP_RESAMPLE_U8: every image of the job takes the integer resample); flags = 0 is the call above
+int64_t JxlHipPipelineSubmitJpegPixelsResampled(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
+                                                void* const* host_out, const size_t* out_capacity, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, int jpeg_scale,
+                                                uint32_t flags) {
+  return PipelineSubmitJpegPixels(h, datas, sizes, n, format, device_out, host_out, out_capacity, layout, each, jpeg_scale, "JxlHipPipelineSubmitJpegPixelsResampled", flags);
 }
 JxlDecoderStatus JxlHipPipelineWait(JxlHipPipeline* h, int64_t ticket, int* image_status, int n, float* end_ms) {
   try {

@@ -401,11 +401,13 @@ struct ResizeAxisDev { const uint32_t* lo; const uint32_t* first; const float* w
 // src: interleaved f32 picture of od.out_channels slots, src_stride floats per row, of which the rectangle (x0, y0) in_w x in_h is resampled to out_w x out_h; tmp:
 // in_h x out_w x slots floats (the horizontally filtered rows); od: the caller's destination, out_orient 1 — the source is oriented already; mirror: target column ox is
 // stored at out_w - 1 - ox
-struct ResizeArgs { const float* src; float* tmp; uint64_t src_stride; uint32_t x0, y0, in_w, in_h, out_w, out_h, mirror; ResizeAxisDev ax, ay; OutputDesc od; };
-// The resizes of a decode are one device table of ResizeArgs, sorted by slot count; a group is a run of `count` entries from `first` on with the same number of slots,
+// u8 (the integer resample of libjpeg-exact outputs, OutputSpec::resize_u8 — ResizeU8Kernel): src and tmp are bytes (src_stride in bytes, tmp in_h x out_w x slots bytes) and
+// the two axes' `weight` are int32 (decoder.cc ResizeAxisInt: the normalised double weight x 2^22, rounded half away from zero); everything else as above
+struct ResizeArgs { const float* src; float* tmp; uint64_t src_stride; uint32_t x0, y0, in_w, in_h, out_w, out_h, mirror, u8; ResizeAxisDev ax, ay; OutputDesc od; };
+// The resizes of a decode are one device table of ResizeArgs, sorted by arithmetic (f32, then u8) and slot count; a group is a run of `count` entries from `first` on with the same arithmetic and number of slots,
 // served by one launch per pass (image on blockIdx.z, the grid sized for the group's largest extents).  count <= kResizeGroupMax (gridDim.z is limited to 65535).
 constexpr uint32_t kResizeGroupMax = 32768;
-struct ResizeGroup { uint32_t first, count, slots, max_out_w, max_in_h, max_out_h; };
+struct ResizeGroup { uint32_t first, count, slots, max_out_w, max_in_h, max_out_h, u8 = 0; };   // u8: a group of ResizeU8Kernel's entries (a group never mixes the two arithmetics)
 void LaunchResizeGroup(const ResizeArgs* table, const ResizeGroup& g, void* stream);
 
 // names of the kernels (for profiling summaries)

@@ -448,6 +448,61 @@ template <int NC, bool kVertical> __global__ __launch_bounds__(256) void ResizeK
   }
 }
 
+// ---- integer resample of libjpeg-exact outputs (OutputSpec::resize_u8; the rule: include/jxl_hip.h, JxlHipBatchSetOutputJpegResampled) -----------------------------------
+// Pillow's 8-bit resize over the u8 picture the libjpeg-exact write stage left (decoder.cc FillOutput: interleaved u8, every slot of the output): the same two passes, the
+// same table entry, grid and grouping as ResizeKernel — entries with ResizeArgs::u8 set, whose src / tmp are bytes and whose weights are the host's int32 kk
+// (ResizeAxisInt) — in int32: a sample is clamp((2^21 + sum p x kk) >> 22, 0, 255), arithmetic shift, once behind the horizontal pass (u8 `tmp`) and once behind the
+// vertical one.  The finished k goes out as the libjpeg-exact write stage stores a sample: (float)k x (1 / 255) through SlotValue / StoreSample, which gives k for u8 and
+// 257 k for u16.  A lane reads its taps byte by byte: 64 neighbouring pixels' windows adjoin or overlap, so a wave's taps fall into a few lines of the vector L1, as in
+// ResizeKernel; the sum of |kk| x 255 stays below 2^31 for both filters (the normalised weights' absolute sum is below 2: the centre's own sample is always in the range, so the positive lobe
+// outweighs the cubic's negative ones by far more than three to one).
+__device__ __forceinline__ int32_t ResizeU8Round(int32_t acc) { return min(max((acc + (1 << 21)) >> 22, 0), 255); }
+template <int NC, bool kVertical> __global__ __launch_bounds__(256) void ResizeU8Kernel(const ResizeArgs* __restrict__ table) {
+  const ResizeArgs a = table[blockIdx.z];
+  const uint32_t ox = blockIdx.x * 64 + threadIdx.x;
+  if (ox >= a.out_w) return;
+  const uint8_t* __restrict__ const tmp_in = (const uint8_t*)a.tmp;
+  int32_t acc[NC];
+  if (!kVertical) {
+    const uint32_t lo = a.ax.lo[ox], t0 = a.ax.first[ox], nt = a.ax.first[ox + 1] - t0;
+    const int32_t* __restrict__ wt = (const int32_t*)a.ax.weight + t0;
+    uint8_t* __restrict__ const tmp_out = (uint8_t*)a.tmp;
+    for (uint32_t y = blockIdx.y * 4 + threadIdx.y; y < a.in_h; y += gridDim.y * 4) {
+      const uint8_t* __restrict__ in = (const uint8_t*)a.src + (size_t)(a.y0 + y) * a.src_stride + (size_t)(a.x0 + lo) * NC;
+#pragma unroll
+      for (int c = 0; c < NC; c++) acc[c] = 0;
+      for (uint32_t j = 0; j < nt; j++) {
+        const int32_t w = wt[j];
+#pragma unroll
+        for (int c = 0; c < NC; c++) acc[c] += (int32_t)in[(size_t)j * NC + c] * w;
+      }
+      uint8_t* __restrict__ out = tmp_out + ((size_t)y * a.out_w + ox) * NC;
+#pragma unroll
+      for (int c = 0; c < NC; c++) out[c] = (uint8_t)ResizeU8Round(acc[c]);
+    }
+  } else {
+    const uint32_t oy = blockIdx.y * 4 + threadIdx.y;
+    if (oy >= a.out_h) return;
+    const uint32_t lo = a.ay.lo[oy], t0 = a.ay.first[oy], nt = a.ay.first[oy + 1] - t0;
+    const int32_t* __restrict__ wt = (const int32_t*)a.ay.weight + t0;
+    const size_t pitch = (size_t)a.out_w * NC;
+    const uint8_t* __restrict__ in = tmp_in + (size_t)lo * pitch + (size_t)ox * NC;
+#pragma unroll
+    for (int c = 0; c < NC; c++) acc[c] = 0;
+    for (uint32_t j = 0; j < nt; j++) {
+      const int32_t w = wt[j];
+#pragma unroll
+      for (int c = 0; c < NC; c++) acc[c] += (int32_t)in[(size_t)j * pitch + c] * w;
+    }
+    const uint32_t bps = a.od.out_type == 0 ? 1 : a.od.out_type == 2 ? 4 : 2;
+    uint8_t* const p = OutPixelPtr(a.od, (int)a.out_w, (int)a.out_h, (int)(a.mirror ? a.out_w - 1 - ox : ox), (int)oy, bps);
+    const size_t step = a.od.planar ? (size_t)a.od.plane_stride : (size_t)bps;
+    const float k255 = 1.0f / 255;
+#pragma unroll
+    for (int c = 0; c < NC; c++) StoreSample(a.od, p + c * step, SlotValue(a.od, c, (float)ResizeU8Round(acc[c]) * k255));
+  }
+}
+
 // ---- JPEG reconstruction: coefficients back into JPEG layout --------------------------------------------------------------------------
 __global__ void JpegCoefKernel(const FrameDev* __restrict__ frames, int fidx, JpegCoefArgs a) {
   const FrameDev& f = frames[fidx];
@@ -556,8 +611,23 @@ template <int NC> static void LaunchResizeNc(const ResizeArgs* table, const Resi
   hipLaunchKernelGGL((ResizeKernel<NC, false>), dim3(gx, std::min<uint32_t>((g.max_in_h + 3) / 4, 65535u), g.count), block, 0, st, table + g.first);
   hipLaunchKernelGGL((ResizeKernel<NC, true>), dim3(gx, (g.max_out_h + 3) / 4, g.count), block, 0, st, table + g.first);
 }
+template <int NC> static void LaunchResizeU8Nc(const ResizeArgs* table, const ResizeGroup& g, hipStream_t st) {
+  const dim3 block(64, 4);
+  const uint32_t gx = (g.max_out_w + 63) / 64;
+  hipLaunchKernelGGL((ResizeU8Kernel<NC, false>), dim3(gx, std::min<uint32_t>((g.max_in_h + 3) / 4, 65535u), g.count), block, 0, st, table + g.first);
+  hipLaunchKernelGGL((ResizeU8Kernel<NC, true>), dim3(gx, (g.max_out_h + 3) / 4, g.count), block, 0, st, table + g.first);
+}
 void LaunchResizeGroup(const ResizeArgs* table, const ResizeGroup& g, void* stream) {
   if (!g.count || g.count > kResizeGroupMax || !g.max_out_w || !g.max_in_h || !g.max_out_h) return;
+  if (g.u8) {      // (a group is of one arithmetic: Batch::BuildResizeTable)
+    switch (g.slots) {
+      case 1: LaunchResizeU8Nc<1>(table, g, (hipStream_t)stream); break;
+      case 2: LaunchResizeU8Nc<2>(table, g, (hipStream_t)stream); break;
+      case 3: LaunchResizeU8Nc<3>(table, g, (hipStream_t)stream); break;
+      default: LaunchResizeU8Nc<4>(table, g, (hipStream_t)stream); break;
+    }
+    return;
+  }
   switch (g.slots) {
     case 1: LaunchResizeNc<1>(table, g, (hipStream_t)stream); break;
     case 2: LaunchResizeNc<2>(table, g, (hipStream_t)stream); break;

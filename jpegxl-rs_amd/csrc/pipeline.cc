@@ -299,6 +299,9 @@ void Pipeline::PrepareJob(Job* j, int worker) {
       o.device_ptr = j->device_out.empty() ? nullptr : j->device_out[(size_t)i];
       // (an image the libjpeg-exact decode does not take has no scaled picture: it stays in the batch at scale 1, unwritten, and fails with that decode's reason below)
       if (j->kind == kJpegPixels && o.jpeg_scale != 1 && !bt.CanDecodeJpegPixels(index[(size_t)i], nullptr)) o.jpeg_scale = 1;
+      // (nor a u8 picture for the integer resample, OutputSpec::resize_u8: it stays as an f32-resampled output, unwritten, and fails alone with the reason below)
+      const bool wants_u8 = o.resize_u8;
+      if (j->kind == kJpegPixels && o.resize_u8 && !bt.CanDecodeJpegPixels(index[(size_t)i], nullptr)) o.resize_u8 = false;
       size_t need = 0;
       std::string refusal;
       try { need = bt.OutputSizeOf(index[(size_t)i], o); } catch (const ParseError& e) { refusal = e.what(); }     // (a plane_stride this image does not fit, a crop that leaves it: Batch::LayoutRefusal / ResizeRefusal)
@@ -310,7 +313,7 @@ void Pipeline::PrepareJob(Job* j, int worker) {
         j->batch_index[(size_t)i] = -2 - index[(size_t)i];
       } else if (j->kind == kJpegPixels && !bt.CanDecodeJpegPixels(index[(size_t)i], &not_eligible)) {
         // (a libjpeg-exact job: what that decode does not take stays in the batch too and fails with the batch call's reason; nothing is written for it)
-        j->result.error[(size_t)i] = not_eligible;
+        j->result.error[(size_t)i] = wants_u8 ? "unsupported: integer resample of an image the libjpeg-exact decode does not take (" + not_eligible + ")" : not_eligible;
         o.device_ptr = nullptr;
         j->batch_index[(size_t)i] = -2 - index[(size_t)i];
       } else if (!j->capacity.empty() && j->capacity[(size_t)i] < need) {
@@ -586,6 +589,7 @@ void Pipeline::Harvest(Job* j) {
   {
     std::lock_guard<std::mutex> lock(mu_);
     if (readback_ok) last_info_["hf_nonzeros"] = bt.Info("hf_nonzeros");
+    if (readback_ok) last_info_["resize_u8_images"] = bt.Info("resize_u8_images");     // (of the job harvested last: its images resampled in Pillow's 8-bit arithmetic)
     if (readback_ok) { last_info_["jpeg_pixel_images"] = j->kind == kJpegPixels ? bt.Info("jpeg_pixel_images") : 0; last_info_["jpeg_pixel_launches"] = j->kind == kJpegPixels ? bt.Info("jpeg_pixel_launches") : 0; }
     if (readback_ok) {
       last_info_["jpeg_device_images"] = j->jpeg_counts[0]; last_info_["jpeg_host_images"] = j->jpeg_counts[1];

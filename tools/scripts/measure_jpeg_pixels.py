@@ -15,6 +15,8 @@ turned into JPEG XL by tests/jpeg_tools.transcode.  Output of the two device leg
                --resize W,H: every image of the jobs comes out W x H (the triangle filter); --jpeg_scale 2 | 4 | 8: libjpeg's scaled decode (Pipeline.submit(jpeg_scale=)),
                the source of that resize.  With either, the pixels are not compared with Pillow here (tests/test_jpeg_scaled_pixels.py does); "pixel_half_ms_per_job" is
                idct_ms + out_ms of the brackets: integer IDCT, colour-out and the resizes
+               --resize_u8 (with --resize): the resample in Pillow's 8-bit arithmetic over a u8 intermediate (Pipeline.submit(resize_u8=True)); the first image of the first
+               job is compared with PIL's resize of the source file (after draft() for --jpeg_scale), byte for byte
   pipeline_float  the same jobs without jpeg_pixels: libjxl's rendering through the float tail — what a loader of these files gets from a Pipeline otherwise
 
 Every leg runs --reps times after --warmup; the median is reported.  The first run of a leg is checked: pixels and reconstruct equal Pillow's decode of the source
@@ -54,6 +56,7 @@ def main():
     ap.add_argument("--jobs", type=int, default=6, help="pipeline legs: jobs per repetition")
     ap.add_argument("--resize", default=None, help="pipeline legs: W,H of every output")
     ap.add_argument("--jpeg_scale", type=int, default=1, help="pipeline leg: libjpeg's scaled decode (2, 4, 8)")
+    ap.add_argument("--resize_u8", action="store_true", help="pipeline leg: the integer resample (needs --resize)")
     args = ap.parse_args()
     import numpy as np
     from PIL import Image
@@ -145,6 +148,13 @@ def main():
                 kw["resize"] = resize
             if scaled:
                 kw["jpeg_scale"] = args.jpeg_scale
+            u8 = exact and args.resize_u8
+            if u8 and (not resize or "resize_u8" not in jx.Pipeline.submit.__code__.co_varnames):
+                out[leg] = "--resize_u8 needs --resize and a build with Pipeline.submit(resize_u8=)"
+                p.close()
+                continue
+            if u8:
+                kw["resize_u8"] = True
             stages = None
             for r in range(args.warmup + args.reps):
                 if r == args.warmup:
@@ -157,7 +167,14 @@ def main():
                     assert st == [0] * len(inputs), st
                 torch.cuda.synchronize()
                 times.append((time.perf_counter() - t0) * 1e3 / args.jobs)
-                if r == 0 and (resize or scaled):
+                if r == 0 and u8:
+                    im = Image.open(io.BytesIO(files[0]))
+                    if scaled:
+                        im.draft(im.mode, (w // args.jpeg_scale, h // args.jpeg_scale))
+                    ref = np.asarray(im.resize(resize, Image.BILINEAR))
+                    diff = int(np.abs(bufs[0][0].cpu().numpy().reshape(ref.shape).astype(int) - ref).max())
+                    assert diff == 0, "the integer resample differs from PIL's resize of the source file"
+                elif r == 0 and (resize or scaled):
                     diff = None
                 elif r == 0:
                     got = [bufs[0][k].cpu().numpy().reshape(h, w, 3) for k in range(args.distinct)]
@@ -169,7 +186,7 @@ def main():
             out[leg].update(jobs_per_rep=args.jobs, max_difference_from_pillow=diff, stages_ms_per_job=stages, timed_jobs=runs, private_plane_jobs=p.info("private_plane_jobs"))
             out[leg].update(output_size=[ow, oh], device_bytes=p.info("device_bytes"), pixel_half_ms_per_job=round(stages.get("idct_ms", 0) + stages.get("out_ms", 0), 3))
             if exact:
-                out[leg].update(pixel_launches=p.info("jpeg_pixel_launches"), jpeg_scale=args.jpeg_scale)
+                out[leg].update(pixel_launches=p.info("jpeg_pixel_launches"), jpeg_scale=args.jpeg_scale, resize_u8=bool(u8))
             p.close()
             del p, bufs
         elif leg == "reconstruct":

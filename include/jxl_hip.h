@@ -380,6 +380,24 @@ JxlDecoderStatus JxlHipBatchOutBufferSizeJpegScaled(const JxlHipBatch* batch, in
                                                     const JxlHipOutputResample* resample, size_t* size);
 JxlDecoderStatus JxlHipBatchSetOutputJpegScaled(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int jpeg_scale, const JxlHipOutputLayout* layout,
                                                 const JxlHipOutputResample* resample);
+/* jpeg_scale = 8 from the DC terms alone.  At that scale grey, 4:4:4 and 4:2:2 images take the 1 x 1 IDCT for every component (rules 1 and 6 above): a sample is
+ * clamp(DESCALE(dc x q[0], 3) + 128) of one DC term, and the DC terms are what the LF stage of the decode writes.  Such an image is DC-only: the HF entropy stage, the
+ * integer IDCT and the intermediate planes are left out for it, it takes neither coefficient nor pixel planes, and one kernel writes the picture — byte for byte what
+ * the general path gives.  4:2:0 needs the 2 x 2 chroma IDCT, hence AC terms, and keeps the general path, as does every image at scale 1, 2 and 4.
+ * JxlHipBatchJpegDcOnly(index), host only, after the image's output has been set: 1 if the image will be decoded from its DC terms, else 0.
+ * Prefixes: a DC-only image may end anywhere behind the LF part of its frame (LfGlobal, the LfGroups, HfGlobal — a fifth of a typical quality-85 transcode), as for the
+ * 1:8 decode: add it under JxlHipBatchSetOption "allow_partial" = 1.  A prefix that ends inside the LF part is "truncated"; so is one whose image is not DC-only —
+ * when the batch is prepared, as for a prefix that is not decoded at 1:8.  A one-section frame (one group) has no LF prefix: it is DC-only from the whole file only.
+ * Jobs of JxlHipPipelineSubmitJpegPixelsScaled / ...Resampled with jpeg_scale = 8 take prefixes as they are; a prefix that is not enough fails alone, "truncated".
+ * JxlHipLfPartSize: *bytes = the number of leading bytes of the FILE (container boxes included) that hold the LF part of the first frame — the smallest n for which
+ * data[0 .. n) is accepted by the 1:8 decode and by a DC-only decode.  It needs the headers and the frame's TOC only, so any prefix that holds those gives the same
+ * answer as the whole file; JXL_DEC_ERROR with "truncated" when the TOC is not there yet (or the codestream goes on in a box that is not).  *bytes = 0: the whole file
+ * is needed (a one-section frame, a Modular frame, sections stored out of order).
+ * JxlHipBatchSetOption "jpeg_dc_only" (default 1; 0: the general path for every image, read by the next JxlHipBatchPrepare — what a doubted result is compared with;
+ * pipelines always take the DC-only path).  JxlHipBatchGetInfo / JxlHipPipelineGetInfo "jpeg_dc_only_images": images of the last call / the job finished last that were
+ * written from their DC terms; they count in "jpeg_pixel_images" as before.  A group of DC-only images adds one launch to "jpeg_pixel_launches", not two. */
+int JxlHipBatchJpegDcOnly(const JxlHipBatch* batch, int index);
+JxlDecoderStatus JxlHipLfPartSize(const uint8_t* data, size_t size, size_t* bytes);
 /* The integer resample of libjpeg-exact outputs: Pillow's 8-bit resize, byte for byte.  JxlHipBatchSetOutputJpegResampled is JxlHipBatchSetOutputJpegScaled with
  * `flags`; flags = 0 is that call, byte for byte; bit 0, JXL_HIP_RESAMPLE_U8, selects the integer resample; every other bit is refused.  Sizes are those of
  * JxlHipBatchOutBufferSizeJpegScaled / JxlHipImageOutSizeJpegScaled.  With the flag the u8 output equals

@@ -202,6 +202,7 @@ def libjxl():
             "JxlHipImageOutSizeJpegScaled": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(JxlBasicInfo),
                                                        C.POINTER(sz)]),
             "JxlHipBatchCanDecodeJpegPixels": (C.c_int, [vp, C.c_int]), "JxlHipBatchDecodeJpegPixels": (C.c_int, [vp, vp]), "JxlHipBatchJpegPixelsStatus": (C.c_int, [vp, C.c_int]),
+            "JxlHipBatchJpegDcOnly": (C.c_int, [vp, C.c_int]), "JxlHipLfPartSize": (C.c_int, [vp, sz, C.POINTER(sz)]),
             "JxlHipBatchSetLaneStride": (None, [vp, C.c_int, C.c_int]), "JxlHipBatchSetOption": (None, [vp, C.c_char_p, C.c_int]),
             "JxlHipBatchPrepare": (C.c_int, [vp, vp]), "JxlHipBatchDecode": (C.c_int, [vp, vp]),
             "JxlHipBatchDecodeTimed": (C.c_int, [vp, vp]), "JxlHipBatchFinish": (C.c_int, [vp, vp]),
@@ -790,7 +791,9 @@ class BatchDecoder:
         picture is stored with its columns reversed (include/jxl_hip.h JxlHipOutputResample).  Both need resize; a call without them is the ...Resized call as before.
         jpeg_scale=2 | 4 | 8: libjpeg's scaled decode of a JPEG transcode (include/jxl_hip.h JxlHipBatchSetOutputJpegScaled) — the ceil(w / s) x ceil(h / s) picture
         PIL's draft() gives for the original file, sample for sample, as the source of everything above (a crop is in the scaled picture).  Only decode_jpeg_pixels()
-        writes such an output (decode() + finish() fail the image); not together with downscale.
+        writes such an output (decode() + finish() fail the image); not together with downscale.  jpeg_scale=8 of a grey, 4:4:4 or 4:2:2 image is decoded from
+        the DC terms alone (jpeg_dc_only(i)): `data` may then end anywhere behind the LF part of its frame (lf_part_size(data)); a prefix of any other image
+        fails the next prepare() with "truncated".
         resize_u8=True (needs resize, and an image decode_jpeg_pixels() takes): the resample runs in Pillow's 8-bit arithmetic over the u8 picture libjpeg gives
         (include/jxl_hip.h JxlHipBatchSetOutputJpegResampled) — the u8 output is np.asarray(Image.open(file).crop(box).resize(size, BILINEAR | BICUBIC)) byte for
         byte, every other type and layout follows from it, and the intermediates are u8.  Only decode_jpeg_pixels() writes such an output; not together with downscale."""
@@ -798,12 +801,13 @@ class BatchDecoder:
         rs = _resize(resize, crop) if filter is None and not mirror else _resample(resize, crop, filter, mirror)
         L = libjxl()
         buf = np.frombuffer(data, dtype=np.uint8)
-        if downscale != 1:
+        prefix_ok = downscale != 1 or int(jpeg_scale) == 8                  # decodes that may end behind the LF stage
+        if prefix_ok:
             L.JxlHipBatchSetOption(self._h, b"allow_partial", 1)
         try:
             i = L.JxlHipBatchAddImage(self._h, buf.ctypes.data, len(data))
         finally:
-            if downscale != 1:
+            if prefix_ok:
                 L.JxlHipBatchSetOption(self._h, b"allow_partial", 0)
         if i < 0:
             raise GenericError(last_error())
@@ -822,12 +826,13 @@ class BatchDecoder:
         n = len(datas)
         ptrs = (C.c_char_p * n)(*datas)
         sizes = (C.c_size_t * n)(*[len(d) for d in datas])
-        if downscale != 1:
+        prefix_ok = downscale != 1 or int(jpeg_scale) == 8
+        if prefix_ok:
             L.JxlHipBatchSetOption(self._h, b"allow_partial", 1)
         try:
             first = L.JxlHipBatchAddImages(self._h, ptrs, sizes, n, int(threads))
         finally:
-            if downscale != 1:
+            if prefix_ok:
                 L.JxlHipBatchSetOption(self._h, b"allow_partial", 0)
         if first < 0:
             raise GenericError(last_error())
@@ -933,6 +938,11 @@ class BatchDecoder:
         """True if decode_jpeg_pixels() takes image i (host only); otherwise last_error() says why not: "unsupported: libjpeg-exact decode of ..."."""
         return bool(libjxl().JxlHipBatchCanDecodeJpegPixels(self._h, i))
 
+    def jpeg_dc_only(self, i) -> bool:
+        """True if image i (output set: after add) will be decoded from its DC terms alone — jpeg_scale=8 of a grey, 4:4:4 or 4:2:2 transcode — i.e. if a prefix
+        of lf_part_size() bytes was enough (include/jxl_hip.h JxlHipBatchJpegDcOnly); set_option("jpeg_dc_only", 0) turns the path off."""
+        return bool(libjxl().JxlHipBatchJpegDcOnly(self._h, int(i)))
+
     def decode_jpeg_pixels(self, stream=None) -> list:
         """The samples libjpeg gives for the original JPEG file of every transcode of the batch (integer IDCT, libjpeg's chroma upsampling and colour conversion), written
         like a decode(): output(i) / device_output(i) hand them out.  Returns, per image, None or the reason why that image has no pixels (it fails alone)."""
@@ -981,6 +991,17 @@ class BatchDecoder:
     @property
     def device_bytes(self):
         return libjxl().JxlHipBatchDeviceBytes(self._h)
+
+
+def lf_part_size(data: bytes) -> int:
+    """The number of leading bytes of the file that hold the LF part of its first frame: data[:n] is the shortest prefix the 1:8 decode (downscale=8) and a DC-only
+    decode (jpeg_scale=8, BatchDecoder.jpeg_dc_only) accept.  From the headers and the TOC, so a prefix that holds those gives the same answer; DecodeError
+    "truncated" before that.  0: the whole file is needed (one-group frames).  Host only (include/jxl_hip.h JxlHipLfPartSize)."""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    n = C.c_size_t()
+    if libjxl().JxlHipLfPartSize(buf.ctypes.data if len(data) else None, len(data), C.byref(n)) != JXL_DEC_SUCCESS:
+        raise GenericError(last_error())
+    return int(n.value)
 
 
 def arena_pool_trim() -> int:

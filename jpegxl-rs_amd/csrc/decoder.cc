@@ -545,12 +545,15 @@ int Batch::AddImages(const uint8_t* const* datas, const size_t* sizes, int n, in
 
 // The pipelined form: an image that does not parse (truncated, damaged headers, a feature the device path does not take) is left out instead of failing the call —
 // (*index)[i] = its index in the batch or -1, (*errors)[i] = what it threw ("" if it parsed).
-void Batch::AddImagesTolerant(const uint8_t* const* datas, const size_t* sizes, int n, int threads, vec<int>* index, std::vector<std::string>* errors, bool for_downscale) {
-  AddImagesImpl(datas, sizes, n, threads, /*tolerant=*/true, index, errors, /*allow_partial=*/for_downscale, /*only_downscalable=*/for_downscale);
+void Batch::AddImagesTolerant(const uint8_t* const* datas, const size_t* sizes, int n, int threads, vec<int>* index, std::vector<std::string>* errors, bool for_downscale, bool for_jpeg_dc) {
+  AddImagesImpl(datas, sizes, n, threads, /*tolerant=*/true, index, errors, /*allow_partial=*/for_downscale || for_jpeg_dc, /*only_downscalable=*/for_downscale, /*partial_only_jpeg_dc=*/for_jpeg_dc);
 }
 
 static std::string DownscaleRefusalOf(int num_units, const ImageEntry& e);   // (below, with SetOutput)
-int Batch::AddImagesImpl(const uint8_t* const* datas, const size_t* sizes, int n, int threads, bool tolerant, vec<int>* index, std::vector<std::string>* errs, bool allow_partial, bool only_downscalable) {
+static std::string JpegPixelsRefusalOf(int num_units, bool complex, const ImageEntry& e, const OutputSpec& out);   // (below, with DecodeJpegPixels)
+static bool JpegDcEligibleOf(const FramePlan& p, const OutputSpec& out);
+int Batch::AddImagesImpl(const uint8_t* const* datas, const size_t* sizes, int n, int threads, bool tolerant, vec<int>* index, std::vector<std::string>* errs, bool allow_partial, bool only_downscalable,
+                         bool partial_only_jpeg_dc) {
   index->assign((size_t)std::max(n, 0), -1);
   errs->assign((size_t)std::max(n, 0), std::string());
   if (n <= 0) return (int)pub_.size();
@@ -585,6 +588,13 @@ int Batch::AddImagesImpl(const uint8_t* const* datas, const size_t* sizes, int n
       // a job decoded at 1:8: what that decode does not take is left out like an image that does not parse (nothing of it is uploaded or decoded)
       (*errs)[i] = DownscaleRefusalOf((int)parsed[i].units.size(), *parsed[i].units[0]);
       if (!(*errs)[i].empty()) continue;
+    }
+    if (tolerant && partial_only_jpeg_dc && !parsed[i].units.empty() && parsed[i].units[0]->plan.partial) {
+      // a job decoded at libjpeg's scale 1/8: a stream that ends behind its LF part is enough for a DC-only image and for no other — that one is left out, "truncated"
+      OutputSpec o8;
+      o8.jpeg_scale = 8;
+      const ImageEntry& e = *parsed[i].units[0];
+      if (!jpeg_dc_only || !JpegPixelsRefusalOf((int)parsed[i].units.size(), parsed[i].complex, e, o8).empty() || !JpegDcEligibleOf(e.plan, o8)) { (*errs)[i] = "truncated"; continue; }
     }
     (*index)[i] = Append(std::move(parsed[i]));
   }
@@ -932,6 +942,7 @@ void Batch::SetOutput(int i, const OutputSpec& o) {
     if (!CanDecodeJpegPixelsAs(i, o, &why)) throw ParseError("unsupported: integer resample of an image the libjpeg-exact decode does not take (" + why + ")", true);
   }
   e.out = o;
+  e.jpeg_dc_eligible = JpegDcEligibleOf(e.plan, o);      // (jpeg_scale 8: CanDecodeJpegPixelsAs has taken the image above)
   if (o.only_frame >= pub_[i].num_units) throw ParseError("non-coalesced output: no such frame", false);
   // (a lone frame that fills the image is the same either way: the plain path keeps it)
   if (o.only_frame == 0 && pub_[i].num_units == 1 && !e.plan.have_crop) e.out.only_frame = -1;
@@ -1001,6 +1012,10 @@ void Batch::StageBytes(uint64_t out[6]) const {
       out[5] += (uint64_t)((p.width + 7) / 8) * ((p.height + 7) / 8) * (12 + out_px);
       continue;
     }
+    if (JpegDcOnlyUnit((int)u)) {        // DC-only: no HF stage, no IDCT; JpegDcOutKernel reads one DC term (i32) per component and writes one pixel of the scaled picture
+      out[5] += (uint64_t)((e.ih.xsize + 7) / 8) * ((e.ih.ysize + 7) / 8) * (4 * (e.ih.color_space == 1 ? 1 : 3) + out_px);
+      continue;
+    }
     out[2] += hf_sec + (u < hf_written_.size() ? (uint64_t)hf_written_[u] * 4 : 0);
     out[3] += npx * (12 + 12);
     const bool fused = p.lf.gab && p.lf.epf_iters == 1 && e.ih.xyb_encoded && SimpleTransfer(e.ih) && p.upsampling == 1 && !e.complex && !cfg.force_unfused_filters;
@@ -1068,7 +1083,8 @@ int64_t Batch::Info(const std::string& name) const {
   if (name == "jpeg_device_progressive_images") return jpeg_device_progressive_images_;    // ... of the device's, those with at least one progressive scan
   if (name == "jpeg_gather_launches") return jpeg_gather_launches_;                        // ... launches of JpegGatherKernel: one per group of the gather table
   if (name == "jpeg_pixel_images") return jpeg_pixel_images_;       // images the last DecodeJpegPixels wrote
-  if (name == "jpeg_pixel_launches") return jpeg_pixel_launches_;   // ... launches of its two pixel kernels (two per group of the image table, however many images a group holds)
+  if (name == "jpeg_pixel_launches") return jpeg_pixel_launches_;   // ... launches of its pixel kernels (two per group of the image table, one per DC-only group, however many images a group holds)
+  if (name == "jpeg_dc_only_images") return jpeg_dc_only_images_;   // ... images of it written from their DC terms alone (JpegDcOutKernel; Batch::JpegDcOnly)
   if (name == "lf_simt_lanes") return lf_simt_.num_lanes;
   if (name == "lf_simt_wp") return lf_simt_.num_lanes ? lf_simt_.any_wp : 0;     // the SIMT launch is the weighted-predictor instantiation
   // the kernels the last decode's LF / HF stage launched (kernels.h kHfVar* / kLfVar* bits) and the LDS sizes that chose them (bytes, after Prepare)
@@ -1287,6 +1303,8 @@ struct Batch::PrepareState {
 
 // frames decoded at 1:8 (OutputSpec::downscale == 8; SetOutput only lets single-frame VarDCT images through): their decode ends behind the LF post-processing
 bool Batch::DecodedAtEighth(int unit) const { return images_[unit]->frame_index == 0 && images_[unit]->out.downscale == 8; }
+// the frame of a DC-only image (decoder.h JpegDcOnly; SetOutput only lets single-frame JPEG transcodes through): its decode ends behind the LF decode
+bool Batch::JpegDcOnlyUnit(int unit) const { return jpeg_dc_only && images_[unit]->frame_index == 0 && images_[unit]->jpeg_dc_eligible; }
 
 // Device allocations are kept from one Prepare to the next and only replaced when they are too small (DevReserve): a batch object
 // that is refilled step after step (JxlHipBatchReset + AddImages + Prepare, the streaming loop of bench.py) allocates once —
@@ -1360,8 +1378,8 @@ void Batch::PutStreamTables(PrepareState& st) {
       resize_plans_.push_back(rp);
     }
     st.cs_bytes[i] = e.cs.size;
-    if (DecodedAtEighth(i) && !p.single_section) {
-      // the 1:8 decode reads LfGlobal, the LfGroups and (on the host) HfGlobal: what lies behind the last of them — the AC groups, most of the file — stays on the host
+    if (EndsBehindLf(i) && !p.single_section) {
+      // the 1:8 decode and the DC-only one read LfGlobal, the LfGroups and (on the host) HfGlobal: what lies behind the last of them — the AC groups, most of the file — stays on the host
       size_t end = 0;
       for (size_t k = 0; k < 2 + (size_t)p.num_lf_groups && k < p.sections.size(); k++) end = std::max<size_t>(end, p.sections[k].offset + p.sections[k].size);
       st.cs_bytes[i] = std::min(e.cs.size, end);
@@ -1383,8 +1401,9 @@ void Batch::PutStreamTables(PrepareState& st) {
     max_groups_ = std::max<int>(max_groups_, p.num_groups);
     max_w_ = std::max<int>(max_w_, p.width); max_h_ = std::max<int>(max_h_, p.height);
     max_bw_ = std::max<int>(max_bw_, p.bw); max_bh_ = std::max<int>(max_bh_, p.bh);
-    if (!p.modular) (DecodedAtEighth(i) ? any_scaled_ : any_full_vardct_) = true;
-    if (!p.modular && !DecodedAtEighth(i)) {
+    if (!p.modular && DecodedAtEighth(i)) any_scaled_ = true;
+    if (!p.modular && !EndsBehindLf(i)) any_full_vardct_ = true;
+    if (!p.modular && !EndsBehindLf(i)) {
       const bool fusable = p.lf.gab && p.lf.epf_iters == 1 && e.ih.xyb_encoded && SimpleTransfer(e.ih) && p.upsampling == 1 && !e.complex;
       if (p.upsampling > 1 && !e.complex) { fplan_.any_upsampled = true; fplan_.max_out_w = std::max<int>(fplan_.max_out_w, e.ih.xsize); fplan_.max_out_h = std::max<int>(fplan_.max_out_h, e.ih.ysize); }
       fplan_.any_fused |= fusable; fplan_.any_unfused |= !fusable;
@@ -1415,7 +1434,7 @@ void Batch::LayOutWork(PrepareState& st) {
   size_t wcoef = 0;
   for (int i = 0; i < n; i++) {
     const FramePlan& p = images_[i]->plan;
-    if (p.modular || DecodedAtEighth(i)) continue;
+    if (p.modular || EndsBehindLf(i)) continue;
     for (int c = 0; c < 3; c++) { st.wo[i].coeff[c] = Align(wcoef); wcoef = st.wo[i].coeff[c] + (size_t)p.num_groups * 65536 * 4; }
   }
   coeff_bytes_ = Align(wcoef);
@@ -1448,7 +1467,7 @@ void Batch::LayOutWork(PrepareState& st) {
     }
     if (((p.has_global_tree && p.tree_code.lz77) || lz_local) && (!p.gchannels.empty() || !p.modular))   // LZ77 windows of the Modular streams (4 MiB each); VarDCT: + one per LF group
       o.lz_window = st.take((size_t)(1 + p.NumModUnits() + (p.modular ? 0 : p.num_lf_groups)) * (4u << 20));
-    if (!p.modular && !DecodedAtEighth(i)) {   // LZ77-coded AC streams: a window per group stream (1 MiB each, only for the frames that use them)
+    if (!p.modular && !EndsBehindLf(i)) {   // LZ77-coded AC streams: a window per group stream (1 MiB each, only for the frames that use them)
       bool lz_ac = p.single_section;    // (a one-section frame's AC code is only parsed once its LF streams have been decoded: always reserved, 1 MiB)
       for (auto& code : p.ac_code) lz_ac |= code.lz77;
       if (lz_ac) o.lz_ac_window = st.take((size_t)p.num_groups * kAcLzWindow * 4);
@@ -1484,7 +1503,7 @@ void Batch::LayOutVarDct(int i, PrepareState& st) {
   o.ytox = st.take(ntile); o.ytob = st.take(ntile);
   const size_t plane = (size_t)p.bw * 8 * p.bh * 8 * 4;
   for (int c = 0; c < 3; c++) {
-    if (DecodedAtEighth(i)) { o.plane_a[c] = o.plane_b[c] = (size_t)-1; continue; }      // (no full-resolution planes)
+    if (EndsBehindLf(i)) { o.plane_a[c] = o.plane_b[c] = (size_t)-1; continue; }      // (no full-resolution planes)
     o.plane_a[c] = st.take_big(plane); o.plane_b[c] = (st.need_plane_b || e.complex) ? st.take_big(plane) : (size_t)-1;
   }
   if (p.upsampling > 1 && !e.complex) for (int c = 0; c < 4; c++) o.up_plane[c] = st.take_big((size_t)e.ih.xsize * e.ih.ysize * 4);
@@ -1676,7 +1695,8 @@ void Batch::FillFrameCommon(int i, const uint8_t* cbase, const PrepareState& st)
   // (an output with jpeg_scale: DecodeJpegPixels writes it from its own table; the write stage of a Run, which fails such an image, stays inside the scaled picture —
   // OutputKernel, the only writer of a frame CanDecodeJpegPixelsAs takes, is bounded by img_w x img_h)
   if (e.frame_index == 0 && e.out.jpeg_scale > 1) { f.img_w = (e.ih.xsize + e.out.jpeg_scale - 1) / e.out.jpeg_scale; f.img_h = (e.ih.ysize + e.out.jpeg_scale - 1) / e.out.jpeg_scale; }
-  if (DecodedAtEighth(i)) { f.lf_only = 1; f.img_w = (p.width + 7) / 8; f.img_h = (p.height + 7) / 8; }     // (the picture LfOutputKernel writes; out_stride is SetOutput's, of the same picture)
+  if (DecodedAtEighth(i)) { f.lf_only = kLfOnlyEighth; f.img_w = (p.width + 7) / 8; f.img_h = (p.height + 7) / 8; }     // (the picture LfOutputKernel writes; out_stride is SetOutput's, of the same picture)
+  else if (JpegDcOnlyUnit(i)) f.lf_only = kLfOnlyJpegDc;      // (img_w x img_h: the scaled picture, above; JpegDcOutKernel goes by its own table)
   if (p.upsampling > 1) { f.up_weights = (const float*)(cbase + c.up_weights); for (int k = 0; k < 4; k++) f.up_plane[k] = (float*)(dbig_ + o.up_plane[k]); }
   f.post_mode = e.complex ? 1 : 0;
   f.lz_window = o.lz_window == (size_t)-1 ? nullptr : (uint32_t*)(dwork_ + o.lz_window);
@@ -1715,7 +1735,7 @@ void Batch::FillFrameVarDct(int i, const uint8_t* cbase, const PrepareState& st)
   FillColor(e.ih, p.do_ycbcr, f);
   for (int k = 0; k < 3; k++) {
     f.lfq[k] = (int32_t*)(dwork_ + o.lfq[k]); f.lf[k] = (float*)(dwork_ + o.lf[k]); f.lf_tmp[k] = (float*)(dwork_ + o.lf_tmp[k]);
-    f.llf[k] = (float*)(dwork_ + o.llf[k]); f.coeff[k] = DecodedAtEighth(i) ? nullptr : (int32_t*)(dcoef_ + o.coeff[k]);
+    f.llf[k] = (float*)(dwork_ + o.llf[k]); f.coeff[k] = EndsBehindLf(i) ? nullptr : (int32_t*)(dcoef_ + o.coeff[k]);
     f.plane_a[k] = o.plane_a[k] == (size_t)-1 ? nullptr : (float*)(dbig_ + o.plane_a[k]); f.plane_b[k] = o.plane_b[k] == (size_t)-1 ? nullptr : (float*)(dbig_ + o.plane_b[k]);
   }
   f.blk_info = (uint32_t*)(dwork_ + o.blk_info); f.coef_off = (uint32_t*)(dwork_ + o.coef_off);
@@ -1830,7 +1850,7 @@ void Batch::PutHfTables(PrepareState& st) {
         cp.orders[b * 3 + ch] = cu.empty() ? st.natural_off[b] : arena.Put(cu.data(), cu.size() * 2);
       }
     }
-    if (p.num_passes > 1 && !DecodedAtEighth(i)) any_multipass_ = true;     // (what the HF stage must handle: frames decoded at 1:8 never reach it)
+    if (p.num_passes > 1 && !EndsBehindLf(i)) any_multipass_ = true;     // (what the HF stage must handle: frames decoded at 1:8 never reach it)
     for (int k = 0; k < 17; k++) {
       const size_t* off = QuantTableOffsets(arena, st.qcache, p.qspec[k], k);
       for (int ch = 0; ch < 3; ch++) c.qtable[k * 3 + ch] = off[ch];
@@ -1849,7 +1869,7 @@ void Batch::SizeLds() {
     for (auto& ls : p.local_streams) { SizeForModularStream(cfg, ls.tree, ls.code); if (ls.unit != 0) cfg.any_local_trees = 1; }
     if (!p.lf_local.empty()) cfg.any_local_lf = 1;
     for (auto& l : p.lf_local) if (l.present) SizeForModularStream(cfg, l.tree, l.code);
-    if (!p.modular && DecodedAtEighth(i)) continue;     // (the rest sizes and picks the HF / IDCT kernels)
+    if (!p.modular && EndsBehindLf(i)) continue;     // (the rest sizes and picks the HF / IDCT kernels)
     if (!p.modular) for (auto& code : p.ac_code) { cfg.ac_code_bytes = std::max(cfg.ac_code_bytes, CodeBytes(code, true)); cfg.ac_code_bytes_compact = std::max(cfg.ac_code_bytes_compact, CodeBytesCompact(code)); }
     if (p.subsampled) cfg.any_subsampled = 1;
     if (!p.modular) for (auto& code : p.ac_code) if (code.use_prefix || code.lz77) cfg.any_prefix_ac = 1;
@@ -2014,9 +2034,9 @@ void Batch::PrepareLfFrameBatch(void* stream_v, bool wait_upload) {
 void Batch::FinishCfg() {
   const int n = (int)images_.size();
   // (a frame cut off inside its AC groups, FramePlan::partial: the HF kernels leave out the group streams that are not completely there; nothing to do when none is)
-  for (int i = 0; i < n; i++) if (images_[i]->plan.partial && images_[i]->plan.partial_ac_sections == 0 && !DecodedAtEighth(i)) cfg.skip_hf = 1;
+  for (int i = 0; i < n; i++) if (images_[i]->plan.partial && images_[i]->plan.partial_ac_sections == 0 && !EndsBehindLf(i)) cfg.skip_hf = 1;
   if (refuse_partial_unscaled)
-    for (int i = 0; i < n; i++) if (images_[i]->plan.partial && !DecodedAtEighth(i)) throw ParseError("truncated", false);
+    for (int i = 0; i < n; i++) if (images_[i]->plan.partial && !EndsBehindLf(i)) throw ParseError("truncated", false);
   cfg.any_multipass = any_multipass_ ? 1 : 0;
   if (any_multipass_) cfg.lane_stride_hf = 1;   // progressive frames: only the SIMT HF kernel walks the passes
   if (cfg.any_subsampled) cfg.lane_stride_hf = 1;   // so do chroma-subsampled frames (per-channel block grids)
@@ -2897,15 +2917,14 @@ void Batch::ApplyIdctFlags(const uint32_t* flags) {
 // ---- JPEG reconstruction -----------------------------------------------------------------------------------------------------------------
 // What a lossless JPEG transcode looks like as a frame: one VarDCT frame in YCbCr (or of a grey image), not XYB, without extra channels, upsampling, passes or
 // image features.  (The RAW quantisation table belongs to it too, but a one-group frame's is only known after Prepare: the callers look at it then.)
-bool Batch::IsPlainJpegFrame(int i) const {
-  const PubImage& pi = pub_[i];
-  const ImageEntry& e = *images_[pi.first_unit];
+static bool IsPlainJpegFrameOf(int num_units, bool complex, const ImageEntry& e) {
   const FramePlan& p = e.plan;
-  if (pi.num_units != 1 || (pi.complex && !p.subsampled) || p.modular || e.ih.xyb_encoded || !p.do_ycbcr && e.ih.color_space != 1) return false;
+  if (num_units != 1 || (complex && !p.subsampled) || p.modular || e.ih.xyb_encoded || !p.do_ycbcr && e.ih.color_space != 1) return false;
   if (p.upsampling != 1 || p.num_passes != 1 || !e.ih.extra.empty()) return false;
   if (p.subsampled && ((p.flags & (1 | 2 | 16)) || p.have_crop || p.frame_type != 0)) return false;
   return true;
 }
+bool Batch::IsPlainJpegFrame(int i) const { return IsPlainJpegFrameOf(pub_[i].num_units, pub_[i].complex, *images_[pub_[i].first_unit]); }
 
 bool Batch::CanReconstructJpeg(int i, std::string* why) {
   auto no = [&](const char* m) { if (why) *why = m; return false; };
@@ -3470,11 +3489,16 @@ bool Batch::CanDecodeJpegPixels(int i, std::string* why) const { return CanDecod
 // upsampling, extra channels and image features a frame reaches the caller's buffer through OutputKernel alone, which is bounded by img_w x img_h.  The fused filter
 // kernels, the EPF kernels that write, the Modular write and the frame tail are bounded by the frame's own size — whoever lets such a frame in here must bound those too.
 bool Batch::CanDecodeJpegPixelsAs(int i, const OutputSpec& out, std::string* why) const {
-  auto no = [&](const std::string& m) { if (why) *why = "unsupported: libjpeg-exact decode of " + m; return false; };
-  const ImageEntry& e = *images_[pub_[i].first_unit];
+  const std::string refusal = JpegPixelsRefusalOf(pub_[i].num_units, pub_[i].complex, *images_[pub_[i].first_unit], out);
+  if (why && !refusal.empty()) *why = refusal;
+  return refusal.empty();
+}
+// ("" = taken) over an image as it was parsed, in a batch or not yet (AddImagesImpl)
+static std::string JpegPixelsRefusalOf(int num_units, bool complex, const ImageEntry& e, const OutputSpec& out) {
+  auto no = [&](const std::string& m) { return "unsupported: libjpeg-exact decode of " + m; };
   const FramePlan& p = e.plan;
-  if (!IsPlainJpegFrame(i)) return no("an image that is not a plain JPEG-transcoded frame");
-  if (pub_[i].complex || p.have_crop || p.frame_type != 0 || (p.flags & (1 | 2 | 16))) return no("a frame with patches, splines, noise, a crop or blending");
+  if (!IsPlainJpegFrameOf(num_units, complex, e)) return no("an image that is not a plain JPEG-transcoded frame");
+  if (complex || p.have_crop || p.frame_type != 0 || (p.flags & (1 | 2 | 16))) return no("a frame with patches, splines, noise, a crop or blending");
   if (p.use_lf_frame || e.lf_source) return no("a frame that takes its LF image from an LF frame");
   if (p.lf.gab || p.lf.epf_iters) return no("a frame with restoration filters");
   // Y at full resolution, both chroma channels with the same shifts: 4:4:4, 4:2:2, 4:2:0 (4:4:0 and the rest: libjpeg has rules for them that no test here could pin)
@@ -3486,20 +3510,24 @@ bool Batch::CanDecodeJpegPixelsAs(int i, const OutputSpec& out, std::string* why
     const std::string t = JpegPixelTableRefusal(p);
     if (!t.empty()) return no(t);
   }
-  return true;
+  return std::string();
 }
+// libjpeg's 1/8 decode from the DC terms alone (decoder.h JpegDcOnly), for an image JpegPixelsRefusalOf takes: jdmaster.c gives every component the 1 x 1 IDCT unless
+// both of its dimensions still need upsampling by two — 4:2:0 chroma ((hs, vs) == (1, 1): the 2 x 2 form, three AC terms per block)
+static bool JpegDcEligibleOf(const FramePlan& p, const OutputSpec& out) { return out.jpeg_scale == 8 && out.downscale == 1 && !p.modular && !(p.hs[0] == 1 && p.vs[0] == 1); }
 
 // ---- host plan (after Prepare): which images take the path, their component grids, the image table and the launch groups over it
 size_t Batch::PlanJpegPixels() {
   const int n = (int)pub_.size();
   jpeg_pixel_results_.clear(); jpeg_pixel_results_.resize((size_t)n);
-  jpeg_pixel_images_ = jpeg_pixel_launches_ = 0;
+  jpeg_pixel_images_ = jpeg_pixel_launches_ = jpeg_dc_only_images_ = 0;
   jpeg_pixel_table_.clear(); jpeg_pixel_table_image_.clear(); jpeg_pixel_groups_.clear();
   if (!prepared_) throw ParseError("PlanJpegPixels: the batch is not prepared", false);
-  // entries of scale 1 first, the scaled ones (OutputSpec::jpeg_scale) behind them: the two kinds take different kernels and never share a launch group
+  // entries of scale 1 first, the scaled ones (OutputSpec::jpeg_scale) behind them, the DC-only ones (JpegDcOnly) last: the three kinds take different kernels and never
+  // share a launch group
   vec<JpegPixelImage>& table = jpeg_pixel_table_;
-  vec<JpegPixelImage> scaled_table;
-  vec<int> scaled_image;
+  vec<JpegPixelImage> scaled_table, dc_table;
+  vec<int> scaled_image, dc_image;
   for (int i = 0; i < n; i++) {
     std::string why;
     if (!CanDecodeJpegPixels(i, &why)) { jpeg_pixel_results_[i].error = why; continue; }
@@ -3512,21 +3540,25 @@ size_t Batch::PlanJpegPixels() {
     JpegFrameGrid g;
     if (!JpegGridFromFrame(p, ncomp, "libjpeg-exact decode", &g, &why)) { jpeg_pixel_results_[i].error = why; continue; }
     const FrameDev& f = frames_host_[u];
-    // every address of the two kernels follows from this entry and the frame's own block grid: the component grids must hold the components' real extents and lie inside
+    // a DC-only image (Prepare gave its frame neither coefficient nor pixel planes: FrameDev::lf_only) is written by JpegDcOutKernel from lfq and block info alone
+    const bool dc = JpegDcOnlyUnit(u);
+    // every address of the kernels follows from this entry and the frame's own block grid: the component grids must hold the components' real extents and lie inside
     // the frame's grid, the planes that are read and written must exist
-    bool fits = g.nblk < ((size_t)1 << 31) && f.plane_a[0] && f.plane_a[1] && f.plane_a[2] && !f.lf_only && f.coef_off && f.blk_info && f.status;
+    bool fits = g.nblk < ((size_t)1 << 31) && f.blk_info && f.status;
+    if (dc) fits = fits && f.lf_only == kLfOnlyJpegDc && !(ncomp == 3 && g.vs[1]);
+    else fits = fits && f.plane_a[0] && f.plane_a[1] && f.plane_a[2] && !f.lf_only && f.coef_off;
     for (uint32_t c = 0; c < ncomp && fits; c++) {
       const int chn = ncomp == 1 ? 1 : (c == 0 ? 1 : c == 1 ? 0 : 2);
       const uint32_t cw = (e.ih.xsize + (1u << g.hs[c]) - 1) >> g.hs[c], ch = (e.ih.ysize + (1u << g.vs[c]) - 1) >> g.vs[c];
-      fits = g.grid_w[c] && g.grid_h[c] && (uint64_t)g.grid_w[c] * 8 >= cw && (uint64_t)g.grid_h[c] * 8 >= ch && g.grid_w[c] <= p.bw && g.grid_h[c] <= p.bh && f.coeff[chn] && f.lfq[chn];
+      fits = g.grid_w[c] && g.grid_h[c] && (uint64_t)g.grid_w[c] * 8 >= cw && (uint64_t)g.grid_h[c] * 8 >= ch && g.grid_w[c] <= p.bw && g.grid_h[c] <= p.bh && (dc || f.coeff[chn]) && f.lfq[chn];
     }
     const bool walk = ncomp == 3 && !g.hs[1] && !g.vs[1];      // 4:4:4 colour: chroma from luma, one position per block of the frame
-    if (walk) fits = fits && f.ytox && f.ytob;
+    if (walk && !dc) fits = fits && f.ytox && f.ytob;
     if (!fits) { jpeg_pixel_results_[i].error = "unsupported: libjpeg-exact decode of a frame whose block grid does not hold the image"; continue; }
     JpegPixelImage t;
     memset(&t, 0, sizeof(t));
     for (uint32_t c = 0; c < ncomp; c++) {
-      t.plane[c] = (uint8_t*)f.plane_a[ncomp == 1 ? 1 : (c == 0 ? 1 : c == 1 ? 0 : 2)];     // (the frame's own pixel planes, which this decode does not use otherwise: bw x bh x 64 floats each)
+      t.plane[c] = (uint8_t*)f.plane_a[ncomp == 1 ? 1 : (c == 0 ? 1 : c == 1 ? 0 : 2)];     // (the frame's own pixel planes, which this decode does not use otherwise: bw x bh x 64 floats each; DC-only: none)
       t.comp_first[c] = (uint32_t)g.comp_first[c]; t.grid_w[c] = g.grid_w[c]; t.grid_h[c] = g.grid_h[c];
       for (int v = 0; v < 8; v++) for (int h = 0; h < 8; h++) {
         const int nat = v * 8 + h, tr = h * 8 + v;           // (the kernel reads the tables beside the coefficients: the planes' transposed layout)
@@ -3554,15 +3586,26 @@ size_t Batch::PlanJpegPixels() {
     // (the grids hold the full-size extents — `fits` above —, so grid x n holds these; a plane of grid_w x n by grid_h x n bytes lies inside the frame's float plane)
     t.chroma_up = ncomp == 3 && t.hs && !t.vs ? 1u : 0u;      // 4:2:2: ext_w = ceil(out_w / 2), all of the picture's height
     t.chroma_fancy = m > 1 ? 1u : 0u;                         // (jdsample.c: no fancy upsampling when the smallest IDCT is 1 x 1)
+    if (dc) {
+      // (what JpegDcOutKernel relies on: one sample per block for every component, chroma as tall as the picture and never interpolated)
+      if (t.scale != 8 || t.n[0] != 1 || (ncomp == 3 && (t.n[1] != 1 || t.n[2] != 1 || t.vs || t.chroma_fancy)) || t.out_w > p.bw || t.out_h > p.bh) {
+        jpeg_pixel_results_[i].error = "unsupported: libjpeg-exact decode of a frame whose block grid does not hold the image";
+        continue;
+      }
+      dc_table.push_back(t); dc_image.push_back(i);
+      continue;
+    }
     scaled_table.push_back(t); scaled_image.push_back(i);
   }
-  const size_t plain = table.size();
+  const size_t plain = table.size(), general = plain + scaled_table.size();
   table.insert(table.end(), scaled_table.begin(), scaled_table.end());
+  table.insert(table.end(), dc_table.begin(), dc_table.end());
   jpeg_pixel_table_image_.insert(jpeg_pixel_table_image_.end(), scaled_image.begin(), scaled_image.end());
-  auto group_runs = [&](size_t from, size_t to, bool scaled) {
+  jpeg_pixel_table_image_.insert(jpeg_pixel_table_image_.end(), dc_image.begin(), dc_image.end());
+  auto group_runs = [&](size_t from, size_t to, uint32_t scaled) {
     for (size_t first = from; first < to; first += kJpegPixelGroupMax) {
       JpegPixelGroup g{(uint32_t)first, (uint32_t)std::min<size_t>(kJpegPixelGroupMax, to - first), 0, 0, 0};
-      g.scaled = scaled ? 1u : 0u;
+      g.scaled = scaled;
       for (uint32_t k = 0; k < g.count; k++) {
         const JpegPixelImage& t = table[first + k];
         g.max_npos = std::max(g.max_npos, t.npos);
@@ -3571,8 +3614,9 @@ size_t Batch::PlanJpegPixels() {
       jpeg_pixel_groups_.push_back(g);
     }
   };
-  group_runs(0, plain, false);
-  group_runs(plain, table.size(), true);
+  group_runs(0, plain, 0);
+  group_runs(plain, general, 1);
+  group_runs(general, table.size(), kJpegGroupDc);
   return table.size();
 }
 
@@ -3598,9 +3642,11 @@ void Batch::EnqueueJpegPixelTable(void* stream_v, bool fail_refused) {
 
 void Batch::EnqueueJpegIdct(void* stream_v) {
   const JpegPixelImage* dtable = (const JpegPixelImage*)djpeg_table_;
-  for (const JpegPixelGroup& g : jpeg_pixel_groups_) { LaunchJpegIdctGroup(dframes_, dtable, g, stream_v); jpeg_pixel_launches_++; }
+  // (a DC-only group has no coefficients to transform: a job of such groups only launches nothing here)
+  bool any = false;
+  for (const JpegPixelGroup& g : jpeg_pixel_groups_) if (g.scaled != kJpegGroupDc) { LaunchJpegIdctGroup(dframes_, dtable, g, stream_v); jpeg_pixel_launches_++; any = true; }
   // (a frame the kernel failed — kErrVarblock — has been consumed in part only: its planes are zeroed whole, as behind the HF stage)
-  if (!jpeg_pixel_groups_.empty()) LaunchZeroFailedCoefficients(dframes_, (int)images_.size(), stream_v);
+  if (any) LaunchZeroFailedCoefficients(dframes_, (int)images_.size(), stream_v);
 }
 void Batch::EnqueueJpegColorOut(void* stream_v) {
   const JpegPixelImage* dtable = (const JpegPixelImage*)djpeg_table_;
@@ -3614,13 +3660,14 @@ static std::string JpegPixelStatusMessage(uint32_t st, int frame) {
   return DeviceStatusMessage(st, frame, &unsupported);
 }
 void Batch::HarvestJpegPixels(const vec<uint32_t>& status) {
-  jpeg_pixel_images_ = 0;
+  jpeg_pixel_images_ = jpeg_dc_only_images_ = 0;
   for (size_t k = 0; k < jpeg_pixel_table_image_.size(); k++) {
     const int i = jpeg_pixel_table_image_[k];
     JpegPixelResult& r = jpeg_pixel_results_[i];
     const int u = pub_[i].first_unit;
     if (const uint32_t st = (size_t)u < status.size() ? status[(size_t)u] : 1u) { r.error = JpegPixelStatusMessage(st, u); continue; }
     r.ok = true; jpeg_pixel_images_++;
+    if (JpegDcOnlyUnit(u)) jpeg_dc_only_images_++;
   }
 }
 
@@ -3628,7 +3675,7 @@ void Batch::HarvestJpegPixels(const vec<uint32_t>& status) {
 void Batch::DecodeJpegPixels(void* stream_v) {
   const int n = (int)pub_.size();
   jpeg_pixel_results_.clear(); jpeg_pixel_results_.resize((size_t)n);
-  jpeg_pixel_images_ = jpeg_pixel_launches_ = 0;
+  jpeg_pixel_images_ = jpeg_pixel_launches_ = jpeg_dc_only_images_ = 0;
   jpeg_pixel_table_.clear(); jpeg_pixel_table_image_.clear(); jpeg_pixel_groups_.clear();
   if (!n) throw ParseError("DecodeJpegPixels: the batch holds no image", false);
   bool any = false;

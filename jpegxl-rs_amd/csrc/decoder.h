@@ -79,6 +79,7 @@ struct ImageEntry {
   size_t off_resize_src = 0, off_resize_tmp = 0;   // (first unit, resized output; pixel-plane arena) the f32 picture the write stage leaves for ResizeKernel, the horizontally filtered rows
                                                    // (OutputSpec::resize_u8: both in u8, for ResizeU8Kernel)
   uint32_t src_w = 0, src_h = 0;                   // (first unit) size of that picture: SetOutput
+  bool jpeg_dc_eligible = false;                   // (first unit) SetOutput: the output is libjpeg's 1/8 decode and every component takes the 1 x 1 IDCT (Batch::JpegDcOnly)
   explicit ImageEntry(std::shared_ptr<ImageShared> s) : shared(std::move(s)), cs(shared->cs), ih(shared->ih) {}
 };
 
@@ -126,7 +127,10 @@ class Batch {
   // Same, but an image that does not parse is left out instead of failing the call: (*index)[i] = its index in the batch or -1, (*errors)[i] = what it threw.
   // for_downscale: the images are going to be decoded at 1:8 — a stream may end behind its LF part (allow_partial as for AddImage), and an image that decode does not take is
   // left out with DownscaleRefusal's message
-  void AddImagesTolerant(const uint8_t* const* datas, const size_t* sizes, int n, int threads, vec<int>* index, std::vector<std::string>* errors, bool for_downscale = false);
+  // for_jpeg_dc: the images are going to be decoded at libjpeg's scale 1/8 (OutputSpec::jpeg_scale == 8) — a stream may end behind its LF part too, and one that does
+  // and is not DC-only at that scale (JpegDcOnly: 4:2:0 needs AC terms; what the libjpeg-exact decode does not take) is left out as "truncated"
+  void AddImagesTolerant(const uint8_t* const* datas, const size_t* sizes, int n, int threads, vec<int>* index, std::vector<std::string>* errors, bool for_downscale = false,
+                         bool for_jpeg_dc = false);
   // Forgets the images, keeps device arenas / staging buffer / buffer sharing: the object can be filled and prepared again.
   void Reset();
   size_t size() const { return pub_.size(); }
@@ -209,6 +213,14 @@ class Batch {
   struct JpegPixelResult { bool ok = false; std::string error; };
   bool CanDecodeJpegPixels(int i, std::string* why = nullptr) const;
   bool CanDecodeJpegPixelsAs(int i, const OutputSpec& out, std::string* why) const;      // the same for an output that is not set yet (SetOutput)
+  // The DC-only frame kind.  An image whose output is libjpeg's 1/8 decode (OutputSpec::jpeg_scale == 8; SetOutput has asked CanDecodeJpegPixelsAs) and whose sampling is
+  // grey, 4:4:4 or 4:2:2 takes the 1 x 1 "IDCT" for every component: each sample is one DC term, and the DC terms are FrameDev::lfq, written by the LF stage.  Its decode
+  // ends behind the LF stage like a 1:8 frame's (EndsBehindLf): no HF stage, no coefficient or pixel planes, a stream that ends behind its LF part will do;
+  // JpegDcOutKernel writes the picture.  4:2:0 takes the 2 x 2 IDCT for chroma, hence AC terms, and keeps the general path.  Known from the frame header and the
+  // output alone.  jpeg_dc_only = false keeps the general path for every image (the A/B of the tests; read by the next Prepare).
+  bool jpeg_dc_only = true;
+  void SetJpegDcOnly(bool on) { if (on != jpeg_dc_only) { jpeg_dc_only = on; prepared_ = false; } }      // (another layout of the arenas: the batch is prepared again)
+  bool JpegDcOnly(int i) const { return jpeg_dc_only && images_[pub_[i].first_unit]->jpeg_dc_eligible; }
   void DecodeJpegPixels(void* stream);
   // DecodeJpegPixels in its steps, for callers that order the stages themselves (Pipeline jobs of this kind):
   //   PlanJpegPixels            host only, after Prepare: eligibility, the component grids, the image table and its launch groups; an image that is refused gets its
@@ -220,7 +232,8 @@ class Batch {
   size_t PlanJpegPixels();
   void EnqueueJpegPixelTable(void* stream, bool fail_refused);
   void HarvestJpegPixels(const vec<uint32_t>& per_unit);
-  size_t jpeg_pixel_group_count() const { return jpeg_pixel_groups_.size(); }      // (after PlanJpegPixels: every group is one launch of each of the two pixel kernels)
+  // (after PlanJpegPixels) the launches of the pixel kernels its groups take: two per group, one per DC-only group
+  size_t jpeg_pixel_launch_count() const { size_t n = 0; for (const JpegPixelGroup& g : jpeg_pixel_groups_) n += g.scaled == kJpegGroupDc ? 1 : 2; return n; }
   const JpegPixelResult* jpeg_pixel_result(int i) const { return i >= 0 && (size_t)i < jpeg_pixel_results_.size() ? &jpeg_pixel_results_[(size_t)i] : nullptr; }
   void FinishStatus(void* stream, vec<uint32_t>* per_unit);
   // Copies frame i's pixels to host memory (after Finish).
@@ -290,6 +303,8 @@ class Batch {
   void PrepareLfFrameBatch(void* stream, bool wait_upload);
   void FinishCfg();
   bool DecodedAtEighth(int unit) const;      // the unit is decoded at 1:8 (OutputSpec::downscale == 8): its decode ends behind the LF post-processing
+  bool JpegDcOnlyUnit(int unit) const;       // the unit is the frame of a DC-only image (JpegDcOnly): its decode ends behind the LF decode
+  bool EndsBehindLf(int unit) const { return DecodedAtEighth(unit) || JpegDcOnlyUnit(unit); }   // either: no HF stage, no IDCT, no filters, no coefficient or pixel planes
   // ---- frame tail of complex images
   struct ComplexBufs {      // big-arena offsets of one complex unit ((size_t)-1: not allocated)
     size_t up[3], noise[3], rgb[3], canvas[3], pa[3], pb[3];
@@ -309,7 +324,8 @@ class Batch {
   vec<std::unique_ptr<JpegData>> jpeg_data_;   // per image, parsed lazily by CanReconstructJpeg
   std::vector<JpegResult> jpeg_results_;       // per image, of the last ReconstructJpegs
   std::vector<JpegPixelResult> jpeg_pixel_results_;   // per image, of the last DecodeJpegPixels
-  int64_t jpeg_pixel_images_ = 0, jpeg_pixel_launches_ = 0;   // images the last DecodeJpegPixels wrote; launches of its two pixel kernels (two per group of the image table)
+  int64_t jpeg_pixel_images_ = 0, jpeg_pixel_launches_ = 0;   // images the last DecodeJpegPixels wrote; launches of its pixel kernels (two per group of the image table, one per DC-only group)
+  int64_t jpeg_dc_only_images_ = 0;                            // ... images of it that were written from their DC terms alone (JpegDcOutKernel)
   vec<JpegPixelImage> jpeg_pixel_table_;       // PlanJpegPixels: the image table (host copy; the upload reads it), the image of every entry, the launch groups
   vec<int> jpeg_pixel_table_image_;
   std::vector<JpegPixelGroup> jpeg_pixel_groups_;
@@ -344,7 +360,8 @@ class Batch {
   HostStage hconst_;
   struct ParsedImage { vec<std::unique_ptr<ImageEntry>> units; bool complex = false; };
   static void ParseImage(const uint8_t* data, size_t size, ParsedImage* out, bool allow_partial = false);
-  int AddImagesImpl(const uint8_t* const* datas, const size_t* sizes, int n, int threads, bool tolerant, vec<int>* index, std::vector<std::string>* errors, bool allow_partial = false, bool only_downscalable = false);
+  int AddImagesImpl(const uint8_t* const* datas, const size_t* sizes, int n, int threads, bool tolerant, vec<int>* index, std::vector<std::string>* errors, bool allow_partial = false, bool only_downscalable = false,
+                    bool partial_only_jpeg_dc = false);
   int Append(ParsedImage&& im);
   bool DevReserve(void** ptr, size_t* cap, size_t bytes);
   size_t const_cap_ = 0, work_cap_ = 0, big_cap_ = 0, coef_cap_ = 0, coef_laid_out_ = 0, frames_cap_ = 0, passes_cap_ = 0, local_cap_ = 0;
@@ -388,7 +405,7 @@ class Batch {
   bool prepared_ = false;
   int max_lf_groups_ = 0, max_groups_ = 0, max_w_ = 0, max_h_ = 0, max_bw_ = 0, max_bh_ = 0;
   bool any_vardct_ = false;
-  bool any_scaled_ = false, any_full_vardct_ = false;   // some VarDCT frame is decoded at 1:8 / at full size (a batch of 1:8 frames only skips the HF stage, the IDCT and the filters)
+  bool any_scaled_ = false, any_full_vardct_ = false;   // some VarDCT frame is decoded at 1:8 / goes through the HF stage (a batch of 1:8 and DC-only frames skips the HF stage, the IDCT and the filters)
   FilterPlan fplan_;
   LaunchTrace trace_;             // the entropy-decode kernels the last LF / HF launch took (Info: hf_variant, lf_variant, lf_wide_bytes, lf_wide_only)
   LfSimtPlan lf_simt_;            // SIMT LF decode: device descriptors of the eligible frames' LF-group streams (cfg.lane_stride_lf < 64)

@@ -669,8 +669,9 @@ Codestream::~Codestream() {
   p.free.push_back(std::move(storage));
 }
 
-bool ExtractCodestream(const uint8_t* data, size_t size, Codestream* cs, bool* have_container, bool* has_jbrd, MetadataBoxes* boxes) {
+bool ExtractCodestream(const uint8_t* data, size_t size, Codestream* cs, bool* have_container, bool* has_jbrd, MetadataBoxes* boxes, vec<CodestreamRange>* ranges) {
   *have_container = false; *has_jbrd = false;
+  if (ranges) ranges->clear();
   vec<uint8_t> tmp;
   const uint8_t* src = data; size_t n = size;
   bool complete = true;
@@ -697,8 +698,11 @@ bool ExtractCodestream(const uint8_t* data, size_t size, Codestream* cs, bool* h
         else end = pos + (size_t)bs;
       }
       if (end < pos + hdr) { complete = false; break; }     // the box header itself is cut off: nothing of the payload is there
-      if (!memcmp(type, "jxlc", 4)) { tmp.insert(tmp.end(), data + pos + hdr, data + end); found = true; }
-      else if (!memcmp(type, "jxlp", 4)) { if (end >= pos + hdr + 4) { tmp.insert(tmp.end(), data + pos + hdr + 4, data + end); found = true; } }
+      const bool open_end = bs == 0 || bs > (uint64_t)(size - pos);      // the payload runs to the end of the file, or beyond what is there of it
+      if (!memcmp(type, "jxlc", 4)) { if (ranges) ranges->push_back({pos + hdr, tmp.size(), end - (pos + hdr), open_end}); tmp.insert(tmp.end(), data + pos + hdr, data + end); found = true; }
+      else if (!memcmp(type, "jxlp", 4)) {
+        if (end >= pos + hdr + 4) { if (ranges) ranges->push_back({pos + hdr + 4, tmp.size(), end - (pos + hdr + 4), open_end}); tmp.insert(tmp.end(), data + pos + hdr + 4, data + end); found = true; }
+      }
       else if (!memcmp(type, "jbrd", 4)) { *has_jbrd = true; if (boxes) boxes->jbrd.assign(data + pos + hdr, data + end); }
       else if (boxes) {
         // metadata a reconstructed JPEG gets its APP1 markers from (decode.cc box handling: the first box of a kind counts)
@@ -713,7 +717,7 @@ bool ExtractCodestream(const uint8_t* data, size_t size, Codestream* cs, bool* h
     (void)last_unbounded;
     if (!found) complete = false;
     src = tmp.data(); n = tmp.size();
-  }
+  } else if (ranges) ranges->push_back({0, 0, size, true});
   cs->size = n;
   const size_t words = (n + 3) / 4 + 20;       // 80 zero bytes after the stream: the HF kernel's bit-stream ring prefetches up to 64 bytes ahead
   cs->storage = TakeCodestreamStorage(words);
@@ -980,6 +984,7 @@ void ParseFrameStart(const Codestream& cs, const ImageHeader& ih, uint64_t frame
   for (size_t i = 0; i < n; i++) { phys[i] = {off, sizes[i]}; off += sizes[i]; }
   p->sections.resize(n);
   for (size_t i = 0; i < n; i++) p->sections[i] = perm.empty() ? phys[i] : phys[perm[i]];
+  if (off > cs.size && skip && allow_partial) { p->partial = true; p->frame_end_bitpos = off * 8; return; }     // (the TOC alone was asked for: where the sections lie, there or not yet)
   if (off > cs.size) {
     // the stream ends inside this frame.  A VarDCT frame whose LfGlobal, LfGroup and HfGlobal sections are all there can be shown without its AC groups (the kDC step of
     // progressive decoding, JxlDecoderFlushImage): only for the plain case — sections in file order, no Modular extra channels riding in the PassGroups, no LF frame

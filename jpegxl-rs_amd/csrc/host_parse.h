@@ -220,7 +220,10 @@ SigResult CheckSignature(const uint8_t* buf, size_t len);
 // container boxes JPEG reconstruction draws on: `jbrd`, the first `Exif` and the first `xml ` box; *_brob: the payload is still the Brotli
 // stream of a `brob` box (decompressed where it is used, jpeg_recon.cc)
 struct MetadataBoxes { vec<uint8_t> jbrd, exif, xml; bool have_exif = false, have_xml = false, exif_brob = false, xml_brob = false; };
-bool ExtractCodestream(const uint8_t* data, size_t size, Codestream* cs, bool* have_container, bool* has_jbrd, MetadataBoxes* boxes = nullptr);
+// ranges (optional): where the codestream's bytes lie in the file — one entry per jxlc / jxlp payload in file order (a bare codestream: one entry, the file);
+// open_end: the payload goes on behind the bytes that are there (a box that is cut off, or one that runs to the end of the file)
+struct CodestreamRange { size_t file_offset, cs_offset, size; bool open_end; };
+bool ExtractCodestream(const uint8_t* data, size_t size, Codestream* cs, bool* have_container, bool* has_jbrd, MetadataBoxes* boxes = nullptr, vec<CodestreamRange>* ranges = nullptr);
 
 // Parses the image header; *frame_bitpos receives the bit position of the first frame header.
 void ParseImageHeader(const Codestream& cs, ImageHeader* ih, uint64_t* frame_bitpos);

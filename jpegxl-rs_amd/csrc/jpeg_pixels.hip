@@ -7,6 +7,8 @@
 //                        reconstruction jobs of the pipeline, one launch per group of images
 //   JpegColorOutKernel   "fancy" chroma upsampling (jdsample.c h2v1 / h2v2 triangle filters; plain replication for planes at most two samples wide), fixed-point
 //                        YCbCr -> RGB (jdcolor.c), sample k enters the write stage as (float)k x (1 / 255)
+//   JpegDcOutKernel      libjpeg's 1/8 decode where every component takes the 1 x 1 IDCT (grey, 4:4:4, 4:2:2): the picture straight from the DC terms in FrameDev::lfq —
+//                        such a frame's decode ends behind the LF stage, it has no coefficient and no pixel planes
 //   JpegIdctScaledKernel / JpegColorOutScaledKernel   the same two stages for libjpeg's scaled decodes (scale 1/2, 1/4, 1/8: jdmaster.c, jidctred.c): reduced IDCTs
 //                        of 4 x 4, 2 x 2 or 1 x 1 samples per block (8 x 8 for 4:2:0 chroma at 1/2) -> planes of n x n samples per block -> the scaled picture
 // Every sum that a damaged stream can drive out of range is formed in uint32_t: it wraps, nothing is undefined; the samples of such a stream mean nothing, but every
@@ -322,6 +324,24 @@ __device__ __forceinline__ void ChromaPair(const uint8_t* __restrict__ s, uint32
   out[0] = (3 * cm + cl + 8) >> 4; out[1] = (3 * cm + cr + 7) >> 4;
 }
 
+// The end of all three colour-out kernels: the npix (1 or 2) pixels (x0, y), (x0 + 1, y) of a w x h picture from their u8 component samples — grey (ncomp == 1) as
+// they are, else fixed-point YCbCr -> RGB (jdcolor.c) — into the write stage; sample k enters it as (float)k x (1 / 255)
+__device__ __forceinline__ void StoreJpegPair(const OutputDesc& od, uint32_t ncomp, uint32_t w, uint32_t h, uint32_t x0, uint32_t y, uint32_t npix, const int32_t lum[2],
+                                              const int32_t cb[2], const int32_t cr[2]) {
+  const float k255 = 1.0f / 255;
+  if (ncomp == 1) {
+    for (uint32_t i = 0; i < npix; i++) { const float v = (float)lum[i] * k255; StorePixel(od, (int)w, (int)h, (int)(x0 + i), (int)y, v, v, v, 1.0f); }
+    return;
+  }
+  for (uint32_t i = 0; i < npix; i++) {
+    const int32_t u = cb[i] - 128, v = cr[i] - 128;
+    const int32_t r = min(max(lum[i] + ((91881 * v + 32768) >> 16), 0), 255);
+    const int32_t g = min(max(lum[i] + ((-22554 * u - 46802 * v + 32768) >> 16), 0), 255);
+    const int32_t b = min(max(lum[i] + ((116130 * u + 32768) >> 16), 0), 255);
+    StorePixel(od, (int)w, (int)h, (int)(x0 + i), (int)y, (float)r * k255, (float)g * k255, (float)b * k255, 1.0f);
+  }
+}
+
 // A thread takes the output pixels (2 t, 2 t + 1) of a row: they share their chroma position in the subsampled modes.
 __global__ __launch_bounds__(256) void JpegColorOutKernel(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table) {
   const JpegPixelImage& im = table[blockIdx.z];
@@ -329,15 +349,11 @@ __global__ __launch_bounds__(256) void JpegColorOutKernel(const FrameDev* __rest
   const uint32_t t = blockIdx.x * 32 + threadIdx.x, x0 = t * 2, y = blockIdx.y * 8 + threadIdx.y;
   if (x0 >= im.width || y >= im.height || *f.status != 0) return;
   const uint32_t npix = x0 + 1 < im.width ? 2 : 1;
-  const float k255 = 1.0f / 255;
   const uint8_t* __restrict__ yrow = im.plane[0] + (size_t)y * ((size_t)im.grid_w[0] * 8);
   const int32_t lum[2] = {yrow[x0], yrow[x0 + 1]};      // (x0 + 1 is inside the padded grid: its width is a multiple of 8)
+  int32_t cb[2] = {128, 128}, cr[2] = {128, 128};
   if (im.ncomp == 1) {
-    for (uint32_t i = 0; i < npix; i++) { const float v = (float)lum[i] * k255; StorePixel(f.od, (int)im.width, (int)im.height, (int)(x0 + i), (int)y, v, v, v, 1.0f); }
-    return;
-  }
-  int32_t cb[2], cr[2];
-  if (!im.hs) {
+  } else if (!im.hs) {
     const size_t o = (size_t)y * ((size_t)im.grid_w[1] * 8) + x0;
     cb[0] = im.plane[1][o]; cb[1] = im.plane[1][o + 1]; cr[0] = im.plane[2][o]; cr[1] = im.plane[2][o + 1];
   } else {
@@ -345,13 +361,7 @@ __global__ __launch_bounds__(256) void JpegColorOutKernel(const FrameDev* __rest
     ChromaPair(im.plane[1], pitch, im.vs, cw, ch, t, y, cb);
     ChromaPair(im.plane[2], pitch, im.vs, cw, ch, t, y, cr);
   }
-  for (uint32_t i = 0; i < npix; i++) {
-    const int32_t u = cb[i] - 128, v = cr[i] - 128;
-    const int32_t r = min(max(lum[i] + ((91881 * v + 32768) >> 16), 0), 255);
-    const int32_t g = min(max(lum[i] + ((-22554 * u - 46802 * v + 32768) >> 16), 0), 255);
-    const int32_t b = min(max(lum[i] + ((116130 * u + 32768) >> 16), 0), 255);
-    StorePixel(f.od, (int)im.width, (int)im.height, (int)(x0 + i), (int)y, (float)r * k255, (float)g * k255, (float)b * k255, 1.0f);
-  }
+  StoreJpegPair(f.od, im.ncomp, im.width, im.height, x0, y, npix, lum, cb, cr);
 }
 
 // JpegColorOutKernel for libjpeg's scaled decodes: the picture is im.out_w x im.out_h, component c's plane has im.pitch[c] bytes per row and im.ext_w[c] x im.ext_h[c]
@@ -364,15 +374,11 @@ __global__ __launch_bounds__(256) void JpegColorOutScaledKernel(const FrameDev* 
   const uint32_t t = blockIdx.x * 32 + threadIdx.x, x0 = t * 2, y = blockIdx.y * 8 + threadIdx.y;
   if (x0 >= im.out_w || y >= im.out_h || *f.status != 0) return;
   const uint32_t npix = x0 + 1 < im.out_w ? 2 : 1;
-  const float k255 = 1.0f / 255;
   const uint8_t* __restrict__ yrow = im.plane[0] + (size_t)y * im.pitch[0];
   const int32_t lum[2] = {yrow[x0], npix == 2 ? yrow[x0 + 1] : 0};      // (a row of n = 1 samples per block may end at x0)
+  int32_t cb[2] = {128, 128}, cr[2] = {128, 128};
   if (im.ncomp == 1) {
-    for (uint32_t i = 0; i < npix; i++) { const float v = (float)lum[i] * k255; StorePixel(f.od, (int)im.out_w, (int)im.out_h, (int)(x0 + i), (int)y, v, v, v, 1.0f); }
-    return;
-  }
-  int32_t cb[2], cr[2];
-  if (!im.chroma_up) {
+  } else if (!im.chroma_up) {
     const size_t o = (size_t)y * im.pitch[1] + x0, o1 = o + (npix == 2 ? 1 : 0);
     cb[0] = im.plane[1][o]; cb[1] = im.plane[1][o1]; cr[0] = im.plane[2][o]; cr[1] = im.plane[2][o1];
   } else {
@@ -381,19 +387,49 @@ __global__ __launch_bounds__(256) void JpegColorOutScaledKernel(const FrameDev* 
     ChromaPair(im.plane[1], im.pitch[1], 0, cw, im.ext_h[1], t, y, cb);
     ChromaPair(im.plane[2], im.pitch[1], 0, cw, im.ext_h[1], t, y, cr);
   }
-  for (uint32_t i = 0; i < npix; i++) {
-    const int32_t u = cb[i] - 128, v = cr[i] - 128;
-    const int32_t r = min(max(lum[i] + ((91881 * v + 32768) >> 16), 0), 255);
-    const int32_t g = min(max(lum[i] + ((-22554 * u - 46802 * v + 32768) >> 16), 0), 255);
-    const int32_t b = min(max(lum[i] + ((116130 * u + 32768) >> 16), 0), 255);
-    StorePixel(f.od, (int)im.out_w, (int)im.out_h, (int)(x0 + i), (int)y, (float)r * k255, (float)g * k255, (float)b * k255, 1.0f);
+  StoreJpegPair(f.od, im.ncomp, im.out_w, im.out_h, x0, y, npix, lum, cb, cr);
+}
+
+// libjpeg's 1/8 decode of an image whose components all take the 1 x 1 "IDCT" (grey, 4:4:4, 4:2:2 at scale 8 — JpegPixelImage::n[c] == 1 for every c; the entries of a
+// kJpegGroupDc run): the n = 1 case of JpegIdctScaledKernel + JpegColorOutScaledKernel with nothing in between.  A sample is clamp(DESCALE(dc x qt[c][0], 3) + 128) of
+// one DC term, and the DC terms are FrameDev::lfq, which the LF stage wrote: the frame has no coefficient planes and no pixel planes (FrameDev::lf_only ==
+// kLfOnlyJpegDc), the HF stage never ran for it.  A thread takes the output pixels (2 t, 2 t + 1) of a row, as above.
+//   Luma sample (x, y) is the DC term of component block (x, y): lfq[Y] at y x f.bw + x (the LF planes have the frame grid's pitch, whatever the component's grid is).
+//   Chroma (x >> hs, y): 4:2:2 replicates — jdsample.c has no fancy upsampling when the smallest IDCT is 1 x 1 (chroma_fancy == 0), and vs == 0 for every entry here.
+//   Loads: two dwords per component and thread, lanes on consecutive pairs — a row of a wavefront is one contiguous run of 64 dwords, read by two instructions of 8-byte
+//   lane stride, both out of the same lines.  No 8-byte load: y x f.bw + x0 is odd for odd f.bw and y.  At 4:2:2 both pixels take the one chroma dword t.
+//   Addresses: x < out_w <= grid_w[0] <= f.bw and y < out_h <= grid_h[0] <= f.bh, x >> hs < grid_w[1], all from the host's table (PlanJpegPixels checks the grids against
+//   the frame's); the stream decides values only.  The product is formed in uint32_t like every sum here.
+//   A block that is not DCT8 fails the frame with kErrVarblock as in JpegIdctBody (block info is the LF stage's): the lane of a block's luma sample looks at it; the
+//   frame block of a 4:2:2 chroma block, (2 t, y), is one of those.  Pixels other lanes stored before the word was set mean nothing: the image has failed.
+__global__ __launch_bounds__(256) void JpegDcOutKernel(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table) {
+  const JpegPixelImage& im = table[blockIdx.z];
+  const FrameDev& f = frames[im.frame];
+  const uint32_t t = blockIdx.x * 32 + threadIdx.x, x0 = t * 2, y = blockIdx.y * 8 + threadIdx.y;
+  if (x0 >= im.out_w || y >= im.out_h || x0 >= f.bw || y >= f.bh || *f.status != 0) return;
+  const uint32_t npix = x0 + 1 < im.out_w && x0 + 1 < f.bw ? 2 : 1;
+  const size_t row = (size_t)y * f.bw;
+  auto sample = [&](uint32_t c, uint32_t ch, uint32_t x) -> int32_t {
+    return (int32_t)ClampU8(Descale<3>((uint32_t)(int32_t)(int16_t)f.lfq[ch][row + x] * (uint32_t)im.qt[c][0]) + 128);      // (int16_t: the width JPEG gives a coefficient, as in JpegIdctBody)
+  };
+  uint32_t other = 0;
+  for (uint32_t i = 0; i < npix; i++) other |= f.blk_info[row + x0 + i] & 31u;
+  const int32_t lum[2] = {sample(0, 1, x0), npix == 2 ? sample(0, 1, x0 + 1) : 0};      // (Y lives in channel 1, Cb in the X slot 0, Cr in the B slot 2)
+  int32_t cb[2] = {128, 128}, cr[2] = {128, 128};
+  if (im.ncomp == 3) {
+    const uint32_t hs = im.hs ? 1u : 0u;
+    const uint32_t c0 = x0 >> hs, c1 = npix == 2 ? (x0 + 1) >> hs : c0;      // (4:2:2: c0 == c1 == t, whose frame block (2 t, y) is the luma block looked at above)
+    cb[0] = sample(1, 0, c0); cr[0] = sample(2, 2, c0);
+    if (c1 != c0) { cb[1] = sample(1, 0, c1); cr[1] = sample(2, 2, c1); } else { cb[1] = cb[0]; cr[1] = cr[0]; }
   }
+  if (other) { atomicOr(f.status, (uint32_t)kErrVarblock); return; }
+  StoreJpegPair(f.od, im.ncomp, im.out_w, im.out_h, x0, y, npix, lum, cb, cr);
 }
 
 }  // namespace
 
 void LaunchJpegIdctGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream) {
-  if (!g.count || g.count > kJpegPixelGroupMax || !g.max_npos || !g.max_w || !g.max_h) return;
+  if (!g.count || g.count > kJpegPixelGroupMax || !g.max_npos || !g.max_w || !g.max_h || g.scaled == kJpegGroupDc) return;     // (a DC-only run has no coefficients)
   const uint32_t per_wg = kIdctWaves * kIdctBlocksPerWave;
   if (g.scaled) hipLaunchKernelGGL(JpegIdctScaledKernel, dim3((g.max_npos + per_wg - 1) / per_wg, 1, g.count), dim3(256), 0, (hipStream_t)stream, frames, table + g.first);
   else hipLaunchKernelGGL(JpegIdctPlanesKernel, dim3((g.max_npos + per_wg - 1) / per_wg, 1, g.count), dim3(256), 0, (hipStream_t)stream, frames, table + g.first);
@@ -405,7 +441,8 @@ void LaunchJpegGatherGroup(const FrameDev* frames, const JpegPixelImage* table, 
 }
 void LaunchJpegColorOutGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream) {
   if (!g.count || g.count > kJpegPixelGroupMax || !g.max_npos || !g.max_w || !g.max_h) return;
-  if (g.scaled) hipLaunchKernelGGL(JpegColorOutScaledKernel, dim3((g.max_w + 63) / 64, (g.max_h + 7) / 8, g.count), dim3(32, 8), 0, (hipStream_t)stream, frames, table + g.first);
+  if (g.scaled == kJpegGroupDc) hipLaunchKernelGGL(JpegDcOutKernel, dim3((g.max_w + 63) / 64, (g.max_h + 7) / 8, g.count), dim3(32, 8), 0, (hipStream_t)stream, frames, table + g.first);
+  else if (g.scaled) hipLaunchKernelGGL(JpegColorOutScaledKernel, dim3((g.max_w + 63) / 64, (g.max_h + 7) / 8, g.count), dim3(32, 8), 0, (hipStream_t)stream, frames, table + g.first);
   else hipLaunchKernelGGL(JpegColorOutKernel, dim3((g.max_w + 63) / 64, (g.max_h + 7) / 8, g.count), dim3(32, 8), 0, (hipStream_t)stream, frames, table + g.first);
 }
 

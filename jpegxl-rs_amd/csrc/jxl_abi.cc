@@ -1077,6 +1077,7 @@ void JxlHipBatchSetOption(JxlHipBatch* h, const char* name, int value) {
   else if (n == "jpeg_host_writer") h->b->jpeg_host_writer = value != 0;   // JxlHipBatchReconstructJpegs: every image through the host's Huffman writer
   else if (n == "jpeg_device_progressive") h->b->jpeg_device_progressive = value != 0;   // ... progressive files written by the device as well (jpeg_host_writer wins)
   else if (n == "resize_group_max" && value >= 1 && (uint32_t)value <= kResizeGroupMax) h->b->resize_group_max = (uint32_t)value;   // testing: images per resize launch (applies to the next Prepare)
+  else if (n == "jpeg_dc_only") h->b->SetJpegDcOnly(value != 0);   // libjpeg's 1/8 decode from the DC terms alone where every component takes the 1 x 1 IDCT (default), or the general path for every image
   else if (n == "hf_lanes_per_wave" && value >= 0 && value <= 64) h->b->cfg.hf_lanes_per_wave = value;   // SIMT HF stage: group streams per wavefront (1: the wave-wide kernel where it applies); 0: the throughput packing
 }
 size_t JxlHipBatchDebugRead(JxlHipBatch* h, int index, const char* name, int channel, void* dst, size_t cap, void* s) {
@@ -1125,6 +1126,10 @@ int JxlHipBatchCanDecodeJpegPixels(JxlHipBatch* h, int i) {
   } catch (const std::exception& e) { SetLastError(e.what()); return 0; }
 }
 JxlDecoderStatus JxlHipBatchDecodeJpegPixels(JxlHipBatch* h, void* s) { BATCH_TRY(h->b->DecodeJpegPixels(s)) }
+int JxlHipBatchJpegDcOnly(const JxlHipBatch* h, int i) {
+  if (!h || i < 0 || (size_t)i >= h->b->size()) { SetLastError("JxlHipBatchJpegDcOnly: no such image"); return 0; }
+  return h->b->JpegDcOnly(i) ? 1 : 0;
+}
 JxlDecoderStatus JxlHipBatchJpegPixelsStatus(const JxlHipBatch* h, int i) {
   const Batch::JpegPixelResult* r = h->b->jpeg_pixel_result(i);
   if (!r) { SetLastError("JxlHipBatchJpegPixelsStatus: no such image, or JxlHipBatchDecodeJpegPixels has not run"); return JXL_DEC_ERROR; }
@@ -1373,6 +1378,48 @@ JxlDecoderStatus JxlHipImageOutSizeJpegScaled(const uint8_t* data, size_t size, 
     if (info) FillBasicInfo(sh->ih, info, false);
     if (out_size) *out_size = Batch::OutputSize(sh->ih, o);
     return JXL_DEC_SUCCESS;
+  } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
+}
+// The LF part of the first frame in FILE bytes: the codestream offset behind LfGlobal, the LfGroups and HfGlobal (JxlHipDebugDescribe's lf_part_end, from the TOC)
+// mapped through the jxlc / jxlp payload ranges ExtractCodestream walks.
+JxlDecoderStatus JxlHipLfPartSize(const uint8_t* data, size_t size, size_t* bytes) {
+  try {
+    if (!data || !bytes) { SetLastError("JxlHipLfPartSize: no data / no result pointer"); return JXL_DEC_ERROR; }
+    std::shared_ptr<ImageShared> sh(new ImageShared());
+    bool have_container = false, has_jbrd = false;
+    vec<CodestreamRange> ranges;
+    ExtractCodestream(data, size, &sh->cs, &have_container, &has_jbrd, nullptr, &ranges);      // (a prefix is what this call is for)
+    uint64_t bitpos = 0;
+    ParseImageHeader(sh->cs, &sh->ih, &bitpos);
+    if (sh->ih.have_preview) {      // the preview frame is stepped over, as Batch::ParseImage does
+      ImageHeader ph = sh->ih;
+      ph.xsize = sh->ih.preview_x; ph.ysize = sh->ih.preview_y;
+      FramePlan pp;
+      ParseFrameStart(sh->cs, ph, bitpos, &pp, /*header_and_toc_only=*/true);
+      bitpos = pp.frame_end_bitpos;
+    }
+    FramePlan p;
+    ParseFrameStart(sh->cs, sh->ih, bitpos, &p, /*header_and_toc_only=*/true, /*allow_partial=*/true);
+    *bytes = 0;
+    if (p.modular || p.single_section) return JXL_DEC_SUCCESS;
+    const size_t lf_sections = 2 + (size_t)p.num_lf_groups;
+    if (p.sections.size() <= lf_sections) return JXL_DEC_SUCCESS;
+    uint64_t end = 0;
+    for (size_t k = 0; k < lf_sections; k++) {
+      if (k && p.sections[k].offset < p.sections[k - 1].offset) return JXL_DEC_SUCCESS;      // (a permuted TOC: no prefix of such a frame is accepted)
+      end = std::max<uint64_t>(end, p.sections[k].offset + p.sections[k].size);
+    }
+    if (p.sections[lf_sections].offset < p.sections[lf_sections - 1].offset || end == 0) return JXL_DEC_SUCCESS;
+    // codestream byte end - 1 lies in one of the payload ranges — or behind the last one where that goes on behind the bytes given
+    for (const CodestreamRange& r : ranges) {
+      const bool last = &r == &ranges.back();
+      if (end - 1 < (uint64_t)r.cs_offset + r.size || (last && r.open_end)) {
+        if (end - 1 < r.cs_offset) break;
+        *bytes = (size_t)(r.file_offset + (end - r.cs_offset));
+        return JXL_DEC_SUCCESS;
+      }
+    }
+    throw ParseError("truncated", false);
   } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
 }
 JxlDecoderStatus JxlHipImageOutSize(const uint8_t* data, size_t size, const JxlPixelFormat* format, JxlBasicInfo* info, size_t* out_size) {

@@ -139,9 +139,12 @@ struct FrameDev {
                                   // write stage are done by the host-planned frame tail (kernels_features.hip) — multi-frame images, image features
   float inverse_gamma;            // colour mode 4 (XYB -> gamma transfer)
   float hdr_par[5];               // colour mode 6 (PQ): [0] intensity_target / 10000; 7 (HLG): [0] OOTF exponent, [1] apply it, [2..4] luminances
-  uint32_t lf_only;               // 1:8 decode (OutputSpec::downscale == 8): the output is the LF image, one pixel per 8x8 block, written by LfOutputKernel — img_w / img_h / out_stride
-                                  // describe that bw x bh picture; the HF stage, the IDCT, the filters and OutputKernel leave the frame alone, it has no coefficient or pixel planes
+  uint32_t lf_only;               // != 0: the decode of this frame ends behind the LF stage — the HF stage, the IDCT, the filters and OutputKernel leave the frame alone, it has no
+                                  // coefficient or pixel planes.  kLfOnlyEighth: the 1:8 decode (OutputSpec::downscale == 8), the output is the LF image, one pixel per 8x8 block,
+                                  // written by LfOutputKernel — img_w / img_h / out_stride describe that bw x bh picture.  kLfOnlyJpegDc: libjpeg's 1/8 decode of a JPEG transcode
+                                  // whose components all take the 1 x 1 IDCT (OutputSpec::jpeg_scale == 8, not 4:2:0): JpegDcOutKernel writes it from lfq, the DC terms
 };
+constexpr uint32_t kLfOnlyEighth = 1, kLfOnlyJpegDc = 2;
 
 struct LaunchCfg {
   int lane_stride_lf = 64;   // lanes between active decode threads (64 = one stream per wave, 1 = one per lane)
@@ -387,11 +390,13 @@ struct alignas(16) JpegPixelImage {
   alignas(16) int32_t cfl_ratio[2][64];
 };
 constexpr uint32_t kJpegPixelGroupMax = 32768;       // images per launch (gridDim.z is limited to 65535)
-// a run of the table served by one launch per kernel, the grids sized for its largest image (max_w x max_h: of the pictures that are written); scaled: a run of
-// entries with scale 2, 4, 8, which take the two ...Scaled kernels — entries of scale 1 and scaled ones never share a run
+// a run of the table served by one launch per kernel, the grids sized for its largest image (max_w x max_h: of the pictures that are written); scaled: 1 = a run of
+// entries with scale 2, 4, 8, which take the two ...Scaled kernels; kJpegGroupDc = a run of DC-only entries (scale 8, every component at the 1 x 1 IDCT; their frames
+// have FrameDev::lf_only == kLfOnlyJpegDc and neither coefficient nor pixel planes), which take no IDCT launch at all and JpegDcOutKernel — the kinds never share a run
+constexpr uint32_t kJpegGroupDc = 2;
 struct JpegPixelGroup { uint32_t first, count, max_npos, max_w, max_h, scaled = 0; };
-void LaunchJpegIdctGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);       // JpegIdctPlanesKernel / JpegIdctScaledKernel
-void LaunchJpegColorOutGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);   // JpegColorOutKernel / JpegColorOutScaledKernel, behind it on the same stream
+void LaunchJpegIdctGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);       // JpegIdctPlanesKernel / JpegIdctScaledKernel; nothing for a DC-only run
+void LaunchJpegColorOutGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);   // JpegColorOutKernel / JpegColorOutScaledKernel, behind it on the same stream; JpegDcOutKernel
 void LaunchJpegGatherGroup(const FrameDev* frames, const JpegPixelImage* table, const JpegPixelGroup& g, void* stream);     // JpegGatherKernel (max_w / max_h unused)
 void LaunchCopyPlane(const float* src, uint32_t src_stride, float* dst, uint32_t dst_stride, uint32_t w, uint32_t h, void* stream);
 // ---- resized output (OutputSpec::resize_w / resize_h): separable antialiased filter (triangle or cubic convolution), horizontal pass then vertical, f32 throughout.

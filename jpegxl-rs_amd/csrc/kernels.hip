@@ -4998,7 +4998,7 @@ __global__ void OutputKernel(const FrameDev* __restrict__ frames, int unfused, i
 // set img_w x img_h / out_stride to the ceil(width / 8) x ceil(height / 8) picture, so StorePixel applies the orientation to it as it does to the full one.
 __global__ void LfOutputKernel(const FrameDev* __restrict__ frames) {
   const FrameDev& f = frames[blockIdx.z];
-  if (f.is_modular || !f.lf_only || FrameFailed(f)) return;
+  if (f.is_modular || f.lf_only != kLfOnlyEighth || FrameFailed(f)) return;      // (kLfOnlyJpegDc: JpegDcOutKernel writes that frame)
   const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
   if (x >= f.img_w || y >= f.img_h || x >= f.bw || y >= f.bh) return;
   float X, Y, B;

@@ -274,7 +274,10 @@ void Pipeline::PrepareJob(Job* j, int worker) {
     bt.Reset();
     vec<int> index;
     std::vector<std::string> errors;
-    bt.AddImagesTolerant(j->datas.data(), j->sizes.data(), n, opt_.parse_threads, &index, &errors, /*for_downscale=*/j->spec.downscale == 8);   // (a 1:8 job needs the LF part of a stream only; what that decode does not take fails alone, here)
+    // (a 1:8 job needs the LF part of a stream only; what that decode does not take fails alone, here.  So does a libjpeg-exact job at scale 1/8 for its DC-only images,
+    // Batch::JpegDcOnly: a stream that ends behind its LF part and is not one of those fails alone, "truncated")
+    bt.AddImagesTolerant(j->datas.data(), j->sizes.data(), n, opt_.parse_threads, &index, &errors, /*for_downscale=*/j->spec.downscale == 8,
+                         /*for_jpeg_dc=*/j->kind == kJpegPixels && j->spec.jpeg_scale == 8);
     t_parse = std::chrono::steady_clock::now();
     j->batch_index.assign(index.begin(), index.end());
     bool any = false;
@@ -371,7 +374,7 @@ void Pipeline::PrepareJob(Job* j, int worker) {
     {
       std::lock_guard<std::mutex> lock(mu_);
       last_info_["jpeg_pixel_images"] = (int64_t)jpeg_table;
-      last_info_["jpeg_pixel_launches"] = j->kind == kJpegPixels ? 2 * (int64_t)bt.jpeg_pixel_group_count() : 0;
+      last_info_["jpeg_pixel_launches"] = j->kind == kJpegPixels ? (int64_t)bt.jpeg_pixel_launch_count() : 0;
       want_big_ = std::max(want_big_, bt.big_bytes_wanted()); want_coef_ = std::max(want_coef_, bt.coef_bytes_wanted());
       if (!bt.uses_shared_big() || !bt.uses_shared_coef()) private_plane_jobs_++;
       bt.StageBytes(last_stage_bytes_);
@@ -590,7 +593,8 @@ void Pipeline::Harvest(Job* j) {
     std::lock_guard<std::mutex> lock(mu_);
     if (readback_ok) last_info_["hf_nonzeros"] = bt.Info("hf_nonzeros");
     if (readback_ok) last_info_["resize_u8_images"] = bt.Info("resize_u8_images");     // (of the job harvested last: its images resampled in Pillow's 8-bit arithmetic)
-    if (readback_ok) { last_info_["jpeg_pixel_images"] = j->kind == kJpegPixels ? bt.Info("jpeg_pixel_images") : 0; last_info_["jpeg_pixel_launches"] = j->kind == kJpegPixels ? bt.Info("jpeg_pixel_launches") : 0; }
+    if (readback_ok) { last_info_["jpeg_pixel_images"] = j->kind == kJpegPixels ? bt.Info("jpeg_pixel_images") : 0; last_info_["jpeg_pixel_launches"] = j->kind == kJpegPixels ? bt.Info("jpeg_pixel_launches") : 0;
+                       last_info_["jpeg_dc_only_images"] = j->kind == kJpegPixels ? bt.Info("jpeg_dc_only_images") : 0; }
     if (readback_ok) {
       last_info_["jpeg_device_images"] = j->jpeg_counts[0]; last_info_["jpeg_host_images"] = j->jpeg_counts[1];
       last_info_["jpeg_device_progressive_images"] = j->jpeg_counts[2]; last_info_["jpeg_gather_launches"] = j->jpeg_counts[3];

@@ -86,7 +86,7 @@ class Pipeline {
   void ResetClock();                               // end_ms of later jobs counts from here (call on an idle pipeline)
   StageTimes CollectTimes(int* runs);              // per-stage HIP-event sums over all jobs since the last call (options.timed)
   void StageBytes(uint64_t out[6]);                // algorithmic bytes per stage of the job prepared last
-  int64_t Info(const char* name);                  // "device_bytes", "jobs", "shared_big_bytes", "shared_coef_bytes", "private_plane_jobs", "jpeg_pixel_images", "jpeg_pixel_launches" (of the job prepared or finished last), "jpeg_device_images", "jpeg_host_images", "jpeg_device_progressive_images", "jpeg_gather_launches" (of the job finished last; 0 unless it was a reconstruction job), batch infos of the last job ("hf_nonzeros", "lf_simt_frames" ...)
+  int64_t Info(const char* name);                  // "device_bytes", "jobs", "shared_big_bytes", "shared_coef_bytes", "private_plane_jobs", "jpeg_pixel_images", "jpeg_pixel_launches" (of the job prepared or finished last), "jpeg_dc_only_images" (of the job finished last), "jpeg_device_images", "jpeg_host_images", "jpeg_device_progressive_images", "jpeg_gather_launches" (of the job finished last; 0 unless it was a reconstruction job), batch infos of the last job ("hf_nonzeros", "lf_simt_frames" ...)
   double prepare_seconds_total() const { return prepare_s_total_; }
   int64_t prepared_jobs() const { return prepared_jobs_; }
   int device() const { return device_; }

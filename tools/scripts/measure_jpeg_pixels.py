@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Milliseconds per batch and Mpixel/s of the ways from a batch of JPEG transcodes to the pixels of the original JPEG files.
 
-Input: --files baseline 4:2:0 JPEGs of --width x --height, written at run time by Pillow from tests/jpeg_cases.photo (--distinct different pictures, cycled) and
+Input: --files baseline JPEGs (--sampling 444 | 422 | 420 | grey, default 420) of --width x --height, written at run time by Pillow from tests/jpeg_cases.photo (--distinct different pictures, cycled) and
 turned into JPEG XL by tests/jpeg_tools.transcode.  Output of the two device legs: u8 RGB in device memory (one caller-owned buffer per image).  Legs (--legs):
 
   pixels       BatchDecoder.decode_jpeg_pixels() of a prepared batch: the entropy stages, then the integer pixel path (csrc/jpeg_pixels.hip); the call waits for the result
@@ -17,6 +17,9 @@ turned into JPEG XL by tests/jpeg_tools.transcode.  Output of the two device leg
                idct_ms + out_ms of the brackets: integer IDCT, colour-out and the resizes
                --resize_u8 (with --resize): the resample in Pillow's 8-bit arithmetic over a u8 intermediate (Pipeline.submit(resize_u8=True)); the first image of the first
                job is compared with PIL's resize of the source file (after draft() for --jpeg_scale), byte for byte
+               --prefix (with --jpeg_scale 8 and a sampling that is decoded from the DC terms alone: 444, 422, grey): every file is submitted cut at lf_part_size(),
+               the bytes that hold the LF part of its frame; "submitted_bytes" / "file_bytes" say what a loader read and what the files hold.  "dc_only_images": images
+               of the last job written by JpegDcOutKernel (a build without that path reports None)
   pipeline_float  the same jobs without jpeg_pixels: libjxl's rendering through the float tail — what a loader of these files gets from a Pipeline otherwise
 
 Every leg runs --reps times after --warmup; the median is reported.  The first run of a leg is checked: pixels and reconstruct equal Pillow's decode of the source
@@ -57,12 +60,15 @@ def main():
     ap.add_argument("--resize", default=None, help="pipeline legs: W,H of every output")
     ap.add_argument("--jpeg_scale", type=int, default=1, help="pipeline leg: libjpeg's scaled decode (2, 4, 8)")
     ap.add_argument("--resize_u8", action="store_true", help="pipeline leg: the integer resample (needs --resize)")
+    ap.add_argument("--sampling", default="420", choices=("444", "422", "420", "grey"), help="chroma sampling of the source files")
+    ap.add_argument("--prefix", action="store_true", help="pipeline leg at --jpeg_scale 8: submit each file cut at lf_part_size()")
     args = ap.parse_args()
     import numpy as np
     from PIL import Image
     import jpeg_cases as JC
     import jpeg_tools as J
-    cached = args.cache and os.path.join(args.cache, "jpeg_pixels_%dx%d_q%d_n%d.pickle" % (args.width, args.height, args.quality, args.distinct))
+    tag = "" if args.sampling == "420" else "_" + args.sampling
+    cached = args.cache and os.path.join(args.cache, "jpeg_pixels_%dx%d_q%d_n%d%s.pickle" % (args.width, args.height, args.quality, args.distinct, tag))
     if cached and os.path.exists(cached):
         with open(cached, "rb") as f:
             jpegs, jxls = pickle.load(f)
@@ -70,7 +76,11 @@ def main():
         jpegs = []
         for k in range(args.distinct):
             buf = io.BytesIO()
-            Image.fromarray(JC.photo(args.width, args.height, seed=100 + k)).save(buf, "JPEG", quality=args.quality, subsampling=2)
+            img = JC.photo(args.width, args.height, seed=100 + k)
+            if args.sampling == "grey":
+                Image.fromarray(np.ascontiguousarray(img[:, :, 0])).save(buf, "JPEG", quality=args.quality)
+            else:
+                Image.fromarray(img).save(buf, "JPEG", quality=args.quality, subsampling={"444": 0, "422": 1, "420": 2}[args.sampling])
             jpegs.append(buf.getvalue())
         jxls = [J.transcode(d) for d in jpegs]
         if cached:
@@ -86,8 +96,8 @@ def main():
     inputs = [jxls[k % args.distinct] for k in range(args.files)]
     w, h = args.width, args.height
     mpix = args.files * w * h / 1e6
-    want = [np.asarray(Image.open(io.BytesIO(d))) for d in jpegs]
-    out = {"what": "pixels of JPEG transcodes, u8 RGB", "files": args.files, "distinct": args.distinct, "size": [w, h], "quality": args.quality, "megapixels": round(mpix, 1),
+    want = [np.asarray(Image.open(io.BytesIO(d)).convert("RGB")) for d in jpegs]
+    out = {"what": "pixels of JPEG transcodes, u8 RGB", "files": args.files, "distinct": args.distinct, "size": [w, h], "quality": args.quality, "megapixels": round(mpix, 1), "sampling": args.sampling,
            "jpeg_bytes": sum(len(f) for f in files), "package": os.path.dirname(os.path.abspath(jx.__file__))}
 
     def report(times):
@@ -155,13 +165,20 @@ def main():
                 continue
             if u8:
                 kw["resize_u8"] = True
+            submitted = inputs
+            if exact and args.prefix:
+                if args.jpeg_scale != 8 or not hasattr(jx, "lf_part_size"):
+                    out[leg] = "--prefix needs --jpeg_scale 8 and a build with lf_part_size()"
+                    p.close()
+                    continue
+                submitted = [d[:jx.lf_part_size(d)] for d in inputs]
             stages = None
             for r in range(args.warmup + args.reps):
                 if r == args.warmup:
                     p.collect_times()                      # (the brackets of the warm-up jobs are dropped)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                tickets = [p.submit(inputs, "uint8", 3, device_ptrs=[t.data_ptr() for t in bufs[k % len(bufs)]], **kw) for k in range(args.jobs)]
+                tickets = [p.submit(submitted, "uint8", 3, device_ptrs=[t.data_ptr() for t in bufs[k % len(bufs)]], **kw) for k in range(args.jobs)]
                 for t in tickets:
                     st, _ = p.wait(t)
                     assert st == [0] * len(inputs), st
@@ -171,7 +188,7 @@ def main():
                     im = Image.open(io.BytesIO(files[0]))
                     if scaled:
                         im.draft(im.mode, (w // args.jpeg_scale, h // args.jpeg_scale))
-                    ref = np.asarray(im.resize(resize, Image.BILINEAR))
+                    ref = np.asarray(im.resize(resize, Image.BILINEAR).convert("RGB"))
                     diff = int(np.abs(bufs[0][0].cpu().numpy().reshape(ref.shape).astype(int) - ref).max())
                     assert diff == 0, "the integer resample differs from PIL's resize of the source file"
                 elif r == 0 and (resize or scaled):
@@ -187,6 +204,9 @@ def main():
             out[leg].update(output_size=[ow, oh], device_bytes=p.info("device_bytes"), pixel_half_ms_per_job=round(stages.get("idct_ms", 0) + stages.get("out_ms", 0), 3))
             if exact:
                 out[leg].update(pixel_launches=p.info("jpeg_pixel_launches"), jpeg_scale=args.jpeg_scale, resize_u8=bool(u8))
+                dc = p.info("jpeg_dc_only_images")
+                out[leg].update(dc_only_images=dc if dc >= 0 else None, hf_nonzeros=p.info("hf_nonzeros"), prefix=bool(args.prefix), submitted_bytes=sum(len(d) for d in submitted),
+                                file_bytes=sum(len(d) for d in inputs))
             p.close()
             del p, bufs
         elif leg == "reconstruct":

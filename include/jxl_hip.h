@@ -460,7 +460,9 @@ uint64_t JxlHipBatchCompressedBytes(const JxlHipBatch* batch);
 void JxlHipBatchStageBytes(const JxlHipBatch* batch, uint64_t out[6]);
 uint64_t JxlHipBatchDeviceBytes(const JxlHipBatch* batch);
 /* Facts about a prepared batch, by name (-1: unknown name): "lf_simt_frames" / "lf_legacy_frames" = VarDCT frames whose LF-group streams
- * take the SIMT kernel (one stream per lane, lane stride < 64) / the one-wavefront-per-stream kernel, "lf_simt_lanes", "lf_simt_waves", "lf_simt_wp" (1: the SIMT launch is the instantiation with weighted-predictor state), "hf_nonzeros" = non-zero AC coefficients of one decode of the batch (after a Finish). */
+ * take the SIMT kernel (one stream per lane, lane stride < 64) / the one-wavefront-per-stream kernel, "lf_simt_lanes", "lf_simt_waves", "lf_simt_wp" (1: the SIMT launch is the instantiation with weighted-predictor state), "lf_simt_streams" (more than "lf_simt_lanes": some lane decodes several streams),
+ * "lf_spec_lanes" (after a decode: lanes per stream of the SIMT launch without the weighted predictor, batch option "lf_spec_lanes"; 0: no such launch), "lf_spec_hits" / "lf_spec_misses" (with
+ * JXL_HIP_LF_SPEC_STATS set: samples of this device's launches so far whose cluster was / was not one of the lanes' candidates; -1 otherwise), "hf_nonzeros" = non-zero AC coefficients of one decode of the batch (after a Finish). */
 int64_t JxlHipBatchGetInfo(const JxlHipBatch* batch, const char* name);
 /* Testing: after a decode, copies a device buffer of image `index`'s first (VarDCT) frame to the host — "plane_a" / "plane_b" (the padded
  * float XYB planes the stages ping-pong between, 8 bw x 8 bh samples per channel), "lf" / "llf" / "lfq", "inv_sigma", "blk_info", "coef_off" (one

@@ -1086,6 +1086,10 @@ int64_t Batch::Info(const std::string& name) const {
   if (name == "jpeg_pixel_launches") return jpeg_pixel_launches_;   // ... launches of its pixel kernels (two per group of the image table, one per DC-only group, however many images a group holds)
   if (name == "jpeg_dc_only_images") return jpeg_dc_only_images_;   // ... images of it written from their DC terms alone (JpegDcOutKernel; Batch::JpegDcOnly)
   if (name == "lf_simt_lanes") return lf_simt_.num_lanes;
+  if (name == "lf_simt_streams") return lf_simt_.num_streams;      // (more streams than lanes: some lane decodes several, one after the other)
+  if (name == "lf_spec_lanes") return trace_.lf_spec_lanes;
+  if (name == "lf_spec_hits") return LfSpecStats(0);
+  if (name == "lf_spec_misses") return LfSpecStats(1);
   if (name == "lf_simt_wp") return lf_simt_.num_lanes ? lf_simt_.any_wp : 0;     // the SIMT launch is the weighted-predictor instantiation
   // the kernels the last decode's LF / HF stage launched (kernels.h kHfVar* / kLfVar* bits) and the LDS sizes that chose them (bytes, after Prepare)
   if (name == "hf_variant") return trace_.hf_variant;
@@ -1936,7 +1940,7 @@ void Batch::PlanLfSimt(PrepareState& st) {
   st.simt_streams_off = st.arena.Put(flat.data(), flat.size() * sizeof(LfSimtStream));
   st.simt_lanes_off = st.arena.Put(lanes.data(), lanes.size() * sizeof(LfSimtLane));
   st.simt_luts_off = st.arena.Put(tables.luts.data(), tables.luts.size());
-  lf_simt_.num_lanes = (uint32_t)lanes.size();
+  lf_simt_.num_lanes = (uint32_t)lanes.size(); lf_simt_.num_streams = (uint32_t)flat.size();
   lf_simt_.lanes_per_wave = (uint32_t)std::max(1, 64 / std::max(1, cfg.lane_stride_lf));
   lf_simt_.any_legacy = 0; lf_simt_.any_wp = tables.wp ? 1 : 0; lf_simt_.any_general = tables.general || tables.wp ? 1 : 0;
   for (int i = 0; i < st.n; i++) if (!images_[i]->plan.modular && !st.simt_frame[i]) lf_simt_.any_legacy = 1;

@@ -1074,6 +1074,7 @@ void JxlHipBatchSetOption(JxlHipBatch* h, const char* name, int value) {
   // (rounded down to 16 bytes: the kernels put regions of their own behind the staged tables — HfDecodeSimtKernel its lane slots — that must stay aligned)
   else if (n == "lds_code_budget" && value >= 0 && value <= 128 * 1024) h->b->cfg.lds_code_budget = value & ~15;
   else if (n == "lf_force_big" && value >= -1 && value <= 2) h->b->cfg.lf_force_big = value;
+  else if (n == "lf_spec_lanes" && (value == 0 || value == 1 || value == 2 || value == 4 || value == 8)) h->b->cfg.lf_spec_lanes = value;   // SIMT LF stage: lanes per stream (kernels.h LaunchCfg)
   else if (n == "jpeg_host_writer") h->b->jpeg_host_writer = value != 0;   // JxlHipBatchReconstructJpegs: every image through the host's Huffman writer
   else if (n == "jpeg_device_progressive") h->b->jpeg_device_progressive = value != 0;   // ... progressive files written by the device as well (jpeg_host_writer wins)
   else if (n == "resize_group_max" && value >= 1 && (uint32_t)value <= kResizeGroupMax) h->b->resize_group_max = (uint32_t)value;   // testing: images per resize launch (applies to the next Prepare)

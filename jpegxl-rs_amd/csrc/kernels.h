@@ -165,6 +165,8 @@ struct LaunchCfg {
                                      // on an idle GPU: 100 instead of 250 ms until the first batch can go on); reset by the launch
   int lf_wp_narrow_test = 0;         // testing: the SIMT LF kernel's weighted-predictor lanes hand a stream back at |sample| > 16 instead of 2^20
   int lf_force_big = 0;              // testing: the launch shape of LfDecodeKernel (kernels.hip LaunchLfDecode)
+  int lf_spec_lanes = 0;             // SIMT LF launches without the weighted predictor: lanes per stream, each with a candidate cluster whose alias slot it reads ahead (kernels.hip
+                                     // LfDecodeSimtKernel SPEC).  0: kLfSpecLanesDefault; 1: the one-lane form; 2, 4, 8: that many — never more than 64 / lane_stride_lf leaves idle
   int lf_head_start = 0;             // the LF launch waits until the next HF launch is resident (set for pipelined front-only calls)
   int idct_flags_known = 0, any_irregular_blocks = 1, any_big_blocks = 1;
   int hf_lanes_per_wave = 0, hf_lanes_per_wg = 0;   // SIMT HF decode: group streams per wavefront / per workgroup (0: the throughput defaults — a frame's streams on four wavefronts of one workgroup)
@@ -199,10 +201,11 @@ constexpr int32_t kLfRedoMark = 0x5eed;                    // lf_scratch[2] of a
 struct LfSimtChan { uint32_t lut_off; uint32_t info; };    // lut_off: byte offset in the batch's table blob; info: class word
 struct LfSimtStream { uint32_t frame, group; LfSimtChan chan[7]; };   // channels: LF Y, X, B, then ytox, ytob, block info, sharpness
 struct LfSimtLane { uint32_t first, count; };               // a lane decodes streams [first, first + count) one after the other
+constexpr uint32_t kLfSpecLanesDefault = 8;
 struct LfSimtPlan {
   const LfSimtStream* streams = nullptr; const LfSimtLane* lanes = nullptr; const uint8_t* luts = nullptr;   // device pointers
   const uint2* units = nullptr; uint32_t num_units = 0;     // varblock placement: {frame, LF group | band << 16} of every 32-row band of every VarDCT frame, longest first
-  uint32_t num_lanes = 0, lanes_per_wave = 16;
+  uint32_t num_lanes = 0, lanes_per_wave = 16, num_streams = 0;
   int any_legacy = 1;          // some VarDCT frame of the batch still takes LfDecodeKernel (one wavefront per stream)
   int any_general = 0;         // some SIMT stream needs more than the lean instantiation offers (kernels.hip LfDecodeSimtKernel<WP, GEN>)
   int any_wp = 0;              // some SIMT stream keeps weighted-predictor state (the kernel's WP instantiation; LfDecodeKernel follows for the streams it hands back)
@@ -221,7 +224,9 @@ struct LaunchTrace {
   int hf_variant = 0, lf_variant = 0;
   uint32_t lf_wide_bytes = 0;   // LDS bytes of the wave-wide decoder's copy of the Modular code's alias tables (0: the lane-0 serial path without it)
   int lf_wide_only = 0;         // the plain layout was left out (LdAliasAt puts entries together from the wide one)
+  int lf_spec_lanes = 0;        // lanes per stream of the SIMT LF launch without the weighted predictor (1: the one-lane form); 0: no such launch
 };
+int64_t LfSpecStats(int which);   // JXL_HIP_LF_SPEC_STATS: samples of this device's candidate-lane LF launches so far whose cluster was a candidate (0) / was not (1); -1 without the variable
 
 // VarDCT stages.  max_* are maxima over the batch (grid sizing); nframes = frames in batch.  trace: filled with the kernels launched (nullptr: not recorded).
 void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, const LaunchCfg& cfg, void* stream, const LfSimtPlan* simt = nullptr, LaunchTrace* trace = nullptr);

@@ -2760,11 +2760,33 @@ __device__ __forceinline__ int32_t QuadSum(int32_t v) {
   v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);      // quad_perm [2, 3, 0, 1]
   return v;
 }
-template <bool WP, bool GEN, bool QUAD = false> __global__ __launch_bounds__(256, WP ? 4 : (GEN ? 6 : 7)) void LfDecodeSimtKernel(const FrameDev* __restrict__ frames, const LfSimtStream* __restrict__ streams, const LfSimtLane* __restrict__ lanes,
-                                                          const uint8_t* __restrict__ luts, uint32_t num_lanes, uint32_t lanes_per_wave, int high_priority, const uint32_t* __restrict__ s_div) {
+// SPEC > 0 (launches without the weighted predictor, LaunchCfg::lf_spec_lanes): G = 1 << SPEC adjacent lanes carry ONE stream and run its chain redundantly, as the quads do.
+// Lane s of the group keeps one candidate cluster (and its hybrid-integer configuration) and reads that cluster's alias slot together with the class-table read — the
+// slot index comes from the rANS state alone —, so a sample whose cluster is one of the group's G candidates costs one L2 round trip, not two: the matching lane's entry
+// goes to the whole group by an OR over the group (three DPP steps a word; every other lane contributes zeros, equal candidates contribute equal words).  A group without
+// a match reads the entry as the one-lane form does, under a branch no wavefront without a miss enters, and the lane at a round-robin index takes the cluster as its
+// candidate.  A row of one constant cluster makes that cluster a candidate at its start and then always matches.  Candidates go back to cluster 0 — in every code — at
+// every stream start: a lane's streams may belong to frames with different codes.  Only lane 0 of a group writes (samples, scratch words, errors, the end position); the
+// others read the row above as lane 0 stored it (vector memory operations of one wavefront are performed in order).  Samples do not depend on G: the miss path is the
+// one-lane path.  spec_stats (JXL_HIP_LF_SPEC_STATS, experiments): {matched, missed} samples, added once per stream.
+// (the group size is a template parameter: with it in a register the compiler put a scalar branch around every DPP step, ~30 instructions a sample)
+template <int SHIFT> __device__ __forceinline__ uint32_t GroupOr(uint32_t v) {        // OR over 1 << SHIFT (<= 8) adjacent lanes, in every one of them
+  if constexpr (SHIFT >= 1) v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);      // quad_perm [1, 0, 3, 2]
+  if constexpr (SHIFT >= 2) v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);      // quad_perm [2, 3, 0, 1]
+  if constexpr (SHIFT >= 3) v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true);     // row_half_mirror: the other quad of the eight
+  return v;
+}
+template <bool WP, bool GEN, bool QUAD = false, int SPEC = 0> __global__ __launch_bounds__(256, WP ? 4 : (GEN || SPEC ? 6 : 7)) void LfDecodeSimtKernel(const FrameDev* __restrict__ frames, const LfSimtStream* __restrict__ streams, const LfSimtLane* __restrict__ lanes,
+                                                          const uint8_t* __restrict__ luts, uint32_t num_lanes, uint32_t lanes_per_wave, int high_priority, const uint32_t* __restrict__ s_div,
+                                                          unsigned long long* __restrict__ spec_stats) {
   static_assert(!QUAD || WP, "quads only pay for the weighted predictor");
-  const uint32_t lane_in_wave = QUAD ? (threadIdx.x & 63) >> 2 : (threadIdx.x & 63);
+  static_assert(SPEC >= 0 && SPEC <= 3 && (!SPEC || !WP), "candidate lanes: the launches without the weighted predictor, up to eight per stream");
+  const uint32_t lane_in_wave = QUAD ? (threadIdx.x & 63) >> 2 : (threadIdx.x & 63) >> SPEC;
   const uint32_t q = QUAD ? threadIdx.x & 3 : 0;              // which sub-predictor this lane owns
+  constexpr uint32_t gmask = (1u << SPEC) - 1;
+  const bool writer = !SPEC || (threadIdx.x & gmask) == 0;    // SPEC: lane 0 of its group
+  uint32_t my_cand = 0;                                       // SPEC: this lane's candidate cluster (bits 24-31) and its hybrid-integer configuration (bits 0-23)
+  uint32_t turn = (0u - threadIdx.x) & gmask;                 // bits 0-2: misses until this lane takes the missed cluster (round robin: 0 in one lane of the group at a time); from bit 3: the stream's misses
   const uint32_t li = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * lanes_per_wave + lane_in_wave;
   if (lane_in_wave >= lanes_per_wave || li >= num_lanes) return;
   if (high_priority & 1) __builtin_amdgcn_s_setprio(3);
@@ -2806,9 +2828,17 @@ template <bool WP, bool GEN, bool QUAD = false> __global__ __launch_bounds__(256
           const FrameDev& f = frames[LdG(&st->frame)];
           const uint32_t g = LdG(&st->group);
           const uint64_t limit = (f.single_section ? f.cs_size : f.sec_off[1 + g] + f.sec_size[1 + g]) * 8;
-          if (state != 0x130000u) SetError(f, kErrAnsFinalState);
-          else if (br.BitPos() > limit) SetError(f, kErrOverrun);
-          else if (f.single_section) f.stream_end_bitpos[0] = br.BitPos();
+          if (writer) {
+            if (state != 0x130000u) SetError(f, kErrAnsFinalState);
+            else if (br.BitPos() > limit) SetError(f, kErrOverrun);
+            else if (f.single_section) f.stream_end_bitpos[0] = br.BitPos();
+            if (SPEC && spec_stats) {      // samples of the stream: its seven channels' sizes
+              const uint32_t gbw = min(256u, f.bw - g % f.xlfgroups * 256), gbh = min(256u, f.bh - g / f.xlfgroups * 256), mc = ((gbw + 7) / 8) * ((gbh + 7) / 8);
+              uint32_t total = 2 * mc + 2 * (uint32_t)(f.lf_scratch + (uint64_t)g * f.lf_scratch_stride)[1] + gbw * gbh;
+              for (int pl = 0; pl < 3; pl++) total += (gbw >> f.hs[pl]) * (gbh >> f.vs[pl]);
+              atomicAdd(spec_stats, (unsigned long long)(total - (turn >> 3))); atomicAdd(spec_stats + 1, (unsigned long long)(turn >> 3));
+            }
+          }
           cur++; st++; c = 7;
         }
         if (c >= 7) {
@@ -2817,13 +2847,14 @@ template <bool WP, bool GEN, bool QUAD = false> __global__ __launch_bounds__(256
           const uint32_t g = LdG(&st->group);
           br.Init(f.cs, f.single_section ? (f.mod_nchan ? f.stream_end_bitpos[1] : f.lf_start_bitpos) : f.sec_off[1 + g] * 8, f.cs_size);
           int32_t* scratch = f.lf_scratch + (uint64_t)g * f.lf_scratch_stride;
-          scratch[0] = (int32_t)br.Read(2);      // extra_precision
-          scratch[1] = 0; scratch[2] = 0;
+          const int32_t extra_precision = (int32_t)br.Read(2);
+          if (writer) { scratch[0] = extra_precision; scratch[1] = 0; scratch[2] = 0; }
           bool default_wp = true;
-          if (!SkipGroupHeaderSimt(br, &default_wp)) { SetError(f, kErrUnsupported); cur++; continue; }   // (c stays 7: the next stream)
+          if (!SkipGroupHeaderSimt(br, &default_wp)) { if (writer) SetError(f, kErrUnsupported); cur++; continue; }   // (c stays 7: the next stream)
           if (WP && !default_wp) { scratch[2] = kLfRedoMark; cur++; continue; }
           state = br.Read(32);
           alias = f.mod_code.alias; cfgp = f.mod_code.cfg; la = f.mod_code.log_alpha; cfgu = f.mod_cfg_uniform;
+          if constexpr (SPEC) { my_cand = (cfgu != 0xFFFFFFFFu ? cfgu : LdG(cfgp)) & 0xFFFFFFu; turn &= 7; }      // (cluster 0 exists in every code)
           if (WP) wrows = reinterpret_cast<uint8_t*>(f.wp_scratch + (uint64_t)g * f.wp_scratch_stride);
           c = -1;
         }
@@ -2837,13 +2868,13 @@ template <bool WP, bool GEN, bool QUAD = false> __global__ __launch_bounds__(256
         int32_t* scratch = f.lf_scratch + (uint64_t)g * f.lf_scratch_stride;
         if (c == 3) {   // HF metadata sub-stream
           bool ok = true;
-          if (state != 0x130000u) { SetError(f, kErrAnsFinalState); ok = false; }
+          if (state != 0x130000u) { if (writer) SetError(f, kErrAnsFinalState); ok = false; }
           const uint32_t nb = 1 + br.Read(CeilLog2D(gbw * gbh));
           bool default_wp = true;
-          if (ok && !SkipGroupHeaderSimt(br, &default_wp)) { SetError(f, kErrUnsupported); ok = false; }
+          if (ok && !SkipGroupHeaderSimt(br, &default_wp)) { if (writer) SetError(f, kErrUnsupported); ok = false; }
           if (WP && ok && !default_wp) { scratch[2] = kLfRedoMark; ok = false; }
           if (!ok) { cur++; c = 7; continue; }
-          scratch[1] = (int32_t)nb;
+          if (writer) scratch[1] = (int32_t)nb;
           state = br.Read(32);
         }
         uint32_t nw_ = 0, nh_ = 0;
@@ -2877,6 +2908,13 @@ template <bool WP, bool GEN, bool QUAD = false> __global__ __launch_bounds__(256
           e = LdG(reinterpret_cast<const uint2*>(luts + e.x + 512 + 8 * k));
         }
         lut_off = e.x; cls = e.y; const_cluster = (e.y >> 16) & 0xFF;
+      }
+      if constexpr (SPEC) {
+        if ((cls & 3) == 0 && !GroupOr<SPEC>((my_cand >> 24) == const_cluster ? 1u : 0u)) {      // a row of one cluster: a candidate from here on, every sample matches
+          const uint32_t cm = cfgu != 0xFFFFFFFFu ? cfgu : LdG(cfgp + const_cluster);
+          if ((turn & 7) == 0) my_cand = (const_cluster << 24) | (cm & 0xFFFFFFu);
+          turn = (turn & ~7u) | ((turn + 1) & gmask);
+        }
       }
       if (hp && w < 4) {                 // narrow rows: the rolling prefetch could run ahead of the stores
         up0 = LdG(out - stride); up1 = w > 1 ? LdG(out - stride + 1) : 0; up2 = w > 2 ? LdG(out - stride + 2) : 0;
@@ -2952,7 +2990,11 @@ template <bool WP, bool GEN, bool QUAD = false> __global__ __launch_bounds__(256
       wp_err = p;
     }
     const uint32_t kind = cls & 3, pcode = (cls >> 2) & 7;
-    uint32_t cluster = const_cluster;
+    uint32_t cluster = SPEC ? (cls >> 16) & 0xFF : const_cluster;      // (SPEC: one register fewer across the iteration)
+    const uint32_t res = state & 0xFFF;
+    const uint32_t i = res >> (12 - la), pos = res & ((1u << (12 - la)) - 1);
+    uint64_t e_cand = 0;
+    if constexpr (SPEC) e_cand = LdG(alias + (((my_cand >> 24) << la) + i));      // beside the class-table read, not behind it
     if (kind) {
       uint32_t idx = (uint32_t)(min(max(grad, -512), 511) + 512);
       if (GEN) {
@@ -3025,10 +3067,28 @@ template <bool WP, bool GEN, bool QUAD = false> __global__ __launch_bounds__(256
       if (pcode == 4) guess = (avg + 3) >> 3;
     }
     // rANS symbol + hybrid integer (dec_ans.h), tables through the L2
-    const uint32_t res = state & 0xFFF;
-    const uint32_t i = res >> (12 - la), pos = res & ((1u << (12 - la)) - 1);
-    const uint64_t e = LdG(alias + ((cluster << la) + i));
-    const uint32_t cfg = cfgu != 0xFFFFFFFFu ? cfgu : LdG(cfgp + cluster);
+    uint64_t e;
+    uint32_t cfg;
+    if constexpr (SPEC) {
+      const bool match = (my_cand >> 24) == cluster;
+      uint32_t lo = GroupOr<SPEC>(match ? (uint32_t)e_cand : 0u), hi = GroupOr<SPEC>(match ? (uint32_t)(e_cand >> 32) : 0u);
+      uint32_t cw = GroupOr<SPEC>(match ? my_cand | 0x80000000u : 0u);      // (bit 31: some lane of the group matched — with cluster 128 and above it is set anyway)
+      const bool miss = (cw >> 31) == 0;
+      if (__builtin_expect(__builtin_amdgcn_ballot_w64(miss) != 0, 0)) {           // wavefront-uniform: the second round trip only where some group needs it
+        if (miss) {
+          const uint64_t em = LdG(alias + ((cluster << la) + i));
+          const uint32_t cm = cfgu != 0xFFFFFFFFu ? cfgu : LdG(cfgp + cluster);
+          lo = (uint32_t)em; hi = (uint32_t)(em >> 32); cw = cm;
+          if ((turn & 7) == 0) my_cand = (cluster << 24) | (cm & 0xFFFFFFu);
+          turn = ((turn & ~7u) + 8) | ((turn + 1) & gmask);
+        }
+      }
+      e = (uint64_t)lo | ((uint64_t)hi << 32);
+      cfg = cw & 0xFFFFFFu;
+    } else {
+      e = LdG(alias + ((cluster << la) + i));
+      cfg = cfgu != 0xFFFFFFFFu ? cfgu : LdG(cfgp + cluster);
+    }
     const uint32_t cutoff = (uint32_t)(e & 0xFF), right = (uint32_t)((e >> 8) & 0xFF);
     const uint32_t freq0 = (uint32_t)((e >> 16) & 0x1FFF), offs1 = (uint32_t)((e >> 29) & 0x1FFF), freq1 = (uint32_t)((e >> 42) & 0x1FFF);
     const bool hit = pos >= cutoff;
@@ -3051,7 +3111,7 @@ template <bool WP, bool GEN, bool QUAD = false> __global__ __launch_bounds__(256
       tok = (((hi << nbits) | bits) << lsb) | low;
     }
     const int32_t val = (int32_t)((uint32_t)UnpackSigned(tok) + (uint32_t)guess);
-    if (!(xp & 2)) StG(out + x, val);
+    if (writer && !(xp & 2)) StG(out + x, val);
     left = val;
     if (wp_live) {
       // what the sample turned out to be: true error, error magnitude of every sub-predictor -> this row's record; the chain for x + 1
@@ -6000,11 +6060,35 @@ static const uint32_t* WpDivTable() {
   }
   return table[dev];
 }
+// JXL_HIP_LF_SPEC_STATS (experiments): two 64-bit words per device the candidate-lane launches add their {matched, missed} samples to, once per stream; null otherwise
+static unsigned long long* LfSpecStatsWords() {
+  static const bool on = getenv("JXL_HIP_LF_SPEC_STATS") != nullptr;
+  if (!on) return nullptr;
+  static std::mutex mu;
+  static unsigned long long* words[64] = {nullptr};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64) dev = 0;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!words[dev]) {
+    if (hipMalloc((void**)&words[dev], 2 * sizeof(unsigned long long)) != hipSuccess) return nullptr;
+    (void)hipMemset(words[dev], 0, 2 * sizeof(unsigned long long));
+  }
+  return words[dev];
+}
+int64_t LfSpecStats(int which) {
+  unsigned long long* w = LfSpecStatsWords();
+  unsigned long long v[2] = {0, 0};
+  if (!w || which < 0 || which > 1) return -1;
+  (void)hipDeviceSynchronize();
+  if (hipMemcpy(v, w, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return (int64_t)v[which];
+}
 static void PlanModularLds(const LaunchCfg& cfg, uint32_t* nwaves_io, uint32_t* tree_cap, uint32_t* lds_tables, uint32_t* wp_base, uint32_t* lds_total);
 void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, const LaunchCfg& cfg, void* stream, const LfSimtPlan* simt, LaunchTrace* trace) {
   LaunchTrace tr;
   if (!trace) trace = &tr;
-  trace->lf_variant = 0; trace->lf_wide_bytes = 0; trace->lf_wide_only = 0;
+  trace->lf_variant = 0; trace->lf_wide_bytes = 0; trace->lf_wide_only = 0; trace->lf_spec_lanes = 0;
   if (cfg.any_local_lf) {   // frames whose LfGroup sub-streams bring their own trees / codes: one wavefront per LF group, each staging its tables
     uint32_t nwaves = 1, tree_cap, lds_tables, wp_base, lds_bytes;
     PlanModularLds(cfg, &nwaves, &tree_cap, &lds_tables, &wp_base, &lds_bytes);
@@ -6055,11 +6139,28 @@ void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, cons
       // four lanes per stream: at most 16 streams per wavefront
       const uint32_t lpq = std::min(16u, lpw);
       const int nwq = DivUp((int)simt->num_lanes, (int)lpq);
-      hipLaunchKernelGGL((LfDecodeSimtKernel<true, true, true>), dim3(DivUp(nwq, wpb)), block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpq, lf_flags, wp_div);
+      hipLaunchKernelGGL((LfDecodeSimtKernel<true, true, true>), dim3(DivUp(nwq, wpb)), block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpq, lf_flags, wp_div, nullptr);
       trace->lf_variant |= kLfVarSimtWpQuad;
-    } else if (simt->any_wp) { hipLaunchKernelGGL((LfDecodeSimtKernel<true, true>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div); trace->lf_variant |= kLfVarSimtWp; }
-    else if (simt->any_general) { hipLaunchKernelGGL((LfDecodeSimtKernel<false, true>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div); trace->lf_variant |= kLfVarSimtGen; }
-    else { hipLaunchKernelGGL((LfDecodeSimtKernel<false, false>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div); trace->lf_variant |= kLfVarSimtLean; }
+    } else if (simt->any_wp) { hipLaunchKernelGGL((LfDecodeSimtKernel<true, true>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div, nullptr); trace->lf_variant |= kLfVarSimtWp; }
+    else {
+      // candidate lanes (LfDecodeSimtKernel SPEC): G lanes per stream out of those the packing leaves idle; the wavefronts of the launch stay the same
+      static const int spec_env = getenv("JXL_HIP_LF_SPEC_LANES") ? atoi(getenv("JXL_HIP_LF_SPEC_LANES")) : 0;      // A/B where no LaunchCfg is at hand (pipelines): as lf_spec_lanes
+      const int want = cfg.lf_spec_lanes ? cfg.lf_spec_lanes : spec_env;
+      const uint32_t room = 64u / lpw;                                                 // (lpw is a power of two: 64 / lane_stride_lf)
+      const uint32_t G = std::min(room, want == 1 || want == 2 || want == 4 || want == 8 ? (uint32_t)want : kLfSpecLanesDefault);
+      const uint32_t shift = G >= 8 ? 3u : G >= 4 ? 2u : G >= 2 ? 1u : 0u;
+      unsigned long long* stats = shift ? LfSpecStatsWords() : nullptr;
+      trace->lf_spec_lanes = 1 << shift;
+#define JXL_LF_SIMT_LAUNCH(GEN, SPEC) hipLaunchKernelGGL((LfDecodeSimtKernel<false, GEN, false, SPEC>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div, stats)
+      if (simt->any_general) {
+        if (shift == 3) JXL_LF_SIMT_LAUNCH(true, 3); else if (shift == 2) JXL_LF_SIMT_LAUNCH(true, 2); else if (shift == 1) JXL_LF_SIMT_LAUNCH(true, 1); else JXL_LF_SIMT_LAUNCH(true, 0);
+        trace->lf_variant |= kLfVarSimtGen;
+      } else {
+        if (shift == 3) JXL_LF_SIMT_LAUNCH(false, 3); else if (shift == 2) JXL_LF_SIMT_LAUNCH(false, 2); else if (shift == 1) JXL_LF_SIMT_LAUNCH(false, 1); else JXL_LF_SIMT_LAUNCH(false, 0);
+        trace->lf_variant |= kLfVarSimtLean;
+      }
+#undef JXL_LF_SIMT_LAUNCH
+    }
     if (!simt->any_legacy && !simt->any_wp) { place(); return; }
     simt_mode = simt->any_wp ? 2 : 0;         // the weighted-predictor lanes may hand streams back: LfDecodeKernel follows for those (and for the legacy frames)
   }

@@ -397,6 +397,24 @@ JxlDecoderStatus JxlHipBatchSetOutputJpegScaled(JxlHipBatch* batch, int index, c
  * pipelines always take the DC-only path).  JxlHipBatchGetInfo / JxlHipPipelineGetInfo "jpeg_dc_only_images": images of the last call / the job finished last that were
  * written from their DC terms; they count in "jpeg_pixel_images" as before.  A group of DC-only images adds one launch to "jpeg_pixel_launches", not two. */
 int JxlHipBatchJpegDcOnly(const JxlHipBatch* batch, int index);
+/* Crops decoded by region: JxlHipBatchSetOption "jpeg_region" = 1 (default 0; read by the next JxlHipBatchPrepare), JxlHipPipelineSetOption "jpeg_region" for the jobs
+ * submitted after it.  An output written by JxlHipBatchDecodeJpegPixels (or a libjpeg-exact pipeline job) that carries a crop then decodes only the 256x256 groups the
+ * crop needs — HF entropy stage, integer IDCT and colour stage —; the bytes delivered are exactly those of the decode without the option.  The rule, for an image that
+ * decode takes, that is not DC-only and whose output has a crop (jpeg_scale s = 1, 2, 4, 8):
+ *   1. the crop — given in the oriented picture at scale s — is mapped back through the orientation to a rectangle of the stored picture at scale s;
+ *   2. a luma block covers n x n of its pixels, n = 8 / s: the crop's luma blocks are floor(first / n) .. floor(last / n) per axis;
+ *   3. that range is widened outwards to whole MCUs of (1 << hs) x (1 << vs) luma blocks, hs / vs the chroma shifts (grey and 4:4:4: 1 x 1);
+ *   4. plus one MCU on every side (fancy chroma upsampling reads the neighbouring chroma sample; taken at 4:4:4 and grey too), clamped to the frame's block grid;
+ *   5. the region is every group (32 x 32 blocks) that block rectangle touches: gx0 <= gx < gx1, gy0 <= gy < gy1.
+ * Images without a crop, DC-only images and images the libjpeg-exact decode does not take have no region and are decoded whole.  A damaged stream in a skipped group
+ * goes unnoticed.  JxlHipBatchDecode, the float decode of the same batch, decodes every group whatever the option says.
+ * JxlHipBatchJpegRegion(index, groups), host only, after the image's output has been set: 1 and groups = {gx0, gy0, gx1, gy1} if the image would be decoded by region
+ * under the option (whether or not the option is set), 0 if it would be decoded whole.
+ * JxlHipBatchGetInfo "hf_groups_total" / "hf_groups_decoded" (JxlHipPipelineGetInfo: of the job prepared last): the groups of the frames that took the HF stage of the
+ * last JxlHipBatchDecodeJpegPixels, and those of them that were decoded — equal with the option off.  JxlHipBatchStageBytes counts the HF, IDCT and output stages of an
+ * image with a region by its region after JxlHipBatchDecodeJpegPixels (JxlHipPipelineStageBytes: for a libjpeg-exact job), and by the whole picture after JxlHipBatchDecode.
+ * JxlHipBatchJpegRegion also answers 1 for a cropped output set through the float calls (JxlHipBatchSetOutputResampled): it says what JxlHipBatchDecodeJpegPixels would do. */
+int JxlHipBatchJpegRegion(const JxlHipBatch* batch, int index, uint32_t groups[4]);
 JxlDecoderStatus JxlHipLfPartSize(const uint8_t* data, size_t size, size_t* bytes);
 /* The integer resample of libjpeg-exact outputs: Pillow's 8-bit resize, byte for byte.  JxlHipBatchSetOutputJpegResampled is JxlHipBatchSetOutputJpegScaled with
  * `flags`; flags = 0 is that call, byte for byte; bit 0, JXL_HIP_RESAMPLE_U8, selects the integer resample; every other bit is refused.  Sizes are those of
@@ -430,7 +448,8 @@ void JxlHipBatchSetLaneStride(JxlHipBatch* batch, int lf, int hf);
 /* Tuning / testing knobs: "force_generic_idct", "hf_block_threads", "lds_code_budget", "debug_stop_after", "lf_wide_once" (the next LF stage of the batch takes the
  * one-wavefront-per-stream kernel whatever the lane stride: shorter latency on an idle GPU), "lf_wp_narrow_test" (testing: the SIMT LF kernel's
  * weighted-predictor lanes hand a stream back to the one-wavefront-per-stream kernel at |sample| > 16 instead of 2^20), "allow_partial" (images added afterwards may
- * end behind their LF part: they decode at 1:8 only, JxlHipBatchSetOutputScaled; otherwise JxlHipBatchPrepare fails with "truncated"). Unknown names are ignored. */
+ * end behind their LF part: they decode at 1:8 only, JxlHipBatchSetOutputScaled; otherwise JxlHipBatchPrepare fails with "truncated"), "jpeg_region" (crops of libjpeg-exact outputs decode only the groups they need: JxlHipBatchJpegRegion).
+ * Unknown names are ignored. */
 void JxlHipBatchSetOption(JxlHipBatch* batch, const char* name, int value);
 /* Uploads streams and tables (inputs become HBM-resident) and allocates work buffers.  hip_stream: hipStream_t or NULL. */
 JxlDecoderStatus JxlHipBatchPrepare(JxlHipBatch* batch, void* hip_stream);
@@ -570,6 +589,9 @@ void JxlHipPipelineStageBytes(JxlHipPipeline* pipeline, uint64_t out[6]);   /* a
  * of the job finished last, 0 unless it was a reconstruction job: "jpeg_device_images", "jpeg_host_images", "jpeg_device_progressive_images" (as JxlHipBatchGetInfo),
  * "jpeg_gather_launches" (launches of the gather kernel: one per 32768 images).  -1: unknown name. */
 int64_t JxlHipPipelineGetInfo(JxlHipPipeline* pipeline, const char* name);
+/* Options that apply to the jobs submitted after the call: "jpeg_region" (0 / 1, default 0: libjpeg-exact jobs decode crops by region, JxlHipBatchJpegRegion; GetInfo
+ * "hf_groups_total" / "hf_groups_decoded" of the job prepared last).  Unknown names are ignored. */
+void JxlHipPipelineSetOption(JxlHipPipeline* pipeline, const char* name, int value);
 /* Pinned host memory for host_out destinations (hipHostMalloc / hipHostFree). */
 void* JxlHipHostAlloc(size_t bytes);
 void JxlHipHostFree(void* p);

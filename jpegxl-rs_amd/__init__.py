@@ -202,7 +202,8 @@ def libjxl():
             "JxlHipImageOutSizeJpegScaled": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(JxlBasicInfo),
                                                        C.POINTER(sz)]),
             "JxlHipBatchCanDecodeJpegPixels": (C.c_int, [vp, C.c_int]), "JxlHipBatchDecodeJpegPixels": (C.c_int, [vp, vp]), "JxlHipBatchJpegPixelsStatus": (C.c_int, [vp, C.c_int]),
-            "JxlHipBatchJpegDcOnly": (C.c_int, [vp, C.c_int]), "JxlHipLfPartSize": (C.c_int, [vp, sz, C.POINTER(sz)]),
+            "JxlHipBatchJpegDcOnly": (C.c_int, [vp, C.c_int]), "JxlHipBatchJpegRegion": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint32 * 4)]),
+            "JxlHipPipelineSetOption": (None, [vp, C.c_char_p, C.c_int]), "JxlHipLfPartSize": (C.c_int, [vp, sz, C.POINTER(sz)]),
             "JxlHipBatchSetLaneStride": (None, [vp, C.c_int, C.c_int]), "JxlHipBatchSetOption": (None, [vp, C.c_char_p, C.c_int]),
             "JxlHipBatchPrepare": (C.c_int, [vp, vp]), "JxlHipBatchDecode": (C.c_int, [vp, vp]),
             "JxlHipBatchDecodeTimed": (C.c_int, [vp, vp]), "JxlHipBatchFinish": (C.c_int, [vp, vp]),
@@ -943,6 +944,13 @@ class BatchDecoder:
         of lf_part_size() bytes was enough (include/jxl_hip.h JxlHipBatchJpegDcOnly); set_option("jpeg_dc_only", 0) turns the path off."""
         return bool(libjxl().JxlHipBatchJpegDcOnly(self._h, int(i)))
 
+    def jpeg_region(self, i):
+        """None, or (gx0, gy0, gx1, gy1): the rectangle of 256x256 groups — gx0 <= gx < gx1, gy0 <= gy < gy1 — that decode_jpeg_pixels() decodes of image i (output set:
+        after add) under set_option("jpeg_region", 1): what the crop of its output needs (include/jxl_hip.h JxlHipBatchJpegRegion has the rule).  None: the image is
+        decoded whole — no crop, DC-only, or not taken by the libjpeg-exact decode.  Host only."""
+        g = (C.c_uint32 * 4)()
+        return tuple(int(v) for v in g) if libjxl().JxlHipBatchJpegRegion(self._h, int(i), C.byref(g)) else None
+
     def decode_jpeg_pixels(self, stream=None) -> list:
         """The samples libjpeg gives for the original JPEG file of every transcode of the batch (integer IDCT, libjpeg's chroma upsampling and colour conversion), written
         like a decode(): output(i) / device_output(i) hand them out.  Returns, per image, None or the reason why that image has no pixels (it fails alone)."""
@@ -1221,3 +1229,8 @@ class Pipeline:
 
     def info(self, name: str) -> int:
         return int(libjxl().JxlHipPipelineGetInfo(self._h, name.encode()))
+
+    def set_option(self, name: str, value: int):
+        """Options for the jobs submitted from now on (include/jxl_hip.h JxlHipPipelineSetOption): "jpeg_region" = 1 — libjpeg-exact jobs decode only the groups the
+        crops of their outputs need (BatchDecoder.jpeg_region); info("hf_groups_decoded") / info("hf_groups_total") of the job prepared last."""
+        libjxl().JxlHipPipelineSetOption(self._h, name.encode(), int(value))

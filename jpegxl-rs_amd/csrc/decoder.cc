@@ -101,6 +101,7 @@ static const float kUp8[210] = {
 
 struct ConstOffsets {
   size_t cs = 0, sec_off = 0, sec_size = 0, tree = 0, bcm = 0;
+  size_t hf_list = (size_t)-1; uint32_t hf_count = 0;      // a frame decoded by region (Batch::JpegRegionUnit): the indices of the groups to decode, raster order
   size_t mod_ctx = 0, mod_cfg = 0, mod_alias = 0, mod_pc = 0, mod_po = 0, mod_ps = 0, mod_chan = 0, up_weights = 0;
   struct Pass { size_t ac_ctx = 0, ac_cfg = 0, ac_alias = 0, ac_pc = 0, ac_po = 0, ac_ps = 0; size_t orders[39] = {0}; };
   vec<Pass> pass;
@@ -919,6 +920,47 @@ static std::string DownscaleRefusalOf(int num_units, const ImageEntry& e) {
   return what ? std::string("unsupported: downscaled decode of ") + what : std::string();
 }
 std::string Batch::DownscaleRefusal(int i) const { return DownscaleRefusalOf(pub_[i].num_units, *images_[pub_[i].first_unit]); }
+// Which groups the libjpeg-exact decode of a crop needs (decoder.h jpeg_region), for a single-frame JPEG transcode that decode takes:
+//   1. the crop (source picture: oriented, at jpeg_scale s) is mapped back through the orientation — the inverse of pixel_ops.h OutPixelPtr — to rect[] = x0, y0, w, h of
+//      the stored picture at scale s, ceil(xsize / s) x ceil(ysize / s);
+//   2. a luma block covers n x n of its pixels, n = 8 / s: blocks floor(first / n) .. floor(last / n) per axis;
+//   3. widened outwards to whole MCUs of (1 << hs) x (1 << vs) luma blocks (hs / vs: the chroma shifts; grey and 4:4:4: 1 x 1);
+//   4. one MCU more on every side — h2v1 / h2v2 fancy upsampling reads chroma sample i +- 1, which lies in the neighbouring chroma block at every scale, a block
+//      holding at least one sample; taken at 4:4:4 and grey too: one rule —, clamped to the frame's block grid;
+//   5. groups[] = gx0, gy0, gx1, gy1: every group (32 x 32 blocks) that block rectangle touches, gx0 <= gx < gx1, gy0 <= gy < gy1.
+static bool JpegRegionRule(const ImageEntry& e, const OutputSpec& o, uint32_t groups[4], uint32_t rect[4]) {
+  const FramePlan& p = e.plan;
+  const uint32_t s = o.jpeg_scale ? o.jpeg_scale : 1, n = 8 / s;
+  const uint32_t w = (e.ih.xsize + s - 1) / s, h = (e.ih.ysize + s - 1) / s;
+  if (!n || !w || !h || !p.bw || !p.bh || !o.crop_w || !o.crop_h) return false;
+  const uint32_t X0 = o.crop_x0, Y0 = o.crop_y0, X1 = o.crop_x0 + o.crop_w - 1, Y1 = o.crop_y0 + o.crop_h - 1;      // inclusive, in the oriented picture
+  const uint32_t orient = o.keep_orientation ? 1 : e.ih.orientation;
+  const uint32_t ow = orient > 4 ? h : w, oh = orient > 4 ? w : h;
+  if (X1 >= ow || Y1 >= oh) return false;
+  uint32_t x0 = X0, x1 = X1, y0 = Y0, y1 = Y1;
+  switch (orient) {
+    case 2: x0 = w - 1 - X1; x1 = w - 1 - X0; break;
+    case 3: x0 = w - 1 - X1; x1 = w - 1 - X0; y0 = h - 1 - Y1; y1 = h - 1 - Y0; break;
+    case 4: y0 = h - 1 - Y1; y1 = h - 1 - Y0; break;
+    case 5: x0 = Y0; x1 = Y1; y0 = X0; y1 = X1; break;
+    case 6: x0 = Y0; x1 = Y1; y0 = h - 1 - X1; y1 = h - 1 - X0; break;
+    case 7: x0 = w - 1 - Y1; x1 = w - 1 - Y0; y0 = h - 1 - X1; y1 = h - 1 - X0; break;
+    case 8: x0 = w - 1 - Y1; x1 = w - 1 - Y0; y0 = X0; y1 = X1; break;
+    default: break;
+  }
+  rect[0] = x0; rect[1] = y0; rect[2] = x1 - x0 + 1; rect[3] = y1 - y0 + 1;
+  const bool grey = e.ih.color_space == 1;
+  const uint32_t mx = grey ? 1u : 1u << p.hs[0], my = grey ? 1u : 1u << p.vs[0];      // luma blocks per MCU (Y is channel 1; Cb / Cr share their shifts)
+  auto axis = [](uint32_t first, uint32_t last, uint32_t n, uint32_t mcu, uint32_t nblocks, uint32_t* g0, uint32_t* g1) {
+    const uint32_t m0 = first / n / mcu, m1 = last / n / mcu;                  // MCUs of the crop's blocks
+    const uint32_t b0 = (m0 ? m0 - 1 : 0) * mcu;                                // one MCU more on either side
+    const uint32_t b1 = std::min((m1 + 2) * mcu - 1, nblocks - 1);
+    *g0 = std::min(b0, nblocks - 1) / 32; *g1 = b1 / 32 + 1;
+  };
+  axis(x0, x1, n, mx, p.bw, &groups[0], &groups[2]);
+  axis(y0, y1, n, my, p.bh, &groups[1], &groups[3]);
+  return groups[0] < groups[2] && groups[1] < groups[3] && groups[2] <= p.xgroups && groups[3] <= p.ygroups;
+}
 void Batch::SetOutput(int i, const OutputSpec& o) {
   ImageEntry& e = *images_[pub_[i].first_unit];
   if (o.downscale != 1) {
@@ -954,8 +996,21 @@ void Batch::SetOutput(int i, const OutputSpec& o) {
   e.out.num_channels = nc;
   e.out_size = OutputSize(dims, o);
   e.src_w = SourceWidth(dims, o); e.src_h = SourceHeight(dims, o);
+  // (the crop lies inside the source picture: OutputSize above has thrown otherwise)
+  e.jpeg_region_eligible = false;
+  if (o.cropped() && o.resized() && o.downscale == 1 && CanDecodeJpegPixelsAs(i, o, nullptr)) e.jpeg_region_eligible = JpegRegionRule(e, o, e.region_groups, e.region_rect);
   e.deliver_frames.clear();
   prepared_ = false;
+}
+bool Batch::JpegRegionOf(int i, uint32_t groups[4]) const {
+  const ImageEntry& e = *images_[pub_[i].first_unit];
+  if (!e.jpeg_region_eligible || JpegDcOnly(i)) return false;
+  for (int k = 0; k < 4; k++) groups[k] = e.region_groups[k];
+  return true;
+}
+bool Batch::JpegRegionUnit(int unit) const {
+  const ImageEntry& e = *images_[unit];
+  return jpeg_region && e.frame_index == 0 && e.jpeg_region_eligible && !JpegDcOnlyUnit(unit);
 }
 void Batch::SetOutputAllFrames(int i, const OutputSpec& o, const vec<int>& frames) {
   if (o.device_ptr || o.only_frame >= 0 || frames.empty()) throw ParseError("SetOutputAllFrames: internal output buffers, coalesced frames only", false);
@@ -1016,15 +1071,28 @@ void Batch::StageBytes(uint64_t out[6]) const {
       out[5] += (uint64_t)((e.ih.xsize + 7) / 8) * ((e.ih.ysize + 7) / 8) * (4 * (e.ih.color_space == 1 ? 1 : 3) + out_px);
       continue;
     }
+    // pixels through the IDCT and through the write stage: the frame's — or, for a frame the libjpeg-exact decode planned last decodes by region (hf_by_region_: not after
+    // a Run, which decodes every group whatever lists the frames carry), the sections of the region's groups, the pixels of their blocks, the crop's rectangle
+    uint64_t idct_px = npx, write_px = npx;
+    if (hf_by_region_ && JpegRegionUnit((int)u) && !p.single_section) {
+      const uint32_t* rg = e.region_groups;
+      hf_sec = 0;
+      for (uint32_t gy = rg[1]; gy < rg[3]; gy++) for (uint32_t gx = rg[0]; gx < rg[2]; gx++) {
+        const size_t s = 2 + (size_t)p.num_lf_groups + (size_t)gy * p.xgroups + gx;
+        if (s < p.sections.size()) hf_sec += p.sections[s].size;
+      }
+      idct_px = (uint64_t)(std::min(rg[2] * 32, p.bw) - rg[0] * 32) * (std::min(rg[3] * 32, p.bh) - rg[1] * 32) * 64;
+      write_px = (uint64_t)e.region_rect[2] * e.region_rect[3];
+    }
     out[2] += hf_sec + (u < hf_written_.size() ? (uint64_t)hf_written_[u] * 4 : 0);
-    out[3] += npx * (12 + 12);
+    out[3] += idct_px * (12 + 12);
     const bool fused = p.lf.gab && p.lf.epf_iters == 1 && e.ih.xyb_encoded && SimpleTransfer(e.ih) && p.upsampling == 1 && !e.complex && !cfg.force_unfused_filters;
     const bool any_filter = p.lf.gab || p.lf.epf_iters > 0;
     const bool epf_writes = !fused && p.lf.epf_iters >= 1 && p.upsampling == 1 && !e.complex && cfg.debug_stop_after == 0;    // kernels.hip EpfWritesOutput
     if (fused || epf_writes) out[4] += npx * (12 + out_px);
     else {
       if (any_filter) out[4] += npx * 24;
-      out[5] += npx * (12 + out_px);
+      out[5] += write_px * (12 + out_px);
     }
   }
 }
@@ -1084,6 +1152,8 @@ int64_t Batch::Info(const std::string& name) const {
   if (name == "jpeg_gather_launches") return jpeg_gather_launches_;                        // ... launches of JpegGatherKernel: one per group of the gather table
   if (name == "jpeg_pixel_images") return jpeg_pixel_images_;       // images the last DecodeJpegPixels wrote
   if (name == "jpeg_pixel_launches") return jpeg_pixel_launches_;   // ... launches of its pixel kernels (two per group of the image table, one per DC-only group, however many images a group holds)
+  if (name == "hf_groups_total") return hf_groups_total_;           // ... groups of the frames that took its HF stage, and those of them that were decoded: equal unless
+  if (name == "hf_groups_decoded") return hf_groups_decoded_;       // jpeg_region is on and some image has a region (Batch::JpegRegionOf)
   if (name == "jpeg_dc_only_images") return jpeg_dc_only_images_;   // ... images of it written from their DC terms alone (JpegDcOutKernel; Batch::JpegDcOnly)
   if (name == "lf_simt_lanes") return lf_simt_.num_lanes;
   if (name == "lf_simt_streams") return lf_simt_.num_streams;      // (more streams than lanes: some lane decodes several, one after the other)
@@ -1359,7 +1429,7 @@ void Batch::PutStreamTables(PrepareState& st) {
       st.natural_off[b] = arena.Put(natural[b].data(), natural[b].size() * 2);
     }
   }
-  max_lf_groups_ = max_groups_ = max_w_ = max_h_ = max_bw_ = max_bh_ = 0;
+  max_lf_groups_ = max_groups_ = max_hf_slots_ = max_w_ = max_h_ = max_bw_ = max_bh_ = 0;
   any_vardct_ = any_modchan_ = any_multipass_ = any_scaled_ = any_full_vardct_ = false;
   fplan_ = FilterPlan();
   resize_plans_.clear(); resize_groups_.clear();
@@ -1403,6 +1473,20 @@ void Batch::PutStreamTables(PrepareState& st) {
     if (!p.modular) any_vardct_ = true;      // (single-section frames: HfGlobal is parsed in the pre-run; nothing is reserved for it here)
     max_lf_groups_ = std::max<int>(max_lf_groups_, p.num_lf_groups);
     max_groups_ = std::max<int>(max_groups_, p.num_groups);
+    if (!p.modular && !EndsBehindLf(i)) {
+      // the groups an HF launch that honours the lists decodes for this frame (RunPart 12): those of its region, or all of them
+      uint32_t slots = p.num_groups;
+      if (JpegRegionUnit(i)) {
+        vec<uint32_t> list;
+        for (uint32_t gy = e.region_groups[1]; gy < e.region_groups[3]; gy++) for (uint32_t gx = e.region_groups[0]; gx < e.region_groups[2]; gx++) list.push_back(gy * p.xgroups + gx);
+        // (what the kernels rely on: no entry names a group the frame does not have — every per-group address follows from it)
+        bool ok = !list.empty() && list.size() <= p.num_groups;
+        for (uint32_t g : list) ok = ok && g < p.num_groups;
+        if (!ok) throw ParseError("Prepare: the region of image " + std::to_string(e.pub_index) + " leaves its frame's groups", false);
+        c.hf_list = arena.Put(list.data(), list.size() * 4); c.hf_count = slots = (uint32_t)list.size();
+      }
+      max_hf_slots_ = std::max<int>(max_hf_slots_, (int)slots);
+    }
     max_w_ = std::max<int>(max_w_, p.width); max_h_ = std::max<int>(max_h_, p.height);
     max_bw_ = std::max<int>(max_bw_, p.bw); max_bh_ = std::max<int>(max_bh_, p.bh);
     if (!p.modular && DecodedAtEighth(i)) any_scaled_ = true;
@@ -1655,6 +1739,7 @@ void Batch::FillFrameCommon(int i, const uint8_t* cbase, const PrepareState& st)
   f.group_dim = p.group_dim; f.is_modular = p.modular; f.plane_stride = p.bw * 8; f.plane_rows = p.bh * 8;
   f.cs = cbase + c.cs; f.cs_size = st.cs_bytes[i];
   f.sec_off = (const uint64_t*)(cbase + c.sec_off); f.sec_size = (const uint64_t*)(cbase + c.sec_size);
+  if (c.hf_list != (size_t)-1) { f.hf_list = (const uint32_t*)(cbase + c.hf_list); f.hf_count = c.hf_count; }
   f.single_section = p.single_section;
   f.lf_start_bitpos = p.global_data_bitpos;  // VarDCT without extra channels: LfGroup follows LfGlobal directly
   f.stream_end_bitpos = (uint64_t*)(dwork_ + o.end_bitpos);
@@ -2082,7 +2167,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
   if (st.time_phases) fprintf(stderr, "[jxl-hip] Prepare of %d frames (%.1f MB of tables and streams, %.1f MB work arena), ms:%s\n", st.n, hconst_.size() / 1e6, work_size_ / 1e6, st.t_report.c_str());
   PrepareLfFrameBatch(stream_v, wait_upload);
   FinishCfg();
-  prepared_ = true;
+  prepared_ = true; hf_by_region_ = false;      // (until a libjpeg-exact decode is planned over this layout)
 }
 
 // JXL_HIP_DEBUG_SYNC=1: name every stage on stderr and wait for it (finding the kernel behind a device fault)
@@ -2684,7 +2769,11 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
   // The libjpeg-exact tail of JPEG transcodes (PlanJpegPixels / EnqueueJpegPixelTable first) takes the places of 7 and 8: 9 = integer IDCT over the HF planes, which
   // zeroes what it reads like the float IDCT, 10 = chroma upsampling, colour, write, resizes.
   const bool jpeg_tail = part == 9 || part == 10;
-  const bool do_hf = part == 0 || part == 2 || part == 3, do_tail = part == 0 || part == 2 || part == 4 || part == 7 || part == 8 || jpeg_tail;
+  // 12 = 3 for a libjpeg-exact decode (its tail, 9 / 10, follows): frames decoded by region (jpeg_region) decode the groups of their lists only; every other part that
+  // runs the HF stage decodes every group
+  const bool hf_by_list = part == 12 && jpeg_region;
+  if (part == 12) hf_by_region_ = hf_by_list; else if (part == 0 || part == 2 || part == 3) hf_by_region_ = false;      // (what StageBytes describes: the HF stage enqueued last)
+  const bool do_hf = part == 0 || part == 2 || part == 3 || part == 12, do_tail = part == 0 || part == 2 || part == 4 || part == 7 || part == 8 || jpeg_tail;
   const bool do_idct = do_tail && part != 8 && part != 10, do_post = do_tail && part != 7 && part != 9;
   const bool split = part != 0;                       // halves timed separately
   if (do_hf || do_tail) ran_once_ = true;
@@ -2759,7 +2848,9 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
     if (any_full_vardct_) ClearCoefficientsBeforeHf(stream_v);
     rec(split ? 7 : 2);
     // (progressive flush at the kDC step: no AC group is decoded — the planes stay zero, the IDCT sees the LF part only)
-    if (!cfg.skip_hf && any_full_vardct_) LaunchHfDecode(dframes_, n, max_groups_, cfg, stream_v, &trace_);
+    cfg.hf_by_list = hf_by_list ? 1 : 0;
+    if (!cfg.skip_hf && any_full_vardct_) LaunchHfDecode(dframes_, n, hf_by_list ? max_hf_slots_ : max_groups_, cfg, stream_v, &trace_);
+    cfg.hf_by_list = 0;
     DebugSync("HF decode", stream_v);
     if (any_modchan_) EnqueueModularTail(stream_v);   // (the PassGroup Modular parts start where the HF streams ended)
     if (any_full_vardct_) LaunchZeroFailedCoefficients(dframes_, n, stream_v);   // (frames that failed up to here are skipped by the IDCT kernels: their planes are zeroed now)
@@ -3573,6 +3664,28 @@ size_t Batch::PlanJpegPixels() {
     t.npos = walk ? g.grid_w[0] * g.grid_h[0] : (uint32_t)g.nblk; t.ncomp = ncomp; t.frame = (uint32_t)u;
     t.width = e.ih.xsize; t.height = e.ih.ysize; t.hs = ncomp == 3 ? g.hs[1] : 0; t.vs = ncomp == 3 ? g.vs[1] : 0;
     t.scale = e.out.jpeg_scale;
+    // what of the image is decoded: all of it, or (jpeg_region, an image with a region — the groups of FrameDev::hf_list, which Prepare made from the same rectangle) the
+    // blocks of the region's groups and the pixels of the crop.  Component block (bx, by) is frame block (bx << hs, by << vs) and a group is 32 x 32 frame blocks, so the
+    // component's share of the group rectangle is [32 gx0 >> hs, 32 gx1 >> hs) x [32 gy0 >> vs, 32 gy1 >> vs), cut to its grid.
+    const bool by_region = JpegRegionUnit(u) && f.hf_list;
+    for (uint32_t c = 0; c < ncomp; c++) { t.reg_x0[c] = t.reg_y0[c] = 0; t.reg_w[c] = g.grid_w[c]; t.reg_h[c] = g.grid_h[c]; }
+    t.rect_x0 = t.rect_y0 = 0; t.rect_w = (t.width + t.scale - 1) / t.scale; t.rect_h = (t.height + t.scale - 1) / t.scale;
+    if (by_region) {
+      bool ok = e.region_rect[2] && e.region_rect[3] && e.region_rect[0] < t.rect_w && e.region_rect[2] <= t.rect_w - e.region_rect[0] && e.region_rect[1] < t.rect_h &&
+                e.region_rect[3] <= t.rect_h - e.region_rect[1];
+      uint32_t npos = 0;
+      for (uint32_t c = 0; c < ncomp && ok; c++) {
+        const uint32_t x0 = (e.region_groups[0] * 32) >> g.hs[c], x1 = std::min((e.region_groups[2] * 32) >> g.hs[c], g.grid_w[c]);
+        const uint32_t y0 = (e.region_groups[1] * 32) >> g.vs[c], y1 = std::min((e.region_groups[3] * 32) >> g.vs[c], g.grid_h[c]);
+        ok = x0 < x1 && y0 < y1;
+        if (!ok) break;
+        t.reg_x0[c] = x0; t.reg_y0[c] = y0; t.reg_w[c] = x1 - x0; t.reg_h[c] = y1 - y0;
+        t.comp_first[c] = npos; npos += t.reg_w[c] * t.reg_h[c];
+      }
+      if (!ok) { jpeg_pixel_results_[i].error = "unsupported: libjpeg-exact decode of a frame whose block grid does not hold the image"; continue; }
+      t.npos = walk ? t.reg_w[0] * t.reg_h[0] : npos;      // (the region's positions only)
+      t.rect_x0 = e.region_rect[0]; t.rect_y0 = e.region_rect[1]; t.rect_w = e.region_rect[2]; t.rect_h = e.region_rect[3];
+    }
     if (t.scale == 1) { table.push_back(t); jpeg_pixel_table_image_.push_back(i); continue; }
     // libjpeg's scaled decode (jdmaster.c): the smallest IDCT is m = 8 / scale; a component whose sampling factors are below the largest takes twice that as long as
     // both of its dimensions still need upsampling by a factor of two — 4:2:0 chroma does, once (n = 2 m: it then has the picture's extent), 4:2:2 chroma does not
@@ -3613,7 +3726,8 @@ size_t Batch::PlanJpegPixels() {
       for (uint32_t k = 0; k < g.count; k++) {
         const JpegPixelImage& t = table[first + k];
         g.max_npos = std::max(g.max_npos, t.npos);
-        g.max_w = std::max(g.max_w, scaled ? t.out_w : t.width); g.max_h = std::max(g.max_h, scaled ? t.out_h : t.height);
+        // (the colour launch is sized by the rectangle it writes, JpegPixelImage::rect_*: threads take pixel pairs (2 t, 2 t + 1) from pair rect_x0 >> 1 on)
+        g.max_w = std::max(g.max_w, 2 * (((t.rect_x0 + t.rect_w + 1) >> 1) - (t.rect_x0 >> 1))); g.max_h = std::max(g.max_h, t.rect_h);
       }
       jpeg_pixel_groups_.push_back(g);
     }
@@ -3621,6 +3735,15 @@ size_t Batch::PlanJpegPixels() {
   group_runs(0, plain, 0);
   group_runs(plain, general, 1);
   group_runs(general, table.size(), kJpegGroupDc);
+  // the groups of the frames that take this decode's HF stage (RunPart 12), and how many of them it decodes
+  hf_by_region_ = jpeg_region;      // (StageBytes: the plan of a libjpeg-exact decode — a pipeline asks for the bytes of the job it has prepared, before any stage runs)
+  hf_groups_total_ = hf_groups_decoded_ = 0;
+  for (size_t u = 0; u < images_.size(); u++) {
+    const FramePlan& p = images_[u]->plan;
+    if (p.modular || EndsBehindLf((int)u)) continue;
+    hf_groups_total_ += p.num_groups;
+    hf_groups_decoded_ += jpeg_region && frames_host_[u].hf_list ? frames_host_[u].hf_count : p.num_groups;
+  }
   return table.size();
 }
 
@@ -3694,7 +3817,7 @@ void Batch::DecodeJpegPixels(void* stream_v) {
   EnqueueJpegPixelTable(stream_v, /*fail_refused=*/false);
   // ---- one entropy decode of the batch (LF stage: JPEG DC, block metadata; HF stage: AC)
   RunPart(stream_v, 1, false);
-  RunPart(stream_v, 3, false);
+  RunPart(stream_v, 12, false);
   // ---- the pixel half: one launch per kernel and group of the table, then the resizes of resized outputs over the f32 pictures the write stage left
   RunPart(stream_v, 9, false);
   RunPart(stream_v, 10, false);

@@ -80,6 +80,10 @@ struct ImageEntry {
                                                    // (OutputSpec::resize_u8: both in u8, for ResizeU8Kernel)
   uint32_t src_w = 0, src_h = 0;                   // (first unit) size of that picture: SetOutput
   bool jpeg_dc_eligible = false;                   // (first unit) SetOutput: the output is libjpeg's 1/8 decode and every component takes the 1 x 1 IDCT (Batch::JpegDcOnly)
+  // (first unit) SetOutput: the output is a crop of a picture the libjpeg-exact decode takes (Batch::JpegRegion) — region_groups: gx0, gy0, gx1, gy1, the rectangle of
+  // 256x256 groups the crop needs; region_rect: x0, y0, w, h of the crop in the stored picture at jpeg_scale (mapped back through the orientation)
+  bool jpeg_region_eligible = false;
+  uint32_t region_groups[4] = {0, 0, 0, 0}, region_rect[4] = {0, 0, 0, 0};
   explicit ImageEntry(std::shared_ptr<ImageShared> s) : shared(std::move(s)), cs(shared->cs), ih(shared->ih) {}
 };
 
@@ -221,6 +225,16 @@ class Batch {
   bool jpeg_dc_only = true;
   void SetJpegDcOnly(bool on) { if (on != jpeg_dc_only) { jpeg_dc_only = on; prepared_ = false; } }      // (another layout of the arenas: the batch is prepared again)
   bool JpegDcOnly(int i) const { return jpeg_dc_only && images_[pub_[i].first_unit]->jpeg_dc_eligible; }
+  // Decoding by region (off by default; DESIGN.md §3 has the rule).  An image whose output DecodeJpegPixels writes, that is not DC-only and whose output carries a crop
+  // needs only the blocks the crop covers, widened to whole MCUs plus one MCU on every side (fancy chroma upsampling reads chroma sample i +- 1, which lies in the
+  // neighbouring chroma block at every scale): with jpeg_region on, the HF stage of DecodeJpegPixels (RunPart 12) and of the pipeline jobs built from its steps decodes
+  // only the 256x256 groups that rectangle touches — Prepare uploads their indices per frame (FrameDev::hf_list) —, the integer IDCT walks only those groups' blocks and
+  // the colour kernels write only the crop's rectangle.  The bytes delivered are those of the decode without the option.  Run, the float decode of the same prepared
+  // batch, decodes every group whatever the option says.  Known from the frame header and the output alone (SetOutput); read by the next Prepare.
+  bool jpeg_region = false;
+  void SetJpegRegion(bool on) { if (on != jpeg_region) { jpeg_region = on; prepared_ = false; } }      // (the lists are Prepare's: the batch is prepared again)
+  // the region image i would be decoded by with jpeg_region on (false: it would be decoded whole — no crop, DC-only, not taken by the libjpeg-exact decode); host only
+  bool JpegRegionOf(int i, uint32_t groups[4]) const;
   void DecodeJpegPixels(void* stream);
   // DecodeJpegPixels in its steps, for callers that order the stages themselves (Pipeline jobs of this kind):
   //   PlanJpegPixels            host only, after Prepare: eligibility, the component grids, the image table and its launch groups; an image that is refused gets its
@@ -304,6 +318,7 @@ class Batch {
   void FinishCfg();
   bool DecodedAtEighth(int unit) const;      // the unit is decoded at 1:8 (OutputSpec::downscale == 8): its decode ends behind the LF post-processing
   bool JpegDcOnlyUnit(int unit) const;       // the unit is the frame of a DC-only image (JpegDcOnly): its decode ends behind the LF decode
+  bool JpegRegionUnit(int unit) const;       // the unit is the frame of an image decoded by region (jpeg_region on, JpegRegionOf): its FrameDev carries a group list
   bool EndsBehindLf(int unit) const { return DecodedAtEighth(unit) || JpegDcOnlyUnit(unit); }   // either: no HF stage, no IDCT, no filters, no coefficient or pixel planes
   // ---- frame tail of complex images
   struct ComplexBufs {      // big-arena offsets of one complex unit ((size_t)-1: not allocated)
@@ -325,6 +340,9 @@ class Batch {
   std::vector<JpegResult> jpeg_results_;       // per image, of the last ReconstructJpegs
   std::vector<JpegPixelResult> jpeg_pixel_results_;   // per image, of the last DecodeJpegPixels
   int64_t jpeg_pixel_images_ = 0, jpeg_pixel_launches_ = 0;   // images the last DecodeJpegPixels wrote; launches of its pixel kernels (two per group of the image table, one per DC-only group)
+  int64_t hf_groups_total_ = 0, hf_groups_decoded_ = 0;       // ... groups of the frames that took its HF stage, and those of them that were decoded (fewer with jpeg_region)
+  bool hf_by_region_ = false;                                  // StageBytes counts by region: a libjpeg-exact decode with jpeg_region was planned (PlanJpegPixels) and no Run has enqueued an HF stage since
+  int max_hf_slots_ = 0;                                       // Prepare: the most stream slots a frame fills in an HF launch that honours the lists (<= max_groups_)
   int64_t jpeg_dc_only_images_ = 0;                            // ... images of it that were written from their DC terms alone (JpegDcOutKernel)
   vec<JpegPixelImage> jpeg_pixel_table_;       // PlanJpegPixels: the image table (host copy; the upload reads it), the image of every entry, the launch groups
   vec<int> jpeg_pixel_table_image_;

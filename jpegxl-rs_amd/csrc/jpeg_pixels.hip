@@ -100,6 +100,9 @@ __device__ __forceinline__ uint32_t ClampU8(int32_t v) { return (uint32_t)min(ma
 //   k) hit banks (8 j + k + 8 r) % 32 in store r — the 8 x 8 form's pattern with lanes missing (column 4 at n = 4, the even columns but 0 at n = 2, all but lane 0 at
 //   n = 1) and with only the first n of its eight stores: a subset of a conflict-free pattern.  Pass 2 reads rows with two ds_read_b128 from the lanes k < n, at the
 //   8 x 8 form's addresses 72 j + 8 k: again a subset.  The entries of a row that pass 1 did not write (column 4; the even columns) are read and not used.
+// Regions (Batch::JpegRegion): the positions of an image are the blocks of im.reg_*[c], the block rectangle of component c that the image's decoded groups cover — the
+// whole grid for an image without a region.  Position -> (c, bx, by) goes through that rectangle; everything behind it — frame block, group, loads, zeroing — is as above.
+// The rectangle is whole groups: every coefficient the HF stage wrote (for the groups of FrameDev::hf_list) is read and zeroed, a skipped group's dwords were never written.
 template <bool kScaled> __device__ __forceinline__ void JpegIdctBody(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table,
                                                                     int32_t (*ws)[kIdctBlocksPerWave * kIdctBlockStride]) {
   const JpegPixelImage& im = table[blockIdx.z];
@@ -112,8 +115,8 @@ template <bool kScaled> __device__ __forceinline__ void JpegIdctBody(const Frame
   uint32_t c = 0, bx = 0, by = 0;
   {
     if (!walk && im.ncomp == 3) c = pos >= im.comp_first[2] ? 2u : pos >= im.comp_first[1] ? 1u : 0u;
-    const uint32_t local = pos - (walk ? 0u : im.comp_first[c]), gw = im.grid_w[c];
-    bx = local % gw; by = local / gw;
+    const uint32_t local = pos - (walk ? 0u : im.comp_first[c]), gw = max(im.reg_w[c], 1u);
+    bx = im.reg_x0[c] + local % gw; by = im.reg_y0[c] + local / gw;
   }
   int32_t* const w = ws[wave] + j * kIdctBlockStride;
   int32_t ycol[8] = {0, 0, 0, 0, 0, 0, 0, 0};               // Y's quantised column k (4:4:4), for the chroma steps
@@ -124,7 +127,7 @@ template <bool kScaled> __device__ __forceinline__ void JpegIdctBody(const Frame
     const uint32_t hs = c ? im.hs : 0u, vs = c ? im.vs : 0u;
     const uint32_t n = kScaled ? im.n[c] : 8u, pitch = kScaled ? im.pitch[c] : im.grid_w[c] * 8u;      // (scale 1: the branches on n below fold away)
     const uint32_t sx = bx << hs, sy = by << vs;            // the frame block that carries this component block
-    const bool live = pos < im.npos && by < im.grid_h[c] && sx < f.bw && sy < f.bh;
+    const bool live = pos < im.npos && bx < im.grid_w[c] && by < im.grid_h[c] && sx < f.bw && sy < f.bh;
     if (live) {
       const size_t o = (size_t)sy * f.bw + sx;
       if (k == 0 && (f.blk_info[o] & 31u) != 0) atomicOr(f.status, (uint32_t)kErrVarblock);
@@ -326,14 +329,15 @@ __device__ __forceinline__ void ChromaPair(const uint8_t* __restrict__ s, uint32
 
 // The end of all three colour-out kernels: the npix (1 or 2) pixels (x0, y), (x0 + 1, y) of a w x h picture from their u8 component samples — grey (ncomp == 1) as
 // they are, else fixed-point YCbCr -> RGB (jdcolor.c) — into the write stage; sample k enters it as (float)k x (1 / 255)
+// (`from`: 1 leaves pixel x0 out — the pair straddles the left edge of the rectangle a region's colour launch is confined to)
 __device__ __forceinline__ void StoreJpegPair(const OutputDesc& od, uint32_t ncomp, uint32_t w, uint32_t h, uint32_t x0, uint32_t y, uint32_t npix, const int32_t lum[2],
-                                              const int32_t cb[2], const int32_t cr[2]) {
+                                              const int32_t cb[2], const int32_t cr[2], uint32_t from = 0) {
   const float k255 = 1.0f / 255;
   if (ncomp == 1) {
-    for (uint32_t i = 0; i < npix; i++) { const float v = (float)lum[i] * k255; StorePixel(od, (int)w, (int)h, (int)(x0 + i), (int)y, v, v, v, 1.0f); }
+    for (uint32_t i = from; i < npix; i++) { const float v = (float)lum[i] * k255; StorePixel(od, (int)w, (int)h, (int)(x0 + i), (int)y, v, v, v, 1.0f); }
     return;
   }
-  for (uint32_t i = 0; i < npix; i++) {
+  for (uint32_t i = from; i < npix; i++) {
     const int32_t u = cb[i] - 128, v = cr[i] - 128;
     const int32_t r = min(max(lum[i] + ((91881 * v + 32768) >> 16), 0), 255);
     const int32_t g = min(max(lum[i] + ((-22554 * u - 46802 * v + 32768) >> 16), 0), 255);
@@ -343,12 +347,17 @@ __device__ __forceinline__ void StoreJpegPair(const OutputDesc& od, uint32_t nco
 }
 
 // A thread takes the output pixels (2 t, 2 t + 1) of a row: they share their chroma position in the subsampled modes.
+// The launch covers the rectangle im.rect_* of the picture and writes no pixel outside it: the whole picture, or — an image decoded by region (Batch::JpegRegion) — the
+// crop mapped to the stored picture, the only part of the intermediate the resample reads.  The edge rules of ChromaPair stay those of the *picture* (cw x ch is the
+// component's extent): at a rectangle's edge inside the picture the neighbouring chroma sample is a real one, decoded with the margin of one MCU the region has.
 __global__ __launch_bounds__(256) void JpegColorOutKernel(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table) {
   const JpegPixelImage& im = table[blockIdx.z];
   const FrameDev& f = frames[im.frame];
-  const uint32_t t = blockIdx.x * 32 + threadIdx.x, x0 = t * 2, y = blockIdx.y * 8 + threadIdx.y;
-  if (x0 >= im.width || y >= im.height || *f.status != 0) return;
-  const uint32_t npix = x0 + 1 < im.width ? 2 : 1;
+  const uint32_t t = (im.rect_x0 >> 1) + blockIdx.x * 32 + threadIdx.x, x0 = t * 2, y = im.rect_y0 + blockIdx.y * 8 + threadIdx.y;
+  const uint32_t xe = min(im.rect_x0 + im.rect_w, im.width), ye = min(im.rect_y0 + im.rect_h, im.height);
+  if (x0 >= xe || y >= ye || *f.status != 0) return;
+  const uint32_t npix = x0 + 1 < xe ? 2 : 1, from = x0 < im.rect_x0 ? 1u : 0u;
+  if (from >= npix) return;
   const uint8_t* __restrict__ yrow = im.plane[0] + (size_t)y * ((size_t)im.grid_w[0] * 8);
   const int32_t lum[2] = {yrow[x0], yrow[x0 + 1]};      // (x0 + 1 is inside the padded grid: its width is a multiple of 8)
   int32_t cb[2] = {128, 128}, cr[2] = {128, 128};
@@ -361,7 +370,7 @@ __global__ __launch_bounds__(256) void JpegColorOutKernel(const FrameDev* __rest
     ChromaPair(im.plane[1], pitch, im.vs, cw, ch, t, y, cb);
     ChromaPair(im.plane[2], pitch, im.vs, cw, ch, t, y, cr);
   }
-  StoreJpegPair(f.od, im.ncomp, im.width, im.height, x0, y, npix, lum, cb, cr);
+  StoreJpegPair(f.od, im.ncomp, im.width, im.height, x0, y, npix, lum, cb, cr, from);
 }
 
 // JpegColorOutKernel for libjpeg's scaled decodes: the picture is im.out_w x im.out_h, component c's plane has im.pitch[c] bytes per row and im.ext_w[c] x im.ext_h[c]
@@ -371,9 +380,12 @@ __global__ __launch_bounds__(256) void JpegColorOutKernel(const FrameDev* __rest
 __global__ __launch_bounds__(256) void JpegColorOutScaledKernel(const FrameDev* __restrict__ frames, const JpegPixelImage* __restrict__ table) {
   const JpegPixelImage& im = table[blockIdx.z];
   const FrameDev& f = frames[im.frame];
-  const uint32_t t = blockIdx.x * 32 + threadIdx.x, x0 = t * 2, y = blockIdx.y * 8 + threadIdx.y;
-  if (x0 >= im.out_w || y >= im.out_h || *f.status != 0) return;
-  const uint32_t npix = x0 + 1 < im.out_w ? 2 : 1;
+  // (confined to im.rect_*, a rectangle of the scaled picture, as JpegColorOutKernel is)
+  const uint32_t t = (im.rect_x0 >> 1) + blockIdx.x * 32 + threadIdx.x, x0 = t * 2, y = im.rect_y0 + blockIdx.y * 8 + threadIdx.y;
+  const uint32_t xe = min(im.rect_x0 + im.rect_w, im.out_w), ye = min(im.rect_y0 + im.rect_h, im.out_h);
+  if (x0 >= xe || y >= ye || *f.status != 0) return;
+  const uint32_t npix = x0 + 1 < xe ? 2 : 1, from = x0 < im.rect_x0 ? 1u : 0u;
+  if (from >= npix) return;
   const uint8_t* __restrict__ yrow = im.plane[0] + (size_t)y * im.pitch[0];
   const int32_t lum[2] = {yrow[x0], npix == 2 ? yrow[x0 + 1] : 0};      // (a row of n = 1 samples per block may end at x0)
   int32_t cb[2] = {128, 128}, cr[2] = {128, 128};
@@ -387,7 +399,7 @@ __global__ __launch_bounds__(256) void JpegColorOutScaledKernel(const FrameDev* 
     ChromaPair(im.plane[1], im.pitch[1], 0, cw, im.ext_h[1], t, y, cb);
     ChromaPair(im.plane[2], im.pitch[1], 0, cw, im.ext_h[1], t, y, cr);
   }
-  StoreJpegPair(f.od, im.ncomp, im.out_w, im.out_h, x0, y, npix, lum, cb, cr);
+  StoreJpegPair(f.od, im.ncomp, im.out_w, im.out_h, x0, y, npix, lum, cb, cr, from);
 }
 
 // libjpeg's 1/8 decode of an image whose components all take the 1 x 1 "IDCT" (grey, 4:4:4, 4:2:2 at scale 8 — JpegPixelImage::n[c] == 1 for every c; the entries of a

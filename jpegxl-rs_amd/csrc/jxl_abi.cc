@@ -1079,6 +1079,7 @@ void JxlHipBatchSetOption(JxlHipBatch* h, const char* name, int value) {
   else if (n == "jpeg_device_progressive") h->b->jpeg_device_progressive = value != 0;   // ... progressive files written by the device as well (jpeg_host_writer wins)
   else if (n == "resize_group_max" && value >= 1 && (uint32_t)value <= kResizeGroupMax) h->b->resize_group_max = (uint32_t)value;   // testing: images per resize launch (applies to the next Prepare)
   else if (n == "jpeg_dc_only") h->b->SetJpegDcOnly(value != 0);   // libjpeg's 1/8 decode from the DC terms alone where every component takes the 1 x 1 IDCT (default), or the general path for every image
+  else if (n == "jpeg_region") h->b->SetJpegRegion(value != 0);   // crops of libjpeg-exact outputs decode only the groups they need (decoder.h jpeg_region); read by the next Prepare
   else if (n == "hf_lanes_per_wave" && value >= 0 && value <= 64) h->b->cfg.hf_lanes_per_wave = value;   // SIMT HF stage: group streams per wavefront (1: the wave-wide kernel where it applies); 0: the throughput packing
 }
 size_t JxlHipBatchDebugRead(JxlHipBatch* h, int index, const char* name, int channel, void* dst, size_t cap, void* s) {
@@ -1130,6 +1131,10 @@ JxlDecoderStatus JxlHipBatchDecodeJpegPixels(JxlHipBatch* h, void* s) { BATCH_TR
 int JxlHipBatchJpegDcOnly(const JxlHipBatch* h, int i) {
   if (!h || i < 0 || (size_t)i >= h->b->size()) { SetLastError("JxlHipBatchJpegDcOnly: no such image"); return 0; }
   return h->b->JpegDcOnly(i) ? 1 : 0;
+}
+int JxlHipBatchJpegRegion(const JxlHipBatch* h, int i, uint32_t groups[4]) {
+  if (!h || !groups || i < 0 || (size_t)i >= h->b->size()) { SetLastError("JxlHipBatchJpegRegion: no such image"); return 0; }
+  return h->b->JpegRegionOf(i, groups) ? 1 : 0;
 }
 JxlDecoderStatus JxlHipBatchJpegPixelsStatus(const JxlHipBatch* h, int i) {
   const Batch::JpegPixelResult* r = h->b->jpeg_pixel_result(i);
@@ -1323,6 +1328,10 @@ JxlDecoderStatus JxlHipPipelineCollectTimes(JxlHipPipeline* h, JxlHipStageTimes*
   BATCH_TRY({ StageTimes st = h->p->CollectTimes(runs); t->lf_ms = st.lf_ms; t->lfpost_ms = st.lfpost_ms; t->hf_ms = st.hf_ms; t->idct_ms = st.idct_ms; t->filter_ms = st.filter_ms; t->out_ms = st.out_ms; t->total_ms = st.total_ms; })
 }
 void JxlHipPipelineStageBytes(JxlHipPipeline* h, uint64_t out[6]) { h->p->StageBytes(out); }
+void JxlHipPipelineSetOption(JxlHipPipeline* h, const char* name, int value) {
+  if (!h || !name) return;
+  if (std::string(name) == "jpeg_region") h->p->SetJpegRegion(value != 0);
+}
 int64_t JxlHipPipelineGetInfo(JxlHipPipeline* h, const char* name) {
   try {
     const std::string n(name ? name : "");

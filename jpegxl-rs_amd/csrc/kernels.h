@@ -143,6 +143,8 @@ struct FrameDev {
                                   // coefficient or pixel planes.  kLfOnlyEighth: the 1:8 decode (OutputSpec::downscale == 8), the output is the LF image, one pixel per 8x8 block,
                                   // written by LfOutputKernel — img_w / img_h / out_stride describe that bw x bh picture.  kLfOnlyJpegDc: libjpeg's 1/8 decode of a JPEG transcode
                                   // whose components all take the 1 x 1 IDCT (OutputSpec::jpeg_scale == 8, not 4:2:0): JpegDcOutKernel writes it from lfq, the DC terms
+  const uint32_t* hf_list;        // libjpeg-exact decode of a crop (Batch::JpegRegion): the hf_count groups its region holds, raster order, each < num_groups (the host asserts it);
+  uint32_t hf_count;              // honoured by the HF launches of that decode alone (LaunchCfg::hf_by_list) — stream slot k decodes group hf_list[k].  nullptr: every group
 };
 constexpr uint32_t kLfOnlyEighth = 1, kLfOnlyJpegDc = 2;
 
@@ -177,6 +179,8 @@ struct LaunchCfg {
   int debug_stop_after = 0;          // testing: the tail of a decode stops after 1 = IDCT, 2 = gaborish, 3 / 4 / 5 = EPF pass 0 / 1 / 2 (stage-by-stage filters only)
   int force_unfused_filters = 0;     // testing: stage-by-stage gaborish / EPF / output kernels even for fusable frames        // testing: run the generic (non-tiled) IDCT kernel even for tile-regular frames
   int hf_block_threads = 512;        // threads per HF-decode block (streams per block = threads / lane_stride_hf)
+  int hf_by_list = 0;                // this HF launch belongs to a libjpeg-exact decode (RunPart 12): frames with FrameDev::hf_list decode the groups of that list only, packed into
+                                     // the first stream slots; every other launch — Run, the float decode of the same prepared batch — decodes every group
   int lds_code_budget = 64 * 1024;   // bytes of LDS the entropy-code tables (cfg, ctx map, alias) may take per block
 };
 
@@ -382,6 +386,11 @@ struct alignas(16) JpegPixelImage {
   uint32_t ncomp;
   uint32_t frame;                        // FrameDev of the image: status word, block info, coefficient planes, OutputDesc
   uint32_t width, height, hs, vs;
+  // what of the image is decoded (Batch::JpegRegion; an image without a region: the whole of it).  reg_*[c]: the block rectangle of component c that JpegIdctBody walks —
+  // whole 256x256 groups of the frame, so that every coefficient the HF stage wrote is read and zeroed; comp_first / npos count its positions.  rect_*: the pixel
+  // rectangle of the stored picture (at `scale`) the colour kernels write — the crop mapped back through the orientation — and nothing outside it
+  uint32_t reg_x0[3], reg_y0[3], reg_w[3], reg_h[3];
+  uint32_t rect_x0, rect_y0, rect_w, rect_h;
   // libjpeg's scaled decode (OutputSpec::jpeg_scale = 2, 4, 8; entries of scale 1 leave all of this 0 apart from `scale`): component c takes the n[c] x n[c] IDCT
   // (jdmaster.c: 8 / scale, twice that for 4:2:0 chroma), its plane has pitch[c] = grid_w[c] x n[c] bytes per row and n[c] rows per block row, of which ext_w[c] x
   // ext_h[c] are real samples; the picture is out_w x out_h = ceil(width / scale) x ceil(height / scale).  chroma_up: 0 = the chroma planes have the picture's

@@ -3319,9 +3319,15 @@ __device__ static const uint8_t kNzCtx[64] = {0,   0,   31,  62,  62,  93,  93, 
 
 // only_prefix: the launch beside the SIMT kernel that takes the frames whose AC code is a prefix (Huffman) code — what cjxl's fast efforts
 // write; symbols are then read bit by bit through the canonical-code tables in global memory (jxl_dev.h ReadSymbol)
-__global__ __launch_bounds__(512) void HfDecodeKernel(const FrameDev* __restrict__ frames, int lane_stride, uint32_t lds_bytes, int only_prefix) {
+// by_list (LaunchCfg::hf_by_list, all three HF kernels): a frame with FrameDev::hf_list decodes the hf_count groups of that list only — stream slot k takes group
+// hf_list[k], slots k >= hf_count are dead exactly as slots >= num_groups are otherwise and never read the list; everything per group (section, varblock list,
+// coefficient planes, LZ77 window, end position) keeps the real group number
+__global__ __launch_bounds__(512) void HfDecodeKernel(const FrameDev* __restrict__ frames, int lane_stride, uint32_t lds_bytes, int only_prefix, uint32_t by_list) {
   const FrameDev& f = frames[blockIdx.y];
   if (f.is_modular || f.lf_only || FrameFailed(f)) return;
+  const uint32_t* const glist = by_list ? f.hf_list : nullptr;
+  const uint32_t nslots = glist ? f.hf_count : f.num_groups;
+  if (glist && (uint32_t)(blockIdx.x * blockDim.x) / (uint32_t)lane_stride >= nslots) return;      // (a listed frame's workgroup without a stream leaves before it stages any table; without a list: as ever)
   const bool pfx = f.ac_code.use_prefix != 0, lz77 = f.ac_code.lz77 != 0;
   const bool slow = pfx || lz77;                                       // symbols through the general reader (tables in global memory)
   if (only_prefix && !slow) return;
@@ -3333,8 +3339,9 @@ __global__ __launch_bounds__(512) void HfDecodeKernel(const FrameDev* __restrict
   __syncthreads();
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
   if (tid % lane_stride) return;
-  const uint32_t g = tid / lane_stride;
-  if (g >= f.num_groups) return;
+  const uint32_t slot = tid / lane_stride;
+  if (slot >= nslots) return;
+  const uint32_t g = glist ? min(LdG(glist + slot), f.num_groups - 1) : slot;
   const uint32_t gx = g % f.xgroups, gy = g / f.xgroups;
   const uint32_t bx0 = gx * 32, by0 = gy * 32;
   const uint32_t gbw = min(32u, f.bw - bx0), gbh = min(32u, f.bh - by0);
@@ -3524,7 +3531,7 @@ template <bool ALL_LDS, typename BR> __device__ __forceinline__ uint32_t HybridS
 }
 
 template <bool ALL_LDS, bool SUB, bool MULTI> __global__ __launch_bounds__(1024) void HfDecodeSimtKernel(const FrameDev* __restrict__ frames, uint32_t lds_bytes, uint32_t lanes, uint32_t lanes_per_wave,
-                                                                                 uint32_t* __restrict__ sync, uint32_t epoch, int prio) {
+                                                                                 uint32_t* __restrict__ sync, uint32_t epoch, int prio, uint32_t by_list) {
   // sync[0]: workgroups of this launch that have started, sync[1]: number of the last HF launch whose workgroups all have
   // (the LF stage of a later batch waits for that before its own workgroups are dispatched, see HeadStartKernel)
   // (a counter per launch — slot 2 + epoch % 16 —: up to three HF launches of different sizes run at the same time, and one shared counter could pass both targets
@@ -3541,7 +3548,10 @@ template <bool ALL_LDS, bool SUB, bool MULTI> __global__ __launch_bounds__(1024)
   bool any_pfx = f.ac_code.use_prefix != 0 || f.ac_code.lz77 != 0;     // (prefix codes or LZ77: the general symbol reader)
   for (uint32_t ps = 1; MULTI && ps < f.num_passes; ps++) any_pfx |= f.passes[ps].code.use_prefix != 0 || f.passes[ps].code.lz77 != 0;
   if (any_pfx && !((SUB && f.subsampled) || (MULTI && f.num_passes > 1))) return;
-  if (blockIdx.x * lanes >= f.num_groups) return;
+  // (by_list: HfDecodeKernel above — the live streams of a frame with a list sit in its first hf_count slots, packed into as few wavefronts and workgroups as they need)
+  const uint32_t* const glist = by_list ? f.hf_list : nullptr;
+  const uint32_t nslots = glist ? f.hf_count : f.num_groups;
+  if (blockIdx.x * lanes >= nslots) return;
   if (prio & 1) __builtin_amdgcn_s_setprio(3);   // few, long, latency-critical waves on the critical path of a batch: issue ahead of co-resident waves
   // per-lane regions sit at the end of the dynamic LDS: `lanes` real ones + one scratch region that all stream-less
   // lanes of the last wavefront share (they only ever write zeros / prefetched words there and read nothing back)
@@ -3559,8 +3569,9 @@ template <bool ALL_LDS, bool SUB, bool MULTI> __global__ __launch_bounds__(1024)
   // runs every path; 16 streams per wavefront skip most of them, and the 2-3 wavefronts a SIMD then holds fill each
   // other's issue gaps (the per-lane LDS regions — the binding resource — do not change).
   const uint32_t slot = (threadIdx.x >> 6) * lanes_per_wave + (threadIdx.x & 63);
-  const uint32_t g = blockIdx.x * lanes + slot;
-  bool dead = (threadIdx.x & 63) >= lanes_per_wave || slot >= lanes || g >= f.num_groups;   // no stream, or a stream that failed in an earlier pass
+  const uint32_t gslot = blockIdx.x * lanes + slot;
+  bool dead = (threadIdx.x & 63) >= lanes_per_wave || slot >= lanes || gslot >= nslots;   // no stream, or a stream that failed in an earlier pass
+  const uint32_t g = dead || !glist ? gslot : min(LdG(glist + gslot), f.num_groups - 1);   // (a dead lane never reads the list, and never uses g: gsafe below)
   const uint32_t lane_slot = dead ? lanes : slot;
   const uint32_t nz_base = lane_off + lane_slot * 96;
   const uint32_t wend_all = (uint32_t)((f.cs_size + 3) >> 2);   // 16-byte loads stay inside the codestream buffer
@@ -3773,10 +3784,12 @@ template <bool ALL_LDS, bool SUB, bool MULTI> __global__ __launch_bounds__(1024)
 constexpr uint32_t kHwOrdOff = (kSimtBcmOff + (uint32_t)sizeof(BlockCtxDev) + 15) & ~15u;   // 39 x 64 u16: heads of the order tables
 constexpr uint32_t kHwCodeOff = kHwOrdOff + 39 * 128;
 constexpr uint32_t kHwWaves = 4;
-__global__ __launch_bounds__(64 * kHwWaves) void HfDecodeWaveKernel(const FrameDev* __restrict__ frames, uint32_t lds_bytes) {
+__global__ __launch_bounds__(64 * kHwWaves) void HfDecodeWaveKernel(const FrameDev* __restrict__ frames, uint32_t lds_bytes, uint32_t by_list) {
   const FrameDev& f = frames[blockIdx.y];
   if (f.is_modular || f.lf_only || FrameFailed(f)) return;
-  if (blockIdx.x * kHwWaves >= f.num_groups) return;
+  const uint32_t* const glist = by_list ? f.hf_list : nullptr;      // (by_list: HfDecodeKernel above — a wavefront is a stream slot here)
+  const uint32_t nslots = glist ? f.hf_count : f.num_groups;
+  if (blockIdx.x * kHwWaves >= nslots) return;
   const PassDev& pd = f.passes[0];
   FastCode code;
   if (threadIdx.x < 64) { StS<uint8_t>(threadIdx.x, kNzCtx[threadIdx.x]); StS<uint8_t>(64 + threadIdx.x, kFreqCtx[threadIdx.x]); }
@@ -3788,8 +3801,9 @@ __global__ __launch_bounds__(64 * kHwWaves) void HfDecodeWaveKernel(const FrameD
   StageCode(pd.code, code, kHwCodeOff, lds_bytes > kHwCodeOff ? lds_bytes - kHwCodeOff : 0, /*with_ctx_map=*/true, /*with_wide=*/true, /*with_plain=*/false);
   __syncthreads();
   if (code.wide_off == kNotInLds || code.ctx_map_off == kNotInLds || code.cfg_off == kNotInLds) { if (threadIdx.x == 0) SetError(f, kErrUnsupported); return; }
-  const uint32_t lane = threadIdx.x & 63, g = blockIdx.x * kHwWaves + (threadIdx.x >> 6);
-  if (g >= f.num_groups) return;
+  const uint32_t lane = threadIdx.x & 63, gslot = blockIdx.x * kHwWaves + (threadIdx.x >> 6);
+  if (gslot >= nslots) return;
+  const uint32_t g = glist ? Uniform(min(LdG(glist + gslot), f.num_groups - 1)) : gslot;
   __builtin_amdgcn_s_setprio(3);
   constexpr uint32_t oMap = kSimtBcmOff + offsetof(BlockCtxDev, ctx_map);
   const uint32_t n_qf = Uniform(LdS<uint32_t>(kSimtBcmOff + offsetof(BlockCtxDev, n_qf_thr)));
@@ -6236,6 +6250,8 @@ void LaunchHfDecode(const FrameDev* frames, int nframes, int max_groups, const L
   LaunchTrace tr;
   if (!trace) trace = &tr;
   trace->hf_variant = 0;
+  // (cfg.hf_by_list: max_groups is then the largest number of stream slots a frame of the launch fills — its list's length, or its groups — and sizes every grid below)
+  const uint32_t by_list = cfg.hf_by_list ? 1u : 0u;
   // latency mode (one stream per wavefront asked for) with plain frames whose AC code fits the LDS in the wide layout: the wave-wide kernel
   static const bool no_wave_hf = getenv("JXL_HIP_NO_WAVE_HF") != nullptr;
   if (!no_wave_hf && cfg.lane_stride_hf == 1 && cfg.hf_lanes_per_wave == 1 && !cfg.any_subsampled && !cfg.any_multipass && !cfg.any_prefix_ac && !cfg.skip_hf && cfg.max_passes == 0) {
@@ -6244,7 +6260,7 @@ void LaunchHfDecode(const FrameDev* frames, int nframes, int max_groups, const L
     if (lds <= 150 * 1024) {
       static bool attr = false;
       if (!attr) { SetMaxDynamicLds((const void*)HfDecodeWaveKernel, 160 * 1024 - 2048, "HfDecodeWaveKernel"); attr = true; }
-      hipLaunchKernelGGL(HfDecodeWaveKernel, dim3(DivUp(max_groups, (int)kHwWaves), nframes), dim3(64 * kHwWaves), lds, (hipStream_t)stream, frames, lds);
+      hipLaunchKernelGGL(HfDecodeWaveKernel, dim3(DivUp(max_groups, (int)kHwWaves), nframes), dim3(64 * kHwWaves), lds, (hipStream_t)stream, frames, lds, by_list);
       trace->hf_variant = kHfVarWave;
       return;
     }
@@ -6294,14 +6310,14 @@ void LaunchHfDecode(const FrameDev* frames, int nframes, int max_groups, const L
     // the lock-step loop is paid by all ~37 000 iterations of a frame); everything else takes the general one
     static const int hf_prio = getenv("JXL_HIP_HF_PRIO") ? atoi(getenv("JXL_HIP_HF_PRIO")) : 1;
     const bool plain = all_lds && !cfg.any_subsampled && !cfg.any_multipass;
-    if (plain) hipLaunchKernelGGL((HfDecodeSimtKernel<true, false, false>), grid, dim3(threads), lds, (hipStream_t)stream, frames, lds, lanes, lpw, sync, epoch, hf_prio);
-    else if (all_lds) hipLaunchKernelGGL((HfDecodeSimtKernel<true, true, true>), grid, dim3(threads), lds, (hipStream_t)stream, frames, lds, lanes, lpw, sync, epoch, hf_prio);
-    else hipLaunchKernelGGL((HfDecodeSimtKernel<false, true, true>), grid, dim3(threads), lds, (hipStream_t)stream, frames, lds, lanes, lpw, sync, epoch, hf_prio);
+    if (plain) hipLaunchKernelGGL((HfDecodeSimtKernel<true, false, false>), grid, dim3(threads), lds, (hipStream_t)stream, frames, lds, lanes, lpw, sync, epoch, hf_prio, by_list);
+    else if (all_lds) hipLaunchKernelGGL((HfDecodeSimtKernel<true, true, true>), grid, dim3(threads), lds, (hipStream_t)stream, frames, lds, lanes, lpw, sync, epoch, hf_prio, by_list);
+    else hipLaunchKernelGGL((HfDecodeSimtKernel<false, true, true>), grid, dim3(threads), lds, (hipStream_t)stream, frames, lds, lanes, lpw, sync, epoch, hf_prio, by_list);
     trace->hf_variant = plain ? kHfVarSimtPlain : all_lds ? kHfVarSimtAllLds : kHfVarSimtGlobal;
     if (cfg.any_prefix_ac) {   // frames with a prefix-coded AC stream: one group stream per wavefront lane 0, tables in global memory
       static bool attr2 = false;
       if (!attr2) { SetMaxDynamicLds((const void*)HfDecodeKernel, 160 * 1024 - 2048, "HfDecodeKernel"); attr2 = true; }
-      hipLaunchKernelGGL(HfDecodeKernel, dim3(DivUp(max_groups, 512 / 64), nframes), dim3(512), 128, (hipStream_t)stream, frames, 64, 128u, 1);
+      hipLaunchKernelGGL(HfDecodeKernel, dim3(DivUp(max_groups, 512 / 64), nframes), dim3(512), 128, (hipStream_t)stream, frames, 64, 128u, 1, by_list);
       trace->hf_variant |= kHfVarPrefix;
     }
     return;
@@ -6312,7 +6328,7 @@ void LaunchHfDecode(const FrameDev* frames, int nframes, int max_groups, const L
   static bool attr_set = false;
   if (!attr_set) { SetMaxDynamicLds((const void*)HfDecodeKernel, 160 * 1024 - 2048, "HfDecodeKernel"); attr_set = true; }
   dim3 grid(DivUp(max_groups, per_block), nframes);
-  hipLaunchKernelGGL(HfDecodeKernel, grid, dim3(threads), lds_bytes, (hipStream_t)stream, frames, cfg.lane_stride_hf, lds_bytes, 0);
+  hipLaunchKernelGGL(HfDecodeKernel, grid, dim3(threads), lds_bytes, (hipStream_t)stream, frames, cfg.lane_stride_hf, lds_bytes, 0, by_list);
   trace->hf_variant = kHfVarLaneStride;
 }
 // JXL_HIP_DEBUG_SYNC: names the launch that the runtime rejected (a rejected launch leaves an error code behind that the next runtime call of the process would report)

@@ -178,6 +178,7 @@ int64_t Pipeline::Submit(const uint8_t* const* datas, const size_t* sizes, int n
   job->spec = spec; job->spec.device_ptr = nullptr;
   if (each) job->each.assign(each, each + n);
   job->kind = jpeg_pixels ? kJpegPixels : kPlain;
+  job->jpeg_region = jpeg_pixels && jpeg_region_.load();      // (the option as it stands at the submit)
   return Enqueue(job, n);
 }
 
@@ -272,6 +273,7 @@ void Pipeline::PrepareJob(Job* j, int worker) {
   try {
     HIP_CHECK(hipSetDevice(device_));
     bt.Reset();
+    bt.SetJpegRegion(j->kind == kJpegPixels && j->jpeg_region);      // (before the outputs are set; the slot's batch serves jobs of every kind)
     vec<int> index;
     std::vector<std::string> errors;
     // (a 1:8 job needs the LF part of a stream only; what that decode does not take fails alone, here.  So does a libjpeg-exact job at scale 1/8 for its DC-only images,
@@ -375,6 +377,7 @@ void Pipeline::PrepareJob(Job* j, int worker) {
       std::lock_guard<std::mutex> lock(mu_);
       last_info_["jpeg_pixel_images"] = (int64_t)jpeg_table;
       last_info_["jpeg_pixel_launches"] = j->kind == kJpegPixels ? (int64_t)bt.jpeg_pixel_launch_count() : 0;
+      last_info_["hf_groups_total"] = j->kind == kJpegPixels ? bt.Info("hf_groups_total") : 0; last_info_["hf_groups_decoded"] = j->kind == kJpegPixels ? bt.Info("hf_groups_decoded") : 0;
       want_big_ = std::max(want_big_, bt.big_bytes_wanted()); want_coef_ = std::max(want_coef_, bt.coef_bytes_wanted());
       if (!bt.uses_shared_big() || !bt.uses_shared_coef()) private_plane_jobs_++;
       bt.StageBytes(last_stage_bytes_);
@@ -428,7 +431,8 @@ void Pipeline::IssueHf(Job* j) {
     StreamWait(hs, s.lf_done);
     // the coefficient set's previous user has consumed (and zeroed) it: its tail was issued before this call (tails go out in order, HF stages at most hf_streams ahead)
     if (j->ticket >= ncoef_) StreamWait(hs, slots_[(size_t)((j->ticket - ncoef_) % nbuf_)]->idct_done);
-    s.batch->RunPart(hs, 3, opt_.timed != 0 && j->kind != kJpegFiles);
+    // (a libjpeg-exact job: part 12, the HF stage that honours the group lists of images decoded by region)
+    s.batch->RunPart(hs, j->kind == kJpegPixels ? 12 : 3, opt_.timed != 0 && j->kind != kJpegFiles);
     Record(s.hf_done, hs);
   } catch (const std::exception& e) { j->job_error = e.what(); }
 }

@@ -86,6 +86,8 @@ class Pipeline {
   void ResetClock();                               // end_ms of later jobs counts from here (call on an idle pipeline)
   StageTimes CollectTimes(int* runs);              // per-stage HIP-event sums over all jobs since the last call (options.timed)
   void StageBytes(uint64_t out[6]);                // algorithmic bytes per stage of the job prepared last
+  // libjpeg-exact jobs submitted from now on decode crops by region (Batch::jpeg_region): only the groups a crop needs; Info "hf_groups_total" / "hf_groups_decoded" of the job prepared last
+  void SetJpegRegion(bool on) { jpeg_region_.store(on); }
   int64_t Info(const char* name);                  // "device_bytes", "jobs", "shared_big_bytes", "shared_coef_bytes", "private_plane_jobs", "jpeg_pixel_images", "jpeg_pixel_launches" (of the job prepared or finished last), "jpeg_dc_only_images" (of the job finished last), "jpeg_device_images", "jpeg_host_images", "jpeg_device_progressive_images", "jpeg_gather_launches" (of the job finished last; 0 unless it was a reconstruction job), batch infos of the last job ("hf_nonzeros", "lf_simt_frames" ...)
   double prepare_seconds_total() const { return prepare_s_total_; }
   int64_t prepared_jobs() const { return prepared_jobs_; }
@@ -104,6 +106,7 @@ class Pipeline {
     std::vector<OutputSpec> each;              // per image, when the job was submitted with specs of its own (empty: `spec` for all)
     Kind kind = kPlain;
     uint32_t jpeg_flags = 0;                   // reconstruction jobs: kPipelineJpeg*
+    bool jpeg_region = false;                  // libjpeg-exact jobs: crops are decoded by region (SetJpegRegion as it stood at the submit; Batch::jpeg_region)
     std::vector<vec<uint8_t>> jpeg_files;      // reconstruction jobs, from the harvest on: image i's file (empty: none)
     int64_t jpeg_counts[4] = {0, 0, 0, 0};     // ... device images, host images, device progressive images, gather launches
     bool collected = false;                    // WaitJpegs has returned: the files can be handed out
@@ -161,6 +164,7 @@ class Pipeline {
   std::thread issuer_;
   double prepare_s_total_ = 0; int64_t prepared_jobs_ = 0;
   uint64_t last_stage_bytes_[6] = {0, 0, 0, 0, 0, 0};
+  std::atomic<bool> jpeg_region_{false};
   std::map<std::string, int64_t> last_info_;
 };
 

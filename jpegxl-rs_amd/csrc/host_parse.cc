@@ -1465,7 +1465,8 @@ void ParseHfGlobal(const Codestream& cs, const ImageHeader& ih, uint64_t bitpos,
           for (size_t i = 0; i < size; i++) temp[i] = (uint32_t)i;
           vec<uint16_t>& o = p->custom_order[(size_t)ps * 39 + b * 3 + c];
           o.resize(size);
-          for (size_t i = 0; i < size; i++) { o[i] = natural[temp[lehmer[i]]]; temp.erase(temp.begin() + lehmer[i]); }
+          for (size_t i = 0; i < end; i++) { o[i] = natural[temp[lehmer[i]]]; temp.erase(temp.begin() + lehmer[i]); }
+          for (size_t i = end; i < size; i++) o[i] = natural[temp[i - end]];   // (the code is zero from `end` on: what is left, in order — the 65536-entry orders stay cheap)
         }
       }
       sr.CheckFinal();

@@ -397,8 +397,20 @@ inline void ReadHfGlobal(BitReader& br, Frame& f) {
   f.num_hf_presets = 1 + br.u(CeilLog2(f.fh.num_groups));
   // per pass: coefficient orders + histograms (dec_frame.cc ProcessACGlobal, coeff_order.cc DecodeCoeffOrders)
   f.pass.resize(f.fh.passes.num_passes);
+  // dump (tests/test_vardct_coefficient_formulas.py): "custom_orders" = per pass [used_orders, then per set bucket and channel: size, order[0 .. size)];
+  // "block_ctx_map" = [num_ctxs, then per X / Y / B: count, thresholds, then count, quantiser thresholds, then count, map]; "hf_trace" (ReadPassGroup) = per
+  // section [pass, group, preset, tokens, then (context, value as read) per token]
+  if (f.dump) {
+    f.dump->ints["custom_orders"].clear(); f.dump->ints["hf_trace"].clear();
+    std::vector<int32_t>& bm = f.dump->ints["block_ctx_map"]; bm.clear();
+    bm.push_back(f.bcm.num_ctxs);
+    for (int j : {0, 1, 2}) { bm.push_back((int32_t)f.bcm.lf_thresholds[j].size()); for (int32_t t : f.bcm.lf_thresholds[j]) bm.push_back(t); }
+    bm.push_back((int32_t)f.bcm.qf_thresholds.size()); for (uint32_t t : f.bcm.qf_thresholds) bm.push_back((int32_t)t);
+    bm.push_back((int32_t)f.bcm.ctx_map.size()); for (uint8_t m : f.bcm.ctx_map) bm.push_back(m);
+  }
   for (auto& ps : f.pass) {
     uint32_t used_orders = U32(br, Val(0x5F), Val(0x13), Val(0), Bits(13));
+    if (f.dump) f.dump->ints["custom_orders"].push_back((int32_t)used_orders);
     ps.order.assign(13 * 3, {});
     EntropyCode oc; SymbolReader osr;
     if (used_orders) { ReadEntropyCode(br, 8, oc); osr.Init(&oc, br); }
@@ -412,6 +424,7 @@ inline void ReadHfGlobal(BitReader& br, Frame& f) {
           std::vector<uint32_t>& o = ps.order[b * 3 + c];
           o.resize(size);
           for (size_t i = 0; i < size; i++) o[i] = natural[perm[i]];
+          if (f.dump) { std::vector<int32_t>& d = f.dump->ints["custom_orders"]; d.push_back((int32_t)size); d.insert(d.end(), o.begin(), o.end()); }
         } else {
           ps.order[b * 3 + c] = natural;
         }
@@ -449,6 +462,8 @@ inline void ReadPassGroup(BitReader& br, Frame& f, int pass_idx, int g) {
     const size_t ctx_offset = (size_t)495 * nctx * preset;
     SymbolReader sr;
     sr.Init(&ps.code, br);
+    std::vector<int32_t> trace;
+    std::vector<int32_t>* tr = f.dump ? &trace : nullptr;
     const uint32_t shift = (pass_idx + 1 < (int)f.fh.passes.num_passes) ? f.fh.passes.shift[pass_idx] : 0;
     std::vector<uint8_t> nzmap[3];
     for (auto& v : nzmap) v.assign(32 * 32, 0);
@@ -494,6 +509,7 @@ inline void ReadPassGroup(BitReader& br, Frame& f, int pass_idx, int g) {
           int pc = pred > 64 ? 64 : pred;
           size_t nz_ctx = ctx_offset + (pc < 8 ? (size_t)block_ctx + (size_t)nctx * pc : (size_t)block_ctx + (size_t)nctx * (4 + pc / 2));
           uint32_t nzeros = sr.Read(br, (int)nz_ctx);
+          if (tr) { tr->push_back((int32_t)nz_ctx); tr->push_back((int32_t)nzeros); }
           if (nzeros + covered > (uint32_t)size) JXLO_FAIL("nzeros too large");
           uint8_t nzm = (uint8_t)((nzeros + covered - 1) >> log2cov);
           if (f.subsampled) nzmap[c][sby * 32 + sbx] = nzm;
@@ -507,6 +523,7 @@ inline void ReadPassGroup(BitReader& br, Frame& f, int pass_idx, int g) {
             uint32_t kk = (uint32_t)k >> log2cov;
             size_t ctx = histo_offset + (kCoeffNumNonzeroContext[nzl] + kCoeffFreqContext[kk]) * 2 + prev;
             uint32_t u = sr.Read(br, (int)ctx);
+            if (tr) { tr->push_back((int32_t)ctx); tr->push_back((int32_t)u); }
             int32_t v = UnpackSigned(u);
             prev = u != 0;
             nzeros -= prev;
@@ -518,6 +535,11 @@ inline void ReadPassGroup(BitReader& br, Frame& f, int pass_idx, int g) {
       }
     }
     if (!sr.CheckFinal()) JXLO_FAIL("AC group ANS final state");
+    if (tr) {
+      std::vector<int32_t>& d = f.dump->ints["hf_trace"];
+      d.push_back(pass_idx); d.push_back(g); d.push_back((int32_t)preset); d.push_back((int32_t)(trace.size() / 2));
+      d.insert(d.end(), trace.begin(), trace.end());
+    }
     f.tokens_hf += sr.tokens;
   }
   // modular channels of this group

@@ -573,10 +573,11 @@ inline void ReadPermutation(BitReader& br, SymbolReader& sr, size_t skip, size_t
   std::vector<uint32_t> temp(size);
   for (size_t i = 0; i < size; i++) temp[i] = (uint32_t)i;
   perm.resize(size);
-  for (size_t i = 0; i < size; i++) {
+  for (size_t i = 0; i < end; i++) {
     perm[i] = temp[lehmer[i]];
     temp.erase(temp.begin() + lehmer[i]);
   }
+  for (size_t i = end; i < size; i++) perm[i] = temp[i - end];   // (the code is zero from `end` on: what is left, in order)
 }
 
 struct Section { size_t offset, size; };

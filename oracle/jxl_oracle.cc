@@ -624,6 +624,8 @@ int jxlo_get_ints(jxlo_handle* h, const char* name, const int32_t** p, size_t* n
 }
 // standalone stage entry points for kernel-level parity tests
 void jxlo_idct(int strategy, const float* coeffs, float* out, int stride) { InverseTransform(strategy, coeffs, out, stride); }
+// the two 64-entry tables of the coefficient context model as the oracle holds them (tests assert their typed copy against these)
+void jxlo_coeff_context_tables(uint16_t* freq, uint16_t* num_nonzero) { memcpy(freq, kCoeffFreqContext, 128); memcpy(num_nonzero, kCoeffNumNonzeroContext, 128); }
 void jxlo_natural_order(int strategy, uint32_t* out) { auto v = NaturalCoeffOrder(strategy); memcpy(out, v.data(), v.size() * 4); }
 float jxlo_srgb(float v) { return LinearToSRGB(v); }
 // recalled tables / approximations exposed to their self-consistency tests

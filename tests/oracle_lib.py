@@ -120,6 +120,42 @@ class Decoded:
         return np.ctypeslib.as_array(p, shape=(n.value,)).copy()
 
 
+def hf_trace(d: Decoded):
+    """{(pass, group): (preset, contexts, values)} — the (context, value as read) pairs of every PassGroup section of the last VarDCT frame (dump=True)"""
+    v, at, out = d.ints("hf_trace"), 0, {}
+    while at < v.size:
+        ps, g, preset, n = (int(x) for x in v[at:at + 4])
+        pairs = v[at + 4:at + 4 + 2 * n].reshape(n, 2)
+        out[(ps, g)] = (preset, pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int64) & 0xFFFFFFFF)
+        at += 4 + 2 * n
+    return out
+
+
+def custom_orders(d: Decoded):
+    """per pass (used_orders, {(bucket, channel X / Y / B): order}) as HfGlobal gave them (order[k] = coefficient position of scan position k)"""
+    v, at, out = d.ints("custom_orders"), 0, []
+    while at < v.size:
+        used, at, orders = int(v[at]), at + 1, {}
+        for b in range(13):
+            if used >> b & 1:
+                for c in range(3):
+                    n = int(v[at])
+                    orders[(b, c)] = v[at + 1:at + 1 + n].astype(np.int64)
+                    at += 1 + n
+        out.append((used, orders))
+    return out
+
+
+def block_ctx_map(d: Decoded):
+    """(nctx, [lf thresholds X, Y, B], quantiser thresholds, map) of the last VarDCT frame"""
+    v = [int(x) for x in d.ints("block_ctx_map")]
+    nctx, at, lists = v[0], 1, []
+    for _ in range(5):
+        lists.append(v[at + 1:at + 1 + v[at]])
+        at += 1 + v[at]
+    return nctx, lists[:3], lists[3], lists[4]
+
+
 def decode(data: bytes, dump=False, dc_only=False, max_passes=-1, allow_truncated=False) -> Decoded:
     """dc_only: the image as JxlDecoderFlushImage shows it at the kDC progression step — LF image + HF metadata decoded, every AC coefficient zero; the
     PassGroup sections are not read (the input may end in them).  max_passes: a later progression step — only that many passes of every group.
@@ -141,6 +177,15 @@ def decode(data: bytes, dump=False, dc_only=False, max_passes=-1, allow_truncate
         finally:
             L.jxlo_set_dc_only(0)
     return Decoded(data, dump)
+
+
+def coeff_context_tables():
+    """(kCoeffFreqContext, kCoeffNumNonzeroContext) as the oracle holds them, 64 entries each"""
+    L = lib()
+    L.jxlo_coeff_context_tables.argtypes = [C.c_void_p, C.c_void_p]
+    f, n = np.zeros(64, np.uint16), np.zeros(64, np.uint16)
+    L.jxlo_coeff_context_tables(f.ctypes.data, n.ctypes.data)
+    return f.astype(np.int64), n.astype(np.int64)
 
 
 def set_render_spotcolors(on=True):

@@ -74,13 +74,15 @@ def _take(out, n):
     return data
 
 
-def encode_vardct(rgb, seed=1, distance=1.0, epf_iters=1, gab=1, strategy_mix=1, out_bits=8, hdr=0, skip_lf_smoothing=0, orientation=1, alpha=None, upsampling=1, custom_up_weights=0, num_passes=1, permute_toc=0, pass_ds=0):
+def encode_vardct(rgb, seed=1, distance=1.0, epf_iters=1, gab=1, strategy_mix=1, out_bits=8, hdr=0, skip_lf_smoothing=0, orientation=1, alpha=None, upsampling=1, custom_up_weights=0, num_passes=1, permute_toc=0, pass_ds=0, custom_orders=0):
     """rgb: (h,w,3) uint8 sRGB, or float32 linear when hdr=1; alpha: optional (h,w) uint8 plane carried as a lossless
-    extra channel.  Returns codestream bytes."""
+    extra channel.  custom_orders=1: every pass carries coefficient orders of its own (per bucket in use and channel: positions sorted by how
+    often they are non-zero in that pass, as libjxl's encoder does); 0: natural orders.  Returns codestream bytes."""
     L = lib()
     h, w = rgb.shape[:2]
     p = Params(seed=seed, distance=distance, epf_iters=epf_iters, gab=gab, strategy_mix=strategy_mix, out_bits=out_bits,
-               hdr=hdr, skip_lf_smoothing=skip_lf_smoothing, orientation=orientation, upsampling=upsampling, custom_up_weights=custom_up_weights, num_passes=num_passes, permute_toc=permute_toc, pass_ds=pass_ds)
+               hdr=hdr, skip_lf_smoothing=skip_lf_smoothing, orientation=orientation, upsampling=upsampling, custom_up_weights=custom_up_weights, num_passes=num_passes, permute_toc=permute_toc, pass_ds=pass_ds,
+               custom_orders=custom_orders)
     out = C.c_void_p(); n = C.c_size_t()
     alpha_arr = None if alpha is None else np.ascontiguousarray(alpha, dtype=np.uint8)
     al = None if alpha_arr is None else alpha_arr.ctypes.data
@@ -234,6 +236,80 @@ def encode_modular_scripted(w, h, planes, bits=8, nchan=3, has_alpha=False, grou
                                    ptrs, dims, len(keep), C.byref(out), C.byref(n)):
         raise RuntimeError(L.jxlsynth_last_error().decode())
     return _take(out, n)
+
+
+ORDER_BUCKET_SIZE = (64, 64, 256, 1024, 128, 256, 512, 4096, 2048, 16384, 8192, 65536, 32768)
+
+
+def encode_vardct_scripted(w, h, varblocks, lfq, tokens, ctx_map, block_ctx=None, shifts=(), orders=None, num_presets=1, presets=None, pseudo_counts=None):
+    """Scripted VarDCT coefficient stream (tools/synth_script_hf.h): one XYB VarDCT frame without restoration filters or image features whose PassGroup sections
+    carry exactly the (context, value) pairs given.  The writer computes no context, no coefficient order and no count.
+    varblocks: (by, bx, strategy, hf_mul) each, hf_mul 1..256; they must tile the block grid and none may cross a 256x256 group.
+    lfq: three int arrays (bh, bw), the quantised LF of X, Y, B.
+    tokens: per pass a list with, per group, a pair (contexts, values) of equally long arrays; contexts are final, in [0, 495 * nctx * num_presets).
+    ctx_map: cluster of every context (495 * nctx * num_presets entries, every cluster 0 .. max used).
+    block_ctx: None (the default block context map, 15 block contexts) or (lf_thr_x, lf_thr_y, lf_thr_b, qf_thr, map, nctx).
+    shifts: the shift of every pass but the last (len + 1 passes, at most 3).
+    orders: per pass a dict bucket -> (perm_x, perm_y, perm_b), full permutations of 0 .. ORDER_BUCKET_SIZE[bucket] - 1 whose first size / 64 entries stay put;
+      buckets not named use the natural order.
+    presets: per pass a list with every group's histogram set (default all 0).
+    pseudo_counts: per cluster a list of (symbol, count) that enter the cluster's histogram without being coded.
+    set_code_shape(which="ac") (alias-table size and hybrid-uint configurations; the clustering is the caller's), set_prefix and set_lz77_ac apply.
+    -> (codestream bytes, distributions (passes, clusters, 256): the normalised frequencies of every cluster's code)"""
+    L = lib()
+    num_passes = len(shifts) + 1
+    assert 1 <= num_passes <= 3 and len(tokens) == num_passes
+    ngroups = ((w + 255) // 256) * ((h + 255) // 256)
+    bw, bh = (w + 7) // 8, (h + 7) // 8
+
+    def i32(v):
+        return np.ascontiguousarray(np.asarray(v, dtype=np.int64).reshape(-1), dtype=np.int32)
+
+    def ptr(a):
+        return a.ctypes.data_as(C.c_void_p)
+    ctx_map = np.asarray(ctx_map, dtype=np.int64)
+    nclusters = int(ctx_map.max()) + 1
+    nctx = 0 if block_ctx is None else int(block_ctx[5])
+    assert ctx_map.size == 495 * (nctx or 15) * num_presets, ctx_map.size
+    hdr = i32([w, h, len(varblocks), nctx, num_passes, shifts[0] if num_passes > 1 else 0, shifts[1] if num_passes > 2 else 0, num_presets, nclusters])
+    vbs = i32(varblocks)
+    planes = [i32(p) for p in lfq]
+    assert all(p.size == bw * bh for p in planes)
+    lfq_ptrs = (C.c_void_p * 3)(*[p.ctypes.data for p in planes])
+    bcm = i32([0])
+    if block_ctx is not None:
+        tx, ty, tb, tq, m, _ = block_ctx
+        bcm = i32([len(tx), *tx, len(ty), *ty, len(tb), *tb, len(tq), *tq, len(m), *m])
+    flat = []
+    for ps in range(num_passes):
+        o = (orders[ps] if orders else None) or {}
+        flat.append(np.array([sum(1 << b for b in o)], np.int64))
+        for b in sorted(o):
+            assert len(o[b]) == 3
+            for perm in o[b]:
+                perm = np.asarray(perm, dtype=np.int64)
+                assert perm.shape == (ORDER_BUCKET_SIZE[b],)
+                flat.append(perm)
+    ords = i32(np.concatenate(flat))
+    pre = i32(presets if presets is not None else np.zeros((num_passes, ngroups)))
+    assert pre.size == num_passes * ngroups and all(len(t) == ngroups for t in tokens)
+    counts = i32([len(tokens[ps][g][0]) for ps in range(num_passes) for g in range(ngroups)])
+    ctxs = np.ascontiguousarray(np.concatenate([np.asarray(tokens[ps][g][0], dtype=np.int64) for ps in range(num_passes) for g in range(ngroups)] + [np.zeros(1, np.int64)]), dtype=np.uint32)
+    vals = np.ascontiguousarray(np.concatenate([np.asarray(tokens[ps][g][1], dtype=np.int64) for ps in range(num_passes) for g in range(ngroups)] + [np.zeros(1, np.int64)]), dtype=np.uint32)
+    assert ctxs.size == vals.size == int(counts.sum()) + 1
+    pc = []
+    for cl in range(nclusters):
+        items = pseudo_counts[cl] if pseudo_counts is not None and cl < len(pseudo_counts) else []
+        pc += [len(items)] + [int(v) for it in items for v in it]
+    pseudo = i32(pc)
+    dist = np.zeros((num_passes, nclusters, 256), np.int32)
+    cm = i32(ctx_map)
+    out = C.c_void_p(); n = C.c_size_t()
+    L.jxlsynth_vardct_scripted.argtypes = [C.c_void_p] * 2 + [C.POINTER(C.c_void_p)] + [C.c_void_p] * 9 + [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    if L.jxlsynth_vardct_scripted(ptr(hdr), ptr(vbs), lfq_ptrs, ptr(bcm), ptr(ords), ptr(pre), ptr(counts), ptr(ctxs), ptr(vals), ptr(cm), ptr(pseudo), ptr(dist),
+                                  C.byref(out), C.byref(n)):
+        raise RuntimeError(L.jxlsynth_last_error().decode())
+    return _take(out, n), dist
 
 
 def lf_residuals(planes, shape):

@@ -79,7 +79,8 @@ struct Params {
   int out_bits = 8;       // 8 | 16 | 32 (float, linear, intensity_target 1000 when hdr)
   int hdr = 0;
   int skip_lf_smoothing = 0;
-  int custom_orders = 0;  // reserved
+  int custom_orders = 0;  // VarDCT: 1 = every pass carries coefficient orders of its own, sorted by how often each position is non-zero in that pass (HfGlobal used_orders)
+  int pass_shift[2] = {-1, -1};   // >= 0: the shift of pass 0 / 1 in the frame header instead of PassShift's (scripted streams)
   int orientation = 1;    // EXIF-style 1..8, written to the image header
   int upsampling = 1;     // 1 | 2 | 4 | 8: the frame is coded at 1/upsampling of the image size
   int custom_up_weights = 0;  // 1: the image header carries explicit upsampling weights (required for 4x / 8x here)
@@ -784,7 +785,7 @@ static void WriteFrameHeader(BitWriter& w, const Params& p, bool modular, bool x
     if (np != 1) {
       const int nds = (modular ? p.mod_ds : p.pass_ds) ? np - 1 : 0;
       w.put((uint32_t)nds, 2);                             // num_downsample (0 .. 2)
-      for (int i = 0; i + 1 < np; i++) w.put(modular ? 0u : (uint32_t)PassShift(np, i), 2);   // shift of every pass but the last
+      for (int i = 0; i + 1 < np; i++) w.put(modular ? 0u : (uint32_t)(p.pass_shift[i] >= 0 ? p.pass_shift[i] : PassShift(np, i)), 2);   // shift of every pass but the last
       // entry i: "pass i completes the image at 1 / (2 << (nds - 1 - i))" -> downsample 4, 2 (np = 3) or 2 (np = 2); U32(Val 1, 2, 4, 8)
       for (int i = 0; i < nds; i++) w.put((uint32_t)(nds - i), 2);
       for (int i = 0; i < nds; i++) w.put((uint32_t)i, 2);    // last_pass: U32(Val 0, 1, 2, Bits(3))
@@ -933,6 +934,101 @@ static bool& CustomBlockCtx() { static thread_local bool v = false; return v; }
 static bool& CustomLfGlobal() { static thread_local bool v = false; return v; }
 // group_size_shift of the Modular frames written from now on (this thread): groups of 128 << shift samples a side (frame_header.cc; 1 = 256 is what VarDCT frames always use)
 static int& ModularGroupShift() { static thread_local int v = 1; return v; }
+// What the front half of a VarDCT encode hands to the section writer: the block grid with its strategies, quantiser field, quantised LF, chroma-from-luma maps and
+// sharpness, the block context map, and per (pass, group) the AC tokens.  EncodeVarDCT fills it from an image, EncodeVarDCTScripted (synth_script_hf.h) from a script.
+struct HfOrders { uint32_t used = 0; std::vector<std::vector<uint32_t>> perm; };   // perm[bucket * 3 + c] (c = X, Y, B; set buckets only): scan position -> natural position
+struct ScriptedAcCode {                       // scripted streams: the caller's context map and pseudo-counts instead of the clustering of BuildEntropyCoder
+  std::vector<uint8_t> ctx_map; int num_clusters = 1;
+  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> pseudo;   // per cluster (symbol, count): enter the histogram, never emitted
+  std::vector<std::vector<int>> dist;                                // out: per pass * num_clusters the normalised distribution
+};
+struct VarDctBody {
+  int w = 0, h = 0, img_w = 0, img_h = 0;
+  std::vector<int8_t> strat; std::vector<uint8_t> first;
+  std::vector<int32_t> hf_mul, sharp, lfq[3], ytox, ytob;
+  QuantSpec specs[17];
+  uint32_t global_scale = 1;
+  bool custom_bcm = false; std::vector<int32_t> lf_thr[3]; std::vector<uint32_t> qf_thr; std::vector<uint8_t> bcm_map; int nctx = 15;
+  std::vector<std::vector<Token>> ac_tok_all;   // [pass * groups + group]
+  std::vector<HfOrders> orders;                 // per pass; empty: natural orders
+  int npresets = 0; std::vector<int> preset;    // npresets > 0 (scripted): the preset of every (pass, group), token contexts already final
+  ScriptedAcCode* code = nullptr;
+};
+static std::vector<uint8_t> WriteVarDCTFrame(VarDctBody& b, const Params& p, const uint8_t* alpha);
+static std::vector<uint32_t> LehmerCode(const std::vector<uint32_t>& perm);
+// Lehmer code of a permutation (lehmer[i] = how many of the values not yet used are smaller than perm[i]), with a Fenwick tree: the orders of the two largest
+// transforms have 32768 and 65536 entries
+static std::vector<uint32_t> LehmerCode(const std::vector<uint32_t>& perm) {
+  const size_t n = perm.size();
+  std::vector<uint32_t> tree(n + 1, 0), lehmer(n);
+  std::vector<uint8_t> seen(n, 0);
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t v = perm[i];
+    if (v >= n || seen[v]) throw std::runtime_error("coefficient order: not a permutation");
+    seen[v] = 1;
+    uint32_t used_below = 0;
+    for (size_t k = v; k > 0; k -= k & (~k + 1)) used_below += tree[k];      // values < v already used
+    lehmer[i] = v - used_below;
+    for (size_t k = (size_t)v + 1; k <= n; k += k & (~k + 1)) tree[k]++;
+  }
+  return lehmer;
+}
+// The AC code of a scripted stream: contexts go to the clusters the caller names, every cluster's histogram is its tokens' plus the caller's pseudo-counts.  Of the
+// AC code shape the alias-table size (min_log_alpha) and the hybrid-uint configurations apply (cluster k takes configuration (seed + k) mod the list's length where
+// its tokens fit it); the clustering itself is the caller's.  LZ77: the distance context is a cluster of its own behind the caller's.
+static void BuildScriptedAcCode(const std::vector<const std::vector<Token>*>& streams, int num_ctx, bool lz77, ScriptedAcCode& code, EntropyCoder& ec) {
+  const CodeShape& sh = AcCodeShape();
+  const UintConfig uc{4, 2, 0};
+  if ((int)code.ctx_map.size() != num_ctx) throw std::runtime_error("scripted AC code: the context map has " + std::to_string(code.ctx_map.size()) + " entries, the code " + std::to_string(num_ctx) + " contexts");
+  int ncl = code.num_clusters + (lz77 ? 1 : 0);
+  if (code.num_clusters < 1 || ncl > 256) throw std::runtime_error("scripted AC code: 1..256 clusters (255 with LZ77)");
+  ec.num_ctx = num_ctx + (lz77 ? 1 : 0);
+  ec.ctx_map.assign(code.ctx_map.begin(), code.ctx_map.end());
+  for (uint8_t m : ec.ctx_map) if (m >= code.num_clusters) throw std::runtime_error("scripted AC code: context map entry out of range");
+  { std::vector<uint8_t> seen(code.num_clusters, 0); for (uint8_t m : ec.ctx_map) seen[m] = 1; for (uint8_t v : seen) if (!v) throw std::runtime_error("scripted AC code: a cluster no context maps to"); }
+  if (lz77) ec.ctx_map.push_back((uint8_t)code.num_clusters);
+  ec.cfg.assign(ncl, uc);
+  std::vector<std::vector<const Token*>> per(ncl);
+  for (auto* ts : streams) for (const Token& t : *ts) {
+    if (t.ctx >= (uint32_t)ec.num_ctx) throw std::runtime_error("scripted AC code: token context out of range");
+    per[ec.ctx_map[t.ctx]].push_back(&t);
+  }
+  auto count = [&](const UintConfig& c, int cl, std::vector<uint32_t>& out) {
+    out.clear();
+    for (const Token* t : per[cl]) {
+      uint32_t tok, nb, bits;
+      TokenSymbol(c, *t, &tok, &nb, &bits);
+      if (tok >= 256 || (!t->raw && lz77 && tok >= 224)) return false;
+      if (out.size() <= tok) out.resize(tok + 1, 0);
+      out[tok]++;
+    }
+    return true;
+  };
+  std::vector<std::vector<uint32_t>> ch(ncl);
+  for (int cl = 0; cl < ncl; cl++) {
+    bool ok = false;
+    for (size_t k = 0; k < sh.cfgs.size() && !ok; k++) {
+      UintConfig c = sh.cfgs[(sh.seed + cl + k) % sh.cfgs.size()];
+      if (c.split_exponent < 0) c = UintConfig{8, 0, 0};
+      if (count(c, cl, ch[cl])) { ec.cfg[cl] = c; ok = true; }
+    }
+    if (!ok && !count(uc, cl, ch[cl])) throw std::runtime_error("scripted AC code: a token does not fit the alphabet");
+    if (cl < code.num_clusters && cl < (int)code.pseudo.size())
+      for (const auto& sc : code.pseudo[cl]) {
+        if (sc.first >= (lz77 ? 224u : 256u)) throw std::runtime_error("scripted AC code: pseudo-count symbol out of range");
+        if (ch[cl].size() <= sc.first) ch[cl].resize(sc.first + 1, 0);
+        ch[cl][sc.first] += sc.second;
+      }
+  }
+  size_t max_alpha = 1;
+  for (auto& hh : ch) { size_t n = hh.size(); while (n > 0 && hh[n - 1] == 0) n--; max_alpha = std::max(max_alpha, n); }
+  ec.log_alpha = sh.cfgs.empty() ? std::min(8, std::max(std::max(5, sh.min_log_alpha), CeilLog2((uint32_t)max_alpha))) : 8;
+  ec.clusters.assign(ncl, ClusterCode());
+  BuildClusterTables(ec, ch);
+  for (int cl = 0; cl < code.num_clusters; cl++) code.dist.push_back(ec.clusters[cl].dist);
+  if (UsePrefixCodes() && !lz77) MakePrefixCodes(ec);
+}
+
 static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int h, const Params& p, const uint8_t* alpha = nullptr, int img_w = 0, int img_h = 0) {
   if (img_w == 0) { img_w = w; img_h = h; }   // (w, h) = coded size; (img_w, img_h) = image size when the frame is upsampled
   const int bw = (w + 7) / 8, bh = (h + 7) / 8;
@@ -1100,45 +1196,6 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
       qb[k] = quant((fb[k] - kb * dy) / (tb[k] * sdc[2]));
     }
   }
-  // --- tokens: modular streams (LF coefficients + HF metadata) under the global tree
-  std::vector<int> bfs;
-  GTree gt = MakeGlobalTree(nlf, &bfs);
-  const int root = bfs[0];
-  std::vector<Token> tree_tokens;
-  TreeTokens(gt, bfs, tree_tokens);
-  struct LfGroupData { std::vector<int32_t> ch[3]; std::vector<int32_t> m[4]; int gbw, gbh, nb; std::vector<Token> lf_tok, meta_tok; };
-  std::vector<LfGroupData> lgd(nlf);
-  for (int g = 0; g < nlf; g++) {
-    LfGroupData& d = lgd[g];
-    int gx = g % xlg, gy = g / xlg, bx0 = gx * 256, by0 = gy * 256;
-    d.gbw = std::min(256, bw - bx0); d.gbh = std::min(256, bh - by0);
-    static const int order[3] = {1, 0, 2};  // Y, X, B
-    for (int i = 0; i < 3; i++) {
-      d.ch[i].resize((size_t)d.gbw * d.gbh);
-      for (int y = 0; y < d.gbh; y++) for (int x = 0; x < d.gbw; x++) d.ch[i][(size_t)y * d.gbw + x] = lfq[order[i]][(size_t)(by0 + y) * bw + bx0 + x];
-    }
-    std::vector<ChanRef> cr;
-    for (int i = 0; i < 3; i++) cr.push_back({d.ch[i].data(), d.gbw, d.gbh});
-    ModularTokens(gt, root, cr, 1 + g, d.lf_tok, LfWpParams());
-    // HF metadata
-    int mcw = (d.gbw + 7) / 8, mch = (d.gbh + 7) / 8;
-    d.m[0].resize((size_t)mcw * mch); d.m[1].resize((size_t)mcw * mch);
-    for (int y = 0; y < mch; y++) for (int x = 0; x < mcw; x++) {
-      d.m[0][(size_t)y * mcw + x] = ytox[(size_t)(gy * 32 + y) * cw + gx * 32 + x];
-      d.m[1][(size_t)y * mcw + x] = ytob[(size_t)(gy * 32 + y) * cw + gx * 32 + x];
-    }
-    std::vector<int32_t> st, hm;
-    for (int y = 0; y < d.gbh; y++) for (int x = 0; x < d.gbw; x++) {
-      size_t o = (size_t)(by0 + y) * bw + bx0 + x;
-      if (first[o]) { st.push_back(strat[o]); hm.push_back(hf_mul[o] - 1); }
-    }
-    d.nb = (int)st.size();
-    d.m[2] = st; d.m[2].insert(d.m[2].end(), hm.begin(), hm.end());
-    d.m[3].resize((size_t)d.gbw * d.gbh);
-    for (int y = 0; y < d.gbh; y++) for (int x = 0; x < d.gbw; x++) d.m[3][(size_t)y * d.gbw + x] = sharp[(size_t)(by0 + y) * bw + bx0 + x];
-    std::vector<ChanRef> mr{{d.m[0].data(), mcw, mch}, {d.m[1].data(), mcw, mch}, {d.m[2].data(), d.nb, 2}, {d.m[3].data(), d.gbw, d.gbh}};
-    ModularTokens(gt, root, mr, 1 + 2 * nlf + g, d.meta_tok, LfWpParams());
-  }
   // --- tokens: AC per group
   const bool custom_bcm = CustomBlockCtx();
   std::vector<int32_t> lf_thr[3];
@@ -1171,11 +1228,44 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
     }
   }
   std::vector<std::vector<Token>> ac_tok_all((size_t)ngroups * np);
+  std::vector<HfOrders> pass_orders;
   for (int ps = 0; ps < np; ps++) {
   std::vector<Token>* ac_tok = &ac_tok_all[(size_t)ps * ngroups];
   std::vector<uint32_t> natural[13];
   static const int bucket_rep[13] = {S_DCT, S_IDENTITY, S_DCT16X16, S_DCT32X32, S_DCT16X8, S_DCT32X8, S_DCT32X16, S_DCT64X64, S_DCT64X32, 21, 22, 24, 25};
   for (int b = 0; b < 13; b++) natural[b] = NaturalOrder(bucket_rep[b]);
+  // custom_orders: per pass, bucket in use and channel the scan visits the positions in the order of how often they are non-zero in this pass (what libjxl's
+  // encoder does: enc_coeff_order.cc), ties in natural order, the cx * cy lowest frequencies kept in front
+  std::vector<uint32_t> custom[39];
+  if (p.custom_orders) {
+    HfOrders ho;
+    std::vector<uint32_t> hits[39];
+    for (size_t o = 0; o < strat.size(); o++) {
+      if (!first[o]) continue;
+      const int ord = kBucket[strat[o]];
+      ho.used |= 1u << ord;
+      for (int c = 0; c < 3; c++) {
+        std::vector<uint32_t>& hh = hits[ord * 3 + c];
+        hh.resize(natural[ord].size(), 0);
+        const int32_t* q = qpass[c][ps].data() + coff[o];
+        for (size_t k = 0; k < hh.size(); k++) hh[k] += q[natural[ord][k]] != 0;
+      }
+    }
+    for (int b = 0; b < 13; b++) {
+      if (!(ho.used & (1u << b))) continue;
+      const size_t size = natural[b].size(), skip = size / 64;
+      for (int c = 0; c < 3; c++) {
+        std::vector<uint32_t> perm(size);
+        for (size_t i = 0; i < size; i++) perm[i] = (uint32_t)i;
+        const std::vector<uint32_t>& hh = hits[b * 3 + c];
+        std::stable_sort(perm.begin() + skip, perm.end(), [&](uint32_t x, uint32_t y) { return hh[x] > hh[y]; });
+        custom[b * 3 + c].resize(size);
+        for (size_t i = 0; i < size; i++) custom[b * 3 + c][i] = natural[b][perm[i]];
+        ho.perm.push_back(std::move(perm));
+      }
+    }
+    pass_orders.push_back(std::move(ho));
+  }
   for (int g = 0; g < ngroups; g++) {
     int gx = g % xg, gy = g / xg, bx0 = gx * 32, by0 = gy * 32;
     int gbw = std::min(32, bw - bx0), gbh = std::min(32, bh - by0);
@@ -1186,10 +1276,10 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
       size_t o = (size_t)(by0 + by) * bw + bx0 + bx;
       if (!first[o]) continue;
       int s = strat[o], cx = kCovX[s], cy = kCovY[s], covered = cx * cy, l2 = ILog2(covered), size = covered * 64, ord = kBucket[s];
-      const std::vector<uint32_t>& order = natural[ord];
       static const int chan[3] = {1, 0, 2};
       for (int ci = 0; ci < 3; ci++) {
         int c = chan[ci];
+        const std::vector<uint32_t>& order = p.custom_orders ? custom[ord * 3 + c] : natural[ord];
         int idx = (c < 2 ? (c ^ 1) : 2) * 13 + ord;
         int block_ctx = kDefaultBlockCtx[idx];
         if (custom_bcm) {
@@ -1230,6 +1320,80 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
     }
   }
   }  // passes
+  VarDctBody body;
+  body.w = w; body.h = h; body.img_w = img_w; body.img_h = img_h;
+  body.strat = std::move(strat); body.first = std::move(first); body.hf_mul = std::move(hf_mul); body.sharp = std::move(sharp);
+  for (int c = 0; c < 3; c++) { body.lfq[c] = std::move(lfq[c]); body.lf_thr[c] = lf_thr[c]; }
+  body.ytox = std::move(ytox); body.ytob = std::move(ytob);
+  for (int k = 0; k < 17; k++) body.specs[k] = specs[k];
+  body.global_scale = global_scale;
+  body.custom_bcm = custom_bcm; body.qf_thr = qf_thr; body.bcm_map = bcm_map; body.nctx = nctx;
+  body.ac_tok_all = std::move(ac_tok_all);
+  body.orders = std::move(pass_orders);
+  return WriteVarDCTFrame(body, p, alpha);
+}
+
+// The section writer both entry points share: LfGlobal, the LfGroups (LF coefficients and HF metadata under the global tree), HfGlobal (quantisation tables,
+// coefficient orders, one entropy code per pass) and the PassGroups, under the frame header `p` describes.
+static std::vector<uint8_t> WriteVarDCTFrame(VarDctBody& b, const Params& p, const uint8_t* alpha) {
+  const int w = b.w, h = b.h, img_w = b.img_w, img_h = b.img_h;
+  const int bw = (w + 7) / 8, bh = (h + 7) / 8;
+  const int xg = (w + 255) / 256, yg = (h + 255) / 256, ngroups = xg * yg;
+  const int xlg = (w + 2047) / 2048, ylg = (h + 2047) / 2048, nlf = xlg * ylg;
+  const int cw = (bw + 7) / 8;
+  const std::vector<int8_t>& strat = b.strat; const std::vector<uint8_t>& first = b.first;
+  const std::vector<int32_t>& hf_mul = b.hf_mul; const std::vector<int32_t>& sharp = b.sharp; const std::vector<int32_t>& ytox = b.ytox; const std::vector<int32_t>& ytob = b.ytob;
+  const std::vector<int32_t>* lfq = b.lfq; const std::vector<int32_t>* lf_thr = b.lf_thr;
+  const std::vector<uint32_t>& qf_thr = b.qf_thr; const std::vector<uint8_t>& bcm_map = b.bcm_map;
+  const QuantSpec* specs = b.specs;
+  std::vector<std::vector<Token>>& ac_tok_all = b.ac_tok_all;
+  const uint32_t global_scale = b.global_scale, quant_lf = (uint32_t)QuantLf();
+  const bool custom_bcm = b.custom_bcm, custom_lfg = CustomLfGlobal();
+  const int nctx = b.nctx, np = p.num_passes;
+  const float m_lf[3] = {custom_lfg ? 1.0f / 2048 : 1.0f / 4096, custom_lfg ? 1.0f / 256 : 1.0f / 512, custom_lfg ? 1.0f / 128 : 1.0f / 256};
+  const float cfl_factor = custom_lfg ? 64.0f : 84.0f, cfl_base_x = custom_lfg ? 0.125f : 0.0f, cfl_base_b = custom_lfg ? 0.75f : 1.0f;
+  const int cfl_x_lf = custom_lfg ? 6 : 0, cfl_b_lf = custom_lfg ? -10 : 0;
+  (void)yg; (void)ylg;
+
+  // --- tokens: modular streams (LF coefficients + HF metadata) under the global tree
+  std::vector<int> bfs;
+  GTree gt = MakeGlobalTree(nlf, &bfs);
+  const int root = bfs[0];
+  std::vector<Token> tree_tokens;
+  TreeTokens(gt, bfs, tree_tokens);
+  struct LfGroupData { std::vector<int32_t> ch[3]; std::vector<int32_t> m[4]; int gbw, gbh, nb; std::vector<Token> lf_tok, meta_tok; };
+  std::vector<LfGroupData> lgd(nlf);
+  for (int g = 0; g < nlf; g++) {
+    LfGroupData& d = lgd[g];
+    int gx = g % xlg, gy = g / xlg, bx0 = gx * 256, by0 = gy * 256;
+    d.gbw = std::min(256, bw - bx0); d.gbh = std::min(256, bh - by0);
+    static const int order[3] = {1, 0, 2};  // Y, X, B
+    for (int i = 0; i < 3; i++) {
+      d.ch[i].resize((size_t)d.gbw * d.gbh);
+      for (int y = 0; y < d.gbh; y++) for (int x = 0; x < d.gbw; x++) d.ch[i][(size_t)y * d.gbw + x] = lfq[order[i]][(size_t)(by0 + y) * bw + bx0 + x];
+    }
+    std::vector<ChanRef> cr;
+    for (int i = 0; i < 3; i++) cr.push_back({d.ch[i].data(), d.gbw, d.gbh});
+    ModularTokens(gt, root, cr, 1 + g, d.lf_tok, LfWpParams());
+    // HF metadata
+    int mcw = (d.gbw + 7) / 8, mch = (d.gbh + 7) / 8;
+    d.m[0].resize((size_t)mcw * mch); d.m[1].resize((size_t)mcw * mch);
+    for (int y = 0; y < mch; y++) for (int x = 0; x < mcw; x++) {
+      d.m[0][(size_t)y * mcw + x] = ytox[(size_t)(gy * 32 + y) * cw + gx * 32 + x];
+      d.m[1][(size_t)y * mcw + x] = ytob[(size_t)(gy * 32 + y) * cw + gx * 32 + x];
+    }
+    std::vector<int32_t> st, hm;
+    for (int y = 0; y < d.gbh; y++) for (int x = 0; x < d.gbw; x++) {
+      size_t o = (size_t)(by0 + y) * bw + bx0 + x;
+      if (first[o]) { st.push_back(strat[o]); hm.push_back(hf_mul[o] - 1); }
+    }
+    d.nb = (int)st.size();
+    d.m[2] = st; d.m[2].insert(d.m[2].end(), hm.begin(), hm.end());
+    d.m[3].resize((size_t)d.gbw * d.gbh);
+    for (int y = 0; y < d.gbh; y++) for (int x = 0; x < d.gbw; x++) d.m[3][(size_t)y * d.gbw + x] = sharp[(size_t)(by0 + y) * bw + bx0 + x];
+    std::vector<ChanRef> mr{{d.m[0].data(), mcw, mch}, {d.m[1].data(), mcw, mch}, {d.m[2].data(), d.nb, 2}, {d.m[3].data(), d.gbw, d.gbh}};
+    ModularTokens(gt, root, mr, 1 + 2 * nlf + g, d.meta_tok, LfWpParams());
+  }
   // --- optional alpha: one 8-bit extra channel coded losslessly by the frame's Modular sub-streams (GlobalModular when
   // the image fits one group, else the modular part of every PassGroup), under the same global tree
   // squeezed alpha of a frame with downsampling entries: the sub-channels of shift 0..2 are spread over the PassGroups of every pass (by its bracket);
@@ -1363,9 +1527,10 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
     EncodeTokens(s, ec, t);
   };
   const bool lz77_ac = UseLz77Ac();
-  const int npresets = std::max(1, std::min(HfPresets(), ngroups));
+  const int npresets = b.npresets > 0 ? b.npresets : std::max(1, std::min(HfPresets(), ngroups));
+  auto preset_of = [&](int ps, int g) { return b.npresets > 0 ? b.preset[(size_t)ps * ngroups + g] : g % npresets; };
   for (int ps = 0; ps < np; ps++) {
-    if (npresets > 1)      // histogram set g % npresets: its contexts follow those of the sets before it (dec_group.cc: context offset = histo_selector * num AC contexts)
+    if (npresets > 1 && b.npresets == 0)      // histogram set g % npresets: its contexts follow those of the sets before it (dec_group.cc: context offset = histo_selector * num AC contexts)
       for (int g = 0; g < ngroups; g++) for (Token& t : ac_tok_all[(size_t)ps * ngroups + g]) t.ctx += (uint32_t)((g % npresets) * 495 * nctx);
     if (lz77_ac) {   // LZ77 over every group's coefficient stream of the pass (dec_group.cc reads them with a reader without distance multiplier)
       EntropyCoder proto;
@@ -1373,6 +1538,8 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
       for (int g = 0; g < ngroups; g++) ApplyLz77(ac_tok_all[(size_t)ps * ngroups + g], (uint32_t)(495 * nctx * npresets), proto, 0, /*special=*/false);
     }
     std::vector<const std::vector<Token>*> s; for (int g = 0; g < ngroups; g++) s.push_back(&ac_tok_all[(size_t)ps * ngroups + g]);
+    if (b.code) BuildScriptedAcCode(s, 495 * nctx * npresets, lz77_ac, *b.code, ac_codes[ps]);
+    else
     BuildEntropyCoder(s, 495 * nctx * npresets + (lz77_ac ? 1 : 0), UintConfig{4, 2, 0}, 96, ac_codes[ps], &AcCodeShape());
     if (lz77_ac) { ac_codes[ps].lz77 = true; ac_codes[ps].lz_min_symbol = 224; ac_codes[ps].lz_min_length = 3; ac_codes[ps].lz_len_cfg = UintConfig{3, 0, 0}; }
   }
@@ -1395,7 +1562,7 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
       }
       s.put((uint32_t)qf_thr.size(), 4);
       for (uint32_t t : qf_thr) WriteU32(s, t - 1, {2, 0}, {3, 4}, {5, 12}, {8, 44});
-      WriteContextMap(s, bcm_map, 16);
+      WriteContextMap(s, bcm_map, b.code ? nctx : 16);
     }
     if (!custom_lfg) s.put(1, 1);  // default LfChannelCorrelation
     else {
@@ -1462,14 +1629,35 @@ static std::vector<uint8_t> EncodeVarDCT(const float* xyb_planes[3], int w, int 
     }
     s.put((uint32_t)(npresets - 1), CeilLog2((uint32_t)ngroups));  // num_hf_presets - 1
     for (int ps = 0; ps < np; ps++) {       // HfPass: natural orders, one entropy code per pass
-      s.put(2, 2);                          // used_orders = Val(0)
+      const uint32_t used = b.orders.empty() ? 0 : b.orders[ps].used;
+      if (used == 0) s.put(2, 2);           // used_orders = Val(0)
+      else {
+        WriteU32(s, used, {0, 0x5F}, {0, 0x13}, {0, 0}, {13, 0});
+        // coeff_order.cc: every permutation as its Lehmer code from position cx * cy on, trailing zeros cut through `end`, all under one code of 8 contexts
+        std::vector<Token> tok;
+        auto ctxof = [](uint32_t v) { uint32_t t = 0; while (v) { t++; v >>= 1; } return std::min<uint32_t>(t, 7); };
+        for (const std::vector<uint32_t>& perm : b.orders[ps].perm) {
+          const size_t size = perm.size(), skip = size / 64;
+          const std::vector<uint32_t> lehmer = LehmerCode(perm);
+          for (size_t i = 0; i < skip; i++) if (lehmer[i] != 0) throw std::runtime_error("coefficient order: the lowest frequencies must stay in front");
+          size_t end = size;
+          while (end > skip && lehmer[end - 1] == 0) end--;
+          tok.push_back({ctxof((uint32_t)size), (uint32_t)(end - skip)});
+          uint32_t last = 0;
+          for (size_t i = skip; i < end; i++) { tok.push_back({ctxof(last), lehmer[i]}); last = lehmer[i]; }
+        }
+        EntropyCoder oc;
+        { std::vector<const std::vector<Token>*> ts{&tok}; BuildEntropyCoder(ts, 8, UintConfig{4, 2, 0}, 8, oc); }
+        WriteEntropyCode(s, oc);
+        EncodeTokens(s, oc, tok);
+      }
       WriteEntropyCode(s, ac_codes[ps]);
     }
     sections.push_back(s);
   }
   for (int ps = 0; ps < np; ps++) for (int g = 0; g < ngroups; g++) {  // PassGroup, pass-major
     BitWriter s;
-    s.put((uint32_t)(g % npresets), CeilLog2((uint32_t)npresets));   // which histogram set (0 bits when there is one)
+    s.put((uint32_t)preset_of(ps, g), CeilLog2((uint32_t)npresets));   // which histogram set (0 bits when there is one)
     EncodeTokens(s, ac_codes[ps], ac_tok_all[(size_t)ps * ngroups + g]);
     // extra channels (shift 0..2) ride in the last pass (Passes::GetDownsamplingBracket without downsampling entries), squeezed ones of a frame with
     // downsampling entries in the pass whose bracket holds their shift — behind that pass's coefficients
@@ -1727,6 +1915,7 @@ static std::vector<uint8_t> EncodeModular(const int32_t* const* planes, int ncha
 
 #include "synth_free.h"
 #include "synth_script.h"
+#include "synth_script_hf.h"
 #include "synth_ycbcr.h"
 
 // ---- C API ---------------------------------------------------------------------------------------------------------
@@ -1806,7 +1995,7 @@ int jxlsynth_vardct2(const uint8_t* rgb8, const float* rgb_lin, const uint8_t* a
     p.upsampling = (pp->upsampling == 2 || pp->upsampling == 4 || pp->upsampling == 8) ? pp->upsampling : 1;
     p.custom_up_weights = pp->custom_up_weights;
     p.num_passes = pp->num_passes >= 1 && pp->num_passes <= 3 ? pp->num_passes : 1;
-    p.permute_toc = pp->permute_toc; p.pass_ds = pp->pass_ds;
+    p.permute_toc = pp->permute_toc; p.pass_ds = pp->pass_ds; p.custom_orders = pp->custom_orders == 1;
     std::vector<float> pl[3];
     for (auto& v : pl) v.resize((size_t)w * h);
     const float scale = p.hdr ? 255.0f / 1000.0f : 1.0f;  // intensity_target 1000: linear 1.0 == 1000 nits
@@ -1990,6 +2179,57 @@ int jxlsynth_modular_scripted2(const int32_t* hdr, const int32_t* wp, const int3
 int jxlsynth_modular_scripted(const int32_t* hdr, const int32_t* gt, int n_gt, const int32_t* lt, int n_lt, const int32_t* nodes, int n_nodes,
                               const int32_t* const* planes, const int32_t* dims, int n_planes, uint8_t** out, size_t* n) {
   return jxlsynth_modular_scripted2(hdr, nullptr, gt, n_gt, lt, n_lt, nodes, n_nodes, planes, dims, n_planes, out, n);
+}
+// Scripted VarDCT coefficient stream (synth_script_hf.h).  hdr: w, h, varblocks, nctx (0: default block context map), passes, shift of pass 0, of pass 1, presets,
+// clusters.  vbs: (by, bx, strategy, hf_mul) per varblock.  lfq: X, Y, B planes over the block grid.  bcm (nctx != 0): per X / Y / B count + thresholds, count +
+// quantiser thresholds, count + map.  orders: per pass the used mask, then the permutations of the set buckets (X, Y, B each), back to back.  presets, counts: per
+// (pass, group); ctxs / values: the token pairs of all sections back to back.  ctx_map: 495 * nctx * presets entries.  pseudo: per cluster count + (symbol, count)
+// pairs.  dist_out: passes * clusters * 256 normalised frequencies (sum 4096 each).
+int jxlsynth_vardct_scripted(const int32_t* hdr, const int32_t* vbs, const int32_t* const* lfq, const int32_t* bcm, const int32_t* orders, const int32_t* presets,
+                             const int32_t* counts, const uint32_t* ctxs, const uint32_t* values, const int32_t* ctx_map, const int32_t* pseudo, int32_t* dist_out,
+                             uint8_t** out, size_t* n) {
+  try {
+    synth::HfScript sc;
+    sc.w = hdr[0]; sc.h = hdr[1];
+    const int nvb = hdr[2];
+    sc.nctx = hdr[3]; sc.num_passes = hdr[4]; sc.shift[0] = hdr[5]; sc.shift[1] = hdr[6]; sc.num_presets = hdr[7]; sc.code.num_clusters = hdr[8];
+    if (sc.w < 1 || sc.h < 1 || sc.num_passes < 1 || sc.num_passes > 3 || sc.num_presets < 1 || sc.nctx < 0 || sc.nctx > 16) throw std::runtime_error("scripted VarDCT stream: header out of range");
+    for (int i = 0; i < nvb; i++) sc.varblocks.push_back({vbs[4 * i], vbs[4 * i + 1], vbs[4 * i + 2], vbs[4 * i + 3]});
+    for (int c = 0; c < 3; c++) sc.lfq[c] = lfq[c];
+    if (sc.nctx) {
+      const int32_t* q = bcm;
+      for (int c = 0; c < 3; c++) { const int k = *q++; for (int i = 0; i < k; i++) sc.lf_thr[c].push_back(*q++); }
+      { const int k = *q++; for (int i = 0; i < k; i++) sc.qf_thr.push_back((uint32_t)*q++); }
+      { const int k = *q++; for (int i = 0; i < k; i++) sc.bcm_map.push_back((uint8_t)*q++); }
+    }
+    static const int bucket_size[13] = {64, 64, 256, 1024, 128, 256, 512, 4096, 2048, 16384, 8192, 65536, 32768};
+    const int32_t* q = orders;
+    for (int ps = 0; ps < sc.num_passes; ps++) {
+      synth::HfOrders ho;
+      ho.used = (uint32_t)*q++ & 0x1FFF;
+      for (int b = 0; b < 13; b++) if (ho.used & (1u << b)) for (int c = 0; c < 3; c++) { ho.perm.emplace_back(q, q + bucket_size[b]); q += bucket_size[b]; }
+      sc.orders.push_back(std::move(ho));
+    }
+    const int ngroups = ((sc.w + 255) / 256) * ((sc.h + 255) / 256), nsec = sc.num_passes * ngroups;
+    sc.preset.assign(presets, presets + nsec);
+    sc.tokens.resize(nsec);
+    size_t at = 0;
+    for (int i = 0; i < nsec; i++) {
+      sc.tokens[i].reserve(counts[i]);
+      for (int k = 0; k < counts[i]; k++, at++) sc.tokens[i].push_back(synth::Token{ctxs[at], values[at]});
+    }
+    const int nac = 495 * (sc.nctx ? sc.nctx : 15) * sc.num_presets;
+    for (int i = 0; i < nac; i++) sc.code.ctx_map.push_back((uint8_t)ctx_map[i]);
+    q = pseudo;
+    for (int cl = 0; cl < sc.code.num_clusters; cl++) {
+      sc.code.pseudo.emplace_back();
+      const int k = *q++;
+      for (int i = 0; i < k; i++, q += 2) sc.code.pseudo.back().push_back({(uint32_t)q[0], (uint32_t)q[1]});
+    }
+    const std::vector<uint8_t> bytes = synth::EncodeVarDCTScripted(sc);
+    for (size_t i = 0; i < sc.code.dist.size(); i++) for (int k = 0; k < 256; k++) dist_out[i * 256 + k] = k < (int)sc.code.dist[i].size() ? sc.code.dist[i][k] : 0;
+    return finish(bytes, out, n);
+  } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
 // The synthesiser's LF tokeniser on planes of the caller's: three w x h planes as ONE stream (an LF group's coefficient stream, stream id 1) through the
 // ModularTokens that frame encoding calls, under the LF subtree of MakeGlobalTree for the current LfTreeShape() (1 or 2) with LfWpParams().

@@ -308,6 +308,29 @@ inline double HistoCost(const std::vector<uint32_t>& h, uint64_t total) {
   return c;
 }
 
+// per cluster: the normalised distribution of its histogram, the alias table and the reverse map the encoder codes with (ec.log_alpha is set)
+inline void BuildClusterTables(EntropyCoder& ec, const std::vector<std::vector<uint32_t>>& ch) {
+  for (size_t c = 0; c < ch.size(); c++) {
+    if (ch[c].size() > 256) throw std::runtime_error("ANS alphabet > 256");
+    Normalize(ch[c], ec.clusters[c].dist);
+    BuildAlias(ec.clusters[c].dist, ec.log_alpha, ec.clusters[c].alias);
+    // reverse map
+    auto& cc = ec.clusters[c];
+    cc.reverse.assign(cc.dist.size(), {});
+    for (size_t s = 0; s < cc.dist.size(); s++) cc.reverse[s].assign(cc.dist[s], 0);
+    const int la = ec.log_alpha, B = 4096 >> la;
+    for (int v = 0; v < 4096; v++) {
+      int i = v >> (12 - la), pos = v & (B - 1);
+      const AliasE& e = cc.alias[i];
+      bool hit = pos >= e.cutoff;
+      int sym = hit ? e.right : i;
+      int off = hit ? e.offs1 + pos : pos;
+      if (sym >= (int)cc.reverse.size() || off >= (int)cc.reverse[sym].size()) throw std::runtime_error("alias reverse map inconsistent");
+      cc.reverse[sym][off] = (uint16_t)v;
+    }
+  }
+}
+
 // Builds an entropy code from per-context token statistics: clusters contexts greedily (<= max_clusters) and
 // normalises histograms.  tokens: all tokens that will be coded with this code.  shape: overrides (CodeShape), nullptr = none.
 inline void BuildEntropyCoder(const std::vector<const std::vector<Token>*>& streams, int num_ctx, const UintConfig& uc,
@@ -440,25 +463,7 @@ inline void BuildEntropyCoder(const std::vector<const std::vector<Token>*>& stre
     ec.cfg = pick;
     ch = hist;
   }
-  for (size_t c = 0; c < ch.size(); c++) {
-    if (ch[c].size() > 256) throw std::runtime_error("ANS alphabet > 256");
-    Normalize(ch[c], ec.clusters[c].dist);
-    BuildAlias(ec.clusters[c].dist, ec.log_alpha, ec.clusters[c].alias);
-    // reverse map
-    auto& cc = ec.clusters[c];
-    cc.reverse.assign(cc.dist.size(), {});
-    for (size_t s = 0; s < cc.dist.size(); s++) cc.reverse[s].assign(cc.dist[s], 0);
-    const int la = ec.log_alpha, B = 4096 >> la;
-    for (int v = 0; v < 4096; v++) {
-      int i = v >> (12 - la), pos = v & (B - 1);
-      const AliasE& e = cc.alias[i];
-      bool hit = pos >= e.cutoff;
-      int sym = hit ? e.right : i;
-      int off = hit ? e.offs1 + pos : pos;
-      if (sym >= (int)cc.reverse.size() || off >= (int)cc.reverse[sym].size()) throw std::runtime_error("alias reverse map inconsistent");
-      cc.reverse[sym][off] = (uint16_t)v;
-    }
-  }
+  BuildClusterTables(ec, ch);
   if (UsePrefixCodes() && !ec.lz77) MakePrefixCodes(ec);
 }
 

@@ -1,5 +1,6 @@
 // jxl-hip: batch decoder (see decoder.h).
 #include "decoder.h"
+#include "decoder_impl.h"
 #include <atomic>
 #include <exception>
 #include <deque>
@@ -8,18 +9,11 @@
 #include <chrono>
 #include <map>
 #include <queue>
-#include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 namespace jxlhip {
-
-#define HIP_CHECK(expr)                                                                                    \
-  do {                                                                                                     \
-    hipError_t e_ = (expr);                                                                                \
-    if (e_ != hipSuccess) throw ParseError(std::string("HIP error: ") + hipGetErrorString(e_) + " in " #expr, false); \
-  } while (0)
 
 // Growable byte buffer in pinned host memory — what Prepare assembles the constant arena in and uploads from.  Pinned: the upload is a
 // DMA at link speed (57 GB/s) instead of a staged copy, and can overlap the GPU's work.  The capacity survives clear(): a batch object that is
@@ -63,7 +57,6 @@ void HostStage::Resize(size_t n) {
 }
 
 namespace {
-size_t Align(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 // library-default kernels (image_metadata.cc kWeights2 / 4 / 8): each sub-pixel kernel sums to 1
 static const float kUp2[15] = {-0.01716200f, -0.03452303f, -0.04022174f, -0.02921014f, -0.00624645f, 0.14111091f, 0.28896755f, 0.00278718f,
@@ -110,17 +103,6 @@ struct ConstOffsets {
   vec<Local> lf_local;   // LfGroup sub-streams with their own tree / code (FramePlan::lf_local; unit = 3 g + k)
   size_t qtable[17 * 3] = {0};
   bool has_qtable[17] = {false};
-};
-
-struct Arena {
-  HostStage& buf;
-  explicit Arena(HostStage& b) : buf(b) {}
-  size_t Put(const void* src, size_t n, size_t align = 256) {
-    const size_t off = Align(buf.size(), align), end = off + std::max<size_t>(n, 4);
-    buf.Resize(end);                                   // (the gap before `off` and a short tail are zeroed)
-    if (n) memcpy(buf.data() + off, src, n);
-    return off;
-  }
 };
 
 void PutCode(Arena& a, const HostCode& c, size_t* ctx, size_t* cfg, size_t* alias, size_t* pc, size_t* po, size_t* ps) {
@@ -281,7 +263,7 @@ DevCode ViewCode(const HostCode& c, const uint8_t* base, size_t ctx, size_t cfg,
 // unfused filter kernels and OutputKernel
 static bool SimpleTransfer(const ImageHeader& ih) { return ih.color_default || (!ih.have_gamma && (ih.tf == 13 || ih.tf == 8)); }
 
-static void FillColor(const ImageHeader& ih, bool do_ycbcr, FrameDev& f) {
+void FillColor(const ImageHeader& ih, bool do_ycbcr, FrameDev& f) {
   float inv[9];
   for (int k = 0; k < 9; k++) inv[k] = ih.opsin_inv[k];
   // images whose header names other primaries / another white point than sRGB / D65: XYB decodes to linear sRGB, the matrix takes it on
@@ -411,8 +393,6 @@ Batch::~Batch() {
   if (device_ >= 0 && cur != device_) (void)hipSetDevice(device_);
   if (clear_stream_) { (void)hipStreamSynchronize((hipStream_t)clear_stream_); (void)hipStreamDestroy((hipStream_t)clear_stream_); }
   if (clear_event_) (void)hipEventDestroy((hipEvent_t)clear_event_);
-  for (void* ev : mod_join_events_) (void)hipEventDestroy((hipEvent_t)ev);
-  if (mod_fork_event_) (void)hipEventDestroy((hipEvent_t)mod_fork_event_);
   if (idct_event_) (void)hipEventDestroy((hipEvent_t)idct_event_);
   if (flags_event_) (void)hipEventDestroy((hipEvent_t)flags_event_);
   if (flags_pinned_) (void)hipHostFree(flags_pinned_);
@@ -888,7 +868,7 @@ static float IntMul(const OutputSpec& o) { const uint32_t full = o.type == 0 ? 8
 // A resized output (OutputSpec::resize_w / resize_h): the write stage leaves the picture — oriented, every slot of the output — as plain interleaved f32 among the pixel planes
 // (big: it lives from the write stage to the resize behind it, like the planes the write stage reads), and ResizeKernel writes the caller's destination from it
 // (EnqueueResizes, resize_target = true: the destination as it is described otherwise, the orientation applied already)
-static OutputDesc FillOutput(const ImageEntry& e, uint8_t* work, uint8_t* big, bool resize_target = false) {
+OutputDesc FillOutput(const ImageEntry& e, uint8_t* work, uint8_t* big, bool resize_target) {
   OutputDesc d{};
   if (e.out.resized() && !resize_target) {
     d.out = big + e.off_resize_src;
@@ -1136,6 +1116,11 @@ size_t Batch::DebugRead(int i, const std::string& name, int c, void* dst, size_t
   return bytes;
 }
 
+void Batch::HashPostOps(uint64_t* h) const {
+  if (lf_batch_) lf_batch_->HashPostOps(h);
+  for (auto& op : post_ops_) for (const char* c = op.first;; c++) { *h = (*h ^ (uint8_t)*c) * 1099511628211ull; if (!*c) break; }   // (each name with its terminating zero)
+}
+
 int64_t Batch::Info(const std::string& name) const {
   if (name == "lf_simt_frames" || name == "lf_legacy_frames") {
     int64_t simt = 0, legacy = 0;
@@ -1143,6 +1128,9 @@ int64_t Batch::Info(const std::string& name) const {
     return name == "lf_simt_frames" ? simt : legacy;
   }
   if (name == "hf_nonzeros") { int64_t t = 0; for (uint32_t v : hf_written_) t += v; return t; }   // non-zero AC coefficients per decode of the batch (known after a Finish)
+  // the frame tail's recorded ops, those of the LF frames' batch first (they run first), and FNV-1a (63 bits) over the names of their stages in order
+  if (name == "post_ops") return (int64_t)post_ops_.size() + (lf_batch_ ? lf_batch_->Info(name) : 0);
+  if (name == "post_ops_hash") { uint64_t h = 1469598103934665603ull; HashPostOps(&h); return (int64_t)(h & 0x7fffffffffffffffull); }
   if (name == "mod_group_lds_bytes") return prepared_ ? (int64_t)ModularGroupLdsBytes(cfg) : -1;
   if (name == "resize_u8_images") return resize_u8_images_;         // images of the last decode whose resize ran in Pillow's 8-bit arithmetic (OutputSpec::resize_u8: ResizeU8Kernel)
   if (name == "resize_launches") return resize_launches_;           // kernel launches the last decode's resizes took (two per group of the table: Batch::EnqueueResizes)
@@ -1474,7 +1462,7 @@ void Batch::PutStreamTables(PrepareState& st) {
     max_lf_groups_ = std::max<int>(max_lf_groups_, p.num_lf_groups);
     max_groups_ = std::max<int>(max_groups_, p.num_groups);
     if (!p.modular && !EndsBehindLf(i)) {
-      // the groups an HF launch that honours the lists decodes for this frame (RunPart 12): those of its region, or all of them
+      // the groups an HF launch that honours the lists decodes for this frame (RunPart kPartJpegHf): those of its region, or all of them
       uint32_t slots = p.num_groups;
       if (JpegRegionUnit(i)) {
         vec<uint32_t> list;
@@ -2171,7 +2159,7 @@ void Batch::Prepare(void* stream_v, bool wait_upload) {
 }
 
 // JXL_HIP_DEBUG_SYNC=1: name every stage on stderr and wait for it (finding the kernel behind a device fault)
-static void DebugSync(const char* what, void* stream) {
+void DebugSync(const char* what, void* stream) {
   static const bool on = getenv("JXL_HIP_DEBUG_SYNC") != nullptr;
   if (!on) return;
   fprintf(stderr, "[jxl-hip] %s ...", what); fflush(stderr);
@@ -2179,529 +2167,8 @@ static void DebugSync(const char* what, void* stream) {
   fprintf(stderr, " %s (launch status: %s)\n", hipGetErrorString(e), hipGetErrorString(hipPeekAtLastError())); fflush(stderr);
 }
 
-void Batch::Run(void* stream_v) { RunPart(stream_v, 0, false); }
+void Batch::Run(void* stream_v) { RunPart(stream_v, kPartWhole, false); }
 
-// Everything Modular after the entropy decode of the global stream: the LfGroup / PassGroup sub-streams, then the
-// host-planned inverse transforms (and, for Modular frames, the write stage).
-void Batch::EnqueueModularTail(void* stream_v) {
-  const int n = (int)images_.size();
-  int max_units = 1;
-  for (auto& im : images_) max_units = std::max<int>(max_units, (int)im->plan.NumModUnits());
-  static const bool dbg = getenv("JXL_HIP_DEBUG_SYNC") != nullptr;
-  auto check = [&](const char* what, int kind) { if (!dbg) return; const hipError_t e = hipGetLastError(); if (e != hipSuccess) fprintf(stderr, "[jxl-hip] launch of %s (%d) rejected: %s\n", what, kind, hipGetErrorString(e)); };
-  check("(before the Modular tail)", -1);
-  LaunchModularGroups(dframes_, n, max_units, cfg, stream_v);
-  check("ModularGroupFastKernel", max_units);
-  // The inverse transforms of different images are independent chains of latency-bound kernels (an inverse Squeeze step is one thread per row / column walking a recurrence:
-  // 32 workgroups for the last step of an 8192 x 8192 channel, ~40 launches per channel).  Images whose chains have the same shape — the frames of a job usually do — go through
-  // them together: step k of up to kSqueezeBatch images is ONE launch (blockIdx.y = image).  Side streams per image gave the same overlap and made every later latency-bound
-  // decode of the process 1.3-1.6x slower (profiles/r06_notes.md section 12); the owner's streams (SetTailStreams) are only used when JXL_HIP_MOD_TAIL_STREAMS asks for them.
-  auto P = [&](size_t off) { return (int32_t*)(dwork_ + off); };
-  auto run_op = [&](int i, const ModOp& op, void* st) {
-    check("Modular tail op before", (int)op.kind);
-    switch (op.kind) {
-      case ModOp::kRct: LaunchModRct(P(op.in[0]), P(op.in[1]), P(op.in[2]), op.n, op.param, st); break;
-      case ModOp::kPalette: {
-        int32_t* outs[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (uint32_t c = 0; c < op.num_c; c++) outs[c] = P(op.out[c]);
-        if (op.nb_deltas == 0 && op.predictor == 0) LaunchModPalette(P(op.in[0]), outs, op.param, op.num_c, op.bits, op.n, st);
-        else LaunchModPaletteDelta(P(op.in[0]), outs, op.param, op.num_c, op.bits, op.nb_deltas, op.predictor, op.aw, op.ah, images_[i]->plan.gwp,
-                                   op.predictor == 6 ? P(op.wp_scratch) : nullptr, op.wp_stride, st);
-        break;
-      }
-      case ModOp::kSqueeze: LaunchModInvSqueeze(P(op.in[0]), P(op.in[1]), P(op.out[0]), op.param, op.aw, op.ah, op.rw, op.rh, st); break;
-      case ModOp::kOutput: {
-        ModOutputArgs a;
-        memset(&a, 0, sizeof(a));
-        a.ncolor = op.num_c;
-        for (uint32_t c = 0; c < a.ncolor; c++) a.color[c] = P(op.in[c]);
-        a.color_factor = op.color_factor; a.float_bits = op.float_bits; a.float_exp_bits = op.float_exp_bits;
-        a.alpha = op.has_alpha ? P(op.in[3]) : nullptr; a.alpha_factor = op.alpha_factor;
-        LaunchModOutput(dframes_, i, a, images_[i]->plan.width, images_[i]->plan.height, st);
-        break;
-      }
-    }
-  };
-  static const int tail_streams = getenv("JXL_HIP_MOD_TAIL_STREAMS") ? atoi(getenv("JXL_HIP_MOD_TAIL_STREAMS")) : 0;
-  static const bool no_batch = getenv("JXL_HIP_NO_SQUEEZE_BATCH") != nullptr;      // A/B: every image's chain on its own
-  vec<int> with_ops;
-  for (int i = 0; i < n; i++) if (!mod_ops_[i].empty()) with_ops.push_back(i);
-  if (tail_streams >= 2 && with_ops.size() >= 2 && tail_streams_) {
-    // (experiments) one chain per side stream of the owner, forked from and joined to stream_v
-    vec<void*> side;
-    for (int k = 0; k < std::min<int>((int)with_ops.size(), tail_streams); k++) { void* st = tail_streams_(k); if (!st) break; side.push_back(st); }
-    if (side.size() >= 2) {
-      while (mod_join_events_.size() < side.size()) { hipEvent_t ev; HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); mod_join_events_.push_back(ev); }
-      if (!mod_fork_event_) { hipEvent_t ev; HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); mod_fork_event_ = ev; }
-      HIP_CHECK(hipEventRecord((hipEvent_t)mod_fork_event_, (hipStream_t)stream_v));
-      for (void* st : side) HIP_CHECK(hipStreamWaitEvent((hipStream_t)st, (hipEvent_t)mod_fork_event_, 0));
-      for (size_t k = 0; k < with_ops.size(); k++) for (const ModOp& op : mod_ops_[with_ops[k]]) run_op(with_ops[k], op, side[k % side.size()]);
-      for (size_t k = 0; k < side.size(); k++) {
-        HIP_CHECK(hipEventRecord((hipEvent_t)mod_join_events_[k], (hipStream_t)side[k]));
-        HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream_v, (hipEvent_t)mod_join_events_[k], 0));
-      }
-      return;
-    }
-  }
-  // groups of images whose chains have the same shape (kind and geometry of every step)
-  auto same_shape = [&](int a, int b) {
-    const vec<ModOp>& x = mod_ops_[a]; const vec<ModOp>& y = mod_ops_[b];
-    if (x.size() != y.size()) return false;
-    for (size_t k = 0; k < x.size(); k++)
-      if (x[k].kind != y[k].kind || x[k].param != y[k].param || x[k].aw != y[k].aw || x[k].ah != y[k].ah || x[k].rw != y[k].rw || x[k].rh != y[k].rh) return false;
-    return true;
-  };
-  vec<char> done((size_t)n, 0);
-  for (int lead : with_ops) {
-    if (done[(size_t)lead]) continue;
-    vec<int> grp;
-    for (int i : with_ops) if (!done[(size_t)i] && (int)grp.size() < kSqueezeBatch && (i == lead || (!no_batch && same_shape(lead, i)))) { grp.push_back(i); done[(size_t)i] = 1; }
-    const vec<ModOp>& ops = mod_ops_[lead];
-    for (size_t k = 0; k < ops.size(); k++) {
-      if (ops[k].kind == ModOp::kSqueeze && grp.size() > 1) {
-        check("Modular tail op before", (int)ops[k].kind);
-        SqueezeBatch b;
-        memset(&b, 0, sizeof(b));
-        for (size_t g = 0; g < grp.size(); g++) { const ModOp& o = mod_ops_[grp[g]][k]; b.avg[g] = P(o.in[0]); b.res[g] = P(o.in[1]); b.out[g] = P(o.out[0]); }
-        LaunchModInvSqueezeBatch(b, (int)grp.size(), ops[k].param, ops[k].aw, ops[k].ah, ops[k].rw, ops[k].rh, stream_v);
-      } else {
-        for (int i : grp) run_op(i, mod_ops_[i][k], stream_v);
-      }
-    }
-  }
-}
-
-// Builds the list of kernels that undo the global transforms of Modular image i (transform.cc, reverse order) and feed
-// the write stage, tracking the channel list on the host exactly as MetaApply built it; `take` reserves work-arena bytes.
-void Batch::PlanModularUndo(int i, const std::function<size_t(size_t)>& take) {
-  const ImageEntry& e = *images_[i]; const FramePlan& p = e.plan;
-  struct HC { size_t off; uint32_t w, h; };
-  vec<HC> list;
-  for (size_t k = 0; k < p.gchannels.size(); k++) list.push_back({mod_plane_offsets_[i][k], p.gchannels[k].w, p.gchannels[k].h});
-  vec<ModOp>& ops = mod_ops_[i];
-  ops.clear();
-  for (int t = (int)p.gtransforms.size() - 1; t >= 0; t--) {
-    const TransformDesc& td = p.gtransforms[t];
-    if (td.id == 0) {
-      if (td.begin_c + 3 > list.size()) throw ParseError("rct range", false);
-      const HC &a = list[td.begin_c], &b = list[td.begin_c + 1], &c = list[td.begin_c + 2];
-      if (a.w != b.w || a.w != c.w || a.h != b.h || a.h != c.h) throw ParseError("rct over channels of different size", false);
-      ModOp op; op.kind = ModOp::kRct; op.in[0] = a.off; op.in[1] = b.off; op.in[2] = c.off; op.n = (size_t)a.w * a.h; op.param = td.rct_type;
-      ops.push_back(op);
-    } else if (td.id == 1) {
-      // list[0] = palette, list[begin_c + 1] = index channel -> num_c channels in its place
-      if (td.begin_c + 1 >= list.size()) throw ParseError("palette range", false);
-      const HC idx = list[td.begin_c + 1];
-      ModOp op; op.kind = ModOp::kPalette; op.in[0] = list[0].off; op.num_c = td.num_c; op.param = td.nb_colors;
-      op.bits = std::min<uint32_t>(e.ih.depth.bits, 24); op.n = (size_t)idx.w * idx.h;
-      if (td.num_c > 4) throw ParseError("unsupported: palette with more than 4 channels", true);
-      op.out[0] = idx.off;
-      for (uint32_t c = 1; c < td.num_c; c++) op.out[c] = take(op.n * 4 + 64);
-      op.nb_deltas = td.nb_deltas; op.predictor = td.predictor; op.aw = idx.w; op.ah = idx.h;
-      if (td.predictor == 6) { op.wp_stride = 10 * (idx.w + 2); op.wp_scratch = take((size_t)op.wp_stride * 4 * td.num_c); }   // weighted-predictor state per output channel
-      ops.push_back(op);
-      vec<HC> nl;
-      for (size_t k = 1; k < list.size(); k++) {
-        if (k - 1 == td.begin_c) { for (uint32_t c = 0; c < td.num_c; c++) nl.push_back({op.out[c], idx.w, idx.h}); }
-        else nl.push_back(list[k]);
-      }
-      list.swap(nl);
-    } else {
-      for (int q = (int)td.squeeze.size() - 1; q >= 0; q--) {
-        const SqueezeStep& sq = td.squeeze[q];
-        const uint32_t endc = sq.begin_c + sq.num_c - 1;
-        const uint32_t offset = sq.in_place ? endc + 1 : (uint32_t)(list.size() + sq.begin_c - endc - 1);
-        if (offset + sq.num_c > list.size() || endc >= offset) throw ParseError("squeeze range", false);
-        for (uint32_t c = sq.begin_c; c <= endc; c++) {
-          const HC avg = list[c], res = list[offset + c - sq.begin_c];
-          ModOp op; op.kind = ModOp::kSqueeze; op.param = sq.horizontal; op.in[0] = avg.off; op.in[1] = res.off;
-          op.aw = avg.w; op.ah = avg.h; op.rw = res.w; op.rh = res.h;
-          HC out;
-          if (sq.horizontal) { if (avg.h != res.h) throw ParseError("squeeze dims", false); out = {0, avg.w + res.w, avg.h}; }
-          else { if (avg.w != res.w) throw ParseError("squeeze dims", false); out = {0, avg.w, avg.h + res.h}; }
-          out.off = take((size_t)out.w * out.h * 4 + 64);
-          op.out[0] = out.off;
-          ops.push_back(op);
-          list[c] = out;
-        }
-        list.erase(list.begin() + offset, list.begin() + offset + sq.num_c);
-      }
-    }
-  }
-  ModOp op; op.kind = ModOp::kOutput; op.num_c = p.nb_color_channels;   // (0 for VarDCT frames: only extra channels are Modular)
-  if (list.size() < op.num_c + e.ih.extra.size()) throw ParseError("modular channel list", false);
-  for (size_t k = 0; k < op.num_c + e.ih.extra.size(); k++)
-    if (list[k].w != p.width || list[k].h != p.height) throw ParseError("unsupported: channel of a different size than the image (dim_shift)", true);
-  for (uint32_t c = 0; c < op.num_c; c++) op.in[c] = list[c].off;
-  op.color_factor = e.ih.depth.is_float ? 1.0f : 1.0f / (float)((1u << e.ih.depth.bits) - 1);
-  op.float_bits = e.ih.depth.is_float ? e.ih.depth.bits : 0; op.float_exp_bits = e.ih.depth.exp_bits;
-  const int alpha_pick = images_[pub_[e.pub_index].first_unit]->out.alpha_from_extra;
-  for (size_t k = 0; k < e.ih.extra.size(); k++) if (alpha_pick >= 0 ? (int)k == alpha_pick : e.ih.extra[k].type == 0) {
-    op.has_alpha = true; op.in[3] = list[op.num_c + k].off;
-    op.alpha_factor = e.ih.extra[k].depth.is_float ? 1.0f : 1.0f / (float)((1u << e.ih.extra[k].depth.bits) - 1);   // (float alpha: converted in the frame tail)
-    break;
-  }
-  if (e.complex) {
-    // frames of complex images end in float planes: the tail converts these integer planes itself (PlanPostOps)
-    ComplexBufs& cb = cbufs_[i];
-    cb.nb_color_int = op.num_c;
-    for (uint32_t c = 0; c < op.num_c; c++) cb.color_int[c] = list[c].off;
-    cb.ec_int.clear();
-    for (size_t k = 0; k < e.ih.extra.size(); k++) cb.ec_int.push_back(list[op.num_c + k].off);
-    return;
-  }
-  if (p.modular) ops.push_back(op);
-  else vardct_alpha_[i] = VarDctAlpha{op.has_alpha, op.in[3], op.alpha_factor};   // the VarDCT write stage reads the plane itself
-}
-
-// ---- frame tail of complex images -------------------------------------------------------------------------------------------------
-// Walks the frames of every complex image in codestream order and records, as closures over device addresses, the kernels
-// that turn each frame's planes into the image: dec_cache.cc PreparePipeline's stage order (patches, splines, upsampling,
-// noise | save as reference before the colour transform | XYB / YCbCr -> output colour space | blending onto the canvas |
-// save as reference | write).  Reference slots are tracked here (frame_header.cc save_as_reference / CanBeReferenced).
-void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
-  Arena arena(hconst);
-  struct Slot { bool valid = false, before_ct = false; size_t p[3] = {0, 0, 0}; uint32_t stride = 0; vec<size_t> ec; uint32_t ec_stride = 0; uint32_t w = 0, h = 0; };
-  auto B = [this](size_t off) { return (float*)(dbig_ + off); };
-  // channel tables of the frames with extra channels (kernels.h EcChanDev): a frame's table takes its place in the constant arena when the frame's
-  // plan starts and is filled step by step; the finished tables are copied into the arena once every frame is planned (the end of this function)
-  struct PendingTable { size_t off; vec<EcChanDev> entries; };
-  std::deque<PendingTable> tables;
-  for (const PubImage& pi : pub_) {
-    if (!pi.complex) continue;
-    Slot slots[4];
-    const ImageEntry& first = *images_[pi.first_unit];
-    const ImageHeader& ih = first.ih;
-    const uint32_t ne = (uint32_t)ih.extra.size();
-    bool has_spot = false;
-    for (uint32_t k = 0; k < ne; k++) has_spot |= ih.extra[k].type == 2;
-    const bool render_spots = has_spot && first.out.render_spotcolors;
-    // the write stage's arguments: colour planes, the alpha the caller's layout takes (the picked extra channel, else the first of type alpha), w x h samples
-    auto write_args = [&](const size_t p[3], uint32_t stride, const vec<size_t>& ec, uint32_t ec_stride, uint32_t w, uint32_t h) {
-      WriteArgs wa;
-      memset(&wa, 0, sizeof(wa));
-      for (int c = 0; c < 3; c++) wa.p[c] = B(p[c]);
-      wa.stride = stride;
-      for (uint32_t k = 0; k < ne; k++) if (first.out.alpha_from_extra >= 0 ? (int)k == first.out.alpha_from_extra : ih.extra[k].type == 0) {
-        wa.alpha = B(ec[k]); wa.alpha_stride = ec_stride;
-        wa.unpremul = first.out.unpremul_alpha && ih.extra[k].alpha_associated && (first.out.num_channels == 2 || first.out.num_channels == 4);
-        break;
-      }
-      wa.img_w = w; wa.img_h = h;
-      wa.od = FillOutput(first, dwork_, dbig_);
-      return wa;
-    };
-    for (int u = pi.first_unit; u < pi.first_unit + pi.num_units; u++) {
-      const ImageEntry& e = *images_[u];
-      const FramePlan& p = e.plan;
-      const ComplexBufs& cb = cbufs_[u];
-      const uint32_t cw = p.width, ch = p.height, fw = p.frame_w, fh = p.frame_h;
-      // current planes of the frame: after the restoration filters (VarDCT) / the int -> float conversion (Modular)
-      const uint32_t nstages = p.modular ? 0 : (p.lf.gab ? 1 : 0) + (p.lf.epf_iters >= 3 ? 3 : p.lf.epf_iters);
-      size_t cur[3]; uint32_t cur_stride = p.bw * 8;
-      for (int c = 0; c < 3; c++) cur[c] = (nstages & 1) ? cb.pb[c] : cb.pa[c];
-      vec<size_t> cur_ec(ne, 0); uint32_t cur_ec_stride = cw;
-      // the extra-channel steps below read the frame's channel table in device memory (`tables` above); without extra channels it is empty and they are skipped
-      tables.emplace_back();
-      vec<EcChanDev>& tbl = tables.back().entries;
-      tbl.assign(ne, EcChanDev{});
-      const size_t o_tab = tables.back().off = arena.Put(tbl.data(), ne * sizeof(EcChanDev));
-      auto DT = [this, o_tab]() { return (const EcChanDev*)(dconst_ + o_tab); };
-      if (p.subsampled) {
-        // the subsampled channels sit in the top-left corner of their planes: bring them to full resolution (plane b)
-        for (int c = 0; c < 3; c++) {
-          if (!p.hs[c] && !p.vs[c]) continue;
-          if (cb.pb[c] == (size_t)-1) throw ParseError("chroma upsampling needs the second plane set", false);
-          const size_t src = cur[c], dst = cb.pb[c];
-          const uint32_t chs = p.hs[c], cvs = p.vs[c];
-          post_ops_.push_back([=](void* st) { LaunchChromaUpsample(B(src), cur_stride, B(dst), cur_stride, chs, cvs, cw, ch, st); });
-          cur[c] = dst;
-        }
-      }
-      if (p.modular) {
-        const uint32_t bits = ih.depth.bits;
-        if (ih.xyb_encoded) {
-          if (cb.nb_color_int != 3) throw ParseError("XYB Modular frame without three colour channels", false);
-          const size_t cy = cb.color_int[0], cx = cb.color_int[1], cbb = cb.color_int[2];
-          const float fac[3] = {p.m_lf[0], p.m_lf[1], p.m_lf[2]};
-          post_ops_.push_back([=](void* st) {
-            float* dst[3] = {B(cur[0]), B(cur[1]), B(cur[2])};
-            LaunchXybModToFloat((const int32_t*)(dwork_ + cy), (const int32_t*)(dwork_ + cx), (const int32_t*)(dwork_ + cbb), cw, dst, cur_stride, cw, ch, fac, st);
-          });
-        } else {
-          const bool fl = ih.depth.is_float;
-          const float factor = fl ? 1.0f : (float)(1.0 / (double)((1u << bits) - 1));
-          const uint32_t fbits = fl ? ih.depth.bits : 0, febits = ih.depth.exp_bits;
-          for (int c = 0; c < 3; c++) {
-            const size_t src = cb.color_int[cb.nb_color_int == 1 ? 0 : c], dst = cur[c];
-            post_ops_.push_back([=](void* st) { LaunchIntToFloat((const int32_t*)(dwork_ + src), cw, B(dst), cur_stride, cw, ch, factor, st, fbits, febits); });
-          }
-        }
-      }
-      for (uint32_t k = 0; k < ne; k++) {
-        if (k >= cb.ec_int.size()) throw ParseError("missing extra channel", false);
-        const size_t src = cb.ec_int[k], dst = cb.ecf[k];
-        const bool efl = ih.extra[k].depth.is_float;
-        const float factor = efl ? 1.0f : 1.0f / (float)((1u << ih.extra[k].depth.bits) - 1);
-        const uint32_t ebits = efl ? ih.extra[k].depth.bits : 0, eexp = ih.extra[k].depth.exp_bits;
-        EcChanDev& t = tbl[k];
-        t.src_int = (const int32_t*)(dwork_ + src); t.plane = B(dst); t.factor = factor; t.float_bits = ebits; t.float_exp_bits = eexp;
-        t.premul = ih.extra[k].alpha_associated ? 1 : 0; t.type = ih.extra[k].type;
-        for (int c = 0; c < 4; c++) t.spot[c] = ih.extra[k].spot[c];
-        t.fg = t.plane; t.fg_stride = cw;
-        cur_ec[k] = dst;
-      }
-      EcFrameArgs efa;
-      memset(&efa, 0, sizeof(efa));
-      efa.num_extra = ne; efa.w = cw; efa.h = ch; efa.ow = fw; efa.oh = fh; efa.up = p.upsampling;
-      post_ops_.push_back([=](void* st) { EcFrameArgs a = efa; a.table = DT(); LaunchEcIntToFloat(a, st); });
-      // ---- patches
-      if (p.flags & 2) {
-        vec<PatchEntryDev> entries;
-        vec<PatchEcDev> pec;        // [placement * ne + channel]
-        for (const PatchRefH& pr : p.feat.patches) {
-          const Slot& sl = slots[pr.ref];
-          if (!sl.valid) throw ParseError("patch refers to an empty reference slot", false);
-          if (!sl.before_ct) throw ParseError("patch refers to a frame saved after the colour transform", false);
-          if (pr.xsize == 0 || pr.ysize == 0) throw ParseError("empty patch", false);
-          if ((uint64_t)pr.x0 + pr.xsize > sl.w || (uint64_t)pr.y0 + pr.ysize > sl.h) throw ParseError("patch exceeds its reference frame", false);
-          for (const PatchPosH& pp : pr.pos) {
-            if (pp.x + pr.xsize > cw || pp.y + pr.ysize > ch) throw ParseError("patch exceeds the frame", false);
-            PatchEntryDev en;
-            memset(&en, 0, sizeof(en));
-            for (int c = 0; c < 3; c++) en.src[c] = B(sl.p[c]) + (size_t)pr.y0 * sl.stride + pr.x0;
-            if (sl.ec.size() < ne) throw ParseError("patch source without the extra channels", false);
-            if (pp.blend.size() < 1 + ne) throw ParseError("patch blending list", false);
-            for (uint32_t k = 0; k < ne; k++) {
-              const float* esrc = B(sl.ec[k]) + (size_t)pr.y0 * sl.ec_stride + pr.x0;
-              const uint32_t mode = pp.blend[1 + k].mode | (pp.blend[1 + k].alpha_channel << 8) | (pp.blend[1 + k].clamp << 16);
-              if (pp.blend[1 + k].alpha_channel >= ne) throw ParseError("patch alpha channel", false);
-              pec.push_back(PatchEcDev{esrc, mode, 0});
-            }
-            if (ne && pp.blend[0].alpha_channel >= ne) throw ParseError("patch alpha channel", false);
-            en.src_stride = sl.stride; en.esrc_stride = sl.ec_stride;
-            en.x = (int32_t)pp.x; en.y = (int32_t)pp.y; en.xs = pr.xsize; en.ys = pr.ysize;
-            en.mode = pp.blend[0].mode | (pp.blend[0].alpha_channel << 8) | (pp.blend[0].clamp << 16);
-            entries.push_back(en);
-          }
-        }
-        if (!entries.empty()) {
-          // per 32x32 tile: the placements touching it, in dictionary order
-          const uint32_t tx = (cw + 31) / 32, ty = (ch + 31) / 32;
-          vec<vec<uint32_t>> lists((size_t)tx * ty);
-          for (uint32_t k = 0; k < entries.size(); k++) {
-            const PatchEntryDev& en = entries[k];
-            // (sizes are >= 1 and the placement lies inside the frame — checked above; clamped all the same: the lists must not be overrun)
-            const uint32_t y1 = std::min(ty - 1, ((uint32_t)en.y + std::max(en.ys, 1u) - 1) / 32), x1 = std::min(tx - 1, ((uint32_t)en.x + std::max(en.xs, 1u) - 1) / 32);
-            for (uint32_t yy = (uint32_t)en.y / 32; yy <= y1; yy++)
-              for (uint32_t xx = (uint32_t)en.x / 32; xx <= x1; xx++) lists[(size_t)yy * tx + xx].push_back(k);
-          }
-          vec<uint32_t> start(lists.size() + 1, 0), flat;
-          for (size_t t = 0; t < lists.size(); t++) { start[t + 1] = start[t] + (uint32_t)lists[t].size(); flat.insert(flat.end(), lists[t].begin(), lists[t].end()); }
-          if (flat.empty()) flat.push_back(0);
-          const size_t o_e = arena.Put(entries.data(), entries.size() * sizeof(PatchEntryDev)), o_s = arena.Put(start.data(), start.size() * 4), o_l = arena.Put(flat.data(), flat.size() * 4);
-          PatchFrameArgs pa;
-          memset(&pa, 0, sizeof(pa));
-          for (int c = 0; c < 3; c++) pa.p[c] = B(cur[c]);
-          pa.stride = cur_stride; pa.ec_stride = cur_ec_stride; pa.w = cw; pa.h = ch; pa.num_extra = ne;
-          if (cb.ec_tmp.size() < ne) throw ParseError("patch planes of the extra channels", false);
-          for (uint32_t k = 0; k < ne; k++) tbl[k].tmp = B(cb.ec_tmp[k]);
-          const size_t o_p = arena.Put(pec.data(), pec.size() * sizeof(PatchEcDev));
-          post_ops_.push_back([=](void* st) {
-            LaunchPatches(pa, DT(), (const PatchEntryDev*)(dconst_ + o_e), (const PatchEcDev*)(dconst_ + o_p), (const uint32_t*)(dconst_ + o_s), (const uint32_t*)(dconst_ + o_l), st);
-          });
-        }
-      }
-      // ---- splines (segments from the host, host_features.cc)
-      if (p.flags & 16) {
-        SplineDrawList dl;
-        BuildSplineDrawList(p.feat, p.base_x, p.base_b, ch, &dl);
-        if (!dl.segments.empty() && !dl.indices.empty()) {
-          const size_t o_g = arena.Put(dl.segments.data(), dl.segments.size() * sizeof(SplineSegmentDev)), o_r = arena.Put(dl.row_start.data(), dl.row_start.size() * 4),
-                       o_i = arena.Put(dl.indices.data(), dl.indices.size() * 4);
-          post_ops_.push_back([=](void* st) {
-            float* pl[3] = {B(cur[0]), B(cur[1]), B(cur[2])};
-            LaunchSplines(pl, cur_stride, cw, ch, (const SplineSegmentDev*)(dconst_ + o_g), (const uint32_t*)(dconst_ + o_r), (const uint32_t*)(dconst_ + o_i), st);
-          });
-        }
-      }
-      // ---- upsampling to the frame size
-      if (p.upsampling > 1) {
-        const size_t o_w = up_weights_off[u];
-        const uint32_t up = p.upsampling;
-        for (int c = 0; c < 3; c++) {
-          const size_t src = cur[c], dst = cb.up[c]; const uint32_t ss = cur_stride;
-          post_ops_.push_back([=](void* st) { LaunchUpsamplePlane(B(src), ss, cw, ch, B(dst), fw, fw, fh, up, (const float*)(dconst_ + o_w), st); });
-          cur[c] = dst;
-        }
-        for (uint32_t k = 0; k < ne; k++) {
-          tbl[k].up = B(cb.up_ec[k]); tbl[k].fg = tbl[k].up; tbl[k].fg_stride = fw;
-          cur_ec[k] = cb.up_ec[k];
-        }
-        post_ops_.push_back([=](void* st) { EcFrameArgs a = efa; a.table = DT(); a.up_weights = (const float*)(dconst_ + o_w); LaunchEcUpsample(a, st); });
-        cur_stride = fw; cur_ec_stride = fw;
-      }
-      // ---- noise
-      if (p.feat.has_noise) {
-        NoiseArgs na;
-        memset(&na, 0, sizeof(na));
-        for (int c = 0; c < 3; c++) { na.p[c] = B(cur[c]); na.noise[c] = B(cb.noise[c]); }
-        na.stride = cur_stride; na.w = fw; na.h = fh; na.noise_stride = fw; na.group_dim = p.group_dim;
-        na.visible_frame_index = e.visible_frame_index; na.nonvisible_frame_index = e.nonvisible_frame_index;
-        for (int k = 0; k < 8; k++) na.lut[k] = p.feat.noise_lut[k];
-        na.ytox = p.base_x; na.ytob = p.base_b;
-        post_ops_.push_back([=](void* st) { LaunchNoise(na, st); });
-      }
-      if (p.frame_type == 1) {
-        // an LF frame (this batch is another batch's lf_batch_): its planes, before any colour transform, are the LF image of the frame that refers to it
-        const int pub = e.pub_index;
-        const size_t s0 = cur[0], s1 = cur[1], s2 = cur[2];
-        post_ops_.push_back([=](void* st) {
-          if ((size_t)pub >= lf_targets_.size() || !lf_targets_[pub].dst[0]) return;
-          const LfTarget& t = lf_targets_[pub];
-          const size_t src[3] = {s0, s1, s2};
-          for (int c = 0; c < 3; c++)
-            HIP_CHECK(hipMemcpy2DAsync(t.dst[c], (size_t)t.pitch * 4, B(src[c]), (size_t)cur_stride * 4, (size_t)t.w * 4, t.h, hipMemcpyDeviceToDevice, (hipStream_t)st));
-        });
-        continue;
-      }
-      const bool can_ref = !p.is_last && p.frame_type != 1 && (p.duration == 0 || p.save_as_reference != 0);
-      if (can_ref && p.save_before_ct) {
-        Slot& sl = slots[p.save_as_reference];
-        sl.valid = true; sl.before_ct = true; sl.stride = cur_stride; sl.ec_stride = cur_ec_stride; sl.w = fw; sl.h = fh;
-        for (int c = 0; c < 3; c++) sl.p[c] = cur[c];
-        sl.ec = cur_ec;
-      }
-      if (p.frame_type == 2) continue;    // reference-only frames are not displayed
-      // ---- colour transform into the output space
-      bool blends = p.have_crop || p.blend.mode != 0;
-      for (auto& b : p.ec_blend) if (b.mode != 0) blends = true;
-      const bool spot_after_linear = render_spots && p.is_last && !blends;
-      ColorArgs deferred_tf;
-      memset(&deferred_tf, 0, sizeof(deferred_tf));
-      bool have_deferred_tf = false;
-      {
-        ColorArgs ca;
-        memset(&ca, 0, sizeof(ca));
-        ca.w = fw; ca.h = fh; ca.src_stride = cur_stride;
-        ca.mode = ih.xyb_encoded ? 0 : p.do_ycbcr ? 1 : 2;
-        const bool separate = cb.rgb[0] != (size_t)-1;
-        if (ca.mode != 2 || separate) {
-          for (int c = 0; c < 3; c++) { ca.src[c] = B(cur[c]); ca.dst[c] = separate ? B(cb.rgb[c]) : B(cur[c]); }
-          ca.dst_stride = separate ? fw : cur_stride;
-          FrameDev fd;
-          FillColor(ih, p.do_ycbcr, fd);
-          for (int k = 0; k < 9; k++) ca.opsin_inv[k] = fd.opsin_inv[k];
-          for (int k = 0; k < 3; k++) { ca.neg_bias[k] = fd.neg_bias[k]; ca.neg_bias_cbrt[k] = fd.neg_bias_cbrt[k]; }
-          ca.tf_kind = fd.color_mode;
-          for (int k = 0; k < 5; k++) ca.hdr_par[k] = fd.hdr_par[k];
-          ca.inverse_gamma = fd.inverse_gamma;
-          // spot colours are mixed in linear light when the frame goes straight to the output (dec_cache.cc PreparePipeline: XYB stage,
-          // [from-linear + blending], spot stage, from-linear): the transfer function then follows the spot stage
-          if (spot_after_linear && ca.mode == 0) { deferred_tf = ca; deferred_tf.mode = 3; ca.tf_kind = 1; have_deferred_tf = true; }
-          post_ops_.push_back([=](void* st) { LaunchColor(ca, st); });
-          if (separate) { for (int c = 0; c < 3; c++) cur[c] = cb.rgb[c]; cur_stride = fw; }
-        }
-      }
-      if (first.out.only_frame >= 0 && u == pi.first_unit + first.out.only_frame) {
-        // ---- non-coalesced output (JxlDecoderSetCoalescing(false)): this frame's own pixels after the colour transform, frame-sized, not
-        // blended; the frames before it have been composed as usual (it may draw patches from them), the ones after it are not needed
-        const WriteArgs wa = write_args(cur, cur_stride, cur_ec, cur_ec_stride, fw, fh);
-        if (have_deferred_tf) {          // (the transfer function had been put off for a spot-colour stage this output does not run)
-          ColorArgs ta = deferred_tf;
-          for (int c = 0; c < 3; c++) { ta.src[c] = B(cur[c]); ta.dst[c] = B(cur[c]); }
-          ta.src_stride = ta.dst_stride = cur_stride; ta.w = fw; ta.h = fh;
-          post_ops_.push_back([=](void* st) { LaunchColor(ta, st); });
-        }
-        post_ops_.push_back([=](void* st) { LaunchWrite(wa, st); });
-        break;
-      }
-      // ---- blending onto the canvas
-      bool replace_all = p.blend.mode == 0;
-      for (auto& b : p.ec_blend) if (b.mode != 0) replace_all = false;
-      const bool needs_blending = p.have_crop || !replace_all;
-      size_t canvas[3]; vec<size_t> canvas_ec(ne, 0); uint32_t canvas_stride, canvas_ec_stride;
-      if (!needs_blending) {
-        if (fw != ih.xsize || fh != ih.ysize) throw ParseError("frame size differs from the image size without a crop", false);
-        for (int c = 0; c < 3; c++) canvas[c] = cur[c];
-        for (uint32_t k = 0; k < ne; k++) canvas_ec[k] = cur_ec[k];
-        canvas_stride = cur_stride; canvas_ec_stride = cur_ec_stride;
-      } else {
-        auto source = [&](uint32_t idx) -> const Slot* {
-          const Slot& sl = slots[idx];
-          if (!sl.valid) return nullptr;
-          if (sl.before_ct) throw ParseError("blending source was saved before the colour transform", false);
-          if (sl.w != ih.xsize || sl.h != ih.ysize) throw ParseError("blending source has the wrong size", false);
-          return &sl;
-        };
-        BlendArgs ba;
-        memset(&ba, 0, sizeof(ba));
-        for (int c = 0; c < 3; c++) { ba.fg[c] = B(cur[c]); ba.canvas[c] = B(cb.canvas[c]); }
-        ba.fg_stride = cur_stride; ba.fw = fw; ba.fh = fh; ba.x0 = p.x0; ba.y0 = p.y0;
-        ba.canvas_stride = ih.xsize; ba.img_w = ih.xsize; ba.img_h = ih.ysize; ba.num_extra = ne;
-        const Slot* bg = source(p.blend.source);
-        if (bg) { for (int c = 0; c < 3; c++) ba.bg[c] = B(bg->p[c]); ba.bg_stride = bg->stride; }
-        ba.mode = p.blend.mode | (p.blend.alpha_channel << 8) | ((uint32_t)p.blend.clamp << 16);
-        if (p.blend.mode == 2 || p.blend.mode == 3) {
-          if (ne == 0) throw ParseError("alpha blending without extra channels", false);
-          if (p.blend.alpha_channel >= ne) throw ParseError("blend alpha channel", false);
-          if (bg) { ba.bg_alpha = B(bg->ec.at(p.blend.alpha_channel)); ba.bg_alpha_stride = bg->ec_stride; }
-        }
-        for (uint32_t k = 0; k < ne; k++) {
-          const BlendInfoH& bi = p.ec_blend[k];
-          const uint32_t mode = bi.mode | (bi.alpha_channel << 8) | ((uint32_t)bi.clamp << 16);
-          if (bi.alpha_channel >= ne) throw ParseError("blend alpha channel", false);
-          const Slot* eb = source(bi.source);
-          if (eb && eb->ec.size() < ne) throw ParseError("blending source without the extra channels", false);
-          EcChanDev& t = tbl[k];
-          t.mode = mode; t.canvas = B(cb.canvas_ec[k]); t.canvas_stride = ih.xsize;
-          if (eb) { t.bg = B(eb->ec[k]); t.bg_alpha = B(eb->ec[bi.alpha_channel]); t.bg_stride = eb->ec_stride; }
-        }
-        post_ops_.push_back([=](void* st) { LaunchBlend(ba, DT(), st); });
-        for (int c = 0; c < 3; c++) canvas[c] = cb.canvas[c];
-        for (uint32_t k = 0; k < ne; k++) canvas_ec[k] = cb.canvas_ec[k];
-        canvas_stride = ih.xsize; canvas_ec_stride = ih.xsize;
-      }
-      if (can_ref && !p.save_before_ct) {
-        Slot& sl = slots[p.save_as_reference];
-        sl.valid = true; sl.before_ct = false; sl.stride = canvas_stride; sl.ec_stride = canvas_ec_stride; sl.w = ih.xsize; sl.h = ih.ysize;
-        for (int c = 0; c < 3; c++) sl.p[c] = canvas[c];
-        sl.ec = canvas_ec;
-      }
-      // coalescing: the composite of the last frame is what the caller receives — or, for a frame of an animation, the canvas after that frame
-      // ... or, decoded once for all of them (SetOutputAllFrames), after every frame of the list, each canvas to its own slot of the output area
-      int slot = -1;
-      for (size_t k = 0; k < first.deliver_frames.size(); k++) if (first.deliver_frames[k] == u - pi.first_unit) slot = (int)k;
-      const bool all_frames = !first.deliver_frames.empty();
-      const bool deliver = all_frames ? slot >= 0 : (first.out.upto_frame >= 0 ? u == pi.first_unit + first.out.upto_frame : p.is_last);
-      if (!deliver) continue;
-      if (all_frames) {   // (delivery must leave the canvas as it is: the frames behind blend onto it)
-        if (render_spots || have_deferred_tf) throw ParseError("unsupported: all frames of an animation in one decode with spot colours to render", true);
-      }
-      // ---- spot colours (stage_spot.cc): colour = mix * spot + (1 - mix) * colour with mix = solidity * channel, channel by channel
-      if (render_spots) {
-        const size_t c0 = canvas[0], c1 = canvas[1], c2 = canvas[2];
-        const uint32_t use_canvas = needs_blending ? 1 : 0, iw = ih.xsize, ihh = ih.ysize;
-        post_ops_.push_back([=](void* st) { float* pl[3] = {B(c0), B(c1), B(c2)}; LaunchSpot(pl, canvas_stride, DT(), ne, use_canvas, iw, ihh, st); });
-      }
-      if (have_deferred_tf) {
-        ColorArgs ta = deferred_tf;
-        for (int c = 0; c < 3; c++) { ta.src[c] = B(canvas[c]); ta.dst[c] = B(canvas[c]); }
-        ta.src_stride = ta.dst_stride = canvas_stride; ta.w = ih.xsize; ta.h = ih.ysize;
-        post_ops_.push_back([=](void* st) { LaunchColor(ta, st); });
-      }
-      // ---- write stage
-      WriteArgs wa = write_args(canvas, canvas_stride, canvas_ec, canvas_ec_stride, ih.xsize, ih.ysize);
-      if (all_frames) wa.od.out += (size_t)slot * (first.out_size + 64);
-      post_ops_.push_back([=](void* st) { LaunchWrite(wa, st); });
-      if (all_frames && slot + 1 < (int)first.deliver_frames.size()) continue;
-      break;                      // (frames behind the delivered one: nothing of theirs is needed)
-    }
-  }
-  for (const PendingTable& t : tables) if (!t.entries.empty()) memcpy(hconst.data() + t.off, t.entries.data(), t.entries.size() * sizeof(EcChanDev));
-}
-
-void Batch::EnqueuePostOps(void* stream) { for (auto& op : post_ops_) op(stream); }
 // Resized outputs: behind everything that writes pixels (the write kernels of plain frames, the Modular tail, the frame tail), on the same stream
 // (one launch pair per group of the table Prepare left in the constant arena: kernels_features.hip ResizeKernel)
 void Batch::EnqueueResizes(void* stream) {
@@ -2731,23 +2198,21 @@ void Batch::CheckFilterBuffers() const {
     throw ParseError("force_unfused_filters must be set before Prepare (the second pixel plane is only allocated when a frame needs it)", false);
 }
 
-void Batch::RunTimed(void* stream_v) { RunPart(stream_v, 0, true); }
+void Batch::RunTimed(void* stream_v) { RunPart(stream_v, kPartWhole, true); }
 
-// part 0 = whole decode, 1 = front (coefficient clear + LF decode + LF post-processing), 2 = rest (HF decode, IDCT,
-// filters, output).  Front and rest of one decode may be enqueued on different streams (ordered by the caller with
-// events) so that the latency-bound LF stage of the next batch overlaps the bandwidth stages of the current one.
 // A launch the runtime refuses (too much LDS, an empty grid ...) does not fail at the call site: it leaves an error code that the next runtime call of the thread
-// reports — possibly somebody else's.  Every enqueued part ends with this check, so that such a launch fails the decode it belongs to, by name.
+// reports — possibly somebody else's.  Every enqueued stage ends with this check, so that such a launch fails the decode it belongs to, by name.
 static void CheckLaunches(const char* what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw ParseError(std::string("kernel launch rejected by the runtime (") + what + "): " + hipGetErrorString(e), false);
 }
 
-void Batch::RunPart(void* stream_v, int part, bool timed) {
-  // part 0 = whole decode, 1 = front (LF decode + LF post-processing), 2 = rest (HF decode, IDCT, filters, output);
-  // the rest can be enqueued in two pieces, 3 = HF decode only, 4 = everything after it, so that a caller can record an
-  // event between them (bench.py starts the LF stage of a later batch when an HF stage has ended, not when it starts).
-  hipStream_t stream = (hipStream_t)stream_v;
+// Enqueues the stages of `part` (decode_parts.h) on the stream, in order.  The parts of one decode may be enqueued on different streams (ordered by the caller with
+// events): front and rest, so that the latency-bound LF stage of the next batch overlaps the bandwidth stages of the current one; the HF stage on its own, so that a
+// caller can record an event behind it (bench.py starts the LF stage of a later batch when an HF stage has ended, not when it starts); the LF decode apart from the LF
+// post-processing, whose kernels wait for wavefront slots beside the pixel kernels of the batch before and which only the IDCT and the filters need; the IDCT apart
+// from the pixel stage, so that a caller that rotates coefficient sets lets the next HF stage of that set start behind it.
+void Batch::RunPart(void* stream_v, DecodePart part, bool timed) {
   if (!prepared_) Prepare(stream_v);
   // (whatever an earlier runtime call of this thread left unread is not this decode's — it is named on stderr once, not silently dropped, and then cleared so that
   // the checks behind this part's launches report this part's launches only)
@@ -2756,154 +2221,149 @@ void Batch::RunPart(void* stream_v, int part, bool timed) {
     if (!told.exchange(true)) fprintf(stderr, "[jxl-hip] a HIP error left pending by an earlier call on this thread (not by this decode) is being cleared: %s\n", hipGetErrorString(stale));
     (void)hipGetLastError();
   }
-  const int n = (int)images_.size();
   if (any_vardct_) CheckFilterBuffers();
-  // The front, too, comes in two pieces: 5 = LF decode (what the HF stage needs: block info, varblock lists, coefficient offsets),
-  // 6 = LF post-processing (dequantised LF, LLF, EPF sigma: what the IDCT and the filters need) — a pipelined caller lets the HF stage
-  // wait for piece 5 only, so that the post-processing kernels, which wait for wavefront slots beside the pixel kernels of the batch
-  // before, are off the critical path.
-  // 11 = piece 6 without its kernels, for a decode whose tail reads nothing they produce (the libjpeg-exact tail below): only the stage mark is recorded
-  const bool do_lf = part == 0 || part == 1 || part == 5, do_lfpost = part == 0 || part == 1 || part == 6 || part == 11, do_front = do_lf || do_lfpost;
-  // ... and so may the tail: 7 = IDCT (the last stage that touches the coefficient planes: a caller that rotates coefficient sets lets the next
-  // HF stage of that set start behind it), 8 = restoration filters, colour, write
-  // The libjpeg-exact tail of JPEG transcodes (PlanJpegPixels / EnqueueJpegPixelTable first) takes the places of 7 and 8: 9 = integer IDCT over the HF planes, which
-  // zeroes what it reads like the float IDCT, 10 = chroma upsampling, colour, write, resizes.
-  const bool jpeg_tail = part == 9 || part == 10;
-  // 12 = 3 for a libjpeg-exact decode (its tail, 9 / 10, follows): frames decoded by region (jpeg_region) decode the groups of their lists only; every other part that
-  // runs the HF stage decodes every group
-  const bool hf_by_list = part == 12 && jpeg_region;
-  if (part == 12) hf_by_region_ = hf_by_list; else if (part == 0 || part == 2 || part == 3) hf_by_region_ = false;      // (what StageBytes describes: the HF stage enqueued last)
-  const bool do_hf = part == 0 || part == 2 || part == 3 || part == 12, do_tail = part == 0 || part == 2 || part == 4 || part == 7 || part == 8 || jpeg_tail;
-  const bool do_idct = do_tail && part != 8 && part != 10, do_post = do_tail && part != 7 && part != 9;
-  const bool split = part != 0;                       // halves timed separately
-  if (do_hf || do_tail) ran_once_ = true;
-  if (do_hf) decodes_since_finish_++;
-  vec<void*>* evs = nullptr;
+  const PartPlan plan = PlanOf(part);
+  const bool tail = plan.has(kStageIdct) || plan.has(kStagePixels);
+  if (plan.has(kStageHf)) hf_by_region_ = plan.jpeg && jpeg_region;      // (what StageBytes describes: the HF stage enqueued last)
+  if (plan.has(kStageHf) || tail) ran_once_ = true;
+  if (plan.has(kStageHf)) decodes_since_finish_++;
+  // the row of events a timed part records into: the LF stage opens one; LF post-processing goes into the row opened last, the rest into the oldest row still open
+  vec<void*>* marks = nullptr;
   if (timed) {
-    if (do_lf) { timed_events_.emplace_back(9, nullptr); }
-    if (timed_events_.empty()) timed_events_.emplace_back(9, nullptr);
-    evs = !do_front ? &timed_events_[timed_rest_cursor_ < timed_events_.size() ? timed_rest_cursor_ : timed_events_.size() - 1] : &timed_events_.back();
+    if (plan.has(kStageLf) || timed_events_.empty()) timed_events_.emplace_back(kNumMarks, nullptr);
+    const bool front = plan.has(kStageLf) || plan.has(kStageLfPost);
+    marks = front ? &timed_events_.back() : &timed_events_[std::min(timed_rest_cursor_, timed_events_.size() - 1)];
   }
-  auto rec = [&](int i) {
-    if (!evs) return;
-    hipEvent_t ev; HIP_CHECK(hipEventCreate(&ev)); (*evs)[i] = ev;
-    HIP_CHECK(hipEventRecord(ev, stream));
-  };
-  if (do_lf) {
-    rec(0);
-    DebugSync("start", stream_v);
-    if (any_modchan_) LaunchModularGlobal(dframes_, n, cfg, stream_v);   // Modular frames; extra channels of VarDCT frames
-    DebugSync("modular global", stream_v);
-    cfg.lf_head_start = part == 1 || part == 5;   // front enqueued on its own: a pipelined caller, the HF stage of another batch is about to start
-    if (any_vardct_) LaunchLfDecode(dframes_, n, max_lf_groups_, cfg, stream_v, &lf_simt_, &trace_);
-    cfg.lf_wide_once = 0;
-    DebugSync("LF decode", stream_v);
-    CheckLaunches("LF stage");
-    if (any_vardct_ && !cfg.idct_flags_known && part != 0 && !cfg.no_flag_wait) {
-      // a caller that enqueues the stages separately: the placement flags travel to pinned host memory behind the LF stage, and the tail —
-      // enqueued steps later — waits for that copy (long done by then) instead of launching every IDCT kernel variant
-      if (!flags_pinned_ || flags_pinned_n_ < (size_t)n) {
-        if (flags_pinned_) (void)hipHostFree(flags_pinned_);      // (waits for the device: the capacity is generous so that a refilled batch object rarely gets here)
-        flags_pinned_ = nullptr;
-        const size_t cap = std::max<size_t>(4096, 2 * (size_t)n);
-        HIP_CHECK(hipHostMalloc((void**)&flags_pinned_, cap * 4));
-        flags_pinned_n_ = cap;
-      }
-      if (!flags_event_) { hipEvent_t ev; HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); flags_event_ = ev; }
-      HIP_CHECK(hipMemcpyAsync(flags_pinned_, dwork_ + flags_off_, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-      HIP_CHECK(hipEventRecord((hipEvent_t)flags_event_, stream));
-      flags_pending_ = true;
-    }
-    rec(1);
-  }
-  if (do_lfpost) {
-    if (part != 11) {
-      if (lf_batch_) lf_batch_->RunPart(stream_v, 0, false);     // LF frames: decoded to the end, their planes copied into the LF planes of the units that refer to them
-      if (any_vardct_) LaunchLfPost(dframes_, n, max_bw_, max_bh_, max_groups_, stream_v);
-      DebugSync("LF post", stream_v);
-      CheckLaunches("LF post-processing");
-    }
-    if (part == 1 || part == 6 || part == 11) rec(2);
-  }
-  if (!any_vardct_) {
-    if (do_hf) { rec(split ? 7 : 2); rec(3); }
-    if (do_tail) {
-      if (do_idct) rec(4);
-      if (do_post) {
-        rec(5);
-        if (any_modchan_ && !jpeg_tail) EnqueueModularTail(stream_v);      // (no image of such a batch takes the libjpeg-exact tail: nothing is written)
-        if (any_complex_ && !jpeg_tail) EnqueuePostOps(stream_v);
-        if (!jpeg_tail) EnqueueResizes(stream_v);
-        CheckLaunches("Modular sub-streams / frame tail");
-        rec(6);
-        if (timed && split) timed_rest_cursor_++;
-      }
-    }
-    return;
-  }
-  if (do_hf) {
-    // the HF decoder only writes non-zero coefficients into cleared planes (outside the per-stage brackets when the
-    // halves are timed separately)
-    // (a batch of 1:8 frames only, any_full_vardct_ == false: no coefficient plane exists, nothing of this stage, of the IDCT or of the filters is launched)
-    if (any_full_vardct_) ClearCoefficientsBeforeHf(stream_v);
-    rec(split ? 7 : 2);
-    // (progressive flush at the kDC step: no AC group is decoded — the planes stay zero, the IDCT sees the LF part only)
-    cfg.hf_by_list = hf_by_list ? 1 : 0;
-    if (!cfg.skip_hf && any_full_vardct_) LaunchHfDecode(dframes_, n, hf_by_list ? max_hf_slots_ : max_groups_, cfg, stream_v, &trace_);
-    cfg.hf_by_list = 0;
-    DebugSync("HF decode", stream_v);
-    if (any_modchan_) EnqueueModularTail(stream_v);   // (the PassGroup Modular parts start where the HF streams ended)
-    if (any_full_vardct_) LaunchZeroFailedCoefficients(dframes_, n, stream_v);   // (frames that failed up to here are skipped by the IDCT kernels: their planes are zeroed now)
-    CheckLaunches("HF stage / Modular sub-streams");
-    rec(3);
-  }
-  if (do_tail) {
-    if (!cfg.idct_flags_known && flags_pending_ && part != 0 && any_full_vardct_ && !jpeg_tail) {      // (the libjpeg-exact tail has one IDCT kernel: nothing to wait for)
-      HIP_CHECK(hipEventSynchronize((hipEvent_t)flags_event_));
-      ApplyIdctFlags(flags_pinned_);
-      flags_pending_ = false;
-    }
-    if (do_idct) {
-      if (split) rec(8);                        // the tail may sit on another stream than the HF stage: its own start mark
-      if (jpeg_tail) EnqueueJpegIdct(stream_v);
-      else if (any_full_vardct_) LaunchIdct(dframes_, n, max_groups_, max_bw_, max_bh_, cfg, stream_v);
-      DebugSync("IDCT", stream_v);
-      CheckLaunches("IDCT stage");
-      rec(4);
-      if (any_full_vardct_) ClearCoefficientsAfterDecode(stream_v);   // (the IDCT kernels zeroed what they read)
-    }
-    if (do_post && jpeg_tail) {
-      rec(5);
-      EnqueueJpegColorOut(stream_v);
-      EnqueueResizes(stream_v);
-      DebugSync("JPEG pixels", stream_v);
-      CheckLaunches("JPEG pixels");
-      rec(6);
-      if (timed && split) timed_rest_cursor_++;
-    } else if (do_post) {
-      if (cfg.debug_stop_after != 1 && any_full_vardct_) LaunchFilters(dframes_, n, max_w_, max_h_, fplan_, cfg, stream_v);
-      DebugSync("filters", stream_v);
-      rec(5);
-      if (!cfg.debug_stop_after && any_full_vardct_) LaunchOutput(dframes_, n, max_w_, max_h_, fplan_, cfg, stream_v);
-      if (!cfg.debug_stop_after && any_scaled_) LaunchLfOutput(dframes_, n, max_bw_, max_bh_, stream_v);   // 1:8 frames: the LF image through the colour transform and the write stage
-      if (any_complex_ && !cfg.debug_stop_after) EnqueuePostOps(stream_v);   // frame tail of multi-frame / feature images
-      if (!cfg.debug_stop_after) EnqueueResizes(stream_v);
-      FailJpegScaledOutputs(stream_v);
-      DebugSync("output / frame tail", stream_v);
-      CheckLaunches("filters / output / frame tail");
-      rec(6);
-      if (timed && split) timed_rest_cursor_++;
-    }
-  }
+  const PartRun r{stream_v, plan, timed, marks};
+  if (plan.has(kStageLf)) StageLf(r);
+  if (plan.has(kStageLfPost)) StageLfPost(r);
+  if (plan.has(kStageHf)) StageHf(r);
+  if (plan.has(kStageIdct)) StageIdct(r);
+  if (plan.has(kStagePixels)) StagePixels(r);
 }
 
-// (tracing) when the nine stage marks of the timed decode recorded last were reached, in ms after `ref_event`: LF start, LF end, LF post end, HF end, IDCT end,
-// filters end, output end, HF start, IDCT start; -1 = not recorded
-void Batch::DebugTimeline(void* ref_event, float out[9]) {
-  for (int i = 0; i < 9; i++) out[i] = -1;
+void Batch::RecordMark(const PartRun& r, Mark m) {
+  if (!r.marks) return;
+  hipEvent_t ev; HIP_CHECK(hipEventCreate(&ev)); (*r.marks)[m] = ev;
+  HIP_CHECK(hipEventRecord(ev, (hipStream_t)r.stream));
+}
+
+void Batch::StageLf(const PartRun& r) {
+  const int n = (int)images_.size();
+  RecordMark(r, kMarkLfStart);
+  DebugSync("start", r.stream);
+  if (any_modchan_) LaunchModularGlobal(dframes_, n, cfg, r.stream);   // Modular frames; extra channels of VarDCT frames
+  DebugSync("modular global", r.stream);
+  cfg.lf_head_start = r.plan.lf_head_start;
+  if (any_vardct_) LaunchLfDecode(dframes_, n, max_lf_groups_, cfg, r.stream, &lf_simt_, &trace_);
+  cfg.lf_wide_once = 0;
+  DebugSync("LF decode", r.stream);
+  CheckLaunches("LF stage");
+  if (any_vardct_ && !cfg.idct_flags_known && r.plan.split && !cfg.no_flag_wait) EnqueueFlagReadback(r.stream);
+  RecordMark(r, kMarkLfEnd);
+}
+
+// A caller that enqueues the stages separately: the placement flags travel to pinned host memory behind the LF stage, and the tail —
+// enqueued steps later — waits for that copy (long done by then) instead of launching every IDCT kernel variant
+void Batch::EnqueueFlagReadback(void* stream) {
+  const size_t n = images_.size();
+  if (!flags_pinned_ || flags_pinned_n_ < n) {
+    if (flags_pinned_) (void)hipHostFree(flags_pinned_);      // (waits for the device: the capacity is generous so that a refilled batch object rarely gets here)
+    flags_pinned_ = nullptr;
+    const size_t cap = std::max<size_t>(4096, 2 * n);
+    HIP_CHECK(hipHostMalloc((void**)&flags_pinned_, cap * 4));
+    flags_pinned_n_ = cap;
+  }
+  if (!flags_event_) { hipEvent_t ev; HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); flags_event_ = ev; }
+  HIP_CHECK(hipMemcpyAsync(flags_pinned_, dwork_ + flags_off_, n * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_CHECK(hipEventRecord((hipEvent_t)flags_event_, (hipStream_t)stream));
+  flags_pending_ = true;
+}
+void Batch::WaitForIdctFlags(const PartRun& r) {
+  if (cfg.idct_flags_known || !flags_pending_ || !r.plan.split || !any_full_vardct_ || r.plan.jpeg) return;      // (the libjpeg-exact tail has one IDCT kernel: nothing to wait for)
+  HIP_CHECK(hipEventSynchronize((hipEvent_t)flags_event_));
+  ApplyIdctFlags(flags_pinned_);
+  flags_pending_ = false;
+}
+
+void Batch::StageLfPost(const PartRun& r) {
+  if (!r.plan.jpeg) {
+    if (lf_batch_) lf_batch_->RunPart(r.stream, kPartWhole, false);     // LF frames: decoded to the end, their planes copied into the LF planes of the units that refer to them
+    if (any_vardct_) LaunchLfPost(dframes_, (int)images_.size(), max_bw_, max_bh_, max_groups_, r.stream);
+    DebugSync("LF post", r.stream);
+    CheckLaunches("LF post-processing");
+  }
+  if (r.plan.split) RecordMark(r, kMarkLfPostEnd);      // (the whole decode: the HF stage records it, behind the coefficient clear)
+}
+
+// With VarDCT frames in the batch the Modular sub-streams and tail run here (the PassGroup Modular parts start where the HF streams ended); without, in the pixel stage.
+void Batch::StageHf(const PartRun& r) {
+  const int n = (int)images_.size();
+  // the HF decoder only writes non-zero coefficients into cleared planes (outside the per-stage brackets when the halves are timed separately)
+  // (a batch of 1:8 frames only, any_full_vardct_ == false: no coefficient plane exists, nothing of this stage, of the IDCT or of the filters is launched)
+  if (any_full_vardct_) ClearCoefficientsBeforeHf(r.stream);
+  RecordMark(r, r.plan.split ? kMarkHfStart : kMarkLfPostEnd);
+  if (any_vardct_) {
+    // (progressive flush at the kDC step, cfg.skip_hf: no AC group is decoded — the planes stay zero, the IDCT sees the LF part only)
+    const bool by_list = hf_by_region_;      // frames decoded by region decode the groups of their lists only; every other HF stage decodes every group
+    cfg.hf_by_list = by_list ? 1 : 0;
+    if (!cfg.skip_hf && any_full_vardct_) LaunchHfDecode(dframes_, n, by_list ? max_hf_slots_ : max_groups_, cfg, r.stream, &trace_);
+    cfg.hf_by_list = 0;
+    DebugSync("HF decode", r.stream);
+    if (any_modchan_) EnqueueModularTail(r.stream);
+    if (any_full_vardct_) LaunchZeroFailedCoefficients(dframes_, n, r.stream);   // (frames that failed up to here are skipped by the IDCT kernels: their planes are zeroed now)
+    CheckLaunches("HF stage / Modular sub-streams");
+  }
+  RecordMark(r, kMarkHfEnd);
+}
+
+void Batch::StageIdct(const PartRun& r) {
+  WaitForIdctFlags(r);
+  if (any_vardct_) {
+    if (r.plan.split) RecordMark(r, kMarkIdctStart);                        // the tail may sit on another stream than the HF stage: its own start mark
+    if (r.plan.jpeg) EnqueueJpegIdct(r.stream);
+    else if (any_full_vardct_) LaunchIdct(dframes_, (int)images_.size(), max_groups_, max_bw_, max_bh_, cfg, r.stream);
+    DebugSync("IDCT", r.stream);
+    CheckLaunches("IDCT stage");
+  }
+  RecordMark(r, kMarkIdctEnd);
+  if (any_full_vardct_) ClearCoefficientsAfterDecode(r.stream);   // (the IDCT kernels zeroed what they read)
+}
+
+// Restoration filters | colour and write of plain frames, the 1:8 frames' LF image, (batches without VarDCT frames) the Modular sub-streams and tail, the frame tail of
+// multi-frame / feature images, resizes.  The libjpeg-exact flavour: chroma upsampling, colour, write, resizes (no image of a batch without VarDCT frames takes it).
+void Batch::StagePixels(const PartRun& r) {
+  const int n = (int)images_.size();
+  WaitForIdctFlags(r);
+  if (r.plan.jpeg) {
+    RecordMark(r, kMarkFiltersEnd);
+    if (any_vardct_) { EnqueueJpegColorOut(r.stream); EnqueueResizes(r.stream); DebugSync("JPEG pixels", r.stream); }
+    CheckLaunches(any_vardct_ ? "JPEG pixels" : "Modular sub-streams / frame tail");
+  } else {
+    const bool stop = any_vardct_ && cfg.debug_stop_after;      // (testing: the planes as they stand behind an earlier stage)
+    if (any_vardct_) {
+      if (cfg.debug_stop_after != 1 && any_full_vardct_) LaunchFilters(dframes_, n, max_w_, max_h_, fplan_, cfg, r.stream);
+      DebugSync("filters", r.stream);
+    }
+    RecordMark(r, kMarkFiltersEnd);
+    if (!any_vardct_ && any_modchan_) EnqueueModularTail(r.stream);
+    if (!stop && any_full_vardct_) LaunchOutput(dframes_, n, max_w_, max_h_, fplan_, cfg, r.stream);
+    if (!stop && any_scaled_) LaunchLfOutput(dframes_, n, max_bw_, max_bh_, r.stream);   // 1:8 frames: the LF image through the colour transform and the write stage
+    if (!stop && any_complex_) EnqueuePostOps(r.stream);
+    if (!stop) EnqueueResizes(r.stream);
+    if (any_vardct_) { FailJpegScaledOutputs(r.stream); DebugSync("output / frame tail", r.stream); }
+    CheckLaunches(any_vardct_ ? "filters / output / frame tail" : "Modular sub-streams / frame tail");
+  }
+  RecordMark(r, kMarkOutputEnd);
+  if (r.timed && r.plan.split) timed_rest_cursor_++;
+}
+
+// (tracing) when the marks (decode_parts.h Mark, in that order) of the timed decode recorded last were reached, in ms after `ref_event`; -1 = not recorded
+void Batch::DebugTimeline(void* ref_event, float out[kNumMarks]) {
+  for (int i = 0; i < kNumMarks; i++) out[i] = -1;
   if (timed_events_.empty()) return;
   auto& evs = timed_events_.back();
-  for (int i = 0; i < 9 && i < (int)evs.size(); i++) {
+  for (int i = 0; i < kNumMarks && i < (int)evs.size(); i++) {
     if (!evs[(size_t)i]) continue;
     if (hipEventSynchronize((hipEvent_t)evs[(size_t)i]) != hipSuccess) { (void)hipGetLastError(); continue; }
     float ms = 0;
@@ -2914,14 +2374,20 @@ void Batch::DebugTimeline(void* ref_event, float out[9]) {
 StageTimes Batch::CollectTimes(int* runs) {
   StageTimes t;
   *runs = (int)timed_events_.size();
+  // a stage lasts from the end mark of the stage before it — or, where a split decode recorded one, from its own start mark — to its end mark
+  const struct { float* ms; Mark from, own_start, to; } stages[6] = {
+      {&t.lf_ms, kMarkLfStart, kNumMarks, kMarkLfEnd},         {&t.lfpost_ms, kMarkLfEnd, kNumMarks, kMarkLfPostEnd},         {&t.hf_ms, kMarkLfPostEnd, kMarkHfStart, kMarkHfEnd},
+      {&t.idct_ms, kMarkHfEnd, kMarkIdctStart, kMarkIdctEnd}, {&t.filter_ms, kMarkIdctEnd, kNumMarks, kMarkFiltersEnd}, {&t.out_ms, kMarkFiltersEnd, kNumMarks, kMarkOutputEnd}};
   for (auto& evs : timed_events_) {
     bool complete = true;
-    for (size_t i = 0; i < 7; i++) if (!evs[i]) complete = false;
+    for (int m = kMarkLfStart; m <= kMarkOutputEnd; m++) if (!evs[(size_t)m]) complete = false;
     if (!complete) { for (auto e : evs) if (e) (void)hipEventDestroy((hipEvent_t)e); (*runs)--; continue; }
-    HIP_CHECK(hipEventSynchronize((hipEvent_t)evs[6]));
-    float* dst[6] = {&t.lf_ms, &t.lfpost_ms, &t.hf_ms, &t.idct_ms, &t.filter_ms, &t.out_ms};
-    for (int i = 0; i < 6; i++) { float ms = 0; void* st = (i == 2 && evs[7]) ? evs[7] : (i == 3 && evs[8]) ? evs[8] : evs[i]; HIP_CHECK(hipEventElapsedTime(&ms, (hipEvent_t)st, (hipEvent_t)evs[i + 1])); *dst[i] += ms; }
-    float tot = 0; HIP_CHECK(hipEventElapsedTime(&tot, (hipEvent_t)evs[0], (hipEvent_t)evs[6])); t.total_ms += tot;
+    HIP_CHECK(hipEventSynchronize((hipEvent_t)evs[kMarkOutputEnd]));
+    for (auto& st : stages) {
+      void* from = st.own_start != kNumMarks && evs[st.own_start] ? evs[st.own_start] : evs[st.from];
+      float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, (hipEvent_t)from, (hipEvent_t)evs[st.to])); *st.ms += ms;
+    }
+    float tot = 0; HIP_CHECK(hipEventElapsedTime(&tot, (hipEvent_t)evs[kMarkLfStart], (hipEvent_t)evs[kMarkOutputEnd])); t.total_ms += tot;
     for (auto e : evs) if (e) (void)hipEventDestroy((hipEvent_t)e);
   }
   timed_events_.clear();
@@ -3067,8 +2533,8 @@ vec<uint8_t> Batch::ReconstructJpeg(int i, void* stream_v) {
     }
   }
   // entropy decode only: LF stage (LF coefficients = JPEG DC, block metadata) and HF stage (AC coefficients)
-  RunPart(stream_v, 1, false);
-  RunPart(stream_v, 3, false);
+  RunPart(stream_v, kPartFront, false);
+  RunPart(stream_v, kPartHf, false);
   const size_t ncomp = jd.components.size();
   // component planes: the frame's (padded) block grid shifted by the channel's subsampling; sampling factors for the SOF marker from
   // the frame header (libjxl dec_frame.cc: h_samp_factor = 1 << (max shift - shift), JPEG components Y, Cb, Cr = channels 1, 0, 2)
@@ -3559,8 +3025,8 @@ void Batch::ReconstructJpegs(void* stream_v) {
   PlanJpegWrite();
   EnqueueJpegPlan(stream_v, /*fail_refused=*/false);
   // ---- one entropy decode of the batch (LF stage: JPEG DC, block metadata; HF stage: AC), coefficients into JPEG layout
-  RunPart(stream_v, 1, false);
-  RunPart(stream_v, 3, false);
+  RunPart(stream_v, kPartFront, false);
+  RunPart(stream_v, kPartHf, false);
   EnqueueJpegGather(stream_v);
   EnqueueJpegSizes(stream_v);
   vec<uint32_t> status;
@@ -3735,7 +3201,7 @@ size_t Batch::PlanJpegPixels() {
   group_runs(0, plain, 0);
   group_runs(plain, general, 1);
   group_runs(general, table.size(), kJpegGroupDc);
-  // the groups of the frames that take this decode's HF stage (RunPart 12), and how many of them it decodes
+  // the groups of the frames that take this decode's HF stage (RunPart kPartJpegHf), and how many of them it decodes
   hf_by_region_ = jpeg_region;      // (StageBytes: the plan of a libjpeg-exact decode — a pipeline asks for the bytes of the job it has prepared, before any stage runs)
   hf_groups_total_ = hf_groups_decoded_ = 0;
   for (size_t u = 0; u < images_.size(); u++) {
@@ -3816,11 +3282,11 @@ void Batch::DecodeJpegPixels(void* stream_v) {
   if (!PlanJpegPixels()) return;
   EnqueueJpegPixelTable(stream_v, /*fail_refused=*/false);
   // ---- one entropy decode of the batch (LF stage: JPEG DC, block metadata; HF stage: AC)
-  RunPart(stream_v, 1, false);
-  RunPart(stream_v, 12, false);
+  RunPart(stream_v, kPartFront, false);
+  RunPart(stream_v, kPartJpegHf, false);
   // ---- the pixel half: one launch per kernel and group of the table, then the resizes of resized outputs over the f32 pictures the write stage left
-  RunPart(stream_v, 9, false);
-  RunPart(stream_v, 10, false);
+  RunPart(stream_v, kPartJpegIdct, false);
+  RunPart(stream_v, kPartJpegPixels, false);
   vec<uint32_t> status;
   FinishStatus(stream_v, &status);          // (a frame that failed leaves the set marked dirty)
   // frames outside the table went through the HF stage too, and nobody consumed their coefficients

@@ -5,6 +5,7 @@
 #include "host_parse.h"
 #include "kernels.h"
 #include "jpeg_recon.h"
+#include "decode_parts.h"
 #include <memory>
 #include <string>
 #include <functional>
@@ -193,7 +194,7 @@ class Batch {
   //                             gets its jpeg_result now.  Returns the number of images left.
   //   EnqueueJpegPlan           uploads scan table, tables, resets and gather table on `stream`, clears the flags; fail_refused: the status words of the frames that are
   //                             NOT in the gather table are set (kErrUnsupported), so that ZeroFailedCoefKernel puts zeros back where nobody will consume coefficients
-  //   EnqueueJpegGather         behind the HF stage (RunPart 3): JpegGatherKernel, one launch per group of at most kJpegPixelGroupMax images — the last stage that touches
+  //   EnqueueJpegGather         behind the HF stage (RunPart kPartHf): JpegGatherKernel, one launch per group of at most kJpegPixelGroupMax images — the last stage that touches
   //                             the coefficient planes; with fail_refused they are clean behind it
   //   EnqueueJpegSizes          the sizes pass of the device writer.  Neither waits on the host.
   //   EnqueueJpegHeadReadback   (optional) the raw size and the flag words to pinned memory on a copy stream of the caller's, who waits for it before FinishJpegWrite
@@ -227,7 +228,7 @@ class Batch {
   bool JpegDcOnly(int i) const { return jpeg_dc_only && images_[pub_[i].first_unit]->jpeg_dc_eligible; }
   // Decoding by region (off by default; DESIGN.md §3 has the rule).  An image whose output DecodeJpegPixels writes, that is not DC-only and whose output carries a crop
   // needs only the blocks the crop covers, widened to whole MCUs plus one MCU on every side (fancy chroma upsampling reads chroma sample i +- 1, which lies in the
-  // neighbouring chroma block at every scale): with jpeg_region on, the HF stage of DecodeJpegPixels (RunPart 12) and of the pipeline jobs built from its steps decodes
+  // neighbouring chroma block at every scale): with jpeg_region on, the HF stage of DecodeJpegPixels (RunPart kPartJpegHf) and of the pipeline jobs built from its steps decodes
   // only the 256x256 groups that rectangle touches — Prepare uploads their indices per frame (FrameDev::hf_list) —, the integer IDCT walks only those groups' blocks and
   // the colour kernels write only the crop's rectangle.  The bytes delivered are those of the decode without the option.  Run, the float decode of the same prepared
   // batch, decodes every group whatever the option says.  Known from the frame header and the output alone (SetOutput); read by the next Prepare.
@@ -241,7 +242,7 @@ class Batch {
   //                             jpeg_pixel_result now.  Returns the number of images in the table.
   //   EnqueueJpegPixelTable     uploads the table into a buffer of its own on `stream`; fail_refused: the status words of the frames that are NOT in the table are set
   //                             (kErrUnsupported), so that the HF stage's ZeroFailedCoefKernel puts zeros back where nobody will consume their coefficients
-  //   RunPart(stream, 9 / 10)   the integer IDCT over the HF planes (the last stage that touches the coefficient set, which is clean behind it); colour, write and resizes
+  //   RunPart(stream, kPartJpegIdct / kPartJpegPixels)   the integer IDCT over the HF planes (the last stage that touches the coefficient set, which is clean behind it); colour, write and resizes
   //   HarvestJpegPixels         the status words (FinishStatus / HarvestStatus) -> jpeg_pixel_result of the images in the table
   size_t PlanJpegPixels();
   void EnqueueJpegPixelTable(void* stream, bool fail_refused);
@@ -260,9 +261,9 @@ class Batch {
   // Same as Run but brackets every stage with HIP events recorded on `stream` (no host sync).  CollectTimes() waits for
   // all recorded runs and returns the per-stage sums (ms) and the number of runs; used by bench.py for the roofline.
   void RunTimed(void* stream);
-  void RunPart(void* stream, int part, bool timed);   // parts: decoder.cc; 9 / 10 / 11 are the libjpeg-exact tail (after PlanJpegPixels) in the places of 7 / 8 / 6
+  void RunPart(void* stream, DecodePart part, bool timed);   // parts: decode_parts.h; the libjpeg-exact flavours come after PlanJpegPixels
   StageTimes CollectTimes(int* runs);
-  void DebugTimeline(void* ref_event, float out[9]);
+  void DebugTimeline(void* ref_event, float out[kNumMarks]);
   // ALGORITHMIC bytes per stage for one Run of the batch: 0 lf, 1 lfpost, 2 hf, 3 idct, 4 filters, 5 out
   void StageBytes(uint64_t out[6]) const;
   LaunchCfg cfg;
@@ -275,8 +276,6 @@ class Batch {
   // Planes owned by the caller (pipeline.cc): used by the next Prepare when they are large enough for the batch's layout, otherwise the batch falls back to arenas of
   // its own (big_bytes_wanted / coef_bytes_wanted say what it would have taken).  nullptr = back to own arenas.  The caller orders the decodes that share a set.
   void UseSharedPlanes(SharedPlanes* big, SharedPlanes* coef);
-  // Side streams (hipStream_t, owned by the caller, alive as long as the batch decodes) for the independent inverse-transform chains of a batch's Modular images; without them the chains run one after the other.
-  void SetTailStreams(std::function<void*(int)> provider) { tail_streams_ = std::move(provider); }
   size_t big_bytes_wanted() const { return big_size_; }
   size_t coef_bytes_wanted() const { return coeff_bytes_; }
   bool uses_shared_big() const { return big_is_ext_; }
@@ -330,7 +329,9 @@ class Batch {
     uint32_t nb_color_int = 0;
   };
   vec<ComplexBufs> cbufs_;
-  vec<std::function<void(void*)>> post_ops_;
+  vec<std::pair<const char*, std::function<void(void*)>>> post_ops_;   // the recorded ops, each beside the name of its stage (frame_tail.cc)
+  void HashPostOps(uint64_t* h) const;
+  void PostOp(const char* stage, std::function<void(void*)> op) { post_ops_.emplace_back(stage, std::move(op)); }
   // ---- LF frames: the frames that units of this batch take their LF image from are decoded by a batch of their own (each as a one-frame image that ends
   // in its XYB planes), run in front of this batch's LF post-processing; its frame tail copies the planes into the referring unit's LF planes
   struct LfTarget { float* dst[3] = {nullptr, nullptr, nullptr}; uint32_t pitch = 0, w = 0, h = 0; };
@@ -363,7 +364,16 @@ class Batch {
   uint8_t* djpeg_ = nullptr; size_t jpeg_cap_ = 0;           // ReconstructJpegs: coefficient planes in JPEG layout, scan table, per-block / per-segment arrays
   uint8_t* djpeg_out_ = nullptr; size_t jpeg_out_cap_ = 0;   // ... raw and stuffed segment bytes, segment records
   bool any_complex_ = false;
+  // the frame tail (frame_tail.cc): PlanPostOps walks the frames of every complex image through the stages below, which record the ops EnqueuePostOps replays
+  struct TailImage; struct TailUnit;
   void PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off);
+  void TailToFloat(TailImage& im, TailUnit& t); void TailPatches(TailImage& im, TailUnit& t); void TailSplines(TailImage& im, TailUnit& t); void TailUpsample(TailImage& im, TailUnit& t);
+  void TailNoise(TailUnit& t); void TailLfHandOver(TailUnit& t); void TailColour(TailImage& im, TailUnit& t); void TailOwnFrame(TailImage& im, TailUnit& t);
+  void TailBlend(TailImage& im, TailUnit& t); void TailDeliver(TailImage& im, TailUnit& t, int slot);
+  WriteArgs TailWriteArgs(const TailImage& im, const size_t p[3], uint32_t stride, const vec<size_t>& ec, uint32_t ec_stride, uint32_t w, uint32_t h);
+  void TailDeferredTf(const TailUnit& t, const char* stage, const size_t p[3], uint32_t stride, uint32_t w, uint32_t h);
+  float* BigPlane(size_t off) const { return (float*)(dbig_ + off); }                                // (read when an op runs as well as when it is planned)
+  const EcChanDev* EcTable(size_t off) const { return (const EcChanDev*)(dconst_ + off); }
   void EnqueuePostOps(void* stream);
   // resized outputs: per image one ResizeArgs (kernels.h), built by Prepare into a table of the constant arena — sorted by slot count, cut into groups of at most
   // resize_group_max entries — and launched group by group behind everything that writes pixels
@@ -393,8 +403,6 @@ class Batch {
   // runs under the next batch's latency-bound HF stage.  The next decode of this batch only waits for that event.
   uint8_t* dcoef_ = nullptr;
   void* clear_stream_ = nullptr; void* clear_event_ = nullptr; void* idct_event_ = nullptr;
-  vec<void*> mod_join_events_; void* mod_fork_event_ = nullptr;   // fork / join of the Modular tail's side streams (EnqueueModularTail): one inverse-transform chain per image
-  std::function<void*(int)> tail_streams_;                        // k -> the owner's k-th side stream for those chains (nullptr: no more)
   bool clear_pending_ = false, coef_dirty_ = true;
   Batch* coef_owner_ = nullptr;
   size_t coef_clean_extent_ = 0;   // bytes of this object's own coefficient planes known to be zero after a completed decode
@@ -443,8 +451,14 @@ class Batch {
   struct VarDctAlpha { bool has = false; size_t off = 0; float factor = 1.0f; };
   vec<VarDctAlpha> vardct_alpha_;
   bool any_modchan_ = false;      // some frame carries Modular channels (Modular frames, VarDCT frames with extra channels)
-  void EnqueueModularTail(void* stream);
-  void PlanModularUndo(int i, const std::function<size_t(size_t)>& take);
+  struct ModChan;
+  void EnqueueModularTail(void* stream); void RunModOp(int i, const ModOp& op, void* stream);
+  void PlanModularUndo(int i, const std::function<size_t(size_t)>& take); void PlanModularOutput(int i, const vec<ModChan>& list);
+  // ---- RunPart: one function per stage of the part (decode_parts.h), over what the call shares
+  struct PartRun { void* stream; PartPlan plan; bool timed; vec<void*>* marks; };
+  void RecordMark(const PartRun& r, Mark m);
+  void StageLf(const PartRun& r); void StageLfPost(const PartRun& r); void StageHf(const PartRun& r); void StageIdct(const PartRun& r); void StagePixels(const PartRun& r);
+  void EnqueueFlagReadback(void* stream); void WaitForIdctFlags(const PartRun& r);
   vec<vec<void*>> timed_events_;
   size_t timed_rest_cursor_ = 0;       // timed decodes run in parts (RunPart): which entry of timed_events_ the next "rest" part records into; CollectTimes starts it over
 };

@@ -887,7 +887,7 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
 }
 
 // ---- batch extension ---------------------------------------------------------------------------------------------------
-struct JxlHipBatchStruct { Batch* b; bool keep_orientation = false; bool allow_partial = false; };
+struct JxlHipBatchStruct { Batch* b; bool keep_orientation = false; bool allow_partial = false; int only_frame = -1; bool all_frames = false; };
 
 JxlHipBatch* JxlHipBatchCreate(int device) {
   try {
@@ -956,6 +956,7 @@ static bool BatchSpec(const JxlHipBatch* h, int i, const JxlPixelFormat* format,
   if (!FormatToSpec(format, o) || !ApplyLayout(layout, o, who) || !(resampled ? ApplyResample(resample, o, who) : ApplyResize(resize, o, who))) return false;
   if (!h || i < 0 || (size_t)i >= h->b->size()) { SetLastError(std::string(who) + ": no such image"); return false; }
   o->keep_orientation = h->keep_orientation;
+  o->only_frame = h->only_frame;
   o->downscale = (uint32_t)downscale;
   return true;
 }
@@ -970,7 +971,11 @@ static JxlDecoderStatus BatchSetOutput(JxlHipBatch* h, int i, const JxlPixelForm
   OutputSpec o;
   if (!BatchSpec(h, i, format, downscale, layout, resize, resample, resampled, &o, who)) return JXL_DEC_ERROR;
   o.device_ptr = device_buffer;
-  try { h->b->SetOutput(i, o); return JXL_DEC_SUCCESS; } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }   // ("unsupported: downscaled decode of ...", a plane_stride that does not fit, a crop that leaves the picture)
+  try {
+    if (h->all_frames) { vec<int> frames; for (int f = 0; f < h->b->num_units_of(i); f++) frames.push_back(f); h->b->SetOutputAllFrames(i, o, frames); }
+    else h->b->SetOutput(i, o);
+    return JXL_DEC_SUCCESS;
+  } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }   // ("unsupported: downscaled decode of ...", a plane_stride that does not fit, a crop that leaves the picture)
 }
 JxlDecoderStatus JxlHipBatchOutBufferSize(const JxlHipBatch* h, int i, const JxlPixelFormat* format, size_t* size) { return BatchOutBufferSize(h, i, format, 1, nullptr, nullptr, size, "JxlHipBatchOutBufferSize"); }
 JxlDecoderStatus JxlHipBatchSetOutput(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer) { return BatchSetOutput(h, i, format, device_buffer, 1, nullptr, nullptr, "JxlHipBatchSetOutput"); }
@@ -1052,8 +1057,8 @@ JxlDecoderStatus JxlHipBatchPrepare(JxlHipBatch* h, void* s) { BATCH_TRY(h->b->P
 JxlDecoderStatus JxlHipBatchDecode(JxlHipBatch* h, void* s) { BATCH_TRY(h->b->Run(s)) }
 JxlDecoderStatus JxlHipBatchDecodeTimed(JxlHipBatch* h, void* s) { BATCH_TRY(h->b->RunTimed(s)) }
 JxlDecoderStatus JxlHipBatchDecodePart(JxlHipBatch* h, void* s, int part, int timed) {
-  if (part < 0 || part > 8) return JXL_DEC_ERROR;
-  BATCH_TRY(h->b->RunPart(s, part, timed != 0))
+  if (part < 0 || part >= kNumPublicParts) return JXL_DEC_ERROR;
+  BATCH_TRY(h->b->RunPart(s, (DecodePart)part, timed != 0))
 }
 JxlDecoderStatus JxlHipBatchCollectTimes(JxlHipBatch* h, JxlHipStageTimes* t, int* runs) {
   BATCH_TRY({ StageTimes st = h->b->CollectTimes(runs); t->lf_ms = st.lf_ms; t->lfpost_ms = st.lfpost_ms; t->hf_ms = st.hf_ms; t->idct_ms = st.idct_ms; t->filter_ms = st.filter_ms; t->out_ms = st.out_ms; t->total_ms = st.total_ms; })
@@ -1069,6 +1074,8 @@ void JxlHipBatchSetOption(JxlHipBatch* h, const char* name, int value) {
   else if (n == "lf_wp_narrow_test") h->b->cfg.lf_wp_narrow_test = value != 0;
   else if (n == "debug_stop_after" && value >= 0 && value <= 5) h->b->cfg.debug_stop_after = value;
   else if (n == "keep_orientation") h->keep_orientation = value != 0;   // applies to outputs set afterwards
+  else if (n == "output_only_frame") h->only_frame = value;             // testing, outputs set afterwards: frame `value` as coded (OutputSpec::only_frame; -1: the image) ...
+  else if (n == "output_all_frames") h->all_frames = value != 0;        // ... or every frame's canvas from one decode (Batch::SetOutputAllFrames)
   else if (n == "allow_partial") h->allow_partial = value != 0;         // applies to images added afterwards
   else if (n == "hf_block_threads" && value >= 64 && value <= 1024 && value % 64 == 0) h->b->cfg.hf_block_threads = value;
   // (rounded down to 16 bytes: the kernels put regions of their own behind the staged tables — HfDecodeSimtKernel its lane slots — that must stay aligned)

@@ -179,7 +179,7 @@ struct LaunchCfg {
   int debug_stop_after = 0;          // testing: the tail of a decode stops after 1 = IDCT, 2 = gaborish, 3 / 4 / 5 = EPF pass 0 / 1 / 2 (stage-by-stage filters only)
   int force_unfused_filters = 0;     // testing: stage-by-stage gaborish / EPF / output kernels even for fusable frames        // testing: run the generic (non-tiled) IDCT kernel even for tile-regular frames
   int hf_block_threads = 512;        // threads per HF-decode block (streams per block = threads / lane_stride_hf)
-  int hf_by_list = 0;                // this HF launch belongs to a libjpeg-exact decode (RunPart 12): frames with FrameDev::hf_list decode the groups of that list only, packed into
+  int hf_by_list = 0;                // this HF launch belongs to a libjpeg-exact decode (Batch::RunPart kPartJpegHf): frames with FrameDev::hf_list decode the groups of that list only, packed into
                                      // the first stream slots; every other launch — Run, the float decode of the same prepared batch — decodes every group
   int lds_code_budget = 64 * 1024;   // bytes of LDS the entropy-code tables (cfg, ctx map, alias) may take per block
 };

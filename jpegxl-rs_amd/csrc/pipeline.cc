@@ -22,17 +22,6 @@ void* NewStream(int priority) {
   HIP_CHECK(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority));
   return s;
 }
-}  // namespace
-// The k-th of the pipeline's (at most four) side streams for the inverse-transform chains of a job's Modular images (Batch::EnqueueModularTail), made when first asked for:
-// pipelines that never see such jobs — the one behind the libjxl API decodes single images — keep the process's stream count where it was.
-void* Pipeline::TailStream(int k) {
-  static const int cap = getenv("JXL_HIP_MOD_TAIL_STREAMS") ? std::max(1, std::min(16, atoi(getenv("JXL_HIP_MOD_TAIL_STREAMS")))) : 4;
-  if (k < 0 || k >= cap || cap < 2) return nullptr;
-  std::lock_guard<std::mutex> lock(tail_mu_);
-  while ((int)tail_side_.size() <= k) tail_side_.push_back(NewStream(0));
-  return tail_side_[(size_t)k];
-}
-namespace {
 void* NewEvent(bool timing = false) {
   hipEvent_t e = nullptr;
   HIP_CHECK(hipEventCreateWithFlags(&e, timing ? hipEventDefault : hipEventDisableTiming));
@@ -78,7 +67,6 @@ Pipeline::Pipeline(int device, const PipelineOptions& opt) : device_(device), op
   for (int b = 0; b < nbuf_; b++) {
     std::unique_ptr<Slot> s(new Slot());
     s->batch.reset(new Batch(device_));
-    s->batch->SetTailStreams([this](int k) -> void* { return TailStream(k); });
     s->lf_done = NewEvent(); s->front_done = NewEvent(); s->hf_done = NewEvent(); s->idct_done = NewEvent(); s->rest_done = NewEvent();
     slots_.push_back(std::move(s));
   }
@@ -118,7 +106,6 @@ Pipeline::~Pipeline() {
   if (clock_event_) (void)hipEventDestroy((hipEvent_t)clock_event_);
   for (void* s : lf_side_) (void)hipStreamDestroy((hipStream_t)s);
   for (void* s : hf_side_) (void)hipStreamDestroy((hipStream_t)s);
-  for (void* s : tail_side_) { (void)hipStreamSynchronize((hipStream_t)s); (void)hipStreamDestroy((hipStream_t)s); }
   (void)hipStreamDestroy((hipStream_t)main_);
   for (void* s : d2h_) (void)hipStreamDestroy((hipStream_t)s);
 }
@@ -402,12 +389,12 @@ void Pipeline::PrepareJob(Job* j, int worker) {
       if (chained) StreamWait(side, slots_[(size_t)(j->wide_after % nbuf_)]->lf_done);
     }
     const bool timed = opt_.timed != 0 && !files;   // (a reconstruction job has no pixel stages to bracket: its parts are not timed)
-    bt.RunPart(side, 5, timed);           // LF decode + varblock placement: all the HF stage waits for
+    bt.RunPart(side, kPartLf, timed);           // LF decode + varblock placement: all the HF stage waits for
     Record(s.lf_done, side);
     if (j->wide_chain) { { std::lock_guard<std::mutex> lock(mu_); wide_enqueued_ = std::max(wide_enqueued_, j->ticket); } cv_.notify_all(); }
     // LF post-processing: needed by the float IDCT and the filters only — the libjpeg-exact tail and the reconstruction's gather read lfq, the coefficient planes, block info and offsets, the
     // chroma-from-luma maps: nothing LfDequantKernel, LfSmoothKernel, LlfSigmaKernel or LlfKernel write (lf, lf_tmp, llf, inv_sigma)
-    bt.RunPart(side, j->kind != kPlain ? 11 : 6, timed);
+    bt.RunPart(side, PartOf(kStageLfPost, j->kind != kPlain), timed);
     Record(s.front_done, side);
   } catch (const std::exception& e) {
     j->job_error = e.what();
@@ -432,7 +419,7 @@ void Pipeline::IssueHf(Job* j) {
     // the coefficient set's previous user has consumed (and zeroed) it: its tail was issued before this call (tails go out in order, HF stages at most hf_streams ahead)
     if (j->ticket >= ncoef_) StreamWait(hs, slots_[(size_t)((j->ticket - ncoef_) % nbuf_)]->idct_done);
     // (a libjpeg-exact job: part 12, the HF stage that honours the group lists of images decoded by region)
-    s.batch->RunPart(hs, j->kind == kJpegPixels ? 12 : 3, opt_.timed != 0 && j->kind != kJpegFiles);
+    s.batch->RunPart(hs, PartOf(kStageHf, j->kind == kJpegPixels), opt_.timed != 0 && j->kind != kJpegFiles);
     Record(s.hf_done, hs);
   } catch (const std::exception& e) { j->job_error = e.what(); }
 }
@@ -446,11 +433,11 @@ void Pipeline::IssueTail(Job* j) {
       StreamWait(main_, s.front_done);
       // IDCT (float, or the integer one over the HF planes; a reconstruction job: the gather into the JPEG writer's arena): the last stage that touches the coefficient
       // set, which is clean behind it
-      if (j->kind == kJpegFiles) bt.EnqueueJpegGather(main_); else bt.RunPart(main_, j->kind == kJpegPixels ? 9 : 7, opt_.timed != 0);
+      if (j->kind == kJpegFiles) bt.EnqueueJpegGather(main_); else bt.RunPart(main_, PartOf(kStageIdct, j->kind == kJpegPixels), opt_.timed != 0);
       Record(s.idct_done, main_);
       // restoration filters, colour, write (libjpeg-exact jobs: chroma upsampling, colour, write); resizes.  A reconstruction job: the sizes pass of the writer — its
       // pack pass, sized on the host from what that pass found, and the splice belong to the harvest
-      if (j->kind == kJpegFiles) bt.EnqueueJpegSizes(main_); else bt.RunPart(main_, j->kind == kJpegPixels ? 10 : 8, opt_.timed != 0);
+      if (j->kind == kJpegFiles) bt.EnqueueJpegSizes(main_); else bt.RunPart(main_, PartOf(kStagePixels, j->kind == kJpegPixels), opt_.timed != 0);
       Record(s.rest_done, main_);
       void* d2h = d2h_[0];
       StreamWait(d2h, s.rest_done);
@@ -584,10 +571,10 @@ void Pipeline::Harvest(Job* j) {
     fprintf(stderr, "[pipe %.1f] job %lld (reconstruction, %zu images): status words in hand, then pack pass + copies + splice %.1f ms on the collecting thread; done at %.1f ms\n",
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(), (long long)j->ticket, n, finish_ms, j->result.end_ms);
   if (trace && opt_.timed && readback_ok && j->kind != kJpegFiles) {
-    float tl[9];
+    float tl[kNumMarks];
     bt.DebugTimeline(clock_event_, tl);
-    fprintf(stderr, "[pipe] job %lld timeline (ms): LF %.1f .. %.1f, LF post end %.1f, HF %.1f .. %.1f, IDCT %.1f .. %.1f, filters end %.1f, out end %.1f\n", (long long)j->ticket, tl[0], tl[1], tl[2], tl[7], tl[3],
-            tl[8], tl[4], tl[5], tl[6]);
+    fprintf(stderr, "[pipe] job %lld timeline (ms): LF %.1f .. %.1f, LF post end %.1f, HF %.1f .. %.1f, IDCT %.1f .. %.1f, filters end %.1f, out end %.1f\n", (long long)j->ticket, tl[kMarkLfStart], tl[kMarkLfEnd], tl[kMarkLfPostEnd], tl[kMarkHfStart], tl[kMarkHfEnd],
+            tl[kMarkIdctStart], tl[kMarkIdctEnd], tl[kMarkFiltersEnd], tl[kMarkOutputEnd]);
     int runs = 0;
     const StageTimes t = bt.CollectTimes(&runs);
     fprintf(stderr, "[pipe] job %lld (%zu images) on the GPU: lf %.1f lfpost %.1f hf %.1f idct %.1f filters %.1f out %.1f, first kernel to last %.1f ms; done at %.1f ms\n", (long long)j->ticket, n, t.lf_ms, t.lfpost_ms,

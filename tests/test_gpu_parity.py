@@ -1295,6 +1295,44 @@ def test_mixed_batch_in_two_halves_on_two_streams(jx):
             assert np.array_equal(b.output(i), want[i]), i
 
 
+PART_SEQUENCES = ([0], [1, 2], [1, 3, 4], [5, 6, 3, 7, 8])
+
+
+def split_batches():
+    """the batches of the split test: VarDCT frames; one Modular frame alone (no VarDCT frame in the batch: its sub-streams and tail run in the pixel stage, not
+    in the HF stage); a complex image (two frames, extra channels: the frame tail)"""
+    from test_prepare_fingerprint import stream
+    return {"vardct": [stream("vardct_300x200_mix2_epf2.jxl"), stream("vardct_64x64_dct8.jxl")],
+            "modular": [S.encode_modular(_smooth_image(9, 120, 150, 3, 8), 8, True, 1)],
+            "complex": [stream("layered_vardct_n2")]}
+
+
+@pytest.mark.parametrize("name", ["vardct", "modular", "complex"])
+def test_every_split_of_a_decode_equals_the_whole(jx, name):
+    """A decode enqueued in parts (JxlHipBatchDecodePart) on one stream writes the bytes of the whole decode (part 0), whichever way it is cut: front / rest, front /
+    HF / everything after it, or stage by stage.  Timed, every cut records one complete run whose stage times are not negative."""
+    b = jx.BatchDecoder(0)
+    for d in split_batches()[name]:
+        b.add(d, "uint8", 3)
+    b.prepare()
+    whole = None
+    for seq in PART_SEQUENCES:
+        for timed in (False, True):
+            for part in seq:
+                b.decode_part(part, None, timed)
+            b.finish()
+            out = [b.output(i).tobytes() for i in range(len(split_batches()[name]))]
+            if whole is None:
+                whole = out
+                assert all(any(o) for o in out)
+            assert out == whole, (seq, timed)
+            if timed:
+                times, runs = b.collect_times()
+                print(name, seq, runs, times)
+                assert runs == 1, (seq, runs)
+                assert all(v >= 0 for v in times.values()), (seq, times)
+
+
 def test_corrupted_streams_fail_cleanly_or_decode(jx):
     """Robustness: random byte corruption in the section payloads (VarDCT and Modular streams) must end in a DecodeError or
     a decode of the right size — never a crash or a hang (the kernels bound every loop by the frame geometry and read

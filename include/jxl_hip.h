@@ -313,6 +313,39 @@ JxlDecoderStatus JxlHipBatchOutBufferSizeResampled(const JxlHipBatch* batch, int
                                                    const JxlHipOutputResample* resample, size_t* size);
 JxlDecoderStatus JxlHipBatchSetOutputResampled(JxlHipBatch* batch, int index, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout,
                                                const JxlHipOutputResample* resample);
+/* ---- extra-channel planes beside the colour output, all from one decode ---------------------------------------------------------------------------------
+ * JxlHipOutputPlanes asks for extra channels of the image — depth, masks, spectral bands, any channel by its index, indices may repeat — as planes of one sample per
+ * pixel behind the colour output of the same destination.  Plane k holds channel extra_index[k] "as it is": of the coalesced canvas (or of the frame's own planes for a
+ * non-coalesced output), converted by the channel's own bit depth (float channels through their bit pattern), never un-premultiplied, untouched by spot-colour
+ * rendering and by the output bit depth.  Its sample type, byte order and row alignment are those of the colour output's JxlPixelFormat; its geometry follows the
+ * colour output: orientation (or keep_orientation) and, with a resized output, the same crop, target size, filter and mirror, each plane resampled on its own.
+ *   offset        where plane 0 starts in the destination.  0 = num_channels x plane_stride behind a planar colour output, so that colour and extras form one
+ *                 [C + m, H, W] block; behind an interleaved one the colour size rounded up to 16 bytes.
+ *   plane_stride  bytes from plane k to plane k + 1.  0 = the layout's plane_stride when the colour is planar, else tight (rows x aligned row pitch).
+ *                 Either may be given: at least its default and a multiple of the sample size, or the call fails with a message.
+ *   scale, bias   NULL, or num_planes values: float16 / float32 plane k is stored as fmaf(v, scale[k], bias[k]) (a NULL one of the two: 1 / 0).
+ * The destination is offset + num_planes x plane_stride bytes: JxlHipBatchOutputPlanesLayout (host only) and JxlHipImageOutSizePlanes say so; the capacity checks of a
+ * pipeline job include the planes.  JxlHipBatchSetOutputPlanes is called after the JxlHipBatchSetOutput... call of that image, whose device buffer then takes both; a
+ * later JxlHipBatchSetOutput... call clears the planes, as do a NULL `planes` or num_planes = 0.  At most 4096 planes.
+ * An image with requested planes takes the frame tail (the path of layered, patched and animated images): EcPlanesOutKernel writes every plane of it in one launch
+ * behind the colour write, whatever their number — no decode per plane.  JxlHipBatchGetInfo(batch, "plane_outputs"): planes the last decode wrote.
+ * Refused, "unsupported: extra planes ..." in JxlHipLastError() (an image of a pipeline job fails alone): an index at or beyond the image's number of extra channels;
+ * scale / bias with an integer sample type; downscale 8; libjpeg-exact outputs (jpeg_scale, the integer resample); kept animation canvases ("output_all_frames").
+ * Jobs of libjpeg-exact pixels (JxlHipPipelineSubmitJpegPixels...) and previews (JxlDecoderSetPreviewOutBuffer) have no argument that carries planes.
+ * Host destinations (host_out of a pipeline job, JxlHipBatchCopyOutput) receive the destination as one run of `total` bytes: the bytes between the colour output and
+ * plane 0 — up to 15 behind an interleaved colour output, more under an explicit offset — and behind each plane's rows under an explicit plane_stride are overwritten
+ * with unspecified values, as the gaps of a padded planar layout are.  A device destination is written at the samples alone. */
+typedef struct { uint32_t num_planes; const uint32_t* extra_index; size_t offset; size_t plane_stride; const float* scale; const float* bias; } JxlHipOutputPlanes;
+/* The libjxl API: the buffers of JxlDecoderSetExtraChannelBuffer are served by the frame's main decode, each in its own JxlPixelFormat, when the image takes the frame
+ * tail under its colour output anyway (several frames, patches, splines, noise, rendered spot colours, non-coalesced output, un-premultiplied alpha) and its canvases
+ * are not kept from one decode of an animation; every other image still takes one more decode per buffer.  JxlHipDecoderInfo(decoder, "frame_decodes"): the decodes
+ * the last delivered frame took (1 + the buffers served by a decode of their own; 0: the frame came from kept canvases); -1 for an unknown name. */
+int64_t JxlHipDecoderInfo(const JxlDecoder* decoder, const char* name);
+JxlDecoderStatus JxlHipBatchSetOutputPlanes(JxlHipBatch* batch, int index, const JxlHipOutputPlanes* planes);
+JxlDecoderStatus JxlHipBatchOutputPlanesLayout(const JxlHipBatch* batch, int index, size_t* offset, size_t* plane_stride, size_t* total);
+/* JxlHipImageOutSizeResized with a filter-and-mirror resample (NULL: the image's own size) and the planes: *out_size is the whole destination */
+JxlDecoderStatus JxlHipImageOutSizePlanes(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout,
+                                          const JxlHipOutputResample* resample, const JxlHipOutputPlanes* planes, JxlBasicInfo* info, size_t* out_size);
 /* JPEG bit-stream reconstruction of a whole batch (jpegxl-rs decode.rs:493 `reconstruct`, for many files at once).  JxlHipBatchCanReconstructJpeg: 1 if image
  * `index` is a lossless JPEG transcode with usable reconstruction data (a `jbrd` box whose markers find their ICC / Exif / XMP payloads, a Huffman-coded source),
  * else 0 with the reason in JxlHipLastError().  JxlHipBatchReconstructJpegs runs the LF and HF entropy stages once for all images of the batch (it prepares the batch
@@ -534,6 +567,12 @@ int64_t JxlHipPipelineSubmitResized(JxlHipPipeline* pipeline, const uint8_t* con
 /* The same with a resample per image (JxlHipOutputResample above, n entries; every entry the same xsize x ysize). */
 int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
                                       void* const* host_out, const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each);
+/* The same with extra-channel planes behind every image's colour output (JxlHipOutputPlanes above: one request list for the job).  `each` may be NULL: every image at
+ * its own size.  A destination holds the colour output and the planes (JxlHipImageOutSizePlanes bytes; out_capacity is checked against that); an image the planes are
+ * refused for — a channel it does not have — fails alone with the reason. */
+int64_t JxlHipPipelineSubmitPlanes(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
+                                   void* const* host_out, const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each,
+                                   const JxlHipOutputPlanes* planes);
 /* A job of libjpeg-exact pixels: every image is decoded to the samples libjpeg gives for the JPEG file it was transcoded from (JxlHipBatchDecodeJpegPixels above, as
  * stages of the pipeline: the job shares coefficient sets and pixel planes with plain jobs, which may be mixed with it freely).  Eligible is what
  * JxlHipBatchCanDecodeJpegPixels takes; an image that is not eligible fails alone with that call's reason ("unsupported: libjpeg-exact decode of ..."), and so does an

@@ -110,6 +110,12 @@ class JxlHipOutputResample(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("xsize", "ysize", "crop_x0", "crop_y0", "crop_xsize", "crop_ysize", "filter")] + [("mirror", C.c_int)]
 
 
+class JxlHipOutputPlanes(C.Structure):
+    """include/jxl_hip.h JxlHipOutputPlanes: extra channels as planes behind the colour output (indices, where the first plane starts, the pitch, per-plane scale / bias)"""
+    _fields_ = [("num_planes", C.c_uint32), ("extra_index", C.POINTER(C.c_uint32)), ("offset", C.c_size_t), ("plane_stride", C.c_size_t),
+                ("scale", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float))]
+
+
 assert C.sizeof(JxlBasicInfo) == 204 and C.sizeof(JxlPixelFormat) == 24 and C.sizeof(JxlMemoryManager) == 24
 
 _lib = None
@@ -188,6 +194,13 @@ def libjxl():
             "JxlHipBatchSetOutputResampled": (C.c_int, [vp, C.c_int, C.POINTER(JxlPixelFormat), vp, C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample)]),
             "JxlHipPipelineSubmitResampled": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.c_int,
                                                           C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample)]),
+            "JxlHipBatchSetOutputPlanes": (C.c_int, [vp, C.c_int, C.POINTER(JxlHipOutputPlanes)]),
+            "JxlHipBatchOutputPlanesLayout": (C.c_int, [vp, C.c_int, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+            "JxlHipPipelineSubmitPlanes": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.c_int,
+                                                       C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(JxlHipOutputPlanes)]),
+            "JxlHipImageOutSizePlanes": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(JxlHipOutputPlanes),
+                                                   C.POINTER(JxlBasicInfo), C.POINTER(sz)]),
+            "JxlHipDecoderInfo": (C.c_int64, [vp, C.c_char_p]),
             "JxlHipBatchCanReconstructJpeg": (C.c_int, [vp, C.c_int]), "JxlHipBatchReconstructJpegs": (C.c_int, [vp, vp]),
             "JxlHipBatchJpegStatus": (C.c_int, [vp, C.c_int]), "JxlHipBatchJpegSize": (sz, [vp, C.c_int]), "JxlHipBatchCopyJpeg": (C.c_int, [vp, C.c_int, vp, sz]),
             "JxlHipPipelineSubmitJpegPixels": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz),
@@ -714,6 +727,35 @@ def _resize_u8(downscale, rs):
         raise GenericError("unsupported: integer resample without a target size (resize_u8 needs resize=(width, height))")
 
 
+def _planes(extra_planes, plane_scale, plane_bias, planes_offset, planes_stride=0):
+    """-> JxlHipOutputPlanes (which keeps its arrays referenced), or None without extra_planes.  extra_planes: extra-channel indices, one plane each (they may repeat);
+    plane_scale / plane_bias: one value per plane (float16 / float32 output); planes_offset / planes_stride: where the first plane starts in the destination and the
+    bytes from one plane to the next, 0 = the defaults (include/jxl_hip.h JxlHipOutputPlanes)."""
+    if extra_planes is None:
+        if plane_scale is not None or plane_bias is not None or planes_offset or planes_stride:
+            raise ValueError("plane_scale, plane_bias, planes_offset and planes_stride need extra_planes=[...]")
+        return None
+    idx = [int(k) for k in extra_planes]
+    if any(k < 0 or k >= 1 << 32 for k in idx):
+        raise ValueError("extra_planes holds extra-channel indices (unsigned 32-bit)")
+    m = len(idx)
+    p = JxlHipOutputPlanes()
+    p.num_planes = m
+    p._idx = (C.c_uint32 * max(1, m))(*idx)
+    p.extra_index = C.cast(p._idx, C.POINTER(C.c_uint32))
+    p.offset, p.plane_stride = int(planes_offset), int(planes_stride)
+    for name, src in (("scale", plane_scale), ("bias", plane_bias)):
+        if src is None:
+            continue
+        vals = [float(v) for v in np.atleast_1d(src)]
+        if len(vals) != m:
+            raise ValueError(f"plane_{name} needs one value per requested plane ({m}), not {len(vals)}")
+        arr = (C.c_float * max(1, m))(*vals)
+        setattr(p, "_" + name, arr)
+        setattr(p, name, C.cast(arr, C.POINTER(C.c_float)))
+    return p
+
+
 def _per_image(value, n, is_one):
     """one value for the job, or a sequence of n per-image values -> (list of n, whether it was a sequence)"""
     if value is None or isinstance(value, (str, bytes)) or not hasattr(value, "__iter__"):
@@ -745,6 +787,7 @@ class BatchDecoder:
         self._jpeg_scale = []
         self._layouts = []
         self._resizes = []
+        self._planes = []
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -755,7 +798,7 @@ class BatchDecoder:
         if status != JXL_DEC_SUCCESS:
             raise GenericError(last_error())
 
-    def _set_output(self, i, fmt, device_ptr, downscale, layout=None, resize=None, jpeg_scale=1, resize_u8=False):
+    def _set_output(self, i, fmt, device_ptr, downscale, layout=None, resize=None, jpeg_scale=1, resize_u8=False, planes=None):
         L = libjxl()
         if resize_u8:
             _resize_u8(downscale, resize)
@@ -774,6 +817,9 @@ class BatchDecoder:
             self._chk(L.JxlHipBatchSetOutput(self._h, i, C.byref(fmt), device_ptr))
         else:
             self._chk(L.JxlHipBatchSetOutputScaled(self._h, i, C.byref(fmt), device_ptr, int(downscale)))
+        if planes is not None:
+            self._chk(L.JxlHipBatchSetOutputPlanes(self._h, i, C.byref(planes)))
+        self._planes.append(planes)
         self._fmt.append(fmt)
         self._scale.append(int(downscale))
         self._jpeg_scale.append(int(jpeg_scale))
@@ -781,7 +827,8 @@ class BatchDecoder:
         self._resizes.append(resize)
 
     def add(self, data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, device_ptr=None, downscale=1,
-            planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_scale=1, resize_u8=False) -> int:
+            planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_scale=1, resize_u8=False,
+            extra_planes=None, plane_scale=None, plane_bias=None, planes_offset=0, planes_stride=0) -> int:
         """downscale=8: the 1:8 decode (include/jxl_hip.h JxlHipBatchSetOutputScaled) — output(i) is the ceil(w / 8) x ceil(h / 8) picture; `data` may end behind
         the LF part of its frame.
         planar=True: one plane per channel, [C, H, W] with rows `align`ed and planes plane_stride bytes apart (0 = tight); scale / bias (up to four values, one per
@@ -797,7 +844,13 @@ class BatchDecoder:
         fails the next prepare() with "truncated".
         resize_u8=True (needs resize, and an image decode_jpeg_pixels() takes): the resample runs in Pillow's 8-bit arithmetic over the u8 picture libjpeg gives
         (include/jxl_hip.h JxlHipBatchSetOutputJpegResampled) — the u8 output is np.asarray(Image.open(file).crop(box).resize(size, BILINEAR | BICUBIC)) byte for
-        byte, every other type and layout follows from it, and the intermediates are u8.  Only decode_jpeg_pixels() writes such an output; not together with downscale."""
+        byte, every other type and layout follows from it, and the intermediates are u8.  Only decode_jpeg_pixels() writes such an output; not together with downscale.
+        extra_planes=[k, ...]: extra channel k of the image — as it is: depth, masks, spectral bands — as a plane of one sample per pixel behind the colour output of the
+        same destination, all planes from the one decode (include/jxl_hip.h JxlHipOutputPlanes).  The planes take dtype, endianness and align of the colour output and
+        follow its geometry (orientation, resize, crop, filter, mirror); with planar=True colour and planes form one [C + m, H, W] block.  plane_scale / plane_bias: one
+        value per plane (float output); planes_offset / planes_stride: where the first plane starts and the bytes from plane to plane, 0 = the defaults —
+        planes_layout(i) tells, and out_size(i) / output(i) cover the whole destination.  An index the image does not have, downscale=8 and libjpeg-exact outputs
+        are refused: "unsupported: extra planes ..."."""
         layout = _layout(planar, plane_stride, scale, bias)
         rs = _resize(resize, crop) if filter is None and not mirror else _resample(resize, crop, filter, mirror)
         L = libjxl()
@@ -813,17 +866,20 @@ class BatchDecoder:
         if i < 0:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
-        self._set_output(i, fmt, device_ptr, downscale, layout, rs, jpeg_scale, resize_u8)
+        self._set_output(i, fmt, device_ptr, downscale, layout, rs, jpeg_scale, resize_u8, _planes(extra_planes, plane_scale, plane_bias, planes_offset, planes_stride))
         self._n += 1
         return i
 
     def add_many(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, threads=4, endianness=Endianness.Native, align=0, downscale=1,
-                 planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_scale=1, resize_u8=False) -> int:
+                 planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_scale=1, resize_u8=False,
+                 extra_planes=None, plane_scale=None, plane_bias=None, planes_offset=0, planes_stride=0) -> int:
         """Parses the images of `datas` (bytes objects) on `threads` host threads and appends them in order (JxlHipBatchAddImages);
-        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale, planar, plane_stride, scale, bias, resize, crop, filter, mirror, jpeg_scale, resize_u8: as for add()."""
+        device_ptrs: optional caller-owned device destination per image.  Returns the index of the first one.  downscale, planar, plane_stride, scale, bias, resize, crop, filter, mirror, jpeg_scale, resize_u8,
+        extra_planes, plane_scale, plane_bias, planes_offset, planes_stride: as for add()."""
         L = libjxl()
         layout = _layout(planar, plane_stride, scale, bias)
         rs = _resize(resize, crop) if filter is None and not mirror else _resample(resize, crop, filter, mirror)
+        planes = _planes(extra_planes, plane_scale, plane_bias, planes_offset, planes_stride)
         n = len(datas)
         ptrs = (C.c_char_p * n)(*datas)
         sizes = (C.c_size_t * n)(*[len(d) for d in datas])
@@ -839,7 +895,7 @@ class BatchDecoder:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
         for k in range(n):
-            self._set_output(first + k, fmt, device_ptrs[k] if device_ptrs is not None else None, downscale, layout, rs, jpeg_scale, resize_u8)
+            self._set_output(first + k, fmt, device_ptrs[k] if device_ptrs is not None else None, downscale, layout, rs, jpeg_scale, resize_u8, planes)
         self._n += n
         return first
 
@@ -852,13 +908,23 @@ class BatchDecoder:
         self._jpeg_scale = []
         self._layouts = []
         self._resizes = []
+        self._planes = []
 
     def info(self, i) -> JxlBasicInfo:
         info = JxlBasicInfo()
         self._chk(libjxl().JxlHipBatchGetBasicInfo(self._h, i, C.byref(info)))
         return info
 
+    def planes_layout(self, i):
+        """(offset, plane_stride, total) of image i's destination, in bytes: where the first extra plane starts, the bytes from one plane to the next, the size of the
+        whole destination — colour output and planes (include/jxl_hip.h JxlHipBatchOutputPlanesLayout).  Without extra_planes: (total, 0, total).  Host only."""
+        off, pitch, total = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self._chk(libjxl().JxlHipBatchOutputPlanesLayout(self._h, int(i), C.byref(off), C.byref(pitch), C.byref(total)))
+        return int(off.value), int(pitch.value), int(total.value)
+
     def out_size(self, i) -> int:
+        if self._planes[i] is not None:
+            return self.planes_layout(i)[2]
         s = C.c_size_t()
         if self._jpeg_scale[i] != 1:
             rs = _jpeg_scaled(self._jpeg_scale[i], self._scale[i], self._resizes[i])
@@ -1018,8 +1084,10 @@ def arena_pool_trim() -> int:
 
 
 def image_out_size(data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, downscale=1, planar=False, plane_stride=0, scale=None, bias=None,
-                   resize=None, crop=None, jpeg_scale=1):
+                   resize=None, crop=None, jpeg_scale=1, extra_planes=None, plane_scale=None, plane_bias=None, planes_offset=0, planes_stride=0):
     """(JxlBasicInfo, bytes of the decoded image in that format) from the headers alone — host-only (JxlHipImageOutSize).
+    extra_planes, plane_scale, plane_bias, planes_offset, planes_stride: the size of the colour output with those extra-channel planes behind it, as for BatchDecoder.add
+    (JxlHipImageOutSizePlanes); what the image does not take raises "unsupported: extra planes ...".
     jpeg_scale=2 | 4 | 8: the size of libjpeg's scaled decode, as for BatchDecoder.add (JxlHipImageOutSizeJpegScaled); not together with downscale.
     downscale=8: the size of the 1:8 decode (JxlHipImageOutSizeScaled); the info stays that of the full-size image.
     planar, plane_stride, scale, bias: the layout as for BatchDecoder.add (JxlHipImageOutSizeLayout); a layout the image or the sample type does not take raises.
@@ -1029,6 +1097,14 @@ def image_out_size(data: bytes, dtype="uint8", num_channels=0, endianness=Endian
     buf = np.frombuffer(data, dtype=np.uint8)
     layout = _layout(planar, plane_stride, scale, bias)
     rs = _resize(resize, crop)
+    planes = _planes(extra_planes, plane_scale, plane_bias, planes_offset, planes_stride)
+    if planes is not None:
+        if jpeg_scale != 1:
+            raise GenericError("unsupported: extra planes beside a libjpeg-exact output (jpeg_scale)")
+        rsm = None if rs is None else _resample(resize, crop, None, False)
+        if libjxl().JxlHipImageOutSizePlanes(buf.ctypes.data, len(data), C.byref(fmt), int(downscale), _byref(layout), _byref(rsm), C.byref(planes), C.byref(info), C.byref(size)) != JXL_DEC_SUCCESS:
+            raise GenericError(last_error())
+        return info, size.value
     if jpeg_scale != 1:
         rs = _jpeg_scaled(jpeg_scale, downscale, rs)
         if libjxl().JxlHipImageOutSizeJpegScaled(buf.ctypes.data, len(data), C.byref(fmt), int(jpeg_scale), _byref(layout), _byref(rs), C.byref(info), C.byref(size)) != JXL_DEC_SUCCESS:
@@ -1093,7 +1169,8 @@ class Pipeline:
     __del__ = close
 
     def submit(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, host_ptrs=None, capacities=None, endianness=Endianness.Native, align=0, downscale=1,
-               planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_pixels=False, jpeg_scale=1, resize_u8=False) -> int:
+               planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_pixels=False, jpeg_scale=1, resize_u8=False,
+               extra_planes=None, plane_scale=None, plane_bias=None, planes_offset=0, planes_stride=0) -> int:
         """Job of len(datas) images (bytes objects).  device_ptrs / host_ptrs: one destination address per image (exactly one of the two lists); the bytes objects and
         the destinations are kept referenced until wait().  downscale=8: the job is decoded at 1:8 (JxlHipPipelineSubmitScaled).  planar, plane_stride, scale, bias:
         the layout of every image of the job, as for BatchDecoder.add (JxlHipPipelineSubmitLayout).  resize, crop: every image of the job comes out resize[0] x resize[1]
@@ -1107,7 +1184,13 @@ class Pipeline:
         jpeg_scale=2 | 4 | 8 (with jpeg_pixels only; one scale per job): libjpeg's scaled decode, as for BatchDecoder.add (JxlHipPipelineSubmitJpegPixelsScaled) —
         destinations are sized with image_out_size(..., jpeg_scale=), crops are in the scaled picture.
         resize_u8=True (with jpeg_pixels and resize only): every image of the job is resampled in Pillow's 8-bit arithmetic, as for BatchDecoder.add
-        (JxlHipPipelineSubmitJpegPixelsResampled); an image the libjpeg-exact decode does not take fails alone."""
+        (JxlHipPipelineSubmitJpegPixelsResampled); an image the libjpeg-exact decode does not take fails alone.
+        extra_planes, plane_scale, plane_bias, planes_offset, planes_stride: extra-channel planes behind every image's colour output, as for BatchDecoder.add
+        (JxlHipPipelineSubmitPlanes) — destinations and capacities are sized with image_out_size(..., extra_planes=); an image that lacks one of the channels
+        fails alone; not with jpeg_pixels."""
+        planes = _planes(extra_planes, plane_scale, plane_bias, planes_offset, planes_stride)
+        if planes is not None and jpeg_pixels:
+            raise GenericError("unsupported: extra planes beside a libjpeg-exact output (a jpeg_pixels job)")
         if resize_u8:
             _resize_u8(downscale, resize)
             if not jpeg_pixels:
@@ -1142,6 +1225,10 @@ class Pipeline:
                 t = libjxl().JxlHipPipelineSubmitJpegPixelsScaled(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, _byref(layout), each, int(jpeg_scale))
             else:
                 t = libjxl().JxlHipPipelineSubmitJpegPixels(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, _byref(layout), each)
+        elif planes is not None:
+            if each is None and resize is not None:
+                each = (JxlHipOutputResample * max(1, n))(*[_resample(resize, crop, None, False) for _ in range(n)])
+            t = libjxl().JxlHipPipelineSubmitPlanes(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), _byref(layout), each, C.byref(planes))
         elif each is not None:
             t = libjxl().JxlHipPipelineSubmitResampled(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), _byref(layout), each)
         elif rs is not None:

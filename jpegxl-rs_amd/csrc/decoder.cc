@@ -590,7 +590,7 @@ int Batch::AddImage(const uint8_t* data, size_t size, bool allow_partial) {
 bool Batch::is_partial(int i) const { return images_[pub_[i].first_unit]->plan.partial; }
 
 int Batch::Append(ParsedImage&& im) {
-  PubImage pi; pi.first_unit = (int)images_.size(); pi.num_units = (int)im.units.size(); pi.complex = im.complex;
+  PubImage pi; pi.first_unit = (int)images_.size(); pi.num_units = (int)im.units.size(); pi.complex = pi.parsed_complex = im.complex;
   for (auto& u : im.units) { u->pub_index = (int)pub_.size(); images_.push_back(std::move(u)); }
   pub_.push_back(pi);
   prepared_ = false;
@@ -760,7 +760,56 @@ uint32_t Batch::SourceWidth(const ImageHeader& ih, const OutputSpec& o) { return
 uint32_t Batch::SourceHeight(const ImageHeader& ih, const OutputSpec& o) { return Scaled((!o.keep_orientation && ih.orientation > 4) ? ih.xsize : ih.ysize, o); }
 uint32_t Batch::OrientedWidth(const ImageHeader& ih, const OutputSpec& o) { return o.resized() ? o.resize_w : SourceWidth(ih, o); }
 uint32_t Batch::OrientedHeight(const ImageHeader& ih, const OutputSpec& o) { return o.resized() ? o.resize_h : SourceHeight(ih, o); }
-size_t Batch::OutputSize(const ImageHeader& ih, const OutputSpec& o) {
+static size_t SampleBytes(uint32_t type) { return type == 0 ? 1 : type == 2 ? 4 : 2; }
+size_t Batch::OutputSize(const ImageHeader& ih, const OutputSpec& o) { return o.planes.any() ? PlanesLayoutOf(ih, o).total : ColorOutputSize(ih, o); }
+size_t Batch::PlaneRowStride(const ImageHeader& ih, const OutputSpec& o, const PlaneRequest& r) {
+  size_t stride = (size_t)OrientedWidth(ih, o) * SampleBytes(r.type);
+  if (r.align > 1) stride = (stride + r.align - 1) / r.align * r.align;
+  return stride;
+}
+// Every refusal is worded "unsupported: extra planes ..."; what concerns the kind of decode first, then the requests one by one.
+std::string Batch::PlanesRefusal(const ImageHeader& ih, const OutputSpec& o) {
+  if (!o.planes.any()) return std::string();
+  const std::string head = "unsupported: extra planes ";
+  if (o.downscale == 8) return head + "of the 1:8 decode (downscale 8)";
+  if (o.jpeg_scale != 1 || o.resize_u8) return head + "beside a libjpeg-exact output (jpeg_scale, resize_u8)";
+  if (o.planes.req.size() > kMaxOutputPlanes) return head + "beyond " + std::to_string(kMaxOutputPlanes) + " requests";
+  for (const PlaneRequest& r : o.planes.req) {
+    if (r.index >= ih.extra.size()) return head + "of extra channel " + std::to_string(r.index) + ": the image has " + std::to_string(ih.extra.size()) + " extra channels";
+    if (r.type > 3) return head + "of an unknown sample type";
+    if (r.affine && r.type != 2 && r.type != 3) return head + "with scale / bias need a float sample type";
+  }
+  return std::string();
+}
+PlanesLayout Batch::PlanesLayoutOf(const ImageHeader& ih, const OutputSpec& o) {
+  const size_t color = ColorOutputSize(ih, o);
+  const std::string why = PlanesRefusal(ih, o);
+  if (!why.empty()) throw ParseError(why, true);
+  PlanesLayout l;
+  if (!o.planes.any()) { l.offset = l.total = color; return l; }
+  const size_t rows = OrientedHeight(ih, o);
+  size_t tight = 0, sample = 1;      // the largest plane, the largest sample
+  for (const PlaneRequest& r : o.planes.req) { tight = std::max(tight, PlaneRowStride(ih, o, r) * rows); sample = std::max(sample, SampleBytes(r.type)); }
+  size_t def_offset, def_pitch;
+  if (o.planar) {
+    uint32_t nc;
+    const size_t cstride = OutputStride(ih, o, &nc);
+    const size_t cplane = o.plane_stride ? o.plane_stride : cstride * rows;
+    def_offset = (size_t)nc * cplane; def_pitch = cplane;
+    if (!o.planes.plane_stride && tight > cplane) throw ParseError("extra planes: a plane of this image takes " + std::to_string(tight) + " bytes, the colour layout's plane_stride is " + std::to_string(cplane), false);
+  } else {
+    def_offset = (color + 15) / 16 * 16; def_pitch = tight;
+  }
+  l.offset = o.planes.offset ? o.planes.offset : def_offset;
+  l.pitch = o.planes.plane_stride ? o.planes.plane_stride : def_pitch;
+  if (l.offset < def_offset) throw ParseError("extra planes: offset " + std::to_string(l.offset) + " is below the default, " + std::to_string(def_offset) + " bytes behind the start of the colour output", false);
+  if (l.offset % sample) throw ParseError("extra planes: offset must be a multiple of the sample size", false);
+  if (l.pitch < std::max(tight, def_pitch)) throw ParseError("extra planes: plane_stride " + std::to_string(l.pitch) + " is below the default, " + std::to_string(std::max(tight, def_pitch)) + " bytes", false);
+  if (l.pitch % sample) throw ParseError("extra planes: plane_stride must be a multiple of the sample size", false);
+  l.total = l.offset + o.planes.req.size() * l.pitch;
+  return l;
+}
+size_t Batch::ColorOutputSize(const ImageHeader& ih, const OutputSpec& o) {
   // jpegxl-sys decode.rs:1100 JxlDecoderImageOutBufferSize: stride * (h - 1) + w * C * bytes
   uint32_t nc;
   const size_t stride = OutputStride(ih, o, &nc);
@@ -879,12 +928,29 @@ OutputDesc FillOutput(const ImageEntry& e, uint8_t* work, uint8_t* big, bool res
     return d;
   }
   d.out = (uint8_t*)(e.out.device_ptr ? e.out.device_ptr : work + e.off_out);
-  d.planar = e.out.planar; d.plane_stride = !e.out.planar ? 0 : e.out.plane_stride ? e.out.plane_stride : e.out_size / std::max(1u, e.out.num_channels);
+  d.planar = e.out.planar; d.plane_stride = !e.out.planar ? 0 : e.out.plane_stride ? e.out.plane_stride : e.color_size / std::max(1u, e.out.num_channels);
   d.affine = e.out.affine;
   for (int c = 0; c < 4; c++) { d.scale[c] = e.out.scale[c]; d.bias[c] = e.out.bias[c]; }
   d.out_stride = e.out_stride; d.out_channels = e.out.num_channels; d.out_type = e.out.type; d.out_big_endian = e.out.big_endian; d.out_int_mul = IntMul(e.out);
   d.out_orient = e.out.keep_orientation ? 1 : e.ih.orientation; d.is_gray = e.ih.color_space == 1;
   if (resize_target) d.out_orient = 1;
+  return d;
+}
+// Requested extra-channel plane k (OutputSpec::planes) in the caller's destination: slot 0 of a planar one-channel output at planes_layout.offset + k x pitch, in the
+// request's own format; never int_bits (a plane is the channel as it is).  The write of a resized output goes to the plane's f32 resize source instead (frame_tail.cc
+// TailPlanes builds that descriptor itself); resize_target: the destination as ResizeKernel<1> stores into it, the orientation applied already.
+OutputDesc FillPlaneOutput(const ImageEntry& e, size_t k, uint8_t* work, bool resize_target) {
+  const PlaneRequest& r = e.out.planes.req[k];
+  ImageHeader dims = e.ih;
+  dims.xsize = e.out.resized() ? e.out.resize_w : e.src_w; dims.ysize = 1; dims.orientation = 1;      // (PlaneRowStride reads the oriented width alone)
+  OutputDesc d{};
+  d.out = (uint8_t*)(e.out.device_ptr ? e.out.device_ptr : work + e.off_out) + e.planes_layout.offset + k * e.planes_layout.pitch;
+  d.planar = 1; d.plane_stride = e.planes_layout.pitch; d.out_channels = 1;
+  d.affine = r.affine ? 1 : 0;
+  for (int c = 0; c < 4; c++) { d.scale[c] = r.scale; d.bias[c] = r.bias; }
+  d.out_stride = Batch::PlaneRowStride(dims, OutputSpec(), r);
+  d.out_type = r.type; d.out_big_endian = r.big_endian; d.out_int_mul = r.type == 0 ? 255.0f : 65535.0f;
+  d.out_orient = resize_target || e.out.keep_orientation ? 1 : e.ih.orientation; d.is_gray = 1;
   return d;
 }
 // What the 1:8 decode takes: single-frame VarDCT images that carry their own LF coefficients and end in their own pixels (no frame tail).
@@ -943,6 +1009,10 @@ static bool JpegRegionRule(const ImageEntry& e, const OutputSpec& o, uint32_t gr
 }
 void Batch::SetOutput(int i, const OutputSpec& o) {
   ImageEntry& e = *images_[pub_[i].first_unit];
+  if (o.planes.any()) {      // (first: a request the decode cannot serve is answered in its own words, whatever else the output asks for)
+    const std::string why = PlanesRefusal(e.ih, o);
+    if (!why.empty()) throw ParseError(why, true);
+  }
   if (o.downscale != 1) {
     if (o.downscale != 8) throw ParseError("downscale must be 1 or 8", false);
     const std::string why = DownscaleRefusal(i);
@@ -963,18 +1033,24 @@ void Batch::SetOutput(int i, const OutputSpec& o) {
     std::string why;
     if (!CanDecodeJpegPixelsAs(i, o, &why)) throw ParseError("unsupported: integer resample of an image the libjpeg-exact decode does not take (" + why + ")", true);
   }
-  e.out = o;
-  e.jpeg_dc_eligible = JpegDcEligibleOf(e.plan, o);      // (jpeg_scale 8: CanDecodeJpegPixelsAs has taken the image above)
   if (o.only_frame >= pub_[i].num_units) throw ParseError("non-coalesced output: no such frame", false);
+  // Everything that can refuse the output — a layout, a resize or a crop the image does not fit, an offset or pitch of the planes below its default — is computed
+  // before anything of the entry is assigned: a call that throws leaves the entry, spec and sizes alike, as it was.
+  OutputSpec out = o;
   // (a lone frame that fills the image is the same either way: the plain path keeps it)
-  if (o.only_frame == 0 && pub_[i].num_units == 1 && !e.plan.have_crop) e.out.only_frame = -1;
-  if (o.upto_frame >= pub_[i].num_units - 1 || o.only_frame >= 0) e.out.upto_frame = -1;     // (the last frame's composite is the image)
+  if (o.only_frame == 0 && pub_[i].num_units == 1 && !e.plan.have_crop) out.only_frame = -1;
+  if (o.upto_frame >= pub_[i].num_units - 1 || o.only_frame >= 0) out.upto_frame = -1;     // (the last frame's composite is the image)
   ImageHeader dims = e.ih;
-  OutputDims(i, e.out, &dims.xsize, &dims.ysize);
+  OutputDims(i, out, &dims.xsize, &dims.ysize);
   uint32_t nc;
-  e.out_stride = OutputStride(dims, o, &nc);
-  e.out.num_channels = nc;
-  e.out_size = OutputSize(dims, o);
+  const size_t out_stride = OutputStride(dims, o, &nc);
+  out.num_channels = nc;
+  const size_t color_size = ColorOutputSize(dims, o);
+  const PlanesLayout planes_layout = PlanesLayoutOf(dims, o);
+  e.out = out;
+  e.jpeg_dc_eligible = JpegDcEligibleOf(e.plan, o);      // (jpeg_scale 8: CanDecodeJpegPixelsAs has taken the image above)
+  e.out_stride = out_stride; e.color_size = color_size; e.planes_layout = planes_layout;
+  e.out_size = planes_layout.total;
   e.src_w = SourceWidth(dims, o); e.src_h = SourceHeight(dims, o);
   // (the crop lies inside the source picture: OutputSize above has thrown otherwise)
   e.jpeg_region_eligible = false;
@@ -996,6 +1072,7 @@ void Batch::SetOutputAllFrames(int i, const OutputSpec& o, const vec<int>& frame
   if (o.device_ptr || o.only_frame >= 0 || frames.empty()) throw ParseError("SetOutputAllFrames: internal output buffers, coalesced frames only", false);
   if (o.planar || o.affine) throw ParseError("SetOutputAllFrames: interleaved output without scale / bias only", false);
   if (o.resized() || o.cropped()) throw ParseError("SetOutputAllFrames: no resized output", false);
+  if (o.planes.any()) throw ParseError("unsupported: extra planes of kept animation canvases (all frames in one decode)", true);
   for (size_t k = 0; k < frames.size(); k++)
     if (frames[k] < 0 || frames[k] >= pub_[i].num_units || (k && frames[k] <= frames[k - 1])) throw ParseError("SetOutputAllFrames: frame list must be ascending positions among the image's frames", false);
   OutputSpec oo = o;
@@ -1134,6 +1211,7 @@ int64_t Batch::Info(const std::string& name) const {
   if (name == "mod_group_lds_bytes") return prepared_ ? (int64_t)ModularGroupLdsBytes(cfg) : -1;
   if (name == "resize_u8_images") return resize_u8_images_;         // images of the last decode whose resize ran in Pillow's 8-bit arithmetic (OutputSpec::resize_u8: ResizeU8Kernel)
   if (name == "resize_launches") return resize_launches_;           // kernel launches the last decode's resizes took (two per group of the table: Batch::EnqueueResizes)
+  if (name == "plane_outputs") return plane_outputs_;               // extra-channel planes the last decode wrote beside the colour outputs (OutputSpec::planes: EcPlanesOutKernel)
   if (name == "jpeg_device_images") return jpeg_device_images_;     // images of the last ReconstructJpegs whose scans the device wrote / that went through the host writer
   if (name == "jpeg_host_images") return jpeg_host_images_;
   if (name == "jpeg_device_progressive_images") return jpeg_device_progressive_images_;    // ... of the device's, those with at least one progressive scan
@@ -1387,15 +1465,29 @@ void Batch::MarkComplex(PubImage& pi) {
 
 // Images whose output only the frame tail can write become complex: rendered spot colours (stage_spot.cc; grey images keep one colour plane there: not handled), a single
 // frame as coded (its own size, no blending), un-premultiplied alpha (JxlDecoderSetUnpremultiplyAlpha, jpegxl-rs decode.rs:353).  Reads and adds nothing of PrepareState.
+// ... and extra-channel planes beside the colour output (OutputSpec::planes): the frame tail is the one place where every extra channel of the finished image is a float
+// plane (TailDeliver).  OutputNeedsTail: the rules that do not ask about planes (Batch::ComplexWithoutPlanes).
+static bool OutputNeedsTail(const ImageHeader& ih, const OutputSpec& o) {
+  bool premul = false, spot = false;
+  for (auto& x : ih.extra) if (x.type == 0) { premul = x.alpha_associated; break; }
+  for (auto& x : ih.extra) if (x.type == 2) spot = true;
+  return (spot && o.render_spotcolors) || o.only_frame >= 0 || (o.unpremul_alpha && premul);
+}
 void Batch::PromoteToComplex() {
   for (PubImage& pi : pub_) {
     ImageEntry& first = *images_[pi.first_unit];
-    bool premul = false, spot = false;
-    for (auto& x : first.ih.extra) if (x.type == 0) { premul = x.alpha_associated; break; }
+    bool spot = false;
     for (auto& x : first.ih.extra) if (x.type == 2) spot = true;
     if (spot && first.out.render_spotcolors && first.ih.color_space == 1) throw ParseError("unsupported: spot colours on a grey image", true);
-    if ((spot && first.out.render_spotcolors) || first.out.only_frame >= 0 || (first.out.unpremul_alpha && premul)) MarkComplex(pi);
+    if (OutputNeedsTail(first.ih, first.out) || first.out.planes.any()) MarkComplex(pi);
   }
+}
+bool Batch::ComplexWithoutPlanes(int i, const OutputSpec& o) const {
+  const PubImage& pi = pub_[i];
+  const ImageEntry& first = *images_[pi.first_unit];
+  OutputSpec oo = o;      // (as SetOutput normalises it)
+  if (oo.only_frame == 0 && pi.num_units == 1 && !first.plan.have_crop) oo.only_frame = -1;
+  return pi.parsed_complex || OutputNeedsTail(first.ih, oo);
 }
 
 // "tables1".  Adds natural_off, cs_bytes and, per unit, co's codestream, section tables, trees, codes and bcm; fills resize_plans_ (axis tables), the batch maxima and fplan_.
@@ -1438,6 +1530,7 @@ void Batch::PutStreamTables(PrepareState& st) {
         rp.tab[3 * ax + 2] = e.out.resize_u8 ? arena.Put(kk.data(), kk.size() * 4) : arena.Put(weight.data(), weight.size() * 4);
       }
       resize_plans_.push_back(rp);
+      for (size_t k = 0; k < e.out.planes.req.size(); k++) { rp.plane = (int)k; resize_plans_.push_back(rp); }      // (one-slot entries over the same axis tables)
     }
     st.cs_bytes[i] = e.cs.size;
     if (EndsBehindLf(i) && !p.single_section) {
@@ -1527,6 +1620,12 @@ void Batch::LayOutWork(PrepareState& st) {
       const size_t sample = e.out.resize_u8 ? 1 : 4;
       e.off_resize_src = st.take_big((size_t)e.src_w * e.src_h * e.out.num_channels * sample);
       e.off_resize_tmp = st.take_big((size_t)(e.out.cropped() ? e.out.crop_h : e.src_h) * e.out.resize_w * e.out.num_channels * sample);
+      // ... and per requested extra-channel plane one slot of each (OutputSpec::planes): the planes of one decode are resampled together, so each has rows of its own
+      e.off_plane_src.clear(); e.off_plane_tmp.clear();
+      for (size_t k = 0; k < e.out.planes.req.size(); k++) {
+        e.off_plane_src.push_back(st.take_big((size_t)e.src_w * e.src_h * 4));
+        e.off_plane_tmp.push_back(st.take_big((size_t)(e.out.cropped() ? e.out.crop_h : e.src_h) * e.out.resize_w * 4));
+      }
     }
     if (p.upsampling > 1) {   // kernel weights: custom (image header) or library default
       const int upk = p.upsampling == 2 ? 0 : p.upsampling == 4 ? 1 : 2;
@@ -2023,7 +2122,7 @@ void Batch::PlanLfSimt(PrepareState& st) {
 // resize_plans_ sorted by slot count.  Adds the table's room to the arena.
 void Batch::PlaceResizeTable(PrepareState& st) {
   // (the f32 resizes first, the integer ones of OutputSpec::resize_u8 behind them: the two arithmetics take different kernels and never share a launch group)
-  auto key = [&](const ResizePlan& r) { return (images_[r.unit]->out.resize_u8 ? 8u : 0u) + ResizeSlots(*images_[r.unit]); };
+  auto key = [&](const ResizePlan& r) { return r.plane >= 0 ? 1u : (images_[r.unit]->out.resize_u8 ? 8u : 0u) + ResizeSlots(*images_[r.unit]); };   // (a plane: one f32 slot)
   std::stable_sort(resize_plans_.begin(), resize_plans_.end(), [&](const ResizePlan& a, const ResizePlan& b) { return key(a) < key(b); });
   resize_table_off_ = 0;
   if (resize_plans_.empty()) return;
@@ -2049,8 +2148,12 @@ void Batch::BuildResizeTable() {
     a.ax = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[0]), (const uint32_t*)(dconst_ + rp.tab[1]), (const float*)(dconst_ + rp.tab[2])};
     a.ay = ResizeAxisDev{(const uint32_t*)(dconst_ + rp.tab[3]), (const uint32_t*)(dconst_ + rp.tab[4]), (const float*)(dconst_ + rp.tab[5])};
     a.od = FillOutput(e, dwork_, dbig_, /*resize_target=*/true);
+    if (rp.plane >= 0) {      // requested plane rp.plane of the image: its own source and rows, one slot, its place in the destination
+      a.src = (const float*)(dbig_ + e.off_plane_src[(size_t)rp.plane]); a.tmp = (float*)(dbig_ + e.off_plane_tmp[(size_t)rp.plane]); a.src_stride = e.src_w;
+      a.od = FillPlaneOutput(e, (size_t)rp.plane, dwork_, /*resize_target=*/true);
+    }
     table[k] = a;
-    const uint32_t slots = ResizeSlots(e);
+    const uint32_t slots = rp.plane >= 0 ? 1u : ResizeSlots(e);
     if (resize_groups_.empty() || resize_groups_.back().slots != slots || resize_groups_.back().u8 != a.u8 || resize_groups_.back().count >= group_max)
       resize_groups_.push_back(ResizeGroup{(uint32_t)k, 0, slots, 0, 0, 0, a.u8});
     ResizeGroup& g = resize_groups_.back();
@@ -2349,6 +2452,7 @@ void Batch::StagePixels(const PartRun& r) {
     if (!any_vardct_ && any_modchan_) EnqueueModularTail(r.stream);
     if (!stop && any_full_vardct_) LaunchOutput(dframes_, n, max_w_, max_h_, fplan_, cfg, r.stream);
     if (!stop && any_scaled_) LaunchLfOutput(dframes_, n, max_bw_, max_bh_, r.stream);   // 1:8 frames: the LF image through the colour transform and the write stage
+    plane_outputs_ = 0;
     if (!stop && any_complex_) EnqueuePostOps(r.stream);
     if (!stop) EnqueueResizes(r.stream);
     if (any_vardct_) { FailJpegScaledOutputs(r.stream); DebugSync("output / frame tail", r.stream); }
@@ -3303,6 +3407,12 @@ void Batch::CopyOutputSlotToHost(int i, int slot, void* dst, size_t size, void* 
 void Batch::CopyOutputToHost(int i, void* dst, size_t size, void* stream_v) {
   const ImageEntry& e = *images_[pub_[i].first_unit];
   HIP_CHECK(hipMemcpyAsync(dst, device_output(i), std::min(size, e.out_size), hipMemcpyDeviceToHost, (hipStream_t)stream_v));
+  HIP_CHECK(hipStreamSynchronize((hipStream_t)stream_v));
+}
+void Batch::CopyOutputRangeToHost(int i, size_t offset, void* dst, size_t size, void* stream_v) {
+  const ImageEntry& e = *images_[pub_[i].first_unit];
+  if (offset > e.out_size || size > e.out_size - offset) throw ParseError("CopyOutputRangeToHost: the range leaves the output", false);
+  HIP_CHECK(hipMemcpyAsync(dst, (const uint8_t*)device_output(i) + offset, size, hipMemcpyDeviceToHost, (hipStream_t)stream_v));
   HIP_CHECK(hipStreamSynchronize((hipStream_t)stream_v));
 }
 

@@ -13,6 +13,28 @@
 
 namespace jxlhip {
 
+// One extra-channel plane written beside the colour output (OutputSpec::planes): channel `index` as it is — the values alpha_from_extra = index puts into the alpha
+// slot, never un-premultiplied, untouched by spot rendering and int_bits — as one sample per pixel in a format of its own; float types may be stored as
+// fmaf(v, scale, bias).  The public calls give every plane the colour output's format; jxl_abi.cc serves buffers of differing formats.
+struct PlaneRequest {
+  uint32_t index = 0;          // extra channel
+  uint32_t type = 0;           // 0 u8, 1 u16, 2 f32, 3 f16
+  uint32_t big_endian = 0;
+  size_t align = 0;            // row pitch = oriented width x sample size, rounded up to this
+  bool affine = false; float scale = 1.0f, bias = 0.0f;
+};
+// The planes sit behind the colour output, plane k at offset + k x pitch of the destination; they follow the colour output's geometry (orientation, resize, crop, filter, mirror).
+// offset 0 = num_channels x plane_stride of a planar colour output (colour and extras form one [C + m, H, W] block), the colour size rounded up to 16 bytes of an
+// interleaved one; plane_stride 0 = the colour layout's plane_stride when the colour is planar, else tight (rows x row pitch).  Either may be given: at least the default
+// and a multiple of the sample size (Batch::PlanesLayoutOf).  Indices may repeat.
+struct OutputPlanes {
+  std::vector<PlaneRequest> req;
+  size_t offset = 0, plane_stride = 0;
+  bool any() const { return !req.empty(); }
+};
+struct PlanesLayout { size_t offset = 0, pitch = 0, total = 0; };
+constexpr size_t kMaxOutputPlanes = 4096;      // (the format's limit on channels)
+
 struct OutputSpec {
   uint32_t num_channels = 0;   // 0 = colour + alpha
   uint32_t type = 0;           // 0 u8, 1 u16, 2 f32, 3 f16
@@ -25,7 +47,8 @@ struct OutputSpec {
   int only_frame = -1;            // >= 0: non-coalesced output (JxlDecoderSetCoalescing(false)) — frame `only_frame` of the image as coded: its own size, its own
                                   // pixels after the colour transform, not blended onto the canvas
   int alpha_from_extra = -1;      // which extra channel fills the alpha slot of 2 / 4-channel output: -1 = the first one of type alpha; >= 0: that extra channel, as it is
-                                  // (JxlDecoderSetExtraChannelBuffer hands out any extra channel through this slot)
+                                  // (JxlDecoderSetExtraChannelBuffer hands out the extra channels of simple images through this slot, a decode per plane; `planes` below
+                                  // delivers any number of them from one decode, through the frame tail)
   uint32_t int_bits = 0;          // integer output: 0 = the full range of the sample type, else samples in [0, 2^int_bits - 1] (JxlDecoderSetImageOutBitDepth)
   bool render_spotcolors = true;  // JxlDecoderSetRenderSpotcolors: spot-colour extra channels are mixed into the colour channels (stage_spot.cc)
   uint32_t downscale = 1;         // 1, or 8: the 1:8 decode — the output is the frame's LF image, ceil(w / 8) x ceil(h / 8) pixels, one per 8x8 block, through the colour transform and the
@@ -49,6 +72,8 @@ struct OutputSpec {
   bool resize_u8 = false;                  // resized outputs of the libjpeg-exact decode only (Batch::CanDecodeJpegPixels, downscale 1): the resample is Pillow's 8-bit one over the
                                            // u8 picture libjpeg gives (include/jxl_hip.h, JxlHipBatchSetOutputJpegResampled: int32 weights of 22 fraction bits, rounded and clamped
                                            // to u8 behind each pass), byte for byte im.crop(box).resize(size, filter); the intermediate is u8.  Written by DecodeJpegPixels alone
+  // ---- extra-channel planes behind the colour output (Batch and Pipeline outputs; an image with any becomes complex, the frame tail delivers them: EcPlanesOutKernel)
+  OutputPlanes planes;
   bool resized() const { return resize_w || resize_h; }
   bool cropped() const { return crop_x0 || crop_y0 || crop_w || crop_h; }
 };
@@ -66,7 +91,11 @@ struct ImageEntry {
   FramePlan plan;
   uint64_t frame_bitpos = 0;
   OutputSpec out;                      // (first unit of the image)
-  size_t out_stride = 0, out_size = 0;
+  size_t out_stride = 0, out_size = 0; // out_size: the whole destination, the colour output and the planes behind it
+  size_t color_size = 0;               // (first unit) the colour output alone (= out_size without planes)
+  PlanesLayout planes_layout;          // (first unit) where out.planes go in the destination
+  vec<size_t> off_plane_src, off_plane_tmp;   // (first unit, resized output with planes; pixel-plane arena) per requested plane: the oriented f32 plane EcPlanesOutKernel leaves for
+                                              // ResizeKernel<1>, the horizontally filtered rows
   vec<int> deliver_frames;             // (first unit) coalesced animation decoded once: the canvas after each of these frames goes to its own slot of the output area (SetOutputAllFrames)
   bool has_jbrd = false;
   int pub_index = 0, frame_index = 0;  // image the frame belongs to, position among its frames
@@ -148,7 +177,14 @@ class Batch {
   // size of the picture a resize reads (OrientedWidth / OrientedHeight of the same output without its resize)
   static uint32_t SourceWidth(const ImageHeader& ih, const OutputSpec& o);
   static uint32_t SourceHeight(const ImageHeader& ih, const OutputSpec& o);
-  static size_t OutputSize(const ImageHeader& ih, const OutputSpec& o);
+  static size_t OutputSize(const ImageHeader& ih, const OutputSpec& o);      // the colour output and, behind it, o.planes
+  static size_t ColorOutputSize(const ImageHeader& ih, const OutputSpec& o); // the colour output alone
+  // "" when o.planes can be written for an image with ih's extra channels, else the reason, "unsupported: extra planes ..."; OutputSize and SetOutput throw it
+  static std::string PlanesRefusal(const ImageHeader& ih, const OutputSpec& o);
+  // where o.planes go: offset of the first, pitch from one to the next, size of the whole destination; throws what does not fit (an offset or pitch below the default ...)
+  static PlanesLayout PlanesLayoutOf(const ImageHeader& ih, const OutputSpec& o);
+  // row pitch of requested plane k, bytes
+  static size_t PlaneRowStride(const ImageHeader& ih, const OutputSpec& o, const PlaneRequest& r);
   // "" when the layout of `o` (planar, plane_stride, affine) can be written for an image of ih's size, else the reason; OutputSize and SetOutput throw it
   static std::string LayoutRefusal(const ImageHeader& ih, const OutputSpec& o);
   // "" when the resize of `o` can be done for an image of ih's size (a target side of 0 or above 65535, a crop that is empty or leaves the picture), else the reason;
@@ -162,6 +198,8 @@ class Batch {
   // delivery (spot colours, a transfer function deferred behind them): the caller then decodes frame by frame (OutputSpec::upto_frame).
   void SetOutputAllFrames(int i, const OutputSpec& o, const vec<int>& frames);
   void CopyOutputSlotToHost(int i, int slot, void* dst, size_t size, void* stream);
+  // image i takes the frame tail under output `o` whether or not planes are asked for (what PromoteToComplex decides without its clause for OutputSpec::planes): host only
+  bool ComplexWithoutPlanes(int i, const OutputSpec& o) const;
   int num_frames(int i) const { return pub_[i].num_units; }
   const ImageEntry& frame(int i, int k) const { return *images_[pub_[i].first_unit + k]; }
   void SetOutput(int i, const OutputSpec& o);
@@ -253,6 +291,7 @@ class Batch {
   void FinishStatus(void* stream, vec<uint32_t>* per_unit);
   // Copies frame i's pixels to host memory (after Finish).
   void CopyOutputToHost(int i, void* dst, size_t size, void* stream);
+  void CopyOutputRangeToHost(int i, size_t offset, void* dst, size_t size, void* stream);   // bytes [offset, offset + size) of it (one plane of OutputSpec::planes)
   // the preview of image i (JXL_DEC_PREVIEW_IMAGE): its header (the image header with the preview's size), the size of its output, the decode into host memory
   ImageHeader PreviewHeaderOf(int i) const;
   size_t PreviewOutputSize(int i, const OutputSpec& o) const;
@@ -295,7 +334,7 @@ class Batch {
  private:
   int device_;
   vec<std::unique_ptr<ImageEntry>> images_;   // decode units (frames), in image order
-  struct PubImage { int first_unit = 0, num_units = 1; bool complex = false; };
+  struct PubImage { int first_unit = 0, num_units = 1; bool complex = false, parsed_complex = false; };   // parsed_complex: complex as parsed, before any output promoted it
   vec<PubImage> pub_;                          // images as the caller counts them
   // ---- the phases of Prepare, in the order it calls them (decoder.cc); what they share beyond the members is in PrepareState
   struct PrepareState;
@@ -370,6 +409,8 @@ class Batch {
   void TailToFloat(TailImage& im, TailUnit& t); void TailPatches(TailImage& im, TailUnit& t); void TailSplines(TailImage& im, TailUnit& t); void TailUpsample(TailImage& im, TailUnit& t);
   void TailNoise(TailUnit& t); void TailLfHandOver(TailUnit& t); void TailColour(TailImage& im, TailUnit& t); void TailOwnFrame(TailImage& im, TailUnit& t);
   void TailBlend(TailImage& im, TailUnit& t); void TailDeliver(TailImage& im, TailUnit& t, int slot);
+  void TailPlanes(TailImage& im, const char* stage, const vec<size_t>& ec, uint32_t ec_stride, uint32_t w, uint32_t h);   // OutputSpec::planes: the delivery op behind LaunchWrite
+  int64_t plane_outputs_planned_ = 0, plane_outputs_ = 0;   // planes the recorded ops write (PlanPostOps); planes the last decode wrote (EnqueuePostOps)
   WriteArgs TailWriteArgs(const TailImage& im, const size_t p[3], uint32_t stride, const vec<size_t>& ec, uint32_t ec_stride, uint32_t w, uint32_t h);
   void TailDeferredTf(const TailUnit& t, const char* stage, const size_t p[3], uint32_t stride, uint32_t w, uint32_t h);
   float* BigPlane(size_t off) const { return (float*)(dbig_ + off); }                                // (read when an op runs as well as when it is planned)
@@ -377,7 +418,8 @@ class Batch {
   void EnqueuePostOps(void* stream);
   // resized outputs: per image one ResizeArgs (kernels.h), built by Prepare into a table of the constant arena — sorted by slot count, cut into groups of at most
   // resize_group_max entries — and launched group by group behind everything that writes pixels
-  struct ResizePlan { int unit; size_t tab[6]; };    // constant-arena offsets of the two axes' tables: lo, first, weights of x, then of y
+  struct ResizePlan { int unit; size_t tab[6]; int plane = -1; };    // constant-arena offsets of the two axes' tables: lo, first, weights of x, then of y; plane >= 0: the one-slot
+                                                                     // entry of requested plane `plane` of the image (OutputSpec::planes), which shares the image's tables
   vec<ResizePlan> resize_plans_;
   vec<ResizeGroup> resize_groups_;
   size_t resize_table_off_ = 0;

@@ -29,6 +29,8 @@ struct Arena {
 
 void FillColor(const ImageHeader& ih, bool do_ycbcr, FrameDev& f);
 OutputDesc FillOutput(const ImageEntry& e, uint8_t* work, uint8_t* big, bool resize_target = false);
+// ... and requested extra-channel plane k (OutputSpec::planes) in the caller's destination: one planar slot with the plane's own type, byte order, row pitch, scale / bias
+OutputDesc FillPlaneOutput(const ImageEntry& e, size_t k, uint8_t* work, bool resize_target = false);
 void DebugSync(const char* what, void* stream);     // under JXL_HIP_DEBUG_SYNC: names the stage on stderr and waits for it
 
 }  // namespace jxlhip

@@ -250,6 +250,36 @@ void Batch::TailDeferredTf(const TailUnit& t, const char* stage, const size_t p[
   PostOp(stage, [=](void* st) { LaunchColor(ta, st); });
 }
 
+// ---- extra-channel planes beside the colour output (OutputSpec::planes): one more op behind the write stage, over the extra channels of what was just written — the
+// canvas planes (TailDeliver) or the frame's own (TailOwnFrame), w x h samples each.  One table entry per request in the constant arena; a resized output takes the plane
+// as oriented f32 into its resize source among the pixel planes, from where the plane's one-slot entry of the resample table stores it (Batch::BuildResizeTable).
+void Batch::TailPlanes(TailImage& im, const char* stage, const vec<size_t>& ec, uint32_t ec_stride, uint32_t w, uint32_t h) {
+  const ImageEntry& first = im.first;
+  const OutputPlanes& pl = first.out.planes;
+  if (!pl.any()) return;
+  vec<EcPlaneOutDev> table(pl.req.size());
+  for (size_t k = 0; k < pl.req.size(); k++) {
+    if (pl.req[k].index >= ec.size()) throw ParseError("unsupported: extra planes of extra channel " + std::to_string(pl.req[k].index) + ": the image has " + std::to_string(ec.size()) + " extra channels", true);
+    EcPlaneOutDev& e = table[k];
+    memset(&e, 0, sizeof(e));
+    e.src = BigPlane(ec[pl.req[k].index]); e.src_stride = ec_stride;
+    if (first.out.resized()) {
+      if (k >= first.off_plane_src.size()) throw ParseError("resize source of an extra plane", false);
+      e.od.out = dbig_ + first.off_plane_src[k];
+      e.od.out_stride = (uint64_t)first.src_w * 4; e.od.out_channels = 1; e.od.out_type = 2; e.od.out_int_mul = 1.0f; e.od.planar = 1;
+      e.od.out_orient = first.out.keep_orientation ? 1 : im.ih.orientation; e.od.is_gray = 1;
+    } else {
+      e.od = FillPlaneOutput(first, k, dwork_);
+    }
+  }
+  EcPlanesOutArgs a;
+  memset(&a, 0, sizeof(a));
+  a.num_planes = (uint32_t)table.size(); a.w = w; a.h = h;
+  const size_t o_tab = im.arena.Put(table.data(), table.size() * sizeof(EcPlaneOutDev));
+  plane_outputs_planned_ += (int64_t)table.size();
+  PostOp(stage, [=](void* st) { EcPlanesOutArgs b = a; b.table = (const EcPlaneOutDev*)(dconst_ + o_tab); LaunchEcPlanesOut(b, st); });
+}
+
 // ---- chroma upsampling, int -> float, the channel table
 void Batch::TailToFloat(TailImage& im, TailUnit& t) {
   const FramePlan& p = t.p; const ComplexBufs& cb = t.cb; const ImageHeader& ih = im.ih;
@@ -456,6 +486,7 @@ void Batch::TailOwnFrame(TailImage& im, TailUnit& t) {
   const WriteArgs wa = TailWriteArgs(im, t.cur, t.cur_stride, t.cur_ec, t.cur_ec_stride, t.fw, t.fh);
   TailDeferredTf(t, "own-frame output", t.cur, t.cur_stride, t.fw, t.fh);          // (the transfer function had been put off for a spot-colour stage this output does not run)
   PostOp("own-frame output", [=](void* st) { LaunchWrite(wa, st); });
+  TailPlanes(im, "own-frame output", t.cur_ec, t.cur_ec_stride, t.fw, t.fh);
 }
 
 static const Slot* BlendSource(const Slot* slots, const ImageHeader& ih, uint32_t idx) {
@@ -521,11 +552,13 @@ void Batch::TailDeliver(TailImage& im, TailUnit& t, int slot) {
   WriteArgs wa = TailWriteArgs(im, t.canvas, t.canvas_stride, t.canvas_ec, t.canvas_ec_stride, ih.xsize, ih.ysize);
   if (all_frames) wa.od.out += (size_t)slot * (im.first.out_size + 64);
   PostOp("delivery", [=](void* st) { LaunchWrite(wa, st); });
+  TailPlanes(im, "delivery", t.canvas_ec, t.canvas_ec_stride, ih.xsize, ih.ysize);      // (never with kept canvases: SetOutputAllFrames refuses planes)
 }
 
 void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
   Arena arena(hconst);
   std::deque<PendingTable> tables;
+  plane_outputs_planned_ = 0;
   for (const PubImage& pi : pub_) {
     if (!pi.complex) continue;
     const ImageEntry& first = *images_[pi.first_unit];
@@ -573,6 +606,7 @@ void Batch::PlanPostOps(HostStage& hconst, const vec<size_t>& up_weights_off) {
 // Under JXL_HIP_DEBUG_SYNC every op is named and waited for (DebugSync), so that a fault in the tail is reported with its stage.
 void Batch::EnqueuePostOps(void* stream) {
   for (auto& op : post_ops_) { op.second(stream); DebugSync(op.first, stream); }
+  plane_outputs_ = plane_outputs_planned_;
 }
 
 }  // namespace jxlhip

@@ -60,6 +60,7 @@ struct JxlDecoderStruct {
   int progression_passes;     // passes of every group the latest progression step of the current frame shows (0: the kDC step) — what JxlDecoderFlushImage draws
   size_t downsampling_target; // JxlDecoderGetIntendedDownsamplingRatio: 8 at the kDC step, the frame header's ratio for the passes shown after that, 1 for the full image
   bool frame_done;     // JXL_DEC_FULL_IMAGE of frames[frame_cursor] has been returned: its header stays readable until the next JxlDecoderProcessInput moves on
+  int64_t frame_decodes;   // Batch::Run calls the last delivered frame took (JxlHipDecoderInfo "frame_decodes"): 1, + one per extra-channel buffer served by a pass of its own; 0 from kept canvases
   Batch* batch;
   int device;
   void* stream;        // the decoder's own non-blocking HIP stream (SURVEY 8b "Threading"): created with the first decode, kept over Reset, destroyed with the decoder
@@ -98,7 +99,7 @@ static void ClearState(JxlDecoder* d) {
   d->jpeg_buffer = nullptr; d->jpeg_size = 0; d->jpeg_set = false;
   d->jpeg_available = false; d->jpeg_written = 0; d->jpeg_bytes.clear();
   d->stage = JxlDecoderStruct::kInit; d->events_emitted = 0; d->started = false; d->need_out_reported = false;
-  d->frames.clear(); d->frame_cursor = 0; d->skip_frames = 0; d->frame_announced = false; d->frame_done = false;
+  d->frames.clear(); d->frame_cursor = 0; d->skip_frames = 0; d->frame_announced = false; d->frame_done = false; d->frame_decodes = 0;
   d->anim_cached = d->anim_cache_failed = false; d->partial = false; d->progression_emitted = false; d->progression_passes = 0; d->downsampling_target = 1;
   d->mt_init = nullptr; d->mt_run = nullptr; d->mt_destroy = nullptr; d->mt_opaque = nullptr;
   d->ec_buffers.clear(); d->progressive_detail = 1 /* kDC, libjxl's default */; d->out_int_bits = 0;
@@ -484,6 +485,13 @@ JxlDecoderStatus JxlDecoderSetExtraChannelBuffer(JxlDecoder* d, const JxlPixelFo
   return JXL_DEC_SUCCESS;
 }
 
+// facts about the decoder by name (include/jxl_hip.h); -1: unknown
+int64_t JxlHipDecoderInfo(const JxlDecoder* d, const char* name) {
+  if (!d || !name) return -1;
+  if (!strcmp(name, "frame_decodes")) return d->frame_decodes;
+  return -1;
+}
+
 // ---- decode.rs:1482 / :1513 / :1528
 JxlDecoderStatus JxlDecoderSetProgressiveDetail(JxlDecoder* d, int detail) {
   if (!d || detail < 0 || detail > 3) { SetLastError("unsupported progressive detail (kFrames, kDC, kLastPasses, kPasses are accepted)"); return JXL_DEC_ERROR; }
@@ -780,6 +788,7 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
                                d->anim_unpremul == d->unpremul_alpha && d->anim_spot == d->render_spotcolors && d->anim_int_bits == d->out_int_bits;
       int anim_slot = -1;
       bool scheduled = false;       // the pixels are in the caller's buffer already (shared pipeline)
+      d->frame_decodes = 0;
       if (o.upto_frame >= 0 || (d->coalescing && d->frames.size() > 1)) {
         if (!d->anim_cached && !d->anim_cache_failed && d->ec_buffers.empty()) {
           try {
@@ -790,6 +799,7 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
             d->batch->Prepare(DecoderStream(d));
             d->batch->Run(DecoderStream(d));       // ══► the HIP hot path, once for the whole animation
             d->batch->Finish(DecoderStream(d));
+            d->frame_decodes = 1;
             d->anim_cached = true; d->anim_format = d->out_format; d->anim_keep_orientation = d->keep_orientation; d->anim_unpremul = d->unpremul_alpha; d->anim_spot = d->render_spotcolors; d->anim_int_bits = d->out_int_bits;
             anim_slot = (int)d->frame_cursor;
           } catch (const ParseError& e) {
@@ -798,10 +808,34 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
           }
         } else if (same_format && d->ec_buffers.empty()) anim_slot = (int)d->frame_cursor;
       }
+      // Extra-channel buffers (JxlDecoderSetExtraChannelBuffer) of an image that takes the frame tail under its colour output anyway — layers, patches, spot colours,
+      // non-coalesced frames — ride in the frame's main decode as planes behind the colour output (OutputSpec::planes), each in its own buffer's format: the colour
+      // bytes of such a decode cannot change.  Every other image keeps the pass per plane below (the fused kernels of simple images do not write planes).
+      bool planes_in_main = false;
       if (anim_slot < 0) {
         d->anim_cached = false;           // (the batch is prepared for something else from here on)
+        if (!d->ec_buffers.empty() && d->batch->ComplexWithoutPlanes(0, o)) {
+          for (auto& eb : d->ec_buffers) {
+            OutputSpec one_spec;
+            JxlPixelFormat one = eb.format; one.num_channels = 1;
+            if (!FormatToSpec(&one, &one_spec)) throw ParseError("bad pixel format of an extra channel buffer", false);
+            PlaneRequest r;
+            r.index = eb.index; r.type = one_spec.type; r.big_endian = one_spec.big_endian; r.align = one_spec.align;
+            o.planes.req.push_back(r);
+          }
+          planes_in_main = true;
+        }
         d->batch->SetOutput(0, o);
-        if (d->batch->image(0).out_size > d->out_size) { SetLastError("output buffer too small for this frame"); return JXL_DEC_ERROR; }
+        if (d->batch->image(0).color_size > d->out_size) { SetLastError("output buffer too small for this frame"); return JXL_DEC_ERROR; }
+        if (planes_in_main) {
+          uint32_t w = 0, h = 0;
+          d->batch->OutputDims(0, d->batch->image(0).out, &w, &h);
+          if (!d->keep_orientation && d->batch->image(0).ih.orientation > 4) std::swap(w, h);
+          for (size_t k = 0; k < d->ec_buffers.size(); k++) {
+            ImageHeader dims = d->batch->image(0).ih; dims.xsize = w; dims.ysize = 1; dims.orientation = 1;
+            if (Batch::PlaneRowStride(dims, OutputSpec(), o.planes.req[k]) * h > d->ec_buffers[k].size) throw ParseError("extra channel buffer too small for this frame", false);
+          }
+        }
         // A plain one-shot decode into the caller's buffer — what jpegxl-rs' decode_with does (decode.rs:461-484) — rides in a job of the device's shared pipeline:
         // decoders that run on other threads at this moment share the job (scheduler.cc).  Everything else runs as a batch of one on the decoder's own stream.
         const bool via_scheduler = SchedulerEnabled() && !d->has_mm && d->input_set && d->coalescing && d->frames.size() == 1 && o.only_frame < 0 && o.upto_frame < 0 &&
@@ -815,6 +849,7 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
           d->batch->Run(DecoderStream(d));       // ══► the HIP hot path
           d->batch->Finish(DecoderStream(d));
         }
+        d->frame_decodes = 1;
       } else if (d->batch->image(0).out_size > d->out_size) { SetLastError("output buffer too small for this frame"); return JXL_DEC_ERROR; }
       auto copy_out = [&](void* dst, size_t size) {
         if (scheduled) return;
@@ -823,7 +858,7 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
       };
       if (d->out_callback || d->mt_run) {
         // callback output: the image is decoded as a whole on the device, then handed out row by row
-        vec<uint8_t> host(d->batch->image(0).out_size);
+        vec<uint8_t> host(d->batch->image(0).color_size);
         copy_out(host.data(), host.size());
         uint32_t w = 0, h = 0;
         d->batch->OutputDims(0, d->batch->image(0).out, &w, &h);
@@ -835,8 +870,22 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
           for (size_t y = 0; y < h; y++) d->mt_run(run_opaque, 0, 0, y, w, host.data() + y * stride);
           d->mt_destroy(run_opaque);
         } else for (size_t y = 0; y < h; y++) d->out_callback(d->out_callback_opaque, 0, y, w, host.data() + y * stride);
-      } else copy_out(d->out_buffer, d->batch->image(0).out_size);
+      } else copy_out(d->out_buffer, d->batch->image(0).color_size);
+      if (planes_in_main) {
+        // the planes the main decode left behind the colour output, each in its buffer's format already: copied to the host plane by plane
+        const ImageEntry& e0 = d->batch->image(0);
+        uint32_t w = 0, h = 0;
+        d->batch->OutputDims(0, e0.out, &w, &h);
+        if (!d->keep_orientation && e0.ih.orientation > 4) std::swap(w, h);
+        for (size_t k = 0; k < d->ec_buffers.size(); k++) {
+          ImageHeader dims = e0.ih; dims.xsize = w; dims.ysize = 1; dims.orientation = 1;
+          const size_t bytes = Batch::PlaneRowStride(dims, OutputSpec(), e0.out.planes.req[k]) * h;
+          d->batch->CopyOutputRangeToHost(0, e0.planes_layout.offset + k * e0.planes_layout.pitch, d->ec_buffers[k].buffer, bytes, DecoderStream(d));
+        }
+        d->ec_buffers.clear();
+      }
       if (!d->ec_buffers.empty()) {
+        // (the buffers the main decode did not serve: simple images, whose fused kernels write no planes)
         // an extra channel as a plane of its own (JxlDecoderSetExtraChannelBuffer): one more pass of the frame per plane with that channel in the alpha slot of the interleaved
         // output (OutputSpec::alpha_from_extra), in the plane's sample type, de-interleaved here
         for (auto& eb : d->ec_buffers) {
@@ -848,6 +897,7 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
           oe.keep_orientation = o.keep_orientation; oe.unpremul_alpha = false; oe.render_spotcolors = o.render_spotcolors; oe.only_frame = o.only_frame; oe.upto_frame = o.upto_frame;
           d->batch->SetOutput(0, oe);
           d->batch->Prepare(DecoderStream(d)); d->batch->Run(DecoderStream(d)); d->batch->Finish(DecoderStream(d));
+          d->frame_decodes++;
           vec<uint8_t> host(d->batch->image(0).out_size);
           d->batch->CopyOutputToHost(0, host.data(), host.size(), DecoderStream(d));
           uint32_t w = 0, h = 0;
@@ -1006,6 +1056,47 @@ JxlDecoderStatus JxlHipBatchOutBufferSizeResampled(const JxlHipBatch* h, int i, 
 JxlDecoderStatus JxlHipBatchSetOutputResampled(JxlHipBatch* h, int i, const JxlPixelFormat* format, void* device_buffer, int downscale, const JxlHipOutputLayout* layout,
                                                const JxlHipOutputResample* resample) {
   return BatchSetOutput(h, i, format, device_buffer, downscale, layout, nullptr, "JxlHipBatchSetOutputResampled", resample, true);
+}
+// JxlHipOutputPlanes -> OutputSpec::planes, every plane in the colour output's format (NULL or no planes: none); what depends on the image is checked where the image is
+// known (Batch::PlanesRefusal / PlanesLayoutOf)
+static bool ApplyPlanes(const JxlHipOutputPlanes* p, OutputSpec* o, const char* who) {
+  o->planes = OutputPlanes();
+  if (!p || !p->num_planes) return true;
+  if (!p->extra_index) { SetLastError(std::string(who) + ": extra planes: no list of extra-channel indices"); return false; }
+  if (p->num_planes > kMaxOutputPlanes) { SetLastError(std::string(who) + ": unsupported: extra planes beyond " + std::to_string(kMaxOutputPlanes) + " requests"); return false; }
+  const bool affine = p->scale || p->bias;
+  if (affine && o->type != 2 && o->type != 3) { SetLastError(std::string(who) + ": unsupported: extra planes with scale / bias need a float sample type"); return false; }
+  o->planes.offset = p->offset; o->planes.plane_stride = p->plane_stride;
+  for (uint32_t k = 0; k < p->num_planes; k++) {
+    PlaneRequest r;
+    r.index = p->extra_index[k]; r.type = o->type; r.big_endian = o->big_endian; r.align = o->align;
+    r.affine = affine; r.scale = p->scale ? p->scale[k] : 1.0f; r.bias = p->bias ? p->bias[k] : 0.0f;
+    o->planes.req.push_back(r);
+  }
+  return true;
+}
+JxlDecoderStatus JxlHipBatchSetOutputPlanes(JxlHipBatch* h, int i, const JxlHipOutputPlanes* planes) {
+  const char* who = "JxlHipBatchSetOutputPlanes";
+  if (!h || i < 0 || (size_t)i >= h->b->size()) { SetLastError(std::string(who) + ": no such image"); return JXL_DEC_ERROR; }
+  try {
+    const ImageEntry& e = h->b->image(i);
+    if (e.out_size == 0) { SetLastError(std::string(who) + ": the image has no output yet (call JxlHipBatchSetOutput... first)"); return JXL_DEC_ERROR; }
+    OutputSpec o = e.out;
+    if (!ApplyPlanes(planes, &o, who)) return JXL_DEC_ERROR;
+    if (o.planes.any() && !e.deliver_frames.empty()) { SetLastError(std::string(who) + ": unsupported: extra planes of kept animation canvases (all frames in one decode)"); return JXL_DEC_ERROR; }
+    if (!e.deliver_frames.empty()) return JXL_DEC_SUCCESS;      // (nothing to clear: that output never had planes)
+    h->b->SetOutput(i, o);
+    return JXL_DEC_SUCCESS;
+  } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
+}
+JxlDecoderStatus JxlHipBatchOutputPlanesLayout(const JxlHipBatch* h, int i, size_t* offset, size_t* plane_stride, size_t* total) {
+  if (!h || i < 0 || (size_t)i >= h->b->size()) { SetLastError("JxlHipBatchOutputPlanesLayout: no such image"); return JXL_DEC_ERROR; }
+  const ImageEntry& e = h->b->image(i);
+  if (e.out_size == 0) { SetLastError("JxlHipBatchOutputPlanesLayout: the image has no output yet"); return JXL_DEC_ERROR; }
+  if (offset) *offset = e.planes_layout.offset;
+  if (plane_stride) *plane_stride = e.planes_layout.pitch;
+  if (total) *total = e.planes_layout.total;
+  return JXL_DEC_SUCCESS;
 }
 // libjpeg's scaled decodes (OutputSpec::jpeg_scale): the ...Resampled calls at downscale 1 with a scale of their own; layout and resample may be NULL
 static bool JpegScaleOk(int jpeg_scale, const char* who) {
@@ -1236,6 +1327,31 @@ int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* h, const uint8_t* const* d
     return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity, specs.empty() ? nullptr : specs.data());
   } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
 }
+// ... with extra-channel planes behind every image's colour output (OutputSpec::planes: one request list for the job); each may be NULL (no resize)
+int64_t JxlHipPipelineSubmitPlanes(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                                   const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, const JxlHipOutputPlanes* planes) {
+  const char* who = "JxlHipPipelineSubmitPlanes";
+  if (!DownscaleOk(downscale, who)) return -1;
+  try {
+    OutputSpec base;
+    if (!h || !FormatToSpec(format, &base)) { SetLastError(std::string(who) + ": bad pixel format"); return -1; }
+    if (!ApplyLayout(layout, &base, who) || !ApplyPlanes(planes, &base, who)) return -1;
+    base.downscale = (uint32_t)downscale;
+    if (base.planes.any() && downscale == 8) { SetLastError(std::string(who) + ": unsupported: extra planes of the 1:8 decode (downscale 8)"); return -1; }
+    if (!each) return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity);
+    std::vector<OutputSpec> specs((size_t)std::max(n, 0), base);
+    for (int i = 0; i < n; i++) {
+      if (!ApplyResample(&each[i], &specs[(size_t)i], who)) { SetLastError("image " + std::to_string(i) + ": " + JxlHipLastError()); return -1; }
+      if (each[i].xsize != each[0].xsize || each[i].ysize != each[0].ysize) {
+        SetLastError(std::string(who) + ": image " + std::to_string(i) + " asks for " + std::to_string(each[i].xsize) + " x " + std::to_string(each[i].ysize) + ", image 0 for " +
+                     std::to_string(each[0].xsize) + " x " + std::to_string(each[0].ysize) + ": one target size per job");
+        return -1;
+      }
+    }
+    if (n > 0) { base.resize_w = each[0].xsize; base.resize_h = each[0].ysize; }
+    return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity, specs.empty() ? nullptr : specs.data());
+  } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
+}
 // a libjpeg-exact job (Pipeline::Submit, jpeg_pixels): the layout and the per-image resamples of the calls above, no downscale
 static int64_t PipelineSubmitJpegPixels(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
                                         const size_t* out_capacity, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, int jpeg_scale, const char* who, uint32_t flags = 0) {
@@ -1368,6 +1484,26 @@ static JxlDecoderStatus ImageOutSize(const uint8_t* data, size_t size, const Jxl
     std::shared_ptr<ImageShared> sh(new ImageShared());
     bool have_container = false, has_jbrd = false;
     // (1:8: a prefix of the file will do — the headers say the size)
+    if (!ExtractCodestream(data, size, &sh->cs, &have_container, &has_jbrd, nullptr) && downscale == 1) return JXL_DEC_NEED_MORE_INPUT;
+    uint64_t bitpos = 0;
+    ParseImageHeader(sh->cs, &sh->ih, &bitpos);
+    sh->ih.have_container = have_container;
+    if (info) FillBasicInfo(sh->ih, info, false);
+    if (out_size) *out_size = Batch::OutputSize(sh->ih, o);
+    return JXL_DEC_SUCCESS;
+  } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
+}
+JxlDecoderStatus JxlHipImageOutSizePlanes(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout,
+                                          const JxlHipOutputResample* resample, const JxlHipOutputPlanes* planes, JxlBasicInfo* info, size_t* out_size) {
+  const char* who = "JxlHipImageOutSizePlanes";
+  if (!DownscaleOk(downscale, who)) return JXL_DEC_ERROR;
+  try {
+    OutputSpec o;
+    if (!FormatToSpec(format, &o)) { SetLastError("bad pixel format"); return JXL_DEC_ERROR; }
+    if (!ApplyLayout(layout, &o, who) || (resample && !ApplyResample(resample, &o, who)) || !ApplyPlanes(planes, &o, who)) return JXL_DEC_ERROR;
+    o.downscale = (uint32_t)downscale;
+    std::shared_ptr<ImageShared> sh(new ImageShared());
+    bool have_container = false, has_jbrd = false;
     if (!ExtractCodestream(data, size, &sh->cs, &have_container, &has_jbrd, nullptr) && downscale == 1) return JXL_DEC_NEED_MORE_INPUT;
     uint64_t bitpos = 0;
     ParseImageHeader(sh->cs, &sh->ih, &bitpos);

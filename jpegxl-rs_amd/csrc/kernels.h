@@ -321,6 +321,12 @@ void LaunchBlend(const BlendArgs& a, const EcChanDev* table, void* stream);
 // mix is order-dependent); use_canvas: the plates are the blended planes (else fg)
 void LaunchSpot(float* const p[3], uint32_t stride, const EcChanDev* table, uint32_t num_extra, uint32_t use_canvas, uint32_t w, uint32_t h, void* stream);
 void LaunchWrite(const WriteArgs& a, void* stream);
+// Extra-channel planes beside the colour output (OutputSpec::planes; EcPlanesOutKernel): one table entry per requested plane in the constant arena — the float plane of the
+// finished image it is taken from (w x h samples, src_stride floats per row) and where it goes: od is a one-slot planar output (pixel_ops.h OutPixelPtr / SlotValue /
+// StoreSample: type, byte order, orientation, row pitch, scale[0] / bias[0]), the caller's destination or — resized outputs — the plane's oriented f32 resize source.
+struct EcPlaneOutDev { const float* src; uint32_t src_stride, pad; OutputDesc od; };
+struct EcPlanesOutArgs { const EcPlaneOutDev* table; uint32_t num_planes, w, h; };
+void LaunchEcPlanesOut(const EcPlanesOutArgs& a, void* stream);
 // JPEG reconstruction: quantised coefficients of a JPEG-transcoded frame in JPEG layout — component c (0 Y, 1 Cb, 2 Cr), block raster
 // order, 64 coefficients in natural (row-major) order: DC from the quantised LF image, AC from the coefficient planes with the integer
 // chroma-from-luma of the transcoder undone (dec_group.cc, jpeg branch).  qt: the JPEG quantisation tables, natural order.

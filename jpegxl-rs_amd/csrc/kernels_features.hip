@@ -386,6 +386,22 @@ __global__ void WriteKernel(WriteArgs a) {
   StorePixel(a.od, w, h, x, y, r, g, b, al);
 }
 
+// ---- extra-channel planes beside the colour output (OutputSpec::planes): a float plane of the finished image -> one plane of the caller's layout ---------------
+// A streaming pass like EcIntToFloatKernel: lanes along x, rows on blockIdx.y (a block walks rows blockIdx.y, blockIdx.y + gridDim.y, ...: the grid's y extent is
+// limited, an image's height is not), the requested plane on blockIdx.z — its table entry is the same for every lane of the block (scalar loads) and the same channel
+// may stand in several entries.  Every lane stays inside w x h of its source; OutPixelPtr maps that rectangle onto the oriented one the host sized the destination
+// for.  No LDS.  The conversion is pixel_ops.h's, as for every other sample the decoder stores.
+__global__ __launch_bounds__(256) void EcPlanesOutKernel(EcPlanesOutArgs a) {
+  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= a.w) return;
+  const EcPlaneOutDev& e = a.table[blockIdx.z];
+  const uint32_t bps = e.od.out_type == 0 ? 1 : e.od.out_type == 2 ? 4 : 2;
+  for (uint32_t y = blockIdx.y; y < a.h; y += gridDim.y) {
+    const float v = e.src[(size_t)y * e.src_stride + x];
+    StoreSample(e.od, OutPixelPtr(e.od, (int)a.w, (int)a.h, (int)x, (int)y, bps), SlotValue(e.od, 0, v));
+  }
+}
+
 __global__ void CopyPlaneKernel(const float* __restrict__ src, uint32_t src_stride, float* __restrict__ dst, uint32_t dst_stride, uint32_t w, uint32_t h) {
   const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
   if (x >= w || y >= h) return;
@@ -573,6 +589,10 @@ void LaunchNoise(const NoiseArgs& a, void* stream) {
 }
 void LaunchColor(const ColorArgs& a, void* stream) { hipLaunchKernelGGL(ColorKernel, Grid2(a.w, a.h), kBlock2, 0, (hipStream_t)stream, a); }
 void LaunchWrite(const WriteArgs& a, void* stream) { hipLaunchKernelGGL(WriteKernel, Grid2(a.img_w, a.img_h), kBlock2, 0, (hipStream_t)stream, a); }
+void LaunchEcPlanesOut(const EcPlanesOutArgs& a, void* stream) {
+  if (!a.num_planes || !a.w || !a.h || a.num_planes > 65535) return;      // (the host caps the requests at 4096: OutputSpec::planes)
+  hipLaunchKernelGGL(EcPlanesOutKernel, dim3((a.w + 255) / 256, std::min<uint32_t>(a.h, 65535u), a.num_planes), dim3(256), 0, (hipStream_t)stream, a);
+}
 void LaunchEcIntToFloat(const EcFrameArgs& a, void* stream) {
   if (!a.num_extra) return;
   dim3 g = Grid2(a.w, a.h); g.z = a.num_extra;

@@ -78,7 +78,7 @@ typedef JxlParallelRetCode (*JxlParallelRunner)(void* runner_opaque, void* jpegx
 /* ---- live decoder entry points (the 22 symbols jpegxl-rs/src/decode.rs calls) ----------------- */
 uint32_t JxlDecoderVersion(void);                                                             /* decode.rs:370 -> 11002 */
 JxlSignature JxlSignatureCheck(const uint8_t* buf, size_t len);                               /* decode.rs:385 */
-JxlDecoder* JxlDecoderCreate(const JxlMemoryManager* memory_manager);                         /* decode.rs:400 */
+JxlDecoder* JxlDecoderCreate(const JxlMemoryManager* memory_manager);                         /* decode.rs:400; on device JXL_HIP_DEVICE (default 0).  -1: a host-only decoder — headers, events up to JXL_DEC_FRAME, getters and settings need no GPU; the preview, a frame and JxlDecoderFlushImage fail, "a host-only decoder ..." */
 void JxlDecoderReset(JxlDecoder* dec);                                                        /* decode.rs:408 */
 void JxlDecoderDestroy(JxlDecoder* dec);                                                      /* decode.rs:414 */
 JxlDecoderStatus JxlDecoderSetParallelRunner(JxlDecoder* dec, JxlParallelRunner runner, void* opaque);   /* decode.rs:487 */
@@ -346,6 +346,46 @@ JxlDecoderStatus JxlHipBatchOutputPlanesLayout(const JxlHipBatch* batch, int ind
 /* JxlHipImageOutSizeResized with a filter-and-mirror resample (NULL: the image's own size) and the planes: *out_size is the whole destination */
 JxlDecoderStatus JxlHipImageOutSizePlanes(const uint8_t* data, size_t size, const JxlPixelFormat* format, int downscale, const JxlHipOutputLayout* layout,
                                           const JxlHipOutputResample* resample, const JxlHipOutputPlanes* planes, JxlBasicInfo* info, size_t* out_size);
+/* ---- output colour: decode to a requested colour encoding ----------------------------------------------------------------------------------------------------------
+ * Every image is decoded into the encoding its own header names; JxlHipOutputColor asks for another one, so that a job of sRGB, Display-P3, PQ and HLG files lands in one
+ * space.  The rule:
+ *   linear light  display light with 1.0 = the image's intensity_target (what the XYB -> linear stage produces).  The intensity target is always the image's own; a
+ *                 target encoding never changes it.  No gamut mapping and no tone mapping: what leaves the target's range clips at the write stage (float output keeps it).
+ *   target        a JxlColorEncoding with color_space 0 (RGB) or 1 (grey), any white point / primaries (enumerated or custom xy: the xy fields count under the custom
+ *                 enums only) and transfer function 1, 8, 13, 16, 17, 18 or 65535 (gamma in (0, 1], kept in units of 1e-7 as the codestream keeps it).  Refused with a
+ *                 message: color_space 2 / 3, transfer function 2, a chromaticity with y <= 0, singular primaries, a grey target for a colour image or the reverse.
+ *   XYB images    come out exactly — bit for bit — as the same codestream under a header that names the target at the same intensity target: the inverse opsin matrix is
+ *                 multiplied by inv(AdaptToXyzD50(w_t) x PrimariesToXyz(p_t, w_t)) x AdaptToXyzD50(D65) x PrimariesToXyz(sRGB, D65) in double and rounded to float32 once,
+ *                 the target's luminances feed the HLG inverse OOTF, and the transfer function — hence the kernel: sRGB and linear targets take the fused filter kernel, the
+ *                 others the stage-by-stage one — follows from the target.  An embedded ICC profile does not matter: XYB pixels are absolute.
+ *   other images  (lossless Modular RGB, YCbCr transcodes) keep their samples under non_xyb = 0, libjxl's rule.  Under non_xyb = 1 an image with enumerated encoding A is
+ *                 converted to the target T per pixel, behind blending and spot colours, in float32: A's transfer function undone to linear light; the matrix
+ *                 inv(AdaptToXyzD50(w_T) x PrimariesToXyz(p_T, w_T)) x AdaptToXyzD50(w_A) x PrimariesToXyz(p_A, w_A) (double, rounded once; left out between equal
+ *                 chromaticities); T's transfer function as for XYB images.  Inverse transfer functions: sRGB (IEC 61966-2-1), Rec.709, gamma; PQ: the ST 2084 EOTF x
+ *                 10000 / intensity_target; HLG: the BT.2100 inverse OETF, then the OOTF display = scene x Y_s^(gamma - 1) with gamma = 1.2 x 1.111^log2(intensity_target /
+ *                 1000) and Y_s from A's primaries, skipped in the band the forward path skips its inverse in (|1 / gamma - 1| <= 0.01).  Negative samples: odd extension;
+ *                 gamma gives 0 at or below 1e-5.  A grey image converts its transfer function only.  T equal to A (the same xy and transfer function; linear = gamma 1,
+ *                 DCI = gamma 1 / 2.6): nothing happens, the image takes the path and gives the bytes of the plain decode.  Such an image takes the frame tail (ColorKernel).
+ *                 An image whose colour is only an ICC profile fails, "unsupported: output colour of an image whose colour is an ICC profile needs a CMS".  So does one whose own encoding cannot
+ *                 be taken to linear light (an unknown transfer function or colour space): "unsupported: output colour of an image whose own encoding cannot be converted ...".
+ * JxlHipBatchSetOutputColor is called after the JxlHipBatchSetOutput... call of that image, like JxlHipBatchSetOutputPlanes; a later JxlHipBatchSetOutput... call or a
+ * NULL clears it; a refused call leaves the output that was set.  downscale 8, every layout, resize and extra planes compose with it (planes are never colour-converted).
+ * Refused, "unsupported: output colour ...": libjpeg-exact outputs (jpeg_scale, the integer resample: those are libjpeg's samples; jobs of libjpeg-exact pixels have no
+ * argument that carries a colour); non_xyb = 1 on kept animation canvases ("output_all_frames") of an image that is not XYB.
+ * JxlHipColorConversionMatrix (host only): the row-major linear-light matrix of the rule from `from` to `to`, in double; the identity, exactly, between equal
+ * chromaticities.  Returns 0, or 1 with a message for an encoding the rule refuses. */
+/* The libjxl-style decoder takes the same request through JxlHipDecoderSetOutputColorProfile, which has the argument list and the contract of libjxl's call of that name for a
+ * decoder without a CMS (jpegxl-sys decode.rs:891-973): XYB images come out in the encoding, images that are not XYB keep their samples and the call still succeeds, a
+ * non-NULL icc_data is JXL_DEC_ERROR (it needs a CMS).  Call it between JXL_DEC_COLOR_ENCODING and the first frame: JXL_DEC_ERROR with a message before the headers are known,
+ * after the frame decode (or a progressive flush) has begun — so an animation decoded once keeps one target —, without an encoding, and for everything the rule above
+ * refuses.  Afterwards JxlDecoderGetColorAsEncodedProfile and the two ICC profile calls with target DATA describe the requested encoding for XYB images, also for those with
+ * an embedded ICC profile, and ORIGINAL stays the image's own; JxlDecoderFlushImage shows the target's pixels.  JxlDecoderReset clears the request, JxlDecoderRewind keeps it.
+ * libjxl's own pair of names for this stays among the error-returning stubs (csrc/jxl_stubs.cc) beside the CMS hook: the ABI test pins that list, and a caller that links
+ * against libjxl's names gets the answer it got before.  Forwarding them here is one line each. */
+typedef struct { JxlColorEncoding encoding; uint32_t non_xyb; } JxlHipOutputColor;
+JxlDecoderStatus JxlHipDecoderSetOutputColorProfile(JxlDecoder* dec, const JxlColorEncoding* color_encoding, const uint8_t* icc_data, size_t icc_size);
+JxlDecoderStatus JxlHipBatchSetOutputColor(JxlHipBatch* batch, int index, const JxlHipOutputColor* color);
+int JxlHipColorConversionMatrix(const JxlColorEncoding* from, const JxlColorEncoding* to, double m[9]);
 /* JPEG bit-stream reconstruction of a whole batch (jpegxl-rs decode.rs:493 `reconstruct`, for many files at once).  JxlHipBatchCanReconstructJpeg: 1 if image
  * `index` is a lossless JPEG transcode with usable reconstruction data (a `jbrd` box whose markers find their ICC / Exif / XMP payloads, a Huffman-coded source),
  * else 0 with the reason in JxlHipLastError().  JxlHipBatchReconstructJpegs runs the LF and HF entropy stages once for all images of the batch (it prepares the batch
@@ -573,6 +613,11 @@ int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* pipeline, const uint8_t* c
 int64_t JxlHipPipelineSubmitPlanes(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
                                    void* const* host_out, const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each,
                                    const JxlHipOutputPlanes* planes);
+/* The same with an output colour for the job (JxlHipOutputColor above; NULL = JxlHipPipelineSubmitPlanes): an image the target is refused for — a grey target on a colour
+ * image, non_xyb = 1 on an image whose colour is only an ICC profile — fails alone with the reason. */
+int64_t JxlHipPipelineSubmitColor(JxlHipPipeline* pipeline, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out,
+                                  void* const* host_out, const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each,
+                                  const JxlHipOutputPlanes* planes, const JxlHipOutputColor* color);
 /* A job of libjpeg-exact pixels: every image is decoded to the samples libjpeg gives for the JPEG file it was transcoded from (JxlHipBatchDecodeJpegPixels above, as
  * stages of the pipeline: the job shares coefficient sets and pixel planes with plain jobs, which may be mixed with it freely).  Eligible is what
  * JxlHipBatchCanDecodeJpegPixels takes; an image that is not eligible fails alone with that call's reason ("unsupported: libjpeg-exact decode of ..."), and so does an

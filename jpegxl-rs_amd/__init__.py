@@ -116,6 +116,11 @@ class JxlHipOutputPlanes(C.Structure):
                 ("scale", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float))]
 
 
+class JxlHipOutputColor(C.Structure):
+    """include/jxl_hip.h JxlHipOutputColor: the colour encoding the output is asked for in, and what becomes of images that are not XYB (0 leave, 1 convert)"""
+    _fields_ = [("encoding", JxlColorEncoding), ("non_xyb", C.c_uint32)]
+
+
 assert C.sizeof(JxlBasicInfo) == 204 and C.sizeof(JxlPixelFormat) == 24 and C.sizeof(JxlMemoryManager) == 24
 
 _lib = None
@@ -200,6 +205,11 @@ def libjxl():
                                                        C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(JxlHipOutputPlanes)]),
             "JxlHipImageOutSizePlanes": (C.c_int, [vp, sz, C.POINTER(JxlPixelFormat), C.c_int, C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(JxlHipOutputPlanes),
                                                    C.POINTER(JxlBasicInfo), C.POINTER(sz)]),
+            "JxlHipDecoderSetOutputColorProfile": (C.c_int, [vp, C.POINTER(JxlColorEncoding), vp, sz]),
+            "JxlHipBatchSetOutputColor": (C.c_int, [vp, C.c_int, C.POINTER(JxlHipOutputColor)]),
+            "JxlHipColorConversionMatrix": (C.c_int, [C.POINTER(JxlColorEncoding), C.POINTER(JxlColorEncoding), C.POINTER(C.c_double * 9)]),
+            "JxlHipPipelineSubmitColor": (C.c_int64, [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.c_int, C.POINTER(JxlPixelFormat), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.c_int,
+                                                      C.POINTER(JxlHipOutputLayout), C.POINTER(JxlHipOutputResample), C.POINTER(JxlHipOutputPlanes), C.POINTER(JxlHipOutputColor)]),
             "JxlHipDecoderInfo": (C.c_int64, [vp, C.c_char_p]),
             "JxlHipBatchCanReconstructJpeg": (C.c_int, [vp, C.c_int]), "JxlHipBatchReconstructJpegs": (C.c_int, [vp, vp]),
             "JxlHipBatchJpegStatus": (C.c_int, [vp, C.c_int]), "JxlHipBatchJpegSize": (sz, [vp, C.c_int]), "JxlHipBatchCopyJpeg": (C.c_int, [vp, C.c_int, vp, sz]),
@@ -756,6 +766,62 @@ def _planes(extra_planes, plane_scale, plane_bias, planes_offset, planes_stride=
     return p
 
 
+# output_color= by name: white point, primaries, transfer function (JxlColorEncoding's enums)
+_NAMED_COLORS = {"srgb": (1, 1, 13), "linear_srgb": (1, 1, 8), "display_p3": (1, 11, 13), "rec2020_pq": (1, 9, 16), "rec2020_hlg": (1, 9, 18)}
+
+
+def color_encoding(color) -> JxlColorEncoding:
+    """-> JxlColorEncoding of `color`: one of "srgb", "linear_srgb", "display_p3", "rec2020_pq", "rec2020_hlg", a JxlColorEncoding, or a dict with the enums
+    white_point (1 D65 / 2 custom / 10 E / 11 DCI), primaries (1 sRGB / 2 custom / 9 BT.2100 / 11 P3), tf (1 Rec.709 / 8 linear / 13 sRGB / 16 PQ / 17 DCI / 18 HLG),
+    gamma (!= 0 replaces tf), color_space (0 RGB, 1 grey), rendering_intent, and for the custom enums white_xy / red_xy / green_xy / blue_xy.  white_xy or the three
+    primaries given without their enum select the custom one."""
+    if isinstance(color, JxlColorEncoding):
+        return color
+    if isinstance(color, str):
+        if color not in _NAMED_COLORS:
+            raise ValueError("output_color: %r is none of %s" % (color, ", ".join(sorted(_NAMED_COLORS))))
+        color = dict(zip(("white_point", "primaries", "tf"), _NAMED_COLORS[color]))
+    d = dict(color)
+    e = JxlColorEncoding()
+    e.color_space = int(d.pop("color_space", 0))
+    white_xy, prim = d.pop("white_xy", None), [d.pop(k, None) for k in ("red_xy", "green_xy", "blue_xy")]
+    if any(v is not None for v in prim) and not all(v is not None for v in prim):
+        raise ValueError("output_color: red_xy, green_xy and blue_xy come together")
+    e.white_point = int(d.pop("white_point", 2 if white_xy is not None else 1))
+    e.primaries = int(d.pop("primaries", 2 if prim[0] is not None else 1))
+    if white_xy is not None:
+        e.white_point_xy[0], e.white_point_xy[1] = float(white_xy[0]), float(white_xy[1])
+    for name, v in zip(("primaries_red_xy", "primaries_green_xy", "primaries_blue_xy"), prim):
+        if v is not None:
+            getattr(e, name)[0], getattr(e, name)[1] = float(v[0]), float(v[1])
+    gamma = float(d.pop("gamma", 0.0))
+    e.transfer_function, e.gamma = (65535, gamma) if gamma != 0.0 else (int(d.pop("tf", 13)), 0.0)
+    d.pop("tf", None)
+    e.rendering_intent = int(d.pop("rendering_intent", 1))
+    if d:
+        raise ValueError("output_color: unknown keys %s" % sorted(d))
+    return e
+
+
+def _color(output_color, convert_non_xyb):
+    """-> JxlHipOutputColor, or None without output_color"""
+    if output_color is None:
+        if convert_non_xyb:
+            raise ValueError("convert_non_xyb needs output_color=")
+        return None
+    return JxlHipOutputColor(color_encoding(output_color), 1 if convert_non_xyb else 0)
+
+
+def color_conversion_matrix(from_color, to_color) -> np.ndarray:
+    """The 3x3 float64 matrix that takes linear light of `from_color` to linear light of `to_color` (each as for color_encoding): through XYZ D50 with linear Bradford
+    adaptation, the rule of output_color= (include/jxl_hip.h JxlHipColorConversionMatrix).  Host only."""
+    a, b = color_encoding(from_color), color_encoding(to_color)
+    m = (C.c_double * 9)()
+    if libjxl().JxlHipColorConversionMatrix(C.byref(a), C.byref(b), C.byref(m)) != 0:
+        raise GenericError(last_error())
+    return np.array(list(m), dtype=np.float64).reshape(3, 3)
+
+
 def _per_image(value, n, is_one):
     """one value for the job, or a sequence of n per-image values -> (list of n, whether it was a sequence)"""
     if value is None or isinstance(value, (str, bytes)) or not hasattr(value, "__iter__"):
@@ -798,7 +864,7 @@ class BatchDecoder:
         if status != JXL_DEC_SUCCESS:
             raise GenericError(last_error())
 
-    def _set_output(self, i, fmt, device_ptr, downscale, layout=None, resize=None, jpeg_scale=1, resize_u8=False, planes=None):
+    def _set_output(self, i, fmt, device_ptr, downscale, layout=None, resize=None, jpeg_scale=1, resize_u8=False, planes=None, color=None):
         L = libjxl()
         if resize_u8:
             _resize_u8(downscale, resize)
@@ -819,6 +885,8 @@ class BatchDecoder:
             self._chk(L.JxlHipBatchSetOutputScaled(self._h, i, C.byref(fmt), device_ptr, int(downscale)))
         if planes is not None:
             self._chk(L.JxlHipBatchSetOutputPlanes(self._h, i, C.byref(planes)))
+        if color is not None:
+            self._chk(L.JxlHipBatchSetOutputColor(self._h, i, C.byref(color)))
         self._planes.append(planes)
         self._fmt.append(fmt)
         self._scale.append(int(downscale))
@@ -828,7 +896,7 @@ class BatchDecoder:
 
     def add(self, data: bytes, dtype="uint8", num_channels=0, endianness=Endianness.Native, align=0, device_ptr=None, downscale=1,
             planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_scale=1, resize_u8=False,
-            extra_planes=None, plane_scale=None, plane_bias=None, planes_offset=0, planes_stride=0) -> int:
+            extra_planes=None, plane_scale=None, plane_bias=None, planes_offset=0, planes_stride=0, output_color=None, convert_non_xyb=False) -> int:
         """downscale=8: the 1:8 decode (include/jxl_hip.h JxlHipBatchSetOutputScaled) — output(i) is the ceil(w / 8) x ceil(h / 8) picture; `data` may end behind
         the LF part of its frame.
         planar=True: one plane per channel, [C, H, W] with rows `align`ed and planes plane_stride bytes apart (0 = tight); scale / bias (up to four values, one per
@@ -850,7 +918,11 @@ class BatchDecoder:
         follow its geometry (orientation, resize, crop, filter, mirror); with planar=True colour and planes form one [C + m, H, W] block.  plane_scale / plane_bias: one
         value per plane (float output); planes_offset / planes_stride: where the first plane starts and the bytes from plane to plane, 0 = the defaults —
         planes_layout(i) tells, and out_size(i) / output(i) cover the whole destination.  An index the image does not have, downscale=8 and libjpeg-exact outputs
-        are refused: "unsupported: extra planes ..."."""
+        are refused: "unsupported: extra planes ...".
+        output_color="srgb" | "linear_srgb" | "display_p3" | "rec2020_pq" | "rec2020_hlg" | a dict (color_encoding()): the colour encoding the pixels come out in, whatever
+        the image's header names (include/jxl_hip.h JxlHipOutputColor) — an XYB image exactly as if its header named that encoding, at its own intensity target; an image
+        that is not XYB keeps its samples unless convert_non_xyb=True, which converts it (transfer function, primaries, transfer function) in the frame tail.  Composes with
+        downscale=8, layouts, resize and extra_planes; libjpeg-exact outputs refuse it: "unsupported: output colour ..."."""
         layout = _layout(planar, plane_stride, scale, bias)
         rs = _resize(resize, crop) if filter is None and not mirror else _resample(resize, crop, filter, mirror)
         L = libjxl()
@@ -866,7 +938,8 @@ class BatchDecoder:
         if i < 0:
             raise GenericError(last_error())
         fmt = JxlPixelFormat(num_channels, _PIXEL_TYPES[np.dtype(dtype).name][0], endianness, align)
-        self._set_output(i, fmt, device_ptr, downscale, layout, rs, jpeg_scale, resize_u8, _planes(extra_planes, plane_scale, plane_bias, planes_offset, planes_stride))
+        self._set_output(i, fmt, device_ptr, downscale, layout, rs, jpeg_scale, resize_u8, _planes(extra_planes, plane_scale, plane_bias, planes_offset, planes_stride),
+                         _color(output_color, convert_non_xyb))
         self._n += 1
         return i
 
@@ -1170,7 +1243,7 @@ class Pipeline:
 
     def submit(self, datas, dtype="uint8", num_channels=0, device_ptrs=None, host_ptrs=None, capacities=None, endianness=Endianness.Native, align=0, downscale=1,
                planar=False, plane_stride=0, scale=None, bias=None, resize=None, crop=None, filter=None, mirror=False, jpeg_pixels=False, jpeg_scale=1, resize_u8=False,
-               extra_planes=None, plane_scale=None, plane_bias=None, planes_offset=0, planes_stride=0) -> int:
+               extra_planes=None, plane_scale=None, plane_bias=None, planes_offset=0, planes_stride=0, output_color=None, convert_non_xyb=False) -> int:
         """Job of len(datas) images (bytes objects).  device_ptrs / host_ptrs: one destination address per image (exactly one of the two lists); the bytes objects and
         the destinations are kept referenced until wait().  downscale=8: the job is decoded at 1:8 (JxlHipPipelineSubmitScaled).  planar, plane_stride, scale, bias:
         the layout of every image of the job, as for BatchDecoder.add (JxlHipPipelineSubmitLayout).  resize, crop: every image of the job comes out resize[0] x resize[1]
@@ -1187,7 +1260,12 @@ class Pipeline:
         (JxlHipPipelineSubmitJpegPixelsResampled); an image the libjpeg-exact decode does not take fails alone.
         extra_planes, plane_scale, plane_bias, planes_offset, planes_stride: extra-channel planes behind every image's colour output, as for BatchDecoder.add
         (JxlHipPipelineSubmitPlanes) — destinations and capacities are sized with image_out_size(..., extra_planes=); an image that lacks one of the channels
-        fails alone; not with jpeg_pixels."""
+        fails alone; not with jpeg_pixels.
+        output_color, convert_non_xyb: the colour encoding of every image of the job, as for BatchDecoder.add (JxlHipPipelineSubmitColor); an image the target is refused
+        for — a grey target on a colour image, convert_non_xyb on an image whose colour is only an ICC profile — fails alone; not with jpeg_pixels."""
+        color = _color(output_color, convert_non_xyb)
+        if color is not None and jpeg_pixels:
+            raise GenericError("unsupported: output colour of a libjpeg-exact output (a jpeg_pixels job): those are libjpeg's samples")
         planes = _planes(extra_planes, plane_scale, plane_bias, planes_offset, planes_stride)
         if planes is not None and jpeg_pixels:
             raise GenericError("unsupported: extra planes beside a libjpeg-exact output (a jpeg_pixels job)")
@@ -1225,6 +1303,10 @@ class Pipeline:
                 t = libjxl().JxlHipPipelineSubmitJpegPixelsScaled(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, _byref(layout), each, int(jpeg_scale))
             else:
                 t = libjxl().JxlHipPipelineSubmitJpegPixels(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, _byref(layout), each)
+        elif color is not None:
+            if each is None and resize is not None:
+                each = (JxlHipOutputResample * max(1, n))(*[_resample(resize, crop, None, False) for _ in range(n)])
+            t = libjxl().JxlHipPipelineSubmitColor(self._h, ptrs, sizes, n, C.byref(fmt), dev, host, caps, int(downscale), _byref(layout), each, _byref(planes), C.byref(color))
         elif planes is not None:
             if each is None and resize is not None:
                 each = (JxlHipOutputResample * max(1, n))(*[_resample(resize, crop, None, False) for _ in range(n)])

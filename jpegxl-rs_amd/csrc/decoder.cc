@@ -313,6 +313,71 @@ void FillColor(const ImageHeader& ih, bool do_ycbcr, FrameDev& f) {
   } else f.color_mode = do_ycbcr ? 2 : 3;
 }
 
+// ---- output colour (OutputSpec::color; include/jxl_hip.h has the rule)
+// The header the colour stage and the kernel choice go by: an XYB image under a requested encoding is the same codestream under a header that names that encoding, at
+// its own intensity target — everything FillColor and SimpleTransfer read is taken from there, so the pixels are those of that file bit for bit.  Every other image:
+// its own header (`store` is only written when the two differ).
+const ImageHeader& Batch::ColourHeader(const ImageHeader& ih, const OutputSpec& o, ImageHeader* store) {
+  if (!o.color_set || !ih.xyb_encoded) return ih;
+  ImageHeader& h = *store;
+  h = ImageHeader();
+  h.xyb_encoded = true; h.intensity_target = ih.intensity_target;
+  for (int k = 0; k < 9; k++) h.opsin_inv[k] = ih.opsin_inv[k];
+  for (int k = 0; k < 3; k++) h.opsin_bias[k] = ih.opsin_bias[k];
+  ApplyColorTarget(o.color, &h);
+  return h;
+}
+bool Batch::ConvertsNonXyb(const ImageHeader& ih, const OutputSpec& o) {
+  return o.color_set && o.color_non_xyb && !ih.xyb_encoded && !ih.want_icc && !SameColorEncoding(ColorTargetOf(ih), o.color);
+}
+std::string Batch::ColourRefusal(const ImageHeader& ih, const OutputSpec& o) {
+  if (!o.color_set) return std::string();
+  if (o.color_non_xyb > 1) return "unsupported: output colour with non_xyb = " + std::to_string(o.color_non_xyb) + " (0 leave, 1 convert)";
+  const std::string why = ColorTargetRefusal(o.color);
+  if (!why.empty()) return why;
+  if (o.jpeg_scale != 1 || o.resize_u8) return "unsupported: output colour of a libjpeg-exact output (jpeg_scale, the integer resample): those are libjpeg's samples";
+  const bool grey = ih.color_space == 1 && !ih.color_default;
+  if (o.color.color_space == 1 && !grey) return "unsupported: output colour: a grey encoding for a colour image";
+  if (o.color.color_space == 0 && grey) return "unsupported: output colour: an RGB encoding for a grey image";
+  if (o.color_non_xyb && !ih.xyb_encoded && ih.want_icc) return "unsupported: output colour of an image whose colour is an ICC profile needs a CMS";
+  if (o.color_non_xyb && !ih.xyb_encoded) {
+    // (the source side of the conversion: an encoding the decoder cannot take to linear light — an unknown transfer function or colour space, a bad chromaticity — is no
+    // more convertible than an ICC profile; AddImage only checks the transfer function of XYB images, which are rendered through it)
+    const std::string src = ColorTargetRefusal(ColorTargetOf(ih)), head = "unsupported: output colour ";
+    if (!src.empty()) return "unsupported: output colour of an image whose own encoding cannot be converted: an encoding " + src.substr(head.size());
+  }
+  return std::string();
+}
+// The conversion of an image that is not XYB (ConvertsNonXyb), for ColorKernel: the source's inverse transfer function, the matrix between the two sets of primaries,
+// and — in the fields TransferFromLinear reads — the target's transfer function.  Both parameter sets are the ones FillColor gives an XYB image of that encoding.
+void FillColourConversion(const ImageHeader& ih, const OutputSpec& o, ColorArgs* ca) {
+  const ColorTarget own = ColorTargetOf(ih);
+  ImageHeader h;
+  h.xyb_encoded = true; h.intensity_target = ih.intensity_target;
+  for (int k = 0; k < 9; k++) h.opsin_inv[k] = ih.opsin_inv[k];
+  for (int k = 0; k < 3; k++) h.opsin_bias[k] = ih.opsin_bias[k];
+  FrameDev src, dst;
+  memset(&src, 0, sizeof(src)); memset(&dst, 0, sizeof(dst));
+  ApplyColorTarget(own, &h); FillColor(h, false, src);
+  ApplyColorTarget(o.color, &h); FillColor(h, false, dst);
+  double m[9];
+  ColorConversionMatrix(own, o.color, m);
+  ca->convert = 1;
+  ca->src_tf = src.color_mode;
+  for (int k = 0; k < 5; k++) ca->src_par[k] = 0.0f;
+  if (src.color_mode == 4) ca->src_par[0] = 1.0f / src.inverse_gamma;                      // gamma: the reciprocal exponent
+  else if (src.color_mode == 6) ca->src_par[0] = 10000.0f / ih.intensity_target;           // PQ: 1.0 = the intensity target
+  else if (src.color_mode == 7) {                                                          // HLG: the OOTF's exponent gamma - 1 (FillColor's is 1 / gamma - 1), inside the same band
+    ca->src_par[0] = 1.0f / (src.hdr_par[0] + 1.0f) - 1.0f; ca->src_par[1] = src.hdr_par[1];
+    for (int k = 0; k < 3; k++) ca->src_par[2 + k] = src.hdr_par[2 + k];      // (luminances of the source's primaries)
+  }
+  for (int k = 0; k < 9; k++) ca->conv[k] = (float)m[k];
+  ca->conv_identity = 1;
+  for (int k = 0; k < 9; k++) if (m[k] != (k % 4 == 0 ? 1.0 : 0.0)) ca->conv_identity = 0;
+  ca->tf_kind = dst.color_mode; ca->inverse_gamma = dst.inverse_gamma;
+  for (int k = 0; k < 5; k++) ca->hdr_par[k] = dst.hdr_par[k];
+}
+
 // ---- device arena pool.  hipMalloc / hipFree of the multi-gigabyte arenas cost 0.5-3.5 s per batch object on the boxes measured (page tables of tens of GB set up and
 // torn down), which is what a "fresh batch" paid each time (bench.py one_pass_128: 92 ms here, 3.6 s on the driver's box in round 3).  Arenas that a batch lets go of are kept
 // in a process-wide free list (bounded: JXL_HIP_ARENA_POOL_MB, default 60 % of the device's memory; 0 turns the pool off) and handed to the next batch that asks for that much memory on that device.
@@ -910,6 +975,10 @@ void Batch::OutputDims(int i, const OutputSpec& o, uint32_t* w, uint32_t* h) con
 size_t Batch::OutputSizeOf(int i, const OutputSpec& o) const {
   ImageHeader dims = images_[pub_[i].first_unit]->ih;       // (OutputStride / OutputSize only look at the size, the orientation and the channel list)
   OutputDims(i, o, &dims.xsize, &dims.ysize);
+  if (o.color_set) {      // (what SetOutput would refuse for this image: a pipeline job asks here first and lets the image fail alone)
+    const std::string why = ColourRefusal(dims, o);
+    if (!why.empty()) throw ParseError(why, true);
+  }
   return OutputSize(dims, o);
 }
 static float IntMul(const OutputSpec& o) { const uint32_t full = o.type == 0 ? 8 : 16; const uint32_t b = o.int_bits && o.int_bits < full ? o.int_bits : full; return (float)((1u << b) - 1); }
@@ -1034,6 +1103,10 @@ void Batch::SetOutput(int i, const OutputSpec& o) {
     if (!CanDecodeJpegPixelsAs(i, o, &why)) throw ParseError("unsupported: integer resample of an image the libjpeg-exact decode does not take (" + why + ")", true);
   }
   if (o.only_frame >= pub_[i].num_units) throw ParseError("non-coalesced output: no such frame", false);
+  if (o.color_set) {
+    const std::string why = ColourRefusal(e.ih, o);
+    if (!why.empty()) throw ParseError(why, true);
+  }
   // Everything that can refuse the output — a layout, a resize or a crop the image does not fit, an offset or pitch of the planes below its default — is computed
   // before anything of the entry is assigned: a call that throws leaves the entry, spec and sizes alike, as it was.
   OutputSpec out = o;
@@ -1073,6 +1146,7 @@ void Batch::SetOutputAllFrames(int i, const OutputSpec& o, const vec<int>& frame
   if (o.planar || o.affine) throw ParseError("SetOutputAllFrames: interleaved output without scale / bias only", false);
   if (o.resized() || o.cropped()) throw ParseError("SetOutputAllFrames: no resized output", false);
   if (o.planes.any()) throw ParseError("unsupported: extra planes of kept animation canvases (all frames in one decode)", true);
+  if (ConvertsNonXyb(images_[pub_[i].first_unit]->ih, o)) throw ParseError("unsupported: output colour conversion of kept animation canvases of an image that is not XYB (all frames in one decode)", true);
   for (size_t k = 0; k < frames.size(); k++)
     if (frames[k] < 0 || frames[k] >= pub_[i].num_units || (k && frames[k] <= frames[k - 1])) throw ParseError("SetOutputAllFrames: frame list must be ascending positions among the image's frames", false);
   OutputSpec oo = o;
@@ -1143,7 +1217,8 @@ void Batch::StageBytes(uint64_t out[6]) const {
     }
     out[2] += hf_sec + (u < hf_written_.size() ? (uint64_t)hf_written_[u] * 4 : 0);
     out[3] += idct_px * (12 + 12);
-    const bool fused = p.lf.gab && p.lf.epf_iters == 1 && e.ih.xyb_encoded && SimpleTransfer(e.ih) && p.upsampling == 1 && !e.complex && !cfg.force_unfused_filters;
+    ImageHeader colour_store;
+    const bool fused = p.lf.gab && p.lf.epf_iters == 1 && e.ih.xyb_encoded && SimpleTransfer(ColourHeader(e.ih, first.out, &colour_store)) && p.upsampling == 1 && !e.complex && !cfg.force_unfused_filters;
     const bool any_filter = p.lf.gab || p.lf.epf_iters > 0;
     const bool epf_writes = !fused && p.lf.epf_iters >= 1 && p.upsampling == 1 && !e.complex && cfg.debug_stop_after == 0;    // kernels.hip EpfWritesOutput
     if (fused || epf_writes) out[4] += npx * (12 + out_px);
@@ -1479,7 +1554,7 @@ void Batch::PromoteToComplex() {
     bool spot = false;
     for (auto& x : first.ih.extra) if (x.type == 2) spot = true;
     if (spot && first.out.render_spotcolors && first.ih.color_space == 1) throw ParseError("unsupported: spot colours on a grey image", true);
-    if (OutputNeedsTail(first.ih, first.out) || first.out.planes.any()) MarkComplex(pi);
+    if (OutputNeedsTail(first.ih, first.out) || first.out.planes.any() || ConvertsNonXyb(first.ih, first.out)) MarkComplex(pi);
   }
 }
 bool Batch::ComplexWithoutPlanes(int i, const OutputSpec& o) const {
@@ -1573,7 +1648,8 @@ void Batch::PutStreamTables(PrepareState& st) {
     if (!p.modular && DecodedAtEighth(i)) any_scaled_ = true;
     if (!p.modular && !EndsBehindLf(i)) any_full_vardct_ = true;
     if (!p.modular && !EndsBehindLf(i)) {
-      const bool fusable = p.lf.gab && p.lf.epf_iters == 1 && e.ih.xyb_encoded && SimpleTransfer(e.ih) && p.upsampling == 1 && !e.complex;
+      ImageHeader colour_store;      // (the transfer function of the encoding the image is rendered to: its header's, or the output's target)
+      const bool fusable = p.lf.gab && p.lf.epf_iters == 1 && e.ih.xyb_encoded && SimpleTransfer(ColourHeader(e.ih, images_[pub_[e.pub_index].first_unit]->out, &colour_store)) && p.upsampling == 1 && !e.complex;
       if (p.upsampling > 1 && !e.complex) { fplan_.any_upsampled = true; fplan_.max_out_w = std::max<int>(fplan_.max_out_w, e.ih.xsize); fplan_.max_out_h = std::max<int>(fplan_.max_out_h, e.ih.ysize); }
       fplan_.any_fused |= fusable; fplan_.any_unfused |= !fusable;
       fplan_.any_gab |= p.lf.gab != 0; fplan_.max_epf = std::max<int>(fplan_.max_epf, p.lf.epf_iters);
@@ -1908,7 +1984,8 @@ void Batch::FillFrameVarDct(int i, const uint8_t* cbase, const PrepareState& st)
   f.epf_quant_mul = p.lf.quant_mul; f.epf_quant_scale = (float)p.global_scale / 65536.0f;
   const float scales[3] = {p.lf.pass0_sigma_scale, 1.0f, p.lf.pass2_sigma_scale};
   for (int k = 0; k < 3; k++) { f.epf_sm[k] = scales[k] * 1.65f; f.epf_bsm[k] = f.epf_sm[k] * p.lf.border_sad_mul; }
-  FillColor(e.ih, p.do_ycbcr, f);
+  ImageHeader colour_store;
+  FillColor(ColourHeader(e.ih, images_[pub_[e.pub_index].first_unit]->out, &colour_store), p.do_ycbcr, f);
   for (int k = 0; k < 3; k++) {
     f.lfq[k] = (int32_t*)(dwork_ + o.lfq[k]); f.lf[k] = (float*)(dwork_ + o.lf[k]); f.lf_tmp[k] = (float*)(dwork_ + o.lf_tmp[k]);
     f.llf[k] = (float*)(dwork_ + o.llf[k]); f.coeff[k] = EndsBehindLf(i) ? nullptr : (int32_t*)(dcoef_ + o.coeff[k]);

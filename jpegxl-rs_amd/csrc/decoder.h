@@ -74,6 +74,12 @@ struct OutputSpec {
                                            // to u8 behind each pass), byte for byte im.crop(box).resize(size, filter); the intermediate is u8.  Written by DecodeJpegPixels alone
   // ---- extra-channel planes behind the colour output (Batch and Pipeline outputs; an image with any becomes complex, the frame tail delivers them: EcPlanesOutKernel)
   OutputPlanes planes;
+  // ---- output colour (Batch, Pipeline and JxlHipDecoderSetOutputColorProfile): XYB images are rendered to `color` instead of the encoding their header names — the colour
+  // stage's parameters and the kernel choice go by it (Batch::ColourHeader); an image that is not XYB keeps its samples unless color_non_xyb is set, and is then
+  // converted in the frame tail (ColorKernel; the image becomes complex) when its encoding differs from the target
+  bool color_set = false;
+  ColorTarget color;
+  uint32_t color_non_xyb = 0;              // 0 leave (libjxl's rule), 1 convert
   bool resized() const { return resize_w || resize_h; }
   bool cropped() const { return crop_x0 || crop_y0 || crop_w || crop_h; }
 };
@@ -185,6 +191,12 @@ class Batch {
   static PlanesLayout PlanesLayoutOf(const ImageHeader& ih, const OutputSpec& o);
   // row pitch of requested plane k, bytes
   static size_t PlaneRowStride(const ImageHeader& ih, const OutputSpec& o, const PlaneRequest& r);
+  // Output colour (OutputSpec::color).  ColourRefusal: "" when `o`'s target can be served for an image with header ih, else the reason, "unsupported: output colour ...";
+  // SetOutput throws it.  ColourHeader: the header the colour stage and the kernel choice go by — for an XYB image under a target, ih's colour fields replaced by the
+  // target (built in *store), else ih itself.  ConvertsNonXyb: the image is not XYB and `o` asks for its conversion to another encoding than its own (frame tail).
+  static std::string ColourRefusal(const ImageHeader& ih, const OutputSpec& o);
+  static const ImageHeader& ColourHeader(const ImageHeader& ih, const OutputSpec& o, ImageHeader* store);
+  static bool ConvertsNonXyb(const ImageHeader& ih, const OutputSpec& o);
   // "" when the layout of `o` (planar, plane_stride, affine) can be written for an image of ih's size, else the reason; OutputSize and SetOutput throw it
   static std::string LayoutRefusal(const ImageHeader& ih, const OutputSpec& o);
   // "" when the resize of `o` can be done for an image of ih's size (a target side of 0 or above 65535, a crop that is empty or leaves the picture), else the reason;

@@ -28,6 +28,7 @@ struct Arena {
 };
 
 void FillColor(const ImageHeader& ih, bool do_ycbcr, FrameDev& f);
+void FillColourConversion(const ImageHeader& ih, const OutputSpec& o, ColorArgs* ca);      // ColorKernel's conversion of an image that is not XYB to o.color
 OutputDesc FillOutput(const ImageEntry& e, uint8_t* work, uint8_t* big, bool resize_target = false);
 // ... and requested extra-channel plane k (OutputSpec::planes) in the caller's destination: one planar slot with the plane's own type, byte order, row pitch, scale / bias
 OutputDesc FillPlaneOutput(const ImageEntry& e, size_t k, uint8_t* work, bool resize_target = false);

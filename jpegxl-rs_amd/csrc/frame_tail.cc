@@ -463,16 +463,28 @@ void Batch::TailColour(TailImage& im, TailUnit& t) {
   ca.w = t.fw; ca.h = t.fh; ca.src_stride = t.cur_stride;
   ca.mode = im.ih.xyb_encoded ? 0 : p.do_ycbcr ? 1 : 2;
   const bool separate = t.cb.rgb[0] != (size_t)-1;
-  if (ca.mode == 2 && !separate) return;
+  // An image that is not XYB on its way to a requested encoding (OutputSpec::color_non_xyb): the conversion applies to the finished picture — blending and spot colours
+  // work on the image's own samples —, so it rides behind them like the transfer function put off for a spot-colour stage; a last frame that is the picture by itself
+  // takes it in this launch
+  const bool converts = ca.mode != 0 && ConvertsNonXyb(im.ih, im.first.out);
+  const bool convert_here = converts && p.is_last && !t.needs_blending && !im.render_spots;
+  if (converts && !convert_here) {
+    t.deferred_tf = ca; t.deferred_tf.mode = 2;
+    FillColourConversion(im.ih, im.first.out, &t.deferred_tf);
+    t.have_deferred_tf = true;
+  }
+  if (ca.mode == 2 && !separate && !convert_here) return;
   for (int c = 0; c < 3; c++) { ca.src[c] = BigPlane(t.cur[c]); ca.dst[c] = separate ? BigPlane(t.cb.rgb[c]) : BigPlane(t.cur[c]); }
   ca.dst_stride = separate ? t.fw : t.cur_stride;
   FrameDev fd;
-  FillColor(im.ih, p.do_ycbcr, fd);
+  ImageHeader colour_store;
+  FillColor(ColourHeader(im.ih, im.first.out, &colour_store), p.do_ycbcr, fd);
   for (int k = 0; k < 9; k++) ca.opsin_inv[k] = fd.opsin_inv[k];
   for (int k = 0; k < 3; k++) { ca.neg_bias[k] = fd.neg_bias[k]; ca.neg_bias_cbrt[k] = fd.neg_bias_cbrt[k]; }
   ca.tf_kind = fd.color_mode;
   for (int k = 0; k < 5; k++) ca.hdr_par[k] = fd.hdr_par[k];
   ca.inverse_gamma = fd.inverse_gamma;
+  if (convert_here) FillColourConversion(im.ih, im.first.out, &ca);
   // spot colours are mixed in linear light when the frame goes straight to the output (dec_cache.cc PreparePipeline: XYB stage,
   // [from-linear + blending], spot stage, from-linear): the transfer function then follows the spot stage
   if (spot_after_linear && ca.mode == 0) { t.deferred_tf = ca; t.deferred_tf.mode = 3; ca.tf_kind = 1; t.have_deferred_tf = true; }

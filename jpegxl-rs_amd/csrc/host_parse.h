@@ -247,6 +247,22 @@ std::string ColorDescription(const ImageHeader& ih);
 // with linear Bradford adaptation) and the luminance weights of those primaries.  Returns false — identity, sRGB luminances — for
 // sRGB / D65, grey images and images that carry an ICC profile.
 bool SrgbToOriginalPrimaries(const ImageHeader& ih, double m[9], float luminances[3]);
+// A colour encoding on its own — a requested output encoding (OutputSpec::color) or an image's — in the forms ImageHeader keeps: enumerated values, gamma in units of
+// 1e-7, custom CIE xy.  include/jxl_hip.h ("output colour") has the rule these serve.
+struct ColorTarget {
+  uint32_t color_space = 0, white_point = 1, primaries = 1, tf = 13, rendering_intent = 1;
+  bool have_gamma = false; uint32_t gamma = 0;
+  double white_xy[2] = {0.3127, 0.3290}, prim_xy[6] = {0.639998686, 0.330010138, 0.300003784, 0.600003357, 0.150002046, 0.059997204};
+};
+ColorTarget ColorTargetOf(const ImageHeader& ih);                    // the header's enumerated encoding (the default one: sRGB); not meaningful under want_icc
+void ApplyColorTarget(const ColorTarget& t, ImageHeader* ih);        // the header names `t` from now on: no default, no ICC profile
+// "" for an encoding the decoder can render to, else the reason: colour space 2 / 3, an unknown enum, transfer function 2, a chromaticity with y <= 0, a gamma outside (0, 1]
+std::string ColorTargetRefusal(const ColorTarget& t);
+// the same white point, primaries (by their xy; grey: the white point alone) and transfer function (linear is gamma 1, DCI is gamma 1 / 2.6); the rendering intent does not count
+bool SameColorEncoding(const ColorTarget& a, const ColorTarget& b);
+// linear light of `from` -> linear light of `to`: inv(AdaptToXyzD50(w_to) x PrimariesToXyz(p_to, w_to)) x AdaptToXyzD50(w_from) x PrimariesToXyz(p_from, w_from), row-major,
+// in double; the identity, exactly, between equal chromaticities and when either side is grey
+void ColorConversionMatrix(const ColorTarget& from, const ColorTarget& to, double m[9]);
 extern const uint8_t kBucketStrategy[13];
 extern const uint8_t kKindRows[17], kKindCols[17];
 

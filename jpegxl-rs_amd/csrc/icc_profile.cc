@@ -180,6 +180,69 @@ bool SrgbToOriginalPrimaries(const ImageHeader& ih, double m[9], float luminance
   return true;
 }
 
+// ---- colour encodings on their own (ColorTarget): what a requested output encoding needs of the functions above
+ColorTarget ColorTargetOf(const ImageHeader& ih) {
+  ColorTarget t;
+  if (ih.color_default) return t;
+  t.color_space = ih.color_space; t.white_point = ih.white_point; t.primaries = ih.primaries; t.tf = ih.tf; t.rendering_intent = ih.rendering_intent;
+  t.have_gamma = ih.have_gamma; t.gamma = ih.gamma;
+  for (int i = 0; i < 2; i++) t.white_xy[i] = ih.white_xy[i];
+  for (int i = 0; i < 6; i++) t.prim_xy[i] = ih.prim_xy[i];
+  return t;
+}
+void ApplyColorTarget(const ColorTarget& t, ImageHeader* ih) {
+  ih->color_default = false; ih->want_icc = false;
+  ih->color_space = t.color_space; ih->white_point = t.white_point; ih->primaries = t.primaries; ih->tf = t.tf; ih->rendering_intent = t.rendering_intent;
+  ih->have_gamma = t.have_gamma; ih->gamma = t.gamma;
+  for (int i = 0; i < 2; i++) ih->white_xy[i] = t.white_xy[i];
+  for (int i = 0; i < 6; i++) ih->prim_xy[i] = t.prim_xy[i];
+}
+namespace {
+ImageHeader HeaderOf(const ColorTarget& t) { ImageHeader h; ApplyColorTarget(t, &h); return h; }
+// the transfer function as (is it a power law?, its exponent in units of 1e-7 / its enum)
+std::pair<bool, uint32_t> TransferOf(const ColorTarget& t) {
+  if (t.have_gamma) return {true, t.gamma};
+  if (t.tf == 8) return {true, 10000000u};
+  if (t.tf == 17) return {true, 3846154u};
+  return {false, t.tf};
+}
+}  // namespace
+std::string ColorTargetRefusal(const ColorTarget& t) {
+  const std::string head = "unsupported: output colour ";
+  if (t.color_space > 1) return head + "in the XYB / an unknown colour space (colour space " + std::to_string(t.color_space) + ")";
+  if (t.white_point != 1 && t.white_point != 2 && t.white_point != 10 && t.white_point != 11) return head + "with white point enum " + std::to_string(t.white_point);
+  if (t.color_space == 0 && t.primaries != 1 && t.primaries != 2 && t.primaries != 9 && t.primaries != 11) return head + "with primaries enum " + std::to_string(t.primaries);
+  if (t.have_gamma) { if (t.gamma == 0 || t.gamma > 10000000) return head + "with a gamma outside (0, 1]"; }
+  else if (t.tf == 2) return head + "with an unknown transfer function (2)";
+  else if (t.tf != 1 && t.tf != 8 && t.tf != 13 && t.tf != 16 && t.tf != 17 && t.tf != 18) return head + "with transfer function enum " + std::to_string(t.tf);
+  if (t.white_point == 2 && !(t.white_xy[1] > 1e-9)) return head + "with a white point of y <= 0";
+  if (t.color_space == 0 && t.primaries == 2) {
+    for (int c = 0; c < 3; c++) if (!(t.prim_xy[2 * c + 1] > 1e-9)) return head + "with a primary of y <= 0";
+    try { double w[2], p[6]; const ImageHeader h = HeaderOf(t); WhiteXy(h, w); PrimariesXy(h, p); (void)Inv(PrimariesToXyz(p, w)); }
+    catch (const ParseError&) { return head + "with singular primaries"; }
+  }
+  return std::string();
+}
+bool SameColorEncoding(const ColorTarget& a, const ColorTarget& b) {
+  if (a.color_space != b.color_space || TransferOf(a) != TransferOf(b)) return false;
+  double wa[2], wb[2], pa[6], pb[6];
+  ColorChromaticities(HeaderOf(a), wa, pa); ColorChromaticities(HeaderOf(b), wb, pb);
+  if (wa[0] != wb[0] || wa[1] != wb[1]) return false;
+  if (a.color_space == 0) for (int i = 0; i < 6; i++) if (pa[i] != pb[i]) return false;
+  return true;
+}
+void ColorConversionMatrix(const ColorTarget& from, const ColorTarget& to, double m[9]) {
+  for (int i = 0; i < 9; i++) m[i] = i % 4 == 0 ? 1.0 : 0.0;
+  if (from.color_space != 0 || to.color_space != 0) return;
+  double wf[2], wt[2], pf[6], pt[6];
+  ColorChromaticities(HeaderOf(from), wf, pf); ColorChromaticities(HeaderOf(to), wt, pt);
+  bool same = wf[0] == wt[0] && wf[1] == wt[1];
+  for (int i = 0; i < 6; i++) same = same && pf[i] == pt[i];
+  if (same) return;
+  const Mat3 r = Mul(Inv(Mul(AdaptToXyzD50(wt), PrimariesToXyz(pt, wt))), Mul(AdaptToXyzD50(wf), PrimariesToXyz(pf, wf)));
+  for (int i = 0; i < 9; i++) m[i] = r.m[i / 3][i % 3];
+}
+
 void ColorChromaticities(const ImageHeader& ih, double white_xy[2], double primaries_xy[6]) {
   ImageHeader h = ih;
   if (h.color_default) { h.white_point = 1; h.primaries = 1; }

@@ -5,6 +5,7 @@
 #include "pipeline.h"
 #include "jpeg_recon.h"
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
@@ -26,6 +27,7 @@ struct JxlDecoderStruct {
   int events_wanted;
   bool keep_orientation, unpremul_alpha, render_spotcolors, coalescing;
   float desired_intensity_target;
+  bool out_color_set; ColorTarget out_color;      // JxlHipDecoderSetOutputColorProfile: XYB images are rendered to it (cleared by Reset, kept by Rewind)
   JxlParallelRunner runner; void* runner_opaque;
   const uint8_t* input; size_t input_size; bool input_set, input_closed;
   void* out_buffer; size_t out_size; JxlPixelFormat out_format; bool out_set;
@@ -85,13 +87,18 @@ static int DefaultDevice() {
 
 // host allocations made on behalf of decoder `d` (parser, tables, staging buffers, the Batch object) go through its memory manager
 #define JXL_MM_SCOPE(d) MmScope mm_scope_((d) && (d)->has_mm ? &(d)->hooks : nullptr)
+// JXL_HIP_DEVICE=-1 makes host-only decoders (as JxlHipBatchCreate(-1) makes host-only batches): headers, events up to JXL_DEC_FRAME and every setting work without a GPU;
+// every entry that would decode — the preview, a frame, a progressive flush — goes through this guard first
+static void RequireDevice(const JxlDecoder* d) {
+  if (d->device == -1) throw ParseError("a host-only decoder (JXL_HIP_DEVICE=-1) answers header queries only: it cannot decode", false);
+}
 static Batch* NewBatch(int device) { void* mem = MmAllocate(sizeof(Batch)); try { return new (mem) Batch(device); } catch (...) { MmDeallocate(mem); throw; } }
 static void DeleteBatch(Batch* b) { if (b) { b->~Batch(); MmDeallocate(b); } }
 
 static void ClearState(JxlDecoder* d) {
   d->events_wanted = 0;
   d->keep_orientation = d->unpremul_alpha = false; d->render_spotcolors = true; d->coalescing = true;
-  d->desired_intensity_target = 0;
+  d->desired_intensity_target = 0; d->out_color_set = false;
   d->runner = nullptr; d->runner_opaque = nullptr;
   d->input = nullptr; d->input_size = 0; d->input_set = d->input_closed = false;
   d->out_buffer = nullptr; d->out_size = 0; d->out_set = false; d->out_callback = nullptr; d->out_callback_opaque = nullptr;
@@ -187,7 +194,9 @@ void JxlDecoderRewind(JxlDecoder* d) {
   const int events = d->events_wanted; const bool ko = d->keep_orientation, up = d->unpremul_alpha, rs = d->render_spotcolors, co = d->coalescing;
   const float it = d->desired_intensity_target; const JxlParallelRunner runner = d->runner; void* const ro = d->runner_opaque;
   const bool db = d->decompress_boxes; const int pd = d->progressive_detail;
+  const bool ocs = d->out_color_set; const ColorTarget oc = d->out_color;
   ClearState(d);
+  d->out_color_set = ocs; d->out_color = oc;
   d->decompress_boxes = db; d->progressive_detail = pd;
   d->events_wanted = events; d->keep_orientation = ko; d->unpremul_alpha = up; d->render_spotcolors = rs; d->coalescing = co;
   d->desired_intensity_target = it; d->runner = runner; d->runner_opaque = ro;
@@ -213,9 +222,28 @@ JxlDecoderStatus JxlDecoderGetFrameHeader(const JxlDecoder* d, JxlFrameHeader* h
   h->layer_info.save_as_reference = p.save_as_reference;
   return JXL_DEC_SUCCESS;
 }
-JxlDecoderStatus JxlDecoderGetColorAsEncodedProfile(const JxlDecoder* d, JxlColorProfileTarget, JxlColorEncoding* out) {
-  if (!d->batch || d->stage < JxlDecoderStruct::kHeaders || !out) return JXL_DEC_ERROR;
+// JxlColorEncoding -> ColorTarget (the header's forms: gamma in units of 1e-7; the xy fields count under the custom enums only)
+static void EncodingToTarget(const JxlColorEncoding& c, ColorTarget* t) {
+  *t = ColorTarget();
+  t->color_space = (uint32_t)c.color_space; t->white_point = (uint32_t)c.white_point; t->primaries = c.color_space == 1 ? 1u : (uint32_t)c.primaries;
+  t->rendering_intent = (uint32_t)c.rendering_intent & 3;
+  if (c.transfer_function == 65535) { t->have_gamma = true; t->gamma = c.gamma > 0 && c.gamma <= 1.0 ? (uint32_t)std::lround(c.gamma * 1e7) : 0u; t->tf = 13; }
+  else t->tf = (uint32_t)c.transfer_function;
+  if (t->white_point == 2) for (int i = 0; i < 2; i++) t->white_xy[i] = c.white_point_xy[i];
+  if (t->primaries == 2) for (int i = 0; i < 2; i++) { t->prim_xy[i] = c.primaries_red_xy[i]; t->prim_xy[2 + i] = c.primaries_green_xy[i]; t->prim_xy[4 + i] = c.primaries_blue_xy[i]; }
+}
+// the header the pixel data of the decoder's image is described by: under a requested output colour an XYB image's names that target (want_icc or not)
+static bool DataHeader(const JxlDecoder* d, ImageHeader* store) {
   const ImageHeader& ih = d->batch->image(0).ih;
+  if (!d->out_color_set || !ih.xyb_encoded) return false;
+  *store = ih; store->icc.clear();
+  ApplyColorTarget(d->out_color, store);
+  return true;
+}
+JxlDecoderStatus JxlDecoderGetColorAsEncodedProfile(const JxlDecoder* d, JxlColorProfileTarget target, JxlColorEncoding* out) {
+  if (!d->batch || d->stage < JxlDecoderStruct::kHeaders || !out) return JXL_DEC_ERROR;
+  ImageHeader data_header;
+  const ImageHeader& ih = target == JXL_COLOR_PROFILE_TARGET_DATA && DataHeader(d, &data_header) ? data_header : d->batch->image(0).ih;
   if (ih.want_icc) { SetLastError("the image carries an ICC profile: no enumerated colour encoding"); return JXL_DEC_ERROR; }
   try {
     memset(out, 0, sizeof(*out));
@@ -271,6 +299,26 @@ JxlDecoderStatus JxlDecoderGetExtraChannelBlendInfo(const JxlDecoder* d, size_t 
   FillBlendInfo(p.ec_blend[index], out);
   return JXL_DEC_SUCCESS;
 }
+// The output colour of the libjxl-style decoder, with the argument list and the contract of libjxl's JxlDecoderSetOutputColorProfile (decode.rs:891-973) for a decoder without a
+// CMS: an enumerated encoding makes XYB images come out in that encoding, images that are not XYB keep their samples, an ICC profile is an error.  Between the headers and
+// the first frame's decode (a progressive flush counts) only.  libjxl's own two names stay among the stubs of jxl_stubs.cc, whose list the ABI test pins: forwarding them is
+// `return JxlHipDecoderSetOutputColorProfile(dec, color_encoding, icc_data, icc_size);` and the same with (NULL, 0) for the older JxlDecoderSetPreferredColorProfile.
+JxlDecoderStatus JxlHipDecoderSetOutputColorProfile(JxlDecoder* d, const JxlColorEncoding* color_encoding, const uint8_t* icc_data, size_t icc_size) {
+  const char* who = "JxlHipDecoderSetOutputColorProfile";
+  (void)icc_size;
+  if (!d || !d->batch || d->stage < JxlDecoderStruct::kHeaders) { SetLastError(std::string(who) + ": the colour encoding of the image is not known yet (call after JXL_DEC_COLOR_ENCODING)"); return JXL_DEC_ERROR; }
+  if (d->stage == JxlDecoderStruct::kDone || d->frame_decodes > 0 || d->frame_done || d->frame_cursor > 0 || d->anim_cached || d->progression_emitted) { SetLastError(std::string(who) + ": the frame decode has begun"); return JXL_DEC_ERROR; }
+  if (icc_data) { SetLastError(std::string(who) + ": an ICC output profile needs a CMS, which this decoder does not have (JxlDecoderSetCms is not supported)"); return JXL_DEC_ERROR; }
+  if (!color_encoding) { SetLastError(std::string(who) + ": neither a colour encoding nor an ICC profile"); return JXL_DEC_ERROR; }
+  OutputSpec o;
+  o.color_set = true;
+  EncodingToTarget(*color_encoding, &o.color);
+  const std::string why = Batch::ColourRefusal(d->batch->image(0).ih, o);
+  if (!why.empty()) { SetLastError(std::string(who) + ": " + why); return JXL_DEC_ERROR; }
+  d->out_color_set = true; d->out_color = o.color;
+  return JXL_DEC_SUCCESS;
+}
+
 // decode.rs:360-362.  libjxl tone-maps (Rec. 2408, then gamut mapping) when the target is below the intensity target of a PQ image, and applies the inverse
 // HLG OOTF for the new peak when an HLG image is rendered to another transfer function; everything else is unaffected by the setting.  The tone mapper is not
 // built here: the setting is stored, and a decode that WOULD need it fails with a message instead of handing out pixels that were not tone-mapped (NeedsToneMapping).
@@ -369,6 +417,7 @@ static bool PreviewSpec(const JxlDecoder* d, const JxlPixelFormat* format, Outpu
   if (o->num_channels != 0 && o->num_channels < 3 && d->batch->image(0).ih.color_space != 1) { SetLastError("number of channels is too low for colour output"); return false; }
   o->keep_orientation = d->keep_orientation;
   o->unpremul_alpha = d->unpremul_alpha;
+  o->color_set = d->out_color_set; o->color = d->out_color;
   return true;
 }
 JxlDecoderStatus JxlDecoderPreviewOutBufferSize(const JxlDecoder* d, const JxlPixelFormat* format, size_t* size) {
@@ -417,7 +466,9 @@ static JxlDecoderStatus IccOf(const JxlDecoder* d, JxlColorProfileTarget target,
   if (!d || !d->batch || d->stage < JxlDecoderStruct::kHeaders) { SetLastError("ICC profile requested before the headers were decoded"); return JXL_DEC_ERROR; }
   const ImageHeader& ih = d->batch->image(0).ih;
   try {
-    if (ih.want_icc && (target == JXL_COLOR_PROFILE_TARGET_ORIGINAL || !ih.xyb_encoded)) *icc = ih.icc;
+    ImageHeader data_header;
+    if (target == JXL_COLOR_PROFILE_TARGET_DATA && DataHeader(d, &data_header)) *icc = SynthesizeIcc(data_header);      // (JxlHipDecoderSetOutputColorProfile: the pixels are in the target encoding)
+    else if (ih.want_icc && (target == JXL_COLOR_PROFILE_TARGET_ORIGINAL || !ih.xyb_encoded)) *icc = ih.icc;
     else if (ih.want_icc) { ImageHeader srgb = ih; srgb.want_icc = false; srgb.icc.clear(); *icc = SynthesizeIcc(srgb); }   // XYB pixel data: rendered to sRGB (grey: same curve)
     else *icc = SynthesizeIcc(ih);
   } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
@@ -511,6 +562,7 @@ JxlDecoderStatus JxlDecoderFlushImage(JxlDecoder* d) {
   if (!d || !d->batch || d->stage < JxlDecoderStruct::kHeaders || !d->out_set || !d->out_buffer || d->out_callback || d->mt_run) { SetLastError("nothing to flush: no frame in progress or no image out buffer set"); return JXL_DEC_ERROR; }
   if (!d->input_set) { SetLastError("nothing to flush: the input has been released"); return JXL_DEC_ERROR; }
   try {
+    RequireDevice(d);
     if (hipSetDevice(d->device) != hipSuccess) { (void)hipGetLastError(); SetLastError("no usable HIP device"); return JXL_DEC_ERROR; }
     struct Holder { Batch* b; ~Holder() { DeleteBatch(b); } } hold{NewBatch(d->device)};
     hold.b->AddImage(d->input, d->input_size, /*allow_partial=*/true);
@@ -520,6 +572,7 @@ JxlDecoderStatus JxlDecoderFlushImage(JxlDecoder* d) {
     OutputSpec o;
     FormatToSpec(&d->out_format, &o);
     o.keep_orientation = d->keep_orientation; o.int_bits = d->out_int_bits;
+    o.color_set = d->out_color_set; o.color = d->out_color;      // (what is flushed is in the encoding the finished image will come out in)
     hold.b->SetOutput(0, o);
     if (hold.b->image(0).out_size > d->out_size) throw ParseError("output buffer too small for this frame", false);
     // what is shown: input that ends inside the frame — every group with the passes that have completely arrived (the HF kernels leave the others out); after a
@@ -663,13 +716,15 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
   try {
     if (d->stage == JxlDecoderStruct::kHeaders || d->stage == JxlDecoderStruct::kFrame) {
       // (the current device is per thread, and a decoder may be called from another thread than last time)
-      if (hipSetDevice(d->device) != hipSuccess) { (void)hipGetLastError(); SetLastError("no usable HIP device"); return JXL_DEC_ERROR; }
+      if (d->device != -1 && hipSetDevice(d->device) != hipSuccess) { (void)hipGetLastError(); SetLastError("no usable HIP device"); return JXL_DEC_ERROR; }
     }
     if (d->stage == JxlDecoderStruct::kInit) {
       JxlSignature sig = JxlSignatureCheck(d->input, d->input_size);
       if (sig == JXL_SIG_INVALID) { SetLastError("invalid signature"); return JXL_DEC_ERROR; }
       if (sig == JXL_SIG_NOT_ENOUGH_BYTES) return d->input_closed ? JXL_DEC_ERROR : JXL_DEC_NEED_MORE_INPUT;
-      if (hipSetDevice(d->device) != hipSuccess) { SetLastError("no usable HIP device: the JPEG XL decode path requires an MI355X-class GPU (no CPU fallback)"); return JXL_DEC_ERROR; }
+      // (JXL_HIP_DEVICE=-1: a host-only decoder, as JxlHipBatchCreate(-1) makes host-only batches — headers, events up to JXL_DEC_FRAME and every setting work without a GPU;
+      // what would decode fails below)
+      if (d->device != -1 && hipSetDevice(d->device) != hipSuccess) { SetLastError("no usable HIP device: the JPEG XL decode path requires an MI355X-class GPU (no CPU fallback)"); return JXL_DEC_ERROR; }
       struct Holder { Batch* b; ~Holder() { DeleteBatch(b); } } hold{NewBatch(d->device)};
       try {
         hold.b->AddImage(d->input, d->input_size);      // (throws "truncated" while the frame index is incomplete)
@@ -696,6 +751,7 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
       if ((d->events_wanted & JXL_DEC_COLOR_ENCODING) && !(d->events_emitted & JXL_DEC_COLOR_ENCODING)) { d->events_emitted |= JXL_DEC_COLOR_ENCODING; return JXL_DEC_COLOR_ENCODING; }
       if ((d->events_wanted & JXL_DEC_PREVIEW_IMAGE) && !(d->events_emitted & JXL_DEC_PREVIEW_IMAGE) && d->batch->image(0).ih.have_preview) {
         if (!d->preview_set) return JXL_DEC_NEED_PREVIEW_OUT_BUFFER;
+        RequireDevice(d);
         OutputSpec o;
         if (!PreviewSpec(d, &d->preview_format, &o)) return JXL_DEC_ERROR;
         d->batch->DecodePreview(0, o, d->preview_buffer, d->preview_size, DecoderStream(d));      // ══► the HIP hot path, on the preview frame
@@ -719,6 +775,7 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
       if ((d->events_wanted & JXL_DEC_FRAME) && !d->frame_announced) { d->frame_announced = true; d->events_emitted |= JXL_DEC_FRAME; return JXL_DEC_FRAME; }
       d->frame_announced = true;
       if (!(d->events_wanted & JXL_DEC_FULL_IMAGE)) { d->frame_cursor++; d->frame_announced = false; continue; }
+      RequireDevice(d);
       if (d->jpeg_available && d->jpeg_set) {
         // the caller asked for the JPEG file: entropy decode on the GPU, Huffman re-encode on the host, written in one piece
         if (d->jpeg_bytes.empty()) {
@@ -780,6 +837,7 @@ JxlDecoderStatus JxlDecoderProcessInput(JxlDecoder* d) {
       o.unpremul_alpha = d->unpremul_alpha;
       o.render_spotcolors = d->render_spotcolors;
       o.int_bits = d->out_int_bits;
+      o.color_set = d->out_color_set; o.color = d->out_color;      // (fixed before the first frame: JxlHipDecoderSetOutputColorProfile refuses later calls, so kept canvases stay valid)
       o.only_frame = d->coalescing ? -1 : d->frames[d->frame_cursor];
       o.upto_frame = d->coalescing && d->frames.size() > 1 ? d->frames[d->frame_cursor] : -1;
       // Animations (coalescing): one decode serves every shown frame — the canvas after each of them is kept in device memory (Batch::SetOutputAllFrames) — as long as
@@ -1089,6 +1147,41 @@ JxlDecoderStatus JxlHipBatchSetOutputPlanes(JxlHipBatch* h, int i, const JxlHipO
     return JXL_DEC_SUCCESS;
   } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
 }
+// JxlHipOutputColor -> OutputSpec::color (NULL: none); what depends on the image is checked where the image is known (Batch::ColourRefusal)
+static bool ApplyColor(const JxlHipOutputColor* c, OutputSpec* o, const char* who) {
+  o->color_set = false; o->color = ColorTarget(); o->color_non_xyb = 0;
+  if (!c) return true;
+  o->color_set = true; o->color_non_xyb = c->non_xyb;
+  EncodingToTarget(c->encoding, &o->color);
+  const std::string why = c->non_xyb > 1 ? "unsupported: output colour with non_xyb = " + std::to_string(c->non_xyb) + " (0 leave, 1 convert)" : ColorTargetRefusal(o->color);
+  if (!why.empty()) { SetLastError(std::string(who) + ": " + why); return false; }
+  return true;
+}
+JxlDecoderStatus JxlHipBatchSetOutputColor(JxlHipBatch* h, int i, const JxlHipOutputColor* color) {
+  const char* who = "JxlHipBatchSetOutputColor";
+  if (!h || i < 0 || (size_t)i >= h->b->size()) { SetLastError(std::string(who) + ": no such image"); return JXL_DEC_ERROR; }
+  try {
+    const ImageEntry& e = h->b->image(i);
+    if (e.out_size == 0) { SetLastError(std::string(who) + ": the image has no output yet (call JxlHipBatchSetOutput... first)"); return JXL_DEC_ERROR; }
+    OutputSpec o = e.out;
+    if (!ApplyColor(color, &o, who)) return JXL_DEC_ERROR;
+    if (!e.deliver_frames.empty()) { const vec<int> frames = e.deliver_frames; h->b->SetOutputAllFrames(i, o, frames); }      // (kept canvases: refused there for what it cannot convert)
+    else h->b->SetOutput(i, o);
+    return JXL_DEC_SUCCESS;
+  } catch (const std::exception& e) { SetLastError(std::string(who) + ": " + e.what()); return JXL_DEC_ERROR; }
+}
+int JxlHipColorConversionMatrix(const JxlColorEncoding* from, const JxlColorEncoding* to, double m[9]) {
+  const char* who = "JxlHipColorConversionMatrix";
+  if (!from || !to || !m) { SetLastError(std::string(who) + ": null argument"); return 1; }
+  try {
+    ColorTarget a, b;
+    EncodingToTarget(*from, &a); EncodingToTarget(*to, &b);
+    for (const ColorTarget* t : {&a, &b}) { const std::string why = ColorTargetRefusal(*t); if (!why.empty()) { SetLastError(std::string(who) + ": " + why); return 1; } }
+    if (a.color_space != b.color_space) { SetLastError(std::string(who) + ": unsupported: output colour: a grey encoding on one side, an RGB encoding on the other"); return 1; }
+    ColorConversionMatrix(a, b, m);
+    return 0;
+  } catch (const std::exception& e) { SetLastError(std::string(who) + ": " + e.what()); return 1; }
+}
 JxlDecoderStatus JxlHipBatchOutputPlanesLayout(const JxlHipBatch* h, int i, size_t* offset, size_t* plane_stride, size_t* total) {
   if (!h || i < 0 || (size_t)i >= h->b->size()) { SetLastError("JxlHipBatchOutputPlanesLayout: no such image"); return JXL_DEC_ERROR; }
   const ImageEntry& e = h->b->image(i);
@@ -1327,15 +1420,16 @@ int64_t JxlHipPipelineSubmitResampled(JxlHipPipeline* h, const uint8_t* const* d
     return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity, specs.empty() ? nullptr : specs.data());
   } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
 }
-// ... with extra-channel planes behind every image's colour output (OutputSpec::planes: one request list for the job); each may be NULL (no resize)
-int64_t JxlHipPipelineSubmitPlanes(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
-                                   const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, const JxlHipOutputPlanes* planes) {
-  const char* who = "JxlHipPipelineSubmitPlanes";
+// the body of JxlHipPipelineSubmitPlanes and JxlHipPipelineSubmitColor: a job with per-image resamples (each; NULL: no resize), extra-channel planes (NULL: none) and an output
+// colour (OutputSpec::color; NULL: none); an image the target is refused for fails alone
+static int64_t PipelineSubmitColor(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                                   const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, const JxlHipOutputPlanes* planes,
+                                   const JxlHipOutputColor* color, const char* who) {
   if (!DownscaleOk(downscale, who)) return -1;
   try {
     OutputSpec base;
     if (!h || !FormatToSpec(format, &base)) { SetLastError(std::string(who) + ": bad pixel format"); return -1; }
-    if (!ApplyLayout(layout, &base, who) || !ApplyPlanes(planes, &base, who)) return -1;
+    if (!ApplyLayout(layout, &base, who) || !ApplyPlanes(planes, &base, who) || !ApplyColor(color, &base, who)) return -1;
     base.downscale = (uint32_t)downscale;
     if (base.planes.any() && downscale == 8) { SetLastError(std::string(who) + ": unsupported: extra planes of the 1:8 decode (downscale 8)"); return -1; }
     if (!each) return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity);
@@ -1351,6 +1445,16 @@ int64_t JxlHipPipelineSubmitPlanes(JxlHipPipeline* h, const uint8_t* const* data
     if (n > 0) { base.resize_w = each[0].xsize; base.resize_h = each[0].ysize; }
     return h->p->Submit(datas, sizes, n, base, device_out, host_out, out_capacity, specs.empty() ? nullptr : specs.data());
   } catch (const std::exception& e) { SetLastError(e.what()); return -1; }
+}
+// ... with extra-channel planes behind every image's colour output (OutputSpec::planes: one request list for the job); each may be NULL (no resize)
+int64_t JxlHipPipelineSubmitPlanes(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                                   const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, const JxlHipOutputPlanes* planes) {
+  return PipelineSubmitColor(h, datas, sizes, n, format, device_out, host_out, out_capacity, downscale, layout, each, planes, nullptr, "JxlHipPipelineSubmitPlanes");
+}
+int64_t JxlHipPipelineSubmitColor(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,
+                                  const size_t* out_capacity, int downscale, const JxlHipOutputLayout* layout, const JxlHipOutputResample* each, const JxlHipOutputPlanes* planes,
+                                  const JxlHipOutputColor* color) {
+  return PipelineSubmitColor(h, datas, sizes, n, format, device_out, host_out, out_capacity, downscale, layout, each, planes, color, "JxlHipPipelineSubmitColor");
 }
 // a libjpeg-exact job (Pipeline::Submit, jpeg_pixels): the layout and the per-image resamples of the calls above, no downscale
 static int64_t PipelineSubmitJpegPixels(JxlHipPipeline* h, const uint8_t* const* datas, const size_t* sizes, int n, const JxlPixelFormat* format, void* const* device_out, void* const* host_out,

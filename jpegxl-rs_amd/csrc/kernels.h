@@ -296,7 +296,11 @@ struct PatchEcDev { const float* src; uint32_t mode, pad; };
 struct PatchFrameArgs { float* p[3]; uint32_t stride, ec_stride, w, h, num_extra; };
 struct NoiseArgs { float* p[3]; uint32_t stride, w, h; float* noise[3]; uint32_t noise_stride, group_dim, visible_frame_index, nonvisible_frame_index; float lut[8]; float ytox, ytob; };
 // mode: 3 = transfer function only (after a spot-colour stage in linear light); 0 XYB -> linear -> transfer function (tf_kind: FrameDev::color_mode's values 0, 1, 4..7), 1 YCbCr -> RGB, 2 copy
-struct ColorArgs { const float* src[3]; float* dst[3]; uint32_t src_stride, dst_stride, w, h, mode, tf_kind; float inverse_gamma, opsin_inv[9], neg_bias[3], neg_bias_cbrt[3], hdr_par[5]; };
+// convert (modes 1 and 2 only; decoder.cc FillColourConversion): the samples of an image that is not XYB go on to a requested output encoding — src_tf (color_mode's
+// values) with src_par decodes them to linear light (gamma: par[0] = 1 / exponent; PQ: par[0] = 10000 / intensity target; HLG: par = {OOTF exponent, apply?, luminances of
+// the source's primaries}), conv is the row-major matrix between the two sets of primaries (conv_identity: left out), tf_kind / inverse_gamma / hdr_par are the target's
+struct ColorArgs { const float* src[3]; float* dst[3]; uint32_t src_stride, dst_stride, w, h, mode, tf_kind; float inverse_gamma, opsin_inv[9], neg_bias[3], neg_bias_cbrt[3], hdr_par[5];
+                   uint32_t convert, conv_identity, src_tf; float src_par[5], conv[9]; };
 // Blending of the colour: mode = BlendMode | alpha channel << 8 | clamp << 16; bg pointers are null when the source slot is empty (treated as zeros); bg_alpha: the colour
 // source's plane of the alpha channel.  The foreground alpha and every extra channel go through the table.
 struct BlendArgs {

@@ -269,6 +269,18 @@ __global__ void ColorKernel(ColorArgs a) {
     r = X; g = Y; b = B;
     const float3 t = TransferFromLinear(a, a.tf_kind, r, g, b); r = t.x; g = t.y; b = t.z;
   } else { r = X; g = Y; b = B; }
+  // an image that is not XYB on its way to a requested encoding (ColorArgs::convert, modes 1 and 2): its transfer function undone, the matrix between the two sets of
+  // primaries, the target's transfer function.  Every switch is on a kernel argument: scalar branches.
+  if (a.convert && (a.mode == 1 || a.mode == 2)) {
+    const float3 l = TransferToLinear(a.src_par, a.src_tf, r, g, b);
+    r = l.x; g = l.y; b = l.z;
+    if (!a.conv_identity) {
+      r = fmaf(a.conv[2], l.z, fmaf(a.conv[1], l.y, a.conv[0] * l.x));
+      g = fmaf(a.conv[5], l.z, fmaf(a.conv[4], l.y, a.conv[3] * l.x));
+      b = fmaf(a.conv[8], l.z, fmaf(a.conv[7], l.y, a.conv[6] * l.x));
+    }
+    const float3 t = TransferFromLinear(a, a.tf_kind, r, g, b); r = t.x; g = t.y; b = t.z;
+  }
   a.dst[0][di] = r; a.dst[1][di] = g; a.dst[2][di] = b;
 }
 

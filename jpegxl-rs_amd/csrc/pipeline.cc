@@ -301,7 +301,7 @@ void Pipeline::PrepareJob(Job* j, int worker) {
       if (!refusal.empty()) {
         // (stays in the batch like an image whose buffer is too small, with a tight plane of its own and no crop, mirror or filter)
         j->result.error[(size_t)i] = refusal;
-        o.device_ptr = nullptr; o.plane_stride = 0; o.crop_x0 = o.crop_y0 = o.crop_w = o.crop_h = 0; o.mirror = false; o.resize_filter = 0; o.planes = OutputPlanes();
+        o.device_ptr = nullptr; o.plane_stride = 0; o.crop_x0 = o.crop_y0 = o.crop_w = o.crop_h = 0; o.mirror = false; o.resize_filter = 0; o.planes = OutputPlanes(); o.color_set = false;
         j->batch_index[(size_t)i] = -2 - index[(size_t)i];
       } else if (j->kind == kJpegPixels && !bt.CanDecodeJpegPixels(index[(size_t)i], &not_eligible)) {
         // (a libjpeg-exact job: what that decode does not take stays in the batch too and fails with the batch call's reason; nothing is written for it)

@@ -67,6 +67,50 @@ template <typename P> __device__ __forceinline__ float3 TransferFromLinear(const
   return make_float3(r, g, b);
 }
 
+// ---- inverse transfer functions: encoded samples -> linear light (1.0 = the image's intensity target), for images that are not XYB on their way to a requested
+// output encoding (ColorKernel).  The textbook definitions in float32 with the device's powf / expf — no fast approximations, nothing here is held bit for bit against
+// libjxl.  Negative inputs as the forward functions above treat them: odd extension; the power law gives 0 at or below GammaFromLinear's threshold.
+__device__ __forceinline__ float SrgbToLinear(float v) {            // IEC 61966-2-1
+  const float x = fabsf(v);
+  return copysignf(x <= 0.04045f ? x * (1.0f / 12.92f) : powf((x + 0.055f) * (1.0f / 1.055f), 2.4f), v);
+}
+__device__ __forceinline__ float GammaToLinear(float v, float gamma) { return v <= 1e-5f ? 0.0f : powf(v, gamma); }      // gamma: 1 / the encoding exponent
+__device__ __forceinline__ float Rec709ToLinear(float v) { return v < 0.081f ? v * (1.0f / 4.5f) : powf((v + 0.099f) * (1.0f / 1.099f), 1.0f / 0.45f); }
+// SMPTE ST 2084 EOTF, Y = (max(p - c1, 0) / (c2 - c3 p))^(1 / m1) with p = E^(1 / m2); scale = 10000 / intensity target.  In double, as HlgFromLinear is: towards code
+// 1.0 the denominator is the difference of two numbers a hundred times its size and the power 1 / m1 = 6.3 multiplies what that loses — in float32, 5e-5 of the value
+// (measured: 6e-4 on a linear light of 10, code 1.0 of a 1000-nit image)
+__device__ __forceinline__ float PqToLinear(float v, float scale) {
+  const double m1 = 2610.0 / 16384, m2 = 2523.0 / 4096 * 128, c1 = 3424.0 / 4096, c2 = 2413.0 / 4096 * 32, c3 = 2392.0 / 4096 * 32;
+  const double p = pow(fabs((double)v), 1.0 / m2);
+  return copysignf((float)(pow(fmax(p - c1, 0.0) / (c2 - c3 * p), 1.0 / m1) * (double)scale), v);
+}
+// BT.2100 HLG inverse OETF: scene light, 1.0 at signal 1.0
+__device__ __forceinline__ float HlgToLinear(float v) {
+  const float kA = 0.17883277f, kB = 1 - 4 * kA, kC = 0.5599107295f;
+  const float e = fabsf(v);
+  return copysignf(e <= 0.5f ? e * e * (1.0f / 3) : (expf((e - kC) * (1.0f / kA)) + kB) * (1.0f / 12), v);
+}
+// BT.2100 HLG OOTF: display = scene x Y_s^(gamma - 1); par = {gamma - 1, apply?, luminances of the source's primaries} (the inverse of HlgInverseOotf, skipped in its band)
+__device__ __forceinline__ void HlgOotf(const float* par, float& r, float& g, float& b) {
+  if (par[1] == 0.0f) return;
+  const float luminance = fmaf(par[2], r, fmaf(par[3], g, par[4] * b));
+  const float ratio = fminf(powf(fmaxf(luminance, 0.0f), par[0]), 1e9f);
+  r *= ratio; g *= ratio; b *= ratio;
+}
+// Encoded samples of encoding `kind` (FrameDev::color_mode's values: 0 sRGB, 1 linear, 4 gamma, 5 Rec.709, 6 PQ, 7 HLG) -> linear light.  kind is the same for the whole
+// launch (a kernel argument): one scalar branch, not a select over the functions
+__device__ __forceinline__ float3 TransferToLinear(const float* par, uint32_t kind, float r, float g, float b) {
+  switch (kind) {
+    case 0: r = SrgbToLinear(r); g = SrgbToLinear(g); b = SrgbToLinear(b); break;
+    case 4: r = GammaToLinear(r, par[0]); g = GammaToLinear(g, par[0]); b = GammaToLinear(b, par[0]); break;
+    case 5: r = Rec709ToLinear(r); g = Rec709ToLinear(g); b = Rec709ToLinear(b); break;
+    case 6: r = PqToLinear(r, par[0]); g = PqToLinear(g, par[0]); b = PqToLinear(b, par[0]); break;
+    case 7: r = HlgToLinear(r); g = HlgToLinear(g); b = HlgToLinear(b); HlgOotf(par, r, g, b); break;
+    default: break;
+  }
+  return make_float3(r, g, b);
+}
+
 // ---- colour transforms ----------------------------------------------------------------------------------------------------------------------------
 // stage_xyb.cc: XYB -> linear RGB (bias, cube, 3x3 matrix).  P: FrameDev or ColorArgs (opsin_inv, neg_bias, neg_bias_cbrt as decoder.cc FillColor sets them)
 template <typename P> __device__ __forceinline__ void XybToLinear(const P& p, float X, float Y, float B, float& r, float& g, float& b) {

@@ -27,7 +27,8 @@ struct Request {
 bool SameSpec(const OutputSpec& a, const OutputSpec& b) {
   return a.num_channels == b.num_channels && a.type == b.type && a.big_endian == b.big_endian && a.align == b.align && a.keep_orientation == b.keep_orientation &&
          a.unpremul_alpha == b.unpremul_alpha && a.upto_frame == b.upto_frame && a.only_frame == b.only_frame && a.alpha_from_extra == b.alpha_from_extra &&
-         a.int_bits == b.int_bits && a.render_spotcolors == b.render_spotcolors;
+         a.int_bits == b.int_bits && a.render_spotcolors == b.render_spotcolors && a.color_set == b.color_set &&
+         (!a.color_set || (a.color_non_xyb == b.color_non_xyb && a.color.rendering_intent == b.color.rendering_intent && SameColorEncoding(a.color, b.color)));
 }
 
 std::atomic<int> g_live_decoders{0};      // JxlDecoderCreate / Destroy (SchedulerNoteDecoder)

@@ -538,6 +538,10 @@ JxlDecoderStatus JxlHipBatchDecodeTimed(JxlHipBatch* batch, void* hip_stream);
  * go to different streams; the caller orders them with events, which lets the latency-bound LF stage of later batches overlap
  * the other stages of the current one (bench.py: three batches in flight, LF stages on two side streams). */
 JxlDecoderStatus JxlHipBatchDecodePart(JxlHipBatch* batch, void* hip_stream, int part, int timed);
+/* Piece 5 (LF decode) of n prepared batches on one stream, as the pipeline enqueues it for jobs that are ready together: adjacent batches whose LF streams take the same
+ * SIMT kernel (plain VarDCT frames, equal lane strides) share ONE launch of it, at most 8 batches a launch; every other batch gets exactly the launches of
+ * JxlHipBatchDecodePart(batch, stream, 5, timed).  Order is kept.  The remaining pieces of each batch follow through JxlHipBatchDecodePart. */
+JxlDecoderStatus JxlHipBatchDecodeLfGrouped(JxlHipBatch* const* batches, int n, void* hip_stream, int timed);
 /* Waits for all timed decodes so far; returns per-stage sums in ms and the number of timed decodes. */
 JxlDecoderStatus JxlHipBatchCollectTimes(JxlHipBatch* batch, JxlHipStageTimes* times, int* runs);
 /* Waits for completion and checks per-frame device status. */
@@ -573,7 +577,7 @@ size_t JxlHipBatchDebugRead(JxlHipBatch* batch, int index, const char* name, int
 typedef struct JxlHipPipelineStruct JxlHipPipeline;
 typedef struct {
   int32_t jobs_in_flight;    /* jobs in flight on the GPU; 0 = default (11) */
-  int32_t lf_streams;        /* side streams for the LF stages; 0 = default (11) */
+  int32_t lf_streams;        /* side streams for the LF stages, at most; 0 = default (11).  In use: as many as the hardware queues leave room for (JxlHipPipelineSetOption "lf_streams_effective") */
   int32_t hf_streams;        /* HF stages in flight beside the tail, one coefficient set each + one; 0 = default (2) */
   int32_t prepare_threads;   /* host threads that each prepare one job at a time; 0 = default (3) */
   int32_t parse_threads;     /* host threads one job's images are parsed on; 0 = default (8) */
@@ -671,10 +675,15 @@ void JxlHipPipelineStageBytes(JxlHipPipeline* pipeline, uint64_t out[6]);   /* a
  * "compressed_bytes", "total_pixels", "hf_nonzeros", "lf_simt_frames", "lf_legacy_frames", "lf_simt_wp", "jpeg_pixel_images" (images of a libjpeg-exact job that took
  * that path; after the job has finished: that were decoded; 0 for a plain job), "jpeg_pixel_launches" (launches of its two pixel kernels: two per 32768 such images);
  * of the job finished last, 0 unless it was a reconstruction job: "jpeg_device_images", "jpeg_host_images", "jpeg_device_progressive_images" (as JxlHipBatchGetInfo),
- * "jpeg_gather_launches" (launches of the gather kernel: one per 32768 images).  -1: unknown name. */
+ * "jpeg_gather_launches" (launches of the gather kernel: one per 32768 images); "lf_groups" / "lf_grouped_jobs" (LF stages enqueued since the last clock reset — a
+ * launch may serve several jobs — and the jobs in them), "lf_group_largest", "lf_streams_effective" (LF streams in use), "lf_group_max".  -1: unknown name. */
 int64_t JxlHipPipelineGetInfo(JxlHipPipeline* pipeline, const char* name);
 /* Options that apply to the jobs submitted after the call: "jpeg_region" (0 / 1, default 0: libjpeg-exact jobs decode crops by region, JxlHipBatchJpegRegion; GetInfo
- * "hf_groups_total" / "hf_groups_decoded" of the job prepared last).  Unknown names are ignored. */
+ * "hf_groups_total" / "hf_groups_decoded" of the job prepared last); "lf_group_max" (1 .. 8, default 4: jobs that are ready together while the LF stream is busy share
+ * one launch of the SIMT LF kernel, at most this many; 1: every job its own launch); "lf_streams_effective" (LF streams in use, at most options.lf_streams; default 0 =
+ * min(lf_streams, 6, max(3, Q - 2 - hf_streams)) with Q = GPU_MAX_HW_QUEUES of the process, 4 if unset: streams that share a hardware queue serialise).  Both also as
+ * JXL_HIP_LF_GROUP_MAX / JXL_HIP_LF_STREAMS_EFFECTIVE in the environment, read when a pipeline is created: there the environment takes precedence over the defaults,
+ * a JxlHipPipelineSetOption call afterwards over the environment.  Unknown names are ignored. */
 void JxlHipPipelineSetOption(JxlHipPipeline* pipeline, const char* name, int value);
 /* Pinned host memory for host_out destinations (hipHostMalloc / hipHostFree). */
 void* JxlHipHostAlloc(size_t bytes);

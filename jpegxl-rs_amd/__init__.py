@@ -1140,6 +1140,17 @@ class BatchDecoder:
         return libjxl().JxlHipBatchDeviceBytes(self._h)
 
 
+def decode_lf_grouped(batches, stream=None, timed=False):
+    """Piece 5 (LF decode) of several prepared BatchDecoders on one stream, as the pipeline enqueues it for jobs that are ready together: adjacent batches whose LF
+    streams take the same SIMT kernel share one launch of it, every other batch gets the launches of decode_part(5) (include/jxl_hip.h JxlHipBatchDecodeLfGrouped).
+    The other pieces of each batch follow through decode_part."""
+    fn = libjxl().JxlHipBatchDecodeLfGrouped
+    fn.restype, fn.argtypes = C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int]
+    hs = (C.c_void_p * len(batches))(*[b._h for b in batches])
+    if fn(hs, len(batches), stream, 1 if timed else 0) != JXL_DEC_SUCCESS:
+        raise GenericError(last_error())
+
+
 def lf_part_size(data: bytes) -> int:
     """The number of leading bytes of the file that hold the LF part of its first frame: data[:n] is the shortest prefix the 1:8 decode (downscale=8) and a DC-only
     decode (jpeg_scale=8, BatchDecoder.jpeg_dc_only) accept.  From the headers and the TOC, so a prefix that holds those gives the same answer; DecodeError
@@ -1401,5 +1412,7 @@ class Pipeline:
 
     def set_option(self, name: str, value: int):
         """Options for the jobs submitted from now on (include/jxl_hip.h JxlHipPipelineSetOption): "jpeg_region" = 1 — libjpeg-exact jobs decode only the groups the
-        crops of their outputs need (BatchDecoder.jpeg_region); info("hf_groups_decoded") / info("hf_groups_total") of the job prepared last."""
+        crops of their outputs need (BatchDecoder.jpeg_region); info("hf_groups_decoded") / info("hf_groups_total") of the job prepared last.  "lf_group_max" (1 .. 8):
+        jobs that are ready together share one SIMT LF launch, at most this many; "lf_streams_effective": LF streams in use (0: sized to the hardware queues);
+        info("lf_groups") / info("lf_grouped_jobs") / info("lf_group_largest") count the launches since the last reset_clock()."""
         libjxl().JxlHipPipelineSetOption(self._h, name.encode(), int(value))

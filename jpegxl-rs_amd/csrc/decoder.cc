@@ -2392,15 +2392,18 @@ static void CheckLaunches(const char* what) {
 // caller can record an event behind it (bench.py starts the LF stage of a later batch when an HF stage has ended, not when it starts); the LF decode apart from the LF
 // post-processing, whose kernels wait for wavefront slots beside the pixel kernels of the batch before and which only the IDCT and the filters need; the IDCT apart
 // from the pixel stage, so that a caller that rotates coefficient sets lets the next HF stage of that set start behind it.
-void Batch::RunPart(void* stream_v, DecodePart part, bool timed) {
-  if (!prepared_) Prepare(stream_v);
-  // (whatever an earlier runtime call of this thread left unread is not this decode's — it is named on stderr once, not silently dropped, and then cleared so that
-  // the checks behind this part's launches report this part's launches only)
+// (whatever an earlier runtime call of this thread left unread is not this decode's — it is named on stderr once, not silently dropped, and then cleared so that
+// the checks behind this part's launches report this part's launches only)
+static void ClearStaleLaunchError() {
   if (const hipError_t stale = hipPeekAtLastError()) {
     static std::atomic<bool> told{false};
     if (!told.exchange(true)) fprintf(stderr, "[jxl-hip] a HIP error left pending by an earlier call on this thread (not by this decode) is being cleared: %s\n", hipGetErrorString(stale));
     (void)hipGetLastError();
   }
+}
+void Batch::RunPart(void* stream_v, DecodePart part, bool timed) {
+  if (!prepared_) Prepare(stream_v);
+  ClearStaleLaunchError();
   if (any_vardct_) CheckFilterBuffers();
   const PartPlan plan = PlanOf(part);
   const bool tail = plan.has(kStageIdct) || plan.has(kStagePixels);
@@ -2428,19 +2431,61 @@ void Batch::RecordMark(const PartRun& r, Mark m) {
   HIP_CHECK(hipEventRecord(ev, (hipStream_t)r.stream));
 }
 
-void Batch::StageLf(const PartRun& r) {
-  const int n = (int)images_.size();
+void Batch::StageLfBegin(const PartRun& r) {
   RecordMark(r, kMarkLfStart);
   DebugSync("start", r.stream);
-  if (any_modchan_) LaunchModularGlobal(dframes_, n, cfg, r.stream);   // Modular frames; extra channels of VarDCT frames
+  if (any_modchan_) LaunchModularGlobal(dframes_, (int)images_.size(), cfg, r.stream);   // Modular frames; extra channels of VarDCT frames
   DebugSync("modular global", r.stream);
+}
+void Batch::StageLfRest(const PartRun& r, bool simt_launched) {
+  const int n = (int)images_.size();
   cfg.lf_head_start = r.plan.lf_head_start;
+  cfg.lf_simt_launched = simt_launched ? 1 : 0;
   if (any_vardct_) LaunchLfDecode(dframes_, n, max_lf_groups_, cfg, r.stream, &lf_simt_, &trace_);
-  cfg.lf_wide_once = 0;
+  cfg.lf_wide_once = 0; cfg.lf_simt_launched = 0;
   DebugSync("LF decode", r.stream);
   CheckLaunches("LF stage");
   if (any_vardct_ && !cfg.idct_flags_known && r.plan.split && !cfg.no_flag_wait) EnqueueFlagReadback(r.stream);
   RecordMark(r, kMarkLfEnd);
+}
+
+LfGroupKey Batch::LfKey() const {
+  LfGroupKey k;
+  const LfSimtShape s = LfSimtShapeOf(cfg, &lf_simt_);
+  k.eligible = prepared_ && any_vardct_ && !any_modchan_ && !lf_batch_ && !cfg.any_local_lf && s.kernel != kLfSimtNone;
+  k.kernel = s.kernel * 4 + (int)s.spec_shift; k.lanes_per_wave = s.lanes_per_wave; k.lf_flags = s.lf_flags;
+  return k;
+}
+
+void Batch::RunLfGroup(Batch* const* batches, int n, void* stream, bool timed, const std::function<void(int)>& after) {
+  if (n < 1 || !batches || !batches[0]) throw ParseError("LF group: no batch", false);
+  if (n == 1) { batches[0]->RunPart(stream, kPartLf, timed); if (after) after(0); return; }
+  if (n > kLfGroupMax) throw ParseError("LF group: more batches than a launch has parts", false);
+  const LfGroupKey key = batches[0]->LfKey();
+  for (int i = 0; i < n; i++) {
+    if (!batches[i] || batches[i]->device_ != batches[0]->device_) throw ParseError("LF group: batches of different devices", false);
+    for (int k = 0; k < i; k++) if (batches[k] == batches[i]) throw ParseError("LF group: a batch appears twice", false);
+    const LfGroupKey ki = batches[i]->LfKey();
+    if (!ki.eligible || !(ki == key)) throw ParseError("LF group: batches whose SIMT LF launches cannot be shared", false);
+  }
+  ClearStaleLaunchError();
+  const PartPlan plan = PlanOf(kPartLf);
+  const LfSimtShape shape = LfSimtShapeOf(batches[0]->cfg, &batches[0]->lf_simt_);
+  PartRun runs[kLfGroupMax];
+  LfSimtGroupPart parts[kLfGroupMax];
+  for (int i = 0; i < n; i++) {
+    Batch& b = *batches[i];
+    b.CheckFilterBuffers();
+    if (timed) b.timed_events_.emplace_back(kNumMarks, nullptr);      // (the LF stage opens a row of events: RunPart)
+    runs[i] = PartRun{stream, plan, timed, timed ? &b.timed_events_.back() : nullptr};
+    b.StageLfBegin(runs[i]);
+    parts[i] = LfSimtGroupPart{b.dframes_, &b.lf_simt_};
+  }
+  LaunchLfSimtGroup(parts, n, shape, stream);
+  for (int i = 0; i < n; i++) {
+    batches[i]->StageLfRest(runs[i], /*simt_launched=*/true);
+    if (after) after(i);
+  }
 }
 
 // A caller that enqueues the stages separately: the placement flags travel to pinned host memory behind the LF stage, and the tail —

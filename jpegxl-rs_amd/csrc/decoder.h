@@ -313,6 +313,14 @@ class Batch {
   // all recorded runs and returns the per-stage sums (ms) and the number of runs; used by bench.py for the roofline.
   void RunTimed(void* stream);
   void RunPart(void* stream, DecodePart part, bool timed);   // parts: decode_parts.h; the libjpeg-exact flavours come after PlanJpegPixels
+  // The LF stage (kPartLf) of several prepared batches on one stream, their SIMT LF kernels as ONE launch (kernels.h LaunchLfSimtGroup).  LfKey: what the batch's next LF stage
+  // launches, as lf_group_plan.h compares it (cfg as it stands: lf_wide_once, lf_spec_lanes); eligible are plain VarDCT batches — no Modular channels, no LF frames, no LF groups
+  // with trees of their own — whose SIMT plan is not overridden by the wide launch.  RunLfGroup takes one group of PlanLfGroups: n = 1 is RunPart(kPartLf) — exactly those
+  // launches —, n > 1 (equal eligible keys, one device; anything else throws) opens every member's timing bracket, launches the kernel once and then runs, member by member in
+  // order, what follows it (LfDecodeKernel for handed-back streams, placement, the flag read-back), with after(i) behind member i.  So the group kernel's time lies inside
+  // every member's "lf" bracket.
+  LfGroupKey LfKey() const;
+  static void RunLfGroup(Batch* const* batches, int n, void* stream, bool timed, const std::function<void(int)>& after = nullptr);
   StageTimes CollectTimes(int* runs);
   void DebugTimeline(void* ref_event, float out[kNumMarks]);
   // ALGORITHMIC bytes per stage for one Run of the batch: 0 lf, 1 lfpost, 2 hf, 3 idct, 4 filters, 5 out
@@ -511,7 +519,9 @@ class Batch {
   // ---- RunPart: one function per stage of the part (decode_parts.h), over what the call shares
   struct PartRun { void* stream; PartPlan plan; bool timed; vec<void*>* marks; };
   void RecordMark(const PartRun& r, Mark m);
-  void StageLf(const PartRun& r); void StageLfPost(const PartRun& r); void StageHf(const PartRun& r); void StageIdct(const PartRun& r); void StagePixels(const PartRun& r);
+  void StageLf(const PartRun& r) { StageLfBegin(r); StageLfRest(r, false); }
+  void StageLfBegin(const PartRun& r); void StageLfRest(const PartRun& r, bool simt_launched);      // (between the two: the batch's SIMT LF launch, or the grouped one that takes it along)
+  void StageLfPost(const PartRun& r); void StageHf(const PartRun& r); void StageIdct(const PartRun& r); void StagePixels(const PartRun& r);
   void EnqueueFlagReadback(void* stream); void WaitForIdctFlags(const PartRun& r);
   vec<vec<void*>> timed_events_;
   size_t timed_rest_cursor_ = 0;       // timed decodes run in parts (RunPart): which entry of timed_events_ the next "rest" part records into; CollectTimes starts it over

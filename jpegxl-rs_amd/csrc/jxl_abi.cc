@@ -1244,6 +1244,20 @@ JxlDecoderStatus JxlHipBatchDecodePart(JxlHipBatch* h, void* s, int part, int ti
   if (part < 0 || part >= kNumPublicParts) return JXL_DEC_ERROR;
   BATCH_TRY(h->b->RunPart(s, (DecodePart)part, timed != 0))
 }
+JxlDecoderStatus JxlHipBatchDecodeLfGrouped(JxlHipBatch* const* hs, int n, void* s, int timed) {
+  try {
+    if (!hs || n < 1) { SetLastError("JxlHipBatchDecodeLfGrouped: no batches"); return JXL_DEC_ERROR; }
+    std::vector<Batch*> batches;
+    std::vector<LfGroupKey> keys;
+    for (int i = 0; i < n; i++) {
+      if (!hs[i]) { SetLastError("JxlHipBatchDecodeLfGrouped: a NULL batch"); return JXL_DEC_ERROR; }
+      batches.push_back(hs[i]->b); keys.push_back(hs[i]->b->LfKey());      // (a batch that is not prepared is not eligible: RunPart prepares it, alone)
+    }
+    int at = 0;
+    for (int m : PlanLfGroups(keys.data(), n, kLfGroupMax)) { Batch::RunLfGroup(batches.data() + at, m, s, timed != 0); at += m; }
+    return JXL_DEC_SUCCESS;
+  } catch (const std::exception& e) { SetLastError(e.what()); return JXL_DEC_ERROR; }
+}
 JxlDecoderStatus JxlHipBatchCollectTimes(JxlHipBatch* h, JxlHipStageTimes* t, int* runs) {
   BATCH_TRY({ StageTimes st = h->b->CollectTimes(runs); t->lf_ms = st.lf_ms; t->lfpost_ms = st.lfpost_ms; t->hf_ms = st.hf_ms; t->idct_ms = st.idct_ms; t->filter_ms = st.filter_ms; t->out_ms = st.out_ms; t->total_ms = st.total_ms; })
 }
@@ -1557,7 +1571,7 @@ JxlDecoderStatus JxlHipPipelineCollectTimes(JxlHipPipeline* h, JxlHipStageTimes*
 void JxlHipPipelineStageBytes(JxlHipPipeline* h, uint64_t out[6]) { h->p->StageBytes(out); }
 void JxlHipPipelineSetOption(JxlHipPipeline* h, const char* name, int value) {
   if (!h || !name) return;
-  if (std::string(name) == "jpeg_region") h->p->SetJpegRegion(value != 0);
+  (void)h->p->SetOption(name, value);      // "jpeg_region", "lf_group_max", "lf_streams_effective"; unknown names are ignored
 }
 int64_t JxlHipPipelineGetInfo(JxlHipPipeline* h, const char* name) {
   try {

@@ -1,6 +1,7 @@
 // jxl-hip: device-side frame descriptor + kernel launch interface (implemented in kernels.hip).
 #pragma once
 #include "jxl_dev.h"
+#include "lf_group_plan.h"
 #if !defined(__HIPCC__)
 // host-only builds of the library's host sources (the sanitizer build, tests/test_sanitizers.py): the runtime API and the vector types, no device code
 #include <hip/hip_runtime_api.h>
@@ -165,7 +166,9 @@ struct LaunchCfg {
   // kernels for varblocks outside a 64x64 tile / the DCT128-256 family are only launched when some frame needs them
   int lf_wide_once = 0;              // the next LF launch takes the one-wavefront-per-stream kernel for every frame, SIMT-eligible or not (a pipeline that starts
                                      // on an idle GPU: 100 instead of 250 ms until the first batch can go on); reset by the launch
-  int lf_wp_narrow_test = 0;         // testing: the SIMT LF kernel's weighted-predictor lanes hand a stream back at |sample| > 16 instead of 2^20
+  int lf_simt_launched = 0;          // the batch's SIMT LF kernel went out already, as a part of a grouped launch (LaunchLfSimtGroup): LaunchLfDecode runs what follows it only —
+                                     // LfDecodeKernel for handed-back streams and legacy frames, the placement kernels; reset by the caller
+  int lf_wp_narrow_test = 0;        // testing: the SIMT LF kernel's weighted-predictor lanes hand a stream back at |sample| > 16 instead of 2^20
   int lf_force_big = 0;              // testing: the launch shape of LfDecodeKernel (kernels.hip LaunchLfDecode)
   int lf_spec_lanes = 0;             // SIMT LF launches without the weighted predictor: lanes per stream, each with a candidate cluster whose alias slot it reads ahead (kernels.hip
                                      // LfDecodeSimtKernel SPEC).  0: kLfSpecLanesDefault; 1: the one-lane form; 2, 4, 8: that many — never more than 64 / lane_stride_lf leaves idle
@@ -230,6 +233,23 @@ struct LaunchTrace {
   int lf_wide_only = 0;         // the plain layout was left out (LdAliasAt puts entries together from the wide one)
   int lf_spec_lanes = 0;        // lanes per stream of the SIMT LF launch without the weighted predictor (1: the one-lane form); 0: no such launch
 };
+// One SIMT LF launch for several batches (pipeline.cc: the LF stages of the jobs that became ready while the LF stream was busy).  The kernel is latency-bound and uses
+// 64 of the chip's 1024 SIMDs for 256 frames: the parts of a launch run side by side, so M jobs cost one launch time.  A part is one batch's descriptors and the first
+// wavefront that works on them; the table is passed by value (kernel arguments).  Unused slots: first_wave = ~0.
+struct LfSimtPart { const FrameDev* frames; const LfSimtStream* streams; const LfSimtLane* lanes; const uint8_t* luts; uint32_t first_wave, num_lanes; };
+struct LfSimtPartTable { LfSimtPart part[kLfGroupMax]; };
+// What LaunchLfDecode decides about a batch's SIMT launch: batches with equal shapes can share one (lf_group_plan.h LfGroupKey).
+enum : int { kLfSimtNone = 0, kLfSimtWpQuad, kLfSimtWp, kLfSimtGen, kLfSimtLean };
+struct LfSimtShape {
+  int kernel = kLfSimtNone;      // kLfSimtNone: no SIMT launch (no plan, or the wide one-wavefront-per-stream launch takes every frame)
+  uint32_t spec_shift = 0;       // log2 of the candidate lanes per stream (kLfSimtGen / kLfSimtLean)
+  uint32_t lanes_per_wave = 0;   // streams a wavefront carries (quads: at most 16)
+  int lf_flags = 0, waves_per_wg = 1;
+};
+LfSimtShape LfSimtShapeOf(const LaunchCfg& cfg, const LfSimtPlan* simt);
+struct LfSimtGroupPart { const FrameDev* frames; const LfSimtPlan* simt; };
+// The SIMT kernel of `shape` over n <= kLfGroupMax batches that all have that shape; every part starts at a workgroup boundary.
+void LaunchLfSimtGroup(const LfSimtGroupPart* parts, int n, const LfSimtShape& shape, void* stream);
 int64_t LfSpecStats(int which);   // JXL_HIP_LF_SPEC_STATS: samples of this device's candidate-lane LF launches so far whose cluster was a candidate (0) / was not (1); -1 without the variable
 
 // VarDCT stages.  max_* are maxima over the batch (grid sizing); nframes = frames in batch.  trace: filled with the kernels launched (nullptr: not recorded).

@@ -2776,18 +2776,29 @@ template <int SHIFT> __device__ __forceinline__ uint32_t GroupOr(uint32_t v) {  
   if constexpr (SHIFT >= 3) v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true);     // row_half_mirror: the other quad of the eight
   return v;
 }
-template <bool WP, bool GEN, bool QUAD = false, int SPEC = 0> __global__ __launch_bounds__(256, WP ? 4 : (GEN || SPEC ? 6 : 7)) void LfDecodeSimtKernel(const FrameDev* __restrict__ frames, const LfSimtStream* __restrict__ streams, const LfSimtLane* __restrict__ lanes,
-                                                          const uint8_t* __restrict__ luts, uint32_t num_lanes, uint32_t lanes_per_wave, int high_priority, const uint32_t* __restrict__ s_div,
+// One launch serves the LF stages of up to kLfGroupMax batches (`table`, kernel arguments: nothing to keep alive): a wavefront finds its part from its wave index — wave-uniform,
+// scalar registers — and from there on runs over that part's frames, streams, lanes and tables as a launch for that batch alone would.  Slots behind the last part start at wave ~0.
+template <bool WP, bool GEN, bool QUAD = false, int SPEC = 0> __global__ __launch_bounds__(256, WP ? 4 : (GEN || SPEC ? 6 : 7)) void LfDecodeSimtKernel(const LfSimtPartTable table, uint32_t lanes_per_wave, int high_priority, const uint32_t* __restrict__ s_div,
                                                           unsigned long long* __restrict__ spec_stats) {
   static_assert(!QUAD || WP, "quads only pay for the weighted predictor");
   static_assert(SPEC >= 0 && SPEC <= 3 && (!SPEC || !WP), "candidate lanes: the launches without the weighted predictor, up to eight per stream");
+  const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  uint32_t pi = 0;        // (first_wave ascends over the parts in use; at most kLfGroupMax - 1)
+#pragma unroll
+  for (int p = 1; p < kLfGroupMax; p++) pi += wave >= table.part[p].first_wave ? 1u : 0u;
+  const LfSimtPart& mine = table.part[pi];
+  const FrameDev* __restrict__ frames = mine.frames;
+  const LfSimtStream* __restrict__ streams = mine.streams;
+  const LfSimtLane* __restrict__ lanes = mine.lanes;
+  const uint8_t* __restrict__ luts = mine.luts;
+  const uint32_t first_wave = mine.first_wave, num_lanes = mine.num_lanes;
   const uint32_t lane_in_wave = QUAD ? (threadIdx.x & 63) >> 2 : (threadIdx.x & 63) >> SPEC;
   const uint32_t q = QUAD ? threadIdx.x & 3 : 0;              // which sub-predictor this lane owns
   constexpr uint32_t gmask = (1u << SPEC) - 1;
   const bool writer = !SPEC || (threadIdx.x & gmask) == 0;    // SPEC: lane 0 of its group
   uint32_t my_cand = 0;                                       // SPEC: this lane's candidate cluster (bits 24-31) and its hybrid-integer configuration (bits 0-23)
   uint32_t turn = (0u - threadIdx.x) & gmask;                 // bits 0-2: misses until this lane takes the missed cluster (round robin: 0 in one lane of the group at a time); from bit 3: the stream's misses
-  const uint32_t li = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * lanes_per_wave + lane_in_wave;
+  const uint32_t li = (wave - first_wave) * lanes_per_wave + lane_in_wave;
   if (lane_in_wave >= lanes_per_wave || li >= num_lanes) return;
   if (high_priority & 1) __builtin_amdgcn_s_setprio(3);
   const int xp = high_priority;     // experiments (JXL_HIP_LF_PRIO bits 2, 4: drop the sample stores / the row-above prefetch — wrong pixels, timing only)
@@ -6099,6 +6110,59 @@ int64_t LfSpecStats(int which) {
   return (int64_t)v[which];
 }
 static void PlanModularLds(const LaunchCfg& cfg, uint32_t* nwaves_io, uint32_t* tree_cap, uint32_t* lds_tables, uint32_t* wp_base, uint32_t* lds_total);
+LfSimtShape LfSimtShapeOf(const LaunchCfg& cfg, const LfSimtPlan* simt) {
+  LfSimtShape s;
+  static const bool wide_wp = getenv("JXL_HIP_WIDE_WP") != nullptr;       // experiments
+  const bool wide = cfg.lf_wide_once && (wide_wp || !(simt && simt->num_lanes && simt->any_wp));
+  if (!simt || !simt->num_lanes || wide) return s;
+  static const int lf_prio = getenv("JXL_HIP_LF_PRIO") ? atoi(getenv("JXL_HIP_LF_PRIO")) : 0;
+  static const int wpb_env = getenv("JXL_HIP_LF_WAVES_PER_WG") ? atoi(getenv("JXL_HIP_LF_WAVES_PER_WG")) : 1;
+  static const bool no_quad = getenv("JXL_HIP_LF_NOQUAD") != nullptr;      // A/B: the one-lane-per-stream weighted-predictor instantiation
+  const uint32_t lpw = std::min(64u, std::max(1u, simt->lanes_per_wave));
+  s.waves_per_wg = std::max(1, std::min(4, wpb_env));
+  s.lf_flags = lf_prio | (cfg.lf_wp_narrow_test ? 8 : 0);
+  s.lanes_per_wave = lpw;
+  if (simt->any_wp && !no_quad) { s.kernel = kLfSimtWpQuad; s.lanes_per_wave = std::min(16u, lpw); }     // four lanes per stream: at most 16 streams per wavefront
+  else if (simt->any_wp) s.kernel = kLfSimtWp;
+  else {
+    // candidate lanes (LfDecodeSimtKernel SPEC): G lanes per stream out of those the packing leaves idle; the wavefronts of the launch stay the same
+    static const int spec_env = getenv("JXL_HIP_LF_SPEC_LANES") ? atoi(getenv("JXL_HIP_LF_SPEC_LANES")) : 0;      // A/B where no LaunchCfg is at hand (pipelines): as lf_spec_lanes
+    const int want = cfg.lf_spec_lanes ? cfg.lf_spec_lanes : spec_env;
+    const uint32_t room = 64u / lpw;                                                 // (lpw is a power of two: 64 / lane_stride_lf)
+    const uint32_t G = std::min(room, want == 1 || want == 2 || want == 4 || want == 8 ? (uint32_t)want : kLfSpecLanesDefault);
+    s.spec_shift = G >= 8 ? 3u : G >= 4 ? 2u : G >= 2 ? 1u : 0u;
+    s.kernel = simt->any_general ? kLfSimtGen : kLfSimtLean;
+  }
+  return s;
+}
+void LaunchLfSimtGroup(const LfSimtGroupPart* parts, int n, const LfSimtShape& shape, void* stream) {
+  if (n < 1 || n > kLfGroupMax || shape.kernel == kLfSimtNone) return;
+  const uint32_t lpw = shape.lanes_per_wave, wpb = (uint32_t)shape.waves_per_wg;
+  LfSimtPartTable table;
+  uint32_t waves = 0;
+  for (int p = 0; p < kLfGroupMax; p++) {
+    LfSimtPart& t = table.part[p];
+    if (p >= n) { t = LfSimtPart{nullptr, nullptr, nullptr, nullptr, ~0u, 0u}; continue; }
+    const LfSimtPlan* simt = parts[p].simt;
+    t = LfSimtPart{parts[p].frames, simt->streams, simt->lanes, simt->luts, waves, simt->num_lanes};
+    waves += DivUp(DivUp(simt->num_lanes, lpw), wpb) * wpb;      // the next part starts at a workgroup boundary
+  }
+  const dim3 grid(waves / wpb), block(64 * wpb);
+  const uint32_t* wp_div = WpDivTable();
+  unsigned long long* stats = shape.spec_shift ? LfSpecStatsWords() : nullptr;
+  const uint32_t shift = shape.spec_shift;
+  if (shape.kernel == kLfSimtWpQuad) hipLaunchKernelGGL((LfDecodeSimtKernel<true, true, true>), grid, block, 0, (hipStream_t)stream, table, lpw, shape.lf_flags, wp_div, nullptr);
+  else if (shape.kernel == kLfSimtWp) hipLaunchKernelGGL((LfDecodeSimtKernel<true, true>), grid, block, 0, (hipStream_t)stream, table, lpw, shape.lf_flags, wp_div, nullptr);
+  else {
+#define JXL_LF_SIMT_LAUNCH(GEN, SPEC) hipLaunchKernelGGL((LfDecodeSimtKernel<false, GEN, false, SPEC>), grid, block, 0, (hipStream_t)stream, table, lpw, shape.lf_flags, wp_div, stats)
+    if (shape.kernel == kLfSimtGen) {
+      if (shift == 3) JXL_LF_SIMT_LAUNCH(true, 3); else if (shift == 2) JXL_LF_SIMT_LAUNCH(true, 2); else if (shift == 1) JXL_LF_SIMT_LAUNCH(true, 1); else JXL_LF_SIMT_LAUNCH(true, 0);
+    } else {
+      if (shift == 3) JXL_LF_SIMT_LAUNCH(false, 3); else if (shift == 2) JXL_LF_SIMT_LAUNCH(false, 2); else if (shift == 1) JXL_LF_SIMT_LAUNCH(false, 1); else JXL_LF_SIMT_LAUNCH(false, 0);
+    }
+#undef JXL_LF_SIMT_LAUNCH
+  }
+}
 void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, const LaunchCfg& cfg, void* stream, const LfSimtPlan* simt, LaunchTrace* trace) {
   LaunchTrace tr;
   if (!trace) trace = &tr;
@@ -6135,46 +6199,15 @@ void LaunchLfDecode(const FrameDev* frames, int nframes, int max_lf_groups, cons
   // this launch: one wavefront per stream for every frame (shorter latency, the whole GPU's SIMDs) — not for batches whose SIMT launch is the weighted-predictor
   // instantiation: per stream the lane-serial form is the faster one there (1.5 against 2.8 us per sample), four of these wide launches at the start of a cold
   // pipeline took 1.0-2.3 s each (profiles/r04_notes.md)
-  static const bool wide_wp = getenv("JXL_HIP_WIDE_WP") != nullptr;       // experiments
   static const int force_big_env = getenv("JXL_HIP_LF_FORCE_BIG") ? atoi(getenv("JXL_HIP_LF_FORCE_BIG")) : 0;
-  const int wide = cfg.lf_wide_once && (wide_wp || !(simt && simt->num_lanes && simt->any_wp));
+  const LfSimtShape shape = LfSimtShapeOf(cfg, simt);
+  const int wide = cfg.lf_wide_once && shape.kernel == kLfSimtNone;
   int simt_mode = wide ? 1 : 0;           // LfDecodeKernel's take_simt_frames: 0 legacy frames only, 1 every frame, 2 legacy frames + the streams the SIMT kernel handed back
-  if (simt && simt->num_lanes && !wide) {
-    // SIMT frames: the entropy decode on a handful of wavefronts (one stream per lane)
-    const uint32_t lpw = std::min(64u, std::max(1u, simt->lanes_per_wave));
-    static const int lf_prio = getenv("JXL_HIP_LF_PRIO") ? atoi(getenv("JXL_HIP_LF_PRIO")) : 0;
-    static const int wpb_env = getenv("JXL_HIP_LF_WAVES_PER_WG") ? atoi(getenv("JXL_HIP_LF_WAVES_PER_WG")) : 1;
-    const int nwaves = DivUp((int)simt->num_lanes, (int)lpw), wpb = std::max(1, std::min(4, wpb_env));
-    const int lf_flags = lf_prio | (cfg.lf_wp_narrow_test ? 8 : 0);
-    const dim3 grid(DivUp(nwaves, wpb)), block(64 * wpb);
-    const uint32_t* wp_div = WpDivTable();
-    static const bool no_quad = getenv("JXL_HIP_LF_NOQUAD") != nullptr;      // A/B: the one-lane-per-stream weighted-predictor instantiation
-    if (simt->any_wp && !no_quad) {
-      // four lanes per stream: at most 16 streams per wavefront
-      const uint32_t lpq = std::min(16u, lpw);
-      const int nwq = DivUp((int)simt->num_lanes, (int)lpq);
-      hipLaunchKernelGGL((LfDecodeSimtKernel<true, true, true>), dim3(DivUp(nwq, wpb)), block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpq, lf_flags, wp_div, nullptr);
-      trace->lf_variant |= kLfVarSimtWpQuad;
-    } else if (simt->any_wp) { hipLaunchKernelGGL((LfDecodeSimtKernel<true, true>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div, nullptr); trace->lf_variant |= kLfVarSimtWp; }
-    else {
-      // candidate lanes (LfDecodeSimtKernel SPEC): G lanes per stream out of those the packing leaves idle; the wavefronts of the launch stay the same
-      static const int spec_env = getenv("JXL_HIP_LF_SPEC_LANES") ? atoi(getenv("JXL_HIP_LF_SPEC_LANES")) : 0;      // A/B where no LaunchCfg is at hand (pipelines): as lf_spec_lanes
-      const int want = cfg.lf_spec_lanes ? cfg.lf_spec_lanes : spec_env;
-      const uint32_t room = 64u / lpw;                                                 // (lpw is a power of two: 64 / lane_stride_lf)
-      const uint32_t G = std::min(room, want == 1 || want == 2 || want == 4 || want == 8 ? (uint32_t)want : kLfSpecLanesDefault);
-      const uint32_t shift = G >= 8 ? 3u : G >= 4 ? 2u : G >= 2 ? 1u : 0u;
-      unsigned long long* stats = shift ? LfSpecStatsWords() : nullptr;
-      trace->lf_spec_lanes = 1 << shift;
-#define JXL_LF_SIMT_LAUNCH(GEN, SPEC) hipLaunchKernelGGL((LfDecodeSimtKernel<false, GEN, false, SPEC>), grid, block, 0, (hipStream_t)stream, frames, simt->streams, simt->lanes, simt->luts, simt->num_lanes, lpw, lf_flags, wp_div, stats)
-      if (simt->any_general) {
-        if (shift == 3) JXL_LF_SIMT_LAUNCH(true, 3); else if (shift == 2) JXL_LF_SIMT_LAUNCH(true, 2); else if (shift == 1) JXL_LF_SIMT_LAUNCH(true, 1); else JXL_LF_SIMT_LAUNCH(true, 0);
-        trace->lf_variant |= kLfVarSimtGen;
-      } else {
-        if (shift == 3) JXL_LF_SIMT_LAUNCH(false, 3); else if (shift == 2) JXL_LF_SIMT_LAUNCH(false, 2); else if (shift == 1) JXL_LF_SIMT_LAUNCH(false, 1); else JXL_LF_SIMT_LAUNCH(false, 0);
-        trace->lf_variant |= kLfVarSimtLean;
-      }
-#undef JXL_LF_SIMT_LAUNCH
-    }
+  if (shape.kernel != kLfSimtNone) {
+    // SIMT frames: the entropy decode on a handful of wavefronts (one stream per lane) — unless a grouped launch took this batch along already
+    if (!cfg.lf_simt_launched) { const LfSimtGroupPart one{frames, simt}; LaunchLfSimtGroup(&one, 1, shape, stream); }
+    trace->lf_variant |= shape.kernel == kLfSimtWpQuad ? kLfVarSimtWpQuad : shape.kernel == kLfSimtWp ? kLfVarSimtWp : shape.kernel == kLfSimtGen ? kLfVarSimtGen : kLfVarSimtLean;
+    if (shape.kernel == kLfSimtGen || shape.kernel == kLfSimtLean) trace->lf_spec_lanes = 1 << shape.spec_shift;
     if (!simt->any_legacy && !simt->any_wp) { place(); return; }
     simt_mode = simt->any_wp ? 2 : 0;         // the weighted-predictor lanes may hand streams back: LfDecodeKernel follows for those (and for the legacy frames)
   }

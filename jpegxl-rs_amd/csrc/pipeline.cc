@@ -1,5 +1,5 @@
-// jxl-hip: streaming decode pipeline of one GPU (pipeline.h).  Threads: `prepare_threads` workers (parse, tables, upload, LF stage), one issuer (HF stages and
-// tails in submission order); Submit / Wait are called by anybody.  All GPU work goes to non-blocking streams of the object's own; nothing touches the NULL stream.
+// jxl-hip: streaming decode pipeline of one GPU (pipeline.h).  Threads: `prepare_threads` workers (parse, tables, upload), one LF issuer (LF stages in submission
+// order, jobs that are ready together as one launch), one issuer (HF stages and tails in submission order); Submit / Wait are called by anybody.  All GPU work goes to non-blocking streams of the object's own; nothing touches the NULL stream.
 #include "pipeline.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -57,9 +57,19 @@ Pipeline::Pipeline(int device, const PipelineOptions& opt) : device_(device), op
   int prio_least = 0, prio_high = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_high);   // (numerically lower = higher priority)
   prio_high = std::min(prio_high, 0);
+  prio_high_ = prio_high;
   main_ = NewStream(0);
   d2h_[0] = NewStream(0); d2h_[1] = NewStream(0);
-  for (int i = 0; i < opt_.lf_streams; i++) lf_side_.push_back(NewStream(prio_high));
+  upload_ = NewStream(0);      // (high priority, among the entropy streams' queues, measured the same: profiles/r08_notes.md)
+  // LF streams: as many as the hardware queues leave room for (streams that share a queue serialise: eleven LF streams over four queues ran four LF launches at a time
+  // and held up the HF stages queued behind them).  JXL_HIP_LF_GROUP_MAX / JXL_HIP_LF_STREAMS_EFFECTIVE: the two options for A/B runs; at creation the environment
+  // takes precedence over the options structure, SetOption afterwards over both
+  if (const char* e = getenv("JXL_HIP_LF_GROUP_MAX")) opt_.lf_group_max = atoi(e);
+  if (const char* e = getenv("JXL_HIP_LF_STREAMS_EFFECTIVE")) opt_.lf_streams_effective = atoi(e);
+  lf_group_max_ = std::max(1, std::min(opt_.lf_group_max, kLfGroupMax));
+  lf_streams_effective_ = std::max(0, std::min(opt_.lf_streams_effective, opt_.lf_streams));
+  lf_side_.reserve(32); lf_side_done_.reserve(32);      // (they grow under mu_ and never move)
+  for (int i = 0, n = LfStreamsInUse(); i < n; i++) { lf_side_.push_back(NewStream(prio_high)); lf_side_done_.push_back(nullptr); }
   for (int i = 0; i < opt_.hf_streams; i++) hf_side_.push_back(NewStream(prio_high));
   clock_event_ = NewEvent(true);
   Record(clock_event_, main_);
@@ -67,7 +77,7 @@ Pipeline::Pipeline(int device, const PipelineOptions& opt) : device_(device), op
   for (int b = 0; b < nbuf_; b++) {
     std::unique_ptr<Slot> s(new Slot());
     s->batch.reset(new Batch(device_));
-    s->lf_done = NewEvent(); s->front_done = NewEvent(); s->hf_done = NewEvent(); s->idct_done = NewEvent(); s->rest_done = NewEvent();
+    s->uploaded = NewEvent(); s->lf_done = NewEvent(); s->front_done = NewEvent(); s->hf_done = NewEvent(); s->idct_done = NewEvent(); s->rest_done = NewEvent();
     slots_.push_back(std::move(s));
   }
   if (opt_.reserve_frames > 0 && opt_.reserve_width > 0 && opt_.reserve_height > 0) {
@@ -80,15 +90,33 @@ Pipeline::Pipeline(int device, const PipelineOptions& opt) : device_(device), op
     for (auto& c : coef_) ReservePlanes(&c, want_coef_);
   }
   for (int w = 0; w < opt_.prepare_threads; w++) workers_.emplace_back([this, w] { PrepareWorker(w); });
+  lf_issuer_ = std::thread([this] { LfIssuerLoop(); });
   issuer_ = std::thread([this] { IssuerLoop(); });
+}
+
+int Pipeline::LfStreamsInUse() const {
+  const int v = lf_streams_effective_.load();
+  return v > 0 ? std::min(v, opt_.lf_streams) : LfStreamsForQueues(opt_.lf_streams, opt_.hf_streams, getenv("GPU_MAX_HW_QUEUES"));
+}
+
+bool Pipeline::SetOption(const std::string& name, int value) {
+  if (name == "jpeg_region") SetJpegRegion(value != 0);
+  else if (name == "lf_group_max") lf_group_max_ = std::max(1, std::min(value, kLfGroupMax));
+  else if (name == "lf_streams_effective") lf_streams_effective_ = std::max(0, std::min(value, opt_.lf_streams));
+  else return false;
+  return true;
 }
 
 Pipeline::~Pipeline() {
   { std::lock_guard<std::mutex> lock(mu_); shutdown_ = true; }
   cv_.notify_all();
   for (auto& t : workers_) t.join();
+  if (lf_issuer_.joinable()) lf_issuer_.join();
   if (issuer_.joinable()) issuer_.join();
+  if (getenv("JXL_HIP_SCHED_TRACE"))
+    fprintf(stderr, "[pipe] LF launches since the clock was reset: %lld for %lld jobs, largest group %lld, %d LF streams in use\n", (long long)lf_groups_, (long long)lf_grouped_jobs_, (long long)lf_group_largest_, LfStreamsInUse());
   DeviceScope scope(device_);
+  (void)hipStreamSynchronize((hipStream_t)upload_);
   for (void* s : lf_side_) (void)hipStreamSynchronize((hipStream_t)s);
   for (void* s : hf_side_) (void)hipStreamSynchronize((hipStream_t)s);
   (void)hipStreamSynchronize((hipStream_t)main_);
@@ -98,14 +126,16 @@ Pipeline::~Pipeline() {
   for (auto& s : slots_) {
     if (s->finish_stream) { (void)hipStreamSynchronize((hipStream_t)s->finish_stream); (void)hipStreamDestroy((hipStream_t)s->finish_stream); }
     s->batch.reset();
-    for (void* e : {s->lf_done, s->front_done, s->hf_done, s->idct_done, s->rest_done}) if (e) (void)hipEventDestroy((hipEvent_t)e);
+    for (void* e : {s->uploaded, s->lf_done, s->front_done, s->hf_done, s->idct_done, s->rest_done}) if (e) (void)hipEventDestroy((hipEvent_t)e);
   }
   slots_.clear();
   if (big_.p) DeviceArenaGive(big_.p, big_.cap, device_);
   for (auto& c : coef_) if (c.p) DeviceArenaGive(c.p, c.cap, device_);
   if (clock_event_) (void)hipEventDestroy((hipEvent_t)clock_event_);
+  for (void* e : lf_side_done_) if (e) (void)hipEventDestroy((hipEvent_t)e);
   for (void* s : lf_side_) (void)hipStreamDestroy((hipStream_t)s);
   for (void* s : hf_side_) (void)hipStreamDestroy((hipStream_t)s);
+  (void)hipStreamDestroy((hipStream_t)upload_);
   (void)hipStreamDestroy((hipStream_t)main_);
   for (void* s : d2h_) (void)hipStreamDestroy((hipStream_t)s);
 }
@@ -246,7 +276,7 @@ void Pipeline::PrepareWorker(int worker) {
       }
     }
     PrepareJob(job.get(), worker);
-    { std::lock_guard<std::mutex> lock(mu_); job->state = kFrontIssued; if (job->wide_chain) wide_enqueued_ = std::max(wide_enqueued_, job->ticket); /* (also when its prepare failed: the job behind it must not wait for ever) */ }
+    { std::lock_guard<std::mutex> lock(mu_); job->state = kPrepared; /* (also when its prepare failed: the LF issuer passes it on) */ }
     cv_.notify_all();
   }
 }
@@ -329,9 +359,8 @@ void Pipeline::PrepareJob(Job* j, int worker) {
       else if (n <= 96) { bt.cfg.hf_lanes_per_wave = 4; bt.cfg.hf_lanes_per_wg = 64; }
     }
     bt.UseSharedPlanes(&big_, &coef_[(size_t)(j->ticket % ncoef_)]);
-    // tables + upload go to the stream the job's LF stage runs on, which follows without a host-side wait (an upload stream of its own was seen waiting tens of
-    // milliseconds behind other streams' entropy kernels)
-    void* side = lf_side_[(size_t)(j->ticket % (int64_t)lf_side_.size())];
+    // tables + upload start at once, on the upload stream: the job's LF stage — enqueued by the LF issuer, perhaps with other jobs' — waits for `uploaded` on the device
+    void* side = upload_;
     bt.Prepare(side, /*wait_upload=*/false);
     size_t jpeg_table = 0;
     if (files) {
@@ -373,39 +402,121 @@ void Pipeline::PrepareJob(Job* j, int worker) {
       last_info_["total_pixels"] = (int64_t)bt.total_pixels();
       last_info_["frames"] = (int64_t)bt.size();
     }
-    // the LF stage goes out right away, from this thread: the earlier it starts the better
+    // the first LF stages of a cold pipeline, and small jobs, take the one-wavefront-per-stream kernel (read by the LF issuer: such a job never shares a launch)
     if (j->cold_wide && opt_.lane_stride_lf < 64) bt.cfg.lf_wide_once = 1;
-    // (jobs whose LF trees use the weighted predictor keep the SIMT kernel whatever lf_wide_once says — LaunchLfDecode —: 420 ms a launch, nothing to chain)
-    static const bool wide_wp = getenv("JXL_HIP_WIDE_WP") != nullptr;       // experiments (kernels.hip LaunchLfDecode)
-    const bool lf_wide = bt.cfg.lf_wide_once && (wide_wp || !bt.Info("lf_simt_wp"));
-    if (j->wide_chain) { std::lock_guard<std::mutex> lock(mu_); j->lf_wide = lf_wide; }
-    if (j->wide_after >= 0 && lf_wide) {
-      // behind the cold-start job before it: wait (host) until that job's LF stage is in its stream, then make ours wait for it (device)
-      std::unique_lock<std::mutex> lock(mu_);
-      cv_.wait(lock, [&] { return shutdown_ || wide_enqueued_ >= j->wide_after; });
-      auto it = jobs_.find(j->wide_after);
-      const bool chained = it != jobs_.end() && it->second->job_error.empty() && it->second->state < kHarvested && it->second->lf_wide;
-      lock.unlock();
-      if (chained) StreamWait(side, slots_[(size_t)(j->wide_after % nbuf_)]->lf_done);
-    }
-    const bool timed = opt_.timed != 0 && !files;   // (a reconstruction job has no pixel stages to bracket: its parts are not timed)
-    bt.RunPart(side, kPartLf, timed);           // LF decode + varblock placement: all the HF stage waits for
-    Record(s.lf_done, side);
-    if (j->wide_chain) { { std::lock_guard<std::mutex> lock(mu_); wide_enqueued_ = std::max(wide_enqueued_, j->ticket); } cv_.notify_all(); }
-    // LF post-processing: needed by the float IDCT and the filters only — the libjpeg-exact tail and the reconstruction's gather read lfq, the coefficient planes, block info and offsets, the
-    // chroma-from-luma maps: nothing LfDequantKernel, LfSmoothKernel, LlfSigmaKernel or LlfKernel write (lf, lf_tmp, llf, inv_sigma)
-    bt.RunPart(side, PartOf(kStageLfPost, j->kind != kPlain), timed);
-    Record(s.front_done, side);
+    Record(s.uploaded, side);
   } catch (const std::exception& e) {
     j->job_error = e.what();
     if (j->job_error.empty()) j->job_error = "prepare failed";
   }
   const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   static const bool trace = getenv("JXL_HIP_SCHED_TRACE") != nullptr;
-  if (trace) fprintf(stderr, "[pipe %.1f] job %lld (%d images, slot %d): prepare + LF enqueue %.1f ms (parse %.1f, prepare %.1f)%s%s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(),
+  if (trace) fprintf(stderr, "[pipe %.1f] job %lld (%d images, slot %d): prepare %.1f ms (parse %.1f, prepare %.1f)%s%s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(),
                      (long long)j->ticket, n, (int)(j->ticket % nbuf_), dt * 1e3, std::chrono::duration<double, std::milli>(t_parse - t0).count(), std::chrono::duration<double, std::milli>(t_prep - t_parse).count(), j->job_error.empty() ? "" : " ERROR ", j->job_error.c_str());
   std::lock_guard<std::mutex> lock(mu_);
   prepare_s_total_ += dt; prepared_jobs_++;
+}
+
+// The LF stages of every job, from one thread, in ticket order.  The thread takes the next LF stream round robin, waits (host) until the group before on that stream has
+// left the GPU, and then takes along every job that is ready by then and that PlanLfGroups puts into the first group: while streams are free every job leaves alone, the
+// moment it is prepared; when LF launches are the bottleneck the jobs that queued up meanwhile share one launch, which takes about as long as a launch for one of them.
+void Pipeline::LfIssuerLoop() {
+  (void)hipSetDevice(device_);
+  size_t turn = 0;
+  auto ready = [&](int64_t t) { auto it = jobs_.find(t); return it != jobs_.end() && it->second->state == kPrepared; };
+  for (;;) {
+    void* stream = nullptr; void* busy = nullptr;
+    {
+      std::unique_lock<std::mutex> lock(mu_);
+      cv_.wait(lock, [&] { return shutdown_ || ready(next_lf_); });
+      if (shutdown_) return;
+      const size_t in_use = (size_t)LfStreamsInUse();
+      try {
+        while (lf_side_.size() < in_use) { lf_side_.push_back(NewStream(prio_high_)); lf_side_done_.push_back(nullptr); }      // (an option raised the number)
+      } catch (const std::exception&) {}
+      turn %= std::min(in_use, lf_side_.size());
+      stream = lf_side_[turn]; busy = lf_side_done_[turn];
+    }
+    if (busy) (void)hipEventSynchronize((hipEvent_t)busy);
+    std::vector<std::shared_ptr<Job>> group;
+    {
+      std::lock_guard<std::mutex> lock(mu_);
+      if (shutdown_) return;
+      std::vector<std::shared_ptr<Job>> cand;
+      std::vector<LfGroupKey> keys;
+      for (int64_t t = next_lf_; (int)cand.size() < kLfGroupMax && ready(t); t++) {
+        cand.push_back(jobs_[t]);
+        Job& j = *cand.back();
+        // (a job whose prepare failed has nothing to launch; reconstruction and libjpeg-exact jobs keep a launch of their own)
+        keys.push_back(j.job_error.empty() && j.kind == kPlain ? slots_[(size_t)(j.ticket % nbuf_)]->batch->LfKey() : LfGroupKey());
+      }
+      const int m = PlanLfGroups(keys.data(), (int)keys.size(), lf_group_max_.load())[0];
+      group.assign(cand.begin(), cand.begin() + m);
+    }
+    IssueLfGroup(group, stream);
+    {
+      std::lock_guard<std::mutex> lock(mu_);
+      try {
+        if (!lf_side_done_[turn]) lf_side_done_[turn] = NewEvent();
+        Record(lf_side_done_[turn], stream);
+      } catch (const std::exception&) {}
+      int launched = 0;
+      for (auto& j : group) { j->state = kFrontIssued; launched += j->job_error.empty(); }
+      if (launched) { lf_groups_++; lf_grouped_jobs_ += launched; lf_group_largest_ = std::max<int64_t>(lf_group_largest_, launched); }
+      next_lf_ += (int64_t)group.size();
+    }
+    cv_.notify_all();
+    turn++;
+  }
+}
+
+void Pipeline::IssueLfGroup(const std::vector<std::shared_ptr<Job>>& group, void* stream) {
+  std::vector<Job*> live;
+  std::vector<Batch*> batches;
+  size_t done = 0;        // members whose front is in the stream
+  try {
+    for (auto& jp : group) {
+      Job* j = jp.get();
+      if (!j->job_error.empty()) continue;
+      Slot& s = *slots_[(size_t)(j->ticket % nbuf_)];
+      Batch& bt = *s.batch;
+      StreamWait(stream, s.uploaded);
+      // (jobs whose LF trees use the weighted predictor keep the SIMT kernel whatever lf_wide_once says — LaunchLfDecode —: 420 ms a launch, nothing to chain)
+      static const bool wide_wp = getenv("JXL_HIP_WIDE_WP") != nullptr;       // experiments (kernels.hip LfSimtShapeOf)
+      const bool lf_wide = bt.cfg.lf_wide_once && (wide_wp || !bt.Info("lf_simt_wp"));
+      bool chained = false;
+      {
+        std::lock_guard<std::mutex> lock(mu_);
+        if (j->wide_chain) j->lf_wide = lf_wide;
+        if (j->wide_after >= 0 && lf_wide) {
+          // behind the cold-start job before it, whose LF stage this thread has enqueued already: ours waits for it on the device
+          auto it = jobs_.find(j->wide_after);
+          chained = it != jobs_.end() && it->second->job_error.empty() && it->second->state < kHarvested && it->second->lf_wide;
+        }
+      }
+      if (chained) StreamWait(stream, slots_[(size_t)(j->wide_after % nbuf_)]->lf_done);
+      live.push_back(j); batches.push_back(&bt);
+    }
+    if (live.empty()) return;
+    const bool timed = opt_.timed != 0 && live[0]->kind != kJpegFiles;   // (a reconstruction job has no pixel stages to bracket: its parts are not timed; it is a group of its own)
+    Batch::RunLfGroup(batches.data(), (int)batches.size(), stream, timed, [&](int i) {
+      // LF decode + varblock placement are in the stream: all the HF stage waits for
+      Job* j = live[(size_t)i];
+      Slot& s = *slots_[(size_t)(j->ticket % nbuf_)];
+      Record(s.lf_done, stream);
+      // LF post-processing: needed by the float IDCT and the filters only — the libjpeg-exact tail and the reconstruction's gather read lfq, the coefficient planes, block info and offsets, the
+      // chroma-from-luma maps: nothing LfDequantKernel, LfSmoothKernel, LlfSigmaKernel or LlfKernel write (lf, lf_tmp, llf, inv_sigma)
+      s.batch->RunPart(stream, PartOf(kStageLfPost, j->kind != kPlain), timed);
+      Record(s.front_done, stream);
+      done = (size_t)i + 1;
+    });
+  } catch (const std::exception& e) {
+    // what is in the stream keeps those slots busy (Harvest drains the streams of a failed job); the members behind the failure fail with it
+    const std::string why = *e.what() ? e.what() : "LF stage failed";
+    std::lock_guard<std::mutex> lock(mu_);
+    for (auto& jp : group)
+      if (jp->job_error.empty() && std::find(live.begin(), live.begin() + (ptrdiff_t)done, jp.get()) == live.begin() + (ptrdiff_t)done) jp->job_error = why;
+  }
 }
 
 void Pipeline::IssueHf(Job* j) {
@@ -542,7 +653,10 @@ void Pipeline::Harvest(Job* j) {
   if (!j->job_error.empty() && !readback_ok) {
     // a job that failed half-way: whatever it enqueued must have left the GPU before the slot is reused
     (void)hipStreamSynchronize((hipStream_t)main_);
-    for (void* x : lf_side_) (void)hipStreamSynchronize((hipStream_t)x);
+    (void)hipStreamSynchronize((hipStream_t)upload_);
+    std::vector<void*> lf_now;
+    { std::lock_guard<std::mutex> lock(mu_); lf_now = lf_side_; }      // (the LF issuer adds streams under mu_ when an option raises their number)
+    for (void* x : lf_now) (void)hipStreamSynchronize((hipStream_t)x);
     for (void* x : hf_side_) (void)hipStreamSynchronize((hipStream_t)x);
     for (void* x : d2h_) (void)hipStreamSynchronize((hipStream_t)x);
   }
@@ -676,6 +790,7 @@ void Pipeline::ResetClock() {
   Record(clock_event_, main_);
   (void)hipStreamSynchronize((hipStream_t)main_);
   prepare_s_total_ = 0; prepared_jobs_ = 0;
+  lf_groups_ = lf_grouped_jobs_ = lf_group_largest_ = 0;
 }
 
 StageTimes Pipeline::CollectTimes(int* runs) {
@@ -703,6 +818,11 @@ int64_t Pipeline::Info(const char* name) {
   if (n == "shared_big_bytes") return (int64_t)big_.cap;
   if (n == "shared_coef_bytes") { int64_t v = 0; for (auto& c : coef_) v += (int64_t)c.cap; return v; }
   if (n == "private_plane_jobs") return private_plane_jobs_;
+  if (n == "lf_groups") return lf_groups_;
+  if (n == "lf_grouped_jobs") return lf_grouped_jobs_;
+  if (n == "lf_group_largest") return lf_group_largest_;
+  if (n == "lf_streams_effective") return LfStreamsInUse();
+  if (n == "lf_group_max") return lf_group_max_.load();
   if (n == "device_bytes") {
     int64_t v = (int64_t)big_.cap;
     for (auto& c : coef_) v += (int64_t)c.cap;

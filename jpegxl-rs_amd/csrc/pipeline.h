@@ -3,10 +3,13 @@
 // A decode is LF (entropy decode of the LF groups: a serial chain per stream, hundreds of milliseconds per launch whatever the batch size) ->
 // varblock placement + LF post-processing -> HF (entropy decode of the coefficients) -> IDCT -> filters + write.  Throughput comes from jobs in
 // flight: while the tail (IDCT, filters, write) of job k runs on the main stream, the HF stage of job k + 1 runs on a stream of its own against
-// the other coefficient set, the LF stages of the jobs behind it on side streams, and host worker threads parse, build tables for, upload and
-// enqueue the LF stage of the jobs after those.  The object owns what that takes: the ring of batch objects (their LF-stage outputs), the
-// coefficient sets and the pixel planes all jobs share, the HIP streams and events, the prepare threads and the thread that issues HF stages
-// and tails in submission order.  (Rounds 1-4 kept this schedule in bench.py; it is a property of the library now.)
+// the other coefficient set, the LF stages of the jobs behind it on side streams, and host worker threads parse, build tables for and upload
+// the jobs after those.  One thread enqueues the LF stages, in submission order, on as many LF streams as the hardware queues of the process
+// leave room for (streams that share a queue serialise); jobs that became ready while the next LF stream was busy go out as ONE launch of the
+// SIMT LF kernel, which is latency-bound and takes about as long for several jobs as for one.  The object owns what that takes: the ring of
+// batch objects (their LF-stage outputs), the coefficient sets and the pixel planes all jobs share, the HIP streams and events, the prepare
+// threads, the LF issuer and the thread that issues HF stages and tails in submission order.  (Rounds 1-4 kept this schedule in bench.py; it
+// is a property of the library now.)
 //
 // The reference decodes batches by looping decode_with over files (jpegxl-rs/benches/decode.rs:16-19): there is no counterpart of this object
 // in the reference API.  The libjxl-compatible JxlDecoder reaches it through DeviceScheduler (scheduler.cc): concurrent decode_with callers of
@@ -27,9 +30,12 @@ namespace jxlhip {
 
 struct PipelineOptions {
   int in_flight = 11;        // jobs in flight on the GPU (LF stages run this many jobs ahead of the tail, minus one)
-  int lf_streams = 11;       // side streams the LF stages are spread over (one per job in flight: weighted-predictor LF stages take ~590 ms per launch against steps of ~75 ms, seven streams bound such frames at 84 ms per step)
+  int lf_streams = 11;       // side streams the LF stages are spread over, at most (one per job in flight: weighted-predictor LF stages take ~590 ms per launch against steps of ~75 ms, seven streams bound such frames
+                             // at 84 ms per step).  Streams that share a hardware queue serialise, so only as many are used as the process has queues for: lf_streams_effective
+  int lf_streams_effective = 0;   // LF streams in use; 0: the rule of lf_group_plan.h LfStreamsForQueues over GPU_MAX_HW_QUEUES as the process has it (3 at 4 queues, 6 at 16)
+  int lf_group_max = 4;      // jobs whose SIMT LF kernels may go out as one launch when they are ready together (1: every job its own launch; at most kLfGroupMax)
   int hf_streams = 2;        // HF stages in flight beside the tail (one stream and one coefficient set each, + the set the tail consumes)
-  int prepare_threads = 3;   // host threads that each parse + prepare + upload one job at a time and enqueue its LF stage
+  int prepare_threads = 3;   // host threads that each parse + prepare + upload one job at a time
   int parse_threads = 8;     // host threads one job's images are parsed on
   int lane_stride_lf = 8, lane_stride_hf = 1;
   int wide_first = 4;        // LF stages at the start of a cold pipeline that take the one-wavefront-per-stream kernel (shorter latency on an idle GPU)
@@ -88,13 +94,15 @@ class Pipeline {
   void StageBytes(uint64_t out[6]);                // algorithmic bytes per stage of the job prepared last
   // libjpeg-exact jobs submitted from now on decode crops by region (Batch::jpeg_region): only the groups a crop needs; Info "hf_groups_total" / "hf_groups_decoded" of the job prepared last
   void SetJpegRegion(bool on) { jpeg_region_.store(on); }
-  int64_t Info(const char* name);                  // "device_bytes", "jobs", "shared_big_bytes", "shared_coef_bytes", "private_plane_jobs", "jpeg_pixel_images", "jpeg_pixel_launches" (of the job prepared or finished last), "jpeg_dc_only_images" (of the job finished last), "jpeg_device_images", "jpeg_host_images", "jpeg_device_progressive_images", "jpeg_gather_launches" (of the job finished last; 0 unless it was a reconstruction job), batch infos of the last job ("hf_nonzeros", "lf_simt_frames" ...)
+  // "lf_group_max" (1 .. kLfGroupMax), "lf_streams_effective" (0: the rule; at most options.lf_streams) for the LF stages issued from now on; "jpeg_region": SetJpegRegion.  false: no such option
+  bool SetOption(const std::string& name, int value);
+  int64_t Info(const char* name);                  // "lf_groups" / "lf_grouped_jobs" (LF launches and the jobs in them since the last ResetClock), "lf_group_largest", "lf_streams_effective", "device_bytes", "jobs", "shared_big_bytes", "shared_coef_bytes", "private_plane_jobs", "jpeg_pixel_images", "jpeg_pixel_launches" (of the job prepared or finished last), "jpeg_dc_only_images" (of the job finished last), "jpeg_device_images", "jpeg_host_images", "jpeg_device_progressive_images", "jpeg_gather_launches" (of the job finished last; 0 unless it was a reconstruction job), batch infos of the last job ("hf_nonzeros", "lf_simt_frames" ...)
   double prepare_seconds_total() const { return prepare_s_total_; }
   int64_t prepared_jobs() const { return prepared_jobs_; }
   int device() const { return device_; }
 
  private:
-  enum State { kQueued = 0, kPreparing, kFrontIssued, kTailIssued, kHarvested };
+  enum State { kQueued = 0, kPreparing, kPrepared, kFrontIssued, kTailIssued, kHarvested };      // kPrepared: parsed and uploading, waiting for the LF issuer
   // what a job's tail is: the float IDCT, filters and write; the integer IDCT over the HF planes + libjpeg's upsampling and colour conversion (libjpeg-exact pixels);
   // the gather into the JPEG writer's arena + its sizes pass, with the pack pass and the splice at harvest (reconstruction)
   enum Kind { kPlain = 0, kJpegPixels, kJpegFiles };
@@ -116,18 +124,22 @@ class Pipeline {
     State state = kQueued;
     bool hf_issued = false, waited = false, cold_wide = false;
     bool wide_chain = false;     // one of the chained cold-start jobs
-    bool lf_wide = false;        // ... whose LF stage really is the one-wavefront-per-stream launch (set before wide_enqueued_ reaches its ticket)
-    int64_t wide_after = -1;     // cold-start job (one-wavefront-per-stream LF kernel) behind another one: its LF stage waits for that job's (round 6: four at once took 95-120 ms each, one after the other 55)
+    bool lf_wide = false;        // ... whose LF stage really is the one-wavefront-per-stream launch (set by the LF issuer, which goes through the jobs in ticket order)
+    int64_t wide_after = -1;     // cold-start job (one-wavefront-per-stream LF kernel) behind another one: its LF stage waits for that job's, on the device (round 6: four at once took 95-120 ms each, one after the other 55)
     void* done_event = nullptr;                // (timing enabled) recorded behind the job's last copy
   };
   struct Slot {
     std::unique_ptr<Batch> batch;
+    void* uploaded = nullptr;                  // behind the job's tables and compressed bytes on the upload stream: what its LF stage waits for
     void *lf_done = nullptr, *front_done = nullptr, *hf_done = nullptr, *idct_done = nullptr, *rest_done = nullptr;
     void* finish_stream = nullptr;             // reconstruction jobs: the stream of FinishJpegWrite at harvest (nothing else queues on it; made when first needed)
     std::mutex mu;                             // harvest of the slot's current job
   };
   void PrepareWorker(int worker);
   void IssuerLoop();
+  void LfIssuerLoop();                         // the one thread that enqueues LF stages: in ticket order, jobs that are ready together as one group (Batch::RunLfGroup)
+  void IssueLfGroup(const std::vector<std::shared_ptr<Job>>& group, void* stream);
+  int LfStreamsInUse() const;
   void PrepareJob(Job* j, int worker);
   void IssueHf(Job* j);
   void IssueTail(Job* j);
@@ -141,25 +153,28 @@ class Pipeline {
 
   const int device_;
   PipelineOptions opt_;
-  int nbuf_ = 1, ncoef_ = 2;
+  int nbuf_ = 1, ncoef_ = 2, prio_high_ = 0;
   std::vector<std::unique_ptr<Slot>> slots_;
   SharedPlanes big_;
   std::vector<SharedPlanes> coef_;
   size_t want_big_ = 0, want_coef_ = 0;        // the largest layouts seen: what the shared planes grow to when the pipeline is idle
   void* main_ = nullptr; void* d2h_[2] = {nullptr, nullptr};     // [0]: copies to host + status words of every job, in job order ([1] spare: two streams taking turns measured slower)
-  std::vector<void*> lf_side_, hf_side_;
+  void* upload_ = nullptr;                     // tables and compressed bytes of every job (default priority: not one of the entropy streams' queues)
+  std::vector<void*> lf_side_, hf_side_;       // lf_side_: the streams in use (LfStreamsInUse), created when first needed
+  std::vector<void*> lf_side_done_;            // per LF stream: recorded behind the last group enqueued on it (nullptr: none yet) — the LF issuer waits for it before the next group
+  std::atomic<int> lf_group_max_{4}, lf_streams_effective_{0};
+  int64_t lf_groups_ = 0, lf_grouped_jobs_ = 0, lf_group_largest_ = 0;
   void* clock_event_ = nullptr;
   std::mutex mu_;
   std::condition_variable cv_;
   std::map<int64_t, std::shared_ptr<Job>> jobs_;   // submitted, not yet waited for (bounded: old harvested jobs nobody waits for are dropped)
   std::deque<std::shared_ptr<Job>> prep_queue_;
-  int64_t next_ticket_ = 0, next_issue_ = 0, completed_upto_ = 0;   // completed_upto_: every ticket below has state >= kHarvested or has been dropped
+  int64_t next_ticket_ = 0, next_lf_ = 0, next_issue_ = 0, completed_upto_ = 0;   // completed_upto_: every ticket below has state >= kHarvested or has been dropped
   int64_t cold_count_ = 0;
-  int64_t wide_enqueued_ = -1;    // ticket of the last chained cold-start job whose LF stage has been enqueued (or given up)
   int64_t private_plane_jobs_ = 0;
   bool shutdown_ = false;
   std::vector<std::thread> workers_;
-  std::thread issuer_;
+  std::thread issuer_, lf_issuer_;
   double prepare_s_total_ = 0; int64_t prepared_jobs_ = 0;
   uint64_t last_stage_bytes_[6] = {0, 0, 0, 0, 0, 0};
   std::atomic<bool> jpeg_region_{false};

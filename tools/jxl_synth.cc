@@ -140,7 +140,15 @@ static GTree MakeGlobalTree(int nlf, std::vector<int>* bfs_order) {
     // -> clamped gradient, the (strategy, quantiser) rows -> zero / W under splits on the row and on W, the sharpness map -> zero under N > 0, W > 0.
     static const int wcuts[] = {-500, -392, -255, -191, -127, -95, -63, -47, -31, -23, -15, -11, -7, -4, -3, -1, 0, 1, 3, 5, 7, 11, 15, 23, 31, 47, 63, 95, 127, 191, 255, 392, 500};
     std::vector<int> cut(wcuts, wcuts + sizeof(wcuts) / sizeof(wcuts[0]));
-    const int lf = BuildCutoffTree(t, 15, cut, 0, (int)cut.size(), 6);        // one subtree for the three channels (the real encoder does not split on the channel either)
+    int lf = -1;
+    if (LfTreeShape() == 3) {
+      // shape 3: the HF-metadata trees of this branch (tables over W and N) under the gradient trees of shape 0 for the LF coefficients — no weighted predictor anywhere
+      static const int gcuts[] = {-255, -127, -63, -31, -15, -7, -3, -1, 0, 1, 3, 7, 15, 31, 63, 127, 255};
+      std::vector<int> gcut(gcuts, gcuts + sizeof(gcuts) / sizeof(gcuts[0]));
+      const int ty = BuildCutoffTree(t, 9, gcut, 0, (int)gcut.size(), 5), tx = BuildCutoffTree(t, 9, gcut, 0, (int)gcut.size(), 5), tb = BuildCutoffTree(t, 9, gcut, 0, (int)gcut.size(), 5);
+      lf = t.add_inner(0, 0, t.add_inner(0, 1, tb, tx), ty);
+    } else
+    lf = BuildCutoffTree(t, 15, cut, 0, (int)cut.size(), 6);        // one subtree for the three channels (the real encoder does not split on the channel either)
     auto w_split3 = [&](int pred) {   // W > 5 ? (W > 11 ? a : b) : (W > 3 ? c : d)
       return t.add_inner(7, 5, t.add_inner(7, 11, t.add_leaf(pred), t.add_leaf(pred)), t.add_inner(7, 3, t.add_leaf(pred), t.add_leaf(pred)));
     };

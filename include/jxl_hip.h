@@ -713,6 +713,42 @@ size_t JxlHipArenaPoolHeld(void);
 void JxlHipSchedulerStats(int device, int64_t* jobs, int64_t* images);
 void JxlHipSchedulerShutdown(void);
 
+/* ---- extension: lossless batch encoder (csrc/encode_lossless.cc, csrc/encode_lossless.hip) -----------------------------------------
+ * Writes bare JPEG XL codestreams that decode to the input exactly: one prefix-coded Modular frame per image (group dimension 256, one pass, RCT type 6 over three colour
+ * channels, one fixed MA tree, codes built from the image's own histograms; no Squeeze, palette, LZ77 or ANS).  Tokens, bit counts and the bits themselves are computed on the
+ * GPU for all images of a call at once; the host writes headers, TOC and code tables.  libjxl's own encoder names stay error-returning stubs.
+ *
+ * One input: interleaved samples, `num_channels` 1 (grey), 2 (grey + alpha), 3 (RGB), 4 (RGBA); sRGB (grey: the sRGB transfer function), orientation 1;
+ * bits_per_sample 1..16; data_type JXL_TYPE_UINT8 (up to 8 bits) or JXL_TYPE_UINT16 (little endian, any depth); row_pitch in bytes, 0 = tight; pixels in host memory, or in
+ * device memory when on_device is set.
+ * Refused per image, with a message in the last-error text: a side of 0 or above 16384, channels outside 1..4, bits outside 1..16, a type that does not fit the depth, a
+ * pitch below one row, NULL pixels, a device pointer on a host-only encoder, a sample above 2^bits_per_sample - 1. */
+typedef struct JxlHipEncoderStruct JxlHipEncoder;
+typedef struct {
+  const void* pixels; JXL_BOOL on_device; uint32_t xsize, ysize, num_channels, bits_per_sample; JxlDataType data_type; size_t row_pitch; JXL_BOOL alpha_premultiplied;
+} JxlHipEncodeImage;
+/* device -1: a host-only encoder (needs no GPU) — bounds and refusals work, encoding does not. */
+JxlHipEncoder* JxlHipEncoderCreate(int device);
+void JxlHipEncoderDestroy(JxlHipEncoder* enc);
+/* Host only.  The worst-case size of the image's codestream (`pixels` is not looked at), derived from the stream shape:
+ *   48 (image + frame header) + 8192 (LfGlobal: tree, code tables, context map) + 2 + 6 * toc_entries + ceil(xsize * ysize * num_channels * (15 + extra) / 8)
+ * where toc_entries = 1 for an image of one 256 x 256 group, else 2 + ceil(xsize / 2048) * ceil(ysize / 2048) + ceil(xsize / 256) * ceil(ysize / 256); 15 is the
+ * longest prefix code; extra, the most extra bits of a token, is n - 2 for n = bits_per_sample + (1 if num_channels >= 3: the RCT), 0 if n < 4.
+ * Returns 0, or 1 for a description that would be refused. */
+int JxlHipEncodeLosslessBound(const JxlHipEncodeImage* image, size_t* bytes);
+/* Encodes `num_images` images in one set of launches on hip_stream (NULL: the default stream); the results are complete when it returns.  An image that is refused fails
+ * alone.  The bytes of an image do not depend on the other images of the call.  Returns 0 if every image was encoded, else 1 (the text names the first failure). */
+int JxlHipEncoderEncodeLossless(JxlHipEncoder* enc, const JxlHipEncodeImage* images, size_t num_images, void* hip_stream);
+/* Results of the last call: Status 0 = encoded, 1 = failed (with that image's message as the last-error text); Size 0 for a failed image; Copy returns 1 and writes nothing if
+ * `capacity` is below Size.  MaxToken: the largest hybrid-uint token of the image (71 is the largest there is). */
+int JxlHipEncoderStatus(JxlHipEncoder* enc, size_t index);
+size_t JxlHipEncoderSize(JxlHipEncoder* enc, size_t index);
+int JxlHipEncoderCopy(JxlHipEncoder* enc, size_t index, uint8_t* dst, size_t capacity);
+uint32_t JxlHipEncoderMaxToken(JxlHipEncoder* enc, size_t index);
+/* Wall-clock ms of the last call's phases: upload, tokenise + histogram readback, host code build, count + scans + size readback, pack, copy back, splice. */
+#define JXL_HIP_ENCODE_PHASES 7
+void JxlHipEncoderPhaseTimes(JxlHipEncoder* enc, float* ms);
+
 /* ---- extension: the gather of decoded pixels over RCCL / xGMI (csrc/gather.cc) --------------------------------------------------
  * The multi-GPU path shards independent frames over one process per GPU and has ONE exchange step: the decoded pixels go to the consumer rank.  These
  * calls put it behind the C ABI so that a caller needs no PyTorch: rank 0 makes an id, the job hands it to the other ranks (file, environment, MPI ...), every rank

@@ -127,6 +127,11 @@ _lib = None
 _threads = None
 
 
+class JxlHipEncodeImage(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("on_device", C.c_int), ("xsize", C.c_uint32), ("ysize", C.c_uint32), ("num_channels", C.c_uint32),
+                ("bits_per_sample", C.c_uint32), ("data_type", C.c_int), ("row_pitch", C.c_size_t), ("alpha_premultiplied", C.c_int)]
+
+
 class JxlBitDepth(C.Structure):
     """jpegxl-sys/src/common/types.rs:133-144"""
     _fields_ = [("type", C.c_int), ("bits_per_sample", C.c_uint32), ("exponent_bits_per_sample", C.c_uint32)]
@@ -257,6 +262,11 @@ def libjxl():
             "JxlHipGatherFramesRagged": (C.c_int, [vp, vp, sz, C.POINTER(C.c_int), vp, C.c_int, C.c_int, vp]),
             "JxlHipAllReduceSumI64": (C.c_int, [vp, vp, sz, vp]),
             "JxlHipSchedulerStats": (None, [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]), "JxlHipSchedulerShutdown": (None, []),
+            "JxlHipEncoderCreate": (vp, [C.c_int]), "JxlHipEncoderDestroy": (None, [vp]),
+            "JxlHipEncodeLosslessBound": (C.c_int, [C.POINTER(JxlHipEncodeImage), C.POINTER(sz)]),
+            "JxlHipEncoderEncodeLossless": (C.c_int, [vp, C.POINTER(JxlHipEncodeImage), sz, vp]),
+            "JxlHipEncoderStatus": (C.c_int, [vp, sz]), "JxlHipEncoderSize": (sz, [vp, sz]), "JxlHipEncoderCopy": (C.c_int, [vp, sz, vp, sz]),
+            "JxlHipEncoderMaxToken": (C.c_uint32, [vp, sz]), "JxlHipEncoderPhaseTimes": (None, [vp, C.POINTER(C.c_float * 7)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -1416,3 +1426,164 @@ class Pipeline:
         jobs that are ready together share one SIMT LF launch, at most this many; "lf_streams_effective": LF streams in use (0: sized to the hardware queues);
         info("lf_groups") / info("lf_grouped_jobs") / info("lf_group_largest") count the launches since the last reset_clock()."""
         libjxl().JxlHipPipelineSetOption(self._h, name.encode(), int(value))
+
+
+# ---- lossless encoder (include/jxl_hip.h JxlHipEncoder*; jpegxl-rs/src/encode.rs for the builder's names) ---------------------------------------
+class EncodeError(Exception):
+    """errors.rs EncodeError"""
+
+
+ENCODE_PHASES = ("upload", "tokenise", "code_build", "count_scan", "pack", "copy_back", "splice")
+
+
+def _rows_are_tight(shape, strides, item):
+    """whether the samples of a row follow one another (the stride of an axis of extent 1 means nothing) and the rows go forward"""
+    w, c = shape[1], shape[2] if len(shape) == 3 else 1
+    if len(shape) == 3 and c > 1 and strides[2] != item:
+        return False
+    return (w == 1 or strides[1] == c * item) and (shape[0] == 1 or strides[0] >= w * c * item)
+
+
+def _describe_input(img, bits, alpha_premultiplied, keep):
+    """-> JxlHipEncodeImage for a numpy array, a torch tensor or anything with __cuda_array_interface__ (H x W or H x W x C, uint8 / uint16); `keep` holds what must outlive the call"""
+    cai = None
+    if type(img).__module__.split(".")[0] == "torch":
+        import torch
+        if img.is_cuda:                         # (read directly: torch's own __cuda_array_interface__ does not cover every integer type)
+            torch.cuda.synchronize(img.device)
+            item = img.element_size()
+            cai = {"shape": tuple(img.shape), "typestr": {torch.uint8: "|u1", getattr(torch, "uint16", None): "<u2"}.get(img.dtype, str(img.dtype)),
+                   "strides": tuple(s * item for s in img.stride()), "data": (img.data_ptr(), False)}
+        else:
+            img = img.numpy()
+    if cai is None:
+        cai = getattr(img, "__cuda_array_interface__", None)
+    if cai is not None:
+        shape, typestr, strides, ptr, on_device = tuple(cai["shape"]), cai["typestr"], cai.get("strides"), int(cai["data"][0]), 1
+    else:
+        img = np.asarray(img)
+        if img.ndim in (2, 3) and not _rows_are_tight(img.shape, img.strides, img.itemsize):
+            img = np.ascontiguousarray(img)
+        shape, typestr, strides, ptr, on_device = img.shape, img.dtype.str, img.strides, img.ctypes.data, 0
+    keep.append(img)
+    if typestr not in ("|u1", "<u2"):
+        raise EncodeError("unsupported: samples of type %s (uint8 and little-endian uint16 are encoded)" % typestr)
+    item = 1 if typestr == "|u1" else 2
+    if len(shape) not in (2, 3):
+        raise EncodeError("unsupported: an image of %d dimensions (H x W or H x W x C)" % len(shape))
+    h, w, c = shape[0], shape[1], shape[2] if len(shape) == 3 else 1
+    pitch = 0
+    if strides is not None:
+        if not _rows_are_tight(shape, strides, item):
+            raise EncodeError("unsupported: samples that are not interleaved and contiguous within a row")
+        pitch = int(strides[0]) if h > 1 else 0
+    return JxlHipEncodeImage(ptr, on_device, w, h, c, int(bits) if bits is not None else 8 * item, JXL_TYPE_UINT8 if item == 1 else JXL_TYPE_UINT16, pitch, 1 if alpha_premultiplied else 0)
+
+
+def encode_lossless_bound(width, height, num_channels, bits=8, dtype="uint8") -> int:
+    """JxlHipEncodeLosslessBound: the worst-case codestream size; needs no GPU."""
+    im = JxlHipEncodeImage(None, 0, width, height, num_channels, bits, JXL_TYPE_UINT8 if np.dtype(dtype) == np.uint8 else JXL_TYPE_UINT16, 0, 0)
+    n = C.c_size_t()
+    if libjxl().JxlHipEncodeLosslessBound(C.byref(im), C.byref(n)):
+        raise EncodeError(last_error())
+    return n.value
+
+
+class LosslessEncoder:
+    """One JxlHipEncoder: encode(images) runs the whole list through one set of kernel launches.  device=-1: host only (refusals and bounds)."""
+
+    def __init__(self, device: int = 0):
+        self._h = libjxl().JxlHipEncoderCreate(device)
+        if not self._h:
+            raise EncodeError(last_error())
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            libjxl().JxlHipEncoderDestroy(self._h)
+            self._h = None
+
+    def encode(self, images, bits=None, alpha_premultiplied=False, stream=None, raise_on_error=True):
+        """-> list of codestreams (bytes); with raise_on_error=False a failed image gives its EncodeError in the list instead"""
+        L, keep = libjxl(), []
+        per_bits, _ = _per_image(bits, len(images), lambda v: False)
+        arr = (JxlHipEncodeImage * max(1, len(images)))(*[_describe_input(im, b, alpha_premultiplied, keep) for im, b in zip(images, per_bits)])
+        L.JxlHipEncoderEncodeLossless(self._h, arr, len(images), stream)
+        out = []
+        for i in range(len(images)):
+            if L.JxlHipEncoderStatus(self._h, i):
+                err = EncodeError(last_error())
+                if raise_on_error:
+                    raise err
+                out.append(err)
+                continue
+            buf = C.create_string_buffer(L.JxlHipEncoderSize(self._h, i))
+            if L.JxlHipEncoderCopy(self._h, i, buf, len(buf)):
+                raise EncodeError(last_error())
+            out.append(buf.raw)
+        return out
+
+    def max_token(self, i) -> int:
+        return int(libjxl().JxlHipEncoderMaxToken(self._h, i))
+
+    def phase_times(self) -> dict:
+        ms = (C.c_float * 7)()
+        libjxl().JxlHipEncoderPhaseTimes(self._h, C.byref(ms))
+        return dict(zip(ENCODE_PHASES, [float(v) for v in ms]))
+
+
+def encode_lossless(images, bits=None, device=0) -> list:
+    """Lossless JPEG XL codestreams of `images` (numpy H x W / H x W x C uint8 / uint16 arrays, torch tensors or anything with __cuda_array_interface__; 1 to 4 channels:
+    grey, grey + alpha, RGB, RGBA), all through one set of GPU launches.  bits: the depth (1..16), one value or one per image; default 8 / 16 by type."""
+    return LosslessEncoder(device).encode(images, bits=bits)
+
+
+@dataclass
+class EncoderResult:
+    """encode.rs:42 EncoderResult"""
+    data: bytes
+
+
+class JxlEncoder:
+    """encode.rs JxlEncoder, the lossless case: encoder_builder(lossless=True, has_alpha=...).encode(data, width, height)."""
+
+    def __init__(self, has_alpha=False, lossless=None, device=0, **other):
+        refused = {"speed", "quality", "jpeg_quality", "use_container", "uses_original_profile", "decoding_speed", "init_buffer_size", "color_encoding", "target_intensity",
+                   "parallel_runner", "use_box", "memory_manager"}
+        for k in other:
+            if k not in refused:
+                raise TypeError(f"unknown encoder option {k}")
+            raise EncodeError(f"unsupported: encoder option {k} (the encoder writes lossless bare codestreams only)")
+        if not lossless:
+            raise EncodeError("unsupported: lossy encoding (build the encoder with lossless=True)")
+        self.has_alpha, self.lossless, self._device = bool(has_alpha), True, device
+
+    def encode(self, data, width, height, bits=None) -> EncoderResult:
+        a = np.asarray(data)
+        if a.dtype not in (np.uint8, np.uint16):
+            raise EncodeError("unsupported: samples of type %s (uint8 and uint16 are encoded)" % a.dtype)
+        if width <= 0 or height <= 0 or a.size % (width * height) or not 1 <= a.size // (width * height) <= 4:
+            raise EncodeError("the data does not hold width x height pixels of 1 to 4 channels")
+        c = a.size // (width * height)
+        if (c in (2, 4)) != self.has_alpha:
+            raise EncodeError("%d channels %s has_alpha" % (c, "need" if c in (2, 4) else "contradict"))
+        return EncoderResult(LosslessEncoder(self._device).encode([a.reshape(height, width, c)], bits=bits)[0])
+
+    def encode_jpeg(self, data):
+        raise EncodeError("unsupported: encode_jpeg (JPEG transcoding is not written)")
+
+    def encode_frame(self, frame, width, height):
+        raise EncodeError("unsupported: encode_frame (one frame of interleaved samples through encode())")
+
+    def multiple(self, width, height):
+        raise EncodeError("unsupported: multiple frames (animation is not written)")
+
+    def add_metadata(self, metadata, compress=False):
+        raise EncodeError("unsupported: metadata boxes (the encoder writes bare codestreams)")
+
+    def set_frame_option(self, option, value):
+        raise EncodeError("unsupported: frame options (one fixed lossless stream shape)")
+
+
+def encoder_builder(**options) -> JxlEncoder:
+    """encode.rs:523 encoder_builder(): options are keyword arguments; everything but lossless=True and has_alpha raises EncodeError("unsupported: ...")"""
+    return JxlEncoder(**options)
